@@ -2,15 +2,21 @@
 argmax) on 252 hypotheses x 160x160 crops of ONE object - BASELINE.json's metric on configs[1] (one GPU) /
 configs[2] (the same object, its hypotheses sharded over N GPUs).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]        (N > 1 without a rendezvous in the environment: starts its own N ranks)
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]      (N > 1 without a rendezvous in the environment: starts its own N ranks)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...       (the driver's form; WORLD_SIZE must equal N)
+
+A plain run sets up ONE object, runs W warm-up steps, times exactly K steps and prints the headline (`value`, `ms_per_step`) with the
+roofline figure of the dominant kernel class, which comes from HIP events in the same timed region.  --dump-outputs DIR writes what the
+last timed step returned (argmax.npy, poses.npy; the inputs are seeded, identical from run to run).  Everything else takes runs of its
+own and comes with --full only: per-class kernel times, the step timed with the events off, per-rank phases, the extra keys below and the
+CPU baseline (--no-extras / --no-cpu-baseline leave parts of it out).
 
 One "step" = one register-core pass: est_refine_iter=5 x (crop window, render,
 observed crop, RefineNet, pose update) + 1 x (crop window, render, observed crop, ScoreNet features)
 + cross-hypothesis tail + argmax, with the RGB-D frame, mesh, weights and hypotheses already resident
 in HBM.  With N GPUs the 252 hypotheses are cut into N contiguous shards, ONE RCCL all-gather of
 [feature|pose] rows (532 KB) precedes the cross-hypothesis tail, which every rank runs (strong scaling:
-the work is fixed, `value` = 252 x K / max-over-ranks time).  Extra keys of the JSON line: the weak-scaling
+the work is fixed, `value` = 252 x K / max-over-ranks time).  Extra keys of the JSON line (--full): the weak-scaling
 figure (N objects x 252, fixed work per GPU), configs[3] (4 objects x 252 on the N ranks), per-rank phase
 times (local / all-gather / tail) and, on one GPU, configs[4] tracking rates.  Rank 0 prints ONE JSON line.
 """
@@ -152,6 +158,15 @@ def timed_steps(fn, n_steps, barrier, device, world):
   if world > 1:
     dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
   return float(tmax.item()), out
+
+
+def dump_outputs(out_dir, res):
+  """--dump-outputs: what the caller of step() received from the last timed step, for the one object of the headline, as
+  out_dir/argmax.npy ((1,) float64: the winning hypothesis) and out_dir/poses.npy ((252, 4, 4) float32: the refined poses)."""
+  os.makedirs(out_dir, exist_ok=True)
+  am, poses = res[0]
+  np.save(os.path.join(out_dir, 'argmax.npy'), am.cpu().numpy().astype(np.float64).reshape(-1))
+  np.save(os.path.join(out_dir, 'poses.npy'), poses.cpu().numpy().astype(np.float32))
 
 
 def tracking_fps(est, device, n_frames):
@@ -330,12 +345,17 @@ def main(argv=None):
   ap.add_argument('--gpus', type=int, default=1)
   ap.add_argument('--steps', type=int, default=10)
   ap.add_argument('--warmup', type=int, default=2)
-  ap.add_argument('--no-cpu-baseline', action='store_true')
-  ap.add_argument('--no-extras', action='store_true', help='headline only: skip the weak-scaling / configs[3] / tracking figures')
+  ap.add_argument('--full', action='store_true', help='also every figure beyond the headline: per-class kernel times, the events-off and '
+                  'per-phase timings, the weak-scaling / configs[3] / tracking figures and the CPU baseline (runs of their own)')
+  ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+  ap.add_argument('--no-extras', action='store_true', help='with --full: skip the weak-scaling / configs[3] / tracking figures')
+  ap.add_argument('--dump-outputs', metavar='DIR', help='write what the last timed step returned to DIR/<name>.npy')
   ap.add_argument('--launch-check', action='store_true', help='rendezvous only: start the ranks, all-gather the rank ids, print them')
   args = ap.parse_args(argv)
   if args.gpus < 1:
     raise SystemExit('--gpus must be >= 1')
+  if args.steps < 1 or args.warmup < 0:
+    raise SystemExit('--steps must be >= 1 and --warmup >= 0')
   # FP_BENCH_REHEARSAL=1: every rank on cuda:0 with the gloo backend - rehearses the multi-process flow (rendezvous, barriers,
   # the all-gather, finalisation) on a one-GPU box; the numbers it prints mean nothing
   rehearsal = os.environ.get('FP_BENCH_REHEARSAL') == '1'
@@ -375,7 +395,7 @@ def main(argv=None):
   if args.launch_check:
     return launch_check(world, rank, device, backend)
 
-  n_obj = max(world, 1 if args.no_extras else 4)
+  n_obj = max(world, 1 if args.no_extras else 4) if args.full else 1
   est, objects = build_job(device, n_objects=n_obj, rank=rank)
   ctx = est.refiner.ctx
   ctx.reserve(max(N_HYP, 4 * math.ceil(N_HYP / world)))
@@ -397,71 +417,74 @@ def main(argv=None):
   dt, res = timed_steps(single, args.steps, barrier, device, world)       # launch stream: the roofline figure comes from the timed region
   ctx.prof_enable(False)
   conv = ctx.prof_read('conv3x3_halo')
-  # every kernel class: a separate, untimed pass of the same steps (events around all ~160 launches of a step cost 2 % of it)
-  ctx.prof_reset()
-  ctx.prof_enable(2)
-  timed_steps(single, args.steps, barrier, device, world)
-  ctx.prof_enable(False)
-  classes = {}
-  for c in ('conv3x3_halo', 'conv3x3_s2', 'conv7x7', 'linear', 'attention', 'heads_wall', 'render', 'crop'):
-    r = ctx.prof_read(c)
-    if r['launches']:
-      # ms_per_step: sum of the launch spans; busy_ms_per_step: time with at least one launch of the class executing (smaller where
-      # launches of the class overlap on two streams: the two half-batch trunks, the two RefineNet heads); tflops = FLOPs / busy time
-      classes[c] = {'ms_per_step': r['total_ms'] / args.steps, 'busy_ms_per_step': r['busy_ms'] / args.steps,
-                    'launches_per_step': r['launches'] / args.steps,
-                    'tflops': (r['flops'] / (r['busy_ms'] * 1e-3) / 1e12) if r['flops'] and r['busy_ms'] > 0 and c not in ('render', 'crop') else None}
-      if c in ('render', 'crop'):          # these two report BYTES WRITTEN as their work figure
-        classes[c]['bytes_written_per_step'] = r['flops'] / args.steps
-  # the same K steps with the per-launch events off (how much the events cost), and where a step's time goes on this rank
-  dt_noprof, _ = timed_steps(single, args.steps, barrier, device, world)
-  marks = []
-  t_start = _mark()
-  starts = [t_start]
-  for _ in range(min(args.steps, 5)):
-    step(est, objects[:1], world, rank, replicate_tail=True, marks=marks)
-    starts.append(marks[-1])
-  torch.cuda.synchronize()
-  n_m = len(marks) // 3
-  phases = {'local_ms': sum(starts[i].elapsed_time(marks[3 * i]) for i in range(n_m)) / n_m,
-            'allgather_ms': sum(marks[3 * i].elapsed_time(marks[3 * i + 1]) for i in range(n_m)) / n_m,
-            'tail_ms': sum(marks[3 * i + 1].elapsed_time(marks[3 * i + 2]) for i in range(n_m)) / n_m}
-  ph = torch.tensor([phases['local_ms'], phases['allgather_ms'], phases['tail_ms']], device=device, dtype=torch.float64)
-  ph_all = [torch.zeros_like(ph) for _ in range(world)]
-  if world > 1:
-    dist.all_gather(ph_all, ph)
-  else:
-    ph_all = [ph]
-
+  if args.dump_outputs and rank == 0:
+    dump_outputs(args.dump_outputs, res)
   extras = {}
-  if not args.no_extras:
-    if world > 1:                # N objects x 252 on N ranks: fixed 252 hypotheses per GPU (weak scaling)
-      weak = lambda: step(est, objects[:world], world, rank)
+  if args.full:
+    # every kernel class: a separate, untimed pass of the same steps (events around all ~160 launches of a step cost 2 % of it)
+    ctx.prof_reset()
+    ctx.prof_enable(2)
+    timed_steps(single, args.steps, barrier, device, world)
+    ctx.prof_enable(False)
+    classes = {}
+    for c in ('conv3x3_halo', 'conv3x3_s2', 'conv7x7', 'linear', 'attention', 'heads_wall', 'render', 'crop'):
+      r = ctx.prof_read(c)
+      if r['launches']:
+        # ms_per_step: sum of the launch spans; busy_ms_per_step: time with at least one launch of the class executing (smaller where
+        # launches of the class overlap on two streams: the two half-batch trunks, the two RefineNet heads); tflops = FLOPs / busy time
+        classes[c] = {'ms_per_step': r['total_ms'] / args.steps, 'busy_ms_per_step': r['busy_ms'] / args.steps,
+                      'launches_per_step': r['launches'] / args.steps,
+                      'tflops': (r['flops'] / (r['busy_ms'] * 1e-3) / 1e12) if r['flops'] and r['busy_ms'] > 0 and c not in ('render', 'crop') else None}
+        if c in ('render', 'crop'):          # these two report BYTES WRITTEN as their work figure
+          classes[c]['bytes_written_per_step'] = r['flops'] / args.steps
+    # the same K steps with the per-launch events off (how much the events cost), and where a step's time goes on this rank
+    dt_noprof, _ = timed_steps(single, args.steps, barrier, device, world)
+    marks = []
+    t_start = _mark()
+    starts = [t_start]
+    for _ in range(min(args.steps, 5)):
+      step(est, objects[:1], world, rank, replicate_tail=True, marks=marks)
+      starts.append(marks[-1])
+    torch.cuda.synchronize()
+    n_m = len(marks) // 3
+    phases = {'local_ms': sum(starts[i].elapsed_time(marks[3 * i]) for i in range(n_m)) / n_m,
+              'allgather_ms': sum(marks[3 * i].elapsed_time(marks[3 * i + 1]) for i in range(n_m)) / n_m,
+              'tail_ms': sum(marks[3 * i + 1].elapsed_time(marks[3 * i + 2]) for i in range(n_m)) / n_m}
+    ph = torch.tensor([phases['local_ms'], phases['allgather_ms'], phases['tail_ms']], device=device, dtype=torch.float64)
+    ph_all = [torch.zeros_like(ph) for _ in range(world)]
+    if world > 1:
+      dist.all_gather(ph_all, ph)
+    else:
+      ph_all = [ph]
+
+    if not args.no_extras:
+      if world > 1:                # N objects x 252 on N ranks: fixed 252 hypotheses per GPU (weak scaling)
+        weak = lambda: step(est, objects[:world], world, rank)
+        for _ in range(args.warmup):
+          weak()
+        dtw, _ = timed_steps(weak, args.steps, barrier, device, world)
+        extras['weak_n_objects'] = {'objects': world, 'value': N_HYP * world * args.steps / dtw, 'unit': 'pose-hypotheses/sec',
+                                    'ms_per_step': dtw / args.steps * 1e3, 'scaling': 'weak'}
+      # the headline workload with the observed side of iteration 1 cropped and encoded per hypothesis, as the reference's loop does (identical poses)
+      global SHARED_HINT
+      SHARED_HINT = False
       for _ in range(args.warmup):
-        weak()
-      dtw, _ = timed_steps(weak, args.steps, barrier, device, world)
-      extras['weak_n_objects'] = {'objects': world, 'value': N_HYP * world * args.steps / dtw, 'unit': 'pose-hypotheses/sec',
-                                  'ms_per_step': dtw / args.steps * 1e3, 'scaling': 'weak'}
-    # the headline workload with the observed side of iteration 1 cropped and encoded per hypothesis, as the reference's loop does (identical poses)
-    global SHARED_HINT
-    SHARED_HINT = False
-    for _ in range(args.warmup):
-      single()
-    dtp, _ = timed_steps(single, args.steps, barrier, device, world)
-    SHARED_HINT = True
-    extras['per_hypothesis_observed_side'] = {'value': N_HYP * args.steps / dtp, 'unit': 'pose-hypotheses/sec', 'ms_per_step': dtp / args.steps * 1e3,
-                                              'note': 'configs[1] / configs[2] without FP_REFINE_SHARED_TRANSLATION: iteration 1 crops and encodes the observed side once per hypothesis'}
-    c3 = lambda: step(est, objects[:4], world, rank)       # configs[3]: 4 concurrent objects x 252 = 1008 hypotheses, per-object argmax
-    for _ in range(args.warmup):
-      c3()
-    dt3, _ = timed_steps(c3, args.steps, barrier, device, world)
-    extras['configs3_4x252'] = {'objects': 4, 'value': 4 * N_HYP * args.steps / dt3, 'unit': 'pose-hypotheses/sec',
-                                'ms_per_step': dt3 / args.steps * 1e3}
-    if world == 1:
-      extras['shard_local_ms'] = shard_local_ms(est, objects, device)
-      extras['shard_local_ms_note'] = ('local ms per step of the largest shard of a 2 / 4 / 8-GPU configs[2] job (126 / 63 / 32 hypotheses of the one object: '
-                                       'refine x5 + score features), measured on this one GPU; the all-gather and the replicated tail come on top')
-      extras['tracking_configs4'] = tracking_fps(est, device, n_frames=1000)
+        single()
+      dtp, _ = timed_steps(single, args.steps, barrier, device, world)
+      SHARED_HINT = True
+      extras['per_hypothesis_observed_side'] = {'value': N_HYP * args.steps / dtp, 'unit': 'pose-hypotheses/sec', 'ms_per_step': dtp / args.steps * 1e3,
+                                                'note': 'configs[1] / configs[2] without FP_REFINE_SHARED_TRANSLATION: iteration 1 crops and encodes the observed side once per hypothesis'}
+      c3 = lambda: step(est, objects[:4], world, rank)       # configs[3]: 4 concurrent objects x 252 = 1008 hypotheses, per-object argmax
+      for _ in range(args.warmup):
+        c3()
+      dt3, _ = timed_steps(c3, args.steps, barrier, device, world)
+      extras['configs3_4x252'] = {'objects': 4, 'value': 4 * N_HYP * args.steps / dt3, 'unit': 'pose-hypotheses/sec',
+                                  'ms_per_step': dt3 / args.steps * 1e3}
+      if world == 1:
+        extras['shard_local_ms'] = shard_local_ms(est, objects, device)
+        extras['shard_local_ms_note'] = ('local ms per step of the largest shard of a 2 / 4 / 8-GPU configs[2] job (126 / 63 / 32 hypotheses of the one object: '
+                                         'refine x5 + score features), measured on this one GPU; the all-gather and the replicated tail come on top')
+        extras['tracking_configs4'] = tracking_fps(est, device, n_frames=1000)
 
   if rank == 0:
     total_hyp = N_HYP * args.steps
@@ -499,8 +522,6 @@ def main(argv=None):
                    'traffic': (traffic or {}).get('total') if world == 1 else None,
                    'traffic_source': 'committed rocprofv3 PMC passes over this command at N=1 (see traffic_detail.source), not this run',
                    'traffic_detail': traffic if world == 1 else None},
-      'ms_per_step_events_off': dt_noprof / args.steps * 1e3,
-      'phases_ms_per_rank': [dict(zip(('local', 'allgather', 'tail'), [float(x) for x in p.tolist()])) for p in ph_all],
     }
     # SURVEY 8(d) / BASELINE.md section 4: the step as a fraction of the MFMA roofline, and the render + crop stage against the HBM roofline
     step_flops = 141.7e9 * N_HYP                  # (5 x 23.95 + 21.94) GFLOP per hypothesis - the reference's work
@@ -513,25 +534,28 @@ def main(argv=None):
     out['roofline']['step_frac_reference_flops'] = step_flops / (dt / args.steps) / 1e12 / PEAK_F16_TFLOPS
     out['roofline']['step_note'] = ('step_frac = EXECUTED TFLOP per step / time / peak; step_frac_reference_flops counts the reference\'s 141.7 GFLOP per hypothesis '
                                     '(SURVEY 8(d)), of which the shared observed side of iteration 1 is computed once per object here')
-    rc = [classes[c] for c in ('render', 'crop') if c in classes]
-    if len(rc) == 2:
-      b = sum(c['bytes_written_per_step'] for c in rc)
-      t = sum(c['busy_ms_per_step'] for c in rc) * 1e-3
-      out['hbm_stage'] = {'bound': 'hbm', 'kernels': 'classify_faces_kernel + render_kernel (side A) and crop_observed_kernel (side B): the fp16 network tensor of every pass',
-                          'bytes_written_per_step': b, 'busy_ms_per_step': t * 1e3, 'achieved': b / t / 1e9 if t > 0 else None, 'peak': 8000.0, 'unit': 'GB/s',
-                          'frac': (b / t / 1e9 / 8000.0) if t > 0 else None,
-                          'note': 'algorithmic bytes (SURVEY 8(d): 2 x 160 x 160 x 16 B per hypothesis and pass) over the busy time of the two classes; the rasteriser is '
-                                  'bound by lane utilisation in its classification and triangle passes, not by these writes (DESIGN.md section 5)'}
-    out['kernel_classes'] = classes       # HIP-event time per kernel class, from an untimed pass of the same K steps
-    out['kernel_classes_note'] = ('ms_per_step = sum of the launch spans, busy_ms_per_step = time with at least one launch of the class executing. The classes '
-                                  'OVERLAP: the trunk runs as two half batches on two streams (two launches of a convolution class in flight: spans sum to about '
-                                  'twice the busy time) and RefineNet runs its two transformer heads on two streams (linear / attention likewise); kernels of '
-                                  'different classes overlap too (the tail of one half batch beside the other half, a head beside the other head): the busy times '
-                                  'of all classes sum to 1 - 2 % more than the step. heads_wall = first in-projection .. join of the heads on the main stream '
-                                  '(their wall-clock share, one span per network pass)')
-    out.update(extras)
-    if not args.no_cpu_baseline and world == 1:        # timed on rank 0 of the single-GPU run only
-      out['cpu_baseline'] = cpu_baseline()
+    if args.full:
+      out['ms_per_step_events_off'] = dt_noprof / args.steps * 1e3
+      out['phases_ms_per_rank'] = [dict(zip(('local', 'allgather', 'tail'), [float(x) for x in p.tolist()])) for p in ph_all]
+      rc = [classes[c] for c in ('render', 'crop') if c in classes]
+      if len(rc) == 2:
+        b = sum(c['bytes_written_per_step'] for c in rc)
+        t = sum(c['busy_ms_per_step'] for c in rc) * 1e-3
+        out['hbm_stage'] = {'bound': 'hbm', 'kernels': 'classify_faces_kernel + render_kernel (side A) and crop_observed_kernel (side B): the fp16 network tensor of every pass',
+                            'bytes_written_per_step': b, 'busy_ms_per_step': t * 1e3, 'achieved': b / t / 1e9 if t > 0 else None, 'peak': 8000.0, 'unit': 'GB/s',
+                            'frac': (b / t / 1e9 / 8000.0) if t > 0 else None,
+                            'note': 'algorithmic bytes (SURVEY 8(d): 2 x 160 x 160 x 16 B per hypothesis and pass) over the busy time of the two classes; the rasteriser is '
+                                    'bound by lane utilisation in its classification and triangle passes, not by these writes (DESIGN.md section 5)'}
+      out['kernel_classes'] = classes       # HIP-event time per kernel class, from an untimed pass of the same K steps
+      out['kernel_classes_note'] = ('ms_per_step = sum of the launch spans, busy_ms_per_step = time with at least one launch of the class executing. The classes '
+                                    'OVERLAP: the trunk runs as two half batches on two streams (two launches of a convolution class in flight: spans sum to about '
+                                    'twice the busy time) and RefineNet runs its two transformer heads on two streams (linear / attention likewise); kernels of '
+                                    'different classes overlap too (the tail of one half batch beside the other half, a head beside the other head): the busy times '
+                                    'of all classes sum to 1 - 2 % more than the step. heads_wall = first in-projection .. join of the heads on the main stream '
+                                    '(their wall-clock share, one span per network pass)')
+      out.update(extras)
+      if not args.no_cpu_baseline and world == 1:        # timed on rank 0 of the single-GPU run only
+        out['cpu_baseline'] = cpu_baseline()
     print(json.dumps(out))
   if world > 1:
     dist.barrier()

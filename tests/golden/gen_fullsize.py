@@ -15,7 +15,8 @@ tests/cases.py, shared with the tests.
                                                 # top-1 / top-2 logit margin over all cases; prints the ranking
   python tests/golden/gen_fullsize.py write     # fixture with synthetic.py's current default tail seed
   python tests/golden/gen_fullsize.py d16       # adds <case>/poses_iter_d16 (the refine chain with the HIP kernels' rounding points, oracle/nets.py refine_forward_d16)
-  python tests/golden/gen_fullsize.py ac16      # adds <case>/poses_iter_ac16 (the refine chain with the network under CPU autocast fp16) to the fixture
+  python tests/golden/gen_fullsize.py ac16      # adds <case>/poses_iter_ac16 (the refine chain with the network under CPU autocast fp16)
+                                                # (both to tests/golden/fullsize_chains.npz)
 
 The chosen tail seed is the default of foundationpose_amd.synthetic.make_score_state_dict; fullsize.npz records, per case,
 the oracle's margin and logit spread, and the tests assert margin >= 20 x the fp16 logit noise they measure.
@@ -182,10 +183,7 @@ def stage_write():
   ms = [margin_stats(l) for l in lgs]
   out['trk/multi_margin'] = np.array([m for m, _ in ms])
   print('tracking margins / spread:', [f'{m / s:.2f}' for m, s in ms], 'argmax', lgs.argmax(1))
-  path = os.path.join(HERE, 'fullsize.npz')
-  if os.path.exists(path):                       # (the autocast chains of stage 'ac16' do not depend on the tail seed: kept)
-    old = np.load(path)
-    out.update({k: old[k] for k in old.files if (k.endswith('_ac16') or k.endswith('_d16')) and k not in out})
+  path = os.path.join(HERE, 'fullsize.npz')      # (the chains of stages 'ac16' / 'd16' do not depend on the tail seed: fullsize_chains.npz is kept)
   np.savez_compressed(path, **out)
   print('wrote', path, f'{os.path.getsize(path) / 1e6:.2f} MB')
 
@@ -207,15 +205,17 @@ def stage_ac16():
 
 def _stage_chain(tag, kw):
   """The oracle's refine loop with the network in another precision through the same five full-gain iterations, for configs[1] and the three
-  other objects of configs[3]; added to the existing fixture as `<case>/poses_iter_<tag>` (the other keys are left as they are).
+  other objects of configs[3]; written to tests/golden/fullsize_chains.npz as `<case>/poses_iter_<tag>` (the other keys are left as they are;
+  apart from fullsize.npz so that each file stays under 1 MiB).
   ac16: the reference's OWN precision - torch.autocast('cpu', float16), what predict_pose_refine.py:190 runs on the GPU; the full-gain chain
   test measures the HIP path's scatter against THIS chain's scatter around the fp32 chain.  d16: see stage_d16.  ~7 min per case on 8 cores."""
   from foundationpose_amd import synthetic as S
   from oracle import predict as OP
   from tests import cases
   torch.set_num_threads(int(os.environ.get('FP_GEN_THREADS', os.cpu_count())))
-  path = os.path.join(HERE, 'fullsize.npz')
-  out = dict(np.load(path))
+  base = np.load(os.path.join(HERE, 'fullsize.npz'))
+  path = os.path.join(HERE, 'fullsize_chains.npz')
+  out = dict(np.load(path)) if os.path.exists(path) else {}
   for name in AC16_CASES:
     c = cases.case(name)
     sc = c['sc']
@@ -227,7 +227,7 @@ def _stage_chain(tag, kw):
                               iteration=c['iteration'], chunk=16, trace=trace, **kw)
     per_iter = np.stack([t['poseA'].numpy() for t in trace[1:]] + [poses.numpy()]).astype(np.float32)
     out[f'{name}/poses_iter_{tag}'] = per_iter
-    d = np.abs(per_iter - out[f'{name}/poses_iter']).reshape(per_iter.shape[0], per_iter.shape[1], -1).max(2)
+    d = np.abs(per_iter - base[f'{name}/poses_iter']).reshape(per_iter.shape[0], per_iter.shape[1], -1).max(2)
     print(f'{name}: {tag} chain in {time.time() - t0:.0f} s; |chain - fp32| per iteration: median ' + ' '.join(f'{np.median(x):.1e}' for x in d) +
           ' max ' + ' '.join(f'{x.max():.1e}' for x in d), flush=True)
   np.savez_compressed(path, **out)

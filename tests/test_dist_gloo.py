@@ -184,9 +184,9 @@ def _run_bench(args, env_extra=None, timeout=180):
 def test_bench_launches_its_own_ranks():
   """`python bench.py --gpus 2` without a rendezvous in the environment must start 2 ranks itself (a child torch.distributed.run,
   never an exec) and relay rank 0's JSON line; --launch-check stops after the rendezvous + one all-gather of the rank ids, which
-  on this GPU-less container runs over gloo."""
+  runs over gloo when the ranks see no GPU.  They are shown none, so that the check runs the same on a node with one GPU."""
   import json
-  r = _run_bench(['--gpus', '2', '--launch-check'])
+  r = _run_bench(['--gpus', '2', '--launch-check'], {'HIP_VISIBLE_DEVICES': '-1', 'CUDA_VISIBLE_DEVICES': '-1'})
   assert r.returncode == 0, r.stderr[-2000:]
   line = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])
   assert line['n_gpus'] == 2 and line['rccl_ranks'] == 2 and line['ranks'] == [0, 1]

@@ -24,7 +24,13 @@ OWN_MARGIN_FRACTION = 0.5          # end to end (GPU-refined poses, up to ~3e-4 
 
 @pytest.fixture(scope='module')
 def full():
-  return np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'fullsize.npz'))
+  """fullsize.npz and fullsize_chains.npz (the `*_ac16` / `*_d16` chains, kept apart to hold each file under 1 MiB) as one mapping."""
+  golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
+  out = {}
+  for f in ('fullsize.npz', 'fullsize_chains.npz'):
+    with np.load(os.path.join(golden, f)) as z:
+      out.update({k: z[k] for k in z.files})
+  return out
 
 
 @pytest.fixture(scope='module')
