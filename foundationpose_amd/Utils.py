@@ -388,3 +388,70 @@ def cluster_poses(angle_diff, dist_diff, poses_in, symmetry_tfs):
     check(n)
   logging.info(f'num of pose after clustering: {n}')
   return [out[i] for i in range(n)]
+
+
+# ---------------------------------------------------------------------------------------------- evaluation against ground truth
+_POSE_METRICS = {'add': _lib.FP_ERR_ADD, 'adds': _lib.FP_ERR_ADDS, 'add_sym': _lib.FP_ERR_ADD_SYM}
+
+
+def pose_errors(poses, gt, model_pts, symmetry_tfs=None, metrics=('add', 'adds')):
+  """ADD / ADD-S / symmetric ADD of a batch of poses on the device (fp_pose_errors; src/Utils.py:232-253).
+
+  poses (B,4,4) object-to-camera; gt (4,4) shared by every pose or (B,4,4), one per pose (a tracked sequence against its
+  ground truth in one call); model_pts (N,3); symmetry_tfs (K,4,4) in the frame of model_pts (None: the identity only).  numpy or
+  torch inputs.  Returns {metric: (B,) float32 device tensor} for each name of `metrics`, in metres:
+    'add'     mean_i |pred p_i - gt p_i|
+    'adds'    mean_i min_j |gt p_i - pred p_j|   (each ground-truth point queries the predicted points, as adds_err does)
+    'add_sym' min_k mean_i |pred p_i - gt S_k p_i|
+  ADD-S is an exact brute force over all N x N point pairs.  The results are written on the current stream; nothing synchronises."""
+  unknown = [m for m in metrics if m not in _POSE_METRICS]
+  if unknown:
+    raise ValueError(f'unknown metric(s) {unknown}: choose from {sorted(_POSE_METRICS)}')
+  which = 0
+  for m in metrics:
+    which |= _POSE_METRICS[m]
+  dev = poses.device if torch.is_tensor(poses) and poses.is_cuda else torch.device('cuda', torch.cuda.current_device())
+  f32 = lambda x: torch.as_tensor(x).to(device=dev, dtype=torch.float).contiguous()
+  P, G, pts = f32(poses).reshape(-1, 4, 4), f32(gt), f32(model_pts).reshape(-1, 3)
+  B = len(P)
+  if G.shape == (4, 4):
+    gt_per_pose = 0
+  elif G.shape == (B, 4, 4):
+    gt_per_pose = 1
+  else:
+    raise ValueError(f'gt must be (4,4) or ({B},4,4), got {tuple(G.shape)}')
+  sym = None
+  if 'add_sym' in metrics:
+    sym = f32(np.eye(4)[None] if symmetry_tfs is None else symmetry_tfs).reshape(-1, 4, 4)
+  out = {m: torch.empty(B, dtype=torch.float, device=dev) for m in metrics}
+  ctx = _lib.Context.get(dev)
+  check(lib().fp_pose_errors(ctx.handle, ptr(pts), len(pts), ptr(P), ptr(G), gt_per_pose, B, ptr(sym), 0 if sym is None else len(sym), which,
+                             ptr(out.get('add')), ptr(out.get('adds')), ptr(out.get('add_sym')), stream_ptr(dev)))
+  return out
+
+
+def add_err(pred, gt, model_pts, symetry_tfs=np.eye(4)[None]):
+  """src/Utils.py:232-240: mean_i |pred p_i - gt p_i| as a Python float.  Like the reference, `symetry_tfs` is accepted and
+  IGNORED; the symmetric form is pose_errors(..., symmetry_tfs=..., metrics=('add_sym',))."""
+  return float(pose_errors(torch.as_tensor(pred).reshape(1, 4, 4), gt, model_pts, metrics=('add',))['add'][0])
+
+
+def adds_err(pred, gt, model_pts):
+  """src/Utils.py:242-253: mean over the ground-truth points of the distance to the nearest predicted point, as a Python float
+  (exact brute force on the device instead of the reference's cKDTree)."""
+  return float(pose_errors(torch.as_tensor(pred).reshape(1, 4, 4), gt, model_pts, metrics=('adds',))['adds'][0])
+
+
+def compute_auc_sklearn(errs, max_val=0.1, step=0.001):
+  """src/Utils.py:255-267 on the host: the fraction of errors <= x on the grid 0, step, .., max_val (the curve stays at 1 from the
+  first x where every error is covered, as the reference's early `break` leaves it), integrated by the trapezoid rule - what
+  sklearn.metrics.auc computes for an increasing x - over max_val."""
+  errs = np.sort(np.array(errs))
+  X = np.arange(0, max_val + step, step)
+  Y = np.ones(len(X))
+  for i, x in enumerate(X):
+    y = (errs <= x).sum() / len(errs)
+    Y[i] = y
+    if y >= 1:
+      break
+  return float((np.diff(X) * (Y[1:] + Y[:-1]) / 2.0).sum() / (max_val * 1))

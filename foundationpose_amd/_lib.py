@@ -17,6 +17,8 @@ _lib = None
 
 FP_REFINE_SHARED_TRANSLATION = 1      # include/foundationpose_amd.h
 FP_NET_REFINE, FP_NET_SCORE = 0, 1
+FP_EINVAL = -1
+FP_ERR_ADD, FP_ERR_ADDS, FP_ERR_ADD_SYM = 1, 2, 4      # fp_pose_errors' `which` bits
 
 
 class FpTensor(Structure):
@@ -74,6 +76,7 @@ _PROTOS = {
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
   'fp_depth2xyzmap_f64': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
   'fp_mask_depth_stats': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
+  'fp_pose_errors': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
   'fp_net_create': (c_int, [c_void_p, c_int, POINTER(FpTensor), c_int, c_int, POINTER(c_void_p)]),
   'fp_net_destroy': (c_int, [c_void_p]),
   'fp_net_rot_dim': (c_int, [c_void_p]),

@@ -489,7 +489,30 @@ extern "C" int fp_mask_depth_stats(fp_ctx *ctx, const float *d_depth, const uint
   return FP_OK;
 }
 
-extern "C" int fp_pose_update(fp_ctx *ctx, const float *d_poseA, const float *d_trans, const float *d_rot, int N, int rot_dim,
+extern "C" int fp_pose_errors(fp_ctx *ctx, const float *d_pts, int n_pts, const float *d_pred, const float *d_gt, int gt_per_pose, int n_poses,
+                              const float *d_sym, int n_sym, int which, float *d_add, float *d_adds, float *d_add_sym, void *stream) {
+  FP_REQUIRE(ctx && d_pts && d_pred && d_gt, "fp_pose_errors: null argument");
+  FP_REQUIRE(n_pts >= 1 && n_poses >= 1, "fp_pose_errors: n_pts %d, n_poses %d (both must be >= 1)", n_pts, n_poses);
+  FP_REQUIRE((which & ~(FP_ERR_ADD | FP_ERR_ADDS | FP_ERR_ADD_SYM)) == 0, "fp_pose_errors: unknown bits in which = %d", which);
+  FP_REQUIRE(gt_per_pose == 0 || gt_per_pose == 1, "fp_pose_errors: gt_per_pose must be 0 or 1");
+  FP_REQUIRE(!(which & FP_ERR_ADD) || d_add, "fp_pose_errors: FP_ERR_ADD requested with d_add null");
+  FP_REQUIRE(!(which & FP_ERR_ADDS) || d_adds, "fp_pose_errors: FP_ERR_ADDS requested with d_adds null");
+  FP_REQUIRE(!(which & FP_ERR_ADD_SYM) || (d_add_sym && d_sym && n_sym >= 1),
+             "fp_pose_errors: FP_ERR_ADD_SYM needs d_add_sym, d_sym and n_sym >= 1 (n_sym %d)", n_sym);
+  if (which == 0) return FP_OK;
+  const size_t bytes = pose_errors_slab_bytes(n_pts, n_poses, (which & FP_ERR_ADD_SYM) ? n_sym : 0);
+  FP_TRY(fp_arena_ensure(ctx, bytes + 4096));
+  const size_t mark = ctx->arena.off;
+  double *slab = (double *)ctx->arena.take(bytes);
+  FP_REQUIRE(slab, "fp_pose_errors: arena exhausted");
+  // the slab is consumed by the finishing launch on the same stream before anything else takes it
+  const int rc = launch_pose_errors(d_pts, n_pts, d_pred, d_gt, gt_per_pose, n_poses, d_sym, n_sym, which, slab, d_add, d_adds, d_add_sym,
+                                    (hipStream_t)stream);
+  ctx->arena.off = mark;
+  return rc;
+}
+
+extern "C" int fp_pose_update(fp_ctx *ctx,const float *d_poseA, const float *d_trans, const float *d_rot, int N, int rot_dim,
                               int trans_rep_tanh, const float *tn, float rot_normalizer, float trans_scale, float *d_pose_out,
                               void *stream) {
   FP_REQUIRE(ctx && d_poseA && d_trans && d_rot && d_pose_out, "fp_pose_update: null argument");

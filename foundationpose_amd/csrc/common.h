@@ -439,3 +439,7 @@ int launch_depth_prefilter(const float *d, int H, int W, float diff_thres, float
                            float sigmaR, const double *K, float zfar_x, float *out, float *xyz, const unsigned char *rgb_u8, float *rgb_f, hipStream_t s);
 int launch_depth2xyz_f64(const float *d, int H, int W, const double *K, float *xyz, hipStream_t s);
 int launch_mask_depth_stats(const float *d, const unsigned char *mask, int H, int W, float min_depth, int *out6, float *median, hipStream_t s);
+// metrics.hip: ADD / ADD-S / ADDsym of n_poses poses (fp_pose_errors); `slab` holds pose_errors_slab_bytes(...) bytes of partial sums
+size_t pose_errors_slab_bytes(int n_pts, int n_poses, int n_sym);
+int launch_pose_errors(const float *pts, int n_pts, const float *pred, const float *gt, int gt_per_pose, int n_poses, const float *sym,
+                       int n_sym, int which, double *slab, float *add, float *adds, float *add_sym, hipStream_t s);

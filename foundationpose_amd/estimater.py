@@ -145,7 +145,15 @@ class FoundationPose:
     return hyp
 
   def compute_add_err_to_gt_pose(self, poses):
-    return -torch.ones(len(poses), device='cuda', dtype=torch.float)
+    """src/estimater.py:243-247 (a stub there: -1 per pose, still the result while `self.gt_pose` is None).  poses (B,4,4) of the
+    CENTRED mesh (as self.poses holds them); self.gt_pose is the pose of the ORIGINAL mesh (what register() returns and a dataset
+    gives).  Returns ADD over self.symmetry_tfs (the least over the transforms; plain ADD for the default identity) on the centred
+    vertices against gt_pose @ inv(get_tf_to_centered_mesh()), as a (B,) float32 device tensor."""
+    if self.gt_pose is None:
+      return -torch.ones(len(poses), device='cuda', dtype=torch.float)
+    tf = self.get_tf_to_centered_mesh().double()
+    gt_c = torch.as_tensor(self.gt_pose, device=tf.device).double() @ torch.linalg.inv(tf)
+    return U.pose_errors(poses, gt_c, self.mesh.vertices, symmetry_tfs=self.symmetry_tfs, metrics=('add_sym',))['add_sym']
 
   # ------------------------------------------------------------------ hot path
   def _refine_and_score(self, K, rgb, depth, xyz_map, hyp, iteration):

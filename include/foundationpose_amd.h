@@ -137,6 +137,24 @@ int fp_depth2xyzmap_f64(fp_ctx *ctx, const float *d_depth, int H, int W, const d
 int fp_mask_depth_stats(fp_ctx *ctx, const float *d_depth, const uint8_t *d_mask, int H, int W, float min_depth, int32_t *h_stats6,
                         float *h_median, void *stream);
 
+/* ---- evaluation against ground truth ----------------------------------------------------------- */
+#define FP_ERR_ADD 1
+#define FP_ERR_ADDS 2
+#define FP_ERR_ADD_SYM 4
+/* Pose errors of n_poses poses against ground truth: add_err / adds_err (src/Utils.py:232-253), in one launch plus a small one that
+ * adds the partial sums.  d_pts (n_pts,3) model points; d_pred (n_poses,4,4); d_gt (4,4) shared by every pose (gt_per_pose = 0) or
+ * (n_poses,4,4) (gt_per_pose = 1); d_sym (n_sym,4,4) symmetry transforms in the frame of d_pts.  Only rows 0..2 of a matrix are read.
+ * `which` ORs FP_ERR_*; each requested output (n_poses float32, device) receives, with p the model points and T p = R p + t:
+ *   FP_ERR_ADD      d_add[b]     = mean_i |pred_b p_i - gt_b p_i|
+ *   FP_ERR_ADDS     d_adds[b]    = mean_i min_j |gt_b p_i - pred_b p_j|     (each ground-truth point queries the predicted points)
+ *   FP_ERR_ADD_SYM  d_add_sym[b] = min_k mean_i |pred_b p_i - gt_b S_k p_i|  (= ADD for the single transform S_0 = I)
+ * ADD-S is exact brute force over all n_pts x n_pts pairs.  A pose's results are bit-identical whatever the batch it is in and its
+ * index there (no float atomics).  Workspace comes from the context's arena; nothing synchronises.  FP_EINVAL: n_pts or n_poses < 1,
+ * a null input, a requested output that is null, FP_ERR_ADD_SYM with n_sym < 1 or d_sym null, gt_per_pose not 0 / 1, unknown bits
+ * in `which`.  which = 0 launches nothing. */
+int fp_pose_errors(fp_ctx *ctx, const float *d_pts, int n_pts, const float *d_pred, const float *d_gt, int gt_per_pose, int n_poses,
+                   const float *d_sym, int n_sym, int which, float *d_add, float *d_adds, float *d_add_sym, void *stream);
+
 /* ---- networks -------------------------------------------------------------------------------- */
 typedef struct {
   const char *name;    /* reference state_dict key, e.g. "encodeA.0.net.0.weight" */
