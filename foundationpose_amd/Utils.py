@@ -455,3 +455,165 @@ def compute_auc_sklearn(errs, max_val=0.1, step=0.001):
     if y >= 1:
       break
   return float((np.diff(X) * (Y[1:] + Y[:-1]) / 2.0).sum() / (max_val * 1))
+
+
+# ---------------------------------------------------------------------------------------------- BOP errors and average recall
+BOP19_VSD_TAUS = np.arange(0.05, 0.51, 0.05)               # misfit tolerances of VSD, as fractions of the object diameter
+BOP19_VSD_DELTA = 0.015                                     # VSD visibility tolerance: BOP's 15 mm, in metres
+BOP19_VSD_THETAS = np.arange(0.05, 0.51, 0.05)              # correctness thresholds of e_VSD
+BOP19_MSSD_THETAS = np.arange(0.05, 0.51, 0.05)             # x the object diameter
+BOP19_MSPD_THETAS = np.arange(5, 51, 5)                     # pixels, x image_width / 640
+_BOP_METRICS = {'mssd': _lib.FP_BOP_MSSD, 'mspd': _lib.FP_BOP_MSPD}
+
+
+def _pose_batch(poses, gt, dev):
+  f32 = lambda x: torch.as_tensor(x).to(device=dev, dtype=torch.float).contiguous()
+  P, G = f32(poses).reshape(-1, 4, 4), f32(gt)
+  B = len(P)
+  if G.shape == (4, 4):
+    return P, G, 0
+  if G.shape == (B, 4, 4):
+    return P, G, 1
+  raise ValueError(f'gt must be (4,4) or ({B},4,4), got {tuple(G.shape)}')
+
+
+def _device_of(x):
+  return x.device if torch.is_tensor(x) and x.is_cuda else torch.device('cuda', torch.cuda.current_device())
+
+
+def bop_pose_errors(poses, gt, model_pts, K=None, symmetry_tfs=None, metrics=('mssd', 'mspd')):
+  """MSSD / MSPD of a batch of poses on the device (fp_pose_errors_bop; bop_toolkit pose_error.mssd / mspd).
+
+  poses (B,4,4) object-to-camera; gt (4,4) shared by every pose or (B,4,4), one per pose; model_pts (N,3); K (3,3) intrinsics, needed
+  for 'mspd'; symmetry_tfs (S,4,4) in the frame of model_pts, e.g. symmetry_tfs_from_info(models_info[obj_id]) (None: the identity
+  only).  numpy or torch inputs.  Returns {metric: (B,) float32 device tensor}:
+    'mssd'  min_k max_i |pred p_i - gt S_k p_i|                    metres
+    'mspd'  min_k max_i |pi(pred p_i) - pi(gt S_k p_i)|            pixels; +inf when a point lies at z <= 0 under either pose
+  The results are written on the current stream; nothing synchronises."""
+  unknown = [m for m in metrics if m not in _BOP_METRICS]
+  if unknown:
+    raise ValueError(f'unknown metric(s) {unknown}: choose from {sorted(_BOP_METRICS)}')
+  if 'mspd' in metrics and K is None:
+    raise ValueError("'mspd' needs the intrinsics K")
+  which = 0
+  for m in metrics:
+    which |= _BOP_METRICS[m]
+  dev = _device_of(poses)
+  P, G, gt_per_pose = _pose_batch(poses, gt, dev)
+  pts = torch.as_tensor(model_pts).to(device=dev, dtype=torch.float).reshape(-1, 3).contiguous()
+  sym = None if symmetry_tfs is None else torch.as_tensor(symmetry_tfs).to(device=dev, dtype=torch.float).reshape(-1, 4, 4).contiguous()
+  Kd, Kp = k_ptr(K) if K is not None else (None, None)
+  B = len(P)
+  out = {m: torch.empty(B, dtype=torch.float, device=dev) for m in metrics}
+  ctx = _lib.Context.get(dev)
+  check(lib().fp_pose_errors_bop(ctx.handle, ptr(pts), len(pts), ptr(P), ptr(G), gt_per_pose, B, ptr(sym), 0 if sym is None else len(sym),
+                                 Kp, which, ptr(out.get('mssd')), ptr(out.get('mspd')), stream_ptr(dev)))
+  return out
+
+
+def vsd_errors(poses, gt, depth_test, K, mesh=None, mesh_tensors=None, glctx=None, diameter=None, delta=BOP19_VSD_DELTA,
+               taus=BOP19_VSD_TAUS, return_counts=False):
+  """Visible surface discrepancy of a batch of poses on the device (fp_vsd; bop_toolkit pose_error.vsd with visib_mode='bop19' and
+  normalized_by_diameter=True), defined on this library's depth renders (nvdiffrast_render).
+
+  poses (B,4,4); gt (4,4) shared by every pose (rendered once) or (B,4,4); depth_test (H,W) in metres, 0 = missing, shared by every
+  pose, or (B,H,W), one frame per pose (a tracked sequence in one call); K (3,3).  The mesh is given as for nvdiffrast_render, in the
+  frame the poses refer to (for the poses of register() / track_one(), the original mesh).  diameter=None: compute_mesh_diameter of
+  its vertices.  Returns e (B, len(taus)) float32 on the device, and with return_counts=True also (B, 2 + len(taus)) int32 counts:
+  |union|, |inter| and the cost of every tau.  Nothing synchronises."""
+  if mesh_tensors is None:
+    if mesh is None:
+      raise ValueError('vsd_errors needs mesh or mesh_tensors')
+    mesh_tensors = make_mesh_tensors(mesh)
+  if diameter is None:
+    verts = np.asarray(mesh.vertices) if mesh is not None else mesh_tensors['pos'].detach().cpu().numpy()
+    diameter = compute_mesh_diameter(model_pts=verts, n_sample=10000)
+  ctx = _ctx_of(glctx, _device_of(poses))
+  dev = torch.device('cuda', ctx.device_index)
+  P, G, gt_per_pose = _pose_batch(poses, gt, dev)
+  B = len(P)
+  D = torch.as_tensor(depth_test).to(device=dev, dtype=torch.float).contiguous()
+  if D.dim() == 2:
+    depth_per_pose = 0
+  elif D.dim() == 3 and len(D) == B:
+    depth_per_pose = 1
+  else:
+    raise ValueError(f'depth_test must be (H,W) or ({B},H,W), got {tuple(D.shape)}')
+  H, W = D.shape[-2:]
+  t = np.ascontiguousarray(np.asarray(taus, dtype=np.float64).reshape(-1))
+  Kd, Kp = k_ptr(K)
+  err = torch.empty((B, len(t)), dtype=torch.float, device=dev)
+  counts = torch.empty((B, 2 + len(t)), dtype=torch.int32, device=dev) if return_counts else None
+  dm = _lib.device_mesh(ctx, mesh_tensors)
+  check(lib().fp_vsd(ctx.handle, dm.handle, ptr(D), depth_per_pose, int(H), int(W), Kp, ptr(P), ptr(G), gt_per_pose, B, float(diameter),
+                     float(delta), ptr(t), len(t), ptr(err), ptr(counts), stream_ptr(dev)))
+  return (err, counts) if return_counts else err
+
+
+def _host(x):
+  return None if x is None else np.asarray(x.detach().cpu().numpy() if torch.is_tensor(x) else x, dtype=np.float64)
+
+
+def bop_average_recall(e_vsd=None, e_mssd=None, e_mspd=None, diameter=None, image_width=640, n_targets=None):
+  """BOP 2019 average recall on the host (bop_toolkit eval_bop19: the recall of every threshold, averaged).
+
+  e_vsd (n, T) VSD errors of n estimates at T taus; e_mssd (n,) metres; e_mspd (n,) pixels - one estimate per target.  diameter: a
+  scalar or one value per estimate (needed for MSSD).  n_targets: the number of targets, estimated or not (default n); the targets
+  without an estimate count as misses.  An estimate is correct when e < theta:
+    AR_VSD   the mean over every (tau, theta) pair, theta in BOP19_VSD_THETAS
+    AR_MSSD  the mean over theta in BOP19_MSSD_THETAS * diameter
+    AR_MSPD  the mean over theta in BOP19_MSPD_THETAS * image_width / 640
+  Returns a dict with the AR_* of the errors given, and AR, the mean of the three, when all three are given."""
+  e_vsd, e_mssd, e_mspd = _host(e_vsd), _host(e_mssd), _host(e_mspd)
+  n = next((len(e) for e in (e_vsd, e_mssd, e_mspd) if e is not None), None)
+  if n is None:
+    raise ValueError('bop_average_recall needs at least one of e_vsd, e_mssd, e_mspd')
+  for e in (e_vsd, e_mssd, e_mspd):
+    if e is not None and len(e) != n:
+      raise ValueError('the error arrays must hold one entry per estimate each')
+  n_targets = n if n_targets is None else int(n_targets)
+  if n_targets < n or n_targets < 1:
+    raise ValueError(f'n_targets {n_targets} must be >= the number of estimates {n} and >= 1')
+  recall = lambda e, th: float((e < th).sum()) / n_targets
+  out = {}
+  if e_vsd is not None:
+    e_vsd = e_vsd.reshape(n, -1)
+    out['AR_VSD'] = float(np.mean([recall(e_vsd[:, t], th) for t in range(e_vsd.shape[1]) for th in BOP19_VSD_THETAS]))
+  if e_mssd is not None:
+    if diameter is None:
+      raise ValueError('AR_MSSD needs the object diameter')
+    d = np.broadcast_to(np.asarray(diameter, dtype=np.float64), (n,))
+    out['AR_MSSD'] = float(np.mean([recall(e_mssd, th * d) for th in BOP19_MSSD_THETAS]))
+  if e_mspd is not None:
+    r = image_width / 640.0
+    out['AR_MSPD'] = float(np.mean([recall(e_mspd, th * r) for th in BOP19_MSPD_THETAS]))
+  if len(out) == 3:
+    out['AR'] = (out['AR_VSD'] + out['AR_MSSD'] + out['AR_MSPD']) / 3.0
+  return out
+
+
+def symmetry_tfs_from_info(info, rot_angle_discrete=5):
+  """The symmetry transforms of a BOP models_info entry as (S,4,4) float64, with the signature and results of the reference's helper
+  (src/Utils.py:806-835), quirks included:
+    - the identity comes first, then every 'symmetries_discrete' matrix with its translation scaled from mm to m (x 0.001);
+    - of 'symmetries_continuous' only the first entry is read: its axis is the first of x, y, z with a positive component, and the
+      rotations about it by 0, rot_angle_discrete, .. degrees (below 360) follow, each with the entry's 'offset' as its translation,
+      NOT scaled - so the identity appears twice for an offset of 0, and an axis about z gives 1 + 360 / rot_angle_discrete transforms;
+    - an axis with no positive component gives the single rotation by 0 degrees with that offset.
+  The rotations are euler_matrix(angle about x, about y, about z)."""
+  tfs = [np.eye(4)]
+  if 'symmetries_discrete' in info:
+    for T in np.array(info['symmetries_discrete'], dtype=np.float64).reshape(-1, 4, 4):
+      T[:3, 3] = T[:3, 3] * 0.001
+      tfs.append(T)
+  if 'symmetries_continuous' in info:
+    cont = info['symmetries_continuous'][0]
+    positive = np.flatnonzero(np.asarray(cont['axis'], dtype=np.float64).reshape(3) > 0)
+    degrees = np.arange(0, 360, rot_angle_discrete) if len(positive) else np.zeros(1)
+    for deg in degrees:
+      euler = [0.0, 0.0, 0.0]
+      euler[positive[0] if len(positive) else 0] = deg / 180.0 * np.pi
+      T = euler_matrix(*euler)
+      T[:3, 3] = cont['offset']
+      tfs.append(T)
+  return np.stack(tfs)

@@ -19,6 +19,8 @@ FP_REFINE_SHARED_TRANSLATION = 1      # include/foundationpose_amd.h
 FP_NET_REFINE, FP_NET_SCORE = 0, 1
 FP_EINVAL = -1
 FP_ERR_ADD, FP_ERR_ADDS, FP_ERR_ADD_SYM = 1, 2, 4      # fp_pose_errors' `which` bits
+FP_BOP_MSSD, FP_BOP_MSPD = 1, 2                       # fp_pose_errors_bop's `which` bits
+FP_VSD_MAX_TAUS = 32
 
 
 class FpTensor(Structure):
@@ -77,6 +79,9 @@ _PROTOS = {
   'fp_depth2xyzmap_f64': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
   'fp_mask_depth_stats': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
   'fp_pose_errors': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+  'fp_pose_errors_bop': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+  'fp_vsd': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_double, c_void_p, c_int,
+                     c_void_p, c_void_p, c_void_p]),
   'fp_net_create': (c_int, [c_void_p, c_int, POINTER(FpTensor), c_int, c_int, POINTER(c_void_p)]),
   'fp_net_destroy': (c_int, [c_void_p]),
   'fp_net_rot_dim': (c_int, [c_void_p]),

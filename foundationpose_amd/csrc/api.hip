@@ -512,6 +512,84 @@ extern "C" int fp_pose_errors(fp_ctx *ctx, const float *d_pts, int n_pts, const 
   return rc;
 }
 
+extern "C" int fp_pose_errors_bop(fp_ctx *ctx, const float *d_pts, int n_pts, const float *d_pred, const float *d_gt, int gt_per_pose,
+                                  int n_poses, const float *d_sym, int n_sym, const double *K, int which, float *d_mssd, float *d_mspd,
+                                  void *stream) {
+  FP_REQUIRE(ctx && d_pts && d_pred && d_gt, "fp_pose_errors_bop: null argument");
+  FP_REQUIRE(n_pts >= 1 && n_poses >= 0 && n_sym >= 0, "fp_pose_errors_bop: n_pts %d (>= 1), n_poses %d, n_sym %d (>= 0)", n_pts, n_poses, n_sym);
+  FP_REQUIRE(n_sym == 0 || d_sym, "fp_pose_errors_bop: n_sym %d with d_sym null", n_sym);
+  FP_REQUIRE(gt_per_pose == 0 || gt_per_pose == 1, "fp_pose_errors_bop: gt_per_pose must be 0 or 1");
+  FP_REQUIRE((which & ~(FP_BOP_MSSD | FP_BOP_MSPD)) == 0, "fp_pose_errors_bop: unknown bits in which = %d", which);
+  FP_REQUIRE(!(which & FP_BOP_MSSD) || d_mssd, "fp_pose_errors_bop: FP_BOP_MSSD requested with d_mssd null");
+  FP_REQUIRE(!(which & FP_BOP_MSPD) || (d_mspd && K), "fp_pose_errors_bop: FP_BOP_MSPD needs d_mspd and K");
+  if (which == 0 || n_poses == 0) return FP_OK;
+  const size_t bytes = bop_errors_slab_bytes(n_pts, n_poses, n_sym);
+  FP_TRY(fp_arena_ensure(ctx, bytes + 4096));
+  const size_t mark = ctx->arena.off;
+  float *slab = (float *)ctx->arena.take(bytes);
+  FP_REQUIRE(slab, "fp_pose_errors_bop: arena exhausted");
+  // the slab is consumed by the finishing launch on the same stream before anything else takes it
+  const int rc = launch_bop_errors(d_pts, n_pts, d_pred, d_gt, gt_per_pose, n_poses, d_sym, n_sym, K, which, slab, d_mssd, d_mspd,
+                                   (hipStream_t)stream);
+  ctx->arena.off = mark;
+  return rc;
+}
+
+// poses per render chunk of fp_vsd: their depth images (and those of their ground truth, one per pose) within this many bytes
+static const size_t kVsdDepthBudget = (size_t)512 << 20;
+
+extern "C" int fp_vsd(fp_ctx *ctx, const fp_mesh *mesh, const float *d_depth_test, int depth_per_pose, int H, int W, const double *K,
+                      const float *d_pred, const float *d_gt, int gt_per_pose, int n_poses, double diameter, double delta,
+                      const double *h_taus, int n_taus, float *d_err, int32_t *d_counts, void *stream) {
+  FP_REQUIRE(ctx && mesh && d_depth_test && K && d_pred && d_gt && h_taus && d_err, "fp_vsd: null argument");
+  FP_REQUIRE(n_taus >= 1 && n_taus <= FP_VSD_MAX_TAUS, "fp_vsd: n_taus %d outside 1..%d", n_taus, FP_VSD_MAX_TAUS);
+  FP_REQUIRE(H >= 1 && W >= 1 && (size_t)H * W <= ((size_t)1 << 30), "fp_vsd: image %dx%d", H, W);
+  FP_REQUIRE(diameter > 0, "fp_vsd: diameter %g must be > 0", diameter);
+  FP_REQUIRE((depth_per_pose == 0 || depth_per_pose == 1) && (gt_per_pose == 0 || gt_per_pose == 1),
+             "fp_vsd: depth_per_pose and gt_per_pose must be 0 or 1");
+  FP_REQUIRE(n_poses >= 0, "fp_vsd: n_poses %d", n_poses);
+  if (n_poses == 0) return FP_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const size_t px = (size_t)H * W;
+  const size_t per_pose = px * sizeof(float) * (gt_per_pose ? 2 : 1);
+  const int chunk = (int)std::min<size_t>({(size_t)n_poses, std::max<size_t>(1, kVsdDepthBudget / per_pose), 65535});
+  const int last = n_poses - (n_poses - 1) / chunk * chunk;
+  // one scratch for every render of the call: the largest of the full chunk, the last one and the shared ground truth
+  size_t rs = std::max(render_scratch_bytes(chunk, mesh->d.V, mesh->d.F, H, W, ctx->num_cu),
+                       render_scratch_bytes(last, mesh->d.V, mesh->d.F, H, W, ctx->num_cu));
+  if (!gt_per_pose) rs = std::max(rs, render_scratch_bytes(1, mesh->d.V, mesh->d.F, H, W, ctx->num_cu));
+  const size_t counts_bytes = (size_t)n_poses * (2 + FP_VSD_MAX_TAUS) * sizeof(unsigned);
+  const size_t dg_bytes = px * sizeof(float) * (gt_per_pose ? chunk : 1), de_bytes = px * sizeof(float) * chunk;
+  FP_TRY(fp_arena_ensure(ctx, counts_bytes + dg_bytes + de_bytes + rs + 4 * 256 + 4096));
+  const size_t mark = ctx->arena.off;
+  auto run = [&]() -> int {
+    unsigned *counts = (unsigned *)ctx->arena.take(counts_bytes);
+    float *dg = (float *)ctx->arena.take(dg_bytes);
+    float *de = (float *)ctx->arena.take(de_bytes);
+    FP_REQUIRE(counts && dg && de, "fp_vsd: arena exhausted");
+    FP_CHECK_HIP(hipMemsetAsync(counts, 0, counts_bytes, s));
+    // render_with_arena_scratch takes the render scratch behind these buffers and releases it when the launches are queued
+    auto render_depth = [&](const float *poses, int n, float *out) -> int {
+      RenderArgs a;
+      FP_TRY(fill_render(a, mesh, poses, n, K, H, W, nullptr, H, W));
+      a.depth = out;
+      return render_with_arena_scratch(ctx, a, s);
+    };
+    if (!gt_per_pose) FP_TRY(render_depth(d_gt, 1, dg));
+    for (int b0 = 0; b0 < n_poses; b0 += chunk) {
+      const int n = std::min(chunk, n_poses - b0);
+      FP_TRY(render_depth(d_pred + (size_t)b0 * 16, n, de));
+      if (gt_per_pose) FP_TRY(render_depth(d_gt + (size_t)b0 * 16, n, dg));
+      FP_TRY(launch_vsd_count(d_depth_test + (depth_per_pose ? (size_t)b0 * px : 0), depth_per_pose ? px : 0, dg, gt_per_pose ? px : 0, de,
+                              n, H, W, K, diameter, delta, h_taus, n_taus, counts + (size_t)b0 * (2 + FP_VSD_MAX_TAUS), s));
+    }
+    return launch_vsd_finish(counts, n_poses, n_taus, d_err, d_counts, s);
+  };
+  const int rc = run();
+  ctx->arena.off = mark;
+  return rc;
+}
+
 extern "C" int fp_pose_update(fp_ctx *ctx,const float *d_poseA, const float *d_trans, const float *d_rot, int N, int rot_dim,
                               int trans_rep_tanh, const float *tn, float rot_normalizer, float trans_scale, float *d_pose_out,
                               void *stream) {

@@ -443,3 +443,12 @@ int launch_mask_depth_stats(const float *d, const unsigned char *mask, int H, in
 size_t pose_errors_slab_bytes(int n_pts, int n_poses, int n_sym);
 int launch_pose_errors(const float *pts, int n_pts, const float *pred, const float *gt, int gt_per_pose, int n_poses, const float *sym,
                        int n_sym, int which, double *slab, float *add, float *adds, float *add_sym, hipStream_t s);
+// metrics.hip: MSSD / MSPD of n_poses poses (fp_pose_errors_bop); `slab` holds bop_errors_slab_bytes(...) bytes of tile maxima
+size_t bop_errors_slab_bytes(int n_pts, int n_poses, int n_sym);
+int launch_bop_errors(const float *pts, int n_pts, const float *pred, const float *gt, int gt_per_pose, int n_poses, const float *sym,
+                      int n_sym, const double *K, int which, float *slab, float *mssd, float *mspd, hipStream_t s);
+// metrics.hip: the VSD counts of n_poses depth renders (fp_vsd): pose b's images at dt + b * dt_stride, dg + b * dg_stride, de + b * H * W;
+// adds into counts[b][2 + FP_VSD_MAX_TAUS]; launch_vsd_finish turns the counts into errors (and int32 counts, if counts_out)
+int launch_vsd_count(const float *dt, size_t dt_stride, const float *dg, size_t dg_stride, const float *de, int n_poses, int H, int W,
+                     const double *K, double diameter, double delta, const double *taus, int n_taus, unsigned *counts, hipStream_t s);
+int launch_vsd_finish(const unsigned *counts, int n_poses, int n_taus, float *err, int *counts_out, hipStream_t s);

@@ -792,6 +792,12 @@ RenderPlan render_plan(int N, int V, int F, int Ho, int Wo, int num_cu) {
   p.lds_verts = (size_t)V * 8 <= 64 * 1024 ? 1 : 0;                          // the hypothesis' A records beside the strip
   p.a_lds = p.lds_verts ? (((size_t)V * 8 + 15) & ~(size_t)15) : 0;
   int rows_max = (int)((budget - p.a_lds - 16) / ((size_t)Wo * 10));        // 8 B framebuffer + 2 B covered-pixel queue per pixel
+  if (p.lds_verts && (rows_max < 1 || (Ho + rows_max - 1) / rows_max > RB_MAXS)) {
+    // a large full frame (1920x1200 beside 8k vertices) would need more than RB_MAXS strips: the A records stay in global memory
+    p.lds_verts = 0;
+    p.a_lds = 0;
+    rows_max = (int)((budget - 16) / ((size_t)Wo * 10));
+  }
   if (rows_max > Ho) rows_max = Ho;
   if (rows_max < 1) rows_max = 1;
   int S = (Ho + rows_max - 1) / rows_max;

@@ -155,6 +155,41 @@ int fp_mask_depth_stats(fp_ctx *ctx, const float *d_depth, const uint8_t *d_mask
 int fp_pose_errors(fp_ctx *ctx, const float *d_pts, int n_pts, const float *d_pred, const float *d_gt, int gt_per_pose, int n_poses,
                    const float *d_sym, int n_sym, int which, float *d_add, float *d_adds, float *d_add_sym, void *stream);
 
+#define FP_BOP_MSSD 1
+#define FP_BOP_MSPD 2
+/* BOP pose errors of n_poses poses against ground truth: bop_toolkit pose_error.mssd and pose_error.mspd (BOP 2019 evaluation), in one
+ * launch plus a small one that reduces the tile maxima.  d_pts, d_pred, d_gt, gt_per_pose, d_sym as for fp_pose_errors; d_sym may be
+ * null with n_sym = 0 (the identity only).  K: host float64 3x3 intrinsics, required for FP_BOP_MSPD.  `which` ORs FP_BOP_*; each
+ * requested output (n_poses float32, device) receives
+ *   FP_BOP_MSSD  d_mssd[b] = min_k max_i |(pred_b - gt_b S_k) p_i|                     metres
+ *   FP_BOP_MSPD  d_mspd[b] = min_k max_i |pi(pred_b p_i) - pi(gt_b S_k p_i)|           pixels, pi(x) = (fx x/z + cx, fy y/z + cy)
+ * pred_b - gt_b S_k and gt_b S_k are formed in double and rounded once, so pred = gt gives exactly 0.  A point at z <= 0 under either
+ * transform makes that k's MSPD maximum +inf.  A pose's results are bit-identical whatever the batch it is in.  Workspace comes from
+ * the context's arena; nothing synchronises.  FP_EINVAL: a null ctx, d_pts, d_pred or d_gt, n_pts < 1, n_poses < 0, n_sym < 0,
+ * n_sym > 0 with d_sym null, gt_per_pose not 0 / 1, unknown bits in `which`, a requested output that is null, FP_BOP_MSPD with K
+ * null.  n_poses = 0 or which = 0 launches nothing. */
+int fp_pose_errors_bop(fp_ctx *ctx, const float *d_pts, int n_pts, const float *d_pred, const float *d_gt, int gt_per_pose, int n_poses,
+                       const float *d_sym, int n_sym, const double *K, int which, float *d_mssd, float *d_mspd, void *stream);
+
+#define FP_VSD_MAX_TAUS 32
+/* Visible surface discrepancy of n_poses poses: bop_toolkit pose_error.vsd with visib_mode = 'bop19' and the distances normalised by
+ * the diameter.  d_depth_test: metres, 0 = missing, (H,W) shared by every pose (depth_per_pose = 0) or (n_poses,H,W) (= 1).  d_pred
+ * (n_poses,4,4); d_gt (4,4) (gt_per_pose = 0, rendered once) or (n_poses,4,4) (= 1).  K: host float64 3x3.  The depth of every pose is
+ * rendered full frame by this library's rasteriser (fp_render), into workspace from the context's arena, in chunks of poses.  Per pixel,
+ * with u, v the integer pixel indices:
+ *   dist(d) = sqrt(X*X + Y*Y + d*d),  X = ((u - cx) * d) * (1/fx),  Y = ((v - cy) * d) * (1/fy)      float64, not contracted
+ *   Dt = dist(depth_test), Dg = dist(render(gt)), De = dist(render(pred))
+ *   vis(Dm) = Dm > 0 && ((double)((float)Dm - (float)Dt) <= delta || Dt == 0)
+ *   visib_gt = vis(Dg),  visib_est = vis(De) || (visib_gt && De > 0)
+ *   cost_t = #{inter : |Dg - De| / diameter >= h_taus[t]},  e_t = (cost_t + |union| - |inter|) / |union|  (1 when |union| = 0)
+ * d_err (n_poses, n_taus) float32 receives e; d_counts, if not null, (n_poses, 2 + n_taus) int32: |union|, |inter|, cost_0 ..
+ * Nothing synchronises.  FP_EINVAL: a null ctx, mesh, d_depth_test, K, d_pred, d_gt, h_taus or d_err, n_taus outside
+ * 1..FP_VSD_MAX_TAUS, H or W < 1, H * W > 2^30, diameter <= 0 (or NaN), depth_per_pose or gt_per_pose not 0 / 1, n_poses < 0.
+ * n_poses = 0 launches nothing.  A frame the rasteriser cannot take (W above 6553, for one) is refused with FP_EINVAL as well. */
+int fp_vsd(fp_ctx *ctx, const fp_mesh *mesh, const float *d_depth_test, int depth_per_pose, int H, int W, const double *K, const float *d_pred,
+           const float *d_gt, int gt_per_pose, int n_poses, double diameter, double delta, const double *h_taus, int n_taus, float *d_err,
+           int32_t *d_counts, void *stream);
+
 /* ---- networks -------------------------------------------------------------------------------- */
 typedef struct {
   const char *name;    /* reference state_dict key, e.g. "encodeA.0.net.0.weight" */
