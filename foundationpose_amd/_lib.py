@@ -47,6 +47,21 @@ class FpTrackArgs(Structure):
               ('d_scores', c_void_p), ('d_best', c_void_p), ('d_depth_f', c_void_p), ('d_xyz', c_void_p), ('d_rgb_f', c_void_p)]
 
 
+FP_TRACK_MAX_OBJECTS = 8             # include/foundationpose_amd.h
+
+
+class FpTrackObject(Structure):
+  """fp_track_object (include/foundationpose_amd.h): one object of a multi-object tracking frame."""
+  _fields_ = [('mesh', c_void_p), ('mesh_diameter', c_double), ('model_center', c_float * 3), ('d_pose', c_void_p), ('d_pose_of_mesh', c_void_p)]
+
+
+class FpTrackObjectsArgs(Structure):
+  """fp_track_objects_args (include/foundationpose_amd.h): track_one for several objects of one frame, every launch of it."""
+  _fields_ = [('struct_size', ctypes.c_size_t), ('refine_net', c_void_p), ('d_rgb', c_void_p), ('rgb_is_u8', c_int), ('d_depth', c_void_p),
+              ('H', c_int), ('W', c_int), ('K', c_void_p), ('refine_cfg', c_void_p), ('iteration', c_int), ('n_obj', c_int), ('objs', c_void_p),
+              ('d_depth_f', c_void_p), ('d_xyz', c_void_p), ('d_rgb_f', c_void_p)]
+
+
 class FpObjectBatch(Structure):
   _fields_ = [('mesh', c_void_p), ('d_rgb', c_void_p), ('d_geom', c_void_p), ('H', c_int), ('W', c_int), ('K', c_void_p),
               ('mesh_diameter', c_double), ('n', c_int)]
@@ -92,6 +107,7 @@ _PROTOS = {
   'fp_score_tail_scores': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
   'fp_score_predict_rows_multi': (c_int, [c_void_p, c_void_p, POINTER(FpObjectBatch), c_int, c_double, c_int, c_void_p, c_void_p, c_void_p]),
   'fp_track_frame': (c_int, [c_void_p, POINTER(FpTrackArgs), c_void_p]),
+  'fp_track_objects': (c_int, [c_void_p, POINTER(FpTrackObjectsArgs), c_void_p]),
   'fp_pose_update': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_float, c_float, c_void_p, c_void_p]),
   'fp_pose_update_deepim': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_float, c_float, c_float, c_void_p, c_void_p]),
   'fp_refine_predict': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_double, POINTER(FpRefineCfg), c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),

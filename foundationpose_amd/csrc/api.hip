@@ -978,6 +978,131 @@ extern "C" int fp_track_frame(fp_ctx *ctx, const fp_track_args *a, void *stream)
   return rc;
 }
 
+// ---- track_one of several objects of one frame (fp_track_objects): hypothesis o of the pass is object o.  Per iteration ONE render launch
+// for the objects the one-launch form takes (render_objects_kernel; the others one launch each), ONE observed-crop launch, one network pass
+// over the n_obj images and one tail launch; the first iteration's crop windows are one launch that also gathers the objects' poses.  Each
+// stage is the one-object pass' arithmetic on the object's own mesh and diameter.
+static int track_objects_pass(fp_ctx *ctx, const fp_track_objects_args *a, const float *rgb_f, hipStream_t s) {
+  const int N = a->n_obj;
+  const fp_refine_cfg *cfg = a->refine_cfg;
+  const fp_track_object *objs = a->objs;
+  const size_t img = (size_t)160 * 160 * 8;
+  bool solo[FP_TRACK_MAX_OBJECTS];
+  size_t rs = 0;                // scratch of the objects rendered on their own
+  for (int o = 0; o < N; ++o) {
+    const MeshDev &m = objs[o].mesh->d;
+    solo[o] = render_objects_form(m.V, m.F, 160, 160, ctx->num_cu);
+    if (!solo[o]) rs += (render_scratch_bytes(1, m.V, m.F, 160, 160, ctx->num_cu) + 255) & ~(size_t)255;
+  }
+  FP_TRY(fp_arena_ensure(ctx, pass_arena_bytes(N, rs) + (size_t)N * 16 * sizeof(float) + 4096));
+  const size_t mark = ctx->arena.off;
+  auto body = [&]() -> int {
+    TAKE(poses, float, (size_t)N * 16);
+    TAKE(tf, float, (size_t)N * 9);
+    TAKE(bbox, float, (size_t)N * 4);
+    TAKE(trans, float, (size_t)N * 3);
+    TAKE(rot, float, (size_t)N * 6);
+    TAKE(net_in, f16, (size_t)2 * N * img);
+    TAKE(rscratch, char, rs);
+    const float *pose_in[FP_TRACK_MAX_OBJECTS];
+    const MeshDev *mesh[FP_TRACK_MAX_OBJECTS];
+    float diam[FP_TRACK_MAX_OBJECTS], rdiam[FP_TRACK_MAX_OBJECTS];
+    double diam_d[FP_TRACK_MAX_OBJECTS];
+    int hyp[FP_TRACK_MAX_OBJECTS], n_solo = 0;
+    for (int o = 0; o < N; ++o) {
+      pose_in[o] = objs[o].d_pose;
+      diam[o] = (float)objs[o].mesh_diameter;
+      diam_d[o] = objs[o].mesh_diameter;
+      if (solo[o]) mesh[n_solo] = &objs[o].mesh->d, rdiam[n_solo] = diam[o], hyp[n_solo++] = o;
+    }
+    RenderArgs ra;          // render_net_impl's fields; mesh and diameter come per object
+    FP_TRY(fill_render(ra, objs[0].mesh, poses, N, a->K, a->H, a->W, bbox, 160, 160));
+    ra.use_light = 1;
+    ra.w_ambient = 0.8f;
+    ra.w_diffuse = 0.5f;
+    ra.net_out = net_in;
+    ra.invalid_thres = 0.001f;
+    ra.normalize_xyz = cfg->normalize_xyz;
+    CropArgs ca;            // fp_crop_observed's fields; the diameter comes per object
+    memset(&ca, 0, sizeof(ca));
+    ca.rgb = rgb_f, ca.geom = a->d_xyz, ca.tf = tf, ca.poses = poses;
+    for (int i = 0; i < 9; ++i) ca.K[i] = a->K[i];
+    ca.H = a->H, ca.W = a->W, ca.N = N, ca.Ho = 160, ca.Wo = 160, ca.mode = 0, ca.normalize_xyz = cfg->normalize_xyz, ca.out_fmt = 1;
+    ca.out = net_in + (size_t)N * img;
+    // as in the one-object pass: the observed side is a chain of its own up to the channel concat
+    const bool two_sides = N < fp_trunk_split_min() && !g_one_chain;
+    for (int it = 0; it < a->iteration; ++it) {
+      if (it == 0)         // (from the second iteration on the previous pass' tail has written the windows)
+        FP_TRY(launch_crop_window_objects(pose_in, a->K, cfg->crop_ratio, diam_d, N, 160, 160, poses, tf, bbox, s));
+      std::unique_ptr<StreamFanout> ab;
+      if (two_sides) ab.reset(new StreamFanout(ctx, s, 2));          // forks behind the crop windows
+      if (n_solo) FP_TRY(launch_render_objects(ctx, ra, mesh, rdiam, hyp, n_solo, s));
+      size_t voff = 0;
+      for (int o = 0; o < N; ++o) {
+        if (solo[o]) continue;
+        const MeshDev &m = objs[o].mesh->d;
+        const size_t rsb = (render_scratch_bytes(1, m.V, m.F, 160, 160, ctx->num_cu) + 255) & ~(size_t)255;
+        FP_TRY(render_net_impl(ctx, objs[o].mesh, poses + (size_t)o * 16, 1, a->K, a->H, a->W, bbox + (size_t)o * 4, 160, 160, objs[o].mesh_diameter,
+                               cfg->normalize_xyz, 0.001f, net_in + (size_t)o * img, rscratch + voff, rsb, s));
+        voff += rsb;
+      }
+      {
+        hipStream_t sb = ab ? ab->stream_for(0) : s;
+        ProfScope ps(ctx, sb, "crop", (double)N * 160 * 160 * 16.0);      // bytes written
+        FP_TRY(launch_crop_observed_objects(ca, diam, sb));
+      }
+      RefineTailArgs t;
+      memset(&t, 0, sizeof(t));
+      t.poses = poses;
+      t.trans_tanh = cfg->trans_rep_tanh;
+      t.tn0 = cfg->trans_normalizer[0], t.tn1 = cfg->trans_normalizer[1], t.tn2 = cfg->trans_normalizer[2];
+      t.rot_normalizer = cfg->rot_normalizer;
+      for (int i = 0; i < 9; ++i) t.K[i] = (float)a->K[i];
+      t.resize = 160.f;
+      t.tf = tf, t.bbox = bbox;
+      t.next_window = it + 1 < a->iteration;
+      t.win = crop_window_k(a->K, cfg->crop_ratio, objs[0].mesh_diameter, 160, 160);
+      t.obj.n = N;
+      const bool last = it + 1 == a->iteration;
+      for (int o = 0; o < N; ++o) {
+        t.obj.trans_scale[o] = cfg->normalize_xyz ? (float)(objs[o].mesh_diameter / 2) : 1.f;
+        t.obj.radius[o] = crop_window_k(a->K, cfg->crop_ratio, objs[o].mesh_diameter, 160, 160).radius;
+        for (int c = 0; c < 3; ++c) t.obj.cneg[o][c] = -objs[o].model_center[c];
+        t.obj.centered[o] = last ? objs[o].d_pose_of_mesh : nullptr;
+        t.obj.pose_out[o] = last ? objs[o].d_pose : nullptr;
+      }
+      FP_TRY(fp_refine_forward_ab(ctx, a->refine_net, net_in, N, trans, rot, s, ab.get(), &t, nullptr));
+    }
+    return FP_OK;
+  };
+  int rc = body();
+  ctx->arena.off = mark;
+  return rc;
+}
+
+extern "C" int fp_track_objects(fp_ctx *ctx, const fp_track_objects_args *a, void *stream) {
+  FP_REQUIRE(ctx && a, "fp_track_objects: null argument");
+  FP_REQUIRE(a->struct_size == sizeof(fp_track_objects_args), "fp_track_objects: fp_track_objects_args.struct_size = %zu (this library knows %zu)",
+             a->struct_size, sizeof(fp_track_objects_args));
+  FP_REQUIRE(a->refine_net && a->d_rgb && a->d_depth && a->K && a->refine_cfg && a->objs && a->d_depth_f && a->d_xyz, "fp_track_objects: null field");
+  FP_REQUIRE(a->H > 1 && a->W > 1 && a->iteration >= 1, "fp_track_objects: bad H / W / iteration");
+  FP_REQUIRE(a->n_obj >= 1 && a->n_obj <= FP_TRACK_MAX_OBJECTS, "fp_track_objects: n_obj = %d (1 .. %d objects)", a->n_obj, FP_TRACK_MAX_OBJECTS);
+  FP_REQUIRE(!a->rgb_is_u8 || a->d_rgb_f, "fp_track_objects: a uint8 frame needs the float workspace d_rgb_f");
+  for (int o = 0; o < a->n_obj; ++o) {
+    const fp_track_object &ob = a->objs[o];
+    FP_REQUIRE(ob.mesh && ob.d_pose && ob.d_pose_of_mesh, "fp_track_objects: object %d has a null field", o);
+    FP_REQUIRE(ob.mesh_diameter > 0, "fp_track_objects: object %d has a bad mesh_diameter", o);
+  }
+  FP_REQUIRE(fp_hyp_chunk(a->n_obj) == a->n_obj, "fp_track_objects: FP_CHUNK cuts the pass of %d images (the fused tail needs it whole)", a->n_obj);
+  hipStream_t s = (hipStream_t)stream;
+  // the depth prelude of fp_track_frame, once for all objects
+  double K32[9];
+  for (int i = 0; i < 9; ++i) K32[i] = (double)(float)a->K[i];
+  FP_TRY(launch_depth_prefilter(a->d_depth, a->H, a->W, 0.001f, 0.8f, 100.f, 100.f, 2.f, 100000.f, K32, 3.0e38f, a->d_depth_f, a->d_xyz,
+                                a->rgb_is_u8 ? (const uint8_t *)a->d_rgb : nullptr, a->rgb_is_u8 ? a->d_rgb_f : nullptr, s));
+  return track_objects_pass(ctx, a, a->rgb_is_u8 ? a->d_rgb_f : (const float *)a->d_rgb, s);
+}
+
 int conv_ksplit(const ConvArgs &a, int num_cu);      // conv.hip
 
 // ---- building blocks ---------------------------------------------------------------------------------

@@ -618,6 +618,9 @@ __global__ __launch_bounds__(512) void mean_head_kernel(const float *__restrict_
 // and of the rotation head (two mean_head_kernel launches), the pose update (pose_update_kernel) and - when another iteration
 // follows - its crop windows (crop_window_tf_kernel): four dependent launches of a few microseconds each, a workgroup per hypothesis.
 // Every piece is the building block's own device function: the results are those of the four launches bit for bit.
+// OBJS (a pass of fp_track_objects, hypothesis b = object b): trans_scale, the window radius, cneg and the centred output are object b's,
+// and the updated pose is also copied to the object's own buffer
+template <bool OBJS>
 __global__ __launch_bounds__(512) void refine_tail_kernel(RefineTailArgs a) {
   __shared__ float meanv[2][512], delta[2][8];      // delta: this hypothesis' head outputs (also written to a.trans / a.rot)
   const int b = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -637,16 +640,32 @@ __global__ __launch_bounds__(512) void refine_tail_kernel(RefineTailArgs a) {
   dp.tf = a.tf;
   dp.resize = a.resize;
   for (int i = 0; i < 9; ++i) dp.K[i] = a.K[i];
-  pose_update_one(b, a.poses, delta[0], delta[1], a.rot_dim, a.trans_tanh, a.tn0, a.tn1, a.tn2, a.rot_normalizer, a.trans_scale, dp, a.poses);
-  if (a.next_window) crop_window_tf_one(b, a.poses, a.win, a.tf, a.bbox);
-  if (a.centered) pose_of_mesh_one(a.poses + (size_t)b * 16, a.cneg, a.centered + (size_t)b * 16);
+  if constexpr (OBJS) {
+    pose_update_one(b, a.poses, delta[0], delta[1], a.rot_dim, a.trans_tanh, a.tn0, a.tn1, a.tn2, a.rot_normalizer, a.obj.trans_scale[b], dp, a.poses);
+    if (a.next_window) {
+      CropWindowK w = a.win;
+      w.radius = a.obj.radius[b];
+      crop_window_tf_one(b, a.poses, w, a.tf, a.bbox);
+    }
+    const float *p = a.poses + (size_t)b * 16;
+    if (float *c = a.obj.centered[b]) pose_of_mesh_one(p, a.obj.cneg[b], c);
+    if (float *o = a.obj.pose_out[b])
+#pragma unroll
+      for (int i = 0; i < 16; ++i) o[i] = p[i];
+  } else {
+    pose_update_one(b, a.poses, delta[0], delta[1], a.rot_dim, a.trans_tanh, a.tn0, a.tn1, a.tn2, a.rot_normalizer, a.trans_scale, dp, a.poses);
+    if (a.next_window) crop_window_tf_one(b, a.poses, a.win, a.tf, a.bbox);
+    if (a.centered) pose_of_mesh_one(a.poses + (size_t)b * 16, a.cneg, a.centered + (size_t)b * 16);
+  }
 }
 
 int launch_refine_tail(const RefineTailArgs &a, int N, hipStream_t s) {
   FP_REQUIRE(a.rot_dim == 3 || a.rot_dim == 6, "refine tail: rot_dim must be 3 or 6");
   FP_REQUIRE(a.nparts >= 1 && a.nparts <= MH_MAXPARTS, "refine tail: %d partial rows per hypothesis (at most %d)", a.nparts, MH_MAXPARTS);
+  FP_REQUIRE(a.obj.n == 0 || (a.obj.n == N && N <= FP_TRACK_MAX_OBJECTS), "refine tail: %d hypotheses for %d objects", N, a.obj.n);
   if (N == 0) return FP_OK;
-  hipLaunchKernelGGL(refine_tail_kernel, dim3(N), dim3(512), 0, s, a);
+  if (a.obj.n) hipLaunchKernelGGL(refine_tail_kernel<true>, dim3(N), dim3(512), 0, s, a);
+  else hipLaunchKernelGGL(refine_tail_kernel<false>, dim3(N), dim3(512), 0, s, a);
   FP_CHECK_HIP(hipGetLastError());
   return FP_OK;
 }

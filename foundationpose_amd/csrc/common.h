@@ -360,6 +360,13 @@ struct CropWindowK {             // intrinsics as float, radius = diameter * cro
   float k00, k01, k02, k10, k11, k12, k20, k21, k22, radius, ow, oh;
 };
 CropWindowK crop_window_k(const double *K, double crop_ratio, double diameter, int ow, int oh);
+// A pass of fp_track_objects: hypothesis b is object b.  What differs between the objects, per hypothesis (the rest of the tail is shared)
+struct RefineTailObjs {
+  int n = 0;                                      // 0: not such a pass (the scalar fields of RefineTailArgs hold for every hypothesis)
+  float trans_scale[FP_TRACK_MAX_OBJECTS], radius[FP_TRACK_MAX_OBJECTS], cneg[FP_TRACK_MAX_OBJECTS][3];
+  float *centered[FP_TRACK_MAX_OBJECTS];          // the object's pose @ get_tf_to_centered_mesh() (nullptr: not written)
+  float *pose_out[FP_TRACK_MAX_OBJECTS];          // the object's own pose buffer, which receives the updated pose (nullptr: not written)
+};
 struct RefineTailArgs {
   const float *partial[2], *gam[2], *bet[2], *hw[2], *hb[2];      // per head: group sums of linear2's LayerNorm rows, ln2 gamma / beta, head Linear
   int nparts, T, rot_dim;
@@ -375,6 +382,7 @@ struct RefineTailArgs {
   // cneg = -model_center (the translation column of that matrix)
   float *centered = nullptr;
   float cneg[3] = {0.f, 0.f, 0.f};
+  RefineTailObjs obj;            // fp_track_objects: per-object trans_scale, window radius, cneg, centered and pose copy (obj.n = N)
 };
 int launch_refine_tail(const RefineTailArgs &a, int N, hipStream_t s);
 int launch_pose_update(const float *poseA, const float *trans, const float *rot, int N, int rot_dim, int trans_tanh,
@@ -420,6 +428,14 @@ size_t render_scratch_bytes(int N, int V, int F, int Ho, int Wo, int num_cu);
 int launch_render(fp_ctx *ctx, const RenderArgs &a, hipStream_t s);      // a.scratch: render_scratch_bytes(a.N, ...) bytes
 int launch_crop_window_tf(const float *poses, int N, const double *K, double crop_ratio, double diameter, int ow, int oh, float *tf,
                           float *bbox, hipStream_t s);
+// fp_track_objects (hypothesis b = object b, n <= FP_TRACK_MAX_OBJECTS): several objects' one-launch renders (render_kernel<1, true>) as
+// ONE launch; a.mesh / a.mesh_diameter are replaced by each object's, the other fields are shared.  Every object must take the one-launch
+// form (render_objects_form); each image is the one render_kernel<1, true> makes of that object alone.  `hyp`: the object's hypothesis.
+bool render_objects_form(int V, int F, int Ho, int Wo, int num_cu);      // a mesh launch_render_objects takes (else: launch_render, on its own)
+int launch_render_objects(fp_ctx *ctx, const RenderArgs &a, const MeshDev *const *mesh, const float *diameter, const int *hyp, int n, hipStream_t s);
+// the first crop windows of such a pass: object b's pose is first copied from pose_in[b] to poses + 16 b; radius from diameter[b]
+int launch_crop_window_objects(const float *const *pose_in, const double *K, double crop_ratio, const double *diameter, int n, int ow, int oh,
+                               float *poses, float *tf, float *bbox, hipStream_t s);
 
 struct CropArgs {
   const float *rgb, *geom, *tf, *poses;
@@ -429,6 +445,8 @@ struct CropArgs {
   void *out;
 };
 int launch_crop_observed(const CropArgs &a, hipStream_t s);
+// the same with hypothesis b's mesh diameter from diameter[b] (a.N <= FP_TRACK_MAX_OBJECTS; fp_track_objects) instead of a.mesh_diameter
+int launch_crop_observed_objects(const CropArgs &a, const float *diameter, hipStream_t s);
 int launch_warp_nearest(const float *src, int src_batch, int Hs, int Ws, int C, const float *tf, int N, int Ho, int Wo, float *out,
                         hipStream_t s);
 

@@ -26,8 +26,8 @@ __device__ __forceinline__ float frame_at(const float *img, int H, int W, int C,
   return (y >= 0 && y < H && x >= 0 && x < W) ? img[((size_t)y * W + x) * C + c] : 0.f;
 }
 
-__global__ __launch_bounds__(256) void crop_observed_kernel(CropArgs a) {
-  const int b = blockIdx.y;
+// hypothesis b, one pixel per thread; mesh_diameter: the hypothesis' object's
+__device__ __forceinline__ void crop_observed_px(const CropArgs &a, int b, float mesh_diameter) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   const float *T = a.tf + (size_t)b * 9;
   const float *pose = a.poses + (size_t)b * 16;
@@ -102,7 +102,7 @@ __global__ __launch_bounds__(256) void crop_observed_kernel(CropArgs a) {
   }
   // ---- batch transform (h5_dataset.py:104-112 | :162-170) ----
   const bool invalid = xyz[2] < invalid_thres;
-  const float radius = __fdiv_rn(a.mesh_diameter, 2.f);
+  const float radius = __fdiv_rn(mesh_diameter, 2.f);
   const float inv_r = __fdiv_rn(1.f, radius);
   float o6[6] = {rgb[0], rgb[1], rgb[2], 0.f, 0.f, 0.f};
 #pragma unroll
@@ -128,12 +128,33 @@ __global__ __launch_bounds__(256) void crop_observed_kernel(CropArgs a) {
   }
 }
 
+__global__ __launch_bounds__(256) void crop_observed_kernel(CropArgs a) { crop_observed_px(a, blockIdx.y, a.mesh_diameter); }
+
+// several objects of one frame (fp_track_objects): what differs per hypothesis is the diameter of its object
+struct CropDiameters {
+  float d[FP_TRACK_MAX_OBJECTS];
+};
+__global__ __launch_bounds__(256) void crop_observed_objects_kernel(CropArgs a, CropDiameters t) { crop_observed_px(a, blockIdx.y, t.d[blockIdx.y]); }
+
 int launch_crop_observed(const CropArgs &a, hipStream_t s) {
   FP_REQUIRE(a.mode == 0 || a.mode == 1, "crop_observed: mode must be 0 (refiner) or 1 (scorer)");
   FP_REQUIRE(a.H > 1 && a.W > 1 && a.Ho > 1 && a.Wo > 1, "crop_observed: degenerate image size");
   if (a.N == 0) return FP_OK;
   dim3 grid((a.Ho * a.Wo + 255) / 256, a.N);
   hipLaunchKernelGGL(crop_observed_kernel, grid, dim3(256), 0, s, a);
+  FP_CHECK_HIP(hipGetLastError());
+  return FP_OK;
+}
+
+int launch_crop_observed_objects(const CropArgs &a, const float *diameter, hipStream_t s) {
+  FP_REQUIRE(a.mode == 0 || a.mode == 1, "crop_observed: mode must be 0 (refiner) or 1 (scorer)");
+  FP_REQUIRE(a.H > 1 && a.W > 1 && a.Ho > 1 && a.Wo > 1, "crop_observed: degenerate image size");
+  FP_REQUIRE(a.N >= 0 && a.N <= FP_TRACK_MAX_OBJECTS, "crop_observed: %d objects in one launch (at most %d)", a.N, FP_TRACK_MAX_OBJECTS);
+  if (a.N == 0) return FP_OK;
+  CropDiameters t;
+  memset(&t, 0, sizeof(t));
+  for (int b = 0; b < a.N; ++b) t.d[b] = diameter[b];
+  hipLaunchKernelGGL(crop_observed_objects_kernel, dim3((a.Ho * a.Wo + 255) / 256, a.N), dim3(256), 0, s, a, t);
   FP_CHECK_HIP(hipGetLastError());
   return FP_OK;
 }

@@ -31,6 +31,7 @@
 #include "common.h"
 #include "pose_math.h"
 #include <cstdlib>
+#include <type_traits>
 
 #define RB_THREADS 1024
 
@@ -178,11 +179,10 @@ struct VtxRecords {
   uint2 a;
   float4 b0, b1;
 };
-__device__ __forceinline__ VtxRecords vertex_records(const RenderArgs &a, int v, const float *sM, const float *sP) {
+__device__ __forceinline__ VtxRecords vertex_records(const RenderArgs &a, const MeshDev &m, int v, const float *sM, const float *sP) {
   float M[16];
 #pragma unroll
   for (int i = 0; i < 16; ++i) M[i] = sM[i];
-  const MeshDev &m = a.mesh;
   const Vtx o = xform_vertex(m.pos, v, M, 0.5f * (float)a.Wo, 0.5f * (float)a.Ho);
   const float P0 = sP[0], P1 = sP[1], P2 = sP[2], P3 = sP[3], P4 = sP[4], P5 = sP[5], P6 = sP[6], P7 = sP[7], P8 = sP[8],
               P9 = sP[9], P10 = sP[10], P11 = sP[11];
@@ -232,7 +232,7 @@ __global__ __launch_bounds__(256) void xform_vertices_kernel(RenderArgs a, int4 
   __syncthreads();
   const int v = blockIdx.x * 256 + threadIdx.x;
   if (v >= a.mesh.V) return;
-  const VtxRecords q = vertex_records(a, v, sM, sP);
+  const VtxRecords q = vertex_records(a, a.mesh, v, sM, sP);
   const size_t r = (size_t)b * a.mesh.V + v;
   recC[r] = q.c;
   recA[r] = q.a;
@@ -274,7 +274,7 @@ __global__ __launch_bounds__(RB_THREADS) void classify_faces_kernel(RenderArgs a
     }
     __syncthreads();
     for (int v = threadIdx.x; v < m.V; v += RB_THREADS) {
-      const VtxRecords q = vertex_records(a, v, sM, sP);
+      const VtxRecords q = vertex_records(a, a.mesh, v, sM, sP);
       cl_ldsA[v] = q.a;
       if ((v / RB_THREADS) % G == grp) {               // this workgroup's share of the hypothesis' records
         const size_t r = (size_t)b * m.V + v;
@@ -335,10 +335,23 @@ __global__ __launch_bounds__(RB_THREADS) void classify_faces_kernel(RenderArgs a
 // classify_faces_kernel), and takes the B / C records of the few vertices it needs from vertex_records() directly: the same
 // functions on the same inputs, and a z-buffer of (depth, face) keys under atomicMin does not depend on the order of the lists,
 // so the images are bit-identical to the three-launch form (test_render_solo_equals_three_launches).
-template <int MODE, bool SOLO>
+//
+// OBJ = RenderObjs (launch_render_objects, fp_track_objects): several objects' solo renders as ONE launch.  Workgroup L is strip L - wg0[o] of
+// object o, which keeps the strips of its own plan and its own mesh and diameter, so its image is the one render_kernel<1, true> makes of
+// it alone.  The table rides in the kernel arguments.
+struct NoObjs {};
+struct RenderObjs {
+  int n;
+  int wg0[FP_TRACK_MAX_OBJECTS + 1], hyp[FP_TRACK_MAX_OBJECTS], n_strips[FP_TRACK_MAX_OBJECTS], strip_rows[FP_TRACK_MAX_OBJECTS];
+  float diameter[FP_TRACK_MAX_OBJECTS];
+  MeshDev mesh[FP_TRACK_MAX_OBJECTS];
+};
+template <int MODE, bool SOLO, typename OBJ = NoObjs>
 __global__ __launch_bounds__(RB_THREADS) void render_kernel(RenderArgs a, int strip_rows, int n_strips, const int4 *__restrict__ recC,
                                                             const float4 *__restrict__ recB, const uint2 *__restrict__ recA, const int *__restrict__ count,
-                                                            const unsigned *__restrict__ listA, const unsigned *__restrict__ listB, int lds_verts, int G, int Fg) {
+                                                            const unsigned *__restrict__ listA, const unsigned *__restrict__ listB, int lds_verts, int G, int Fg,
+                                                            OBJ t) {
+  constexpr bool OBJS = !std::is_same<OBJ, NoObjs>::value;
   // dynamic LDS: the strip (8 B per pixel), the queue of its covered pixels (2 B per pixel), then (lds_verts) the hypothesis' A records,
   // then (SOLO) the strip's two face lists, 2 B per face each
   extern __shared__ __attribute__((aligned(16))) unsigned long long zbuf[];
@@ -347,13 +360,25 @@ __global__ __launch_bounds__(RB_THREADS) void render_kernel(RenderArgs a, int st
   __shared__ int covn;
   __shared__ int scnt[3];
   const int L = xcd_remap(blockIdx.x, gridDim.x);          // the strips of one hypothesis share an XCD's L2
-  const int b = L / n_strips, strip = L % n_strips;
+  int b, strip;
+  const MeshDev *mp = &a.mesh;
+  float obj_diameter = 0.f;
+  if constexpr (OBJS) {
+    int o = 0;
+    while (o + 1 < t.n && L >= t.wg0[o + 1]) ++o;
+    b = t.hyp[o], strip = L - t.wg0[o];
+    strip_rows = t.strip_rows[o], n_strips = t.n_strips[o];
+    mp = &t.mesh[o];
+    obj_diameter = t.diameter[o];
+  } else {
+    b = L / n_strips, strip = L % n_strips;
+  }
   const int Ho = a.Ho, Wo = a.Wo;
   const int row0 = strip * strip_rows;  // GL (bottom-up) rows [row0, row1)
   const int row1 = min(Ho, row0 + strip_rows);
   const int npix = (row1 - row0) * Wo;
   const float *pose = a.poses + (size_t)b * 16;
-  const MeshDev &m = a.mesh;
+  const MeshDev &m = *mp;
   const uint2 *gA = recA + (size_t)b * m.V;
   unsigned short *covq = reinterpret_cast<unsigned short *>(zbuf + (size_t)strip_rows * Wo);
   uint2 *ldsA = reinterpret_cast<uint2 *>(reinterpret_cast<char *>(covq) + ((((size_t)strip_rows * Wo * 2) + 15) & ~(size_t)15));
@@ -371,7 +396,7 @@ __global__ __launch_bounds__(RB_THREADS) void render_kernel(RenderArgs a, int st
   for (int i = threadIdx.x; i < npix; i += RB_THREADS) zbuf[i] = ~0ull;
   if constexpr (SOLO) {
     __syncthreads();
-    for (int v = threadIdx.x; v < m.V; v += RB_THREADS) ldsA[v] = (a.dbg & 64) ? make_uint2(RB_A_NONE, 0u) : vertex_records(a, v, sM, sP).a;
+    for (int v = threadIdx.x; v < m.V; v += RB_THREADS) ldsA[v] = (a.dbg & 64) ? make_uint2(RB_A_NONE, 0u) : vertex_records(a, m, v, sM, sP).a;
     __syncthreads();
     // the faces of this strip (classify_faces_kernel's tests, for one strip): small from the front of soloA, medium from its back
     // (four faces per thread and round: their index quads are requested together - at one hypothesis a load's latency is all there is to hide)
@@ -417,7 +442,7 @@ __global__ __launch_bounds__(RB_THREADS) void render_kernel(RenderArgs a, int st
   const float4 *vbB = recB + 2 * (size_t)b * m.V;
   auto getA = [&](int i) -> uint2 { return (SOLO || lds_verts) ? ldsA[i] : gA[i]; };
   auto getC = [&](int i) -> int4 {
-    if constexpr (SOLO) return vertex_records(a, i, sM, sP).c;
+    if constexpr (SOLO) return vertex_records(a, m, i, sM, sP).c;
     else return vc[i];
   };
   auto unpack = [](const int4 &q) -> Vtx {      // record C: exactly xform_vertex's values
@@ -614,7 +639,7 @@ __global__ __launch_bounds__(RB_THREADS) void render_kernel(RenderArgs a, int st
 #pragma unroll
       for (int c = 0; c < 3; ++c) r[c] = __fdiv_rn(__fmul_rn(col[c], 255.f), 255.f);
       bool invalid = p3[2] < a.invalid_thres;
-      float radius = __fdiv_rn(a.mesh_diameter, 2.f);
+      float radius = __fdiv_rn(OBJS ? obj_diameter : a.mesh_diameter, 2.f);
       float inv_r = __fdiv_rn(1.f, radius);
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
@@ -663,7 +688,7 @@ __global__ __launch_bounds__(RB_THREADS) void render_kernel(RenderArgs a, int st
       float4 rb0, rb1, rb2, rc0, rc1, rc2;
       [[maybe_unused]] int4 cc0, cc1, cc2;
       if constexpr (SOLO) {
-        const VtxRecords q0 = vertex_records(a, i0, sM, sP), q1 = vertex_records(a, i1, sM, sP), q2 = vertex_records(a, i2, sM, sP);
+        const VtxRecords q0 = vertex_records(a, m, i0, sM, sP), q1 = vertex_records(a, m, i1, sM, sP), q2 = vertex_records(a, m, i2, sM, sP);
         rb0 = q0.b0, rb1 = q1.b0, rb2 = q2.b0, rc0 = q0.b1, rc1 = q1.b1, rc2 = q2.b1;
         cc0 = q0.c, cc1 = q1.c, cc2 = q2.c;
       } else {
@@ -838,6 +863,7 @@ void raster_kernel_lds(std::vector<KernelLds> &v) {
   v.push_back({(const void *)render_kernel<1, true>, 148 * 1024});
   v.push_back({(const void *)render_kernel<0, true>, 148 * 1024});
   v.push_back({(const void *)render_kernel<2, true>, 148 * 1024});
+  v.push_back({(const void *)render_kernel<1, true, RenderObjs>, 148 * 1024});
 }
 
 int render_chunk(int N, int V, int F, int Ho, int Wo, int num_cu) {
@@ -890,7 +916,7 @@ static int launch_render_one(fp_ctx *ctx, const RenderArgs &a_in, int plan_n, hi
   auto go = [&](auto kern) -> int {
     hipLaunchKernelGGL(kern, dim3((unsigned)(a.N * pl.S)), dim3(RB_THREADS), pl.solo ? pl.solo_lds : pl.lds_bytes, s, a, pl.strip_rows, pl.S, (const int4 *)recC,
                        (const float4 *)recB, (const uint2 *)recA, (const int *)count, (const unsigned *)listA, (const unsigned *)listB, pl.lds_verts, pl.G,
-                       pl.Fg);
+                       pl.Fg, NoObjs());
     return FP_OK;
   };
   if (a.net_out) {
@@ -899,6 +925,43 @@ static int launch_render_one(fp_ctx *ctx, const RenderArgs &a_in, int plan_n, hi
     if (a.color || a.depth || a.normal || a.xyz) FP_TRY(pl.solo ? go(render_kernel<0, true>) : go(render_kernel<0, false>));
     if (a.rast) FP_TRY(pl.solo ? go(render_kernel<2, true>) : go(render_kernel<2, false>));        // (a second pass over the same lists: the parity tests' output)
   }
+  FP_CHECK_HIP(hipGetLastError());
+  return FP_OK;
+}
+
+bool render_objects_form(int V, int F, int Ho, int Wo, int num_cu) {
+  const RenderPlan pl = render_plan(1, V, F, Ho, Wo, num_cu);
+  return pl.solo && pl.S <= RB_MAXS && pl.strip_rows * Wo <= 65535;
+}
+
+int launch_render_objects(fp_ctx *ctx, const RenderArgs &a_in, const MeshDev *const *mesh, const float *diameter, const int *hyp, int n, hipStream_t s) {
+  FP_REQUIRE(n >= 1 && n <= FP_TRACK_MAX_OBJECTS, "render: %d objects in one launch (1 .. %d)", n, FP_TRACK_MAX_OBJECTS);
+  FP_REQUIRE(a_in.net_out && a_in.Ho > 0 && a_in.Wo > 0, "render: the multi-object form writes the network tensor");
+  RenderArgs a = a_in;
+  static const int dbg_env = getenv("FP_RENDER_DBG") ? atoi(getenv("FP_RENDER_DBG")) : 0;      // as launch_render_one
+  a.dbg = dbg_env;
+  RenderObjs t;
+  memset(&t, 0, sizeof(t));
+  t.n = n;
+  size_t lds = 0;
+  int wg = 0;
+  for (int o = 0; o < n; ++o) {
+    const RenderPlan pl = render_plan(1, mesh[o]->V, mesh[o]->F, a.Ho, a.Wo, ctx->num_cu);
+    FP_REQUIRE(render_objects_form(mesh[o]->V, mesh[o]->F, a.Ho, a.Wo, ctx->num_cu), "render: object %d (%d vertices, %d faces) does not take the one-launch form",
+               o, mesh[o]->V, mesh[o]->F);
+    t.wg0[o] = wg;
+    t.hyp[o] = hyp[o];
+    t.n_strips[o] = pl.S;
+    t.strip_rows[o] = pl.strip_rows;
+    t.diameter[o] = diameter[o];
+    t.mesh[o] = *mesh[o];
+    wg += pl.S;
+    lds = pl.solo_lds > lds ? pl.solo_lds : lds;
+  }
+  t.wg0[n] = wg;
+  ProfScope ps(ctx, s, "render", (double)n * a.Ho * a.Wo * 16.0);
+  hipLaunchKernelGGL((render_kernel<1, true, RenderObjs>), dim3((unsigned)wg), dim3(RB_THREADS), lds, s, a, 0, 1, (const int4 *)nullptr,
+                     (const float4 *)nullptr, (const uint2 *)nullptr, (const int *)nullptr, (const unsigned *)nullptr, (const unsigned *)nullptr, 1, 1, 0, t);
   FP_CHECK_HIP(hipGetLastError());
   return FP_OK;
 }
@@ -944,6 +1007,39 @@ int launch_crop_window_tf(const float *poses, int N, const double *K, double cro
                           float *bbox, hipStream_t s) {
   if (N == 0) return FP_OK;
   hipLaunchKernelGGL(crop_window_tf_kernel, dim3((N + 63) / 64), dim3(64), 0, s, poses, N, crop_window_k(K, crop_ratio, diameter, ow, oh), tf, bbox);
+  FP_CHECK_HIP(hipGetLastError());
+  return FP_OK;
+}
+
+// the first crop windows of a pass of fp_track_objects: thread b copies object b's pose into the pass' pose array, then makes its window
+// with the object's radius (the intrinsics and output size are shared)
+struct CropWindowObjs {
+  int n;
+  float radius[FP_TRACK_MAX_OBJECTS];
+  const float *pose_in[FP_TRACK_MAX_OBJECTS];
+};
+__global__ void crop_window_objects_kernel(CropWindowK c, CropWindowObjs t, float *poses, float *tf, float *bbox) {
+  const int b = threadIdx.x;
+  if (b >= t.n) return;
+  const float *src = t.pose_in[b];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) poses[(size_t)b * 16 + i] = src[i];
+  CropWindowK w = c;
+  w.radius = t.radius[b];
+  crop_window_tf_one(b, poses, w, tf, bbox);
+}
+
+int launch_crop_window_objects(const float *const *pose_in, const double *K, double crop_ratio, const double *diameter, int n, int ow, int oh,
+                               float *poses, float *tf, float *bbox, hipStream_t s) {
+  FP_REQUIRE(n >= 1 && n <= FP_TRACK_MAX_OBJECTS, "crop windows: %d objects in one launch (1 .. %d)", n, FP_TRACK_MAX_OBJECTS);
+  CropWindowObjs t;
+  memset(&t, 0, sizeof(t));
+  t.n = n;
+  for (int b = 0; b < n; ++b) {
+    t.radius[b] = crop_window_k(K, crop_ratio, diameter[b], ow, oh).radius;
+    t.pose_in[b] = pose_in[b];
+  }
+  hipLaunchKernelGGL(crop_window_objects_kernel, dim3(1), dim3(64), 0, s, crop_window_k(K, crop_ratio, diameter[0], ow, oh), t, poses, tf, bbox);
   FP_CHECK_HIP(hipGetLastError());
   return FP_OK;
 }

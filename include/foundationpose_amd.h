@@ -309,6 +309,37 @@ typedef struct fp_track_args {
 } fp_track_args;
 int fp_track_frame(fp_ctx *ctx, const fp_track_args *args, void *stream);
 
+/* ---- track_one for several objects of ONE frame in one call: the depth prelude once, then per iteration one crop-window (first
+ *      iteration), one render and one observed-crop launch over all objects (an object whose mesh the one-launch render cannot take
+ *      gets a render launch of its own), ONE network pass over the n_obj images and one fused tail that refines each object's pose and,
+ *      in the last iteration, writes it back to d_pose together with pose @ get_tf_to_centered_mesh().  One hypothesis per object, no
+ *      scoring.  hipGraph-capturable, no host synchronisation; the arena must already hold the pass (fp_ctx_reserve(ctx, 64)).  Each
+ *      object's result is fp_track_frame's for it alone except for the last bits of the network pass, whose kernel forms depend on the
+ *      number of images; with one object it is fp_track_frame's bit for bit. ----------------------------------- */
+#define FP_TRACK_MAX_OBJECTS 8
+typedef struct {
+  const fp_mesh *mesh;             /* objects may share a mesh (two instances of one part) */
+  double mesh_diameter;
+  float model_center[3];           /* get_tf_to_centered_mesh() = translation by -model_center */
+  float *d_pose;                   /* 16: in = the previous pose (centred mesh), out = this frame's; device memory */
+  float *d_pose_of_mesh;           /* 16 out: d_pose @ get_tf_to_centered_mesh(); device or pinned host memory */
+} fp_track_object;
+typedef struct {
+  size_t struct_size;              /* = sizeof(fp_track_objects_args) */
+  const fp_net *refine_net;
+  const void *d_rgb;               /* H*W*3: uint8 (rgb_is_u8) or float [0,255] */
+  int rgb_is_u8;
+  const float *d_depth;            /* H*W raw depth, metres */
+  int H, W;
+  const double *K;                 /* host, 3x3 row-major */
+  const fp_refine_cfg *refine_cfg;
+  int iteration;
+  int n_obj;                       /* 1 .. FP_TRACK_MAX_OBJECTS */
+  const fp_track_object *objs;     /* host array of n_obj objects */
+  float *d_depth_f, *d_xyz, *d_rgb_f; /* workspace, as in fp_track_args */
+} fp_track_objects_args;
+int fp_track_objects(fp_ctx *ctx, const fp_track_objects_args *args, void *stream);
+
 /* fp_score_tail with a feature row stride (feat_ld >= 512 floats: 528 reads the [feature | pose] rows below in place) and, optionally
  * (d_scores != NULL), scores = logits + score_offset from the same launch (ScorePredictor.predict: + 100, predict_score.py:209) */
 int fp_score_tail_scores(fp_ctx *ctx, const fp_net *net, const float *d_feats, int feat_ld, int groups, int L, float score_offset, float *d_logits,
