@@ -212,6 +212,33 @@ def mask_depth_stats(depth, mask, min_depth=0.001):
   return dict(cmin=st[0], cmax=st[1], rmin=st[2], rmax=st[3], n_mask=st[4], n_usable=st[5], median=np.float32(med.value))
 
 
+def mask_depth_stats_objects(depth, masks, min_depth=0.001, labels=None):
+  """mask_depth_stats of several objects in ONE launch and one copy to the host (fp_mask_depth_stats_objects): `masks` is a sequence of
+  (H,W) masks (anything non-zero = object) or, with `labels` = [id_0, ...], one (H,W) integer label image (pixel == id_o: object o).
+  Returns one dict(cmin, cmax, rmin, rmax, n_mask, n_usable, median) per object, each equal to mask_depth_stats of that mask."""
+  d = torch.as_tensor(depth, dtype=torch.float, device='cuda').contiguous()
+  dev_of = lambda m: torch.as_tensor(np.ascontiguousarray(m) if isinstance(m, np.ndarray) else m, device=d.device)
+  H, W = d.shape
+  if labels is not None:
+    img = dev_of(masks).to(torch.int32).contiguous()
+    assert img.shape == d.shape, 'label image and depth shapes differ'
+    n = len(labels)
+    ids = (ctypes.c_int32 * n)(*[int(x) for x in labels])
+    mptr, lptr, keep = None, ptr(img), img
+  else:
+    keep = [(dev_of(m) != 0).to(torch.uint8).contiguous() for m in masks]
+    assert all(m.shape == d.shape for m in keep), 'mask and depth shapes differ'
+    n = len(keep)
+    ids = None
+    mptr, lptr = (ctypes.c_void_p * n)(*[m.data_ptr() for m in keep]), None
+  ctx = _lib.Context.get(d.device)
+  st = (ctypes.c_int32 * (6 * n))()
+  med = (ctypes.c_float * n)()
+  check(lib().fp_mask_depth_stats_objects(ctx.handle, ptr(d), mptr, lptr, ids, n, H, W, float(min_depth), st, med, stream_ptr(d.device)))
+  return [dict(cmin=st[6 * o], cmax=st[6 * o + 1], rmin=st[6 * o + 2], rmax=st[6 * o + 3], n_mask=st[6 * o + 4], n_usable=st[6 * o + 5],
+               median=np.float32(med[o])) for o in range(n)]
+
+
 def depth2xyzmap_batch(depths, Ks, zfar):
   """src/Utils.py:420-438: (B,H,W) device tensor + (B,3,3) -> (B,H,W,3), float32 on the device."""
   depths = torch.as_tensor(depths, dtype=torch.float, device='cuda').contiguous()

@@ -62,6 +62,25 @@ class FpTrackObjectsArgs(Structure):
               ('d_depth_f', c_void_p), ('d_xyz', c_void_p), ('d_rgb_f', c_void_p)]
 
 
+FP_REGISTER_PASS_HYP, FP_REGISTER_MIN_VALID = 1008, 4      # include/foundationpose_amd.h
+
+
+class FpRegisterObject(Structure):
+  """fp_register_object (include/foundationpose_amd.h): one object of a multi-object registration, its device and host outputs."""
+  _fields_ = [('mesh', c_void_p), ('mesh_diameter', c_double), ('model_center', c_float * 3), ('d_mask', c_void_p), ('label', ctypes.c_int32),
+              ('d_rot_grid', c_void_p), ('n_hyp', c_int), ('d_poses', c_void_p), ('d_scores', c_void_p), ('d_order', c_void_p),
+              ('d_pose_of_mesh', c_void_p), ('stats', ctypes.c_int32 * 6), ('median', c_float), ('registered', c_int),
+              ('guess_translation', c_double * 3)]
+
+
+class FpRegisterObjectsArgs(Structure):
+  """fp_register_objects_args (include/foundationpose_amd.h): register() for several objects of one frame, every launch of it."""
+  _fields_ = [('struct_size', ctypes.c_size_t), ('refine_net', c_void_p), ('score_net', c_void_p), ('d_rgb', c_void_p), ('rgb_is_u8', c_int),
+              ('d_depth', c_void_p), ('H', c_int), ('W', c_int), ('K', c_void_p), ('K_inv', c_void_p), ('refine_cfg', c_void_p),
+              ('score_crop_ratio', c_double), ('score_normalize_xyz', c_int), ('iteration', c_int), ('n_obj', c_int), ('objs', c_void_p),
+              ('d_labels', c_void_p), ('max_pass_hyp', c_int), ('d_depth_f', c_void_p), ('d_xyz', c_void_p), ('d_rgb_f', c_void_p)]
+
+
 class FpObjectBatch(Structure):
   _fields_ = [('mesh', c_void_p), ('d_rgb', c_void_p), ('d_geom', c_void_p), ('H', c_int), ('W', c_int), ('K', c_void_p),
               ('mesh_diameter', c_double), ('n', c_int)]
@@ -108,6 +127,10 @@ _PROTOS = {
   'fp_score_predict_rows_multi': (c_int, [c_void_p, c_void_p, POINTER(FpObjectBatch), c_int, c_double, c_int, c_void_p, c_void_p, c_void_p]),
   'fp_track_frame': (c_int, [c_void_p, POINTER(FpTrackArgs), c_void_p]),
   'fp_track_objects': (c_int, [c_void_p, POINTER(FpTrackObjectsArgs), c_void_p]),
+  'fp_register_objects': (c_int, [c_void_p, POINTER(FpRegisterObjectsArgs), c_void_p]),
+  'fp_mask_depth_stats_objects': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
+  'fp_register_hypotheses': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+  'fp_register_rank': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
   'fp_pose_update': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_float, c_float, c_void_p, c_void_p]),
   'fp_pose_update_deepim': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_float, c_float, c_float, c_void_p, c_void_p]),
   'fp_refine_predict': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_double, POINTER(FpRefineCfg), c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),

@@ -1103,6 +1103,214 @@ extern "C" int fp_track_objects(fp_ctx *ctx, const fp_track_objects_args *a, voi
   return track_objects_pass(ctx, a, a->rgb_is_u8 ? a->d_rgb_f : (const float *)a->d_rgb, s);
 }
 
+// ---- FoundationPose.register for several objects of one frame (fp_register_objects) and its pieces -----------------------------------
+static int mask_stats_objects(fp_ctx *ctx, const float *d_depth, const MaskStatsObjs &mo, int H, int W, float min_depth, int32_t *h_stats,
+                              float *h_median, hipStream_t s) {
+  FP_TRY(fp_arena_ensure(ctx, 4096));
+  const size_t mark = ctx->arena.off;
+  int *d_out = (int *)ctx->arena.take((size_t)mo.n * 8 * sizeof(int));
+  FP_REQUIRE(d_out, "mask stats: arena exhausted");
+  int rc;
+  {
+    ProfScope ps(ctx, s, "mask_stats", (double)H * W * mo.n);
+    rc = launch_mask_depth_stats_objects(d_depth, mo, H, W, min_depth, d_out, s);
+  }
+  ctx->arena.off = mark;
+  if (rc != FP_OK) return rc;
+  int host[FP_TRACK_MAX_OBJECTS * 8];
+  FP_CHECK_HIP(hipMemcpyAsync(host, d_out, (size_t)mo.n * 8 * sizeof(int), hipMemcpyDeviceToHost, s));      // ONE copy for all objects
+  FP_CHECK_HIP(hipStreamSynchronize(s));
+  for (int o = 0; o < mo.n; ++o) {
+    for (int i = 0; i < 6; ++i) h_stats[o * 6 + i] = host[o * 8 + i];
+    memcpy(h_median + o, &host[o * 8 + 6], sizeof(float));
+  }
+  return FP_OK;
+}
+
+extern "C" int fp_mask_depth_stats_objects(fp_ctx *ctx, const float *d_depth, const uint8_t *const *d_masks, const int32_t *d_labels,
+                                           const int32_t *labels, int n_obj, int H, int W, float min_depth, int32_t *h_stats, float *h_median,
+                                           void *stream) {
+  FP_REQUIRE(ctx && d_depth && h_stats && h_median && H > 0 && W > 0 && (size_t)H * W <= ((size_t)1 << 30), "fp_mask_depth_stats_objects: bad argument");
+  FP_REQUIRE(n_obj >= 1 && n_obj <= FP_TRACK_MAX_OBJECTS, "fp_mask_depth_stats_objects: n_obj = %d (1 .. %d objects)", n_obj, FP_TRACK_MAX_OBJECTS);
+  FP_REQUIRE(d_labels ? labels != nullptr : d_masks != nullptr, "fp_mask_depth_stats_objects: a label image needs `labels`, otherwise `d_masks`");
+  MaskStatsObjs mo;
+  memset(&mo, 0, sizeof(mo));
+  mo.n = n_obj, mo.labels = d_labels;
+  for (int o = 0; o < n_obj; ++o) {
+    if (d_labels) {
+      mo.label[o] = labels[o];
+    } else {
+      FP_REQUIRE(d_masks[o], "fp_mask_depth_stats_objects: mask %d is null", o);
+      mo.mask[o] = d_masks[o];
+    }
+  }
+  return mask_stats_objects(ctx, d_depth, mo, H, W, min_depth, h_stats, h_median, (hipStream_t)stream);
+}
+
+static void fill_hyp_object(RegHypObjs &ho, int k, const float *rot_grid, int n, int off, const int32_t *st6, float median) {
+  ho.rot_grid[k] = rot_grid, ho.n[k] = n, ho.off[k] = off;
+  ho.cmin[k] = st6[0], ho.cmax[k] = st6[1], ho.rmin[k] = st6[2], ho.rmax[k] = st6[3];
+  ho.median[k] = median;
+}
+
+extern "C" int fp_register_hypotheses(fp_ctx *ctx, const float *const *d_rot_grids, const int *n_hyp, int n_obj, const int32_t *h_stats,
+                                      const float *h_median, const double *K_inv, float *d_poses, void *stream) {
+  FP_REQUIRE(ctx && d_rot_grids && n_hyp && h_stats && h_median && K_inv && d_poses, "fp_register_hypotheses: null argument");
+  FP_REQUIRE(n_obj >= 1 && n_obj <= FP_TRACK_MAX_OBJECTS, "fp_register_hypotheses: n_obj = %d (1 .. %d objects)", n_obj, FP_TRACK_MAX_OBJECTS);
+  RegHypObjs ho;
+  memset(&ho, 0, sizeof(ho));
+  ho.n_obj = n_obj;
+  for (int i = 0; i < 9; ++i) ho.kinv[i] = K_inv[i];
+  int off = 0;
+  for (int o = 0; o < n_obj; ++o) {
+    FP_REQUIRE(n_hyp[o] >= 0 && (n_hyp[o] == 0 || d_rot_grids[o]), "fp_register_hypotheses: object %d has a bad rotation grid", o);
+    fill_hyp_object(ho, o, d_rot_grids[o], n_hyp[o], off, h_stats + o * 6, h_median[o]);
+    off += n_hyp[o];
+  }
+  return launch_register_hypotheses(ho, d_poses, (hipStream_t)stream);
+}
+
+extern "C" int fp_register_rank(fp_ctx *ctx, const float *d_poses, const float *d_scores, const int *n_hyp, int n_obj, const float *model_centers,
+                                float *const *d_poses_out, float *const *d_scores_out, int64_t *const *d_order_out, float *const *d_pose_of_mesh,
+                                void *stream) {
+  FP_REQUIRE(ctx && d_poses && d_scores && n_hyp && model_centers && d_poses_out && d_scores_out && d_order_out && d_pose_of_mesh,
+             "fp_register_rank: null argument");
+  FP_REQUIRE(n_obj >= 1 && n_obj <= FP_TRACK_MAX_OBJECTS, "fp_register_rank: n_obj = %d (1 .. %d objects)", n_obj, FP_TRACK_MAX_OBJECTS);
+  RegRankObjs ro;
+  memset(&ro, 0, sizeof(ro));
+  ro.n_obj = n_obj;
+  int off = 0;
+  for (int o = 0; o < n_obj; ++o) {
+    FP_REQUIRE(n_hyp[o] >= 1 && d_poses_out[o] && d_scores_out[o] && d_order_out[o] && d_pose_of_mesh[o], "fp_register_rank: object %d has a null output or no hypothesis", o);
+    ro.n[o] = n_hyp[o], ro.off[o] = off;
+    ro.poses_out[o] = d_poses_out[o], ro.scores_out[o] = d_scores_out[o], ro.order_out[o] = (long long *)d_order_out[o], ro.pose_of_mesh[o] = d_pose_of_mesh[o];
+    for (int c = 0; c < 3; ++c) ro.cneg[o][c] = -model_centers[o * 3 + c];
+    off += n_hyp[o];
+  }
+  return launch_register_rank(ro, d_poses, d_scores, (hipStream_t)stream);
+}
+
+extern "C" int fp_register_objects(fp_ctx *ctx, fp_register_objects_args *a, void *stream) {
+  FP_REQUIRE(ctx && a, "fp_register_objects: null argument");
+  FP_REQUIRE(a->struct_size == sizeof(fp_register_objects_args), "fp_register_objects: fp_register_objects_args.struct_size = %zu (this library knows %zu)",
+             a->struct_size, sizeof(fp_register_objects_args));
+  FP_REQUIRE(a->refine_net && a->score_net && a->d_rgb && a->d_depth && a->K && a->K_inv && a->refine_cfg && a->objs && a->d_depth_f && a->d_xyz,
+             "fp_register_objects: null field");
+  FP_REQUIRE(a->H > 1 && a->W > 1 && (size_t)a->H * a->W <= ((size_t)1 << 30) && a->iteration >= 0, "fp_register_objects: bad H / W / iteration");
+  FP_REQUIRE(a->n_obj >= 1 && a->n_obj <= FP_TRACK_MAX_OBJECTS, "fp_register_objects: n_obj = %d (1 .. %d objects)", a->n_obj, FP_TRACK_MAX_OBJECTS);
+  FP_REQUIRE(!a->rgb_is_u8 || a->d_rgb_f, "fp_register_objects: a uint8 frame needs the float workspace d_rgb_f");
+  FP_REQUIRE(a->max_pass_hyp >= 0, "fp_register_objects: bad max_pass_hyp");
+  const int n_obj = a->n_obj, cap = a->max_pass_hyp ? a->max_pass_hyp : FP_REGISTER_PASS_HYP;
+  MaskStatsObjs mo;
+  memset(&mo, 0, sizeof(mo));
+  mo.n = n_obj, mo.labels = a->d_labels;
+  for (int o = 0; o < n_obj; ++o) {
+    const fp_register_object &ob = a->objs[o];
+    FP_REQUIRE(ob.mesh && ob.d_rot_grid && ob.d_poses && ob.d_scores && ob.d_order && ob.d_pose_of_mesh, "fp_register_objects: object %d has a null field", o);
+    FP_REQUIRE(ob.mesh_diameter > 0 && ob.n_hyp >= 1, "fp_register_objects: object %d has a bad mesh_diameter / n_hyp", o);
+    FP_REQUIRE(a->d_labels || ob.d_mask, "fp_register_objects: object %d has no mask and there is no label image", o);
+    mo.mask[o] = a->d_labels ? nullptr : ob.d_mask, mo.label[o] = ob.label;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  // the depth prelude of register(), once for all objects: erode -> bilateral (and uint8 -> float colours) in one launch, then the float64
+  // back-projection register() uses (Utils.depth2xyzmap), which overwrites the prelude's float32 one
+  {
+    ProfScope ps(ctx, s, "prelude", (double)a->H * a->W);
+    FP_TRY(launch_depth_prefilter(a->d_depth, a->H, a->W, 0.001f, 0.8f, 100.f, 100.f, 2.f, 100000.f, a->K, 3.0e38f, a->d_depth_f, a->d_xyz,
+                                  a->rgb_is_u8 ? (const uint8_t *)a->d_rgb : nullptr, a->rgb_is_u8 ? a->d_rgb_f : nullptr, s));
+  }
+  FP_TRY(launch_depth2xyz_f64(a->d_depth_f, a->H, a->W, a->K, a->d_xyz, s));
+  const float *rgb_f = a->rgb_is_u8 ? a->d_rgb_f : (const float *)a->d_rgb;
+  // every object's mask reductions: one launch, one copy, the call's one wait for the stream
+  int32_t st[FP_TRACK_MAX_OBJECTS * 6];
+  float med[FP_TRACK_MAX_OBJECTS];
+  FP_TRY(mask_stats_objects(ctx, a->d_depth_f, mo, a->H, a->W, 0.001f, st, med, s));
+  int live[FP_TRACK_MAX_OBJECTS], off[FP_TRACK_MAX_OBJECTS], n_live = 0, N = 0;
+  for (int o = 0; o < n_obj; ++o) {
+    fp_register_object &ob = a->objs[o];
+    for (int i = 0; i < 6; ++i) ob.stats[i] = st[o * 6 + i];
+    ob.median = med[o];
+    ob.registered = ob.stats[5] >= FP_REGISTER_MIN_VALID;
+    for (int r = 0; r < 3; ++r) ob.guess_translation[r] = 0.0;
+    if (ob.stats[4] > 0 && ob.stats[5] > 0) {
+      const double uc = (ob.stats[0] + ob.stats[1]) / 2.0, vc = (ob.stats[2] + ob.stats[3]) / 2.0;
+      for (int r = 0; r < 3; ++r)
+        ob.guess_translation[r] = (__builtin_fma(a->K_inv[r * 3], uc, a->K_inv[r * 3 + 1] * vc) + a->K_inv[r * 3 + 2]) * (double)med[o];
+    }
+    if (ob.registered) live[n_live] = o, off[n_live++] = N, N += ob.n_hyp;
+  }
+  if (n_live == 0) return FP_OK;
+  // network passes: consecutive live objects while the pass stays within `cap` hypotheses; an object of 1 or 2 hypotheses is a pass of its own
+  int pass_of[FP_TRACK_MAX_OBJECTS], n_pass = 0;
+  size_t pass_bytes = 0;
+  for (int k = 0, in_pass = 0; k < n_live; ++k) {
+    const int n = a->objs[live[k]].n_hyp;
+    const bool alone = n <= 2 || (k > 0 && a->objs[live[k - 1]].n_hyp <= 2);
+    if (k == 0 || alone || in_pass + n > cap) ++n_pass, in_pass = 0;
+    pass_of[k] = n_pass - 1;
+    in_pass += n;
+  }
+  fp_object_batch batch[FP_TRACK_MAX_OBJECTS];
+  for (int k = 0; k < n_live; ++k) {
+    const fp_register_object &ob = a->objs[live[k]];
+    batch[k] = fp_object_batch{ob.mesh, rgb_f, a->d_xyz, a->H, a->W, a->K, ob.mesh_diameter, ob.n_hyp};
+  }
+  for (int p = 0, k0 = 0; p < n_pass; ++p) {
+    int k1 = k0, np = 0;
+    while (k1 < n_live && pass_of[k1] == p) np += batch[k1++].n;
+    const size_t need = pass_arena_bytes(np, render_scratch_total(ctx, batch + k0, k1 - k0)) + (size_t)(k1 - k0) * ((size_t)4 << 20);
+    pass_bytes = need > pass_bytes ? need : pass_bytes;
+    k0 = k1;
+  }
+  // the call's own buffers (hypotheses, features, logits, scores) lie in front of the passes' workspace: sized before anything is taken
+  const size_t own = (size_t)N * (16 + 512 + 2) * sizeof(float) + ((size_t)1 << 20);
+  const size_t tail_bytes = (size_t)N * (1024 * 4 + 4 * 8) + ((size_t)2 << 20);
+  FP_TRY(fp_arena_ensure(ctx, own + (pass_bytes > tail_bytes ? pass_bytes : tail_bytes) + ((size_t)1 << 20)));
+  const size_t mark = ctx->arena.off;
+  auto body = [&]() -> int {
+    TAKE(hyp, float, (size_t)N * 16);
+    TAKE(feats, float, (size_t)N * 512);
+    TAKE(logits, float, (size_t)N);
+    TAKE(scores, float, (size_t)N);
+    RegHypObjs ho;
+    memset(&ho, 0, sizeof(ho));
+    ho.n_obj = n_live;
+    for (int i = 0; i < 9; ++i) ho.kinv[i] = a->K_inv[i];
+    for (int k = 0; k < n_live; ++k) fill_hyp_object(ho, k, a->objs[live[k]].d_rot_grid, a->objs[live[k]].n_hyp, off[k], st + live[k] * 6, med[live[k]]);
+    FP_TRY(launch_register_hypotheses(ho, hyp, s));
+    for (int p = 0, k0 = 0; p < n_pass; ++p) {
+      int k1 = k0;
+      while (k1 < n_live && pass_of[k1] == p) ++k1;
+      float *ph = hyp + (size_t)off[k0] * 16;
+      // (every hypothesis of an object has the object's guessed translation: FP_REFINE_SHARED_TRANSLATION holds by construction)
+      FP_TRY(refine_predict_impl(ctx, a->refine_net, batch + k0, k1 - k0, a->refine_cfg, ph, a->iteration, nullptr, nullptr, stream, nullptr,
+                                 FP_REFINE_SHARED_TRANSLATION));
+      for (int k = k0; k < k1; ++k) batch[k].d_geom = a->d_depth_f;         // the scorer reads the filtered depth
+      FP_TRY(score_features_impl(ctx, a->score_net, batch + k0, k1 - k0, a->score_crop_ratio, a->score_normalize_xyz, ph, feats + (size_t)off[k0] * 512,
+                                 512, false, stream));
+      for (int k = k0; k < k1; ++k) {      // att_cross couples the hypotheses of ONE object: a group of its own length per object
+        ScoreTailOut to;
+        to.logits = logits + off[k], to.scores = scores + off[k], to.score_offset = 100.f;
+        FP_TRY(fp_score_tail_impl(ctx, a->score_net, feats + (size_t)off[k] * 512, 512, 1, batch[k].n, to, s));
+      }
+      k0 = k1;
+    }
+    RegRankObjs ro;
+    memset(&ro, 0, sizeof(ro));
+    ro.n_obj = n_live;
+    for (int k = 0; k < n_live; ++k) {
+      const fp_register_object &ob = a->objs[live[k]];
+      ro.n[k] = ob.n_hyp, ro.off[k] = off[k];
+      ro.poses_out[k] = ob.d_poses, ro.scores_out[k] = ob.d_scores, ro.order_out[k] = (long long *)ob.d_order, ro.pose_of_mesh[k] = ob.d_pose_of_mesh;
+      for (int c = 0; c < 3; ++c) ro.cneg[k][c] = -ob.model_center[c];
+    }
+    return launch_register_rank(ro, hyp, scores, s);          // the call's last launch: the results land in the objects' buffers (pinned host: no copy)
+  };
+  int rc = body();
+  ctx->arena.off = mark;
+  return rc;
+}
+
 int conv_ksplit(const ConvArgs &a, int num_cu);      // conv.hip
 
 // ---- building blocks ---------------------------------------------------------------------------------

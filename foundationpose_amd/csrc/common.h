@@ -457,6 +457,32 @@ int launch_depth_prefilter(const float *d, int H, int W, float diff_thres, float
                            float sigmaR, const double *K, float zfar_x, float *out, float *xyz, const unsigned char *rgb_u8, float *rgb_f, hipStream_t s);
 int launch_depth2xyz_f64(const float *d, int H, int W, const double *K, float *xyz, hipStream_t s);
 int launch_mask_depth_stats(const float *d, const unsigned char *mask, int H, int W, float min_depth, int *out6, float *median, hipStream_t s);
+// register.hip: the kernels around the networks of fp_register_objects (n <= FP_TRACK_MAX_OBJECTS objects of one frame)
+struct MaskStatsObjs {           // object o: mask[o] (H*W bytes, non-zero = object) or, with `labels` (H*W int32), the pixels equal to label[o]
+  const unsigned char *mask[FP_TRACK_MAX_OBJECTS];
+  int label[FP_TRACK_MAX_OBJECTS];
+  const int *labels;
+  int n;
+};
+// every object's mask_depth_stats in ONE launch: out8 + 8 o = cmin, cmax, rmin, rmax, n_mask, n_usable, median (float bits), 0
+int launch_mask_depth_stats_objects(const float *d, const MaskStatsObjs &ob, int H, int W, float min_depth, int *out8, hipStream_t s);
+struct RegHypObjs {              // object o: n[o] rotations at rot_grid[o], written to poses + 16 off[o] with the translation guessed from its mask
+  const float *rot_grid[FP_TRACK_MAX_OBJECTS];
+  int n[FP_TRACK_MAX_OBJECTS], off[FP_TRACK_MAX_OBJECTS];
+  int cmin[FP_TRACK_MAX_OBJECTS], cmax[FP_TRACK_MAX_OBJECTS], rmin[FP_TRACK_MAX_OBJECTS], rmax[FP_TRACK_MAX_OBJECTS];
+  float median[FP_TRACK_MAX_OBJECTS];
+  double kinv[9];                // np.linalg.inv(K), row-major
+  int n_obj;
+};
+int launch_register_hypotheses(const RegHypObjs &ob, float *poses, hipStream_t s);
+struct RegRankObjs {             // object o: its n[o] refined poses / scores at off[o], ranked best first into its own buffers
+  int n[FP_TRACK_MAX_OBJECTS], off[FP_TRACK_MAX_OBJECTS];
+  float *poses_out[FP_TRACK_MAX_OBJECTS], *scores_out[FP_TRACK_MAX_OBJECTS], *pose_of_mesh[FP_TRACK_MAX_OBJECTS];
+  long long *order_out[FP_TRACK_MAX_OBJECTS];
+  float cneg[FP_TRACK_MAX_OBJECTS][3];
+  int n_obj;
+};
+int launch_register_rank(const RegRankObjs &ob, const float *poses, const float *scores, hipStream_t s);
 // metrics.hip: ADD / ADD-S / ADDsym of n_poses poses (fp_pose_errors); `slab` holds pose_errors_slab_bytes(...) bytes of partial sums
 size_t pose_errors_slab_bytes(int n_pts, int n_poses, int n_sym);
 int launch_pose_errors(const float *pts, int n_pts, const float *pred, const float *gt, int gt_per_pose, int n_poses, const float *sym,

@@ -45,6 +45,22 @@ def tracking_hypotheses(pose, n, trans_sigma=0.01, rot_sigma_deg=5.0, seed=0):
   return hyp
 
 
+def registration_hypotheses(rot_grids, stats, K):
+  """generate_random_pose_hypo of several objects in one launch (fp_register_hypotheses): `rot_grids` a list of (n_o,4,4) device tensors,
+  `stats` the objects' mask_depth_stats (Utils.mask_depth_stats_objects).  Returns the (sum n_o, 4, 4) hypotheses, object after object."""
+  from ._lib import Context, check, lib, ptr, stream_ptr
+  grids = [g.to(torch.float).contiguous() for g in rot_grids]
+  n = len(grids)
+  dev = grids[0].device
+  st = (ctypes.c_int32 * (6 * n))(*[int(s[k]) for s in stats for k in ('cmin', 'cmax', 'rmin', 'rmax', 'n_mask', 'n_usable')])
+  med = (ctypes.c_float * n)(*[float(s['median']) for s in stats])
+  Kinv = np.ascontiguousarray(np.linalg.inv(K), dtype=np.float64)
+  out = torch.empty((sum(len(g) for g in grids), 4, 4), dtype=torch.float, device=dev)
+  check(lib().fp_register_hypotheses(Context.get(dev).handle, (ctypes.c_void_p * n)(*[g.data_ptr() for g in grids]), (ctypes.c_int * n)(*[len(g) for g in grids]),
+                                     n, st, med, Kinv.ctypes.data, ptr(out), stream_ptr(dev)))
+  return out
+
+
 class MultiObjectTracker:
   """track_one for several objects of ONE camera stream in one call per frame (fp_track_objects, a build extension): the frame is uploaded
   once, its depth prelude runs once, and every refinement iteration is one render, one observed-crop and one network pass over all the
@@ -53,6 +69,7 @@ class MultiObjectTracker:
       tracker = MultiObjectTracker([est_a, est_b, est_c])      # registered FoundationPose instances sharing one PoseRefinePredictor
       poses = tracker.track(rgb, depth, K, iteration=2)        # np (n_obj, 4, 4) float32: row o = what est_o.track_one would return
       tracker.enable_graph(True)                               # one hipGraph per (objects, frame size, camera, iteration)
+      poses = tracker.register(rgb, depth, K, masks)           # the first poses of all objects in one call (fp_register_objects)
 
   Each object's pose is what its estimator's track_one gives, except for the last bits of the network pass: its kernels depend on the
   number of images, so a frame of K objects matches K separate track_one calls only within tolerance (one object:
@@ -190,4 +207,148 @@ class MultiObjectTracker:
     for o, e in enumerate(self.estimators):
       e.pose_last = ws['poses'][o].reshape(1, 4, 4)
       ws['holds'][o] = e.pose_last
+    return out
+
+  def _check_register(self, depth, masks, labels):
+    """The argument checks of register(): (H, W, label image or None, list of masks or None); ValueError names the cause."""
+    ests = self.estimators
+    s0 = ests[0].scorer
+    for i, e in enumerate(ests):
+      if e.scorer.ctx is not s0.ctx or e.scorer.model.handle.value != s0.model.handle.value:
+        raise ValueError(f'MultiObjectTracker.register: estimator {i} does not share estimator 0\'s scorer (scorer.model.handle and scorer.ctx): '
+                         'one network pass needs one ScoreNet')
+    if s0.ctx is not ests[0].refiner.ctx:
+      raise ValueError('MultiObjectTracker.register: the scorer and the refiner live in different contexts (scorer.ctx, refiner.ctx)')
+    H, W = (int(x) for x in depth.shape[:2])
+    is_image = (isinstance(masks, np.ndarray) or torch.is_tensor(masks)) and masks.ndim == 2
+    if is_image:
+      if labels is None:
+        raise ValueError('MultiObjectTracker.register: one (H, W) label image needs labels=[id_0, ...], the id of every object')
+      labels = [int(x) for x in labels]
+      if len(labels) != len(ests):
+        raise ValueError(f'MultiObjectTracker.register: {len(labels)} labels for {len(ests)} objects')
+      if len(set(labels)) != len(labels):
+        raise ValueError(f'MultiObjectTracker.register: a label is repeated in {labels}; each object has its own id')
+      if tuple(masks.shape) != (H, W):
+        raise ValueError(f'MultiObjectTracker.register: the label image is {tuple(masks.shape)}, the depth image {(H, W)}: the shapes differ')
+      return H, W, masks, None, labels
+    if labels is not None:
+      raise ValueError('MultiObjectTracker.register: labels= goes with one (H, W) label image, not with a list of masks')
+    masks = list(masks)
+    if len(masks) != len(ests):
+      raise ValueError(f'MultiObjectTracker.register: {len(masks)} masks for {len(ests)} objects')
+    for o, m in enumerate(masks):
+      if tuple(m.shape) != (H, W):
+        raise ValueError(f'MultiObjectTracker.register: mask {o} is {tuple(m.shape)}, the depth image {(H, W)}: the shapes differ')
+    return H, W, None, masks, None
+
+  def register(self, rgb, depth, K, masks, iteration=5, labels=None, max_pass_hyp=0):
+    """FoundationPose.register for every object of ONE frame in one call (fp_register_objects): np (n_obj, 4, 4) float32, row o = what
+    `self.estimators[o].register(K, rgb, depth, masks[o], iteration=iteration)` returns.  `masks`: a sequence of n_obj (H,W) masks (anything
+    non-zero = object; they may overlap, each object sees its own) or ONE (H,W) integer label image with `labels=[id_0, ...]` (pixel ==
+    id_o: object o) - numpy arrays or device tensors.  The frame goes up once, the depth prelude and the mask reductions of all objects
+    run once, the networks run over the hypotheses of all objects in passes of at most `max_pass_hyp` hypotheses (0: 1008), cut at object
+    boundaries; one host wait (the mask reductions: the validity test needs them) and one at the end.
+
+    Afterwards every registered estimator holds what its own register() leaves: pose_last, poses / scores (best first), best_id, H, W, K,
+    ob_mask; `track` can follow at once.  An object with fewer than 4 usable mask pixels is not registered: its row is eye(4) with the
+    guessed translation (register() returns that as float64; here it is rounded to the array's float32) and its estimator stays as it was.
+    set_seed(0) is called once, as register() does.  No debug canvases: unlike register() at `debug >= 2`, this call writes nothing."""
+    from . import _lib, Utils as U
+    from ._lib import check, lib, stream_ptr
+    ests = self.estimators
+    H, W, label_img, mask_list, labels = self._check_register(depth, masks, labels)
+    U.set_seed(0)
+    for e in ests:
+      if e.glctx is None:
+        e.glctx = U.RasterizeContext()
+    n = len(ests)
+    ctx = ests[0].refiner.ctx
+    dev = ests[0].mesh_tensors['pos'].device
+    is_u8 = (rgb.dtype == np.uint8) if isinstance(rgb, np.ndarray) else (rgb.dtype == torch.uint8)
+    HW = H * W
+    n_lab, n_rgb, n_msk = (HW * 4 if label_img is not None else 0), HW * 3 * (1 if is_u8 else 4), (0 if label_img is not None else n * HW)
+    key = (H, W, is_u8, label_img is not None)
+    ws = self._reg_ws.get(key) if hasattr(self, '_reg_ws') else None
+    if ws is None:
+      if not hasattr(self, '_reg_ws'):
+        self._reg_ws = {}
+      # the frame, the label image or the masks behind one another in ONE buffer: host arrays go up in one copy
+      frame = torch.empty((HW * 4 + n_lab + n_rgb + n_msk,), dtype=torch.uint8, device=dev)
+      o_rgb, o_msk = HW * 4 + n_lab, HW * 4 + n_lab + n_rgb
+      ws = self._reg_ws[key] = dict(
+        frame=frame, host=torch.empty_like(frame, device='cpu').pin_memory(), depth=frame[:HW * 4].view(torch.float).reshape(H, W),
+        labels=frame[HW * 4:o_rgb].view(torch.int32).reshape(H, W) if n_lab else None,
+        rgb=frame[o_rgb:o_msk].reshape(H, W, 3) if is_u8 else frame[o_rgb:o_msk].view(torch.float).reshape(H, W, 3),
+        masks=frame[o_msk:].reshape(n, H, W) if n_msk else None,
+        depth_f=torch.empty((H, W), dtype=torch.float, device=dev), xyz=torch.empty((H, W, 3), dtype=torch.float, device=dev),
+        rgb_f=torch.empty((H, W, 3), dtype=torch.float, device=dev) if is_u8 else None,
+        pose_of_mesh=torch.zeros((n, 4, 4), dtype=torch.float).pin_memory())
+    host_in = all(isinstance(x, np.ndarray) for x in [rgb, depth] + ([label_img] if mask_list is None else mask_list))
+    if host_in:
+      hb = ws['host'].numpy()
+      view = lambda t: hb[t.data_ptr() - ws['frame'].data_ptr():][:t.numel() * t.element_size()].view(
+        {torch.float: np.float32, torch.int32: np.int32, torch.uint8: np.uint8}[t.dtype]).reshape(tuple(t.shape))
+      view(ws['depth'])[:] = depth
+      view(ws['rgb'])[:] = rgb
+      if label_img is not None:
+        view(ws['labels'])[:] = label_img
+      else:
+        mv = view(ws['masks'])
+        for o, m in enumerate(mask_list):
+          np.not_equal(m, 0, out=mv[o].view(bool))
+      ws['frame'].copy_(ws['host'], non_blocking=True)
+    else:
+      up = lambda x: torch.as_tensor(np.ascontiguousarray(x) if isinstance(x, np.ndarray) else x).to(dev)
+      ws['depth'].copy_(up(depth))
+      ws['rgb'].copy_(up(rgb))
+      if label_img is not None:
+        ws['labels'].copy_(up(label_img))
+      else:
+        for o, m in enumerate(mask_list):
+          ws['masks'][o].copy_(up(m) != 0)
+    Kd = np.ascontiguousarray(np.asarray(K.detach().cpu().numpy() if torch.is_tensor(K) else K, dtype=np.float64).reshape(3, 3))
+    Kinv = np.ascontiguousarray(np.linalg.inv(K.detach().cpu().numpy() if torch.is_tensor(K) else K), dtype=np.float64)
+    cfg = ests[0].refiner._c_cfg()
+    meshes = [_lib.device_mesh(ctx, e.mesh_tensors) for e in ests]
+    grids = [e.rot_grid.to(device=dev, dtype=torch.float).contiguous() for e in ests]
+    out_p = [torch.empty((len(g), 4, 4), dtype=torch.float, device=dev) for g in grids]
+    out_s = [torch.empty((len(g),), dtype=torch.float, device=dev) for g in grids]
+    out_o = [torch.empty((len(g),), dtype=torch.int64, device=dev) for g in grids]
+    objs = (_lib.FpRegisterObject * n)()
+    for o, e in enumerate(ests):
+      objs[o].mesh, objs[o].mesh_diameter = meshes[o].handle, float(e.diameter)
+      objs[o].model_center[:] = [float(x) for x in np.asarray(e.model_center, dtype=np.float32)]
+      objs[o].d_mask = ws['masks'][o].data_ptr() if label_img is None else None
+      objs[o].label = labels[o] if labels is not None else 0
+      objs[o].d_rot_grid, objs[o].n_hyp = grids[o].data_ptr(), len(grids[o])
+      objs[o].d_poses, objs[o].d_scores, objs[o].d_order = out_p[o].data_ptr(), out_s[o].data_ptr(), out_o[o].data_ptr()
+      objs[o].d_pose_of_mesh = ws['pose_of_mesh'][o].data_ptr()
+    a = _lib.FpRegisterObjectsArgs()
+    a.struct_size = ctypes.sizeof(a)
+    a.refine_net, a.score_net = ests[0].refiner.model.handle, ests[0].scorer.model.handle
+    a.d_rgb, a.rgb_is_u8, a.d_depth, a.H, a.W = ws['rgb'].data_ptr(), 1 if is_u8 else 0, ws['depth'].data_ptr(), H, W
+    a.K, a.K_inv, a.refine_cfg = Kd.ctypes.data, Kinv.ctypes.data, ctypes.addressof(cfg)
+    scfg = ests[0].scorer.cfg
+    a.score_crop_ratio, a.score_normalize_xyz = float(scfg['crop_ratio']), 1 if scfg['normalize_xyz'] else 0
+    a.iteration, a.n_obj, a.objs = int(iteration), n, ctypes.addressof(objs)
+    a.d_labels = ws['labels'].data_ptr() if label_img is not None else None
+    a.max_pass_hyp = int(max_pass_hyp)
+    a.d_depth_f, a.d_xyz = ws['depth_f'].data_ptr(), ws['xyz'].data_ptr()
+    a.d_rgb_f = ws['rgb_f'].data_ptr() if is_u8 else None
+    check(lib().fp_register_objects(ctx.handle, ctypes.byref(a), stream_ptr(dev)))
+    torch.cuda.current_stream(dev).synchronize()             # the results were written to pinned host memory by the call's last launch
+    out = np.empty((n, 4, 4), dtype=np.float32)
+    for o, e in enumerate(ests):
+      if not objs[o].registered:
+        st = objs[o].stats
+        stats = dict(cmin=st[0], cmax=st[1], rmin=st[2], rmax=st[3], n_mask=st[4], n_usable=st[5], median=np.float32(objs[o].median))
+        out[o] = np.eye(4)
+        out[o, :3, 3] = e.guess_translation(depth=None, mask=None, K=K, stats=stats)
+        continue
+      e.H, e.W, e.K, e.ob_id = H, W, K, None
+      e.ob_mask = mask_list[o] if mask_list is not None else (label_img == labels[o])
+      e.poses, e.scores, e.best_id = out_p[o], out_s[o], out_o[o][0]
+      e.pose_last = e.poses[0]
+      out[o] = ws['pose_of_mesh'][o].numpy()
     return out

@@ -340,6 +340,75 @@ typedef struct {
 } fp_track_objects_args;
 int fp_track_objects(fp_ctx *ctx, const fp_track_objects_args *args, void *stream);
 
+/* ---- FoundationPose.register (src/estimater.py:159-240) for several objects of ONE frame in one call (a build extension; the reference
+ *      registers one object per call).  The frame's depth prelude runs once (erode -> bilateral, :169-170, and the float64 back-projection
+ *      of :198), the mask reductions of every object are one launch (fp_mask_depth_stats_objects), the hypothesis sets are built on the
+ *      device (fp_register_hypotheses), then `iteration` refinement passes and one scoring pass run over the hypotheses of all objects
+ *      (fp_refine_predict_multi_flags with FP_REFINE_SHARED_TRANSLATION, fp_score_predict_features_multi, one score tail per object), and
+ *      one last launch ranks every object's hypotheses (fp_register_rank).  The objects are cut into network passes at object boundaries:
+ *      a pass holds at most max_pass_hyp hypotheses (an object with more gets a pass of its own), and an object with 1 or 2 hypotheses
+ *      always gets a pass of its own (the few-image kernel forms) - so every object's poses and scores are those of
+ *      its own register() call.  Synchronises the stream ONCE, after the mask reductions (register() has the same wait): not capturable. */
+typedef struct {
+  const fp_mesh *mesh;             /* objects may share a mesh */
+  double mesh_diameter;
+  float model_center[3];           /* get_tf_to_centered_mesh() = translation by -model_center */
+  const uint8_t *d_mask;           /* H*W bytes, non-zero = object; NULL when the frame comes with a label image */
+  int32_t label;                   /* label image: the pixels equal to `label` are this object */
+  const float *d_rot_grid;         /* n_hyp*16: the rotation grid (src/estimater.py:106-124); its length differs between objects */
+  int n_hyp;
+  /* device outputs, written only when the object is registered */
+  float *d_poses;                  /* n_hyp*16: refined poses of the centred mesh, best first (self.poses) */
+  float *d_scores;                 /* n_hyp: logits + 100, descending (self.scores); equal scores keep their hypothesis order */
+  int64_t *d_order;                /* n_hyp: hypothesis index of every rank; d_order[0] = best_id */
+  float *d_pose_of_mesh;           /* 16: d_poses[0] @ get_tf_to_centered_mesh(), what register() returns; device or pinned host memory */
+  /* host outputs */
+  int32_t stats[6];                /* cmin, cmax, rmin, rmax, n_mask, n_usable of the mask on the filtered depth (as fp_mask_depth_stats) */
+  float median;                    /* np.median of the usable depths */
+  int registered;                  /* 0: fewer than 4 usable pixels (src/estimater.py:173-177) - nothing ran for this object, the device outputs are
+                                      untouched; the caller returns eye(4) with guess_translation (:184-189) */
+  double guess_translation[3];     /* (inv(K) @ [uc, vc, 1]) * median, zeros for an empty mask or no usable pixel (src/estimater.py:137-156) */
+} fp_register_object;
+typedef struct {
+  size_t struct_size;              /* = sizeof(fp_register_objects_args) */
+  const fp_net *refine_net, *score_net;
+  const void *d_rgb;               /* H*W*3: uint8 (rgb_is_u8) or float [0,255] */
+  int rgb_is_u8;
+  const float *d_depth;            /* H*W raw depth, metres */
+  int H, W;
+  const double *K;                 /* host, 3x3 row-major */
+  const double *K_inv;             /* host, 3x3 row-major: np.linalg.inv(K) as the caller computes it */
+  const fp_refine_cfg *refine_cfg;
+  double score_crop_ratio;
+  int score_normalize_xyz;
+  int iteration;
+  int n_obj;                       /* 1 .. FP_TRACK_MAX_OBJECTS */
+  fp_register_object *objs;        /* host array of n_obj objects (its host outputs are written) */
+  const int32_t *d_labels;         /* H*W label image, or NULL: every object brings its d_mask */
+  int max_pass_hyp;                /* hypotheses per network pass; 0: FP_REGISTER_PASS_HYP */
+  float *d_depth_f, *d_xyz, *d_rgb_f; /* workspace / outputs: filtered depth H*W, xyz_map H*W*3, float colours H*W*3 (uint8 frames only) */
+} fp_register_objects_args;
+#define FP_REGISTER_PASS_HYP 1008  /* 4 x 252: the largest network pass the library's tests cover */
+#define FP_REGISTER_MIN_VALID 4    /* src/estimater.py:185 */
+int fp_register_objects(fp_ctx *ctx, fp_register_objects_args *args, void *stream);
+/* The pieces of fp_register_objects, one launch each.
+ * fp_mask_depth_stats for n_obj objects (src/estimater.py:137-156,173-177 per object) in ONE launch and one copy to the host: object o is
+ * d_masks[o] (host array of n_obj device pointers, H*W bytes each) or, with d_labels (H*W int32) not NULL, the pixels equal to labels[o]
+ * (d_masks may then be NULL).  h_stats (n_obj, 6) and h_median (n_obj) equal fp_mask_depth_stats of each mask bit for bit.  Synchronises. */
+int fp_mask_depth_stats_objects(fp_ctx *ctx, const float *d_depth, const uint8_t *const *d_masks, const int32_t *d_labels, const int32_t *labels,
+                                int n_obj, int H, int W, float min_depth, int32_t *h_stats, float *h_median, void *stream);
+/* generate_random_pose_hypo over guess_translation (src/estimater.py:126-156) for n_obj objects in one launch: d_poses receives, object
+ * after object, d_rot_grids[o][i] with the translation (K_inv @ [(cmin+cmax)/2, (rmin+rmax)/2, 1]) * median in float64 (the dot product as
+ * fma(k0, u, k1 * v) + k2), rounded once to float32.  h_stats (n_obj, 6) / h_median (n_obj): fp_mask_depth_stats_objects' results. */
+int fp_register_hypotheses(fp_ctx *ctx, const float *const *d_rot_grids, const int *n_hyp, int n_obj, const int32_t *h_stats, const float *h_median,
+                           const double *K_inv, float *d_poses, void *stream);
+/* The ranking that ends register() (src/estimater.py:230-237) for n_obj objects in one launch: object o's n_hyp[o] poses / scores lie
+ * behind one another in d_poses / d_scores; its d_poses_out[o] / d_scores_out[o] / d_order_out[o] receive them in stable descending order
+ * of the score (equal scores: the lower hypothesis index first), d_pose_of_mesh[o] (device or pinned host) the best pose @
+ * get_tf_to_centered_mesh() (model_centers: n_obj*3 host floats).  The pointer arrays are host arrays of device pointers. */
+int fp_register_rank(fp_ctx *ctx, const float *d_poses, const float *d_scores, const int *n_hyp, int n_obj, const float *model_centers,
+                     float *const *d_poses_out, float *const *d_scores_out, int64_t *const *d_order_out, float *const *d_pose_of_mesh, void *stream);
+
 /* fp_score_tail with a feature row stride (feat_ld >= 512 floats: 528 reads the [feature | pose] rows below in place) and, optionally
  * (d_scores != NULL), scores = logits + score_offset from the same launch (ScorePredictor.predict: + 100, predict_score.py:209) */
 int fp_score_tail_scores(fp_ctx *ctx, const fp_net *net, const float *d_feats, int feat_ld, int groups, int L, float score_offset, float *d_logits,
