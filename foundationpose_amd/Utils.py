@@ -341,6 +341,34 @@ def compute_mesh_diameter(model_pts=None, mesh=None, n_sample=1000):
   return best
 
 
+def mesh_diameter(model_pts=None, mesh=None, mesh_tensors=None, return_pair=False):
+  """The exact diameter of a model on the device (fp_mesh_diameter): the largest distance between two of its points, over ALL pairs.
+
+  It replaces the random sub-sample of compute_mesh_diameter (src/Utils.py:559-574) where a value that does not depend on numpy's
+  seed is wanted, e.g. against BOP's thresholds, which are defined on the exact diameter of models_info.json.  The points are
+  model_pts (N,3), else mesh.vertices, else mesh_tensors['pos']; numpy or torch, rounded to float32.  Returns a python float, and with
+  return_pair=True also the pair (i, j), i < j, that spans it - among tied pairs the smallest (i, j).  Fewer than two points give 0.0
+  and (0, 0).  The value is read back, so this call synchronises."""
+  if model_pts is None:
+    if mesh is not None:
+      model_pts = np.asarray(mesh.vertices)
+    elif mesh_tensors is not None:
+      model_pts = mesh_tensors['pos']
+    else:
+      raise ValueError('mesh_diameter needs model_pts, mesh or mesh_tensors')
+  dev = _device_of(model_pts)
+  pts = torch.as_tensor(model_pts).to(device=dev, dtype=torch.float).reshape(-1, 3).contiguous()
+  out = torch.empty(1, dtype=torch.float, device=dev)
+  pair = torch.empty(2, dtype=torch.int32, device=dev)
+  ctx = _lib.Context.get(dev)
+  check(lib().fp_mesh_diameter(ctx.handle, ptr(pts) if len(pts) else None, len(pts), ptr(out), ptr(pair), stream_ptr(dev)))
+  d = float(out.item())
+  if return_pair:
+    i, j = pair.tolist()
+    return d, (int(i), int(j))
+  return d
+
+
 def _icosphere_vertices(subdivisions):
   """Unit icosphere: the 12 icosahedron vertices followed, per subdivision, by the normalised
   midpoints of the unique edges (sorted by vertex pair).  trimesh.creation.icosphere

@@ -21,6 +21,7 @@ FP_EINVAL = -1
 FP_ERR_ADD, FP_ERR_ADDS, FP_ERR_ADD_SYM = 1, 2, 4      # fp_pose_errors' `which` bits
 FP_BOP_MSSD, FP_BOP_MSPD = 1, 2                       # fp_pose_errors_bop's `which` bits
 FP_VSD_MAX_TAUS = 32
+FP_MESH_DIAMETER_MAX_POINTS = 1 << 21                     # fp_mesh_diameter's largest n_pts
 
 
 class FpTensor(Structure):
@@ -116,6 +117,7 @@ _PROTOS = {
   'fp_pose_errors_bop': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
   'fp_vsd': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_double, c_void_p, c_int,
                      c_void_p, c_void_p, c_void_p]),
+  'fp_mesh_diameter': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
   'fp_net_create': (c_int, [c_void_p, c_int, POINTER(FpTensor), c_int, c_int, POINTER(c_void_p)]),
   'fp_net_destroy': (c_int, [c_void_p]),
   'fp_net_rot_dim': (c_int, [c_void_p]),

@@ -535,6 +535,21 @@ extern "C" int fp_pose_errors_bop(fp_ctx *ctx, const float *d_pts, int n_pts, co
   return rc;
 }
 
+extern "C" int fp_mesh_diameter(fp_ctx *ctx, const float *d_pts, int n_pts, float *d_out_diameter, int32_t *d_out_pair, void *stream) {
+  FP_REQUIRE(ctx && d_out_diameter, "fp_mesh_diameter: null argument");
+  FP_REQUIRE(n_pts >= 0 && n_pts <= FP_MESH_DIAMETER_MAX_POINTS, "fp_mesh_diameter: n_pts %d (0 .. %d)", n_pts, FP_MESH_DIAMETER_MAX_POINTS);
+  FP_REQUIRE(d_pts || n_pts == 0, "fp_mesh_diameter: d_pts null with n_pts %d", n_pts);
+  const size_t bytes = mesh_diameter_slab_bytes(n_pts);
+  FP_TRY(fp_arena_ensure(ctx, bytes + 4096));
+  const size_t mark = ctx->arena.off;
+  void *slab = ctx->arena.take(bytes);
+  FP_REQUIRE(slab, "fp_mesh_diameter: arena exhausted");
+  // the slab is consumed by the finishing launch on the same stream before anything else takes it
+  const int rc = launch_mesh_diameter(d_pts, n_pts, slab, d_out_diameter, d_out_pair, (hipStream_t)stream);
+  ctx->arena.off = mark;
+  return rc;
+}
+
 // poses per render chunk of fp_vsd: their depth images (and those of their ground truth, one per pose) within this many bytes
 static const size_t kVsdDepthBudget = (size_t)512 << 20;
 

@@ -487,6 +487,10 @@ int launch_register_rank(const RegRankObjs &ob, const float *poses, const float 
 size_t pose_errors_slab_bytes(int n_pts, int n_poses, int n_sym);
 int launch_pose_errors(const float *pts, int n_pts, const float *pred, const float *gt, int gt_per_pose, int n_poses, const float *sym,
                        int n_sym, int which, double *slab, float *add, float *adds, float *add_sym, hipStream_t s);
+// mesh.hip: exact diameter of n_pts points and the pair that spans it (fp_mesh_diameter); `slab` holds mesh_diameter_slab_bytes(n_pts)
+// bytes of per-workgroup candidates
+size_t mesh_diameter_slab_bytes(int n_pts);
+int launch_mesh_diameter(const float *pts, int n_pts, void *slab, float *out, int32_t *pair, hipStream_t s);
 // metrics.hip: MSSD / MSPD of n_poses poses (fp_pose_errors_bop); `slab` holds bop_errors_slab_bytes(...) bytes of tile maxima
 size_t bop_errors_slab_bytes(int n_pts, int n_poses, int n_sym);
 int launch_bop_errors(const float *pts, int n_pts, const float *pred, const float *gt, int gt_per_pose, int n_poses, const float *sym,

@@ -8,6 +8,7 @@ rotation + guessed translation as float64, track before register -> RuntimeError
 the HIP library; with `dist_group` set the hypotheses are sharded over the ranks of one node
 (foundationpose_amd/dist.py) - the reference is single-GPU only.
 """
+import copy
 import ctypes
 import logging
 import os
@@ -44,13 +45,13 @@ def _voxel_centroids(points, normals, voxel):
 class FoundationPose:
   def __init__(self, model_pts, model_normals, symmetry_tfs=None, mesh=None, scorer: ScorePredictor = None,
                refiner: PoseRefinePredictor = None, glctx=None, debug=0, debug_dir='/tmp/foundationpose_amd_debug/',
-               dist_group=None):
+               dist_group=None, diameter=None):
     self.gt_pose = None
     self.ignore_normal_flip = True
     self.debug, self.debug_dir = debug, debug_dir
     os.makedirs(debug_dir, exist_ok=True)
     self.dist_group = dist_group
-    self.reset_object(model_pts, model_normals, symmetry_tfs=symmetry_tfs, mesh=mesh)
+    self.reset_object(model_pts, model_normals, symmetry_tfs=symmetry_tfs, mesh=mesh, diameter=diameter)
     self.make_rotation_grid(min_n_views=40, inplane_step=60)
     self.glctx = glctx
     self.scorer = ScorePredictor() if scorer is None else scorer
@@ -58,15 +59,27 @@ class FoundationPose:
     self.pose_last = None          # pose of the centred mesh, kept for track_one
 
   # ------------------------------------------------------------------ object set-up (cold path)
-  def reset_object(self, model_pts, model_normals, symmetry_tfs=None, mesh=None):
-    """src/estimater.py:44-78: centre the mesh on its bounding-box centre, measure it, upload it."""
+  def reset_object(self, model_pts, model_normals, symmetry_tfs=None, mesh=None, diameter=None):
+    """src/estimater.py:44-78: centre the mesh on its bounding-box centre, measure it, upload it.
+
+    diameter (not in the reference): None measures the object as the reference does, compute_mesh_diameter over 10000 vertices drawn
+    with numpy's global generator - for a larger model the value, and with it every crop window, depends on numpy's seed; a number is
+    used as given (the models_info.json value of a BOP model, in metres); 'exact' is Utils.mesh_diameter, every vertex pair on the
+    device."""
     lo, hi = mesh.vertices.min(axis=0), mesh.vertices.max(axis=0)
     self.model_center = (lo + hi) / 2
     self.mesh_ori = mesh.copy()
     centred = mesh.copy()
     centred.vertices = centred.vertices - self.model_center.reshape(1, 3)
     self.mesh = centred
-    self.diameter = U.compute_mesh_diameter(model_pts=centred.vertices, n_sample=10000)
+    if diameter is None:
+      self.diameter = U.compute_mesh_diameter(model_pts=centred.vertices, n_sample=10000)
+    elif isinstance(diameter, str):
+      if diameter != 'exact':
+        raise ValueError(f"diameter must be None, a number or 'exact', got {diameter!r}")
+      self.diameter = U.mesh_diameter(model_pts=centred.vertices)
+    else:
+      self.diameter = float(diameter)
     self.vox_size = max(self.diameter / 20.0, 0.003)
     self.dist_bin, self.angle_bin = self.vox_size / 2, 20
     logging.info(f'self.diameter:{self.diameter}, vox_size:{self.vox_size}')
@@ -83,6 +96,15 @@ class FoundationPose:
     # tracking workspaces (and their captured graphs) hold the previous object's mesh handle and centre: none survives a new object
     self._track_ws = {}
     logging.info("reset done")
+
+  def instance(self):
+    """Another instance of this object in the same image: the same mesh tensors, rotation grid, networks and measurements, its own
+    `pose_last / poses / scores / best_id` (all None) and tracking workspaces.  What several instances of one BOP object in one image
+    are registered and tracked through (tracking.MultiObjectTracker takes one estimator per instance)."""
+    other = copy.copy(self)
+    other._track_ws = {}
+    other.pose_last = other.poses = other.scores = other.best_id = None
+    return other
 
   def get_tf_to_centered_mesh(self):
     tf = torch.eye(4, dtype=torch.float, device='cuda')

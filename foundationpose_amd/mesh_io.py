@@ -1,15 +1,59 @@
-"""Mesh / intrinsics ingestion for the estimator: Wavefront OBJ -> SimpleMesh with
-angle-weighted vertex normals and vertex colours (`v x y z r g b`) or a uv-mapped texture array."""
+"""Mesh / intrinsics ingestion for the estimator: Wavefront OBJ (with its .mtl texture) and Stanford PLY (ascii and
+binary, the form of the BOP object models) -> SimpleMesh with angle-weighted vertex normals and vertex colours or a uv-mapped
+texture array.  Images are decoded with PIL, imported only where one is decoded."""
+import logging
+import os
+
 import numpy as np
 
 from .synthetic import SimpleMesh, TextureVisual
 
 
+def _read_image(path):
+  """An image file as (H,W,3) uint8 RGB."""
+  from PIL import Image
+  with Image.open(path) as im:
+    return np.array(im.convert('RGB'), dtype=np.uint8)
+
+
+def _mtl_texture(obj_path, mtllib, usemtl):
+  """The decoded `map_Kd` image of material `usemtl` (None: the library's first material) of the .mtl file `mtllib` beside the OBJ, or
+  None - with a logging line - when the library, the material, its map or the image file is missing."""
+  base = os.path.dirname(os.path.abspath(obj_path))
+  mtl_path = os.path.join(base, mtllib)
+  if not os.path.isfile(mtl_path):
+    logging.info(f'{obj_path}: material library {mtllib} not found, no texture')
+    return None
+  maps, order, cur = {}, [], None
+  with open(mtl_path) as f:
+    for line in f:
+      p = line.split()
+      if not p or p[0].startswith('#'):
+        continue
+      if p[0] == 'newmtl' and len(p) > 1:
+        cur = p[1]
+        order.append(cur)
+      elif p[0] == 'map_Kd' and cur is not None and len(p) > 1:
+        maps[cur] = p[-1]                     # (options such as -s 1 1 1 come before the file name)
+  name = usemtl if usemtl in order else (order[0] if order else None)
+  if name is None or name not in maps:
+    logging.info(f'{obj_path}: material {usemtl!r} of {mtllib} has no map_Kd, no texture')
+    return None
+  img_path = os.path.join(os.path.dirname(mtl_path), maps[name].replace('\\', '/'))
+  if not os.path.isfile(img_path):
+    logging.info(f'{obj_path}: texture {maps[name]} of material {name!r} not found, no texture')
+    return None
+  return _read_image(img_path)
+
+
 def load_obj(path, texture_image=None):
   """Triangles and polygons (fan-triangulated); `v/vt/vn` index forms; negative (relative) indices.
   Vertices are split per (v, vt) pair when texture coordinates are present, so faces index uv directly
-  (make_mesh_tensors uses `mesh.faces` as `uv_idx`, src/Utils.py:115)."""
+  (make_mesh_tensors uses `mesh.faces` as `uv_idx`, src/Utils.py:115).  The texture is `texture_image` when given, else the `map_Kd`
+  image of the material the first `usemtl` names (or the first material) in the `mtllib` file beside the OBJ - the YCB
+  textured.obj + .mtl + .png form; a missing library or image leaves the mesh untextured."""
   v, vc, vt, corners = [], [], [], []
+  mtllib = usemtl = None
   with open(path) as f:
     for line in f:
       p = line.split()
@@ -20,6 +64,10 @@ def load_obj(path, texture_image=None):
         vc.append([float(x) for x in p[4:7]] if len(p) >= 7 else None)
       elif p[0] == 'vt':
         vt.append([float(p[1]), float(p[2]) if len(p) > 2 else 0.0])
+      elif p[0] == 'mtllib' and mtllib is None and len(p) > 1:
+        mtllib = line.split(None, 1)[1].strip()
+      elif p[0] == 'usemtl' and usemtl is None and len(p) > 1:
+        usemtl = p[1]
       elif p[0] == 'f':
         idx = []
         for tok in p[1:]:
@@ -45,6 +93,8 @@ def load_obj(path, texture_image=None):
         face.append(remap[key])
       faces.append(face)
     mesh = SimpleMesh(np.asarray(verts), np.asarray(faces))
+    if texture_image is None and mtllib is not None:
+      texture_image = _mtl_texture(path, mtllib, usemtl)
     if texture_image is not None:
       mesh.visual = TextureVisual(uv=np.asarray(uvs, dtype=np.float64), image=np.asarray(texture_image))
     return mesh
@@ -64,6 +114,238 @@ def save_obj(mesh, path):
       f.write('v %.9g %.9g %.9g%s\n' % (p[0], p[1], p[2], c))
     for t in mesh.faces:
       f.write('f %d %d %d\n' % (t[0] + 1, t[1] + 1, t[2] + 1))
+
+
+# ---------------------------------------------------------------------------------------------- Stanford PLY
+_PLY_TYPES = {'char': 'i1', 'uchar': 'u1', 'short': 'i2', 'ushort': 'u2', 'int': 'i4', 'uint': 'u4', 'float': 'f4', 'double': 'f8',
+              'int8': 'i1', 'uint8': 'u1', 'int16': 'i2', 'uint16': 'u2', 'int32': 'i4', 'uint32': 'u4', 'float32': 'f4', 'float64': 'f8'}
+
+
+def _ply_header(path, f):
+  """-> (format, [(element name, count, [property, ...])], texture file name or None); a property is (name, type) or
+  (name, count type, item type) for a list."""
+  if f.readline().strip() != b'ply':
+    raise ValueError(f'{path}: not a PLY file')
+  fmt, elements, texture = None, [], None
+  while True:
+    raw = f.readline()
+    if not raw:
+      raise ValueError(f'{path}: the header has no end_header')
+    p = raw.decode('ascii', 'replace').split()
+    if not p:
+      continue
+    if p[0] == 'end_header':
+      break
+    if p[0] == 'format':
+      fmt = p[1]
+    elif p[0] == 'comment' and len(p) > 2 and p[1] == 'TextureFile':
+      texture = raw.decode('ascii', 'replace').split(None, 2)[2].strip()
+    elif p[0] == 'element':
+      elements.append((p[1], int(p[2]), []))
+    elif p[0] == 'property':
+      if not elements:
+        raise ValueError(f'{path}: a property before any element')
+      try:
+        prop = (p[4], _PLY_TYPES[p[2]], _PLY_TYPES[p[3]]) if p[1] == 'list' else (p[2], _PLY_TYPES[p[1]])
+      except (KeyError, IndexError):
+        raise ValueError(f'{path}: unknown property declaration {" ".join(p)!r}') from None
+      elements[-1][2].append(prop)
+  if fmt not in ('ascii', 'binary_little_endian', 'binary_big_endian'):
+    raise ValueError(f'{path}: unknown PLY format {fmt!r}')
+  return fmt, elements, texture
+
+
+def _ply_element_binary(path, buf, off, name, count, props, order):
+  """One element of a binary body -> ({scalar property: (count,) array}, {list property: list of arrays}, new offset)."""
+  short = ValueError(f'{path}: the body ends inside element {name!r} (truncated file)')
+  lists = [p for p in props if len(p) == 3]
+  if not lists:
+    dt = np.dtype([(p[0], order + p[1]) for p in props])
+    if off + count * dt.itemsize > len(buf):
+      raise short
+    rec = np.frombuffer(buf, dtype=dt, count=count, offset=off)
+    return {p[0]: rec[p[0]] for p in props}, {}, off + count * dt.itemsize
+  if count == 0:
+    return {p[0]: np.zeros(0, p[1]) for p in props if len(p) == 2}, {p[0]: [] for p in lists}, off
+  # every row of one length (a mesh of triangles, the usual case): the rows are one record array; else row by row
+  if len(lists) == 1:
+    ct = np.dtype(order + lists[0][1])
+    if off + ct.itemsize > len(buf):
+      raise short
+    n0 = int(np.frombuffer(buf, dtype=ct, count=1, offset=off + sum(np.dtype(p[1]).itemsize for p in props[:props.index(lists[0])]))[0])
+    dt = np.dtype([(p[0], order + p[1]) if len(p) == 2 else (p[0], [('n', order + p[1]), ('i', order + p[2], (n0,))]) for p in props])
+    if off + count * dt.itemsize <= len(buf):
+      rec = np.frombuffer(buf, dtype=dt, count=count, offset=off)
+      if (rec[lists[0][0]]['n'] == n0).all():
+        return ({p[0]: rec[p[0]] for p in props if len(p) == 2}, {lists[0][0]: list(rec[lists[0][0]]['i'])}, off + count * dt.itemsize)
+  scal = {p[0]: np.zeros(count, p[1]) for p in props if len(p) == 2}
+  out = {p[0]: [] for p in lists}
+  for r in range(count):
+    for p in props:
+      if len(p) == 2:
+        dt = np.dtype(order + p[1])
+        if off + dt.itemsize > len(buf):
+          raise short
+        scal[p[0]][r] = np.frombuffer(buf, dtype=dt, count=1, offset=off)[0]
+        off += dt.itemsize
+      else:
+        ct, it = np.dtype(order + p[1]), np.dtype(order + p[2])
+        if off + ct.itemsize > len(buf):
+          raise short
+        n = int(np.frombuffer(buf, dtype=ct, count=1, offset=off)[0])
+        off += ct.itemsize
+        if n < 0 or off + n * it.itemsize > len(buf):
+          raise short
+        out[p[0]].append(np.frombuffer(buf, dtype=it, count=n, offset=off))
+        off += n * it.itemsize
+  return scal, out, off
+
+
+def _ply_element_ascii(path, lines, pos, name, count, props):
+  if pos + count > len(lines):
+    raise ValueError(f'{path}: the body ends inside element {name!r} (truncated file)')
+  scal = {p[0]: np.zeros(count, p[1]) for p in props if len(p) == 2}
+  out = {p[0]: [] for p in props if len(p) == 3}
+  try:
+    if not out:
+      rows = np.array([ln.split()[:len(props)] for ln in lines[pos:pos + count]], dtype=np.float64).reshape(count, len(props))
+      for c, p in enumerate(props):
+        scal[p[0]] = rows[:, c].astype(p[1])
+    else:
+      for r in range(count):
+        tok, k = lines[pos + r].split(), 0
+        for p in props:
+          if len(p) == 2:
+            scal[p[0]][r] = float(tok[k])
+            k += 1
+          else:
+            n = int(tok[k])
+            if len(tok) < k + 1 + n:
+              raise IndexError
+            out[p[0]].append(np.array(tok[k + 1:k + 1 + n], dtype=np.float64).astype(p[2]))
+            k += 1 + n
+  except (ValueError, IndexError):
+    raise ValueError(f'{path}: malformed row in element {name!r}') from None
+  return scal, out, pos + count
+
+
+def load_ply(path, texture_image=None):
+  """Stanford PLY -> SimpleMesh: `format ascii 1.0`, `binary_little_endian 1.0` and `binary_big_endian 1.0`; the scalar types char ..
+  double and their int8 .. float64 aliases.  Element `vertex`: x y z (required); nx ny nz -> vertex_normals (else angle-weighted,
+  computed when first read); red green blue [alpha] -> (V,4) uint8 colours; texture_u texture_v (also u v, s t) -> uv.  Element `face`:
+  the list property vertex_indices / vertex_index, polygons fan-triangulated as load_obj does.  Other elements and other properties are
+  skipped.  With uv, the texture is `texture_image` when given, else the file a `comment TextureFile NAME` header line names, beside the
+  PLY; a mesh without either shows its vertex colours, or SimpleMesh's grey.  ValueError for a malformed header, a body that ends
+  early, or a vertex index out of range."""
+  with open(path, 'rb') as f:
+    fmt, elements, texture = _ply_header(path, f)
+    body = f.read()
+  data = {}
+  if fmt == 'ascii':
+    lines = [ln for ln in body.decode('ascii', 'replace').splitlines() if ln.strip()]
+    pos = 0
+    for name, count, props in elements:
+      scal, lst, pos = _ply_element_ascii(path, lines, pos, name, count, props)
+      data.setdefault(name, (scal, lst))
+  else:
+    off, order = 0, '<' if fmt == 'binary_little_endian' else '>'
+    for name, count, props in elements:
+      scal, lst, off = _ply_element_binary(path, body, off, name, count, props, order)
+      data.setdefault(name, (scal, lst))
+  if 'vertex' not in data or not all(k in data['vertex'][0] for k in 'xyz'):
+    raise ValueError(f'{path}: no vertex element with x, y, z')
+  vs = data['vertex'][0]
+  verts = np.stack([vs['x'], vs['y'], vs['z']], 1).astype(np.float64)
+  faces = []
+  if 'face' in data:
+    lst = data['face'][1]
+    rows = lst.get('vertex_indices', lst.get('vertex_index'))
+    if rows is None:
+      raise ValueError(f'{path}: the face element has no vertex_indices / vertex_index list')
+    if rows and all(len(r) == 3 for r in rows):
+      faces = np.asarray(rows, dtype=np.int64).reshape(-1, 3)
+    else:
+      faces = np.asarray([(r[0], r[k], r[k + 1]) for r in rows for k in range(1, len(r) - 1)], dtype=np.int64).reshape(-1, 3)
+  faces = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+  if len(faces) and (faces.min() < 0 or faces.max() >= len(verts)):
+    raise ValueError(f'{path}: a face indexes a vertex outside 0 .. {len(verts) - 1}')
+  normals = np.stack([vs['nx'], vs['ny'], vs['nz']], 1).astype(np.float64) if all(k in vs for k in ('nx', 'ny', 'nz')) else None
+  colors = None
+  if all(k in vs for k in ('red', 'green', 'blue')):
+    chans = [vs['red'], vs['green'], vs['blue'], vs['alpha'] if 'alpha' in vs else None]
+    to_u8 = lambda c: np.clip(c * 255.0 if c.dtype.kind == 'f' else c, 0, 255).astype(np.uint8)
+    colors = np.stack([np.full(len(verts), 255, np.uint8) if c is None else to_u8(c) for c in chans], 1)
+  uv = next((np.stack([vs[a], vs[b]], 1).astype(np.float64) for a, b in (('texture_u', 'texture_v'), ('u', 'v'), ('s', 't'))
+             if a in vs and b in vs), None)
+  mesh = SimpleMesh(verts, faces, vertex_normals=normals, vertex_colors=colors)
+  if uv is not None:
+    if texture_image is None and texture is not None:
+      tex_path = os.path.join(os.path.dirname(os.path.abspath(path)), texture)
+      if os.path.isfile(tex_path):
+        texture_image = _read_image(tex_path)
+      else:
+        logging.info(f'{path}: texture file {texture} not found, no texture')
+    if texture_image is not None:
+      mesh.visual = TextureVisual(uv=uv, image=np.asarray(texture_image))
+  return mesh
+
+
+def save_ply(mesh, path, binary=True, texture_file=None, normals=True):
+  """Write what load_ply reads: float32 positions (and normals), then uv (float32) for a textured mesh - with `comment TextureFile
+  <texture_file>` when a name is given; the image itself is not written - or uchar red green blue alpha for a coloured one, and the
+  triangles as `list uchar int vertex_indices`.  binary=True: binary_little_endian; else ascii with 9 significant digits, which a
+  float32 survives unchanged."""
+  v = np.asarray(mesh.vertices, dtype=np.float32)
+  cols = [('x', v[:, 0]), ('y', v[:, 1]), ('z', v[:, 2])]
+  if normals:
+    n = np.asarray(mesh.vertex_normals, dtype=np.float32)
+    cols += [('nx', n[:, 0]), ('ny', n[:, 1]), ('nz', n[:, 2])]
+  if hasattr(mesh.visual, 'uv'):
+    uv = np.asarray(mesh.visual.uv, dtype=np.float32)
+    cols += [('texture_u', uv[:, 0]), ('texture_v', uv[:, 1])]
+  elif getattr(mesh.visual, 'vertex_colors', None) is not None:
+    c = np.asarray(mesh.visual.vertex_colors, dtype=np.uint8)
+    if c.shape[1] == 3:
+      c = np.concatenate([c, np.full((len(c), 1), 255, np.uint8)], 1)
+    cols += [(k, c[:, i]) for i, k in enumerate(('red', 'green', 'blue', 'alpha'))]
+  faces = np.asarray(mesh.faces, dtype=np.int32).reshape(-1, 3)
+  names = {'f': 'float', 'u': 'uchar'}
+  head = ['ply', 'format %s 1.0' % ('binary_little_endian' if binary else 'ascii')]
+  if texture_file is not None and hasattr(mesh.visual, 'uv'):
+    head.append(f'comment TextureFile {texture_file}')
+  head += [f'element vertex {len(v)}'] + [f'property {names[a.dtype.kind]} {k}' for k, a in cols]
+  head += [f'element face {len(faces)}', 'property list uchar int vertex_indices', 'end_header']
+  with open(path, 'wb') as f:
+    f.write(('\n'.join(head) + '\n').encode('ascii'))
+    if binary:
+      rec = np.zeros(len(v), dtype=[(k, '<' + a.dtype.str[1:]) for k, a in cols])
+      for k, a in cols:
+        rec[k] = a
+      f.write(rec.tobytes())
+      fr = np.zeros(len(faces), dtype=[('n', 'u1'), ('i', '<i4', (3,))])
+      fr['n'], fr['i'] = 3, faces
+      f.write(fr.tobytes())
+    else:
+      fmt = lambda x: '%.9g' % x if isinstance(x, (float, np.floating)) else '%d' % x
+      for r in range(len(v)):
+        f.write((' '.join(fmt(a[r]) for _, a in cols) + '\n').encode('ascii'))
+      for t in faces:
+        f.write(('3 %d %d %d\n' % tuple(t)).encode('ascii'))
+
+
+def load_mesh(path, scale=1.0):
+  """A model file by its extension (.obj, .ply; any case), its vertices multiplied by `scale` - BOP models are in millimetres:
+  scale=1e-3 (src/datareader.py:322)."""
+  ext = os.path.splitext(path)[1].lower()
+  if ext == '.obj':
+    mesh = load_obj(path)
+  elif ext == '.ply':
+    mesh = load_ply(path)
+  else:
+    raise ValueError(f'{path}: unknown model file extension {ext!r} (.obj or .ply)')
+  if scale != 1.0:
+    mesh.vertices = mesh.vertices * float(scale)
+  return mesh
 
 
 def load_intrinsics(path):

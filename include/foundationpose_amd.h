@@ -190,6 +190,18 @@ int fp_vsd(fp_ctx *ctx, const fp_mesh *mesh, const float *d_depth_test, int dept
            const float *d_gt, int gt_per_pose, int n_poses, double diameter, double delta, const double *h_taus, int n_taus, float *d_err,
            int32_t *d_counts, void *stream);
 
+#define FP_MESH_DIAMETER_MAX_POINTS (1 << 21)
+/* Exact diameter of a point set: max over i < j of |p_i - p_j| over ALL pairs, in place of the reference's maximum over a random
+ * sample of the points (compute_mesh_diameter, src/Utils.py:559-574, `np.random.choice`), whose value changes with numpy's seed once
+ * a model has more points than the sample.  d_pts (n_pts,3) float32, device, finite.  d_out_diameter: 1 float32, device.  d_out_pair:
+ * 2 int32, device, or null: the pair (i, j), i < j, that spans the diameter.  Upper-triangle pairs of 1024-point tiles, one workgroup
+ * each; the squared distance is dx*dx + dy*dy + dz*dz in fp32 in that order and the square root is taken once, of the maximum.  The
+ * result is deterministic and independent of the execution order: among pairs whose fp32 squared distances tie, the smallest (i, j) in
+ * lexicographic order is returned.  No atomics; per-workgroup candidates go to the context's arena and a second launch folds them.
+ * Nothing synchronises.  n_pts < 2 gives diameter 0 and pair (0, 0).  FP_EINVAL: a null ctx or d_out_diameter, d_pts null with
+ * n_pts > 0, n_pts < 0 or above FP_MESH_DIAMETER_MAX_POINTS (2^21: 2.1 M tile pairs, 34 MB of arena). */
+int fp_mesh_diameter(fp_ctx *ctx, const float *d_pts, int n_pts, float *d_out_diameter, int32_t *d_out_pair, void *stream);
+
 /* ---- networks -------------------------------------------------------------------------------- */
 typedef struct {
   const char *name;    /* reference state_dict key, e.g. "encodeA.0.net.0.weight" */
