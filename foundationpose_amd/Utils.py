@@ -672,3 +672,127 @@ def symmetry_tfs_from_info(info, rot_angle_discrete=5):
       T[:3, 3] = cont['offset']
       tfs.append(T)
   return np.stack(tfs)
+
+
+# ---------------------------------------------------------------------------------------------- masks and visibility from poses
+SCENE_INFO_KEYS = ('px_count_all', 'px_count_valid', 'px_count_visib', 'visib_fract', 'bbox_obj', 'bbox_visib')     # scene_gt_info.json's
+_SCENE_OCCLUDERS = {'depth': _lib.FP_SCENE_OCC_DEPTH, 'instances': _lib.FP_SCENE_OCC_INSTANCES,
+                    'both': _lib.FP_SCENE_OCC_DEPTH | _lib.FP_SCENE_OCC_INSTANCES}
+_SCENE_WANT = ('mask', 'mask_visib', 'owner', 'depth', 'info')
+
+
+def scene_info_rows(rows):
+  """fp_scene_instances' int rows (n, FP_SCENE_INFO_COLS) -> one dict per instance with scene_gt_info.json's keys (bop_toolkit
+  calc_gt_info.py): px_count_all, px_count_valid, px_count_visib, visib_fract = px_count_visib / px_count_all in float64 (0.0 for an
+  object that renders nowhere), bbox_obj and bbox_visib as [x, y, w, h] with w = x1 - x0 + 1 ([-1, -1, -1, -1] for an empty set: told by
+  the COUNT, a corner at -1 is legal on a padded canvas), and px_count_in_frame.  Host only: Python ints and floats, ready for json."""
+  rows = np.asarray(rows)
+  if rows.ndim != 2 or rows.shape[1] != _lib.FP_SCENE_INFO_COLS:
+    raise ValueError(f'scene_info_rows takes (n, {_lib.FP_SCENE_INFO_COLS}) integer rows, got {rows.shape}')
+
+  def box(r, c, count):
+    if count == 0:
+      return [-1, -1, -1, -1]
+    x0, y0, x1, y1 = (int(x) for x in r[c:c + 4])
+    return [x0, y0, x1 - x0 + 1, y1 - y0 + 1]
+  out = []
+  for r in rows:
+    n_all, n_valid = int(r[_lib.FP_SCENE_INFO_PX_COUNT_ALL]), int(r[_lib.FP_SCENE_INFO_PX_COUNT_VALID])
+    n_visib, n_in = int(r[_lib.FP_SCENE_INFO_PX_COUNT_VISIB]), int(r[_lib.FP_SCENE_INFO_PX_COUNT_IN_FRAME])
+    out.append(dict(px_count_all=n_all, px_count_valid=n_valid, px_count_visib=n_visib,
+                    visib_fract=float(np.float64(n_visib) / np.float64(n_all)) if n_all > 0 else 0.0,
+                    bbox_obj=box(r, _lib.FP_SCENE_INFO_BBOX_OBJ, n_all), bbox_visib=box(r, _lib.FP_SCENE_INFO_BBOX_VISIB, n_visib),
+                    px_count_in_frame=n_in))
+  return out
+
+
+def _scene_pad(pad, H, W):
+  """`pad` of scene_instances as (pad_x, pad_y): an int, an (x, y) pair, or 'bop' = (W, H), calc_gt_info's canvas of three frames a side."""
+  if isinstance(pad, str):
+    if pad != 'bop':
+      raise ValueError(f"pad must be an int, an (x, y) pair or 'bop', got {pad!r}")
+    return int(W), int(H)
+  if np.ndim(pad) == 0:
+    return int(pad), int(pad)
+  px, py = pad
+  return int(px), int(py)
+
+
+def _scene_occluders(occluders, has_depth):
+  """`occluders` of scene_instances as FP_SCENE_OCC_* bits: None = 'depth' if a depth image is given, plus 'instances'; a name, a
+  sequence of names, or the bits themselves."""
+  if occluders is None:
+    return _lib.FP_SCENE_OCC_INSTANCES | (_lib.FP_SCENE_OCC_DEPTH if has_depth else 0)
+  if isinstance(occluders, (int, np.integer)):
+    return int(occluders)
+  names = [occluders] if isinstance(occluders, str) else list(occluders)
+  unknown = [o for o in names if o not in _SCENE_OCCLUDERS]
+  if unknown:
+    raise ValueError(f'unknown occluder(s) {unknown}: choose from {sorted(_SCENE_OCCLUDERS)}')
+  bits = 0
+  for o in names:
+    bits |= _SCENE_OCCLUDERS[o]
+  return bits
+
+
+def scene_instances(K, H, W, meshes, poses, depth=None, occluders=None, delta=BOP19_VSD_DELTA, pad=0,
+                    want=('mask', 'mask_visib', 'owner', 'depth', 'info'), glctx=None):
+  """Which pixels every object instance of a frame covers, which of them are visible, and how much of the object that is, from the
+  instances' poses (fp_scene_instances; bop_toolkit calc_gt_masks.py / calc_gt_info.py, visibility rule 'bop19'), on the device.
+
+  meshes: one mesh or mesh_tensors dict per instance, or a single one shared by all, in the frame the poses refer to; poses (n,4,4);
+  depth (H,W) metres, 0 = missing, or None.  occluders: 'depth' (the depth image hides what lies more than delta behind it),
+  'instances' (the instances hide one another), 'both' (or a sequence of names), or None = both when a depth image is given, else 'instances'.  pad: pixels of
+  canvas around the frame, an int, an (x, y) pair or 'bop' (= (W, H), bop_toolkit's): the part of an object outside the image then
+  counts in px_count_all and bbox_obj.  The canvas must fit the rasteriser: at most 6553 pixels wide and 255 of its strips high (a
+  strip holds about 15 000 pixels), about 3.8 M pixels - 'bop' fits frames up to 640 x 480; give a smaller pad for larger ones.  Returns a dict with the entries named in `want`:
+    'mask', 'mask_visib'  (n,H,W) uint8 device tensors, 0 / 255 as the BOP mask files hold them (`> 0` for bool)
+    'owner'               (H,W) int32: the instance in front at the pixel (the smaller index at equal depth), -1 where none renders
+    'depth'               (H,W) float32: the depth of that instance, 0 where none
+    'info'                a list of n dicts (scene_info_rows); this entry alone waits for the device.
+  A visible pixel lies inside the image, so px_count_visib == (mask_visib[i] > 0).sum() and visib_fract is BOP's."""
+  unknown = [w for w in want if w not in _SCENE_WANT]
+  if unknown:
+    raise ValueError(f'unknown output(s) {unknown}: choose from {list(_SCENE_WANT)}')
+  H, W = int(H), int(W)
+  ctx = _ctx_of(glctx, _device_of(poses))
+  dev = torch.device('cuda', ctx.device_index)
+  P = torch.as_tensor(poses).to(device=dev, dtype=torch.float).reshape(-1, 4, 4).contiguous()
+  n = len(P)
+  if isinstance(meshes, dict) or not isinstance(meshes, (list, tuple)):
+    meshes = [meshes] * n
+  if len(meshes) == 1 and n != 1:
+    meshes = list(meshes) * n
+  if len(meshes) != n:
+    raise ValueError(f'{len(meshes)} meshes for {n} poses: give one per instance, or one for all')
+  tensors = {}                                      # one upload per mesh object, however many instances share it
+  for m in meshes:
+    if id(m) not in tensors:
+      tensors[id(m)] = _lib.device_mesh(ctx, m if isinstance(m, dict) else make_mesh_tensors(m))
+  handles = (ctypes.c_void_p * max(n, 1))(*[tensors[id(m)].handle for m in meshes])
+  D = None
+  if depth is not None:
+    D = torch.as_tensor(depth).to(device=dev, dtype=torch.float).contiguous()
+    if tuple(D.shape) != (H, W):
+      raise ValueError(f'depth is {tuple(D.shape)}, the frame {(H, W)}')
+  bits = _scene_occluders(occluders, D is not None)
+  pad_x, pad_y = _scene_pad(pad, H, W)
+  new = lambda name, shape, dtype: torch.empty(shape, dtype=dtype, device=dev) if name in want else None
+  mask, visib = new('mask', (n, H, W), torch.uint8), new('mask_visib', (n, H, W), torch.uint8)
+  owner, dcomp = new('owner', (H, W), torch.int32), new('depth', (H, W), torch.float)
+  rows = new('info', (n, _lib.FP_SCENE_INFO_COLS), torch.int32)
+  Kd, Kp = k_ptr(K)
+  check(lib().fp_scene_instances(ctx.handle, handles, ptr(P), n, Kp, H, W, pad_x, pad_y, ptr(D), bits, float(delta), ptr(mask), ptr(visib),
+                                 ptr(owner), ptr(dcomp), ptr(rows), stream_ptr(dev)))
+  out = {}
+  if mask is not None:
+    out['mask'] = mask
+  if visib is not None:
+    out['mask_visib'] = visib
+  if owner is not None:
+    out['owner'] = owner
+  if dcomp is not None:
+    out['depth'] = dcomp
+  if rows is not None:
+    out['info'] = scene_info_rows(rows.cpu().numpy())
+  return out

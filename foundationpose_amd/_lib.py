@@ -22,6 +22,12 @@ FP_ERR_ADD, FP_ERR_ADDS, FP_ERR_ADD_SYM = 1, 2, 4      # fp_pose_errors' `which`
 FP_BOP_MSSD, FP_BOP_MSPD = 1, 2                       # fp_pose_errors_bop's `which` bits
 FP_VSD_MAX_TAUS = 32
 FP_MESH_DIAMETER_MAX_POINTS = 1 << 21                     # fp_mesh_diameter's largest n_pts
+FP_SCENE_MAX_INSTANCES = 1024                             # fp_scene_instances
+FP_SCENE_OCC_DEPTH, FP_SCENE_OCC_INSTANCES = 1, 2         # its `occluders` bits
+FP_SCENE_INFO_COLS = 12                                   # int32 columns of a d_info row:
+FP_SCENE_INFO_PX_COUNT_ALL, FP_SCENE_INFO_PX_COUNT_VALID, FP_SCENE_INFO_PX_COUNT_VISIB, FP_SCENE_INFO_PX_COUNT_IN_FRAME = 0, 1, 2, 3
+FP_SCENE_INFO_BBOX_OBJ, FP_SCENE_INFO_BBOX_VISIB = 4, 8   # x0, y0, x1, y1 each
+SCENE_DEPTH_BUDGET = 512 << 20                            # bytes of depth layers per render chunk of fp_scene_instances (api.hip)
 
 
 class FpTensor(Structure):
@@ -118,6 +124,8 @@ _PROTOS = {
   'fp_vsd': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_double, c_void_p, c_int,
                      c_void_p, c_void_p, c_void_p]),
   'fp_mesh_diameter': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+  'fp_scene_instances': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_double, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, c_void_p]),
   'fp_net_create': (c_int, [c_void_p, c_int, POINTER(FpTensor), c_int, c_int, POINTER(c_void_p)]),
   'fp_net_destroy': (c_int, [c_void_p]),
   'fp_net_rot_dim': (c_int, [c_void_p]),

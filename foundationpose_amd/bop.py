@@ -9,6 +9,9 @@ METRES.  Images are decoded with PIL, imported only where one is read.
     rows = run_bop(root, 'test', models, refiner, scorer)            # one MultiObjectTracker.register per image (and group of 8)
     write_results('est_dataset-test.csv', rows)
     print(evaluate_results(root, 'test', models, rows))                # AR_VSD, AR_MSSD, AR_MSPD, AR
+
+A home-made dataset that has scene_gt.json but no masks and no scene_gt_info.json gets them from annotate_scene (the device's
+Utils.scene_instances in place of bop_toolkit's calc_gt_masks.py / calc_gt_info.py) before run_bop.
 """
 import csv
 import glob
@@ -44,6 +47,7 @@ class BopModels:
     self._info = {int(k): v for k, v in _read_json(os.path.join(self.models_dir, 'models_info.json')).items()}
     self.obj_ids = sorted(self._info)
     self._meshes = {}
+    self._tensors = {}
 
   def info(self, obj_id):
     return self._info[int(obj_id)]
@@ -58,6 +62,15 @@ class BopModels:
       from .mesh_io import load_mesh
       self._meshes[obj_id] = load_mesh(self.path(obj_id), scale=1e-3)
     return self._meshes[obj_id]
+
+  def mesh_tensors(self, obj_id):
+    """make_mesh_tensors of mesh(obj_id) (the model as the file holds it, in metres, not centred), built once and kept: one upload
+    per model however many images render it."""
+    obj_id = int(obj_id)
+    if obj_id not in self._tensors:
+      from .mesh_tensors import make_mesh_tensors
+      self._tensors[obj_id] = make_mesh_tensors(self.mesh(obj_id))
+    return self._tensors[obj_id]
 
   def diameter(self, obj_id):
     """models_info's exact diameter, in metres."""
@@ -148,6 +161,80 @@ class BopScene:
     return (m if m.ndim == 2 else m[..., 0]) > 0
 
 
+# ---------------------------------------------------------------------------------------------- masks and gt_info from the ground truth
+def _render_gt(scene, im_id, models, delta=0.015, pad='bop', want=('mask', 'mask_visib', 'info')):
+  """Utils.scene_instances over the ground-truth instances of one image, as bop_toolkit annotates: the recorded depth is the only
+  occluder, the models are rendered as the files hold them (metres, NOT centred: the poses are model-frame poses).  Host arrays: mask /
+  mask_visib (n,H,W) bool, info (list of dicts)."""
+  from . import Utils as U
+  gts = scene.gt(im_id)
+  depth = scene.depth(im_id)
+  H, W = depth.shape
+  out = U.scene_instances(scene.K(im_id), H, W, [models.mesh_tensors(g['obj_id']) for g in gts], np.stack([g['pose'] for g in gts]).astype(np.float32),
+                          depth=depth, occluders='depth', delta=delta, pad=pad, want=want)
+  return {k: (v.cpu().numpy() > 0 if k in ('mask', 'mask_visib') else v) for k, v in out.items()}
+
+
+def write_gt_info(scene_dir, info_by_image):
+  """scene_gt_info.json from {im_id: [dict per ground-truth instance, in gt order]} (keys as Utils.scene_info_rows gives them; the BOP
+  keys are written, px_count_in_frame is not one)."""
+  from .Utils import SCENE_INFO_KEYS
+  doc = {str(int(i)): [{k: e[k] for k in SCENE_INFO_KEYS if k in e} for e in entries] for i, entries in sorted(info_by_image.items())}
+  with open(os.path.join(str(scene_dir), 'scene_gt_info.json'), 'w') as f:
+    json.dump(doc, f)
+
+
+def annotate_scene(scene_dir, models, im_ids=None, delta=0.015, pad='bop', write=('mask', 'mask_visib', 'gt_info'), overwrite=False):
+  """Write what a recorded scene with ground-truth poses still lacks to be evaluated: `mask/{im:06d}_{gt:06d}.png` and
+  `mask_visib/..png` (8-bit, 0 / 255) of every ground-truth instance and `scene_gt_info.json` (px_count_all, px_count_valid,
+  px_count_visib, visib_fract, bbox_obj, bbox_visib per instance, one list per image in gt order) - bop_toolkit's calc_gt_masks.py and
+  calc_gt_info.py, on the device: one Utils.scene_instances call per image, the recorded depth image as the occluder (delta: BOP's
+  15 mm), pad='bop' so that the part of an object outside the image counts in px_count_all.  Deviation from the toolkit: masks, counts
+  and boxes come from ONE render on the padded canvas, so px_count_visib == count(mask_visib) always.
+  pad: as Utils.scene_instances takes it; 'bop' fits frames up to 640 x 480, a larger frame needs a smaller pad (an (x, y) pair), and
+  what lies beyond the canvas is then not counted in px_count_all.
+  im_ids=None: every image of scene_gt.json.  Existing files are kept unless overwrite=True, and an image that lacks nothing is not
+  rendered; an existing scene_gt_info.json keeps its entries of images outside im_ids either way.  Returns {im_id: [info dicts]}: as
+  computed (px_count_in_frame included), or as scene_gt_info.json holds them for an image that was complete."""
+  unknown = [w for w in write if w not in ('mask', 'mask_visib', 'gt_info')]
+  if unknown:
+    raise ValueError(f"unknown item(s) {unknown} in write: choose from 'mask', 'mask_visib', 'gt_info'")
+  from PIL import Image
+  if not isinstance(models, BopModels):
+    models = BopModels(models)
+  scene = BopScene(scene_dir)
+  im_ids = sorted(scene._gt) if im_ids is None else [int(i) for i in im_ids]
+  info_path = os.path.join(scene.scene_dir, 'scene_gt_info.json')
+  mask_path = lambda kind, im_id, g: os.path.join(scene.scene_dir, kind, f"{im_id:06d}_{g['gt_id']:06d}.png")
+  out = {}
+  for im_id in im_ids:
+    gts = scene.gt(im_id)
+    if not gts:
+      out[im_id] = []
+      continue
+    have = scene.gt_info(im_id)
+    if not overwrite and ('gt_info' not in write or (have is not None and len(have) == len(gts))) and \
+       all(os.path.isfile(mask_path(k, im_id, g)) for k in ('mask', 'mask_visib') if k in write for g in gts):
+      if have is not None and len(have) == len(gts):
+        out[im_id] = have                         # nothing to write for this image: it is not rendered, its entries are the file's
+        continue
+    r = _render_gt(scene, im_id, models, delta=delta, pad=pad)
+    out[im_id] = r['info']
+    for kind in ('mask', 'mask_visib'):
+      if kind not in write:
+        continue
+      os.makedirs(os.path.join(scene.scene_dir, kind), exist_ok=True)
+      for g in gts:
+        p = mask_path(kind, im_id, g)
+        if overwrite or not os.path.isfile(p):
+          Image.fromarray(r[kind][g['gt_id']].astype(np.uint8) * 255).save(p)
+  if 'gt_info' in write and (overwrite or not os.path.isfile(info_path)):
+    doc = {} if scene._gt_info is None else dict(scene._gt_info)
+    doc.update(out)
+    write_gt_info(scene.scene_dir, doc)
+  return out
+
+
 def _scene_dirs(dataset_dir, split):
   out = {}
   for p in sorted(glob.glob(os.path.join(str(dataset_dir), split, '*'))):
@@ -236,11 +323,14 @@ def build_estimators(models, obj_ids, refiner, scorer, diameter='info'):
   return out
 
 
-def image_instances(scene, im_id, targets, mask_source='gt_visib'):
+def image_instances(scene, im_id, targets, mask_source='gt_visib', models=None, pad='bop'):
   """The instances run_bop registers in one image, in order: [(obj_id, mask bool (H,W))].  targets: the image's targets.
   mask_source='gt_visib': for every target the `mask_visib` of the object's counted ground-truth instances (visib_fract >= 0.1), in
   gt_id order, inst_count at most; a callable (scene, im_id) -> [(obj_id, mask, det_score)]: the inst_count best-scored detections of
-  the object.  An instance without a mask file, or with an empty mask, is left out."""
+  the object.  An instance without a mask file, or with an empty mask, is left out.
+  mask_source='gt_render' (needs `models`, a BopModels): as 'gt_visib', but an instance without a mask file gets the mask_visib that
+  annotate_scene would write (Utils.scene_instances on the image's ground truth, the recorded depth as the occluder), and without
+  scene_gt_info.json the instances are counted by the computed visib_fract; `pad` as annotate_scene takes it."""
   out = []
   if callable(mask_source):
     dets = list(mask_source(scene, im_id))
@@ -248,13 +338,26 @@ def image_instances(scene, im_id, targets, mask_source='gt_visib'):
       mine = sorted([d for d in dets if int(d[0]) == t['obj_id']], key=lambda d: -float(d[2]))[:t['inst_count']]
       out += [(t['obj_id'], np.asarray(d[1]) > 0) for d in mine if d[1] is not None and np.any(d[1])]
     return out
-  if mask_source != 'gt_visib':
-    raise ValueError(f"mask_source must be 'gt_visib' or a callable, got {mask_source!r}")
+  if mask_source not in ('gt_visib', 'gt_render'):
+    raise ValueError(f"mask_source must be 'gt_visib', 'gt_render' or a callable, got {mask_source!r}")
   gts, counted = scene.gt(im_id), scene.counted(im_id)
+  rendered = None
+  if mask_source == 'gt_render':
+    if models is None:
+      raise ValueError("mask_source='gt_render' needs models=BopModels(...)")
+    if not isinstance(models, BopModels):
+      models = BopModels(models)
+    missing = [g for g in gts if not os.path.isfile(os.path.join(scene.scene_dir, 'mask_visib', f"{int(im_id):06d}_{g['gt_id']:06d}.png"))]
+    if gts and (missing or scene.gt_info(im_id) is None):
+      rendered = _render_gt(scene, im_id, models, pad=pad, want=('mask_visib', 'info'))
+      if scene.gt_info(im_id) is None:
+        counted = [r['visib_fract'] >= VISIB_GT_MIN for r in rendered['info']]
   for t in targets:
     mine = [g for g, c in zip(gts, counted) if c and g['obj_id'] == t['obj_id']][:t['inst_count']]
     for g in mine:
       m = scene.mask(im_id, g['gt_id'], 'mask_visib')
+      if m is None and rendered is not None:
+        m = rendered['mask_visib'][g['gt_id']]
       if m is not None and m.any():
         out.append((t['obj_id'], m))
   return out
@@ -268,7 +371,7 @@ def _by_image(targets):
 
 
 def run_bop(dataset_dir, split, models, refiner, scorer, targets=None, iteration=5, mask_source='gt_visib', diameter='info',
-            max_objects=None, estimators=None):
+            max_objects=None, estimators=None, pad='bop'):
   """Register every target of a BOP split: rows for write_results (pose float32 (4,4) in metres, score = the registration's best
   score, time = the wall time of the image's registrations, the same on every row of an image as BOP asks).
 
@@ -277,7 +380,7 @@ def run_bop(dataset_dir, split, models, refiner, scorer, targets=None, iteration
   ones); every instance of an image gets `FoundationPose.instance()` of its object's estimator, and the image's instances
   (image_instances) are registered by MultiObjectTracker(...).register(rgb, depth, K, masks, iteration) in groups of at most
   max_objects (None: FP_TRACK_MAX_OBJECTS), the image handed over as the numpy arrays BopScene reads.  An instance with fewer than 4
-  usable depth pixels in its mask gets register()'s fallback pose with score 0."""
+  usable depth pixels in its mask gets register()'s fallback pose with score 0.  pad: the canvas of mask_source='gt_render'."""
   from ._lib import FP_TRACK_MAX_OBJECTS
   from .tracking import MultiObjectTracker
   if not isinstance(models, BopModels):
@@ -293,7 +396,7 @@ def run_bop(dataset_dir, split, models, refiner, scorer, targets=None, iteration
     if scene_id not in scenes:
       scenes[scene_id] = BopScene(dirs[scene_id])
     scene = scenes[scene_id]
-    inst = image_instances(scene, im_id, ts, mask_source)
+    inst = image_instances(scene, im_id, ts, mask_source, models=models, pad=pad)
     if not inst:
       continue
     rgb, depth, K = scene.color(im_id), scene.depth(im_id), scene.K(im_id)

@@ -605,6 +605,112 @@ extern "C" int fp_vsd(fp_ctx *ctx, const fp_mesh *mesh, const float *d_depth_tes
   return rc;
 }
 
+// instances per render chunk of fp_scene_instances: their depth layers on the padded canvas within this many bytes
+static const size_t kSceneDepthBudget = (size_t)512 << 20;
+
+extern "C" int fp_scene_instances(fp_ctx *ctx, const fp_mesh *const *meshes, const float *d_poses, int n_inst, const double *K, int H, int W,
+                                  int pad_x, int pad_y, const float *d_depth_test, int occluders, double delta, uint8_t *d_mask,
+                                  uint8_t *d_mask_visib, int32_t *d_owner, float *d_depth, int32_t *d_info, void *stream) {
+  FP_REQUIRE(ctx && K, "fp_scene_instances: null ctx or K");
+  FP_REQUIRE(n_inst >= 0 && n_inst <= FP_SCENE_MAX_INSTANCES, "fp_scene_instances: n_inst %d outside 0..%d", n_inst, FP_SCENE_MAX_INSTANCES);
+  FP_REQUIRE(n_inst == 0 || (meshes && d_poses), "fp_scene_instances: null meshes or d_poses with n_inst %d", n_inst);
+  for (int i = 0; i < n_inst; ++i) FP_REQUIRE(meshes[i], "fp_scene_instances: meshes[%d] is null", i);
+  FP_REQUIRE(H >= 1 && W >= 1, "fp_scene_instances: image %dx%d", H, W);
+  FP_REQUIRE(pad_x >= 0 && pad_y >= 0, "fp_scene_instances: negative pad (%d, %d)", pad_x, pad_y);
+  FP_REQUIRE(occluders != 0 && (occluders & ~(FP_SCENE_OCC_DEPTH | FP_SCENE_OCC_INSTANCES)) == 0,
+             "fp_scene_instances: occluders = %d (FP_SCENE_OCC_DEPTH | FP_SCENE_OCC_INSTANCES, at least one)", occluders);
+  FP_REQUIRE(!(occluders & FP_SCENE_OCC_DEPTH) || d_depth_test, "fp_scene_instances: FP_SCENE_OCC_DEPTH with d_depth_test null");
+  FP_REQUIRE(delta >= 0, "fp_scene_instances: delta %g must be >= 0", delta);
+  const long long Wc_ll = (long long)W + 2LL * pad_x, Hc_ll = (long long)H + 2LL * pad_y;
+  FP_REQUIRE(Wc_ll * 10 <= 64 * 1024, "fp_scene_instances: canvas width %lld (W %d + 2 pad_x %d) is above the rasteriser's 6553: reduce pad_x",
+             Wc_ll, W, pad_x);
+  FP_REQUIRE(Hc_ll <= 65535 && Hc_ll * Wc_ll <= ((long long)1 << 30), "fp_scene_instances: canvas %lldx%lld: reduce pad_y", Hc_ll, Wc_ll);
+  hipStream_t s = (hipStream_t)stream;
+  const int Hc = (int)Hc_ll, Wc = (int)Wc_ll;
+  const size_t pxf = (size_t)H * W, pxc = (size_t)Hc * Wc;
+  if (n_inst == 0) {
+    if (d_owner) FP_CHECK_HIP(hipMemsetAsync(d_owner, 0xff, pxf * sizeof(int32_t), s));
+    if (d_depth) FP_CHECK_HIP(hipMemsetAsync(d_depth, 0, pxf * sizeof(float), s));
+    return FP_OK;
+  }
+  double Kc[9];
+  for (int i = 0; i < 9; ++i) Kc[i] = K[i];
+  Kc[2] = K[2] + (double)pad_x, Kc[5] = K[5] + (double)pad_y;
+  const bool occ_inst = (occluders & FP_SCENE_OCC_INSTANCES) != 0, occ_depth = (occluders & FP_SCENE_OCC_DEPTH) != 0;
+  const bool want_masks = d_mask || d_mask_visib || d_info;
+  const bool need_min = d_owner || d_depth || (occ_inst && (d_mask_visib || d_info));
+  if (!want_masks && !need_min) return FP_OK;
+  const int chunk = (int)std::min<size_t>((size_t)n_inst, std::max<size_t>(1, kSceneDepthBudget / (pxc * sizeof(float))));
+  // the minimum over every chunk first, then the masks (two renders), only where a visibility test reads that minimum
+  const bool two_pass = occ_inst && (d_mask_visib || d_info) && chunk < n_inst;
+  // one scratch for every render of the call: the largest run of instances of one mesh inside a chunk
+  size_t rs = 0;
+  for (int b0 = 0; b0 < n_inst; b0 += chunk)
+    for (int r0 = b0, e = std::min(n_inst, b0 + chunk); r0 < e;) {
+      int r1 = r0 + 1;
+      while (r1 < e && meshes[r1] == meshes[r0]) ++r1;
+      if (!render_fits(r1 - r0, meshes[r0]->d.V, meshes[r0]->d.F, Hc, Wc, ctx->num_cu)) {
+        if (pad_x || pad_y)
+          fp_set_error("fp_scene_instances: the canvas of %dx%d pixels (frame %dx%d, pad_x %d, pad_y %d) needs more strips than the rasteriser "
+                       "has: reduce pad_x / pad_y", Wc, Hc, W, H, pad_x, pad_y);
+        else
+          fp_set_error("fp_scene_instances: a frame of %dx%d pixels needs more strips than the rasteriser has", W, H);
+        return FP_EINVAL;
+      }
+      rs = std::max(rs, render_scratch_bytes(r1 - r0, meshes[r0]->d.V, meshes[r0]->d.F, Hc, Wc, ctx->num_cu));
+      r0 = r1;
+    }
+  const size_t layer_bytes = pxc * sizeof(float) * chunk, acc_bytes = (size_t)n_inst * FP_SCENE_INFO_COLS * sizeof(int);
+  FP_TRY(fp_arena_ensure(ctx, layer_bytes + acc_bytes + pxf * 8 + rs + 8 * 256 + 4096));
+  const size_t mark = ctx->arena.off;
+  auto run = [&]() -> int {
+    float *layers = (float *)ctx->arena.take(layer_bytes);
+    int *acc = d_info ? (int *)ctx->arena.take(acc_bytes) : nullptr;
+    // the running minimum lives in the caller's d_depth / d_owner; a call that needs it over several chunks without asking for it borrows the arena
+    float *dmin = d_depth ? d_depth : (need_min && chunk < n_inst ? (float *)ctx->arena.take(pxf * sizeof(float)) : nullptr);
+    if (!layers || (d_info && !acc) || (need_min && chunk < n_inst && !dmin)) {
+      fp_set_error("fp_scene_instances: arena exhausted");
+      return FP_ENOMEM;
+    }
+    if (acc) FP_TRY(launch_scene_info_init(acc, n_inst, s));
+    // render_with_arena_scratch takes the render scratch behind these buffers and releases it when the launches are queued
+    auto render_chunk_layers = [&](int b0, int n) -> int {
+      for (int r0 = b0; r0 < b0 + n;) {
+        int r1 = r0 + 1;
+        while (r1 < b0 + n && meshes[r1] == meshes[r0]) ++r1;
+        RenderArgs a;
+        FP_TRY(fill_render(a, meshes[r0], d_poses + (size_t)r0 * 16, r1 - r0, Kc, Hc, Wc, nullptr, Hc, Wc));
+        a.depth = layers + (size_t)(r0 - b0) * pxc;
+        FP_TRY(render_with_arena_scratch(ctx, a, s));
+        r0 = r1;
+      }
+      return FP_OK;
+    };
+    auto pass = [&](bool do_min, bool do_masks) -> int {
+      for (int b0 = 0; b0 < n_inst; b0 += chunk) {
+        const int n = std::min(chunk, n_inst - b0);
+        FP_TRY(render_chunk_layers(b0, n));
+        SceneLaunch l;
+        l.layers = layers, l.dt = d_depth_test, l.n = n, l.i0 = b0, l.H = H, l.W = W, l.pad_x = pad_x, l.pad_y = pad_y;
+        l.do_min = do_min, l.do_masks = do_masks, l.first = b0 == 0, l.occ_depth = occ_depth, l.occ_inst = occ_inst;
+        l.K = K, l.delta = delta, l.dmin = dmin, l.owner = d_owner, l.mask = d_mask, l.mask_visib = d_mask_visib, l.acc = acc;
+        FP_TRY(launch_scene_instances(ctx, l, s));
+      }
+      return FP_OK;
+    };
+    if (two_pass) {
+      FP_TRY(pass(true, false));
+      FP_TRY(pass(false, true));
+    } else {
+      FP_TRY(pass(need_min, want_masks));
+    }
+    return acc ? launch_scene_info_finish(acc, n_inst, d_info, s) : FP_OK;
+  };
+  const int rc = run();
+  ctx->arena.off = mark;
+  return rc;
+}
+
 extern "C" int fp_pose_update(fp_ctx *ctx,const float *d_poseA, const float *d_trans, const float *d_rot, int N, int rot_dim,
                               int trans_rep_tanh, const float *tn, float rot_normalizer, float trans_scale, float *d_pose_out,
                               void *stream) {

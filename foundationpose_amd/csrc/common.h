@@ -426,6 +426,7 @@ RenderPlan render_plan(int N, int V, int F, int Ho, int Wo, int num_cu);
 int render_chunk(int N, int V, int F, int Ho, int Wo, int num_cu);
 size_t render_scratch_bytes(int N, int V, int F, int Ho, int Wo, int num_cu);
 int launch_render(fp_ctx *ctx, const RenderArgs &a, hipStream_t s);      // a.scratch: render_scratch_bytes(a.N, ...) bytes
+bool render_fits(int N, int V, int F, int Ho, int Wo, int num_cu);       // launch_render takes this output size (strips per hypothesis, pixels per strip)
 int launch_crop_window_tf(const float *poses, int N, const double *K, double crop_ratio, double diameter, int ow, int oh, float *tf,
                           float *bbox, hipStream_t s);
 // fp_track_objects (hypothesis b = object b, n <= FP_TRACK_MAX_OBJECTS): several objects' one-launch renders (render_kernel<1, true>) as
@@ -500,3 +501,21 @@ int launch_bop_errors(const float *pts, int n_pts, const float *pred, const floa
 int launch_vsd_count(const float *dt, size_t dt_stride, const float *dg, size_t dg_stride, const float *de, int n_poses, int H, int W,
                      const double *K, double diameter, double delta, const double *taus, int n_taus, unsigned *counts, hipStream_t s);
 int launch_vsd_finish(const unsigned *counts, int n_poses, int n_taus, float *err, int *counts_out, hipStream_t s);
+// scene.hip: one pass over the depth layers of a chunk of instances (fp_scene_instances): loop A (do_min) keeps the smallest positive
+// depth and its instance per frame pixel in dmin / owner (read first unless `first`), loop B (do_masks) writes the chunk's masks and adds
+// its counts and boxes into acc (n_inst x FP_SCENE_INFO_COLS of the whole call: launch_scene_info_init before the first chunk,
+// launch_scene_info_finish after the last).  With occ_inst and do_masks but not do_min, dmin holds the finished minimum.
+struct SceneLaunch {
+  const float *layers, *dt;
+  int n, i0, H, W, pad_x, pad_y;
+  int do_min, do_masks, first, occ_depth, occ_inst;
+  const double *K;
+  double delta;
+  float *dmin;
+  int32_t *owner;
+  uint8_t *mask, *mask_visib;
+  int *acc;
+};
+int launch_scene_instances(fp_ctx *ctx, const SceneLaunch &l, hipStream_t s);
+int launch_scene_info_init(int *acc, int n_inst, hipStream_t s);
+int launch_scene_info_finish(const int *acc, int n_inst, int32_t *info, hipStream_t s);

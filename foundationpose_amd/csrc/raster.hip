@@ -929,6 +929,13 @@ static int launch_render_one(fp_ctx *ctx, const RenderArgs &a_in, int plan_n, hi
   return FP_OK;
 }
 
+// does launch_render take N hypotheses of this mesh at this output size (the strip limits launch_render_one checks)
+bool render_fits(int N, int V, int F, int Ho, int Wo, int num_cu) {
+  if (Ho < 1 || Wo < 1 || (size_t)Wo * 10 > 64 * 1024 || F >= (1 << 30)) return false;
+  const RenderPlan pl = render_plan(render_chunk(N, V, F, Ho, Wo, num_cu), V, F, Ho, Wo, num_cu);
+  return pl.S <= RB_MAXS && pl.strip_rows * Wo <= 65535;
+}
+
 bool render_objects_form(int V, int F, int Ho, int Wo, int num_cu) {
   const RenderPlan pl = render_plan(1, V, F, Ho, Wo, num_cu);
   return pl.solo && pl.S <= RB_MAXS && pl.strip_rows * Wo <= 65535;

@@ -152,6 +152,7 @@ class MultiObjectTracker:
     is_np = isinstance(rgb, np.ndarray)
     is_u8 = (rgb.dtype == np.uint8) if is_np else (rgb.dtype == torch.uint8)
     H, W = depth.shape[:2]
+    self._last_frame = (int(H), int(W), K)
     ws = self._workspace(iteration, (H, W), is_u8, K)
     # the frame as in FoundationPose._run_frame: ONE host-to-device copy through pinned memory, or one device copy of a packed [depth | rgb]
     if is_np or not torch.is_tensor(depth) or not depth.is_cuda:
@@ -258,6 +259,7 @@ class MultiObjectTracker:
     from ._lib import check, lib, stream_ptr
     ests = self.estimators
     H, W, label_img, mask_list, labels = self._check_register(depth, masks, labels)
+    self._last_frame = (H, W, K)
     U.set_seed(0)
     for e in ests:
       if e.glctx is None:
@@ -352,3 +354,22 @@ class MultiObjectTracker:
       e.pose_last = e.poses[0]
       out[o] = ws['pose_of_mesh'][o].numpy()
     return out
+
+  def instance_masks(self, depth=None, K=None, occluders=None, delta=0.015):
+    """Which pixels every object covers at its current pose, after `register` / `track`: dict(owner (H,W) int32 device tensor, the
+    object in front at the pixel, -1 = none; mask_visib (n_obj,H,W) uint8 0 / 255; visib_fract (n_obj,) float64 numpy, the visible
+    fraction of each object's silhouette).  One Utils.scene_instances call (fp_scene_instances) over the estimators' centred meshes at
+    their `pose_last`; the frame size and K (unless given) are those of the last frame.  depth=None: only the objects hide one another;
+    with the frame's depth image (H,W) it hides them as well (occluders as in scene_instances)."""
+    from . import Utils as U
+    for i, e in enumerate(self.estimators):
+      if e.pose_last is None:
+        raise ValueError(f'MultiObjectTracker.instance_masks: estimator {i} has no pose yet (pose_last is None): register it first')
+    if getattr(self, '_last_frame', None) is None:
+      raise ValueError('MultiObjectTracker.instance_masks: no frame seen yet: call register or track first')
+    H, W, K_last = self._last_frame
+    dev = self.estimators[0].mesh_tensors['pos'].device
+    poses = torch.stack([torch.as_tensor(e.pose_last, device=dev, dtype=torch.float).reshape(4, 4) for e in self.estimators])
+    out = U.scene_instances(K_last if K is None else K, H, W, [e.mesh_tensors for e in self.estimators], poses, depth=depth, occluders=occluders,
+                            delta=delta, want=('mask_visib', 'owner', 'info'), glctx=self.estimators[0].refiner.ctx)
+    return dict(owner=out['owner'], mask_visib=out['mask_visib'], visib_fract=np.array([r['visib_fract'] for r in out['info']], dtype=np.float64))

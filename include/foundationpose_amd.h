@@ -190,6 +190,53 @@ int fp_vsd(fp_ctx *ctx, const fp_mesh *mesh, const float *d_depth_test, int dept
            const float *d_gt, int gt_per_pose, int n_poses, double diameter, double delta, const double *h_taus, int n_taus, float *d_err,
            int32_t *d_counts, void *stream);
 
+#define FP_SCENE_MAX_INSTANCES 1024
+#define FP_SCENE_OCC_DEPTH 1      /* the observed depth image occludes */
+#define FP_SCENE_OCC_INSTANCES 2  /* the instances occlude one another (z-buffer over all of them) */
+#define FP_SCENE_INFO_COLS 12     /* int32 columns of a d_info row: */
+#define FP_SCENE_INFO_PX_COUNT_ALL 0
+#define FP_SCENE_INFO_PX_COUNT_VALID 1
+#define FP_SCENE_INFO_PX_COUNT_VISIB 2
+#define FP_SCENE_INFO_PX_COUNT_IN_FRAME 3
+#define FP_SCENE_INFO_BBOX_OBJ 4   /* x0, y0, x1, y1 */
+#define FP_SCENE_INFO_BBOX_VISIB 8 /* x0, y0, x1, y1 */
+/* From the poses of the n_inst object instances of a frame to which pixels each covers, which of them are visible and how much of the
+ * object that is: what bop_toolkit's calc_gt_masks.py, calc_gt_info.py and visibility.estimate_visib_mask_gt compute on the CPU with an
+ * OpenGL renderer, and a z-buffer composite of the instances.  meshes: host array of n_inst handles (repeats allowed); d_poses
+ * (n_inst,4,4) device; K host float64 3x3.
+ *   Canvas.  Every instance is rendered alone, depth only, by this library's rasteriser (fp_render) on a canvas of
+ * (H + 2 pad_y) x (W + 2 pad_x) with K' = K except cx' = cx + pad_x, cy' = cy + pad_y (in double).  Image pixel (u, v) is canvas pixel
+ * (u + pad_x, v + pad_y).  pad = 0 is the plain frame; calc_gt_info uses pad_x = W, pad_y = H, so that the part of an object outside the
+ * frame counts in px_count_all.  Every output comes from this ONE render per instance (bop_toolkit renders twice, padded and not).
+ *   Distance.  dist(d) at canvas pixel (u', v') as under fp_vsd with K' and the canvas indices, float64, not contracted.  Dm_i = dist of
+ * instance i's render; Dt = dist(d_depth_test) inside the frame with FP_SCENE_OCC_DEPTH, else 0.
+ *   Occluder.  FP_SCENE_OCC_DEPTH alone: Docc = Dt.  With FP_SCENE_OCC_INSTANCES: Dmin = the smallest positive Dm_i at the pixel (0 if
+ * none) and Docc = Dmin, or with both bits the smaller positive one of Dt and Dmin (0 if neither is positive).
+ *   Masks.  mask_i = Dm_i > 0.  mask_visib_i = Dm_i > 0 && ((double)((float)Dm_i - (float)Docc) <= delta || Docc == 0) inside the frame
+ * (BOP's 'bop19' rule, the expression of fp_vsd) and false outside it: what lies outside the image is not visible in it, so
+ * px_count_visib == count(mask_visib) always and visib_fract = px_count_visib / px_count_all is BOP's.  d_mask / d_mask_visib
+ * (n_inst,H,W) uint8 receive 0 / 255 for the in-frame part.
+ *   Composite.  d_owner (H,W) int32: the instance with the smallest positive render DEPTH at the pixel, the smallest index among equal
+ * depths, -1 where none renders; d_depth (H,W): that depth in metres, 0 where none.  Neither looks at d_depth_test or `occluders`.
+ *   Info.  d_info (n_inst, FP_SCENE_INFO_COLS) int32, columns FP_SCENE_INFO_*: px_count_all = |mask| over the whole canvas;
+ * px_count_valid = mask pixels inside the frame with d_depth_test > 0 (0 when d_depth_test is null); px_count_visib = |mask_visib|;
+ * px_count_in_frame; bbox_obj = x0, y0, x1, y1 inclusive, in IMAGE coordinates, of the mask over the whole canvas (negative or beyond
+ * W-1 / H-1 with padding); bbox_visib the same of mask_visib.  An empty set has count 0 and a box of four -1: test the count, -1 is a
+ * legal coordinate with padding.
+ *   The instances are rendered in chunks whose depth layers fit 512 MB of the context's arena; the results do not depend on the
+ * chunking.  With FP_SCENE_OCC_INSTANCES and more than one chunk a first pass over the chunks forms the running minimum and a second
+ * one the masks: every instance is then rendered twice.  Without FP_SCENE_OCC_INSTANCES an instance's masks and info row are
+ * bit-identical whatever else is in the call.  Counts and boxes are accumulated with integer atomics (add, min, max): deterministic.
+ * Nothing synchronises; every output pointer may be null independently; n_inst = 0 launches nothing but clears d_owner (-1) and d_depth
+ * (0) when given.  FP_EINVAL: a null ctx or K, null meshes (or one of its entries) or d_poses with n_inst > 0, n_inst outside
+ * 0..FP_SCENE_MAX_INSTANCES, H or W < 1, a negative pad, `occluders` 0 or with unknown bits, FP_SCENE_OCC_DEPTH with d_depth_test null,
+ * delta < 0 or NaN, a canvas the rasteriser refuses (wider than 6553 pixels, or more rows than 255 of its strips hold - a strip holds
+ * about 15 000 pixels, so about 3.8 M canvas pixels: pad_x = W, pad_y = H fits frames up to 640 x 480; the message says to reduce the
+ * pad when there is one), checked before anything is queued.  FP_ENOMEM: the arena cannot hold the call's workspace. */
+int fp_scene_instances(fp_ctx *ctx, const fp_mesh *const *meshes, const float *d_poses, int n_inst, const double *K, int H, int W, int pad_x,
+                       int pad_y, const float *d_depth_test, int occluders, double delta, uint8_t *d_mask, uint8_t *d_mask_visib,
+                       int32_t *d_owner, float *d_depth, int32_t *d_info, void *stream);
+
 #define FP_MESH_DIAMETER_MAX_POINTS (1 << 21)
 /* Exact diameter of a point set: max over i < j of |p_i - p_j| over ALL pairs, in place of the reference's maximum over a random
  * sample of the points (compute_mesh_diameter, src/Utils.py:559-574, `np.random.choice`), whose value changes with numpy's seed once
