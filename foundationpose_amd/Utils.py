@@ -796,3 +796,124 @@ def scene_instances(K, H, W, meshes, poses, depth=None, occluders=None, delta=BO
   if rows is not None:
     out['info'] = scene_info_rows(rows.cpu().numpy())
   return out
+
+
+# ---- drawing poses on the frame (src/Utils.py:667-749, main.py:67-71) ----------------------------------------------------------------
+DRAW_PALETTE = np.array([[0, 255, 0], [255, 128, 0], [0, 160, 255], [255, 0, 255], [255, 255, 0], [0, 255, 255], [160, 96, 255], [255, 255, 255]],
+                        dtype=np.uint8)      # RGB; object o takes entry o % 8
+
+
+def project_3d_to_2d(pt, K, ob_in_cam):
+  """src/Utils.py:667-672 on the host: the pixel of the homogeneous object point `pt` (4,), rounded as np.round does (ties to even)."""
+  cam = np.asarray(ob_in_cam) @ np.asarray(pt).reshape(4, 1)
+  uvw = (np.asarray(K) @ cam[:3]).reshape(-1)
+  uvw = uvw / uvw[2]
+  return uvw[:2].round().astype(int)
+
+
+def model_box(mesh_or_pts):
+  """(to_origin (4,4), bbox (2,3)) of a model in the shape main.py:38-39 builds: bbox = [-extents / 2, extents / 2] and to_origin moves the
+  model into it, so that a pose of the model is drawn with `pose @ inv(to_origin)`.  This is the AXIS-ALIGNED box about the middle of
+  the vertices' extent; trimesh's minimum-volume `oriented_bounds`, which the reference calls, is out of scope."""
+  pts = np.asarray(getattr(mesh_or_pts, 'vertices', mesh_or_pts), dtype=np.float64).reshape(-1, 3)
+  lo, hi = pts.min(axis=0), pts.max(axis=0)
+  to_origin = np.eye(4)
+  to_origin[:3, 3] = -(lo + hi) / 2
+  extents = hi - lo
+  return to_origin, np.stack([-extents / 2, extents / 2], axis=0)
+
+
+def _per_object(x, n, shape, name):
+  """`x` as (n, *shape) float64: one entry for all objects, or one each"""
+  x = np.asarray(x.detach().cpu().numpy() if torch.is_tensor(x) else x, dtype=np.float64)
+  if x.shape == tuple(shape):
+    x = np.broadcast_to(x, (n,) + tuple(shape))
+  if x.shape != (n,) + tuple(shape):
+    raise ValueError(f'{name} is {x.shape}: give {tuple(shape)} for all objects or {(n,) + tuple(shape)}')
+  return x
+
+
+def draw_poses(img, K, poses, bboxes=None, offsets=None, owner=None, box=True, axes=True, fill_alpha=0.0, contour=False, axis_scale=0.1,
+               box_thickness=2, axis_thickness=3, transparency=0, colors=None, is_input_rgb=True, out=None, glctx=None):
+  """The boxes and axes of n posed objects, and optionally their silhouettes, drawn on a frame in one call (fp_draw_poses; the drawing
+  rule is in include/foundationpose_amd.h - the project's own anti-aliased capsules, not cv2's Wu lines).
+
+  img (H,W,3) uint8, a numpy array or a device tensor: the result is of the same kind - a new image, or `out` (which may be `img`
+  itself: in place).  poses (n,4,4), numpy or a tensor; a float32 device tensor is read where it lies.  bboxes (2,3) or (n,2,3) min / max
+  corners (None: no boxes); offsets (4,4) or (n,4,4), right-multiplied on the poses (main.py:67: inv(to_origin); None: identity).
+  owner (H,W) int32: scene_instances' owner map; fill_alpha > 0 tints every object's pixels with its colour, contour=True outlines its
+  region.  colors: (3,) or (n,3) for box, fill and contour, in the image's channel order; None takes DRAW_PALETTE.  The x, y, z axes are
+  red, green and blue in the order is_input_rgb says.  transparency as draw_xyz_axis': the lines are blended with 1 - transparency."""
+  is_np = not torch.is_tensor(img)
+  ctx = _ctx_of(glctx, None if is_np else img.device)
+  dev = torch.device('cuda', ctx.device_index)
+  src = torch.as_tensor(np.ascontiguousarray(img) if is_np else img).to(dev).contiguous()
+  if src.dtype != torch.uint8 or src.ndim != 3 or src.shape[2] != 3:
+    raise ValueError(f'img must be (H,W,3) uint8, got {tuple(src.shape)} {src.dtype}')
+  H, W = int(src.shape[0]), int(src.shape[1])
+  P = torch.as_tensor(poses).to(device=dev, dtype=torch.float).reshape(-1, 4, 4).contiguous()
+  n = len(P)
+  if n > _lib.FP_DRAW_MAX_OBJECTS:
+    raise ValueError(f'{n} poses: one call draws at most {_lib.FP_DRAW_MAX_OBJECTS} objects')
+  flags = (_lib.FP_DRAW_BOX if box and bboxes is not None else 0) | (_lib.FP_DRAW_AXES if axes else 0)
+  if fill_alpha > 0 or contour:
+    if owner is None:
+      raise ValueError('fill_alpha > 0 and contour=True need the owner map (scene_instances(...)["owner"])')
+    flags |= (_lib.FP_DRAW_FILL if fill_alpha > 0 else 0) | (_lib.FP_DRAW_CONTOUR if contour else 0)
+  own = None
+  if flags & (_lib.FP_DRAW_FILL | _lib.FP_DRAW_CONTOUR):
+    own = torch.as_tensor(owner).to(device=dev, dtype=torch.int32).contiguous()
+    if tuple(own.shape) != (H, W):
+      raise ValueError(f'owner is {tuple(own.shape)}, the frame {(H, W)}')
+  boxes = _per_object(bboxes if bboxes is not None else np.zeros((2, 3)), n, (2, 3), 'bboxes')
+  offs = _per_object(offsets if offsets is not None else np.eye(4), n, (4, 4), 'offsets')
+  cols = DRAW_PALETTE[np.arange(n) % len(DRAW_PALETTE)][:, ::1 if is_input_rgb else -1] if colors is None else _per_object(colors, n, (3,), 'colors')
+  axis_cols = np.eye(3, dtype=np.uint8)[:, ::1 if is_input_rgb else -1] * 255
+  objs = (_lib.FpDrawObject * max(n, 1))()
+  for o in range(n):
+    objs[o].bbox_min[:], objs[o].bbox_max[:] = [float(v) for v in boxes[o, 0]], [float(v) for v in boxes[o, 1]]
+    objs[o].offset[:] = [float(v) for v in offs[o].reshape(-1)]
+    objs[o].axis_scale = float(axis_scale)
+    objs[o].box_color[:] = objs[o].fill_color[:] = [int(v) for v in cols[o]]
+    objs[o].axis_color[:] = [int(v) for v in axis_cols.reshape(-1)]
+  if out is None:
+    dst = torch.empty_like(src)
+  elif is_np:
+    if not isinstance(out, np.ndarray) or out.shape != (H, W, 3) or out.dtype != np.uint8:
+      raise ValueError('out must be a (H,W,3) uint8 numpy array like img')
+    dst = src                                        # (the upload is a scratch copy: drawn in place, copied back below)
+  else:
+    if not torch.is_tensor(out) or out.dtype != torch.uint8 or tuple(out.shape) != (H, W, 3) or out.device != dev or not out.is_contiguous():
+      raise ValueError('out must be a contiguous (H,W,3) uint8 tensor on the device of img')
+    dst = out
+    if out is img and src is not img:                # a non-contiguous img cannot be drawn in place
+      raise ValueError('in-place drawing needs a contiguous img')
+  Kd, Kp = k_ptr(K)
+  a = _lib.FpDrawArgs()
+  a.struct_size = ctypes.sizeof(a)
+  a.d_img_in, a.d_img_out, a.H, a.W, a.K = src.data_ptr(), dst.data_ptr(), H, W, Kd.ctypes.data
+  a.d_poses, a.n_obj, a.objs, a.flags = (P.data_ptr() if n else None), n, ctypes.addressof(objs), flags
+  a.box_thickness, a.axis_thickness, a.opacity, a.fill_alpha = float(box_thickness), float(axis_thickness), 1.0 - float(transparency), float(fill_alpha)
+  a.d_owner = own.data_ptr() if own is not None else None
+  check(lib().fp_draw_poses(ctx.handle, ctypes.byref(a), stream_ptr(dev)))
+  if not is_np:
+    return dst
+  res = dst.cpu().numpy()
+  if out is None:
+    return res
+  out[...] = res
+  return out
+
+
+def draw_xyz_axis(color, ob_in_cam, scale=0.1, K=np.eye(3), thickness=3, transparency=0, is_input_rgb=False):
+  """src/Utils.py:675-710: the x, y, z axes of a pose, `scale` metres long, in red, green and blue on a COPY of the image `color` (BGR
+  unless is_input_rgb)."""
+  return draw_poses(color, K, np.asarray(ob_in_cam, dtype=np.float64).reshape(1, 4, 4), box=False, axes=True, axis_scale=scale, axis_thickness=thickness,
+                    transparency=transparency, is_input_rgb=is_input_rgb)
+
+
+def draw_posed_3d_box(K, img, ob_in_cam, bbox, line_color=(0, 255, 0), linewidth=2):
+  """src/Utils.py:713-749: the 12 edges of `bbox` (2,3) at the pose, drawn INTO `img` (a numpy array or a device tensor), which is also
+  returned, as cv2.line does - main.py:68-69 relies on it."""
+  return draw_poses(img, K, np.asarray(ob_in_cam, dtype=np.float64).reshape(1, 4, 4), bboxes=np.asarray(bbox, dtype=np.float64).reshape(2, 3), box=True,
+                    axes=False, box_thickness=linewidth, colors=np.asarray(line_color, dtype=np.float64), out=img)

@@ -88,6 +88,24 @@ class FpRegisterObjectsArgs(Structure):
               ('d_labels', c_void_p), ('max_pass_hyp', c_int), ('d_depth_f', c_void_p), ('d_xyz', c_void_p), ('d_rgb_f', c_void_p)]
 
 
+FP_DRAW_MAX_OBJECTS = 64             # include/foundationpose_amd.h: fp_draw_poses
+FP_DRAW_BOX, FP_DRAW_AXES, FP_DRAW_FILL, FP_DRAW_CONTOUR = 1, 2, 4, 8
+FP_DRAW_ZNEAR = 0.01
+
+
+class FpDrawObject(Structure):
+  """fp_draw_object (include/foundationpose_amd.h): the box, the axes and the colours of one object of fp_draw_poses."""
+  _fields_ = [('bbox_min', c_float * 3), ('bbox_max', c_float * 3), ('offset', c_float * 16), ('axis_scale', c_float),
+              ('box_color', ctypes.c_uint8 * 3), ('axis_color', ctypes.c_uint8 * 9), ('fill_color', ctypes.c_uint8 * 3)]
+
+
+class FpDrawArgs(Structure):
+  """fp_draw_args (include/foundationpose_amd.h): one fp_draw_poses call."""
+  _fields_ = [('struct_size', ctypes.c_size_t), ('d_img_in', c_void_p), ('d_img_out', c_void_p), ('H', c_int), ('W', c_int), ('K', c_void_p),
+              ('d_poses', c_void_p), ('n_obj', c_int), ('objs', c_void_p), ('flags', c_int), ('box_thickness', c_float),
+              ('axis_thickness', c_float), ('opacity', c_float), ('fill_alpha', c_float), ('d_owner', c_void_p)]
+
+
 class FpObjectBatch(Structure):
   _fields_ = [('mesh', c_void_p), ('d_rgb', c_void_p), ('d_geom', c_void_p), ('H', c_int), ('W', c_int), ('K', c_void_p),
               ('mesh_diameter', c_double), ('n', c_int)]
@@ -126,6 +144,7 @@ _PROTOS = {
   'fp_mesh_diameter': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
   'fp_scene_instances': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_double, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_void_p, c_void_p]),
+  'fp_draw_poses': (c_int, [c_void_p, POINTER(FpDrawArgs), c_void_p]),
   'fp_net_create': (c_int, [c_void_p, c_int, POINTER(FpTensor), c_int, c_int, POINTER(c_void_p)]),
   'fp_net_destroy': (c_int, [c_void_p]),
   'fp_net_rot_dim': (c_int, [c_void_p]),

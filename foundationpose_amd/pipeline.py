@@ -112,3 +112,12 @@ class FoundationPoseEstimator(Processor):
     else:
       data.pose = self.est.track_one(rgb=data.rgb, depth=data.depth, K=K, iteration=self.track_refine_iter)
     return data
+
+  def visualize(self, data):
+    """The picture main.py:67-71 saves: the model's box and the xyz axes at `data.pose` on `data.rgb`; sets and returns `data.vis`."""
+    from . import Utils as U
+    K = self.K if data.K is None else np.asarray(data.K, dtype=np.float64)
+    to_origin, bbox = U.model_box(self.mesh)
+    data.vis = U.draw_poses(data.rgb, K, np.asarray(data.pose, dtype=np.float64).reshape(1, 4, 4), bboxes=bbox, offsets=np.linalg.inv(to_origin),
+                            colors=(0, 255, 0))
+    return data.vis

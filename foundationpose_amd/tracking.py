@@ -208,6 +208,7 @@ class MultiObjectTracker:
     for o, e in enumerate(self.estimators):
       e.pose_last = ws['poses'][o].reshape(1, 4, 4)
       ws['holds'][o] = e.pose_last
+    self._returned = [(e.pose_last, out[o].copy()) for o, e in enumerate(self.estimators)]
     return out
 
   def _check_register(self, depth, masks, labels):
@@ -353,6 +354,7 @@ class MultiObjectTracker:
       e.poses, e.scores, e.best_id = out_p[o], out_s[o], out_o[o][0]
       e.pose_last = e.poses[0]
       out[o] = ws['pose_of_mesh'][o].numpy()
+    self._returned = [(e.pose_last if objs[o].registered else False, out[o].copy()) for o, e in enumerate(ests)]      # (False: never a pose_last)
     return out
 
   def instance_masks(self, depth=None, K=None, occluders=None, delta=0.015):
@@ -373,3 +375,30 @@ class MultiObjectTracker:
     out = U.scene_instances(K_last if K is None else K, H, W, [e.mesh_tensors for e in self.estimators], poses, depth=depth, occluders=occluders,
                             delta=delta, want=('mask_visib', 'owner', 'info'), glctx=self.estimators[0].refiner.ctx)
     return dict(owner=out['owner'], mask_visib=out['mask_visib'], visib_fract=np.array([r['visib_fract'] for r in out['info']], dtype=np.float64))
+
+  def draw(self, rgb, fill_alpha=0.0, contour=False, depth=None, **kw):
+    """The frame `rgb` (H,W,3) uint8, numpy or device tensor, with every object's box and xyz axes at its current pose of the ORIGINAL
+    mesh - the poses the last `register` / `track` returned - in one Utils.draw_poses call; the result is of the kind of `rgb`.  The box
+    of object o is Utils.model_box of its mesh, in object o's palette colour.  fill_alpha > 0 tints each object's visible pixels,
+    contour=True outlines them: the owner map then comes from instance_masks(depth=depth).  Other keywords go to Utils.draw_poses."""
+    from . import Utils as U
+    ests = self.estimators
+    for i, e in enumerate(ests):
+      if e.pose_last is None:
+        raise ValueError(f'MultiObjectTracker.draw: estimator {i} has no pose yet (pose_last is None): register it first')
+    if getattr(self, '_last_frame', None) is None:
+      raise ValueError('MultiObjectTracker.draw: no frame seen yet: call register or track first')
+    returned = getattr(self, '_returned', None) or [(None, None)] * len(ests)
+    poses, boxes, offs = [], [], []
+    for e, (held, pose) in zip(ests, returned):
+      if held is not e.pose_last:                           # set elsewhere since: the pose of the original mesh as track_one forms it
+        last = torch.as_tensor(e.pose_last, dtype=torch.float).reshape(4, 4)
+        pose = (last.to(e.get_tf_to_centered_mesh().device) @ e.get_tf_to_centered_mesh()).cpu().numpy()
+      to_origin, bbox = U.model_box(e.mesh_ori)
+      poses.append(pose), boxes.append(bbox), offs.append(np.linalg.inv(to_origin))
+    owner = None
+    if fill_alpha > 0 or contour:
+      owner = self.instance_masks(depth=depth)['owner']
+    K = kw.pop('K', self._last_frame[2])
+    return U.draw_poses(rgb, K, np.stack(poses), bboxes=np.stack(boxes), offsets=np.stack(offs), owner=owner, fill_alpha=fill_alpha, contour=contour,
+                        glctx=ests[0].refiner.ctx, **kw)

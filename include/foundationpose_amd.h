@@ -477,6 +477,52 @@ int fp_score_tail_scores(fp_ctx *ctx, const fp_net *net, const float *d_feats, i
 int fp_score_predict_rows_multi(fp_ctx *ctx, const fp_net *net, const fp_object_batch *objs, int n_obj, double crop_ratio,
                                 int normalize_xyz, const float *d_poses, float *d_rows, void *stream);
 
+/* ---- the picture the reference's demo ends with (main.py:67-71: draw_posed_3d_box and draw_xyz_axis, src/Utils.py:667-749, on the frame),
+ *      for up to FP_DRAW_MAX_OBJECTS objects of one frame in two launches, plus the silhouettes of an owner map (fp_scene_instances' d_owner).
+ *      The reference draws with cv2.line / cv2.arrowedLine (LINE_AA, Wu's lines); cv2 is not part of this build and the drawing rule below is
+ *      the project's own, like the font of vis.py: the same segments between the same rounded endpoints, but cv2's anti-aliased fringe
+ *      differs from it.
+ *      Segments: per object in index order the 12 edges of the box - the edges along x over (y, z), those along y over (x, z), those along z
+ *      over (x, y), each min before max (draw_posed_3d_box's order; bbox_min / bbox_max after a per-component min / max) - then the axes x, y,
+ *      z from the origin, axis_scale long.  Endpoints: p_cam = (d_poses[o] @ offset) p in float64 (offset is rigid: its last row is taken as
+ *      0 0 0 1); a segment wholly behind z = FP_DRAW_ZNEAR is dropped, one that crosses it is cut there; (u, v) = (K[0,:] . p / z,
+ *      K[1,:] . p / z), each rounded to the nearest integer, ties to even (np.round, as the reference rounds); a segment with a rounded
+ *      coordinate beyond +-2^20 is dropped whole.  Coverage of a pixel: d = the Euclidean distance in fp32 of its integer centre to the
+ *      segment (a segment of length zero is a point), a = clamp(thickness / 2 + 0.5 - d, 0, 1) * opacity, c = c + a (colour - c) in fp32,
+ *      segment after segment in the order above.  (The launch holds each segment as the part inside the frame grown by 64 pixels, cut in
+ *      float64 - the pixels' distances are those to the whole segment; on frames up to 4096 pixels a side d is within 1e-3 of the exact one.)
+ *      Before the segments, where d_owner[p] = o in 0 .. n_obj-1 (any other value is "none"): with FP_DRAW_FILL c = c + fill_alpha
+ *      (fill_color_o - c); with FP_DRAW_CONTOUR, if a 4-neighbour of p inside the frame has another owner, c = box_color_o.  Each channel is
+ *      rounded once at the end (rint, clamped to 0 .. 255); a pixel nothing touched keeps its byte.  Deterministic: no atomics, a pixel
+ *      belongs to one thread.
+ *      d_poses is read by the launches, not by the host: the call can sit behind fp_track_objects in one hipGraph, and a replay draws the
+ *      poses the buffer holds then.  K, objs and the scalar arguments are read during the call (a captured graph keeps their values).
+ *      Nothing synchronises.  Workspace: under 64 KB of the context's arena - the call leaves the arena generation alone when
+ *      fp_ctx_reserve (or any larger call) has run before; call it before capturing.
+ *      n_obj = 0 or flags = 0: d_img_in is copied to d_img_out when they differ, nothing else happens. */
+#define FP_DRAW_MAX_OBJECTS 64
+#define FP_DRAW_BOX 1       /* the 12 edges of bbox */
+#define FP_DRAW_AXES 2      /* x, y, z axes from the origin, length axis_scale */
+#define FP_DRAW_FILL 4      /* tint the pixels d_owner gives to an object */
+#define FP_DRAW_CONTOUR 8   /* 1-pixel inner contour of d_owner's regions */
+#define FP_DRAW_ZNEAR 0.01  /* metres: segments are clipped to z >= this before projection */
+typedef struct {
+  float bbox_min[3], bbox_max[3];  /* in the frame `offset` maps from */
+  float offset[16];                /* row-major rigid 4x4, right-multiplied: drawn pose = d_poses[o] @ offset (main.py:67: inv(to_origin)); identity leaves the pose */
+  float axis_scale;                /* metres (reference default 0.1) */
+  uint8_t box_color[3], axis_color[9] /* x, y, z */, fill_color[3];   /* in the channel order of the image */
+} fp_draw_object;
+typedef struct {
+  size_t struct_size;              /* = sizeof(fp_draw_args) */
+  const uint8_t *d_img_in; uint8_t *d_img_out;   /* H*W*3; equal pointers = in place; any other overlap is refused */
+  int H, W; const double *K;                     /* host 3x3; the first two rows are used in full (skew included) */
+  const float *d_poses; int n_obj;               /* (n_obj,4,4) DEVICE: read by the launch, not by the host */
+  const fp_draw_object *objs;                    /* host */
+  int flags; float box_thickness /* 2 */, axis_thickness /* 3 */, opacity /* 1 - transparency */, fill_alpha;
+  const int32_t *d_owner;                        /* H*W, fp_scene_instances' owner; required with FILL / CONTOUR */
+} fp_draw_args;
+int fp_draw_poses(fp_ctx *ctx, const fp_draw_args *args, void *stream);
+
 /* ---- building blocks exported for parity tests and profiling ---------------------------------- */
 /* fp16 NHWC implicit-GEMM convolution on MFMA: out = act(conv(in, w) + bias [+ res]).  w_packed is
  * [Cout][Kpad] fp16 with k = (ky*KW+kx)*Cin + ci, Kpad = roundup(KH*KW*Cin, 32), zero padded. */
@@ -529,7 +575,7 @@ int fp_head_mlp_f16(fp_ctx *ctx, const void *d_att, const void *d_tok, int M, co
 int fp_cluster_poses(float angle_diff_deg, float dist_diff_m, const float *h_poses_in, int n_in, const float *h_symmetry_tfs,
                      int n_sym, float *h_out);
 
-/* timing helper: device time of a kernel class ("conv3x3_halo", "conv3x3_s2", "conv7x7", "linear", "attention", "render") over
+/* timing helper: device time of a kernel class ("conv3x3_halo", "conv3x3_s2", "conv7x7", "linear", "attention", "render", "scene_pass", "draw", "draw_setup") over
  * the launches since the last reset, measured with (pooled) HIP events on the launch stream.  on = 0: off; 1: events around the
  * dominant class only (the 3x3 stride-1 convolutions: what a timed benchmark run carries); 2: around every class. */
 int fp_prof_enable(fp_ctx *ctx, int on);
