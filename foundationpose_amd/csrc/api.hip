@@ -135,15 +135,7 @@ extern "C" int fp_ctx_reserve(fp_ctx *ctx, int max_hyp) {
   FP_REQUIRE(ctx->arena.off == 0, "fp_ctx_reserve: arena in use");
   size_t need = fp_arena_bytes_for(max_hyp);
   if (ctx->arena.cap >= need) return FP_OK;
-  ctx->arena.off = 0;
-  Arena &a = ctx->arena;
-  if (a.base) {
-    FP_CHECK_HIP(hipDeviceSynchronize());
-    FP_CHECK_HIP(hipFree(a.base));
-    a.base = nullptr;
-    a.cap = 0;
-  }
-  FP_TRY(fp_arena_ensure(ctx, need));
+  FP_TRY(fp_arena_ensure(ctx, need));          // (off == 0 and cap < need: it frees the old block and allocates)
   ctx->reserved_hyp = max_hyp;
   return FP_OK;
 }
@@ -304,12 +296,10 @@ static int render_with_arena_scratch(fp_ctx *ctx, RenderArgs &a, hipStream_t s) 
   if (a.N == 0) return FP_OK;
   const size_t bytes = render_scratch_bytes(a.N, a.mesh.V, a.mesh.F, a.Ho, a.Wo, ctx->num_cu);     // (sub-batches above 1 GiB: launch_render)
   FP_TRY(fp_arena_ensure(ctx, bytes + 4096));
-  const size_t mark = ctx->arena.off;
+  ArenaScope scope(ctx->arena);
   a.scratch = ctx->arena.take(bytes);
   a.scratch_bytes = bytes;
-  const int rc = a.scratch ? launch_render(ctx, a, s) : FP_ENOMEM;
-  ctx->arena.off = mark;
-  return rc;
+  return a.scratch ? launch_render(ctx, a, s) : FP_ENOMEM;
 }
 
 static int fill_render(RenderArgs &a, const fp_mesh *mesh, const float *d_poses, int N, const double *K, int H, int W,
@@ -475,12 +465,10 @@ extern "C" int fp_mask_depth_stats(fp_ctx *ctx, const float *d_depth, const uint
   FP_REQUIRE(ctx && d_depth && d_mask && h_stats6 && h_median && H > 0 && W > 0, "fp_mask_depth_stats: bad argument");
   hipStream_t s = (hipStream_t)stream;
   FP_TRY(fp_arena_ensure(ctx, 4096));
-  const size_t mark = ctx->arena.off;
+  ArenaScope scope(ctx->arena);      // (released behind the copy and the wait below: host bookkeeping, nothing else takes in between)
   int *d_out = (int *)ctx->arena.take(8 * sizeof(int));
   FP_REQUIRE(d_out, "fp_mask_depth_stats: arena exhausted");
-  int rc = launch_mask_depth_stats(d_depth, d_mask, H, W, min_depth, d_out, (float *)(d_out + 6), s);
-  ctx->arena.off = mark;
-  if (rc != FP_OK) return rc;
+  FP_TRY(launch_mask_depth_stats(d_depth, d_mask, H, W, min_depth, d_out, (float *)(d_out + 6), s));
   int host[8];
   FP_CHECK_HIP(hipMemcpyAsync(host, d_out, sizeof(host), hipMemcpyDeviceToHost, s));
   FP_CHECK_HIP(hipStreamSynchronize(s));
@@ -502,14 +490,12 @@ extern "C" int fp_pose_errors(fp_ctx *ctx, const float *d_pts, int n_pts, const 
   if (which == 0) return FP_OK;
   const size_t bytes = pose_errors_slab_bytes(n_pts, n_poses, (which & FP_ERR_ADD_SYM) ? n_sym : 0);
   FP_TRY(fp_arena_ensure(ctx, bytes + 4096));
-  const size_t mark = ctx->arena.off;
+  ArenaScope scope(ctx->arena);
   double *slab = (double *)ctx->arena.take(bytes);
   FP_REQUIRE(slab, "fp_pose_errors: arena exhausted");
   // the slab is consumed by the finishing launch on the same stream before anything else takes it
-  const int rc = launch_pose_errors(d_pts, n_pts, d_pred, d_gt, gt_per_pose, n_poses, d_sym, n_sym, which, slab, d_add, d_adds, d_add_sym,
-                                    (hipStream_t)stream);
-  ctx->arena.off = mark;
-  return rc;
+  return launch_pose_errors(d_pts, n_pts, d_pred, d_gt, gt_per_pose, n_poses, d_sym, n_sym, which, slab, d_add, d_adds, d_add_sym,
+                            (hipStream_t)stream);
 }
 
 extern "C" int fp_pose_errors_bop(fp_ctx *ctx, const float *d_pts, int n_pts, const float *d_pred, const float *d_gt, int gt_per_pose,
@@ -525,14 +511,11 @@ extern "C" int fp_pose_errors_bop(fp_ctx *ctx, const float *d_pts, int n_pts, co
   if (which == 0 || n_poses == 0) return FP_OK;
   const size_t bytes = bop_errors_slab_bytes(n_pts, n_poses, n_sym);
   FP_TRY(fp_arena_ensure(ctx, bytes + 4096));
-  const size_t mark = ctx->arena.off;
+  ArenaScope scope(ctx->arena);
   float *slab = (float *)ctx->arena.take(bytes);
   FP_REQUIRE(slab, "fp_pose_errors_bop: arena exhausted");
   // the slab is consumed by the finishing launch on the same stream before anything else takes it
-  const int rc = launch_bop_errors(d_pts, n_pts, d_pred, d_gt, gt_per_pose, n_poses, d_sym, n_sym, K, which, slab, d_mssd, d_mspd,
-                                   (hipStream_t)stream);
-  ctx->arena.off = mark;
-  return rc;
+  return launch_bop_errors(d_pts, n_pts, d_pred, d_gt, gt_per_pose, n_poses, d_sym, n_sym, K, which, slab, d_mssd, d_mspd, (hipStream_t)stream);
 }
 
 extern "C" int fp_mesh_diameter(fp_ctx *ctx, const float *d_pts, int n_pts, float *d_out_diameter, int32_t *d_out_pair, void *stream) {
@@ -541,13 +524,11 @@ extern "C" int fp_mesh_diameter(fp_ctx *ctx, const float *d_pts, int n_pts, floa
   FP_REQUIRE(d_pts || n_pts == 0, "fp_mesh_diameter: d_pts null with n_pts %d", n_pts);
   const size_t bytes = mesh_diameter_slab_bytes(n_pts);
   FP_TRY(fp_arena_ensure(ctx, bytes + 4096));
-  const size_t mark = ctx->arena.off;
+  ArenaScope scope(ctx->arena);
   void *slab = ctx->arena.take(bytes);
   FP_REQUIRE(slab, "fp_mesh_diameter: arena exhausted");
   // the slab is consumed by the finishing launch on the same stream before anything else takes it
-  const int rc = launch_mesh_diameter(d_pts, n_pts, slab, d_out_diameter, d_out_pair, (hipStream_t)stream);
-  ctx->arena.off = mark;
-  return rc;
+  return launch_mesh_diameter(d_pts, n_pts, slab, d_out_diameter, d_out_pair, (hipStream_t)stream);
 }
 
 // poses per render chunk of fp_vsd: their depth images (and those of their ground truth, one per pose) within this many bytes
@@ -576,33 +557,28 @@ extern "C" int fp_vsd(fp_ctx *ctx, const fp_mesh *mesh, const float *d_depth_tes
   const size_t counts_bytes = (size_t)n_poses * (2 + FP_VSD_MAX_TAUS) * sizeof(unsigned);
   const size_t dg_bytes = px * sizeof(float) * (gt_per_pose ? chunk : 1), de_bytes = px * sizeof(float) * chunk;
   FP_TRY(fp_arena_ensure(ctx, counts_bytes + dg_bytes + de_bytes + rs + 4 * 256 + 4096));
-  const size_t mark = ctx->arena.off;
-  auto run = [&]() -> int {
-    unsigned *counts = (unsigned *)ctx->arena.take(counts_bytes);
-    float *dg = (float *)ctx->arena.take(dg_bytes);
-    float *de = (float *)ctx->arena.take(de_bytes);
-    FP_REQUIRE(counts && dg && de, "fp_vsd: arena exhausted");
-    FP_CHECK_HIP(hipMemsetAsync(counts, 0, counts_bytes, s));
-    // render_with_arena_scratch takes the render scratch behind these buffers and releases it when the launches are queued
-    auto render_depth = [&](const float *poses, int n, float *out) -> int {
-      RenderArgs a;
-      FP_TRY(fill_render(a, mesh, poses, n, K, H, W, nullptr, H, W));
-      a.depth = out;
-      return render_with_arena_scratch(ctx, a, s);
-    };
-    if (!gt_per_pose) FP_TRY(render_depth(d_gt, 1, dg));
-    for (int b0 = 0; b0 < n_poses; b0 += chunk) {
-      const int n = std::min(chunk, n_poses - b0);
-      FP_TRY(render_depth(d_pred + (size_t)b0 * 16, n, de));
-      if (gt_per_pose) FP_TRY(render_depth(d_gt + (size_t)b0 * 16, n, dg));
-      FP_TRY(launch_vsd_count(d_depth_test + (depth_per_pose ? (size_t)b0 * px : 0), depth_per_pose ? px : 0, dg, gt_per_pose ? px : 0, de,
-                              n, H, W, K, diameter, delta, h_taus, n_taus, counts + (size_t)b0 * (2 + FP_VSD_MAX_TAUS), s));
-    }
-    return launch_vsd_finish(counts, n_poses, n_taus, d_err, d_counts, s);
+  ArenaScope scope(ctx->arena);
+  unsigned *counts = (unsigned *)ctx->arena.take(counts_bytes);
+  float *dg = (float *)ctx->arena.take(dg_bytes);
+  float *de = (float *)ctx->arena.take(de_bytes);
+  FP_REQUIRE(counts && dg && de, "fp_vsd: arena exhausted");
+  FP_CHECK_HIP(hipMemsetAsync(counts, 0, counts_bytes, s));
+  // render_with_arena_scratch takes the render scratch behind these buffers and releases it when the launches are queued
+  auto render_depth = [&](const float *poses, int n, float *out) -> int {
+    RenderArgs a;
+    FP_TRY(fill_render(a, mesh, poses, n, K, H, W, nullptr, H, W));
+    a.depth = out;
+    return render_with_arena_scratch(ctx, a, s);
   };
-  const int rc = run();
-  ctx->arena.off = mark;
-  return rc;
+  if (!gt_per_pose) FP_TRY(render_depth(d_gt, 1, dg));
+  for (int b0 = 0; b0 < n_poses; b0 += chunk) {
+    const int n = std::min(chunk, n_poses - b0);
+    FP_TRY(render_depth(d_pred + (size_t)b0 * 16, n, de));
+    if (gt_per_pose) FP_TRY(render_depth(d_gt + (size_t)b0 * 16, n, dg));
+    FP_TRY(launch_vsd_count(d_depth_test + (depth_per_pose ? (size_t)b0 * px : 0), depth_per_pose ? px : 0, dg, gt_per_pose ? px : 0, de,
+                            n, H, W, K, diameter, delta, h_taus, n_taus, counts + (size_t)b0 * (2 + FP_VSD_MAX_TAUS), s));
+  }
+  return launch_vsd_finish(counts, n_poses, n_taus, d_err, d_counts, s);
 }
 
 // instances per render chunk of fp_scene_instances: their depth layers on the padded canvas within this many bytes
@@ -662,53 +638,48 @@ extern "C" int fp_scene_instances(fp_ctx *ctx, const fp_mesh *const *meshes, con
     }
   const size_t layer_bytes = pxc * sizeof(float) * chunk, acc_bytes = (size_t)n_inst * FP_SCENE_INFO_COLS * sizeof(int);
   FP_TRY(fp_arena_ensure(ctx, layer_bytes + acc_bytes + pxf * 8 + rs + 8 * 256 + 4096));
-  const size_t mark = ctx->arena.off;
-  auto run = [&]() -> int {
-    float *layers = (float *)ctx->arena.take(layer_bytes);
-    int *acc = d_info ? (int *)ctx->arena.take(acc_bytes) : nullptr;
-    // the running minimum lives in the caller's d_depth / d_owner; a call that needs it over several chunks without asking for it borrows the arena
-    float *dmin = d_depth ? d_depth : (need_min && chunk < n_inst ? (float *)ctx->arena.take(pxf * sizeof(float)) : nullptr);
-    if (!layers || (d_info && !acc) || (need_min && chunk < n_inst && !dmin)) {
-      fp_set_error("fp_scene_instances: arena exhausted");
-      return FP_ENOMEM;
+  ArenaScope scope(ctx->arena);
+  float *layers = (float *)ctx->arena.take(layer_bytes);
+  int *acc = d_info ? (int *)ctx->arena.take(acc_bytes) : nullptr;
+  // the running minimum lives in the caller's d_depth / d_owner; a call that needs it over several chunks without asking for it borrows the arena
+  float *dmin = d_depth ? d_depth : (need_min && chunk < n_inst ? (float *)ctx->arena.take(pxf * sizeof(float)) : nullptr);
+  if (!layers || (d_info && !acc) || (need_min && chunk < n_inst && !dmin)) {
+    fp_set_error("fp_scene_instances: arena exhausted");
+    return FP_ENOMEM;
+  }
+  if (acc) FP_TRY(launch_scene_info_init(acc, n_inst, s));
+  // render_with_arena_scratch takes the render scratch behind these buffers and releases it when the launches are queued
+  auto render_chunk_layers = [&](int b0, int n) -> int {
+    for (int r0 = b0; r0 < b0 + n;) {
+      int r1 = r0 + 1;
+      while (r1 < b0 + n && meshes[r1] == meshes[r0]) ++r1;
+      RenderArgs a;
+      FP_TRY(fill_render(a, meshes[r0], d_poses + (size_t)r0 * 16, r1 - r0, Kc, Hc, Wc, nullptr, Hc, Wc));
+      a.depth = layers + (size_t)(r0 - b0) * pxc;
+      FP_TRY(render_with_arena_scratch(ctx, a, s));
+      r0 = r1;
     }
-    if (acc) FP_TRY(launch_scene_info_init(acc, n_inst, s));
-    // render_with_arena_scratch takes the render scratch behind these buffers and releases it when the launches are queued
-    auto render_chunk_layers = [&](int b0, int n) -> int {
-      for (int r0 = b0; r0 < b0 + n;) {
-        int r1 = r0 + 1;
-        while (r1 < b0 + n && meshes[r1] == meshes[r0]) ++r1;
-        RenderArgs a;
-        FP_TRY(fill_render(a, meshes[r0], d_poses + (size_t)r0 * 16, r1 - r0, Kc, Hc, Wc, nullptr, Hc, Wc));
-        a.depth = layers + (size_t)(r0 - b0) * pxc;
-        FP_TRY(render_with_arena_scratch(ctx, a, s));
-        r0 = r1;
-      }
-      return FP_OK;
-    };
-    auto pass = [&](bool do_min, bool do_masks) -> int {
-      for (int b0 = 0; b0 < n_inst; b0 += chunk) {
-        const int n = std::min(chunk, n_inst - b0);
-        FP_TRY(render_chunk_layers(b0, n));
-        SceneLaunch l;
-        l.layers = layers, l.dt = d_depth_test, l.n = n, l.i0 = b0, l.H = H, l.W = W, l.pad_x = pad_x, l.pad_y = pad_y;
-        l.do_min = do_min, l.do_masks = do_masks, l.first = b0 == 0, l.occ_depth = occ_depth, l.occ_inst = occ_inst;
-        l.K = K, l.delta = delta, l.dmin = dmin, l.owner = d_owner, l.mask = d_mask, l.mask_visib = d_mask_visib, l.acc = acc;
-        FP_TRY(launch_scene_instances(ctx, l, s));
-      }
-      return FP_OK;
-    };
-    if (two_pass) {
-      FP_TRY(pass(true, false));
-      FP_TRY(pass(false, true));
-    } else {
-      FP_TRY(pass(need_min, want_masks));
-    }
-    return acc ? launch_scene_info_finish(acc, n_inst, d_info, s) : FP_OK;
+    return FP_OK;
   };
-  const int rc = run();
-  ctx->arena.off = mark;
-  return rc;
+  auto pass = [&](bool do_min, bool do_masks) -> int {
+    for (int b0 = 0; b0 < n_inst; b0 += chunk) {
+      const int n = std::min(chunk, n_inst - b0);
+      FP_TRY(render_chunk_layers(b0, n));
+      SceneLaunch l;
+      l.layers = layers, l.dt = d_depth_test, l.n = n, l.i0 = b0, l.H = H, l.W = W, l.pad_x = pad_x, l.pad_y = pad_y;
+      l.do_min = do_min, l.do_masks = do_masks, l.first = b0 == 0, l.occ_depth = occ_depth, l.occ_inst = occ_inst;
+      l.K = K, l.delta = delta, l.dmin = dmin, l.owner = d_owner, l.mask = d_mask, l.mask_visib = d_mask_visib, l.acc = acc;
+      FP_TRY(launch_scene_instances(ctx, l, s));
+    }
+    return FP_OK;
+  };
+  if (two_pass) {
+    FP_TRY(pass(true, false));
+    FP_TRY(pass(false, true));
+  } else {
+    FP_TRY(pass(need_min, want_masks));
+  }
+  return acc ? launch_scene_info_finish(acc, n_inst, d_info, s) : FP_OK;
 }
 
 extern "C" int fp_pose_update(fp_ctx *ctx,const float *d_poseA, const float *d_trans, const float *d_rot, int N, int rot_dim,
@@ -756,14 +727,31 @@ static bool same_render_key(const fp_object_batch &a, const fp_object_batch &b) 
   return a.mesh == b.mesh && a.H == b.H && a.W == b.W && a.mesh_diameter == b.mesh_diameter && memcmp(a.K, b.K, 9 * sizeof(double)) == 0;
 }
 
-// Scratch of the renders of a pass: one render_scratch_bytes(...) per run of like objects (the renders of the runs may overlap on side
-// streams, so each has its own block; a run whose worst case exceeds 1 GiB is rendered in sub-batches: launch_render).
-static size_t render_scratch_total(fp_ctx *ctx, const fp_object_batch *objs, int n_obj) {
+// scratch block of one 160 x 160 render of n hypotheses, rounded to the arena's 256 bytes: the passes lay such blocks end to end
+static size_t render_block_bytes(fp_ctx *ctx, const fp_mesh *mesh, int n) {
+  return (render_scratch_bytes(n, mesh->d.V, mesh->d.F, 160, 160, ctx->num_cu) + 255) & ~(size_t)255;
+}
+
+// The non-empty runs of like objects of a pass, in order: objects [o0, o1), their `cnt` hypotheses from hypothesis `off` on, and the run's
+// own block of the pass' render scratch (the renders of the runs may overlap on side streams; a run whose worst case exceeds 1 GiB is
+// rendered in sub-batches: launch_render).  An object without hypotheses adds nothing to its run; a run of such objects only is left out.
+struct RenderRun {
+  int o0, o1, off, cnt;
+  size_t soff, sbytes;
+};
+
+// -> the scratch of all runs; `runs` (optional) receives them
+static size_t render_runs(fp_ctx *ctx, const fp_object_batch *objs, int n_obj, std::vector<RenderRun> *runs) {
   size_t bytes = 0;
-  for (int o = 0; o < n_obj;) {
+  for (int o = 0, off = 0; o < n_obj;) {
     int e = o + 1, cnt = objs[o].n;
     while (e < n_obj && same_render_key(objs[o], objs[e])) cnt += objs[e++].n;
-    if (cnt > 0) bytes += (render_scratch_bytes(cnt, objs[o].mesh->d.V, objs[o].mesh->d.F, 160, 160, ctx->num_cu) + 255) & ~(size_t)255;
+    if (cnt > 0) {
+      const size_t sb = render_block_bytes(ctx, objs[o].mesh, cnt);
+      if (runs) runs->push_back(RenderRun{o, e, off, cnt, bytes, sb});
+      bytes += sb;
+    }
+    off += cnt;
     o = e;
   }
   return bytes;
@@ -775,15 +763,86 @@ static size_t pass_arena_bytes(int N, size_t render_scratch) {
   return (size_t)N * ((size_t)1 << 20) + ((size_t)1 << 20) + render_scratch + fp_arena_inner_bytes(N);
 }
 
-static int count_runs(const fp_object_batch *objs, int n_obj) {
+// One run of like objects in a batch that the trunk does not cut in two by hypotheses: the rendered side (crop window -> rasteriser ->
+// encodeA) and the observed side (crop window -> observed crop -> encodeA) are two chains on two streams up to the channel concat
+// (run_trunk): side B does not wait for the rasteriser.  Bit-identical to one chain.
+static bool two_side_chains(int n_runs, int N) { return n_runs == 1 && N < fp_trunk_split_min() && !g_one_chain; }
+
+struct NetInputOpts {
+  int mode;                  // of the observed crop (fp_crop_observed)
+  float invalid_thres;       // of the rendered side
+  double crop_ratio;
+  int normalize_xyz;
+  bool windows_written;      // tf / bbox hold this pass' crop windows already
+  // shared side B (`sb` optional; one run): ONE observed crop per live object (window and translation of its first hypothesis = of all of
+  // them) into xB1, encoded into featB (= sb->feat) by `net`; sb->start / n_groups are filled here
+  const fp_net *net;
+  SharedB *sb;
+  f16 *xB1, *featB;
+};
+
+// The input of ONE network pass over every object: per run of like objects the crop windows (tf, bbox) and the render (side A: net_in[0, N))
+// on the run's stream, per object the observed crop (side B: net_in[N, 2N)).  `ab` (set for two side chains or a shared side B; forked
+// behind the crop windows) is left for the forward pass to join; the runs' streams are joined here.
+static int build_net_input(fp_ctx *ctx, const fp_object_batch *objs, const std::vector<RenderRun> &runs, int N, const float *d_poses,
+                           const NetInputOpts &op, float *tf, float *bbox, f16 *net_in, char *rscratch, hipStream_t s,
+                           std::unique_ptr<StreamFanout> &ab) {
+  const size_t img = (size_t)160 * 160 * 8;
+  const bool two_sides = two_side_chains((int)runs.size(), N);
+  StreamFanout fo(ctx, s, two_sides ? 1 : (int)runs.size());
+  if (op.sb) op.sb->n_groups = 0;
   int k = 0;
-  for (int o = 0; o < n_obj;) {
-    int e = o + 1, cnt = objs[o].n;
-    while (e < n_obj && same_render_key(objs[o], objs[e])) cnt += objs[e++].n;
-    k += cnt > 0;
-    o = e;
+  for (const RenderRun &r : runs) {
+    const fp_object_batch &ob = objs[r.o0];
+    hipStream_t so = fo.stream_for(k++);
+    int off = r.off;
+    const float *p = d_poses + (size_t)off * 16;
+    if (!op.windows_written)
+      FP_TRY(launch_crop_window_tf(p, r.cnt, ob.K, op.crop_ratio, ob.mesh_diameter, 160, 160, tf + (size_t)off * 9, bbox + (size_t)off * 4, so));
+    if (two_sides || op.sb) ab.reset(new StreamFanout(ctx, s, 2));
+    int rc = render_net_impl(ctx, ob.mesh, p, r.cnt, ob.K, ob.H, ob.W, bbox + (size_t)off * 4, 160, 160, ob.mesh_diameter, op.normalize_xyz,
+                             op.invalid_thres, net_in + (size_t)off * img, rscratch + r.soff, r.sbytes, so);
+    hipStream_t sb_stream = ab ? ab->stream_for(0) : so;
+    for (int q = r.o0; q < r.o1 && rc == FP_OK; ++q) {
+      const fp_object_batch &oq = objs[q];
+      if (oq.n == 0) continue;
+      f16 *out = net_in + ((size_t)N + off) * img;
+      if (op.sb) {
+        op.sb->start[op.sb->n_groups] = off;
+        out = op.xB1 + (size_t)op.sb->n_groups++ * img;
+      }
+      rc = fp_crop_observed(ctx, oq.d_rgb, oq.d_geom, oq.H, oq.W, oq.K, tf + (size_t)off * 9, d_poses + (size_t)off * 16, op.sb ? 1 : oq.n, 160, 160,
+                            op.mode, oq.mesh_diameter, op.normalize_xyz, 1, out, sb_stream);
+      off += oq.n;
+    }
+    if (op.sb && rc == FP_OK) {
+      op.sb->start[op.sb->n_groups] = off;
+      rc = fp_encode_side_b(ctx, op.net, op.xB1, op.sb->n_groups, N, op.featB, sb_stream);
+    }
+    if (rc != FP_OK) {
+      if (ab) (void)ab->join();
+      (void)fo.join();
+      return rc;
+    }
   }
-  return k;
+  return fo.join();
+}
+
+// The fields of a refinement pass' tail launch that every pass fills alike (iteration `it` of `iteration`; `diameter`: of the crop windows)
+static RefineTailArgs fill_refine_tail(const fp_refine_cfg *cfg, const double *K, double diameter, float *tf, float *bbox, float *poses, int it,
+                                       int iteration) {
+  RefineTailArgs t;
+  memset(&t, 0, sizeof(t));
+  t.poses = poses;
+  t.trans_tanh = cfg->trans_rep_tanh;
+  t.tn0 = cfg->trans_normalizer[0], t.tn1 = cfg->trans_normalizer[1], t.tn2 = cfg->trans_normalizer[2];
+  t.rot_normalizer = cfg->rot_normalizer;
+  for (int i = 0; i < 9; ++i) t.K[i] = (float)K[i];
+  t.resize = 160.f;
+  t.tf = tf, t.bbox = bbox;
+  t.next_window = it + 1 < iteration;
+  t.win = crop_window_k(K, cfg->crop_ratio, diameter, 160, 160);
+  return t;
 }
 
 // `centered` (optional, one run of like objects): poses @ get_tf_to_centered_mesh() of the LAST iteration, written by that pass' tail launch
@@ -801,137 +860,73 @@ static int refine_predict_impl(fp_ctx *ctx, const fp_net *net, const fp_object_b
   if (N == 0 || iteration == 0) return FP_OK;
   hipStream_t s = (hipStream_t)stream;
   const int rot_dim = fp_net_rot_dim(net);
-  const size_t rs_total = render_scratch_total(ctx, objs, n_obj);
+  std::vector<RenderRun> runs;          // once per call: every iteration walks the same runs over the same scratch blocks
+  const size_t rs_total = render_runs(ctx, objs, n_obj, &runs);
+  const int n_runs = (int)runs.size();
   FP_TRY(fp_arena_ensure(ctx, pass_arena_bytes(N, rs_total) + (size_t)n_obj * ((size_t)4 << 20)));
-  const size_t mark = ctx->arena.off;
+  ArenaScope scope(ctx->arena);
   const size_t img = (size_t)160 * 160 * 8;
   static const bool no_shared = getenv("FP_NO_SHARED_B") != nullptr;       // A/B knob: ignore FP_REFINE_SHARED_TRANSLATION (identical results)
-  auto body = [&]() -> int {
-    TAKE(tf, float, (size_t)N * 9);
-    TAKE(bbox, float, (size_t)N * 4);
-    TAKE(trans, float, (size_t)N * 3);
-    TAKE(rot, float, (size_t)N * 6);
-    TAKE(net_in, f16, (size_t)2 * N * img);
-    float *tr = d_trans ? d_trans : trans, *ro = d_rot ? d_rot : rot;
-    const int n_runs = count_runs(objs, n_obj);
-    TAKE(rscratch, char, rs_total);                              // reused by every iteration
-    // One run of like objects in a batch that the trunk does not cut in two by hypotheses: the rendered side (crop window -> rasteriser ->
-    // encodeA) and the observed side (crop window -> observed crop -> encodeA) are two chains on two streams up to the channel concat
-    // (run_trunk): side B does not wait for the rasteriser.  Bit-identical to one chain.
-    const bool two_sides = n_runs == 1 && N < fp_trunk_split_min() && !g_one_chain;
-    // One run of like objects (one camera, one mesh, one diameter): the heads' token means, the pose update and the crop windows of
-    // the next iteration are ONE launch behind the heads (refine_tail_kernel) instead of four.  Bit-identical (FP_TAIL_SPLIT=1: the four).
-    static const bool tail_split = getenv("FP_TAIL_SPLIT") != nullptr;
-    int first = 0;
-    while (first < n_obj && objs[first].n == 0) ++first;
-    const bool fused_tail = n_runs == 1 && !tail_split && fp_hyp_chunk(N) == N;
-    // FP_REFINE_SHARED_TRANSLATION: in the FIRST iteration every hypothesis of an object has the crop window of the object's first one, so
-    // side B - the observed crop and its way through encodeA - is ONE image per object: cropped and encoded once on the side stream
-    // (fp_encode_side_b), copied into the B half of the channel concat by run_trunk.  One run of like objects, at most 8 of them, no
-    // hypothesis chunks; otherwise the plain pass runs.
-    int n_live = 0;
-    for (int o = 0; o < n_obj; ++o) n_live += objs[o].n > 0;
-    const bool shared0 = (flags & FP_REFINE_SHARED_TRANSLATION) && !no_shared && n_runs == 1 && n_live <= 8 && fp_hyp_chunk(N) == N;
-    f16 *xB1 = nullptr, *featB = nullptr;
-    if (shared0) {
-      TAKE(xB1_, f16, (size_t)n_live * img);
-      TAKE(featB_, f16, (size_t)n_live * 1600 * 128);
-      xB1 = xB1_, featB = featB_;
+  TAKE(tf, float, (size_t)N * 9);
+  TAKE(bbox, float, (size_t)N * 4);
+  TAKE(trans, float, (size_t)N * 3);
+  TAKE(rot, float, (size_t)N * 6);
+  TAKE(net_in, f16, (size_t)2 * N * img);
+  float *tr = d_trans ? d_trans : trans, *ro = d_rot ? d_rot : rot;
+  TAKE(rscratch, char, rs_total);                              // reused by every iteration
+  // One run of like objects (one camera, one mesh, one diameter): the heads' token means, the pose update and the crop windows of
+  // the next iteration are ONE launch behind the heads (refine_tail_kernel) instead of four.  Bit-identical (FP_TAIL_SPLIT=1: the four).
+  static const bool tail_split = getenv("FP_TAIL_SPLIT") != nullptr;
+  const bool fused_tail = n_runs == 1 && !tail_split && fp_hyp_chunk(N) == N;
+  // FP_REFINE_SHARED_TRANSLATION: in the FIRST iteration every hypothesis of an object has the crop window of the object's first one, so
+  // side B - the observed crop and its way through encodeA - is ONE image per object: cropped and encoded once on the side stream
+  // (fp_encode_side_b), copied into the B half of the channel concat by run_trunk.  One run of like objects, at most 8 of them, no
+  // hypothesis chunks; otherwise the plain pass runs.
+  int n_live = 0;
+  for (int o = 0; o < n_obj; ++o) n_live += objs[o].n > 0;
+  const bool shared0 = (flags & FP_REFINE_SHARED_TRANSLATION) && !no_shared && n_runs == 1 && n_live <= 8 && fp_hyp_chunk(N) == N;
+  NetInputOpts op = {0, 0.001f, cfg->crop_ratio, cfg->normalize_xyz, false, net, nullptr, nullptr, nullptr};
+  SharedB sb;
+  sb.feat = nullptr;
+  if (shared0) {
+    TAKE(xB1, f16, (size_t)n_live * img);
+    TAKE(featB, f16, (size_t)n_live * 1600 * 128);
+    op.xB1 = xB1, op.featB = featB, sb.feat = featB;
+  }
+  for (int it = 0; it < iteration; ++it) {
+    std::unique_ptr<StreamFanout> ab;
+    op.windows_written = fused_tail && it > 0;       // (from the second iteration on the previous pass' tail has written the windows)
+    op.sb = shared0 && it == 0 ? &sb : nullptr;
+    FP_TRY(build_net_input(ctx, objs, runs, N, d_poses, op, tf, bbox, net_in, rscratch, s, ab));
+    if (fused_tail) {
+      const fp_object_batch &ob = objs[runs[0].o0];
+      RefineTailArgs t = fill_refine_tail(cfg, ob.K, ob.mesh_diameter, tf, bbox, d_poses, it, iteration);
+      t.trans_scale = cfg->normalize_xyz ? (float)(ob.mesh_diameter / 2) : 1.f;
+      if (fin && it + 1 == iteration) {
+        t.centered = fin->centered;
+        for (int c = 0; c < 3; ++c) t.cneg[c] = fin->cneg[c];
+      }
+      FP_TRY(fp_refine_forward_ab(ctx, net, net_in, N, tr, ro, s, ab.get(), &t, op.sb));
+      continue;
     }
-    for (int it = 0; it < iteration; ++it) {
-      size_t voff = 0;
-      int off = 0, k = 0;
-      StreamFanout fo(ctx, s, two_sides ? 1 : n_runs);
-      std::unique_ptr<StreamFanout> ab;
-      const bool shared = shared0 && it == 0;
-      SharedB sb;
-      sb.feat = featB, sb.n_groups = 0;
-      for (int o = 0; o < n_obj;) {       // per run of like objects: crop windows + render (side A); per object: observed crop (side B)
-        int e = o + 1, cnt = objs[o].n;
-        while (e < n_obj && same_render_key(objs[o], objs[e])) cnt += objs[e++].n;
-        if (cnt > 0) {
-          const fp_object_batch &ob = objs[o];
-          hipStream_t so = fo.stream_for(k++);
-          float *p = d_poses + (size_t)off * 16;
-          if (!(fused_tail && it > 0))       // (from the second iteration on the previous pass' tail has written the windows)
-            FP_TRY(launch_crop_window_tf(p, cnt, ob.K, cfg->crop_ratio, ob.mesh_diameter, 160, 160, tf + (size_t)off * 9, bbox + (size_t)off * 4, so));
-          if (two_sides || shared) ab.reset(new StreamFanout(ctx, s, 2));          // forks behind the crop windows
-          const size_t rsb = (render_scratch_bytes(cnt, ob.mesh->d.V, ob.mesh->d.F, 160, 160, ctx->num_cu) + 255) & ~(size_t)255;
-          int rc = render_net_impl(ctx, ob.mesh, p, cnt, ob.K, ob.H, ob.W, bbox + (size_t)off * 4, 160, 160, ob.mesh_diameter,
-                                   cfg->normalize_xyz, 0.001f, net_in + (size_t)off * img, rscratch + voff, rsb, so);
-          voff += rsb;
-          hipStream_t sb_stream = ab ? ab->stream_for(0) : so;
-          for (int q = o; q < e && rc == FP_OK; ++q) {
-            const fp_object_batch &oq = objs[q];
-            if (oq.n == 0) continue;
-            if (shared) {       // the object's ONE observed crop (window and translation of its first hypothesis = of all of them)
-              sb.start[sb.n_groups] = off;
-              rc = fp_crop_observed(ctx, oq.d_rgb, oq.d_geom, oq.H, oq.W, oq.K, tf + (size_t)off * 9, d_poses + (size_t)off * 16, 1, 160, 160, 0,
-                                    oq.mesh_diameter, cfg->normalize_xyz, 1, xB1 + (size_t)sb.n_groups * img, sb_stream);
-              ++sb.n_groups;
-            } else {
-              rc = fp_crop_observed(ctx, oq.d_rgb, oq.d_geom, oq.H, oq.W, oq.K, tf + (size_t)off * 9, d_poses + (size_t)off * 16, oq.n, 160, 160, 0,
-                                    oq.mesh_diameter, cfg->normalize_xyz, 1, net_in + ((size_t)N + off) * img, sb_stream);
-            }
-            off += oq.n;
-          }
-          if (shared && rc == FP_OK) {
-            sb.start[sb.n_groups] = off;
-            rc = fp_encode_side_b(ctx, net, xB1, sb.n_groups, N, featB, sb_stream);
-          }
-          if (rc != FP_OK) {
-            if (ab) (void)ab->join();
-            (void)fo.join();
-            return rc;
-          }
-        }
-        o = e;
-      }
-      FP_TRY(fo.join());
-      if (fused_tail) {
-        const fp_object_batch &ob = objs[first];
-        RefineTailArgs t;
-        memset(&t, 0, sizeof(t));
-        t.poses = d_poses;
-        t.trans_tanh = cfg->trans_rep_tanh;
-        t.tn0 = cfg->trans_normalizer[0], t.tn1 = cfg->trans_normalizer[1], t.tn2 = cfg->trans_normalizer[2];
-        t.rot_normalizer = cfg->rot_normalizer;
-        t.trans_scale = cfg->normalize_xyz ? (float)(ob.mesh_diameter / 2) : 1.f;
-        for (int i = 0; i < 9; ++i) t.K[i] = (float)ob.K[i];
-        t.resize = 160.f;
-        t.tf = tf, t.bbox = bbox;
-        t.next_window = it + 1 < iteration;
-        t.win = crop_window_k(ob.K, cfg->crop_ratio, ob.mesh_diameter, 160, 160);
-        if (fin && it + 1 == iteration) {
-          t.centered = fin->centered;
-          for (int c = 0; c < 3; ++c) t.cneg[c] = fin->cneg[c];
-        }
-        FP_TRY(fp_refine_forward_ab(ctx, net, net_in, N, tr, ro, s, ab.get(), &t, shared ? &sb : nullptr));
-        continue;
-      }
-      FP_REQUIRE(!fin, "refine pass: the centred poses come from the fused tail launch (one run of like objects, FP_TAIL_SPLIT unset)");
-      FP_TRY(fp_refine_forward_ab(ctx, net, net_in, N, tr, ro, s, ab.get(), nullptr, shared ? &sb : nullptr));     // ONE network pass for every object (joins `ab`)
-      // pose update: one launch per run of objects with the same translation scale (one launch when they share a mesh)
-      off = 0;
-      for (int o = 0; o < n_obj;) {
-        const float trans_scale = cfg->normalize_xyz ? (float)(objs[o].mesh_diameter / 2) : 1.f;
-        int cnt = 0, e = o;
-        // (trans_rep='deepim' also needs the object's intrinsics: one launch per object)
-        while (e < n_obj && (cfg->normalize_xyz ? (float)(objs[e].mesh_diameter / 2) : 1.f) == trans_scale && (cfg->trans_rep_tanh != 2 || e == o))
-          cnt += objs[e++].n;
-        if (cnt > 0)
-          FP_TRY(launch_pose_update(d_poses + (size_t)off * 16, tr + (size_t)off * 3, ro + (size_t)off * rot_dim, cnt, rot_dim,
-                                    cfg->trans_rep_tanh, cfg->trans_normalizer[0], cfg->trans_normalizer[1], cfg->trans_normalizer[2],
-                                    cfg->rot_normalizer, trans_scale, d_poses + (size_t)off * 16, s, tf + (size_t)off * 9, objs[o].K, 160.f));      // in place
-        off += cnt;
-        o = e;
-      }
+    FP_REQUIRE(!fin, "refine pass: the centred poses come from the fused tail launch (one run of like objects, FP_TAIL_SPLIT unset)");
+    FP_TRY(fp_refine_forward_ab(ctx, net, net_in, N, tr, ro, s, ab.get(), nullptr, op.sb));     // ONE network pass for every object (joins `ab`)
+    // pose update: one launch per run of objects with the same translation scale (one launch when they share a mesh).  Not the render
+    // runs: the key here is the scale alone, and trans_rep='deepim' also needs the object's intrinsics (one launch per object)
+    for (int o = 0, off = 0; o < n_obj;) {
+      const float trans_scale = cfg->normalize_xyz ? (float)(objs[o].mesh_diameter / 2) : 1.f;
+      int cnt = 0, e = o;
+      while (e < n_obj && (cfg->normalize_xyz ? (float)(objs[e].mesh_diameter / 2) : 1.f) == trans_scale && (cfg->trans_rep_tanh != 2 || e == o))
+        cnt += objs[e++].n;
+      if (cnt > 0)
+        FP_TRY(launch_pose_update(d_poses + (size_t)off * 16, tr + (size_t)off * 3, ro + (size_t)off * rot_dim, cnt, rot_dim,
+                                  cfg->trans_rep_tanh, cfg->trans_normalizer[0], cfg->trans_normalizer[1], cfg->trans_normalizer[2],
+                                  cfg->rot_normalizer, trans_scale, d_poses + (size_t)off * 16, s, tf + (size_t)off * 9, objs[o].K, 160.f));      // in place
+      off += cnt;
+      o = e;
     }
-    return FP_OK;
-  };
-  int rc = body();
-  ctx->arena.off = mark;
-  return rc;
+  }
+  return FP_OK;
 }
 
 extern "C" int fp_refine_predict_multi(fp_ctx *ctx, const fp_net *net, const fp_object_batch *objs, int n_obj, const fp_refine_cfg *cfg,
@@ -960,57 +955,18 @@ static int score_features_impl(fp_ctx *ctx, const fp_net *net, const fp_object_b
   FP_TRY(check_objs(objs, n_obj, &N));
   if (N == 0) return FP_OK;
   hipStream_t s = (hipStream_t)stream;
-  const size_t rs_total = render_scratch_total(ctx, objs, n_obj);
+  std::vector<RenderRun> runs;
+  const size_t rs_total = render_runs(ctx, objs, n_obj, &runs);
   FP_TRY(fp_arena_ensure(ctx, pass_arena_bytes(N, rs_total)));
-  const size_t mark = ctx->arena.off;
-  const size_t img = (size_t)160 * 160 * 8;
-  auto body = [&]() -> int {
-    TAKE(tf, float, (size_t)N * 9);
-    TAKE(bbox, float, (size_t)N * 4);
-    TAKE(net_in, f16, (size_t)2 * N * img);
-    int off = 0, k = 0;
-    TAKE(rscratch, char, rs_total);
-    size_t voff = 0;
-    const int n_runs = count_runs(objs, n_obj);
-    const bool two_sides = n_runs == 1 && N < fp_trunk_split_min() && !g_one_chain;       // as in fp_refine_predict_multi
-    StreamFanout fo(ctx, s, two_sides ? 1 : n_runs);
-    std::unique_ptr<StreamFanout> ab;
-    for (int o = 0; o < n_obj;) {
-      int e = o + 1, cnt = objs[o].n;
-      while (e < n_obj && same_render_key(objs[o], objs[e])) cnt += objs[e++].n;
-      if (cnt > 0) {
-        const fp_object_batch &ob = objs[o];
-        hipStream_t so = fo.stream_for(k++);
-        const float *p = d_poses + (size_t)off * 16;
-        FP_TRY(launch_crop_window_tf(p, cnt, ob.K, crop_ratio, ob.mesh_diameter, 160, 160, tf + (size_t)off * 9, bbox + (size_t)off * 4, so));
-        if (two_sides) ab.reset(new StreamFanout(ctx, s, 2));
-        const size_t rsb = (render_scratch_bytes(cnt, ob.mesh->d.V, ob.mesh->d.F, 160, 160, ctx->num_cu) + 255) & ~(size_t)255;
-        int rc = render_net_impl(ctx, ob.mesh, p, cnt, ob.K, ob.H, ob.W, bbox + (size_t)off * 4, 160, 160, ob.mesh_diameter, normalize_xyz, 0.1f,
-                                 net_in + (size_t)off * img, rscratch + voff, rsb, so);
-        voff += rsb;
-        hipStream_t sb = ab ? ab->stream_for(0) : so;
-        for (int q = o; q < e && rc == FP_OK; ++q) {
-          const fp_object_batch &oq = objs[q];
-          if (oq.n == 0) continue;
-          rc = fp_crop_observed(ctx, oq.d_rgb, oq.d_geom, oq.H, oq.W, oq.K, tf + (size_t)off * 9, d_poses + (size_t)off * 16, oq.n, 160, 160, 1,
-                                oq.mesh_diameter, normalize_xyz, 1, net_in + ((size_t)N + off) * img, sb);
-          off += oq.n;
-        }
-        if (rc != FP_OK) {
-          if (ab) (void)ab->join();
-          (void)fo.join();
-          return rc;
-        }
-      }
-      o = e;
-    }
-    FP_TRY(fo.join());
-    FP_TRY(fp_score_features_ab(ctx, net, net_in, N, d_feats, s, ab.get(), feat_ld, with_pose ? d_poses : nullptr));
-    return FP_OK;
-  };
-  int rc = body();
-  ctx->arena.off = mark;
-  return rc;
+  ArenaScope scope(ctx->arena);
+  TAKE(tf, float, (size_t)N * 9);
+  TAKE(bbox, float, (size_t)N * 4);
+  TAKE(net_in, f16, (size_t)2 * N * (size_t)160 * 160 * 8);
+  TAKE(rscratch, char, rs_total);
+  std::unique_ptr<StreamFanout> ab;
+  const NetInputOpts op = {1, 0.1f, crop_ratio, normalize_xyz, false, nullptr, nullptr, nullptr, nullptr};
+  FP_TRY(build_net_input(ctx, objs, runs, N, d_poses, op, tf, bbox, net_in, rscratch, s, ab));
+  return fp_score_features_ab(ctx, net, net_in, N, d_feats, s, ab.get(), feat_ld, with_pose ? d_poses : nullptr);
 }
 
 extern "C" int fp_score_predict_features_multi(fp_ctx *ctx, const fp_net *net, const fp_object_batch *objs, int n_obj, double crop_ratio,
@@ -1050,6 +1006,13 @@ __global__ void track_hypotheses_kernel(const float *__restrict__ P, const float
   o[12] = 0.f, o[13] = 0.f, o[14] = 0.f, o[15] = 1.f;
 }
 
+// depth prelude of a frame: erode -> bilateral -> back-projection with `K` (src/estimater.py:256-260), + uint8 -> float colours; one launch
+static int depth_prelude(const float *d_depth, int H, int W, const double *K, float *d_depth_f, float *d_xyz, int rgb_is_u8, const void *d_rgb,
+                         float *d_rgb_f, hipStream_t s) {
+  return launch_depth_prefilter(d_depth, H, W, 0.001f, 0.8f, 100.f, 100.f, 2.f, 100000.f, K, 3.0e38f, d_depth_f, d_xyz,
+                                rgb_is_u8 ? (const uint8_t *)d_rgb : nullptr, rgb_is_u8 ? d_rgb_f : nullptr, s);
+}
+
 extern "C" int fp_track_frame(fp_ctx *ctx, const fp_track_args *a, void *stream) {
   FP_REQUIRE(ctx && a, "fp_track_frame: null argument");
   FP_REQUIRE(a->struct_size == sizeof(fp_track_args), "fp_track_frame: fp_track_args.struct_size = %zu (this library knows %zu)", a->struct_size, sizeof(fp_track_args));
@@ -1060,11 +1023,9 @@ extern "C" int fp_track_frame(fp_ctx *ctx, const fp_track_args *a, void *stream)
   const bool multi = a->n_hyp > 1;
   FP_REQUIRE(!multi || (a->score_net && a->d_perturb && a->d_poses && a->d_scores && a->d_best), "fp_track_frame: n_hyp > 1 needs score_net, d_perturb, d_poses, d_scores, d_best");
   hipStream_t s = (hipStream_t)stream;
-  // depth prelude: erode -> bilateral -> back-projection with the float32 camera matrix (src/estimater.py:256-260), + uint8 -> float colours
-  double K32[9];
+  double K32[9];          // the prelude back-projects with the float32 camera matrix
   for (int i = 0; i < 9; ++i) K32[i] = (double)(float)a->K[i];
-  FP_TRY(launch_depth_prefilter(a->d_depth, a->H, a->W, 0.001f, 0.8f, 100.f, 100.f, 2.f, 100000.f, K32, 3.0e38f, a->d_depth_f, a->d_xyz,
-                                a->rgb_is_u8 ? (const uint8_t *)a->d_rgb : nullptr, a->rgb_is_u8 ? a->d_rgb_f : nullptr, s));
+  FP_TRY(depth_prelude(a->d_depth, a->H, a->W, K32, a->d_depth_f, a->d_xyz, a->rgb_is_u8, a->d_rgb, a->d_rgb_f, s));
   const float *rgb_f = a->rgb_is_u8 ? a->d_rgb_f : (const float *)a->d_rgb;
   RefineFinal fin;
   for (int c = 0; c < 3; ++c) fin.cneg[c] = -a->model_center[c];
@@ -1079,24 +1040,20 @@ extern "C" int fp_track_frame(fp_ctx *ctx, const fp_track_args *a, void *stream)
   fp_object_batch ob = {a->mesh, rgb_f, a->d_xyz, a->H, a->W, a->K, a->mesh_diameter, a->n_hyp};
   FP_TRY(refine_predict_impl(ctx, a->refine_net, &ob, 1, a->refine_cfg, a->d_poses, a->iteration, nullptr, nullptr, stream, nullptr));
   FP_TRY(fp_arena_ensure(ctx, (size_t)a->n_hyp * (512 + 1) * 4 + 4096));
-  const size_t mark = ctx->arena.off;
+  ArenaScope scope(ctx->arena);
   float *feats = (float *)ctx->arena.take((size_t)a->n_hyp * 512 * sizeof(float));
   float *logits = (float *)ctx->arena.take((size_t)a->n_hyp * sizeof(float));
-  int rc = (feats && logits) ? FP_OK : FP_ENOMEM;
-  if (rc != FP_OK) fp_set_error("fp_track_frame: arena exhausted");
-  if (rc == FP_OK) {
-    fp_object_batch od = {a->mesh, rgb_f, a->d_depth_f, a->H, a->W, a->K, a->mesh_diameter, a->n_hyp};
-    rc = fp_score_predict_features_multi(ctx, a->score_net, &od, 1, a->score_crop_ratio, a->score_normalize_xyz, a->d_poses, feats, stream);
+  if (!feats || !logits) {
+    fp_set_error("fp_track_frame: arena exhausted");
+    return FP_ENOMEM;
   }
-  if (rc == FP_OK) {
-    ScoreTailOut o;
-    o.logits = logits, o.scores = a->d_scores, o.score_offset = 100.f, o.argmax = a->d_best;
-    o.poses = a->d_poses, o.best_pose = a->d_pose, o.best_centered = a->d_pose_of_mesh;
-    for (int c = 0; c < 3; ++c) o.cneg[c] = fin.cneg[c];
-    rc = fp_score_tail_impl(ctx, a->score_net, feats, 512, 1, a->n_hyp, o, s);
-  }
-  ctx->arena.off = mark;
-  return rc;
+  fp_object_batch od = {a->mesh, rgb_f, a->d_depth_f, a->H, a->W, a->K, a->mesh_diameter, a->n_hyp};
+  FP_TRY(fp_score_predict_features_multi(ctx, a->score_net, &od, 1, a->score_crop_ratio, a->score_normalize_xyz, a->d_poses, feats, stream));
+  ScoreTailOut o;
+  o.logits = logits, o.scores = a->d_scores, o.score_offset = 100.f, o.argmax = a->d_best;
+  o.poses = a->d_poses, o.best_pose = a->d_pose, o.best_centered = a->d_pose_of_mesh;
+  for (int c = 0; c < 3; ++c) o.cneg[c] = fin.cneg[c];
+  return fp_score_tail_impl(ctx, a->score_net, feats, 512, 1, a->n_hyp, o, s);
 }
 
 // ---- track_one of several objects of one frame (fp_track_objects): hypothesis o of the pass is object o.  Per iteration ONE render launch
@@ -1113,92 +1070,75 @@ static int track_objects_pass(fp_ctx *ctx, const fp_track_objects_args *a, const
   for (int o = 0; o < N; ++o) {
     const MeshDev &m = objs[o].mesh->d;
     solo[o] = render_objects_form(m.V, m.F, 160, 160, ctx->num_cu);
-    if (!solo[o]) rs += (render_scratch_bytes(1, m.V, m.F, 160, 160, ctx->num_cu) + 255) & ~(size_t)255;
+    if (!solo[o]) rs += render_block_bytes(ctx, objs[o].mesh, 1);
   }
   FP_TRY(fp_arena_ensure(ctx, pass_arena_bytes(N, rs) + (size_t)N * 16 * sizeof(float) + 4096));
-  const size_t mark = ctx->arena.off;
-  auto body = [&]() -> int {
-    TAKE(poses, float, (size_t)N * 16);
-    TAKE(tf, float, (size_t)N * 9);
-    TAKE(bbox, float, (size_t)N * 4);
-    TAKE(trans, float, (size_t)N * 3);
-    TAKE(rot, float, (size_t)N * 6);
-    TAKE(net_in, f16, (size_t)2 * N * img);
-    TAKE(rscratch, char, rs);
-    const float *pose_in[FP_TRACK_MAX_OBJECTS];
-    const MeshDev *mesh[FP_TRACK_MAX_OBJECTS];
-    float diam[FP_TRACK_MAX_OBJECTS], rdiam[FP_TRACK_MAX_OBJECTS];
-    double diam_d[FP_TRACK_MAX_OBJECTS];
-    int hyp[FP_TRACK_MAX_OBJECTS], n_solo = 0;
+  ArenaScope scope(ctx->arena);
+  TAKE(poses, float, (size_t)N * 16);
+  TAKE(tf, float, (size_t)N * 9);
+  TAKE(bbox, float, (size_t)N * 4);
+  TAKE(trans, float, (size_t)N * 3);
+  TAKE(rot, float, (size_t)N * 6);
+  TAKE(net_in, f16, (size_t)2 * N * img);
+  TAKE(rscratch, char, rs);
+  const float *pose_in[FP_TRACK_MAX_OBJECTS];
+  const MeshDev *mesh[FP_TRACK_MAX_OBJECTS];
+  float diam[FP_TRACK_MAX_OBJECTS], rdiam[FP_TRACK_MAX_OBJECTS];
+  double diam_d[FP_TRACK_MAX_OBJECTS];
+  int hyp[FP_TRACK_MAX_OBJECTS], n_solo = 0;
+  for (int o = 0; o < N; ++o) {
+    pose_in[o] = objs[o].d_pose;
+    diam[o] = (float)objs[o].mesh_diameter;
+    diam_d[o] = objs[o].mesh_diameter;
+    if (solo[o]) mesh[n_solo] = &objs[o].mesh->d, rdiam[n_solo] = diam[o], hyp[n_solo++] = o;
+  }
+  RenderArgs ra;          // render_net_impl's fields; mesh and diameter come per object
+  FP_TRY(fill_render(ra, objs[0].mesh, poses, N, a->K, a->H, a->W, bbox, 160, 160));
+  ra.use_light = 1;
+  ra.w_ambient = 0.8f;
+  ra.w_diffuse = 0.5f;
+  ra.net_out = net_in;
+  ra.invalid_thres = 0.001f;
+  ra.normalize_xyz = cfg->normalize_xyz;
+  CropArgs ca;            // fp_crop_observed's fields; the diameter comes per object
+  memset(&ca, 0, sizeof(ca));
+  ca.rgb = rgb_f, ca.geom = a->d_xyz, ca.tf = tf, ca.poses = poses;
+  for (int i = 0; i < 9; ++i) ca.K[i] = a->K[i];
+  ca.H = a->H, ca.W = a->W, ca.N = N, ca.Ho = 160, ca.Wo = 160, ca.mode = 0, ca.normalize_xyz = cfg->normalize_xyz, ca.out_fmt = 1;
+  ca.out = net_in + (size_t)N * img;
+  const bool two_sides = two_side_chains(1, N);       // the objects share the camera: one run, as in the one-object pass
+  for (int it = 0; it < a->iteration; ++it) {
+    if (it == 0)         // (from the second iteration on the previous pass' tail has written the windows)
+      FP_TRY(launch_crop_window_objects(pose_in, a->K, cfg->crop_ratio, diam_d, N, 160, 160, poses, tf, bbox, s));
+    std::unique_ptr<StreamFanout> ab;
+    if (two_sides) ab.reset(new StreamFanout(ctx, s, 2));          // forks behind the crop windows
+    if (n_solo) FP_TRY(launch_render_objects(ctx, ra, mesh, rdiam, hyp, n_solo, s));
+    size_t voff = 0;
     for (int o = 0; o < N; ++o) {
-      pose_in[o] = objs[o].d_pose;
-      diam[o] = (float)objs[o].mesh_diameter;
-      diam_d[o] = objs[o].mesh_diameter;
-      if (solo[o]) mesh[n_solo] = &objs[o].mesh->d, rdiam[n_solo] = diam[o], hyp[n_solo++] = o;
+      if (solo[o]) continue;
+      const size_t rsb = render_block_bytes(ctx, objs[o].mesh, 1);
+      FP_TRY(render_net_impl(ctx, objs[o].mesh, poses + (size_t)o * 16, 1, a->K, a->H, a->W, bbox + (size_t)o * 4, 160, 160, objs[o].mesh_diameter,
+                             cfg->normalize_xyz, 0.001f, net_in + (size_t)o * img, rscratch + voff, rsb, s));
+      voff += rsb;
     }
-    RenderArgs ra;          // render_net_impl's fields; mesh and diameter come per object
-    FP_TRY(fill_render(ra, objs[0].mesh, poses, N, a->K, a->H, a->W, bbox, 160, 160));
-    ra.use_light = 1;
-    ra.w_ambient = 0.8f;
-    ra.w_diffuse = 0.5f;
-    ra.net_out = net_in;
-    ra.invalid_thres = 0.001f;
-    ra.normalize_xyz = cfg->normalize_xyz;
-    CropArgs ca;            // fp_crop_observed's fields; the diameter comes per object
-    memset(&ca, 0, sizeof(ca));
-    ca.rgb = rgb_f, ca.geom = a->d_xyz, ca.tf = tf, ca.poses = poses;
-    for (int i = 0; i < 9; ++i) ca.K[i] = a->K[i];
-    ca.H = a->H, ca.W = a->W, ca.N = N, ca.Ho = 160, ca.Wo = 160, ca.mode = 0, ca.normalize_xyz = cfg->normalize_xyz, ca.out_fmt = 1;
-    ca.out = net_in + (size_t)N * img;
-    // as in the one-object pass: the observed side is a chain of its own up to the channel concat
-    const bool two_sides = N < fp_trunk_split_min() && !g_one_chain;
-    for (int it = 0; it < a->iteration; ++it) {
-      if (it == 0)         // (from the second iteration on the previous pass' tail has written the windows)
-        FP_TRY(launch_crop_window_objects(pose_in, a->K, cfg->crop_ratio, diam_d, N, 160, 160, poses, tf, bbox, s));
-      std::unique_ptr<StreamFanout> ab;
-      if (two_sides) ab.reset(new StreamFanout(ctx, s, 2));          // forks behind the crop windows
-      if (n_solo) FP_TRY(launch_render_objects(ctx, ra, mesh, rdiam, hyp, n_solo, s));
-      size_t voff = 0;
-      for (int o = 0; o < N; ++o) {
-        if (solo[o]) continue;
-        const MeshDev &m = objs[o].mesh->d;
-        const size_t rsb = (render_scratch_bytes(1, m.V, m.F, 160, 160, ctx->num_cu) + 255) & ~(size_t)255;
-        FP_TRY(render_net_impl(ctx, objs[o].mesh, poses + (size_t)o * 16, 1, a->K, a->H, a->W, bbox + (size_t)o * 4, 160, 160, objs[o].mesh_diameter,
-                               cfg->normalize_xyz, 0.001f, net_in + (size_t)o * img, rscratch + voff, rsb, s));
-        voff += rsb;
-      }
-      {
-        hipStream_t sb = ab ? ab->stream_for(0) : s;
-        ProfScope ps(ctx, sb, "crop", (double)N * 160 * 160 * 16.0);      // bytes written
-        FP_TRY(launch_crop_observed_objects(ca, diam, sb));
-      }
-      RefineTailArgs t;
-      memset(&t, 0, sizeof(t));
-      t.poses = poses;
-      t.trans_tanh = cfg->trans_rep_tanh;
-      t.tn0 = cfg->trans_normalizer[0], t.tn1 = cfg->trans_normalizer[1], t.tn2 = cfg->trans_normalizer[2];
-      t.rot_normalizer = cfg->rot_normalizer;
-      for (int i = 0; i < 9; ++i) t.K[i] = (float)a->K[i];
-      t.resize = 160.f;
-      t.tf = tf, t.bbox = bbox;
-      t.next_window = it + 1 < a->iteration;
-      t.win = crop_window_k(a->K, cfg->crop_ratio, objs[0].mesh_diameter, 160, 160);
-      t.obj.n = N;
-      const bool last = it + 1 == a->iteration;
-      for (int o = 0; o < N; ++o) {
-        t.obj.trans_scale[o] = cfg->normalize_xyz ? (float)(objs[o].mesh_diameter / 2) : 1.f;
-        t.obj.radius[o] = crop_window_k(a->K, cfg->crop_ratio, objs[o].mesh_diameter, 160, 160).radius;
-        for (int c = 0; c < 3; ++c) t.obj.cneg[o][c] = -objs[o].model_center[c];
-        t.obj.centered[o] = last ? objs[o].d_pose_of_mesh : nullptr;
-        t.obj.pose_out[o] = last ? objs[o].d_pose : nullptr;
-      }
-      FP_TRY(fp_refine_forward_ab(ctx, a->refine_net, net_in, N, trans, rot, s, ab.get(), &t, nullptr));
+    {
+      hipStream_t sb = ab ? ab->stream_for(0) : s;
+      ProfScope ps(ctx, sb, "crop", (double)N * 160 * 160 * 16.0);      // bytes written
+      FP_TRY(launch_crop_observed_objects(ca, diam, sb));
     }
-    return FP_OK;
-  };
-  int rc = body();
-  ctx->arena.off = mark;
-  return rc;
+    RefineTailArgs t = fill_refine_tail(cfg, a->K, objs[0].mesh_diameter, tf, bbox, poses, it, a->iteration);
+    t.obj.n = N;
+    const bool last = it + 1 == a->iteration;
+    for (int o = 0; o < N; ++o) {
+      t.obj.trans_scale[o] = cfg->normalize_xyz ? (float)(objs[o].mesh_diameter / 2) : 1.f;
+      t.obj.radius[o] = crop_window_k(a->K, cfg->crop_ratio, objs[o].mesh_diameter, 160, 160).radius;
+      for (int c = 0; c < 3; ++c) t.obj.cneg[o][c] = -objs[o].model_center[c];
+      t.obj.centered[o] = last ? objs[o].d_pose_of_mesh : nullptr;
+      t.obj.pose_out[o] = last ? objs[o].d_pose : nullptr;
+    }
+    FP_TRY(fp_refine_forward_ab(ctx, a->refine_net, net_in, N, trans, rot, s, ab.get(), &t, nullptr));
+  }
+  return FP_OK;
 }
 
 extern "C" int fp_track_objects(fp_ctx *ctx, const fp_track_objects_args *a, void *stream) {
@@ -1219,8 +1159,7 @@ extern "C" int fp_track_objects(fp_ctx *ctx, const fp_track_objects_args *a, voi
   // the depth prelude of fp_track_frame, once for all objects
   double K32[9];
   for (int i = 0; i < 9; ++i) K32[i] = (double)(float)a->K[i];
-  FP_TRY(launch_depth_prefilter(a->d_depth, a->H, a->W, 0.001f, 0.8f, 100.f, 100.f, 2.f, 100000.f, K32, 3.0e38f, a->d_depth_f, a->d_xyz,
-                                a->rgb_is_u8 ? (const uint8_t *)a->d_rgb : nullptr, a->rgb_is_u8 ? a->d_rgb_f : nullptr, s));
+  FP_TRY(depth_prelude(a->d_depth, a->H, a->W, K32, a->d_depth_f, a->d_xyz, a->rgb_is_u8, a->d_rgb, a->d_rgb_f, s));
   return track_objects_pass(ctx, a, a->rgb_is_u8 ? a->d_rgb_f : (const float *)a->d_rgb, s);
 }
 
@@ -1228,16 +1167,13 @@ extern "C" int fp_track_objects(fp_ctx *ctx, const fp_track_objects_args *a, voi
 static int mask_stats_objects(fp_ctx *ctx, const float *d_depth, const MaskStatsObjs &mo, int H, int W, float min_depth, int32_t *h_stats,
                               float *h_median, hipStream_t s) {
   FP_TRY(fp_arena_ensure(ctx, 4096));
-  const size_t mark = ctx->arena.off;
+  ArenaScope scope(ctx->arena);      // (released behind the copy and the wait below: host bookkeeping, nothing else takes in between)
   int *d_out = (int *)ctx->arena.take((size_t)mo.n * 8 * sizeof(int));
   FP_REQUIRE(d_out, "mask stats: arena exhausted");
-  int rc;
   {
     ProfScope ps(ctx, s, "mask_stats", (double)H * W * mo.n);
-    rc = launch_mask_depth_stats_objects(d_depth, mo, H, W, min_depth, d_out, s);
+    FP_TRY(launch_mask_depth_stats_objects(d_depth, mo, H, W, min_depth, d_out, s));
   }
-  ctx->arena.off = mark;
-  if (rc != FP_OK) return rc;
   int host[FP_TRACK_MAX_OBJECTS * 8];
   FP_CHECK_HIP(hipMemcpyAsync(host, d_out, (size_t)mo.n * 8 * sizeof(int), hipMemcpyDeviceToHost, s));      // ONE copy for all objects
   FP_CHECK_HIP(hipStreamSynchronize(s));
@@ -1337,8 +1273,7 @@ extern "C" int fp_register_objects(fp_ctx *ctx, fp_register_objects_args *a, voi
   // back-projection register() uses (Utils.depth2xyzmap), which overwrites the prelude's float32 one
   {
     ProfScope ps(ctx, s, "prelude", (double)a->H * a->W);
-    FP_TRY(launch_depth_prefilter(a->d_depth, a->H, a->W, 0.001f, 0.8f, 100.f, 100.f, 2.f, 100000.f, a->K, 3.0e38f, a->d_depth_f, a->d_xyz,
-                                  a->rgb_is_u8 ? (const uint8_t *)a->d_rgb : nullptr, a->rgb_is_u8 ? a->d_rgb_f : nullptr, s));
+    FP_TRY(depth_prelude(a->d_depth, a->H, a->W, a->K, a->d_depth_f, a->d_xyz, a->rgb_is_u8, a->d_rgb, a->d_rgb_f, s));
   }
   FP_TRY(launch_depth2xyz_f64(a->d_depth_f, a->H, a->W, a->K, a->d_xyz, s));
   const float *rgb_f = a->rgb_is_u8 ? a->d_rgb_f : (const float *)a->d_rgb;
@@ -1379,7 +1314,7 @@ extern "C" int fp_register_objects(fp_ctx *ctx, fp_register_objects_args *a, voi
   for (int p = 0, k0 = 0; p < n_pass; ++p) {
     int k1 = k0, np = 0;
     while (k1 < n_live && pass_of[k1] == p) np += batch[k1++].n;
-    const size_t need = pass_arena_bytes(np, render_scratch_total(ctx, batch + k0, k1 - k0)) + (size_t)(k1 - k0) * ((size_t)4 << 20);
+    const size_t need = pass_arena_bytes(np, render_runs(ctx, batch + k0, k1 - k0, nullptr)) + (size_t)(k1 - k0) * ((size_t)4 << 20);
     pass_bytes = need > pass_bytes ? need : pass_bytes;
     k0 = k1;
   }
@@ -1387,119 +1322,107 @@ extern "C" int fp_register_objects(fp_ctx *ctx, fp_register_objects_args *a, voi
   const size_t own = (size_t)N * (16 + 512 + 2) * sizeof(float) + ((size_t)1 << 20);
   const size_t tail_bytes = (size_t)N * (1024 * 4 + 4 * 8) + ((size_t)2 << 20);
   FP_TRY(fp_arena_ensure(ctx, own + (pass_bytes > tail_bytes ? pass_bytes : tail_bytes) + ((size_t)1 << 20)));
-  const size_t mark = ctx->arena.off;
-  auto body = [&]() -> int {
-    TAKE(hyp, float, (size_t)N * 16);
-    TAKE(feats, float, (size_t)N * 512);
-    TAKE(logits, float, (size_t)N);
-    TAKE(scores, float, (size_t)N);
-    RegHypObjs ho;
-    memset(&ho, 0, sizeof(ho));
-    ho.n_obj = n_live;
-    for (int i = 0; i < 9; ++i) ho.kinv[i] = a->K_inv[i];
-    for (int k = 0; k < n_live; ++k) fill_hyp_object(ho, k, a->objs[live[k]].d_rot_grid, a->objs[live[k]].n_hyp, off[k], st + live[k] * 6, med[live[k]]);
-    FP_TRY(launch_register_hypotheses(ho, hyp, s));
-    for (int p = 0, k0 = 0; p < n_pass; ++p) {
-      int k1 = k0;
-      while (k1 < n_live && pass_of[k1] == p) ++k1;
-      float *ph = hyp + (size_t)off[k0] * 16;
-      // (every hypothesis of an object has the object's guessed translation: FP_REFINE_SHARED_TRANSLATION holds by construction)
-      FP_TRY(refine_predict_impl(ctx, a->refine_net, batch + k0, k1 - k0, a->refine_cfg, ph, a->iteration, nullptr, nullptr, stream, nullptr,
-                                 FP_REFINE_SHARED_TRANSLATION));
-      for (int k = k0; k < k1; ++k) batch[k].d_geom = a->d_depth_f;         // the scorer reads the filtered depth
-      FP_TRY(score_features_impl(ctx, a->score_net, batch + k0, k1 - k0, a->score_crop_ratio, a->score_normalize_xyz, ph, feats + (size_t)off[k0] * 512,
-                                 512, false, stream));
-      for (int k = k0; k < k1; ++k) {      // att_cross couples the hypotheses of ONE object: a group of its own length per object
-        ScoreTailOut to;
-        to.logits = logits + off[k], to.scores = scores + off[k], to.score_offset = 100.f;
-        FP_TRY(fp_score_tail_impl(ctx, a->score_net, feats + (size_t)off[k] * 512, 512, 1, batch[k].n, to, s));
-      }
-      k0 = k1;
+  ArenaScope scope(ctx->arena);
+  TAKE(hyp, float, (size_t)N * 16);
+  TAKE(feats, float, (size_t)N * 512);
+  TAKE(logits, float, (size_t)N);
+  TAKE(scores, float, (size_t)N);
+  RegHypObjs ho;
+  memset(&ho, 0, sizeof(ho));
+  ho.n_obj = n_live;
+  for (int i = 0; i < 9; ++i) ho.kinv[i] = a->K_inv[i];
+  for (int k = 0; k < n_live; ++k) fill_hyp_object(ho, k, a->objs[live[k]].d_rot_grid, a->objs[live[k]].n_hyp, off[k], st + live[k] * 6, med[live[k]]);
+  FP_TRY(launch_register_hypotheses(ho, hyp, s));
+  for (int p = 0, k0 = 0; p < n_pass; ++p) {
+    int k1 = k0;
+    while (k1 < n_live && pass_of[k1] == p) ++k1;
+    float *ph = hyp + (size_t)off[k0] * 16;
+    // (every hypothesis of an object has the object's guessed translation: FP_REFINE_SHARED_TRANSLATION holds by construction)
+    FP_TRY(refine_predict_impl(ctx, a->refine_net, batch + k0, k1 - k0, a->refine_cfg, ph, a->iteration, nullptr, nullptr, stream, nullptr,
+                               FP_REFINE_SHARED_TRANSLATION));
+    for (int k = k0; k < k1; ++k) batch[k].d_geom = a->d_depth_f;         // the scorer reads the filtered depth
+    FP_TRY(score_features_impl(ctx, a->score_net, batch + k0, k1 - k0, a->score_crop_ratio, a->score_normalize_xyz, ph, feats + (size_t)off[k0] * 512,
+                               512, false, stream));
+    for (int k = k0; k < k1; ++k) {      // att_cross couples the hypotheses of ONE object: a group of its own length per object
+      ScoreTailOut to;
+      to.logits = logits + off[k], to.scores = scores + off[k], to.score_offset = 100.f;
+      FP_TRY(fp_score_tail_impl(ctx, a->score_net, feats + (size_t)off[k] * 512, 512, 1, batch[k].n, to, s));
     }
-    RegRankObjs ro;
-    memset(&ro, 0, sizeof(ro));
-    ro.n_obj = n_live;
-    for (int k = 0; k < n_live; ++k) {
-      const fp_register_object &ob = a->objs[live[k]];
-      ro.n[k] = ob.n_hyp, ro.off[k] = off[k];
-      ro.poses_out[k] = ob.d_poses, ro.scores_out[k] = ob.d_scores, ro.order_out[k] = (long long *)ob.d_order, ro.pose_of_mesh[k] = ob.d_pose_of_mesh;
-      for (int c = 0; c < 3; ++c) ro.cneg[k][c] = -ob.model_center[c];
-    }
-    return launch_register_rank(ro, hyp, scores, s);          // the call's last launch: the results land in the objects' buffers (pinned host: no copy)
-  };
-  int rc = body();
-  ctx->arena.off = mark;
-  return rc;
+    k0 = k1;
+  }
+  RegRankObjs ro;
+  memset(&ro, 0, sizeof(ro));
+  ro.n_obj = n_live;
+  for (int k = 0; k < n_live; ++k) {
+    const fp_register_object &ob = a->objs[live[k]];
+    ro.n[k] = ob.n_hyp, ro.off[k] = off[k];
+    ro.poses_out[k] = ob.d_poses, ro.scores_out[k] = ob.d_scores, ro.order_out[k] = (long long *)ob.d_order, ro.pose_of_mesh[k] = ob.d_pose_of_mesh;
+    for (int c = 0; c < 3; ++c) ro.cneg[k][c] = -ob.model_center[c];
+  }
+  return launch_register_rank(ro, hyp, scores, s);          // the call's last launch: the results land in the objects' buffers (pinned host: no copy)
 }
 
 int conv_ksplit(const ConvArgs &a, int num_cu);      // conv.hip
 
 // ---- building blocks ---------------------------------------------------------------------------------
+// one convolution launch on its own: fp16 NHWC output, no split, no post-add
+static ConvArgs conv_args(const void *d_in, const void *d_w, const float *d_bias, const void *d_res, void *d_out, int Nimg, int H, int W, int Cin,
+                          int Cout, int KH, int KW, int stride, int pad, int relu) {
+  ConvArgs a;
+  memset(&a, 0, sizeof(a));
+  a.in = (const f16 *)d_in;
+  a.w = (const f16 *)d_w;
+  a.bias = d_bias;
+  a.res = (const f16 *)d_res;
+  a.out = d_out;
+  a.Nimg = Nimg, a.H = H, a.W = W, a.Cin = Cin, a.Cout = Cout, a.KH = KH, a.KW = KW, a.stride = stride, a.pad = pad;
+  a.Ho = (H + 2 * pad - KH) / stride + 1;
+  a.Wo = (W + 2 * pad - KW) / stride + 1;
+  a.Kpad = (KH * KW * Cin + 31) / 32 * 32;
+  a.M = Nimg * a.Ho * a.Wo;
+  a.relu = relu;
+  a.out_ld = Cout;
+  a.split_m = 0x7fffffff;
+  a.post_period = 1;
+  a.tokens = 400;
+  return a;
+}
+
 extern "C" int fp_conv2d_f16(fp_ctx *ctx, const void *d_in, int Nimg, int H, int W, int Cin, const void *d_w_packed, const float *d_bias,
                              int Cout, int KH, int KW, int stride, int pad, const void *d_res, int relu, void *d_out, int out_f32,
                              void *stream) {
   FP_REQUIRE(ctx && d_in && d_w_packed && d_bias && d_out, "fp_conv2d_f16: null argument");
   FP_REQUIRE(stride >= 1 && pad >= 0 && Nimg >= 0, "fp_conv2d_f16: bad stride/pad/N");
-  ConvArgs a;
-  memset(&a, 0, sizeof(a));
-  a.in = (const f16 *)d_in;
-  a.w = (const f16 *)d_w_packed;
-  a.bias = d_bias;
-  a.res = (const f16 *)d_res;
-  a.out = d_out;
-  a.Nimg = Nimg;
-  a.H = H;
-  a.W = W;
-  a.Cin = Cin;
-  a.KH = KH;
-  a.KW = KW;
-  a.stride = stride;
-  a.pad = pad;
-  a.Ho = (H + 2 * pad - KH) / stride + 1;
-  a.Wo = (W + 2 * pad - KW) / stride + 1;
-  a.Cout = Cout;
-  a.Kpad = (KH * KW * Cin + 31) / 32 * 32;
-  a.M = Nimg * a.Ho * a.Wo;
-  a.relu = relu;
+  ConvArgs a = conv_args(d_in, d_w_packed, d_bias, d_res, d_out, Nimg, H, W, Cin, Cout, KH, KW, stride, pad, relu);
   a.out_mode = out_f32 ? 1 : 0;
-  a.out_ld = Cout;
-  a.split_m = 0x7fffffff;
-  a.post_period = 1;
-  a.tokens = 400;
+  ArenaScope scope(ctx->arena);        // the forms below take packed weights or scratch, consumed on the stream before anything else takes them
   // a few images of a 3x3 stride-1 trunk layer: conv_small.hip on weights packed here, as inside the networks (a tracking frame)
   if (!out_f32 && conv_small_shape(a, ctx->num_cu)) {
     const size_t bytes = small_packed_halfs(Cout, Cin) * sizeof(f16);
     FP_TRY(fp_arena_ensure(ctx, bytes + 4096));
-    const size_t mark = ctx->arena.off;
     f16 *pk = (f16 *)ctx->arena.take(bytes);
-    int rc = pk ? small_pack_weights(a.w, Cout, Cin, a.Kpad, pk, (hipStream_t)stream) : FP_ENOMEM;
+    if (!pk) return FP_ENOMEM;
+    FP_TRY(small_pack_weights(a.w, Cout, Cin, a.Kpad, pk, (hipStream_t)stream));
     a.wsm = pk;
-    if (rc == FP_OK) rc = launch_conv(ctx, a, (hipStream_t)stream);
-    ctx->arena.off = mark;
-    return rc;
+    return launch_conv(ctx, a, (hipStream_t)stream);
   }
   // launches of a few workgroups take the split-K form of the 3x3 stride-1 kernel, as inside the networks (2 .. 4 hypotheses)
   a.ksplit = out_f32 ? 0 : conv_ksplit(a, ctx->num_cu);
   if (a.ksplit > 1) {
     const size_t bytes = (size_t)a.ksplit * a.M * a.Cout * sizeof(float);
     FP_TRY(fp_arena_ensure(ctx, bytes + 4096));
-    const size_t mark = ctx->arena.off;
     a.splitk = (float *)ctx->arena.take(bytes);
-    int rc = a.splitk ? launch_conv(ctx, a, (hipStream_t)stream) : FP_ENOMEM;
-    ctx->arena.off = mark;        // the scratch is consumed by the finishing pass on the same stream before anything else takes it
-    return rc;
+    return a.splitk ? launch_conv(ctx, a, (hipStream_t)stream) : FP_ENOMEM;
   }
   a.ksplit = 0;
   if (!out_f32 && a.M >= S2_MIN_PIXELS && s2_supported(a)) {       // the band-in-LDS form of the 3x3 stride-2 layers, as inside the networks
     const size_t bytes = s2_packed_halfs(Cout, Cin) * sizeof(f16);
     FP_TRY(fp_arena_ensure(ctx, bytes + 4096));
-    const size_t mark = ctx->arena.off;
     f16 *pk = (f16 *)ctx->arena.take(bytes);
-    int rc = pk ? s2_pack_weights(a.w, Cout, Cin, a.Kpad, pk, (hipStream_t)stream) : FP_ENOMEM;
+    if (!pk) return FP_ENOMEM;
+    FP_TRY(s2_pack_weights(a.w, Cout, Cin, a.Kpad, pk, (hipStream_t)stream));
     a.wpk = pk;
-    if (rc == FP_OK) rc = launch_conv(ctx, a, (hipStream_t)stream);
-    ctx->arena.off = mark;
-    return rc;
+    return launch_conv(ctx, a, (hipStream_t)stream);
   }
   return launch_conv(ctx, a, (hipStream_t)stream);
 }
@@ -1510,75 +1433,35 @@ extern "C" int fp_conv3x3_band_f16(fp_ctx *ctx, const void *d_in, int Nimg, int 
                                    int relu, void *d_out, void *stream) {
   FP_REQUIRE(ctx && d_in && d_w_packed && d_bias && d_out && Nimg >= 0, "fp_conv3x3_band_f16: bad argument");
   FP_REQUIRE(C == 128 || C == 256, "fp_conv3x3_band_f16: C=%d (128 or 256)", C);
-  ConvArgs a;
-  memset(&a, 0, sizeof(a));
-  a.in = (const f16 *)d_in;
-  a.w = (const f16 *)d_w_packed;
-  a.bias = d_bias;
-  a.res = (const f16 *)d_res;
-  a.out = d_out;
-  a.Nimg = Nimg;
-  a.H = a.W = a.Ho = a.Wo = 40;
-  a.Cin = a.Cout = C;
-  a.KH = a.KW = 3;
-  a.stride = 1;
-  a.pad = 1;
-  a.Kpad = 9 * C;
-  a.M = Nimg * 1600;
-  a.relu = relu;
-  a.out_ld = C;
-  a.split_m = 0x7fffffff;
-  a.post_period = 1;
-  a.tokens = 400;
+  ConvArgs a = conv_args(d_in, d_w_packed, d_bias, d_res, d_out, Nimg, 40, 40, C, C, 3, 3, 1, 1, relu);
   if (a.M == 0) return FP_OK;
   const size_t bytes = s2_packed_halfs(C, C) * sizeof(f16);
   FP_TRY(fp_arena_ensure(ctx, bytes + 4096));
-  const size_t mark = ctx->arena.off;
+  ArenaScope scope(ctx->arena);
   f16 *pk = (f16 *)ctx->arena.take(bytes);
-  int rc = pk ? s2_pack_weights(a.w, C, C, a.Kpad, pk, (hipStream_t)stream, 2, 1) : FP_ENOMEM;
+  if (!pk) return FP_ENOMEM;
+  FP_TRY(s2_pack_weights(a.w, C, C, a.Kpad, pk, (hipStream_t)stream, 2, 1));
   a.wpk = pk;
-  if (rc == FP_OK) rc = launch_conv_s1b(ctx, a, (hipStream_t)stream);
-  ctx->arena.off = mark;
-  return rc;
+  return launch_conv_s1b(ctx, a, (hipStream_t)stream);
 }
 
 extern "C" int fp_conv3x3_wino_f16(fp_ctx *ctx, const void *d_in, int Nimg, int HW, int Cin, int Cout, const float *h_weight, const float *d_bias,
                                    const void *d_res, int relu, void *d_out, void *stream) {
   FP_REQUIRE(ctx && d_in && h_weight && d_bias && d_out && Nimg >= 0, "fp_conv3x3_wino_f16: bad argument");
   FP_REQUIRE((HW == 40 || HW == 20) && Cin % 32 == 0 && Cin >= 64 && Cout % 64 == 0, "fp_conv3x3_wino_f16: HW=%d Cin=%d Cout=%d unsupported", HW, Cin, Cout);
-  ConvArgs a;
-  memset(&a, 0, sizeof(a));
-  a.in = (const f16 *)d_in;
-  a.bias = d_bias;
-  a.res = (const f16 *)d_res;
-  a.out = d_out;
-  a.Nimg = Nimg;
-  a.H = a.W = a.Ho = a.Wo = HW;
-  a.Cin = Cin, a.Cout = Cout;
-  a.KH = a.KW = 3;
-  a.stride = 1;
-  a.pad = 1;
-  a.Kpad = 9 * Cin;
-  a.M = Nimg * HW * HW;
-  a.relu = relu;
-  a.out_ld = Cout;
-  a.split_m = 0x7fffffff;
-  a.post_period = 1;
-  a.tokens = 400;
+  ConvArgs a = conv_args(d_in, nullptr, d_bias, d_res, d_out, Nimg, HW, HW, Cin, Cout, 3, 3, 1, 1, relu);      // (the weights: a.wwino below)
   if (a.M == 0) return FP_OK;
   std::vector<f16> hu(wino_packed_halfs(Cout, Cin));
   wino_pack_weights(h_weight, nullptr, Cout, Cin, hu.data());
   const size_t bytes = hu.size() * sizeof(f16);
   FP_TRY(fp_arena_ensure(ctx, bytes + 4096));
-  const size_t mark = ctx->arena.off;
+  ArenaScope scope(ctx->arena);
   f16 *pk = (f16 *)ctx->arena.take(bytes);
-  int rc = pk ? FP_OK : FP_ENOMEM;
-  if (rc == FP_OK && hipMemcpyAsync(pk, hu.data(), bytes, hipMemcpyHostToDevice, (hipStream_t)stream) != hipSuccess) rc = FP_EHIP;
+  if (!pk) return FP_ENOMEM;
+  if (hipMemcpyAsync(pk, hu.data(), bytes, hipMemcpyHostToDevice, (hipStream_t)stream) != hipSuccess) return FP_EHIP;
   a.wwino = pk;
-  if (rc == FP_OK) rc = launch_conv_wino(ctx, a, (hipStream_t)stream);
-  if (rc == FP_OK && hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = FP_EHIP;      // (hu is a host temporary)
-  ctx->arena.off = mark;
-  return rc;
+  FP_TRY(launch_conv_wino(ctx, a, (hipStream_t)stream));
+  return hipStreamSynchronize((hipStream_t)stream) == hipSuccess ? FP_OK : FP_EHIP;      // (hu is a host temporary)
 }
 
 extern "C" int fp_attention_f16(fp_ctx *ctx, const void *d_qk, const void *d_vt, int B, int T, void *d_out, void *stream) {

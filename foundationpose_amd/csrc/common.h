@@ -78,6 +78,17 @@ struct Arena {
   }
 };
 
+// Everything taken inside a scope goes back on every way out of it.  Declared BEFORE a StreamFanout of the same scope: the side streams
+// are then joined before the offset they may still be writing behind goes back.
+struct ArenaScope {
+  Arena &arena;
+  const size_t off;
+  explicit ArenaScope(Arena &a) : arena(a), off(a.off) {}
+  ~ArenaScope() { arena.off = off; }
+  ArenaScope(const ArenaScope &) = delete;
+  ArenaScope &operator=(const ArenaScope &) = delete;
+};
+
 struct fp_ctx {
   int device = 0;
   Arena arena;

@@ -173,6 +173,32 @@ def test_multi_object_pass_equals_per_object_passes(env):
   assert r2.shape == (152, 4, 4)
 
 
+def test_empty_objects_leave_the_runs_of_like_objects_unchanged(env):
+  """The runs of like objects of a multi-object pass (hypothesis offsets, render scratch blocks, launches) with objects of zero
+  hypotheses in between: two meshes A and B of different diameters in one frame, [A x3, A x2, B x4, A x1] against the same list with an
+  empty object inside the first run, one in front of B's and one in front of the last.  An empty object adds nothing to the run it falls
+  in, so both lists are the runs A x5 | B x4 | A x1: refined poses (two iterations) and scorer features are equal bit for bit."""
+  sc, refiner, scorer = env['sc'], env['refiner'], env['scorer']
+  sc2 = util.scene(1)
+  frame = dict(rgb=sc['rgb'], depth=env['depth'], xyz_map=env['xyz'], K=sc['K'])
+  A = dict(frame, mesh_tensors=env['mt'], mesh_diameter=sc['diameter'])
+  # (the synthetic bottles all have one diameter: B is the second one at 0.9 of its size)
+  B = dict(frame, mesh_tensors=util.to_dev(dict(sc2['mt'], pos=sc2['mt']['pos'] * 0.9)), mesh_diameter=0.9 * sc2['diameter'])
+  assert B['mesh_diameter'] != A['mesh_diameter']
+  dense = ((A, 3), (A, 2), (B, 4), (A, 1))
+  sparse = ((A, 3), (A, 0), (A, 2), (B, 0), (B, 4), (A, 0), (A, 1))
+
+  def objects(spec, poses):
+    offs = np.cumsum([0] + [n for _, n in spec])
+    return [dict(ob, ob_in_cams=poses[a:a + n], shared_translation=False) for (ob, n), a in zip(spec, offs)]
+  poses = torch.from_numpy(util.hypotheses(sc, 10, jitter_seed=3)).cuda()
+  refined = refiner.predict_multi(objects(dense, poses), iteration=2)
+  assert refined.shape == (10, 4, 4) and torch.equal(refined, refiner.predict_multi(objects(sparse, poses), iteration=2))
+  assert float((refined - poses).abs().max()) > 1e-4                   # the pass moved the poses
+  feats = scorer.extract_features_multi(objects(dense, refined))
+  assert feats.shape == (10, 512) and torch.equal(feats, scorer.extract_features_multi(objects(sparse, refined)))
+
+
 def test_four_objects_in_one_network_pass_1008(env):
   """configs[3] at full size in ONE pass: RefineNet and the ScoreNet feature extractor on 4 x 252 = 1008 hypotheses
   (2016 input images, 51.6 M stem pixels: the largest tensors the 32-bit lane offsets of the kernels see) must equal four
