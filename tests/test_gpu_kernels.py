@@ -501,29 +501,31 @@ def _pack_conv_weight(w, cin_pad):
 
 
 @pytest.mark.parametrize('shape', [
-  # (N, H, W, Cin, Cout, k, stride, residual, relu)
-  (3, 40, 40, 128, 128, 3, 1, True, True),
-  (2, 40, 40, 256, 256, 3, 1, False, True),
-  (2, 80, 80, 64, 128, 3, 2, False, True),
-  (3, 20, 20, 512, 512, 3, 1, True, True),
-  (2, 40, 40, 256, 512, 3, 2, False, True),
-  (328, 40, 40, 128, 128, 3, 1, True, True),        # 1025 tiles: four full rounds + one tile (quarter tiles for the remainder)
+  # (N, H, W, Cin, Cout, k, stride, residual, relu).  The form named is the one the fp16 output runs on 256 CUs (fp_conv2d_f16, launch_conv,
+  # conv_small_shape, conv_ksplit, halo_plan); the fp32 output of every shape runs the generic conv_igemm2_kernel.  tests/tools/conv_ref.py
+  # lists one case per form and instantiation.
+  (3, 40, 40, 128, 128, 3, 1, True, True),          # conv_halo.hip, tail tiles only: 38 tiles of 128 pixels (600 workgroups would be too many for conv_small.hip, 4 chunks too few to split K)
+  (2, 40, 40, 256, 256, 3, 1, False, True),         # conv_halo.hip split-K, 4 shares of 2 chunks + finishing pass (800 workgroups: not conv_small.hip)
+  (2, 80, 80, 64, 128, 3, 2, False, True),          # conv_small.hip <1, 80, 2, 4>: 400 workgroups, tiles that straddle rows and the two images
+  (3, 20, 20, 512, 512, 3, 1, True, True),          # conv_halo.hip split-K, 4 shares of 4 chunks (608 workgroups: not conv_small.hip)
+  (2, 40, 40, 256, 512, 3, 2, False, True),         # conv_small.hip <2, 40, 2>: 400 workgroups
+  (328, 40, 40, 128, 128, 3, 1, True, True),        # conv_halo.hip: four whole rounds of 256 tiles of 512 pixels + 4 tail tiles of 128 (conv_s1b.hip needs packed weights: fp_conv3x3_band_f16)
   (9, 40, 40, 256, 512, 3, 2, False, True),         # band-in-LDS stride-2 kernel (conv_s2.hip): 8-row tiles straddle images, last tile partial
   (9, 40, 40, 64, 128, 3, 2, False, False),         # the same with 128-cout blocks, no ReLU
-  (2, 160, 160, 6, 64, 7, 2, False, True),
-  (1, 20, 20, 512, 512, 3, 1, True, True),          # one hypothesis: conv_small.hip (13 x 16 workgroups; FP_SMALL=0: split-K, 8 shares of 2 chunks + finishing pass)
-  (1, 40, 40, 256, 256, 3, 1, False, True),         # split-K, 4 shares of 2 chunks
-  (2, 40, 40, 128, 128, 3, 1, True, False),         # 26 quarter tiles of a 128-channel layer: too few chunks to split, one launch of 128-pixel tiles, no ReLU
-  (2, 40, 40, 256, 256, 3, 1, True, False),         # split-K, 4 shares of 2 chunks, residual, no ReLU
-  (1, 40, 40, 128, 128, 3, 1, True, True),          # conv_small.hip (a few images: 32 x 32 tiles, K split over the waves): 50 x 4 workgroups
-  (3, 20, 20, 512, 512, 3, 1, True, False),         # ... tiles that straddle images, last tile partial (1200 pixels), no ReLU
-  (1, 40, 40, 256, 128, 3, 1, False, True),         # ... Cout != Cin
-  (1, 80, 80, 64, 128, 3, 2, False, True),          # ... the 64 -> 128 stride-2 layer behind the stem: four waves of 16 channels, 305-pixel band
-  (2, 80, 80, 64, 128, 3, 2, True, False),          # ... tiles that straddle rows and the two images
-  (1, 40, 40, 256, 512, 3, 2, False, True),         # stride 2, 72 K-steps at one hypothesis: split-K of the implicit GEMM (4 shares of 18 steps), last 64-pixel tile partial
-  (4, 40, 40, 256, 512, 3, 2, False, False),        # the same at the largest batch that takes it (1600 pixels), no ReLU
-  (1, 1, 1000, 512, 1024, 1, 1, False, False),     # a Linear layer (1x1, M=1000 tokens: ragged last tile)
-  (1, 1, 130, 512, 64, 1, 1, False, False),
+  (2, 160, 160, 6, 64, 7, 2, False, True),          # stem.hip: 50 blocks of 16 x 16 output pixels
+  (1, 20, 20, 512, 512, 3, 1, True, True),          # one hypothesis: conv_small.hip <4, 20, 1> (13 x 16 workgroups; FP_SMALL=0: split-K, 8 shares of 2 chunks + finishing pass)
+  (1, 40, 40, 256, 256, 3, 1, False, True),         # conv_small.hip <2, 40, 1>: 50 x 8 workgroups (FP_SMALL=0: split-K, 4 shares of 2 chunks)
+  (2, 40, 40, 128, 128, 3, 1, True, False),         # conv_small.hip <1, 40, 1> at the largest launch it takes: 100 x 4 workgroups, no ReLU
+  (2, 40, 40, 256, 256, 3, 1, True, False),         # conv_halo.hip split-K, 4 shares of 2 chunks, residual, no ReLU
+  (1, 40, 40, 128, 128, 3, 1, True, True),          # conv_small.hip <1, 40, 1> (a few images: 32 x 32 tiles, K split over the waves): 50 x 4 workgroups
+  (3, 20, 20, 512, 512, 3, 1, True, False),         # conv_halo.hip split-K again (38 x 16 = 608 workgroups: more than conv_small.hip takes), no ReLU
+  (1, 40, 40, 256, 128, 3, 1, False, True),         # conv_small.hip <2, 40, 1>, Cout != Cin
+  (1, 80, 80, 64, 128, 3, 2, False, True),          # conv_small.hip <1, 80, 2, 4>: the 64 -> 128 stride-2 layer behind the stem: four waves of 16 channels, 305-pixel band
+  (2, 80, 80, 64, 128, 3, 2, True, False),          # ... tiles that straddle rows and the two images, residual
+  (1, 40, 40, 256, 512, 3, 2, False, True),         # conv_small.hip <2, 40, 2>: 13 x 16 workgroups (FP_SMALL=0: split-K of the implicit GEMM, 4 shares of 18 steps)
+  (4, 40, 40, 256, 512, 3, 2, False, False),        # stride 2, 72 K-steps: split-K of the implicit GEMM (conv_igemm2_splitk_kernel, 4 shares of 18 steps) at the largest batch that takes it (1600 pixels), no ReLU
+  (1, 1, 1000, 512, 1024, 1, 1, False, False),     # a Linear layer (1x1, M=1000 tokens: ragged last tile): conv_igemm2_kernel <128, 1>
+  (1, 1, 130, 512, 64, 1, 1, False, False),        # conv_igemm2_kernel <64, 1>
 ])
 def test_conv_igemm_vs_fp32_reference(fp, shape):
   """MFMA implicit GEMM vs torch fp32 conv2d on the same fp16-rounded operands; fp32 accumulate ->
@@ -550,10 +552,11 @@ def test_conv_igemm_vs_fp32_reference(fp, shape):
   x_d, b_d = xin.cuda(), b.cuda()
   Ho, Wo = ref.shape[-2:]
   for out_f32 in (0, 1):
-    out = torch.empty((N, Ho, Wo, Cout), dtype=torch.float32 if out_f32 else torch.float16, device='cuda')
+    out = torch.full((N, Ho, Wo, Cout), float('nan'), dtype=torch.float32 if out_f32 else torch.float16, device='cuda')
     check(lib().fp_conv2d_f16(fp['ctx'].handle, ptr(x_d), N, H, W, cin_pad, ptr(wp), ptr(b_d), Cout, k, k, stride, pad,
                               ptr(res_d) if use_res else None, 1 if relu else 0, ptr(out), out_f32, stream_ptr()))
     got = out.float().permute(0, 3, 1, 2).cpu()
+    assert not bool(torch.isnan(got).any()), f'out_f32={out_f32}: NaN left in the output'
     scale = float(ref.abs().max())
     err = float((got - ref).abs().max())
     assert err <= (2e-3 if not out_f32 else 2e-4) * scale + 1e-5, f'out_f32={out_f32}: err {err:.3e} scale {scale:.2f}'
