@@ -106,6 +106,10 @@ class FpDrawArgs(Structure):
               ('axis_thickness', c_float), ('opacity', c_float), ('fill_alpha', c_float), ('d_owner', c_void_p)]
 
 
+FP_TSDF_MAX_POINTS, FP_TSDF_MAX_VIEWS = 1 << 27, 64      # include/foundationpose_amd.h: fp_tsdf_create, fp_tsdf_integrate
+FP_TSDF_PLANES = ('tsdf', 'weight', 'r', 'g', 'b', 'color_weight')      # FP_TSDF_PLANE_*
+
+
 class FpObjectBatch(Structure):
   _fields_ = [('mesh', c_void_p), ('d_rgb', c_void_p), ('d_geom', c_void_p), ('H', c_int), ('W', c_int), ('K', c_void_p),
               ('mesh_diameter', c_double), ('n', c_int)]
@@ -145,6 +149,13 @@ _PROTOS = {
   'fp_scene_instances': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_double, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_void_p, c_void_p]),
   'fp_draw_poses': (c_int, [c_void_p, POINTER(FpDrawArgs), c_void_p]),
+  'fp_tsdf_create': (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_float, POINTER(c_void_p)]),
+  'fp_tsdf_destroy': (c_int, [c_void_p]),
+  'fp_tsdf_reset': (c_int, [c_void_p, c_void_p, c_void_p]),
+  'fp_tsdf_integrate': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p]),
+  'fp_tsdf_extract_count': (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_void_p]),
+  'fp_tsdf_extract_write': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
+  'fp_tsdf_read_plane': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
   'fp_net_create': (c_int, [c_void_p, c_int, POINTER(FpTensor), c_int, c_int, POINTER(c_void_p)]),
   'fp_net_destroy': (c_int, [c_void_p]),
   'fp_net_rot_dim': (c_int, [c_void_p]),

@@ -523,6 +523,72 @@ typedef struct {
 } fp_draw_args;
 int fp_draw_poses(fp_ctx *ctx, const fp_draw_args *args, void *stream);
 
+/* ---- model-free set-up: posed RGB-D reference views fused into a truncated signed distance volume, and a coloured triangle mesh
+ *      extracted from it by marching tetrahedra.  The reference trains a neural field for this (bundlesdf/run_nerf.py); this is a
+ *      different, classical algorithm with the arithmetic below.  Everything is fp32, not contracted, every
+ *      operation in the written order; / and sqrt are correctly rounded.
+ *      Volume.  dims = (nx, ny, nz) sample points; point (i, j, k) has index i + nx (j + ny k) in every plane (i fastest) and lies at
+ *      s = (ox + v (float)i, oy + v (float)j, oz + v (float)k), with o = (float)origin (object frame, metres) and v = voxel_size.  Six
+ *      fp32 planes, zero after create and reset: tsdf T, weight W, r, g, b (0 .. 255), color_weight Wc.  The volume owns its device
+ *      memory (planes and extraction scratch: 33 bytes a point, plus 8 per 1024 points), not the context's arena.
+ *      fp_tsdf_create: FP_EINVAL for a null pointer, a dim < 2, nx ny nz above FP_TSDF_MAX_POINTS, voxel_size or trunc not > 0 (or not
+ *      finite), a non-finite origin; FP_ENOMEM when an allocation fails (nothing is kept).
+ *      Integrate.  One thread per sample point; the views are taken inside the thread in index order, so a call reads and writes the
+ *      volume once.  d_depth (n_views,H,W) fp32 metres; d_rgb (n_views,H,W,3) uint8 or null; d_mask (n_views,H,W) uint8 or null; K host
+ *      float64 3x3, of which fx = K[0], cx = K[2], fy = K[4], cy = K[5] are used, each cast to fp32 (no skew); cam_in_ob host float64
+ *      (n_views,4,4), camera-to-object, rigid: its inverse is taken on the host in float64 as R = Rc^T and
+ *      t_i = -((Rc[0][i] tc[0] + Rc[1][i] tc[1]) + Rc[2][i] tc[2]), then cast to fp32.  Per view, for the point s:
+ *        q_a = ((R[a][0] s.x + R[a][1] s.y) + R[a][2] s.z) + t[a];                    skip the view unless q.z >= 0.001
+ *        col = floor((fx (q.x / q.z) + cx) + 0.5), row = floor((fy (q.y / q.z) + cy) + 0.5);   skip unless 0 <= col < W and 0 <= row < H
+ *        d = depth[row, col];               skip unless d >= 0.001 and d < zfar, and, with a mask, mask[row, col] != 0
+ *        sdf = d - q.z;                     skip if sdf < -trunc
+ *        tau = min(1, sdf / trunc);  T = (T W + tau) / (W + 1);  W = W + 1
+ *        if rgb is given and sdf <= trunc:  c = (c Wc + (float)rgb[row, col, ch]) / (Wc + 1) for c = r, g, b;  Wc = Wc + 1
+ *      ("unless" so that a NaN skips.)  Consequences: one call with n views is bit for bit n calls with one view each in the same order;
+ *      a point belongs to one thread - no atomics, deterministic; nothing synchronises.  FP_EINVAL: a null ctx, vol, d_depth, K or
+ *      cam_in_ob, n_views outside 0 .. FP_TSDF_MAX_VIEWS (0 does nothing), H or W < 1, fx or fy not > 0, zfar not > 0 (infinity is
+ *      allowed), a view matrix that is not finite or whose last row is not 0 0 0 1.
+ *      Surface (marching tetrahedra, Kuhn / Freudenthal split).  A point is observed when W >= min_weight and negative when T < 0.  It
+ *      owns 7 edges, slot 0 .. 6, to the points at +x, +y, +z, +xy, +xz, +yz, +xyz (those inside the volume).  An edge (a, b) carries a
+ *      vertex iff both ends are observed and exactly one is negative: u = T_a / (T_a - T_b), position s_a + (s_b - s_a) u per component,
+ *      colour floor((c_a + (c_b - c_a) u) + 0.5) clamped to 0 .. 255, normal n = g_a + (g_b - g_a) u divided by sqrt((n.x n.x + n.y n.y)
+ *      + n.z n.z) (left as it is when that is 0), where g is the gradient of T per axis: (T[+1] - T[-1]) 0.5 when both neighbours exist
+ *      and are observed, T[+1] - T or T - T[-1] when one does, else 0.  Vertices are welded by construction: id = the number of
+ *      vertices of all points with a smaller index (an exclusive scan) + the number of lower slots of the same point that carry one.
+ *      The cube at (i, j, k), i < nx-1, j < ny-1, k < nz-1, is cut into 6 tetrahedra around its (0,0,0)-(1,1,1) diagonal: tetrahedron p
+ *      has the corners 0, e_a, e_a + e_b, (1,1,1) for the p-th permutation (a, b, c) of (x, y, z) in lexicographic order, numbered
+ *      0 .. 3.  It emits triangles only if its four corners are observed.  One corner L of the other sign than A < B < C: the triangle
+ *      (LA, LB, LC) of the vertices on those edges; two negative N0 < N1 and two non-negative P0 < P1: the quad q = (N0P0, N0P1, N1P1,
+ *      N1P0) as (q0, q1, q2), (q0, q2, q3).  The last two indices of every triangle are swapped where needed so that the normal
+ *      (v1 - v0) x (v2 - v0) points from the negative to the non-negative side - outward.  (The 16-case table is derived from this
+ *      rule when the volume is created.)  Faces are ordered by cube index, tetrahedron, triangle; vertices by point index, slot.  Both
+ *      orders are independent of the execution order; no atomics.  The scan is reduce / scan of the block sums / add, recursive, with
+ *      no waiting between workgroups.
+ *      fp_tsdf_extract_count runs the flag and count pass and the scan, SYNCHRONISES the stream and returns h_counts = {vertices, faces}.
+ *      fp_tsdf_extract_write fills d_vertices (n_vertices,3) fp32, d_normals (n_vertices,3) fp32 or null, d_colors (n_vertices,3) uint8
+ *      or null, d_faces (n_faces,3) int32; nothing synchronises.  It returns FP_EINVAL when no count has happened since the last
+ *      integrate or reset of the volume, when n_vertices / n_faces are not the counted ones, or when a required buffer is null
+ *      (d_vertices with n_vertices > 0, d_faces with n_faces > 0).  min_weight must be > 0 (FP_EINVAL).
+ *      fp_tsdf_read_plane copies plane FP_TSDF_PLANE_* into d_out (nx ny nz fp32, device) on the stream. */
+typedef struct fp_tsdf fp_tsdf;
+#define FP_TSDF_MAX_POINTS (1 << 27)   /* 512^3 */
+#define FP_TSDF_MAX_VIEWS 64           /* per fp_tsdf_integrate call: the view matrices travel as kernel arguments */
+#define FP_TSDF_PLANE_TSDF 0
+#define FP_TSDF_PLANE_WEIGHT 1
+#define FP_TSDF_PLANE_R 2
+#define FP_TSDF_PLANE_G 3
+#define FP_TSDF_PLANE_B 4
+#define FP_TSDF_PLANE_COLOR_WEIGHT 5
+int fp_tsdf_create(fp_ctx *ctx, const double *origin, float voxel_size, const int *dims, float trunc, fp_tsdf **out);
+int fp_tsdf_destroy(fp_tsdf *vol);
+int fp_tsdf_reset(fp_ctx *ctx, fp_tsdf *vol, void *stream);
+int fp_tsdf_integrate(fp_ctx *ctx, fp_tsdf *vol, const float *d_depth, const uint8_t *d_rgb, const uint8_t *d_mask, int n_views, int H, int W,
+                      const double *K, const double *cam_in_ob, float zfar, void *stream);
+int fp_tsdf_extract_count(fp_ctx *ctx, fp_tsdf *vol, float min_weight, int64_t *h_counts, void *stream);
+int fp_tsdf_extract_write(fp_ctx *ctx, fp_tsdf *vol, float *d_vertices, float *d_normals, uint8_t *d_colors, int32_t *d_faces,
+                          int64_t n_vertices, int64_t n_faces, void *stream);
+int fp_tsdf_read_plane(fp_ctx *ctx, const fp_tsdf *vol, int plane, float *d_out, void *stream);
+
 /* ---- building blocks exported for parity tests and profiling ---------------------------------- */
 /* fp16 NHWC implicit-GEMM convolution on MFMA: out = act(conv(in, w) + bias [+ res]).  w_packed is
  * [Cout][Kpad] fp16 with k = (ky*KW+kx)*Cin + ci, Kpad = roundup(KH*KW*Cin, 32), zero padded. */

@@ -1,0 +1,34 @@
+"""A mesh from a folder of posed RGB-D reference views (the reference's model-free layout: rgb/, depth_enhanced/ or depth/, mask/,
+cam_in_ob/, K.txt), by TSDF fusion and marching tetrahedra on the GPU (foundationpose_amd.reconstruct).
+usage: python scripts/reconstruct_object.py DIR [--voxel 0.002] [--trunc T] [--min-weight 1] [--no-depth-filter] [--out DIR/model/model.obj]
+The output format follows the extension: .obj or .ply."""
+import argparse
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from foundationpose_amd import mesh_io
+from foundationpose_amd.reconstruct import reconstruct_object
+
+
+def main():
+  ap = argparse.ArgumentParser()
+  ap.add_argument('dir')
+  ap.add_argument('--voxel', type=float, default=0.002)
+  ap.add_argument('--trunc', type=float, default=None)
+  ap.add_argument('--min-weight', type=float, default=1)
+  ap.add_argument('--no-depth-filter', action='store_true')
+  ap.add_argument('--out', default=None)
+  args = ap.parse_args()
+  out = args.out or os.path.join(args.dir, 'model', 'model.obj')
+  mesh = reconstruct_object(args.dir, voxel_size=args.voxel, trunc=args.trunc, min_weight=args.min_weight, depth_filter=not args.no_depth_filter)
+  os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+  if out.lower().endswith('.ply'):
+    mesh_io.save_ply(mesh, out)
+  else:
+    mesh_io.save_obj(mesh, out)
+  print(f'{out}: {len(mesh.vertices)} vertices, {len(mesh.faces)} faces')
+
+
+if __name__ == '__main__':
+  main()
