@@ -108,6 +108,7 @@ class FpDrawArgs(Structure):
 
 FP_TSDF_MAX_POINTS, FP_TSDF_MAX_VIEWS = 1 << 27, 64      # include/foundationpose_amd.h: fp_tsdf_create, fp_tsdf_integrate
 FP_TSDF_PLANES = ('tsdf', 'weight', 'r', 'g', 'b', 'color_weight')      # FP_TSDF_PLANE_*
+FP_TSDF_ALIGN_TERMS = 29                                                  # fp_tsdf_align: doubles per view of h_sums
 
 
 class FpObjectBatch(Structure):
@@ -156,6 +157,7 @@ _PROTOS = {
   'fp_tsdf_extract_count': (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_void_p]),
   'fp_tsdf_extract_write': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
   'fp_tsdf_read_plane': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+  'fp_tsdf_align': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p]),
   'fp_net_create': (c_int, [c_void_p, c_int, POINTER(FpTensor), c_int, c_int, POINTER(c_void_p)]),
   'fp_net_destroy': (c_int, [c_void_p]),
   'fp_net_rot_dim': (c_int, [c_void_p]),

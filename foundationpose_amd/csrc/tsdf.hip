@@ -542,3 +542,196 @@ extern "C" int fp_tsdf_read_plane(fp_ctx *ctx, const fp_tsdf *vol, int plane, fl
   FP_CHECK_HIP(hipMemcpyAsync(d_out, vol->plane[plane], (size_t)vol->g.n * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return FP_OK;
 }
+
+// ---- frame-to-model alignment: one Gauss-Newton linearisation of every view against the volume (fp_tsdf_align) -----------------------
+// A workgroup owns (view, a tile of AL_TILE pixels); the view is uniform in the workgroup, so its matrix arrives as scalar loads.  A lane
+// takes AL_PIX pixels, TS_THREADS apart (the depth reads coalesce), in three passes over them: depth and mask, then the cell and the 16
+// gathers of each pixel (tsdf and weight of the 8 corners) - nothing in this pass depends on a gathered value, so all AL_PIX x 16 loads
+// are in flight together - then the arithmetic.  The 29 sums are kept in double per lane, added over the wave by a butterfly (every lane
+// ends with the same value, the order is fixed), over the waves in wave order through LDS, and written to the workgroup's own slot of the
+// slab; tsdf_align_fold_kernel adds the slots of a view in tile order.  No atomics: a view's sums depend on nothing but its own pixels.
+namespace {
+
+constexpr int AL_PIX = 4;
+constexpr int AL_TILE = TS_THREADS * AL_PIX;
+
+struct AlignView {
+  float r[9], t[3];      // camera -> object
+};
+
+struct AlignViews {
+  AlignView v[FP_TSDF_MAX_VIEWS];
+};
+
+__global__ __launch_bounds__(TS_THREADS) void tsdf_align_kernel(TsdfGrid g, const float *__restrict__ pT, const float *__restrict__ pW,
+                                                                const float *__restrict__ depth, const uint8_t *__restrict__ mask, TsdfCam cam,
+                                                                float min_w, int n_tiles, AlignViews views, float *__restrict__ rows,
+                                                                double *__restrict__ slab) {
+  __shared__ double red[TS_THREADS / 64][FP_TSDF_ALIGN_TERMS];
+  const int tid = threadIdx.x;
+  const int tile = blockIdx.x % n_tiles, v = blockIdx.x / n_tiles;
+  const AlignView &m = views.v[v];
+  const long long hw = (long long)cam.H * cam.W;
+  const size_t view0 = (size_t)v * (size_t)hw;
+  const int sxy = g.nx * g.ny;
+
+  // pass 1: depth and mask
+  float d[AL_PIX];
+  bool ok[AL_PIX];
+  long long pix[AL_PIX];
+#pragma unroll
+  for (int q = 0; q < AL_PIX; ++q) {
+    pix[q] = (long long)tile * AL_TILE + q * TS_THREADS + tid;
+    const bool in = pix[q] < hw;                                   // the last tile of a view is ragged
+    d[q] = in ? depth[view0 + (size_t)pix[q]] : 0.f;
+    ok[q] = d[q] >= 0.001f && d[q] < cam.zfar;
+    if (mask) ok[q] = ok[q] && (in ? mask[view0 + (size_t)pix[q]] : (uint8_t)0) != 0;
+  }
+
+  // pass 2: the point in the object frame, its cell, the 16 gathers
+  float x[AL_PIX][3], f[AL_PIX][3], Tc[AL_PIX][8], Wc[AL_PIX][8];
+#pragma unroll
+  for (int q = 0; q < AL_PIX; ++q) {
+    const int row = (int)(pix[q] / cam.W), col = (int)(pix[q] - (long long)row * cam.W);
+    const float px = (((float)col - cam.cx) / cam.fx) * d[q], py = (((float)row - cam.cy) / cam.fy) * d[q], pz = d[q];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) x[q][a] = ((m.r[a * 3] * px + m.r[a * 3 + 1] * py) + m.r[a * 3 + 2] * pz) + m.t[a];
+    const float gx = (x[q][0] - g.ox) / g.vs, gy = (x[q][1] - g.oy) / g.vs, gz = (x[q][2] - g.oz) / g.vs;
+    const float fi = floorf(gx), fj = floorf(gy), fk = floorf(gz);
+    f[q][0] = gx - fi, f[q][1] = gy - fj, f[q][2] = gz - fk;
+    // all eight corners inside: 0 <= i and i + 1 <= n - 1, decided in float so that a NaN or a huge value never reaches the cast
+    ok[q] = ok[q] && fi >= 0.f && fi <= (float)(g.nx - 2) && fj >= 0.f && fj <= (float)(g.ny - 2) && fk >= 0.f && fk <= (float)(g.nz - 2);
+    const int idx = ok[q] ? (int)fi + g.nx * ((int)fj + g.ny * (int)fk) : 0;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      const int p = idx + (c & 1) + g.nx * ((c >> 1) & 1) + sxy * (c >> 2);      // inside the volume whenever ok
+      Tc[q][c] = ok[q] ? pT[p] : 0.f;
+      Wc[q][c] = ok[q] ? pW[p] : 0.f;
+    }
+  }
+
+  // pass 3: interpolant, gradient, the row, the sums
+  double acc[FP_TSDF_ALIGN_TERMS];
+#pragma unroll
+  for (int e = 0; e < FP_TSDF_ALIGN_TERMS; ++e) acc[e] = 0.0;
+  const float gscale = g.trunc / g.vs;
+#pragma unroll
+  for (int q = 0; q < AL_PIX; ++q) {
+    const float *T = Tc[q];
+    const float u = f[q][0], w = f[q][1], z = f[q][2];
+    bool valid = ok[q];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) valid = valid && Wc[q][c] >= min_w;
+    const float d00 = T[1] - T[0], d10 = T[3] - T[2], d01 = T[5] - T[4], d11 = T[7] - T[6];      // x-differences at (y, z)
+    const float a00 = T[0] + d00 * u, a10 = T[2] + d10 * u, a01 = T[4] + d01 * u, a11 = T[6] + d11 * u;
+    const float e0 = a10 - a00, e1 = a11 - a01;                                                    // y-differences of the x-lerps at z
+    const float b0 = a00 + e0 * w, b1 = a01 + e1 * w;
+    const float dz = b1 - b0;
+    const float Ti = b0 + dz * z;
+    valid = valid && fabsf(Ti) < 1.f;
+    const float h0 = d00 + (d10 - d00) * w, h1 = d01 + (d11 - d01) * w;
+    const float Gx = (h0 + (h1 - h0) * z) * gscale, Gy = (e0 + (e1 - e0) * z) * gscale, Gz = dz * gscale;
+    const float X = x[q][0], Y = x[q][1], Z = x[q][2];
+    float J[6] = {Gx, Gy, Gz, Y * Gz - Z * Gy, Z * Gx - X * Gz, X * Gy - Y * Gx};
+    float r = Ti * g.trunc;
+    if (!valid) {
+#pragma unroll
+      for (int i = 0; i < 6; ++i) J[i] = 0.f;
+      r = 0.f;
+    }
+    if (rows && pix[q] < hw) {
+      float4 *o = (float4 *)(rows + (view0 + (size_t)pix[q]) * 8);
+      o[0] = make_float4(J[0], J[1], J[2], J[3]);
+      o[1] = make_float4(J[4], J[5], r, valid ? 1.f : 0.f);
+    }
+    double Jd[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) Jd[i] = (double)J[i];
+    const double rd = (double)r;
+    int e = 0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+      for (int j = i; j < 6; ++j) acc[e++] += Jd[i] * Jd[j];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) acc[21 + i] += Jd[i] * rd;
+    acc[27] += rd * rd;
+    acc[28] += valid ? 1.0 : 0.0;
+  }
+
+#pragma unroll
+  for (int e = 0; e < FP_TSDF_ALIGN_TERMS; ++e) {
+    double s = acc[e];
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
+    if ((tid & 63) == 0) red[tid >> 6][e] = s;
+  }
+  __syncthreads();
+  if (tid < FP_TSDF_ALIGN_TERMS) {
+    double s = red[0][tid];
+    for (int wv = 1; wv < TS_THREADS / 64; ++wv) s += red[wv][tid];
+    slab[((size_t)v * n_tiles + tile) * FP_TSDF_ALIGN_TERMS + tid] = s;
+  }
+}
+
+// one thread per (view, term): the tiles' slots in tile order
+__global__ __launch_bounds__(64) void tsdf_align_fold_kernel(const double *__restrict__ slab, int n_views, int n_tiles, double *__restrict__ sums) {
+  const int t = blockIdx.x * 64 + threadIdx.x;
+  if (t >= n_views * FP_TSDF_ALIGN_TERMS) return;
+  const int v = t / FP_TSDF_ALIGN_TERMS, e = t % FP_TSDF_ALIGN_TERMS;
+  const double *sb = slab + (size_t)v * n_tiles * FP_TSDF_ALIGN_TERMS + e;
+  double s = 0.0;
+  for (int k = 0; k < n_tiles; ++k) s += sb[(size_t)k * FP_TSDF_ALIGN_TERMS];
+  sums[t] = s;
+}
+
+}  // namespace
+
+extern "C" int fp_tsdf_align(fp_ctx *ctx, const fp_tsdf *vol, const float *d_depth, const uint8_t *d_mask, int n_views, int H, int W, const double *K,
+                             const double *cam_in_ob, float zfar, float min_weight, float *d_rows, double *h_sums, void *stream) {
+  // Every check of a value comes before the first look INTO ctx or vol (the device check below): tests/test_tsdf_align_host.py calls this
+  // without a GPU, with pointers for ctx and vol that must not be dereferenced.  Keep that order when adding checks.
+  FP_REQUIRE(ctx && vol && d_depth && K && cam_in_ob && h_sums, "fp_tsdf_align: null argument");
+  FP_REQUIRE(((uintptr_t)d_rows & 15) == 0, "fp_tsdf_align: d_rows is not 16-byte aligned (it is written as float4)");
+  FP_REQUIRE(n_views >= 0 && n_views <= FP_TSDF_MAX_VIEWS, "fp_tsdf_align: n_views %d (0 .. %d)", n_views, FP_TSDF_MAX_VIEWS);
+  FP_REQUIRE(H >= 1 && W >= 1, "fp_tsdf_align: H %d, W %d", H, W);
+  FP_REQUIRE(zfar > 0.f, "fp_tsdf_align: zfar %g (> 0)", (double)zfar);
+  FP_REQUIRE(min_weight > 0.f, "fp_tsdf_align: min_weight %g (> 0)", (double)min_weight);
+  TsdfCam cam{(float)K[0], (float)K[4], (float)K[2], (float)K[5], zfar, H, W, n_views};
+  FP_REQUIRE(cam.fx > 0.f && cam.fy > 0.f && isfinite(cam.fx) && isfinite(cam.fy) && isfinite(cam.cx) && isfinite(cam.cy),
+             "fp_tsdf_align: K is not a finite camera matrix with positive focal lengths");
+  AlignViews views;
+  memset(&views, 0, sizeof(views));
+  for (int v = 0; v < n_views; ++v) {
+    const double *m = cam_in_ob + (size_t)v * 16;
+    for (int e = 0; e < 12; ++e) FP_REQUIRE(isfinite(m[e]), "fp_tsdf_align: cam_in_ob[%d] is not finite", v);
+    FP_REQUIRE(m[12] == 0 && m[13] == 0 && m[14] == 0 && m[15] == 1, "fp_tsdf_align: the last row of cam_in_ob[%d] is not 0 0 0 1", v);
+    for (int a = 0; a < 3; ++a) {
+      for (int i = 0; i < 3; ++i) views.v[v].r[a * 3 + i] = (float)m[a * 4 + i];
+      views.v[v].t[a] = (float)m[a * 4 + 3];
+    }
+  }
+  const long long n_tiles = ((long long)H * W + AL_TILE - 1) / AL_TILE;
+  FP_REQUIRE(n_tiles * FP_TSDF_MAX_VIEWS <= 0x7fffffff, "fp_tsdf_align: %d x %d pixels are too many for one launch", H, W);
+  FP_REQUIRE(ctx->device == vol->device, "fp_tsdf_align: the volume lives on device %d, the context on %d", vol->device, ctx->device);
+  if (n_views == 0) return FP_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const size_t slab_bytes = (size_t)n_views * (size_t)n_tiles * FP_TSDF_ALIGN_TERMS * sizeof(double);
+  const size_t sums_bytes = (size_t)n_views * FP_TSDF_ALIGN_TERMS * sizeof(double);
+  FP_TRY(fp_arena_ensure(ctx, slab_bytes + sums_bytes + 4096));
+  ArenaScope scope(ctx->arena);
+  double *slab = (double *)ctx->arena.take(slab_bytes);
+  double *sums = (double *)ctx->arena.take(sums_bytes);
+  FP_REQUIRE(slab && sums, "fp_tsdf_align: arena exhausted");
+  const TsdfGrid &g = vol->g;
+  hipLaunchKernelGGL(tsdf_align_kernel, dim3((unsigned)(n_tiles * n_views)), dim3(TS_THREADS), 0, s, g, (const float *)vol->plane[0],
+                     (const float *)vol->plane[1], d_depth, d_mask, cam, min_weight, (int)n_tiles, views, d_rows, slab);
+  FP_CHECK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(tsdf_align_fold_kernel, dim3((unsigned)((n_views * FP_TSDF_ALIGN_TERMS + 63) / 64)), dim3(64), 0, s, (const double *)slab,
+                     n_views, (int)n_tiles, sums);
+  FP_CHECK_HIP(hipGetLastError());
+  // the slab and the sums go back to the arena when this returns: the stream has been synchronised by then
+  FP_CHECK_HIP(hipMemcpyAsync(h_sums, sums, sums_bytes, hipMemcpyDeviceToHost, s));
+  FP_CHECK_HIP(hipStreamSynchronize(s));
+  return FP_OK;
+}

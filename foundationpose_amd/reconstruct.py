@@ -4,7 +4,10 @@ goes - make_mesh_tensors and FoundationPose(model_pts, model_normals, mesh=...).
 The reference trains a neural object field for this (bundlesdf/run_nerf.py: run_one_ob -> model/model.obj).  This module reads the same
 folder layout and does something else: the depth maps are fused into a truncated signed distance volume and a
 coloured triangle mesh is extracted by marching tetrahedra, both on the GPU (csrc/tsdf.hip; the arithmetic is stated in
-include/foundationpose_amd.h).  It does not optimise the poses of the reference views and has no view-dependent appearance.
+include/foundationpose_amd.h).  The poses of the reference views can be refined first (refine_view_poses, reconstruct_object(...,
+refine_poses=True)): each view's depth map is aligned rigidly to the geometry fused so far, frame-to-model Gauss-Newton on the volume
+(fp_tsdf_align builds the normal equations on the GPU, the 6x6 solves run on the host).  There is no joint bundle adjustment over all
+views, no photometric term and no view-dependent appearance.
 """
 import ctypes
 import glob
@@ -78,6 +81,80 @@ class TsdfVolume:
       check(lib().fp_tsdf_integrate(self.ctx.handle, self.handle, ptr(depths[a:b]), None if rgbs is None else ptr(rgbs[a:b]),
                                     None if masks is None else ptr(masks[a:b]), b - a, H, W, Kp, ptr(poses[a:b]), zf, stream_ptr(self.device)))
 
+  def _views(self, depths, cam_in_obs, masks):
+    depths = torch.as_tensor(depths, device=self.device).to(torch.float).contiguous()
+    if depths.dim() == 2:
+      depths = depths[None]
+    n, H, W = depths.shape
+    poses = np.ascontiguousarray(np.asarray(torch.as_tensor(cam_in_obs).cpu(), dtype=np.float64).reshape(-1, 4, 4))
+    if len(poses) != n:
+      raise ValueError(f'{n} depth maps, {len(poses)} poses')
+    if masks is not None:
+      masks = torch.as_tensor(masks, device=self.device)
+      if tuple(masks.shape) != (n, H, W):
+        raise ValueError(f'masks must have the shape {(n, H, W)}, got {tuple(masks.shape)}')
+      masks = (masks != 0).to(torch.uint8).contiguous()
+    return depths, poses, masks
+
+  def align_step(self, depths, K, cam_in_obs, masks=None, zfar=np.inf, min_weight=1, rows=False):
+    """One linearisation of every view's pose against the volume (fp_tsdf_align; arguments as for integrate): the (n,29) float64 array
+    of the header - per view the upper triangle of J^T J, J^T r, sum r^2, the number of valid pixels - and, with rows=True, the
+    (n,H,W,8) float32 device tensor of the per-pixel rows.  Synchronises.  More than MAX_VIEWS views are cut into calls (a view's
+    numbers do not depend on the batch it is in)."""
+    depths, poses, masks = self._views(depths, cam_in_obs, masks)
+    n, H, W = depths.shape
+    Kd, Kp = _lib.k_ptr(K)
+    zf = float(zfar) if np.isfinite(zfar) else float('inf')
+    sums = np.zeros((n, _lib.FP_TSDF_ALIGN_TERMS), dtype=np.float64)
+    out = torch.empty((n, H, W, 8), dtype=torch.float, device=self.device) if rows else None
+    for a in range(0, n, MAX_VIEWS):
+      b = min(a + MAX_VIEWS, n)
+      part = np.zeros((b - a, _lib.FP_TSDF_ALIGN_TERMS), dtype=np.float64)
+      check(lib().fp_tsdf_align(self.ctx.handle, self.handle, ptr(depths[a:b]), None if masks is None else ptr(masks[a:b]), b - a, H, W, Kp,
+                                ptr(poses[a:b]), zf, float(min_weight), None if out is None else ptr(out[a:b]), ptr(part),
+                                stream_ptr(self.device)))
+      sums[a:b] = part
+    return (sums, out) if rows else sums
+
+  def align(self, depths, K, cam_in_obs, masks=None, iterations=10, min_pixels=100, damping=1e-9, max_step=None, zfar=np.inf, min_weight=1):
+    """Frame-to-model alignment of n views to the volume: Gauss-Newton on the host in float64 over the sums of align_step - per view
+    (A + damping trace(A) I) xi = -b, pose <- expm_se3(xi) @ pose - with ALL views advanced by one fp_tsdf_align call per iteration
+    (`iterations` steps and one closing evaluation).  A view with fewer than min_pixels valid pixels, or whose RMS residual rose, goes
+    back to the pose it had before its last step and stops.  max_step = (metres, radians) scales a step down to that translation and
+    rotation.  Returns (cam_in_obs (n,4,4) float64, info) with info['valid'] and info['rms'] (evaluations, n), info['stopped'] {view:
+    reason} and info['after_first'], the poses after the first step."""
+    depths, poses, masks = self._views(depths, cam_in_obs, masks)
+    poses = poses.copy()
+    n = len(poses)
+    prev_pose, prev_rms = poses.copy(), np.full(n, np.inf)
+    active = np.ones(n, dtype=bool)
+    info = dict(valid=[], rms=[], stopped={}, after_first=None)
+    for it in range(iterations + 1):
+      if not active.any():
+        break
+      s = self.align_step(depths, K, poses, masks=masks, zfar=zfar, min_weight=min_weight)
+      cnt = s[:, 28]
+      rms = np.sqrt(s[:, 27] / np.maximum(cnt, 1))
+      info['valid'].append(cnt.copy())
+      info['rms'].append(rms.copy())
+      for v in range(n):
+        if not active[v]:
+          continue
+        if cnt[v] < min_pixels:
+          poses[v], active[v], info['stopped'][v] = prev_pose[v], False, 'too few valid pixels'
+        elif rms[v] > prev_rms[v]:
+          poses[v], active[v], info['stopped'][v] = prev_pose[v], False, 'residual rose'
+        elif it < iterations:
+          prev_pose[v], prev_rms[v] = poses[v], rms[v]
+          xi = solve_step(s[v], damping)
+          if max_step is not None:
+            xi = xi * min(1.0, max_step[0] / max(np.linalg.norm(xi[:3]), 1e-300), max_step[1] / max(np.linalg.norm(xi[3:]), 1e-300))
+          poses[v] = expm_se3(xi) @ poses[v]
+      if it == 0:
+        info['after_first'] = poses.copy()
+    info['valid'], info['rms'] = np.array(info['valid']).reshape(-1, n), np.array(info['rms']).reshape(-1, n)
+    return poses, info
+
   def plane(self, name):
     """A copy of one plane as a (nz, ny, nx) float32 device tensor: 'tsdf', 'weight', 'r', 'g', 'b' or 'color_weight'."""
     nx, ny, nz = self.dims
@@ -105,6 +182,34 @@ class TsdfVolume:
     v, nr, c, f = self.extract_arrays(min_weight)
     rgba = np.concatenate([c.cpu().numpy(), np.full((len(c), 1), 255, dtype=np.uint8)], 1)
     return SimpleMesh(v.cpu().numpy(), f.cpu().numpy(), vertex_normals=nr.cpu().numpy(), vertex_colors=rgba)
+
+
+def expm_se3(xi):
+  """exp of the twist xi = (u, w) - translation part, rotation vector - as a 4x4 float64 matrix: R = I + A [w] + B [w]^2,
+  t = (I + B [w] + C [w]^2) u with A = sin th / th, B = (1 - cos th) / th^2, C = (th - sin th) / th^3 (their series below 1e-4 rad)."""
+  xi = np.asarray(xi, dtype=np.float64).reshape(6)
+  u, w = xi[:3], xi[3:]
+  th = float(np.linalg.norm(w))
+  Kx = np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
+  if th < 1e-4:
+    A, B, C = 1 - th * th / 6, 0.5 - th * th / 24, 1 / 6 - th * th / 120
+  else:
+    A, B, C = np.sin(th) / th, (1 - np.cos(th)) / (th * th), (th - np.sin(th)) / th ** 3
+  m = np.eye(4)
+  m[:3, :3] = np.eye(3) + A * Kx + B * (Kx @ Kx)
+  m[:3, 3] = (np.eye(3) + B * Kx + C * (Kx @ Kx)) @ u
+  return m
+
+
+def solve_step(sums, damping=1e-9):
+  """The Gauss-Newton step of one view from its 29 sums: (A + damping trace(A) I) xi = -b."""
+  A = np.zeros((6, 6))
+  e = 0
+  for i in range(6):
+    for j in range(i, 6):
+      A[i, j] = A[j, i] = sums[e]
+      e += 1
+  return np.linalg.solve(A + damping * np.trace(A) * np.eye(6), -np.asarray(sums[21:27]))
 
 
 def volume_from_views(depths, masks, K, cam_in_obs, voxel_size, margin=None, device='cuda'):
@@ -181,22 +286,121 @@ def largest_component(faces, n_vertices):
   return face_label == np.bincount(face_label).argmax()
 
 
-def reconstruct_object(views, voxel_size=0.002, trunc=None, min_weight=1, depth_filter=True, margin=None, device='cuda'):
+def _eroded_depths(views, depth_filter, dev):
+  """The depth maps the ALIGNMENT runs on: erode_depth only (pixels at depth discontinuities dropped, none invented); raw without filter."""
+  from .Utils import erode_depth
+  depths = torch.as_tensor(views['depths'], device=dev).to(torch.float)
+  if depth_filter:
+    depths = torch.stack([erode_depth(d.contiguous(), radius=2, device=dev) for d in depths])
+  return depths
+
+
+def _fusion_depths(eroded, depth_filter, dev):
+  """The depth maps the FUSION runs on: bilateral_filter_depth over the eroded maps, as the estimator does with an observed frame."""
+  from .Utils import bilateral_filter_depth
+  if depth_filter:
+    return torch.stack([bilateral_filter_depth(d.contiguous(), radius=2, device=dev) for d in eroded])
+  return eroded
+
+
+def refine_view_poses(views, voxel_size=0.002, anchor=0, order='greedy', rounds=0, depth_filter=True, trunc=None, margin=None, iterations=10,
+                      min_pixels=100, damping=1e-9, max_step=None, device='cuda'):
+  """Rigid per-view refinement of the reference views' poses against the geometry they fuse into.  `views` as for reconstruct_object.
+  The anchor view fixes the gauge and is never moved.  The volume holds all views at their given poses, grown by `margin` (default:
+  5 voxels + 1 cm, for poses that are off by millimetres and a degree or two).  The anchor is integrated; then, until every view is
+  fused: the view whose optical axis makes the smallest angle with that of any fused view (order='greedy'; 'index': the lowest index;
+  or a sequence of view indices) is aligned to the volume as it stands (TsdfVolume.align) and integrated at its refined pose.
+  Two things differ from the fusion of reconstruct_object, both measured.  `trunc` is 2 voxels by default, not 4:
+  a point within the truncation distance BEHIND a surface that the model has seen from elsewhere (the side face next to an edge)
+  carries a residual that is an artefact of the projective distance, so the band is kept as narrow as the interpolation allows; it must
+  stay above the pose error to be recovered.  depth_filter runs erode_depth only, which drops pixels at depth discontinuities; the
+  bilateral filter also fills the eroded silhouette from the neighbours, and a model of few views fused from such maps pulls the
+  alignment off.  rounds > 0 appends whole-model rounds: everything is fused again at the current poses and all views but the anchor are
+  aligned in one batched call.  A view that cannot be aligned (too few valid pixels) is integrated at its given pose and named in
+  info['stopped']; the call does not raise for that.  Returns (cam_in_obs (n,4,4) float64, info: order, stopped {view: reason}, valid
+  and rms per view at its last evaluation)."""
+  if isinstance(views, (str, os.PathLike)):
+    views = load_reference_views(views)
+  dev = _device(device)
+  return _refine_on(_eroded_depths(views, depth_filter, dev), views, voxel_size, anchor, order, rounds, trunc, margin,
+                    dict(iterations=iterations, min_pixels=min_pixels, damping=damping, max_step=max_step), dev)
+
+
+def _refine_on(depths, views, voxel_size, anchor, order, rounds, trunc, margin, kw, dev):
+  """refine_view_poses on depth maps that are already prepared for the alignment (device tensor (n,H,W)); kw: TsdfVolume.align's."""
+  trunc = 2.0 * voxel_size if trunc is None else float(trunc)
+  masks, K = views.get('masks'), views['K']
+  poses = np.array(np.asarray(torch.as_tensor(views['cam_in_obs']).cpu(), dtype=np.float64).reshape(-1, 4, 4))
+  n = len(poses)
+  if not 0 <= anchor < n:
+    raise ValueError(f'anchor {anchor} of {n} views')
+  margin = 5.0 * voxel_size + 0.01 if margin is None else float(margin)
+  origin, dims = volume_from_views(depths, masks, K, poses, voxel_size, margin=margin, device=dev)
+  vol = TsdfVolume(origin, voxel_size, dims, trunc=trunc, device=dev)
+  one = lambda a, v: None if a is None else a[v:v + 1]
+  vol.integrate(depths[anchor:anchor + 1], K, poses[anchor:anchor + 1], masks=one(masks, anchor))
+  fused, left = [anchor], [v for v in range(n) if v != anchor]
+  if not isinstance(order, str):
+    left = [int(v) for v in order if int(v) != anchor]
+    if sorted(left) != [v for v in range(n) if v != anchor]:
+      raise ValueError('order must name every view but the anchor once')
+  elif order not in ('greedy', 'index'):
+    raise ValueError(f"order must be 'greedy', 'index' or a sequence of view indices, got {order!r}")
+  info = dict(order=[anchor], stopped={}, valid=np.zeros(n), rms=np.zeros(n))
+  while left:
+    v = left[0]
+    if order == 'greedy':
+      cos = [max(float(poses[c, :3, 2] @ poses[u, :3, 2]) for u in fused) for c in left]
+      v = left[int(np.argmax(cos))]          # the first of equals: the lowest index
+    got, inf = vol.align(depths[v:v + 1], K, poses[v:v + 1], masks=one(masks, v), **kw)
+    poses[v] = got[0]
+    if 0 in inf['stopped']:
+      info['stopped'][v] = inf['stopped'][0]
+    info['valid'][v], info['rms'][v] = inf['valid'][-1, 0], inf['rms'][-1, 0]
+    vol.integrate(depths[v:v + 1], K, poses[v:v + 1], masks=one(masks, v))
+    left.remove(v)
+    fused.append(v)
+    info['order'].append(v)
+  others = [v for v in range(n) if v != anchor]
+  for _ in range(rounds if others else 0):
+    vol.reset()
+    vol.integrate(depths, K, poses, masks=masks)
+    got, inf = vol.align(depths[others], K, poses[others], masks=None if masks is None else torch.as_tensor(masks)[others], **kw)
+    poses[others] = got
+    for k, v in enumerate(others):
+      if k in inf['stopped']:
+        info['stopped'][v] = inf['stopped'][k]
+      info['valid'][v], info['rms'][v] = inf['valid'][-1, k], inf['rms'][-1, k]
+  return poses, info
+
+
+def reconstruct_object(views, voxel_size=0.002, trunc=None, min_weight=1, depth_filter=True, margin=None, device='cuda', refine_poses=False):
   """Reference views -> mesh (synthetic.SimpleMesh with vertex normals and colours).  `views`: a folder in the reference's layout
   (load_reference_views) or a dict with depths, masks, K, cam_in_obs and optionally rgbs.  depth_filter runs erode_depth and
   bilateral_filter_depth on every view first, as the estimator does with an observed frame.  The fusion and the extraction run on the
   GPU; afterwards every connected component except the one with the most faces is dropped ON THE HOST (scipy connected_components over
-  the faces) and the vertices are re-indexed in their old order - fused depth noise leaves small floating pieces."""
-  from .Utils import bilateral_filter_depth, erode_depth
+  the faces) and the vertices are re-indexed in their old order - fused depth noise leaves small floating pieces.  refine_poses=True
+  runs the procedure of refine_view_poses first (view 0 is the anchor) and fuses with the poses it returns; the default fuses with the
+  poses as given.  The refinement aligns on the eroded maps, before the bilateral filter, in a volume of its own: `trunc` and `margin`
+  here are the fusion's and are NOT passed on to it (its band is 2 voxels, its margin 5 voxels + 1 cm); give refine_poses a dict of
+  refine_view_poses' keyword arguments (anchor, order, rounds, trunc, margin, iterations, min_pixels, damping, max_step) to set them."""
   if isinstance(views, (str, os.PathLike)):
     views = load_reference_views(views)
   dev = _device(device)
-  depths = torch.as_tensor(views['depths'], device=dev).to(torch.float)
-  if depth_filter:
-    depths = torch.stack([bilateral_filter_depth(erode_depth(d.contiguous(), radius=2, device=dev), radius=2, device=dev) for d in depths])
-  origin, dims = volume_from_views(depths, views.get('masks'), views['K'], views['cam_in_obs'], voxel_size, margin=margin, device=dev)
+  eroded = _eroded_depths(views, depth_filter, dev)
+  cam_in_obs = views['cam_in_obs']
+  if refine_poses:
+    kw = dict(anchor=0, order='greedy', rounds=0, trunc=None, margin=None, iterations=10, min_pixels=100, damping=1e-9, max_step=None)
+    given = dict(refine_poses) if isinstance(refine_poses, dict) else {}
+    if set(given) - set(kw):
+      raise TypeError(f'refine_poses: unknown keys {sorted(set(given) - set(kw))}')
+    kw.update(given)
+    solver = {k: kw.pop(k) for k in ('iterations', 'min_pixels', 'damping', 'max_step')}
+    cam_in_obs, _ = _refine_on(eroded, views, voxel_size, kw['anchor'], kw['order'], kw['rounds'], kw['trunc'], kw['margin'], solver, dev)
+  depths = _fusion_depths(eroded, depth_filter, dev)
+  origin, dims = volume_from_views(depths, views.get('masks'), views['K'], cam_in_obs, voxel_size, margin=margin, device=dev)
   vol = TsdfVolume(origin, voxel_size, dims, trunc=trunc, device=dev)
-  vol.integrate(depths, views['K'], views['cam_in_obs'], rgbs=views.get('rgbs'), masks=views.get('masks'))
+  vol.integrate(depths, views['K'], cam_in_obs, rgbs=views.get('rgbs'), masks=views.get('masks'))
   mesh = vol.extract_mesh(min_weight)
   keep = largest_component(mesh.faces, len(mesh.vertices))
   if len(keep) and not keep.all():

@@ -569,7 +569,37 @@ int fp_draw_poses(fp_ctx *ctx, const fp_draw_args *args, void *stream);
  *      or null, d_faces (n_faces,3) int32; nothing synchronises.  It returns FP_EINVAL when no count has happened since the last
  *      integrate or reset of the volume, when n_vertices / n_faces are not the counted ones, or when a required buffer is null
  *      (d_vertices with n_vertices > 0, d_faces with n_faces > 0).  min_weight must be > 0 (FP_EINVAL).
- *      fp_tsdf_read_plane copies plane FP_TSDF_PLANE_* into d_out (nx ny nz fp32, device) on the stream. */
+ *      fp_tsdf_read_plane copies plane FP_TSDF_PLANE_* into d_out (nx ny nz fp32, device) on the stream.
+ *      Align (frame-to-model: one Gauss-Newton linearisation of the poses of n_views depth maps against the volume; the solver is the
+ *      caller's - foundationpose_amd/reconstruct.py: TsdfVolume.align).  d_depth, d_mask, K and cam_in_ob as for integrate, but cam_in_ob
+ *      is used as given, not inverted: Rc, tc = its rotation and translation cast to fp32.  One workgroup per (view, tile of 1024 pixels),
+ *      pixel index row W + col.  Per view and pixel, in fp32, not contracted, in the written order:
+ *        d = depth[row, col];               skip unless d >= 0.001 and d < zfar, and, with a mask, mask[row, col] != 0
+ *        p = ((((float)col - cx) / fx) d, (((float)row - cy) / fy) d, d)
+ *        x_a = ((Rc[a][0] p.x + Rc[a][1] p.y) + Rc[a][2] p.z) + tc[a]                  the pixel's point in the object frame
+ *        g_a = (x_a - o_a) / v,  i_a = floor(g_a),  f_a = g_a - i_a;   skip unless 0 <= i_a <= n_a - 2 for a = x, y, z (the 8 corners
+ *        (i + {0,1}) of the cell lie inside the volume), and unless W >= min_weight at all 8 corners
+ *        T_c = T at corner c = dx + 2 dy + 4 dz.  x-differences d00 = T1 - T0, d10 = T3 - T2, d01 = T5 - T4, d11 = T7 - T6; x-lerps
+ *        a00 = T0 + d00 f.x, a10 = T2 + d10 f.x, a01 = T4 + d01 f.x, a11 = T6 + d11 f.x; y-differences e0 = a10 - a00, e1 = a11 - a01;
+ *        y-lerps b0 = a00 + e0 f.y, b1 = a01 + e1 f.y; dz = b1 - b0; the trilinear interpolant T = b0 + dz f.z
+ *        skip unless |T| < 1                                                            (a truncated sample has no gradient)
+ *        h0 = d00 + (d10 - d00) f.y, h1 = d01 + (d11 - d01) f.y;  s = trunc / v
+ *        G = ((h0 + (h1 - h0) f.z) s, (e0 + (e1 - e0) f.z) s, dz s)                     the gradient of the same interpolant, per metre
+ *        r = T trunc                                                                    the residual, metres
+ *        J = (G.x, G.y, G.z, x.y G.z - x.z G.y, x.z G.x - x.x G.z, x.x G.y - x.y G.x)   dr / dxi of cam_in_ob <- exp(xi) cam_in_ob,
+ *                                                                                       xi = (translation, rotation), object frame
+ *      ("unless" so that a NaN skips.)  d_rows, when not null, (n_views,H,W,8) fp32 on the device, 16-byte aligned
+ *      (it is written as float4; FP_EINVAL otherwise), gets (J0 .. J5, r, valid = 1) per
+ *      pixel and eight zeros where the pixel was skipped: it exists so that the rule can be tested bit for bit.  h_sums, HOST
+ *      (n_views, FP_TSDF_ALIGN_TERMS) float64: per view the 21 entries of the upper triangle of J^T J row by row ((0,0), (0,1) .. (0,5),
+ *      (1,1) .. (5,5)), the 6 of J^T r, sum r r, the number of valid pixels.  Every term is formed in double from the fp32 values (a
+ *      product of two fp32 numbers is exact in double) and added in double: over a lane's 4 pixels, over the wave by a butterfly, over
+ *      the waves in order, and by a second launch over the tiles in order.  No atomics: a view's 29 numbers are bit-identical from run
+ *      to run, in any batch and at any index of it.  fp_tsdf_align SYNCHRONISES the stream (the sums are copied to the host; the partial
+ *      sums live in the context's arena for the duration of the call).  The volume is only read; one that was never integrated into
+ *      skips every pixel (count 0).  FP_EINVAL: a null ctx, vol, d_depth, K, cam_in_ob or h_sums, n_views outside 0 ..
+ *      FP_TSDF_MAX_VIEWS (0 writes nothing), H or W < 1, fx or fy not > 0, zfar not > 0 (infinity is allowed), min_weight not > 0, a
+ *      view matrix that is not finite or whose last row is not 0 0 0 1. */
 typedef struct fp_tsdf fp_tsdf;
 #define FP_TSDF_MAX_POINTS (1 << 27)   /* 512^3 */
 #define FP_TSDF_MAX_VIEWS 64           /* per fp_tsdf_integrate call: the view matrices travel as kernel arguments */
@@ -579,6 +609,7 @@ typedef struct fp_tsdf fp_tsdf;
 #define FP_TSDF_PLANE_G 3
 #define FP_TSDF_PLANE_B 4
 #define FP_TSDF_PLANE_COLOR_WEIGHT 5
+#define FP_TSDF_ALIGN_TERMS 29         /* doubles per view of fp_tsdf_align's h_sums */
 int fp_tsdf_create(fp_ctx *ctx, const double *origin, float voxel_size, const int *dims, float trunc, fp_tsdf **out);
 int fp_tsdf_destroy(fp_tsdf *vol);
 int fp_tsdf_reset(fp_ctx *ctx, fp_tsdf *vol, void *stream);
@@ -588,6 +619,8 @@ int fp_tsdf_extract_count(fp_ctx *ctx, fp_tsdf *vol, float min_weight, int64_t *
 int fp_tsdf_extract_write(fp_ctx *ctx, fp_tsdf *vol, float *d_vertices, float *d_normals, uint8_t *d_colors, int32_t *d_faces,
                           int64_t n_vertices, int64_t n_faces, void *stream);
 int fp_tsdf_read_plane(fp_ctx *ctx, const fp_tsdf *vol, int plane, float *d_out, void *stream);
+int fp_tsdf_align(fp_ctx *ctx, const fp_tsdf *vol, const float *d_depth, const uint8_t *d_mask, int n_views, int H, int W, const double *K,
+                  const double *cam_in_ob, float zfar, float min_weight, float *d_rows, double *h_sums, void *stream);
 
 /* ---- building blocks exported for parity tests and profiling ---------------------------------- */
 /* fp16 NHWC implicit-GEMM convolution on MFMA: out = act(conv(in, w) + bias [+ res]).  w_packed is

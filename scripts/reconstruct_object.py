@@ -1,14 +1,18 @@
 """A mesh from a folder of posed RGB-D reference views (the reference's model-free layout: rgb/, depth_enhanced/ or depth/, mask/,
 cam_in_ob/, K.txt), by TSDF fusion and marching tetrahedra on the GPU (foundationpose_amd.reconstruct).
-usage: python scripts/reconstruct_object.py DIR [--voxel 0.002] [--trunc T] [--min-weight 1] [--no-depth-filter] [--out DIR/model/model.obj]
-The output format follows the extension: .obj or .ply."""
+usage: python scripts/reconstruct_object.py DIR [--voxel 0.002] [--trunc T] [--min-weight 1] [--no-depth-filter] [--refine-poses]
+       [--out DIR/model/model.obj]
+The output format follows the extension: .obj or .ply.  --refine-poses aligns every view but the first to the geometry fused so far before the
+fusion (reconstruct.refine_view_poses) and also writes the poses it used to DIR/cam_in_ob_refined/NAME.txt."""
 import argparse
 import os
 import sys
 
+import numpy as np
+
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from foundationpose_amd import mesh_io
-from foundationpose_amd.reconstruct import reconstruct_object
+from foundationpose_amd.reconstruct import load_reference_views, reconstruct_object, refine_view_poses
 
 
 def main():
@@ -18,10 +22,20 @@ def main():
   ap.add_argument('--trunc', type=float, default=None)
   ap.add_argument('--min-weight', type=float, default=1)
   ap.add_argument('--no-depth-filter', action='store_true')
+  ap.add_argument('--refine-poses', action='store_true')
   ap.add_argument('--out', default=None)
   args = ap.parse_args()
   out = args.out or os.path.join(args.dir, 'model', 'model.obj')
-  mesh = reconstruct_object(args.dir, voxel_size=args.voxel, trunc=args.trunc, min_weight=args.min_weight, depth_filter=not args.no_depth_filter)
+  views = load_reference_views(args.dir)
+  if args.refine_poses:
+    poses, info = refine_view_poses(views, voxel_size=args.voxel, depth_filter=not args.no_depth_filter)
+    os.makedirs(os.path.join(args.dir, 'cam_in_ob_refined'), exist_ok=True)
+    for name, pose in zip(views['names'], poses):
+      np.savetxt(os.path.join(args.dir, 'cam_in_ob_refined', name + '.txt'), pose, fmt='%.18e')
+    for v, why in sorted(info['stopped'].items()):
+      print(f'view {views["names"][v]}: alignment stopped ({why})')
+    views = dict(views, cam_in_obs=poses)
+  mesh = reconstruct_object(views, voxel_size=args.voxel, trunc=args.trunc, min_weight=args.min_weight, depth_filter=not args.no_depth_filter)
   os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
   if out.lower().endswith('.ply'):
     mesh_io.save_ply(mesh, out)
