@@ -6,6 +6,7 @@
 // pose update: learning/training/predict_pose_refine.py:195-231 + pytorch3d so3_exp_map +
 // src/Utils.py:848-855.
 #include "common.h"
+#include "device_util.h"
 #include "pose_math.h"
 
 #define AT_DH 128
@@ -22,12 +23,7 @@
 #define FA_QW_HALFS (32 * AT_DH)             // a wave's Q^T staging area: 8 fragments x 64 lanes x 8 halfs (8 KB)
 #define FA_LDS_BYTES ((FA_NSTAGE * FA_STAGE_HALFS + FA_WAVES * FA_QW_HALFS) * 2)
 
-// LDS-DMA from inline asm (see conv_halo.hip: through the builtin, hipcc turns every later LDS-read wait into lgkmcnt(0));
-// completion is waited for by the explicit s_waitcnt vmcnt(n) in front of the barriers of the key loop.
-__device__ __forceinline__ void at_glds16(const f16 *g, f16 *l) {
-  const unsigned la = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) void *)l);
-  asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "s"(la) : "memory");
-}
+// LDS-DMA (glds16) and the counted waits in front of the barriers of the key loop: device_util.h
 
 // Flash-style multi-head self-attention core (400 tokens, 4 heads x 128) on v_mfma_f32_32x32x16_f16.
 // A work item = one (hypothesis, head, 224-query block): 13 query tiles of 32 split 7 + 6 over two items; each of the
@@ -81,10 +77,6 @@ __device__ __forceinline__ float fa_max3(float a, float b, float c) {
   float r;
   asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
   return r;
-}
-__device__ __forceinline__ void at_glds16s(const f16 *sbase, unsigned voff_bytes, f16 *l) {
-  const unsigned la = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) void *)l);
-  asm volatile("s_mov_b32 m0, %2\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff_bytes), "s"(sbase), "s"(la) : "memory");
 }
 
 __global__ __launch_bounds__(FA_THREADS, 2) void attention_kernel(const f16 *__restrict__ qk, const f16 *__restrict__ vt, int T,
@@ -150,7 +142,7 @@ __global__ __launch_bounds__(FA_THREADS, 2) void attention_kernel(const f16 *__r
       const bool is_k = i < 16;                              // wave-uniform
       const unsigned t = min((unsigned)(s_kb * FA_KB) + sx[u], is_k ? (unsigned)(T - 1) : 408u);
       const unsigned voff = t * (is_k ? 2048u : 2u) + sadd[u];
-      at_glds16s(is_k ? s_kbase : s_vsrc, voff, smem + s_slot * FA_STAGE_HALFS + i * 512);
+      glds16(is_k ? s_kbase : s_vsrc, voff, smem + s_slot * FA_STAGE_HALFS + i * 512);
     }
     s_slot = s_slot + 1 == FA_NSTAGE ? 0 : s_slot + 1;
     if (++s_kb == nkb) {
@@ -168,7 +160,7 @@ __global__ __launch_bounds__(FA_THREADS, 2) void attention_kernel(const f16 *__r
     const f16 *qbase = qk + ((size_t)b * T + qb * FA_QB) * 1024 + h * AT_DH;
     const unsigned voff = min(qrow, (unsigned)(T - 1 - qb * FA_QB)) * 2048u + lh * 16;
 #pragma unroll
-    for (int s = 0; s < 8; ++s) at_glds16s(qbase + s * 16, voff, qlds + s * 512);
+    for (int s = 0; s < 8; ++s) glds16(qbase + s * 16, voff, qlds + s * 512);
   };
 
   // ---- LDS fragment offsets (bytes, within a stage) ----
@@ -227,10 +219,10 @@ __global__ __launch_bounds__(FA_THREADS, 2) void attention_kernel(const f16 *__r
       int allowed = inflight > 1 ? 5 : 0;
       if (KB0) allowed = first ? 0 : (nkb == 1 ? st_prev : allowed + st_prev);
       else if (kb == 1 && has_next) allowed += 8;
-      if (allowed == 0) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-      else if (allowed == 5) asm volatile("s_waitcnt vmcnt(5) lgkmcnt(0)" ::: "memory");
-      else if (allowed == 8) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(13) lgkmcnt(0)" ::: "memory");
+      if (allowed == 0) wait_vm_lgkm<0>();
+      else if (allowed == 5) wait_vm_lgkm<5>();
+      else if (allowed == 8) wait_vm_lgkm<8>();
+      else wait_vm_lgkm<13>();
       __builtin_amdgcn_s_barrier();
       __builtin_amdgcn_sched_barrier(0);
       ASTAMP(3 + 4 * kb);
@@ -410,7 +402,6 @@ __global__ __launch_bounds__(FS_WAVES * 64) void attention_small_kernel(const f1
   const float c2 = 0.08838834764831845f * 1.4426950408889634f;      // log2(e) / sqrt(128)
   f16 *area = reinterpret_cast<f16 *>(fs_lds + (size_t)w * FS_AREA_BYTES);
   if (w < nkb) {
-    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
     // K block and V^T block of this wave: coalesced 16-byte loads (a key row is 256 contiguous bytes, a dim row of the block 128), all
     // requested up front; (first form, measured: the fragments as per-lane gathers, 40 per wave at the L1's tag rate: 12.3 us)
     u32x4 kq[16], vq[16];
@@ -439,7 +430,7 @@ __global__ __launch_bounds__(FS_WAVES * 64) void attention_small_kernel(const f1
       const int i = lane + 64 * u;
       *reinterpret_cast<u32x4 *>(area + (i >> 4) * FS_KP + (i & 15) * 8) = kq[u];
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                 // (the wave reads what it wrote itself: no barrier)
+    wait_lgkm();                 // (the wave reads what it wrote itself: no barrier)
     half8 kf[2][8];
 #pragma unroll
     for (int kt = 0; kt < 2; ++kt)
@@ -477,13 +468,13 @@ __global__ __launch_bounds__(FS_WAVES * 64) void attention_small_kernel(const f1
       }
     ps += __shfl_xor(ps, 32);
     // the K fragments are in registers: the area takes the V^T block (rows = dims, the block's 64 keys in the image's token order)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkm();
 #pragma unroll
     for (int u = 0; u < 16; ++u) {
       const int i = lane + 64 * u;
       *reinterpret_cast<u32x4 *>(area + (i >> 3) * FS_VP + (i & 7) * 8) = vq[u];
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkm();
     floatx16 oacc[4];
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt)
@@ -503,7 +494,7 @@ __global__ __launch_bounds__(FS_WAVES * 64) void attention_small_kernel(const f1
                                                             oacc[dt], 0, 0, 0);
       }
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                 // the V^T block is read: the area takes the partial O^T
+    wait_lgkm();                 // the V^T block is read: the area takes the partial O^T
     float *po = reinterpret_cast<float *>(area) + lr;
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt)
@@ -560,12 +551,6 @@ int launch_attention(fp_ctx *ctx, const f16 *qk, const f16 *vt, int B, int T, f1
 }
 
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 // Token mean + output Linear behind the final LayerNorm of a RefineNet head:
 // mean_t(Linear(LN(x_t))) == Linear(mean_t LN(x_t))  (refine_network.py:90-91).  The LayerNorm itself runs in the epilogue of
 // linear2 (tok_gemm.hip, EPI_LNSUM), which leaves the sums of the normalised rows over groups of 16 tokens; one small workgroup

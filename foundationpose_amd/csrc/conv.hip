@@ -15,6 +15,7 @@
 // v_mfma_f32_32x32x16_f16; both operands staged by LDS-DMA through a 3-deep ring (below).  The 3x3 stride-1 layers
 // have their own kernel (conv_halo.hip).
 #include "common.h"
+#include "device_util.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -40,17 +41,7 @@ extern "C" __attribute__((visibility("default"))) int fp_dbg_igemm_stamps(unsign
 #define ISTAMP(x)
 #endif
 
-// LDS-DMA from inline asm (see conv_halo.hip: through the builtin hipcc turns every later LDS-read wait into lgkmcnt(0) and
-// every barrier into a full vmcnt(0) drain).  Completion is waited for by the explicit s_waitcnt vmcnt(n) before the barriers.
-// scalar base + 32-bit lane offset form: no per-lane 64-bit address arithmetic in front of the DMA
-__device__ __forceinline__ void glds16s(const f16 *sbase, unsigned voff_bytes, f16 *l) {
-  const unsigned la = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) void *)l);
-  asm volatile("s_mov_b32 m0, %2\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff_bytes), "s"(sbase), "s"(la) : "memory");
-}
-__device__ __forceinline__ void glds16c(const f16 *g, f16 *l) {
-  const unsigned la = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) void *)l);
-  asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "s"(la) : "memory");
-}
+// LDS-DMA (glds16: scalar base + lane offset for the linear operands, one address per lane for the gather) and the counted waits: device_util.h
 
 // One workgroup tile: 64 NT pixels x BM couts, 4 waves as 2 (cout halves) x 2 (pixel halves), each wave (BM/2) x 32 NT.
 // NT = 4 -> the 256-pixel main tiles, NT = 1 -> 64-pixel tail tiles (conv_igemm2_kernel).  The accumulation order of an
@@ -111,7 +102,7 @@ __device__ __forceinline__ void igemm2_tile(const ConvArgs &p, const f16 *__rest
       if (kt > 1) return;      // timing experiment only (wrong results): no activation DMA after the first two stages
 #endif
       if (lin) {
-        glds16s(p.in + kt * C2_BK, xlin[q], xs + (q * 4 + wave) * 512);
+        glds16(p.in + kt * C2_BK, xlin[q], xs + (q * 4 + wave) * 512);
         return;
       }
       const int k = kt * C2_BK + xch[q] * 8;
@@ -127,13 +118,13 @@ __device__ __forceinline__ void igemm2_tile(const ConvArgs &p, const f16 *__rest
       const int iy = iy0[q] + ky, ix = ix0[q] + kx;
       const bool ok = tap < ntaps && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
       const f16 *src = ok ? p.in + xbase[q] + ((long long)iy * p.W + ix) * p.Cin + ci : zero_page;
-      glds16c(src, xs + (q * 4 + wave) * 512);
+      glds16(src, xs + (q * 4 + wave) * 512);
     } else {
       const int q = d - NT;
 #ifdef IGEMM_SKIP_W
       if (kt > 1) return;      // timing experiment only (wrong results): no weight DMA after the first two stages
 #endif
-      glds16s(wbase + (size_t)(q * 64) * p.Kpad + (size_t)kt * C2_BK, woff, ws + (q * 4 + wave) * 512);
+      glds16(wbase + (size_t)(q * 64) * p.Kpad + (size_t)kt * C2_BK, woff, ws + (q * 4 + wave) * 512);
     }
   };
   auto stage = [&](int kt, int buf) __attribute__((always_inline)) {
@@ -182,8 +173,8 @@ __device__ __forceinline__ void igemm2_tile(const ConvArgs &p, const f16 *__rest
   if (nk > 1) stage(kb + 1, 1);
   for (int kt = 0; kt < nk; ++kt) {
     const int cur = kt % 3;
-    if (kt + 1 < nk) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(DMAW) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    if (kt + 1 < nk) wait_vm_lgkm<DMAW>();
+    else wait_vm_lgkm<0>();
     __builtin_amdgcn_s_barrier();          // stage kt landed for every wave; slot (kt+2)%3 was last read in step kt-1: free
     __builtin_amdgcn_sched_barrier(0);
     if (kt + 2 < nk) stage(kb + kt + 2, (kt + 2) % 3);
@@ -238,7 +229,6 @@ __device__ __forceinline__ void igemm2_tile(const ConvArgs &p, const f16 *__rest
     constexpr int CPR = BM / 8;           // 16-byte chunks per staged row
     constexpr int NCH = TN * CPR / 256;
     constexpr int RB = NCH < 8 ? NCH : 8;
-    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
     u32x4 rv[NCH];
     if constexpr (RES) {                  // residual tile: ONE batch of coalesced 16-byte loads before the barrier, staged through LDS
 #pragma unroll

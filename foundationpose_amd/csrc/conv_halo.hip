@@ -13,9 +13,8 @@
 // Epilogue: accumulators start at the bias; residual (staged through LDS) + ReLU (+ positional embedding) in fp32, one
 // rounding to fp16, LDS transpose, 16-byte row-contiguous NHWC stores.
 #include "common.h"
+#include "device_util.h"
 #include <cstdlib>
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));   // 16-byte register value (plain vector loads / stores in IR)
 
 
 #define HL_BM 128
@@ -45,15 +44,7 @@ struct IC {
   static constexpr int value = V;
 };
 
-// LDS-DMA issued from inline asm.  Through __builtin_amdgcn_global_load_lds the compiler marks a "flat access that may
-// touch LDS" as pending until the next full drain, and while that mark is up EVERY wait it inserts for an LDS fragment read
-// is s_waitcnt lgkmcnt(0) (and every barrier drains vmcnt(0)) - no LDS read can stay in flight under the MFMAs.  Hidden in
-// asm, the DMA is outside its bookkeeping: fragment reads get counted lgkmcnt(n); the DMA's completion is waited for by
-// the explicit s_waitcnt vmcnt(n) in front of the barriers below.  m0 = wave-uniform LDS byte address, lane i lands at +16 i.
-__device__ __forceinline__ void glds16(const f16 *sbase, unsigned voff_bytes, f16 *l) {
-  const unsigned la = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) void *)l);
-  asm volatile("s_mov_b32 m0, %2\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff_bytes), "s"(sbase), "s"(la) : "memory");
-}
+// LDS-DMA (glds16) and the counted waits in front of the barriers below: device_util.h
 
 #ifdef HALO_STAMP      // diagnostic builds only: the register-staged form that carries the in-kernel cycle stamps
 #define HALO_DIAG_SECTION 1
@@ -300,14 +291,9 @@ __device__ __forceinline__ void halo_tile_dma(const ConvArgs &p, const int m0, c
       // weights(g) - and at ky=0 the band of this chunk - must have landed.  The band DMAs of the NEXT chunk, issued in
       // group ky=0, are younger than the weights needed at ky=1: a counted vmcnt leaves them in flight there.
       if (ky == 1 && cc + 1 < nchunk) {
-        static_assert(HQ >= 2 && HQ <= 6, "add the vmcnt immediate for this tile");
-        if constexpr (HQ == 6) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");
-        else if constexpr (HQ == 5) asm volatile("s_waitcnt vmcnt(5) lgkmcnt(0)" ::: "memory");
-        else if constexpr (HQ == 4) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
-        else if constexpr (HQ == 3) asm volatile("s_waitcnt vmcnt(3) lgkmcnt(0)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
+        wait_vm_lgkm<HQ>();
       } else {
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        wait_vm_lgkm<0>();
       }
       __builtin_amdgcn_s_barrier();
       STAMP(unsigned long long tb = __builtin_amdgcn_s_memtime(); t_wait += tb - ta;)

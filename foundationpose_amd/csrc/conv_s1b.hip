@@ -23,6 +23,7 @@
 // eight K groups the halo kernel's prologue / epilogue share is small and its weights are shared through LDS (here each cout block
 // re-reads the band and each wave streams its own weights).
 #include "common.h"
+#include "device_util.h"
 
 #define B1_THREADS 256
 #define B1_W 40
@@ -36,11 +37,6 @@
 #define B1_NPT 5
 #define B1_STAGE_LD 72                                    // halfs per staged pixel: 64 couts + 8 pad
 #define B1_LDS_BYTES (2 * B1_BAND_BYTES)
-
-__device__ __forceinline__ void b1_glds16(const void *g, unsigned lds_addr) {
-  lds_addr = __builtin_amdgcn_readfirstlane(lds_addr);
-  asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "s"(lds_addr) : "memory");
-}
 
 template <bool RES>
 __global__ __launch_bounds__(B1_THREADS, 2) void conv3x3_s1_band_kernel(ConvArgs p, const f16 *__restrict__ wpk, const f16 *__restrict__ zero_page, int n_tiles,
@@ -72,7 +68,7 @@ __global__ __launch_bounds__(B1_THREADS, 2) void conv3x3_s1_band_kernel(ConvArgs
 #pragma unroll
     for (int v = 0; v < DPW; ++v) {
       const char *src = src_off[v] != 0xffffffffu ? (const char *)p.in + src_off[v] + grp * 64 : (const char *)zero_page;
-      b1_glds16(src, lds0 + buf * B1_BAND_BYTES + (wave + 4 * v) * 1024);
+      glds16(src, lds0 + buf * B1_BAND_BYTES + (wave + 4 * v) * 1024);
     }
   };
   // ---- B fragments: lane = output pixel 32 j + lr of the wave's 160 (local row jr of its 4, column ox), k half lh; tap (ky, kx) of
@@ -114,7 +110,7 @@ __global__ __launch_bounds__(B1_THREADS, 2) void conv3x3_s1_band_kernel(ConvArgs
       }
   }
   for (int grp = 0; grp < ngrp; ++grp) {
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    wait_vm_lgkm<0>();
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
     if (grp + 1 < ngrp) band_dma(grp + 1, (grp + 1) & 1);
@@ -144,7 +140,7 @@ __global__ __launch_bounds__(B1_THREADS, 2) void conv3x3_s1_band_kernel(ConvArgs
       __builtin_amdgcn_sched_barrier(0);
     }
   }
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+  wait_vm_lgkm<0>();
   __builtin_amdgcn_s_barrier();
   __builtin_amdgcn_sched_barrier(0);
 
@@ -164,7 +160,7 @@ __global__ __launch_bounds__(B1_THREADS, 2) void conv3x3_s1_band_kernel(ConvArgs
         const uint4 rv = *reinterpret_cast<const uint4 *>(p.res + (size_t)m * p.Cout + co0 + c8 * 8);
         *reinterpret_cast<uint4 *>(&stage[px * B1_STAGE_LD + c8 * 8]) = rv;
       }
-      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+      wait_vm_lgkm<0>();
     }
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct)
@@ -182,7 +178,7 @@ __global__ __launch_bounds__(B1_THREADS, 2) void conv3x3_s1_band_kernel(ConvArgs
         for (int e = 0; e < 4; ++e) hv[e] = (f16)fmaxf(v[e], lo);
         *reinterpret_cast<half4 *>(sp) = hv;
       }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkm();
     uint4 v4[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) v4[u] = *reinterpret_cast<const uint4 *>(&stage[(u * 8 + (lane >> 3)) * B1_STAGE_LD + (lane & 7) * 8]);
@@ -193,7 +189,7 @@ __global__ __launch_bounds__(B1_THREADS, 2) void conv3x3_s1_band_kernel(ConvArgs
       const long long orow = hi ? (long long)(m - p.split_m) : (long long)m;
       *reinterpret_cast<uint4 *>((f16 *)p.out + orow * p.out_ld + (hi ? p.coff_hi : 0) + co0 + (lane & 7) * 8) = v4[u];
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkm();
   }
 }
 

@@ -24,14 +24,10 @@
 // 208 us in a bench step - a 16-channel chunk pass touches every 128-byte line of the band and uses 32 bytes of it, and with Cin = 64 the
 // bands in flight on an XCD (64 workgroups x 104 KB of lines) overflow its 4-MB L2 before the other three chunks come by.
 #include "common.h"
+#include "device_util.h"
 
 #define S2_THREADS 256
 #define S2_STAGE_PAD 8
-
-__device__ __forceinline__ void s2_glds16(const void *g, unsigned lds_addr) {
-  lds_addr = __builtin_amdgcn_readfirstlane(lds_addr);
-  asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "s"(lds_addr) : "memory");
-}
 
 template <int WO, int ROWS, int CT>
 struct S2Cfg {
@@ -112,7 +108,7 @@ __global__ __launch_bounds__(S2_THREADS, 2) void conv3x3_s2_kernel(ConvArgs p, c
 #pragma unroll
     for (int v = 0; v < DPW; ++v) {
       const char *src = src_off[v] != 0xffffffffu ? (const char *)p.in + src_off[v] + ch * 32 : (const char *)zero_page;
-      s2_glds16(src, lds0 + buf * C::BAND_BYTES + (wave + 4 * v) * 1024);
+      glds16(src, lds0 + buf * C::BAND_BYTES + (wave + 4 * v) * 1024);
     }
   };
 
@@ -160,7 +156,7 @@ __global__ __launch_bounds__(S2_THREADS, 2) void conv3x3_s2_kernel(ConvArgs p, c
   for (int ch = 0; ch < nch; ++ch) {
     // this wave's part of chunk ch has landed (everything this wave has in flight: the three prefetched weight taps are needed next
     // anyway); after the barrier every wave's part has, and every wave is done reading the other buffer (chunk ch - 1)
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    wait_vm_lgkm<0>();
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
     if (ch + 1 < nch) band_dma(ch + 1, (ch + 1) & 1);
@@ -191,7 +187,7 @@ __global__ __launch_bounds__(S2_THREADS, 2) void conv3x3_s2_kernel(ConvArgs p, c
       __builtin_amdgcn_sched_barrier(0);
     }
   }
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");          // the trailing weight prefetches
+  wait_vm_lgkm<0>();          // the trailing weight prefetches
   __builtin_amdgcn_s_barrier();                                         // every wave is done with the bands: staging may overwrite them
   __builtin_amdgcn_sched_barrier(0);
 
@@ -213,7 +209,7 @@ __global__ __launch_bounds__(S2_THREADS, 2) void conv3x3_s2_kernel(ConvArgs p, c
         for (int e = 0; e < 4; ++e) hv[e] = (f16)fmaxf(acc[ct][j][rg * 4 + e], lo);
         *reinterpret_cast<half4 *>(&stage[lr * C::STAGE_LD + ct * 32 + rg * 8 + lh * 4]) = hv;
       }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkm();
     uint4 v[32 / PPI];
 #pragma unroll
     for (int u = 0; u < 32 / PPI; ++u) v[u] = *reinterpret_cast<const uint4 *>(&stage[(u * PPI + lane / LPP) * C::STAGE_LD + (lane % LPP) * 8]);
@@ -222,7 +218,7 @@ __global__ __launch_bounds__(S2_THREADS, 2) void conv3x3_s2_kernel(ConvArgs p, c
       const size_t m = m0 + 32 * j + u * PPI + lane / LPP;
       if (m < (size_t)p.M) *reinterpret_cast<uint4 *>((f16 *)p.out + m * p.Cout + co0 + (lane % LPP) * 8) = v[u];
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkm();
   }
 }
 

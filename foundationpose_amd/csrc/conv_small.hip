@@ -22,6 +22,7 @@
 // fp32 accumulation; one summation order of its own (per wave: taps in order, 16-channel steps in order; then the waves in
 // order), so results differ in the last fp32 bits from the large-batch kernels' - like the split-K form it replaces.
 #include "common.h"
+#include "device_util.h"
 
 namespace {
 
@@ -66,7 +67,6 @@ __global__ __launch_bounds__(NW * 64) void conv3x3_small_kernel(ConvArgs p, cons
   {
     constexpr int PPR = C::CIN / 8;                     // 16-byte pieces per pixel
     constexpr int NP = C::SPAN * PPR, IT = (NP + NW * 64 - 1) / (NW * 64);
-    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
     u32x4 v[IT];
 #pragma unroll
     for (int u = 0; u < IT; ++u) {
@@ -93,7 +93,7 @@ __global__ __launch_bounds__(NW * 64) void conv3x3_small_kernel(ConvArgs p, cons
     if (tid < PPR) *reinterpret_cast<u32x4 *>(&band[C::SPAN * C::PITCH + tid * 8]) = u32x4{0u, 0u, 0u, 0u};
   }
   // the band is in LDS for every wave (a __syncthreads() would also wait for the weight loads: vmcnt(0))
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  wait_lgkm();
   __builtin_amdgcn_s_barrier();
   __builtin_amdgcn_sched_barrier(0);
   // ---- K loop: this lane's pixel (operand B) m0 + lr; its k-block of step j: channels cofs + 8 j .. + 8

@@ -24,6 +24,7 @@
 // LDS-DMA fills from the context's zero page - so the inner loop has no border selects at all.  Double buffered (2 x 46 KB); the
 // transformed weights of one (chunk, ky) are a contiguous, pre-swizzled 16-KB block in global memory, ring of 3.
 #include "common.h"
+#include "device_util.h"
 #include <cstdlib>
 
 #define WN_CK 32
@@ -71,45 +72,24 @@ struct WinoCfg {
   static constexpr int LDS_BYTES = 2 * LDS_HALFS_MAIN;            // (the epilogue's fp32 staging, 4 x 33 KB, fits inside)
 };
 
-// LDS-DMA from inline asm (outside the compiler's waitcnt bookkeeping, see conv_halo.hip): m0 = wave-uniform LDS byte address, lane i lands at + 16 i
-// (destinations are LDS BYTE addresses: the kernel casts its LDS array to address space 3 once - a generic -> LDS cast per call makes hipcc
-// emit a null check against src_shared_base per DMA, and in the stamped build an illegal VOPC operand)
-__device__ __forceinline__ void wn_glds16_v(const void *g, unsigned lds_byte) {                 // per-lane 64-bit source address
-  const unsigned la = __builtin_amdgcn_readfirstlane(lds_byte);
-  asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "s"(la) : "memory");
-}
-// ... through a buffer resource: lanes whose offset lies outside the buffer (>= num_records: the 0x80000000 of the pad entries / zero rows)
+// LDS-DMA (glds16) and the counted waits: device_util.h.  Destinations are LDS BYTE addresses: the kernel casts its LDS array to address space 3
+// once (a generic -> LDS cast per call costs a null check per DMA, and in the stamped build an illegal VOPC operand).
+// The buffer-resource form: lanes whose offset lies outside the buffer (>= num_records: the 0x80000000 of the pad entries / zero rows)
 // land ZEROS - the hardware's own border handling, no zero page, no 64-bit address arithmetic per lane
 typedef int wn_i32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void wn_glds16_b(wn_i32x4 srd, unsigned voff_bytes, unsigned lds_byte) {
   const unsigned la = __builtin_amdgcn_readfirstlane(lds_byte);
   asm volatile("s_mov_b32 m0, %2\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds" ::"v"(voff_bytes), "s"(srd), "s"(la) : "memory");
 }
-__device__ __forceinline__ void wn_glds16_s(const f16 *sbase, unsigned voff_bytes, unsigned lds_byte) {   // scalar base + 32-bit lane offset
-  const unsigned la = __builtin_amdgcn_readfirstlane(lds_byte);
-  asm volatile("s_mov_b32 m0, %2\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff_bytes), "s"(sbase), "s"(la) : "memory");
-}
 
 // a - b on eight packed halfs: v_pk_add_f16 with the negate modifiers on the second operand (hipcc scalarises a v2f16 fsub into
 // v_sub_f16 + v_sub_f16_sdwa + v_pack_b32_f16: three instructions where one does)
-typedef unsigned int wn_u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ half8 wn_pk_sub(half8 a, half8 b) {
-  const wn_u32x4 ua = __builtin_bit_cast(wn_u32x4, a), ub = __builtin_bit_cast(wn_u32x4, b);
-  wn_u32x4 r;
+  const u32x4 ua = __builtin_bit_cast(u32x4, a), ub = __builtin_bit_cast(u32x4, b);
+  u32x4 r;
 #pragma unroll
   for (int k = 0; k < 4; ++k) asm("v_pk_add_f16 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r[k]) : "v"(ua[k]), "v"(ub[k]));
   return __builtin_bit_cast(half8, r);
-}
-
-template <int N>
-__device__ __forceinline__ void wn_wait_vm() {
-  if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-  else if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
-  else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
-  else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");
-  else if constexpr (N == 11) asm volatile("s_waitcnt vmcnt(11) lgkmcnt(0)" ::: "memory");
-  else if constexpr (N == 12) asm volatile("s_waitcnt vmcnt(12) lgkmcnt(0)" ::: "memory");
-  else static_assert(N < 0, "add the vmcnt immediate");
 }
 
 template <int W, int NW, bool RES, bool POST>
@@ -191,7 +171,7 @@ __global__ __launch_bounds__(NW * 64) void conv3x3_wino_kernel(ConvArgs p, const
     const f16 *sb = wsrc + (size_t)g * WN_WHALFS;
     const unsigned dst = lds0 + (C::WOFF + (g % WN_RING) * WN_WHALFS + wave * WQ * 512) * 2;
 #pragma unroll
-    for (int u = u0; u < u1; ++u) wn_glds16_s(sb + u * 512, (unsigned)lane * 16u, dst + u * 1024);
+    for (int u = u0; u < u1; ++u) glds16(sb + u * 512, (unsigned)lane * 16u, dst + u * 1024);
   };
 
   // ---- per-lane read bases: entry of (ky = 0, d1) of this lane's pair in pair tile j ----
@@ -243,7 +223,7 @@ __global__ __launch_bounds__(NW * 64) void conv3x3_wino_kernel(ConvArgs p, const
   // operands of group g + 1 - and the ring slot of weights(g - 1) and, in a ky = 0 group, the other band buffer are free: the DMA of
   // weights(g + 2) (WQ instructions) and band(cc + 1) (HQ) is issued from the eight phases behind B_g, weights first.
   // vmcnt in front of B_g: younger than weights(g + 1) is only the band that followed it behind B_(g-1), i.e. in a ky = 1 group.
-  if (G > 1) wn_wait_vm<WQ>(); else wn_wait_vm<0>();
+  if (G > 1) wait_vm_lgkm<WQ>(); else wait_vm_lgkm<0>();
   __builtin_amdgcn_s_barrier();
 
   struct Adr {            // LDS half offsets of one group's operands
@@ -276,18 +256,18 @@ __global__ __launch_bounds__(NW * 64) void conv3x3_wino_kernel(ConvArgs p, const
       }
     return A;
   };
-  typedef wn_u32x4 raw_t[NPT][4];
+  typedef u32x4 raw_t[NPT][4];
   auto load_raw = [&](const Adr &A, int ks, int j, int k, raw_t &d) __attribute__((always_inline)) {
     // k = 0: d0 (odd plane, L), 1: d1 (even, L), 2: d2 (odd, L + 1), 3: d3 (even, L + 1)
     const int base = (k & 2) ? A.a1[j][ks] : A.a0[j][ks];
-    d[j][k] = *reinterpret_cast<const wn_u32x4 *>(&lds[base + ((k & 1) ? 0 : PE * 32)]);
+    d[j][k] = *reinterpret_cast<const u32x4 *>(&lds[base + ((k & 1) ? 0 : PE * 32)]);
   };
   auto load_w = [&](const Adr &A, int ks, int i, half8 (&af)[2]) __attribute__((always_inline)) {
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct) af[ct] = *reinterpret_cast<const half8 *>(&lds[A.woff + i * (WN_BN * WN_CK) + ct * (32 * WN_CK) + wa[ks]]);
   };
   // dwords [k0, k0 + 2) of v_i of pair tile j from its raw fragments
-  auto vcalc = [&](int i, const raw_t &d, int j, int k0, wn_u32x4 &v) __attribute__((always_inline)) {
+  auto vcalc = [&](int i, const raw_t &d, int j, int k0, u32x4 &v) __attribute__((always_inline)) {
 #pragma unroll
     for (int k = k0; k < k0 + 2; ++k) {
       if (i == 0) asm("v_pk_add_f16 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(v[k]) : "v"(d[j][0][k]), "v"(d[j][2][k]));
@@ -319,14 +299,14 @@ __global__ __launch_bounds__(NW * 64) void conv3x3_wino_kernel(ConvArgs p, const
     }
   };
   // one k-step (A, ks); (An, ksn) is the next one.  In: dcur raw, w0 weight fragments of m_0, va = v_0.  Out: the same for the next step.
-  auto kstep = [&](const Adr &A, int ks, const Adr &An, int ksn, raw_t &dcur, raw_t &dnxt, half8 (&w0)[2], half8 (&w1)[2], wn_u32x4 (&va)[NPT],
-                   wn_u32x4 (&vb)[NPT], int slot0) __attribute__((always_inline)) {
+  auto kstep = [&](const Adr &A, int ks, const Adr &An, int ksn, raw_t &dcur, raw_t &dnxt, half8 (&w0)[2], half8 (&w1)[2], u32x4 (&va)[NPT],
+                   u32x4 (&vb)[NPT], int slot0) __attribute__((always_inline)) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       half8(&wi)[2] = (i & 1) ? w1 : w0;          // m_0, m_2 in w0's registers, m_1, m_3 in w1's
       half8(&wn)[2] = (i & 1) ? w0 : w1;
-      wn_u32x4(&vi)[NPT] = (i & 1) ? vb : va;
-      wn_u32x4(&vn)[NPT] = (i & 1) ? va : vb;
+      u32x4(&vi)[NPT] = (i & 1) ? vb : va;
+      u32x4(&vn)[NPT] = (i & 1) ? va : vb;
       const raw_t &dsrc = i == 3 ? dnxt : dcur;   // v_(i+1) of this step, or v_0 of the next
       const int in = (i + 1) & 3;
       if (WN_EXP != 3) {
@@ -353,7 +333,7 @@ __global__ __launch_bounds__(NW * 64) void conv3x3_wino_kernel(ConvArgs p, const
 
   raw_t dA, dB;
   half8 w0[2], w1[2];
-  wn_u32x4 va[NPT], vb[NPT];
+  u32x4 va[NPT], vb[NPT];
   Adr cur = make_adr(0, 0, 0);
 #pragma unroll
   for (int j = 0; j < NPT; ++j)
@@ -372,8 +352,8 @@ __global__ __launch_bounds__(NW * 64) void conv3x3_wino_kernel(ConvArgs p, const
       WSTAMP(const unsigned long long tb = __builtin_amdgcn_s_memtime(); t_k0 += tb - ta;)
       dma_g = -1;
       if (g + 1 < G) {
-        if (ky == 1 && cc + 1 < nchunk) wn_wait_vm<HQ>();
-        else wn_wait_vm<0>();
+        if (ky == 1 && cc + 1 < nchunk) wait_vm_lgkm<HQ>();
+        else wait_vm_lgkm<0>();
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
         dma_g = g;

@@ -1,0 +1,126 @@
+// Device-side primitives shared by the gfx950 kernel files: LDS-DMA, counted waits, lane reductions, the token-tile load and the
+// bias start of the token GEMM accumulators.  Device only; include after common.h.  Everything is __forceinline__: a kernel
+// that uses a helper from here compiles to the instructions it had with a private copy.
+#pragma once
+#include "common.h"
+
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));   // 16-byte register value (plain vector loads / stores in IR)
+
+// ---- LDS-DMA: 16 bytes per lane, global memory -> LDS without passing through registers ----
+// Issued from inline asm.  Through __builtin_amdgcn_global_load_lds the compiler marks a "flat access that may touch LDS" as
+// pending until the next full drain, and while that mark is up EVERY wait it inserts for an LDS fragment read is
+// s_waitcnt lgkmcnt(0) (and every barrier drains vmcnt(0)) - no LDS read can stay in flight under the MFMAs.  Hidden in asm,
+// the DMA is outside its bookkeeping: fragment reads get counted lgkmcnt(n), and the DMA's completion is waited for by the
+// caller with a counted wait_vm<N>() / wait_vm_lgkm<N>() in front of the barrier that publishes the data (loads, stores and
+// LDS-DMA retire in issue order).  m0 = wave-uniform LDS byte address; lane i lands at + 16 i (the destination of an LDS-DMA is
+// always lane-linear: a swizzle goes on the source address).
+// The destination is an LDS BYTE address or an f16 * into LDS.  A kernel that issues many DMAs casts its LDS array to address
+// space 3 once and passes byte addresses: a generic -> LDS cast per call makes hipcc emit a null check against src_shared_base
+// per DMA.
+__device__ __forceinline__ unsigned lds_addr(const void *l) { return (unsigned)(size_t)(__attribute__((address_space(3))) void *)l; }
+
+// scalar base + 32-bit lane byte offset: no per-lane 64-bit address arithmetic in front of the DMA
+__device__ __forceinline__ void glds16(const f16 *sbase, unsigned voff_bytes, unsigned lds_byte) {
+  lds_byte = __builtin_amdgcn_readfirstlane(lds_byte);
+  asm volatile("s_mov_b32 m0, %2\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff_bytes), "s"(sbase), "s"(lds_byte) : "memory");
+}
+__device__ __forceinline__ void glds16(const f16 *sbase, unsigned voff_bytes, f16 *l) { glds16(sbase, voff_bytes, lds_addr(l)); }
+// one 64-bit source address per lane (gathers; out-of-image taps point at a zero page)
+__device__ __forceinline__ void glds16(const void *g, unsigned lds_byte) {
+  lds_byte = __builtin_amdgcn_readfirstlane(lds_byte);
+  asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "s"(lds_byte) : "memory");
+}
+__device__ __forceinline__ void glds16(const void *g, f16 *l) { glds16(g, lds_addr(l)); }
+
+// ---- counted waits: at most N vector-memory operations (loads, stores, LDS-DMA) of this wave still in flight ----
+// wait_vm_lgkm also drains the LDS / scalar-memory counter: the form in front of a raw s_barrier of a DMA ring.
+template <int N>
+__device__ __forceinline__ void wait_vm() {
+  static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit field");
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+template <int N>
+__device__ __forceinline__ void wait_vm_lgkm() {
+  static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit field");
+  asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
+}
+// the wave's own LDS operations have completed (same-wave LDS operations are in order); vector-memory operations stay in flight
+__device__ __forceinline__ void wait_lgkm() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+
+// ---- lane reductions ----
+// sum over the 16 lanes of a DPP row (lanes 16r .. 16r+15), result in every lane; fixed order.  quad_perm [1,0,3,2] and
+// [2,3,0,1] add within quads, row_half_mirror / row_mirror exchange quads whose four lanes already hold equal sums.
+__device__ __forceinline__ float row16_sum(float x) {
+  x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0xB1, 0xf, 0xf, false));
+  x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x4E, 0xf, 0xf, false));
+  x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x141, 0xf, 0xf, false));
+  x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x140, 0xf, 0xf, false));
+  return x;
+}
+
+// butterfly over the 64 lanes of a wave, partner distance 32, 16, .. 1; the result is in every lane.  The order is part of the
+// documented bit-exact results of the kernels that use it: do not change it.
+template <typename T, typename Op>
+__device__ __forceinline__ T wave_reduce(T v, Op op) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v = op(v, __shfl_xor(v, o, 64));
+  return v;
+}
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) { return wave_reduce(v, [](T a, T b) { return a + b; }); }
+__device__ __forceinline__ int wave_min(int v) { return wave_reduce(v, [](int a, int b) { return min(a, b); }); }
+__device__ __forceinline__ int wave_max(int v) { return wave_reduce(v, [](int a, int b) { return max(a, b); }); }
+__device__ __forceinline__ float wave_max(float v) { return wave_reduce(v, [](float a, float b) { return fmaxf(a, b); }); }
+__device__ __forceinline__ double wave_max(double v) { return wave_reduce(v, [](double a, double b) { return fmax(a, b); }); }
+
+// ---- token tile (tok_gemm.hip, tok_qkv.hip, head_mlp.hip) ----
+// ROWS rows x 512 fp16 of `src` (rows past M repeat the last one) -> LDS [k segment of 128][row][256 B], 16-byte chunk c of a
+// row segment stored at c ^ (row & 15): conflict-free ds_read_b128.  One DMA instruction = 4 rows of one segment (1 KB,
+// lane-linear destination; the swizzle is applied on the source address); ROWS / WAVES instructions per wave.
+// PIN_LANE: the lane offsets are recomputed per call - hoisted out of a loop over tiles they would live across the K loops.
+template <int ROWS, int WAVES, bool PIN_LANE = false>
+__device__ __forceinline__ void tok_tile_dma(const f16 *src, int m0, int M, int wave, int lane, unsigned lds0) {
+  constexpr int U = ROWS / 4 / WAVES;
+  if constexpr (PIN_LANE) asm volatile("" : "+v"(lane));
+#pragma unroll
+  for (int seg = 0; seg < 4; ++seg)
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int r4 = wave * U + u, row = r4 * 4 + (lane >> 4);
+      const int m = min(m0 + row, M - 1);
+      const unsigned voff = (unsigned)(((size_t)m * 512 + seg * 128 + (((lane & 15) ^ (row & 15)) * 8)) * 2);
+      glds16(src, voff, lds0 + seg * (ROWS * 256) + r4 * 1024);
+    }
+}
+
+// Accumulators of a token GEMM start at the bias.  col0 is the first of the wave's NI * 32 output columns; acc[i][j] is the 32x32 MFMA
+// tile of columns col0 + i*32 .. +31 and tokens j*32 .. +31; lr = lane & 31, lh = lane >> 5.
+// Row layout: a lane owns one token and channels col0 + i*32 + rg*8 + lh*4 + (0..3) in register quad rg.
+template <int NI, int NJ>
+__device__ __forceinline__ void acc_from_bias(floatx16 (&acc)[NI][NJ], const float *bias, int col0, int lh) {
+#pragma unroll
+  for (int i = 0; i < NI; ++i)
+#pragma unroll
+    for (int rg = 0; rg < 4; ++rg) {
+      const float4 bv = *reinterpret_cast<const float4 *>(bias + col0 + i * 32 + rg * 8 + lh * 4);
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        acc[i][j][rg * 4 + 0] = bv.x;
+        acc[i][j][rg * 4 + 1] = bv.y;
+        acc[i][j][rg * 4 + 2] = bv.z;
+        acc[i][j][rg * 4 + 3] = bv.w;
+      }
+    }
+}
+// Swapped operands (the transposed V image): a lane owns ONE channel col0 + i*32 + lr and 4 consecutive tokens per register quad.
+template <int NI, int NJ>
+__device__ __forceinline__ void acc_from_bias_vt(floatx16 (&acc)[NI][NJ], const float *bias, int col0, int lr) {
+#pragma unroll
+  for (int i = 0; i < NI; ++i) {
+    const float b = bias[col0 + i * 32 + lr];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[i][j][e] = b;
+  }
+}

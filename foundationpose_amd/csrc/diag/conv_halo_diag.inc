@@ -154,15 +154,9 @@ __device__ __forceinline__ void halo_tile(const ConvArgs &p, const int m0, const
       // group ky=0 are YOUNGER than the weights needed at ky=1, so a counted vmcnt leaves them in flight there
       // (a __syncthreads() would drain them one group after issue).
       if (ky == 1 && cc + 1 < nchunk) {
-        static_assert(HLOADS >= 2 && HLOADS <= 7, "add the vmcnt immediate for this tile");
-        if constexpr (HLOADS == 7) asm volatile("s_waitcnt vmcnt(7) lgkmcnt(0)" ::: "memory");
-        else if constexpr (HLOADS == 6) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");
-        else if constexpr (HLOADS == 5) asm volatile("s_waitcnt vmcnt(5) lgkmcnt(0)" ::: "memory");
-        else if constexpr (HLOADS == 4) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
-        else if constexpr (HLOADS == 3) asm volatile("s_waitcnt vmcnt(3) lgkmcnt(0)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
+        wait_vm_lgkm<HLOADS>();
       } else {
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        wait_vm_lgkm<0>();
       }
       __builtin_amdgcn_s_barrier();
       STAMP(unsigned long long tb = __builtin_amdgcn_s_memtime(); t_wait += tb - ta;)
@@ -475,19 +469,14 @@ __device__ __forceinline__ void halo_persist(const ConvArgs &p, const int n_wg, 
         // at ky = 1 the HQ band DMAs requested one group ago; at the first group of a tile the NST stores of the previous
         // tile's epilogue (issued after this group's weights and band were requested).
         if (ky == 1 && band_next) {
-          static_assert(HQ >= 2 && HQ <= 6, "add the vmcnt immediate for this tile");
-          if constexpr (HQ == 6) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");
-          else if constexpr (HQ == 5) asm volatile("s_waitcnt vmcnt(5) lgkmcnt(0)" ::: "memory");
-          else if constexpr (HQ == 4) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
-          else if constexpr (HQ == 3) asm volatile("s_waitcnt vmcnt(3) lgkmcnt(0)" ::: "memory");
-          else asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
+          wait_vm_lgkm<HQ>();
         } else if (ky == 0 && cc == 0 && prev_full) {
           // behind this group's band and weight requests the previous epilogue issued its residual loads (consumed, so
           // complete) and then NST stores: the stores may stay in flight
           static_assert(NST == 16, "the immediates below");
-          asm volatile("s_waitcnt vmcnt(16) lgkmcnt(0)" ::: "memory");
+          wait_vm_lgkm<16>();
         } else {
-          asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+          wait_vm_lgkm<0>();
         }
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
@@ -580,7 +569,7 @@ __device__ __forceinline__ void halo_persist(const ConvArgs &p, const int n_wg, 
           rv[j][u] = *reinterpret_cast<const u32x4 *>(p.res + (size_t)mr * p.Cout + c0 + wm * 64 + c16 * 8);
         }
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkm();
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
     {
@@ -594,7 +583,7 @@ __device__ __forceinline__ void halo_persist(const ConvArgs &p, const int n_wg, 
         if constexpr (RES) {
 #pragma unroll
           for (int u = 0; u < 4; ++u) *reinterpret_cast<u32x4 *>(&stage[(u * 8 + rpx) * PLD + c16 * 8]) = rv[j][u];
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+          wait_lgkm();
         }
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
@@ -615,7 +604,7 @@ __device__ __forceinline__ void halo_persist(const ConvArgs &p, const int n_wg, 
             *reinterpret_cast<half4 *>(sp) = hv;
           }
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkm();
         u32x4 ov[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) ov[u] = *reinterpret_cast<const u32x4 *>(&stage[(u * 8 + rpx) * PLD + c16 * 8]);
@@ -626,7 +615,7 @@ __device__ __forceinline__ void halo_persist(const ConvArgs &p, const int n_wg, 
           f16 *o = (f16 *)p.out + (hi ? (long long)(mc - p.split_m) : (long long)mc) * p.out_ld + (hi ? p.coff_hi : 0) + c0 + wm * 64 + c16 * 8;
           if (mr < p.M) *reinterpret_cast<u32x4 *>(o) = ov[u];
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the rows are in registers before the next tile's values overwrite them
+        wait_lgkm();   // the rows are in registers before the next tile's values overwrite them
       }
     }
     prev_full = m0 + TM <= p.M;

@@ -22,41 +22,13 @@
 // One workgroup per CU (132 KB of LDS); what the second workgroup per CU bought the unfused kernels - one's loads beside the other's
 // K loop - is bought here by having no loads behind the first 128 KB.
 #include "common.h"
+#include "device_util.h"
 #include <cstdlib>
 
 #define HM_THREADS 512
 #define HM_TILE 65536
 #define HM_RED_OFF (2 * HM_TILE)                 // [2][8 waves][64 tokens] floats
 #define HM_LDS_BYTES (2 * HM_TILE + 4096)
-
-typedef unsigned int hm_u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void hm_glds16(const f16 *sbase, unsigned voff_bytes, unsigned lds_addr) {
-  lds_addr = __builtin_amdgcn_readfirstlane(lds_addr);
-  asm volatile("s_mov_b32 m0, %2\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff_bytes), "s"(sbase), "s"(lds_addr) : "memory");
-}
-
-// sum over the 16 lanes of a DPP row, result in every lane; fixed order (as tok_gemm.hip)
-__device__ __forceinline__ float hm_row16_sum(float x) {
-  x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0xB1, 0xf, 0xf, false));
-  x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x4E, 0xf, 0xf, false));
-  x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x141, 0xf, 0xf, false));
-  x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x140, 0xf, 0xf, false));
-  return x;
-}
-
-// 64 rows x 512 fp16 of `src` (rows past M repeat the last one) -> LDS tile; 8 DMA instructions (1 KB each) per wave
-__device__ __forceinline__ void hm_tile_dma(const f16 *src, int m0, int M, int wave, int lane, unsigned lds0) {
-#pragma unroll
-  for (int seg = 0; seg < 4; ++seg)
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const int r4 = wave * 2 + u, row = r4 * 4 + (lane >> 4);
-      const int m = min(m0 + row, M - 1);
-      const unsigned voff = (unsigned)(((size_t)m * 512 + seg * 128 + (((lane & 15) ^ (row & 15)) * 8)) * 2);
-      hm_glds16(src, voff, lds0 + seg * 16384 + r4 * 1024);
-    }
-}
 
 struct HmCtx {
   int lane, wave, lr, lh;
@@ -65,23 +37,11 @@ struct HmCtx {
 
 // acc[i][j] (channels wave*64 + i*32 + ..., tokens j*32 + lr) = bias + tile (64 x 512, LDS) @ W^T
 __device__ __forceinline__ void hm_gemm(const HmCtx &c, const f16 *w, const float *bias, const unsigned char *tile, floatx16 (&acc)[2][2]) {
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int rg = 0; rg < 4; ++rg) {
-      const float4 bv = *reinterpret_cast<const float4 *>(bias + c.wave * 64 + i * 32 + rg * 8 + c.lh * 4);
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        acc[i][j][rg * 4 + 0] = bv.x;
-        acc[i][j][rg * 4 + 1] = bv.y;
-        acc[i][j][rg * 4 + 2] = bv.z;
-        acc[i][j][rg * 4 + 3] = bv.w;
-      }
-    }
+  acc_from_bias(acc, bias, c.wave * 64, c.lh);
   // packed [wave4][k16 32][i4 4][lane 64][8 halfs] (pack_tok_weights): this wave's fragments are (wave >> 1, k16, (wave & 1) * 2 + i)
-  const hm_u32x4 *wp = reinterpret_cast<const hm_u32x4 *>(w) + (size_t)(c.wave >> 1) * (32 * 4 * 64) + ((c.wave & 1) * 2) * 64 + c.lane;
+  const u32x4 *wp = reinterpret_cast<const u32x4 *>(w) + (size_t)(c.wave >> 1) * (32 * 4 * 64) + ((c.wave & 1) * 2) * 64 + c.lane;
   constexpr int D = 4;
-  hm_u32x4 wr[D][2];
+  u32x4 wr[D][2];
 #pragma unroll
   for (int d = 0; d < D; ++d)
 #pragma unroll
@@ -190,16 +150,16 @@ __global__ __launch_bounds__(HM_THREADS, 1) void head_mlp_kernel(HeadMlpArgs p) 
   float *red = reinterpret_cast<float *>(hm_smem + HM_RED_OFF);
   const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) void *)hm_smem;
 
-  hm_tile_dma(p.att, m0, p.M, c.wave, c.lane, lds0);             // 8 instructions: the attention output -> P
-  hm_tile_dma(p.tok, m0, p.M, c.wave, c.lane, lds0 + HM_TILE);   // 8 more: the residual tokens -> Q
-  asm volatile("s_waitcnt vmcnt(8)" ::: "memory");               // P has landed (this wave's part; the barrier covers the others')
+  tok_tile_dma<64, 8>(p.att, m0, p.M, c.wave, c.lane, lds0);             // 8 instructions: the attention output -> P
+  tok_tile_dma<64, 8>(p.tok, m0, p.M, c.wave, c.lane, lds0 + HM_TILE);   // 8 more: the residual tokens -> Q
+  wait_vm<8>();               // P has landed (this wave's part; the barrier covers the others')
   __syncthreads();
 
   floatx16 acc[2][2];
   float rstd[2];
   // ---- out-projection + residual + LayerNorm1 -> x1 (fp16) in place into Q ----
   hm_gemm(c, p.w_out, p.b_out, P, acc);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");               // Q has landed
+  wait_vm<0>();               // Q has landed
   __syncthreads();                                               // (and every wave is done with P)
   hm_residual_stats(c, Q, red, acc, rstd);
 #pragma unroll
@@ -245,7 +205,7 @@ __global__ __launch_bounds__(HM_THREADS, 1) void head_mlp_kernel(HeadMlpArgs p) 
       for (int rg = 0; rg < 4; ++rg) {
         float v[4];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = hm_row16_sum(acc[i][j][rg * 4 + e] * rstd[j]);
+        for (int e = 0; e < 4; ++e) v[e] = row16_sum(acc[i][j][rg * 4 + e] * rstd[j]);
         const int g = (m0 + j * 32 + (c.lr & 16)) >> 4;          // global 16-token group (16 divides 400: never two hypotheses)
         if ((c.lr & 15) == 0 && g * 16 < p.M)
           *reinterpret_cast<float4 *>(p.gsum + (size_t)g * 512 + c.wave * 64 + i * 32 + rg * 8 + c.lh * 4) = make_float4(v[0], v[1], v[2], v[3]);
@@ -296,19 +256,6 @@ extern "C" __attribute__((visibility("default"))) int fp_dbg_hm_stamps(unsigned 
 #define H2_RED_OFF H2_RING_OFF                    // reduction scratch [8 waves][128 tokens] x (sum, sum of squares) floats = 8 KB: in the idle ring
 #define H2_LDS_BYTES (H2_TILE + 2 * H2_SLOT)      // 160 KB
 
-__device__ __forceinline__ void h2_tile_dma(const f16 *src, int m0, int M, int wave, int lane, unsigned lds0) {
-  asm volatile("" : "+v"(lane));
-#pragma unroll
-  for (int seg = 0; seg < 4; ++seg)
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int r4 = wave * 4 + u, row = r4 * 4 + (lane >> 4);
-      const int m = min(m0 + row, M - 1);
-      const unsigned voff = (unsigned)(((size_t)m * 512 + seg * 128 + (((lane & 15) ^ (row & 15)) * 8)) * 2);
-      hm_glds16(src, voff, lds0 + seg * H2_SEG + r4 * 1024);
-    }
-}
-
 // 64-k segment s8 (0 .. 7) of 128 rows of `src` -> ring slot: [row][128 B], chunk c (0 .. 7) at c ^ (row & 7); 2 DMA instructions per wave
 __device__ __forceinline__ void h2_ring_dma(const f16 *src, int m0, int M, int s8, int wave, int lane, unsigned slot_addr) {
 #pragma unroll
@@ -316,7 +263,7 @@ __device__ __forceinline__ void h2_ring_dma(const f16 *src, int m0, int M, int s
     const int r8 = wave * 2 + u, row = r8 * 8 + (lane >> 3);
     const int m = min(m0 + row, M - 1);
     const unsigned voff = (unsigned)(((size_t)m * 512 + s8 * 64 + (((lane & 7) ^ (row & 7)) * 8)) * 2);
-    hm_glds16(src, voff, slot_addr + r8 * 1024);
+    glds16(src, voff, slot_addr + r8 * 1024);
   }
 }
 
@@ -331,9 +278,9 @@ template <bool RING, bool BIAS, typename Pre>
 __device__ __forceinline__ void h2_gemm(const H2Ctx &c, const f16 *w, const float *bias, const unsigned char *smem, floatx16 (&acc)[2][4], Pre before_loop,
                                         unsigned lds0 = 0, const f16 *ring_src = nullptr, int m0 = 0, int M = 0) {
   // packed [wave4][k16 32][i4 4][lane 64][8 halfs] (pack_tok_weights): this wave's fragments are (wave >> 1, k16, (wave & 1) * 2 + i)
-  const hm_u32x4 *wp = reinterpret_cast<const hm_u32x4 *>(w) + (size_t)(c.wave >> 1) * (32 * 4 * 64) + ((c.wave & 1) * 2) * 64 + c.lane;
+  const u32x4 *wp = reinterpret_cast<const u32x4 *>(w) + (size_t)(c.wave >> 1) * (32 * 4 * 64) + ((c.wave & 1) * 2) * 64 + c.lane;
   constexpr int D = 3;
-  hm_u32x4 wr[D][2];
+  u32x4 wr[D][2];
 #pragma unroll
   for (int d = 0; d < D; ++d)
 #pragma unroll
@@ -342,7 +289,7 @@ __device__ __forceinline__ void h2_gemm(const H2Ctx &c, const f16 *w, const floa
   if constexpr (RING) {
     // RING: A streams through the two ring slots; segment 0 was requested by the caller in front of this call (and in front of the 6 weight
     // loads above, which may stay in flight)
-    asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+    wait_vm<6>();
     __syncthreads();
     h2_ring_dma(ring_src, m0, M, 1, c.wave, c.lane, lds0 + H2_RING_OFF + H2_SLOT);
   }
@@ -394,7 +341,7 @@ __device__ __forceinline__ void h2_gemm(const H2Ctx &c, const f16 *w, const floa
     }
     if (seg_edge) {
       // segment kn >> 2 was requested at the top of the previous segment; since then this wave has issued 8 weight loads (2 per k-step)
-      asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
+      wait_vm_lgkm<8>();
       __syncthreads();                                          // landed everywhere, and everybody is done with the other slot
       if ((kn >> 2) + 1 < 8) h2_ring_dma(ring_src, m0, M, (kn >> 2) + 1, c.wave, c.lane, lds0 + H2_RING_OFF + (((kn >> 2) + 1) & 1) * H2_SLOT);
 #pragma unroll
@@ -464,7 +411,7 @@ __global__ __launch_bounds__(HM_THREADS, 1) void head_mlp128_kernel(HeadMlpArgs 
   const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) void *)h2_smem;
 
   HSTAMP(0);
-  h2_tile_dma(p.tok, m0, p.M, c.wave, c.lane, lds0);                                   // 16 instructions: the residual tokens -> Q
+  tok_tile_dma<H2_ROWS, 8, true>(p.tok, m0, p.M, c.wave, c.lane, lds0);                                   // 16 instructions: the residual tokens -> Q
   h2_ring_dma(p.att, m0, p.M, 0, c.wave, c.lane, lds0 + H2_RING_OFF);                  // 2: segment 0 of the attention output -> slot 0
   floatx16 acc[2][4];
   float mean[4], rstd[4];

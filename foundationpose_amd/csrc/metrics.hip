@@ -10,6 +10,7 @@
 // pred_b = gt_b gives exactly 0.  No float atomics: each (b, tile) writes its double partial sums to a slab, which pose_errors_finish
 // adds in tile order and divides by N, so a pose's result is bit-identical whatever batch it is in and at whatever index.
 #include "common.h"
+#include "device_util.h"
 
 namespace {
 
@@ -64,7 +65,8 @@ __device__ __forceinline__ void xform(const float *M, float x, float y, float z,
 __device__ __forceinline__ float norm3(float x, float y, float z) { return sqrtf(fmaf(x, x, fmaf(y, y, z * z))); }
 
 // sum over the workgroup in a fixed order (butterfly within each wave, then the waves in order); the total is valid in thread 0.
-// `red` holds PM_THREADS / 64 doubles; the caller synchronises before `red` is reused.
+// `red` holds PM_THREADS / 64 doubles; the caller synchronises before `red` is reused.  The butterfly is device_util.h's wave_sum written
+// out: through the call hipcc orders the instructions of pose_errors_kernel differently.
 __device__ __forceinline__ double block_sum(double v, double *red) {
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -230,8 +232,7 @@ struct BopErrArgs {
 
 // maximum over the workgroup, valid in every thread; `red` holds PM_THREADS / 64 floats
 __device__ __forceinline__ float block_max(float v, float *red) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  v = wave_max(v);
   __syncthreads();                        // the previous maximum has been read
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();

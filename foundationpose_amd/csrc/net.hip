@@ -2,6 +2,7 @@
 // RefineNet (learning/models/refine_network.py:73-93) and ScoreNetMultiPair
 // (learning/models/score_network.py:60-90) as sequences of the gfx950 kernels in conv.hip / attn.hip.
 #include "common.h"
+#include "device_util.h"
 
 #include <algorithm>
 #include <cmath>
@@ -421,7 +422,6 @@ __global__ __launch_bounds__(256) void broadcast_side_b_kernel(const f16 *__rest
   const int n = (int)(i / (1600 * 16)), r = (int)(i - (long long)n * (1600 * 16)), px = r >> 4, c8 = r & 15;
   int g = 0;
   while (g + 1 < sb.n_groups && h0 + n >= sb.start[g + 1]) ++g;
-  typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
   *reinterpret_cast<u32x4 *>(ab0 + ((size_t)n * 1600 + px) * 256 + 128 + c8 * 8) =
       *reinterpret_cast<const u32x4 *>(feat + ((size_t)g * 1600 + px) * 128 + c8 * 8);
 }

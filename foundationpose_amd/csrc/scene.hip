@@ -12,6 +12,7 @@
 // shuffles, add into the workgroup's LDS row with LDS atomics, and the workgroup issues one global integer atomic (add / min / max) per
 // field that it changed.  Integer sums, minima and maxima do not depend on their order: the results are deterministic.
 #include "common.h"
+#include "device_util.h"
 #include <algorithm>
 #include <climits>
 
@@ -40,22 +41,6 @@ __device__ __forceinline__ double scene_dist(double d, double u_cx, double v_cy,
 #pragma clang fp contract(off)
   const double X = (u_cx * d) * inv_fx, Y = (v_cy * d) * inv_fy;
   return sqrt((X * X + Y * Y) + d * d);
-}
-
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ int wave_min(int v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ int wave_max(int v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-  return v;
 }
 
 __device__ __forceinline__ bool is_min_col(int c) { return c == FP_SCENE_INFO_BBOX_OBJ || c == FP_SCENE_INFO_BBOX_OBJ + 1 ||

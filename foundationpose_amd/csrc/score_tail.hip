@@ -14,18 +14,8 @@
 // Until round 4 this was seven launches (token mean, out-projection, q/k/v projection, attention with one workgroup per query,
 // out-projection, Linear, argmax): 0.18 - 0.3 ms replicated on every rank of a multi-GPU job.
 #include "common.h"
+#include "device_util.h"
 #include "pose_math.h"
-
-__device__ __forceinline__ double st_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ double st_wave_max(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-  return v;
-}
 
 // ---- feature: token mean (fp32 sums of fp16 values, eight waves x 50 tokens, fixed order) + out-projection (float64 sums) ----
 // out: rows of `ld` floats; with `poses` the row is the all-gather record [feature 512 | pose 16] (dist.py) and the pose rides along
@@ -102,7 +92,7 @@ __global__ __launch_bounds__(256) void cross_qk_kernel(const float *__restrict__
       double s = 0.0;
 #pragma unroll
       for (int k = 0; k < 8; ++k) s += u[h * 512 + k * 64 + lane] * xs[r][k * 64 + lane];
-      s = st_wave_sum(s);
+      s = wave_sum(s);
       if (lane == 0) sv[(size_t)(m0 + r) * 4 + h] = s + c[h];
     }
     return;
@@ -202,9 +192,9 @@ __global__ __launch_bounds__(256) void cross_logit_kernel(const float *__restric
   }
 #pragma unroll
   for (int q = 0; q < CL_QB; ++q) {
-    const double m = st_wave_max(mx[q]);
+    const double m = wave_max(mx[q]);
     const double r = exp(mx[q] - m);              // (a lane without keys: exp(-1e300 - m) = 0)
-    const double zt = st_wave_sum(z[q] * r), wt = st_wave_sum(wsum[q] * r);
+    const double zt = wave_sum(z[q] * r), wt = wave_sum(wsum[q] * r);
     if (lane == 0) head_out[hd][q] = wt / zt;
   }
   __syncthreads();

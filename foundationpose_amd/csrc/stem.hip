@@ -14,6 +14,7 @@
 // Epilogue: accumulators start at the folded BN bias, ReLU, fp16, staged per wave, 16-byte NHWC stores (2 KB per output row
 // of a block).  The accumulation order of an output element (taps in order, 8 channels per tap) does not depend on the block.
 #include "common.h"
+#include "device_util.h"
 
 #define ST_THREADS 512
 #define ST_BLK 16                         // output block edge
@@ -27,11 +28,6 @@
 #define ST_LDS_BYTES (ST_W_BYTES + 4 * ST_REGION_ALLOC)       // 149504: weights + two sets of two regions (the next pair of blocks lands
                                                               // while this one is multiplied); the output staging re-uses the current set
 
-__device__ __forceinline__ void st_glds16(const f16 *g, unsigned lds_addr) {
-  lds_addr = __builtin_amdgcn_readfirstlane(lds_addr);
-  asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "s"(lds_addr) : "memory");
-}
-
 __global__ __launch_bounds__(ST_THREADS, 1) void stem7x7_kernel(ConvArgs p, const f16 *__restrict__ zero_page, int n_pairs, int blocks_x,
                                                                 int blocks_per_img, int n_blocks) {
   extern __shared__ __attribute__((aligned(16))) unsigned char st_smem[];
@@ -44,7 +40,7 @@ __global__ __launch_bounds__(ST_THREADS, 1) void stem7x7_kernel(ConvArgs p, cons
   // ---- weights -> LDS in fragment order: fragment f = i*25 + s, lane (lr, lh) = W[i*32 + lr][(2s + lh)*8 .. +8] ----
   for (int f = wave; f < 50; f += 8) {
     const int i = f / 25, s = f - i * 25;
-    st_glds16(p.w + (size_t)(i * 32 + lr) * p.Kpad + (2 * s + lh) * 8, lds0 + f * 1024);
+    glds16(p.w + (size_t)(i * 32 + lr) * p.Kpad + (2 * s + lh) * 8, lds0 + f * 1024);
   }
   float4 bias[2][4];
 #pragma unroll
@@ -75,7 +71,7 @@ __global__ __launch_bounds__(ST_THREADS, 1) void stem7x7_kernel(ConvArgs p, cons
       const int slot = u * 64 + lane, r = slot / ST_ROW_SLOTS, q = slot - r * ST_ROW_SLOTS;
       const int iy = 2 * oy0 - 3 + r, ix = 2 * ox0 - 3 + 2 * (q % 20) + q / 20;
       const bool ok = r < ST_REG && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
-      st_glds16(ok ? src_img + ((size_t)iy * p.W + ix) * 8 : zero_page, lds0 + ST_W_BYTES + (set * 2 + half) * ST_REGION_ALLOC + u * 1024);
+      glds16(ok ? src_img + ((size_t)iy * p.W + ix) * 8 : zero_page, lds0 + ST_W_BYTES + (set * 2 + half) * ST_REGION_ALLOC + u * 1024);
     }
   };
   static_assert(ST_REGION_INSTR % 4 == 0, "six region DMAs per wave");
@@ -94,10 +90,10 @@ __global__ __launch_bounds__(ST_THREADS, 1) void stem7x7_kernel(ConvArgs p, cons
     // wave's DMAs of THIS pair are older than its 8 output stores of the previous iteration and the 6 DMAs just issued.
     if (more) {
       load_region(pair + gridDim.x, set ^ 1);
-      if (it == 0) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");      // no stores yet: only the 6 new DMAs may be in flight
-      else asm volatile("s_waitcnt vmcnt(14) lgkmcnt(0)" ::: "memory");
+      if (it == 0) wait_vm_lgkm<6>();      // no stores yet: only the 6 new DMAs may be in flight
+      else wait_vm_lgkm<14>();
     } else {
-      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+      wait_vm_lgkm<0>();
     }
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
@@ -128,7 +124,7 @@ __global__ __launch_bounds__(ST_THREADS, 1) void stem7x7_kernel(ConvArgs p, cons
 #pragma unroll
         for (int i = 0; i < 2; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[i], bf[j], acc[i][j], 0, 0, 0);
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkm();
     __builtin_amdgcn_s_barrier();                            // every wave is done with this set's regions: staging may overwrite them
     __builtin_amdgcn_sched_barrier(0);
 
@@ -146,7 +142,7 @@ __global__ __launch_bounds__(ST_THREADS, 1) void stem7x7_kernel(ConvArgs p, cons
           for (int e = 0; e < 4; ++e) hv[e] = (f16)fmaxf(acc[i][j][rg * 4 + e], lo);
           *reinterpret_cast<half4 *>(&stage[lr * ST_STAGE_LD + i * 32 + rg * 8 + lh * 4]) = hv;
         }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // the wave's own staging writes have landed (same-wave LDS ops are in order)
+      wait_lgkm();     // the wave's own staging writes have landed (same-wave LDS ops are in order)
       uint4 v[4];
 #pragma unroll
       for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const uint4 *>(&stage[(u * 8 + (lane >> 3)) * ST_STAGE_LD + (lane & 7) * 8]);
@@ -159,7 +155,7 @@ __global__ __launch_bounds__(ST_THREADS, 1) void stem7x7_kernel(ConvArgs p, cons
         f16 *dst = (f16 *)p.out + (((size_t)img * p.Ho + oy) * p.Wo + ox) * 64 + c16 * 8;
         if (store) *reinterpret_cast<uint4 *>(dst) = v[u];
       }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // staging read back before the next tile overwrites it
+      wait_lgkm();     // staging read back before the next tile overwrites it
     }
     __builtin_amdgcn_s_barrier();                            // every wave has read its staging back: the next iteration's DMAs may overwrite this set
   }

@@ -31,6 +31,7 @@
 // The residual stream and the LayerNorm inputs stay fp32 (the reference's autocast keeps them fp32 as well: `x + pe`
 // promotes, layer_norm runs in fp32); only GEMM operands are fp16.
 #include "common.h"
+#include "device_util.h"
 
 #define TG_ROWS 64
 #define TG_K 512
@@ -43,8 +44,6 @@
 
 enum { EPI_ROWS = TG_EPI_ROWS, EPI_VT = TG_EPI_VT, EPI_LN = TG_EPI_LN, EPI_LNSUM = TG_EPI_LNSUM };
 
-typedef unsigned int tg_u32x4 __attribute__((ext_vector_type(4)));
-
 #ifdef HALO_STAMP
 // diagnostic build only (make -B EXTRA=-DHALO_STAMP): s_memtime per wave at entry / tile resident / K loop done / exit
 __device__ unsigned long long g_tok_stamps[2048 * 4 * 4];
@@ -55,36 +54,6 @@ extern "C" __attribute__((visibility("default"))) int fp_dbg_tok_stamps(unsigned
 #else
 #define TSTAMP(i) do { } while (0)
 #endif
-
-__device__ __forceinline__ void tg_glds16(const f16 *sbase, unsigned voff_bytes, unsigned lds_addr) {
-  lds_addr = __builtin_amdgcn_readfirstlane(lds_addr);
-  asm volatile("s_mov_b32 m0, %2\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff_bytes), "s"(sbase), "s"(lds_addr) : "memory");
-}
-
-// sum over the 16 lanes of a DPP row (lanes 16r .. 16r+15), result in every lane; fixed order.  quad_perm [1,0,3,2] and
-// [2,3,0,1] add within quads, row_half_mirror / row_mirror exchange quads whose four lanes already hold equal sums.
-__device__ __forceinline__ float tg_row16_sum(float x) {
-  x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0xB1, 0xf, 0xf, false));
-  x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x4E, 0xf, 0xf, false));
-  x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x141, 0xf, 0xf, false));
-  x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x140, 0xf, 0xf, false));
-  return x;
-}
-
-// 64 rows x 512 fp16 of `src` (rows past M repeat the last one) -> LDS [k segment of 128][row][256 B], 16-byte chunk c of
-// a row segment stored at c ^ (row & 15).  One DMA instruction = 4 rows of one segment (1 KB, lane-linear destination; the
-// swizzle is applied on the source address).  16 instructions per wave.
-__device__ __forceinline__ void tg_tile_dma(const f16 *src, int m0, int M, int wave, int lane, unsigned lds0) {
-#pragma unroll
-  for (int seg = 0; seg < 4; ++seg)
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int r4 = wave * 4 + u, row = r4 * 4 + (lane >> 4);
-      const int m = min(m0 + row, M - 1);
-      const unsigned voff = (unsigned)(((size_t)m * TG_K + seg * 128 + (((lane & 15) ^ (row & 15)) * 8)) * 2);
-      tg_glds16(src, voff, lds0 + seg * TG_SEG_BYTES + r4 * 1024);
-    }
-}
 
 template <int EPI>
 __global__ __launch_bounds__(TG_THREADS, 2) void tok_gemm_kernel(TokGemmArgs p) {
@@ -97,10 +66,11 @@ __global__ __launch_bounds__(TG_THREADS, 2) void tok_gemm_kernel(TokGemmArgs p) 
   const int lr = lane & 31, lh = lane >> 5;
   const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) void *)tg_smem;
   TSTAMP(0);
-  tg_tile_dma(p.in, m0, p.M, wave, lane, lds0);
+  tok_tile_dma<TG_ROWS, 4>(p.in, m0, p.M, wave, lane, lds0);
 
-  // ---- weight fragments: packed [wave][k16][i][lane][8 halfs]; accumulators start at the bias ----
-  const tg_u32x4 *wp = reinterpret_cast<const tg_u32x4 *>(blk.w) + (size_t)wave * (32 * 4 * 64) + lane;
+  // ---- weight fragments: packed [wave][k16][i][lane][8 halfs]; accumulators start at the bias (device_util.h's acc_from_bias /
+  // acc_from_bias_vt written out: through the calls hipcc allocates this kernel's registers differently) ----
+  const u32x4 *wp = reinterpret_cast<const u32x4 *>(blk.w) + (size_t)wave * (32 * 4 * 64) + lane;
   floatx16 acc[4][2];
   if constexpr (EPI == EPI_VT) {          // swapped operands: a lane owns ONE channel (i*32 + lr) of the wave's 128
 #pragma unroll
@@ -128,7 +98,7 @@ __global__ __launch_bounds__(TG_THREADS, 2) void tok_gemm_kernel(TokGemmArgs p) 
   }
   constexpr int TG_D = (EPI == EPI_LN || EPI == EPI_LNSUM) ? 3 : 4;   // weight prefetch distance in k-steps of 16 (3 where the
                                                                         // LayerNorm epilogue needs the registers: no spills)
-  tg_u32x4 wr[TG_D][4];
+  u32x4 wr[TG_D][4];
 #pragma unroll
   for (int d = 0; d < TG_D; ++d)
 #pragma unroll
@@ -140,7 +110,7 @@ __global__ __launch_bounds__(TG_THREADS, 2) void tok_gemm_kernel(TokGemmArgs p) 
 #pragma unroll
   for (int s = 0; s < 8; ++s) xo[s] = (unsigned)(((2 * s + lh) ^ (lr & 15)) * 16);
 
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // tile (and the first weight fragments) landed
+  wait_vm<0>();      // tile (and the first weight fragments) landed
   __syncthreads();
   TSTAMP(1);
 
@@ -219,8 +189,8 @@ __global__ __launch_bounds__(TG_THREADS, 2) void tok_gemm_kernel(TokGemmArgs p) 
   if constexpr (EPI == EPI_LN || EPI == EPI_LNSUM) {
     // residual tile -> the (now free) tile region by LDS-DMA, then added in fp32 in the accumulator layout: global column
     // wave*128 + i*32 + rg*8 + lh*4 is chunk i*4 + rg of k segment `wave`, 8-byte half lh
-    tg_tile_dma(p.res, m0, p.M, wave, lane, lds0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    tok_tile_dma<TG_ROWS, 4>(p.res, m0, p.M, wave, lane, lds0);
+    wait_vm<0>();
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -288,7 +258,7 @@ __global__ __launch_bounds__(TG_THREADS, 2) void tok_gemm_kernel(TokGemmArgs p) 
           for (int rg = 0; rg < 4; ++rg) {
             float v[4];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = tg_row16_sum(acc[i][j][rg * 4 + e] * rstd[j]);
+            for (int e = 0; e < 4; ++e) v[e] = row16_sum(acc[i][j][rg * 4 + e] * rstd[j]);
             const int g = (m0 + j * 32 + (lr & 16)) >> 4;          // global 16-token group
             if ((lr & 15) == 0 && g * 16 < p.M)
               *reinterpret_cast<float4 *>(p.gsum + (size_t)g * 512 + wave * 128 + i * 32 + rg * 8 + lh * 4) = make_float4(v[0], v[1], v[2], v[3]);

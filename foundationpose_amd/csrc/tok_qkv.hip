@@ -20,6 +20,7 @@
 // Arithmetic per output element is that of tok_gemm.hip (bias first, k ascending in steps of 16, one rounding to fp16): bit-identical
 // (tests/test_gpu_kernels.py::test_token_qkv_equals_the_64_token_kernel).
 #include "common.h"
+#include "device_util.h"
 
 #define TQ_ROWS 128
 #define TQ_THREADS 512
@@ -28,59 +29,16 @@
 #define TQ_STAGE_BYTES 4096                       // per wave: 32 tokens x 64 columns (rows) / 64 channels x 32 tokens (V image)
 #define TQ_LDS_BYTES (TQ_TILE_BYTES + 8 * TQ_STAGE_BYTES)      // 160 KB
 
-typedef unsigned int tq_u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void tq_glds16(const f16 *sbase, unsigned voff_bytes, unsigned lds_addr) {
-  lds_addr = __builtin_amdgcn_readfirstlane(lds_addr);
-  asm volatile("s_mov_b32 m0, %2\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff_bytes), "s"(sbase), "s"(lds_addr) : "memory");
-}
-
-// 128 rows x 512 fp16 of `src` (rows past M repeat the last one) -> LDS [k segment of 128][row][256 B], chunk c of a row segment at
-// c ^ (row & 15).  One DMA instruction = 4 rows of one segment (1 KB, lane-linear destination; the swizzle is applied on the source
-// address).  16 instructions per wave.
-__device__ __forceinline__ void tq_tile_dma(const f16 *src, int m0, int M, int wave, int lane, unsigned lds0) {
-  asm volatile("" : "+v"(lane));          // the 16 lane offsets are recomputed per tile: hoisted out of the unit loop they would live across the K loops
-#pragma unroll
-  for (int seg = 0; seg < 4; ++seg)
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int r4 = wave * 4 + u, row = r4 * 4 + (lane >> 4);
-      const int m = min(m0 + row, M - 1);
-      const unsigned voff = (unsigned)(((size_t)m * 512 + seg * 128 + (((lane & 15) ^ (row & 15)) * 8)) * 2);
-      tq_glds16(src, voff, lds0 + seg * TQ_SEG_BYTES + r4 * 1024);
-    }
-}
-
 // acc[i][j] = bias + tile (tokens j*32 .. +31) x W^T (columns wave*64 + i*32 .. +31).  VT: operands swapped (a lane owns a channel).
 template <bool VT>
 __device__ __forceinline__ void tq_kloop(const TokGemmBlock &blk, const unsigned char *tile, int wave, int lane, floatx16 (&acc)[2][4]) {
   const int lr = lane & 31, lh = lane >> 5;
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    if constexpr (VT) {
-      const float b = blk.bias[wave * 64 + i * 32 + lr];
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[i][j][e] = b;
-    } else {
-#pragma unroll
-      for (int rg = 0; rg < 4; ++rg) {
-        const float4 bv = *reinterpret_cast<const float4 *>(blk.bias + wave * 64 + i * 32 + rg * 8 + lh * 4);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          acc[i][j][rg * 4 + 0] = bv.x;
-          acc[i][j][rg * 4 + 1] = bv.y;
-          acc[i][j][rg * 4 + 2] = bv.z;
-          acc[i][j][rg * 4 + 3] = bv.w;
-        }
-      }
-    }
-  }
+  if constexpr (VT) acc_from_bias_vt(acc, blk.bias, wave * 64, lr);
+  else acc_from_bias(acc, blk.bias, wave * 64, lh);
   // packed [wave4][k16 32][i4 4][lane 64][8 halfs] (pack_tok_weights): this wave's fragments are (wave >> 1, k16, (wave & 1) * 2 + i)
-  const tq_u32x4 *wp = reinterpret_cast<const tq_u32x4 *>(blk.w) + (size_t)(wave >> 1) * (32 * 4 * 64) + ((wave & 1) * 2) * 64 + lane;
+  const u32x4 *wp = reinterpret_cast<const u32x4 *>(blk.w) + (size_t)(wave >> 1) * (32 * 4 * 64) + ((wave & 1) * 2) * 64 + lane;
   constexpr int D = 3;                    // weight prefetch distance in k-steps (4 spills)
-  tq_u32x4 wr[D][2];
+  u32x4 wr[D][2];
 #pragma unroll
   for (int d = 0; d < D; ++d)
 #pragma unroll
@@ -135,8 +93,8 @@ __global__ __launch_bounds__(TQ_THREADS, 1) void tok_qkv_kernel(TokGemmArgs p, i
     const int m0 = tile * TQ_ROWS;
     if (tile != cur_tile) {
       __syncthreads();                                     // every wave is done with the previous tile
-      tq_tile_dma(p.in, m0, p.M, wave, lane, lds0);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      tok_tile_dma<TQ_ROWS, 8, true>(p.in, m0, p.M, wave, lane, lds0);
+      wait_vm<0>();
       __syncthreads();
       cur_tile = tile;
     }
@@ -228,9 +186,9 @@ __global__ __launch_bounds__(512, 2) void tok_qkv_small_kernel(TokGemmArgs p) {
   const TokGemmBlock &blk = p.blk[b];
   const int m0 = tl * 32;
   // weights: fragment (g, k16, i) of the packed image is 64 lanes x 16 bytes
-  tq_u32x4 wf[8][2];
+  u32x4 wf[8][2];
   {
-    const tq_u32x4 *wp = reinterpret_cast<const tq_u32x4 *>(blk.w) + ((size_t)g * 32 + kq * 8) * 4 * 64 + (chh * 2) * 64 + lane;
+    const u32x4 *wp = reinterpret_cast<const u32x4 *>(blk.w) + ((size_t)g * 32 + kq * 8) * 4 * 64 + (chh * 2) * 64 + lane;
 #pragma unroll
     for (int k = 0; k < 8; ++k)
 #pragma unroll
@@ -238,19 +196,19 @@ __global__ __launch_bounds__(512, 2) void tok_qkv_small_kernel(TokGemmArgs p) {
   }
   // the token tile: rows m0 .. m0 + 31 (rows past M repeat the last one), 2048 pieces of 16 bytes
   {
-    tq_u32x4 v[4];
+    u32x4 v[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int i = tid + u * 512, row = i >> 6, c8 = i & 63;
-      v[u] = *reinterpret_cast<const tq_u32x4 *>(p.in + (size_t)min(m0 + row, p.M - 1) * 512 + c8 * 8);
+      v[u] = *reinterpret_cast<const u32x4 *>(p.in + (size_t)min(m0 + row, p.M - 1) * 512 + c8 * 8);
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int i = tid + u * 512, row = i >> 6, c8 = i & 63;
-      *reinterpret_cast<tq_u32x4 *>(tile + row * TS_PITCH + c8 * 8) = v[u];
+      *reinterpret_cast<u32x4 *>(tile + row * TS_PITCH + c8 * 8) = v[u];
     }
   }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");           // (not a __syncthreads(): the weight loads stay in flight)
+  wait_lgkm();           // (not a __syncthreads(): the weight loads stay in flight)
   __builtin_amdgcn_s_barrier();
   __builtin_amdgcn_sched_barrier(0);
   floatx16 acc[2];
