@@ -369,6 +369,124 @@ def mesh_diameter(model_pts=None, mesh=None, mesh_tensors=None, return_pair=Fals
   return d
 
 
+def simplify_mesh_arrays(pos, faces, cell, normals=None, colors=None, return_map=False):
+  """fp_mesh_simplify_count + fp_mesh_simplify_write on arrays: pos (V,3), faces (F,3) or None (a point cloud), normals (V,3) or None,
+  colors (V,3) uint8 or None; numpy or torch, taken to the device as float32 / int32 / uint8.  Returns the device tensors (pos, normals |
+  None, colors | None, faces, vertex_map | None).  The count is read back, so this call synchronises."""
+  dev = _device_of(pos)
+  ctx = _lib.Context.get(dev)
+  pos = torch.as_tensor(pos).to(device=dev, dtype=torch.float).reshape(-1, 3).contiguous()
+  V = len(pos)
+  faces = torch.zeros((0, 3), dtype=torch.int32, device=dev) if faces is None else \
+      torch.as_tensor(faces).to(device=dev, dtype=torch.int32).reshape(-1, 3).contiguous()
+  F = len(faces)
+  if normals is not None:
+    normals = torch.as_tensor(normals).to(device=dev, dtype=torch.float).reshape(-1, 3).contiguous()
+  if colors is not None:
+    colors = torch.as_tensor(colors).to(device=dev)
+    if colors.dtype != torch.uint8 or colors.dim() != 2 or colors.shape[1] != 3:
+      raise ValueError(f'colors must be (V,3) uint8, got {colors.dtype} {tuple(colors.shape)}')
+    colors = colors.contiguous()
+  for name, a in (('normals', normals), ('colors', colors)):
+    if a is not None and len(a) != V:
+      raise ValueError(f'{len(a)} {name} for {V} vertices')
+  nv, nf = _simplify_count(ctx, dev, pos, faces, cell)
+  o_pos = torch.empty((nv, 3), dtype=torch.float, device=dev)
+  o_nrm = None if normals is None else torch.empty((nv, 3), dtype=torch.float, device=dev)
+  o_col = None if colors is None else torch.empty((nv, 3), dtype=torch.uint8, device=dev)
+  o_faces = torch.empty((nf, 3), dtype=torch.int32, device=dev)
+  vmap = torch.empty((V,), dtype=torch.int32, device=dev) if return_map else None
+  check(lib().fp_mesh_simplify_write(ctx.handle, ptr(pos) if V else None, ptr(normals), ptr(colors), V, ptr(faces) if F else None, F, float(cell),
+                                     ptr(o_pos) if nv else None, ptr(o_nrm) if nv else None, ptr(o_col) if nv else None,
+                                     ptr(o_faces) if nf else None, ptr(vmap) if V and return_map else None, nv, nf, stream_ptr(dev)))
+  return o_pos, o_nrm, o_col, o_faces, vmap
+
+
+def _simplify_count(ctx, dev, pos, faces, cell):
+  counts = (ctypes.c_int64 * 2)()
+  check(lib().fp_mesh_simplify_count(ctx.handle, ptr(pos) if len(pos) else None, len(pos), ptr(faces) if len(faces) else None, len(faces),
+                                     float(cell), counts, stream_ptr(dev)))
+  return int(counts[0]), int(counts[1])
+
+
+SIMPLIFY_SEARCH_STEPS = 20
+
+
+def simplify_mesh(mesh, cell=None, max_vertices=None, return_map=False):
+  """Vertex-clustering simplification on the device (fp_mesh_simplify_*; the rule is stated in include/foundationpose_amd.h): one vertex
+  per occupied cell of a grid of pitch `cell`, degenerate and repeated faces dropped.  Deterministic, bit for bit.
+
+  mesh: anything with `vertices`, `faces` and optionally `vertex_normals` and `visual.vertex_colors` (trimesh.Trimesh, synthetic.SimpleMesh),
+  or a tuple (vertices, faces[, normals[, colors]]) of numpy arrays or device tensors; faces None or empty: a point cloud.  Exactly one of
+  `cell` (metres) and `max_vertices` is given.  max_vertices runs a fixed bisection on the cell: lo = 0, hi = the largest extent of
+  the bounding box (float64); 20 times mid = (lo + hi) / 2, and hi = mid when the count at float32(mid) is at most max_vertices, else
+  lo = mid; the result is the mesh at float32(hi).  A mesh that already has at most max_vertices vertices comes back as a copy, cell 0.
+  The rasteriser's fast forms take up to 8192 vertices and 65 535 faces: max_vertices=8192 puts a fused or scanned mesh onto them.
+
+  Returns (synthetic.SimpleMesh, info) - info: cell, vertices_in, faces_in, vertices, faces, evaluations (count calls) - and, with
+  return_map=True, the (V,) int32 map from input vertex to output vertex (-1: dropped).  A UV-textured mesh is refused (ValueError):
+  texture coordinates are not transferred.  The alpha of RGBA colours is set to 255."""
+  from .synthetic import SimpleMesh
+  if (cell is None) == (max_vertices is None):
+    raise ValueError('simplify_mesh: give exactly one of cell and max_vertices')
+  if isinstance(mesh, (tuple, list)):
+    parts = list(mesh) + [None] * (4 - len(mesh))
+    verts, faces, normals, colors = parts[:4]
+  else:
+    visual = getattr(mesh, 'visual', None)
+    colors = getattr(visual, 'vertex_colors', None)
+    if colors is None and getattr(visual, 'uv', None) is not None:
+      raise ValueError('simplify_mesh: the mesh is UV-textured; texture coordinates are not transferred - bake vertex colours first')
+    verts, faces = mesh.vertices, mesh.faces
+    normals = getattr(mesh, 'vertex_normals', None)
+  dev = _device_of(verts)
+  normals_in = normals
+  pos = torch.as_tensor(verts).to(device=dev, dtype=torch.float).reshape(-1, 3).contiguous()
+  faces = torch.zeros((0, 3), dtype=torch.int32, device=dev) if faces is None else \
+      torch.as_tensor(faces).to(device=dev, dtype=torch.int32).reshape(-1, 3).contiguous()
+  if normals is not None:
+    normals = torch.as_tensor(normals).to(device=dev, dtype=torch.float).reshape(-1, 3).contiguous()
+  if colors is not None:
+    colors = torch.as_tensor(colors).to(device=dev)
+    if colors.dtype != torch.uint8:
+      raise ValueError(f'simplify_mesh: vertex colours must be uint8, got {colors.dtype}')
+    colors = colors.reshape(len(colors), -1)[:, :3].contiguous()
+  V, F = len(pos), len(faces)
+  info = dict(cell=0.0, vertices_in=V, faces_in=F, vertices=V, faces=F, evaluations=0)
+
+  def as_mesh(p, n, c, f):
+    rgba = None if c is None else np.concatenate([c.cpu().numpy(), np.full((len(c), 1), 255, dtype=np.uint8)], 1)
+    return SimpleMesh(p.cpu().numpy(), f.cpu().numpy(), vertex_normals=None if n is None else n.cpu().numpy(), vertex_colors=rgba)
+
+  if max_vertices is not None:
+    max_vertices = int(max_vertices)
+    if max_vertices < 8:
+      raise ValueError(f'simplify_mesh: max_vertices {max_vertices} (at least 8: a cell of the whole extent still leaves up to 8 clusters)')
+    if V <= max_vertices:      # the arrays as they came, copied to the host: no rounding to float32
+      host = lambda x: None if x is None else np.array(x.detach().cpu().numpy() if torch.is_tensor(x) else x)
+      rgba = None if colors is None else np.concatenate([colors.cpu().numpy(), np.full((V, 1), 255, dtype=np.uint8)], 1)
+      f_in = mesh[1] if isinstance(mesh, (tuple, list)) else mesh.faces
+      out = SimpleMesh(host(verts), np.zeros((0, 3), dtype=np.int64) if f_in is None else host(f_in), vertex_normals=host(normals_in), vertex_colors=rgba)
+      vmap = np.arange(V, dtype=np.int32)
+      return (out, info, vmap) if return_map else (out, info)
+    ctx = _lib.Context.get(dev)
+    lo, hi = 0.0, float((pos.max(0).values.double() - pos.min(0).values.double()).max().item())
+    for _ in range(SIMPLIFY_SEARCH_STEPS):
+      mid = (lo + hi) / 2
+      nv, _ = _simplify_count(ctx, dev, pos, faces, np.float32(mid))
+      info['evaluations'] += 1
+      if nv <= max_vertices:
+        hi = mid
+      else:
+        lo = mid
+    cell = hi
+  cell = float(np.float32(cell))
+  p, n, c, f, vmap = simplify_mesh_arrays(pos, faces, cell, normals=normals, colors=colors, return_map=return_map)
+  info.update(cell=cell, vertices=len(p), faces=len(f), evaluations=info['evaluations'] + 1)
+  out = as_mesh(p, n, c, f)
+  return (out, info, vmap.cpu().numpy()) if return_map else (out, info)
+
+
 def _icosphere_vertices(subdivisions):
   """Unit icosphere: the 12 icosahedron vertices followed, per subdivision, by the normalised
   midpoints of the unique edges (sorted by vertex pair).  trimesh.creation.icosphere

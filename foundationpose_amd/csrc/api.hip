@@ -122,6 +122,7 @@ extern "C" int fp_ctx_destroy(fp_ctx *ctx) {
     }
     (void)hipEventDestroy(ctx->ev_fork);
   }
+  fp_simplify_state_free(ctx);
   if (ctx->arena.base) (void)hipFree(ctx->arena.base);
   if (ctx->zero_page) (void)hipFree(ctx->zero_page);
   delete ctx;

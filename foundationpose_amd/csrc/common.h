@@ -108,7 +108,9 @@ struct fp_ctx {
   hipStream_t side[NSIDE] = {};
   hipEvent_t ev_fork = nullptr, ev_join[NSIDE] = {};
   bool side_ready = false;
+  struct fp_simplify_state *simplify = nullptr;   // mesh_simplify.hip: what fp_mesh_simplify_count leaves for fp_mesh_simplify_write
 };
+void fp_simplify_state_free(fp_ctx *ctx);         // mesh_simplify.hip; fp_ctx_destroy
 
 int fp_arena_ensure(fp_ctx *ctx, size_t bytes);
 size_t fp_arena_bytes_for(int n_hyp);     // whole refine/score pass (outer buffers + network)
@@ -503,6 +505,10 @@ int launch_pose_errors(const float *pts, int n_pts, const float *pred, const flo
 // bytes of per-workgroup candidates
 size_t mesh_diameter_slab_bytes(int n_pts);
 int launch_mesh_diameter(const float *pts, int n_pts, void *slab, float *out, int32_t *pair, hipStream_t s);
+// tsdf.hip: in-place exclusive scan of n 64-bit words (reduce, scan of the block sums, add: a workgroup never waits for another one);
+// `sums` holds scan_sums_words(n) words for the block sums of every level
+size_t scan_sums_words(long long n);
+int scan_exclusive(unsigned long long *data, long long n, unsigned long long *sums, hipStream_t s);
 // metrics.hip: MSSD / MSPD of n_poses poses (fp_pose_errors_bop); `slab` holds bop_errors_slab_bytes(...) bytes of tile maxima
 size_t bop_errors_slab_bytes(int n_pts, int n_poses, int n_sym);
 int launch_bop_errors(const float *pts, int n_pts, const float *pred, const float *gt, int gt_per_pose, int n_poses, const float *sym,

@@ -359,6 +359,9 @@ void build_table(uint8_t *tab) {
   }
 }
 
+}  // namespace
+
+// declared in common.h: mesh_simplify.hip numbers its clusters and faces with the same scan
 size_t scan_sums_words(long long n) {
   size_t w = 0;
   while (n > SCAN_TILE) {
@@ -368,7 +371,7 @@ size_t scan_sums_words(long long n) {
   return w + 1;
 }
 
-int scan_exclusive(u64 *data, long long n, u64 *sums, hipStream_t s) {
+int scan_exclusive(unsigned long long *data, long long n, unsigned long long *sums, hipStream_t s) {
   const long long nb = (n + SCAN_TILE - 1) / SCAN_TILE;
   if (nb <= 1) {
     hipLaunchKernelGGL(scan_tile_kernel, dim3(1), dim3(TS_THREADS), 0, s, data, n, (const u64 *)nullptr);
@@ -382,8 +385,6 @@ int scan_exclusive(u64 *data, long long n, u64 *sums, hipStream_t s) {
   FP_CHECK_HIP(hipGetLastError());
   return FP_OK;
 }
-
-}  // namespace
 
 struct fp_tsdf {
   int device = 0;

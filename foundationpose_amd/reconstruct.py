@@ -374,7 +374,8 @@ def _refine_on(depths, views, voxel_size, anchor, order, rounds, trunc, margin, 
   return poses, info
 
 
-def reconstruct_object(views, voxel_size=0.002, trunc=None, min_weight=1, depth_filter=True, margin=None, device='cuda', refine_poses=False):
+def reconstruct_object(views, voxel_size=0.002, trunc=None, min_weight=1, depth_filter=True, margin=None, device='cuda', refine_poses=False,
+                       max_vertices=None, simplify_cell=None):
   """Reference views -> mesh (synthetic.SimpleMesh with vertex normals and colours).  `views`: a folder in the reference's layout
   (load_reference_views) or a dict with depths, masks, K, cam_in_obs and optionally rgbs.  depth_filter runs erode_depth and
   bilateral_filter_depth on every view first, as the estimator does with an observed frame.  The fusion and the extraction run on the
@@ -383,7 +384,12 @@ def reconstruct_object(views, voxel_size=0.002, trunc=None, min_weight=1, depth_
   runs the procedure of refine_view_poses first (view 0 is the anchor) and fuses with the poses it returns; the default fuses with the
   poses as given.  The refinement aligns on the eroded maps, before the bilateral filter, in a volume of its own: `trunc` and `margin`
   here are the fusion's and are NOT passed on to it (its band is 2 voxels, its margin 5 voxels + 1 cm); give refine_poses a dict of
-  refine_view_poses' keyword arguments (anchor, order, rounds, trunc, margin, iterations, min_pixels, damping, max_step) to set them."""
+  refine_view_poses' keyword arguments (anchor, order, rounds, trunc, margin, iterations, min_pixels, damping, max_step) to set them.
+  max_vertices or simplify_cell (one of them; default neither: the mesh as extracted) reduces the mesh by vertex clustering after the
+  largest-component step (Utils.simplify_mesh): the rasteriser keeps a hypothesis' vertices on chip up to 8192 vertices, and a 2 mm fusion
+  of a hand-sized object has tens of times that."""
+  if max_vertices is not None and simplify_cell is not None:
+    raise ValueError('reconstruct_object: give max_vertices or simplify_cell, not both')
   if isinstance(views, (str, os.PathLike)):
     views = load_reference_views(views)
   dev = _device(device)
@@ -409,4 +415,8 @@ def reconstruct_object(views, voxel_size=0.002, trunc=None, min_weight=1, depth_
     used[faces.reshape(-1)] = True
     new_id = np.cumsum(used) - 1
     mesh = SimpleMesh(mesh.vertices[used], new_id[faces], vertex_normals=mesh.vertex_normals[used], vertex_colors=mesh.visual.vertex_colors[used])
+  if max_vertices is not None or simplify_cell is not None:
+    from .Utils import simplify_mesh
+    with torch.cuda.device(dev):
+      mesh, _ = simplify_mesh(mesh, cell=simplify_cell, max_vertices=max_vertices)
   return mesh

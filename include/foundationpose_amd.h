@@ -249,6 +249,49 @@ int fp_scene_instances(fp_ctx *ctx, const fp_mesh *const *meshes, const float *d
  * n_pts > 0, n_pts < 0 or above FP_MESH_DIAMETER_MAX_POINTS (2^21: 2.1 M tile pairs, 34 MB of arena). */
 int fp_mesh_diameter(fp_ctx *ctx, const float *d_pts, int n_pts, float *d_out_diameter, int32_t *d_out_pair, void *stream);
 
+#define FP_MESH_SIMPLIFY_MAX_VERTICES (1 << 21)
+#define FP_MESH_SIMPLIFY_MAX_FACES (1 << 23)
+/* Vertex clustering: a mesh (or, with F = 0, a point cloud) reduced to one vertex per occupied cell of a grid of pitch `cell`.  The
+ * rasteriser keeps a hypothesis' vertices in LDS up to 8192 vertices and its one-launch forms take up to 65 535 faces; fused and scanned
+ * meshes are far larger, and this is the stage that takes them there.  Deterministic: the outputs are a function of the inputs alone,
+ * bit for bit, whatever order the device runs in (tests/mesh_simplify_oracle.py restates the rule in numpy).
+ *   Inputs, device: d_pos (V,3) float32, finite; d_faces (F,3) int32 with entries in 0 .. V-1, F may be 0; optional d_normals (V,3) float32
+ * (components within +-2^11) and d_colors (V,3) uint8; cell > 0.  All arithmetic is IEEE without contraction.
+ *   1. Origin.  o = the component-wise minimum of the positions (an exact float32 minimum).
+ *   2. Cell of a vertex.  Per axis c = (int64) floorf((p - o) / cell), subtraction and division in float32.  dims = max c + 1 per axis;
+ *      FP_EINVAL when a dim exceeds 2^21 (the message names a cell that fits).  key = (cz * ny + cy) * nx + cx in int64.
+ *   3. Clusters.  The vertices of one key form a cluster.  Clusters are numbered by their lowest member vertex index, ascending.
+ *      Vertices that no face references cluster like the others.
+ *   4. Cluster attributes, exact and hence independent of the order of the sums.  Position: q = llrint(((double)p - (double)o) * 2^30)
+ *      per axis (round half to even), S = sum of q over the members in int64, n = members; the result is
+ *      (float)((double)o + (double)S / (double)n / 2^30).  Normal: the int64 sums of llrint((double)nrm * 2^30) per axis, converted to
+ *      double (sx, sy, sz), divided by sqrt((sx*sx + sy*sy) + sz*sz) in double, cast to float; a zero sum gives (0,0,0).  Colour:
+ *      (2 * sum c + n) / (2 n) per channel in integers.  A cluster of ONE member keeps that member's position, normal and colour bits:
+ *      a cell below the smallest vertex spacing returns the input vertices bit for bit.
+ *   5. Faces.  Each face is mapped to cluster ids.  A face with two equal ids is dropped.  Among faces with the same unordered id
+ *      triple, whatever their orientation, only the lowest input face index survives.  Survivors keep their input order and their own
+ *      vertex order.
+ *   6. Vertices kept.  With F > 0 the clusters that no surviving face references are dropped and the others renumbered in cluster order.
+ *      With F = 0 every cluster is kept: the per-cell centroid cloud.
+ *   7. Vertex map.  d_out_vertex_map (V,) int32, optional: the output vertex of every input vertex, or -1.
+ *   Consequences: an input vertex whose cluster survives lies within sqrt(3) * cell of its output vertex (plus 1e-6 of the bounding
+ * box' extent for the float32 cell assignment); no output face is degenerate or repeats a vertex triple; with F > 0 every output vertex
+ * is referenced.
+ *   Two calls, as for the TSDF extraction.  fp_mesh_simplify_count builds the cluster and face tables in an allocation owned by the
+ * context (about 50 bytes a vertex and 40 a face, kept until a larger mesh arrives or the context is destroyed), SYNCHRONISES the stream
+ * and returns h_counts = {vertices, faces}.  The caller allocates d_out_pos (nv,3), d_out_normals and d_out_colors (nv,3; each optional,
+ * and only with its input), d_out_faces (nf,3), and calls fp_mesh_simplify_write with the SAME d_pos, V, d_faces, F and cell; it
+ * queues its kernels and does not synchronise.  The sums are 64-bit integer atomic adds; there is no floating-point atomic.
+ *   FP_EINVAL: a null ctx or h_counts, V or F outside their limits, null d_pos or d_faces with a non-zero count, a cell that is not
+ * positive and finite, positions that are not finite, a face index outside 0 .. V-1, a dim above 2^21, a bounding box whose extent times
+ * 2^30 times V reaches 2^62 (the fixed point would overflow: extents in metres are far below it); for write: no count before it on this
+ * context, another mesh (pointers or sizes) or cell than the last count had, n_vertices or n_faces other than its counts, a null
+ * required output, an output attribute without its input.  FP_ENOMEM: the tables do not fit the device. */
+int fp_mesh_simplify_count(fp_ctx *ctx, const float *d_pos, int V, const int32_t *d_faces, int F, float cell, int64_t *h_counts, void *stream);
+int fp_mesh_simplify_write(fp_ctx *ctx, const float *d_pos, const float *d_normals, const uint8_t *d_colors, int V, const int32_t *d_faces, int F,
+                           float cell, float *d_out_pos, float *d_out_normals, uint8_t *d_out_colors, int32_t *d_out_faces,
+                           int32_t *d_out_vertex_map, int64_t n_vertices, int64_t n_faces, void *stream);
+
 /* ---- networks -------------------------------------------------------------------------------- */
 typedef struct {
   const char *name;    /* reference state_dict key, e.g. "encodeA.0.net.0.weight" */

@@ -1,9 +1,10 @@
 """A mesh from a folder of posed RGB-D reference views (the reference's model-free layout: rgb/, depth_enhanced/ or depth/, mask/,
 cam_in_ob/, K.txt), by TSDF fusion and marching tetrahedra on the GPU (foundationpose_amd.reconstruct).
 usage: python scripts/reconstruct_object.py DIR [--voxel 0.002] [--trunc T] [--min-weight 1] [--no-depth-filter] [--refine-poses]
-       [--out DIR/model/model.obj]
+       [--max-vertices N | --simplify-cell C] [--out DIR/model/model.obj]
 The output format follows the extension: .obj or .ply.  --refine-poses aligns every view but the first to the geometry fused so far before the
-fusion (reconstruct.refine_view_poses) and also writes the poses it used to DIR/cam_in_ob_refined/NAME.txt."""
+fusion (reconstruct.refine_view_poses) and also writes the poses it used to DIR/cam_in_ob_refined/NAME.txt.  --max-vertices N (8192: the
+rasteriser's on-chip vertex limit) or --simplify-cell C (metres) reduces the mesh by vertex clustering (Utils.simplify_mesh)."""
 import argparse
 import os
 import sys
@@ -23,6 +24,8 @@ def main():
   ap.add_argument('--min-weight', type=float, default=1)
   ap.add_argument('--no-depth-filter', action='store_true')
   ap.add_argument('--refine-poses', action='store_true')
+  ap.add_argument('--max-vertices', type=int, default=None)
+  ap.add_argument('--simplify-cell', type=float, default=None)
   ap.add_argument('--out', default=None)
   args = ap.parse_args()
   out = args.out or os.path.join(args.dir, 'model', 'model.obj')
@@ -35,7 +38,8 @@ def main():
     for v, why in sorted(info['stopped'].items()):
       print(f'view {views["names"][v]}: alignment stopped ({why})')
     views = dict(views, cam_in_obs=poses)
-  mesh = reconstruct_object(views, voxel_size=args.voxel, trunc=args.trunc, min_weight=args.min_weight, depth_filter=not args.no_depth_filter)
+  mesh = reconstruct_object(views, voxel_size=args.voxel, trunc=args.trunc, min_weight=args.min_weight, depth_filter=not args.no_depth_filter,
+                            max_vertices=args.max_vertices, simplify_cell=args.simplify_cell)
   os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
   if out.lower().endswith('.ply'):
     mesh_io.save_ply(mesh, out)
