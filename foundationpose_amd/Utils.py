@@ -369,17 +369,29 @@ def mesh_diameter(model_pts=None, mesh=None, mesh_tensors=None, return_pair=Fals
   return d
 
 
-def simplify_mesh_arrays(pos, faces, cell, normals=None, colors=None, return_map=False):
-  """fp_mesh_simplify_count + fp_mesh_simplify_write on arrays: pos (V,3), faces (F,3) or None (a point cloud), normals (V,3) or None,
-  colors (V,3) uint8 or None; numpy or torch, taken to the device as float32 / int32 / uint8.  Returns the device tensors (pos, normals |
-  None, colors | None, faces, vertex_map | None).  The count is read back, so this call synchronises."""
+def _mesh_parts(mesh, stored_normals=False):
+  """(vertices, faces, normals, colors, visual) of a mesh object or of a tuple (vertices, faces[, normals[, colors]]).  stored_normals:
+  a synthetic.SimpleMesh that was given no normals yields None instead of computing them on the host."""
+  if isinstance(mesh, (tuple, list)):
+    parts = list(mesh) + [None] * (4 - len(mesh))
+    return parts[0], parts[1], parts[2], parts[3], None
+  visual = getattr(mesh, 'visual', None)
+  normals = mesh._vn if stored_normals and hasattr(mesh, '_vn') else getattr(mesh, 'vertex_normals', None)
+  return mesh.vertices, mesh.faces, normals, getattr(visual, 'vertex_colors', None), visual
+
+
+def _faces_on(faces, dev):
+  return torch.zeros((0, 3), dtype=torch.int32, device=dev) if faces is None else \
+      torch.as_tensor(faces).to(device=dev, dtype=torch.int32).reshape(-1, 3).contiguous()
+
+
+def _mesh_arrays_on(pos, faces, normals, colors):
+  """The arrays of simplify_mesh_arrays / clean_mesh_arrays on the device of `pos` as float32 / int32 / uint8, checked: (dev, pos, faces,
+  normals | None, colors | None)."""
   dev = _device_of(pos)
-  ctx = _lib.Context.get(dev)
   pos = torch.as_tensor(pos).to(device=dev, dtype=torch.float).reshape(-1, 3).contiguous()
   V = len(pos)
-  faces = torch.zeros((0, 3), dtype=torch.int32, device=dev) if faces is None else \
-      torch.as_tensor(faces).to(device=dev, dtype=torch.int32).reshape(-1, 3).contiguous()
-  F = len(faces)
+  faces = _faces_on(faces, dev)
   if normals is not None:
     normals = torch.as_tensor(normals).to(device=dev, dtype=torch.float).reshape(-1, 3).contiguous()
   if colors is not None:
@@ -390,6 +402,24 @@ def simplify_mesh_arrays(pos, faces, cell, normals=None, colors=None, return_map
   for name, a in (('normals', normals), ('colors', colors)):
     if a is not None and len(a) != V:
       raise ValueError(f'{len(a)} {name} for {V} vertices')
+  return dev, pos, faces, normals, colors
+
+
+def _rgb_u8_on(colors, dev, who):
+  """Vertex colours of a mesh object, RGB or RGBA uint8, as a (V,3) device tensor."""
+  colors = torch.as_tensor(colors).to(device=dev)
+  if colors.dtype != torch.uint8:
+    raise ValueError(f'{who}: vertex colours must be uint8, got {colors.dtype}')
+  return colors.reshape(len(colors), -1)[:, :3].contiguous()
+
+
+def simplify_mesh_arrays(pos, faces, cell, normals=None, colors=None, return_map=False):
+  """fp_mesh_simplify_count + fp_mesh_simplify_write on arrays: pos (V,3), faces (F,3) or None (a point cloud), normals (V,3) or None,
+  colors (V,3) uint8 or None; numpy or torch, taken to the device as float32 / int32 / uint8.  Returns the device tensors (pos, normals |
+  None, colors | None, faces, vertex_map | None).  The count is read back, so this call synchronises."""
+  dev, pos, faces, normals, colors = _mesh_arrays_on(pos, faces, normals, colors)
+  ctx = _lib.Context.get(dev)
+  V, F = len(pos), len(faces)
   nv, nf = _simplify_count(ctx, dev, pos, faces, cell)
   o_pos = torch.empty((nv, 3), dtype=torch.float, device=dev)
   o_nrm = None if normals is None else torch.empty((nv, 3), dtype=torch.float, device=dev)
@@ -429,28 +459,13 @@ def simplify_mesh(mesh, cell=None, max_vertices=None, return_map=False):
   from .synthetic import SimpleMesh
   if (cell is None) == (max_vertices is None):
     raise ValueError('simplify_mesh: give exactly one of cell and max_vertices')
-  if isinstance(mesh, (tuple, list)):
-    parts = list(mesh) + [None] * (4 - len(mesh))
-    verts, faces, normals, colors = parts[:4]
-  else:
-    visual = getattr(mesh, 'visual', None)
-    colors = getattr(visual, 'vertex_colors', None)
-    if colors is None and getattr(visual, 'uv', None) is not None:
-      raise ValueError('simplify_mesh: the mesh is UV-textured; texture coordinates are not transferred - bake vertex colours first')
-    verts, faces = mesh.vertices, mesh.faces
-    normals = getattr(mesh, 'vertex_normals', None)
-  dev = _device_of(verts)
-  normals_in = normals
-  pos = torch.as_tensor(verts).to(device=dev, dtype=torch.float).reshape(-1, 3).contiguous()
-  faces = torch.zeros((0, 3), dtype=torch.int32, device=dev) if faces is None else \
-      torch.as_tensor(faces).to(device=dev, dtype=torch.int32).reshape(-1, 3).contiguous()
-  if normals is not None:
-    normals = torch.as_tensor(normals).to(device=dev, dtype=torch.float).reshape(-1, 3).contiguous()
+  visual = None if isinstance(mesh, (tuple, list)) else getattr(mesh, 'visual', None)
+  if getattr(visual, 'vertex_colors', None) is None and getattr(visual, 'uv', None) is not None:
+    raise ValueError('simplify_mesh: the mesh is UV-textured; texture coordinates are not transferred - bake vertex colours first')
+  verts, f_in, normals_in, colors, _ = _mesh_parts(mesh)
   if colors is not None:
-    colors = torch.as_tensor(colors).to(device=dev)
-    if colors.dtype != torch.uint8:
-      raise ValueError(f'simplify_mesh: vertex colours must be uint8, got {colors.dtype}')
-    colors = colors.reshape(len(colors), -1)[:, :3].contiguous()
+    colors = _rgb_u8_on(colors, _device_of(verts), 'simplify_mesh')
+  dev, pos, faces, normals, colors = _mesh_arrays_on(verts, f_in, normals_in, colors)
   V, F = len(pos), len(faces)
   info = dict(cell=0.0, vertices_in=V, faces_in=F, vertices=V, faces=F, evaluations=0)
 
@@ -465,7 +480,6 @@ def simplify_mesh(mesh, cell=None, max_vertices=None, return_map=False):
     if V <= max_vertices:      # the arrays as they came, copied to the host: no rounding to float32
       host = lambda x: None if x is None else np.array(x.detach().cpu().numpy() if torch.is_tensor(x) else x)
       rgba = None if colors is None else np.concatenate([colors.cpu().numpy(), np.full((V, 1), 255, dtype=np.uint8)], 1)
-      f_in = mesh[1] if isinstance(mesh, (tuple, list)) else mesh.faces
       out = SimpleMesh(host(verts), np.zeros((0, 3), dtype=np.int64) if f_in is None else host(f_in), vertex_normals=host(normals_in), vertex_colors=rgba)
       vmap = np.arange(V, dtype=np.int32)
       return (out, info, vmap) if return_map else (out, info)
@@ -485,6 +499,98 @@ def simplify_mesh(mesh, cell=None, max_vertices=None, return_map=False):
   info.update(cell=cell, vertices=len(p), faces=len(f), evaluations=info['evaluations'] + 1)
   out = as_mesh(p, n, c, f)
   return (out, info, vmap.cpu().numpy()) if return_map else (out, info)
+
+
+def _components_count(ctx, dev, faces, V, keep, min_faces, min_fraction):
+  if keep not in ('largest', 'all'):
+    raise ValueError(f"keep must be 'largest' or 'all', got {keep!r}")
+  counts = (ctypes.c_int64 * 4)()
+  check(lib().fp_mesh_components_count(ctx.handle, ptr(faces) if len(faces) else None, len(faces), V, int(min_faces), float(min_fraction),
+                                       1 if keep == 'largest' else 0, counts, stream_ptr(dev)))
+  return tuple(int(c) for c in counts)
+
+
+def mesh_components(mesh):
+  """The connected components of a mesh on the device (fp_mesh_components_*; the rule is stated in include/foundationpose_amd.h): every
+  face (a, b, c) joins a-b and b-c.  mesh: anything with `vertices` and `faces`, or a tuple (vertices, faces, ...) of numpy arrays or
+  device tensors.  Returns the device tensors (labels (V,) int32 - the lowest vertex index of every vertex' component - and stats (C,2)
+  int32 - {n_vertices, n_faces} of the components, numbered by that lowest index).  The count is read back: this call synchronises."""
+  verts, faces = _mesh_parts(mesh)[:2]
+  dev = _device_of(verts)
+  ctx = _lib.Context.get(dev)
+  V = len(verts)
+  faces = _faces_on(faces, dev)
+  # a selection that keeps nothing (no int32 face count reaches min_faces = 2^31 - 1 with F below it): the write then needs no mesh buffers
+  C, _, nv, nf = _components_count(ctx, dev, faces, V, 'all', 2 ** 31 - 1, 0.0)
+  labels = torch.empty((V,), dtype=torch.int32, device=dev)
+  stats = torch.empty((C, 2), dtype=torch.int32, device=dev)
+  F = len(faces)
+  check(lib().fp_mesh_components_write(ctx.handle, None, None, None, V, ptr(faces) if F else None, F, None, None, None, None, None,
+                                       ptr(labels) if V else None, ptr(stats) if C else None, nv, nf, stream_ptr(dev)))
+  return labels, stats
+
+
+def _clean_arrays(pos, faces, normals, colors, keep, min_faces, min_fraction, want_map, want_stats):
+  dev, pos, faces, normals, colors = _mesh_arrays_on(pos, faces, normals, colors)
+  ctx = _lib.Context.get(dev)
+  V, F = len(pos), len(faces)
+  C, kept, nv, nf = _components_count(ctx, dev, faces, V, keep, min_faces, min_fraction)
+  o_pos = torch.empty((nv, 3), dtype=torch.float, device=dev)
+  o_nrm = None if normals is None else torch.empty((nv, 3), dtype=torch.float, device=dev)
+  o_col = None if colors is None else torch.empty((nv, 3), dtype=torch.uint8, device=dev)
+  o_faces = torch.empty((nf, 3), dtype=torch.int32, device=dev)
+  vmap = torch.empty((V,), dtype=torch.int32, device=dev) if want_map else None
+  labels = torch.empty((V,), dtype=torch.int32, device=dev) if want_stats else None
+  stats = torch.empty((C, 2), dtype=torch.int32, device=dev) if want_stats else None
+  check(lib().fp_mesh_components_write(ctx.handle, ptr(pos) if V else None, ptr(normals), ptr(colors), V, ptr(faces) if F else None, F,
+                                       ptr(o_pos) if nv else None, ptr(o_nrm) if nv else None, ptr(o_col) if nv else None,
+                                       ptr(o_faces) if nf else None, ptr(vmap) if V and want_map else None,
+                                       ptr(labels) if V and want_stats else None, ptr(stats) if C and want_stats else None, nv, nf,
+                                       stream_ptr(dev)))
+  info = dict(components=C, kept_components=kept, vertices_in=V, faces_in=F, vertices=nv, faces=nf)
+  return o_pos, o_nrm, o_col, o_faces, vmap, labels, stats, info
+
+
+def clean_mesh_arrays(pos, faces, normals=None, colors=None, keep='largest', min_faces=1, min_fraction=0.0, return_map=False):
+  """fp_mesh_components_count + fp_mesh_components_write on arrays: the mesh of the kept connected components.  pos (V,3), faces (F,3),
+  normals (V,3) or None, colors (V,3) uint8 or None; numpy or torch, taken to the device as float32 / int32 / uint8.  A component is kept
+  when it has at least min_faces faces and at least min_fraction of the largest component's; keep='largest' then keeps only the one
+  with the most faces (the lowest-numbered of equals), keep='all' every such component.  Vertices and faces keep their order; attributes
+  are copied bit for bit.  Returns the device tensors (pos, normals | None, colors | None, faces, vertex_map | None).  The count is read
+  back, so this call synchronises."""
+  return _clean_arrays(pos, faces, normals, colors, keep, min_faces, min_fraction, return_map, False)[:5]
+
+
+def clean_mesh(mesh, keep='largest', min_faces=1, min_fraction=0.0, return_map=False):
+  """Drops the small connected components of a mesh on the device (fp_mesh_components_*; the rule is stated in
+  include/foundationpose_amd.h): fused depth noise and scanned models carry floating debris.  mesh: as for simplify_mesh.  keep, min_faces,
+  min_fraction: as for clean_mesh_arrays - the default keeps the single component with the most faces; keep='all', min_fraction=0.2
+  keeps every part with at least a fifth of the largest one's faces, which is how a lid or a second jaw survives.
+
+  Returns (synthetic.SimpleMesh, info) - info: components, kept_components, vertices_in, faces_in, vertices, faces and component_faces,
+  the face counts of the kept components in component order - and, with return_map=True, the (V,) int32 map from input vertex to
+  output vertex (-1: dropped).  A UV-textured mesh keeps its texture: nothing is blended, so `uv` is gathered with the vertex map and
+  the image is passed through (synthetic.TextureVisual).  The alpha of RGBA colours is set to 255.  A SimpleMesh that was given no normals
+  gets none either: the result computes its own when asked, as the input would."""
+  from .synthetic import SimpleMesh, TextureVisual
+  verts, faces, normals, colors, visual = _mesh_parts(mesh, stored_normals=True)
+  uv = None if colors is not None else getattr(visual, 'uv', None)
+  if colors is not None:
+    colors = _rgb_u8_on(colors, _device_of(verts), 'clean_mesh')
+  p, n, c, f, vmap, labels, stats, info = _clean_arrays(verts, faces, normals, colors, keep, min_faces, min_fraction, True, True)
+  roots = torch.nonzero(labels == torch.arange(len(labels), dtype=torch.int32, device=labels.device))[:, 0]      # component k has the label roots[k]
+  info['component_faces'] = [int(x) for x in stats[vmap[roots] >= 0, 1].tolist()]
+  vmap = vmap.cpu().numpy()
+  host = lambda t: None if t is None else t.cpu().numpy()
+  if uv is not None:
+    image = getattr(visual, 'image', None)
+    if image is None and getattr(visual, 'material', None) is not None:
+      image = visual.material.image
+    out = SimpleMesh(host(p), host(f), vertex_normals=host(n), visual=TextureVisual(np.asarray(uv)[vmap >= 0], image))
+  else:
+    rgba = None if c is None else np.concatenate([host(c), np.full((len(c), 1), 255, dtype=np.uint8)], 1)
+    out = SimpleMesh(host(p), host(f), vertex_normals=host(n), vertex_colors=rgba)
+  return (out, info, vmap) if return_map else (out, info)
 
 
 def _icosphere_vertices(subdivisions):

@@ -23,6 +23,7 @@ FP_BOP_MSSD, FP_BOP_MSPD = 1, 2                       # fp_pose_errors_bop's `wh
 FP_VSD_MAX_TAUS = 32
 FP_MESH_DIAMETER_MAX_POINTS = 1 << 21                     # fp_mesh_diameter's largest n_pts
 FP_MESH_SIMPLIFY_MAX_VERTICES, FP_MESH_SIMPLIFY_MAX_FACES = 1 << 21, 1 << 23      # fp_mesh_simplify_count
+FP_MESH_COMPONENTS_MAX_VERTICES, FP_MESH_COMPONENTS_MAX_FACES = 1 << 21, 1 << 23  # fp_mesh_components_count
 FP_SCENE_MAX_INSTANCES = 1024                             # fp_scene_instances
 FP_SCENE_OCC_DEPTH, FP_SCENE_OCC_INSTANCES = 1, 2         # its `occluders` bits
 FP_SCENE_INFO_COLS = 12                                   # int32 columns of a d_info row:
@@ -151,6 +152,9 @@ _PROTOS = {
   'fp_mesh_simplify_count': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_float, c_void_p, c_void_p]),
   'fp_mesh_simplify_write': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_int64, c_int64, c_void_p]),
+  'fp_mesh_components_count': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p]),
+  'fp_mesh_components_write': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
   'fp_scene_instances': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_double, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_void_p, c_void_p]),
   'fp_draw_poses': (c_int, [c_void_p, POINTER(FpDrawArgs), c_void_p]),

@@ -18,7 +18,7 @@ void fp_set_error(const char *fmt, ...) {
 }
 
 extern "C" const char *fp_last_error(void) { return g_err; }
-extern "C" int fp_version(void) { return 100; }
+extern "C" int fp_version(void) { return 101; }
 
 // ---- context / arena ---------------------------------------------------------------------------
 size_t fp_arena_bytes_for(int n_hyp) {
@@ -123,6 +123,7 @@ extern "C" int fp_ctx_destroy(fp_ctx *ctx) {
     (void)hipEventDestroy(ctx->ev_fork);
   }
   fp_simplify_state_free(ctx);
+  fp_components_state_free(ctx);
   if (ctx->arena.base) (void)hipFree(ctx->arena.base);
   if (ctx->zero_page) (void)hipFree(ctx->zero_page);
   delete ctx;

@@ -375,12 +375,17 @@ def _refine_on(depths, views, voxel_size, anchor, order, rounds, trunc, margin, 
 
 
 def reconstruct_object(views, voxel_size=0.002, trunc=None, min_weight=1, depth_filter=True, margin=None, device='cuda', refine_poses=False,
-                       max_vertices=None, simplify_cell=None):
+                       max_vertices=None, simplify_cell=None, components='largest'):
   """Reference views -> mesh (synthetic.SimpleMesh with vertex normals and colours).  `views`: a folder in the reference's layout
   (load_reference_views) or a dict with depths, masks, K, cam_in_obs and optionally rgbs.  depth_filter runs erode_depth and
   bilateral_filter_depth on every view first, as the estimator does with an observed frame.  The fusion and the extraction run on the
-  GPU; afterwards every connected component except the one with the most faces is dropped ON THE HOST (scipy connected_components over
-  the faces) and the vertices are re-indexed in their old order - fused depth noise leaves small floating pieces.  refine_poses=True
+  GPU; afterwards every connected component except the one with the most faces is dropped, also on the GPU (Utils.clean_mesh_arrays:
+  fp_mesh_components_*, the rule of include/foundationpose_amd.h) and the vertices are re-indexed in their old order - fused depth noise
+  leaves small floating pieces.  components='largest' is that rule; a dict of clean_mesh's keyword arguments selects another one, e.g.
+  dict(keep='all', min_fraction=0.2) keeps every part with at least a fifth of the largest one's faces (a lid, a second jaw) and
+  dict(keep='all', min_faces=50) every part of 50 faces or more.  The mesh stays on the device from the extraction through the clean-up
+  and the simplification and is copied to the host once; only a mesh above the component limits (2^21 vertices, 2^23 faces) takes the
+  host path (largest_component, scipy), which knows the 'largest' rule alone.  refine_poses=True
   runs the procedure of refine_view_poses first (view 0 is the anchor) and fuses with the poses it returns; the default fuses with the
   poses as given.  The refinement aligns on the eroded maps, before the bilateral filter, in a volume of its own: `trunc` and `margin`
   here are the fusion's and are NOT passed on to it (its band is 2 voxels, its margin 5 voxels + 1 cm); give refine_poses a dict of
@@ -407,7 +412,35 @@ def reconstruct_object(views, voxel_size=0.002, trunc=None, min_weight=1, depth_
   origin, dims = volume_from_views(depths, views.get('masks'), views['K'], cam_in_obs, voxel_size, margin=margin, device=dev)
   vol = TsdfVolume(origin, voxel_size, dims, trunc=trunc, device=dev)
   vol.integrate(depths, views['K'], cam_in_obs, rgbs=views.get('rgbs'), masks=views.get('masks'))
-  mesh = vol.extract_mesh(min_weight)
+  rule = dict(keep='largest', min_faces=1, min_fraction=0.0)
+  if isinstance(components, dict):
+    if set(components) - set(rule):
+      raise TypeError(f'components: unknown keys {sorted(set(components) - set(rule))}')
+    rule.update(components)
+  elif components != 'largest':
+    raise ValueError(f"components must be 'largest' or a dict of keep, min_faces, min_fraction, got {components!r}")
+  v, nr, c, f = vol.extract_arrays(min_weight)
+  if len(v) > _lib.FP_MESH_COMPONENTS_MAX_VERTICES or len(f) > _lib.FP_MESH_COMPONENTS_MAX_FACES:
+    if rule != dict(keep='largest', min_faces=1, min_fraction=0.0):
+      raise ValueError(f'reconstruct_object: {len(v)} vertices and {len(f)} faces exceed the limits of the component clean-up on the device; '
+                       f"only components='largest' is available there (a larger voxel_size gives a smaller mesh)")
+    return _finish_on_host(v, nr, c, f, dev, max_vertices, simplify_cell)
+  from .Utils import clean_mesh_arrays, simplify_mesh
+  with torch.cuda.device(dev):
+    if len(f):                   # without a face there is nothing to tell apart: the vertices as extracted
+      kv, kn, kc, kf, _ = clean_mesh_arrays(v, f, normals=nr, colors=c, **rule)
+      if len(kf) != len(f):      # (every face kept: the mesh as extracted)
+        v, nr, c, f = kv, kn, kc, kf
+    if max_vertices is not None or simplify_cell is not None:
+      return simplify_mesh((v, f, nr, c), cell=simplify_cell, max_vertices=max_vertices)[0]
+  rgba = np.concatenate([c.cpu().numpy(), np.full((len(c), 1), 255, dtype=np.uint8)], 1)
+  return SimpleMesh(v.cpu().numpy(), f.cpu().numpy(), vertex_normals=nr.cpu().numpy(), vertex_colors=rgba)
+
+
+def _finish_on_host(v, nr, c, f, dev, max_vertices, simplify_cell):
+  """The tail of reconstruct_object for a mesh above the limits of fp_mesh_components_count: the largest component by scipy."""
+  rgba = np.concatenate([c.cpu().numpy(), np.full((len(c), 1), 255, dtype=np.uint8)], 1)
+  mesh = SimpleMesh(v.cpu().numpy(), f.cpu().numpy(), vertex_normals=nr.cpu().numpy(), vertex_colors=rgba)
   keep = largest_component(mesh.faces, len(mesh.vertices))
   if len(keep) and not keep.all():
     faces = mesh.faces[keep]

@@ -292,6 +292,50 @@ int fp_mesh_simplify_write(fp_ctx *ctx, const float *d_pos, const float *d_norma
                            float cell, float *d_out_pos, float *d_out_normals, uint8_t *d_out_colors, int32_t *d_out_faces,
                            int32_t *d_out_vertex_map, int64_t n_vertices, int64_t n_faces, void *stream);
 
+#define FP_MESH_COMPONENTS_MAX_VERTICES (1 << 21)
+#define FP_MESH_COMPONENTS_MAX_FACES (1 << 23)
+/* Connected components of a triangle list, a selection among them and the mesh of the selected ones: the clean-up that drops the
+ * floating pieces fused depth noise leaves, and the debris of scanned models.  Deterministic: the outputs are a function of the inputs
+ * alone, bit for bit, whatever order the device runs in (tests/mesh_components_oracle.py restates the rule in numpy / scipy).
+ *   Inputs, device: d_faces (F,3) int32 with entries in 0 .. V-1, F may be 0; for write d_pos (V,3) float32 and optional d_normals (V,3)
+ * float32 and d_colors (V,3) uint8.  No arithmetic is done on the attributes.
+ *   1. Graph.  Its nodes are the V vertices; every face (a, b, c) joins a-b and b-c.  Two sheets that share only a vertex are one
+ *      component.  A face with repeated indices is legal: it joins what it names and counts as a face.  A vertex that no face names is a
+ *      component of its own with 0 faces.
+ *   2. Label.  label[v] = the lowest vertex index of v's component.
+ *   3. Numbering.  Components are numbered 0 .. C-1 by that lowest index, ascending (the rule fp_mesh_simplify uses for clusters; it is
+ *      the label order of scipy's connected_components for an undirected graph).
+ *   4. Per component: n_vertices and n_faces, int32.  A face belongs to the component of its FIRST vertex.
+ *   5. Selection.  min_faces >= 1, min_fraction in [0, 1], largest_only 0 / 1.  M = the largest n_faces.  Component c is a candidate iff
+ *      n_faces[c] >= 1 and n_faces[c] >= min_faces and (double)n_faces[c] >= (double)min_fraction * (double)M (one IEEE multiplication in
+ *      double, no contraction).  Without largest_only every candidate is kept.  With it exactly one is: the candidate with the most faces,
+ *      the lowest component number among equals (none when the component of M faces is itself no candidate).  min_faces = 1,
+ *      min_fraction = 0, largest_only = 1 is "the component with the most faces".
+ *   6. Output.  Kept vertices are exactly the members of kept components, in their input order; every one of them is referenced (a kept
+ *      component has a face).  Kept faces are the faces of kept components, in their input order and with their own vertex order,
+ *      re-indexed.  Positions, normals and colours are copied bit for bit.
+ *   7. d_out_vertex_map (V,) int32, optional: the output vertex of every input vertex, or -1.  d_out_label (V,) int32, optional: rule 2.
+ *      d_out_stats (C,2) int32, optional: {n_vertices, n_faces} by component number.
+ *   Two calls, as for the simplification.  fp_mesh_components_count builds the decomposition in an allocation owned by the context (about
+ * 28 bytes a vertex and 8 a face, kept until a larger mesh arrives or the context is destroyed), SYNCHRONISES the stream and returns
+ * h_counts = {components C, kept components, kept vertices nv, kept faces nf}.  F = 0 gives {V, 0, 0, 0}; V = 0 gives zeros.  The caller
+ * allocates d_out_pos (nv,3), d_out_normals and d_out_colors (nv,3; each optional, and only with its input), d_out_faces (nf,3), and calls
+ * fp_mesh_components_write with the SAME d_faces, F and V; it queues its kernels and does not synchronise.
+ *   How: a lock-free union-find over an int32 parent array, one thread per face; the larger root is hooked under the smaller one with a
+ * compare-and-swap, so a root only ever decreases and the final root is the component's minimum whatever the order of the unions; one
+ * flatten pass; exclusive scans for the three numberings; int32 atomic adds for the counts.  No kernel waits for another workgroup.
+ *   FP_EINVAL: a null ctx or h_counts, V or F outside their limits, null d_faces with F > 0, faces without a vertex, min_faces < 1,
+ * min_fraction outside [0, 1] or NaN, largest_only other than 0 / 1, a face index outside 0 .. V-1 (found on the device, never followed);
+ * for write: no count before it on this context, another mesh (d_faces, F or V) than the last count had, n_vertices or n_faces other than
+ * its counts, a null required output or a null d_pos with nv > 0, an output attribute without its input.  FP_ENOMEM: the state does not
+ * fit the device. */
+int fp_mesh_components_count(fp_ctx *ctx, const int32_t *d_faces, int F, int V, int min_faces, float min_fraction, int largest_only,
+                             int64_t *h_counts /* {components, kept components, kept vertices, kept faces} */, void *stream);
+int fp_mesh_components_write(fp_ctx *ctx, const float *d_pos, const float *d_normals, const uint8_t *d_colors, int V, const int32_t *d_faces, int F,
+                             float *d_out_pos, float *d_out_normals, uint8_t *d_out_colors, int32_t *d_out_faces,
+                             int32_t *d_out_vertex_map, int32_t *d_out_label, int32_t *d_out_stats,
+                             int64_t n_vertices, int64_t n_faces, void *stream);
+
 /* ---- networks -------------------------------------------------------------------------------- */
 typedef struct {
   const char *name;    /* reference state_dict key, e.g. "encodeA.0.net.0.weight" */

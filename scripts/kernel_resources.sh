@@ -11,7 +11,7 @@ name = None; row = {}
 for line in sys.stdin:
     m = re.search(r'remark: +Function Name: (\S+)', line)
     if m:
-        name = subprocess.run(['c++filt', m.group(1)], capture_output=True, text=True).stdout.strip().split('(')[0]; row = {}; continue
+        name = subprocess.run(['c++filt', m.group(1)], capture_output=True, text=True).stdout.strip().replace('(anonymous namespace)::', '').split('(')[0]; row = {}; continue
     m = re.search(r'remark: +(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|VGPRs Spill|LDS Size \[bytes/block\]): (\d+)', line)
     if m and name:
         row[m.group(1)] = int(m.group(2))
