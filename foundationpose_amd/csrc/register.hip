@@ -130,11 +130,15 @@ int launch_register_hypotheses(const RegHypObjs &ob, float *poses, hipStream_t s
 // ---- ranking (src/estimater.py:230-237: scores.argsort(descending=True), poses[order], scores[order], best_id, pose_last and
 // pose_last @ get_tf_to_centered_mesh()): workgroup o ranks object o.  The rank of hypothesis i is the number of hypotheses that come before
 // it in the stable descending order (a greater score, or an equal one at a lower index), so every rank is taken exactly once; NaN ranks
-// above every number, as torch sorts it.  pose_of_mesh: the rotation block is copied, column 3 is the dot product row . (cneg, 1) in the
-// order of torch's float32 matrix product on this device (a chain of fused multiply-adds from the left).
+// above every number and -0.0 equals +0.0, as torch sorts them.  pose_of_mesh: the rotation block is copied, column 3 is the dot product
+// row . (cneg, 1) in the order of torch's float32 matrix product on this device (a chain of fused multiply-adds from the left).
 __device__ __forceinline__ unsigned rank_key(float v) {
   const unsigned u = __float_as_uint(v);
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);        // monotone in v; +NaN patterns lie above +inf
+}
+// the key of a score: every NaN is one key above +inf, and -0.0 takes the key of +0.0 (the two compare equal, so their order is the index order)
+__device__ __forceinline__ unsigned score_key(float v) {
+  return rank_key(v != v ? __uint_as_float(0x7fc00000u) : (v == 0.f ? 0.f : v));
 }
 
 __global__ __launch_bounds__(256) void register_rank_kernel(RegRankObjs ob, const float *__restrict__ poses, const float *__restrict__ scores) {
@@ -143,11 +147,10 @@ __global__ __launch_bounds__(256) void register_rank_kernel(RegRankObjs ob, cons
   const float *ps = poses + (size_t)ob.off[o] * 16;
   for (int i = threadIdx.x; i < n; i += blockDim.x) {
     const float v = sc[i];
-    const unsigned k = rank_key(v != v ? __uint_as_float(0x7fc00000u) : v);
+    const unsigned k = score_key(v);
     int rank = 0;
     for (int j = 0; j < n; ++j) {
-      const float w = sc[j];
-      const unsigned kj = rank_key(w != w ? __uint_as_float(0x7fc00000u) : w);
+      const unsigned kj = score_key(sc[j]);
       rank += (kj > k || (kj == k && j < i)) ? 1 : 0;
     }
     ob.scores_out[o][rank] = v;
