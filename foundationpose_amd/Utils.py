@@ -6,6 +6,7 @@ docstring; tensors live on the HIP device ('cuda' in torch-ROCm).  The rasterise
 """
 import logging
 import math
+import os
 import random
 
 import ctypes
@@ -575,6 +576,9 @@ def clean_mesh(mesh, keep='largest', min_faces=1, min_fraction=0.0, return_map=F
   from .synthetic import SimpleMesh, TextureVisual
   verts, faces, normals, colors, visual = _mesh_parts(mesh, stored_normals=True)
   uv = None if colors is not None else getattr(visual, 'uv', None)
+  if getattr(visual, 'uv_idx', None) is not None:
+    raise ValueError('clean_mesh: the mesh carries a per-face texture atlas (visual.uv_idx); its uv entries do not follow the vertices - '
+                     'clean the mesh first, then bake_texture')
   if colors is not None:
     colors = _rgb_u8_on(colors, _device_of(verts), 'clean_mesh')
   p, n, c, f, vmap, labels, stats, info = _clean_arrays(verts, faces, normals, colors, keep, min_faces, min_fraction, True, True)
@@ -591,6 +595,125 @@ def clean_mesh(mesh, keep='largest', min_faces=1, min_fraction=0.0, return_map=F
     rgba = None if c is None else np.concatenate([host(c), np.full((len(c), 1), 255, dtype=np.uint8)], 1)
     out = SimpleMesh(host(p), host(f), vertex_normals=host(n), vertex_colors=rgba)
   return (out, info, vmap) if return_map else (out, info)
+
+
+TEXTURE_COS_MIN = math.cos(math.radians(75.0))
+
+
+def texture_cell(tex_size, n_faces):
+  """The edge, in texels, of a cell of fp_texture_bake's atlas: floor(tex_size / g), g = the smallest integer with g g >= ceil(F / 2)."""
+  g = math.isqrt(max((int(n_faces) + 1) // 2, 1) - 1) + 1
+  return int(tex_size) // g
+
+
+def texture_size_for(n_faces, min_cell=8):
+  """The smallest power of two in fp_texture_bake's range whose cells have at least `min_cell` texels on an edge, or None."""
+  T = _lib.FP_TEXTURE_MIN_SIZE
+  while T <= _lib.FP_TEXTURE_MAX_SIZE:
+    if texture_cell(T, n_faces) >= min_cell:
+      return T
+    T *= 2
+  return None
+
+
+def bake_texture_arrays(pos, faces, rgbs, depths, K, cam_in_obs, tex_size, colors=None, masks=None, top_n=4, depth_tol=0.005,
+                        cos_min=TEXTURE_COS_MIN, zfar=np.inf, want_used=True):
+  """fp_texture_bake on arrays (the rule is stated in include/foundationpose_amd.h): pos (V,3), faces (F,3), colors (V,3) uint8 or None,
+  rgbs (n,H,W,3) uint8, depths (n,H,W) metres, masks (n,H,W) or None, cam_in_obs (n,4,4) camera-to-object; numpy or torch.  Returns the
+  device tensors (texture (T,T,3) uint8, uv (3F,2) float32 in the rasteriser's convention, used (T,T) int8 | None).  Nothing
+  synchronises.  At most FP_TSDF_MAX_VIEWS (64) views a call: the colour of a texel is chosen among all views at once, so more cannot
+  be cut into calls (ValueError)."""
+  dev, pos, faces, _, colors = _mesh_arrays_on(pos, faces, None, colors)
+  V, F, T = len(pos), len(faces), int(tex_size)
+  if V < 1 or F < 1:
+    raise ValueError(f'bake_texture: {V} vertices, {F} faces: nothing to texture')
+  if T < _lib.FP_TEXTURE_MIN_SIZE or T > _lib.FP_TEXTURE_MAX_SIZE or T & (T - 1):
+    raise ValueError(f'bake_texture: tex_size {T} must be a power of two, {_lib.FP_TEXTURE_MIN_SIZE} .. {_lib.FP_TEXTURE_MAX_SIZE}')
+  if texture_cell(T, F) < 4:
+    fit = texture_size_for(F, 4)
+    raise ValueError(f'bake_texture: {F} faces leave cells of {texture_cell(T, F)} texels at tex_size {T} (at least 4); ' +
+                     (f'tex_size {fit} fits' if fit else f'no tex_size up to {_lib.FP_TEXTURE_MAX_SIZE} fits: simplify the mesh first'))
+  if not 1 <= int(top_n) <= _lib.FP_TEXTURE_MAX_TOP_N:
+    raise ValueError(f'bake_texture: top_n {top_n} (1 .. {_lib.FP_TEXTURE_MAX_TOP_N})')
+  poses = np.ascontiguousarray(np.asarray(torch.as_tensor(cam_in_obs).cpu(), dtype=np.float64).reshape(-1, 4, 4))
+  n = len(poses)
+  if n > _lib.FP_TSDF_MAX_VIEWS:
+    raise ValueError(f'bake_texture: {n} views, at most {_lib.FP_TSDF_MAX_VIEWS} in one bake (every texel chooses among all views at once); '
+                     f'pass a subset')
+  H = W = 0
+  if n:
+    rgbs = torch.as_tensor(rgbs, device=dev)
+    if rgbs.dim() != 4 or rgbs.dtype != torch.uint8 or rgbs.shape[0] != n or rgbs.shape[3] != 3:
+      raise ValueError(f'bake_texture: rgbs must be uint8 of shape ({n},H,W,3), got {rgbs.dtype} {tuple(rgbs.shape)}')
+    rgbs = rgbs.contiguous()
+    H, W = int(rgbs.shape[1]), int(rgbs.shape[2])
+    depths = torch.as_tensor(depths, device=dev).to(torch.float).contiguous()
+    if tuple(depths.shape) != (n, H, W):
+      raise ValueError(f'bake_texture: depths must have the shape {(n, H, W)}, got {tuple(depths.shape)}')
+    if masks is not None:
+      masks = torch.as_tensor(masks, device=dev)
+      if tuple(masks.shape) != (n, H, W):
+        raise ValueError(f'bake_texture: masks must have the shape {(n, H, W)}, got {tuple(masks.shape)}')
+      masks = (masks != 0).to(torch.uint8).contiguous()
+  else:
+    rgbs = depths = masks = None
+  ctx = _lib.Context.get(dev)
+  Kd, Kp = k_ptr(K)
+  cfg = _lib.FpTextureCfg(struct_size=ctypes.sizeof(_lib.FpTextureCfg), tex_size=T, top_n=int(top_n), depth_tol=float(depth_tol),
+                          cos_min=float(cos_min), zfar=float(zfar) if np.isfinite(zfar) else float('inf'))
+  tex = torch.empty((T, T, 3), dtype=torch.uint8, device=dev)
+  uv = torch.empty((3 * F, 2), dtype=torch.float, device=dev)
+  used = torch.empty((T, T), dtype=torch.int8, device=dev) if want_used else None
+  check(lib().fp_texture_bake(ctx.handle, ptr(pos), V, ptr(faces), F, ptr(colors), ptr(rgbs), ptr(depths), ptr(masks), n, H, W, Kp,
+                              ptr(poses) if n else None, ctypes.byref(cfg), ptr(tex), ptr(uv), ptr(used), stream_ptr(dev)))
+  return tex, uv, used
+
+
+def bake_texture(mesh, views, tex_size=None, top_n=4, depth_tol=0.005, cos_min=TEXTURE_COS_MIN, return_info=False, min_cell=8, zfar=np.inf):
+  """A texture atlas for `mesh` from posed RGB-D reference views, on the device (fp_texture_bake; the rule is stated in
+  include/foundationpose_amd.h).  Every face gets its own patch of the atlas and its own three uv entries, so the vertices, faces and
+  normals come back unchanged; every texel is the cosang-weighted mean of the bilinear colour samples of the `top_n` views that see
+  its surface point most frontally (visible: the view's depth there agrees within depth_tol metres; cosang >= cos_min, default cos 75
+  degrees), and a texel no view sees takes the mesh's interpolated vertex colours (grey without any).
+
+  mesh: anything with `vertices`, `faces` and optionally `vertex_normals` and `visual.vertex_colors`.  Simplify first (simplify_mesh
+  refuses textured meshes).  views: the dict reconstruct_object takes - rgbs (required), depths, K, cam_in_obs, optional masks - or a
+  folder in the reference's layout; at most 64 views.  tex_size: a power of two, 64 .. 4096; None: the smallest whose cells have
+  at least min_cell texels on an edge.  Returns a synthetic.SimpleMesh whose visual is TextureVisual(uv, image, uv_idx): `uv` (3F,2)
+  float32 in the OBJ / trimesh convention (v up: make_mesh_tensors flips it back, bit for bit), `image` (T,T,3) uint8, `uv_idx`
+  (F,3) = arange(3F).  With return_info=True also info: tex_size, cell (texels on a cell's edge), coverage (the share of owned texels
+  that at least one view coloured), views."""
+  from .synthetic import SimpleMesh, TextureVisual
+  if isinstance(views, (str, os.PathLike)):
+    from .reconstruct import load_reference_views
+    views = load_reference_views(views)
+  if views.get('rgbs') is None:
+    raise ValueError('bake_texture: the views have no rgbs')
+  verts, faces, normals, colors, _ = _mesh_parts(mesh, stored_normals=True)
+  F = len(faces)
+  f_host = np.asarray(torch.as_tensor(faces).cpu()).reshape(-1, 3)
+  if F and (f_host.min() < 0 or f_host.max() >= len(verts)):
+    raise ValueError(f'bake_texture: a face indexes a vertex outside 0 .. {len(verts) - 1}')
+  if tex_size is None:
+    tex_size = texture_size_for(F, min_cell)
+    if tex_size is None:
+      raise ValueError(f'bake_texture: {F} faces do not fit cells of {min_cell} texels at tex_size {_lib.FP_TEXTURE_MAX_SIZE}; '
+                       f'simplify the mesh first or lower min_cell (at least 4)')
+  if colors is not None:
+    colors = _rgb_u8_on(colors, _device_of(verts), 'bake_texture')
+  tex, uv, used = bake_texture_arrays(verts, faces, views['rgbs'], views['depths'], views['K'], views['cam_in_obs'], tex_size, colors=colors,
+                                      masks=views.get('masks'), top_n=top_n, depth_tol=depth_tol, cos_min=cos_min, zfar=zfar)
+  uv = uv.cpu().numpy()
+  uv[:, 1] = np.float32(1) - uv[:, 1]       # exact: texel centres of a power-of-two atlas
+  host = lambda x: None if x is None else np.array(x.detach().cpu().numpy() if torch.is_tensor(x) else x)
+  out = SimpleMesh(host(verts), f_host.copy(), vertex_normals=host(normals),
+                   visual=TextureVisual(uv, tex.cpu().numpy(), uv_idx=np.arange(3 * F, dtype=np.int64).reshape(F, 3)))
+  if not return_info:
+    return out
+  owned = used >= 0
+  info = dict(tex_size=int(tex_size), cell=texture_cell(tex_size, F), views=len(views['cam_in_obs']),
+              coverage=float((used >= 1).sum().item()) / max(1, int(owned.sum().item())))
+  return out, info
 
 
 def _icosphere_vertices(subdivisions):

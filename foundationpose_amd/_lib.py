@@ -113,6 +113,14 @@ FP_TSDF_PLANES = ('tsdf', 'weight', 'r', 'g', 'b', 'color_weight')      # FP_TSD
 FP_TSDF_ALIGN_TERMS = 29                                                  # fp_tsdf_align: doubles per view of h_sums
 
 
+FP_TEXTURE_MIN_SIZE, FP_TEXTURE_MAX_SIZE, FP_TEXTURE_MAX_TOP_N, FP_TEXTURE_MAX_FACES = 64, 4096, 4, 1 << 21      # fp_texture_bake
+
+
+class FpTextureCfg(Structure):
+  """fp_texture_cfg (include/foundationpose_amd.h)."""
+  _fields_ = [('struct_size', ctypes.c_size_t), ('tex_size', c_int), ('top_n', c_int), ('depth_tol', c_float), ('cos_min', c_float), ('zfar', c_float)]
+
+
 class FpObjectBatch(Structure):
   _fields_ = [('mesh', c_void_p), ('d_rgb', c_void_p), ('d_geom', c_void_p), ('H', c_int), ('W', c_int), ('K', c_void_p),
               ('mesh_diameter', c_double), ('n', c_int)]
@@ -166,6 +174,8 @@ _PROTOS = {
   'fp_tsdf_extract_write': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
   'fp_tsdf_read_plane': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
   'fp_tsdf_align': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p]),
+  'fp_texture_bake': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                              POINTER(FpTextureCfg), c_void_p, c_void_p, c_void_p, c_void_p]),
   'fp_net_create': (c_int, [c_void_p, c_int, POINTER(FpTensor), c_int, c_int, POINTER(c_void_p)]),
   'fp_net_destroy': (c_int, [c_void_p]),
   'fp_net_rot_dim': (c_int, [c_void_p]),

@@ -46,10 +46,12 @@ def _mtl_texture(obj_path, mtllib, usemtl):
   return _read_image(img_path)
 
 
-def load_obj(path, texture_image=None):
+def load_obj(path, texture_image=None, split_uv=True):
   """Triangles and polygons (fan-triangulated); `v/vt/vn` index forms; negative (relative) indices.
   Vertices are split per (v, vt) pair when texture coordinates are present, so faces index uv directly
-  (make_mesh_tensors uses `mesh.faces` as `uv_idx`, src/Utils.py:115).  The texture is `texture_image` when given, else the `map_Kd`
+  (make_mesh_tensors uses `mesh.faces` as `uv_idx`, src/Utils.py:115).  split_uv=False keeps the file's vertices and faces instead and
+  returns the `vt` entries as they stand with the faces' vt indices as `visual.uv_idx` - the form of a per-face atlas
+  (Utils.bake_texture), which splitting would triple in vertices.  The texture is `texture_image` when given, else the `map_Kd`
   image of the material the first `usemtl` names (or the first material) in the `mtllib` file beside the OBJ - the YCB
   textured.obj + .mtl + .png form; a missing library or image leaves the mesh untextured."""
   v, vc, vt, corners = [], [], [], []
@@ -81,6 +83,14 @@ def load_obj(path, texture_image=None):
     raise ValueError(f'{path}: no geometry')
   v = np.asarray(v, dtype=np.float64)
   use_uv = bool(vt) and all(c[1] >= 0 for tri in corners for c in tri)
+  if use_uv and not split_uv:
+    mesh = SimpleMesh(v, np.asarray([[c[0] for c in tri] for tri in corners], dtype=np.int64))
+    if texture_image is None and mtllib is not None:
+      texture_image = _mtl_texture(path, mtllib, usemtl)
+    if texture_image is not None:
+      mesh.visual = TextureVisual(uv=np.asarray(vt, dtype=np.float64), image=np.asarray(texture_image),
+                                  uv_idx=np.asarray([[c[1] for c in tri] for tri in corners], dtype=np.int64))
+    return mesh
   if use_uv:
     remap, verts, uvs, faces = {}, [], [], []
     for tri in corners:
@@ -107,6 +117,11 @@ def load_obj(path, texture_image=None):
 
 
 def save_obj(mesh, path):
+  """`v` (with colours when the mesh has vertex colours) and `f`.  A mesh whose visual carries `uv_idx` (a per-face atlas,
+  Utils.bake_texture) is written with `vt`, `f v/vt`, and beside the OBJ NAME.mtl and NAME.png (the image as it stands, rows top-down,
+  for uv in the OBJ convention); uv with 9 significant digits, which a float32 survives unchanged."""
+  if getattr(mesh.visual, 'uv_idx', None) is not None:
+    return _save_obj_atlas(mesh, path)
   colors = np.asarray(mesh.visual.vertex_colors)[:, :3] / 255.0 if hasattr(mesh.visual, 'vertex_colors') else None
   with open(path, 'w') as f:
     for i, p in enumerate(mesh.vertices):
@@ -114,6 +129,24 @@ def save_obj(mesh, path):
       f.write('v %.9g %.9g %.9g%s\n' % (p[0], p[1], p[2], c))
     for t in mesh.faces:
       f.write('f %d %d %d\n' % (t[0] + 1, t[1] + 1, t[2] + 1))
+
+
+def _save_obj_atlas(mesh, path):
+  from PIL import Image
+  stem = os.path.splitext(os.path.basename(path))[0]
+  base = os.path.dirname(os.path.abspath(path))
+  Image.fromarray(np.ascontiguousarray(np.asarray(mesh.visual.image)[..., :3].astype(np.uint8))).save(os.path.join(base, stem + '.png'))
+  with open(os.path.join(base, stem + '.mtl'), 'w') as f:
+    f.write('newmtl material_0\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nmap_Kd %s.png\n' % stem)
+  uv_idx = np.asarray(mesh.visual.uv_idx).reshape(-1, 3)
+  with open(path, 'w') as f:
+    f.write('mtllib %s.mtl\nusemtl material_0\n' % stem)
+    for p in mesh.vertices:
+      f.write('v %.9g %.9g %.9g\n' % (p[0], p[1], p[2]))
+    for t in np.asarray(mesh.visual.uv):
+      f.write('vt %.9g %.9g\n' % (t[0], t[1]))
+    for t, u in zip(mesh.faces, uv_idx):
+      f.write('f %d/%d %d/%d %d/%d\n' % (t[0] + 1, u[0] + 1, t[1] + 1, u[1] + 1, t[2] + 1, u[2] + 1))
 
 
 # ---------------------------------------------------------------------------------------------- Stanford PLY
@@ -295,6 +328,8 @@ def save_ply(mesh, path, binary=True, texture_file=None, normals=True):
   <texture_file>` when a name is given; the image itself is not written - or uchar red green blue alpha for a coloured one, and the
   triangles as `list uchar int vertex_indices`.  binary=True: binary_little_endian; else ascii with 9 significant digits, which a
   float32 survives unchanged."""
+  if getattr(mesh.visual, 'uv_idx', None) is not None:
+    raise ValueError('save_ply: the mesh carries a per-face texture atlas (visual.uv_idx); a PLY holds one uv per vertex - use save_obj')
   v = np.asarray(mesh.vertices, dtype=np.float32)
   cols = [('x', v[:, 0]), ('y', v[:, 1]), ('z', v[:, 2])]
   if normals:
@@ -333,12 +368,12 @@ def save_ply(mesh, path, binary=True, texture_file=None, normals=True):
         f.write(('3 %d %d %d\n' % tuple(t)).encode('ascii'))
 
 
-def load_mesh(path, scale=1.0):
+def load_mesh(path, scale=1.0, split_uv=True):
   """A model file by its extension (.obj, .ply; any case), its vertices multiplied by `scale` - BOP models are in millimetres:
-  scale=1e-3 (src/datareader.py:322)."""
+  scale=1e-3 (src/datareader.py:322).  split_uv: load_obj's (an OBJ with a per-face atlas keeps its vertex count with False)."""
   ext = os.path.splitext(path)[1].lower()
   if ext == '.obj':
-    mesh = load_obj(path)
+    mesh = load_obj(path, split_uv=split_uv)
   elif ext == '.ply':
     mesh = load_ply(path)
   else:

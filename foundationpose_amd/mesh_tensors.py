@@ -10,7 +10,8 @@ def _is_textured(visual):
 
 def make_mesh_tensors(mesh, device='cuda', max_tex_size=None):
   """Same keys / dtypes / value ranges as the reference: pos (V,3) f32, faces (F,3) i32, vnormals (V,3) f32
-  and either vertex_color (V,3) f32 in [0,1] or tex (1,Ht,Wt,3) f32 in [0,1] + uv (V,2) (v flipped) + uv_idx."""
+  and either vertex_color (V,3) f32 in [0,1] or tex (1,Ht,Wt,3) f32 in [0,1] + uv (V,2) (v flipped) + uv_idx
+  (the faces, or `visual.uv_idx` where the visual has one: uv is then (n_uv,2))."""
   mesh_tensors = {}
   visual = mesh.visual
   if _is_textured(visual):
@@ -28,7 +29,8 @@ def make_mesh_tensors(mesh, device='cuda', max_tex_size=None):
         xs = (np.arange(int(round(img.shape[1] * scale))) / scale).astype(int).clip(0, img.shape[1] - 1)
         img = img[ys][:, xs]
     mesh_tensors['tex'] = torch.as_tensor(np.ascontiguousarray(img), device=device, dtype=torch.float)[None] / 255.0
-    mesh_tensors['uv_idx'] = torch.as_tensor(np.asarray(mesh.faces), device=device, dtype=torch.int)
+    uv_idx = getattr(visual, 'uv_idx', None)      # a per-face atlas (Utils.bake_texture) indexes uv on its own; else per vertex
+    mesh_tensors['uv_idx'] = torch.as_tensor(np.asarray(mesh.faces if uv_idx is None else uv_idx), device=device, dtype=torch.int)
     uv = torch.as_tensor(np.asarray(visual.uv), device=device, dtype=torch.float).clone()
     uv[:, 1] = 1 - uv[:, 1]
     mesh_tensors['uv'] = uv

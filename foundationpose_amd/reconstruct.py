@@ -375,7 +375,7 @@ def _refine_on(depths, views, voxel_size, anchor, order, rounds, trunc, margin, 
 
 
 def reconstruct_object(views, voxel_size=0.002, trunc=None, min_weight=1, depth_filter=True, margin=None, device='cuda', refine_poses=False,
-                       max_vertices=None, simplify_cell=None, components='largest'):
+                       max_vertices=None, simplify_cell=None, components='largest', texture=None):
   """Reference views -> mesh (synthetic.SimpleMesh with vertex normals and colours).  `views`: a folder in the reference's layout
   (load_reference_views) or a dict with depths, masks, K, cam_in_obs and optionally rgbs.  depth_filter runs erode_depth and
   bilateral_filter_depth on every view first, as the estimator does with an observed frame.  The fusion and the extraction run on the
@@ -392,11 +392,27 @@ def reconstruct_object(views, voxel_size=0.002, trunc=None, min_weight=1, depth_
   refine_view_poses' keyword arguments (anchor, order, rounds, trunc, margin, iterations, min_pixels, damping, max_step) to set them.
   max_vertices or simplify_cell (one of them; default neither: the mesh as extracted) reduces the mesh by vertex clustering after the
   largest-component step (Utils.simplify_mesh): the rasteriser keeps a hypothesis' vertices on chip up to 8192 vertices, and a 2 mm fusion
-  of a hand-sized object has tens of times that."""
+  of a hand-sized object has tens of times that.
+  texture (default None: vertex colours, the mesh as before) bakes a texture atlas last (Utils.bake_texture: fp_texture_bake), after
+  the clean-up and the simplification - a simplified mesh has one colour per 2.5 - 3 mm of surface, the views have a pixel per
+  millimetre - with the poses the fusion used (the refined ones under refine_poses), the depth maps the fusion used and the rgb as
+  given.  True: the smallest atlas with cells of 8 texels; an int: tex_size; a dict of bake_texture's tex_size, top_n, depth_tol,
+  cos_min, min_cell.  depth_tol defaults to 2 voxels here.  The views need rgbs, at most 64 of them."""
   if max_vertices is not None and simplify_cell is not None:
     raise ValueError('reconstruct_object: give max_vertices or simplify_cell, not both')
   if isinstance(views, (str, os.PathLike)):
     views = load_reference_views(views)
+  bake = None
+  if texture is not None and texture is not False:
+    bake = dict(tex_size=None, top_n=4, depth_tol=2.0 * voxel_size, min_cell=8)
+    if isinstance(texture, dict):
+      if set(texture) - (set(bake) | {'cos_min'}):
+        raise TypeError(f'texture: unknown keys {sorted(set(texture) - (set(bake) | {"cos_min"}))}')
+      bake.update(texture)
+    elif texture is not True:
+      bake['tex_size'] = int(texture)
+    if views.get('rgbs') is None:
+      raise ValueError('reconstruct_object: texture needs the views\' rgbs')
   dev = _device(device)
   eroded = _eroded_depths(views, depth_filter, dev)
   cam_in_obs = views['cam_in_obs']
@@ -424,7 +440,7 @@ def reconstruct_object(views, voxel_size=0.002, trunc=None, min_weight=1, depth_
     if rule != dict(keep='largest', min_faces=1, min_fraction=0.0):
       raise ValueError(f'reconstruct_object: {len(v)} vertices and {len(f)} faces exceed the limits of the component clean-up on the device; '
                        f"only components='largest' is available there (a larger voxel_size gives a smaller mesh)")
-    return _finish_on_host(v, nr, c, f, dev, max_vertices, simplify_cell)
+    return _textured(_finish_on_host(v, nr, c, f, dev, max_vertices, simplify_cell), bake, views, depths, cam_in_obs, dev)
   from .Utils import clean_mesh_arrays, simplify_mesh
   with torch.cuda.device(dev):
     if len(f):                   # without a face there is nothing to tell apart: the vertices as extracted
@@ -432,9 +448,19 @@ def reconstruct_object(views, voxel_size=0.002, trunc=None, min_weight=1, depth_
       if len(kf) != len(f):      # (every face kept: the mesh as extracted)
         v, nr, c, f = kv, kn, kc, kf
     if max_vertices is not None or simplify_cell is not None:
-      return simplify_mesh((v, f, nr, c), cell=simplify_cell, max_vertices=max_vertices)[0]
+      return _textured(simplify_mesh((v, f, nr, c), cell=simplify_cell, max_vertices=max_vertices)[0], bake, views, depths, cam_in_obs, dev)
   rgba = np.concatenate([c.cpu().numpy(), np.full((len(c), 1), 255, dtype=np.uint8)], 1)
-  return SimpleMesh(v.cpu().numpy(), f.cpu().numpy(), vertex_normals=nr.cpu().numpy(), vertex_colors=rgba)
+  return _textured(SimpleMesh(v.cpu().numpy(), f.cpu().numpy(), vertex_normals=nr.cpu().numpy(), vertex_colors=rgba), bake, views, depths,
+                   cam_in_obs, dev)
+
+
+def _textured(mesh, bake, views, depths, cam_in_obs, dev):
+  """The last stage of reconstruct_object: `mesh` as it is without `bake`, else with the atlas baked from the fusion's views."""
+  if bake is None or len(mesh.faces) == 0:
+    return mesh
+  from .Utils import bake_texture
+  with torch.cuda.device(dev):
+    return bake_texture(mesh, dict(rgbs=views['rgbs'], depths=depths, masks=views.get('masks'), K=views['K'], cam_in_obs=cam_in_obs), **bake)
 
 
 def _finish_on_host(v, nr, c, f, dev, max_vertices, simplify_cell):

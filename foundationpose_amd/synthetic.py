@@ -17,10 +17,13 @@ class _Visual:
 
 
 class TextureVisual:
-  """Stand-in for trimesh.visual.texture.TextureVisuals: `.uv` (V,2), `.image` (Ht,Wt,3) uint8."""
-  def __init__(self, uv, image):
+  """Stand-in for trimesh.visual.texture.TextureVisuals: `.uv` (V,2), `.image` (Ht,Wt,3) uint8.  `uv_idx` (F,3), optional: the uv
+  entries of every face's corners when they are not the face's vertex indices (a per-face atlas, Utils.bake_texture); `.uv` is then
+  (n_uv,2) with its own count."""
+  def __init__(self, uv, image, uv_idx=None):
     self.uv = uv
     self.image = image
+    self.uv_idx = uv_idx
 
 
 class SimpleMesh:

@@ -709,6 +709,70 @@ int fp_tsdf_read_plane(fp_ctx *ctx, const fp_tsdf *vol, int plane, float *d_out,
 int fp_tsdf_align(fp_ctx *ctx, const fp_tsdf *vol, const float *d_depth, const uint8_t *d_mask, int n_views, int H, int W, const double *K,
                   const double *cam_in_ob, float zfar, float min_weight, float *d_rows, double *h_sums, void *stream);
 
+/* ---- texture baking: the colours of posed RGB-D reference views gathered into a per-face texture atlas of a mesh - the last stage of
+ *      the model-free set-up, after the simplification (fp_mesh_simplify_* refuses textured meshes: simplify first, then bake).  The
+ *      reference does this in mesh_texture_from_train_images (bundlesdf/nerf_runner.py:1122) with a UV parametrisation and the equal
+ *      mean of each triangle's best 4 views; the atlas and the weighting below are this library's own.
+ *      Deterministic: one thread per texel, the views in index order inside it, no atomics; nothing synchronises.  Everything is fp32,
+ *      not contracted, every operation in the written order; / and sqrt are correctly rounded (tests/texture_bake_oracle.py restates
+ *      the rule in numpy).
+ *      Atlas.  T = tex_size, a power of two, FP_TEXTURE_MIN_SIZE .. FP_TEXTURE_MAX_SIZE.  g = the smallest integer with g g >=
+ *      ceil(F / 2); cells of c x c texels, c = floor(T / g), in row-major order: cell k has its first texel at column (k mod g) c, row
+ *      floor(k / g) c, and holds face 2k (A) and face 2k + 1 (B).  c < 4 is refused.  With m = c - 3 and (i, j) = (column, row) of a
+ *      texel inside its cell, A has its corners 0, 1, 2 at (0,0), (m,0), (0,m) and owns the texels with i + j <= c - 2; B has them at
+ *      (c-1,c-1), (c-1-m,c-1), (c-1,c-1-m) and owns those with i + j >= c.  The anti-diagonal i + j = c - 1, the B half of a last odd
+ *      cell and every texel outside the g x g cells belong to no face: colour 0, used -1.
+ *      uv.  Face f has its own entries 3f, 3f + 1, 3f + 2 of d_uv (the uv_idx of fp_mesh_create is 0, 1, .. 3F - 1; the vertex count
+ *      does not change), at the texel CENTRES of its corners: (((float)column + 0.5) / (float)T, ((float)row + 0.5) / (float)T) with
+ *      atlas columns and rows, in the rasteriser's convention ("v already flipped" for fp_mesh_create): v T - 0.5 is the texture row,
+ *      rows top-down.  Both values and 1 - v are exact in fp32, so the v -> 1 - v of an OBJ file or of make_mesh_tensors round-trips bit
+ *      for bit.  Consequence: for a uv inside a face's uv triangle the rasteriser's bilinear fetch (x = u T - 0.5, floor, + 1) gives
+ *      non-zero weight to texels of that face alone - on an edge of the triangle the far neighbour's weight is exactly 0 - so nothing
+ *      bleeds between faces or wraps at the atlas border.  (The rasteriser interpolates uv itself in fp32; its rounding can put a uv a
+ *      few ulp outside, where a foreign texel's weight is of that order: below 1e-5 of a colour step.)
+ *      Point of an owned texel.  For A b1 = (float)i / (float)m, b2 = (float)j / (float)m; for B b1 = (float)(c-1-i) / (float)m,
+ *      b2 = (float)(c-1-j) / (float)m; b0 = (1 - b1) - b2.  If b0 < 0 (a ring texel beyond the hypotenuse): s = b1 + b2, b0 = 0,
+ *      b1 = b1 / s, b2 = b2 / s - the nearest edge region.  With P0, P1, P2 the face's vertices in its index order:
+ *      p = (b0 P0 + b1 P1) + b2 P2 per component.  Normal: e = P1 - P0, h = P2 - P0, n = (e.y h.z - e.z h.y, e.z h.x - e.x h.z,
+ *      e.x h.y - e.y h.x), divided by sqrt((n.x n.x + n.y n.y) + n.z n.z) (a degenerate face gives NaN: every view skips).
+ *      Views.  d_rgb (n_views,H,W,3) uint8, d_depth (n_views,H,W) fp32 metres, d_mask (n_views,H,W) uint8 or null, K and cam_in_ob as
+ *      for fp_tsdf_integrate (R, t: the float64 inverse cast to fp32).  Per view, in index order:
+ *        q_a = ((R[a][0] p.x + R[a][1] p.y) + R[a][2] p.z) + t[a];                    skip the view unless q.z >= 0.001
+ *        x = fx (q.x / q.z) + cx, y = fy (q.y / q.z) + cy (pixel centres at integers);  x0 = floor(x), y0 = floor(y)
+ *        skip unless 0 <= x0 < W - 1 and 0 <= y0 < H - 1                                (the bilinear footprint lies inside the image)
+ *        d = depth[floor(y + 0.5), floor(x + 0.5)];  skip unless d >= 0.001 and d < zfar, and, with a mask, mask there != 0
+ *        skip unless |d - q.z| <= depth_tol                                             (occluded, or not on the observed surface)
+ *        o_i = -((R[0][i] t[0] + R[1][i] t[1]) + R[2][i] t[2])                          (the camera centre, from the fp32 R, t)
+ *        w = o - p;  cosang = ((n.x w.x + n.y w.y) + n.z w.z) / sqrt((w.x w.x + w.y w.y) + w.z w.z);   skip unless cosang >= cos_min
+ *        sample, per channel: t00 = rgb[y0, x0], t10 = rgb[y0, x0 + 1], t01 = rgb[y0 + 1, x0], t11 = rgb[y0 + 1, x0 + 1] as float,
+ *        wx = x - x0, wy = y - y0, ta = t00 + wx (t10 - t00), tb = t01 + wx (t11 - t01), colour = ta + wy (tb - ta)
+ *      ("unless" so that a NaN skips.)  The top_n views with the largest cosang are kept, ordered by cosang descending; among equal
+ *      values the lower view index comes first and wins the last place.  used = the number kept.  With used > 0:
+ *      sw = sum of cosang, sc = sum of cosang colour, both added in that order starting from 0; the texel is sc / sw.  With used = 0:
+ *      (b0 C0 + b1 C1) + b2 C2 of the face's vertex colours as float, or 128 without vertex colours.  Each channel is stored as
+ *      floor(value + 0.5) clamped to 0 .. 255.
+ *      Outputs, device: d_texture (T,T,3) uint8, rows top-down; d_uv (3F,2) fp32; d_used (T,T) int8 or null.  n_views = 0 bakes the
+ *      vertex colours alone.  A face index outside 0 .. V-1 is found on the device and never followed: the face's texels are 128 with
+ *      used 0, and no error is reported (the call does not synchronise).
+ *      FP_EINVAL: a null ctx, d_pos, d_faces, K, cfg, d_texture or d_uv; null d_rgb, d_depth or cam_in_ob with n_views > 0; a
+ *      struct_size the library does not know; V or F < 1, F above FP_TEXTURE_MAX_FACES; tex_size not a power of two in range; c < 4
+ *      (the message names the tex_size that fits); top_n outside 1 .. FP_TEXTURE_MAX_TOP_N; n_views outside 0 .. FP_TSDF_MAX_VIEWS (the
+ *      view matrices travel as kernel arguments); H or W < 2 with views; depth_tol < 0, cos_min outside (0, 1], zfar not > 0 (infinity
+ *      is allowed), or one of them NaN; fx or fy not > 0; a view matrix that is not finite or whose last row is not 0 0 0 1.  All of
+ *      it is checked on the host before anything is queued. */
+#define FP_TEXTURE_MIN_SIZE 64
+#define FP_TEXTURE_MAX_SIZE 4096
+#define FP_TEXTURE_MAX_TOP_N 4         /* the reference's _CHOOSE_TOP_N */
+#define FP_TEXTURE_MAX_FACES (1 << 21) /* 1024 x 1024 cells of 4 texels at tex_size 4096 */
+typedef struct fp_texture_cfg {
+  size_t struct_size;      /* = sizeof(fp_texture_cfg) */
+  int tex_size, top_n;
+  float depth_tol /* metres */, cos_min, zfar;
+} fp_texture_cfg;
+int fp_texture_bake(fp_ctx *ctx, const float *d_pos, int V, const int32_t *d_faces, int F, const uint8_t *d_vertex_colors,
+                    const uint8_t *d_rgb, const float *d_depth, const uint8_t *d_mask, int n_views, int H, int W, const double *K,
+                    const double *cam_in_ob, const fp_texture_cfg *cfg, uint8_t *d_texture, float *d_uv, int8_t *d_used, void *stream);
+
 /* ---- building blocks exported for parity tests and profiling ---------------------------------- */
 /* fp16 NHWC implicit-GEMM convolution on MFMA: out = act(conv(in, w) + bias [+ res]).  w_packed is
  * [Cout][Kpad] fp16 with k = (ky*KW+kx)*Cin + ci, Kpad = roundup(KH*KW*Cin, 32), zero padded. */

@@ -1,12 +1,14 @@
 """A mesh from a folder of posed RGB-D reference views (the reference's model-free layout: rgb/, depth_enhanced/ or depth/, mask/,
 cam_in_ob/, K.txt), by TSDF fusion and marching tetrahedra on the GPU (foundationpose_amd.reconstruct).
 usage: python scripts/reconstruct_object.py DIR [--voxel 0.002] [--trunc T] [--min-weight 1] [--no-depth-filter] [--refine-poses]
-       [--max-vertices N | --simplify-cell C] [--min-component-fraction X] [--out DIR/model/model.obj]
+       [--max-vertices N | --simplify-cell C] [--min-component-fraction X] [--texture [SIZE]] [--out DIR/model/model.obj]
 The output format follows the extension: .obj or .ply.  --refine-poses aligns every view but the first to the geometry fused so far before the
 fusion (reconstruct.refine_view_poses) and also writes the poses it used to DIR/cam_in_ob_refined/NAME.txt.  --max-vertices N (8192: the
 rasteriser's on-chip vertex limit) or --simplify-cell C (metres) reduces the mesh by vertex clustering (Utils.simplify_mesh).  By default
 only the connected component with the most faces is kept; --min-component-fraction X (0 .. 1) keeps EVERY component with at least X of
-the largest one's faces (Utils.clean_mesh: an object of several parts)."""
+the largest one's faces (Utils.clean_mesh: an object of several parts).  --texture bakes a texture atlas from the views' rgb onto the
+finished mesh (Utils.bake_texture; SIZE: a power of two, 64 .. 4096, default: the smallest with cells of 8 texels) and writes
+model.obj with model.mtl and model.png beside it; OBJ only - a PLY holds one uv per vertex, the atlas three per face."""
 import argparse
 import os
 import sys
@@ -29,9 +31,12 @@ def main():
   ap.add_argument('--max-vertices', type=int, default=None)
   ap.add_argument('--simplify-cell', type=float, default=None)
   ap.add_argument('--min-component-fraction', type=float, default=None)
+  ap.add_argument('--texture', type=int, nargs='?', const=0, default=None, metavar='SIZE')
   ap.add_argument('--out', default=None)
   args = ap.parse_args()
   out = args.out or os.path.join(args.dir, 'model', 'model.obj')
+  if args.texture is not None and out.lower().endswith('.ply'):
+    ap.error('--texture writes an OBJ with its .mtl and .png: give --out a name ending in .obj')
   views = load_reference_views(args.dir)
   if args.refine_poses:
     poses, info = refine_view_poses(views, voxel_size=args.voxel, depth_filter=not args.no_depth_filter)
@@ -43,13 +48,15 @@ def main():
     views = dict(views, cam_in_obs=poses)
   mesh = reconstruct_object(views, voxel_size=args.voxel, trunc=args.trunc, min_weight=args.min_weight, depth_filter=not args.no_depth_filter,
                             max_vertices=args.max_vertices, simplify_cell=args.simplify_cell,
+                            texture=None if args.texture is None else (args.texture or True),
                             components='largest' if args.min_component_fraction is None else dict(keep='all', min_fraction=args.min_component_fraction))
   os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
   if out.lower().endswith('.ply'):
     mesh_io.save_ply(mesh, out)
   else:
     mesh_io.save_obj(mesh, out)
-  print(f'{out}: {len(mesh.vertices)} vertices, {len(mesh.faces)} faces')
+  tex = f', texture {mesh.visual.image.shape[1]} x {mesh.visual.image.shape[0]}' if args.texture is not None else ''
+  print(f'{out}: {len(mesh.vertices)} vertices, {len(mesh.faces)} faces{tex}')
 
 
 if __name__ == '__main__':
