@@ -1264,3 +1264,156 @@ def draw_posed_3d_box(K, img, ob_in_cam, bbox, line_color=(0, 255, 0), linewidth
   returned, as cv2.line does - main.py:68-69 relies on it."""
   return draw_poses(img, K, np.asarray(ob_in_cam, dtype=np.float64).reshape(1, 4, 4), bboxes=np.asarray(bbox, dtype=np.float64).reshape(2, 3), box=True,
                     axes=False, box_thickness=linewidth, colors=np.asarray(line_color, dtype=np.float64), out=img)
+
+
+# ---- distance between surfaces (fp_point_mesh_distance, fp_mesh_sample_surface, fp_distance_stats) -----------------------------------
+def _surface_on(mesh, vertices, faces, dev, what):
+  """(pos float32 (V,3), faces int32 (F,3)) on `dev` of mesh (an object with .vertices / .faces, or a (vertices, faces) tuple) or of the
+  two arrays.  Face arrays that live on the host are validated up front; device faces are checked by the kernels (a face with an index
+  outside [0, V) is never followed)."""
+  if mesh is not None:
+    vertices, faces = _mesh_parts(mesh)[:2]
+  if vertices is None or faces is None:
+    raise ValueError(f'{what} needs a mesh, or vertices and faces')
+  pos = torch.as_tensor(vertices).to(device=dev, dtype=torch.float).reshape(-1, 3).contiguous()
+  if not (torch.is_tensor(faces) and faces.is_cuda):
+    f = np.asarray(faces.cpu() if torch.is_tensor(faces) else faces)
+    if f.size and (not np.issubdtype(f.dtype, np.integer) or f.min() < 0 or f.max() >= len(pos)):
+      raise ValueError(f'{what}: faces must be integers in [0, {len(pos)})')
+  fc = _faces_on(faces, dev)
+  if len(pos) < 1 or len(fc) < 1:
+    raise ValueError(f'{what}: the mesh has {len(pos)} vertices and {len(fc)} faces (at least one of each)')
+  if len(fc) > _lib.FP_SURFDIST_MAX_FACES:
+    raise ValueError(f'{what}: {len(fc)} faces (at most {_lib.FP_SURFDIST_MAX_FACES})')
+  return pos, fc
+
+
+def _point_mesh_distance_on(pts, pos, fc, want_face=False, want_closest=False):
+  dev, n = pts.device, len(pts)
+  dist = torch.empty(n, dtype=torch.float, device=dev)
+  face = torch.empty(n, dtype=torch.int32, device=dev) if want_face else None
+  closest = torch.empty((n, 3), dtype=torch.float, device=dev) if want_closest else None
+  check(lib().fp_point_mesh_distance(_lib.Context.get(dev).handle, ptr(pts) if n else None, n, ptr(pos), len(pos), ptr(fc), len(fc),
+                                     ptr(dist) if n else None, ptr(face) if n else None, ptr(closest) if n else None, stream_ptr(dev)))
+  return dist, face, closest
+
+
+def point_mesh_distance(points, mesh=None, vertices=None, faces=None, return_face=False, return_closest=False):
+  """The exact distance from every point to the surface of a triangle mesh on the device (fp_point_mesh_distance): the minimum over ALL
+  faces of the point-to-triangle distance, in fp32 - not the distance to the nearest vertex or sample, which depends on the tessellation.
+
+  points (N,3); the mesh as `mesh` (an object with .vertices and .faces, or a (vertices, faces) tuple) or as `vertices` (V,3) and `faces`
+  (F,3).  numpy in -> numpy out, device tensor in -> device tensor out.  Returns dist (N,) float32 and, as asked, face (N,) int32 (the
+  nearest face; among faces at equal distance the lowest index) and closest (N,3) float32 (the nearest point on it).  A point with a
+  non-finite coordinate gets NaN, -1, NaN.  Brute force, N x F pair tests; with device tensors nothing
+  synchronises."""
+  dev = _device_of(points)
+  pts = torch.as_tensor(points).to(device=dev, dtype=torch.float).reshape(-1, 3).contiguous()
+  if len(pts) > _lib.FP_SURFDIST_MAX_POINTS:
+    raise ValueError(f'point_mesh_distance: {len(pts)} points (at most {_lib.FP_SURFDIST_MAX_POINTS})')
+  pos, fc = _surface_on(mesh, vertices, faces, dev, 'point_mesh_distance')
+  out = _point_mesh_distance_on(pts, pos, fc, return_face, return_closest)
+  out = [o for o in out if o is not None]
+  if not (torch.is_tensor(points) and points.is_cuda):
+    out = [o.cpu().numpy() for o in out]
+  return out[0] if len(out) == 1 else tuple(out)
+
+
+def _sample_surface_on(pos, fc, n, seed, want_face=False, want_bary=False, want_area_q=False):
+  dev = pos.device
+  if not 0 <= n <= _lib.FP_SURFDIST_MAX_SAMPLES:
+    raise ValueError(f'sample_surface: n {n} (0 .. {_lib.FP_SURFDIST_MAX_SAMPLES})')
+  pts = torch.empty((n, 3), dtype=torch.float, device=dev)
+  face = torch.empty(n, dtype=torch.int32, device=dev) if want_face else None
+  bary = torch.empty((n, 2), dtype=torch.float, device=dev) if want_bary else None
+  area_q = torch.empty(len(fc), dtype=torch.int64, device=dev) if want_area_q else None
+  check(lib().fp_mesh_sample_surface(_lib.Context.get(dev).handle, ptr(pos), len(pos), ptr(fc), len(fc), n, int(seed) & 0xffffffff,
+                                     ptr(pts) if n else None, ptr(face) if n else None, ptr(bary) if n else None, ptr(area_q), stream_ptr(dev)))
+  return pts, face, bary, area_q
+
+
+def sample_surface(mesh, n, seed=0, return_face=False, return_info=False):
+  """n points on the surface of a mesh, on the device (fp_mesh_sample_surface): area-weighted and stratified along the face order (every
+  face gets its area share of the samples to within one), a function of (mesh, n, seed) alone - the same bits on every run.
+
+  mesh: an object with .vertices and .faces, or a (vertices, faces) tuple, numpy or torch.  Returns points (n,3) float32 on the device of
+  the vertices (the current device for numpy) and, as asked, face (n,) int32 and info = {'bary': (n,2) float32 (u, v) with
+  p = a + u (b - a) + v (c - a), 'area_q': (F,) int64, the device's table of face areas in units of 2^-40 of the total}.  A mesh
+  without area raises.  The call synchronises once (the library reads the total area)."""
+  vertices = _mesh_parts(mesh)[0]
+  dev = _device_of(vertices)
+  pos, fc = _surface_on(mesh, None, None, dev, 'sample_surface')
+  pts, face, bary, area_q = _sample_surface_on(pos, fc, int(n), seed, return_face, return_info, return_info)
+  out = [pts] + ([face] if return_face else []) + ([dict(bary=bary, area_q=area_q)] if return_info else [])
+  return out[0] if len(out) == 1 else tuple(out)
+
+
+def _distance_stats_on(dist, taus):
+  """d_stats of fp_distance_stats as a device tensor of FP_SURFDIST_STATS_TAU0 + len(taus) doubles; nothing synchronises"""
+  dev = dist.device
+  th = np.ascontiguousarray(np.asarray(taus, dtype=np.float64).reshape(-1))
+  if len(th) > _lib.FP_SURFDIST_MAX_TAUS:
+    raise ValueError(f'at most {_lib.FP_SURFDIST_MAX_TAUS} thresholds ({len(th)} given)')
+  stats = torch.empty(_lib.FP_SURFDIST_STATS_TAU0 + len(th), dtype=torch.float64, device=dev)
+  check(lib().fp_distance_stats(_lib.Context.get(dev).handle, ptr(dist) if len(dist) else None, len(dist), ptr(th) if len(th) else None, len(th),
+                                ptr(stats), stream_ptr(dev)))
+  return stats
+
+
+def distance_stats(dist, taus=()):
+  """Statistics of a distance array on the device (fp_distance_stats), deterministic (no float atomics): {'n': finite entries,
+  'not_finite': the others (left out of everything), 'sum', 'sum_sq', 'max', 'within': [count of d <= tau per tau]}.  Synchronises."""
+  d = torch.as_tensor(dist).to(device=_device_of(dist), dtype=torch.float).reshape(-1).contiguous()
+  s = _distance_stats_on(d, taus).cpu().numpy()
+  L = _lib
+  return dict(n=int(s[L.FP_SURFDIST_STATS_COUNT]), not_finite=int(s[L.FP_SURFDIST_STATS_NOT_FINITE]), sum=float(s[L.FP_SURFDIST_STATS_SUM]),
+              sum_sq=float(s[L.FP_SURFDIST_STATS_SUM_SQ]), max=float(s[L.FP_SURFDIST_STATS_MAX]),
+              within=[int(x) for x in s[L.FP_SURFDIST_STATS_TAU0:]])
+
+
+def mesh_distance(mesh_a, mesh_b, n_samples=100_000, seed=0, taus=(0.001, 0.002, 0.005), use_vertices=True):
+  """How far apart two meshes are, measured on the device: Chamfer and Hausdorff distance and precision / recall / F-score.
+
+  The points of A are its vertices (use_vertices) plus n_samples surface samples (sample_surface, seeded); each is measured against B's
+  TRIANGLES with point_mesh_distance - exact point-to-surface distances, independent of B's tessellation - and the same from B to A.
+  Returns a dict:
+    'a_to_b', 'b_to_a'   {'n', 'mean', 'rms', 'max'} of the distances of that direction (n: the points with a finite distance)
+    'chamfer'            a_to_b.mean + b_to_a.mean: the SUM of the two mean UNSQUARED distances, in the meshes' unit.  (Conventions
+                         differ: some report the mean of the two, or sums of squared distances; convert with the four numbers above.)
+    'hausdorff'          the larger of the two maxima (over the measured points, so a lower bound of the true value that tightens with
+                         n_samples)
+    'taus'               the thresholds, and per threshold:
+    'precision'          the share of A's points within tau of B;  'recall': the share of B's points within tau of A
+    'fscore'             their harmonic mean, 0 when both are 0
+  With A a reconstruction and B the CAD model this is the usual reporting of model-free results.  Meshes: objects with .vertices and
+  .faces or (vertices, faces) tuples.  The statistics are deterministic sums (fp_distance_stats) and are read back together at the end;
+  sampling a mesh synchronises once more per mesh (the library reads its total area)."""
+  n_samples = int(n_samples)
+  if n_samples < 0 or (n_samples == 0 and not use_vertices):
+    raise ValueError('mesh_distance: nothing to measure (n_samples = 0 and use_vertices = False)')
+  dev = _device_of(_mesh_parts(mesh_a)[0])
+  surf = [_surface_on(m, None, None, dev, 'mesh_distance') for m in (mesh_a, mesh_b)]
+  pts = []
+  for k, (pos, fc) in enumerate(surf):
+    parts = [pos] if use_vertices else []
+    if n_samples:
+      parts.append(_sample_surface_on(pos, fc, n_samples, seed)[0])
+    pts.append(parts[0] if len(parts) == 1 else torch.cat(parts))
+  taus = [float(t) for t in taus]
+  stats = torch.stack([_distance_stats_on(_point_mesh_distance_on(pts[k], *surf[1 - k])[0], taus) for k in (0, 1)]).cpu().numpy()
+  L = _lib
+
+  def side(s):
+    n = s[L.FP_SURFDIST_STATS_COUNT]
+    return dict(n=int(n), mean=float(s[L.FP_SURFDIST_STATS_SUM] / n) if n else float('nan'),
+                rms=float(math.sqrt(s[L.FP_SURFDIST_STATS_SUM_SQ] / n)) if n else float('nan'), max=float(s[L.FP_SURFDIST_STATS_MAX]))
+
+  def share(s, k):
+    return float(s[L.FP_SURFDIST_STATS_TAU0 + k] / s[L.FP_SURFDIST_STATS_COUNT]) if s[L.FP_SURFDIST_STATS_COUNT] else 0.0
+
+  ab, ba = side(stats[0]), side(stats[1])
+  precision = [share(stats[0], k) for k in range(len(taus))]
+  recall = [share(stats[1], k) for k in range(len(taus))]
+  fscore = [2 * p * r / (p + r) if p + r > 0 else 0.0 for p, r in zip(precision, recall)]
+  return dict(a_to_b=ab, b_to_a=ba, chamfer=ab['mean'] + ba['mean'], hausdorff=max(ab['max'], ba['max']), taus=taus, precision=precision,
+              recall=recall, fscore=fscore)

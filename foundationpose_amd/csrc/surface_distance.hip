@@ -1,0 +1,479 @@
+// Distance between surfaces: the exact distance from points to a triangle mesh (fp_point_mesh_distance), its statistics
+// (fp_distance_stats) and a deterministic area-weighted surface sampler (fp_mesh_sample_surface).  The rules are stated in
+// include/foundationpose_amd.h and restated in float64 numpy in tests/surface_distance_oracle.py.  The nearest thing in the reference is
+// the cKDTree query of adds_err (src/Utils.py:242-253): point to VERTEX, so it depends on the tessellation; this is point to triangle.
+//
+// Brute force.  A workgroup owns (a tile of SD_TILE queries, a slice of the faces); each lane keeps SD_Q queries in registers.  The faces
+// are staged through LDS in chunks of SD_CHUNK precomputed records of five float4 (a, ab, ac, the dot products, their guarded inverses,
+// the unit normal, a flag; formed in double, rounded once): the per-face work is done once per chunk and the records are read back as broadcasts (every lane reads the same address).  A
+// lane keeps the smallest fp32 squared distance and its face per query (strictly smaller replaces, faces ascend: ties go to the lowest
+// index) and folds the pair into the query's 64-bit key (d2 bits << 32 | face) with one integer atomicMin: non-negative fp32 bit
+// patterns order as unsigned integers, so the key keeps the tie rule whatever the face slices are.  surfdist_finish_kernel unpacks the
+// keys and, for `closest`, evaluates the winning pair again with the same function.  No float atomics; 20 KiB of static LDS.
+#include "common.h"
+#include "device_util.h"
+
+namespace {
+
+typedef unsigned long long u64;
+
+constexpr int SD_THREADS = 256;
+constexpr int SD_Q = FP_SURFDIST_TILE / SD_THREADS;      // queries per lane
+constexpr int SD_TILE = FP_SURFDIST_TILE;                // queries per workgroup
+constexpr int SD_CHUNK = FP_SURFDIST_CHUNK;              // face records per LDS chunk (5 float4 each: 20 KiB)
+constexpr int SD_REC = 5;
+constexpr int SD_MIN_GROUPS = 1024;                      // the face slices bring the grid to about this many workgroups (256 CUs x 4)
+constexpr float SD_FLAG_TRIANGLE = 0.f, SD_FLAG_DEGENERATE = 1.f;
+static_assert(SD_TILE % SD_THREADS == 0 && SD_CHUNK % SD_THREADS == 0, "tile and chunk are multiples of the workgroup");
+
+struct FaceRec {
+  float ax, ay, az, flag;
+  float abx, aby, abz, e00;
+  float acx, acy, acz, e11;
+  float e01, inv_e00, inv_e11, inv_ebc;
+  float nx, ny, nz, det;
+};
+
+__device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz) { return fmaf(ax, bx, fmaf(ay, by, az * bz)); }
+__device__ __forceinline__ double dot3d(double ax, double ay, double az, double bx, double by, double bz) { return fma(ax, bx, fma(ay, by, az * bz)); }
+// (float)(1 / e), or 0 where e is 0 or that is not finite (a segment of zero length is its end point)
+__device__ __forceinline__ float guarded_inv(double e) {
+  const float r = (float)(1.0 / e);
+  return (e > 0.0 && r < __builtin_inff()) ? r : 0.f;
+}
+
+// The record of face f.  What belongs to the face alone is formed in DOUBLE from the fp32 positions and rounded once: the work is done
+// once per chunk, and the unit normal of a sliver - its cross product cancels - keeps full fp32 precision.  A face that is never
+// selected (an index outside [0, V), a non-finite vertex) has a = NaN: every d2 of it is NaN.
+__device__ __forceinline__ FaceRec face_record(const float *__restrict__ pos, int V, const int32_t *__restrict__ faces, int f) {
+  FaceRec r;
+  const int i0 = faces[(size_t)f * 3], i1 = faces[(size_t)f * 3 + 1], i2 = faces[(size_t)f * 3 + 2];
+  const bool in_range = (unsigned)i0 < (unsigned)V && (unsigned)i1 < (unsigned)V && (unsigned)i2 < (unsigned)V;
+  const size_t k0 = in_range ? (size_t)i0 * 3 : 0, k1 = in_range ? (size_t)i1 * 3 : 0, k2 = in_range ? (size_t)i2 * 3 : 0;
+  const float ax = pos[k0], ay = pos[k0 + 1], az = pos[k0 + 2];
+  const double abx = (double)pos[k1] - ax, aby = (double)pos[k1 + 1] - ay, abz = (double)pos[k1 + 2] - az;
+  const double acx = (double)pos[k2] - ax, acy = (double)pos[k2 + 1] - ay, acz = (double)pos[k2 + 2] - az;
+  const double bcx = acx - abx, bcy = acy - aby, bcz = acz - abz;
+  const double e00 = dot3d(abx, aby, abz, abx, aby, abz), e01 = dot3d(abx, aby, abz, acx, acy, acz), e11 = dot3d(acx, acy, acz, acx, acy, acz);
+  const double nx = aby * acz - abz * acy, ny = abz * acx - abx * acz, nz = abx * acy - aby * acx;
+  const double det = dot3d(nx, ny, nz, nx, ny, nz), inv_len = 1.0 / sqrt(det);
+  r.abx = (float)abx, r.aby = (float)aby, r.abz = (float)abz;
+  r.acx = (float)acx, r.acy = (float)acy, r.acz = (float)acz;
+  r.e00 = (float)e00, r.e01 = (float)e01, r.e11 = (float)e11, r.det = (float)det;
+  r.inv_e00 = guarded_inv(e00), r.inv_e11 = guarded_inv(e11), r.inv_ebc = guarded_inv(dot3d(bcx, bcy, bcz, bcx, bcy, bcz));
+  const bool triangle = det > 0.0 && inv_len < __builtin_inf() && r.det > 0.f;
+  r.nx = triangle ? (float)(nx * inv_len) : 0.f, r.ny = triangle ? (float)(ny * inv_len) : 0.f, r.nz = triangle ? (float)(nz * inv_len) : 0.f;
+  r.flag = triangle ? SD_FLAG_TRIANGLE : SD_FLAG_DEGENERATE;
+  const bool finite = abx - abx == 0.0 && aby - aby == 0.0 && abz - abz == 0.0 && acx - acx == 0.0 && acy - acy == 0.0 && acz - acz == 0.0 &&
+                      fabsf(ax) < __builtin_inff() && fabsf(ay) < __builtin_inff() && fabsf(az) < __builtin_inff();
+  const float bad = __builtin_nanf("");
+  const bool keep = in_range && finite;
+  r.ax = keep ? ax : bad, r.ay = keep ? ay : bad, r.az = keep ? az : bad;
+  return r;
+}
+
+// squared distance from the point at `ap` (relative to the segment's origin) to the segment o + t e, t in [0, 1]; (qx, qy, qz) = t e
+__device__ __forceinline__ float segment_d2(float apx, float apy, float apz, float ex, float ey, float ez, float inv_ee, float &qx, float &qy,
+                                            float &qz) {
+  const float t = fminf(fmaxf(dot3(apx, apy, apz, ex, ey, ez) * inv_ee, 0.f), 1.f);
+  qx = t * ex, qy = t * ey, qz = t * ez;
+  const float dx = apx - qx, dy = apy - qy, dz = apz - qz;
+  return fmaf(dx, dx, fmaf(dy, dy, dz * dz));
+}
+
+// The pair rule of the header.  (px, py, pz) the query; `degenerate`: the record's flag as the caller tests it; returns d2 and the
+// closest point RELATIVE TO a in (qx, qy, qz).
+__device__ __forceinline__ float pair_d2(const FaceRec &r, bool degenerate, float px, float py, float pz, float &qx, float &qy, float &qz) {
+  const float apx = px - r.ax, apy = py - r.ay, apz = pz - r.az;
+  if (degenerate) {
+    float best = segment_d2(apx, apy, apz, r.abx, r.aby, r.abz, r.inv_e00, qx, qy, qz);
+    float tx, ty, tz;
+    float d = segment_d2(apx, apy, apz, r.acx, r.acy, r.acz, r.inv_e11, tx, ty, tz);
+    if (d < best) best = d, qx = tx, qy = ty, qz = tz;
+    d = segment_d2(apx - r.abx, apy - r.aby, apz - r.abz, r.acx - r.abx, r.acy - r.aby, r.acz - r.abz, r.inv_ebc, tx, ty, tz);
+    if (d < best) best = d, qx = r.abx + tx, qy = r.aby + ty, qz = r.abz + tz;
+    return best;
+  }
+  // the six dot products, each from its own difference vector: nothing cancels against the distance from a to b or c
+  const float bpx = apx - r.abx, bpy = apy - r.aby, bpz = apz - r.abz, cpx = apx - r.acx, cpy = apy - r.acy, cpz = apz - r.acz;
+  const float d1 = dot3(r.abx, r.aby, r.abz, apx, apy, apz), d2 = dot3(r.acx, r.acy, r.acz, apx, apy, apz);
+  const float d3 = dot3(r.abx, r.aby, r.abz, bpx, bpy, bpz), d4 = dot3(r.acx, r.acy, r.acz, bpx, bpy, bpz);
+  const float d5 = dot3(r.abx, r.aby, r.abz, cpx, cpy, cpz), d6 = dot3(r.acx, r.acy, r.acz, cpx, cpy, cpz);
+  const float vc = fmaf(r.e00, d2, -(r.e01 * d1)), vb = fmaf(r.e11, d1, -(r.e01 * d2));
+  // the interior: the foot of the perpendicular, q = ap - h n with the unit normal n - (s, t) of a sliver would be ill-conditioned
+  const float h = dot3(r.nx, r.ny, r.nz, apx, apy, apz);
+  float dx = h * r.nx, dy = h * r.ny, dz = h * r.nz;
+  // edge bc: q = ab + w bc, from b along the edge itself.  va = d3 d6 - d5 d4 = det - vb - vc is tested by its sign alone:
+  // va <= 0  <=>  vb + vc >= det
+  const float bcx = r.acx - r.abx, bcy = r.acy - r.aby, bcz = r.acz - r.abz;
+  const float w = fminf(fmaxf(dot3(bcx, bcy, bcz, bpx, bpy, bpz) * r.inv_ebc, 0.f), 1.f);
+  bool inside = true, on_bc = false;
+  if (vb + vc >= r.det && d4 - d3 >= 0.f && d5 - d6 >= 0.f) on_bc = true, inside = false;
+  // the other five regions: q = s ab + t ac
+  float s = 0.f, t = 0.f;
+  if (vb <= 0.f && d2 >= 0.f && d6 <= 0.f) s = 0.f, t = d2 * r.inv_e11, inside = false, on_bc = false;  // edge ac
+  if (d6 >= 0.f && d5 <= d6) s = 0.f, t = 1.f, inside = false, on_bc = false;                          // vertex c
+  if (vc <= 0.f && d1 >= 0.f && d3 <= 0.f) s = d1 * r.inv_e00, t = 0.f, inside = false, on_bc = false;  // edge ab
+  if (d3 >= 0.f && d4 <= d3) s = 1.f, t = 0.f, inside = false, on_bc = false;                          // vertex b
+  if (d1 <= 0.f && d2 <= 0.f) s = 0.f, t = 0.f, inside = false, on_bc = false;                         // vertex a
+  const float ex = on_bc ? fmaf(w, bcx, r.abx) : fmaf(t, r.acx, s * r.abx);
+  const float ey = on_bc ? fmaf(w, bcy, r.aby) : fmaf(t, r.acy, s * r.aby);
+  const float ez = on_bc ? fmaf(w, bcz, r.abz) : fmaf(t, r.acz, s * r.abz);
+  qx = inside ? apx - dx : ex, qy = inside ? apy - dy : ey, qz = inside ? apz - dz : ez;
+  dx = inside ? dx : apx - ex, dy = inside ? dy : apy - ey, dz = inside ? dz : apz - ez;
+  return fmaf(dx, dx, fmaf(dy, dy, dz * dz));
+}
+
+__device__ __forceinline__ FaceRec load_record(const float4 *lds, int j) {
+  const float4 r0 = lds[j * SD_REC], r1 = lds[j * SD_REC + 1], r2 = lds[j * SD_REC + 2], r3 = lds[j * SD_REC + 3], r4 = lds[j * SD_REC + 4];
+  return FaceRec{r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w, r2.x, r2.y, r2.z, r2.w, r3.x, r3.y, r3.z, r3.w, r4.x, r4.y, r4.z, r4.w};
+}
+
+struct SurfDistArgs {
+  const float *pts;        // (n, 3)
+  const float *pos;        // (V, 3)
+  const int32_t *faces;    // (F, 3)
+  int n, V, F, chunks_per_slice;
+  u64 *keys;               // [n]: d2 bits << 32 | face, all ones before the launch
+};
+
+// grid (tiles of SD_TILE queries, face slices of chunks_per_slice chunks)
+__global__ __launch_bounds__(SD_THREADS) void surfdist_kernel(SurfDistArgs a) {
+  __shared__ float4 lds[SD_CHUNK * SD_REC];
+  const int tid = threadIdx.x;
+  const int q0 = blockIdx.x * SD_TILE;
+  float px[SD_Q], py[SD_Q], pz[SD_Q], best[SD_Q];
+  int bface[SD_Q];
+#pragma unroll
+  for (int q = 0; q < SD_Q; ++q) {
+    const int i = min(q0 + q * SD_THREADS + tid, a.n - 1);      // a query past n repeats the last one and is not written
+    px[q] = a.pts[(size_t)i * 3], py[q] = a.pts[(size_t)i * 3 + 1], pz[q] = a.pts[(size_t)i * 3 + 2];
+    best[q] = __builtin_inff(), bface[q] = -1;
+  }
+  const long long f_begin = (long long)blockIdx.y * a.chunks_per_slice * SD_CHUNK;
+  const int f_end = (int)min((long long)a.F, f_begin + (long long)a.chunks_per_slice * SD_CHUNK);
+  for (int c0 = (int)f_begin; c0 < f_end; c0 += SD_CHUNK) {
+    const int cnt = min(SD_CHUNK, f_end - c0);
+    __syncthreads();                      // the previous chunk has been read by every wave
+    for (int j = tid; j < cnt; j += SD_THREADS) {
+      const FaceRec r = face_record(a.pos, a.V, a.faces, c0 + j);
+      lds[j * SD_REC] = make_float4(r.ax, r.ay, r.az, r.flag);
+      lds[j * SD_REC + 1] = make_float4(r.abx, r.aby, r.abz, r.e00);
+      lds[j * SD_REC + 2] = make_float4(r.acx, r.acy, r.acz, r.e11);
+      lds[j * SD_REC + 3] = make_float4(r.e01, r.inv_e00, r.inv_e11, r.inv_ebc);
+      lds[j * SD_REC + 4] = make_float4(r.nx, r.ny, r.nz, r.det);
+    }
+    __syncthreads();
+    for (int j = 0; j < cnt; ++j) {
+      const FaceRec r = load_record(lds, j);
+      const bool degenerate = __builtin_amdgcn_readfirstlane(__float_as_int(r.flag)) != 0;      // the same in every lane: a scalar branch
+#pragma unroll
+      for (int q = 0; q < SD_Q; ++q) {
+        float qx, qy, qz;
+        const float d = pair_d2(r, degenerate, px[q], py[q], pz[q], qx, qy, qz);
+        if (d < best[q]) best[q] = d, bface[q] = c0 + j;      // NaN and +inf never pass: such a pair is never selected
+      }
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < SD_Q; ++q) {
+    const int i = q0 + q * SD_THREADS + tid;
+    if (i < a.n && bface[q] >= 0) atomicMin(a.keys + i, ((u64)__float_as_uint(best[q]) << 32) | (u64)(unsigned)bface[q]);
+  }
+}
+
+// one thread per query: the key unpacked; `closest` from the winning pair, evaluated by the same function
+__global__ __launch_bounds__(SD_THREADS) void surfdist_finish_kernel(SurfDistArgs a, float *dist, int32_t *face, float *closest) {
+  const int i = blockIdx.x * SD_THREADS + threadIdx.x;
+  if (i >= a.n) return;
+  const u64 key = a.keys[i];
+  const int f = (int)(unsigned)(key & 0xffffffffu);
+  const bool found = key != ~(u64)0;
+  const float nan = __builtin_nanf("");
+  dist[i] = found ? sqrtf(__uint_as_float((unsigned)(key >> 32))) : nan;
+  if (face) face[i] = found ? f : -1;
+  if (!closest) return;
+  float cx = nan, cy = nan, cz = nan;
+  if (found) {
+    const FaceRec r = face_record(a.pos, a.V, a.faces, f);
+    float qx, qy, qz;
+    (void)pair_d2(r, r.flag != SD_FLAG_TRIANGLE, a.pts[(size_t)i * 3], a.pts[(size_t)i * 3 + 1], a.pts[(size_t)i * 3 + 2], qx, qy, qz);
+    cx = r.ax + qx, cy = r.ay + qy, cz = r.az + qz;
+  }
+  closest[(size_t)i * 3] = cx, closest[(size_t)i * 3 + 1] = cy, closest[(size_t)i * 3 + 2] = cz;
+}
+
+// ---- statistics of a distance array ---------------------------------------------------------------------------------------------------
+constexpr int DS_THREADS = 256;
+constexpr int DS_ITEMS = 16;
+constexpr int DS_TILE = DS_THREADS * DS_ITEMS;           // entries per workgroup
+constexpr int DS_TERMS = FP_SURFDIST_STATS_TAU0 + FP_SURFDIST_MAX_TAUS;
+
+struct DistStatsArgs {
+  const float *dist;
+  int n, n_taus, n_tiles;
+  double taus[FP_SURFDIST_MAX_TAUS];
+  double *slab;            // [DS_TERMS][n_tiles]
+};
+
+// sum over the workgroup in a fixed order (butterfly within each wave, then the waves in order), valid in thread 0
+__device__ __forceinline__ double ds_block_sum(double v, double *red) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+  __syncthreads();                        // `red` of the previous sum has been read
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double s = 0.0;
+  if (threadIdx.x == 0)
+    for (int i = 0; i < DS_THREADS / 64; ++i) s += red[i];
+  return s;
+}
+
+__global__ __launch_bounds__(DS_THREADS) void dist_stats_kernel(DistStatsArgs a) {
+  __shared__ double red[DS_THREADS / 64];
+  double cnt = 0.0, bad = 0.0, s1 = 0.0, s2 = 0.0, mx = 0.0, le[FP_SURFDIST_MAX_TAUS];
+#pragma unroll
+  for (int t = 0; t < FP_SURFDIST_MAX_TAUS; ++t) le[t] = 0.0;
+#pragma unroll 4
+  for (int k = 0; k < DS_ITEMS; ++k) {
+    const long long i = (long long)blockIdx.x * DS_TILE + k * DS_THREADS + threadIdx.x;
+    if (i >= a.n) break;
+    const float f = a.dist[i];
+    if (!(fabsf(f) < __builtin_inff())) {
+      bad += 1.0;
+      continue;
+    }
+    const double d = (double)f;
+    cnt += 1.0, s1 += d, s2 = fma(d, d, s2), mx = fmax(mx, d);
+#pragma unroll
+    for (int t = 0; t < FP_SURFDIST_MAX_TAUS; ++t)
+      if (t < a.n_taus && d <= a.taus[t]) le[t] += 1.0;
+  }
+  double *slab = a.slab + blockIdx.x;
+  double v;
+  v = ds_block_sum(cnt, red);
+  if (threadIdx.x == 0) slab[(size_t)FP_SURFDIST_STATS_COUNT * a.n_tiles] = v;
+  v = ds_block_sum(s1, red);
+  if (threadIdx.x == 0) slab[(size_t)FP_SURFDIST_STATS_SUM * a.n_tiles] = v;
+  v = ds_block_sum(s2, red);
+  if (threadIdx.x == 0) slab[(size_t)FP_SURFDIST_STATS_SUM_SQ * a.n_tiles] = v;
+  v = ds_block_sum(bad, red);
+  if (threadIdx.x == 0) slab[(size_t)FP_SURFDIST_STATS_NOT_FINITE * a.n_tiles] = v;
+  mx = wave_max(mx);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int i = 1; i < DS_THREADS / 64; ++i) mx = fmax(mx, red[i]);
+    slab[(size_t)FP_SURFDIST_STATS_MAX * a.n_tiles] = fmax(mx, red[0]);
+  }
+#pragma unroll
+  for (int t = 0; t < FP_SURFDIST_MAX_TAUS; ++t) {
+    if (t >= a.n_taus) break;
+    v = ds_block_sum(le[t], red);
+    if (threadIdx.x == 0) slab[(size_t)(FP_SURFDIST_STATS_TAU0 + t) * a.n_tiles] = v;
+  }
+}
+
+// one thread per term: the tile partials in tile order (the maximum: in any order)
+__global__ __launch_bounds__(64) void dist_stats_finish_kernel(const double *__restrict__ slab, int n_tiles, int n_terms, double *stats) {
+  const int term = threadIdx.x;
+  if (term >= n_terms) return;
+  const double *p = slab + (size_t)term * n_tiles;
+  double s = 0.0;
+  if (term == FP_SURFDIST_STATS_MAX)
+    for (int t = 0; t < n_tiles; ++t) s = fmax(s, p[t]);
+  else
+    for (int t = 0; t < n_tiles; ++t) s += p[t];
+  stats[term] = s;
+}
+
+// ---- surface sampler -------------------------------------------------------------------------------------------------------------------
+constexpr int SS_THREADS = 256;
+constexpr int SS_TOTAL_THREADS = 1024;
+
+// area of face f in double from the fp32 positions: 0.5 |ab x ac|; 0 for a face that is not followed (index out of range) or not finite
+__global__ __launch_bounds__(SS_THREADS) void sample_area_kernel(const float *__restrict__ pos, int V, const int32_t *__restrict__ faces, int F,
+                                                                 double *area) {
+  const int f = blockIdx.x * SS_THREADS + threadIdx.x;
+  if (f >= F) return;
+  const int i0 = faces[(size_t)f * 3], i1 = faces[(size_t)f * 3 + 1], i2 = faces[(size_t)f * 3 + 2];
+  double A = 0.0;
+  if ((unsigned)i0 < (unsigned)V && (unsigned)i1 < (unsigned)V && (unsigned)i2 < (unsigned)V) {
+    const double ax = pos[(size_t)i0 * 3], ay = pos[(size_t)i0 * 3 + 1], az = pos[(size_t)i0 * 3 + 2];
+    const double ux = (double)pos[(size_t)i1 * 3] - ax, uy = (double)pos[(size_t)i1 * 3 + 1] - ay, uz = (double)pos[(size_t)i1 * 3 + 2] - az;
+    const double vx = (double)pos[(size_t)i2 * 3] - ax, vy = (double)pos[(size_t)i2 * 3 + 1] - ay, vz = (double)pos[(size_t)i2 * 3 + 2] - az;
+    const double nx = uy * vz - uz * vy, ny = uz * vx - ux * vz, nz = ux * vy - uy * vx;
+    A = 0.5 * sqrt(nx * nx + ny * ny + nz * nz);
+    if (!(A < __builtin_inf())) A = 0.0;
+  }
+  area[f] = A;
+}
+
+// one workgroup: total[0] = the sum of the areas (thread t adds faces t, t + 1024, ..; then a tree over the threads)
+__global__ __launch_bounds__(SS_TOTAL_THREADS) void sample_total_kernel(const double *__restrict__ area, int F, double *total) {
+  __shared__ double red[SS_TOTAL_THREADS];
+  double s = 0.0;
+  for (int f = threadIdx.x; f < F; f += SS_TOTAL_THREADS) s += area[f];
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = SS_TOTAL_THREADS / 2; o >= 1; o >>= 1) {
+    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) total[0] = red[0];
+}
+
+// area_q[f] = rint(area[f] / total 2^40) as int64 (0 when the total is not a positive finite number); prefix[F] = 0 closes the scan
+__global__ __launch_bounds__(SS_THREADS) void sample_quantise_kernel(const double *__restrict__ area, const double *__restrict__ total, int F,
+                                                                     u64 *prefix, long long *area_q) {
+  const int f = blockIdx.x * SS_THREADS + threadIdx.x;
+  if (f > F) return;
+  const double A = total[0];
+  long long q = 0;
+  if (f < F && A > 0.0 && A < __builtin_inf()) q = __double2ll_rn(area[f] / A * 1099511627776.0);
+  prefix[f] = (u64)q;
+  if (f < F && area_q) area_q[f] = q;
+}
+
+// Chris Wellons' lowbias32
+__device__ __forceinline__ unsigned lowbias32(unsigned x) {
+  x ^= x >> 16;
+  x *= 0x7feb352du;
+  x ^= x >> 15;
+  x *= 0x846ca68bu;
+  x ^= x >> 16;
+  return x;
+}
+
+// prefix: the exclusive sums of area_q, prefix[F] the total
+__global__ __launch_bounds__(SS_THREADS) void sample_points_kernel(const float *__restrict__ pos, const int32_t *__restrict__ faces, int F,
+                                                                   const u64 *__restrict__ prefix, int n, unsigned seed, float *points,
+                                                                   int32_t *face, float *bary) {
+  const int i = blockIdx.x * SS_THREADS + threadIdx.x;
+  if (i >= n) return;
+  const u64 total = prefix[F];
+  const u64 t = ((2ull * (u64)i + 1ull) * total) / (2ull * (u64)n);
+  // the first face whose inclusive sum prefix[f + 1] exceeds t (total > t: it exists whenever total > 0)
+  int lo = 0, hi = F - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (prefix[mid + 1] > t) hi = mid; else lo = mid + 1;
+  }
+  const int f = lo;
+  const unsigned base = lowbias32(seed);
+  unsigned ku = lowbias32(base + 2u * (unsigned)i) >> 8, kv = lowbias32(base + 2u * (unsigned)i + 1u) >> 8;
+  if (ku + kv >= (1u << 24)) ku = (1u << 24) - 1u - ku, kv = (1u << 24) - 1u - kv;      // u + v > 1: reflected, exactly
+  const float u = (float)(((double)ku + 0.5) * (1.0 / 16777216.0)), v = (float)(((double)kv + 0.5) * (1.0 / 16777216.0));
+  const int i0 = faces[(size_t)f * 3], i1 = faces[(size_t)f * 3 + 1], i2 = faces[(size_t)f * 3 + 2];      // in range: its area is > 0
+  const bool ok = total > 0;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    float p = __builtin_nanf("");
+    if (ok) {
+      const float a = pos[(size_t)i0 * 3 + k];
+      p = fmaf(v, pos[(size_t)i2 * 3 + k] - a, fmaf(u, pos[(size_t)i1 * 3 + k] - a, a));
+    }
+    points[(size_t)i * 3 + k] = p;
+  }
+  if (face) face[i] = ok ? f : -1;
+  if (bary) bary[(size_t)i * 2] = u, bary[(size_t)i * 2 + 1] = v;
+}
+
+}  // namespace
+
+extern "C" int fp_point_mesh_distance(fp_ctx *ctx, const float *d_points, int n, const float *d_pos, int V, const int32_t *d_faces, int F,
+                                      float *d_dist, int32_t *d_face, float *d_closest, void *stream) {
+  FP_REQUIRE(ctx && d_pos && d_faces, "fp_point_mesh_distance: null argument");
+  FP_REQUIRE(V >= 1 && F >= 1 && F <= FP_SURFDIST_MAX_FACES, "fp_point_mesh_distance: V %d, F %d (at least 1; at most %d faces)", V, F,
+             FP_SURFDIST_MAX_FACES);
+  FP_REQUIRE(n >= 0 && n <= FP_SURFDIST_MAX_POINTS, "fp_point_mesh_distance: n %d (0 .. %d)", n, FP_SURFDIST_MAX_POINTS);
+  if (n == 0) return FP_OK;
+  FP_REQUIRE(d_points && d_dist, "fp_point_mesh_distance: null d_points or d_dist with n %d", n);
+  hipStream_t s = (hipStream_t)stream;
+  FP_CHECK_HIP(hipSetDevice(ctx->device));
+  const size_t bytes = (size_t)n * sizeof(u64);
+  FP_TRY(fp_arena_ensure(ctx, bytes + 4096));
+  ArenaScope scope(ctx->arena);
+  u64 *keys = (u64 *)ctx->arena.take(bytes);
+  FP_REQUIRE(keys, "fp_point_mesh_distance: arena exhausted");
+  FP_CHECK_HIP(hipMemsetAsync(keys, 0xff, bytes, s));
+  const int tiles = (n + SD_TILE - 1) / SD_TILE, chunks = (F + SD_CHUNK - 1) / SD_CHUNK;
+  const int slices = std::min(chunks, std::max(1, (SD_MIN_GROUPS + tiles - 1) / tiles));
+  SurfDistArgs a{d_points, d_pos, d_faces, n, V, F, (chunks + slices - 1) / slices, keys};
+  const int slices_used = (chunks + a.chunks_per_slice - 1) / a.chunks_per_slice;
+  hipLaunchKernelGGL(surfdist_kernel, dim3((unsigned)tiles, (unsigned)slices_used), dim3(SD_THREADS), 0, s, a);
+  FP_CHECK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(surfdist_finish_kernel, dim3((unsigned)((n + SD_THREADS - 1) / SD_THREADS)), dim3(SD_THREADS), 0, s, a, d_dist, d_face,
+                     d_closest);
+  FP_CHECK_HIP(hipGetLastError());
+  return FP_OK;
+}
+
+extern "C" int fp_distance_stats(fp_ctx *ctx, const float *d_dist, int n, const double *h_taus, int n_taus, double *d_stats, void *stream) {
+  FP_REQUIRE(ctx && d_stats, "fp_distance_stats: null argument");
+  FP_REQUIRE(n >= 0 && n <= FP_SURFDIST_MAX_POINTS, "fp_distance_stats: n %d (0 .. %d)", n, FP_SURFDIST_MAX_POINTS);
+  FP_REQUIRE(d_dist || n == 0, "fp_distance_stats: d_dist null with n %d", n);
+  FP_REQUIRE(n_taus >= 0 && n_taus <= FP_SURFDIST_MAX_TAUS && (h_taus || n_taus == 0), "fp_distance_stats: n_taus %d (0 .. %d)", n_taus,
+             FP_SURFDIST_MAX_TAUS);
+  hipStream_t s = (hipStream_t)stream;
+  FP_CHECK_HIP(hipSetDevice(ctx->device));
+  const int n_terms = FP_SURFDIST_STATS_TAU0 + n_taus;
+  if (n == 0) {
+    FP_CHECK_HIP(hipMemsetAsync(d_stats, 0, (size_t)n_terms * sizeof(double), s));
+    return FP_OK;
+  }
+  DistStatsArgs a;
+  a.dist = d_dist, a.n = n, a.n_taus = n_taus, a.n_tiles = (n + DS_TILE - 1) / DS_TILE;
+  for (int t = 0; t < FP_SURFDIST_MAX_TAUS; ++t) a.taus[t] = t < n_taus ? h_taus[t] : 0.0;
+  const size_t bytes = (size_t)DS_TERMS * a.n_tiles * sizeof(double);
+  FP_TRY(fp_arena_ensure(ctx, bytes + 4096));
+  ArenaScope scope(ctx->arena);
+  a.slab = (double *)ctx->arena.take(bytes);
+  FP_REQUIRE(a.slab, "fp_distance_stats: arena exhausted");
+  hipLaunchKernelGGL(dist_stats_kernel, dim3((unsigned)a.n_tiles), dim3(DS_THREADS), 0, s, a);
+  FP_CHECK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(dist_stats_finish_kernel, dim3(1), dim3(64), 0, s, (const double *)a.slab, a.n_tiles, n_terms, d_stats);
+  FP_CHECK_HIP(hipGetLastError());
+  return FP_OK;
+}
+
+extern "C" int fp_mesh_sample_surface(fp_ctx *ctx, const float *d_pos, int V, const int32_t *d_faces, int F, int n, uint32_t seed,
+                                      float *d_points, int32_t *d_face, float *d_bary, int64_t *d_area_q, void *stream) {
+  FP_REQUIRE(ctx && d_pos && d_faces, "fp_mesh_sample_surface: null argument");
+  FP_REQUIRE(V >= 1 && F >= 1 && F <= FP_SURFDIST_MAX_FACES, "fp_mesh_sample_surface: V %d, F %d (at least 1; at most %d faces)", V, F,
+             FP_SURFDIST_MAX_FACES);
+  FP_REQUIRE(n >= 0 && n <= FP_SURFDIST_MAX_SAMPLES, "fp_mesh_sample_surface: n %d (0 .. %d)", n, FP_SURFDIST_MAX_SAMPLES);
+  FP_REQUIRE(d_points || n == 0, "fp_mesh_sample_surface: d_points null with n %d", n);
+  hipStream_t s = (hipStream_t)stream;
+  FP_CHECK_HIP(hipSetDevice(ctx->device));
+  const size_t area_bytes = (size_t)F * sizeof(double), prefix_bytes = ((size_t)F + 1) * sizeof(u64);
+  const size_t sums_bytes = scan_sums_words((long long)F + 1) * sizeof(u64);
+  FP_TRY(fp_arena_ensure(ctx, area_bytes + prefix_bytes + sums_bytes + 256 + 5 * 256 + 4096));
+  ArenaScope scope(ctx->arena);
+  double *area = (double *)ctx->arena.take(area_bytes);
+  double *total = (double *)ctx->arena.take(256);
+  u64 *prefix = (u64 *)ctx->arena.take(prefix_bytes);
+  u64 *sums = (u64 *)ctx->arena.take(sums_bytes);
+  FP_REQUIRE(area && total && prefix && sums, "fp_mesh_sample_surface: arena exhausted");
+  const unsigned fb = (unsigned)((F + SS_THREADS - 1) / SS_THREADS);
+  hipLaunchKernelGGL(sample_area_kernel, dim3(fb), dim3(SS_THREADS), 0, s, d_pos, V, d_faces, F, area);
+  FP_CHECK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(sample_total_kernel, dim3(1), dim3(SS_TOTAL_THREADS), 0, s, (const double *)area, F, total);
+  FP_CHECK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(sample_quantise_kernel, dim3((unsigned)((F + 1 + SS_THREADS - 1) / SS_THREADS)), dim3(SS_THREADS), 0, s,
+                     (const double *)area, (const double *)total, F, prefix, (long long *)d_area_q);
+  FP_CHECK_HIP(hipGetLastError());
+  // the one synchronisation: a mesh without area cannot be sampled, and the caller is told so
+  double h_total = 0.0;
+  FP_CHECK_HIP(hipMemcpyAsync(&h_total, total, sizeof(double), hipMemcpyDeviceToHost, s));
+  FP_CHECK_HIP(hipStreamSynchronize(s));
+  FP_REQUIRE(h_total > 0.0 && h_total < __builtin_inf(), "fp_mesh_sample_surface: the mesh's total area is %g (it must be positive and finite)",
+             h_total);
+  if (n == 0) return FP_OK;
+  FP_TRY(scan_exclusive(prefix, (long long)F + 1, sums, s));
+  hipLaunchKernelGGL(sample_points_kernel, dim3((unsigned)((n + SS_THREADS - 1) / SS_THREADS)), dim3(SS_THREADS), 0, s, d_pos, d_faces, F,
+                     (const u64 *)prefix, n, (unsigned)seed, d_points, d_face, d_bary);
+  FP_CHECK_HIP(hipGetLastError());
+  return FP_OK;
+}

@@ -773,6 +773,88 @@ int fp_texture_bake(fp_ctx *ctx, const float *d_pos, int V, const int32_t *d_fac
                     const uint8_t *d_rgb, const float *d_depth, const uint8_t *d_mask, int n_views, int H, int W, const double *K,
                     const double *cam_in_ob, const fp_texture_cfg *cfg, uint8_t *d_texture, float *d_uv, int8_t *d_used, void *stream);
 
+/* ---- distance between surfaces: the exact distance from points to a triangle mesh, a deterministic surface sampler and the
+ *      statistics Chamfer, Hausdorff and F-score are made of (csrc/surface_distance.hip).  The reference has no such function; the
+ *      nearest is the cKDTree query of adds_err (src/Utils.py:242-253), which is point to VERTEX and so depends on the tessellation.
+ *      tests/surface_distance_oracle.py restates the rules below in float64 numpy. */
+#define FP_SURFDIST_MAX_POINTS (1 << 24)
+#define FP_SURFDIST_MAX_FACES (1 << 23)
+#define FP_SURFDIST_MAX_TAUS 8
+#define FP_SURFDIST_MAX_SAMPLES (1 << 22)
+#define FP_SURFDIST_TILE 1024   /* queries of one workgroup */
+#define FP_SURFDIST_CHUNK 256   /* face records of one LDS chunk */
+/* Nearest triangle of a mesh for n query points, by brute force over ALL F faces.  d_points (n,3), d_pos (V,3) float32, d_faces (F,3)
+ * int32, device.  d_dist (n) float32; d_face (n) int32 or null; d_closest (n,3) float32 or null: the nearest point on that face.
+ *   Per face, once, in DOUBLE from the fp32 positions and rounded to fp32 once: ab = b - a, ac = c - a, e00 = ab.ab, e01 = ab.ac,
+ * e11 = ac.ac, n = ab x ac, det = n.n, the unit normal nu = n / sqrt(det), and inv(x) = 1 / x where x > 0 and the fp32 value is finite,
+ * else 0, of e00, e11 and ebc = bc.bc (bc = ac - ab).  (The cross product of a sliver cancels; in double its unit normal keeps full fp32
+ * precision.)
+ *   Per pair (point p, face a b c), fp32, nothing contracted, fma(x, y, z) where written; dot(u, w) = fma(u.x, w.x, fma(u.y, w.y,
+ * u.z w.z)).  Everything is relative to a: ap = p - a, bp = ap - ab, cp = ap - ac, and the six dot products of the region
+ * classification, each from its own difference vector so that nothing cancels against the size of the face: d1 = dot(ab, ap),
+ * d2 = dot(ac, ap), d3 = dot(ab, bp), d4 = dot(ac, bp), d5 = dot(ab, cp), d6 = dot(ac, cp); vc = fma(e00, d2, -(e01 d1)),
+ * vb = fma(e11, d1, -(e01 d2)).  The closest point relative to a is q of the FIRST region that applies, of seven:
+ *     vertex a   d1 <= 0 and d2 <= 0                                   q = 0
+ *     vertex b   d3 >= 0 and d4 <= d3                                  q = ab
+ *     edge ab    vc <= 0 and d1 >= 0 and d3 <= 0                       q = s ab, s = d1 inv(e00)
+ *     vertex c   d6 >= 0 and d5 <= d6                                  q = ac
+ *     edge ac    vb <= 0 and d2 >= 0 and d6 <= 0                       q = t ac, t = d2 inv(e11)
+ *     edge bc    vb + vc >= det and d4 - d3 >= 0 and d5 - d6 >= 0      q = fma(w, bc, ab), bc = ac - ab in fp32,
+ *                                                                      w = min(max(dot(bc, bp) inv(ebc), 0), 1)
+ *     interior   otherwise                                             q = ap - h nu, h = dot(nu, ap): the foot of the perpendicular
+ * (vertices and the edges ab, ac: q = fma(t, ac, s ab) per component with the (s, t) shown, 0 or 1 otherwise.)  (dx, dy, dz) = ap - q -
+ * for the interior h nu itself - and d2 = fma(dx, dx, fma(dy, dy, dz dz)): the difference form of fp_pose_errors, so a point that is a
+ * vertex of the face gives exactly 0.  closest = a + q.  Against float64 the distance is off by at most 1 x 2^-24 x (the diagonal of the
+ * bounding box of points and mesh) on the shapes of tests/test_gpu_surface_distance.py, slivers included.
+ *   Degenerate faces.  A face with det = 0 - its cross product is exactly zero: collinear or coincident vertices - (or with a det below
+ * the smallest fp32 number) is the minimum over its three segments (a, ab), (a, ac), (b, bc) in that order, a later one replacing an
+ * earlier one only when strictly smaller: with o the segment's origin and e its direction, u = p - o (for b: bp),
+ * t = min(max(dot(u, e) inv(dot(e, e)), 0), 1), q = t e, d2 of u - q as above.  A segment of zero length has inv = 0: it is its end
+ * point.  No NaN comes of it.
+ *   Over the faces.  The smallest fp32 d2 wins; equal values go to the LOWEST face index; dist = sqrtf(d2).  The result of a point is a
+ * function of that point and the mesh alone, bit for bit: it does not depend on the batch, the query's index, how the faces are divided
+ * among the workgroups, or the run.  (Each workgroup folds its candidates into a 64-bit key, d2's bits << 32 | face, with an integer
+ * atomicMin: non-negative fp32 bit patterns order as unsigned integers.  No float atomics.)
+ *   Bad values.  A pair whose d2 is NaN or infinite is never selected: a face with a non-finite vertex is never selected, and a query
+ * with a non-finite coordinate, like one for which no face is left, gets dist = NaN,
+ * face = -1, closest = NaN.  A face index outside [0, V) is found on the device and that face is never followed or selected; no error
+ * is reported (the call does not synchronise).
+ *   Work: n F pair tests, about 0.4 M of them per microsecond on an MI355X (README.md) - no spatial cull.  The context's arena holds the n
+ * keys (8 n bytes).  n = 0 succeeds and writes nothing.  FP_EINVAL: a null ctx, d_pos or d_faces; d_points or d_dist null with n > 0;
+ * V < 1; F < 1 (F = 0 included) or above FP_SURFDIST_MAX_FACES; n < 0 or above FP_SURFDIST_MAX_POINTS. */
+int fp_point_mesh_distance(fp_ctx *ctx, const float *d_points, int n, const float *d_pos, int V, const int32_t *d_faces, int F,
+                           float *d_dist, int32_t *d_face, float *d_closest, void *stream);
+
+#define FP_SURFDIST_STATS_COUNT 0        /* entries of d_stats: the number of finite entries of d_dist */
+#define FP_SURFDIST_STATS_SUM 1          /* their sum */
+#define FP_SURFDIST_STATS_SUM_SQ 2       /* the sum of their squares */
+#define FP_SURFDIST_STATS_MAX 3          /* the largest (0 when there is none; distances are >= 0) */
+#define FP_SURFDIST_STATS_NOT_FINITE 4   /* the number of entries that are NaN or infinite: they are left out of everything else */
+#define FP_SURFDIST_STATS_TAU0 5         /* [5 + k]: the number of finite entries with (double)d <= h_taus[k] */
+/* Statistics of n distances, as FP_SURFDIST_STATS_TAU0 + n_taus doubles in d_stats (device).  d_dist (n) float32, device; h_taus
+ * (n_taus <= FP_SURFDIST_MAX_TAUS) float64, host, read before the call returns.  Every entry is widened to double first; the sums are
+ * double sums of per-workgroup partials that a finishing launch adds in tile order - no float atomics - so the same input gives the same
+ * bits on every run; the counts and the maximum are exact.  Nothing synchronises.  n = 0 gives zeros.  FP_EINVAL: a null ctx or d_stats,
+ * d_dist null with n > 0, n outside 0 .. FP_SURFDIST_MAX_POINTS, n_taus outside 0 .. FP_SURFDIST_MAX_TAUS, h_taus null with n_taus > 0. */
+int fp_distance_stats(fp_ctx *ctx, const float *d_dist, int n, const double *h_taus, int n_taus, double *d_stats, void *stream);
+
+/* n points on the surface of a mesh, area-weighted, stratified along the face order, a function of (mesh, n, seed) alone.
+ *   Face choice, exact.  area_f = 0.5 |ab x ac| in double from the fp32 positions (edge differences, cross product and square root in
+ * double; 0 for a face with an index outside [0, V) or a non-finite area), A = their double sum, area_q[f] = rint(area_f / A 2^40) as
+ * int64: units of 2^-40 A, so the integer total A_q is 2^40 to within F / 2, and integer prefix sums are exact in any order.  Sample i
+ * of n targets t_i = ((2 i + 1) A_q) div (2 n) in unsigned 64-bit integers and lands on the first face whose INCLUSIVE prefix sum of
+ * area_q exceeds t_i: every face gets its share n area_q[f] / A_q of the samples to within one.
+ *   Barycentrics.  h = lowbias32 (Chris Wellons' 32-bit integer hash: x ^= x >> 16, x *= 0x7feb352d, x ^= x >> 15, x *= 0x846ca68b,
+ * x ^= x >> 16, in uint32); ku = h(h(seed) + 2 i) >> 8, kv = h(h(seed) + 2 i + 1) >> 8 (uint32 sums); u, v = (k + 0.5) / 2^24,
+ * reflected when u + v > 1, which is done exactly on the integers: if ku + kv >= 2^24 then ku = 2^24 - 1 - ku, kv = 2^24 - 1 - kv.
+ * u and v are (k + 0.5) 2^-24 in double rounded to fp32 once; p = fma(v, c - a, fma(u, b - a, a)) per component in fp32.
+ *   Outputs, device: d_points (n,3) float32; d_face (n) int32 or null; d_bary (n,2) float32 (u, v) or null; d_area_q (F) int64 or null
+ * (written for n = 0 too).  SYNCHRONISES the stream once, to read A: FP_EINVAL for a mesh whose total area is zero or not finite,
+ * and for a null ctx, d_pos or d_faces, d_points null with n > 0, V or F < 1, F above FP_SURFDIST_MAX_FACES, n outside
+ * 0 .. FP_SURFDIST_MAX_SAMPLES. */
+int fp_mesh_sample_surface(fp_ctx *ctx, const float *d_pos, int V, const int32_t *d_faces, int F, int n, uint32_t seed, float *d_points,
+                           int32_t *d_face, float *d_bary, int64_t *d_area_q, void *stream);
+
 /* ---- building blocks exported for parity tests and profiling ---------------------------------- */
 /* fp16 NHWC implicit-GEMM convolution on MFMA: out = act(conv(in, w) + bias [+ res]).  w_packed is
  * [Cout][Kpad] fp16 with k = (ky*KW+kx)*Cin + ci, Kpad = roundup(KH*KW*Cin, 32), zero padded. */

@@ -2,14 +2,18 @@
 cam_in_ob/, K.txt), by TSDF fusion and marching tetrahedra on the GPU (foundationpose_amd.reconstruct).
 usage: python scripts/reconstruct_object.py DIR [--voxel 0.002] [--trunc T] [--min-weight 1] [--no-depth-filter] [--refine-poses]
        [--max-vertices N | --simplify-cell C] [--min-component-fraction X] [--texture [SIZE]] [--out DIR/model/model.obj]
+       [--compare-to MODEL]
 The output format follows the extension: .obj or .ply.  --refine-poses aligns every view but the first to the geometry fused so far before the
 fusion (reconstruct.refine_view_poses) and also writes the poses it used to DIR/cam_in_ob_refined/NAME.txt.  --max-vertices N (8192: the
 rasteriser's on-chip vertex limit) or --simplify-cell C (metres) reduces the mesh by vertex clustering (Utils.simplify_mesh).  By default
 only the connected component with the most faces is kept; --min-component-fraction X (0 .. 1) keeps EVERY component with at least X of
 the largest one's faces (Utils.clean_mesh: an object of several parts).  --texture bakes a texture atlas from the views' rgb onto the
 finished mesh (Utils.bake_texture; SIZE: a power of two, 64 .. 4096, default: the smallest with cells of 8 texels) and writes
-model.obj with model.mtl and model.png beside it; OBJ only - a PLY holds one uv per vertex, the atlas three per face."""
+model.obj with model.mtl and model.png beside it; OBJ only - a PLY holds one uv per vertex, the atlas three per face.  --compare-to MODEL
+(OBJ or PLY, e.g. the CAD model, in the frame and unit of the views' poses) adds one JSON line: the Chamfer and Hausdorff distance and
+precision / recall / F-score of the written model against MODEL (Utils.mesh_distance; scripts/mesh_distance.py has more options)."""
 import argparse
+import json
 import os
 import sys
 
@@ -33,6 +37,7 @@ def main():
   ap.add_argument('--min-component-fraction', type=float, default=None)
   ap.add_argument('--texture', type=int, nargs='?', const=0, default=None, metavar='SIZE')
   ap.add_argument('--out', default=None)
+  ap.add_argument('--compare-to', default=None, metavar='MODEL')
   args = ap.parse_args()
   out = args.out or os.path.join(args.dir, 'model', 'model.obj')
   if args.texture is not None and out.lower().endswith('.ply'):
@@ -57,6 +62,9 @@ def main():
     mesh_io.save_obj(mesh, out)
   tex = f', texture {mesh.visual.image.shape[1]} x {mesh.visual.image.shape[0]}' if args.texture is not None else ''
   print(f'{out}: {len(mesh.vertices)} vertices, {len(mesh.faces)} faces{tex}')
+  if args.compare_to is not None:
+    from foundationpose_amd import Utils as U
+    print(json.dumps(dict(compared_to=args.compare_to, **U.mesh_distance(mesh, mesh_io.load_mesh(args.compare_to)))))
 
 
 if __name__ == '__main__':
