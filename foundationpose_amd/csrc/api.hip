@@ -18,7 +18,7 @@ void fp_set_error(const char *fmt, ...) {
 }
 
 extern "C" const char *fp_last_error(void) { return g_err; }
-extern "C" int fp_version(void) { return 101; }
+extern "C" int fp_version(void) { return 102; }
 
 // ---- context / arena ---------------------------------------------------------------------------
 size_t fp_arena_bytes_for(int n_hyp) {
@@ -59,12 +59,9 @@ int fp_arena_ensure(fp_ctx *ctx, size_t bytes) {
   return FP_OK;
 }
 
-extern int g_halo_tail, g_halo_npw, g_halo_form;
-static int g_one_chain = 0;      // FP_ONE_CHAIN=1: the two sides of encodeA as one chain (A/B timing; identical results)
-
 int fp_set_kernel_attributes(fp_ctx *ctx) {
   std::vector<KernelLds> v;
-  conv_kernel_lds(v), conv_halo_kernel_lds(v), conv_s1b_kernel_lds(v), conv_small_kernel_lds(v), conv_wino_kernel_lds(v), conv_s2_kernel_lds(v), stem_kernel_lds(v);
+  conv_kernel_lds(v), conv_halo_kernel_lds(v), conv_s1b_kernel_lds(v), conv_small_kernel_lds(v), conv_s2_kernel_lds(v), stem_kernel_lds(v);
   tok_gemm_kernel_lds(v), tok_qkv_kernel_lds(v), head_mlp_kernel_lds(v), attn_kernel_lds(v), raster_kernel_lds(v);
   FP_CHECK_HIP(hipSetDevice(ctx->device));
   for (const KernelLds &k : v)
@@ -74,10 +71,6 @@ int fp_set_kernel_attributes(fp_ctx *ctx) {
 
 extern "C" int fp_ctx_create(int device, fp_ctx **out) {
   FP_REQUIRE(out, "fp_ctx_create: null out");
-  if (const char *e = getenv("FP_HALO_TAIL")) g_halo_tail = atoi(e) != 0;
-  if (const char *e = getenv("FP_ONE_CHAIN")) g_one_chain = atoi(e) != 0;
-  if (const char *e = getenv("FP_HALO_NPW")) g_halo_npw = atoi(e) == 2 ? 2 : 4;
-  if (const char *e = getenv("FP_HALO_FORM")) g_halo_form = atoi(e);
   int n = 0;
   FP_CHECK_HIP(hipGetDeviceCount(&n));
   FP_REQUIRE(device >= 0 && device < n, "fp_ctx_create: device %d out of range (%d visible)", device, n);
@@ -768,7 +761,10 @@ static size_t pass_arena_bytes(int N, size_t render_scratch) {
 // One run of like objects in a batch that the trunk does not cut in two by hypotheses: the rendered side (crop window -> rasteriser ->
 // encodeA) and the observed side (crop window -> observed crop -> encodeA) are two chains on two streams up to the channel concat
 // (run_trunk): side B does not wait for the rasteriser.  Bit-identical to one chain.
-static bool two_side_chains(int n_runs, int N) { return n_runs == 1 && N < fp_trunk_split_min() && !g_one_chain; }
+static bool two_side_chains(int n_runs, int N) {
+  static const bool one_chain = fp_env_int("FP_ONE_CHAIN", 0) != 0;      // FP_ONE_CHAIN=1: the two sides of encodeA as one chain (A/B timing; identical results)
+  return n_runs == 1 && N < fp_trunk_split_min() && !one_chain;
+}
 
 struct NetInputOpts {
   int mode;                  // of the observed crop (fp_crop_observed)
@@ -868,7 +864,7 @@ static int refine_predict_impl(fp_ctx *ctx, const fp_net *net, const fp_object_b
   FP_TRY(fp_arena_ensure(ctx, pass_arena_bytes(N, rs_total) + (size_t)n_obj * ((size_t)4 << 20)));
   ArenaScope scope(ctx->arena);
   const size_t img = (size_t)160 * 160 * 8;
-  static const bool no_shared = getenv("FP_NO_SHARED_B") != nullptr;       // A/B knob: ignore FP_REFINE_SHARED_TRANSLATION (identical results)
+  static const bool no_shared = fp_env_set("FP_NO_SHARED_B");       // A/B knob: ignore FP_REFINE_SHARED_TRANSLATION (identical results)
   TAKE(tf, float, (size_t)N * 9);
   TAKE(bbox, float, (size_t)N * 4);
   TAKE(trans, float, (size_t)N * 3);
@@ -878,7 +874,7 @@ static int refine_predict_impl(fp_ctx *ctx, const fp_net *net, const fp_object_b
   TAKE(rscratch, char, rs_total);                              // reused by every iteration
   // One run of like objects (one camera, one mesh, one diameter): the heads' token means, the pose update and the crop windows of
   // the next iteration are ONE launch behind the heads (refine_tail_kernel) instead of four.  Bit-identical (FP_TAIL_SPLIT=1: the four).
-  static const bool tail_split = getenv("FP_TAIL_SPLIT") != nullptr;
+  static const bool tail_split = fp_env_set("FP_TAIL_SPLIT");
   const bool fused_tail = n_runs == 1 && !tail_split && fp_hyp_chunk(N) == N;
   // FP_REFINE_SHARED_TRANSLATION: in the FIRST iteration every hypothesis of an object has the crop window of the object's first one, so
   // side B - the observed crop and its way through encodeA - is ONE image per object: cropped and encoded once on the side stream
@@ -1445,25 +1441,6 @@ extern "C" int fp_conv3x3_band_f16(fp_ctx *ctx, const void *d_in, int Nimg, int 
   FP_TRY(s2_pack_weights(a.w, C, C, a.Kpad, pk, (hipStream_t)stream, 2, 1));
   a.wpk = pk;
   return launch_conv_s1b(ctx, a, (hipStream_t)stream);
-}
-
-extern "C" int fp_conv3x3_wino_f16(fp_ctx *ctx, const void *d_in, int Nimg, int HW, int Cin, int Cout, const float *h_weight, const float *d_bias,
-                                   const void *d_res, int relu, void *d_out, void *stream) {
-  FP_REQUIRE(ctx && d_in && h_weight && d_bias && d_out && Nimg >= 0, "fp_conv3x3_wino_f16: bad argument");
-  FP_REQUIRE((HW == 40 || HW == 20) && Cin % 32 == 0 && Cin >= 64 && Cout % 64 == 0, "fp_conv3x3_wino_f16: HW=%d Cin=%d Cout=%d unsupported", HW, Cin, Cout);
-  ConvArgs a = conv_args(d_in, nullptr, d_bias, d_res, d_out, Nimg, HW, HW, Cin, Cout, 3, 3, 1, 1, relu);      // (the weights: a.wwino below)
-  if (a.M == 0) return FP_OK;
-  std::vector<f16> hu(wino_packed_halfs(Cout, Cin));
-  wino_pack_weights(h_weight, nullptr, Cout, Cin, hu.data());
-  const size_t bytes = hu.size() * sizeof(f16);
-  FP_TRY(fp_arena_ensure(ctx, bytes + 4096));
-  ArenaScope scope(ctx->arena);
-  f16 *pk = (f16 *)ctx->arena.take(bytes);
-  if (!pk) return FP_ENOMEM;
-  if (hipMemcpyAsync(pk, hu.data(), bytes, hipMemcpyHostToDevice, (hipStream_t)stream) != hipSuccess) return FP_EHIP;
-  a.wwino = pk;
-  FP_TRY(launch_conv_wino(ctx, a, (hipStream_t)stream));
-  return hipStreamSynchronize((hipStream_t)stream) == hipSuccess ? FP_OK : FP_EHIP;      // (hu is a host temporary)
 }
 
 extern "C" int fp_attention_f16(fp_ctx *ctx, const void *d_qk, const void *d_vt, int B, int T, void *d_out, void *stream) {

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 #include <string>
 #include <vector>
@@ -17,6 +18,15 @@ typedef float floatx16 __attribute__((ext_vector_type(16)));
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 void fp_set_error(const char *fmt, ...);
+
+// The FP_* environment knobs: every one is read through these two, into a function-local static at its first use,
+// i.e. once per process.  fp_env_int: the variable's integer value, `fallback` when it is unset; fp_env_set: whether it is set at
+// all, whatever its value (FP_TAIL_SPLIT=0 switches the knob ON).
+inline long long fp_env_int(const char *name, long long fallback) {
+  const char *e = getenv(name);
+  return e ? atoll(e) : fallback;
+}
+inline bool fp_env_set(const char *name) { return getenv(name) != nullptr; }
 
 #define FP_CHECK_HIP(expr)                                                                   \
   do {                                                                                       \
@@ -248,7 +258,6 @@ void conv_kernel_lds(std::vector<KernelLds> &v);        // conv.hip
 void conv_halo_kernel_lds(std::vector<KernelLds> &v);   // conv_halo.hip
 void conv_s1b_kernel_lds(std::vector<KernelLds> &v);    // conv_s1b.hip
 void conv_small_kernel_lds(std::vector<KernelLds> &v);  // conv_small.hip
-void conv_wino_kernel_lds(std::vector<KernelLds> &v);   // conv_wino.hip
 void conv_s2_kernel_lds(std::vector<KernelLds> &v);     // conv_s2.hip
 void stem_kernel_lds(std::vector<KernelLds> &v);        // stem.hip
 void tok_gemm_kernel_lds(std::vector<KernelLds> &v);    // tok_gemm.hip
@@ -276,8 +285,6 @@ struct ConvArgs {
   int ksplit = 0;
   // 3x3 stride-2 layers: the weights in the fragment order of conv_s2.hip (s2_pack_weights); nullptr: the implicit-GEMM kernel runs
   const f16 *wpk = nullptr;
-  // 3x3 stride-1 layers: the Winograd F(2,3)-along-rows image of the fp32 weights (conv_wino.hip: wino_pack_weights); nullptr: the direct kernels run
-  const f16 *wwino = nullptr;
   // 3x3 stride-1 layers: the weights in the fragment order of conv_small.hip (small_pack_weights); nullptr: that form is not used
   const f16 *wsm = nullptr;
   // hypotheses of the network pass this launch belongs to (0: a stand-alone call): the few-image form is chosen by it, so that the two sides
@@ -302,13 +309,6 @@ bool conv_small_use(const ConvArgs &a, int num_cu);       // ... and the caller 
 size_t small_packed_halfs(int Cout, int Cin);
 int small_pack_weights(const f16 *d_w, int Cout, int Cin, int Kpad, f16 *d_out, hipStream_t s);
 int launch_conv_small(fp_ctx *ctx, const ConvArgs &a, hipStream_t s);
-
-// conv_wino.hip: Winograd F(2,3) along rows for the 3x3 stride-1 layers (its own numerics: transformed weights and inputs in fp16)
-bool conv_wino_supported(const ConvArgs &a);
-size_t wino_packed_halfs(int Cout, int Cin);
-void wino_pack_weights(const float *w_oihw, const float *scale_per_cout, int Cout, int Cin, f16 *out_host);
-int launch_conv_wino(fp_ctx *ctx, const ConvArgs &a, hipStream_t s);
-int fp_wino_mode();            // conv.hip: FP_WINO (0: off, the default - measured slower or equal, profiles/r05_experiments.md; 1: every supported 3x3 stride-1 launch; 2: the 512-channel layers)
 
 // Column of token t inside the transposed V image [b][4][128][416].  Within each group of 16 tokens the order is
 // {0-3, 8-11, 4-7, 12-15}: the 8 keys that one lane half of the attention kernel's P^T operand carries (the S^T

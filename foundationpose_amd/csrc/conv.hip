@@ -98,9 +98,6 @@ __device__ __forceinline__ void igemm2_tile(const ConvArgs &p, const f16 *__rest
     f16 *xs = smem + buf * (XH + WH), *ws = xs + XH;
     if (d < NT) {
       const int q = d;
-#ifdef IGEMM_SKIP_A
-      if (kt > 1) return;      // timing experiment only (wrong results): no activation DMA after the first two stages
-#endif
       if (lin) {
         glds16(p.in + kt * C2_BK, xlin[q], xs + (q * 4 + wave) * 512);
         return;
@@ -121,9 +118,6 @@ __device__ __forceinline__ void igemm2_tile(const ConvArgs &p, const f16 *__rest
       glds16(src, xs + (q * 4 + wave) * 512);
     } else {
       const int q = d - NT;
-#ifdef IGEMM_SKIP_W
-      if (kt > 1) return;      // timing experiment only (wrong results): no weight DMA after the first two stages
-#endif
       glds16(wbase + (size_t)(q * 64) * p.Kpad + (size_t)kt * C2_BK, woff, ws + (q * 4 + wave) * 512);
     }
   };
@@ -503,11 +497,6 @@ int launch_conv_halo(fp_ctx *ctx, const ConvArgs &a, hipStream_t s);
 bool stem_supported(const ConvArgs &a);                     // stem.hip
 int launch_stem(fp_ctx *ctx, const ConvArgs &a, hipStream_t s);
 
-int fp_wino_mode() {
-  static const int m = getenv("FP_WINO") ? atoi(getenv("FP_WINO")) : 0;
-  return m;
-}
-
 int launch_conv(fp_ctx *ctx, const ConvArgs &a, hipStream_t s) {
   FP_REQUIRE(a.Cin == 8 || a.Cin % 32 == 0, "conv: Cin=%d must be 8 or a multiple of 32", a.Cin);
   FP_REQUIRE(a.Cout % 64 == 0, "conv: Cout=%d must be a multiple of 64", a.Cout);
@@ -521,10 +510,8 @@ int launch_conv(fp_ctx *ctx, const ConvArgs &a, hipStream_t s) {
   const char *cls = halo ? "conv3x3_halo" : (a.KW == 3) ? "conv3x3_s2" : (a.KW == 7 ? "conv7x7" : "linear");
   ProfScope ps(ctx, s, cls, flops);
   if (!(a.splitk && a.ksplit > 1) && conv_small_use(a, ctx->num_cu)) return launch_conv_small(ctx, a, s);      // a few images: conv_small.hip
-  if (halo && fp_wino_mode() != 0 && (fp_wino_mode() != 2 || a.Cin == 512) && (fp_wino_mode() != 3 || a.Cin >= 256) && conv_wino_supported(a))
-    return launch_conv_wino(ctx, a, s);      // (2: the 512-channel layers only; 3: from 256 channels on)
   {
-    static const int band = getenv("FP_C128_BAND") ? atoi(getenv("FP_C128_BAND")) : 1;   // conv_s1b.hip (bit-identical to the halo kernel); 0: off, 2: also the 256 -> 256 layers
+    static const int band = fp_env_int("FP_C128_BAND", 1);   // conv_s1b.hip (bit-identical to the halo kernel); 0: off, 2: also the 256 -> 256 layers
     // ... from the batch size on at which the general kernel needs more than one round of its 512-pixel tiles (82 images on 256 CUs): below,
     // one round of those is faster (32 hypotheses per GPU: 6.67 against 6.79 ms per step; 63: 10.24 against 10.13)
     if (band != 0 && (a.Cin == 128 || band == 2) && (long long)a.M > (long long)ctx->num_cu * 512 && s1b_supported(a)) return launch_conv_s1b(ctx, a, s);

@@ -7,9 +7,7 @@
 //   * brings the input rows it needs ONCE into LDS (the "halo band") and feeds all 9 taps from it: a tap shift is just a
 //     different LDS address per lane (+-1 pixel, +-1 row; taps outside the image select a zero chunk),
 //   * streams the 3 taps of one kernel row of weights at a time (128 co x 32 ci x 3 = 24 KB, double buffered) by LDS-DMA.
-// conv3x3_halo_dma_kernel: 8 waves, 512 px, band by LDS-DMA (double buffered), v_mfma_f32_32x32x16_f16.  The diagnostic forms
-// (the earlier register-staged kernel that carries the in-kernel cycle stamps, the persistent-workgroup experiment) live in
-// diag/conv_halo_diag.inc and are compiled only by `make -B EXTRA=-DHALO_STAMP` (never shipped); identical results.
+// conv3x3_halo_dma_kernel: 8 waves, 512 px, band by LDS-DMA (double buffered), v_mfma_f32_32x32x16_f16.
 // Epilogue: accumulators start at the bias; residual (staged through LDS) + ReLU (+ positional embedding) in fp32, one
 // rounding to fp16, LDS transpose, 16-byte row-contiguous NHWC stores.
 #include "common.h"
@@ -20,11 +18,9 @@
 #define HL_BM 128
 #define HL_CK 32
 #define HL_SLD 136  // halfs per staged output row (128 + 8 pad) -> 272 B
-#define HL_PS 40    // halfs per halo pixel (32 channels + 8 pad = 80 B): conflict-free ds_read_b128 AND every tap
-                    // shift / k-step is a compile-time immediate offset from ONE base register per pixel tile
 
 #ifdef HALO_STAMP
-// diagnostic build only (make STAMP=1): per-wave cycle sums of [wait + barrier] and [group body], see scripts/halo_stamps.py
+// diagnostic build only (make -B EXTRA=-DHALO_STAMP): per-wave cycle sums of [wait + barrier] and [group body], see scripts/halo_stamps.py
 __device__ unsigned long long g_halo_stamps[4096 * 8 * 8];
 extern "C" __attribute__((visibility("default"))) int fp_dbg_halo_stamps(unsigned long long *host, int clear) {
   if (host) (void)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_halo_stamps), sizeof(g_halo_stamps));
@@ -46,14 +42,8 @@ struct IC {
 
 // LDS-DMA (glds16) and the counted waits in front of the barriers below: device_util.h
 
-#ifdef HALO_STAMP      // diagnostic builds only: the register-staged form that carries the in-kernel cycle stamps
-#define HALO_DIAG_SECTION 1
-#include "diag/conv_halo_diag.inc"
-#undef HALO_DIAG_SECTION
-#endif
-
 // ------------------------------------------------------------------------------------------------------------------------
-// DEFAULT FORM.  8-wave tile (512 px x 128 co, one workgroup per CU) with the halo band staged by LDS-DMA as well, double
+// 8-wave tile (512 px x 128 co, one workgroup per CU) with the halo band staged by LDS-DMA as well, double
 // buffered:
 //   * halo pixels are 64 bytes, UNPADDED (so a DMA instruction's 64 lanes x 16 B land linearly: 16 pixels x 4 channel groups);
 //     bank conflicts are avoided by an XOR swizzle instead: pixel P keeps channel group c at position c ^ ((P >> 2) & 3),
@@ -81,7 +71,7 @@ struct HaloCfgD {
   static constexpr int LDS_BYTES = 2 * (LDS_HALFS_MAIN > LDS_HALFS_EPI ? LDS_HALFS_MAIN : LDS_HALFS_EPI);
 };
 
-// Epilogue of a tile (both schedules): residual (staged through LDS) + ReLU (+ positional embedding) in fp32, one rounding to fp16,
+// Epilogue of a tile: residual (staged through LDS) + ReLU (+ positional embedding) in fp32, one rounding to fp16,
 // LDS transpose, 16-byte row-contiguous NHWC stores.
 template <int NT, bool RES, bool POST>
 __device__ __forceinline__ void halo_epilogue(const ConvArgs &p, const int m0, const int c0, f16 *lds, floatx16 (&acc)[2][NT]) {
@@ -89,7 +79,6 @@ __device__ __forceinline__ void halo_epilogue(const ConvArgs &p, const int m0, c
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / NPW, wn = wave % NPW;
   const int lr = lane & 31, lh = lane >> 5;
-  // ---------------- epilogue (as in halo_tile) ----------------
   f16 *stage = lds;   // [TM px][HL_SLD]
   constexpr int NRES = TM * 16 / NTH;
   u32x4 rv[NRES];
@@ -242,7 +231,7 @@ __device__ __forceinline__ void halo_tile_dma(const ConvArgs &p, const int m0, c
     const unsigned off = (unsigned)(gp * p.Cin + cc * HL_CK + c * 8) * 2u;
     glds16(p.in, off, lds + hb * C::HBUF_HALFS + (h * 8 + wave) * 512);
   };
-  // ---- weights (as in halo_tile): row (g%8)*16 + lane/4 -> (row>>2)&3 = (lane>>4)&3
+  // ---- weights: row (g%8)*16 + lane/4 -> (row>>2)&3 = (lane>>4)&3
   const unsigned woff = (unsigned)(((wave * 16 + (lane >> 2)) * p.Kpad + (((lane & 3) ^ ((lane >> 4) & 3)) * 8)) * 2);
   auto wstage = [&](int cc, int ky, int buf, auto q0c, auto q1c) __attribute__((always_inline)) {
     constexpr int Q0 = decltype(q0c)::value, Q1 = decltype(q1c)::value;
@@ -305,7 +294,7 @@ __device__ __forceinline__ void halo_tile_dma(const ConvArgs &p, const int m0, c
       }
       const bool more_w = ncc < nchunk, more_h = (ky == 0) && (cc + 1 < nchunk);
       const f16 *wb = wbuf + buf * C::WBUF_HALFS;
-      unsigned vm[(NT + 2) / 3];           // keep the border selects inside the loop (see halo_tile)
+      unsigned vm[(NT + 2) / 3];           // keep the per-tap border selects INSIDE the loop: hoisted, their results would not fit the register file
 #pragma unroll
       for (int t = 0; t < (NT + 2) / 3; ++t) {
         vm[t] = vmp[t];
@@ -394,12 +383,6 @@ __device__ __forceinline__ void halo_tile_dma(const ConvArgs &p, const int m0, c
   })
 }
 
-#ifdef HALO_STAMP      // diagnostic builds only: the persistent-workgroup form (FP_HALO_PERSIST=1)
-#define HALO_DIAG_SECTION 2
-#include "diag/conv_halo_diag.inc"
-#undef HALO_DIAG_SECTION
-#endif
-
 // Grid = n_main workgroups of 512 px x 128 co (whole rounds), then the rest of the pixels as tiles of nt_tail x 128 px (halo_plan):
 // what is less than a round of 512-pixel tiles is cut so that it fills the chip once.  A pixel's arithmetic does not depend on its tile.
 template <int W, bool RES, bool POST>
@@ -407,7 +390,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_halo_dma_kernel(ConvArgs p, in
   extern __shared__ __attribute__((aligned(16))) f16 lds[];
   constexpr int TMM = 512;
   const int n_ct = p.Cout / HL_BM;
-  // tile0: logical tiles before it were done by the persistent launch (0 when this launch is the whole layer)
+  // tile0: the logical tile at which this launch starts (0: the launch is the whole layer, as launch_halo_dma always makes it)
   if ((int)blockIdx.x < n_main) {
     const int L = tile0 + xcd_remap(blockIdx.x, n_main);
     halo_tile_dma<W, 4, RES, POST>(p, (L / n_ct) * TMM, (L % n_ct) * HL_BM, lds);
@@ -470,10 +453,11 @@ bool conv_halo_supported(const ConvArgs &a) {
          a.Cout % HL_BM == 0 && a.out_mode == 0 && a.Kpad == 9 * a.Cin && a.out_ld % 8 == 0 && a.coff_hi % 8 == 0;
 }
 
-int g_halo_tail = 1;   // FP_HALO_TAIL=0 disables the tail split (A/B timing only; results are identical)
-int g_halo_form = 0;   // diagnostic builds only, FP_HALO_FORM: 0 = band by LDS-DMA, 8 waves (default); 1 = band through registers, FP_HALO_NPW x 2 waves
-                       // (A/B timing; identical results: same MFMA shape and accumulation order)
-int g_halo_npw = 4;    // diagnostic builds: FP_HALO_NPW=2 selects the 4-wave / 2-workgroups-per-CU form (A/B timing only; results are identical)
+// FP_HALO_TAIL=0 disables the tail split of halo_split and halo_plan (A/B timing only; results are identical)
+static bool halo_tail_on() {
+  static const bool on = fp_env_int("FP_HALO_TAIL", 1) != 0;
+  return on;
+}
 
 // main/tail split: whole rounds of `slots` main tiles stay; the remainder is cut in four when that shortens the last round
 // (a quarter tile costs ~0.35 of a main tile: less operand reuse), i.e. when the remainder fills < ~70 % of a round.
@@ -481,7 +465,7 @@ void halo_split(int n_tiles, int slots, int *n_main, int *n_tail4) {
   const int rem = n_tiles % slots;
   *n_main = n_tiles;
   *n_tail4 = 0;
-  if (!g_halo_tail || rem == 0) return;
+  if (!halo_tail_on() || rem == 0) return;
   if (n_tiles < slots) {
     // less than one round (tracking; a rank's shard of an 8-way job: 32 hypotheses = 100 tiles at C = 512): the launch lasts as
     // long as ONE workgroup, so quarter tiles (4 x the workgroups, ~0.35 x the time each) win as long as they fit two rounds
@@ -512,11 +496,11 @@ void halo_plan(int M, int n_ct, int slots, int *n_main, int *nt_tail, int *n_tai
   *nt_tail = 4;
   *n_tail = 0;
   if (rem == 0) return;
-  if (!g_halo_tail) {                                   // FP_HALO_TAIL=0: 512-pixel tiles only
+  if (!halo_tail_on()) {                                 // FP_HALO_TAIL=0: 512-pixel tiles only
     *n_tail = ((rem + 3) / 4) * n_ct;
     return;
   }
-  static const int force_nt = getenv("FP_HALO_NT") ? atoi(getenv("FP_HALO_NT")) : 0;      // experiments: tiles of this many x 128 pixels for whatever is not a whole round
+  static const int force_nt = fp_env_int("FP_HALO_NT", 0);      // experiments: tiles of this many x 128 pixels for whatever is not a whole round
   if (force_nt >= 1 && force_nt <= 4) {
     *nt_tail = force_nt;
     *n_tail = ((rem + force_nt - 1) / force_nt) * n_ct;
@@ -533,12 +517,6 @@ void halo_plan(int M, int n_ct, int slots, int *n_main, int *nt_tail, int *n_tai
     }
   }
 }
-
-#ifdef HALO_STAMP      // diagnostic builds only: entry points and launchers of the forms above
-#define HALO_DIAG_SECTION 3
-#include "diag/conv_halo_diag.inc"
-#undef HALO_DIAG_SECTION
-#endif
 
 template <int W>
 static void halo_lds_all(std::vector<KernelLds> &v) {
@@ -558,12 +536,8 @@ static int launch_halo_dma(fp_ctx *ctx, const ConvArgs &a, hipStream_t s) {
   const int slots = ctx->num_cu;
   int n_main, nt_tail, n_tail;
   halo_plan(a.M, a.Cout / HL_BM, slots, &n_main, &nt_tail, &n_tail);
-  int tile0 = 0;
-#ifdef HALO_STAMP
-  FP_TRY((diag_launch_persist<W, RES, POST>(a, slots, C::LDS_BYTES, &n_main, &tile0, s)));
-#endif
   if (n_main + n_tail > 0)
-    hipLaunchKernelGGL((conv3x3_halo_dma_kernel<W, RES, POST>), dim3(n_main + n_tail), dim3(512), C::LDS_BYTES, s, a, n_main, tile0, nt_tail);
+    hipLaunchKernelGGL((conv3x3_halo_dma_kernel<W, RES, POST>), dim3(n_main + n_tail), dim3(512), C::LDS_BYTES, s, a, n_main, 0, nt_tail);
   FP_CHECK_HIP(hipGetLastError());
   return FP_OK;
 }
@@ -596,10 +570,10 @@ int conv_halo_ksplit(const ConvArgs &a, int num_cu) {
   if (!conv_halo_supported(a)) return 0;
   const int n_q = ((a.M + 127) / 128) * (a.Cout / HL_BM), nchunk = a.Cin / HL_CK;
   if (n_q * 4 > num_cu) return 0;
-  static const int k_max = getenv("FP_KSPLIT_MAX") ? atoi(getenv("FP_KSPLIT_MAX")) : 8;
+  static const int k_max = fp_env_int("FP_KSPLIT_MAX", 8);
   // from 256 input channels on: with the four chunks of a 128-channel layer two shares + the finishing launch take longer than the one
   // launch (one-hypothesis step 2.17 -> 2.12 ms, four hypotheses 2.74 -> 2.56 without them; FP_KSPLIT_MIN_CHUNKS=0: split those too)
-  static const int min_chunks = getenv("FP_KSPLIT_MIN_CHUNKS") ? atoi(getenv("FP_KSPLIT_MIN_CHUNKS")) : 8;
+  static const int min_chunks = fp_env_int("FP_KSPLIT_MIN_CHUNKS", 8);
   if (nchunk < min_chunks) return 0;
   int k = k_max;
   while (k > 1 && (nchunk % k != 0 || nchunk / k < 2 || n_q * k > num_cu)) k >>= 1;
@@ -613,11 +587,5 @@ int launch_conv_halo(fp_ctx *ctx, const ConvArgs &a, hipStream_t s) {
     FP_REQUIRE((a.Cin / HL_CK) % a.ksplit == 0 && a.out_ld % 4 == 0 && a.coff_hi % 4 == 0, "conv3x3 split-K: %d shares do not divide %d chunks", a.ksplit, a.Cin / HL_CK);
     return a.W == 40 ? launch_halo_splitk<40>(a, s) : launch_halo_splitk<20>(a, s);
   }
-#ifdef HALO_STAMP
-  if (g_halo_form != 0) {
-    if (g_halo_npw == 2) return a.W == 40 ? launch_halo_flags<40, 2>(a, s) : launch_halo_flags<20, 2>(a, s);
-    return a.W == 40 ? launch_halo_flags<40, 4>(a, s) : launch_halo_flags<20, 4>(a, s);
-  }
-#endif
   return a.W == 40 ? launch_halo_dma_flags<40>(ctx, a, s) : launch_halo_dma_flags<20>(ctx, a, s);
 }

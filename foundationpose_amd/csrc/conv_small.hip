@@ -200,8 +200,8 @@ int small_pack_weights(const f16 *d_w, int Cout, int Cin, int Kpad, f16 *d_out, 
 // of one or two hypotheses, and stand-alone launches of at most FP_SMALL_MAX_WG workgroups (default 2 per CU), when the caller holds the
 // packed weights (ConvArgs::wsm).  FP_SMALL=0: off (A/B timing).
 bool conv_small_shape(const ConvArgs &a, int num_cu) {
-  static const int on = getenv("FP_SMALL") ? atoi(getenv("FP_SMALL")) : 1;
-  static const int max_wg = getenv("FP_SMALL_MAX_WG") ? atoi(getenv("FP_SMALL_MAX_WG")) : 0;
+  static const int on = fp_env_int("FP_SMALL", 1);
+  static const int max_wg = fp_env_int("FP_SMALL_MAX_WG", 0);
   if (!on) return false;
   const bool s1 = a.stride == 1 && a.Ho == a.H && a.Wo == a.W && ((a.W == 40 && (a.Cin == 128 || a.Cin == 256)) || (a.W == 20 && a.Cin == 512));
   const bool s2 = a.stride == 2 && ((a.W == 40 && a.Ho == 20 && a.Wo == 20 && a.Cin == 256) ||   // the 256 -> 512 stride-2 layer between the two halves of encodeAB

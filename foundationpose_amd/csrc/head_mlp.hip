@@ -551,7 +551,7 @@ int launch_head_mlp(fp_ctx *ctx, const HeadMlpArgs &a, hipStream_t s) {
   if (a.M == 0) return FP_OK;
   FP_REQUIRE((double)a.M * 1024.0 < 4294967296.0, "head_mlp: M=%d too large for 32-bit lane offsets", a.M);
   ProfScope ps(ctx, s, "linear", 3.0 * 2.0 * (double)a.M * 512.0 * 512.0);
-  static const bool form64 = getenv("FP_HEADMLP64") != nullptr;       // A/B knob: the 64-token form (two resident tiles)
+  static const bool form64 = fp_env_set("FP_HEADMLP64");       // A/B knob: the 64-token form (two resident tiles)
   // 1 .. 4 hypotheses (tracking): the 64-token form.  Every workgroup streams all 1.5 MB of weights whatever its tile holds, so a launch
   // of a handful of workgroups lasts one workgroup's life: 26.8 us for seven 64-token tiles against 38.5 for four 128-token ones at one
   // hypothesis.  (Its own size class, like split-K in the 3x3 kernel: the two forms differ in the last bits, see the 128-token form's header.)

@@ -12,7 +12,6 @@
 struct ConvW {
   f16 *w = nullptr;
   f16 *wpk = nullptr;     // 3x3 stride-2 layers: the same weights in the fragment order of conv_s2.hip
-  f16 *wwino = nullptr;   // 3x3 stride-1 layers from 128 channels on: the Winograd image of the fp32 weights (conv_wino.hip)
   f16 *wsm = nullptr;     // 3x3 stride-1 layers with 128 / 256 / 512 input channels: fragment order of conv_small.hip (launches of a few images)
   float *bias = nullptr;
   int Cin = 0, Cout = 0, K = 1, Kpad = 0, stride = 1;
@@ -50,7 +49,7 @@ struct fp_net {
 
 // Hypotheses per network pass: the whole batch.  FP_CHUNK=n (environment, experiments only) splits it.
 int fp_hyp_chunk(int n_total) {
-  static int env = getenv("FP_CHUNK") ? atoi(getenv("FP_CHUNK")) : -1;
+  static int env = fp_env_int("FP_CHUNK", -1);
   int ch = env >= 0 ? env : 0;
   if (ch <= 0 || ch > n_total) ch = n_total;
   return ch;
@@ -59,8 +58,8 @@ int fp_hyp_chunk(int n_total) {
 int fp_trunk_split_min() {
   // from 48 hypotheses on (round 4, refine x5 + score of one object: 40 hypotheses 6.55 ms as one batch / 7.08 split, 48: 7.82 / 7.55, 56: 8.87 / 8.17,
   // 63: 9.85 / 9.23, 64: 9.95 / 9.32, 96: 13.97 / 13.71; scripts/bench_nhyp.py): below, the halves' tiles get too small
-  static const int n_min = getenv("FP_TRUNK_MIN") ? atoi(getenv("FP_TRUNK_MIN")) : 48;
-  static const int n_streams = getenv("FP_TRUNK_STREAMS") ? atoi(getenv("FP_TRUNK_STREAMS")) : 2;
+  static const int n_min = fp_env_int("FP_TRUNK_MIN", 48);
+  static const int n_streams = fp_env_int("FP_TRUNK_STREAMS", 2);
   return n_streams < 2 ? 0x7fffffff : n_min;
 }
 
@@ -144,12 +143,6 @@ int make_conv(fp_net *net, const SD &sd, const std::string &wkey, const std::str
   out->stride = stride;
   FP_TRY(upload(net, hw, &out->w));
   FP_TRY(upload(net, hb, &out->bias));
-  if (K == 3 && stride == 1 && CinP >= 128 && CinP % 32 == 0 && Cout % 64 == 0 && fp_wino_mode() != 0) {
-    // Winograd F(2,3) along rows: u = G g from the fp32 BN-folded weights, rounded to fp16 once
-    std::vector<f16> hu(wino_packed_halfs(Cout, CinP));
-    wino_pack_weights(w->data, scale.data(), Cout, Cin, hu.data());
-    FP_TRY(upload(net, hu, &out->wwino));
-  }
   // fragment-ordered copy for the band kernels: the 3x3 stride-2 layers (conv_s2.hip) and the 128 -> 128 / 256 -> 256 stride-1 layers, which run on 40x40 maps (conv_s1b.hip)
   if (K == 3 && (stride == 2 || (stride == 1 && CinP == Cout && (Cout == 128 || Cout == 256))) && CinP % 16 == 0 && s2_ct_for(Cout) != 0) {
     void *pk = nullptr;
@@ -375,7 +368,6 @@ int run_conv(fp_ctx *ctx, const Conv2dCall &c, hipStream_t s, float *splitk_scra
   a.in = c.in;
   a.w = w.w;
   a.wpk = w.wpk;
-  a.wwino = w.wwino;
   a.wsm = w.wsm;
   a.hyp = hyp;
   a.bias = w.bias;
@@ -523,7 +515,7 @@ int run_trunk(fp_ctx *ctx, const fp_net *net, const f16 *xA, const f16 *xB, int 
 // batch bit for bit (a hypothesis' arithmetic does not depend on its batch).
 int run_trunk_maybe_split(fp_ctx *ctx, const fp_net *net, const f16 *in, int s0, int NT, int N, f16 **tokens_out, hipStream_t s, StreamFanout *ab = nullptr,
                           const SharedB *sb = nullptr) {
-  static const int n_streams = getenv("FP_TRUNK_STREAMS") ? atoi(getenv("FP_TRUNK_STREAMS")) : 2;
+  static const int n_streams = fp_env_int("FP_TRUNK_STREAMS", 2);
   const size_t img = (size_t)160 * 160 * 8;
   if (N < fp_trunk_split_min()) return run_trunk(ctx, net, in + s0 * img, in + ((size_t)NT + s0) * img, N, tokens_out, s, nullptr, ab, sb, s0);
   if (ab) FP_TRY(ab->join());          // (a batch that is cut in two by hypotheses keeps both sides of a half on one stream)
@@ -554,7 +546,7 @@ int run_qkv(fp_ctx *ctx, const LinP *const *q, const LinP *const *k, const LinP 
   a.in = tok;
   a.M = N * 400;
   a.tokens = 400;
-  static const bool old_form = getenv("FP_QKV64") != nullptr;          // A/B knob: the 64-token kernel, one launch for q | k, one for v (bit-identical)
+  static const bool old_form = fp_env_set("FP_QKV64");          // A/B knob: the 64-token kernel, one launch for q | k, one for v (bit-identical)
   if (old_form && N > tok_qkv_small_max()) {          // (the few-image form of one and two hypotheses has its own bits: the knob compares the two batch kernels)
     a.nblk = 2 * n_layers;
     for (int l = 0; l < n_layers; ++l) {
@@ -636,7 +628,7 @@ int fp_refine_forward_ab(fp_ctx *ctx, const fp_net *net, const void *d_net_in, i
     const LinP *q_[2] = {&net->heads[0].q, &net->heads[1].q}, *k_[2] = {&net->heads[0].k, &net->heads[1].k}, *v_[2] = {&net->heads[0].v, &net->heads[1].v};
     ProfScope wall(ctx, s, "heads_wall", 0.0);      // first in-projection .. join of both heads, on the main stream: the heads' share of wall time
     FP_TRY(run_qkv(ctx, q_, k_, v_, 2, tok, N, qk, vt, s));
-    static const bool serial_heads = getenv("FP_HEADS_SERIAL") != nullptr;      // A/B timing knob
+    static const bool serial_heads = fp_env_set("FP_HEADS_SERIAL");      // A/B timing knob
     StreamFanout fo(ctx, s, serial_heads ? 1 : 2);
     for (int h = 0; h < 2; ++h) {
       const HeadW &H = net->heads[h];

@@ -831,7 +831,7 @@ RenderPlan render_plan(int N, int V, int F, int Ho, int Wo, int num_cu) {
   while (S < 4 && Ho / (S * 2) >= 8) S *= 2;
   // (measured, 160x160 crops of the 16k-face mesh, strips 6 -> 12: 24 hypotheses 58 -> 49 us, 32: 72 -> 62, 40: 72 -> 78, 63: 92 -> 100)
   while ((size_t)N * S * 5 <= (size_t)num_cu * 4 && S < 16 && Ho / (S * 2) >= 8) S *= 2;
-  static const int force_s = getenv("FP_RENDER_S") ? atoi(getenv("FP_RENDER_S")) : 0;      // experiments: strips per hypothesis
+  static const int force_s = fp_env_int("FP_RENDER_S", 0);      // experiments: strips per hypothesis
   if (force_s > 0 && (Ho + force_s - 1) / force_s <= rows_max) S = force_s;
   p.strip_rows = (Ho + S - 1) / S;
   p.S = (Ho + p.strip_rows - 1) / p.strip_rows;
@@ -847,7 +847,7 @@ RenderPlan render_plan(int N, int V, int F, int Ho, int Wo, int num_cu) {
   p.total = p.c_bytes + p.b_bytes + p.a_bytes + p.count_bytes + 2 * p.list_bytes;
   // one or two hypotheses (a tracking frame): vertex pass, classification and triangle pass as ONE launch (render_kernel<.., true>) when a
   // strip, the A records and the strip's two 16-bit face lists fit a workgroup's LDS.  FP_RENDER_SOLO = largest batch that takes it (0: off).
-  static const int solo_max = getenv("FP_RENDER_SOLO") ? atoi(getenv("FP_RENDER_SOLO")) : 2;
+  static const int solo_max = fp_env_int("FP_RENDER_SOLO", 2);
   p.solo_lds = (((size_t)p.strip_rows * Wo * 8 + ((((size_t)p.strip_rows * Wo * 2) + 15) & ~(size_t)15) + (size_t)((V + 1) & ~1) * 8 + 15) & ~(size_t)15) +
                2 * (size_t)((F + 7) & ~7) * 2;
   p.solo = (N <= solo_max && p.lds_verts && F <= 65535 && p.solo_lds <= budget) ? 1 : 0;
@@ -867,7 +867,7 @@ void raster_kernel_lds(std::vector<KernelLds> &v) {
 }
 
 int render_chunk(int N, int V, int F, int Ho, int Wo, int num_cu) {
-  static const size_t cap = getenv("FP_RENDER_SCRATCH_MAX") ? (size_t)atoll(getenv("FP_RENDER_SCRATCH_MAX")) : ((size_t)1 << 30);
+  static const size_t cap = (size_t)fp_env_int("FP_RENDER_SCRATCH_MAX", 1ll << 30);
   int chunk = N < 1 ? 1 : N;
   while (chunk > 1 && render_plan(chunk, V, F, Ho, Wo, num_cu).total > cap) chunk = (chunk + 1) / 2;
   return chunk;
@@ -881,7 +881,7 @@ size_t render_scratch_bytes(int N, int V, int F, int Ho, int Wo, int num_cu) {
 // the plan of the full ones, so the scratch of a full one always holds it)
 static int launch_render_one(fp_ctx *ctx, const RenderArgs &a_in, int plan_n, hipStream_t s) {
   RenderArgs a = a_in;
-  static const int dbg_env = getenv("FP_RENDER_DBG") ? atoi(getenv("FP_RENDER_DBG")) : 0;      // timing experiments only (wrong images): 1 no per-lane rasterisation, 2 no resolve, 4 no triangle pass, 16 no per-wave rasterisation
+  static const int dbg_env = fp_env_int("FP_RENDER_DBG", 0);      // timing experiments only (wrong images): 1 no per-lane rasterisation, 2 no resolve, 4 no triangle pass, 16 no per-wave rasterisation
   a.dbg = dbg_env;
   FP_REQUIRE(a.N >= 0 && a.Ho > 0 && a.Wo > 0, "render: bad shape N=%d out=%dx%d", a.N, a.Ho, a.Wo);
   if (a.N == 0) return FP_OK;
@@ -899,7 +899,7 @@ static int launch_render_one(fp_ctx *ctx, const RenderArgs &a_in, int plan_n, hi
   unsigned *listB = (unsigned *)(sc + pl.c_bytes + pl.b_bytes + pl.a_bytes + pl.count_bytes + pl.list_bytes);
   // (profiling: the class' work figure is BYTES WRITTEN - the fused fp16 net tensor, or the API's fp32 maps - for the HBM-stage line of bench.py)
   ProfScope ps(ctx, s, "render", a.net_out ? (double)a.N * a.Ho * a.Wo * 16.0 : (double)a.N * a.Ho * a.Wo * 40.0);
-  static const bool two_launches = getenv("FP_RENDER_PREPASS2") != nullptr;       // A/B knob: vertex pre-pass and classification as two launches (identical images)
+  static const bool two_launches = fp_env_set("FP_RENDER_PREPASS2");       // A/B knob: vertex pre-pass and classification as two launches (identical images)
   // fused where one workgroup per hypothesis classifies (G == 1: from 64 hypotheses on): 220 -> 210 us at 252 hypotheses, 144 -> 136 at 126; with
   // the faces of a hypothesis cut into G ranges every range's workgroup would redo the vertex pass (32 hypotheses: 70 -> 73 us, 1: 32 -> 34)
   if (pl.solo) {
@@ -945,7 +945,7 @@ int launch_render_objects(fp_ctx *ctx, const RenderArgs &a_in, const MeshDev *co
   FP_REQUIRE(n >= 1 && n <= FP_TRACK_MAX_OBJECTS, "render: %d objects in one launch (1 .. %d)", n, FP_TRACK_MAX_OBJECTS);
   FP_REQUIRE(a_in.net_out && a_in.Ho > 0 && a_in.Wo > 0, "render: the multi-object form writes the network tensor");
   RenderArgs a = a_in;
-  static const int dbg_env = getenv("FP_RENDER_DBG") ? atoi(getenv("FP_RENDER_DBG")) : 0;      // as launch_render_one
+  static const int dbg_env = fp_env_int("FP_RENDER_DBG", 0);      // as launch_render_one
   a.dbg = dbg_env;
   RenderObjs t;
   memset(&t, 0, sizeof(t));

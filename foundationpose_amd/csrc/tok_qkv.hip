@@ -285,7 +285,7 @@ void tok_qkv_kernel_lds(std::vector<KernelLds> &v) {
 }
 
 int tok_qkv_small_max() {
-  static const int small_max = getenv("FP_QKV_SMALL") ? atoi(getenv("FP_QKV_SMALL")) : 2;       // hypotheses of the pass up to which the few-image form runs (0: off)
+  static const int small_max = fp_env_int("FP_QKV_SMALL", 2);       // hypotheses of the pass up to which the few-image form runs (0: off)
   return small_max;
 }
 

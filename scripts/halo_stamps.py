@@ -1,6 +1,6 @@
 """Diagnostic (needs `make -B EXTRA=-DHALO_STAMP`): in-kernel cycle sums of the 3x3 halo kernel, per wave:
 [s_waitcnt + s_barrier in front of each kernel-row group], [group body: fragment reads + 48 MFMAs + DMA / halo issue],
-[chunk top: barrier + halo ds_writes], [whole main loop].  Prints the mean over the main-tile workgroups."""
+[prologue], [whole main loop], [epilogue].  Prints the mean over the main-tile workgroups (8 waves each)."""
 import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -26,23 +26,14 @@ def main():
     run(); torch.cuda.synchronize()
     buf = np.zeros((4096, 8, 8), dtype=np.uint64)
     L.fp_dbg_halo_stamps(buf.ctypes.data_as(ctypes.c_void_p), 0)
-    nw = 4 if (os.environ.get('FP_HALO_FORM', '0') == '1' and os.environ.get('FP_HALO_NPW', '4') == '2') else 8
-    if int(os.environ.get('FP_HALO_DBG', '0')) & 4:
-      b = buf[:200, :(4 if (os.environ.get('FP_HALO_FORM', '0') == '1' and os.environ.get('FP_HALO_NPW', '4') == '2') else 8)].reshape(-1, 8)
-      b = b[b[:, 7] > 0]
-      f = lambda x: float(np.mean(x.astype(np.float64)))
-      lo = np.uint64(0xffffffff)
-      print(f'{name}: epilogue phases (cycles): issue res/bias loads {f(b[:,0] >> np.uint64(32)):.0f} | barrier {f(b[:,0] & lo):.0f} | stage res + barrier {f(b[:,1] >> np.uint64(32)):.0f} | '
-            f'acc->stage {f(b[:,1] & lo):.0f} | barrier {f(b[:,2] & lo):.0f} | total epilogue {f(b[:,5]):.0f}')
-      continue
     hw = (buf[:, 0, 2] >> np.uint64(32)).astype(np.int64)
     buf[:, :, 2] &= np.uint64(0xffffffff)
-    v = buf[:200, :nw].astype(np.float64)
+    v = buf[:200].astype(np.float64)
     v = v[v[..., 3] > 0].reshape(-1, 8)
     groups = 3 * Cin // 32
     m = v.mean(0)
     life = (v[:, 7] - v[:, 6]) * 10.0      # ns (s_memrealtime = 100 MHz)
-    print(f'{name}: per group  wait+barrier {m[0]/groups:7.0f}  body {m[1]/groups:7.0f}  | per chunk top {m[2]/(Cin//32):7.0f} | '
+    print(f'{name}: per group  wait+barrier {m[0]/groups:7.0f}  body {m[1]/groups:7.0f}  | '
           f'prologue {m[4]:7.0f}  loop {m[3]:8.0f}  epilogue {m[5]:7.0f} cycles | lifetime {life.mean()/1e3:6.1f} us -> {(m[3]+m[4]+m[5])/life.mean():.2f} GHz')
     # per-CU timeline: HW_ID bits: wave_id[3:0] simd[5:4] pipe[7:6] cu[11:8] sh[12] se[15:13] ... xcc? (print raw layout stats)
     ok = buf[:, 0, 7] > 0

@@ -1,5 +1,5 @@
-"""The convolution encoder's kernels against the references of tests/tools/conv_ref.py, through the public entry points fp_conv2d_f16,
-fp_conv3x3_band_f16 and fp_conv3x3_wino_f16 only.  Every output buffer is NaN-prefilled and must hold no NaN afterwards.
+"""The convolution encoder's kernels against the references of tests/tools/conv_ref.py, through the public entry points fp_conv2d_f16 and
+fp_conv3x3_band_f16 only.  Every output buffer is NaN-prefilled and must hold no NaN afterwards.
 
 A. test_conv_exact_integers: small-integer operands, for which every correct form gives the integer reference BIT for bit (torch.equal), in
    fp16 and in fp32: a dropped, doubled or misplaced term of any size shows.  Each case runs dense and relu_like activations, each with
@@ -25,15 +25,14 @@ CASE -> KERNEL (rocprofv3 --kernel-trace --stats over this file on an MI355X; `f
   stem with one                                 conv_igemm2_kernel<64, 7, true, true>
   igemm2<BM,KW[,CIN8]> without / with           conv_igemm2_kernel<128, 3, false>, <64, 3, false>, <64, 7, true>, <128, 7, true>, <128, 1, false>, <64, 1, false>,
                                                 each with RES = false / true: all twelve instantiations; fp32 output of the Linear shapes: <128 | 64, 1, false, false>
-  wino                                          conv3x3_wino_kernel<20 | 40, 8, RES = true | false, false>
-  All nine forms, the five conv_small and the twelve conv_igemm2 instantiations are reached; no case landed in a form other than the one it names.
+  All eight forms, the five conv_small and the twelve conv_igemm2 instantiations are reached; no case landed in a form other than the one it names.
 
 LARGEST |err| / tol PER REGIME on an MI355X:
   fp16 output:  relu 0.970 (halo-tail1 3x40x40 128)   wide 0.982 (halo-round 83x40x40 128)   cancel 0.300 (igemm2<128,3> 1x33x9)   res_cancel 0.726 (halo-round)
   fp32 output:  relu 0.039   wide 0.230   cancel 0.004   res_cancel 0.149 (3x40x40 128 -> 128)
   relu and wide sit just below 1 in fp16 because the bound's first term IS the worst case of the one output rounding (half a step at the bottom of a
   binade); where that term is small beside the values handed on (cancel) or absent (fp32) the kernels use a third of the bound or less.
-  All 48 exact-integer cases are bit-identical.  The whole file takes 14 s, its slowest test 1.2 s.
+  All 45 exact-integer cases are bit-identical.  The whole file takes 14 s, its slowest test 1.2 s.
 """
 import pytest
 import torch
@@ -54,7 +53,7 @@ def ctx():
 
 
 def run_conv(ctx, c, dev, use_res, relu, out_f32):
-  """One launch of case c on the device operands `dev` (x, wp or w, b, res) -> (N, Ho, Wo, Cout) on the CPU, NaN-checked."""
+  """One launch of case c on the device operands `dev` (x, wp, b, res) -> (N, Ho, Wo, Cout) on the CPU, NaN-checked."""
   from foundationpose_amd._lib import check, lib, ptr, stream_ptr
   Ho, Wo = R.out_hw(c)
   out = torch.full((c.N, Ho, Wo, c.Cout), float('nan'), dtype=torch.float32 if out_f32 else torch.float16, device='cuda')
@@ -63,9 +62,6 @@ def run_conv(ctx, c, dev, use_res, relu, out_f32):
   if c.entry == 'band':
     assert c.H == c.W == 40 and c.Cin == c.Cout and not out_f32
     check(lib().fp_conv3x3_band_f16(h, ptr(dev['x']), c.N, c.Cin, ptr(dev['wp']), ptr(dev['b']), res, int(relu), ptr(out), s))
-  elif c.entry == 'wino':
-    assert c.H == c.W and not out_f32
-    check(lib().fp_conv3x3_wino_f16(h, ptr(dev['x']), c.N, c.H, c.Cin, c.Cout, ptr(dev['w_host']), ptr(dev['b']), res, int(relu), ptr(out), s))
   else:
     check(lib().fp_conv2d_f16(h, ptr(dev['x']), c.N, c.H, c.W, R.cin_pad(c), ptr(dev['wp']), ptr(dev['b']), c.Cout, c.k, c.k, c.stride, (c.k - 1) // 2,
                               res, int(relu), ptr(out), int(out_f32), s))
@@ -79,7 +75,6 @@ def run_conv(ctx, c, dev, use_res, relu, out_f32):
 def to_device(d):
   dev = {k: d[k].cuda() for k in ('x', 'wp', 'b')}
   dev['res'] = None if d['res'] is None else d['res'].cuda()
-  dev['w_host'] = d['w'].contiguous().numpy()            # fp_conv3x3_wino_f16 packs fp32 weights (Cout, Cin, 3, 3) from the host
   return dev
 
 

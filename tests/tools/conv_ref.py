@@ -1,13 +1,12 @@
 """References, inputs and bounds of the convolution encoder's tests (csrc/conv_small.hip, conv_halo.hip, conv_s1b.hip, conv_s2.hip, conv.hip,
-stem.hip, conv_wino.hip).  Plain torch / numpy, no GPU: tests/test_conv_ref_host.py checks what is here, tests/test_gpu_conv_numerics.py the
+stem.hip).  Plain torch / numpy, no GPU: tests/test_conv_ref_host.py checks what is here, tests/test_gpu_conv_numerics.py the
 kernels against it.  Every reference reads the SAME fp16 operands the kernel reads.
 
 A. EXACT-INTEGER PARITY (EXACT_CASES, exact_case).  Activations are integers in {-2, -1, 1, 2} (`dense`: no zeros, every product is nonzero and
 every dropped, doubled or misplaced term shows) or the same with about half of them set to exact 0 (`relu_like`); weights in {-1, 0, 1}; bias and
 residual integers in [-8, 8].  The stem's activations are integers in [-3, 3] in six channels, padded to eight: the two pad channels hold zero
 ACTIVATIONS and nonzero garbage WEIGHTS.  Every partial sum is an integer below 2^24, so fp32 addition is exact in any order, and every result
-with |value| <= 2048 is exact in fp16: whatever form runs - one launch, K split over waves, split-K with its finishing pass, Winograd (G g and
-B^T d of these operands are exact multiples of 1/2) - has to give the integer reference bit for bit, in fp16 and in fp32.  The reference is
+with |value| <= 2048 is exact in fp16: whatever form runs - one launch, K split over waves, split-K with its finishing pass - has to give the integer reference bit for bit, in fp16 and in fp32.  The reference is
 torch's float32 conv2d; the host test shows on every case that it equals the float64 one and that max |conv + bias + residual| <= 2048.
 
 The form each case runs was worked out from fp_conv2d_f16, launch_conv, conv_small_shape, conv_ksplit, conv_halo_ksplit and halo_plan for the
@@ -110,8 +109,6 @@ EXACT_CASES = (
   _c('igemm2<128,7,CIN8>', 1, 34, 30, 6, 128, k=7, stride=2),
   _c('igemm2<128,1>', 1, 1, 1000, 512, 1024, k=1, outs=(0, 1)), _c('igemm2<64,1>', 1, 1, 130, 512, 64, k=1, outs=(0, 1)),
   _c('igemm2<64,1>', 3, 7, 5, 32, 64, k=1),
-  # conv_wino.hip
-  _c('wino', 2, 20, 20, 512, 512, entry='wino'), _c('wino', 3, 40, 40, 128, 128, entry='wino'), _c('wino', 9, 40, 40, 128, 256, entry='wino'),
 )
 VARIANTS = ('dense', 'relu_like')
 EXACT_LIMIT = 2048
