@@ -1417,3 +1417,121 @@ def mesh_distance(mesh_a, mesh_b, n_samples=100_000, seed=0, taus=(0.001, 0.002,
   fscore = [2 * p * r / (p + r) if p + r > 0 else 0.0 for p, r in zip(precision, recall)]
   return dict(a_to_b=ab, b_to_a=ba, chamfer=ab['mean'] + ba['mean'], hausdorff=max(ab['max'], ba['max']), taus=taus, precision=precision,
               recall=recall, fscore=fscore)
+
+
+# ---- symmetries of a model (fp_symmetry_residuals; the search itself is foundationpose_amd/symmetry.py, host float64) ------------------
+def _symmetry_residuals_on(pts, tfs, pos, fc, taus=(), want_q=False, want_dist=False):
+  """d_stats of fp_symmetry_residuals as a device tensor (T, FP_SURFDIST_STATS_TAU0 + len(taus)) float64, and d_q, d_dist as asked;
+  pts (n,3) float32, tfs (T,3,4) float32, on the device of the mesh.  Nothing synchronises."""
+  dev, n, T = pos.device, len(pts), len(tfs)
+  th = np.ascontiguousarray(np.asarray(taus, dtype=np.float64).reshape(-1))
+  if len(th) > _lib.FP_SURFDIST_MAX_TAUS:
+    raise ValueError(f'at most {_lib.FP_SURFDIST_MAX_TAUS} thresholds ({len(th)} given)')
+  if T < 1 or T * n > _lib.FP_SURFDIST_MAX_POINTS:
+    raise ValueError(f'symmetry_residuals: {T} transforms of {n} points (at least one transform, at most {_lib.FP_SURFDIST_MAX_POINTS} queries)')
+  stats = torch.empty((T, _lib.FP_SURFDIST_STATS_TAU0 + len(th)), dtype=torch.float64, device=dev)
+  q = torch.empty((T * n, 3), dtype=torch.float, device=dev) if want_q else None
+  dist = torch.empty(T * n, dtype=torch.float, device=dev) if want_dist else None
+  check(lib().fp_symmetry_residuals(_lib.Context.get(dev).handle, ptr(pts) if n else None, n, ptr(tfs), T, ptr(pos), len(pos), ptr(fc), len(fc),
+                                    ptr(th) if len(th) else None, len(th), ptr(stats), ptr(q) if n else None, ptr(dist) if n else None,
+                                    stream_ptr(dev)))
+  return stats, q, dist
+
+
+def _tfs_f32_on(tfs, dev):
+  """(S,4,4) transforms -> (S,3,4) float32 [R|t] on dev: float64 on the host, rounded to fp32 once"""
+  t = np.asarray(tfs.cpu() if torch.is_tensor(tfs) else tfs, dtype=np.float64).reshape(-1, 4, 4)
+  return torch.as_tensor(np.ascontiguousarray(t[:, :3, :].astype(np.float32)), device=dev)
+
+
+def _stats_dict(s):
+  L = _lib
+  n = s[:, L.FP_SURFDIST_STATS_COUNT]
+  with np.errstate(invalid='ignore', divide='ignore'):
+    mean = np.where(n > 0, s[:, L.FP_SURFDIST_STATS_SUM] / n, np.nan)
+    rms = np.where(n > 0, np.sqrt(s[:, L.FP_SURFDIST_STATS_SUM_SQ] / n), np.nan)
+  return dict(n=n.astype(np.int64), not_finite=s[:, L.FP_SURFDIST_STATS_NOT_FINITE].astype(np.int64), max=s[:, L.FP_SURFDIST_STATS_MAX].copy(),
+              mean=mean, rms=rms, within=s[:, L.FP_SURFDIST_STATS_TAU0:].astype(np.int64))
+
+
+def symmetry_residuals(mesh=None, vertices=None, faces=None, tfs=None, n_samples=4096, seed=0, taus=()):
+  """How far a mesh is from itself under each of S rigid transforms, on the device (fp_symmetry_residuals): n_samples surface samples
+  (sample_surface: a function of the mesh, n_samples and seed alone) are moved by every transform and measured against the mesh's
+  triangles, exactly (point_mesh_distance's rule), in one launch; only the statistics come back.
+
+  The mesh as `mesh` (.vertices / .faces or a (vertices, faces) tuple) or as vertices and faces; tfs (S,4,4), taken as float64 and
+  rounded to fp32 once.  Returns a dict of numpy arrays over the transforms: 'max', 'mean', 'rms' (float64; NaN where no distance is
+  finite), 'n' and 'not_finite' (counts), 'within' (S, len(taus)): the number of samples within each tau.  A symmetry of the mesh has
+  max about 0 (fp32 rounding); what a value means otherwise is up to the caller.  Synchronises (the sampler once, the read-back once)."""
+  if tfs is None:
+    raise ValueError('symmetry_residuals needs tfs')
+  v = _mesh_parts(mesh)[0] if mesh is not None else vertices
+  dev = _device_of(v)
+  pos, fc = _surface_on(mesh, vertices, faces, dev, 'symmetry_residuals')
+  pts = _sample_surface_on(pos, fc, int(n_samples), seed)[0]
+  stats = _symmetry_residuals_on(pts, _tfs_f32_on(tfs, dev), pos, fc, taus)[0]
+  return _stats_dict(stats.cpu().numpy())
+
+
+SYMMETRY_TOL_FRACTION = 0.02       # find_symmetries' default tol as a share of the exact diameter: this project's choice
+
+
+def find_symmetries(mesh, tol=None, max_order=12, angle_step_deg=1.0, n_samples=4096, n_coarse=512, seed=0, rot_angle_discrete=5,
+                    max_group=128):
+  """The rotational symmetries of a mesh: what a hand-edited models_info.json supplies for a CAD model, found for any mesh - a
+  reconstructed one included.  Proper rotations only (a reflection is not a pose).  The search runs on the host in float64
+  (foundationpose_amd/symmetry.py); every residual it looks at comes from the device (fp_symmetry_residuals): the largest distance from
+  the mesh's surface samples, moved by a candidate, to the mesh's triangles.  A transform is ACCEPTED when that maximum is <= tol.
+
+  Pivot and axes: the area-weighted centroid and covariance of the surface, in closed form per triangle.  Every rotational symmetry fixes
+  the centroid and commutes with the covariance, so an axis of order >= 3 is an eigenvector and a 2-fold axis is an eigenvector or lies
+  in the plane of two equal eigenvalues.  Candidates, for each of the three eigenvectors a (so no eigenvalue gap is thresholded):
+  rotations about a by 2 pi m / k, k = 2 .. max_order (order k stands only when EVERY multiple of 2 pi / k passes); rotations about a by
+  every multiple of angle_step_deg - if ALL pass, a is a
+  continuous axis; 2-fold rotations about the axes of the plane perpendicular to a, on a grid of angle_step_deg, every local minimum of
+  the mean residual refined by halving to angle_step_deg / 64.  All candidates are scored on n_coarse samples in one call, the survivors
+  verified on n_samples in a second, the accepted set closed under composition (elements closer than half a step are one; elements that
+  differ by a rotation about a continuous axis are one), and every element the closure adds is verified too.  More than max_group
+  discrete elements raise ValueError.
+
+  tol: in the mesh's unit; None is SYMMETRY_TOL_FRACTION = 0.02 x mesh_diameter (exact) - this project's own choice, wide enough for the
+  noise of a 2 mm fusion on a hand-sized object; a CAD model takes a much smaller one.
+
+  Returns a dict:
+    'symmetry_tfs'           (S,4,4) float64 in the mesh's frame, what FoundationPose(symmetry_tfs=), pose_errors and bop_pose_errors
+                             take: the identity first, every transform fixing the centroid; a continuous axis is sampled every
+                             rot_angle_discrete degrees and multiplied with the discrete elements
+    'symmetries_discrete'    models_info.json's form: each discrete element but the identity as its 4x4 matrix, row-major, 16 numbers,
+                             the translation in MILLIMETRES (the mesh is in metres)
+    'symmetries_continuous'  [{'axis': the unit axis, 'offset': a point on it (the centroid) in millimetres}] or []
+    'centroid', 'eigenvalues' (ascending), 'axes' (rows: the eigenvectors)
+    'max', 'mean'            (S,) the residuals of every element of symmetry_tfs on n_samples samples
+    'n_candidates', 'tol', 'closed' (False: the closure produced an element that did not verify and was left out),
+    'continuous_axes'        the eigenvectors about which every rotation passed (more than one: a sphere; the first is used)
+  When all three eigenvalues are nearly equal (a cube, a sphere) the principal axes are arbitrary and the result may be INCOMPLETE: what
+  is returned verifies - it is never wrong, only possibly partial - and 'eigenvalues' shows the case.  The same mesh and arguments give
+  the same bits on every run.  Synchronises several times (cold path)."""
+  from . import symmetry as _sym
+  vertices, faces = _mesh_parts(mesh)[:2]
+  dev = _device_of(vertices)
+  pos, fc = _surface_on(mesh, None, None, dev, 'find_symmetries')
+  if tol is None:
+    tol = SYMMETRY_TOL_FRACTION * mesh_diameter(model_pts=pos)
+  tol = float(tol)
+  if not tol >= 0:
+    raise ValueError(f'find_symmetries: tol {tol}')
+  samples = {}
+
+  def residuals(tfs, n):
+    if n not in samples:
+      samples[n] = _sample_surface_on(pos, fc, int(n), seed)[0]
+    tfs = np.asarray(tfs, dtype=np.float64).reshape(-1, 4, 4)
+    per_call = max(1, _lib.FP_SURFDIST_MAX_POINTS // max(int(n), 1))
+    parts = [_symmetry_residuals_on(samples[n], _tfs_f32_on(tfs[s0:s0 + per_call], dev), pos, fc)[0] for s0 in range(0, len(tfs), per_call)]
+    d = _stats_dict(torch.cat(parts).cpu().numpy())
+    bad = d['not_finite'] > 0
+    return np.where(bad, np.inf, d['max']), np.where(bad, np.inf, d['mean'])
+
+  v = pos.cpu().numpy().astype(np.float64)
+  return _sym.find_symmetries(v, fc.cpu().numpy(), residuals, tol, max_order=max_order, angle_step_deg=angle_step_deg, n_samples=n_samples,
+                              n_coarse=n_coarse, rot_angle_discrete=rot_angle_discrete, max_group=max_group)

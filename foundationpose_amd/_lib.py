@@ -116,7 +116,7 @@ FP_TSDF_ALIGN_TERMS = 29                                                  # fp_t
 FP_TEXTURE_MIN_SIZE, FP_TEXTURE_MAX_SIZE, FP_TEXTURE_MAX_TOP_N, FP_TEXTURE_MAX_FACES = 64, 4096, 4, 1 << 21      # fp_texture_bake
 
 
-# fp_point_mesh_distance, fp_distance_stats, fp_mesh_sample_surface
+# fp_point_mesh_distance, fp_distance_stats, fp_mesh_sample_surface, fp_symmetry_residuals
 FP_SURFDIST_MAX_POINTS, FP_SURFDIST_MAX_FACES, FP_SURFDIST_MAX_TAUS, FP_SURFDIST_MAX_SAMPLES = 1 << 24, 1 << 23, 8, 1 << 22
 FP_SURFDIST_TILE, FP_SURFDIST_CHUNK = 1024, 256          # queries of a workgroup, face records of an LDS chunk
 FP_SURFDIST_STATS_COUNT, FP_SURFDIST_STATS_SUM, FP_SURFDIST_STATS_SUM_SQ, FP_SURFDIST_STATS_MAX, FP_SURFDIST_STATS_NOT_FINITE = 0, 1, 2, 3, 4
@@ -185,6 +185,8 @@ _PROTOS = {
                               POINTER(FpTextureCfg), c_void_p, c_void_p, c_void_p, c_void_p]),
   'fp_point_mesh_distance': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
   'fp_distance_stats': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+  'fp_symmetry_residuals': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                    c_void_p, c_void_p]),
   'fp_mesh_sample_surface': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_uint, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
   'fp_net_create': (c_int, [c_void_p, c_int, POINTER(FpTensor), c_int, c_int, POINTER(c_void_p)]),
   'fp_net_destroy': (c_int, [c_void_p]),

@@ -82,6 +82,40 @@ class BopModels:
     return symmetry_tfs_from_info(self.info(obj_id))
 
 
+def write_models_info(models_dir, meshes, symmetries='auto', diameters=None, **find_kw):
+  """Write `models_dir`/models_info.json, the file BopModels reads, for {obj_id: mesh} with meshes in METRES (as BopModels.mesh gives
+  them): per object `diameter` (the exact one, Utils.mesh_diameter on the device, unless `diameters` {obj_id: metres} has it),
+  `min_x/y/z` and `size_x/y/z`, all in millimetres, and the two symmetry keys from `symmetries`: 'auto' runs Utils.find_symmetries on
+  every mesh (find_kw are its keyword arguments: tol, max_order, ..), None writes none, a dict {obj_id: info or None} takes
+  find_symmetries' results as given.  `symmetries_discrete` holds each element but the identity as 16 numbers, the translation in mm;
+  `symmetries_continuous` [{'axis', 'offset'}] the true unit axis and a point on it in mm.  BopModels.symmetry_tfs reads the discrete
+  elements back exactly; the reference's helper behind it (Utils.symmetry_tfs_from_info) reads a continuous axis only along x, y or z
+  and takes the offset as a translation, so for a continuous axis off the coordinate axes the entry written here is correct but that
+  helper cannot express it: pass info['symmetry_tfs'] to FoundationPose and the metrics directly.  Returns {obj_id: entry}."""
+  from .symmetry import models_info_entry
+  if not (symmetries is None or isinstance(symmetries, dict) or symmetries == 'auto'):
+    raise ValueError(f"write_models_info: symmetries must be 'auto', None or a dict, got {symmetries!r}")
+  entries = {}
+  for obj_id in sorted(int(k) for k in meshes):
+    mesh = meshes[obj_id]
+    if diameters is not None and obj_id in diameters:
+      diameter = float(diameters[obj_id])
+    else:
+      from .Utils import mesh_diameter
+      diameter = mesh_diameter(model_pts=np.asarray(mesh.vertices))
+    info = None
+    if isinstance(symmetries, dict):
+      info = symmetries.get(obj_id)
+    elif symmetries == 'auto':
+      from .Utils import find_symmetries
+      info = find_symmetries(mesh, **find_kw)
+    entries[obj_id] = models_info_entry(np.asarray(mesh.vertices), diameter, info)
+  os.makedirs(str(models_dir), exist_ok=True)
+  with open(os.path.join(str(models_dir), 'models_info.json'), 'w') as f:
+    json.dump({str(k): v for k, v in entries.items()}, f, indent=2)
+  return entries
+
+
 # ---------------------------------------------------------------------------------------------- scenes
 class BopScene:
   """One scene directory (src/datareader.py:183-344).  Deviation from the reference: `depth_scale` is taken PER IMAGE from

@@ -1,5 +1,6 @@
 // Distance between surfaces: the exact distance from points to a triangle mesh (fp_point_mesh_distance), its statistics
-// (fp_distance_stats) and a deterministic area-weighted surface sampler (fp_mesh_sample_surface).  The rules are stated in
+// (fp_distance_stats), a deterministic area-weighted surface sampler (fp_mesh_sample_surface) and the distances of a sample set under many
+// rigid transforms with their statistics per transform (fp_symmetry_residuals: the same kernel, the queries formed in registers).  The rules are stated in
 // include/foundationpose_amd.h and restated in float64 numpy in tests/surface_distance_oracle.py.  The nearest thing in the reference is
 // the cKDTree query of adds_err (src/Utils.py:242-253): point to VERTEX, so it depends on the tessellation; this is point to triangle.
 //
@@ -135,9 +136,22 @@ struct SurfDistArgs {
   const int32_t *faces;    // (F, 3)
   int n, V, F, chunks_per_slice;
   u64 *keys;               // [n]: d2 bits << 32 | face, all ones before the launch
+  // fp_symmetry_residuals (TRANSFORMED): the n queries are g = k n_per + i, query g the point pts[i] under tfs[k]
+  const float *tfs;        // (n / n_per, 3, 4) row-major [R|t]
+  int n_per;
+  float *q_out;            // (n, 3) or null: the transformed points
 };
 
-// grid (tiles of SD_TILE queries, face slices of chunks_per_slice chunks)
+// the query of the header: q = R p + t per row, the translation innermost
+__device__ __forceinline__ void transform_point(const float *__restrict__ m, float x, float y, float z, float &qx, float &qy, float &qz) {
+  qx = fmaf(m[0], x, fmaf(m[1], y, fmaf(m[2], z, m[3])));
+  qy = fmaf(m[4], x, fmaf(m[5], y, fmaf(m[6], z, m[7])));
+  qz = fmaf(m[8], x, fmaf(m[9], y, fmaf(m[10], z, m[11])));
+}
+
+// grid (tiles of SD_TILE queries, face slices of chunks_per_slice chunks).  TRANSFORMED: the queries are formed here from (transform,
+// point) and never read back; everything after the load is the same code, so the result of a query is the same function of (q, mesh)
+template <bool TRANSFORMED>
 __global__ __launch_bounds__(SD_THREADS) void surfdist_kernel(SurfDistArgs a) {
   __shared__ float4 lds[SD_CHUNK * SD_REC];
   const int tid = threadIdx.x;
@@ -147,7 +161,14 @@ __global__ __launch_bounds__(SD_THREADS) void surfdist_kernel(SurfDistArgs a) {
 #pragma unroll
   for (int q = 0; q < SD_Q; ++q) {
     const int i = min(q0 + q * SD_THREADS + tid, a.n - 1);      // a query past n repeats the last one and is not written
-    px[q] = a.pts[(size_t)i * 3], py[q] = a.pts[(size_t)i * 3 + 1], pz[q] = a.pts[(size_t)i * 3 + 2];
+    if (TRANSFORMED) {
+      const int k = i / a.n_per, j = i - k * a.n_per;
+      transform_point(a.tfs + (size_t)k * 12, a.pts[(size_t)j * 3], a.pts[(size_t)j * 3 + 1], a.pts[(size_t)j * 3 + 2], px[q], py[q], pz[q]);
+      if (a.q_out && blockIdx.y == 0 && i == q0 + q * SD_THREADS + tid)
+        a.q_out[(size_t)i * 3] = px[q], a.q_out[(size_t)i * 3 + 1] = py[q], a.q_out[(size_t)i * 3 + 2] = pz[q];
+    } else {
+      px[q] = a.pts[(size_t)i * 3], py[q] = a.pts[(size_t)i * 3 + 1], pz[q] = a.pts[(size_t)i * 3 + 2];
+    }
     best[q] = __builtin_inff(), bface[q] = -1;
   }
   const long long f_begin = (long long)blockIdx.y * a.chunks_per_slice * SD_CHUNK;
@@ -288,6 +309,95 @@ __global__ __launch_bounds__(64) void dist_stats_finish_kernel(const double *__r
   stats[term] = s;
 }
 
+// ---- statistics per transform (fp_symmetry_residuals) ---------------------------------------------------------------------------------
+// The T n keys are tiled by SD_TILE like the queries; a tile may hold the end of one transform, whole ones, and the start of another.  A
+// workgroup writes one partial per (tile j, transform k) it holds into column j + k of the slab: along g = k n + i the pair (j, k) only
+// ever steps forward, so j + k names each pair once and the columns of transform k are k + its first tile .. k + its last tile.
+constexpr int SR_ITEMS = SD_TILE / DS_THREADS;
+
+struct SymStatsArgs {
+  const u64 *keys;         // [total]
+  int total, n_per, n_taus, n_cols;      // n_cols = tiles + T
+  double taus[FP_SURFDIST_MAX_TAUS];
+  double *slab;            // [DS_TERMS][n_cols]
+  float *dist;             // (total) or null
+};
+
+__global__ __launch_bounds__(DS_THREADS) void sym_stats_kernel(SymStatsArgs a) {
+  __shared__ double red[DS_TERMS][DS_THREADS / 64];
+  const int g0 = blockIdx.x * SD_TILE, g1 = min(g0 + SD_TILE, a.total);
+  float d[SR_ITEMS];
+  int kq[SR_ITEMS];
+#pragma unroll
+  for (int q = 0; q < SR_ITEMS; ++q) {
+    const int g = g0 + q * DS_THREADS + threadIdx.x;
+    d[q] = 0.f, kq[q] = -1;
+    if (g < g1) {
+      const u64 key = a.keys[g];
+      d[q] = key != ~(u64)0 ? sqrtf(__uint_as_float((unsigned)(key >> 32))) : __builtin_nanf("");      // as surfdist_finish_kernel
+      kq[q] = g / a.n_per;
+      if (a.dist) a.dist[g] = d[q];
+    }
+  }
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  for (int k = g0 / a.n_per; k <= (g1 - 1) / a.n_per; ++k) {
+    double v[DS_TERMS];
+#pragma unroll
+    for (int t = 0; t < DS_TERMS; ++t) v[t] = 0.0;
+#pragma unroll
+    for (int q = 0; q < SR_ITEMS; ++q) {
+      if (kq[q] != k) continue;
+      if (!(fabsf(d[q]) < __builtin_inff())) {
+        v[FP_SURFDIST_STATS_NOT_FINITE] += 1.0;
+        continue;
+      }
+      const double x = (double)d[q];
+      v[FP_SURFDIST_STATS_COUNT] += 1.0, v[FP_SURFDIST_STATS_SUM] += x, v[FP_SURFDIST_STATS_SUM_SQ] = fma(x, x, v[FP_SURFDIST_STATS_SUM_SQ]);
+      v[FP_SURFDIST_STATS_MAX] = fmax(v[FP_SURFDIST_STATS_MAX], x);
+#pragma unroll
+      for (int t = 0; t < FP_SURFDIST_MAX_TAUS; ++t)
+        if (t < a.n_taus && x <= a.taus[t]) v[FP_SURFDIST_STATS_TAU0 + t] += 1.0;
+    }
+    // a fixed order: butterfly within each wave, then the waves in order; a lane outside transform k adds 0
+#pragma unroll
+    for (int t = 0; t < DS_TERMS; ++t) {
+#pragma unroll
+      for (int o = 32; o >= 1; o >>= 1) {
+        const double w = __shfl_xor(v[t], o, 64);
+        v[t] = t == FP_SURFDIST_STATS_MAX ? fmax(v[t], w) : v[t] + w;
+      }
+    }
+    __syncthreads();                      // `red` of the previous transform has been read
+    if (lane == 0) {
+#pragma unroll
+      for (int t = 0; t < DS_TERMS; ++t) red[t][wave] = v[t];
+    }
+    __syncthreads();
+    if (threadIdx.x < FP_SURFDIST_STATS_TAU0 + a.n_taus) {
+      const int t = threadIdx.x;
+      double s = 0.0;
+      for (int i = 0; i < DS_THREADS / 64; ++i) s = t == FP_SURFDIST_STATS_MAX ? fmax(s, red[t][i]) : s + red[t][i];
+      a.slab[(size_t)t * a.n_cols + blockIdx.x + k] = s;
+    }
+  }
+}
+
+// one thread per (transform, term): the partials of the transform's tiles in tile order
+__global__ __launch_bounds__(DS_THREADS) void sym_stats_finish_kernel(const double *__restrict__ slab, int n_cols, int n_per, int T, int n_terms,
+                                                                      double *stats) {
+  const int idx = blockIdx.x * DS_THREADS + threadIdx.x;
+  const int k = idx / n_terms, term = idx - k * n_terms;
+  if (k >= T) return;
+  const int j0 = (int)(((long long)k * n_per) / SD_TILE), j1 = (int)((((long long)k + 1) * n_per - 1) / SD_TILE);
+  const double *p = slab + (size_t)term * n_cols + k;
+  double s = 0.0;
+  if (term == FP_SURFDIST_STATS_MAX)
+    for (int j = j0; j <= j1; ++j) s = fmax(s, p[j]);
+  else
+    for (int j = j0; j <= j1; ++j) s += p[j];
+  stats[(size_t)k * n_terms + term] = s;
+}
+
 // ---- surface sampler -------------------------------------------------------------------------------------------------------------------
 constexpr int SS_THREADS = 256;
 constexpr int SS_TOTAL_THREADS = 1024;
@@ -400,12 +510,56 @@ extern "C" int fp_point_mesh_distance(fp_ctx *ctx, const float *d_points, int n,
   FP_CHECK_HIP(hipMemsetAsync(keys, 0xff, bytes, s));
   const int tiles = (n + SD_TILE - 1) / SD_TILE, chunks = (F + SD_CHUNK - 1) / SD_CHUNK;
   const int slices = std::min(chunks, std::max(1, (SD_MIN_GROUPS + tiles - 1) / tiles));
-  SurfDistArgs a{d_points, d_pos, d_faces, n, V, F, (chunks + slices - 1) / slices, keys};
+  SurfDistArgs a{d_points, d_pos, d_faces, n, V, F, (chunks + slices - 1) / slices, keys, nullptr, 0, nullptr};
   const int slices_used = (chunks + a.chunks_per_slice - 1) / a.chunks_per_slice;
-  hipLaunchKernelGGL(surfdist_kernel, dim3((unsigned)tiles, (unsigned)slices_used), dim3(SD_THREADS), 0, s, a);
+  hipLaunchKernelGGL(surfdist_kernel<false>, dim3((unsigned)tiles, (unsigned)slices_used), dim3(SD_THREADS), 0, s, a);
   FP_CHECK_HIP(hipGetLastError());
   hipLaunchKernelGGL(surfdist_finish_kernel, dim3((unsigned)((n + SD_THREADS - 1) / SD_THREADS)), dim3(SD_THREADS), 0, s, a, d_dist, d_face,
                      d_closest);
+  FP_CHECK_HIP(hipGetLastError());
+  return FP_OK;
+}
+
+extern "C" int fp_symmetry_residuals(fp_ctx *ctx, const float *d_points, int n, const float *d_tfs, int T, const float *d_pos, int V,
+                                     const int32_t *d_faces, int F, const double *h_taus, int n_taus, double *d_stats, float *d_q, float *d_dist,
+                                     void *stream) {
+  FP_REQUIRE(ctx && d_pos && d_faces && d_tfs && d_stats, "fp_symmetry_residuals: null argument");
+  FP_REQUIRE(V >= 1 && F >= 1 && F <= FP_SURFDIST_MAX_FACES, "fp_symmetry_residuals: V %d, F %d (at least 1; at most %d faces)", V, F,
+             FP_SURFDIST_MAX_FACES);
+  FP_REQUIRE(T >= 1 && n >= 0 && (long long)T * n <= FP_SURFDIST_MAX_POINTS, "fp_symmetry_residuals: T %d, n %d (T at least 1, T n 0 .. %d)", T, n,
+             FP_SURFDIST_MAX_POINTS);
+  FP_REQUIRE(n_taus >= 0 && n_taus <= FP_SURFDIST_MAX_TAUS && (h_taus || n_taus == 0), "fp_symmetry_residuals: n_taus %d (0 .. %d)", n_taus,
+             FP_SURFDIST_MAX_TAUS);
+  FP_REQUIRE(d_points || n == 0, "fp_symmetry_residuals: d_points null with n %d", n);
+  hipStream_t s = (hipStream_t)stream;
+  FP_CHECK_HIP(hipSetDevice(ctx->device));
+  const int n_terms = FP_SURFDIST_STATS_TAU0 + n_taus;
+  if (n == 0) {
+    FP_CHECK_HIP(hipMemsetAsync(d_stats, 0, (size_t)T * n_terms * sizeof(double), s));
+    return FP_OK;
+  }
+  const int total = T * n;
+  const int tiles = (total + SD_TILE - 1) / SD_TILE, chunks = (F + SD_CHUNK - 1) / SD_CHUNK;
+  SymStatsArgs st;
+  st.total = total, st.n_per = n, st.n_taus = n_taus, st.n_cols = tiles + T, st.dist = d_dist;
+  for (int t = 0; t < FP_SURFDIST_MAX_TAUS; ++t) st.taus[t] = t < n_taus ? h_taus[t] : 0.0;
+  const size_t key_bytes = (size_t)total * sizeof(u64), slab_bytes = (size_t)DS_TERMS * st.n_cols * sizeof(double);
+  FP_TRY(fp_arena_ensure(ctx, key_bytes + slab_bytes + 256 + 4096));
+  ArenaScope scope(ctx->arena);
+  u64 *keys = (u64 *)ctx->arena.take(key_bytes);
+  st.slab = (double *)ctx->arena.take(slab_bytes);
+  FP_REQUIRE(keys && st.slab, "fp_symmetry_residuals: arena exhausted");
+  st.keys = keys;
+  FP_CHECK_HIP(hipMemsetAsync(keys, 0xff, key_bytes, s));
+  const int slices = std::min(chunks, std::max(1, (SD_MIN_GROUPS + tiles - 1) / tiles));
+  SurfDistArgs a{d_points, d_pos, d_faces, total, V, F, (chunks + slices - 1) / slices, keys, d_tfs, n, d_q};
+  const int slices_used = (chunks + a.chunks_per_slice - 1) / a.chunks_per_slice;
+  hipLaunchKernelGGL(surfdist_kernel<true>, dim3((unsigned)tiles, (unsigned)slices_used), dim3(SD_THREADS), 0, s, a);
+  FP_CHECK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(sym_stats_kernel, dim3((unsigned)tiles), dim3(DS_THREADS), 0, s, st);
+  FP_CHECK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(sym_stats_finish_kernel, dim3((unsigned)(((long long)T * n_terms + DS_THREADS - 1) / DS_THREADS)), dim3(DS_THREADS), 0, s,
+                     (const double *)st.slab, st.n_cols, n, T, n_terms, d_stats);
   FP_CHECK_HIP(hipGetLastError());
   return FP_OK;
 }

@@ -65,7 +65,8 @@ class FoundationPose:
     diameter (not in the reference): None measures the object as the reference does, compute_mesh_diameter over 10000 vertices drawn
     with numpy's global generator - for a larger model the value, and with it every crop window, depends on numpy's seed; a number is
     used as given (the models_info.json value of a BOP model, in metres); 'exact' is Utils.mesh_diameter, every vertex pair on the
-    device."""
+    device.  symmetry_tfs='auto' (not in the reference either) runs Utils.find_symmetries with its defaults on the centred mesh and
+    keeps the whole result in self.symmetry_info; for another tol run find_symmetries yourself and pass info['symmetry_tfs']."""
     lo, hi = mesh.vertices.min(axis=0), mesh.vertices.max(axis=0)
     self.model_center = (lo + hi) / 2
     self.mesh_ori = mesh.copy()
@@ -91,6 +92,13 @@ class FoundationPose:
     # file back, so none is written: no file is left behind per object)
     self.mesh_path = None
     self.mesh_tensors = U.make_mesh_tensors(centred)
+    self.symmetry_info = None
+    if isinstance(symmetry_tfs, str):
+      if symmetry_tfs != 'auto':
+        raise ValueError(f"symmetry_tfs must be None, (S,4,4) transforms or 'auto', got {symmetry_tfs!r}")
+      # not in the reference: the group is found on the CENTRED mesh, the frame every pose of this object is held in
+      self.symmetry_info = U.find_symmetries(centred)
+      symmetry_tfs = self.symmetry_info['symmetry_tfs']
     sym = torch.eye(4)[None] if symmetry_tfs is None else torch.as_tensor(symmetry_tfs)
     self.symmetry_tfs = sym.to(device='cuda', dtype=torch.float)
     # tracking workspaces (and their captured graphs) hold the previous object's mesh handle and centre: none survives a new object

@@ -375,7 +375,23 @@ def _refine_on(depths, views, voxel_size, anchor, order, rounds, trunc, margin, 
 
 
 def reconstruct_object(views, voxel_size=0.002, trunc=None, min_weight=1, depth_filter=True, margin=None, device='cuda', refine_poses=False,
-                       max_vertices=None, simplify_cell=None, components='largest', texture=None):
+                       max_vertices=None, simplify_cell=None, components='largest', texture=None, symmetries=None):
+  """_reconstruct_mesh (which documents every other argument) and, with `symmetries`, the rotational symmetries of the finished mesh:
+  symmetries=True runs Utils.find_symmetries with its defaults, a dict gives its keyword arguments (tol, max_order, ..), and the call
+  then returns (mesh, info) - info['symmetry_tfs'] is what FoundationPose(symmetry_tfs=) takes, and bop.write_models_info writes the
+  rest to models_info.json.  The default (None or False) returns the mesh alone, as before."""
+  mesh = _reconstruct_mesh(views, voxel_size=voxel_size, trunc=trunc, min_weight=min_weight, depth_filter=depth_filter, margin=margin,
+                           device=device, refine_poses=refine_poses, max_vertices=max_vertices, simplify_cell=simplify_cell,
+                           components=components, texture=texture)
+  if symmetries is None or symmetries is False:
+    return mesh
+  from .Utils import find_symmetries
+  with torch.cuda.device(_device(device)):
+    return mesh, find_symmetries(mesh, **(symmetries if isinstance(symmetries, dict) else {}))
+
+
+def _reconstruct_mesh(views, voxel_size=0.002, trunc=None, min_weight=1, depth_filter=True, margin=None, device='cuda', refine_poses=False,
+                      max_vertices=None, simplify_cell=None, components='largest', texture=None):
   """Reference views -> mesh (synthetic.SimpleMesh with vertex normals and colours).  `views`: a folder in the reference's layout
   (load_reference_views) or a dict with depths, masks, K, cam_in_obs and optionally rgbs.  depth_filter runs erode_depth and
   bilateral_filter_depth on every view first, as the estimator does with an observed frame.  The fusion and the extraction run on the

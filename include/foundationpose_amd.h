@@ -838,6 +838,29 @@ int fp_point_mesh_distance(fp_ctx *ctx, const float *d_points, int n, const floa
  * d_dist null with n > 0, n outside 0 .. FP_SURFDIST_MAX_POINTS, n_taus outside 0 .. FP_SURFDIST_MAX_TAUS, h_taus null with n_taus > 0. */
 int fp_distance_stats(fp_ctx *ctx, const float *d_dist, int n, const double *h_taus, int n_taus, double *d_stats, void *stream);
 
+/* Distances of n surface samples to a mesh under T rigid transforms, and their statistics per transform: what a search for the mesh's
+ * symmetries asks of the device (Utils.find_symmetries).  d_points (n,3) float32; d_tfs (T,3,4) float32, row-major [R|t] with rows
+ * (r00 r01 r02 tx), (r10 r11 r12 ty), (r20 r21 r22 tz); d_pos (V,3) float32, d_faces (F,3) int32: device.  h_taus (n_taus <=
+ * FP_SURFDIST_MAX_TAUS) float64, host, read before the call returns.
+ *   The query (k, i) is q = R_k p_i + t_k in fp32, nothing contracted, the translation innermost:
+ *     q.x = fma(r00, p.x, fma(r01, p.y, fma(r02, p.z, tx))), and q.y, q.z the same with rows 1 and 2.
+ * Its distance is what fp_point_mesh_distance gives for the point q - the same pair rule, the smallest fp32 d2, equal values to the
+ * lowest face, sqrtf - bit for bit a function of (q, mesh) alone: not of T, n, the tile the query lands in or how the faces are divided.
+ * The bad-value rules are those of fp_point_mesh_distance (a non-finite q, or no face left: dist = NaN).
+ *   d_stats (T, FP_SURFDIST_STATS_TAU0 + n_taus) float64, device: row k holds the entries of fp_distance_stats over the n distances of
+ * transform k.  The queries are flattened to g = k n + i and tiled by FP_SURFDIST_TILE - a tile may hold parts of several transforms -
+ * and the sums are double sums of per-workgroup partials, one per (tile, transform), that a finishing launch adds in tile order: no
+ * float atomics, the same input gives the same bits on every run.  The counts and the maximum are exact.
+ *   d_q (T n,3) float32 or null: the transformed points; d_dist (T n) float32 or null: their distances.  (Feeding d_q to
+ * fp_point_mesh_distance gives d_dist again, bit for bit: tests/test_gpu_symmetry.py.)
+ *   Work: T n F pair tests at the rate of fp_point_mesh_distance - no spatial cull - plus one pass over the T n keys; the arena holds
+ * the keys (8 T n bytes) and the partials.  Nothing synchronises.  n = 0 gives zeros.  FP_EINVAL: T < 1; n < 0; T n above
+ * FP_SURFDIST_MAX_POINTS; a null ctx, d_tfs, d_pos, d_faces or d_stats; d_points null with n > 0; V < 1; F < 1 or above
+ * FP_SURFDIST_MAX_FACES; n_taus outside 0 .. FP_SURFDIST_MAX_TAUS; h_taus null with n_taus > 0. */
+int fp_symmetry_residuals(fp_ctx *ctx, const float *d_points, int n, const float *d_tfs, int T, const float *d_pos, int V,
+                          const int32_t *d_faces, int F, const double *h_taus, int n_taus, double *d_stats, float *d_q, float *d_dist,
+                          void *stream);
+
 /* n points on the surface of a mesh, area-weighted, stratified along the face order, a function of (mesh, n, seed) alone.
  *   Face choice, exact.  area_f = 0.5 |ab x ac| in double from the fp32 positions (edge differences, cross product and square root in
  * double; 0 for a face with an index outside [0, V) or a non-finite area), A = their double sum, area_q[f] = rint(area_f / A 2^40) as

@@ -2,7 +2,7 @@
 cam_in_ob/, K.txt), by TSDF fusion and marching tetrahedra on the GPU (foundationpose_amd.reconstruct).
 usage: python scripts/reconstruct_object.py DIR [--voxel 0.002] [--trunc T] [--min-weight 1] [--no-depth-filter] [--refine-poses]
        [--max-vertices N | --simplify-cell C] [--min-component-fraction X] [--texture [SIZE]] [--out DIR/model/model.obj]
-       [--compare-to MODEL]
+       [--compare-to MODEL] [--symmetries [--symmetry-tol T]]
 The output format follows the extension: .obj or .ply.  --refine-poses aligns every view but the first to the geometry fused so far before the
 fusion (reconstruct.refine_view_poses) and also writes the poses it used to DIR/cam_in_ob_refined/NAME.txt.  --max-vertices N (8192: the
 rasteriser's on-chip vertex limit) or --simplify-cell C (metres) reduces the mesh by vertex clustering (Utils.simplify_mesh).  By default
@@ -11,7 +11,9 @@ the largest one's faces (Utils.clean_mesh: an object of several parts).  --textu
 finished mesh (Utils.bake_texture; SIZE: a power of two, 64 .. 4096, default: the smallest with cells of 8 texels) and writes
 model.obj with model.mtl and model.png beside it; OBJ only - a PLY holds one uv per vertex, the atlas three per face.  --compare-to MODEL
 (OBJ or PLY, e.g. the CAD model, in the frame and unit of the views' poses) adds one JSON line: the Chamfer and Hausdorff distance and
-precision / recall / F-score of the written model against MODEL (Utils.mesh_distance; scripts/mesh_distance.py has more options)."""
+precision / recall / F-score of the written model against MODEL (Utils.mesh_distance; scripts/mesh_distance.py has more options).
+--symmetries finds the model's rotational symmetries (Utils.find_symmetries; --symmetry-tol T in metres, default 2 % of the diameter) and
+writes DIR/model/models_info.json with object id 1 (bop.write_models_info: diameter, bounds and the symmetry keys, in millimetres)."""
 import argparse
 import json
 import os
@@ -38,6 +40,8 @@ def main():
   ap.add_argument('--texture', type=int, nargs='?', const=0, default=None, metavar='SIZE')
   ap.add_argument('--out', default=None)
   ap.add_argument('--compare-to', default=None, metavar='MODEL')
+  ap.add_argument('--symmetries', action='store_true')
+  ap.add_argument('--symmetry-tol', type=float, default=None)
   args = ap.parse_args()
   out = args.out or os.path.join(args.dir, 'model', 'model.obj')
   if args.texture is not None and out.lower().endswith('.ply'):
@@ -62,6 +66,14 @@ def main():
     mesh_io.save_obj(mesh, out)
   tex = f', texture {mesh.visual.image.shape[1]} x {mesh.visual.image.shape[0]}' if args.texture is not None else ''
   print(f'{out}: {len(mesh.vertices)} vertices, {len(mesh.faces)} faces{tex}')
+  if args.symmetries:
+    from foundationpose_amd import Utils as U
+    from foundationpose_amd import bop
+    info = U.find_symmetries(mesh, tol=args.symmetry_tol)
+    models_dir = os.path.join(args.dir, 'model')
+    bop.write_models_info(models_dir, {1: mesh}, symmetries={1: info})
+    print(f'{os.path.join(models_dir, "models_info.json")}: {len(info["symmetries_discrete"])} discrete symmetries, '
+          f'{len(info["symmetries_continuous"])} continuous axes, {len(info["symmetry_tfs"])} transforms (tol {info["tol"]:.3g})')
   if args.compare_to is not None:
     from foundationpose_amd import Utils as U
     print(json.dumps(dict(compared_to=args.compare_to, **U.mesh_distance(mesh, mesh_io.load_mesh(args.compare_to)))))
