@@ -773,6 +773,9 @@ __global__ __launch_bounds__(RB_THREADS) void render_kernel(RenderArgs a, int st
         float x = tu * (float)m.texW - 0.5f, y = tv * (float)m.texH - 0.5f;
         float fx0 = floorf(x), fy0 = floorf(y);
         float fx = x - fx0, fy = y - fy0;
+        // (a whole number beyond the int range: its residue taken in float, where it is exact - the conversion alone would saturate)
+        if (fabsf(fx0) >= 2147483648.f) fx0 = fmodf(fx0, (float)m.texW);
+        if (fabsf(fy0) >= 2147483648.f) fy0 = fmodf(fy0, (float)m.texH);
         int x0 = (int)fx0 % m.texW;
         if (x0 < 0) x0 += m.texW;
         int y0 = (int)fy0 % m.texH;

@@ -42,6 +42,9 @@ static void tex_fetch(const oracle_mesh *m, float u, float v, float *rgb) {
   float fx0 = floorf(x), fy0 = floorf(y);
   float fx = x - fx0, fy = y - fy0;
   int W = m->texW, H = m->texH;
+  /* a whole number beyond the int range: its residue taken in float, where it is exact (the conversion alone is undefined) */
+  if (fabsf(fx0) >= 2147483648.f) fx0 = fmodf(fx0, (float)W);
+  if (fabsf(fy0) >= 2147483648.f) fy0 = fmodf(fy0, (float)H);
   int x0 = (int)fx0 % W; if (x0 < 0) x0 += W;
   int y0 = (int)fy0 % H; if (y0 < 0) y0 += H;
   int x1 = (x0 + 1) % W, y1 = (y0 + 1) % H;

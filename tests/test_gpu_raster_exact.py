@@ -2,7 +2,7 @@
 exactly (no exclusions but zclip_slant's stated band), u, v, z/w within TOL_UVZ, depth, xyz and colour within TOL_ATTR times the value range; the
 launch forms (one launch for 1 or 2 hypotheses, fused classification at 5, vertex pre-pass + G face ranges, A records in global memory) bit-identical
 to each other; the fused network tensor within one fp16 ulp of float64; and the two float64 tests of tests/test_oracle_independent.py (slanted
-quad, ground plane through the camera) run on the kernel itself.  Every case passed on the first run: csrc/ is unchanged.
+quad, ground plane through the camera) run on the kernel itself.  Every lattice case passed on the first run.
 
 MEASURED on an MI355X, largest |err| / tol over the five hypotheses (TOL_UVZ = 5.0e-7, TOL_ATTR = 6.2e-7 x value range):
   case                                u,v,z/w  attributes
@@ -43,6 +43,37 @@ MEASURED on an MI355X, largest |err| / tol over the five hypotheses (TOL_UVZ = 5
   padded_solo_over                   0.000  0.000
   network tensor, largest |err| / fp16 ulp: centres_small 0.400, depth_signs_mixed 0.500, large32 0.498, window_zoom 0.500
 
+TEXTURE FETCH AND LIGHTING (R.SHADE_CASES against shade_float64; tolerance = TOL_TEX 6.9e-7 x the case's scale, normal map TOL_ATTR 6.2e-7), MEASURED
+on an MI355X, largest |err| / tol over 1, 2 and 5 hypotheses; every case passed on the first run:
+  case               light          colour (tol)       normal
+  tex_identity       -              0.000 (1.63e-05)   0.000      bit for bit
+  tex_identity_5x7   -              0.110 (1.00e-05)   0.000
+  tex_corners        -              0.000 (1.63e-05)   0.000      bit for bit
+  tex_wrap           -              0.168 (9.22e-06)   0.000
+  tex_thin_1x1       -              0.000 (6.92e-07)   0.000
+  tex_thin_1x6       -              0.201 (5.04e-06)   0.000
+  tex_thin_6x1       -              0.207 (4.60e-06)   0.000
+  tex_charts         -              0.083 (8.02e-06)   0.000
+  tex_atlas          -              0.016 (1.11e-05)   0.000      (and within 1e-5 of a colour step of the face's own colour)
+  tex_perspective    -              0.250 (5.54e-06)   0.000
+  lit_vcol           bright         0.094 (1.87e-06)   0.205
+  lit_vcol           default        0.121 (1.25e-06)   0.205
+  lit_vcol           default_color  0.107 (1.25e-06)   0.205
+  lit_vcol           dir            0.112 (1.25e-06)   0.205
+  lit_vcol           dir_color      0.103 (1.25e-06)   0.205
+  lit_vcol           pos            0.133 (1.25e-06)   0.205
+  lit_vcol           pos_color      0.108 (1.25e-06)   0.205
+  lit_tex            bright         0.099 (1.08e-05)   0.205
+  lit_tex            default        0.110 (7.66e-06)   0.205
+  lit_tex            default_color  0.087 (7.66e-06)   0.205
+  lit_tex            dir            0.086 (7.66e-06)   0.205
+  lit_tex            dir_color      0.086 (7.66e-06)   0.205
+  lit_tex            pos            0.134 (7.66e-06)   0.205
+  lit_tex            pos_color      0.092 (7.66e-06)   0.205
+  network tensor rgb, largest |err| / fp16 ulp: tex_identity 0.400, tex_wrap 0.500, tex_perspective 0.500
+The one change to csrc/ that these tests brought: the fetch reduces a texel index beyond the int range in float before converting it
+(test_texture_fetch_far_from_the_origin; no image of any other test moves).
+
 KERNELS of one `rocprofv3 --kernel-trace --stats` run of tests/tools/raster_lattice_digest.py (1, 2 and 5 hypotheses each; workgroups = hypotheses x 8
 strips of 8 rows at 64 x 64; every API render is a render_kernel<0, .> and a render_kernel<2, .> launch over the same lists; fp_render_net is
 render_kernel<1, .>):
@@ -66,7 +97,7 @@ import pytest
 import torch
 
 from tests.tools import raster_ref as R
-from tests.test_raster_ref_host import compare_with_reference, render_case
+from tests.test_raster_ref_host import FAR_UV, compare_shaded, compare_with_reference, far_uv_case, render_case, render_shaded, shade_light
 
 pytestmark = pytest.mark.gpu
 
@@ -191,6 +222,62 @@ def test_network_tensor_against_float64(name):
   print('net %s: largest |err| / fp16 ulp %.3f; pixels invalid / valid %d / %d, channels masked / kept %d / %d' % ((name, worst) + tuple(sides)))
   if name == 'depth_signs_mixed':
     assert sides.min() > 0, sides
+
+
+@pytest.mark.parametrize('name', R.SHADE_CASES)
+def test_texture_fetch_and_lighting_against_float64(U, name):
+  """Every SHADE case under every light setting at 1, 2 and 5 hypotheses (the one-launch form and the fused classification): winner exactly, colour
+  within shade_tol of shade_float64 - bit for bit where the case is exact -, normal map within TOL_ATTR, background exactly 0; the 1- and 2-hypothesis
+  renders equal the 5-hypothesis one's slices bit for bit.  Every covered pixel is compared."""
+  c = R.lattice_case(name)
+  for var in R.shade_variants(name):
+    five = render_shaded(U.nvdiffrast_render, c, 5, dev='cuda', **shade_light(var))
+    compare_shaded(c, five, 5, 'hip', var)
+    for n in (1, 2):
+      part = render_shaded(U.nvdiffrast_render, c, n, dev='cuda', **shade_light(var))
+      for k in five:
+        assert np.array_equal(part[k], five[k][:n]), (name, var, n, k)
+
+
+@pytest.mark.parametrize('fu,fv', FAR_UV)
+def test_texture_fetch_far_from_the_origin(U, fu, fv):
+  """a million periods away, and |uv size| beyond the int range (the index reduced in float): the contract's value exactly, on every pixel"""
+  c, want = far_uv_case(fu, fv)
+  got = render_shaded(U.nvdiffrast_render, c, 1, dev='cuda')
+  covered = got['rast'][0][..., 3] > 0
+  assert covered.sum() == 512 and np.array_equal(got['color'][0][covered].astype(np.float64), np.tile(want, (512, 1))), (got['color'][0][covered][0], want)
+
+
+@pytest.mark.parametrize('name', ['tex_identity', 'tex_wrap', 'tex_perspective'])
+def test_network_tensor_rgb_of_textured_cases(name):
+  """fp_render_net's rgb channels of a textured mesh: 0.8 base + 0.5 d base with d = 1 (make_crop_data_batch's lighting; every normal of these cases faces
+  the camera), within one fp16 ulp of float64, zero exactly where the reference covers nothing.  (The cases' texels are >= 1/8: the value never comes
+  near the range where an fp16 ulp is smaller than the float32 error of the fetch.)"""
+  from foundationpose_amd import _lib
+  from foundationpose_amd._lib import check, k_ptr, lib, ptr, stream_ptr
+  c = R.with_default_projection(R.lattice_case(name))
+  assert c['mesh_tensors']['tex'].min() >= 0.125
+  ctx = _lib.Context.get('cuda:0')
+  dm = _lib.device_mesh(ctx, {k: torch.as_tensor(v).cuda() for k, v in c['mesh_tensors'].items()})
+  Kd, Kp = k_ptr(c['K'])
+  outs = {}
+  for n in (1, 2, 5):
+    poses = torch.as_tensor(c['poses'][:n]).cuda().contiguous()
+    out = torch.zeros((n, c['Ho'], c['Wo'], 8), dtype=torch.float16, device='cuda')
+    check(lib().fp_render_net(ctx.handle, dm.handle, ptr(poses), n, Kp, c['H'], c['W'], None, c['Ho'], c['Wo'], 2.0, 1, 1.5, ptr(out), stream_ptr()))
+    torch.cuda.synchronize()
+    outs[n] = out.cpu().numpy()
+  assert np.array_equal(outs[1], outs[5][:1]) and np.array_equal(outs[2], outs[5][:2])
+  worst = 0.0
+  for h in range(5):
+    cov = R.coverage_exact(c, h)
+    ref = R.shade_float64(c, h, cov, use_light=True)
+    got = outs[5][h].astype(np.float64)[..., :3]
+    assert not got[~ref['covered']].any() and np.array_equal(got.max(-1) > 0, ref['covered']), (name, h)
+    err = np.abs(got - ref['color']) / _fp16_ulp(ref['color'])
+    worst = max(worst, float(err.max()))
+    assert err.max() <= 1.0, (name, h, float(err.max()))
+  print('net rgb %s: largest |err| / fp16 ulp %.3f' % (name, worst))
 
 
 def test_slanted_quad_against_float64_point_in_triangle(U):

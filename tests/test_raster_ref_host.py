@@ -1,6 +1,10 @@
 """CPU checks of the rasteriser's exact reference (tests/tools/raster_ref.py): that every lattice case is what it says it is, that the reference's
 fill rule equals the literal top-left statement and a concrete-epsilon evaluation in Python integers, that the CPU mirror (oracle/raster_c.c) equals
-the reference - winner exactly, floats within the derived tolerance -, and that seven deliberately wrong rasterisers are told apart from it."""
+the reference - winner exactly, floats within the derived tolerance -, and that seven deliberately wrong rasterisers are told apart from it.
+Texture fetch and lighting (R.SHADE_CASES): the float64 reference against closed forms that do not go through its fetch, the float32 emulation inside
+EMU_TEX, wrong fetches told apart, and the CPU mirror against float64 under every light setting."""
+import functools
+
 import numpy as np
 import pytest
 
@@ -260,3 +264,296 @@ def test_cpu_mirror_equals_the_reference(name):
   from oracle.render import nvdiffrast_render
   c = R.lattice_case(name)
   compare_with_reference(c, render_case(nvdiffrast_render, c, 5), 5, 'mirror')
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# texture fetch and lighting (R.SHADE_CASES)
+# ---------------------------------------------------------------------------------------------------------------------------------------
+def shade_light(var):
+  """nvdiffrast_render's light arguments of a variant name (None: use_light = False)"""
+  return {} if var is None else dict(R.LIGHTS[var], use_light=True)
+
+
+@pytest.mark.parametrize('name', R.SHADE_CASES + ['tex_wrap_shifted'])
+def test_shade_case_is_what_it_says(name):
+  c = R.lattice_case(name)
+  assert len(R.transform_check(c)) == 5
+  mt = c['mesh_tensors']
+  for h in _hyps(c):
+    cl = R.claims_exact(c, h)
+    assert cl.sum(0).max() == 1 and cl.any((1, 2)).all()                       # no two faces compete, every face shows
+  if 'tex' in mt:
+    assert 'vertex_color' not in mt and max(mt['tex'].shape[1:3]) <= 16
+    assert not (mt['uv_idx'] == mt['faces']).any() and len(mt['uv']) > len(mt['pos'])
+    assert np.abs(mt['uv'][mt['uv_idx']]).max() <= 3
+    wrong = mt['uv'][mt['faces']] - mt['uv'][mt['uv_idx']]                     # what indexing uv through `faces` would change
+    assert (np.abs(wrong).max((1, 2)) >= 1 / 16).all()
+  if name == 'tex_perspective':
+    assert 'slow' in R.face_classes(c, 0, 1) and 'slow' in R.face_classes(c, 4, 5)
+    assert c['w'].min() == 1 and c['w'].max() == 4
+  if name in R.LIT_CASES:
+    n = mt['vnormals'].astype(np.float64)
+    assert len(np.unique(n, axis=0)) == len(n) and not np.array_equal(c['poses'][0][:3, :3], np.eye(3))
+    for var in R.shade_variants(name):
+      clipped0 = clipped1 = 0
+      for h in _hyps(c):
+        s = R.shade_float64(c, h, **shade_light(var))
+        clipped0 += int((s['dvert'] < -0.05).sum())
+        clipped1 += int((s['preclip'] > 1.01).sum())
+        g = R.interp_float64(c, h)                   # |sum uvw_k n_k| against sum uvw_k |n_k|: how much the interpolation shortens the normal
+        short = np.linalg.norm((g['uvw'][..., None] * n[g['vid']]).sum(-2), axis=-1) / (g['uvw'] * np.linalg.norm(n, axis=1)[g['vid']]).sum(-1)
+        assert short[g['covered']].min() > 0.68
+      assert clipped0 >= 5, (var, clipped0)                                   # some normals face away: the clip at 0 acts (5 hypotheses x vertices)
+      if var == 'bright':
+        assert clipped1 >= 100, clipped1                                      # ... and the final clip at 1
+
+
+def _grid_expected(c, h):
+  """closed form of tex_identity / tex_identity_5x7 / tex_corners in integers: (rows, cols, value) of every pixel inside the quad"""
+  i0, j0, pw, ph, half = c['claims']['grid']
+  tex = c['mesh_tensors']['tex'][0].astype(np.float64)
+  Ht, Wt = tex.shape[:2]
+  dx, dy = c['shifts'][h]
+  assert dx % 16 == 0 and dy % 16 == 0
+  out = {}
+  for j in range(64):
+    for i in range(64):
+      ti, tj = i - i0 - dx // 16, (j0 + dy // 16 + ph - 1) - j            # texel steps right of the quad's left edge / below its top edge (rows bottom-up)
+      if half == 0:
+        if 0 <= ti < pw and 0 <= tj < ph:
+          out[(63 - j, i)] = tex[tj % Ht, ti % Wt]
+      elif 0 <= ti <= pw and 0 <= tj + 1 <= ph:                # (the closed box: the fill rule keeps one of each pair of opposite boundary lines)
+        # corners on pixel centres: the centre (i, j) sits on the corner between texel columns ti - 1, ti and rows tj, tj + 1 counted from the top vertex row
+        tj += 1
+        out[(63 - j, i)] = (tex[(tj - 1) % Ht, (ti - 1) % Wt] + tex[(tj - 1) % Ht, ti % Wt] + tex[tj % Ht, (ti - 1) % Wt] + tex[tj % Ht, ti % Wt]) / 4
+  return out
+
+
+@pytest.mark.parametrize('name', ['tex_identity', 'tex_identity_5x7', 'tex_corners'])
+def test_reference_fetch_equals_the_texel_and_the_four_texel_mean(name):
+  """closed forms that do not go through fetch_float64: where every pixel centre is a texel centre the colour IS the texel (row 0 of the texture at the
+  top of the quad, column 0 at its left: no flip, no transposition), half a texel further it is the mean of the four texels around the corner"""
+  c = R.lattice_case(name)
+  for h in _hyps(c):
+    cov = R.coverage_exact(c, h)
+    s = R.shade_float64(c, h, cov)
+    want = _grid_expected(c, h)
+    inside = np.zeros((64, 64), bool)
+    for (r, i), v in want.items():
+      inside[r, i] = True
+      if cov['face'][r, i] >= 0:
+        assert np.abs(s['color'][r, i] - v).max() <= (0 if c['claims']['exact'] else 1e-13), (name, h, r, i)
+    assert not (s['covered'] & ~inside).any() and s['covered'].sum() == c['claims']['grid'][2] * c['claims']['grid'][3]
+
+
+def test_reference_fetch_wraps_periodically():
+  """tex_wrap in closed form from integers (2 x = k - 21, 4 y = l - 22 for the k-th column / l-th row of the quad), the blend of the last with the
+  first column where u = 0 and u = 1 fall on pixel centres, the period of 16 px, and whole periods added to every uv (tex_wrap_shifted)"""
+  c, c2 = R.lattice_case('tex_wrap'), R.lattice_case('tex_wrap_shifted')
+  tex = c['mesh_tensors']['tex'][0].astype(np.float64)
+  Ht, Wt = tex.shape[:2]
+  for h in _hyps(c):
+    cov = R.coverage_exact(c, h)
+    s, s2 = R.shade_float64(c, h, cov), R.shade_float64(c2, h)
+    assert np.array_equal(s['covered'], s2['covered']) and np.abs(s['color'] - s2['color']).max() <= 1e-13
+    both = s['covered'][:, 16:] & s['covered'][:, :-16]
+    assert both.sum() > 1500 and np.abs(s['color'][:, 16:] - s['color'][:, :-16])[both].max() <= 1e-13
+    both = s['covered'][16:] & s['covered'][:-16]
+    assert both.sum() > 1500 and np.abs(s['color'][16:] - s['color'][:-16])[both].max() <= 1e-13
+    dx, dy = c['shifts'][h]
+    seen = set()
+    for r in range(64):
+      for i in range(64):
+        if not s['covered'][r, i]:
+          continue
+        k, l = i - 4 - dx // 16, (60 + dy // 16) - (63 - r)          # pixel steps right of the left edge (u = -1.25) / below the top edge (v = -1.25)
+        assert 0 <= k <= 56 and 0 <= l <= 56
+        xf, xr, yf, yr = (k - 21) // 2, (k - 21) % 2, (l - 22) // 4, (l - 22) % 4
+        a = tex[yf % Ht, xf % Wt] * (2 - xr) / 2 + tex[yf % Ht, (xf + 1) % Wt] * xr / 2
+        b = tex[(yf + 1) % Ht, xf % Wt] * (2 - xr) / 2 + tex[(yf + 1) % Ht, (xf + 1) % Wt] * xr / 2
+        assert np.abs(s['color'][r, i] - (a * (4 - yr) / 4 + b * yr / 4)).max() <= 1e-13, (h, r, i)
+        if k in (20, 36):                     # u = 0, u = 1: x = -0.5 and Wt - 0.5, half the last column and half the first
+          assert xf % Wt == Wt - 1 and xr == 1
+          seen.add(k)
+    assert seen == {20, 36}
+
+
+def test_reference_lambert_term_of_a_flat_quad():
+  """One normal for the whole quad: colour = base (w_ambient + w_diffuse d) (or base w_ambient + d light_color w_diffuse) with d from Pythagorean
+  triples by hand; the point light's per-vertex d = p_z / |p| for a light at the camera and a normal along -z."""
+  def flat(ncam):
+    m = R._Mesh()
+    R._quad(m, R._c(8), R._c(8), R._c(40), R._c(40))
+    return R._finish('flat', m, {}, normals_cam=np.tile(np.asarray(ncam, np.float32), (4, 1)), rot=R.LIT_ROT)
+  c = flat((0, 0.75, -1))
+  base = R.interp_float64(c, 0)['color']
+  for light_dir, d in (((0, 0, 1), 0.8), ((0, -3, 4), 1.0), ((0, 4, 3), 0.0), ((0, 3, -4), 0.0), ((3, 0, 4), 0.64)):
+    s = R.shade_float64(c, 0, use_light=True, light_dir=light_dir)
+    np.testing.assert_allclose(s['color'], np.clip(base * (0.8 + 0.5 * d), 0, 1), atol=1e-14)
+    s = R.shade_float64(c, 0, use_light=True, light_dir=light_dir, light_color=(1.0, 0.5, 0.25), w_ambient=0.5, w_diffuse=0.25)
+    want = np.clip(base * 0.5 + d * np.array([1.0, 0.5, 0.25]) * 0.25, 0, 1) * s['covered'][..., None]
+    np.testing.assert_allclose(s['color'], want, atol=1e-14)
+    assert np.abs(s['normal'][s['covered']] - np.array([0, 0.6, -0.8])).max() <= 1e-14 and not s['normal'][~s['covered']].any()
+  c = flat((0, 0, -1))
+  s = R.shade_float64(c, 1, use_light=True, light_dir=None, light_pos=(0, 0, 0))
+  p = R._cam64(c, 1)
+  assert np.all(p[:, 2] == 1) and np.abs(p[:, :2]).max() > 0.2
+  np.testing.assert_allclose(s['dvert'], 1 / np.sqrt(1 + p[:, 0] ** 2 + p[:, 1] ** 2), atol=1e-14)
+
+
+def _wrong_fetch(c, h, what):
+  """the reference's colour with one rule broken"""
+  g = R.interp_float64(c, h)
+  mt = c['mesh_tensors']
+  tex = mt['tex'][0].astype(np.float64)
+  Ht, Wt = tex.shape[:2]
+  uvw = g['uvw']
+  idx = mt['faces'][g['tri']] if what == 'uv_through_faces' else mt['uv_idx'][g['tri']]
+  if what == 'affine_uv':
+    lam = np.moveaxis(R.coverage_exact(c, h)['lam'], 0, -1)
+    uvw = lam / np.where(g['covered'], lam.sum(-1), 1.0)[..., None]
+  t = (uvw[..., None] * mt['uv'].astype(np.float64)[idx]).sum(-2)
+  u, v = t[..., 0], t[..., 1]
+  if what == 'no_half_texel':
+    u, v = u + 0.5 / Wt, v + 0.5 / Ht
+  elif what == 'v_flip':
+    v = 1 - v
+  elif what == 'swap_uv':
+    u, v = v, u
+  elif what == 'swapped_stride':                          # rows addressed with the height as the stride
+    flat = tex.reshape(-1, 3)
+    x, y = u * Wt - 0.5, v * Ht - 0.5
+    x0, y0 = np.floor(x), np.floor(y)
+    fx, fy = (x - x0)[..., None], (y - y0)[..., None]
+    c0, r0 = np.mod(x0, Wt).astype(int), np.mod(y0, Ht).astype(int)
+    c1, r1 = (c0 + 1) % Wt, (r0 + 1) % Ht
+    at = lambda r, cc: flat[(r * Ht + cc) % len(flat)]
+    col = (1 - fy) * ((1 - fx) * at(r0, c0) + fx * at(r0, c1)) + fy * ((1 - fx) * at(r1, c0) + fx * at(r1, c1))
+    return np.where(g['covered'][..., None], col, 0.0)
+  elif what == 'clamp':
+    u, v = np.clip(u, 0.5 / Wt, 1 - 0.5 / Wt), np.clip(v, 0.5 / Ht, 1 - 0.5 / Ht)
+  elif what == 'nearest':
+    u, v = (np.floor(u * Wt) + 0.5) / Wt, (np.floor(v * Ht) + 0.5) / Ht
+  return np.where(g['covered'][..., None], R.fetch_float64(tex, u, v), 0.0)
+
+
+WRONG_FETCHES = [('no_half_texel', 'tex_identity'), ('no_half_texel', 'tex_corners'), ('v_flip', 'tex_identity'), ('swap_uv', 'tex_identity'),
+                 ('swapped_stride', 'tex_identity'), ('swapped_stride', 'tex_identity_5x7'), ('uv_through_faces', 'tex_charts'), ('uv_through_faces', 'tex_atlas'),
+                 ('affine_uv', 'tex_perspective'), ('clamp', 'tex_wrap'), ('nearest', 'tex_corners'), ('nearest', 'tex_wrap')]
+
+
+@pytest.mark.parametrize('what,name', WRONG_FETCHES, ids=['%s-%s' % w for w in WRONG_FETCHES])
+def test_wrong_fetches_are_rejected(what, name):
+  """each broken rule moves some pixel of its case by more than a hundred tolerances"""
+  c = R.lattice_case(name)
+  err = np.abs(_wrong_fetch(c, 0, what) - R.shade_float64(c, 0)['color']).max()
+  assert err > 100 * R.shade_tol(c), (what, name, err)
+
+
+def test_shade_emulation_lies_inside_the_tolerance():
+  worst = worst_n = 0.0
+  for name in R.SHADE_CASES:
+    c = R.lattice_case(name)
+    for var in R.shade_variants(name):
+      ec = 0.0
+      for h in _hyps(c):
+        cov = R.coverage_exact(c, h)
+        ref, emu = R.shade_float64(c, h, cov, **shade_light(var)), R.emulate_shade_f32(c, h, cov, **shade_light(var))
+        ec = max(ec, float(np.abs(emu['color'] - ref['color']).max()))
+        worst_n = max(worst_n, float(np.abs(emu['normal'] - ref['normal']).max()))
+        if c['claims'].get('exact') and var is None:
+          assert np.array_equal(emu['color'].astype(np.float64), ref['color']), (name, h)
+      scale = R.shade_tol(c, **shade_light(var)) / R.TOL_TEX
+      print('%-18s %-14s emulated colour error %.3e = %.3e x scale %.2f' % (name, var, ec, ec / scale, scale))
+      worst = max(worst, ec / scale)
+  print('emulated max error / scale %.3e (recorded %.3e); normal map %.3e (EMU_ATTR %.3e)' % (worst, R.EMU_TEX, worst_n, R.EMU_ATTR))
+  assert 0.5 * R.EMU_TEX < worst <= R.EMU_TEX and worst_n <= R.EMU_ATTR
+  assert R.TOL_TEX == 4 * R.EMU_TEX
+
+
+def render_shaded(render, c, n, dev=None, **light):
+  """the case's n first hypotheses with nvdiffrast_render's light arguments: dict(color, normal, rast) of numpy arrays"""
+  import torch
+  to = (lambda x: torch.as_tensor(x)) if dev is None else (lambda x: torch.as_tensor(x).to(dev))
+  mt = {k: to(v) for k, v in c['mesh_tensors'].items()}
+  extra = {'rast': None}
+  color, depth, normal = render(K=c['K'], H=c['H'], W=c['W'], ob_in_cams=to(c['poses'][:n]), mesh_tensors=mt, projection_mat=c['projection_mat'],
+                                bbox2d=None if c['bbox2d'] is None else to(c['bbox2d'][:n]), output_size=(c['Ho'], c['Wo']), get_normal=True, extra=extra,
+                                **light)
+  return dict(color=color.cpu().numpy(), normal=normal.cpu().numpy(), rast=extra['rast'].cpu().numpy())
+
+
+@functools.lru_cache(maxsize=None)
+def _shade_reference(name, h, var):
+  """(coverage, float64 images) of a SHADE case, computed once and shared by everything that compares with it; never modified"""
+  c = R.lattice_case(name)
+  cov = R.coverage_exact(c, h)
+  return cov, R.shade_float64(c, h, cov, **shade_light(var))
+
+
+def compare_shaded(c, got, n, what, var=None):
+  """winner exactly on every pixel; colour within shade_tol - bit for bit where the case is exact -, normal map within TOL_ATTR, both exactly 0 outside
+  coverage; tex_atlas: within 1e-5 of a colour step of the face's own colour.  Returns the largest |err| / tol (colour, normal)."""
+  light = shade_light(var)
+  tol = R.shade_tol(c, **light)
+  worst = [0.0, 0.0]
+  for h in range(n):
+    cov, ref = _shade_reference(c['name'], h, var)
+    ids = got['rast'][h][..., 3].astype(np.int64)
+    assert np.array_equal(ids, cov['face'] + 1), (what, c['name'], h)
+    col, nrm = got['color'][h].astype(np.float64), got['normal'][h].astype(np.float64)
+    assert not col[~ref['covered']].any() and not nrm[~ref['covered']].any(), (what, c['name'], h)
+    ec, en = np.abs(col - ref['color']).max(), np.abs(nrm - ref['normal']).max()
+    worst = [max(worst[0], ec / tol), max(worst[1], en / R.TOL_ATTR)]
+    if c['claims'].get('exact') and var is None:
+      assert np.array_equal(col, ref['color']), (what, c['name'], h, ec)
+    if c['claims'].get('atlas'):
+      own = R.atlas_face_colors().astype(np.float64)[cov['face']]
+      step = float(c['mesh_tensors']['tex'].max())
+      bleed = np.abs(col - own)[ref['covered']].max()
+      assert bleed <= 1e-5 * step, (what, h, bleed)
+  print('%s %-18s %-14s largest |err| / tol: colour %.3f (tol %.2e), normal %.3f' % (what, c['name'], var, worst[0], tol, worst[1]))
+  assert worst[0] <= 1 and worst[1] <= 1, (what, c['name'], var, worst)
+  return worst
+
+
+@pytest.mark.parametrize('name', R.SHADE_CASES)
+def test_cpu_mirror_shades_like_the_float64_reference(name):
+  """oracle/render.py (the mirror the kernel is compared with on real meshes) on the independent footing of shade_float64"""
+  from oracle.render import nvdiffrast_render
+  c = R.lattice_case(name)
+  for var in R.shade_variants(name):
+    compare_shaded(c, render_shaded(nvdiffrast_render, c, 5, **shade_light(var)), 5, 'mirror', var)
+
+
+def far_uv_case(U, V):
+  """tex_identity's quad (power-of-two legs: barycentrics of at most 6 bits) with a 5 x 7 texture and ONE uv, of few bits, for all corners, so that the
+  interpolated uv is (U, V) exactly at every pixel; and the colour the contract gives it: x = u Wt - 0.5 and y = v Ht - 0.5 as float32 computes them
+  (the product, then the difference), the indices floor(.) modulo the size in Python integers, the weights the fractional parts."""
+  m = R._Mesh()
+  R._quad(m, 256, 384, 256 + 512, 384 + 256)
+  tex = R._distinct_texture(5, 7, 507)
+  uv = np.array([U, V], np.float32)
+  assert uv[0] == U and uv[1] == V
+  c = R._finish('far_uv', m, {}, tex=tex, corner_uv=np.tile(uv.astype(np.float64), (2, 3, 1)))
+  tex = tex.astype(np.float64)
+  x, y = np.float32(uv[0] * np.float32(7)) - np.float32(0.5), np.float32(uv[1] * np.float32(5)) - np.float32(0.5)
+  x0, y0 = int(np.floor(float(x))), int(np.floor(float(y)))
+  fx, fy = float(x) - x0, float(y) - y0
+  a = tex[y0 % 5, x0 % 7] * (1 - fx) + tex[y0 % 5, (x0 + 1) % 7] * fx
+  b = tex[(y0 + 1) % 5, x0 % 7] * (1 - fx) + tex[(y0 + 1) % 5, (x0 + 1) % 7] * fx
+  return c, a * (1 - fy) + b * fy
+
+
+FAR_UV = [(1e6, -1e6), (-1e6, 1e6), (3 * 2.0 ** 30, -5 * 2.0 ** 30), (-2.0 ** 40, 3 * 2.0 ** 36), (2.0 ** 31, -2.0 ** 31)]
+
+
+@pytest.mark.parametrize('U,V', FAR_UV)
+def test_cpu_mirror_fetch_far_from_the_origin(U, V):
+  """uv = +-1e6 (a million periods away: x = 7e6 - 0.5, exact in float32) and |uv size| beyond the int range, where x is a whole number and the index
+  its residue - reduced in float, since the conversion to int alone cannot hold it: the float32 result equals the contract's exactly"""
+  from oracle.render import nvdiffrast_render
+  c, want = far_uv_case(U, V)
+  got = render_shaded(nvdiffrast_render, c, 1)
+  covered = got['rast'][0][..., 3] > 0
+  assert covered.sum() == 512 and np.array_equal(got['color'][0][covered].astype(np.float64), np.tile(want, (512, 1))), (got['color'][0][covered][0], want)

@@ -33,6 +33,20 @@ TOLERANCES of the float outputs, against interp_float64 (float64 from the lattic
   depth, xyz, colour.  w2 = (1 - u) - v carries the errors of u and v; the attribute is fmaf(u, a0, fmaf(v, a1, w2 a2)).  Normalised by the
     largest |vertex value| of the case the emulation gives at most EMU_ATTR = 1.54e-7 (far64_1600008); TOL_ATTR = 4 x that = 6.2e-7 (times the value range).
   (python -m tests.tools.raster_ref prints both maxima per case; the host test asserts that they stay inside the recorded constants.)
+
+TEXTURE FETCH AND LIGHTING (SHADE_CASES; shade_float64, written from src/Utils.py:185-216 and nvdiffrast's documented dr.texture, not from oracle/).
+  Texel (r, c) of tex[0] (Ht, Wt, 3), row 0 first in memory, has its centre at uv = ((c + 0.5) / Wt, (r + 0.5) / Ht); the fetch at the perspective-
+  correct uv[uv_idx[face]] blends floor(x), floor(x) + 1 and floor(y), floor(y) + 1 of x = u Wt - 0.5, y = v Ht - 0.5, indices modulo the size,
+  weights the fractional parts; no v flip.  Lighting is per vertex and interpolated; then the clip to [0, 1]; the normal map is the normalised
+  interpolation of R n.
+  colour.  The fetch is continuous in uv (a floor that falls on the other side of an integer changes weights 0 / 1 by the same few ulps), with slope
+    (texel-to-texel step) x (texture size); uv carries the errors of u, v and its own fmaf chain relative to max(1, |uv|).  tex_scale(case) is that
+    product (not below 1), shade_tol adds the lighting's factors.  The float32 emulation (emulate_shade_f32) over every SHADE case, hypothesis and light
+    setting gives at most EMU_TEX = 1.73e-7 x scale (tex_perspective: 1.38e-6 at scale 8); TOL_TEX = 4 x that = 6.9e-7 (times the scale: 5.5e-6 for
+    the 16-texel checker, 1.6e-5 for the 8 x 16 texture of distinct texels, 1.2e-6 for lit vertex colours).
+  bit equality (claims['exact']).  On a w = 1 right triangle with power-of-two legs b_k = e_k / a, qs = 1, u, v and w2 are exact; with dyadic uv and
+    dyadic texels so are texc, x, the weights (0 or 1/2) and every blend: the emulation equals float64 bit for bit (host test), and so must the kernel.
+  normal map.  Within TOL_ATTR of a unit vector; the emulation's largest error is 1.27e-7 (lit_*: interpolated normals never shorter than 0.68).
 """
 import functools
 from fractions import Fraction as Fr
@@ -42,7 +56,8 @@ import numpy as np
 W = H = 64
 K = np.array([[64.0, 0, 32.0], [0, 64.0, 32.0], [0, 0, 1.0]])
 EMU_UVZ, EMU_ATTR = 1.25e-7, 1.54e-7
-TOL_UVZ, TOL_ATTR = 4 * EMU_UVZ, 4 * EMU_ATTR
+EMU_TEX = 1.73e-7
+TOL_UVZ, TOL_ATTR, TOL_TEX = 4 * EMU_UVZ, 4 * EMU_ATTR, 4 * EMU_TEX
 DEPTH_GAP = 2.0 ** -10          # competing depths that are not exact in float32 are at least this far apart
 ZCLIP_CAP = 0.02                # share of a slanted triangle's pixels that may lie within TOL_UVZ of z/w = +-1
 RB_SMALL, RB_MEDIUM = 4, 32     # candidate pixels of the size classes (restated in face_classes)
@@ -79,8 +94,10 @@ def _window(bbox):
   return W / (r - l), H / (t - b), (W - r - l) / (r - l), (H - t - b) / (t - b)
 
 
-def _finish(name, m, claims, AB=None, bbox=None, out=(64, 64), shifts=None, real=None, order=None):
-  """lattice mesh -> the case dict.  AB = (A, B): projection_mat row 2 = (0, 0, A, B), z/w = B / w - A; None: the default projection (w = 1 only)."""
+def _finish(name, m, claims, AB=None, bbox=None, out=(64, 64), shifts=None, real=None, order=None, tex=None, corner_uv=None, normals_cam=None, rot=None):
+  """lattice mesh -> the case dict.  AB = (A, B): projection_mat row 2 = (0, 0, A, B), z/w = B / w - A; None: the default projection (w = 1 only).
+  tex (Ht, Wt, 3) with corner_uv (F, 3, 2): a textured case (uv / uv_idx built by _uv_table, no vertex_color).  normals_cam (V, 3): per-vertex normals
+  as the camera is to see them; rot: the poses' rotation R, a signed permutation (exact in float32) - the model holds R^T (position | normal)."""
   Ho, Wo = out
   hw, hh = Fr(Wo, 2), Fr(Ho, 2)
   t00, t11, t30, t31 = _window(bbox)
@@ -94,8 +111,14 @@ def _finish(name, m, claims, AB=None, bbox=None, out=(64, 64), shifts=None, real
     py = -wv * (Y / (16 * hh) - 1 - t31) / (2 * t11)
     assert _f32_exact(px) and _f32_exact(py) and _f32_exact(wv - 1), (name, i, X, Y, wv)
     pos[i] = [float(px), float(py), float(wv - 1)]
+  Rm = np.eye(3, dtype=np.float32) if rot is None else np.asarray(rot, np.float32)
+  assert np.array_equal(Rm @ Rm.T, np.eye(3)) and np.linalg.det(Rm) == 1 and set(np.abs(Rm).ravel()) == {0, 1}, name
+  pos = pos @ Rm                                        # rows R^T p: the pose's R p gives the lattice position back, exactly
+  ncam = np.tile(np.array([0, 0, -1], np.float32), (V, 1)) if normals_cam is None else np.asarray(normals_cam, np.float32)
+  assert ncam.shape == (V, 3)
   faces = np.array(m.f, np.int32).reshape(-1, 3)
   if order is not None:
+    assert corner_uv is None
     faces = faces[np.asarray(order)]
   proj = None
   if AB is not None:
@@ -116,13 +139,40 @@ def _finish(name, m, claims, AB=None, bbox=None, out=(64, 64), shifts=None, real
     assert _f32_exact(tx) and _f32_exact(ty)
     assert all((Fr(dx) / wv).denominator == 1 and (Fr(dy) / wv).denominator == 1 for wv in set(v[2] for v in m.v)), (name, dx, dy)
     poses[h, :3, 3] = [float(tx), float(ty), 1.0]
+    poses[h, :3, :3] = Rm
   rs = np.random.RandomState(len(name) * 7919 + V)
   vcol = (rs.randint(0, 257, (V, 3)) / 256.0).astype(np.float32)
   real = np.arange(len(faces)) if real is None else np.asarray(real)
+  mt = dict(pos=pos, faces=faces, vnormals=ncam @ Rm)
+  if tex is None:
+    mt['vertex_color'] = vcol
+  else:
+    tex = np.asarray(tex, np.float32)
+    assert tex.ndim == 3 and tex.shape[2] == 3 and max(tex.shape[:2]) <= 16
+    mt['uv'], mt['uv_idx'] = _uv_table(np.asarray(corner_uv, np.float64), faces, V, rs)
+    mt['tex'] = tex[None].copy()
   return dict(name=name, Ho=Ho, Wo=Wo, H=H, W=W, K=K.copy(), projection_mat=proj, bbox2d=None if bbox is None else np.tile(np.asarray(bbox, np.float32), (len(shifts), 1)),
               Xq=Xq, Yq=Yq, X=np.rint(Xq).astype(np.int64), Y=np.rint(Yq).astype(np.int64), w=w, zw=zw, faces=faces, real=real, shifts=shifts, poses=poses,
-              mesh_tensors=dict(pos=pos, faces=faces, vnormals=np.tile(np.array([0, 0, -1], np.float32), (V, 1)), vertex_color=vcol),
+              mesh_tensors=mt,
               claims=claims, mesh_diameter=2.0)
+
+
+def _uv_table(corner_uv, faces, V, rs):
+  """(F, 3, 2) uv of every face corner -> uv (rows, 2) float32, uv_idx (F, 3) int32.  Rows 0 .. V - 1 are decoys (what a fetch through `faces` would
+  read), the distinct corner values follow in shuffled order with more decoys between them: uv_idx differs from faces in every entry and there are
+  more uv rows than vertices, as in a baked atlas."""
+  assert corner_uv.shape == faces.shape + (2,) and np.array_equal(corner_uv.astype(np.float32).astype(np.float64), corner_uv)
+  keys = sorted(set(map(tuple, corner_uv.reshape(-1, 2))))
+  slot = rs.permutation(len(keys) + 3)
+  rows = np.zeros((V + len(keys) + 3, 2), np.float32)
+  rows[:] = (rs.randint(0, 33, rows.shape) - 8) / 16.0           # decoys everywhere ...
+  where = {}
+  for k, key in enumerate(keys):
+    rows[V + slot[k]] = key                                      # ... but in the rows in use
+    where[key] = V + slot[k]
+  idx = np.array([[where[tuple(c)] for c in f] for f in corner_uv], np.int32)
+  assert not (idx == faces).any() and len(rows) > V
+  return rows, idx
 
 
 def _c(i):
@@ -407,6 +457,169 @@ def _case_window(kind):
                  shifts=[(0, 0), (128, -128), (-128, 256), (256, 128), (-256, -128)])
 
 
+# ---- textured and lit cases (SHADE_CASES): not part of BASE_CASES / ALL_CASES, whose fill-rule and path claims they do not make ------------------
+def _quad(m, x0, y0, x1, y1, w=(1, 1, 1, 1)):
+  """axis-parallel quad of four SHARED vertices a (x0, y0), b (x1, y0), c (x1, y1), d (x0, y1) (lattice units, rows bottom-up), faces (a, b, c), (a, c, d)"""
+  a, b, c, d = m.vert(x0, y0, w[0]), m.vert(x1, y0, w[1]), m.vert(x1, y1, w[2]), m.vert(x0, y1, w[3])
+  m.f += [(a, b, c), (a, c, d)]
+  return a, b, c, d
+
+
+def _quad_uv(u0, v0, u1, v1):
+  """corner uv of _quad's two faces: (u0, v1) at a (bottom left) ... (u0, v0) at d (top left): v grows DOWN the image, like the texture's rows"""
+  a, b, c, d = (u0, v1), (u1, v1), (u1, v0), (u0, v0)
+  return [(a, b, c), (a, c, d)]
+
+
+def _distinct_texture(Ht, Wt, seed):
+  """every texel and channel distinct, dyadic (k / 512), inside [1/4, 1): exact half / quarter blends, and no value so small that one fp16 ulp of
+  the network tensor falls below the float32 error of the fetch"""
+  n = Ht * Wt * 3
+  assert n <= 384
+  k = 128 + np.random.RandomState(seed).permutation(384)[:n]
+  return (k / 512.0).reshape(Ht, Wt, 3).astype(np.float32)
+
+
+def _case_tex_grid(name, Ht, Wt, px_w, px_h, periods, half):
+  """A w = 1 quad of px_w x px_h pixels showing `periods` repeats of an Ht x Wt texture each way, px_w = periods Wt and px_h = periods Ht: a
+  pixel step is a texel step.  half = 0: corners on pixel CORNERS, every pixel centre is a texel centre (the texel itself); half = 1: corners on
+  pixel CENTRES, every pixel centre is a texel corner (the mean of four texels, the column left of u = 0 being the last one).  Power-of-two legs
+  make the barycentrics, u, v and the fetch position exact in float32 (claims['exact'])."""
+  assert px_w == periods * Wt and px_h == periods * Ht
+  m = _Mesh()
+  i0, j0 = (64 - px_w) // 2, (64 - px_h) // 2
+  x0, y0 = 16 * i0 + 8 * half, 16 * j0 + 8 * half
+  _quad(m, x0, y0, x0 + 16 * px_w, y0 + 16 * px_h)
+  pow2 = (px_w & (px_w - 1)) == 0 and (px_h & (px_h - 1)) == 0
+  return _finish(name, m, dict(exact=pow2, grid=(i0, j0, px_w, px_h, half)), tex=_distinct_texture(Ht, Wt, Ht * 100 + Wt),
+                 corner_uv=_quad_uv(0, 0, periods, periods))
+
+
+def _case_tex_wrap(name, Ht, Wt, offset=(0, 0)):
+  """uv from -1.25 to 2.25 both ways over 56 px between pixel centres 4 and 60: 1/16 of a period per pixel, so the centres 24 and 40 lie exactly on
+  u = 0 and u = 1 (x = -0.5: the last column blended with the first) and likewise on v.  `offset`: whole periods added to every uv (the host
+  test's periodicity check)."""
+  m = _Mesh()
+  _quad(m, _c(4), _c(4), _c(60), _c(60))
+  du, dv = offset
+  return _finish(name, m, dict(wrap=True), tex=_distinct_texture(Ht, Wt, Ht * 100 + Wt), corner_uv=_quad_uv(-1.25 + du, -1.25 + dv, 2.25 + du, 2.25 + dv))
+
+
+def _case_tex_charts():
+  """Two triangles over the diagonal a - c of one quad, each addressing a chart of its own in a 16 x 16 texture of distinct texels: the shared
+  vertices a and c have different uv rows in the two faces (no per-vertex uv exists), the charts differ in place, size and orientation."""
+  m = _Mesh()
+  _quad(m, _c(8), _c(6), _c(56), _c(54), w=(1, 2, 1, 2))
+  rs = np.random.RandomState(77)
+  tex = (rs.permutation(768).reshape(16, 16, 3) / 1024.0 + 0.25).astype(np.float32)
+  uv = [((1 / 16, 1 / 16), (7 / 16, 2 / 16), (6 / 16, 7 / 16)), ((15 / 16, 9 / 16), (9 / 16, 15 / 16), (9 / 16, 10 / 16))]
+  return _finish('tex_charts', m, dict(charts=True), AB=(0.5, 1), tex=tex, corner_uv=uv)
+
+
+ATLAS_T, ATLAS_C = 16, 8           # the atlas of include/foundationpose_amd.h for 8 faces: g = 2, cells of c = 8 texels, m = c - 3 = 5
+
+
+def atlas_face_colors():
+  return np.array([[(f + 1) / 16.0, (16 - f) / 32.0, ((5 * f) % 8 + 1) / 8.0] for f in range(8)], np.float32)
+
+
+def _case_tex_atlas():
+  """Eight faces with the uv and texel ownership of the texture bake's atlas rule (restated from the header): cell k = faces 2k (A: corners at texel
+  centres (0,0), (m,0), (0,m) of the cell, owns i + j <= c - 2) and 2k + 1 (B: (c-1,c-1), (c-1-m,c-1), (c-1,c-1-m), owns i + j >= c); every owned
+  texel holds its face's colour, everything else 0.  General w, so that the interpolated uv carries its float32 rounding."""
+  T, c = ATLAS_T, ATLAS_C
+  mm, g = c - 3, T // c
+  col = atlas_face_colors()
+  tex = np.zeros((T, T, 3), np.float32)
+  m = _Mesh()
+  uv = []
+  ws = [1, 2, 4, 2, 1, 4, 2, 1, 2]
+  grid = [[m.vert(_c(6 + 25 * i), _c(5 + 26 * j), ws[3 * j + i]) for i in range(3)] for j in range(3)]
+  for k in range(4):
+    ci, cj = (k % g) * c, (k // g) * c
+    for j in range(c):
+      for i in range(c):
+        if i + j <= c - 2:
+          tex[cj + j, ci + i] = col[2 * k]
+        elif i + j >= c:
+          tex[cj + j, ci + i] = col[2 * k + 1]
+    ctr = lambda i, j: ((ci + i + 0.5) / T, (cj + j + 0.5) / T)
+    uv += [(ctr(0, 0), ctr(mm, 0), ctr(0, mm)), (ctr(c - 1, c - 1), ctr(c - 1 - mm, c - 1), ctr(c - 1, c - 1 - mm))]
+    gi, gj = k % 2, k // 2
+    a, b, cc, d = grid[gj][gi], grid[gj][gi + 1], grid[gj + 1][gi + 1], grid[gj + 1][gi]
+    m.f += [(a, b, cc), (cc, d, a)] if k % 2 == 0 else [(b, cc, d), (d, a, b)]
+  return _finish('tex_atlas', m, dict(atlas=True), AB=(0.5, 1), tex=tex, corner_uv=uv)
+
+
+def _case_tex_perspective():
+  """A slanted quad, w = 1 on its left and 4 on its right edge (zclip_slant's w layout: 1, 2, 4 at general positions, here on shared vertices), with
+  a 16 x 16 checker whose neighbours differ by 1/2: u interpolated affinely would be off by up to 16 (1/2 - 1/5) = 4.8 texels.  One more face has a
+  vertex 1300 px to the right (list B, the 64-bit record form)."""
+  m = _Mesh()
+  a, b, c, d = m.vert(_c(4), _c(8), 1), m.vert(_c(52), _c(4), 4), m.vert(_c(56), _c(40), 4), m.vert(_c(6), _c(36), 1)
+  m.f += [(a, b, c), (a, c, d)]
+  m.tri((_c(8), _c(58), 1), (_c(28), _c(46), 2), (_c(1300), _c(62), 4))
+  rr, cc = np.mgrid[0:16, 0:16]
+  tex = ((0.25 + 0.5 * ((rr + cc) % 2))[..., None] * np.array([1.0, 0.5, 0.75])).astype(np.float32)
+  uv = _quad_uv(0, 0, 1, 1) + [((0, 0), (0.5, 0.25), (1, 1))]
+  return _finish('tex_perspective', m, dict(general_w=True), AB=(0.5, 1), tex=tex, corner_uv=uv, shifts=[(0, 0), (64, -64), (-64, 64), (64, 64), (-64, 0)])
+
+
+LIT_ROT = np.array([[0, 0, 1], [1, 0, 0], [0, 1, 0]], np.float32)          # 120 degrees about (1, 1, 1): exact, moves every axis, R != R^T
+
+
+def _case_lit(textured):
+  """A 2 x 2 grid of quads on nine shared vertices (w 1 and 2 alternating), posed with LIT_ROT.  Camera-space normals (4, y, z) / 4 with |y|, |z| <= 3:
+  not unit length, different at every vertex, z of either sign (the default light's Lambert term -n_z / |n| is clipped at 0 for about half of them),
+  any two at most 94 degrees apart, so an interpolated normal is never shorter than 0.68 of its vertices' (the normal map stays well conditioned)."""
+  m = _Mesh()
+  ws = [1, 2, 1, 2, 1, 2, 1, 2, 1]
+  grid = [[m.vert(_c(5 + 26 * i), _c(7 + 25 * j), ws[3 * j + i]) for i in range(3)] for j in range(3)]
+  uv = []
+  for j in range(2):
+    for i in range(2):
+      a, b, c, d = grid[j][i], grid[j][i + 1], grid[j + 1][i + 1], grid[j + 1][i]
+      m.f += [(a, b, c), (a, c, d)] if (i + j) % 2 == 0 else [(a, b, d), (b, c, d)]
+      q = _quad_uv(i - 0.5, j - 0.75, i + 0.5, j + 0.25)
+      uv += q if (i + j) % 2 == 0 else [(q[0][0], q[0][1], q[1][2]), (q[0][1], q[0][2], q[1][2])]
+  yz = [(0, -3), (2, 3), (-3, -1), (3, 2), (-1, -2), (-2, 3), (1, 1), (3, -3), (-3, 2)]
+  ncam = np.array([(4, y, z) for y, z in yz], np.float32) / 4
+  kw = dict(tex=_distinct_texture(8, 8, 88), corner_uv=uv) if textured else {}
+  return _finish('lit_tex' if textured else 'lit_vcol', m, dict(lit=True), AB=(0.5, 1), normals_cam=ncam, rot=LIT_ROT, **kw)
+
+
+LIGHTS = {            # name -> nvdiffrast_render's light arguments (use_light = True)
+    'default': dict(),
+    'dir': dict(light_dir=(0.5, -1.0, 1.0)),
+    'pos': dict(light_dir=None, light_pos=(0.5, -0.25, 0.25)),
+    'default_color': dict(light_color=(1.0, 0.75, 0.5)),
+    'dir_color': dict(light_dir=(0.5, -1.0, 1.0), light_color=(1.0, 0.75, 0.5)),
+    'pos_color': dict(light_dir=None, light_pos=(0.5, -0.25, 0.25), light_color=(1.0, 0.75, 0.5)),
+    'bright': dict(w_ambient=0.9, w_diffuse=0.9),          # 0.9 base (1 + d) > 1 wherever base (1 + d) > 1.12: the final clip acts
+}
+
+_SHADE_BUILDERS = {
+    'tex_identity': lambda: _case_tex_grid('tex_identity', 8, 16, 32, 16, 2, 0),
+    'tex_identity_5x7': lambda: _case_tex_grid('tex_identity_5x7', 5, 7, 21, 15, 3, 0),
+    'tex_corners': lambda: _case_tex_grid('tex_corners', 8, 16, 32, 16, 2, 1),
+    'tex_wrap': lambda: _case_tex_wrap('tex_wrap', 4, 8),
+    'tex_wrap_shifted': lambda: _case_tex_wrap('tex_wrap_shifted', 4, 8, offset=(-1, -1)),          # host only: equals tex_wrap
+    'tex_thin_1x1': lambda: _case_tex_wrap('tex_thin_1x1', 1, 1), 'tex_thin_1x6': lambda: _case_tex_wrap('tex_thin_1x6', 1, 6),
+    'tex_thin_6x1': lambda: _case_tex_wrap('tex_thin_6x1', 6, 1),
+    'tex_charts': _case_tex_charts, 'tex_atlas': _case_tex_atlas, 'tex_perspective': _case_tex_perspective,
+    'lit_vcol': lambda: _case_lit(False), 'lit_tex': lambda: _case_lit(True),
+}
+TEX_CASES = ['tex_identity', 'tex_identity_5x7', 'tex_corners', 'tex_wrap', 'tex_thin_1x1', 'tex_thin_1x6', 'tex_thin_6x1', 'tex_charts', 'tex_atlas',
+             'tex_perspective']
+LIT_CASES = ['lit_vcol', 'lit_tex']
+SHADE_CASES = TEX_CASES + LIT_CASES
+
+
+def shade_variants(name):
+  """the light settings a case is rendered with: None (use_light = False) for the texture cases, every entry of LIGHTS for the lit ones"""
+  return sorted(LIGHTS) if name in LIT_CASES else [None]
+
+
 def plan_restated(N, V, F, Ho, Wo, num_cu=256):
   """The launch plan of the rasteriser (strips, face ranges, one-launch form), restated: dict(S, strip_rows, lds_verts, G, Fg, solo)."""
   budget = 148 * 1024
@@ -510,6 +723,8 @@ ALL_CASES = BASE_CASES + PADDED_CASES
 def lattice_case(name):
   if name in _BUILDERS:
     return _BUILDERS[name]()
+  if name in _SHADE_BUILDERS:
+    return _SHADE_BUILDERS[name]()
   if name in ('padded_solo_max', 'padded_solo_over'):
     V = len(lattice_case('centres_small')['X']) + 24
     F = solo_face_limit(V) + (1 if name.endswith('over') else 0)
@@ -627,6 +842,158 @@ def coverage_exact(case, h, XY=None):
   return dict(face=face[::-1].copy(), zw=zwin[::-1].copy(), band=band[::-1].copy(), claims=cl, ok=ok, key=key, lam=lamw[:, ::-1].copy(), win=win[::-1].copy())
 
 
+def _cam64(case, h):
+  """camera-space vertex positions R p + t of hypothesis h in float64 (pts_cam, src/Utils.py:168)"""
+  P = case['poses'][h].astype(np.float64)
+  return case['mesh_tensors']['pos'].astype(np.float64) @ P[:3, :3].T + P[:3, 3]
+
+
+def fetch_float64(tex, tu, tv):
+  """dr.texture(filter_mode='linear'), wrap: texel (r, c) has its centre at uv = ((c + 0.5) / Wt, (r + 0.5) / Ht); x = u Wt - 0.5, y = v Ht - 0.5,
+  bilinear over floor and floor + 1, every index modulo the size, weights the fractional parts.  tex (Ht, Wt, 3), row 0 first in memory; no v flip."""
+  tex = np.asarray(tex, np.float64)
+  Ht, Wt = tex.shape[:2]
+  x, y = np.asarray(tu, np.float64) * Wt - 0.5, np.asarray(tv, np.float64) * Ht - 0.5
+  x0, y0 = np.floor(x), np.floor(y)
+  fx, fy = (x - x0)[..., None], (y - y0)[..., None]
+  c0, r0 = np.mod(x0, Wt).astype(np.int64), np.mod(y0, Ht).astype(np.int64)
+  c1, r1 = (c0 + 1) % Wt, (r0 + 1) % Ht
+  return (1 - fy) * ((1 - fx) * tex[r0, c0] + fx * tex[r0, c1]) + fy * ((1 - fx) * tex[r1, c0] + fx * tex[r1, c1])
+
+
+def _base64(case, uvw, vid, tri):
+  """unlit colour before the clip: the texture at the perspective-correct uv[uv_idx[face]] (src/Utils.py:186-187) or the vertex-colour blend (:189)"""
+  mt = case['mesh_tensors']
+  if 'tex' not in mt:
+    return (uvw[..., None] * mt['vertex_color'].astype(np.float64)[vid]).sum(-2)
+  texc = (uvw[..., None] * mt['uv'].astype(np.float64)[mt['uv_idx'][tri]]).sum(-2)
+  return fetch_float64(mt['tex'][0], texc[..., 0], texc[..., 1])
+
+
+def _fma32(a, b, c):
+  return (np.asarray(a, np.float64) * np.asarray(b, np.float64) + np.asarray(c, np.float64)).astype(np.float32)
+
+
+def _base32(case, u, v, w2, vid, tri):
+  """float32, in the documented order: texc = fmaf(u, uv0, fmaf(v, uv1, w2 uv2)); x = texc Wt - 0.5 (product rounded, then the difference); floor,
+  fx = x - floor; indices modulo the size; ta = t00 + fx (t10 - t00), tb = t01 + fx (t11 - t01), colour = ta + fy (tb - ta), every operation rounded."""
+  f32 = np.float32
+  mt = case['mesh_tensors']
+  if 'tex' not in mt:
+    vc = mt['vertex_color'][vid]
+    return np.stack([_fma32(u, vc[..., 0, c], _fma32(v, vc[..., 1, c], w2 * vc[..., 2, c])) for c in range(3)], -1)
+  tex = mt['tex'][0]
+  Ht, Wt = tex.shape[:2]
+  t = mt['uv'][mt['uv_idx'][tri]]                          # (Ho, Wo, 3, 2)
+  tu = _fma32(u, t[..., 0, 0], _fma32(v, t[..., 1, 0], w2 * t[..., 2, 0]))
+  tv = _fma32(u, t[..., 0, 1], _fma32(v, t[..., 1, 1], w2 * t[..., 2, 1]))
+  x, y = tu * f32(Wt) - f32(0.5), tv * f32(Ht) - f32(0.5)
+  x0, y0 = np.floor(x), np.floor(y)
+  fx, fy = (x - x0)[..., None], (y - y0)[..., None]
+  c0, r0 = x0.astype(np.int64) % Wt, y0.astype(np.int64) % Ht
+  c1, r1 = (c0 + 1) % Wt, (r0 + 1) % Ht
+  ta = tex[r0, c0] + fx * (tex[r0, c1] - tex[r0, c0])
+  tb = tex[r1, c0] + fx * (tex[r1, c1] - tex[r1, c0])
+  out = ta + fy * (tb - ta)
+  assert out.dtype == f32
+  return out
+
+
+def _light_args(use_light=False, light_dir=(0, 0, 1), light_pos=(0, 0, 0), light_color=None, w_ambient=0.8, w_diffuse=0.5):
+  return use_light, light_dir, light_pos, light_color, w_ambient, w_diffuse
+
+
+def shade_float64(case, h, cov=None, **light):
+  """Colour and normal map of hypothesis h in float64, top-down, by src/Utils.py:185-216 (`light`: nvdiffrast_render's use_light, light_dir, light_pos,
+  light_color, w_ambient, w_diffuse): base colour as _base64; per VERTEX d = clip(normalize(R n) . normalize(l), 0, 1), l = -light_dir, or light_pos -
+  p_cam when light_dir is None, interpolated like any attribute; colour = base w_ambient + d (light_color or base) w_diffuse; clip to [0, 1]; zero
+  outside coverage.  normal = normalize(interpolated R n), zero outside coverage.  Returns dict(color, normal, covered, preclip, dvert)."""
+  use_light, light_dir, light_pos, light_color, wa, wd = _light_args(**light)
+  cov = cov or coverage_exact(case, h)
+  g = interp_float64(case, h, cov)
+  uvw, vid, covered = g['uvw'], g['vid'], g['covered']
+  Rm = case['poses'][h][:3, :3].astype(np.float64)
+  nc = case['mesh_tensors']['vnormals'].astype(np.float64) @ Rm.T
+  col = _base64(case, uvw, vid, g['tri'])
+  dvert = None
+  if use_light:
+    if light_dir is not None:
+      l = np.broadcast_to(-np.asarray(light_dir, np.float64), nc.shape)
+    else:
+      l = np.asarray(light_pos, np.float64)[None] - _cam64(case, h)
+    unit = lambda a: a / np.linalg.norm(a, axis=-1, keepdims=True)
+    dvert = (unit(nc) * unit(l)).sum(-1)
+    d = (uvw * np.clip(dvert, 0, 1)[vid]).sum(-1)[..., None]
+    col = col * wa + d * (col if light_color is None else np.asarray(light_color, np.float64)) * wd
+  nrm = (uvw[..., None] * nc[vid]).sum(-2)
+  nrm = nrm / np.where(covered, np.linalg.norm(nrm, axis=-1), 1.0)[..., None]
+  m = covered[..., None]
+  return dict(color=np.where(m, np.clip(col, 0, 1), 0.0), normal=np.where(m, nrm, 0.0), covered=covered, preclip=np.where(m, col, 0.0), dvert=dvert)
+
+
+def emulate_shade_f32(case, h, cov=None, **light):
+  """shade_float64 in float32 in the documented operation order, on emulate_f32's u, v, w2: per vertex nc = R n as an fmaf chain (innermost the last
+  column), nn = sqrt(fmaf(nc0, nc0, fmaf(nc1, nc1, nc2 nc2))); the default light: d = clip(-(nc2 / nn)); otherwise L = -light_dir | light_pos - p_cam,
+  ln likewise, d = clip(fmaf(nc0 / nn, L0 / ln, fmaf(nc1 / nn, L1 / ln, (nc2 / nn) (L2 / ln)))); per pixel d = fmaf(u, d0, fmaf(v, d1, w2 d2)),
+  colour = base w_ambient + (d (light_color | base)) w_diffuse, each operation rounded; normal = fmaf-interpolated nc divided by its fmaf-chain norm."""
+  use_light, light_dir, light_pos, light_color, wa, wd = _light_args(**light)
+  f32 = np.float32
+  cov = cov or coverage_exact(case, h)
+  g = emulate_f32(case, h, cov)
+  (u, v, w2), vid, covered = g['uvw'], g['vid'], g['covered']
+  P = case['poses'][h].astype(f32)
+  n = case['mesh_tensors']['vnormals'].astype(f32)
+  nc = np.stack([_fma32(P[r, 0], n[:, 0], _fma32(P[r, 1], n[:, 1], P[r, 2] * n[:, 2])) for r in range(3)], -1)
+  norm = lambda a: np.maximum(np.sqrt(_fma32(a[..., 0], a[..., 0], _fma32(a[..., 1], a[..., 1], a[..., 2] * a[..., 2]))), f32(1e-12))
+  nn = norm(nc)
+  col = _base32(case, u, v, w2, vid, g['tri'])
+  if use_light:
+    if light_dir is not None and np.array_equal(np.asarray(light_dir, float).reshape(-1), [0, 0, 1]):
+      dv = np.clip(-(nc[:, 2] / nn), f32(0), f32(1))
+    else:
+      if light_dir is not None:
+        L = np.broadcast_to(-np.asarray(light_dir, f32), nc.shape)
+      else:
+        L = np.asarray(light_pos, f32)[None] - _cam64(case, h).astype(f32)
+      ln = norm(L)
+      dv = np.clip(_fma32(nc[:, 0] / nn, L[:, 0] / ln, _fma32(nc[:, 1] / nn, L[:, 1] / ln, (nc[:, 2] / nn) * (L[:, 2] / ln))), f32(0), f32(1))
+    dv = dv[vid]
+    d = _fma32(u, dv[..., 0], _fma32(v, dv[..., 1], w2 * dv[..., 2]))[..., None]
+    lc = col if light_color is None else np.asarray(light_color, f32)
+    col = col * f32(wa) + (d * lc) * f32(wd)
+  ncv = nc[vid]
+  nrm = np.stack([_fma32(u, ncv[..., 0, c], _fma32(v, ncv[..., 1, c], w2 * ncv[..., 2, c])) for c in range(3)], -1)
+  nrm = nrm / norm(nrm)[..., None]
+  assert col.dtype == f32 and nrm.dtype == f32
+  m = covered[..., None]
+  return dict(color=np.where(m, np.clip(col, f32(0), f32(1)), f32(0)), normal=np.where(m, nrm, f32(0)), covered=covered)
+
+
+def tex_scale(case):
+  """What multiplies TOL_TEX for a case's unlit colour.  A bilinear fetch is continuous and piecewise linear in uv with slope (texel-to-texel step)
+  x (texels per unit uv), and the float32 uv carries a few 2^-24 relative to max(1, |uv|): the error is bounded by a multiple of the largest
+  (step between wrap-adjacent texels along an axis) x (size along it), times max(1, largest |uv| in use); not below 1, the blend's own roundings on a
+  value <= 1.  1 for vertex colours."""
+  mt = case['mesh_tensors']
+  if 'tex' not in mt:
+    return 1.0
+  tex = mt['tex'][0].astype(np.float64)
+  Ht, Wt = tex.shape[:2]
+  sx = np.abs(tex - np.roll(tex, 1, axis=1)).max() * Wt
+  sy = np.abs(tex - np.roll(tex, 1, axis=0)).max() * Ht
+  return float(max(1.0, max(sx, sy) * max(1.0, np.abs(mt['uv'][mt['uv_idx']]).max())))
+
+
+def shade_tol(case, **light):
+  """tolerance of the colour image: TOL_TEX x tex_scale unlit; lit, colour = base wa + d (light_color | base) wd carries base's error (wa + wd) times
+  and that of d <= 1 (a few 2^-24 from the two normalisations and the dot product) wd max(1, |light_color|) times"""
+  use_light, light_dir, light_pos, light_color, wa, wd = _light_args(**light)
+  s = tex_scale(case)
+  if use_light:
+    s = s * (wa + wd) + wd * (1.0 if light_color is None else max(1.0, float(np.abs(light_color).max())))
+  return TOL_TEX * s
+
+
 def interp_float64(case, h, cov=None):
   """perspective-correct u, v, z/w, camera-space xyz, depth and vertex-colour blend (use_light = False) of every covered pixel in float64, top-down;
   rast (Ho, Wo, 4) = (u, v, z/w, face id + 1) as dr.rasterize returns it"""
@@ -637,13 +1004,14 @@ def interp_float64(case, h, cov=None):
   q = lam / case['w'][f]
   qs = q.sum(-1, keepdims=True)
   uvw = q / np.where(qs == 0, 1.0, qs)
-  pc = case['mesh_tensors']['pos'].astype(np.float64) + case['poses'][h][:3, 3].astype(np.float64)
+  pc = _cam64(case, h)
   xyz = (uvw[..., None] * pc[f]).sum(-2)
-  col = np.clip((uvw[..., None] * case['mesh_tensors']['vertex_color'].astype(np.float64)[f]).sum(-2), 0, 1)
+  col = np.clip(_base64(case, uvw, f, np.where(covered, cov['face'], case['real'][0])), 0, 1)
   m = covered[..., None]
   rast = np.where(m, np.concatenate([uvw[..., :2], cov['zw'][..., None], (cov['face'] + 1.0)[..., None]], -1), 0.0)
   return dict(rast=rast, xyz=np.where(m, xyz, 0.0), depth=np.where(covered, xyz[..., 2], 0.0), color=np.where(m, col, 0.0), covered=covered,
-              attr_scale=dict(xyz=float(np.abs(pc).max()), depth=float(np.abs(pc[:, 2]).max()), color=1.0))
+              attr_scale=dict(xyz=float(np.abs(pc).max()), depth=float(np.abs(pc[:, 2]).max()), color=1.0), uvw=uvw, vid=f,
+              tri=np.where(covered, cov['face'], case['real'][0]))
 
 
 def emulate_f32(case, h, cov=None):
@@ -675,13 +1043,14 @@ def emulate_f32(case, h, cov=None):
   u, v = q0 / qs, q1 / qs
   w2 = (f32(1) - u) - v
   zw = fma(b[2], z[..., 2], fma(b[1], z[..., 1], b[0] * z[..., 0]))
-  pc = (case['mesh_tensors']['pos'].astype(np.float64) + case['poses'][h][:3, 3].astype(np.float64)).astype(f32)[f]
-  vc = case['mesh_tensors']['vertex_color'][f]
-  att = lambda t: np.stack([fma(u, t[..., 0, c], fma(v, t[..., 1, c], w2 * t[..., 2, c])) for c in range(3)], -1)
-  xyz, col = att(pc), np.clip(att(vc), 0, 1)
+  pc = _cam64(case, h).astype(f32)[f]                     # (exact: transform_check)
+  att = lambda t: np.stack([fma(u, t[..., 0, c], fma(v, t[..., 1, c], w2 * t[..., 2, c])) for c in range(t.shape[-1])], -1)
+  tri = np.where(covered, cov['face'], case['real'][0])
+  xyz, col = att(pc), np.clip(_base32(case, u, v, w2, f, tri), 0, 1)
   m = covered[..., None]
   rast = np.where(m, np.stack([u, v, zw, (cov['face'] + 1).astype(f32)], -1), f32(0))
-  return dict(rast=rast, xyz=np.where(m, xyz, f32(0)), depth=np.where(covered, xyz[..., 2], f32(0)), color=np.where(m, col, f32(0)), covered=covered)
+  return dict(rast=rast, xyz=np.where(m, xyz, f32(0)), depth=np.where(covered, xyz[..., 2], f32(0)), color=np.where(m, col, f32(0)), covered=covered,
+              uvw=(u, v, w2), vid=f, tri=tri)
 
 
 def float_errors(got, ref, skip=None):
