@@ -1,0 +1,302 @@
+// Posing reference views from depth alone: normals of depth maps (fp_depth_normals) and one Gauss-Newton linearisation of point-to-plane
+// ICP between pairs of depth maps with projective association (fp_depth_pairs_align).  The arithmetic is stated in
+// include/foundationpose_amd.h and restated in numpy by tests/depth_icp_oracle.py; this file follows it operation for operation (the
+// library is built without contraction).  The joint solve over all views is the caller's (foundationpose_amd/reconstruct.py).
+//
+// Both kernels move memory.  The normals kernel is one thread per pixel: five depth reads (the pixel and its four neighbours, the rows
+// above and below come from L2) and one 16-byte write.  The pairs kernel has the launch shape of tsdf_align_kernel (tsdf.hip): a workgroup
+// owns (pair, a tile of PA_TILE source pixels); the pair is uniform in the workgroup, so its matrices arrive as scalar loads from the
+// pair table.  A lane takes PA_PIX pixels, PA_THREADS apart (the source reads coalesce), in three passes over them: source normal and
+// depth; then the projection into the target and the two gathers of each pixel (16-byte normal, 4-byte depth) - nothing in this pass
+// depends on a gathered value, so all PA_PIX x 2 gathers are in flight together; then the arithmetic.  The 29 sums are kept in double
+// per lane, added over the wave by the butterfly of device_util.h, over the waves in wave order through LDS, and written to the
+// workgroup's own slot of the slab; depth_pairs_fold_kernel adds the slots of a pair in tile order.  No atomics.  A wave whose 256
+// source pixels have no normal (the background of a masked view) skips passes two and three.
+#include "common.h"
+#include "device_util.h"
+
+#include <math.h>
+
+namespace {
+
+constexpr int PA_THREADS = 256;
+constexpr int PA_PIX = 4;
+constexpr int PA_TILE = PA_THREADS * PA_PIX;      // 1024 source pixels per workgroup
+
+struct DepthCam {
+  float fx, fy, cx, cy;
+  int H, W;
+};
+
+// what a pair (s, t) needs of its two views, as fp32
+struct PairRec {
+  float rcs[9], tcs[3];      // C_s: camera s -> object
+  float rit[9], tit[3];      // D_t: object -> camera t
+  float rct[9];              // the rotation of C_t
+  int s, t, pad;
+};
+
+__device__ __forceinline__ bool depth_ok(float d, float zfar) { return d >= 0.001f && d < zfar; }
+
+__global__ __launch_bounds__(PA_THREADS) void depth_normals_kernel(const float *__restrict__ depth, const uint8_t *__restrict__ mask, DepthCam cam,
+                                                                   float zfar, float max_jump, long long total, float4 *__restrict__ out) {
+  const long long idx = (long long)blockIdx.x * PA_THREADS + threadIdx.x;
+  if (idx >= total) return;
+  const long long hw = (long long)cam.H * cam.W;
+  const long long pix = idx % hw;
+  const int r = (int)(pix / cam.W), c = (int)(pix - (long long)r * cam.W);
+  float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (r >= 1 && r <= cam.H - 2 && c >= 1 && c <= cam.W - 2) {      // the four neighbours are pixels of the same view
+    const float d = depth[idx], dl = depth[idx - 1], dr = depth[idx + 1], du = depth[idx - cam.W], dd = depth[idx + cam.W];
+    bool ok = depth_ok(d, zfar) && depth_ok(dl, zfar) && depth_ok(dr, zfar) && depth_ok(du, zfar) && depth_ok(dd, zfar);
+    if (mask) ok = ok && mask[idx] != 0 && mask[idx - 1] != 0 && mask[idx + 1] != 0 && mask[idx - cam.W] != 0 && mask[idx + cam.W] != 0;
+    ok = ok && fabsf(dl - d) <= max_jump && fabsf(dr - d) <= max_jump && fabsf(du - d) <= max_jump && fabsf(dd - d) <= max_jump;
+    if (ok) {
+      const float kl = ((float)(c - 1) - cam.cx) / cam.fx, kr = ((float)(c + 1) - cam.cx) / cam.fx, kc = ((float)c - cam.cx) / cam.fx;
+      const float ku = ((float)(r - 1) - cam.cy) / cam.fy, kd = ((float)(r + 1) - cam.cy) / cam.fy, km = ((float)r - cam.cy) / cam.fy;
+      const float ax = kr * dr - kl * dl, ay = km * dr - km * dl, az = dr - dl;      // p(r,c+1) - p(r,c-1)
+      const float bx = kc * dd - kc * du, by = kd * dd - ku * du, bz = dd - du;      // p(r+1,c) - p(r-1,c)
+      const float mx = by * az - bz * ay, my = bz * ax - bx * az, mz = bx * ay - by * ax;
+      const float l2 = (mx * mx + my * my) + mz * mz;
+      if (l2 > 0.f) {
+        const float l = sqrtf(l2);
+        o = make_float4(mx / l, my / l, mz / l, 1.f);
+      }
+    }
+  }
+  out[idx] = o;
+}
+
+__global__ __launch_bounds__(PA_THREADS) void depth_pairs_kernel(const float *__restrict__ depth, const float4 *__restrict__ normals, DepthCam cam,
+                                                                 const PairRec *__restrict__ recs, int n_tiles, float dist2_max, float cos_min,
+                                                                 float *__restrict__ rows, double *__restrict__ slab) {
+  __shared__ double red[PA_THREADS / 64][FP_DEPTH_ALIGN_TERMS];
+  const int tid = threadIdx.x;
+  const int tile = blockIdx.x % n_tiles, pr = blockIdx.x / n_tiles;
+  const PairRec &m = recs[pr];
+  const long long hw = (long long)cam.H * cam.W;
+  const size_t src0 = (size_t)m.s * (size_t)hw, tgt0 = (size_t)m.t * (size_t)hw;      // 0 <= s, t < n_views: checked on the host
+
+  // pass 1: the source pixel's normal and depth
+  float d[PA_PIX];
+  float4 ns[PA_PIX];
+  bool ok[PA_PIX];
+  long long pix[PA_PIX];
+#pragma unroll
+  for (int q = 0; q < PA_PIX; ++q) {
+    pix[q] = (long long)tile * PA_TILE + q * PA_THREADS + tid;
+    const bool in = pix[q] < hw;                                   // the last tile of a view is ragged
+    ns[q] = in ? normals[src0 + (size_t)pix[q]] : make_float4(0.f, 0.f, 0.f, 0.f);
+    d[q] = in ? depth[src0 + (size_t)pix[q]] : 0.f;
+    ok[q] = ns[q].w != 0.f;
+  }
+
+  // A wave without a single source normal - most waves of a masked object's view - has nothing to project: its rows are zeros and its
+  // 29 partial sums are +0.0, the value the passes below would arrive at (0.f x 0.f widened and added to +0.0).  Uniform in the wave.
+  if (!__any(ok[0] || ok[1] || ok[2] || ok[3])) {
+    if (rows) {
+#pragma unroll
+      for (int q = 0; q < PA_PIX; ++q)
+        if (pix[q] < hw) {
+          float4 *o = (float4 *)(rows + ((size_t)pr * (size_t)hw + (size_t)pix[q]) * 8);
+          o[0] = o[1] = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    }
+    if ((tid & 63) < FP_DEPTH_ALIGN_TERMS) red[tid >> 6][tid & 63] = 0.0;
+  } else {
+  // pass 2: the point in the object frame and in camera t, its pixel there, the two gathers
+  float x[PA_PIX][3], y[PA_PIX][3], cf[PA_PIX], rf[PA_PIX], dt[PA_PIX];
+  float4 nt[PA_PIX];
+#pragma unroll
+  for (int q = 0; q < PA_PIX; ++q) {
+    const int row = (int)(pix[q] / cam.W), col = (int)(pix[q] - (long long)row * cam.W);
+    const float px = (((float)col - cam.cx) / cam.fx) * d[q], py = (((float)row - cam.cy) / cam.fy) * d[q], pz = d[q];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) x[q][a] = ((m.rcs[a * 3] * px + m.rcs[a * 3 + 1] * py) + m.rcs[a * 3 + 2] * pz) + m.tcs[a];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) y[q][a] = ((m.rit[a * 3] * x[q][0] + m.rit[a * 3 + 1] * x[q][1]) + m.rit[a * 3 + 2] * x[q][2]) + m.tit[a];
+    ok[q] = ok[q] && y[q][2] >= 0.001f;
+    const float u = (cam.fx * y[q][0]) / y[q][2] + cam.cx, v = (cam.fy * y[q][1]) / y[q][2] + cam.cy;
+    cf[q] = floorf(u + 0.5f), rf[q] = floorf(v + 0.5f);
+    // decided in float so that a NaN or a huge value never reaches the cast
+    ok[q] = ok[q] && cf[q] >= 0.f && cf[q] <= (float)(cam.W - 1) && rf[q] >= 0.f && rf[q] <= (float)(cam.H - 1);
+    const size_t tp = tgt0 + (ok[q] ? (size_t)(int)rf[q] * cam.W + (size_t)(int)cf[q] : 0);      // inside view t whenever ok
+    nt[q] = ok[q] ? normals[tp] : make_float4(0.f, 0.f, 0.f, 0.f);
+    dt[q] = ok[q] ? depth[tp] : 0.f;
+  }
+
+  // pass 3: the gates, the row, the sums
+  double acc[FP_DEPTH_ALIGN_TERMS];
+#pragma unroll
+  for (int e = 0; e < FP_DEPTH_ALIGN_TERMS; ++e) acc[e] = 0.0;
+#pragma unroll
+  for (int q = 0; q < PA_PIX; ++q) {
+    bool valid = ok[q] && nt[q].w != 0.f;
+    const float qx = ((cf[q] - cam.cx) / cam.fx) * dt[q], qy = ((rf[q] - cam.cy) / cam.fy) * dt[q], qz = dt[q];
+    const float ex = y[q][0] - qx, ey = y[q][1] - qy, ez = y[q][2] - qz;
+    valid = valid && (ex * ex + ey * ey) + ez * ez < dist2_max;
+    const float nx = nt[q].x, ny = nt[q].y, nz = nt[q].z;
+    float w[3], g[3], no[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) w[a] = (m.rcs[a * 3] * ns[q].x + m.rcs[a * 3 + 1] * ns[q].y) + m.rcs[a * 3 + 2] * ns[q].z;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) g[a] = (m.rit[a * 3] * w[0] + m.rit[a * 3 + 1] * w[1]) + m.rit[a * 3 + 2] * w[2];
+    valid = valid && (g[0] * nx + g[1] * ny) + g[2] * nz >= cos_min;
+    float r = (nx * ex + ny * ey) + nz * ez;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) no[a] = (m.rct[a * 3] * nx + m.rct[a * 3 + 1] * ny) + m.rct[a * 3 + 2] * nz;
+    const float X = x[q][0], Y = x[q][1], Z = x[q][2];
+    float J[6] = {no[0], no[1], no[2], Y * no[2] - Z * no[1], Z * no[0] - X * no[2], X * no[1] - Y * no[0]};
+    if (!valid) {
+#pragma unroll
+      for (int i = 0; i < 6; ++i) J[i] = 0.f;
+      r = 0.f;
+    }
+    if (rows && pix[q] < hw) {
+      float4 *o = (float4 *)(rows + ((size_t)pr * (size_t)hw + (size_t)pix[q]) * 8);
+      o[0] = make_float4(J[0], J[1], J[2], J[3]);
+      o[1] = make_float4(J[4], J[5], r, valid ? 1.f : 0.f);
+    }
+    double Jd[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) Jd[i] = (double)J[i];
+    const double rd = (double)r;
+    int e = 0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+      for (int j = i; j < 6; ++j) acc[e++] += Jd[i] * Jd[j];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) acc[21 + i] += Jd[i] * rd;
+    acc[27] += rd * rd;
+    acc[28] += valid ? 1.0 : 0.0;
+  }
+
+#pragma unroll
+  for (int e = 0; e < FP_DEPTH_ALIGN_TERMS; ++e) {
+    const double s = wave_sum(acc[e]);
+    if ((tid & 63) == 0) red[tid >> 6][e] = s;
+  }
+  }
+  __syncthreads();
+  if (tid < FP_DEPTH_ALIGN_TERMS) {
+    double s = red[0][tid];
+    for (int wv = 1; wv < PA_THREADS / 64; ++wv) s += red[wv][tid];
+    slab[((size_t)pr * n_tiles + tile) * FP_DEPTH_ALIGN_TERMS + tid] = s;
+  }
+}
+
+// one thread per (pair, term): the tiles' slots in tile order
+__global__ __launch_bounds__(64) void depth_pairs_fold_kernel(const double *__restrict__ slab, int n_pairs, int n_tiles, double *__restrict__ sums) {
+  const int t = blockIdx.x * 64 + threadIdx.x;
+  if (t >= n_pairs * FP_DEPTH_ALIGN_TERMS) return;
+  const int p = t / FP_DEPTH_ALIGN_TERMS, e = t % FP_DEPTH_ALIGN_TERMS;
+  const double *sb = slab + (size_t)p * n_tiles * FP_DEPTH_ALIGN_TERMS + e;
+  double s = 0.0;
+  int k = 0;
+  for (; k + 8 <= n_tiles; k += 8) {      // eight loads in flight, added in tile order
+    double v[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] = sb[(size_t)(k + i) * FP_DEPTH_ALIGN_TERMS];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) s += v[i];
+  }
+  for (; k < n_tiles; ++k) s += sb[(size_t)k * FP_DEPTH_ALIGN_TERMS];
+  sums[t] = s;
+}
+
+bool camera_ok(const double *K, DepthCam &cam, int H, int W) {
+  cam = DepthCam{(float)K[0], (float)K[4], (float)K[2], (float)K[5], H, W};
+  return cam.fx > 0.f && cam.fy > 0.f && isfinite(cam.fx) && isfinite(cam.fy) && isfinite(cam.cx) && isfinite(cam.cy);
+}
+
+}  // namespace
+
+extern "C" int fp_depth_normals(fp_ctx *ctx, const float *d_depth, const uint8_t *d_mask, int n_views, int H, int W, const double *K, float zfar,
+                                float max_jump, float *d_normals, void *stream) {
+  // Every check of a value comes before the first look INTO ctx: tests/test_depth_icp_host.py calls this without a GPU, with a pointer
+  // for ctx that must not be dereferenced.  Keep that order when adding checks.
+  FP_REQUIRE(ctx && d_depth && K && d_normals, "fp_depth_normals: null argument");
+  FP_REQUIRE(((uintptr_t)d_normals & 15) == 0, "fp_depth_normals: d_normals is not 16-byte aligned (it is written as float4)");
+  FP_REQUIRE(n_views >= 0 && n_views <= FP_TSDF_MAX_VIEWS, "fp_depth_normals: n_views %d (0 .. %d)", n_views, FP_TSDF_MAX_VIEWS);
+  FP_REQUIRE(H >= 1 && W >= 1, "fp_depth_normals: H %d, W %d", H, W);
+  FP_REQUIRE(zfar > 0.f, "fp_depth_normals: zfar %g (> 0)", (double)zfar);
+  FP_REQUIRE(max_jump > 0.f, "fp_depth_normals: max_jump %g (> 0)", (double)max_jump);
+  DepthCam cam;
+  FP_REQUIRE(camera_ok(K, cam, H, W), "fp_depth_normals: K is not a finite camera matrix with positive focal lengths");
+  const long long total = (long long)n_views * H * W;
+  const long long blocks = (total + PA_THREADS - 1) / PA_THREADS;
+  FP_REQUIRE(blocks <= 0x7fffffff, "fp_depth_normals: %d views of %d x %d pixels are too many for one launch", n_views, H, W);
+  if (n_views == 0) return FP_OK;
+  hipLaunchKernelGGL(depth_normals_kernel, dim3((unsigned)blocks), dim3(PA_THREADS), 0, (hipStream_t)stream, d_depth, d_mask, cam, zfar, max_jump,
+                     total, (float4 *)d_normals);
+  FP_CHECK_HIP(hipGetLastError());
+  return FP_OK;
+}
+
+extern "C" int fp_depth_pairs_align(fp_ctx *ctx, const float *d_depth, const float *d_normals, int n_views, int H, int W, const double *K,
+                                    const double *cam_in_ob, const int32_t *pairs, int n_pairs, float dist_max, float cos_min, float *d_rows,
+                                    double *h_sums, void *stream) {
+  // As above: every check of a value before the first look into ctx.
+  FP_REQUIRE(ctx && d_depth && d_normals && K && cam_in_ob && h_sums, "fp_depth_pairs_align: null argument");
+  FP_REQUIRE(((uintptr_t)d_normals & 15) == 0, "fp_depth_pairs_align: d_normals is not 16-byte aligned (it is read as float4)");
+  FP_REQUIRE(((uintptr_t)d_rows & 15) == 0, "fp_depth_pairs_align: d_rows is not 16-byte aligned (it is written as float4)");
+  FP_REQUIRE(n_views >= 0 && n_views <= FP_TSDF_MAX_VIEWS, "fp_depth_pairs_align: n_views %d (0 .. %d)", n_views, FP_TSDF_MAX_VIEWS);
+  FP_REQUIRE(n_pairs >= 0 && n_pairs <= FP_DEPTH_ALIGN_MAX_PAIRS, "fp_depth_pairs_align: n_pairs %d (0 .. %d)", n_pairs, FP_DEPTH_ALIGN_MAX_PAIRS);
+  FP_REQUIRE(pairs || n_pairs == 0, "fp_depth_pairs_align: null pairs");
+  FP_REQUIRE(H >= 1 && W >= 1, "fp_depth_pairs_align: H %d, W %d", H, W);
+  FP_REQUIRE(dist_max > 0.f, "fp_depth_pairs_align: dist_max %g (> 0)", (double)dist_max);
+  FP_REQUIRE(cos_min >= -1.f && cos_min <= 1.f, "fp_depth_pairs_align: cos_min %g (-1 .. 1)", (double)cos_min);
+  DepthCam cam;
+  FP_REQUIRE(camera_ok(K, cam, H, W), "fp_depth_pairs_align: K is not a finite camera matrix with positive focal lengths");
+  for (int v = 0; v < n_views; ++v) {
+    const double *m = cam_in_ob + (size_t)v * 16;
+    for (int e = 0; e < 12; ++e) FP_REQUIRE(isfinite(m[e]), "fp_depth_pairs_align: cam_in_ob[%d] is not finite", v);
+    FP_REQUIRE(m[12] == 0 && m[13] == 0 && m[14] == 0 && m[15] == 1, "fp_depth_pairs_align: the last row of cam_in_ob[%d] is not 0 0 0 1", v);
+  }
+  std::vector<PairRec> recs((size_t)n_pairs);
+  for (int p = 0; p < n_pairs; ++p) {
+    const int s = pairs[2 * p], t = pairs[2 * p + 1];
+    FP_REQUIRE(s >= 0 && s < n_views && t >= 0 && t < n_views, "fp_depth_pairs_align: pair %d = (%d, %d) of %d views", p, s, t, n_views);
+    FP_REQUIRE(s != t, "fp_depth_pairs_align: pair %d joins view %d to itself", p, s);
+    const double *ms = cam_in_ob + (size_t)s * 16, *mt = cam_in_ob + (size_t)t * 16;
+    PairRec &r = recs[p];
+    for (int a = 0; a < 3; ++a) {
+      for (int i = 0; i < 3; ++i) {
+        r.rcs[a * 3 + i] = (float)ms[a * 4 + i];
+        r.rct[a * 3 + i] = (float)mt[a * 4 + i];
+        r.rit[a * 3 + i] = (float)mt[i * 4 + a];
+      }
+      r.tcs[a] = (float)ms[a * 4 + 3];
+      r.tit[a] = (float)(-((mt[a] * mt[3] + mt[4 + a] * mt[7]) + mt[8 + a] * mt[11]));
+    }
+    r.s = s, r.t = t, r.pad = 0;
+  }
+  const long long n_tiles = ((long long)H * W + PA_TILE - 1) / PA_TILE;
+  FP_REQUIRE(n_tiles * FP_DEPTH_ALIGN_MAX_PAIRS <= 0x7fffffff, "fp_depth_pairs_align: %d x %d pixels are too many for one launch", H, W);
+  if (n_pairs == 0) return FP_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const size_t slab_bytes = (size_t)n_pairs * (size_t)n_tiles * FP_DEPTH_ALIGN_TERMS * sizeof(double);
+  const size_t sums_bytes = (size_t)n_pairs * FP_DEPTH_ALIGN_TERMS * sizeof(double);
+  const size_t recs_bytes = (size_t)n_pairs * sizeof(PairRec);
+  FP_TRY(fp_arena_ensure(ctx, slab_bytes + sums_bytes + recs_bytes + 4096));
+  ArenaScope scope(ctx->arena);
+  double *slab = (double *)ctx->arena.take(slab_bytes);
+  double *sums = (double *)ctx->arena.take(sums_bytes);
+  PairRec *d_recs = (PairRec *)ctx->arena.take(recs_bytes);
+  FP_REQUIRE(slab && sums && d_recs, "fp_depth_pairs_align: arena exhausted");
+  // `recs` outlives the copy: the stream is synchronised before this returns
+  FP_CHECK_HIP(hipMemcpyAsync(d_recs, recs.data(), recs_bytes, hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(depth_pairs_kernel, dim3((unsigned)(n_tiles * n_pairs)), dim3(PA_THREADS), 0, s, d_depth, (const float4 *)d_normals, cam,
+                     (const PairRec *)d_recs, (int)n_tiles, dist_max * dist_max, cos_min, d_rows, slab);
+  FP_CHECK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(depth_pairs_fold_kernel, dim3((unsigned)((n_pairs * FP_DEPTH_ALIGN_TERMS + 63) / 64)), dim3(64), 0, s, (const double *)slab,
+                     n_pairs, (int)n_tiles, sums);
+  FP_CHECK_HIP(hipGetLastError());
+  // the slab, the sums and the pair table go back to the arena when this returns: the stream has been synchronised by then
+  hipError_t e1 = hipMemcpyAsync(h_sums, sums, sums_bytes, hipMemcpyDeviceToHost, s);
+  hipError_t e2 = hipStreamSynchronize(s);      // also after a failed copy: `recs` and the arena must not be in use when this returns
+  FP_CHECK_HIP(e1);
+  FP_CHECK_HIP(e2);
+  return FP_OK;
+}

@@ -6,8 +6,10 @@ folder layout and does something else: the depth maps are 
 coloured triangle mesh is extracted by marching tetrahedra, both on the GPU (csrc/tsdf.hip; the arithmetic is stated in
 include/foundationpose_amd.h).  The poses of the reference views can be refined first (refine_view_poses, reconstruct_object(...,
 refine_poses=True)): each view's depth map is aligned rigidly to the geometry fused so far, frame-to-model Gauss-Newton on the volume
-(fp_tsdf_align builds the normal equations on the GPU, the 6x6 solves run on the host).  There is no joint bundle adjustment over all
-views, no photometric term and no view-dependent appearance.
+(fp_tsdf_align builds the normal equations on the GPU, the 6x6 solves run on the host).  They can also be refined jointly, or estimated
+when the folder has none, from depth alone: point-to-plane ICP between pairs of depth maps, linearised for all pairs in one launch
+(fp_depth_pairs_align, csrc/depth_icp.hip) and solved for all views at once on the host (joint_refine_view_poses, estimate_view_poses).
+Joint geometric alignment; still no photometric term and no view-dependent appearance.
 """
 import ctypes
 import glob
@@ -246,11 +248,12 @@ def volume_from_views(depths, masks, K, cam_in_obs, voxel_size, margin=None, dev
   return origin, dims
 
 
-def load_reference_views(dir, depth_dir=None, mask_dir='mask'):
+def load_reference_views(dir, depth_dir=None, mask_dir='mask', poses=True):
   """The reference's folder of reference views (bundlesdf/run_nerf.py: run_one_ob): rgb/NAME.png; depth as 16-bit PNG in millimetres
   under `depth_dir` (default: depth_enhanced/ when it exists, else depth/), read as value / 1e3 in float64 and cast to float32;
   `mask_dir`/NAME.png (non-zero = object); cam_in_ob/NAME.txt (4x4, camera-to-object); K.txt.  Returns a dict: rgbs (n,H,W,3) uint8,
-  depths (n,H,W) float32 metres, masks (n,H,W) uint8, K (3,3), cam_in_obs (n,4,4) float64, names."""
+  depths (n,H,W) float32 metres, masks (n,H,W) uint8, K (3,3), cam_in_obs (n,4,4) float64, names.  poses=False does not read cam_in_ob/
+  (a folder that is still to be posed: estimate_view_poses) and returns no cam_in_obs."""
   from PIL import Image
   files = sorted(glob.glob(os.path.join(dir, 'rgb', '*.png')))
   if not files:
@@ -258,7 +261,7 @@ def load_reference_views(dir, depth_dir=None, mask_dir='mask'):
   if depth_dir is None:
     depth_dir = 'depth_enhanced' if os.path.isdir(os.path.join(dir, 'depth_enhanced')) else 'depth'
   names = [os.path.splitext(os.path.basename(f))[0] for f in files]
-  rgbs, depths, masks, poses = [], [], [], []
+  rgbs, depths, masks, cams = [], [], [], []
   for name, f in zip(names, files):
     rgbs.append(np.asarray(Image.open(f).convert('RGB'), dtype=np.uint8))
     d = np.asarray(Image.open(os.path.join(dir, depth_dir, name + '.png')))
@@ -267,9 +270,12 @@ def load_reference_views(dir, depth_dir=None, mask_dir='mask'):
     depths.append((d.astype(np.float64) / 1e3).astype(np.float32))
     m = np.asarray(Image.open(os.path.join(dir, mask_dir, name + '.png')))
     masks.append(((m if m.ndim == 2 else m.max(-1)) > 0).astype(np.uint8))
-    poses.append(np.loadtxt(os.path.join(dir, 'cam_in_ob', name + '.txt')).reshape(4, 4))
-  return dict(rgbs=np.stack(rgbs), depths=np.stack(depths), masks=np.stack(masks), K=np.loadtxt(os.path.join(dir, 'K.txt')).reshape(3, 3),
-              cam_in_obs=np.stack(poses), names=names)
+    if poses:
+      cams.append(np.loadtxt(os.path.join(dir, 'cam_in_ob', name + '.txt')).reshape(4, 4))
+  out = dict(rgbs=np.stack(rgbs), depths=np.stack(depths), masks=np.stack(masks), K=np.loadtxt(os.path.join(dir, 'K.txt')).reshape(3, 3), names=names)
+  if poses:
+    out['cam_in_obs'] = np.stack(cams)
+  return out
 
 
 def largest_component(faces, n_vertices):
@@ -374,15 +380,253 @@ def _refine_on(depths, views, voxel_size, anchor, order, rounds, trunc, margin, 
   return poses, info
 
 
+# ---- posing views from depth alone: pairwise point-to-plane ICP, solved jointly (csrc/depth_icp.hip) ----------------------------------
+DEFAULT_STAGES = ((0.020, 0.5, 6), (0.010, 0.5, 6), (0.005, 0.7, 8))            # (dist_max metres, cos_min, steps) of joint_refine_view_poses
+ODOMETRY_STAGES = ((0.030, 0.3, 8), (0.015, 0.5, 6), (0.0075, 0.7, 6))          # estimate_view_poses: a new view against the views before it
+ESTIMATE_JOINT_STAGES = ((0.010, 0.5, 8), (0.005, 0.7, 8))                      # estimate_view_poses: the joint pass behind the odometry
+MAX_PAIRS = _lib.FP_DEPTH_ALIGN_MAX_PAIRS
+
+
+def _host_poses(cam_in_obs):
+  return np.ascontiguousarray(np.asarray(torch.as_tensor(cam_in_obs).cpu(), dtype=np.float64).reshape(-1, 4, 4))
+
+
+def depth_normals(depths, K, masks=None, zfar=np.inf, max_jump=0.01, device='cuda'):
+  """fp_depth_normals: (n,H,W,4) float32 device tensor - per pixel the unit normal facing the camera and 1, or four zeros where the pixel,
+  one of its four neighbours or the depth step to one of them (max_jump, metres) rules a normal out.  depths (n,H,W) metres, masks
+  (n,H,W) non-zero = object; numpy arrays or device tensors.  Nothing synchronises."""
+  dev = depths.device if torch.is_tensor(depths) and depths.is_cuda else _device(device)
+  depths = torch.as_tensor(depths, device=dev).to(torch.float).contiguous()
+  if depths.dim() == 2:
+    depths = depths[None]
+  n, H, W = depths.shape
+  if masks is not None:
+    masks = torch.as_tensor(masks, device=dev)
+    if tuple(masks.shape) != (n, H, W):
+      raise ValueError(f'masks must have the shape {(n, H, W)}, got {tuple(masks.shape)}')
+    masks = (masks != 0).to(torch.uint8).contiguous()
+  Kd, Kp = _lib.k_ptr(K)
+  out = torch.empty((n, H, W, 4), dtype=torch.float, device=dev)
+  zf = float(zfar) if np.isfinite(zfar) else float('inf')
+  for a in range(0, n, MAX_VIEWS):      # views are independent: more than MAX_VIEWS are cut into calls
+    b = min(a + MAX_VIEWS, n)
+    check(lib().fp_depth_normals(_lib.Context.get(dev).handle, ptr(depths[a:b]), None if masks is None else ptr(masks[a:b]), b - a, H, W, Kp, zf,
+                                 float(max_jump), ptr(out[a:b]), stream_ptr(dev)))
+  return out
+
+
+def align_pairs_step(depths, normals, K, cam_in_obs, pairs, dist_max, cos_min, rows=False):
+  """One linearisation of point-to-plane ICP for every directed pair (s, t) of `pairs` (fp_depth_pairs_align): the pixels of view s
+  are projected into view t.  depths (n,H,W) and normals (n,H,W,4, of depth_normals) are device tensors.  Returns the (P,29) float64
+  array of the header - per pair the upper triangle of J^T J, J^T r, sum r^2, the number of valid pixels - and, with rows=True, the
+  (P,H,W,8) float32 device tensor of the per-pixel rows.  Synchronises.  More than MAX_PAIRS pairs are cut into calls (a pair's numbers
+  do not depend on the batch it is in)."""
+  dev = normals.device
+  depths = torch.as_tensor(depths, device=dev).to(torch.float).contiguous()
+  normals = normals.contiguous()
+  n, H, W = depths.shape
+  if tuple(normals.shape) != (n, H, W, 4) or normals.dtype != torch.float:
+    raise ValueError(f'normals must be float32 of shape {(n, H, W, 4)}, got {normals.dtype} {tuple(normals.shape)}')
+  poses = _host_poses(cam_in_obs)
+  if len(poses) != n:
+    raise ValueError(f'{n} depth maps, {len(poses)} poses')
+  pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+  P = len(pairs)
+  Kd, Kp = _lib.k_ptr(K)
+  ctx = _lib.Context.get(dev)
+  sums = np.zeros((P, _lib.FP_DEPTH_ALIGN_TERMS), dtype=np.float64)
+  out = torch.empty((P, H, W, 8), dtype=torch.float, device=dev) if rows else None
+  for a in range(0, P, MAX_PAIRS):
+    b = min(a + MAX_PAIRS, P)
+    part = np.zeros((b - a, _lib.FP_DEPTH_ALIGN_TERMS), dtype=np.float64)
+    check(lib().fp_depth_pairs_align(ctx.handle, ptr(depths), ptr(normals), n, H, W, Kp, ptr(poses), ptr(np.ascontiguousarray(pairs[a:b])), b - a,
+                                     float(dist_max), float(cos_min), None if out is None else ptr(out[a:b]), ptr(part), stream_ptr(dev)))
+    sums[a:b] = part
+  return (sums, out) if rows else sums
+
+
+def _pair_blocks(sums, pairs, n_views):
+  """H (n,n,6,6), g (n,6) and the valid count per view: pair (s,t) adds its A to the diagonal blocks of s and t and subtracts it from the
+  blocks (s,t) and (t,s), adds its b to g[s] and subtracts it from g[t] - dr/dxi_t is -J (include/foundationpose_amd.h)."""
+  Hm, g, cnt = np.zeros((n_views, n_views, 6, 6)), np.zeros((n_views, 6)), np.zeros(n_views)
+  iu = np.triu_indices(6)
+  for k, (s, t) in enumerate(np.asarray(pairs, dtype=np.int64).reshape(-1, 2)):
+    A = np.zeros((6, 6))
+    A[iu] = sums[k][:21]
+    A = A + np.triu(A, 1).T
+    b = np.asarray(sums[k][21:27], dtype=np.float64)
+    Hm[s, s] += A
+    Hm[t, t] += A
+    Hm[s, t] -= A
+    Hm[t, s] -= A
+    g[s] += b
+    g[t] -= b
+    cnt[s] += sums[k][28]
+    cnt[t] += sums[k][28]
+  return Hm, g, cnt
+
+
+def solve_joint_step(sums, pairs, n_views, fixed, damping=1e-9):
+  """The joint Gauss-Newton step of all views from the (P,29) sums of align_pairs_step: the 6n x 6n system of _pair_blocks with the rows
+  and columns of the `fixed` views removed and damping x trace of each diagonal block added to that block, solved in float64.  A free
+  view without a valid residual is taken out as well and keeps its pose.  Returns (twists (n,6) - cam_in_ob <- expm_se3(xi) cam_in_ob,
+  zero for fixed and dropped views -, dropped: the list of those views)."""
+  Hm, g, cnt = _pair_blocks(sums, pairs, n_views)
+  fixed = set(int(v) for v in fixed)
+  dropped = [v for v in range(n_views) if v not in fixed and cnt[v] == 0]
+  free = [v for v in range(n_views) if v not in fixed and cnt[v] > 0]
+  xi = np.zeros((n_views, 6))
+  if not free:
+    return xi, dropped
+  M = np.zeros((6 * len(free), 6 * len(free)))
+  for a, u in enumerate(free):
+    for b, v in enumerate(free):
+      M[6 * a:6 * a + 6, 6 * b:6 * b + 6] = Hm[u, v]
+    M[6 * a:6 * a + 6, 6 * a:6 * a + 6] += damping * np.trace(Hm[u, u]) * np.eye(6)
+  sol = np.linalg.solve(M, -np.concatenate([g[v] for v in free]))
+  for a, v in enumerate(free):
+    xi[v] = sol[6 * a:6 * a + 6]
+  return xi, dropped
+
+
+def choose_pairs(cam_in_obs, neighbours=4, max_angle_deg=100):
+  """Directed pairs (s, t): for every view s the `neighbours` views whose optical axes make the smallest angle with its own, among those
+  within max_angle_deg; ties go to the lowest index."""
+  poses = _host_poses(cam_in_obs)
+  cos = poses[:, :3, 2] @ poses[:, :3, 2].T
+  lim = np.cos(np.deg2rad(max_angle_deg))
+  out = []
+  for s in range(len(poses)):
+    cand = [t for t in range(len(poses)) if t != s and cos[s, t] >= lim]
+    cand.sort(key=lambda t: -cos[s, t])            # stable: the lowest index among equals
+    out += [(s, t) for t in cand[:neighbours]]
+  return out
+
+
+def _joint_on(depths, normals, K, poses, fixed, pairs, stages, neighbours, max_angle_deg, damping):
+  """The loop of joint_refine_view_poses on prepared device tensors; `fixed`: the views that are not moved."""
+  poses = poses.copy()
+  n = len(poses)
+  info = dict(rms=[], valid=[], pairs=[], stopped={}, after_first=None, eig_ratio=np.full(n, np.nan))
+  pr = [] if pairs is None else [tuple(int(i) for i in p) for p in pairs]
+  gate = (stages[-1][0], stages[-1][1]) if len(stages) else (DEFAULT_STAGES[-1][0], DEFAULT_STAGES[-1][1])
+
+  def evaluate():
+    sm = align_pairs_step(depths, normals, K, poses, pr, *gate)
+    cnt = float(sm[:, 28].sum())
+    info['valid'].append(cnt)
+    info['rms'].append(float(np.sqrt(sm[:, 27].sum() / max(cnt, 1.0))))
+    return sm
+  for dist_max, cos_min, steps in stages:
+    if pairs is None:
+      pr = choose_pairs(poses, neighbours, max_angle_deg)
+    gate = (dist_max, cos_min)
+    info['pairs'].append(list(pr))
+    for _ in range(int(steps)):
+      xi, dropped = solve_joint_step(evaluate(), pr, n, fixed, damping)
+      for v in dropped:
+        info['stopped'][v] = 'no valid residual'
+      for v in range(n):
+        if xi[v].any():
+          poses[v] = expm_se3(xi[v]) @ poses[v]
+      if info['after_first'] is None:
+        info['after_first'] = poses.copy()
+  Hm, _, _ = _pair_blocks(evaluate(), pr, n)
+  for v in range(n):
+    w = np.linalg.eigvalsh(Hm[v, v])
+    if w[-1] > 0:
+      info['eig_ratio'][v] = w[0] / w[-1]
+  info['rms'], info['valid'] = np.array(info['rms']), np.array(info['valid'])
+  return poses, info
+
+
+def _check_view_count(n):
+  if n > MAX_VIEWS:
+    raise ValueError(f'{n} views: the pairwise alignment takes at most {MAX_VIEWS} per call')
+
+
+def joint_refine_view_poses(views, anchor=0, pairs=None, stages=DEFAULT_STAGES, neighbours=4, max_angle_deg=100, depth_filter=True, max_jump=0.01,
+                            damping=1e-9, device='cuda'):
+  """Joint refinement of the reference views' poses from depth alone.  `views` as for reconstruct_object (at most 64).  Every view is
+  linked to its `neighbours` nearest views by optical axis (choose_pairs; or `pairs`, a list of directed (s, t)); per stage (dist_max
+  metres, cos_min, steps) the pairs are chosen from the current poses and `steps` joint Gauss-Newton steps are taken - each one
+  fp_depth_pairs_align launch sequence over all pairs (point-to-plane residuals of view s's pixels against the surface view t sees at
+  their projection, gated by distance and by the angle between the two normals) and one solve of the 6n x 6n system on the host - and
+  one closing evaluation ends the call.  The anchor fixes the gauge and keeps its bits.  The basin is the first stage's gate
+  (centimetres), not a voxel size; no volume is built.  Depths are prepared as for refine_view_poses (erode_depth only); normals are
+  one-pixel central differences of those maps, skipped where a neighbour is more than max_jump away.  Geometry only: on a rotationally
+  symmetric object the rotation about its axis is unobservable.  Returns (cam_in_obs (n,4,4) float64, info): rms and valid (one entry
+  per evaluation, over all pairs), pairs (per stage), stopped {view: reason} - a free view without a valid residual keeps its pose -,
+  after_first (the poses after the first step) and eig_ratio (per view the smallest over the largest eigenvalue of its 6x6 diagonal
+  block at the closing evaluation: a value orders of magnitude below the others marks a weakly constrained view)."""
+  if isinstance(views, (str, os.PathLike)):
+    views = load_reference_views(views)
+  dev = _device(device)
+  poses = _host_poses(views['cam_in_obs']).copy()
+  n = len(poses)
+  _check_view_count(n)
+  if not 0 <= anchor < n:
+    raise ValueError(f'anchor {anchor} of {n} views')
+  depths = _eroded_depths(views, depth_filter, dev).contiguous()
+  normals = depth_normals(depths, views['K'], views.get('masks'), max_jump=max_jump, device=dev)
+  return _joint_on(depths, normals, views['K'], poses, [anchor], pairs, stages, neighbours, max_angle_deg, damping)
+
+
+def _centroid_pose(depth, mask, K, dev):
+  """Identity rotation and the translation that puts the centroid of the view's valid masked points at the object's origin."""
+  from .Utils import depth2xyzmap
+  xyz = depth2xyzmap(depth.contiguous(), K)
+  keep = xyz[..., 2] >= 0.001
+  if mask is not None:
+    keep &= torch.as_tensor(mask, device=dev) != 0
+  pts = xyz[keep].to(torch.float64)
+  if len(pts) == 0:
+    raise ValueError('estimate_view_poses: the first view has no valid masked depth pixel')
+  m = np.eye(4)
+  m[:3, 3] = -pts.mean(0).cpu().numpy()
+  return m
+
+
+def estimate_view_poses(views, first_pose=None, window=2, stages=ODOMETRY_STAGES, joint=True, joint_stages=ESTIMATE_JOINT_STAGES, neighbours=4,
+                        max_angle_deg=60, depth_filter=True, max_jump=0.01, damping=1e-9, device='cuda'):
+  """Poses for views that have none: a masked RGB-D sequence in which neighbouring frames overlap (`views` without cam_in_obs; a folder
+  is read with load_reference_views(poses=False); at most 64 views).  View 0 gets first_pose, or the identity rotation with the
+  translation that puts the centroid of its valid masked points at the origin - the object frame is then view 0's camera frame moved
+  to the object.  View k starts at view k-1's pose and is solved alone against views k-window .. k-1 (pairs in both directions, those
+  views fixed) over `stages`; then, with joint=True, the joint pass of joint_refine_view_poses runs over all views (joint_stages,
+  neighbours, max_angle_deg; view 0 fixed), which closes loops that the odometry leaves open by less than its first gate.  A frame-to-
+  frame step beyond the odometry's first gate (3 cm) is lost and not recovered.  Returns (cam_in_obs (n,4,4) float64, info: odometry -
+  the poses before the joint pass -, joint - that pass's info or None)."""
+  if isinstance(views, (str, os.PathLike)):
+    views = load_reference_views(views, poses=False)
+  dev = _device(device)
+  depths = _eroded_depths(views, depth_filter, dev).contiguous()
+  n = len(depths)
+  _check_view_count(n)
+  masks, K = views.get('masks'), views['K']
+  normals = depth_normals(depths, K, masks, max_jump=max_jump, device=dev)
+  first = _centroid_pose(depths[0], None if masks is None else masks[0], K, dev) if first_pose is None else _host_poses(first_pose)[0]
+  poses = np.stack([first] * n)
+  for k in range(1, n):
+    poses[k] = poses[k - 1]
+    refs = list(range(max(0, k - int(window)), k))
+    pr = [(k, j) for j in refs] + [(j, k) for j in refs]
+    poses, _ = _joint_on(depths, normals, K, poses, [v for v in range(n) if v != k], pr, stages, neighbours, max_angle_deg, damping)
+  info = dict(odometry=poses.copy(), joint=None)
+  if joint:
+    poses, info['joint'] = _joint_on(depths, normals, K, poses, [0], None, joint_stages, neighbours, max_angle_deg, damping)
+  return poses, info
+
+
 def reconstruct_object(views, voxel_size=0.002, trunc=None, min_weight=1, depth_filter=True, margin=None, device='cuda', refine_poses=False,
-                       max_vertices=None, simplify_cell=None, components='largest', texture=None, symmetries=None):
+                       max_vertices=None, simplify_cell=None, components='largest', texture=None, symmetries=None, estimate_poses=False):
   """_reconstruct_mesh (which documents every other argument) and, with `symmetries`, the rotational symmetries of the finished mesh:
   symmetries=True runs Utils.find_symmetries with its defaults, a dict gives its keyword arguments (tol, max_order, ..), and the call
   then returns (mesh, info) - info['symmetry_tfs'] is what FoundationPose(symmetry_tfs=) takes, and bop.write_models_info writes the
   rest to models_info.json.  The default (None or False) returns the mesh alone, as before."""
   mesh = _reconstruct_mesh(views, voxel_size=voxel_size, trunc=trunc, min_weight=min_weight, depth_filter=depth_filter, margin=margin,
                            device=device, refine_poses=refine_poses, max_vertices=max_vertices, simplify_cell=simplify_cell,
-                           components=components, texture=texture)
+                           components=components, texture=texture, estimate_poses=estimate_poses)
   if symmetries is None or symmetries is False:
     return mesh
   from .Utils import find_symmetries
@@ -391,7 +635,7 @@ def reconstruct_object(views, voxel_size=0.002, trunc=None, min_weight=1, depth_
 
 
 def _reconstruct_mesh(views, voxel_size=0.002, trunc=None, min_weight=1, depth_filter=True, margin=None, device='cuda', refine_poses=False,
-                      max_vertices=None, simplify_cell=None, components='largest', texture=None):
+                      max_vertices=None, simplify_cell=None, components='largest', texture=None, estimate_poses=False):
   """Reference views -> mesh (synthetic.SimpleMesh with vertex normals and colours).  `views`: a folder in the reference's layout
   (load_reference_views) or a dict with depths, masks, K, cam_in_obs and optionally rgbs.  depth_filter runs erode_depth and
   bilateral_filter_depth on every view first, as the estimator does with an observed frame.  The fusion and the extraction run on the
@@ -406,6 +650,10 @@ def _reconstruct_mesh(views, voxel_size=0.002, trunc=None, min_weight=1, depth_f
   poses as given.  The refinement aligns on the eroded maps, before the bilateral filter, in a volume of its own: `trunc` and `margin`
   here are the fusion's and are NOT passed on to it (its band is 2 voxels, its margin 5 voxels + 1 cm); give refine_poses a dict of
   refine_view_poses' keyword arguments (anchor, order, rounds, trunc, margin, iterations, min_pixels, damping, max_step) to set them.
+  refine_poses='joint' runs joint_refine_view_poses instead (pairwise ICP on the eroded maps, all views solved together, view 0 the
+  anchor, its defaults).  estimate_poses=True (or a dict of estimate_view_poses' first_pose, window, stages, joint, joint_stages,
+  neighbours, max_angle_deg, max_jump, damping) is for views WITHOUT cam_in_obs: the poses come from estimate_view_poses on the eroded
+  maps, and refine_poses, if given, then runs on them.  A folder is then read without cam_in_ob/.
   max_vertices or simplify_cell (one of them; default neither: the mesh as extracted) reduces the mesh by vertex clustering after the
   largest-component step (Utils.simplify_mesh): the rasteriser keeps a hypothesis' vertices on chip up to 8192 vertices, and a 2 mm fusion
   of a hand-sized object has tens of times that.
@@ -417,7 +665,7 @@ def _reconstruct_mesh(views, voxel_size=0.002, trunc=None, min_weight=1, depth_f
   if max_vertices is not None and simplify_cell is not None:
     raise ValueError('reconstruct_object: give max_vertices or simplify_cell, not both')
   if isinstance(views, (str, os.PathLike)):
-    views = load_reference_views(views)
+    views = load_reference_views(views, poses=not estimate_poses)
   bake = None
   if texture is not None and texture is not False:
     bake = dict(tex_size=None, top_n=4, depth_tol=2.0 * voxel_size, min_cell=8)
@@ -431,8 +679,21 @@ def _reconstruct_mesh(views, voxel_size=0.002, trunc=None, min_weight=1, depth_f
       raise ValueError('reconstruct_object: texture needs the views\' rgbs')
   dev = _device(device)
   eroded = _eroded_depths(views, depth_filter, dev)
+  if estimate_poses:
+    kw = dict(first_pose=None, window=2, stages=ODOMETRY_STAGES, joint=True, joint_stages=ESTIMATE_JOINT_STAGES, neighbours=4, max_angle_deg=60,
+              max_jump=0.01, damping=1e-9)
+    given = dict(estimate_poses) if isinstance(estimate_poses, dict) else {}
+    if set(given) - set(kw):
+      raise TypeError(f'estimate_poses: unknown keys {sorted(set(given) - set(kw))}')
+    kw.update(given)
+    got, _ = estimate_view_poses(dict(views, depths=eroded), depth_filter=False, device=dev, **kw)
+    views = dict(views, cam_in_obs=got)
   cam_in_obs = views['cam_in_obs']
-  if refine_poses:
+  if isinstance(refine_poses, str):
+    if refine_poses != 'joint':
+      raise ValueError(f"refine_poses must be False, True, 'joint' or a dict of refine_view_poses' keyword arguments, got {refine_poses!r}")
+    cam_in_obs, _ = joint_refine_view_poses(dict(views, depths=eroded), depth_filter=False, device=dev)
+  elif refine_poses:
     kw = dict(anchor=0, order='greedy', rounds=0, trunc=None, margin=None, iterations=10, min_pixels=100, damping=1e-9, max_step=None)
     given = dict(refine_poses) if isinstance(refine_poses, dict) else {}
     if set(given) - set(kw):

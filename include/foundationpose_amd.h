@@ -709,6 +709,68 @@ int fp_tsdf_read_plane(fp_ctx *ctx, const fp_tsdf *vol, int plane, float *d_out,
 int fp_tsdf_align(fp_ctx *ctx, const fp_tsdf *vol, const float *d_depth, const uint8_t *d_mask, int n_views, int H, int W, const double *K,
                   const double *cam_in_ob, float zfar, float min_weight, float *d_rows, double *h_sums, void *stream);
 
+/* ---- posing reference views from depth alone: point-to-plane ICP between PAIRS of depth maps with projective association, linearised
+ *      for all pairs in one launch (csrc/depth_icp.hip); the joint solve over all views is the caller's - foundationpose_amd/
+ *      reconstruct.py: solve_joint_step, joint_refine_view_poses, estimate_view_poses.  No volume is needed and the basin is set by a
+ *      distance gate, not by a voxel size.  Everything is fp32, not contracted, every operation in the written order; / and sqrtf are
+ *      correctly rounded ("unless" so that a NaN skips).  tests/depth_icp_oracle.py restates both rules in numpy.
+ *      d_depth (n_views,H,W) fp32 metres on the device, K (3,3) float64 HOST (fx, fy, cx, cy cast to fp32), pixel index row W + col.
+ *      The back-projection of a depth d at (row, col) is that of fp_tsdf_align: p = ((((float)col - cx) / fx) d, (((float)row - cy) / fy) d, d).
+ *      Normals.  fp_depth_normals writes d_normals (n_views,H,W,4) fp32, 16-byte aligned (it is written as float4; FP_EINVAL
+ *      otherwise), one thread per pixel; nothing synchronises.  d_mask (n_views,H,W) uint8 or null.  Per pixel:
+ *        ok(r,c): d >= 0.001 and d < zfar and, with a mask, mask != 0
+ *        write (0,0,0,0) unless 1 <= r <= H-2 and 1 <= c <= W-2, ok at the pixel and at its four neighbours (r, c-1), (r, c+1), (r-1, c),
+ *        (r+1, c), and |d_neighbour - d| <= max_jump for each of the four
+ *        a = p(r,c+1) - p(r,c-1),  b = p(r+1,c) - p(r-1,c)
+ *        m = b x a = (b.y a.z - b.z a.y, b.z a.x - b.x a.z, b.x a.y - b.y a.x)          each component a difference of two products
+ *        l2 = (m.x m.x + m.y m.y) + m.z m.z;   write (0,0,0,0) unless l2 > 0
+ *        n = m / sqrtf(l2);   write (n.x, n.y, n.z, 1)                                   n faces the camera: n.z < 0 on a fronto-parallel surface
+ *      Normals come from one-pixel central differences of the maps the caller passes: smooth the maps first if they are noisy.
+ *      Pairs.  fp_depth_pairs_align takes the depth maps, the normals of fp_depth_normals, cam_in_ob (n_views,4,4) float64 HOST
+ *      (camera-to-object) and pairs (n_pairs,2) int32 HOST, directed (s, t): the pixels of view s are projected into view t.  Per view v,
+ *      C_v = (Rc, tc) is cam_in_ob cast to fp32 and D_v = (Ri, ti) its inverse formed in double - Ri[a][i] = R[i][a],
+ *      ti[a] = -((R[0][a] t[0] + R[1][a] t[1]) + R[2][a] t[2]) - and then cast to fp32.  One workgroup per (pair, tile of 1024 pixels of
+ *      view s).  Per pair (s, t) and pixel (r, c) of view s:
+ *        skip unless normals_s[r,c].w != 0
+ *        p = the back-projection of depth_s[r,c];  ns = normals_s[r,c].xyz
+ *        x_a = ((Rc_s[a][0] p.x + Rc_s[a][1] p.y) + Rc_s[a][2] p.z) + tc_s[a]            the point in the object frame
+ *        y_a = ((Ri_t[a][0] x.x + Ri_t[a][1] x.y) + Ri_t[a][2] x.z) + ti_t[a]            the point in camera t
+ *        skip unless y.z >= 0.001
+ *        u = (fx y.x) / y.z + cx,  v = (fy y.y) / y.z + cy;   cf = floorf(u + 0.5f),  rf = floorf(v + 0.5f)
+ *        skip unless 0 <= cf <= W-1 and 0 <= rf <= H-1 (compared as floats);   skip unless normals_t[rf,cf].w != 0
+ *        q = the back-projection of depth_t[rf,cf] at (rf, cf);  n = normals_t[rf,cf].xyz;   e = y - q
+ *        skip unless (e.x e.x + e.y e.y) + e.z e.z < dist_max dist_max
+ *        w_a = (Rc_s[a][0] ns.x + Rc_s[a][1] ns.y) + Rc_s[a][2] ns.z;   g_a = (Ri_t[a][0] w.x + Ri_t[a][1] w.y) + Ri_t[a][2] w.z
+ *        skip unless (g.x n.x + g.y n.y) + g.z n.z >= cos_min
+ *        r = (n.x e.x + n.y e.y) + n.z e.z                                               the point-to-plane residual, metres
+ *        no_a = (Rc_t[a][0] n.x + Rc_t[a][1] n.y) + Rc_t[a][2] n.z                        the target normal in the object frame
+ *        J = (no.x, no.y, no.z, x.y no.z - x.z no.y, x.z no.x - x.x no.z, x.x no.y - x.y no.x)
+ *      J is dr / dxi_s for cam_in_ob_s <- exp(xi_s) cam_in_ob_s, xi = (translation, rotation) in the object frame, at fixed association;
+ *      dr / dxi_t is exactly -J (moving view t by xi moves the point in camera t as moving view s by -xi does), so ONE 6-vector serves
+ *      both ends of the pair: the caller adds A = sum J J^T to the diagonal blocks of s and t and subtracts it from the two off-diagonal
+ *      blocks, adds b = sum J r to the gradient of s and subtracts it from that of t.
+ *      d_rows, when not null, (n_pairs,H,W,8) fp32 on the device, 16-byte aligned (FP_EINVAL otherwise), gets (J0 .. J5, r, 1) per pixel
+ *      and eight zeros where the pixel was skipped.  h_sums, HOST (n_pairs, FP_DEPTH_ALIGN_TERMS) float64: per pair the 29 terms of
+ *      fp_tsdf_align's h_sums in the same order (the upper triangle of J^T J row by row, J^T r, sum r r, the number of valid pixels),
+ *      formed and added in double in the same way: over a lane's 4 pixels, over the wave by a butterfly, over the waves in order, and by
+ *      a second launch over the tiles in order.  No atomics: a pair's 29 numbers are bit-identical from run to run, in any batch and at
+ *      any index of it.  fp_depth_pairs_align SYNCHRONISES the stream (the partial sums and the pairs' matrices live in the context's
+ *      arena for the duration of the call).  At most FP_DEPTH_ALIGN_MAX_PAIRS pairs per call (the partial sums of 256 pairs of 640 x 480
+ *      pixels take 17 MB); the Python wrapper cuts longer lists into calls.  At most FP_TSDF_MAX_VIEWS views.
+ *      Geometry only: a turntable of a rotationally symmetric object leaves the rotation about its axis unobservable.
+ *      FP_EINVAL, each checked before ctx is looked into: a null ctx, d_depth, d_normals, K (both calls), cam_in_ob, h_sums, or pairs with
+ *      n_pairs > 0; a misaligned d_normals or d_rows; n_views outside 0 .. FP_TSDF_MAX_VIEWS (fp_depth_normals: 0 writes nothing); n_pairs
+ *      < 0 or above the cap (0 writes nothing); a pair index outside 0 .. n_views-1, or s == t; H or W < 1; a non-finite K or fx or fy
+ *      not > 0; zfar not > 0 (infinity is allowed); max_jump not > 0; dist_max not > 0; cos_min outside [-1, 1]; a view matrix that is
+ *      not finite or whose last row is not 0 0 0 1. */
+#define FP_DEPTH_ALIGN_TERMS 29        /* doubles per pair of fp_depth_pairs_align's h_sums */
+#define FP_DEPTH_ALIGN_MAX_PAIRS 256   /* per fp_depth_pairs_align call */
+int fp_depth_normals(fp_ctx *ctx, const float *d_depth, const uint8_t *d_mask, int n_views, int H, int W, const double *K, float zfar,
+                     float max_jump, float *d_normals, void *stream);
+int fp_depth_pairs_align(fp_ctx *ctx, const float *d_depth, const float *d_normals, int n_views, int H, int W, const double *K,
+                         const double *cam_in_ob, const int32_t *pairs, int n_pairs, float dist_max, float cos_min, float *d_rows,
+                         double *h_sums, void *stream);
+
 /* ---- texture baking: the colours of posed RGB-D reference views gathered into a per-face texture atlas of a mesh - the last stage of
  *      the model-free set-up, after the simplification (fp_mesh_simplify_* refuses textured meshes: simplify first, then bake).  The
  *      reference does this in mesh_texture_from_train_images (bundlesdf/nerf_runner.py:1122) with a UV parametrisation and the equal
