@@ -112,6 +112,7 @@ FP_TSDF_MAX_POINTS, FP_TSDF_MAX_VIEWS = 1 << 27, 64      # include/foundationpos
 FP_TSDF_PLANES = ('tsdf', 'weight', 'r', 'g', 'b', 'color_weight')      # FP_TSDF_PLANE_*
 FP_TSDF_ALIGN_TERMS = 29                                                  # fp_tsdf_align: doubles per view of h_sums
 FP_DEPTH_ALIGN_TERMS, FP_DEPTH_ALIGN_MAX_PAIRS = 29, 256                  # fp_depth_pairs_align: doubles per pair of h_sums, pairs per call
+FP_PHOTO_ALIGN_TERMS = 58                                                 # fp_depth_pairs_align_photo: doubles per pair of h_sums
 
 
 FP_TEXTURE_MIN_SIZE, FP_TEXTURE_MAX_SIZE, FP_TEXTURE_MAX_TOP_N, FP_TEXTURE_MAX_FACES = 64, 4096, 4, 1 << 21      # fp_texture_bake
@@ -185,6 +186,9 @@ _PROTOS = {
   'fp_depth_normals': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_float, c_float, c_void_p, c_void_p]),
   'fp_depth_pairs_align': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_void_p,
                                    c_void_p, c_void_p]),
+  'fp_view_intensity': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+  'fp_depth_pairs_align_photo': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_float, c_float,
+                                         c_float, c_void_p, c_void_p, c_void_p]),
   'fp_texture_bake': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                               POINTER(FpTextureCfg), c_void_p, c_void_p, c_void_p, c_void_p]),
   'fp_point_mesh_distance': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),

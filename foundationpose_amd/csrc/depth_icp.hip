@@ -12,6 +12,13 @@
 // per lane, added over the wave by the butterfly of device_util.h, over the waves in wave order through LDS, and written to the
 // workgroup's own slot of the slab; depth_pairs_fold_kernel adds the slots of a pair in tile order.  No atomics.  A wave whose 256
 // source pixels have no normal (the background of a masked view) skips passes two and three.
+//
+// The photometric term (fp_view_intensity, fp_depth_pairs_align_photo) rides on the same association.  view_intensity_kernel is one thread
+// per pixel again: the pixel's normal, the rgb of the pixel and of its four neighbours where the normal is there, one 16-byte write.
+// depth_pairs_kernel<true> is the same body with one more 16-byte source read in pass one and one more 16-byte gather in pass two; it keeps
+// what the photometric row needs of a pixel (x, y, the sub-pixel offset, the two intensity records, the geometric verdict) and sweeps the
+// pixels a second time after the 29 geometric sums have gone through the wave into LDS, so that only 29 double accumulators are alive at
+// a time; the workgroup's slot then holds 58 numbers.  depth_pairs_kernel<false> is the geometric kernel, statement for statement.
 #include "common.h"
 #include "device_util.h"
 
@@ -67,10 +74,36 @@ __global__ __launch_bounds__(PA_THREADS) void depth_normals_kernel(const float *
   out[idx] = o;
 }
 
-__global__ __launch_bounds__(PA_THREADS) void depth_pairs_kernel(const float *__restrict__ depth, const float4 *__restrict__ normals, DepthCam cam,
+// I = ((0.299 R + 0.587 G) + 0.114 B) / 255 of one pixel
+__device__ __forceinline__ float grey(const uint8_t *__restrict__ rgb, long long idx) {
+  const uint8_t *p = rgb + (size_t)idx * 3;
+  return ((0.299f * (float)p[0] + 0.587f * (float)p[1]) + 0.114f * (float)p[2]) / 255.f;
+}
+
+__global__ __launch_bounds__(PA_THREADS) void view_intensity_kernel(const uint8_t *__restrict__ rgb, const float4 *__restrict__ normals, int H, int W,
+                                                                    long long total, float4 *__restrict__ out) {
+  const long long idx = (long long)blockIdx.x * PA_THREADS + threadIdx.x;
+  if (idx >= total) return;
+  const long long hw = (long long)H * W;
+  const long long pix = idx % hw;
+  const int r = (int)(pix / W), c = (int)(pix - (long long)r * W);
+  float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+  // a normal of fp_depth_normals is never on the border; the test keeps the four neighbours inside the view for any other map
+  if (r >= 1 && r <= H - 2 && c >= 1 && c <= W - 2 && normals[idx].w != 0.f)
+    o = make_float4(grey(rgb, idx), (grey(rgb, idx + 1) - grey(rgb, idx - 1)) * 0.5f, (grey(rgb, idx + W) - grey(rgb, idx - W)) * 0.5f, 1.f);
+  out[idx] = o;
+}
+
+// PHOTO: the photometric rows and their 29 sums behind the geometric ones (the header's second rule); `intensity` and i_max are not
+// looked at without it.
+template <bool PHOTO>
+__global__ __launch_bounds__(PA_THREADS) void depth_pairs_kernel(const float *__restrict__ depth, const float4 *__restrict__ normals,
+                                                                 const float4 *__restrict__ intensity, DepthCam cam,
                                                                  const PairRec *__restrict__ recs, int n_tiles, float dist2_max, float cos_min,
-                                                                 float *__restrict__ rows, double *__restrict__ slab) {
-  __shared__ double red[PA_THREADS / 64][FP_DEPTH_ALIGN_TERMS];
+                                                                 float i_max, float *__restrict__ rows, double *__restrict__ slab) {
+  constexpr int TERMS = PHOTO ? FP_PHOTO_ALIGN_TERMS : FP_DEPTH_ALIGN_TERMS;
+  constexpr int ROW = PHOTO ? 16 : 8;                               // floats per pixel of `rows`
+  __shared__ double red[PA_THREADS / 64][TERMS];
   const int tid = threadIdx.x;
   const int tile = blockIdx.x % n_tiles, pr = blockIdx.x / n_tiles;
   const PairRec &m = recs[pr];
@@ -82,31 +115,37 @@ __global__ __launch_bounds__(PA_THREADS) void depth_pairs_kernel(const float *__
   float4 ns[PA_PIX];
   bool ok[PA_PIX];
   long long pix[PA_PIX];
+  float4 ia[PA_PIX];                                               // PHOTO: the source pixel's intensity record
 #pragma unroll
   for (int q = 0; q < PA_PIX; ++q) {
     pix[q] = (long long)tile * PA_TILE + q * PA_THREADS + tid;
     const bool in = pix[q] < hw;                                   // the last tile of a view is ragged
     ns[q] = in ? normals[src0 + (size_t)pix[q]] : make_float4(0.f, 0.f, 0.f, 0.f);
     d[q] = in ? depth[src0 + (size_t)pix[q]] : 0.f;
+    if constexpr (PHOTO) ia[q] = in ? intensity[src0 + (size_t)pix[q]] : make_float4(0.f, 0.f, 0.f, 0.f);
     ok[q] = ns[q].w != 0.f;
   }
 
   // A wave without a single source normal - most waves of a masked object's view - has nothing to project: its rows are zeros and its
-  // 29 partial sums are +0.0, the value the passes below would arrive at (0.f x 0.f widened and added to +0.0).  Uniform in the wave.
+  // 29 (58) partial sums are +0.0, the value the passes below would arrive at (0.f x 0.f widened and added to +0.0).  Uniform in the wave.
   if (!__any(ok[0] || ok[1] || ok[2] || ok[3])) {
     if (rows) {
 #pragma unroll
       for (int q = 0; q < PA_PIX; ++q)
         if (pix[q] < hw) {
-          float4 *o = (float4 *)(rows + ((size_t)pr * (size_t)hw + (size_t)pix[q]) * 8);
+          float4 *o = (float4 *)(rows + ((size_t)pr * (size_t)hw + (size_t)pix[q]) * ROW);
           o[0] = o[1] = make_float4(0.f, 0.f, 0.f, 0.f);
+          if constexpr (PHOTO) o[2] = o[3] = make_float4(0.f, 0.f, 0.f, 0.f);
         }
     }
-    if ((tid & 63) < FP_DEPTH_ALIGN_TERMS) red[tid >> 6][tid & 63] = 0.0;
+    if ((tid & 63) < TERMS) red[tid >> 6][tid & 63] = 0.0;
   } else {
   // pass 2: the point in the object frame and in camera t, its pixel there, the two gathers
   float x[PA_PIX][3], y[PA_PIX][3], cf[PA_PIX], rf[PA_PIX], dt[PA_PIX];
   float4 nt[PA_PIX];
+  float4 ib[PA_PIX];                                               // PHOTO: the target pixel's intensity record,
+  float du[PA_PIX], dv[PA_PIX];                                    // the projection's offset from that pixel's centre,
+  bool geo[PA_PIX];                                                // and whether the pixel passed every geometric gate
 #pragma unroll
   for (int q = 0; q < PA_PIX; ++q) {
     const int row = (int)(pix[q] / cam.W), col = (int)(pix[q] - (long long)row * cam.W);
@@ -123,6 +162,10 @@ __global__ __launch_bounds__(PA_THREADS) void depth_pairs_kernel(const float *__
     const size_t tp = tgt0 + (ok[q] ? (size_t)(int)rf[q] * cam.W + (size_t)(int)cf[q] : 0);      // inside view t whenever ok
     nt[q] = ok[q] ? normals[tp] : make_float4(0.f, 0.f, 0.f, 0.f);
     dt[q] = ok[q] ? depth[tp] : 0.f;
+    if constexpr (PHOTO) {
+      ib[q] = ok[q] ? intensity[tp] : make_float4(0.f, 0.f, 0.f, 0.f);
+      du[q] = u - cf[q], dv[q] = v - rf[q];
+    }
   }
 
   // pass 3: the gates, the row, the sums
@@ -153,10 +196,11 @@ __global__ __launch_bounds__(PA_THREADS) void depth_pairs_kernel(const float *__
       r = 0.f;
     }
     if (rows && pix[q] < hw) {
-      float4 *o = (float4 *)(rows + ((size_t)pr * (size_t)hw + (size_t)pix[q]) * 8);
+      float4 *o = (float4 *)(rows + ((size_t)pr * (size_t)hw + (size_t)pix[q]) * ROW);
       o[0] = make_float4(J[0], J[1], J[2], J[3]);
       o[1] = make_float4(J[4], J[5], r, valid ? 1.f : 0.f);
     }
+    if constexpr (PHOTO) geo[q] = valid;
     double Jd[6];
 #pragma unroll
     for (int i = 0; i < 6; ++i) Jd[i] = (double)J[i];
@@ -177,31 +221,79 @@ __global__ __launch_bounds__(PA_THREADS) void depth_pairs_kernel(const float *__
     const double s = wave_sum(acc[e]);
     if ((tid & 63) == 0) red[tid >> 6][e] = s;
   }
+
+  // pass 4 (PHOTO): the photometric row and its sums, the 29 accumulators used again
+  if constexpr (PHOTO) {
+#pragma unroll
+    for (int e = 0; e < FP_DEPTH_ALIGN_TERMS; ++e) acc[e] = 0.0;
+#pragma unroll
+    for (int q = 0; q < PA_PIX; ++q) {
+      bool valid = geo[q] && ia[q].w != 0.f && ib[q].w != 0.f;
+      float r = ((ib[q].x + ib[q].y * du[q]) + ib[q].z * dv[q]) - ia[q].x;
+      valid = valid && fabsf(r) < i_max;
+      const float jx = (ib[q].y * cam.fx) / y[q][2], jy = (ib[q].z * cam.fy) / y[q][2];
+      const float jz = -((jx * y[q][0] + jy * y[q][1]) / y[q][2]);
+      float a[3];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) a[k] = (m.rct[k * 3] * jx + m.rct[k * 3 + 1] * jy) + m.rct[k * 3 + 2] * jz;
+      const float X = x[q][0], Y = x[q][1], Z = x[q][2];
+      float J[6] = {a[0], a[1], a[2], Y * a[2] - Z * a[1], Z * a[0] - X * a[2], X * a[1] - Y * a[0]};
+      if (!valid) {
+#pragma unroll
+        for (int i = 0; i < 6; ++i) J[i] = 0.f;
+        r = 0.f;
+      }
+      if (rows && pix[q] < hw) {
+        float4 *o = (float4 *)(rows + ((size_t)pr * (size_t)hw + (size_t)pix[q]) * ROW);
+        o[2] = make_float4(J[0], J[1], J[2], J[3]);
+        o[3] = make_float4(J[4], J[5], r, valid ? 1.f : 0.f);
+      }
+      double Jd[6];
+#pragma unroll
+      for (int i = 0; i < 6; ++i) Jd[i] = (double)J[i];
+      const double rd = (double)r;
+      int e = 0;
+#pragma unroll
+      for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int j = i; j < 6; ++j) acc[e++] += Jd[i] * Jd[j];
+#pragma unroll
+      for (int i = 0; i < 6; ++i) acc[21 + i] += Jd[i] * rd;
+      acc[27] += rd * rd;
+      acc[28] += valid ? 1.0 : 0.0;
+    }
+#pragma unroll
+    for (int e = 0; e < FP_DEPTH_ALIGN_TERMS; ++e) {
+      const double s = wave_sum(acc[e]);
+      if ((tid & 63) == 0) red[tid >> 6][FP_DEPTH_ALIGN_TERMS + e] = s;
+    }
+  }
   }
   __syncthreads();
-  if (tid < FP_DEPTH_ALIGN_TERMS) {
+  if (tid < TERMS) {
     double s = red[0][tid];
     for (int wv = 1; wv < PA_THREADS / 64; ++wv) s += red[wv][tid];
-    slab[((size_t)pr * n_tiles + tile) * FP_DEPTH_ALIGN_TERMS + tid] = s;
+    slab[((size_t)pr * n_tiles + tile) * TERMS + tid] = s;
   }
 }
 
-// one thread per (pair, term): the tiles' slots in tile order
+// one thread per (pair, term): the tiles' slots in tile order; TERMS numbers per slot
+template <int TERMS>
 __global__ __launch_bounds__(64) void depth_pairs_fold_kernel(const double *__restrict__ slab, int n_pairs, int n_tiles, double *__restrict__ sums) {
   const int t = blockIdx.x * 64 + threadIdx.x;
-  if (t >= n_pairs * FP_DEPTH_ALIGN_TERMS) return;
-  const int p = t / FP_DEPTH_ALIGN_TERMS, e = t % FP_DEPTH_ALIGN_TERMS;
-  const double *sb = slab + (size_t)p * n_tiles * FP_DEPTH_ALIGN_TERMS + e;
+  if (t >= n_pairs * TERMS) return;
+  const int p = t / TERMS, e = t % TERMS;
+  const double *sb = slab + (size_t)p * n_tiles * TERMS + e;
   double s = 0.0;
   int k = 0;
   for (; k + 8 <= n_tiles; k += 8) {      // eight loads in flight, added in tile order
     double v[8];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = sb[(size_t)(k + i) * FP_DEPTH_ALIGN_TERMS];
+    for (int i = 0; i < 8; ++i) v[i] = sb[(size_t)(k + i) * TERMS];
 #pragma unroll
     for (int i = 0; i < 8; ++i) s += v[i];
   }
-  for (; k < n_tiles; ++k) s += sb[(size_t)k * FP_DEPTH_ALIGN_TERMS];
+  for (; k < n_tiles; ++k) s += sb[(size_t)k * TERMS];
   sums[t] = s;
 }
 
@@ -234,31 +326,37 @@ extern "C" int fp_depth_normals(fp_ctx *ctx, const float *d_depth, const uint8_t
   return FP_OK;
 }
 
-extern "C" int fp_depth_pairs_align(fp_ctx *ctx, const float *d_depth, const float *d_normals, int n_views, int H, int W, const double *K,
-                                    const double *cam_in_ob, const int32_t *pairs, int n_pairs, float dist_max, float cos_min, float *d_rows,
-                                    double *h_sums, void *stream) {
+namespace {
+
+// fp_depth_pairs_align (d_intensity null) and fp_depth_pairs_align_photo (d_intensity given): the same checks, pair table, slab and fold,
+// with 29 or 58 numbers per pair and rows of 8 or 16 floats.  `fn` names the entry point in the messages.
+int pairs_align(const char *fn, fp_ctx *ctx, const float *d_depth, const float *d_normals, const float *d_intensity, bool photo, int n_views, int H,
+                int W, const double *K, const double *cam_in_ob, const int32_t *pairs, int n_pairs, float dist_max, float cos_min, float i_max,
+                float *d_rows, double *h_sums, void *stream) {
   // As above: every check of a value before the first look into ctx.
-  FP_REQUIRE(ctx && d_depth && d_normals && K && cam_in_ob && h_sums, "fp_depth_pairs_align: null argument");
-  FP_REQUIRE(((uintptr_t)d_normals & 15) == 0, "fp_depth_pairs_align: d_normals is not 16-byte aligned (it is read as float4)");
-  FP_REQUIRE(((uintptr_t)d_rows & 15) == 0, "fp_depth_pairs_align: d_rows is not 16-byte aligned (it is written as float4)");
-  FP_REQUIRE(n_views >= 0 && n_views <= FP_TSDF_MAX_VIEWS, "fp_depth_pairs_align: n_views %d (0 .. %d)", n_views, FP_TSDF_MAX_VIEWS);
-  FP_REQUIRE(n_pairs >= 0 && n_pairs <= FP_DEPTH_ALIGN_MAX_PAIRS, "fp_depth_pairs_align: n_pairs %d (0 .. %d)", n_pairs, FP_DEPTH_ALIGN_MAX_PAIRS);
-  FP_REQUIRE(pairs || n_pairs == 0, "fp_depth_pairs_align: null pairs");
-  FP_REQUIRE(H >= 1 && W >= 1, "fp_depth_pairs_align: H %d, W %d", H, W);
-  FP_REQUIRE(dist_max > 0.f, "fp_depth_pairs_align: dist_max %g (> 0)", (double)dist_max);
-  FP_REQUIRE(cos_min >= -1.f && cos_min <= 1.f, "fp_depth_pairs_align: cos_min %g (-1 .. 1)", (double)cos_min);
+  FP_REQUIRE(ctx && d_depth && d_normals && K && cam_in_ob && h_sums && (d_intensity || !photo), "%s: null argument", fn);
+  FP_REQUIRE(((uintptr_t)d_normals & 15) == 0, "%s: d_normals is not 16-byte aligned (it is read as float4)", fn);
+  FP_REQUIRE(((uintptr_t)d_intensity & 15) == 0, "%s: d_intensity is not 16-byte aligned (it is read as float4)", fn);
+  FP_REQUIRE(((uintptr_t)d_rows & 15) == 0, "%s: d_rows is not 16-byte aligned (it is written as float4)", fn);
+  FP_REQUIRE(n_views >= 0 && n_views <= FP_TSDF_MAX_VIEWS, "%s: n_views %d (0 .. %d)", fn, n_views, FP_TSDF_MAX_VIEWS);
+  FP_REQUIRE(n_pairs >= 0 && n_pairs <= FP_DEPTH_ALIGN_MAX_PAIRS, "%s: n_pairs %d (0 .. %d)", fn, n_pairs, FP_DEPTH_ALIGN_MAX_PAIRS);
+  FP_REQUIRE(pairs || n_pairs == 0, "%s: null pairs", fn);
+  FP_REQUIRE(H >= 1 && W >= 1, "%s: H %d, W %d", fn, H, W);
+  FP_REQUIRE(dist_max > 0.f, "%s: dist_max %g (> 0)", fn, (double)dist_max);
+  FP_REQUIRE(cos_min >= -1.f && cos_min <= 1.f, "%s: cos_min %g (-1 .. 1)", fn, (double)cos_min);
+  FP_REQUIRE(!photo || i_max > 0.f, "%s: i_max %g (> 0)", fn, (double)i_max);
   DepthCam cam;
-  FP_REQUIRE(camera_ok(K, cam, H, W), "fp_depth_pairs_align: K is not a finite camera matrix with positive focal lengths");
+  FP_REQUIRE(camera_ok(K, cam, H, W), "%s: K is not a finite camera matrix with positive focal lengths", fn);
   for (int v = 0; v < n_views; ++v) {
     const double *m = cam_in_ob + (size_t)v * 16;
-    for (int e = 0; e < 12; ++e) FP_REQUIRE(isfinite(m[e]), "fp_depth_pairs_align: cam_in_ob[%d] is not finite", v);
-    FP_REQUIRE(m[12] == 0 && m[13] == 0 && m[14] == 0 && m[15] == 1, "fp_depth_pairs_align: the last row of cam_in_ob[%d] is not 0 0 0 1", v);
+    for (int e = 0; e < 12; ++e) FP_REQUIRE(isfinite(m[e]), "%s: cam_in_ob[%d] is not finite", fn, v);
+    FP_REQUIRE(m[12] == 0 && m[13] == 0 && m[14] == 0 && m[15] == 1, "%s: the last row of cam_in_ob[%d] is not 0 0 0 1", fn, v);
   }
   std::vector<PairRec> recs((size_t)n_pairs);
   for (int p = 0; p < n_pairs; ++p) {
     const int s = pairs[2 * p], t = pairs[2 * p + 1];
-    FP_REQUIRE(s >= 0 && s < n_views && t >= 0 && t < n_views, "fp_depth_pairs_align: pair %d = (%d, %d) of %d views", p, s, t, n_views);
-    FP_REQUIRE(s != t, "fp_depth_pairs_align: pair %d joins view %d to itself", p, s);
+    FP_REQUIRE(s >= 0 && s < n_views && t >= 0 && t < n_views, "%s: pair %d = (%d, %d) of %d views", fn, p, s, t, n_views);
+    FP_REQUIRE(s != t, "%s: pair %d joins view %d to itself", fn, p, s);
     const double *ms = cam_in_ob + (size_t)s * 16, *mt = cam_in_ob + (size_t)t * 16;
     PairRec &r = recs[p];
     for (int a = 0; a < 3; ++a) {
@@ -273,30 +371,71 @@ extern "C" int fp_depth_pairs_align(fp_ctx *ctx, const float *d_depth, const flo
     r.s = s, r.t = t, r.pad = 0;
   }
   const long long n_tiles = ((long long)H * W + PA_TILE - 1) / PA_TILE;
-  FP_REQUIRE(n_tiles * FP_DEPTH_ALIGN_MAX_PAIRS <= 0x7fffffff, "fp_depth_pairs_align: %d x %d pixels are too many for one launch", H, W);
+  FP_REQUIRE(n_tiles * FP_DEPTH_ALIGN_MAX_PAIRS <= 0x7fffffff, "%s: %d x %d pixels are too many for one launch", fn, H, W);
   if (n_pairs == 0) return FP_OK;
   hipStream_t s = (hipStream_t)stream;
-  const size_t slab_bytes = (size_t)n_pairs * (size_t)n_tiles * FP_DEPTH_ALIGN_TERMS * sizeof(double);
-  const size_t sums_bytes = (size_t)n_pairs * FP_DEPTH_ALIGN_TERMS * sizeof(double);
+  const size_t terms = photo ? FP_PHOTO_ALIGN_TERMS : FP_DEPTH_ALIGN_TERMS;
+  const size_t slab_bytes = (size_t)n_pairs * (size_t)n_tiles * terms * sizeof(double);
+  const size_t sums_bytes = (size_t)n_pairs * terms * sizeof(double);
   const size_t recs_bytes = (size_t)n_pairs * sizeof(PairRec);
   FP_TRY(fp_arena_ensure(ctx, slab_bytes + sums_bytes + recs_bytes + 4096));
   ArenaScope scope(ctx->arena);
   double *slab = (double *)ctx->arena.take(slab_bytes);
   double *sums = (double *)ctx->arena.take(sums_bytes);
   PairRec *d_recs = (PairRec *)ctx->arena.take(recs_bytes);
-  FP_REQUIRE(slab && sums && d_recs, "fp_depth_pairs_align: arena exhausted");
+  FP_REQUIRE(slab && sums && d_recs, "%s: arena exhausted", fn);
   // `recs` outlives the copy: the stream is synchronised before this returns
   FP_CHECK_HIP(hipMemcpyAsync(d_recs, recs.data(), recs_bytes, hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(depth_pairs_kernel, dim3((unsigned)(n_tiles * n_pairs)), dim3(PA_THREADS), 0, s, d_depth, (const float4 *)d_normals, cam,
-                     (const PairRec *)d_recs, (int)n_tiles, dist_max * dist_max, cos_min, d_rows, slab);
-  FP_CHECK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(depth_pairs_fold_kernel, dim3((unsigned)((n_pairs * FP_DEPTH_ALIGN_TERMS + 63) / 64)), dim3(64), 0, s, (const double *)slab,
-                     n_pairs, (int)n_tiles, sums);
+  const dim3 grid((unsigned)(n_tiles * n_pairs)), fold_grid((unsigned)((n_pairs * terms + 63) / 64));
+  if (photo) {
+    hipLaunchKernelGGL(depth_pairs_kernel<true>, grid, dim3(PA_THREADS), 0, s, d_depth, (const float4 *)d_normals, (const float4 *)d_intensity, cam,
+                       (const PairRec *)d_recs, (int)n_tiles, dist_max * dist_max, cos_min, i_max, d_rows, slab);
+    FP_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(depth_pairs_fold_kernel<FP_PHOTO_ALIGN_TERMS>, fold_grid, dim3(64), 0, s, (const double *)slab, n_pairs, (int)n_tiles, sums);
+  } else {
+    hipLaunchKernelGGL(depth_pairs_kernel<false>, grid, dim3(PA_THREADS), 0, s, d_depth, (const float4 *)d_normals, (const float4 *)nullptr, cam,
+                       (const PairRec *)d_recs, (int)n_tiles, dist_max * dist_max, cos_min, 0.f, d_rows, slab);
+    FP_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(depth_pairs_fold_kernel<FP_DEPTH_ALIGN_TERMS>, fold_grid, dim3(64), 0, s, (const double *)slab, n_pairs, (int)n_tiles, sums);
+  }
   FP_CHECK_HIP(hipGetLastError());
   // the slab, the sums and the pair table go back to the arena when this returns: the stream has been synchronised by then
   hipError_t e1 = hipMemcpyAsync(h_sums, sums, sums_bytes, hipMemcpyDeviceToHost, s);
   hipError_t e2 = hipStreamSynchronize(s);      // also after a failed copy: `recs` and the arena must not be in use when this returns
   FP_CHECK_HIP(e1);
   FP_CHECK_HIP(e2);
+  return FP_OK;
+}
+
+}  // namespace
+
+extern "C" int fp_depth_pairs_align(fp_ctx *ctx, const float *d_depth, const float *d_normals, int n_views, int H, int W, const double *K,
+                                    const double *cam_in_ob, const int32_t *pairs, int n_pairs, float dist_max, float cos_min, float *d_rows,
+                                    double *h_sums, void *stream) {
+  return pairs_align("fp_depth_pairs_align", ctx, d_depth, d_normals, nullptr, false, n_views, H, W, K, cam_in_ob, pairs, n_pairs, dist_max, cos_min,
+                     0.f, d_rows, h_sums, stream);
+}
+
+extern "C" int fp_depth_pairs_align_photo(fp_ctx *ctx, const float *d_depth, const float *d_normals, const float *d_intensity, int n_views, int H, int W,
+                                          const double *K, const double *cam_in_ob, const int32_t *pairs, int n_pairs, float dist_max, float cos_min,
+                                          float i_max, float *d_rows, double *h_sums, void *stream) {
+  return pairs_align("fp_depth_pairs_align_photo", ctx, d_depth, d_normals, d_intensity, true, n_views, H, W, K, cam_in_ob, pairs, n_pairs, dist_max,
+                     cos_min, i_max, d_rows, h_sums, stream);
+}
+
+extern "C" int fp_view_intensity(fp_ctx *ctx, const uint8_t *d_rgb, const float *d_normals, int n_views, int H, int W, float *d_intensity, void *stream) {
+  // As above: every check of a value before the first look into ctx.
+  FP_REQUIRE(ctx && d_rgb && d_normals && d_intensity, "fp_view_intensity: null argument");
+  FP_REQUIRE(((uintptr_t)d_normals & 15) == 0, "fp_view_intensity: d_normals is not 16-byte aligned (it is read as float4)");
+  FP_REQUIRE(((uintptr_t)d_intensity & 15) == 0, "fp_view_intensity: d_intensity is not 16-byte aligned (it is written as float4)");
+  FP_REQUIRE(n_views >= 0 && n_views <= FP_TSDF_MAX_VIEWS, "fp_view_intensity: n_views %d (0 .. %d)", n_views, FP_TSDF_MAX_VIEWS);
+  FP_REQUIRE(H >= 1 && W >= 1, "fp_view_intensity: H %d, W %d", H, W);
+  const long long total = (long long)n_views * H * W;
+  const long long blocks = (total + PA_THREADS - 1) / PA_THREADS;
+  FP_REQUIRE(blocks <= 0x7fffffff, "fp_view_intensity: %d views of %d x %d pixels are too many for one launch", n_views, H, W);
+  if (n_views == 0) return FP_OK;
+  hipLaunchKernelGGL(view_intensity_kernel, dim3((unsigned)blocks), dim3(PA_THREADS), 0, (hipStream_t)stream, d_rgb, (const float4 *)d_normals, H, W,
+                     total, (float4 *)d_intensity);
+  FP_CHECK_HIP(hipGetLastError());
   return FP_OK;
 }

@@ -385,6 +385,8 @@ DEFAULT_STAGES = ((0.020, 0.5, 6), (0.010, 0.5, 6), (0.005, 0.7, 8))            
 ODOMETRY_STAGES = ((0.030, 0.3, 8), (0.015, 0.5, 6), (0.0075, 0.7, 6))          # estimate_view_poses: a new view against the views before it
 ESTIMATE_JOINT_STAGES = ((0.010, 0.5, 8), (0.005, 0.7, 8))                      # estimate_view_poses: the joint pass behind the odometry
 MAX_PAIRS = _lib.FP_DEPTH_ALIGN_MAX_PAIRS
+PHOTO_WEIGHT = 0.03      # photometric=True: metres per unit of intensity (0 .. 1)
+I_MAX = 0.2              # a photometric residual of this size or more is not used
 
 
 def _host_poses(cam_in_obs):
@@ -415,12 +417,37 @@ def depth_normals(depths, K, masks=None, zfar=np.inf, max_jump=0.01, device='cud
   return out
 
 
-def align_pairs_step(depths, normals, K, cam_in_obs, pairs, dist_max, cos_min, rows=False):
+def view_intensity(rgbs, normals):
+  """fp_view_intensity: (n,H,W,4) float32 device tensor on the device of `normals` (n,H,W,4, of depth_normals) - per pixel the grey value
+  ((0.299 R + 0.587 G) + 0.114 B) / 255 of rgbs (n,H,W,3) uint8, its central differences along the row and the column and 1, or four
+  zeros where the view has no normal: there the pixel and its four neighbours are masked valid depth without a jump, so the differences
+  never reach across an occlusion edge.  Nothing synchronises."""
+  dev = normals.device
+  normals = normals.contiguous()
+  n, H, W = normals.shape[:3]
+  rgbs = torch.as_tensor(rgbs, device=dev)
+  if rgbs.dim() == 3:
+    rgbs = rgbs[None]
+  if tuple(rgbs.shape) != (n, H, W, 3) or rgbs.dtype != torch.uint8:
+    raise ValueError(f'rgbs must be uint8 of shape {(n, H, W, 3)}, got {rgbs.dtype} {tuple(rgbs.shape)}')
+  if tuple(normals.shape) != (n, H, W, 4) or normals.dtype != torch.float:
+    raise ValueError(f'normals must be float32 of shape {(n, H, W, 4)}, got {normals.dtype} {tuple(normals.shape)}')
+  rgbs = rgbs.contiguous()
+  out = torch.empty((n, H, W, 4), dtype=torch.float, device=dev)
+  for a in range(0, n, MAX_VIEWS):      # views are independent: more than MAX_VIEWS are cut into calls
+    b = min(a + MAX_VIEWS, n)
+    check(lib().fp_view_intensity(_lib.Context.get(dev).handle, ptr(rgbs[a:b]), ptr(normals[a:b]), b - a, H, W, ptr(out[a:b]), stream_ptr(dev)))
+  return out
+
+
+def align_pairs_step(depths, normals, K, cam_in_obs, pairs, dist_max, cos_min, rows=False, intensity=None, i_max=I_MAX):
   """One linearisation of point-to-plane ICP for every directed pair (s, t) of `pairs` (fp_depth_pairs_align): the pixels of view s
   are projected into view t.  depths (n,H,W) and normals (n,H,W,4, of depth_normals) are device tensors.  Returns the (P,29) float64
   array of the header - per pair the upper triangle of J^T J, J^T r, sum r^2, the number of valid pixels - and, with rows=True, the
   (P,H,W,8) float32 device tensor of the per-pixel rows.  Synchronises.  More than MAX_PAIRS pairs are cut into calls (a pair's numbers
-  do not depend on the batch it is in)."""
+  do not depend on the batch it is in).  With `intensity` (n,H,W,4, of view_intensity) the photometric rows ride on the same association
+  (fp_depth_pairs_align_photo; residuals of i_max or more are not used): (P,58) - the 29 geometric numbers, bit for bit those of the call
+  without `intensity`, then the same 29 of the photometric rows - and rows of 16 floats."""
   dev = normals.device
   depths = torch.as_tensor(depths, device=dev).to(torch.float).contiguous()
   normals = normals.contiguous()
@@ -434,15 +461,56 @@ def align_pairs_step(depths, normals, K, cam_in_obs, pairs, dist_max, cos_min, r
   P = len(pairs)
   Kd, Kp = _lib.k_ptr(K)
   ctx = _lib.Context.get(dev)
-  sums = np.zeros((P, _lib.FP_DEPTH_ALIGN_TERMS), dtype=np.float64)
-  out = torch.empty((P, H, W, 8), dtype=torch.float, device=dev) if rows else None
+  if intensity is not None:
+    intensity = intensity.contiguous()
+    if tuple(intensity.shape) != (n, H, W, 4) or intensity.dtype != torch.float or intensity.device != dev:
+      raise ValueError(f'intensity must be float32 of shape {(n, H, W, 4)} on {dev}, got {intensity.dtype} {tuple(intensity.shape)} on {intensity.device}')
+  terms, width = (_lib.FP_DEPTH_ALIGN_TERMS, 8) if intensity is None else (_lib.FP_PHOTO_ALIGN_TERMS, 16)
+  sums = np.zeros((P, terms), dtype=np.float64)
+  out = torch.empty((P, H, W, width), dtype=torch.float, device=dev) if rows else None
   for a in range(0, P, MAX_PAIRS):
     b = min(a + MAX_PAIRS, P)
-    part = np.zeros((b - a, _lib.FP_DEPTH_ALIGN_TERMS), dtype=np.float64)
-    check(lib().fp_depth_pairs_align(ctx.handle, ptr(depths), ptr(normals), n, H, W, Kp, ptr(poses), ptr(np.ascontiguousarray(pairs[a:b])), b - a,
-                                     float(dist_max), float(cos_min), None if out is None else ptr(out[a:b]), ptr(part), stream_ptr(dev)))
+    part = np.zeros((b - a, terms), dtype=np.float64)
+    batch, rows_ptr = ptr(np.ascontiguousarray(pairs[a:b])), None if out is None else ptr(out[a:b])
+    if intensity is None:
+      check(lib().fp_depth_pairs_align(ctx.handle, ptr(depths), ptr(normals), n, H, W, Kp, ptr(poses), batch, b - a, float(dist_max), float(cos_min),
+                                       rows_ptr, ptr(part), stream_ptr(dev)))
+    else:
+      check(lib().fp_depth_pairs_align_photo(ctx.handle, ptr(depths), ptr(normals), ptr(intensity), n, H, W, Kp, ptr(poses), batch, b - a,
+                                             float(dist_max), float(cos_min), float(i_max), rows_ptr, ptr(part), stream_ptr(dev)))
     sums[a:b] = part
   return (sums, out) if rows else sums
+
+
+def combine_sums(sums58, photo_weight):
+  """(P,29) for solve_joint_step from the (P,58) of align_pairs_step(intensity=..): terms 0 .. 27 (J^T J, J^T r, sum r^2) are the geometric
+  ones + photo_weight^2 x the photometric ones - the photometric residual, in units of intensity, counts as photo_weight metres per unit -
+  and term 28 is the geometric count.  photo_weight = 0 returns the geometric 29 bit for bit."""
+  sums58 = np.asarray(sums58, dtype=np.float64).reshape(-1, _lib.FP_PHOTO_ALIGN_TERMS)
+  out = sums58[:, :29].copy()
+  out[:, :28] = sums58[:, :28] + (float(photo_weight) * float(photo_weight)) * sums58[:, 29:57]
+  return out
+
+
+def _photo_weight(photometric):
+  """None for photometric=False or None, PHOTO_WEIGHT for True, else the weight itself (a positive finite number)"""
+  if photometric is None or photometric is False:
+    return None
+  if photometric is True:
+    return PHOTO_WEIGHT
+  w = float(photometric)
+  if not (np.isfinite(w) and w > 0):
+    raise ValueError(f'photometric must be False, True or a positive weight in metres per unit of intensity, got {photometric!r}')
+  return w
+
+
+def _view_intensity_of(views, normals, weight):
+  """the intensity maps of `views` for a photometric weight, or None without one"""
+  if weight is None:
+    return None
+  if views.get('rgbs') is None:
+    raise ValueError('photometric: the views have no rgbs')
+  return view_intensity(views['rgbs'], normals)
 
 
 def _pair_blocks(sums, pairs, n_views):
@@ -503,20 +571,26 @@ def choose_pairs(cam_in_obs, neighbours=4, max_angle_deg=100):
   return out
 
 
-def _joint_on(depths, normals, K, poses, fixed, pairs, stages, neighbours, max_angle_deg, damping):
-  """The loop of joint_refine_view_poses on prepared device tensors; `fixed`: the views that are not moved."""
+def _joint_on(depths, normals, K, poses, fixed, pairs, stages, neighbours, max_angle_deg, damping, intensity=None, weight=None, i_max=I_MAX):
+  """The loop of joint_refine_view_poses on prepared device tensors; `fixed`: the views that are not moved.  With `intensity` and
+  `weight` every evaluation takes the 58 sums and the solver gets combine_sums of them."""
   poses = poses.copy()
   n = len(poses)
-  info = dict(rms=[], valid=[], pairs=[], stopped={}, after_first=None, eig_ratio=np.full(n, np.nan))
+  info = dict(rms=[], valid=[], photo_rms=[], photo_valid=[], pairs=[], stopped={}, after_first=None, eig_ratio=np.full(n, np.nan))
   pr = [] if pairs is None else [tuple(int(i) for i in p) for p in pairs]
   gate = (stages[-1][0], stages[-1][1]) if len(stages) else (DEFAULT_STAGES[-1][0], DEFAULT_STAGES[-1][1])
 
   def evaluate():
-    sm = align_pairs_step(depths, normals, K, poses, pr, *gate)
+    sm = align_pairs_step(depths, normals, K, poses, pr, *gate, intensity=intensity, i_max=i_max)
     cnt = float(sm[:, 28].sum())
     info['valid'].append(cnt)
     info['rms'].append(float(np.sqrt(sm[:, 27].sum() / max(cnt, 1.0))))
-    return sm
+    if intensity is None:
+      return sm
+    cnt = float(sm[:, 57].sum())
+    info['photo_valid'].append(cnt)
+    info['photo_rms'].append(float(np.sqrt(sm[:, 56].sum() / max(cnt, 1.0))))
+    return combine_sums(sm, weight)
   for dist_max, cos_min, steps in stages:
     if pairs is None:
       pr = choose_pairs(poses, neighbours, max_angle_deg)
@@ -536,7 +610,8 @@ def _joint_on(depths, normals, K, poses, fixed, pairs, stages, neighbours, max_a
     w = np.linalg.eigvalsh(Hm[v, v])
     if w[-1] > 0:
       info['eig_ratio'][v] = w[0] / w[-1]
-  info['rms'], info['valid'] = np.array(info['rms']), np.array(info['valid'])
+  for k in ('rms', 'valid', 'photo_rms', 'photo_valid'):
+    info[k] = np.array(info[k])
   return poses, info
 
 
@@ -546,8 +621,8 @@ def _check_view_count(n):
 
 
 def joint_refine_view_poses(views, anchor=0, pairs=None, stages=DEFAULT_STAGES, neighbours=4, max_angle_deg=100, depth_filter=True, max_jump=0.01,
-                            damping=1e-9, device='cuda'):
-  """Joint refinement of the reference views' poses from depth alone.  `views` as for reconstruct_object (at most 64).  Every view is
+                            damping=1e-9, device='cuda', photometric=False, i_max=I_MAX):
+  """Joint refinement of the reference views' poses from depth alone, or from depth and grey value (photometric, below).  `views` as for reconstruct_object (at most 64).  Every view is
   linked to its `neighbours` nearest views by optical axis (choose_pairs; or `pairs`, a list of directed (s, t)); per stage (dist_max
   metres, cos_min, steps) the pairs are chosen from the current poses and `steps` joint Gauss-Newton steps are taken - each one
   fp_depth_pairs_align launch sequence over all pairs (point-to-plane residuals of view s's pixels against the surface view t sees at
@@ -558,10 +633,21 @@ def joint_refine_view_poses(views, anchor=0, pairs=None, stages=DEFAULT_STAGES, 
   symmetric object the rotation about its axis is unobservable.  Returns (cam_in_obs (n,4,4) float64, info): rms and valid (one entry
   per evaluation, over all pairs), pairs (per stage), stopped {view: reason} - a free view without a valid residual keeps its pose -,
   after_first (the poses after the first step) and eig_ratio (per view the smallest over the largest eigenvalue of its 6x6 diagonal
-  block at the closing evaluation: a value orders of magnitude below the others marks a weakly constrained view)."""
+  block at the closing evaluation: a value orders of magnitude below the others marks a weakly constrained view).
+  photometric (default False: every result as without the argument) adds a grey-value residual on the same association to every pair
+  (fp_depth_pairs_align_photo): the value of view t at the pixel's projection, corrected to first order for the sub-pixel offset, minus
+  the value of view s at the pixel.  True weighs a unit of intensity (0 .. 1) as PHOTO_WEIGHT = 0.03 metres; a float is that weight.
+  Residuals of i_max (0.2) or more are not used.  Both defaults are this library's own choice, from a CPU experiment on a textured
+  sphere and a textured orbit, not the reference's.  It determines what the geometry leaves free - the rotation
+  of a turntable of a bottle or a can, the sliding of a face seen head-on - where the surface has texture.  The views need rgbs
+  (ValueError otherwise).  Brightness constancy is assumed: a camera moving round a static object under fixed light is served; an
+  object turning under a fixed lamp, speculars and exposure changes are not.  Grey only; no image pyramid - the basin is half a texture
+  wavelength -; no blur: pre-filter rgbs if they are noisy.  info then also holds photo_rms (in units of intensity) and photo_valid, one
+  entry per evaluation (empty without the term), and eig_ratio comes from the combined system."""
   if isinstance(views, (str, os.PathLike)):
     views = load_reference_views(views)
   dev = _device(device)
+  weight = _photo_weight(photometric)
   poses = _host_poses(views['cam_in_obs']).copy()
   n = len(poses)
   _check_view_count(n)
@@ -569,7 +655,8 @@ def joint_refine_view_poses(views, anchor=0, pairs=None, stages=DEFAULT_STAGES, 
     raise ValueError(f'anchor {anchor} of {n} views')
   depths = _eroded_depths(views, depth_filter, dev).contiguous()
   normals = depth_normals(depths, views['K'], views.get('masks'), max_jump=max_jump, device=dev)
-  return _joint_on(depths, normals, views['K'], poses, [anchor], pairs, stages, neighbours, max_angle_deg, damping)
+  return _joint_on(depths, normals, views['K'], poses, [anchor], pairs, stages, neighbours, max_angle_deg, damping,
+                   _view_intensity_of(views, normals, weight), weight, i_max)
 
 
 def _centroid_pose(depth, mask, K, dev):
@@ -588,14 +675,16 @@ def _centroid_pose(depth, mask, K, dev):
 
 
 def estimate_view_poses(views, first_pose=None, window=2, stages=ODOMETRY_STAGES, joint=True, joint_stages=ESTIMATE_JOINT_STAGES, neighbours=4,
-                        max_angle_deg=60, depth_filter=True, max_jump=0.01, damping=1e-9, device='cuda'):
+                        max_angle_deg=60, depth_filter=True, max_jump=0.01, damping=1e-9, device='cuda', photometric=False, i_max=I_MAX):
   """Poses for views that have none: a masked RGB-D sequence in which neighbouring frames overlap (`views` without cam_in_obs; a folder
   is read with load_reference_views(poses=False); at most 64 views).  View 0 gets first_pose, or the identity rotation with the
   translation that puts the centroid of its valid masked points at the origin - the object frame is then view 0's camera frame moved
   to the object.  View k starts at view k-1's pose and is solved alone against views k-window .. k-1 (pairs in both directions, those
   views fixed) over `stages`; then, with joint=True, the joint pass of joint_refine_view_poses runs over all views (joint_stages,
   neighbours, max_angle_deg; view 0 fixed), which closes loops that the odometry leaves open by less than its first gate.  A frame-to-
-  frame step beyond the odometry's first gate (3 cm) is lost and not recovered.  Returns (cam_in_obs (n,4,4) float64, info: odometry -
+  frame step beyond the odometry's first gate (3 cm) is lost and not recovered.  photometric and i_max are those of
+  joint_refine_view_poses and act in the odometry and in the joint pass: without them the odometry loses track where the geometry
+  leaves a direction free, and the joint pass does not bring it back.  Returns (cam_in_obs (n,4,4) float64, info: odometry -
   the poses before the joint pass -, joint - that pass's info or None)."""
   if isinstance(views, (str, os.PathLike)):
     views = load_reference_views(views, poses=False)
@@ -605,28 +694,31 @@ def estimate_view_poses(views, first_pose=None, window=2, stages=ODOMETRY_STAGES
   _check_view_count(n)
   masks, K = views.get('masks'), views['K']
   normals = depth_normals(depths, K, masks, max_jump=max_jump, device=dev)
+  weight = _photo_weight(photometric)
+  photo = (_view_intensity_of(views, normals, weight), weight, i_max)
   first = _centroid_pose(depths[0], None if masks is None else masks[0], K, dev) if first_pose is None else _host_poses(first_pose)[0]
   poses = np.stack([first] * n)
   for k in range(1, n):
     poses[k] = poses[k - 1]
     refs = list(range(max(0, k - int(window)), k))
     pr = [(k, j) for j in refs] + [(j, k) for j in refs]
-    poses, _ = _joint_on(depths, normals, K, poses, [v for v in range(n) if v != k], pr, stages, neighbours, max_angle_deg, damping)
+    poses, _ = _joint_on(depths, normals, K, poses, [v for v in range(n) if v != k], pr, stages, neighbours, max_angle_deg, damping, *photo)
   info = dict(odometry=poses.copy(), joint=None)
   if joint:
-    poses, info['joint'] = _joint_on(depths, normals, K, poses, [0], None, joint_stages, neighbours, max_angle_deg, damping)
+    poses, info['joint'] = _joint_on(depths, normals, K, poses, [0], None, joint_stages, neighbours, max_angle_deg, damping, *photo)
   return poses, info
 
 
 def reconstruct_object(views, voxel_size=0.002, trunc=None, min_weight=1, depth_filter=True, margin=None, device='cuda', refine_poses=False,
-                       max_vertices=None, simplify_cell=None, components='largest', texture=None, symmetries=None, estimate_poses=False):
+                       max_vertices=None, simplify_cell=None, components='largest', texture=None, symmetries=None, estimate_poses=False,
+                       photometric=False):
   """_reconstruct_mesh (which documents every other argument) and, with `symmetries`, the rotational symmetries of the finished mesh:
   symmetries=True runs Utils.find_symmetries with its defaults, a dict gives its keyword arguments (tol, max_order, ..), and the call
   then returns (mesh, info) - info['symmetry_tfs'] is what FoundationPose(symmetry_tfs=) takes, and bop.write_models_info writes the
   rest to models_info.json.  The default (None or False) returns the mesh alone, as before."""
   mesh = _reconstruct_mesh(views, voxel_size=voxel_size, trunc=trunc, min_weight=min_weight, depth_filter=depth_filter, margin=margin,
                            device=device, refine_poses=refine_poses, max_vertices=max_vertices, simplify_cell=simplify_cell,
-                           components=components, texture=texture, estimate_poses=estimate_poses)
+                           components=components, texture=texture, estimate_poses=estimate_poses, photometric=photometric)
   if symmetries is None or symmetries is False:
     return mesh
   from .Utils import find_symmetries
@@ -635,7 +727,7 @@ def reconstruct_object(views, voxel_size=0.002, trunc=None, min_weight=1, depth_
 
 
 def _reconstruct_mesh(views, voxel_size=0.002, trunc=None, min_weight=1, depth_filter=True, margin=None, device='cuda', refine_poses=False,
-                      max_vertices=None, simplify_cell=None, components='largest', texture=None, estimate_poses=False):
+                      max_vertices=None, simplify_cell=None, components='largest', texture=None, estimate_poses=False, photometric=False):
   """Reference views -> mesh (synthetic.SimpleMesh with vertex normals and colours).  `views`: a folder in the reference's layout
   (load_reference_views) or a dict with depths, masks, K, cam_in_obs and optionally rgbs.  depth_filter runs erode_depth and
   bilateral_filter_depth on every view first, as the estimator does with an observed frame.  The fusion and the extraction run on the
@@ -654,6 +746,9 @@ def _reconstruct_mesh(views, voxel_size=0.002, trunc=None, min_weight=1, depth_f
   anchor, its defaults).  estimate_poses=True (or a dict of estimate_view_poses' first_pose, window, stages, joint, joint_stages,
   neighbours, max_angle_deg, max_jump, damping) is for views WITHOUT cam_in_obs: the poses come from estimate_view_poses on the eroded
   maps, and refine_poses, if given, then runs on them.  A folder is then read without cam_in_ob/.
+  photometric (False, True or a weight: joint_refine_view_poses) goes to whichever of refine_poses='joint' and estimate_poses runs, to
+  both if both do; the views need rgbs.  ValueError if neither runs and with refine_poses=True (or a dict): the TSDF procedure has no
+  such term.
   max_vertices or simplify_cell (one of them; default neither: the mesh as extracted) reduces the mesh by vertex clustering after the
   largest-component step (Utils.simplify_mesh): the rasteriser keeps a hypothesis' vertices on chip up to 8192 vertices, and a 2 mm fusion
   of a hand-sized object has tens of times that.
@@ -664,6 +759,12 @@ def _reconstruct_mesh(views, voxel_size=0.002, trunc=None, min_weight=1, depth_f
   cos_min, min_cell.  depth_tol defaults to 2 voxels here.  The views need rgbs, at most 64 of them."""
   if max_vertices is not None and simplify_cell is not None:
     raise ValueError('reconstruct_object: give max_vertices or simplify_cell, not both')
+  if _photo_weight(photometric) is not None:
+    if not isinstance(refine_poses, str) and refine_poses:
+      raise ValueError("reconstruct_object: photometric goes with refine_poses='joint' or estimate_poses; refine_view_poses (refine_poses=True or a "
+                       'dict) aligns to the fused volume and has no photometric term')
+    if not estimate_poses and refine_poses != 'joint':
+      raise ValueError("reconstruct_object: photometric needs refine_poses='joint' or estimate_poses to act on")
   if isinstance(views, (str, os.PathLike)):
     views = load_reference_views(views, poses=not estimate_poses)
   bake = None
@@ -686,13 +787,13 @@ def _reconstruct_mesh(views, voxel_size=0.002, trunc=None, min_weight=1, depth_f
     if set(given) - set(kw):
       raise TypeError(f'estimate_poses: unknown keys {sorted(set(given) - set(kw))}')
     kw.update(given)
-    got, _ = estimate_view_poses(dict(views, depths=eroded), depth_filter=False, device=dev, **kw)
+    got, _ = estimate_view_poses(dict(views, depths=eroded), depth_filter=False, device=dev, photometric=photometric, **kw)
     views = dict(views, cam_in_obs=got)
   cam_in_obs = views['cam_in_obs']
   if isinstance(refine_poses, str):
     if refine_poses != 'joint':
       raise ValueError(f"refine_poses must be False, True, 'joint' or a dict of refine_view_poses' keyword arguments, got {refine_poses!r}")
-    cam_in_obs, _ = joint_refine_view_poses(dict(views, depths=eroded), depth_filter=False, device=dev)
+    cam_in_obs, _ = joint_refine_view_poses(dict(views, depths=eroded), depth_filter=False, device=dev, photometric=photometric)
   elif refine_poses:
     kw = dict(anchor=0, order='greedy', rounds=0, trunc=None, margin=None, iterations=10, min_pixels=100, damping=1e-9, max_step=None)
     given = dict(refine_poses) if isinstance(refine_poses, dict) else {}

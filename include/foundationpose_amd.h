@@ -757,19 +757,57 @@ int fp_tsdf_align(fp_ctx *ctx, const fp_tsdf *vol, const float *d_depth, const u
  *      any index of it.  fp_depth_pairs_align SYNCHRONISES the stream (the partial sums and the pairs' matrices live in the context's
  *      arena for the duration of the call).  At most FP_DEPTH_ALIGN_MAX_PAIRS pairs per call (the partial sums of 256 pairs of 640 x 480
  *      pixels take 17 MB); the Python wrapper cuts longer lists into calls.  At most FP_TSDF_MAX_VIEWS views.
- *      Geometry only: a turntable of a rotationally symmetric object leaves the rotation about its axis unobservable.
+ *      Geometry only: a turntable of a rotationally symmetric object leaves the rotation about its axis unobservable (the photometric
+ *      term below is for that).
  *      FP_EINVAL, each checked before ctx is looked into: a null ctx, d_depth, d_normals, K (both calls), cam_in_ob, h_sums, or pairs with
  *      n_pairs > 0; a misaligned d_normals or d_rows; n_views outside 0 .. FP_TSDF_MAX_VIEWS (fp_depth_normals: 0 writes nothing); n_pairs
  *      < 0 or above the cap (0 writes nothing); a pair index outside 0 .. n_views-1, or s == t; H or W < 1; a non-finite K or fx or fy
  *      not > 0; zfar not > 0 (infinity is allowed); max_jump not > 0; dist_max not > 0; cos_min outside [-1, 1]; a view matrix that is
- *      not finite or whose last row is not 0 0 0 1. */
+ *      not finite or whose last row is not 0 0 0 1.
+ *      Photometric term (optional; fp_view_intensity, fp_depth_pairs_align_photo): a grey-value residual on the SAME association, for
+ *      surfaces whose geometry leaves a direction free (a turntable of a bottle, a face seen head-on) but whose texture does not.
+ *      Same number format and ordering conventions as above.  tests/photo_icp_oracle.py restates both rules in numpy.
+ *      Intensity map.  fp_view_intensity reads d_rgb (n_views,H,W,3) uint8 and the normals of fp_depth_normals and writes d_intensity
+ *      (n_views,H,W,4) fp32, 16-byte aligned (d_normals too; FP_EINVAL otherwise), one thread per pixel; nothing synchronises.  Per pixel:
+ *        I(r,c) = ((0.299f (float)R + 0.587f (float)G) + 0.114f (float)B) / 255.f
+ *        write (0,0,0,0) unless normals[r,c].w != 0 and 1 <= r <= H-2 and 1 <= c <= W-2 (a normal of fp_depth_normals is never on the
+ *        border; the condition keeps the neighbours inside the view for any other map)
+ *        gx = (I(r,c+1) - I(r,c-1)) 0.5f,   gy = (I(r+1,c) - I(r-1,c)) 0.5f;   write (I(r,c), gx, gy, 1)
+ *      Where the normal is there, the pixel and its four neighbours are masked, valid depth within max_jump of each other, so the
+ *      gradient never crosses an occlusion edge.
+ *      Photometric row.  fp_depth_pairs_align_photo is fp_depth_pairs_align with d_intensity and i_max; per pair (s, t) and pixel (r, c)
+ *      of view s that passed EVERY condition of the rule above, with the same x, y, u, v (before rounding), cf, rf:
+ *        a4 = intensity_s[r,c],  b4 = intensity_t[rf,cf];   skip unless a4.w != 0;   skip unless b4.w != 0
+ *        du = u - cf,  dv = v - rf                                                      the projection's offset from the pixel centre
+ *        r = ((b4.x + b4.y du) + b4.z dv) - a4.x                                        first-order sub-pixel value of view t minus view s
+ *        skip unless fabsf(r) < i_max
+ *        jx = (b4.y fx) / y.z,  jy = (b4.z fy) / y.z,  jz = -((jx y.x + jy y.y) / y.z)   d r / d y: the image gradient through the projection
+ *        a_k = (Rc_t[k][0] jx + Rc_t[k][1] jy) + Rc_t[k][2] jz                           the same in the object frame
+ *        J = (a.x, a.y, a.z, x.y a.z - x.z a.y, x.z a.x - x.x a.z, x.x a.y - x.y a.x)
+ *      As for the geometric row J is dr / dxi_s and dr / dxi_t is exactly -J, at fixed association and fixed b4, du and dv taken as
+ *      functions of y: y = C_t^-1 expm(-xi_t) x with x = expm(xi_s) C_s p, and r depends on the two poses through y only (a4 is a value
+ *      of view s at a fixed pixel, b4 a record of view t at a fixed pixel), so moving view t by xi moves y as moving view s by -xi does.
+ *      h_sums is (n_pairs, FP_PHOTO_ALIGN_TERMS = 58): terms 0 .. 28 are fp_depth_pairs_align's 29, bit-identical to that call's on the
+ *      same inputs; terms 29 .. 57 are the same 29 quantities of the photometric rows (the number of valid photometric pixels last),
+ *      formed and added in the same way.  The residual is in units of intensity (0 .. 1): the caller weighs it against metres
+ *      (reconstruct.py: combine_sums).  d_rows, when not null, is (n_pairs,H,W,16): the 8 geometric floats, then (J0 .. J5, r, 1) of the
+ *      photometric row or eight zeros.  i_max > 0 (infinity is allowed).  Every other check, limit and the synchronisation are those of
+ *      fp_depth_pairs_align; d_intensity must not be null and must be 16-byte aligned.
+ *      Limits: brightness constancy is assumed (a camera moving round a static object under fixed light; NOT an object turning under a
+ *      fixed lamp, speculars or exposure changes); grey only; no image pyramid - the basin is half a texture wavelength; no blur - the
+ *      caller may pre-filter the rgb. */
 #define FP_DEPTH_ALIGN_TERMS 29        /* doubles per pair of fp_depth_pairs_align's h_sums */
-#define FP_DEPTH_ALIGN_MAX_PAIRS 256   /* per fp_depth_pairs_align call */
+#define FP_PHOTO_ALIGN_TERMS 58        /* doubles per pair of fp_depth_pairs_align_photo's h_sums */
+#define FP_DEPTH_ALIGN_MAX_PAIRS 256   /* per fp_depth_pairs_align and fp_depth_pairs_align_photo call */
 int fp_depth_normals(fp_ctx *ctx, const float *d_depth, const uint8_t *d_mask, int n_views, int H, int W, const double *K, float zfar,
                      float max_jump, float *d_normals, void *stream);
 int fp_depth_pairs_align(fp_ctx *ctx, const float *d_depth, const float *d_normals, int n_views, int H, int W, const double *K,
                          const double *cam_in_ob, const int32_t *pairs, int n_pairs, float dist_max, float cos_min, float *d_rows,
                          double *h_sums, void *stream);
+int fp_view_intensity(fp_ctx *ctx, const uint8_t *d_rgb, const float *d_normals, int n_views, int H, int W, float *d_intensity, void *stream);
+int fp_depth_pairs_align_photo(fp_ctx *ctx, const float *d_depth, const float *d_normals, const float *d_intensity, int n_views, int H, int W,
+                               const double *K, const double *cam_in_ob, const int32_t *pairs, int n_pairs, float dist_max, float cos_min,
+                               float i_max, float *d_rows, double *h_sums, void *stream);
 
 /* ---- texture baking: the colours of posed RGB-D reference views gathered into a per-face texture atlas of a mesh - the last stage of
  *      the model-free set-up, after the simplification (fp_mesh_simplify_* refuses textured meshes: simplify first, then bake).  The

@@ -5,8 +5,11 @@ Beside them the bytes each call must move and their share of the HBM peak of the
 once (the four neighbours come from the caches), 16 bytes written per pixel.  Pairs: per pair the source view's normals and depth once
 (20 bytes per pixel - the 16 views are read 4 times each, from L2 / MALL after the first), the partial-sum slab written and read once,
 and the gathers: 20 bytes per source pixel that projects into the target (neighbouring pixels project to neighbouring pixels, so most
-of these are served by the caches).  Then the wall time of a whole joint_refine_view_poses beside a whole refine_view_poses on the same
-views with every pose but the anchor's 2 mm / 0.75 degrees off, interleaved in one process (host clock, device synchronised).
+of these are served by the caches).  The photometric term beside them: fp_view_intensity (the normals and 3 bytes of rgb read, 16 bytes written
+per pixel), and one fp_depth_pairs_align_photo call with fp_depth_pairs_align calls in between, call by call, in the same process -
+it adds one 16-byte source read and one 16-byte gather per pixel to the 20 + 20 bytes, and its slab holds 58 numbers.  Then the wall time of a whole joint_refine_view_poses beside a whole refine_view_poses on the same
+views with every pose but the anchor's 2 mm / 0.75 degrees off, and of joint_refine_view_poses(photometric=True) on them (the unlit
+render of the mesh is their rgb), interleaved in one process (host clock, device synchronised).
 Prints one JSON line.
 usage: python scripts/bench_depth_icp.py [--reps R] [--refine-voxel 0.002] [--refine-mm 2] [--refine-deg 0.75] [--out profiles/bench_depth_icp.json]"""
 import argparse
@@ -68,6 +71,24 @@ def timed(run, reps):
   return float(np.min(times)), float(np.median(times))
 
 
+def timed_interleaved(runs, reps):
+  """{name: (min, median)} of the calls of `runs` {name: callable}, timed one after the other in every repetition"""
+  for _ in range(3):
+    for run in runs.values():
+      run()
+  torch.cuda.synchronize()
+  times = {name: [] for name in runs}
+  for _ in range(reps):
+    for name, run in runs.items():
+      e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+      e0.record()
+      run()
+      e1.record()
+      torch.cuda.synchronize()
+      times[name].append(e0.elapsed_time(e1))
+  return {name: (float(np.min(t)), float(np.median(t))) for name, t in times.items()}
+
+
 def perturbed(cams, trans, rot_deg, seed, keep_first=False):
   rs = np.random.RandomState(seed)
   out = cams.copy()
@@ -92,8 +113,9 @@ def main():
   mt = make_mesh_tensors(mesh, device=dev)
   K = np.array([[800.0, 0, 319.5], [0, 800.0, 239.5], [0, 0, 1.0]])
   cams = np.stack([look_at(e) for e in fibonacci_eyes(N_VIEWS, 0.6)])
-  _, depth, _ = U.nvdiffrast_render(K=K, H=H, W=W, ob_in_cams=np.linalg.inv(cams).astype(np.float32), mesh_tensors=mt)
+  color, depth, _ = U.nvdiffrast_render(K=K, H=H, W=W, ob_in_cams=np.linalg.inv(cams).astype(np.float32), mesh_tensors=mt)
   depth = depth.contiguous()
+  rgb = (color.clamp(0, 1) * 255).round().to(torch.uint8).contiguous()
   mask = (depth > 0).to(torch.uint8).contiguous()
   off = perturbed(cams, 0.003, 1.0, 0)
   res = dict(reps=args.reps, hbm_peak_GBs=HBM_PEAK_GBS, views=N_VIEWS, image=[H, W])
@@ -116,12 +138,31 @@ def main():
                             unique_bytes=N_VIEWS * H * W * 20 + 2 * P * tiles * 29 * 8, source_pixels=sources, valid_pixels=valid, gathered_bytes_at_most=sources * 20,
                             workgroups=P * tiles, rms_mm=float(1e3 * np.sqrt(sums[:, 27].sum() / max(valid, 1))))
 
+  intensity = R.view_intensity(rgb, normals)
+  t_min, t_med = timed(lambda: R.view_intensity(rgb, normals), args.reps)
+  nbytes = N_VIEWS * H * W * (16 + 3 + 16)
+  res['view_intensity'] = dict(ms_min=t_min, ms_median=t_med, bytes=nbytes, GBs=nbytes / (t_min * 1e-3) / 1e9, hbm_fraction=nbytes / (t_min * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                               records=int((intensity[..., 3] != 0).sum()))
+  sums58 = R.align_pairs_step(depth, normals, K, off, pairs, 0.02, 0.5, intensity=intensity)
+  assert np.array_equal(sums58[:, :29], sums)
+  both = timed_interleaved(dict(geometric=lambda: R.align_pairs_step(depth, normals, K, off, pairs, 0.02, 0.5),
+                                photometric=lambda: R.align_pairs_step(depth, normals, K, off, pairs, 0.02, 0.5, intensity=intensity)), args.reps)
+  nbytes = P * H * W * 36 + 2 * P * tiles * 58 * 8
+  (t_min, t_med), (g_min, g_med) = both['photometric'], both['geometric']
+  pvalid = int(sums58[:, 57].sum())
+  res['pairs_align_photo'] = dict(pairs=P, ms_min=t_min, ms_median=t_med, bytes=nbytes, GBs=nbytes / (t_min * 1e-3) / 1e9,
+                                  hbm_fraction=nbytes / (t_min * 1e-3) / 1e9 / HBM_PEAK_GBS, unique_bytes=N_VIEWS * H * W * 36 + 2 * P * tiles * 58 * 8,
+                                  bytes_over_geometric=nbytes / res['pairs_align']['bytes'], gathered_bytes_at_most=sources * 36, valid_pixels=pvalid,
+                                  rms_intensity=float(np.sqrt(sums58[:, 56].sum() / max(pvalid, 1))), geometric_interleaved_ms_min=g_min,
+                                  geometric_interleaved_ms_median=g_med, ms_over_geometric=t_min / g_min)
+
   ball = np.random.RandomState(11).randn(2000, 3)
   ball = ball / np.linalg.norm(ball, axis=1, keepdims=True) * 0.05 * np.random.RandomState(12).rand(2000, 1) ** (1 / 3)
-  views = dict(depths=depth, masks=mask, K=K, cam_in_obs=perturbed(cams, args.refine_mm * 1e-3, args.refine_deg, 1, keep_first=True))
+  views = dict(depths=depth, masks=mask, rgbs=rgb, K=K, cam_in_obs=perturbed(cams, args.refine_mm * 1e-3, args.refine_deg, 1, keep_first=True))
   runs = dict(joint=lambda: R.joint_refine_view_poses(views, depth_filter=False, device=dev),
-              tsdf=lambda: R.refine_view_poses(views, voxel_size=args.refine_voxel, depth_filter=False, device=dev))
-  times, got = dict(joint=[], tsdf=[]), {}
+              tsdf=lambda: R.refine_view_poses(views, voxel_size=args.refine_voxel, depth_filter=False, device=dev),
+              photo=lambda: R.joint_refine_view_poses(views, depth_filter=False, device=dev, photometric=True))
+  times, got = dict(joint=[], tsdf=[], photo=[]), {}
   for _ in range(4):
     for name, run in runs.items():
       torch.cuda.synchronize()
@@ -130,7 +171,7 @@ def main():
       torch.cuda.synchronize()
       times[name].append((time.perf_counter() - t0) * 1e3)
   before = [displacement(views['cam_in_obs'][v], cams[v], ball) for v in range(1, N_VIEWS)]
-  for name, key in (('joint', 'joint_refine_view_poses'), ('tsdf', 'refine_view_poses')):
+  for name, key in (('joint', 'joint_refine_view_poses'), ('tsdf', 'refine_view_poses'), ('photo', 'joint_refine_view_poses_photometric')):
     after = [displacement(got[name][0][v], cams[v], ball) for v in range(1, N_VIEWS)]
     res[key] = dict(ms_first=times[name][0], ms_min=float(np.min(times[name][1:])), ms_median=float(np.median(times[name][1:])),
                     perturbation_mm=args.refine_mm, perturbation_deg=args.refine_deg, views_improved=int(np.sum(np.array(after) < np.array(before))),
@@ -139,6 +180,10 @@ def main():
   info = got['joint'][1]
   res['joint_refine_view_poses'].update(evaluations=int(len(info['rms'])), pairs=int(len(info['pairs'][0])), rms_mm_first=float(1e3 * info['rms'][0]),
                                         rms_mm_last=float(1e3 * info['rms'][-1]), eig_ratio_min=float(np.nanmin(info['eig_ratio'])))
+  info = got['photo'][1]
+  res['joint_refine_view_poses_photometric'].update(evaluations=int(len(info['rms'])), weight=R.PHOTO_WEIGHT, i_max=R.I_MAX, rms_mm_last=float(1e3 * info['rms'][-1]),
+                                                    photo_rms_first=float(info['photo_rms'][0]), photo_rms_last=float(info['photo_rms'][-1]),
+                                                    eig_ratio_min=float(np.nanmin(info['eig_ratio'])))
   res['refine_view_poses'].update(voxel=args.refine_voxel, band=2 * args.refine_voxel)
   line = json.dumps(res)
   print(line)

@@ -1,6 +1,7 @@
 """A mesh from a folder of posed RGB-D reference views (the reference's model-free layout: rgb/, depth_enhanced/ or depth/, mask/,
 cam_in_ob/, K.txt), by TSDF fusion and marching tetrahedra on the GPU (foundationpose_amd.reconstruct).
 usage: python scripts/reconstruct_object.py DIR [--voxel 0.002] [--trunc T] [--min-weight 1] [--no-depth-filter] [--refine-poses | --joint-refine] [--estimate-poses]
+       [--photometric [WEIGHT]]
        [--max-vertices N | --simplify-cell C] [--min-component-fraction X] [--texture [SIZE]] [--out DIR/model/model.obj]
        [--compare-to MODEL] [--symmetries [--symmetry-tol T]]
 The output format follows the extension: .obj or .ply.  --refine-poses aligns every view but the first to the geometry fused so far before the
@@ -8,7 +9,9 @@ fusion (reconstruct.refine_view_poses) and also writes the poses it used to DIR/
 together from depth alone instead (reconstruct.joint_refine_view_poses: pairwise ICP, view 0 the anchor) and writes cam_in_ob_refined/ too.
 --estimate-poses is for a folder WITHOUT cam_in_ob/ - a masked RGB-D sequence whose neighbouring frames overlap: the poses come from
 reconstruct.estimate_view_poses (the object frame is the first camera's, moved to the object) and are written to DIR/cam_in_ob_estimated/;
-it is also what happens without the flag when DIR has no cam_in_ob/.  --max-vertices N (8192: the
+it is also what happens without the flag when DIR has no cam_in_ob/.  --photometric [WEIGHT] adds the grey-value residual of the views' rgb to
+--joint-refine and to the pose estimation (WEIGHT: metres per unit of intensity, default 0.03; brightness constancy is assumed - a camera
+moving round a static object under fixed light); it is refused with --refine-poses, which has no such term.  --max-vertices N (8192: the
 rasteriser's on-chip vertex limit) or --simplify-cell C (metres) reduces the mesh by vertex clustering (Utils.simplify_mesh).  By default
 only the connected component with the most faces is kept; --min-component-fraction X (0 .. 1) keeps EVERY component with at least X of
 the largest one's faces (Utils.clean_mesh: an object of several parts).  --texture bakes a texture atlas from the views' rgb onto the
@@ -40,6 +43,7 @@ def main():
   ap.add_argument('--refine-poses', action='store_true')
   ap.add_argument('--joint-refine', action='store_true')
   ap.add_argument('--estimate-poses', action='store_true')
+  ap.add_argument('--photometric', type=float, nargs='?', const=True, default=False, metavar='WEIGHT')
   ap.add_argument('--max-vertices', type=int, default=None)
   ap.add_argument('--simplify-cell', type=float, default=None)
   ap.add_argument('--min-component-fraction', type=float, default=None)
@@ -54,9 +58,12 @@ def main():
     ap.error('--texture writes an OBJ with its .mtl and .png: give --out a name ending in .obj')
   if args.refine_poses and args.joint_refine:
     ap.error('give --refine-poses or --joint-refine, not both')
-  if args.estimate_poses or not os.path.isdir(os.path.join(args.dir, 'cam_in_ob')):
+  estimate = args.estimate_poses or not os.path.isdir(os.path.join(args.dir, 'cam_in_ob'))
+  if args.photometric is not False and (args.refine_poses or not (estimate or args.joint_refine)):
+    ap.error('--photometric goes with --joint-refine or --estimate-poses (--refine-poses has no photometric term)')
+  if estimate:
     views = load_reference_views(args.dir, poses=False)
-    poses, _ = estimate_view_poses(views, depth_filter=not args.no_depth_filter)
+    poses, _ = estimate_view_poses(views, depth_filter=not args.no_depth_filter, photometric=args.photometric)
     os.makedirs(os.path.join(args.dir, 'cam_in_ob_estimated'), exist_ok=True)
     for name, pose in zip(views['names'], poses):
       np.savetxt(os.path.join(args.dir, 'cam_in_ob_estimated', name + '.txt'), pose, fmt='%.18e')
@@ -65,7 +72,7 @@ def main():
     views = load_reference_views(args.dir)
   if args.refine_poses or args.joint_refine:
     if args.joint_refine:
-      poses, info = joint_refine_view_poses(views, depth_filter=not args.no_depth_filter)
+      poses, info = joint_refine_view_poses(views, depth_filter=not args.no_depth_filter, photometric=args.photometric)
     else:
       poses, info = refine_view_poses(views, voxel_size=args.voxel, depth_filter=not args.no_depth_filter)
     os.makedirs(os.path.join(args.dir, 'cam_in_ob_refined'), exist_ok=True)
