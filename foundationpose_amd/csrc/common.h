@@ -1,6 +1,7 @@
 // Shared host-side plumbing for libfoundationpose_amd (gfx950).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -50,6 +51,24 @@ inline bool fp_env_set(const char *name) { return getenv(name) != nullptr; }
     int _rc = (expr);                \
     if (_rc != FP_OK) return _rc;    \
   } while (0)
+
+// The camera matrix as every kernel takes it - fx, fy, cx, cy rounded to fp32.  `fn` names the entry point in the message.
+inline int fp_check_camera(const char *fn, const double *K) {
+  const float fx = (float)K[0], fy = (float)K[4], cx = (float)K[2], cy = (float)K[5];
+  FP_REQUIRE(fx > 0.f && fy > 0.f && isfinite(fx) && isfinite(fy) && isfinite(cx) && isfinite(cy),
+             "%s: K is not a finite camera matrix with positive focal lengths", fn);
+  return FP_OK;
+}
+
+// n_views camera-to-object matrices (4 x 4, row-major): finite, with the last row 0 0 0 1
+inline int fp_check_view_matrices(const char *fn, const double *cam_in_ob, int n_views) {
+  for (int v = 0; v < n_views; ++v) {
+    const double *m = cam_in_ob + (size_t)v * 16;
+    for (int e = 0; e < 12; ++e) FP_REQUIRE(isfinite(m[e]), "%s: cam_in_ob[%d] is not finite", fn, v);
+    FP_REQUIRE(m[12] == 0 && m[13] == 0 && m[14] == 0 && m[15] == 1, "%s: the last row of cam_in_ob[%d] is not 0 0 0 1", fn, v);
+  }
+  return FP_OK;
+}
 
 struct MeshDev {
   const float *pos, *vnormals, *vcolor, *uv, *tex;
@@ -507,7 +526,7 @@ int launch_pose_errors(const float *pts, int n_pts, const float *pred, const flo
 // bytes of per-workgroup candidates
 size_t mesh_diameter_slab_bytes(int n_pts);
 int launch_mesh_diameter(const float *pts, int n_pts, void *slab, float *out, int32_t *pair, hipStream_t s);
-// tsdf.hip: in-place exclusive scan of n 64-bit words (reduce, scan of the block sums, add: a workgroup never waits for another one);
+// scan.hip: in-place exclusive scan of n 64-bit words (reduce, scan of the block sums, add: a workgroup never waits for another one);
 // `sums` holds scan_sums_words(n) words for the block sums of every level
 size_t scan_sums_words(long long n);
 int scan_exclusive(unsigned long long *data, long long n, unsigned long long *sums, hipStream_t s);

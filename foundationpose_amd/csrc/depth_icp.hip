@@ -8,10 +8,9 @@
 // owns (pair, a tile of PA_TILE source pixels); the pair is uniform in the workgroup, so its matrices arrive as scalar loads from the
 // pair table.  A lane takes PA_PIX pixels, PA_THREADS apart (the source reads coalesce), in three passes over them: source normal and
 // depth; then the projection into the target and the two gathers of each pixel (16-byte normal, 4-byte depth) - nothing in this pass
-// depends on a gathered value, so all PA_PIX x 2 gathers are in flight together; then the arithmetic.  The 29 sums are kept in double
-// per lane, added over the wave by the butterfly of device_util.h, over the waves in wave order through LDS, and written to the
-// workgroup's own slot of the slab; depth_pairs_fold_kernel adds the slots of a pair in tile order.  No atomics.  A wave whose 256
-// source pixels have no normal (the background of a masked view) skips passes two and three.
+// depends on a gathered value, so all PA_PIX x 2 gathers are in flight together; then the arithmetic.  The row, the 29 sums in double
+// and their way through the wave, LDS and the slab to gn_fold_kernel are those of gn_sums.h, where the summation order is stated.  No
+// atomics.  A wave whose 256 source pixels have no normal (the background of a masked view) skips passes two and three.
 //
 // The photometric term (fp_view_intensity, fp_depth_pairs_align_photo) rides on the same association.  view_intensity_kernel is one thread
 // per pixel again: the pixel's normal, the rgb of the pixel and of its four neighbours where the normal is there, one 16-byte write.
@@ -21,6 +20,7 @@
 // a time; the workgroup's slot then holds 58 numbers.  depth_pairs_kernel<false> is the geometric kernel, statement for statement.
 #include "common.h"
 #include "device_util.h"
+#include "gn_sums.h"
 
 #include <math.h>
 
@@ -169,9 +169,9 @@ __global__ __launch_bounds__(PA_THREADS) void depth_pairs_kernel(const float *__
   }
 
   // pass 3: the gates, the row, the sums
-  double acc[FP_DEPTH_ALIGN_TERMS];
+  double acc[GN_TERMS];
 #pragma unroll
-  for (int e = 0; e < FP_DEPTH_ALIGN_TERMS; ++e) acc[e] = 0.0;
+  for (int e = 0; e < GN_TERMS; ++e) acc[e] = 0.0;
 #pragma unroll
   for (int q = 0; q < PA_PIX; ++q) {
     bool valid = ok[q] && nt[q].w != 0.f;
@@ -190,42 +190,17 @@ __global__ __launch_bounds__(PA_THREADS) void depth_pairs_kernel(const float *__
     for (int a = 0; a < 3; ++a) no[a] = (m.rct[a * 3] * nx + m.rct[a * 3 + 1] * ny) + m.rct[a * 3 + 2] * nz;
     const float X = x[q][0], Y = x[q][1], Z = x[q][2];
     float J[6] = {no[0], no[1], no[2], Y * no[2] - Z * no[1], Z * no[0] - X * no[2], X * no[1] - Y * no[0]};
-    if (!valid) {
-#pragma unroll
-      for (int i = 0; i < 6; ++i) J[i] = 0.f;
-      r = 0.f;
-    }
-    if (rows && pix[q] < hw) {
-      float4 *o = (float4 *)(rows + ((size_t)pr * (size_t)hw + (size_t)pix[q]) * ROW);
-      o[0] = make_float4(J[0], J[1], J[2], J[3]);
-      o[1] = make_float4(J[4], J[5], r, valid ? 1.f : 0.f);
-    }
+    gn_mask(J, r, valid);
+    if (rows && pix[q] < hw) gn_store_row((float4 *)(rows + ((size_t)pr * (size_t)hw + (size_t)pix[q]) * ROW), J, r, valid);
     if constexpr (PHOTO) geo[q] = valid;
-    double Jd[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) Jd[i] = (double)J[i];
-    const double rd = (double)r;
-    int e = 0;
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-#pragma unroll
-      for (int j = i; j < 6; ++j) acc[e++] += Jd[i] * Jd[j];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) acc[21 + i] += Jd[i] * rd;
-    acc[27] += rd * rd;
-    acc[28] += valid ? 1.0 : 0.0;
+    gn_accumulate(acc, J, r, valid);
   }
-
-#pragma unroll
-  for (int e = 0; e < FP_DEPTH_ALIGN_TERMS; ++e) {
-    const double s = wave_sum(acc[e]);
-    if ((tid & 63) == 0) red[tid >> 6][e] = s;
-  }
+  gn_wave_to_lds(acc, red[tid >> 6], 0);
 
   // pass 4 (PHOTO): the photometric row and its sums, the 29 accumulators used again
   if constexpr (PHOTO) {
 #pragma unroll
-    for (int e = 0; e < FP_DEPTH_ALIGN_TERMS; ++e) acc[e] = 0.0;
+    for (int e = 0; e < GN_TERMS; ++e) acc[e] = 0.0;
 #pragma unroll
     for (int q = 0; q < PA_PIX; ++q) {
       bool valid = geo[q] && ia[q].w != 0.f && ib[q].w != 0.f;
@@ -238,68 +213,15 @@ __global__ __launch_bounds__(PA_THREADS) void depth_pairs_kernel(const float *__
       for (int k = 0; k < 3; ++k) a[k] = (m.rct[k * 3] * jx + m.rct[k * 3 + 1] * jy) + m.rct[k * 3 + 2] * jz;
       const float X = x[q][0], Y = x[q][1], Z = x[q][2];
       float J[6] = {a[0], a[1], a[2], Y * a[2] - Z * a[1], Z * a[0] - X * a[2], X * a[1] - Y * a[0]};
-      if (!valid) {
-#pragma unroll
-        for (int i = 0; i < 6; ++i) J[i] = 0.f;
-        r = 0.f;
-      }
-      if (rows && pix[q] < hw) {
-        float4 *o = (float4 *)(rows + ((size_t)pr * (size_t)hw + (size_t)pix[q]) * ROW);
-        o[2] = make_float4(J[0], J[1], J[2], J[3]);
-        o[3] = make_float4(J[4], J[5], r, valid ? 1.f : 0.f);
-      }
-      double Jd[6];
-#pragma unroll
-      for (int i = 0; i < 6; ++i) Jd[i] = (double)J[i];
-      const double rd = (double)r;
-      int e = 0;
-#pragma unroll
-      for (int i = 0; i < 6; ++i)
-#pragma unroll
-        for (int j = i; j < 6; ++j) acc[e++] += Jd[i] * Jd[j];
-#pragma unroll
-      for (int i = 0; i < 6; ++i) acc[21 + i] += Jd[i] * rd;
-      acc[27] += rd * rd;
-      acc[28] += valid ? 1.0 : 0.0;
+      gn_mask(J, r, valid);
+      if (rows && pix[q] < hw) gn_store_row((float4 *)(rows + ((size_t)pr * (size_t)hw + (size_t)pix[q]) * ROW) + 2, J, r, valid);
+      gn_accumulate(acc, J, r, valid);
     }
-#pragma unroll
-    for (int e = 0; e < FP_DEPTH_ALIGN_TERMS; ++e) {
-      const double s = wave_sum(acc[e]);
-      if ((tid & 63) == 0) red[tid >> 6][FP_DEPTH_ALIGN_TERMS + e] = s;
-    }
+    gn_wave_to_lds(acc, red[tid >> 6], GN_TERMS);
   }
   }
   __syncthreads();
-  if (tid < TERMS) {
-    double s = red[0][tid];
-    for (int wv = 1; wv < PA_THREADS / 64; ++wv) s += red[wv][tid];
-    slab[((size_t)pr * n_tiles + tile) * TERMS + tid] = s;
-  }
-}
-
-// one thread per (pair, term): the tiles' slots in tile order; TERMS numbers per slot
-template <int TERMS>
-__global__ __launch_bounds__(64) void depth_pairs_fold_kernel(const double *__restrict__ slab, int n_pairs, int n_tiles, double *__restrict__ sums) {
-  const int t = blockIdx.x * 64 + threadIdx.x;
-  if (t >= n_pairs * TERMS) return;
-  const int p = t / TERMS, e = t % TERMS;
-  const double *sb = slab + (size_t)p * n_tiles * TERMS + e;
-  double s = 0.0;
-  int k = 0;
-  for (; k + 8 <= n_tiles; k += 8) {      // eight loads in flight, added in tile order
-    double v[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = sb[(size_t)(k + i) * TERMS];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) s += v[i];
-  }
-  for (; k < n_tiles; ++k) s += sb[(size_t)k * TERMS];
-  sums[t] = s;
-}
-
-bool camera_ok(const double *K, DepthCam &cam, int H, int W) {
-  cam = DepthCam{(float)K[0], (float)K[4], (float)K[2], (float)K[5], H, W};
-  return cam.fx > 0.f && cam.fy > 0.f && isfinite(cam.fx) && isfinite(cam.fy) && isfinite(cam.cx) && isfinite(cam.cy);
+  gn_lds_to_slab(red, slab + ((size_t)pr * n_tiles + tile) * TERMS);
 }
 
 }  // namespace
@@ -314,8 +236,8 @@ extern "C" int fp_depth_normals(fp_ctx *ctx, const float *d_depth, const uint8_t
   FP_REQUIRE(H >= 1 && W >= 1, "fp_depth_normals: H %d, W %d", H, W);
   FP_REQUIRE(zfar > 0.f, "fp_depth_normals: zfar %g (> 0)", (double)zfar);
   FP_REQUIRE(max_jump > 0.f, "fp_depth_normals: max_jump %g (> 0)", (double)max_jump);
-  DepthCam cam;
-  FP_REQUIRE(camera_ok(K, cam, H, W), "fp_depth_normals: K is not a finite camera matrix with positive focal lengths");
+  FP_TRY(fp_check_camera("fp_depth_normals", K));
+  const DepthCam cam{(float)K[0], (float)K[4], (float)K[2], (float)K[5], H, W};
   const long long total = (long long)n_views * H * W;
   const long long blocks = (total + PA_THREADS - 1) / PA_THREADS;
   FP_REQUIRE(blocks <= 0x7fffffff, "fp_depth_normals: %d views of %d x %d pixels are too many for one launch", n_views, H, W);
@@ -345,13 +267,9 @@ int pairs_align(const char *fn, fp_ctx *ctx, const float *d_depth, const float *
   FP_REQUIRE(dist_max > 0.f, "%s: dist_max %g (> 0)", fn, (double)dist_max);
   FP_REQUIRE(cos_min >= -1.f && cos_min <= 1.f, "%s: cos_min %g (-1 .. 1)", fn, (double)cos_min);
   FP_REQUIRE(!photo || i_max > 0.f, "%s: i_max %g (> 0)", fn, (double)i_max);
-  DepthCam cam;
-  FP_REQUIRE(camera_ok(K, cam, H, W), "%s: K is not a finite camera matrix with positive focal lengths", fn);
-  for (int v = 0; v < n_views; ++v) {
-    const double *m = cam_in_ob + (size_t)v * 16;
-    for (int e = 0; e < 12; ++e) FP_REQUIRE(isfinite(m[e]), "%s: cam_in_ob[%d] is not finite", fn, v);
-    FP_REQUIRE(m[12] == 0 && m[13] == 0 && m[14] == 0 && m[15] == 1, "%s: the last row of cam_in_ob[%d] is not 0 0 0 1", fn, v);
-  }
+  FP_TRY(fp_check_camera(fn, K));
+  FP_TRY(fp_check_view_matrices(fn, cam_in_ob, n_views));
+  const DepthCam cam{(float)K[0], (float)K[4], (float)K[2], (float)K[5], H, W};
   std::vector<PairRec> recs((size_t)n_pairs);
   for (int p = 0; p < n_pairs; ++p) {
     const int s = pairs[2 * p], t = pairs[2 * p + 1];
@@ -391,12 +309,12 @@ int pairs_align(const char *fn, fp_ctx *ctx, const float *d_depth, const float *
     hipLaunchKernelGGL(depth_pairs_kernel<true>, grid, dim3(PA_THREADS), 0, s, d_depth, (const float4 *)d_normals, (const float4 *)d_intensity, cam,
                        (const PairRec *)d_recs, (int)n_tiles, dist_max * dist_max, cos_min, i_max, d_rows, slab);
     FP_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(depth_pairs_fold_kernel<FP_PHOTO_ALIGN_TERMS>, fold_grid, dim3(64), 0, s, (const double *)slab, n_pairs, (int)n_tiles, sums);
+    hipLaunchKernelGGL(gn_fold_kernel<FP_PHOTO_ALIGN_TERMS>, fold_grid, dim3(64), 0, s, (const double *)slab, n_pairs, (int)n_tiles, sums);
   } else {
     hipLaunchKernelGGL(depth_pairs_kernel<false>, grid, dim3(PA_THREADS), 0, s, d_depth, (const float4 *)d_normals, (const float4 *)nullptr, cam,
                        (const PairRec *)d_recs, (int)n_tiles, dist_max * dist_max, cos_min, 0.f, d_rows, slab);
     FP_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(depth_pairs_fold_kernel<FP_DEPTH_ALIGN_TERMS>, fold_grid, dim3(64), 0, s, (const double *)slab, n_pairs, (int)n_tiles, sums);
+    hipLaunchKernelGGL(gn_fold_kernel<FP_DEPTH_ALIGN_TERMS>, fold_grid, dim3(64), 0, s, (const double *)slab, n_pairs, (int)n_tiles, sums);
   }
   FP_CHECK_HIP(hipGetLastError());
   // the slab, the sums and the pair table go back to the arena when this returns: the stream has been synchronised by then

@@ -1,4 +1,4 @@
-// Device-side primitives shared by the gfx950 kernel files: LDS-DMA, counted waits, lane reductions, the token-tile load and the
+// Device-side primitives shared by the gfx950 kernel files: LDS-DMA, counted waits, lane and workgroup reductions, the token-tile load and the
 // bias start of the token GEMM accumulators.  Device only; include after common.h.  Everything is __forceinline__: a kernel
 // that uses a helper from here compiles to the instructions it had with a private copy.
 #pragma once
@@ -72,6 +72,22 @@ __device__ __forceinline__ int wave_min(int v) { return wave_reduce(v, [](int a,
 __device__ __forceinline__ int wave_max(int v) { return wave_reduce(v, [](int a, int b) { return max(a, b); }); }
 __device__ __forceinline__ float wave_max(float v) { return wave_reduce(v, [](float a, float b) { return fmaxf(a, b); }); }
 __device__ __forceinline__ double wave_max(double v) { return wave_reduce(v, [](double a, double b) { return fmax(a, b); }); }
+
+// sum over a workgroup of THREADS threads in a fixed order (the butterfly within each wave, then the waves in order), valid in thread 0.
+// `red` holds THREADS / 64 doubles of LDS; the first barrier lets the previous sum's `red` be read before it is written again.  The
+// butterfly is wave_sum written out: through the call hipcc orders the instructions of pose_errors_kernel (metrics.hip) differently.
+template <int THREADS>
+__device__ __forceinline__ double block_sum(double v, double *red) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double s = 0.0;
+  if (threadIdx.x == 0)
+    for (int i = 0; i < THREADS / 64; ++i) s += red[i];
+  return s;
+}
 
 // ---- token tile (tok_gemm.hip, tok_qkv.hip, head_mlp.hip) ----
 // ROWS rows x 512 fp16 of `src` (rows past M repeat the last one) -> LDS [k segment of 128][row][256 B], 16-byte chunk c of a

@@ -7,7 +7,7 @@
 //     Every value in the array only decreases, the trees only merge, and the root a component ends with is its lowest vertex index -
 //     WHICH unions won their compare-and-swap depends on the race, the final root does not;
 //   * one flatten pass then makes parent[v] that lowest index for every vertex: the label;
-//   * components are numbered by an exclusive scan over "v is its own label" (scan_exclusive, tsdf.hip), as fp_mesh_simplify numbers
+//   * components are numbered by an exclusive scan over "v is its own label" (scan_exclusive, scan.hip), as fp_mesh_simplify numbers
 //     its clusters; kept vertices and kept faces are numbered by two more scans, so both keep their input order;
 //   * the per-component counts are int32 atomic adds and the largest count an atomicMax: exact, so the order does not matter.  The
 //     lowest-numbered component among those of the largest count is an atomicMin over their labels.

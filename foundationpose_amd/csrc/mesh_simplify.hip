@@ -6,7 +6,7 @@
 //   * a cluster is found through an open-addressing table on the packed cell (cz << 42 | cy << 21 | cx - the same partition as the
 //     header's key, without a wait for the dims): a 64-bit compare-and-swap claims a slot, atomicMin records the lowest member.  WHICH
 //     slot a cluster gets depends on the race; nothing below reads a slot number except to find that lowest member again;
-//   * clusters are numbered by an exclusive scan over "this vertex is the lowest member of its cluster" (scan_exclusive, tsdf.hip);
+//   * clusters are numbered by an exclusive scan over "this vertex is the lowest member of its cluster" (scan_exclusive, scan.hip);
 //   * faces go through a second table keyed on the sorted id triple, atomicMin of the face index; the survivors and the clusters they
 //     reference are numbered by two more scans;
 //   * the attribute sums are 64-bit INTEGER adds of fixed-point values: exact, so the order of the adds does not matter.

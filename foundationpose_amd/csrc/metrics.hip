@@ -64,21 +64,6 @@ __device__ __forceinline__ void xform(const float *M, float x, float y, float z,
 
 __device__ __forceinline__ float norm3(float x, float y, float z) { return sqrtf(fmaf(x, x, fmaf(y, y, z * z))); }
 
-// sum over the workgroup in a fixed order (butterfly within each wave, then the waves in order); the total is valid in thread 0.
-// `red` holds PM_THREADS / 64 doubles; the caller synchronises before `red` is reused.  The butterfly is device_util.h's wave_sum written
-// out: through the call hipcc orders the instructions of pose_errors_kernel differently.
-__device__ __forceinline__ double block_sum(double v, double *red) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) red[w] = v;
-  __syncthreads();
-  double s = 0.0;
-  if (threadIdx.x == 0)
-    for (int i = 0; i < PM_THREADS / 64; ++i) s += red[i];
-  return s;
-}
-
 __global__ __launch_bounds__(PM_THREADS) void pose_errors_kernel(PoseErrArgs a) {
   __shared__ float4 lds[PM_CHUNK];
   double *red = (double *)lds;            // the block sums reuse the chunk buffer once the ADD-S loop is done
@@ -142,8 +127,7 @@ __global__ __launch_bounds__(PM_THREADS) void pose_errors_kernel(PoseErrArgs a) 
       if (valid[2 * k]) s += (double)sqrtf(m[k].x);
       if (valid[2 * k + 1]) s += (double)sqrtf(m[k].y);
     }
-    __syncthreads();                      // the chunk buffer becomes `red`
-    s = block_sum(s, red);
+    s = block_sum<PM_THREADS>(s, red);        // its first barrier: the chunk buffer becomes `red`
     if (tid == 0) slab[0] = s;
   }
 
@@ -159,8 +143,7 @@ __global__ __launch_bounds__(PM_THREADS) void pose_errors_kernel(PoseErrArgs a) 
       xform(D, px[q], py[q], pz[q], x, y, z);
       if (valid[q]) s += (double)norm3(x, y, z);
     }
-    __syncthreads();                      // `red` of the previous sum has been read
-    s = block_sum(s, red);
+    s = block_sum<PM_THREADS>(s, red);
     if (tid == 0) slab[(size_t)(PM_TERMS0 + k) * a.n_tiles] = s;
   }
 }

@@ -237,19 +237,6 @@ struct DistStatsArgs {
   double *slab;            // [DS_TERMS][n_tiles]
 };
 
-// sum over the workgroup in a fixed order (butterfly within each wave, then the waves in order), valid in thread 0
-__device__ __forceinline__ double ds_block_sum(double v, double *red) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();                        // `red` of the previous sum has been read
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-  if (threadIdx.x == 0)
-    for (int i = 0; i < DS_THREADS / 64; ++i) s += red[i];
-  return s;
-}
-
 __global__ __launch_bounds__(DS_THREADS) void dist_stats_kernel(DistStatsArgs a) {
   __shared__ double red[DS_THREADS / 64];
   double cnt = 0.0, bad = 0.0, s1 = 0.0, s2 = 0.0, mx = 0.0, le[FP_SURFDIST_MAX_TAUS];
@@ -272,13 +259,13 @@ __global__ __launch_bounds__(DS_THREADS) void dist_stats_kernel(DistStatsArgs a)
   }
   double *slab = a.slab + blockIdx.x;
   double v;
-  v = ds_block_sum(cnt, red);
+  v = block_sum<DS_THREADS>(cnt, red);
   if (threadIdx.x == 0) slab[(size_t)FP_SURFDIST_STATS_COUNT * a.n_tiles] = v;
-  v = ds_block_sum(s1, red);
+  v = block_sum<DS_THREADS>(s1, red);
   if (threadIdx.x == 0) slab[(size_t)FP_SURFDIST_STATS_SUM * a.n_tiles] = v;
-  v = ds_block_sum(s2, red);
+  v = block_sum<DS_THREADS>(s2, red);
   if (threadIdx.x == 0) slab[(size_t)FP_SURFDIST_STATS_SUM_SQ * a.n_tiles] = v;
-  v = ds_block_sum(bad, red);
+  v = block_sum<DS_THREADS>(bad, red);
   if (threadIdx.x == 0) slab[(size_t)FP_SURFDIST_STATS_NOT_FINITE * a.n_tiles] = v;
   mx = wave_max(mx);
   __syncthreads();
@@ -291,7 +278,7 @@ __global__ __launch_bounds__(DS_THREADS) void dist_stats_kernel(DistStatsArgs a)
 #pragma unroll
   for (int t = 0; t < FP_SURFDIST_MAX_TAUS; ++t) {
     if (t >= a.n_taus) break;
-    v = ds_block_sum(le[t], red);
+    v = block_sum<DS_THREADS>(le[t], red);
     if (threadIdx.x == 0) slab[(size_t)(FP_SURFDIST_STATS_TAU0 + t) * a.n_tiles] = v;
   }
 }

@@ -200,14 +200,12 @@ extern "C" int fp_texture_bake(fp_ctx *ctx, const float *d_pos, int V, const int
   FP_REQUIRE(cfg->depth_tol >= 0.f && cfg->cos_min > 0.f && cfg->cos_min <= 1.f && cfg->zfar > 0.f,
              "fp_texture_bake: depth_tol %g (>= 0), cos_min %g (in (0, 1]), zfar %g (> 0)", (double)cfg->depth_tol, (double)cfg->cos_min, (double)cfg->zfar);
   TexCfg k{T, c, g, F, V, cfg->top_n, H, W, n_views, (float)K[0], (float)K[4], (float)K[2], (float)K[5], cfg->zfar, cfg->depth_tol, cfg->cos_min};
-  FP_REQUIRE(k.fx > 0.f && k.fy > 0.f && isfinite(k.fx) && isfinite(k.fy) && isfinite(k.cx) && isfinite(k.cy),
-             "fp_texture_bake: K is not a finite camera matrix with positive focal lengths");
+  FP_TRY(fp_check_camera("fp_texture_bake", K));
   TexViews views;
   memset(&views, 0, sizeof(views));
+  FP_TRY(fp_check_view_matrices("fp_texture_bake", cam_in_ob, n_views));
   for (int v = 0; v < n_views; ++v) {
     const double *m = cam_in_ob + (size_t)v * 16;
-    for (int e = 0; e < 12; ++e) FP_REQUIRE(isfinite(m[e]), "fp_texture_bake: cam_in_ob[%d] is not finite", v);
-    FP_REQUIRE(m[12] == 0 && m[13] == 0 && m[14] == 0 && m[15] == 1, "fp_texture_bake: the last row of cam_in_ob[%d] is not 0 0 0 1", v);
     for (int i = 0; i < 3; ++i) {
       for (int a = 0; a < 3; ++a) views.v[v].r[i * 3 + a] = (float)m[a * 4 + i];
       views.v[v].t[i] = (float)-((m[0 * 4 + i] * m[3] + m[1 * 4 + i] * m[7]) + m[2 * 4 + i] * m[11]);

@@ -10,17 +10,16 @@
 //
 // Extraction: flag + count per point (7-bit edge mask, faces of the point's cube) -> exclusive scan of (vertices | faces << 32) as one
 // 64-bit word -> vertex write -> face write.  A vertex id is the scanned base of the owning point plus the rank of the edge slot in the
-// mask, so neighbouring cubes find the same id without a hash or an atomic.  The scan is reduce / scan of the block sums / add, recursive
-// on the host: a workgroup never waits for another one.
+// mask, so neighbouring cubes find the same id without a hash or an atomic.  The scan is scan_exclusive of scan.hip.
 #include "common.h"
+#include "device_util.h"
+#include "gn_sums.h"
 
 #include <math.h>
 
 namespace {
 
 constexpr int TS_THREADS = 256;
-constexpr int SCAN_ITEMS = 4;
-constexpr int SCAN_TILE = TS_THREADS * SCAN_ITEMS;     // 1024 words per workgroup
 constexpr int TAB_BYTES = 6 * 16 * 8;                  // per tetrahedron and sign case: the triangle count, then 6 vertex codes
 typedef unsigned long long u64;
 
@@ -156,51 +155,6 @@ __global__ __launch_bounds__(TS_THREADS) void tsdf_count_kernel(TsdfGrid g, cons
   }
   emask[idx] = (uint8_t)em;
   cnt[idx] = (u64)__popc(em) | ((u64)nf << 32);
-}
-
-// ---- exclusive scan of 64-bit words: reduce, scan of the block sums, add ----------------------------------------------------------
-// sum of a workgroup's tile -> sums[block]
-__global__ __launch_bounds__(TS_THREADS) void scan_reduce_kernel(const u64 *__restrict__ in, long long n, u64 *__restrict__ sums) {
-  __shared__ u64 red[TS_THREADS];
-  const long long base = (long long)blockIdx.x * SCAN_TILE + (long long)threadIdx.x * SCAN_ITEMS;
-  u64 s = 0;
-#pragma unroll
-  for (int q = 0; q < SCAN_ITEMS; ++q)
-    if (base + q < n) s += in[base + q];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = TS_THREADS / 2; o >= 1; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) sums[blockIdx.x] = red[0];
-}
-
-// in-place exclusive scan of every workgroup's tile, started at offsets[block] (0 when null: the single-tile level)
-__global__ __launch_bounds__(TS_THREADS) void scan_tile_kernel(u64 *__restrict__ data, long long n, const u64 *__restrict__ offsets) {
-  __shared__ u64 part[TS_THREADS];
-  const long long base = (long long)blockIdx.x * SCAN_TILE + (long long)threadIdx.x * SCAN_ITEMS;
-  u64 x[SCAN_ITEMS];
-  u64 s = 0;
-#pragma unroll
-  for (int q = 0; q < SCAN_ITEMS; ++q) {
-    x[q] = base + q < n ? data[base + q] : 0;
-    s += x[q];
-  }
-  part[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 1; o < TS_THREADS; o <<= 1) {         // Hillis-Steele over the 256 thread sums: inclusive
-    const u64 add = (int)threadIdx.x >= o ? part[threadIdx.x - o] : 0;
-    __syncthreads();
-    part[threadIdx.x] += add;
-    __syncthreads();
-  }
-  u64 run = (offsets ? offsets[blockIdx.x] : 0) + part[threadIdx.x] - s;
-#pragma unroll
-  for (int q = 0; q < SCAN_ITEMS; ++q) {
-    if (base + q < n) data[base + q] = run;
-    run += x[q];
-  }
 }
 
 // ---- pass 3: vertices ----------------------------------------------------------------------------------------------------------
@@ -361,31 +315,6 @@ void build_table(uint8_t *tab) {
 
 }  // namespace
 
-// declared in common.h: mesh_simplify.hip numbers its clusters and faces with the same scan
-size_t scan_sums_words(long long n) {
-  size_t w = 0;
-  while (n > SCAN_TILE) {
-    n = (n + SCAN_TILE - 1) / SCAN_TILE;
-    w += (size_t)n;
-  }
-  return w + 1;
-}
-
-int scan_exclusive(unsigned long long *data, long long n, unsigned long long *sums, hipStream_t s) {
-  const long long nb = (n + SCAN_TILE - 1) / SCAN_TILE;
-  if (nb <= 1) {
-    hipLaunchKernelGGL(scan_tile_kernel, dim3(1), dim3(TS_THREADS), 0, s, data, n, (const u64 *)nullptr);
-    FP_CHECK_HIP(hipGetLastError());
-    return FP_OK;
-  }
-  hipLaunchKernelGGL(scan_reduce_kernel, dim3((unsigned)nb), dim3(TS_THREADS), 0, s, (const u64 *)data, n, sums);
-  FP_CHECK_HIP(hipGetLastError());
-  FP_TRY(scan_exclusive(sums, nb, sums + nb, s));
-  hipLaunchKernelGGL(scan_tile_kernel, dim3((unsigned)nb), dim3(TS_THREADS), 0, s, data, n, (const u64 *)sums);
-  FP_CHECK_HIP(hipGetLastError());
-  return FP_OK;
-}
-
 struct fp_tsdf {
   int device = 0;
   TsdfGrid g{};
@@ -466,15 +395,13 @@ extern "C" int fp_tsdf_integrate(fp_ctx *ctx, fp_tsdf *vol, const float *d_depth
   FP_REQUIRE(H >= 1 && W >= 1, "fp_tsdf_integrate: H %d, W %d", H, W);
   FP_REQUIRE(zfar > 0.f, "fp_tsdf_integrate: zfar %g (> 0)", (double)zfar);
   TsdfCam cam{(float)K[0], (float)K[4], (float)K[2], (float)K[5], zfar, H, W, n_views};
-  FP_REQUIRE(cam.fx > 0.f && cam.fy > 0.f && isfinite(cam.fx) && isfinite(cam.fy) && isfinite(cam.cx) && isfinite(cam.cy),
-             "fp_tsdf_integrate: K is not a finite camera matrix with positive focal lengths");
+  FP_TRY(fp_check_camera("fp_tsdf_integrate", K));
   if (n_views == 0) return FP_OK;
   TsdfViews views;
   memset(&views, 0, sizeof(views));
+  FP_TRY(fp_check_view_matrices("fp_tsdf_integrate", cam_in_ob, n_views));
   for (int v = 0; v < n_views; ++v) {
     const double *m = cam_in_ob + (size_t)v * 16;
-    for (int e = 0; e < 12; ++e) FP_REQUIRE(isfinite(m[e]), "fp_tsdf_integrate: cam_in_ob[%d] is not finite", v);
-    FP_REQUIRE(m[12] == 0 && m[13] == 0 && m[14] == 0 && m[15] == 1, "fp_tsdf_integrate: the last row of cam_in_ob[%d] is not 0 0 0 1", v);
     for (int i = 0; i < 3; ++i) {
       for (int a = 0; a < 3; ++a) views.v[v].r[i * 3 + a] = (float)m[a * 4 + i];
       views.v[v].t[i] = (float)-((m[0 * 4 + i] * m[3] + m[1 * 4 + i] * m[7]) + m[2 * 4 + i] * m[11]);
@@ -548,9 +475,9 @@ extern "C" int fp_tsdf_read_plane(fp_ctx *ctx, const fp_tsdf *vol, int plane, fl
 // A workgroup owns (view, a tile of AL_TILE pixels); the view is uniform in the workgroup, so its matrix arrives as scalar loads.  A lane
 // takes AL_PIX pixels, TS_THREADS apart (the depth reads coalesce), in three passes over them: depth and mask, then the cell and the 16
 // gathers of each pixel (tsdf and weight of the 8 corners) - nothing in this pass depends on a gathered value, so all AL_PIX x 16 loads
-// are in flight together - then the arithmetic.  The 29 sums are kept in double per lane, added over the wave by a butterfly (every lane
-// ends with the same value, the order is fixed), over the waves in wave order through LDS, and written to the workgroup's own slot of the
-// slab; tsdf_align_fold_kernel adds the slots of a view in tile order.  No atomics: a view's sums depend on nothing but its own pixels.
+// are in flight together - then the arithmetic.  The row, the 29 sums in double and their way through the wave, LDS and the slab to
+// gn_fold_kernel are those of gn_sums.h, where the summation order is stated.  No atomics: a view's sums depend on nothing but its own
+// pixels.
 namespace {
 
 constexpr int AL_PIX = 4;
@@ -568,7 +495,7 @@ __global__ __launch_bounds__(TS_THREADS) void tsdf_align_kernel(TsdfGrid g, cons
                                                                 const float *__restrict__ depth, const uint8_t *__restrict__ mask, TsdfCam cam,
                                                                 float min_w, int n_tiles, AlignViews views, float *__restrict__ rows,
                                                                 double *__restrict__ slab) {
-  __shared__ double red[TS_THREADS / 64][FP_TSDF_ALIGN_TERMS];
+  __shared__ double red[TS_THREADS / 64][GN_TERMS];
   const int tid = threadIdx.x;
   const int tile = blockIdx.x % n_tiles, v = blockIdx.x / n_tiles;
   const AlignView &m = views.v[v];
@@ -612,9 +539,9 @@ __global__ __launch_bounds__(TS_THREADS) void tsdf_align_kernel(TsdfGrid g, cons
   }
 
   // pass 3: interpolant, gradient, the row, the sums
-  double acc[FP_TSDF_ALIGN_TERMS];
+  double acc[GN_TERMS];
 #pragma unroll
-  for (int e = 0; e < FP_TSDF_ALIGN_TERMS; ++e) acc[e] = 0.0;
+  for (int e = 0; e < GN_TERMS; ++e) acc[e] = 0.0;
   const float gscale = g.trunc / g.vs;
 #pragma unroll
   for (int q = 0; q < AL_PIX; ++q) {
@@ -635,55 +562,13 @@ __global__ __launch_bounds__(TS_THREADS) void tsdf_align_kernel(TsdfGrid g, cons
     const float X = x[q][0], Y = x[q][1], Z = x[q][2];
     float J[6] = {Gx, Gy, Gz, Y * Gz - Z * Gy, Z * Gx - X * Gz, X * Gy - Y * Gx};
     float r = Ti * g.trunc;
-    if (!valid) {
-#pragma unroll
-      for (int i = 0; i < 6; ++i) J[i] = 0.f;
-      r = 0.f;
-    }
-    if (rows && pix[q] < hw) {
-      float4 *o = (float4 *)(rows + (view0 + (size_t)pix[q]) * 8);
-      o[0] = make_float4(J[0], J[1], J[2], J[3]);
-      o[1] = make_float4(J[4], J[5], r, valid ? 1.f : 0.f);
-    }
-    double Jd[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) Jd[i] = (double)J[i];
-    const double rd = (double)r;
-    int e = 0;
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-#pragma unroll
-      for (int j = i; j < 6; ++j) acc[e++] += Jd[i] * Jd[j];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) acc[21 + i] += Jd[i] * rd;
-    acc[27] += rd * rd;
-    acc[28] += valid ? 1.0 : 0.0;
+    gn_mask(J, r, valid);
+    if (rows && pix[q] < hw) gn_store_row((float4 *)(rows + (view0 + (size_t)pix[q]) * 8), J, r, valid);
+    gn_accumulate(acc, J, r, valid);
   }
-
-#pragma unroll
-  for (int e = 0; e < FP_TSDF_ALIGN_TERMS; ++e) {
-    double s = acc[e];
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
-    if ((tid & 63) == 0) red[tid >> 6][e] = s;
-  }
+  gn_wave_to_lds(acc, red[tid >> 6], 0);
   __syncthreads();
-  if (tid < FP_TSDF_ALIGN_TERMS) {
-    double s = red[0][tid];
-    for (int wv = 1; wv < TS_THREADS / 64; ++wv) s += red[wv][tid];
-    slab[((size_t)v * n_tiles + tile) * FP_TSDF_ALIGN_TERMS + tid] = s;
-  }
-}
-
-// one thread per (view, term): the tiles' slots in tile order
-__global__ __launch_bounds__(64) void tsdf_align_fold_kernel(const double *__restrict__ slab, int n_views, int n_tiles, double *__restrict__ sums) {
-  const int t = blockIdx.x * 64 + threadIdx.x;
-  if (t >= n_views * FP_TSDF_ALIGN_TERMS) return;
-  const int v = t / FP_TSDF_ALIGN_TERMS, e = t % FP_TSDF_ALIGN_TERMS;
-  const double *sb = slab + (size_t)v * n_tiles * FP_TSDF_ALIGN_TERMS + e;
-  double s = 0.0;
-  for (int k = 0; k < n_tiles; ++k) s += sb[(size_t)k * FP_TSDF_ALIGN_TERMS];
-  sums[t] = s;
+  gn_lds_to_slab(red, slab + ((size_t)v * n_tiles + tile) * GN_TERMS);
 }
 
 }  // namespace
@@ -699,14 +584,12 @@ extern "C" int fp_tsdf_align(fp_ctx *ctx, const fp_tsdf *vol, const float *d_dep
   FP_REQUIRE(zfar > 0.f, "fp_tsdf_align: zfar %g (> 0)", (double)zfar);
   FP_REQUIRE(min_weight > 0.f, "fp_tsdf_align: min_weight %g (> 0)", (double)min_weight);
   TsdfCam cam{(float)K[0], (float)K[4], (float)K[2], (float)K[5], zfar, H, W, n_views};
-  FP_REQUIRE(cam.fx > 0.f && cam.fy > 0.f && isfinite(cam.fx) && isfinite(cam.fy) && isfinite(cam.cx) && isfinite(cam.cy),
-             "fp_tsdf_align: K is not a finite camera matrix with positive focal lengths");
+  FP_TRY(fp_check_camera("fp_tsdf_align", K));
   AlignViews views;
   memset(&views, 0, sizeof(views));
+  FP_TRY(fp_check_view_matrices("fp_tsdf_align", cam_in_ob, n_views));
   for (int v = 0; v < n_views; ++v) {
     const double *m = cam_in_ob + (size_t)v * 16;
-    for (int e = 0; e < 12; ++e) FP_REQUIRE(isfinite(m[e]), "fp_tsdf_align: cam_in_ob[%d] is not finite", v);
-    FP_REQUIRE(m[12] == 0 && m[13] == 0 && m[14] == 0 && m[15] == 1, "fp_tsdf_align: the last row of cam_in_ob[%d] is not 0 0 0 1", v);
     for (int a = 0; a < 3; ++a) {
       for (int i = 0; i < 3; ++i) views.v[v].r[a * 3 + i] = (float)m[a * 4 + i];
       views.v[v].t[a] = (float)m[a * 4 + 3];
@@ -728,8 +611,8 @@ extern "C" int fp_tsdf_align(fp_ctx *ctx, const fp_tsdf *vol, const float *d_dep
   hipLaunchKernelGGL(tsdf_align_kernel, dim3((unsigned)(n_tiles * n_views)), dim3(TS_THREADS), 0, s, g, (const float *)vol->plane[0],
                      (const float *)vol->plane[1], d_depth, d_mask, cam, min_weight, (int)n_tiles, views, d_rows, slab);
   FP_CHECK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(tsdf_align_fold_kernel, dim3((unsigned)((n_views * FP_TSDF_ALIGN_TERMS + 63) / 64)), dim3(64), 0, s, (const double *)slab,
-                     n_views, (int)n_tiles, sums);
+  hipLaunchKernelGGL(gn_fold_kernel<FP_TSDF_ALIGN_TERMS>, dim3((unsigned)((n_views * FP_TSDF_ALIGN_TERMS + 63) / 64)), dim3(64), 0, s,
+                     (const double *)slab, n_views, (int)n_tiles, sums);
   FP_CHECK_HIP(hipGetLastError());
   // the slab and the sums go back to the arena when this returns: the stream has been synchronised by then
   FP_CHECK_HIP(hipMemcpyAsync(h_sums, sums, sums_bytes, hipMemcpyDeviceToHost, s));

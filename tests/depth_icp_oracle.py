@@ -335,6 +335,20 @@ def row_case(H=48, W=64, focal=130.0):
   return K, truth, depths, masks, query, pairs
 
 
+def tiny_case(H=5, W=7, focal=130.0):
+  """6 views of W x H (35 pixels: less than one wave of a tile) of the middle of the scene, all within a seeded 1 mm / 0.3 degrees of
+  view 0 of the row case, so that the few pixels of a view land inside its partner; no mask cuts, the queries another 0.3 mm / 0.1
+  degrees off, the pairs of the row case.  Returns what row_case returns."""
+  K = np.array([[focal, 0, W / 2 - 0.5], [0, focal, H / 2 - 0.5], [0, 0, 1.0]])
+  rs = np.random.RandomState(5)
+  first = O.look_at(0.4 * np.array([np.cos(np.deg2rad(10.0)), 0.0, np.sin(np.deg2rad(10.0))]))
+  truth = np.stack([first] + [A.perturb(first, 0.001, 0.3, rs) for _ in range(5)])
+  depths = np.stack([A.scene_depth(p, K, H, W) for p in truth])
+  masks = (depths > 0).astype(np.uint8)
+  query = np.stack([A.perturb(p, 0.0003, 0.1, rs) for p in truth])
+  return K, truth, depths, masks, query, row_case(H, W, focal)[5]
+
+
 ROW_GATE = (0.008, 0.98)     # dist_max, cos_min of the row case: tight, so that both gates skip pixels (248 and 223 over the 16 pairs)
 
 

@@ -224,6 +224,12 @@ def row_case(*size):
   return K, truth, depths, masks, query, pairs, textured_rgbs(depths, K, truth)
 
 
+def tiny_case():
+  """depth_icp_oracle.tiny_case() with the texture"""
+  K, truth, depths, masks, query, pairs = D.tiny_case()
+  return K, truth, depths, masks, query, pairs, textured_rgbs(depths, K, truth)
+
+
 ROW_I_MAX = 0.05                # of the row case: tight, so that it skips pixels
 ROW_INTENSITY_MAX_JUMP = 0.002  # the row case takes its intensity maps from normals of a tighter max_jump than the alignment's (0.01), so
                                 # that pixels with a normal but without an intensity record exist at both ends of a pair

@@ -124,6 +124,24 @@ def test_sums_are_within_the_bound_of_any_summation_order(oracle_step, device_st
   print(f'largest |sum - fsum| / bound: {worst:.3e}')
 
 
+@pytest.mark.parametrize('make', [lambda: D.row_case(96, 100, 200.0), D.tiny_case, D.row_case], ids=['96x100', '5x7', 'masked 48x64'])
+def test_sums_have_the_bits_of_the_stated_order(make):
+  """The device's sums against tests/gn_sums_oracle.py (the order stated in csrc/gn_sums.h) applied to the device's own rows, bit for
+  bit.  96 x 100: 10 tiles - the fold's body of eight and a remainder of two - and a last tile of 384 pixels; 5 x 7: one tile of which
+  three waves hold padding only (depth_icp_oracle.tiny_case); the masked row case of 48 x 64: whole waves without a source normal,
+  which take the kernel's short cut."""
+  from foundationpose_amd import reconstruct as R
+  from tests import gn_sums_oracle as G
+  c = dict(zip(('K', 'truth', 'depths', 'masks', 'query', 'pairs'), make()))
+  nrm = R.depth_normals(c['depths'], c['K'], c['masks'])
+  sums, rows = R.align_pairs_step(torch.as_tensor(c['depths'], device=nrm.device), nrm, c['K'], c['query'], c['pairs'], *D.ROW_GATE, rows=True)
+  rows = rows.cpu().numpy()
+  want = np.stack([G.device_sums(rows[p]) for p in range(len(c['pairs']))])
+  print(f'{rows.shape[1:3]}: valid per pair {sums[:, 28]}; differing words {(sums.view(np.uint64) != want.view(np.uint64)).sum()} of {want.size}')
+  assert sums[:, 28].sum() > 0
+  assert np.array_equal(sums.view(np.uint64), want.view(np.uint64))
+
+
 def test_a_pair_does_not_depend_on_its_batch(case, device_step):
   from foundationpose_amd import _lib
   from foundationpose_amd import reconstruct as R

@@ -142,6 +142,27 @@ def test_photometric_sums_are_within_the_bound_of_any_summation_order(oracle_ste
   assert (device_step[3][:10, 57] >= 60).all()
 
 
+@pytest.mark.parametrize('make', [lambda: P.row_case(96, 100, 200.0), P.tiny_case, P.row_case], ids=['96x100', '5x7', 'masked 48x64'])
+def test_sums_have_the_bits_of_the_stated_order(make):
+  """All 58 of the device's sums against tests/gn_sums_oracle.py (the order stated in csrc/gn_sums.h) applied to the device's own
+  rows, floats 0 .. 7 for terms 0 .. 28 and floats 8 .. 15 for terms 29 .. 57, bit for bit.  The shapes of the same test of
+  tests/test_gpu_depth_icp.py: 10 tiles with a ragged last one, one partial tile, and the masked row case with its empty waves."""
+  from foundationpose_amd import reconstruct as R
+  from tests import gn_sums_oracle as G
+  c = dict(zip(('K', 'truth', 'depths', 'masks', 'query', 'pairs', 'rgbs'), make()))
+  nrm = R.depth_normals(c['depths'], c['K'], c['masks'])
+  inten = R.view_intensity(c['rgbs'], R.depth_normals(c['depths'], c['K'], c['masks'], max_jump=P.ROW_INTENSITY_MAX_JUMP))
+  sums, rows = R.align_pairs_step(torch.as_tensor(c['depths'], device=nrm.device), nrm, c['K'], c['query'], c['pairs'], *D.ROW_GATE, rows=True,
+                                  intensity=inten, i_max=P.ROW_I_MAX)
+  rows = rows.cpu().numpy()
+  want = np.stack([np.concatenate([G.device_sums(np.ascontiguousarray(rows[p, ..., :8])), G.device_sums(np.ascontiguousarray(rows[p, ..., 8:]))])
+                   for p in range(len(c['pairs']))])
+  print(f'{rows.shape[1:3]}: valid per pair {sums[:, 28]}, photometric {sums[:, 57]}; differing words '
+        f'{(sums.view(np.uint64) != want.view(np.uint64)).sum()} of {want.size}')
+  assert sums[:, 28].sum() > 0 and sums[:, 57].sum() > 0
+  assert sums.shape == (len(c['pairs']), 58) and np.array_equal(sums.view(np.uint64), want.view(np.uint64))
+
+
 def test_a_pair_does_not_depend_on_its_batch(case, device_step):
   from foundationpose_amd import _lib
   from foundationpose_amd import reconstruct as R

@@ -115,6 +115,21 @@ def test_sums_are_within_the_bound_of_any_summation_order(oracle_rows, device_st
   print(f'largest |sum - fsum| / bound: {worst:.3e}')
 
 
+@pytest.mark.parametrize('H,W,focal', [(96, 100, 200.0), (5, 7, 130.0), (48, 64, 130.0)])
+def test_sums_have_the_bits_of_the_stated_order(H, W, focal, device_volumes):
+  """The device's sums against tests/gn_sums_oracle.py (the order stated in csrc/gn_sums.h) applied to the device's own rows, bit for
+  bit.  96 x 100: 10 tiles - the fold's body of eight and a remainder of two - and a last tile of 384 pixels; 5 x 7: one tile of which
+  three waves hold padding only; 48 x 64: the masked case of this file, 3 whole tiles."""
+  from tests import gn_sums_oracle as G
+  c = _case(H, W, focal)
+  sums, rows = device_volumes[0].align_step(c['depths'], c['K'], c['query'], masks=c['masks'], rows=True)
+  rows = rows.cpu().numpy()
+  want = np.stack([G.device_sums(rows[v]) for v in range(5)])
+  print(f'{H} x {W}: valid per view {sums[:, 28]}; differing words {(sums.view(np.uint64) != want.view(np.uint64)).sum()} of {want.size}')
+  assert sums[:, 28].sum() > 0
+  assert np.array_equal(sums.view(np.uint64), want.view(np.uint64))
+
+
 def test_a_view_does_not_depend_on_its_batch(case, device_volumes, device_step):
   vol = device_volumes[0]
   d, m, q, K = case['depths'], case['masks'], case['query'], case['K']
