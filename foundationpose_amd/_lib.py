@@ -281,6 +281,11 @@ def k_ptr(K):
   return Kd, c_void_p(Kd.ctypes.data)
 
 
+def center3(model_center):
+  """A model centre rounded to float32, as the `model_center` field of the per-object structures takes it."""
+  return (c_float * 3)(*np.asarray(model_center, dtype=np.float32).reshape(3))
+
+
 class Context:
   """Per-device fp_ctx (workspace arena + profiling).  The opaque handle the reference calls
   `glctx` (dr.RasterizeCudaContext, src/estimater.py:102,168; main.py:42)."""

@@ -57,6 +57,7 @@ class FoundationPose:
     self.scorer = ScorePredictor() if scorer is None else scorer
     self.refiner = PoseRefinePredictor() if refiner is None else refiner
     self.pose_last = None          # pose of the centred mesh, kept for track_one
+    self._graph_on = False         # enable_track_graph
 
   # ------------------------------------------------------------------ object set-up (cold path)
   def reset_object(self, model_pts, model_normals, symmetry_tfs=None, mesh=None, diameter=None):
@@ -236,46 +237,38 @@ class FoundationPose:
   def enable_track_graph(self, on=True):
     """Replay a tracking frame as ONE hipGraph: at 1 .. 64 hypotheses a frame is ~80 kernels of one workgroup round or less
     each, so launch overhead and the gaps between launches are a large part of it.  The graph is captured at the first frame of a
-    given (mode, frame size, camera, iteration count) and re-captured if the library's workspace is re-allocated."""
+    given (mode, frame size, camera, iteration count) and re-captured if the library's workspace is re-allocated (frame.GraphedCall)."""
     self._graph_on = bool(on)
-    for ws in getattr(self, '_track_ws', {}).values():
-      ws['graph'] = None
+    for ws in self._track_ws.values():
+      ws['run'].drop()
 
   def _track_workspace(self, n_hyp, sigmas, iteration, shape, is_u8, K):
     """Static device buffers of one tracking mode (every launch of a frame reads and writes fixed addresses, so the frame can be
-    replayed as a hipGraph): the frame itself - depth (float32) and colours behind one another in ONE buffer, so that a frame is one
-    host-to-device copy -, the library's workspace, the pose (refined in place from frame to frame) and the outputs."""
+    replayed as a hipGraph): the frame itself (`fb`, a frame.FrameBuffer: depth and colours behind one another in ONE buffer, so that a
+    frame is one host-to-device copy), the library's workspace, the pose (refined in place from frame to frame), the outputs, the filled
+    argument structure and the call (`run`, a frame.GraphedCall)."""
     from . import _lib
+    from .frame import FrameBuffer, GraphedCall
     from .tracking import perturbation_set
     key = (n_hyp, sigmas, int(iteration), tuple(shape), bool(is_u8), np.asarray(K, dtype=np.float64).tobytes(), id(self.mesh_tensors['pos']),
            np.asarray(self.model_center, dtype=np.float64).tobytes())
-    ws = self._track_ws.get(key) if hasattr(self, '_track_ws') else None
+    ws = self._track_ws.get(key)
     if ws is not None:
       return ws
-    if not hasattr(self, '_track_ws'):
-      self._track_ws = {}
-    H, W = shape
     dev = self.mesh_tensors['pos'].device
-    n_rgb = H * W * 3 * (1 if is_u8 else 4)
-    frame = torch.empty((H * W * 4 + n_rgb,), dtype=torch.uint8, device=dev)
-    ws = dict(frame=frame, depth=frame[:H * W * 4].view(torch.float).reshape(H, W),
-              rgb=(frame[H * W * 4:].reshape(H, W, 3) if is_u8 else frame[H * W * 4:].view(torch.float).reshape(H, W, 3)),
-              host=torch.empty((H * W * 4 + n_rgb,), dtype=torch.uint8).pin_memory(),
-              depth_f=torch.empty((H, W), dtype=torch.float, device=dev), xyz=torch.empty((H, W, 3), dtype=torch.float, device=dev),
-              rgb_f=torch.empty((H, W, 3), dtype=torch.float, device=dev) if is_u8 else None,
-              pose=torch.eye(4, dtype=torch.float, device=dev), pose_of_mesh=torch.eye(4, dtype=torch.float).pin_memory(),
-              Kd=np.ascontiguousarray(np.asarray(K, dtype=np.float64).reshape(3, 3)), cfg=self.refiner._c_cfg(), holds_pose=None, graph=None)
+    ctx = self.refiner.ctx
+    Kd, K_ptr = _lib.k_ptr(K)
+    ws = dict(fb=FrameBuffer(*shape, is_u8, dev), pose=torch.eye(4, dtype=torch.float, device=dev), pose_of_mesh=torch.eye(4, dtype=torch.float).pin_memory(),
+              Kd=Kd, cfg=self.refiner._c_cfg(), holds_pose=None)
     a = _lib.FpTrackArgs()
     a.struct_size = ctypes.sizeof(a)
-    a.refine_net, a.mesh = self.refiner.model.handle, _lib.device_mesh(self.refiner.ctx, self.mesh_tensors).handle
-    a.d_rgb, a.rgb_is_u8, a.d_depth, a.H, a.W = ws['rgb'].data_ptr(), 1 if is_u8 else 0, ws['depth'].data_ptr(), H, W
-    a.K, a.mesh_diameter = ws['Kd'].ctypes.data, float(self.diameter)
+    a.refine_net, a.mesh = self.refiner.model.handle, _lib.device_mesh(ctx, self.mesh_tensors).handle
+    ws['fb'].fill(a)
+    a.K, a.mesh_diameter = K_ptr, float(self.diameter)
     a.refine_cfg = ctypes.addressof(ws['cfg'])
     a.iteration, a.n_hyp = int(iteration), int(n_hyp)
-    a.model_center[:] = [float(x) for x in np.asarray(self.model_center, dtype=np.float32)]
+    a.model_center = _lib.center3(self.model_center)
     a.d_pose, a.d_pose_of_mesh = ws['pose'].data_ptr(), ws['pose_of_mesh'].data_ptr()
-    a.d_depth_f, a.d_xyz = ws['depth_f'].data_ptr(), ws['xyz'].data_ptr()
-    a.d_rgb_f = ws['rgb_f'].data_ptr() if is_u8 else None
     if n_hyp > 1:
       ws['perturb'] = torch.as_tensor(perturbation_set(int(n_hyp), *sigmas), device=dev).contiguous()
       ws['poses'] = torch.empty((n_hyp, 4, 4), dtype=torch.float, device=dev)
@@ -285,74 +278,29 @@ class FoundationPose:
       a.score_crop_ratio, a.score_normalize_xyz = float(self.scorer.cfg['crop_ratio']), 1 if self.scorer.cfg['normalize_xyz'] else 0
       a.d_perturb, a.d_poses, a.d_scores, a.d_best = ws['perturb'].data_ptr(), ws['poses'].data_ptr(), ws['scores'].data_ptr(), ws['best'].data_ptr()
     ws['args'] = a
+    track_frame, check, stream_ptr = _lib.lib().fp_track_frame, _lib.check, _lib.stream_ptr
+    ws['run'] = GraphedCall(ctx, lambda: check(track_frame(ctx.handle, ctypes.byref(a), stream_ptr(dev))), ws['pose'], max(64, n_hyp))
     self._track_ws[key] = ws
     return ws
 
   def _run_frame(self, rgb, depth, K, iteration, n_hyp, sigmas):
-    """One tracking frame: upload (ONE copy), fp_track_frame (eager, or the replay of its captured hipGraph), the 4x4 result read from pinned host memory.
+    """One tracking frame: upload (ONE copy, the rule of frame.FrameBuffer), fp_track_frame (eager, or the replay of its captured hipGraph), the 4x4
+    result read from pinned host memory.
     Returns (pose_of_mesh as a HOST (4,4) float32 array - what track_one returns -, workspace).  Contract: `self.pose_last` and, in the
     multi-hypothesis mode, `self.poses` / `self.scores` / `self.best_id` are VIEWS of the mode's static buffers, overwritten by the
     next frame of the same mode; clone them to keep them."""
-    from . import _lib
-    from ._lib import check, lib, stream_ptr
-    ctx = self.refiner.ctx
-    is_np = isinstance(rgb, np.ndarray)
-    is_u8 = (rgb.dtype == np.uint8) if is_np else (rgb.dtype == torch.uint8)
-    H, W = depth.shape[:2]
-    ws = self._track_workspace(n_hyp, sigmas, iteration, (H, W), is_u8, K)
-    # the frame: host arrays go through one pinned staging buffer and ONE host-to-device copy; device tensors that already lie behind
-    # one another as [depth | rgb] (bench.py packs its resident frames that way) are one device copy, others two
-    if is_np or not torch.is_tensor(depth) or not depth.is_cuda:
-      hb = ws['host'].numpy()
-      hb[:H * W * 4].view(np.float32)[:] = np.asarray(depth.cpu() if torch.is_tensor(depth) else depth, dtype=np.float32).reshape(-1)
-      r = np.asarray(rgb.cpu() if torch.is_tensor(rgb) else rgb)
-      if is_u8:
-        hb[H * W * 4:] = r.reshape(-1)
-      else:
-        hb[H * W * 4:].view(np.float32)[:] = r.astype(np.float32, copy=False).reshape(-1)
-      ws['frame'].copy_(ws['host'], non_blocking=True)
-    else:
-      d = depth.to(torch.float)
-      r = rgb if is_u8 else rgb.to(torch.float)
-      packed = (d.is_contiguous() and r.is_contiguous() and d.untyped_storage().data_ptr() == r.untyped_storage().data_ptr() and
-                r.data_ptr() == d.data_ptr() + H * W * 4)
-      if packed:
-        ws['frame'].copy_(torch.as_strided(d.view(torch.uint8).reshape(-1), (ws['frame'].numel(),), (1,)))
-      else:
-        ws['depth'].copy_(d)
-        ws['rgb'].copy_(r)
+    is_u8 = rgb.dtype == (np.uint8 if isinstance(rgb, np.ndarray) else torch.uint8)
+    ws = self._track_workspace(n_hyp, sigmas, iteration, depth.shape[:2], is_u8, K)
+    ws['fb'].put(rgb, depth)
     # the pose lives in the workspace and is refined in place; it is (re)loaded only when pose_last was set by someone else (register)
     if ws['holds_pose'] is not self.pose_last:
       ws['pose'].copy_(torch.as_tensor(self.pose_last, device=ws['pose'].device, dtype=torch.float).reshape(4, 4))
     st = torch.cuda.current_stream(ws['pose'].device)
-    if getattr(self, '_graph_on', False):
-      g = ws['graph']
-      if g is not None and g[1] != ctx.arena_generation():
-        g = None                                            # the library's arena moved: the captured addresses are stale
-      if g is None:
-        ctx.reserve(max(64, n_hyp))
-        keep = ws['pose'].clone()
-        side = torch.cuda.Stream()
-        side.wait_stream(st)
-        with torch.cuda.stream(side):                        # eager passes first: lazy initialisation, allocator warm-up
-          for _ in range(2):
-            check(lib().fp_track_frame(ctx.handle, ctypes.byref(ws['args']), stream_ptr(ws['pose'].device)))
-            ws['pose'].copy_(keep)
-        st.wait_stream(side)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-          check(lib().fp_track_frame(ctx.handle, ctypes.byref(ws['args']), stream_ptr(ws['pose'].device)))
-        ws['pose'].copy_(keep)                               # (capturing does not execute)
-        g = ws['graph'] = (graph, ctx.arena_generation())
-      g[0].replay()
-    else:
-      ctx.reserve(max(64, n_hyp))
-      check(lib().fp_track_frame(ctx.handle, ctypes.byref(ws['args']), stream_ptr(ws['pose'].device)))
+    ws['run'](st, self._graph_on)
     # the result lands in pinned host memory, written there by the frame's last launch (the device addresses it directly): no
     # device-to-host copy is enqueued, the frame ends with one wait for the stream
     st.synchronize()
-    out = ws['pose_of_mesh'].numpy().copy()
-    return out, ws
+    return ws['pose_of_mesh'].numpy().copy(), ws
 
   def track_one(self, rgb, depth, K, iteration, extra={}):
     """src/estimater.py:250-268: refine the previous pose against a new frame (no scoring)."""

@@ -93,116 +93,72 @@ class MultiObjectTracker:
         raise ValueError(f'MultiObjectTracker: estimator {i} does not share estimator 0\'s refiner (refiner.model.handle and refiner.ctx): '
                          'one network pass needs one RefineNet')
     self.estimators = ests
-    self._ws = {}
+    self._ws, self._reg_ws = {}, {}          # workspaces of track() and of register(), by what they were built for
     self._graph_on = False
+    self._last_frame = None                  # (H, W, K) of the last frame seen
+    self._returned = None                    # per estimator (the pose_last handed out, the pose of the original mesh returned with it)
 
   def enable_graph(self, on=True):
     """Replay a frame as ONE hipGraph, captured at the first frame of a given (objects, frame size, camera, iteration) after two eager
-    warm-up frames, and re-captured when the library's workspace is re-allocated."""
+    warm-up frames, and re-captured when the library's workspace is re-allocated (frame.GraphedCall)."""
     self._graph_on = bool(on)
     for ws in self._ws.values():
-      ws['graph'] = None
+      ws['run'].drop()
+
+  def _need_poses(self, who, frame=False):
+    """Every estimator has a pose (and, with `frame`, a frame was seen), or ValueError in the name of the method `who`."""
+    for i, e in enumerate(self.estimators):
+      if e.pose_last is None:
+        raise ValueError(f'MultiObjectTracker.{who}: estimator {i} has no pose yet (pose_last is None): register it first')
+    if frame and self._last_frame is None:
+      raise ValueError(f'MultiObjectTracker.{who}: no frame seen yet: call register or track first')
 
   def _workspace(self, iteration, shape, is_u8, K):
     from . import _lib
+    from .frame import FrameBuffer, GraphedCall
     ests = self.estimators
     key = (int(iteration), tuple(shape), bool(is_u8), np.asarray(K, dtype=np.float64).tobytes(),
            tuple((id(e.mesh_tensors['pos']), float(e.diameter), np.asarray(e.model_center, dtype=np.float64).tobytes()) for e in ests))
     ws = self._ws.get(key)
     if ws is not None:
       return ws
-    n, (H, W) = len(ests), shape
+    n = len(ests)
     ctx = ests[0].refiner.ctx
     dev = ests[0].mesh_tensors['pos'].device
-    n_rgb = H * W * 3 * (1 if is_u8 else 4)
-    frame = torch.empty((H * W * 4 + n_rgb,), dtype=torch.uint8, device=dev)
-    ws = dict(frame=frame, depth=frame[:H * W * 4].view(torch.float).reshape(H, W),
-              rgb=(frame[H * W * 4:].reshape(H, W, 3) if is_u8 else frame[H * W * 4:].view(torch.float).reshape(H, W, 3)),
-              host=torch.empty((H * W * 4 + n_rgb,), dtype=torch.uint8).pin_memory(),
-              depth_f=torch.empty((H, W), dtype=torch.float, device=dev), xyz=torch.empty((H, W, 3), dtype=torch.float, device=dev),
-              rgb_f=torch.empty((H, W, 3), dtype=torch.float, device=dev) if is_u8 else None,
-              poses=torch.eye(4, dtype=torch.float, device=dev).repeat(n, 1, 1).contiguous(),
-              pose_of_mesh=torch.zeros((n, 4, 4), dtype=torch.float).pin_memory(),
-              Kd=np.ascontiguousarray(np.asarray(K, dtype=np.float64).reshape(3, 3)), cfg=ests[0].refiner._c_cfg(), holds=[None] * n, graph=None)
+    Kd, K_ptr = _lib.k_ptr(K)
+    ws = dict(fb=FrameBuffer(*shape, is_u8, dev), poses=torch.eye(4, dtype=torch.float, device=dev).repeat(n, 1, 1).contiguous(),
+              pose_of_mesh=torch.zeros((n, 4, 4), dtype=torch.float).pin_memory(), Kd=Kd, cfg=ests[0].refiner._c_cfg(), holds=[None] * n)
     ws['meshes'] = [_lib.device_mesh(ctx, e.mesh_tensors) for e in ests]
     objs = (_lib.FpTrackObject * n)()
     for o, e in enumerate(ests):
-      objs[o].mesh, objs[o].mesh_diameter = ws['meshes'][o].handle, float(e.diameter)
-      objs[o].model_center[:] = [float(x) for x in np.asarray(e.model_center, dtype=np.float32)]
+      objs[o].mesh, objs[o].mesh_diameter, objs[o].model_center = ws['meshes'][o].handle, float(e.diameter), _lib.center3(e.model_center)
       objs[o].d_pose, objs[o].d_pose_of_mesh = ws['poses'][o].data_ptr(), ws['pose_of_mesh'][o].data_ptr()
     a = _lib.FpTrackObjectsArgs()
     a.struct_size = ctypes.sizeof(a)
     a.refine_net = ests[0].refiner.model.handle
-    a.d_rgb, a.rgb_is_u8, a.d_depth, a.H, a.W = ws['rgb'].data_ptr(), 1 if is_u8 else 0, ws['depth'].data_ptr(), H, W
-    a.K, a.refine_cfg = ws['Kd'].ctypes.data, ctypes.addressof(ws['cfg'])
+    ws['fb'].fill(a)
+    a.K, a.refine_cfg = K_ptr, ctypes.addressof(ws['cfg'])
     a.iteration, a.n_obj, a.objs = int(iteration), n, ctypes.addressof(objs)
-    a.d_depth_f, a.d_xyz = ws['depth_f'].data_ptr(), ws['xyz'].data_ptr()
-    a.d_rgb_f = ws['rgb_f'].data_ptr() if is_u8 else None
     ws['objs'], ws['args'] = objs, a
+    track_objects, check, stream_ptr = _lib.lib().fp_track_objects, _lib.check, _lib.stream_ptr
+    ws['run'] = GraphedCall(ctx, lambda: check(track_objects(ctx.handle, ctypes.byref(a), stream_ptr(dev))), ws['poses'], 64)
     self._ws[key] = ws
     return ws
 
   def track(self, rgb, depth, K, iteration=2):
     """One frame: np (n_obj, 4, 4) float32, row o = est_o's pose @ get_tf_to_centered_mesh() (what est_o.track_one returns)."""
-    from ._lib import check, lib, stream_ptr
-    for i, e in enumerate(self.estimators):
-      if e.pose_last is None:
-        raise ValueError(f'MultiObjectTracker: estimator {i} has no pose to track from (pose_last is None): register it first')
-    ctx = self.estimators[0].refiner.ctx
-    is_np = isinstance(rgb, np.ndarray)
-    is_u8 = (rgb.dtype == np.uint8) if is_np else (rgb.dtype == torch.uint8)
+    self._need_poses('track')
+    is_u8 = rgb.dtype == (np.uint8 if isinstance(rgb, np.ndarray) else torch.uint8)
     H, W = depth.shape[:2]
     self._last_frame = (int(H), int(W), K)
     ws = self._workspace(iteration, (H, W), is_u8, K)
-    # the frame as in FoundationPose._run_frame: ONE host-to-device copy through pinned memory, or one device copy of a packed [depth | rgb]
-    if is_np or not torch.is_tensor(depth) or not depth.is_cuda:
-      hb = ws['host'].numpy()
-      hb[:H * W * 4].view(np.float32)[:] = np.asarray(depth.cpu() if torch.is_tensor(depth) else depth, dtype=np.float32).reshape(-1)
-      r = np.asarray(rgb.cpu() if torch.is_tensor(rgb) else rgb)
-      if is_u8:
-        hb[H * W * 4:] = r.reshape(-1)
-      else:
-        hb[H * W * 4:].view(np.float32)[:] = r.astype(np.float32, copy=False).reshape(-1)
-      ws['frame'].copy_(ws['host'], non_blocking=True)
-    else:
-      d = depth.to(torch.float)
-      r = rgb if is_u8 else rgb.to(torch.float)
-      packed = (d.is_contiguous() and r.is_contiguous() and d.untyped_storage().data_ptr() == r.untyped_storage().data_ptr() and
-                r.data_ptr() == d.data_ptr() + H * W * 4)
-      if packed:
-        ws['frame'].copy_(torch.as_strided(d.view(torch.uint8).reshape(-1), (ws['frame'].numel(),), (1,)))
-      else:
-        ws['depth'].copy_(d)
-        ws['rgb'].copy_(r)
+    ws['fb'].put(rgb, depth)                                 # (ONE copy: the rule of frame.FrameBuffer)
     # each pose lives in the workspace and is refined in place; reloaded only when pose_last was set by someone else
     for o, e in enumerate(self.estimators):
       if ws['holds'][o] is not e.pose_last:
         ws['poses'][o].copy_(torch.as_tensor(e.pose_last, device=ws['poses'].device, dtype=torch.float).reshape(4, 4))
     st = torch.cuda.current_stream(ws['poses'].device)
-    run = lambda: check(lib().fp_track_objects(ctx.handle, ctypes.byref(ws['args']), stream_ptr(ws['poses'].device)))
-    if self._graph_on:
-      g = ws['graph']
-      if g is not None and g[1] != ctx.arena_generation():
-        g = None                                            # the library's arena moved: the captured addresses are stale
-      if g is None:
-        ctx.reserve(64)
-        keep = ws['poses'].clone()
-        side = torch.cuda.Stream()
-        side.wait_stream(st)
-        with torch.cuda.stream(side):                        # eager passes first: lazy initialisation, allocator warm-up
-          for _ in range(2):
-            run()
-            ws['poses'].copy_(keep)
-        st.wait_stream(side)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-          run()
-        ws['poses'].copy_(keep)                              # (capturing does not execute)
-        g = ws['graph'] = (graph, ctx.arena_generation())
-      g[0].replay()
-    else:
-      ctx.reserve(64)
-      run()
+    ws['run'](st, self._graph_on)
     st.synchronize()                                         # the results were written to pinned host memory by the frame's last launch
     out = ws['pose_of_mesh'].numpy().copy()
     for o, e in enumerate(self.estimators):
@@ -258,6 +214,7 @@ class MultiObjectTracker:
     set_seed(0) is called once, as register() does.  No debug canvases: unlike register() at `debug >= 2`, this call writes nothing."""
     from . import _lib, Utils as U
     from ._lib import check, lib, stream_ptr
+    from .frame import FrameBuffer
     ests = self.estimators
     H, W, label_img, mask_list, labels = self._check_register(depth, masks, labels)
     self._last_frame = (H, W, K)
@@ -268,49 +225,16 @@ class MultiObjectTracker:
     n = len(ests)
     ctx = ests[0].refiner.ctx
     dev = ests[0].mesh_tensors['pos'].device
-    is_u8 = (rgb.dtype == np.uint8) if isinstance(rgb, np.ndarray) else (rgb.dtype == torch.uint8)
-    HW = H * W
-    n_lab, n_rgb, n_msk = (HW * 4 if label_img is not None else 0), HW * 3 * (1 if is_u8 else 4), (0 if label_img is not None else n * HW)
+    is_u8 = rgb.dtype == (np.uint8 if isinstance(rgb, np.ndarray) else torch.uint8)
     key = (H, W, is_u8, label_img is not None)
-    ws = self._reg_ws.get(key) if hasattr(self, '_reg_ws') else None
+    ws = self._reg_ws.get(key)
     if ws is None:
-      if not hasattr(self, '_reg_ws'):
-        self._reg_ws = {}
       # the frame, the label image or the masks behind one another in ONE buffer: host arrays go up in one copy
-      frame = torch.empty((HW * 4 + n_lab + n_rgb + n_msk,), dtype=torch.uint8, device=dev)
-      o_rgb, o_msk = HW * 4 + n_lab, HW * 4 + n_lab + n_rgb
-      ws = self._reg_ws[key] = dict(
-        frame=frame, host=torch.empty_like(frame, device='cpu').pin_memory(), depth=frame[:HW * 4].view(torch.float).reshape(H, W),
-        labels=frame[HW * 4:o_rgb].view(torch.int32).reshape(H, W) if n_lab else None,
-        rgb=frame[o_rgb:o_msk].reshape(H, W, 3) if is_u8 else frame[o_rgb:o_msk].view(torch.float).reshape(H, W, 3),
-        masks=frame[o_msk:].reshape(n, H, W) if n_msk else None,
-        depth_f=torch.empty((H, W), dtype=torch.float, device=dev), xyz=torch.empty((H, W, 3), dtype=torch.float, device=dev),
-        rgb_f=torch.empty((H, W, 3), dtype=torch.float, device=dev) if is_u8 else None,
-        pose_of_mesh=torch.zeros((n, 4, 4), dtype=torch.float).pin_memory())
-    host_in = all(isinstance(x, np.ndarray) for x in [rgb, depth] + ([label_img] if mask_list is None else mask_list))
-    if host_in:
-      hb = ws['host'].numpy()
-      view = lambda t: hb[t.data_ptr() - ws['frame'].data_ptr():][:t.numel() * t.element_size()].view(
-        {torch.float: np.float32, torch.int32: np.int32, torch.uint8: np.uint8}[t.dtype]).reshape(tuple(t.shape))
-      view(ws['depth'])[:] = depth
-      view(ws['rgb'])[:] = rgb
-      if label_img is not None:
-        view(ws['labels'])[:] = label_img
-      else:
-        mv = view(ws['masks'])
-        for o, m in enumerate(mask_list):
-          np.not_equal(m, 0, out=mv[o].view(bool))
-      ws['frame'].copy_(ws['host'], non_blocking=True)
-    else:
-      up = lambda x: torch.as_tensor(np.ascontiguousarray(x) if isinstance(x, np.ndarray) else x).to(dev)
-      ws['depth'].copy_(up(depth))
-      ws['rgb'].copy_(up(rgb))
-      if label_img is not None:
-        ws['labels'].copy_(up(label_img))
-      else:
-        for o, m in enumerate(mask_list):
-          ws['masks'][o].copy_(up(m) != 0)
-    Kd = np.ascontiguousarray(np.asarray(K.detach().cpu().numpy() if torch.is_tensor(K) else K, dtype=np.float64).reshape(3, 3))
+      ws = self._reg_ws[key] = dict(fb=FrameBuffer(H, W, is_u8, dev, labels=label_img is not None, n_masks=0 if mask_list is None else n),
+                                    pose_of_mesh=torch.zeros((n, 4, 4), dtype=torch.float).pin_memory())
+    fb = ws['fb']
+    fb.put(rgb, depth, labels=label_img, masks=mask_list)
+    Kd, K_ptr = _lib.k_ptr(K)
     Kinv = np.ascontiguousarray(np.linalg.inv(K.detach().cpu().numpy() if torch.is_tensor(K) else K), dtype=np.float64)
     cfg = ests[0].refiner._c_cfg()
     meshes = [_lib.device_mesh(ctx, e.mesh_tensors) for e in ests]
@@ -320,9 +244,8 @@ class MultiObjectTracker:
     out_o = [torch.empty((len(g),), dtype=torch.int64, device=dev) for g in grids]
     objs = (_lib.FpRegisterObject * n)()
     for o, e in enumerate(ests):
-      objs[o].mesh, objs[o].mesh_diameter = meshes[o].handle, float(e.diameter)
-      objs[o].model_center[:] = [float(x) for x in np.asarray(e.model_center, dtype=np.float32)]
-      objs[o].d_mask = ws['masks'][o].data_ptr() if label_img is None else None
+      objs[o].mesh, objs[o].mesh_diameter, objs[o].model_center = meshes[o].handle, float(e.diameter), _lib.center3(e.model_center)
+      objs[o].d_mask = fb.masks[o].data_ptr() if label_img is None else None
       objs[o].label = labels[o] if labels is not None else 0
       objs[o].d_rot_grid, objs[o].n_hyp = grids[o].data_ptr(), len(grids[o])
       objs[o].d_poses, objs[o].d_scores, objs[o].d_order = out_p[o].data_ptr(), out_s[o].data_ptr(), out_o[o].data_ptr()
@@ -330,15 +253,12 @@ class MultiObjectTracker:
     a = _lib.FpRegisterObjectsArgs()
     a.struct_size = ctypes.sizeof(a)
     a.refine_net, a.score_net = ests[0].refiner.model.handle, ests[0].scorer.model.handle
-    a.d_rgb, a.rgb_is_u8, a.d_depth, a.H, a.W = ws['rgb'].data_ptr(), 1 if is_u8 else 0, ws['depth'].data_ptr(), H, W
-    a.K, a.K_inv, a.refine_cfg = Kd.ctypes.data, Kinv.ctypes.data, ctypes.addressof(cfg)
+    fb.fill(a)
+    a.K, a.K_inv, a.refine_cfg = K_ptr, Kinv.ctypes.data, ctypes.addressof(cfg)
     scfg = ests[0].scorer.cfg
     a.score_crop_ratio, a.score_normalize_xyz = float(scfg['crop_ratio']), 1 if scfg['normalize_xyz'] else 0
     a.iteration, a.n_obj, a.objs = int(iteration), n, ctypes.addressof(objs)
-    a.d_labels = ws['labels'].data_ptr() if label_img is not None else None
     a.max_pass_hyp = int(max_pass_hyp)
-    a.d_depth_f, a.d_xyz = ws['depth_f'].data_ptr(), ws['xyz'].data_ptr()
-    a.d_rgb_f = ws['rgb_f'].data_ptr() if is_u8 else None
     check(lib().fp_register_objects(ctx.handle, ctypes.byref(a), stream_ptr(dev)))
     torch.cuda.current_stream(dev).synchronize()             # the results were written to pinned host memory by the call's last launch
     out = np.empty((n, 4, 4), dtype=np.float32)
@@ -364,11 +284,7 @@ class MultiObjectTracker:
     their `pose_last`; the frame size and K (unless given) are those of the last frame.  depth=None: only the objects hide one another;
     with the frame's depth image (H,W) it hides them as well (occluders as in scene_instances)."""
     from . import Utils as U
-    for i, e in enumerate(self.estimators):
-      if e.pose_last is None:
-        raise ValueError(f'MultiObjectTracker.instance_masks: estimator {i} has no pose yet (pose_last is None): register it first')
-    if getattr(self, '_last_frame', None) is None:
-      raise ValueError('MultiObjectTracker.instance_masks: no frame seen yet: call register or track first')
+    self._need_poses('instance_masks', frame=True)
     H, W, K_last = self._last_frame
     dev = self.estimators[0].mesh_tensors['pos'].device
     poses = torch.stack([torch.as_tensor(e.pose_last, device=dev, dtype=torch.float).reshape(4, 4) for e in self.estimators])
@@ -383,12 +299,8 @@ class MultiObjectTracker:
     contour=True outlines them: the owner map then comes from instance_masks(depth=depth).  Other keywords go to Utils.draw_poses."""
     from . import Utils as U
     ests = self.estimators
-    for i, e in enumerate(ests):
-      if e.pose_last is None:
-        raise ValueError(f'MultiObjectTracker.draw: estimator {i} has no pose yet (pose_last is None): register it first')
-    if getattr(self, '_last_frame', None) is None:
-      raise ValueError('MultiObjectTracker.draw: no frame seen yet: call register or track first')
-    returned = getattr(self, '_returned', None) or [(None, None)] * len(ests)
+    self._need_poses('draw', frame=True)
+    returned = self._returned or [(None, None)] * len(ests)
     poses, boxes, offs = [], [], []
     for e, (held, pose) in zip(ests, returned):
       if held is not e.pose_last:                           # set elsewhere since: the pose of the original mesh as track_one forms it
