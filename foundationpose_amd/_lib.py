@@ -113,6 +113,8 @@ FP_TSDF_PLANES = ('tsdf', 'weight', 'r', 'g', 'b', 'color_weight')      # FP_TSD
 FP_TSDF_ALIGN_TERMS = 29                                                  # fp_tsdf_align: doubles per view of h_sums
 FP_DEPTH_ALIGN_TERMS, FP_DEPTH_ALIGN_MAX_PAIRS = 29, 256                  # fp_depth_pairs_align: doubles per pair of h_sums, pairs per call
 FP_PHOTO_ALIGN_TERMS = 58                                                 # fp_depth_pairs_align_photo: doubles per pair of h_sums
+FP_PLANE_MAX_HYP, FP_PLANE_MOMENT_TERMS = 1024, 10                        # fp_plane_score, fp_plane_moments
+FP_SEGMENT_STATS, FP_SEGMENT_MAX_PIXELS = 16, 1 << 28                     # fp_depth_segment_write: int64 per kept component; pixels per call
 
 
 FP_TEXTURE_MIN_SIZE, FP_TEXTURE_MAX_SIZE, FP_TEXTURE_MAX_TOP_N, FP_TEXTURE_MAX_FACES = 64, 4096, 4, 1 << 21      # fp_texture_bake
@@ -189,6 +191,12 @@ _PROTOS = {
   'fp_view_intensity': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
   'fp_depth_pairs_align_photo': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_float, c_float,
                                          c_float, c_void_p, c_void_p, c_void_p]),
+  'fp_plane_score': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_float, c_void_p, c_int, c_float, c_void_p, c_void_p,
+                             c_void_p, c_void_p]),
+  'fp_plane_moments': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_float, c_void_p, c_float, c_void_p, c_void_p]),
+  'fp_depth_segment_count': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_float, c_void_p, c_float, c_float, c_float,
+                                     c_int, c_void_p, c_void_p]),
+  'fp_depth_segment_write': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
   'fp_texture_bake': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                               POINTER(FpTextureCfg), c_void_p, c_void_p, c_void_p, c_void_p]),
   'fp_point_mesh_distance': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),

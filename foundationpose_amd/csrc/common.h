@@ -139,9 +139,11 @@ struct fp_ctx {
   bool side_ready = false;
   struct fp_simplify_state *simplify = nullptr;   // mesh_simplify.hip: what fp_mesh_simplify_count leaves for fp_mesh_simplify_write
   struct fp_components_state *components = nullptr;   // mesh_components.hip: what fp_mesh_components_count leaves for fp_mesh_components_write
+  struct fp_segment_state *segment = nullptr;         // segment.hip: what fp_depth_segment_count leaves for fp_depth_segment_write
 };
 void fp_simplify_state_free(fp_ctx *ctx);         // mesh_simplify.hip; fp_ctx_destroy
 void fp_components_state_free(fp_ctx *ctx);       // mesh_components.hip; fp_ctx_destroy
+void fp_segment_state_free(fp_ctx *ctx);          // segment.hip; fp_ctx_destroy
 
 int fp_arena_ensure(fp_ctx *ctx, size_t bytes);
 size_t fp_arena_bytes_for(int n_hyp);     // whole refine/score pass (outer buffers + network)

@@ -248,13 +248,15 @@ def volume_from_views(depths, masks, K, cam_in_obs, voxel_size, margin=None, dev
   return origin, dims
 
 
-def load_reference_views(dir, depth_dir=None, mask_dir='mask', poses=True):
+def load_reference_views(dir, depth_dir=None, mask_dir='mask', poses=True, masks=True):
   """The reference's folder of reference views (bundlesdf/run_nerf.py: run_one_ob): rgb/NAME.png; depth as 16-bit PNG in millimetres
   under `depth_dir` (default: depth_enhanced/ when it exists, else depth/), read as value / 1e3 in float64 and cast to float32;
   `mask_dir`/NAME.png (non-zero = object); cam_in_ob/NAME.txt (4x4, camera-to-object); K.txt.  Returns a dict: rgbs (n,H,W,3) uint8,
   depths (n,H,W) float32 metres, masks (n,H,W) uint8, K (3,3), cam_in_obs (n,4,4) float64, names.  poses=False does not read cam_in_ob/
-  (a folder that is still to be posed: estimate_view_poses) and returns no cam_in_obs."""
+  (a folder that is still to be posed: estimate_view_poses) and returns no cam_in_obs.  masks=False likewise does not read `mask_dir`
+  (a folder that is still to be segmented: segment_views) and returns no masks."""
   from PIL import Image
+  want_masks = masks
   files = sorted(glob.glob(os.path.join(dir, 'rgb', '*.png')))
   if not files:
     raise FileNotFoundError(f'no rgb/*.png under {dir}')
@@ -268,11 +270,15 @@ def load_reference_views(dir, depth_dir=None, mask_dir='mask', poses=True):
     if d.ndim != 2:
       raise ValueError(f'{depth_dir}/{name}.png is not a single-channel depth image')
     depths.append((d.astype(np.float64) / 1e3).astype(np.float32))
-    m = np.asarray(Image.open(os.path.join(dir, mask_dir, name + '.png')))
-    masks.append(((m if m.ndim == 2 else m.max(-1)) > 0).astype(np.uint8))
+    if want_masks:
+      m = np.asarray(Image.open(os.path.join(dir, mask_dir, name + '.png')))
+      masks.append(((m if m.ndim == 2 else m.max(-1)) > 0).astype(np.uint8))
     if poses:
       cams.append(np.loadtxt(os.path.join(dir, 'cam_in_ob', name + '.txt')).reshape(4, 4))
-  out = dict(rgbs=np.stack(rgbs), depths=np.stack(depths), masks=np.stack(masks), K=np.loadtxt(os.path.join(dir, 'K.txt')).reshape(3, 3), names=names)
+  out = dict(rgbs=np.stack(rgbs), depths=np.stack(depths))
+  if want_masks:
+    out['masks'] = np.stack(masks)
+  out.update(K=np.loadtxt(os.path.join(dir, 'K.txt')).reshape(3, 3), names=names)
   if poses:
     out['cam_in_obs'] = np.stack(cams)
   return out
@@ -709,13 +715,58 @@ def estimate_view_poses(views, first_pose=None, window=2, stages=ODOMETRY_STAGES
   return poses, info
 
 
+def segment_views(views, keep='central', device='cuda', **kw):
+  """Fills views['masks'] from the depth maps alone, for an object standing on a plane (a turntable, a table top): (views, info).  One
+  batched call of each kernel per 64 views: Utils.fit_plane on every view (unless plane= is given), then Utils.segment_on_plane; keywords
+  go to the latter (h_min, h_max, max_jump, min_pixels, zfar, tol, n_hyp, seed, refits, plane).  Of a view's kept segments ONE becomes its
+  mask: keep='central' the one whose centroid projects nearest to the principal point (K[0,2], K[1,2]), keep='largest' the one with the
+  most pixels; ties go to the lowest label.  A view without a kept segment gets an empty mask and is named in info['empty'].  views: a
+  dict with depths (n,H,W) and K (load_reference_views(dir, masks=False)); it is updated in place and returned.  info: label (n,) the
+  chosen label or 0, planes (n,4), stats (the per-view dicts of segment_on_plane), empty (the indices of views without a mask).  The
+  limits of segment_on_plane hold: whatever touches the object without a depth step (a hand, a fixture) is part of its segment."""
+  from .segment import segment_on_plane
+  if keep not in ('central', 'largest'):
+    raise ValueError(f"keep must be 'central' or 'largest', got {keep!r}")
+  depths = views['depths']
+  K = np.asarray(views['K'].detach().cpu() if torch.is_tensor(views['K']) else views['K'], dtype=np.float64).reshape(3, 3)
+  if torch.is_tensor(depths) and depths.is_cuda:
+    dev = depths.device
+  else:
+    dev, depths = _device(device), np.asarray(depths)
+  if depths.ndim != 3:
+    raise ValueError(f'views["depths"] must be (n,H,W), got {tuple(depths.shape)}')
+  labels, stats = segment_on_plane(torch.as_tensor(depths, device=dev), K, **kw)
+  chosen = np.zeros((len(stats),), np.int32)
+  for v, st in enumerate(stats):
+    if len(st['label']) == 0:
+      continue
+    if keep == 'largest':
+      score = -st['n_pixels'].astype(np.float64)
+    else:
+      c = st['centroid']
+      score = (K[0, 0] * c[:, 0] / c[:, 2]) ** 2 + (K[1, 1] * c[:, 1] / c[:, 2]) ** 2      # squared pixel distance from the principal point
+    chosen[v] = st['label'][int(np.argmin(score))]      # argmin takes the first of equals: the lowest label
+  pick = torch.as_tensor(chosen, device=dev).reshape(-1, 1, 1)
+  masks = ((labels == pick) & (pick > 0)).to(torch.uint8)
+  views['masks'] = masks if torch.is_tensor(views['depths']) and views['depths'].is_cuda else masks.cpu().numpy()
+  info = dict(label=chosen, planes=np.stack([st['plane'] for st in stats]), stats=stats, empty=np.nonzero(chosen == 0)[0].tolist())
+  return views, info
+
+
 def reconstruct_object(views, voxel_size=0.002, trunc=None, min_weight=1, depth_filter=True, margin=None, device='cuda', refine_poses=False,
                        max_vertices=None, simplify_cell=None, components='largest', texture=None, symmetries=None, estimate_poses=False,
-                       photometric=False):
+                       photometric=False, segment=False):
   """_reconstruct_mesh (which documents every other argument) and, with `symmetries`, the rotational symmetries of the finished mesh:
   symmetries=True runs Utils.find_symmetries with its defaults, a dict gives its keyword arguments (tol, max_order, ..), and the call
   then returns (mesh, info) - info['symmetry_tfs'] is what FoundationPose(symmetry_tfs=) takes, and bop.write_models_info writes the
-  rest to models_info.json.  The default (None or False) returns the mesh alone, as before."""
+  rest to models_info.json.  The default (None or False) returns the mesh alone, as before.
+  segment (False, True or a dict of segment_views' keyword arguments) is for views WITHOUT masks, of an object standing on a plane:
+  segment_views makes them from the depth maps first; a folder is then read without mask/.  Views that have masks keep them."""
+  if segment is not False and segment is not None:
+    if isinstance(views, (str, os.PathLike)):
+      views = load_reference_views(views, poses=not estimate_poses, masks=False)
+    if views.get('masks') is None:
+      views = segment_views(dict(views), device=device, **(segment if isinstance(segment, dict) else {}))[0]
   mesh = _reconstruct_mesh(views, voxel_size=voxel_size, trunc=trunc, min_weight=min_weight, depth_filter=depth_filter, margin=margin,
                            device=device, refine_poses=refine_poses, max_vertices=max_vertices, simplify_cell=simplify_cell,
                            components=components, texture=texture, estimate_poses=estimate_poses, photometric=photometric)

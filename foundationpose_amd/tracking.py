@@ -277,6 +277,22 @@ class MultiObjectTracker:
     self._returned = [(e.pose_last if objs[o].registered else False, out[o].copy()) for o, e in enumerate(ests)]      # (False: never a pose_last)
     return out
 
+  def segment(self, depth, K, **kw):
+    """Masks for `register` from the depth image alone, for objects standing on one plane: (label_image, labels) with label_image an
+    (H,W) int32 DEVICE tensor (Utils.segment_on_plane; keywords go to it) and labels[o] the segment given to object o by
+    Utils.assign_segments on the estimators' diameters - by size only, so objects of similar diameter cannot be told apart; an object
+    without a segment gets a negative label, which matches no pixel.  `register(rgb, depth, K, label_image, labels=labels)` takes both
+    without a host copy of the image.  Also leaves `self.segments` = dict(stats, cost) of the call."""
+    from . import Utils as U
+    dev = self.estimators[0].mesh_tensors['pos'].device
+    depth = torch.as_tensor(depth, device=dev)
+    if depth.dim() != 2:
+      raise ValueError(f'MultiObjectTracker.segment: depth must be one (H,W) image, got {tuple(depth.shape)}')
+    label_image, stats = U.segment_on_plane(depth, K, **kw)
+    labels, cost = U.assign_segments(stats, [float(e.diameter) for e in self.estimators], K=K)
+    self.segments = dict(stats=stats, cost=cost)
+    return label_image, labels
+
   def instance_masks(self, depth=None, K=None, occluders=None, delta=0.015):
     """Which pixels every object covers at its current pose, after `register` / `track`: dict(owner (H,W) int32 device tensor, the
     object in front at the pixel, -1 = none; mask_visib (n_obj,H,W) uint8 0 / 255; visib_fract (n_obj,) float64 numpy, the visible

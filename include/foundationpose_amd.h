@@ -809,6 +809,70 @@ int fp_depth_pairs_align_photo(fp_ctx *ctx, const float *d_depth, const float *d
                                const double *K, const double *cam_in_ob, const int32_t *pairs, int n_pairs, float dist_max, float cos_min,
                                float i_max, float *d_rows, double *h_sums, void *stream);
 
+/* ---- masks from depth: the objects standing on one supporting plane (csrc/segment.hip).  Find the plane (fp_plane_score over explicit
+ *      three-pixel hypotheses, fp_plane_moments for the least-squares refit on the host), keep what stands above it, cut that into
+ *      4-connected components (fp_depth_segment_count / _write).  Geometry only: no weights, no recognition; objects that touch without
+ *      a depth step between them are one segment, and there is one plane.  The reference offers a mask-painting GUI instead
+ *      (src/masking.py); this rule is the library's own.  tests/segment_oracle.py restates all of it in numpy.
+ *      Everything is fp32, not contracted, every operation in the written order; / and sqrtf are correctly rounded.  d_depth
+ *      (n_views,H,W) fp32 metres on the device, d_mask (n_views,H,W) uint8 or null, K (3,3) float64 HOST (fx, fy, cx, cy cast to fp32),
+ *      one K and one size for all views, pixel index row W + col.  p(r,c) is the back-projection of fp_depth_normals:
+ *        p = ((((float)col - cx) / fx) d, (((float)row - cy) / fy) d, d)
+ *        ok(r,c): d >= 0.001 and d < zfar and, with a mask, mask != 0
+ *      0 < zfar <= 1000 in all four calls, and at most FP_SEGMENT_MAX_PIXELS pixels (n_views H W) a call.  A view's results are
+ *      bit-identical in any batch and at any index of it, and from run to run: counts and statistics are integer atomics, the moments
+ *      are summed in a fixed order, nothing is a float atomic.
+ *      Planes are (n.x, n.y, n.z, dd) with the camera (the origin) on the positive side: (n . p) + dd is the height of p above the plane.
+ *      (a) fp_plane_score.  triplets (n_views,n_hyp,3) int32 HOST pixel indices, 0 <= n_hyp <= FP_PLANE_MAX_HYP.  Per view and
+ *      hypothesis (i, j, k):
+ *        count 0 and plane (0,0,0,0) unless i, j, k are in 0 .. H W - 1, pairwise different and ok
+ *        u = p_j - p_i,  w = p_k - p_i;   m = u x w = (u.y w.z - u.z w.y, u.z w.x - u.x w.z, u.x w.y - u.y w.x)
+ *        l2 = (m.x m.x + m.y m.y) + m.z m.z;   count 0 and plane (0,0,0,0) unless l2 > 0
+ *        l = sqrtf(l2);  n = (m.x / l, m.y / l, m.z / l);   dd = -((n.x p_i.x + n.y p_i.y) + n.z p_i.z)
+ *        if dd < 0: n = -n, dd = -dd
+ *        count = the number of ok pixels with fabsf(((n.x p.x + n.y p.y) + n.z p.z) + dd) < tol, int32
+ *      h_planes (n_views,n_hyp,4) fp32, h_counts (n_views,n_hyp) int32 and h_best (n_views) int32 are HOST arrays: h_best is the
+ *      hypothesis with the largest count, the lowest index among equals, -1 when every count is 0 (or n_hyp is 0).  SYNCHRONISES.
+ *      (b) fp_plane_moments.  planes (n_views,4) float64 HOST, cast to fp32.  h_sums (n_views, FP_PLANE_MOMENT_TERMS) float64 HOST:
+ *      n, Sx, Sy, Sz, Sxx, Sxy, Sxz, Syy, Syz, Szz over the ok pixels with fabsf(((n.x p.x + n.y p.y) + n.z p.z) + dd) < tol; x, y, z
+ *      widened to double before the products; any other pixel adds +0.0 to every term.  Summation order (that of csrc/gn_sums.h): a
+ *      workgroup of 256 threads owns a tile of 1024 pixels of one view (pixels past the view's last one add +0.0); lane tid adds pixels
+ *      tile 1024 + q 256 + tid, q = 0 .. 3 in that order, from +0.0; over the 64 lanes of a wave a butterfly, partner distance 32, 16,
+ *      .. 1, s = s + s[lane ^ o]; the four waves in order, red[0] + red[1] + ..; the tiles in order from 0.0.  SYNCHRONISES.
+ *      (c) fp_depth_segment_count / fp_depth_segment_write, count-then-write as fp_mesh_components_*.  planes as in (b).  Per pixel:
+ *        h = ((n.x p.x + n.y p.y) + n.z p.z) + dd;   foreground: ok and h >= h_min and h <= h_max
+ *        two 4-neighbours a, b are joined when both are foreground and fabsf(d_a - d_b) <= max_jump (the gate of fp_depth_normals)
+ *      A component is kept when it has at least min_pixels pixels; the kept components of a view are numbered 1, 2, .. by their lowest
+ *      pixel index.  fp_depth_segment_count builds the decomposition in an allocation owned by the context (24 bytes a pixel, kept
+ *      until a larger batch arrives or the context is destroyed), SYNCHRONISES and returns h_counts (n_views,2) int32 HOST: components,
+ *      kept components.  The caller allocates d_labels (n_views,H,W) int32 and d_stats (sum of kept, FP_SEGMENT_STATS) int64 (may be
+ *      null when nothing is kept) and calls fp_depth_segment_write with the SAME d_depth, n_views, H, W and n_kept = the sum of the kept
+ *      counts; it queues its kernels and does not synchronise.  d_labels: the component's number where it is kept, else 0.  d_stats: the
+ *      kept components of view 0 in label order, then those of view 1, ..; with q(x) = (long long)rintf(min(max(x 1048576.f, -2^34),
+ *      2^34)), i.e. 2^-20 m fixed point (the clamp is never met by a camera with |col - cx| / fx of ordinary size: 2^34 is 16 km), a row is
+ *        0 pixels;  1 rmin, 2 rmax, 3 cmin, 4 cmax;  5-7 sum of q(p.x), q(p.y), q(p.z);  8-10 min of the same;  11-13 max of the same;
+ *        14 max of q(h);  15 the lowest pixel index
+ *      How: the lock-free union-find of fp_mesh_components_count over the pixels - roots only decrease, hooks are by compare-and-swap,
+ *      one flatten pass - started from the horizontal runs inside each wave; no kernel waits for another workgroup.
+ *      FP_EINVAL, each checked before ctx is looked into (count, score, moments): a null ctx, d_depth, K, planes or host output; H or
+ *      W < 1; n_views outside 0 .. FP_TSDF_MAX_VIEWS (0 writes nothing); more than FP_SEGMENT_MAX_PIXELS pixels; a non-finite K, or fx
+ *      or fy not > 0; zfar outside (0, 1000]; tol or max_jump not > 0; h_max < h_min; min_pixels < 1; n_hyp outside 0 ..
+ *      FP_PLANE_MAX_HYP, or null triplets, h_planes or h_counts with n_hyp > 0; a plane that is not finite or has a zero normal (as
+ *      fp32); for write: no count before it on this context, other maps (d_depth, n_views, H, W) than the last count had, n_kept other
+ *      than its sum, a null d_labels.  FP_ENOMEM: the state does not fit the device. */
+#define FP_PLANE_MAX_HYP 1024          /* hypotheses per view of fp_plane_score */
+#define FP_PLANE_MOMENT_TERMS 10       /* doubles per view of fp_plane_moments' h_sums */
+#define FP_SEGMENT_STATS 16            /* int64 per kept component of fp_depth_segment_write's d_stats */
+#define FP_SEGMENT_MAX_PIXELS (1 << 28) /* n_views H W of one call */
+int fp_plane_score(fp_ctx *ctx, const float *d_depth, const uint8_t *d_mask, int n_views, int H, int W, const double *K, float zfar,
+                   const int32_t *triplets, int n_hyp, float tol, float *h_planes, int32_t *h_counts, int32_t *h_best, void *stream);
+int fp_plane_moments(fp_ctx *ctx, const float *d_depth, const uint8_t *d_mask, int n_views, int H, int W, const double *K, float zfar,
+                     const double *planes, float tol, double *h_sums, void *stream);
+int fp_depth_segment_count(fp_ctx *ctx, const float *d_depth, const uint8_t *d_mask, int n_views, int H, int W, const double *K, float zfar,
+                           const double *planes, float h_min, float h_max, float max_jump, int min_pixels, int32_t *h_counts, void *stream);
+int fp_depth_segment_write(fp_ctx *ctx, const float *d_depth, int n_views, int H, int W, int32_t *d_labels, int64_t *d_stats, int64_t n_kept,
+                           void *stream);
+
 /* ---- texture baking: the colours of posed RGB-D reference views gathered into a per-face texture atlas of a mesh - the last stage of
  *      the model-free set-up, after the simplification (fp_mesh_simplify_* refuses textured meshes: simplify first, then bake).  The
  *      reference does this in mesh_texture_from_train_images (bundlesdf/nerf_runner.py:1122) with a UV parametrisation and the equal

@@ -3,7 +3,7 @@ cam_in_ob/, K.txt), by TSDF fusion and marching tetrahedra on the GPU (foundatio
 usage: python scripts/reconstruct_object.py DIR [--voxel 0.002] [--trunc T] [--min-weight 1] [--no-depth-filter] [--refine-poses | --joint-refine] [--estimate-poses]
        [--photometric [WEIGHT]]
        [--max-vertices N | --simplify-cell C] [--min-component-fraction X] [--texture [SIZE]] [--out DIR/model/model.obj]
-       [--compare-to MODEL] [--symmetries [--symmetry-tol T]]
+       [--compare-to MODEL] [--symmetries [--symmetry-tol T]] [--segment]
 The output format follows the extension: .obj or .ply.  --refine-poses aligns every view but the first to the geometry fused so far before the
 fusion (reconstruct.refine_view_poses) and also writes the poses it used to DIR/cam_in_ob_refined/NAME.txt.  --joint-refine refines all poses
 together from depth alone instead (reconstruct.joint_refine_view_poses: pairwise ICP, view 0 the anchor) and writes cam_in_ob_refined/ too.
@@ -20,7 +20,10 @@ model.obj with model.mtl and model.png beside it; OBJ only - a PLY holds one uv 
 (OBJ or PLY, e.g. the CAD model, in the frame and unit of the views' poses) adds one JSON line: the Chamfer and Hausdorff distance and
 precision / recall / F-score of the written model against MODEL (Utils.mesh_distance; scripts/mesh_distance.py has more options).
 --symmetries finds the model's rotational symmetries (Utils.find_symmetries; --symmetry-tol T in metres, default 2 % of the diameter) and
-writes DIR/model/models_info.json with object id 1 (bop.write_models_info: diameter, bounds and the symmetry keys, in millimetres)."""
+writes DIR/model/models_info.json with object id 1 (bop.write_models_info: diameter, bounds and the symmetry keys, in millimetres).
+--segment is for a folder WITHOUT mask/, of an object standing on a plane (a turntable): the masks come from the depth maps
+(reconstruct.segment_views: the supporting plane, what stands above it, the segment nearest the image centre) and are written to
+DIR/mask/NAME.png; whatever touches the object without a depth step is part of its mask."""
 import argparse
 import json
 import os
@@ -30,7 +33,21 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from foundationpose_amd import mesh_io
-from foundationpose_amd.reconstruct import estimate_view_poses, joint_refine_view_poses, load_reference_views, reconstruct_object, refine_view_poses
+from foundationpose_amd.reconstruct import (estimate_view_poses, joint_refine_view_poses, load_reference_views, reconstruct_object, refine_view_poses,
+                                            segment_views)
+
+
+def load_views(args, poses):
+  if not args.segment:
+    return load_reference_views(args.dir, poses=poses)
+  from PIL import Image
+  views, info = segment_views(load_reference_views(args.dir, poses=poses, masks=False))
+  os.makedirs(os.path.join(args.dir, 'mask'), exist_ok=True)
+  for name, m in zip(views['names'], views['masks']):
+    Image.fromarray((np.asarray(m) != 0).astype(np.uint8) * 255).save(os.path.join(args.dir, 'mask', name + '.png'))
+  for v in info['empty']:
+    print(f'view {views["names"][v]}: no segment above the plane, its mask is empty')
+  return views
 
 
 def main():
@@ -52,6 +69,7 @@ def main():
   ap.add_argument('--compare-to', default=None, metavar='MODEL')
   ap.add_argument('--symmetries', action='store_true')
   ap.add_argument('--symmetry-tol', type=float, default=None)
+  ap.add_argument('--segment', action='store_true')
   args = ap.parse_args()
   out = args.out or os.path.join(args.dir, 'model', 'model.obj')
   if args.texture is not None and out.lower().endswith('.ply'):
@@ -62,14 +80,14 @@ def main():
   if args.photometric is not False and (args.refine_poses or not (estimate or args.joint_refine)):
     ap.error('--photometric goes with --joint-refine or --estimate-poses (--refine-poses has no photometric term)')
   if estimate:
-    views = load_reference_views(args.dir, poses=False)
+    views = load_views(args, poses=False)
     poses, _ = estimate_view_poses(views, depth_filter=not args.no_depth_filter, photometric=args.photometric)
     os.makedirs(os.path.join(args.dir, 'cam_in_ob_estimated'), exist_ok=True)
     for name, pose in zip(views['names'], poses):
       np.savetxt(os.path.join(args.dir, 'cam_in_ob_estimated', name + '.txt'), pose, fmt='%.18e')
     views = dict(views, cam_in_obs=poses)
   else:
-    views = load_reference_views(args.dir)
+    views = load_views(args, poses=True)
   if args.refine_poses or args.joint_refine:
     if args.joint_refine:
       poses, info = joint_refine_view_poses(views, depth_filter=not args.no_depth_filter, photometric=args.photometric)

@@ -1,0 +1,440 @@
+"""GPU: masks from depth - fp_plane_score, fp_plane_moments, fp_depth_segment_count / _write and the Python on top of them
+(foundationpose_amd/segment.py, MultiObjectTracker.segment, reconstruct.segment_views).
+
+The yardstick is tests/segment_oracle.py, the numpy / scipy restatement of the rules of include/foundationpose_amd.h: counts, planes, best
+index, label images and the integer statistics must equal it exactly, the ten moments bit for bit (the oracle restates the summation
+order).  Test 5 checks the meaning without the oracle, on the analytic table scene whose plane and spheres are known."""
+import numpy as np
+import pytest
+import torch
+
+from tests import segment_oracle as O
+
+pytestmark = pytest.mark.gpu
+K_SMALL = np.array([[50.0, 0, 26], [0, 50.0, 18], [0, 0, 1]])
+FRONTO = np.array([0.0, 0, -1, 1])      # height = 1 - depth, exact in fp32 for the depths used below
+SEG = dict(h_min=0.008, h_max=0.5, min_pixels=20)
+
+
+def bits(a):
+  a = np.ascontiguousarray(a)
+  return a.view({4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
+
+
+@pytest.fixture(scope='module')
+def tables():
+  return {a: O.analytic_table(a) for a in (35, 60)}
+
+
+def random_depth(H, W, seed):
+  rs = np.random.RandomState(seed)
+  d = rs.uniform(0.5, 1.5, (H, W)).astype(np.float32)
+  d[rs.uniform(size=(H, W)) < 0.1] = 0      # invalid pixels
+  return d
+
+
+def random_levels(H, W, seed):
+  """Four depth levels 10 cm apart and a tenth of the pixels invalid: neighbours join exactly when they are on one level."""
+  rs = np.random.RandomState(seed)
+  d = (np.float32(0.6) + np.float32(0.1) * rs.randint(0, 4, (H, W)).astype(np.float32)).astype(np.float32)
+  d[rs.uniform(size=(H, W)) < 0.1] = 0
+  return d
+
+
+def gpu_segment(depth, K, plane, **kw):
+  from foundationpose_amd.segment import segment_on_plane
+  return segment_on_plane(depth, K, plane, **kw)
+
+
+def assert_equals_oracle(depth, K, plane, expect_labels=None, **kw):
+  labels, st = gpu_segment(depth, K, plane, **kw)
+  want, rows, n_comp = O.segment(depth, K, plane, **kw)
+  assert labels.dtype == np.int32 and np.array_equal(labels, want)
+  assert st['components'] == n_comp
+  assert st['rows'].shape == rows.shape and np.array_equal(st['rows'], rows), np.nonzero(st['rows'] != rows)
+  if expect_labels is not None:
+    assert labels.max() == expect_labels
+  return labels, st
+
+
+# ---- 1. fp_plane_score ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('H,W', [(72, 96), (1, 7), (7, 1), (53, 37), (37, 53)])
+@pytest.mark.parametrize('n_hyp', [0, 1, 1024])
+def test_plane_score_equals_the_oracle(tables, H, W, n_hyp):
+  from foundationpose_amd.segment import plane_score
+  depth, K = (tables[35]['depth'], tables[35]['K']) if (H, W) == (72, 96) else (random_depth(H, W, H), K_SMALL)
+  tol = 0.004 if (H, W) == (72, 96) else 0.05
+  hw = H * W
+  trip = np.random.RandomState(n_hyp).randint(0, hw, (n_hyp, 3)).astype(np.int32)
+  if n_hyp == 1024:
+    bad = int(np.flatnonzero(depth.ravel() == 0)[0]) if (depth == 0).any() else -5
+    ok3 = np.flatnonzero(depth.ravel() > 0)[:3]
+    trip[0] = (ok3[0], ok3[0], ok3[1])                    # a repeated index
+    trip[1] = (ok3[0], hw, ok3[1])                        # an index outside the image
+    trip[2] = (ok3[0], -1, ok3[1])
+    trip[3] = (ok3[0], bad, ok3[1])                       # an invalid pixel (or another outside index)
+    trip[5] = trip[4] = trip[700]                         # the same triplet twice: equal counts
+    if W >= 3:
+      trip[6] = (0, 1, 2)                                 # three pixels of one row: collinear up to rounding, whatever that gives
+    first = O.plane_score(depth, K, trip, tol)[2]
+    if first >= 0:                                        # the winning triplet once more behind it: the largest count twice
+      trip[1023 if first < 1023 else 1022] = trip[first]
+  planes, counts, best = plane_score(depth[None], K, trip, tol)
+  want_p, want_c, want_b = O.plane_score(depth, K, trip, tol)
+  assert planes.shape == (1, n_hyp, 4) and counts.shape == (1, n_hyp) and best.shape == (1,)
+  assert np.array_equal(counts[0], want_c)
+  assert np.array_equal(bits(planes[0]), bits(want_p))
+  assert best[0] == want_b
+  if n_hyp == 1024:
+    assert (counts[0, :4] == 0).all() and (planes[0, :4] == 0).all()
+    assert counts[0, 4] == counts[0, 5] and best[0] != 5
+    if want_b >= 0:                                       # ties go to the lower index
+      top = np.flatnonzero(counts[0] == counts[0].max())
+      assert len(top) >= 2 and best[0] == top[0]
+    if (H, W) == (72, 96):
+      assert counts[0].max() > 6000                       # the table
+  if n_hyp == 0:
+    assert best[0] == -1
+
+
+def test_plane_score_collinear_pixels_and_a_map_without_a_valid_pixel():
+  from foundationpose_amd.segment import plane_score
+  # fx = fy = 64, cx = cy = 0, depth 2: the points (col / 32, row / 32, 2) are exact, so three pixels of one row ARE collinear: l2 = 0
+  K = np.array([[64.0, 0, 0], [0, 64.0, 0], [0, 0, 1]])
+  d = np.full((8, 8), 2.0, np.float32)
+  trip = np.array([[0, 1, 2], [0, 1, 8], [9, 18, 27]], np.int32)
+  planes, counts, best = plane_score(d[None], K, trip, 0.001)
+  assert counts[0].tolist() == [0, 64, 0] and best[0] == 1
+  assert np.array_equal(planes[0, 1], np.array([0, 0, -1, 2], np.float32)) and (planes[0, [0, 2]] == 0).all()
+  for dead in (np.zeros((8, 8), np.float32), np.full((8, 8), 200.0, np.float32), np.full((8, 8), np.nan, np.float32)):
+    planes, counts, best = plane_score(dead[None], K, trip, 0.001)
+    assert best[0] == -1 and (counts == 0).all() and (planes == 0).all()
+  planes, counts, best = plane_score(d[None], K, trip, 0.001, masks=np.zeros((1, 8, 8), np.uint8))
+  assert best[0] == -1 and (counts == 0).all()
+
+
+# ---- 2. fp_plane_moments -------------------------------------------------------------------------------------------------------------
+def test_plane_moments_bit_equal_alone_and_in_a_batch(tables):
+  from foundationpose_amd.segment import plane_moments
+  views = [tables[35], tables[60], dict(depth=random_depth(72, 96, 5), plane=np.array([0.0, 0, -1, 1.0]))]
+  K = tables[35]['K']
+  want = [O.plane_moments(v['depth'], K, v['plane'], 0.004 if i < 2 else 0.2) for i, v in enumerate(views)]
+  alone = [plane_moments(v['depth'][None], K, v['plane'], 0.004 if i < 2 else 0.2)[0] for i, v in enumerate(views)]
+  for i in range(3):
+    assert alone[i][0] == want[i][0] > 100      # the count is exact
+    assert np.array_equal(bits(alone[i]), bits(want[i])), (alone[i] - want[i])
+  # view 0 at index 0, 1 and 2 of a batch of three (one tol a call: the table scenes and a copy)
+  trio = [views[0], views[1], dict(views[0])]
+  for shift in range(3):
+    order = [(i + shift) % 3 for i in range(3)]
+    got = plane_moments(np.stack([trio[i]['depth'] for i in order]), K, np.stack([trio[i]['plane'] for i in order]), 0.004)
+    for slot, i in enumerate(order):
+      assert np.array_equal(bits(got[slot]), bits(want[i if i < 2 else 0]))
+  # a ragged last tile and a mask
+  d = random_depth(53, 37, 3)
+  m = np.random.RandomState(4).uniform(size=d.shape) < 0.7
+  got = plane_moments(d[None], K_SMALL, FRONTO, 0.3, masks=m[None])[0]
+  assert np.array_equal(bits(got), bits(O.plane_moments(d, K_SMALL, FRONTO, 0.3, mask=m)))
+
+
+# ---- 3. labels and statistics against the oracle ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize('angle', [35, 60])
+@pytest.mark.parametrize('max_jump', [0.01, 0.02])
+def test_segment_analytic_table(tables, angle, max_jump):
+  sc = tables[angle]
+  assert_equals_oracle(sc['depth'], sc['K'], sc['plane'], expect_labels=3, max_jump=max_jump, **SEG)
+  m = np.random.RandomState(angle).uniform(size=sc['depth'].shape) < 0.9
+  assert_equals_oracle(sc['depth'], sc['K'], sc['plane'], max_jump=max_jump, mask=m, h_min=0.008, min_pixels=3)
+
+
+def serpentine(H, W):
+  d = np.full((H, W), 1.0, np.float32)
+  d[0::2, :] = 0.5
+  for k, r in enumerate(range(1, H, 2)):
+    d[r, W - 1 if k % 2 == 0 else 0] = 0.5
+  return d
+
+
+@pytest.mark.parametrize('H,W', [(37, 53), (53, 37), (9, 300)])
+def test_segment_serpentine_is_one_component(H, W):
+  d = serpentine(H, W)
+  labels, st = assert_equals_oracle(d, K_SMALL, FRONTO, expect_labels=1, h_min=0.25, h_max=0.75, max_jump=0.01, min_pixels=1)
+  assert st['components'] == 1 and np.array_equal(labels > 0, d == 0.5)
+  assert st['rows'][0, 14] == 1 << 19 and st['height'][0] == 0.5
+
+
+def test_segment_depth_step_at_and_one_ulp_above_max_jump():
+  mj = np.float32(0.0078125)
+  for step, n_labels in ((mj, 1), (np.nextafter(np.float32(0.5) + mj, np.float32(1)) - np.float32(0.5), 2)):
+    d = np.full((6, 10), 0.5, np.float32)
+    d[:, 5:] = np.float32(0.5) + step
+    assert np.float32(d[0, 5] - d[0, 4]) == step and (step > mj) == (n_labels == 2)
+    labels, st = assert_equals_oracle(d, K_SMALL, FRONTO, expect_labels=n_labels, h_min=0.25, h_max=0.75, max_jump=float(mj), min_pixels=1)
+    assert st['n_pixels'].tolist() == ([60] if n_labels == 1 else [30, 30])
+    labels, st = assert_equals_oracle(d.T.copy(), K_SMALL, FRONTO, expect_labels=n_labels, h_min=0.25, h_max=0.75, max_jump=float(mj), min_pixels=1)
+
+
+def test_segment_height_thresholds_are_inclusive():
+  one = np.float32(1)
+  # depths whose heights 1 - d are exactly h_min, h_max, the fp32 value just below h_min that a depth can give, and one ulp above h_max
+  depths = [np.float32(0.75), np.float32(0.5), np.nextafter(np.float32(0.75), one), np.float32(0.5) - np.float32(2.0 ** -24)]
+  d = np.zeros((3, 9), np.float32)
+  d[1, [1, 3, 5, 7]] = depths
+  assert one - d[1, 1] == np.float32(0.25) and one - d[1, 3] == np.float32(0.5)
+  assert one - d[1, 5] == np.float32(0.25) - np.float32(2.0 ** -24) and one - d[1, 7] == np.nextafter(np.float32(0.5), one)
+  labels, st = assert_equals_oracle(d, K_SMALL, FRONTO, expect_labels=2, h_min=0.25, h_max=0.5, max_jump=0.01, min_pixels=1)
+  assert labels[1].tolist() == [0, 1, 0, 2, 0, 0, 0, 0, 0]
+
+
+def test_segment_minimum_size_and_numbering():
+  d = np.full((8, 12), 1.0, np.float32)
+  d[0, 0:2] = 0.5            # 2 pixels, first in raster order: dropped
+  d[2, 1:6] = 0.5            # exactly 5: kept
+  d[2, 8:12] = 0.5           # 4: dropped
+  d[5:7, 3:7] = 0.5          # 8: kept
+  labels, st = assert_equals_oracle(d, K_SMALL, FRONTO, expect_labels=2, h_min=0.25, h_max=0.75, max_jump=0.01, min_pixels=5)
+  assert st['components'] == 4 and st['n_pixels'].tolist() == [5, 8] and st['lowest_pixel'].tolist() == [2 * 12 + 1, 5 * 12 + 3]
+  assert (labels[2, 1:6] == 1).all() and (labels[5:7, 3:7] == 2).all() and (labels > 0).sum() == 13
+  assert st['bbox'].tolist() == [[2, 1, 2, 5], [5, 3, 6, 6]]
+
+
+@pytest.mark.parametrize('H,W', [(72, 96), (1, 200), (200, 1), (3, 130)])
+def test_segment_degenerate_and_thin_frames(H, W):
+  kw = dict(h_min=0.25, h_max=0.75, max_jump=0.01, min_pixels=1)
+  for dead in (np.full((H, W), 1.0, np.float32), np.zeros((H, W), np.float32)):      # all on the plane; all invalid
+    labels, st = assert_equals_oracle(dead, K_SMALL, FRONTO, expect_labels=0, **kw)
+    assert st['components'] == 0 and (labels == 0).all() and len(st['label']) == 0
+  labels, st = assert_equals_oracle(np.full((H, W), 0.5, np.float32), K_SMALL, FRONTO, expect_labels=1, **kw)
+  assert (labels == 1).all() and st['n_pixels'].tolist() == [H * W]
+  runs = np.full((H, W), 1.0, np.float32)
+  runs.ravel()[np.arange(H * W) % 7 < 4] = 0.5      # runs of 4 with gaps of 3 along the raster: they cross every wave boundary
+  assert_equals_oracle(runs, K_SMALL, FRONTO, **kw)
+  assert_equals_oracle(runs, K_SMALL, FRONTO, **dict(kw, min_pixels=5))
+
+
+@pytest.mark.parametrize('H,W', [(72, 96), (53, 37), (130, 67)])
+def test_segment_random_levels(H, W):
+  """Hundreds of winding components of every size: the union-find against scipy's components, pixel for pixel."""
+  d = random_levels(H, W, H + W)
+  plane = np.array([0.0, 0, -1, 1.5])
+  labels, st = assert_equals_oracle(d, K_SMALL, plane, h_min=0.1, h_max=1.2, max_jump=0.02, min_pixels=1)
+  assert st['components'] == labels.max() > 100
+  labels, st = assert_equals_oracle(d, K_SMALL, plane, h_min=0.1, h_max=1.2, max_jump=0.02, min_pixels=6)
+  assert 0 < labels.max() < st['components']
+  # without the gate everything usable above the plane that touches is one piece
+  assert_equals_oracle(d, K_SMALL, plane, h_min=0.1, h_max=1.2, max_jump=1.0, min_pixels=1)
+
+
+# ---- 4. determinism --------------------------------------------------------------------------------------------------------------------
+def test_segment_is_deterministic_and_independent_of_the_batch(tables):
+  from foundationpose_amd.segment import segment_on_plane
+  K = tables[35]['K']
+  blobs = random_levels(72, 96, 11)
+  views = [(tables[35]['depth'], tables[35]['plane']), (tables[60]['depth'], tables[60]['plane']), (blobs, np.array([0.0, 0, -1, 1.6]))]
+  kw = dict(h_min=0.008, h_max=1.2, max_jump=0.02, min_pixels=3)
+  alone = [segment_on_plane(d, K, p, **kw) for d, p in views]
+  again = [segment_on_plane(d, K, p, **kw) for d, p in views]
+  for (la, sa), (lb, sb) in zip(alone, again):
+    assert np.array_equal(la, lb) and np.array_equal(sa['rows'], sb['rows'])
+  assert len(alone[2][1]['label']) > 20      # the random map has many components
+  for shift in range(3):
+    order = [(i + shift) % 3 for i in range(3)]
+    labels, stats = segment_on_plane(np.stack([views[i][0] for i in order]), K, np.stack([views[i][1] for i in order]), **kw)
+    for slot, i in enumerate(order):
+      assert np.array_equal(labels[slot], alone[i][0]) and np.array_equal(stats[slot]['rows'], alone[i][1]['rows'])
+      assert stats[slot]['components'] == alone[i][1]['components']
+
+
+# ---- 5. meaning, without the oracle ------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('angle', [35, 60])
+def test_plane_and_segments_of_the_analytic_scene_are_the_true_ones(tables, angle):
+  """Purity is a condition, not a measurement.  Coverage with these spheres and this camera from the numpy rule alone
+  (tests/segment_oracle.py on the CPU): 1.0, 1.0, 1.0 at 35 degrees and 0.991, 1.0, 1.0 at 60; the bound 0.95 is a cap chosen before
+  that, not a measured tolerance."""
+  from foundationpose_amd import Utils as U
+  sc = tables[angle]
+  plane, info = U.fit_plane(sc['depth'], sc['K'])
+  assert np.arccos(min(1.0, float(plane[:3] @ sc['plane'][:3]))) < 1e-4 and abs(plane[3] - sc['plane'][3]) < 1e-5
+  assert abs(np.linalg.norm(plane[:3]) - 1) < 1e-12 and info['inliers'].shape == (2,) and info['inliers'][-1] > 6000
+  labels, st = U.segment_on_plane(sc['depth'], sc['K'], plane, max_jump=0.02, **SEG)
+  assert labels.max() == 3 == len(st['label'])
+  owners = []
+  for k in (1, 2, 3):
+    inside = np.unique(sc['gt'][labels == k])
+    assert len(inside) == 1 and inside[0] > 0, f'label {k} is not pure: it holds pixels of {inside.tolist()}'
+    owners.append(int(inside[0]))
+  assert sorted(owners) == [1, 2, 3]
+  for k, s in zip((1, 2, 3), owners):
+    cover = float(((labels == k) & (sc['gt'] == s)).sum()) / float((sc['gt'] == s).sum())
+    print(f'angle {angle}: sphere {s} covered {cover:.4f}')
+    assert cover >= 0.95
+  # the statistics mean what they say: the centroid lies inside its sphere's bounds, the height is below the sphere's top
+  for i, s in enumerate(owners):
+    assert (st['bounds'][i, 0] <= st['centroid'][i]).all() and (st['centroid'][i] <= st['bounds'][i, 1]).all()
+    assert 0 < st['height'][i] <= 2 * (0.05, 0.04, 0.06)[s - 1] + 1e-4
+
+
+# ---- 6. fit_plane ------------------------------------------------------------------------------------------------------------------------
+def test_fit_plane_is_the_host_solve_of_the_oracle_moments(tables):
+  from foundationpose_amd import Utils as U
+  sc = tables[60]
+  dev_depth = torch.as_tensor(sc['depth'], device='cuda')
+  plane, info = U.fit_plane(dev_depth, sc['K'], tol=0.004, n_hyp=256, seed=3, refits=2)
+  want = O.fit_plane(sc['depth'], sc['K'], tol=0.004, n_hyp=256, seed=3, refits=2)
+  assert plane.dtype == np.float64 and np.abs(plane - want).max() <= 1e-12 * np.abs(want).max()
+  trip = np.random.RandomState(3).randint(0, 72 * 96, (256, 3))
+  p, c, b = O.plane_score(sc['depth'], sc['K'], trip, 0.004)
+  assert np.array_equal(info['counts'], c) and info['best'] == b and np.array_equal(info['hypothesis_plane'], p[b].astype(np.float64))
+  assert info['eigenvalues'][0] < 1e-6 * info['eigenvalues'][1]
+  again, _ = U.fit_plane(sc['depth'], sc['K'], tol=0.004, n_hyp=256, seed=3, refits=2)
+  assert np.array_equal(bits(again), bits(plane))
+  both, binfo = U.fit_plane(np.stack([tables[35]['depth'], sc['depth']]), sc['K'], tol=0.004, n_hyp=256, seed=3)      # a batch
+  assert both.shape == (2, 4) and np.array_equal(bits(both[1]), bits(plane)) and binfo['counts'].shape == (2, 256)
+  with pytest.raises(ValueError):
+    U.fit_plane(np.zeros((72, 96), np.float32), sc['K'])
+
+
+# ---- 7. integration ------------------------------------------------------------------------------------------------------------------------
+def _estimator(mesh, refiner, scorer):
+  from foundationpose_amd.estimater import FoundationPose
+  np.random.seed(0)
+  return FoundationPose(model_pts=mesh.vertices, model_normals=mesh.vertex_normals, mesh=mesh, refiner=refiner, scorer=scorer)
+
+
+def test_tracker_segment_feeds_register():
+  """Three bottles of clearly different size (0.5, 0.8 and 1.15 of the synthetic mustard bottle) standing on a tilted analytic table."""
+  from foundationpose_amd import Utils as U
+  from foundationpose_amd import synthetic as S
+  from foundationpose_amd.config import REFINE_DEFAULT, SCORE_DEFAULT
+  from foundationpose_amd.predict_pose_refine import PoseRefinePredictor
+  from foundationpose_amd.predict_score import ScorePredictor
+  from foundationpose_amd.tracking import MultiObjectTracker
+  from tests import cases
+  H, W, K = 480, 640, S.YCB_K
+  refiner = PoseRefinePredictor(state_dict=S.make_refine_state_dict(cases.REFINE_SEED, head_gain=cases.GAIN_CHAIN), cfg=REFINE_DEFAULT)
+  ssd = S.make_score_state_dict(cases.SCORE_SEED)      # spread the seeded scores, as tests/test_gpu_register_objects.py does
+  ssd['linear.weight'] = ssd['linear.weight'] * 3.0e4
+  ssd['linear.bias'] = ssd['linear.bias'] * 3.0e4 - 3.0e4 * 0.0795
+  scorer = ScorePredictor(state_dict=ssd, cfg=SCORE_DEFAULT)
+  base = S.make_mustard_mesh(seed=0, n_theta=48, n_z=42)
+  scales = (0.8, 1.15, 0.5)
+  ests = [_estimator(S.SimpleMesh(base.vertices * s, base.faces, vertex_colors=base.visual.vertex_colors), refiner, scorer) for s in scales]
+  a = np.deg2rad(50.0)
+  n, p0 = np.array([0.0, -np.cos(a), -np.sin(a)]), np.array([0.0, 0.09, 0.8])
+  e1, e2 = np.array([1.0, 0, 0]), np.array([0.0, -np.sin(a), np.cos(a)])
+  poses = []
+  for (u, w), s, e in zip(((-0.15, 0.0), (0.0, 0.04), (0.14, -0.02)), scales, ests):
+    p = np.eye(4)
+    p[:3, 0], p[:3, 1], p[:3, 2] = e1, e2, n                                       # the bottle's axis along the table's normal
+    p[:3, 3] = p0 + u * e1 + w * e2 + (0.0955 * s) * n                             # its bottom on the table
+    poses.append(p @ np.linalg.inv(e.get_tf_to_centered_mesh().cpu().numpy().astype(np.float64)))      # pose of the centred mesh
+  col, row = np.meshgrid(np.arange(W, dtype=np.float64), np.arange(H, dtype=np.float64))
+  ray = np.stack([(col - K[0, 2]) / K[0, 0], (row - K[1, 2]) / K[1, 1], np.ones_like(col)], -1)
+  table = (n @ p0) / (ray @ n)
+  out = U.scene_instances(K, H, W, [e.mesh_tensors for e in ests], np.stack(poses), want=('depth', 'owner'))
+  obj, owner = out['depth'].cpu().numpy(), out['owner'].cpu().numpy()
+  depth = np.where(obj > 0, obj, table).astype(np.float32)
+  vs, us = np.meshgrid(np.arange(H), np.arange(W), indexing='ij')
+  rgb = np.stack([128 + 90 * np.sin(us * 0.07) * np.cos(vs * 0.05), 120 + 80 * np.sin(us * 0.031 + vs * 0.043), 100 + 60 * np.cos(vs * 0.09)], -1)
+  rgb = np.where((owner >= 0)[..., None], rgb[::-1, ::-1], rgb).astype(np.uint8)
+
+  tracker = MultiObjectTracker(ests)
+  label_image, labels = tracker.segment(depth, K)
+  assert torch.is_tensor(label_image) and label_image.is_cuda and label_image.dtype == torch.int32 and tuple(label_image.shape) == (H, W)
+  img = label_image.cpu().numpy()
+  assert len(set(labels)) == 3 and min(labels) >= 1
+  for o, lab in enumerate(labels):      # the segment named for object o lies on object o and holds most of it
+    assert (owner[img == lab] == o).all(), f'object {o}: label {lab} holds pixels of {np.unique(owner[img == lab]).tolist()}'
+    assert (img[owner == o] == lab).mean() > 0.8
+  assert tracker.segments['cost'].shape[0] == 3
+  want, _ = U.assign_segments(tracker.segments['stats'], [float(e.diameter) for e in ests])
+  assert want == labels
+
+  got = tracker.register(rgb, depth, K, label_image, iteration=1, labels=labels)
+  twins = []
+  for e in ests:
+    import copy
+    t = copy.copy(e)
+    t._track_ws = {}
+    t.pose_last = t.poses = t.scores = t.best_id = None
+    twins.append(t)
+  ref = MultiObjectTracker(twins).register(rgb, depth, K, [img == lab for lab in labels], iteration=1)
+  assert got.shape == (3, 4, 4) and np.isfinite(got).all() and np.array_equal(got, ref)
+  for x, y in zip(ests, twins):
+    assert torch.equal(x.poses, y.poses) and torch.equal(x.scores, y.scores)
+
+
+def test_segment_views_and_reconstruct_object():
+  from foundationpose_amd.reconstruct import reconstruct_object, segment_views
+  scenes = [O.analytic_table(a) for a in (35, 45, 55)]
+  views = dict(depths=np.stack([s['depth'] for s in scenes]), K=scenes[0]['K'], cam_in_obs=np.stack([s['cam_in_ob'] for s in scenes]))
+  out, info = segment_views(dict(views), keep='central', max_jump=0.02, **SEG)
+  assert out['masks'].shape == (3, 72, 96) and out['masks'].dtype == np.uint8 and info['empty'] == []
+  for v, s in enumerate(scenes):      # sphere 2 stands in the middle of the image
+    m = out['masks'][v] != 0
+    # pure, exactly the restated rule's segment (below), and most of the sphere: at this resolution the rule itself loses limb pixels
+    # of a 66-pixel sphere (the numpy rule alone: 62 of 66 at 45 degrees), so the share asked here is a half, not test 5's 0.95
+    assert (s['gt'][m] == 2).all() and m.sum() >= 0.5 * (s['gt'] == 2).sum()
+    want, rows, _ = O.segment(s['depth'], s['K'], info['planes'][v], max_jump=0.02, **SEG)
+    assert np.array_equal(m, want == info['label'][v])
+  big, binfo = segment_views(dict(views), keep='largest', max_jump=0.02, **SEG)
+  for v, s in enumerate(scenes):      # sphere 3 is the largest
+    assert (s['gt'][big['masks'][v] != 0] == 3).all()
+  none, ninfo = segment_views(dict(views), min_pixels=5000)
+  assert ninfo['empty'] == [0, 1, 2] and not none['masks'].any()
+  # a central object large enough for the default parameters (at least 200 pixels at 96 x 72)
+  scenes = [O.analytic_table(a, radii=(0.04, 0.09, 0.04)) for a in (35, 45, 55)]
+  views = dict(depths=np.stack([s['depth'] for s in scenes]), K=scenes[0]['K'], cam_in_obs=np.stack([s['cam_in_ob'] for s in scenes]))
+  mesh = reconstruct_object(views, segment=True, voxel_size=0.004)
+  assert len(mesh.vertices) > 50 and len(mesh.faces) > 50
+  assert 'masks' not in views      # the caller's dict is left as it was
+
+
+# ---- 8. argument checks ------------------------------------------------------------------------------------------------------------------
+def test_invalid_arguments_return_einval_and_launch_nothing(tables):
+  from foundationpose_amd import _lib
+  from foundationpose_amd._lib import lib, ptr, stream_ptr
+  dev = torch.device('cuda')
+  ctx = _lib.Context.get(dev)
+  sc = tables[35]
+  H, W = sc['depth'].shape
+  depth = torch.as_tensor(sc['depth'], device=dev)
+  K, Kbad = np.ascontiguousarray(sc['K']), np.ascontiguousarray(sc['K'] * [[0, 1, 1], [1, 1, 1], [1, 1, 1]])
+  plane, zero_n, nan_p = (np.ascontiguousarray(np.asarray(p, dtype=np.float64)[None]) for p in (sc['plane'], [0, 0, 0, 1], [0, np.nan, 1, 1]))
+  trip = np.random.RandomState(0).randint(0, H * W, (1, 8, 3)).astype(np.int32)
+  hp, hc, hb = np.full((1, 8, 4), 7, np.float32), np.full((1, 8), 7, np.int32), np.full((1,), 7, np.int32)
+  sums, counts = np.full((1, 10), 7.0), np.full((1, 2), 7, np.int32)
+  labels = torch.full((1, H, W), 7, dtype=torch.int32, device=dev)
+  st = stream_ptr(dev)
+  E = _lib.FP_EINVAL
+
+  def score(depth=depth, n=1, H=H, W=W, K=K, zfar=100.0, t=trip, nh=8, tol=0.004):
+    return lib().fp_plane_score(ctx.handle, ptr(depth), None, n, H, W, ptr(K), zfar, ptr(t), nh, tol, ptr(hp), ptr(hc), ptr(hb), st)
+
+  def moments(depth=depth, n=1, H=H, W=W, K=K, zfar=100.0, p=plane, tol=0.004):
+    return lib().fp_plane_moments(ctx.handle, ptr(depth), None, n, H, W, ptr(K), zfar, ptr(p), tol, ptr(sums), st)
+
+  def count(depth=depth, n=1, H=H, W=W, K=K, zfar=100.0, p=plane, h_min=0.008, h_max=0.5, jump=0.02, min_pixels=20):
+    return lib().fp_depth_segment_count(ctx.handle, ptr(depth), None, n, H, W, ptr(K), zfar, ptr(p), h_min, h_max, jump, min_pixels, ptr(counts), st)
+
+  shared = [dict(depth=None), dict(K=None), dict(H=0), dict(W=0), dict(n=-1), dict(n=65), dict(K=Kbad), dict(zfar=0.0), dict(zfar=1001.0)]
+  for fn, own in ((score, [dict(tol=0.0), dict(nh=-1), dict(nh=1025), dict(t=None)]),
+                  (moments, [dict(tol=-1.0), dict(p=None), dict(p=zero_n), dict(p=nan_p)]),
+                  (count, [dict(jump=0.0), dict(h_min=0.5, h_max=0.4), dict(min_pixels=0), dict(p=None), dict(p=zero_n), dict(p=nan_p)])):
+    for kw in shared + own:
+      assert fn(**kw) == E and lib().fp_last_error(), (fn.__name__, kw)
+  torch.cuda.synchronize()
+  assert (hp == 7).all() and (hc == 7).all() and (hb == 7).all() and (sums == 7).all() and (counts == 7).all()
+  # write: only after a count, with that count's maps and its number of kept components
+  assert count() == 0 and counts[0].tolist() == [O.segment(sc['depth'], K, sc['plane'], max_jump=0.02, **SEG)[2], 3]
+  rows = torch.full((3, 16), 7, dtype=torch.int64, device=dev)
+  write = lambda d=depth, n=1, Hh=H, Ww=W, lab=labels, k=3: lib().fp_depth_segment_write(ctx.handle, ptr(d), n, Hh, Ww, ptr(lab), ptr(rows), k, st)
+  for kw in (dict(d=depth.clone()), dict(Hh=W, Ww=H), dict(k=2), dict(k=4), dict(lab=None), dict(n=2)):
+    assert write(**kw) == E and lib().fp_last_error(), kw
+  torch.cuda.synchronize()
+  assert bool((labels == 7).all()) and bool((rows == 7).all())
+  assert count() == 0 and write() == 0
+  torch.cuda.synchronize()
+  assert np.array_equal(labels[0].cpu().numpy(), O.segment(sc['depth'], K, sc['plane'], max_jump=0.02, **SEG)[0])
+  # no views: nothing is written
+  assert count(n=0) == 0 and moments(n=0) == 0 and score(n=0) == 0
