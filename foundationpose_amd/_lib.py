@@ -113,6 +113,11 @@ FP_TSDF_PLANES = ('tsdf', 'weight', 'r', 'g', 'b', 'color_weight')      # FP_TSD
 FP_TSDF_ALIGN_TERMS = 29                                                  # fp_tsdf_align: doubles per view of h_sums
 FP_DEPTH_ALIGN_TERMS, FP_DEPTH_ALIGN_MAX_PAIRS = 29, 256                  # fp_depth_pairs_align: doubles per pair of h_sums, pairs per call
 FP_PHOTO_ALIGN_TERMS = 58                                                 # fp_depth_pairs_align_photo: doubles per pair of h_sums
+FP_POSE_ALIGN_TERMS, FP_POSE_ALIGN_MAX_POSES, FP_POSE_POLISH_MAX_ITERATIONS = 29, 1024, 64     # fp_pose_depth_align, fp_pose_gn_step, fp_pose_polish
+FP_POSE_STOP_FEW_PIXELS, FP_POSE_STOP_RESIDUAL_ROSE, FP_POSE_STOP_SINGULAR = 1, 2, 3      # fp_pose_state.stopped
+FP_POSE_STOP_REASONS = {1: 'too few valid pixels', 2: 'residual rose', 3: 'singular'}
+# fp_pose_state as a numpy record (136 bytes); all-zero bytes are a fresh record
+POSE_STATE_DTYPE = np.dtype([('fit_ms', '<f8'), ('fit_count', '<f8'), ('xi', '<f8', (6,)), ('prev_pose', '<f4', (16,)), ('stopped', '<i4'), ('steps', '<i4')])
 FP_PLANE_MAX_HYP, FP_PLANE_MOMENT_TERMS = 1024, 10                        # fp_plane_score, fp_plane_moments
 FP_SEGMENT_STATS, FP_SEGMENT_MAX_PIXELS = 16, 1 << 28                     # fp_depth_segment_write: int64 per kept component; pixels per call
 
@@ -191,6 +196,11 @@ _PROTOS = {
   'fp_view_intensity': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
   'fp_depth_pairs_align_photo': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_float, c_float,
                                          c_float, c_void_p, c_void_p, c_void_p]),
+  'fp_pose_depth_align': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_float, c_float,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+  'fp_pose_gn_step': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_double, c_int, c_int, c_void_p]),
+  'fp_pose_polish': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_double, c_double, c_int, c_float,
+                             c_float, c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
   'fp_plane_score': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_float, c_void_p, c_int, c_float, c_void_p, c_void_p,
                              c_void_p, c_void_p]),
   'fp_plane_moments': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_float, c_void_p, c_float, c_void_p, c_void_p]),

@@ -405,7 +405,7 @@ def _by_image(targets):
 
 
 def run_bop(dataset_dir, split, models, refiner, scorer, targets=None, iteration=5, mask_source='gt_visib', diameter='info',
-            max_objects=None, estimators=None, pad='bop'):
+            max_objects=None, estimators=None, pad='bop', polish=False):
   """Register every target of a BOP split: rows for write_results (pose float32 (4,4) in metres, score = the registration's best
   score, time = the wall time of the image's registrations, the same on every row of an image as BOP asks).
 
@@ -414,7 +414,10 @@ def run_bop(dataset_dir, split, models, refiner, scorer, targets=None, iteration
   ones); every instance of an image gets `FoundationPose.instance()` of its object's estimator, and the image's instances
   (image_instances) are registered by MultiObjectTracker(...).register(rgb, depth, K, masks, iteration) in groups of at most
   max_objects (None: FP_TRACK_MAX_OBJECTS), the image handed over as the numpy arrays BopScene reads.  An instance with fewer than 4
-  usable depth pixels in its mask gets register()'s fallback pose with score 0.  pad: the canvas of mask_source='gt_render'."""
+  usable depth pixels in its mask gets register()'s fallback pose with score 0.  pad: the canvas of mask_source='gt_render'.
+  polish (False; True; or a dict of MultiObjectTracker.polish's arguments): the registered poses of a group are then moved onto the
+  depth by geometry alone (fp_pose_polish), each against the normals of its own mask; the score stays the registration's.  Off, the
+  rows are what they were before the option existed."""
   from ._lib import FP_TRACK_MAX_OBJECTS
   from .tracking import MultiObjectTracker
   if not isinstance(models, BopModels):
@@ -439,6 +442,12 @@ def run_bop(dataset_dir, split, models, refiner, scorer, targets=None, iteration
       group = inst[g0:g0 + max_objects]
       ests = [estimators[o].instance() for o, _ in group]
       poses = MultiObjectTracker(ests).register(rgb, depth, K, [m for _, m in group], iteration=iteration)
+      if polish:
+        reg = [k for k, e in enumerate(ests) if e.pose_last is not None]
+        if reg:
+          got = MultiObjectTracker([ests[k] for k in reg]).polish(depth, K, masks=[group[k][1] for k in reg], **(polish if isinstance(polish, dict) else {}))
+          for j, k in enumerate(reg):
+            poses[k] = got[j]
       found += [(o, poses[k], float(e.scores[0]) if e.scores is not None else 0.0) for k, ((o, _), e) in enumerate(zip(group, ests))]
     elapsed = time.perf_counter() - t0
     rows += [dict(scene_id=scene_id, im_id=im_id, obj_id=o, score=s, pose=p, time=elapsed) for o, p, s in found]

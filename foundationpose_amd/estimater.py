@@ -233,6 +233,30 @@ class FoundationPose:
     self.pose_last = self.poses[0]
     return (self.pose_last @ self.get_tf_to_centered_mesh()).data.cpu().numpy()
 
+  def polish(self, depth, K, mask=None, poses=None, **kw):
+    """Move a pose onto the measured depth by geometry alone (Utils.polish_poses, a build extension; off unless called): point-to-plane
+    ICP between the centred mesh rendered at the pose and `depth` (H,W metres; `mask` as in polish_poses), every step on the device.
+    poses None: `pose_last` is polished, written back as a fresh (1,4,4) tensor - track_one continues from it - and the pose of the
+    original mesh is returned as register() returns it, np (4,4) float32.  poses (n,4,4), poses of the CENTRED mesh such as
+    `self.poses`: they are polished and returned as np (n,4,4) float32 poses of the original mesh; pose_last stays.  `self.polish_info`
+    holds polish_poses' info (valid, rendered, observed, rms, stopped, xi_last per pose): reported, not judged.  kw: polish_poses'
+    iterations, dist_max, cos_min, crop, crop_ratio, max_jump, min_pixels, damping."""
+    own = poses is None
+    if own:
+      if self.pose_last is None:
+        raise ValueError('FoundationPose.polish: no pose yet (pose_last is None): register first, or pass poses')
+      poses = self.pose_last
+    dev = self.mesh_tensors['pos'].device
+    if self.glctx is None:
+      self.glctx = U.RasterizeContext(dev)
+    p = torch.as_tensor(poses, device=dev, dtype=torch.float).reshape(-1, 4, 4)
+    got, self.polish_info = U.polish_poses(p, depth, K, mesh_tensors=self.mesh_tensors, mask=mask, mesh_diameter=self.diameter, glctx=self.glctx, **kw)
+    of_mesh = (got @ self.get_tf_to_centered_mesh().to(dev)).data.cpu().numpy()
+    if own:
+      self.pose_last = got[:1]
+      return of_mesh[0]
+    return of_mesh
+
   # ------------------------------------------------------------------ tracking
   def enable_track_graph(self, on=True):
     """Replay a tracking frame as ONE hipGraph: at 1 .. 64 hypotheses a frame is ~80 kernels of one workgroup round or less

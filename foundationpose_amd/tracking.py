@@ -167,6 +167,51 @@ class MultiObjectTracker:
     self._returned = [(e.pose_last, out[o].copy()) for o, e in enumerate(self.estimators)]
     return out
 
+  def polish(self, depth, K, masks=None, iterations=None, dist_max=None, cos_min=None, crop=160, crop_ratio=1.2, max_jump=0.01, min_pixels=None,
+             damping=None):
+    """Move every object's pose onto the measured depth by geometry alone (fp_pose_polish, a build extension; off unless called): np
+    (n_obj, 4, 4) float32, row o = est_o's polished pose @ get_tf_to_centered_mesh().  One fp_pose_polish per object, all on one stream,
+    and ONE synchronisation at the end.  masks: None, or a sequence of n_obj (H,W) masks (non-zero = may be the object) that enter each
+    object's observed normals and nothing else.  The other arguments are Utils.polish_poses' (None: its defaults).  Every estimator's
+    `pose_last` becomes a fresh (1,4,4) tensor; `self.polish_info[o]` holds object o's fit (valid, rendered, observed, rms, stopped,
+    xi_last): reported, not judged."""
+    from . import _lib, pose_icp as PI
+    self._need_poses('polish')
+    ests = self.estimators
+    if masks is not None and len(masks) != len(ests):
+      raise ValueError(f'MultiObjectTracker.polish: {len(masks)} masks for {len(ests)} objects')
+    pick = lambda v, d: d if v is None else v
+    iterations, dist_max, cos_min = pick(iterations, PI.DEFAULT_ITERATIONS), pick(dist_max, PI.DEFAULT_DIST_MAX), pick(cos_min, PI.DEFAULT_COS_MIN)
+    min_pixels, damping = pick(min_pixels, PI.DEFAULT_MIN_PIXELS), pick(damping, PI.DEFAULT_DAMPING)
+    ctx = ests[0].refiner.ctx
+    dev = ests[0].mesh_tensors['pos'].device
+    depth = torch.as_tensor(depth, device=dev).to(torch.float).contiguous()
+    H, W = depth.shape
+    self._last_frame = (int(H), int(W), K)
+    Kd, Kp = _lib.k_ptr(K)
+    n = len(ests)
+    if masks is None:
+      normals = [PI.depth_normals(depth, K, None, max_jump=max_jump, device=dev)[0]] * n
+    else:
+      m = torch.stack([torch.as_tensor(x, device=dev) != 0 for x in masks])
+      normals = list(PI.depth_normals(depth[None].expand(n, H, W).contiguous(), K, m, max_jump=max_jump, device=dev))
+    poses = torch.stack([torch.as_tensor(e.pose_last, device=dev, dtype=torch.float).reshape(4, 4) for e in ests]).contiguous()
+    state = PI.new_pose_state(n, dev)
+    sums = torch.zeros((n, _lib.FP_POSE_ALIGN_TERMS), dtype=torch.float64, device=dev)
+    counts = torch.zeros((n, 2), dtype=torch.int32, device=dev)
+    meshes = [_lib.device_mesh(ctx, e.mesh_tensors) for e in ests]
+    for o, e in enumerate(ests):
+      PI.enqueue_polish(ctx, meshes[o].handle, poses[o:o + 1], Kp, H, W, depth, normals[o], crop, crop_ratio, float(e.diameter), iterations, dist_max,
+                        cos_min, damping, min_pixels, state[o:o + 1], sums[o:o + 1], counts[o:o + 1])
+    of_mesh = torch.stack([poses[o] @ e.get_tf_to_centered_mesh().to(dev) for o, e in enumerate(ests)])
+    out = of_mesh.cpu().numpy()                              # the one synchronisation
+    info = PI.polish_info(state, counts)
+    self.polish_info = [{k: v[o] for k, v in info.items()} for o in range(n)]
+    for o, e in enumerate(ests):
+      e.pose_last = poses[o].clone().reshape(1, 4, 4)
+    self._returned = [(e.pose_last, out[o].copy()) for o, e in enumerate(ests)]
+    return out
+
   def _check_register(self, depth, masks, labels):
     """The argument checks of register(): (H, W, label image or None, list of masks or None); ValueError names the cause."""
     ests = self.estimators

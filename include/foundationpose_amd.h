@@ -809,6 +809,105 @@ int fp_depth_pairs_align_photo(fp_ctx *ctx, const float *d_depth, const float *d
                                const double *K, const double *cam_in_ob, const int32_t *pairs, int n_pairs, float dist_max, float cos_min,
                                float i_max, float *d_rows, double *h_sums, void *stream);
 
+/* ---- polishing object poses against depth: point-to-plane ICP between a MODEL at a pose and the depth of the frame it is seen in, with
+ *      projective association, linearised for N poses in one launch, stepped on the device and looped without the host
+ *      (csrc/pose_icp.hip).  The aligners above move cameras against other depth maps or a volume; this one moves an object pose onto
+ *      the measured surface by geometry alone.  Number format and ordering conventions are those of fp_depth_pairs_align: fp32, not
+ *      contracted, every operation in the written order, every condition written as "unless" so that a NaN skips, pixel index
+ *      row W + col, back-projection q of a depth d at (row, col) = ((((float)col - cx) / fx) d, (((float)row - cy) / fy) d, d).
+ *      tests/pose_icp_oracle.py restates everything below in numpy and Python floats.
+ *      Linearisation.  fp_pose_depth_align takes, all on the device: d_xyz and d_normal (N,h,w,3) fp32 - the camera-space maps fp_render
+ *      writes for the N poses, at full frame or through d_bbox2d crops, background 0 (any maps of that meaning will do: the rule looks at
+ *      nothing else of the model); the observed d_depth (H,W) and its d_normals (H,W,4) of fp_depth_normals, 16-byte aligned - a mask
+ *      enters there and nowhere else; d_poses (N,16) fp32 row-major, of which only the origin c = (pose[3], pose[7], pose[11]) is read.
+ *      K (3,3) float64 HOST.  Both normal maps face the camera: n.z < 0 on a fronto-parallel surface (fp_render's normal is the outward
+ *      vertex normal rotated into the camera frame; tests/test_gpu_pose_icp.py checks the sign on a sphere).  Per pose i and map pixel k:
+ *        y = xyz[i,k];  nm = normal[i,k]
+ *        skip unless y.z >= 0.001                                                        "rendered" counts the pixels that pass
+ *        u = (fx y.x) / y.z + cx,  v = (fy y.y) / y.z + cy;   cf = floorf(u + 0.5f),  rf = floorf(v + 0.5f)
+ *        skip unless 0 <= cf <= W-1 and 0 <= rf <= H-1 (compared as floats);   n4 = normals[rf,cf];   skip unless n4.w != 0
+ *        q = the back-projection of depth[rf,cf] at (rf, cf);   n = n4.xyz;   e = y - q  "observed" counts the pixels that got here
+ *        skip unless (e.x e.x + e.y e.y) + e.z e.z < dist_max dist_max
+ *        skip unless (nm.x n.x + nm.y n.y) + nm.z n.z >= cos_min
+ *        r = (n.x e.x + n.y e.y) + n.z e.z                                               the point-to-plane residual, metres
+ *        x = y - c
+ *        J = (n.x, n.y, n.z, x.y n.z - x.z n.y, x.z n.x - x.x n.z, x.x n.y - x.y n.x)
+ *      J is dr / dxi for R <- exp([w]) R, t <- t + tau with xi = (tau, w) in the camera frame, at fixed association: a twist about the
+ *      pose's own origin, not about the camera's.  With a mesh centred on its origin (estimater.py) that is the object's centre, which
+ *      keeps tau and w decoupled.
+ *      d_sums (N, FP_POSE_ALIGN_TERMS) float64 on the DEVICE: per pose the 29 terms of fp_tsdf_align's h_sums in the same order (the
+ *      upper triangle of J^T J row by row, J^T r, sum r r, the number of valid pixels), formed and added as csrc/gn_sums.h states: one
+ *      workgroup per (pose, tile of 1024 map pixels), 256 threads x 4 pixels, over a lane's pixels, over the wave by a butterfly, over
+ *      the waves in order, and by a second launch over the tiles in order.  No atomics: a pose's 29 numbers are bit-identical from run
+ *      to run, in any batch and at any index of it.  d_rows, when not null, (N,h,w,8) fp32 on the device, 16-byte aligned, gets
+ *      (J0 .. J5, r, 1) per pixel and eight zeros where the pixel was skipped.  d_counts, when not null, (N,2) int32 on the device:
+ *      the rendered and the observed pixels of each pose, exact (one pair per workgroup, added per pose by a small launch: no atomics).  h_sums, when not null, HOST (N,29): the call copies d_sums to it and
+ *      SYNCHRONISES the stream.  When h_sums is null nothing synchronises and nothing is read on the host: the partial sums live in the
+ *      context's arena (N tiles 232 bytes: 5.9 MB for 1024 maps of 160 x 160) and go back to it when the launches are queued, as the
+ *      scratch of fp_render does - with the arena reserved beforehand (fp_ctx_reserve) the call can sit in a captured graph.  At most
+ *      FP_POSE_ALIGN_MAX_POSES poses per call, maps of at most 2^24 pixels.
+ *      Step.  fp_pose_gn_step is one thread per pose, on the device and in double: d_sums as above, d_poses (N,16) in and out, d_state
+ *      N records of fp_pose_state (8-byte aligned; all-zero bytes are a fresh record).  Per pose, with s its 29 sums:
+ *        nothing unless state.stopped == 0                                               a stopped pose is never touched again
+ *        cnt = s[28].  Unless cnt >= min_pixels: stopped = FP_POSE_STOP_FEW_PIXELS; the pose goes back to prev_pose if steps > 0,
+ *          otherwise prev_pose = pose, fit_count = cnt, fit_ms = s[27] / cnt (0 if cnt is 0)
+ *        ms = s[27] / cnt.  If steps > 0 and ms > fit_ms: the pose goes back to prev_pose, stopped = FP_POSE_STOP_RESIDUAL_ROSE
+ *          (mean squares are compared, not their roots)
+ *        otherwise prev_pose = pose, fit_ms = ms, fit_count = cnt - the fit on record is always that of the pose the call returns -
+ *          and, unless closing:
+ *        A = the symmetric 6 x 6 of s[0 .. 20], b = s[21 .. 26];  lam = damping (((((A00 + A11) + A22) + A33) + A44) + A55)
+ *        M = A with M_aa = A_aa + lam;  g_a = -b_a.  M = L D L^T without square roots, for j = 0 .. 5:
+ *          d = M_jj, then for k = 0 .. j-1 in order d = d - (L_jk D_k) L_jk;  unless d > 0: stopped = FP_POSE_STOP_SINGULAR, the pose
+ *          stays as it is;  D_j = d;  for a = j+1 .. 5: v = M_aj, then for k = 0 .. j-1 v = v - (L_ak D_k) L_jk;  L_aj = v / d
+ *        z_a = g_a, then for k = 0 .. a-1 z_a = z_a - L_ak z_k                            (a = 0 .. 5)
+ *        xi_a = z_a / D_a, then for k = a+1 .. 5 xi_a = xi_a - L_ka xi_k                  (a = 5 .. 0);   state.xi = xi = (tau, w)
+ *        th = sqrt((w0 w0 + w1 w1) + w2 w2);  below 1e-4: ca = 1 - th th / 6, cb = 0.5 - th th / 24;  else ca = sin(th) / th,
+ *          cb = (1 - cos(th)) / (th th);  Kx = [w];  K2_ab = (Kx_a0 Kx_0b + Kx_a1 Kx_1b) + Kx_a2 Kx_2b
+ *        E_ab = ((a == b) + ca Kx_ab) + cb K2_ab;   R_ab <- (float)((E_a0 R_0b + E_a1 R_1b) + E_a2 R_2b);   t_a <- (float)(t_a + tau_a)
+ *          with R, t the fp32 pose widened; the last row is left alone;  steps = steps + 1
+ *      Nothing synchronises.  The host solve of the other aligners costs a synchronisation per iteration, which is wrong for 252
+ *      hypotheses and impossible inside the hipGraph of a tracking frame.
+ *      Loop.  fp_pose_polish enqueues iterations + 1 rounds on the stream: the crop windows of the poses (fp_crop_window_tf's launcher;
+ *      crop = the maps' side, 0 = full-frame maps and no windows), fp_render's launcher for xyz and normals, the linearisation, the
+ *      step - the first round starts every record of d_state afresh, whatever it held; the last has closing = 1.  No memset and no
+ *      atomic is among the launches.  d_poses (N,16) in and out.  d_sums and d_counts are
+ *      left as the last round wrote them (they are those of a pose that round may have taken back; the fit of the returned pose is in
+ *      d_state).  It does not synchronise and reads nothing on the host; the maps, the partial sums and the rasteriser's scratch live in
+ *      the arena as above.  It equals the same rounds issued through the public calls bit for bit.
+ *      Defaults of the Python layer (Utils.polish_poses), this project's own choice, fixed by the experiment with the restatement on the
+ *      CPU that DESIGN.md section 5 records: dist_max 0.010 m, cos_min 0.5, 8 iterations, damping 1e-9, min_pixels 100.
+ *      Limits.  Geometry only: symmetric objects and flat faces slide along their free directions (state.xi and the sums show it; the
+ *      damping only keeps the solve finite).  Projective association needs a start within dist_max of the surface.  Several map pixels
+ *      can land on one observed pixel when the crop magnifies; each counts.  No occlusion reasoning beyond the two gates.  The fit
+ *      numbers are reported, not judged.
+ *      FP_EINVAL, each checked before ctx is looked into: a null ctx, d_xyz, d_normal, d_depth, d_normals, K, d_poses, d_sums (align);
+ *      ctx, d_sums, d_poses, d_state (step); ctx, mesh, d_poses, K, d_depth, d_normals, d_state, d_sums (polish); a misaligned
+ *      d_normals, d_rows or d_state; N < 0 or above the cap (0 writes nothing); h, w, H or W < 1; a non-finite K or fx or fy not > 0;
+ *      dist_max not > 0; cos_min outside [-1, 1]; damping negative or not finite; min_pixels < 1; crop < 0; iterations outside
+ *      0 .. FP_POSE_POLISH_MAX_ITERATIONS; with a crop, crop_ratio or mesh_diameter not > 0. */
+#define FP_POSE_ALIGN_TERMS 29            /* doubles per pose of fp_pose_depth_align's d_sums */
+#define FP_POSE_ALIGN_MAX_POSES 1024      /* per call of the three */
+#define FP_POSE_POLISH_MAX_ITERATIONS 64
+#define FP_POSE_STOP_FEW_PIXELS 1         /* fp_pose_state.stopped: too few valid pixels */
+#define FP_POSE_STOP_RESIDUAL_ROSE 2      /* the mean square residual rose */
+#define FP_POSE_STOP_SINGULAR 3           /* a pivot of the damped system was not > 0 */
+typedef struct fp_pose_state {
+  double fit_ms, fit_count;               /* mean square residual and valid pixels at prev_pose */
+  double xi[6];                           /* the last step taken: (tau, w) */
+  float prev_pose[16];                    /* the pose before the last step; the returned pose once stopped or closed */
+  int32_t stopped;                        /* 0: active; else FP_POSE_STOP_* */
+  int32_t steps;                          /* steps taken */
+} fp_pose_state;
+int fp_pose_depth_align(fp_ctx *ctx, const float *d_xyz, const float *d_normal, int N, int h, int w, const float *d_depth,
+                        const float *d_normals, int H, int W, const double *K, const float *d_poses, float dist_max, float cos_min,
+                        float *d_rows, double *d_sums, int32_t *d_counts, double *h_sums, void *stream);
+int fp_pose_gn_step(fp_ctx *ctx, const double *d_sums, float *d_poses, fp_pose_state *d_state, int N, double damping, int min_pixels,
+                    int closing, void *stream);
+int fp_pose_polish(fp_ctx *ctx, const fp_mesh *mesh, float *d_poses, int N, const double *K, int H, int W, const float *d_depth,
+                   const float *d_normals, int crop, double crop_ratio, double mesh_diameter, int iterations, float dist_max,
+                   float cos_min, double damping, int min_pixels, fp_pose_state *d_state, double *d_sums, int32_t *d_counts,
+                   void *stream);
+
 /* ---- masks from depth: the objects standing on one supporting plane (csrc/segment.hip).  Find the plane (fp_plane_score over explicit
  *      three-pixel hypotheses, fp_plane_moments for the least-squares refit on the host), keep what stands above it, cut that into
  *      4-connected components (fp_depth_segment_count / _write).  Geometry only: no weights, no recognition; objects that touch without

@@ -25,11 +25,12 @@ def main():
   ap.add_argument('--diameter', choices=['info', 'exact', 'sampled'], default='info')
   ap.add_argument('--max-objects', type=int, default=None)
   ap.add_argument('--no-eval', action='store_true')
+  ap.add_argument('--polish', action='store_true', help='move the registered poses onto the depth by geometry alone (fp_pose_polish)')
   args = ap.parse_args()
   models = bop.BopModels(os.path.join(args.dataset_dir, 'models'))
   refiner, scorer = PoseRefinePredictor(weights_root=args.weights_root), ScorePredictor(weights_root=args.weights_root)
   rows = bop.run_bop(args.dataset_dir, args.split, models, refiner, scorer, iteration=args.iteration,
-                     diameter=None if args.diameter == 'sampled' else args.diameter, max_objects=args.max_objects)
+                     diameter=None if args.diameter == 'sampled' else args.diameter, max_objects=args.max_objects, polish=args.polish)
   bop.write_results(args.out_csv, rows)
   res = dict(n_rows=len(rows), csv=args.out_csv)
   if not args.no_eval:
