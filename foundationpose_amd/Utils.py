@@ -416,6 +416,21 @@ def _rgb_u8_on(colors, dev, who):
   return colors.reshape(len(colors), -1)[:, :3].contiguous()
 
 
+def _mesh_outputs(dev, V, nv, nf, normals, colors, want_map):
+  """The output tensors of a mesh *_write call for nv vertices and nf faces: (pos, normals | None, colors | None, faces, vertex_map | None)."""
+  o_pos = torch.empty((nv, 3), dtype=torch.float, device=dev)
+  o_nrm = None if normals is None else torch.empty((nv, 3), dtype=torch.float, device=dev)
+  o_col = None if colors is None else torch.empty((nv, 3), dtype=torch.uint8, device=dev)
+  o_faces = torch.empty((nf, 3), dtype=torch.int32, device=dev)
+  vmap = torch.empty((V,), dtype=torch.int32, device=dev) if want_map else None
+  return o_pos, o_nrm, o_col, o_faces, vmap
+
+
+def _mesh_output_ptrs(out):
+  """Their addresses as the *_write calls take them: NULL for an absent or empty tensor."""
+  return tuple(ptr(t) if t is not None and len(t) else None for t in out)
+
+
 def simplify_mesh_arrays(pos, faces, cell, normals=None, colors=None, return_map=False):
   """fp_mesh_simplify_count + fp_mesh_simplify_write on arrays: pos (V,3), faces (F,3) or None (a point cloud), normals (V,3) or None,
   colors (V,3) uint8 or None; numpy or torch, taken to the device as float32 / int32 / uint8.  Returns the device tensors (pos, normals |
@@ -424,15 +439,10 @@ def simplify_mesh_arrays(pos, faces, cell, normals=None, colors=None, return_map
   ctx = _lib.Context.get(dev)
   V, F = len(pos), len(faces)
   nv, nf = _simplify_count(ctx, dev, pos, faces, cell)
-  o_pos = torch.empty((nv, 3), dtype=torch.float, device=dev)
-  o_nrm = None if normals is None else torch.empty((nv, 3), dtype=torch.float, device=dev)
-  o_col = None if colors is None else torch.empty((nv, 3), dtype=torch.uint8, device=dev)
-  o_faces = torch.empty((nf, 3), dtype=torch.int32, device=dev)
-  vmap = torch.empty((V,), dtype=torch.int32, device=dev) if return_map else None
+  out = _mesh_outputs(dev, V, nv, nf, normals, colors, return_map)
   check(lib().fp_mesh_simplify_write(ctx.handle, ptr(pos) if V else None, ptr(normals), ptr(colors), V, ptr(faces) if F else None, F, float(cell),
-                                     ptr(o_pos) if nv else None, ptr(o_nrm) if nv else None, ptr(o_col) if nv else None,
-                                     ptr(o_faces) if nf else None, ptr(vmap) if V and return_map else None, nv, nf, stream_ptr(dev)))
-  return o_pos, o_nrm, o_col, o_faces, vmap
+                                     *_mesh_output_ptrs(out), nv, nf, stream_ptr(dev)))
+  return out
 
 
 def _simplify_count(ctx, dev, pos, faces, cell):
@@ -538,20 +548,14 @@ def _clean_arrays(pos, faces, normals, colors, keep, min_faces, min_fraction, wa
   ctx = _lib.Context.get(dev)
   V, F = len(pos), len(faces)
   C, kept, nv, nf = _components_count(ctx, dev, faces, V, keep, min_faces, min_fraction)
-  o_pos = torch.empty((nv, 3), dtype=torch.float, device=dev)
-  o_nrm = None if normals is None else torch.empty((nv, 3), dtype=torch.float, device=dev)
-  o_col = None if colors is None else torch.empty((nv, 3), dtype=torch.uint8, device=dev)
-  o_faces = torch.empty((nf, 3), dtype=torch.int32, device=dev)
-  vmap = torch.empty((V,), dtype=torch.int32, device=dev) if want_map else None
+  out = _mesh_outputs(dev, V, nv, nf, normals, colors, want_map)
   labels = torch.empty((V,), dtype=torch.int32, device=dev) if want_stats else None
   stats = torch.empty((C, 2), dtype=torch.int32, device=dev) if want_stats else None
   check(lib().fp_mesh_components_write(ctx.handle, ptr(pos) if V else None, ptr(normals), ptr(colors), V, ptr(faces) if F else None, F,
-                                       ptr(o_pos) if nv else None, ptr(o_nrm) if nv else None, ptr(o_col) if nv else None,
-                                       ptr(o_faces) if nf else None, ptr(vmap) if V and want_map else None,
-                                       ptr(labels) if V and want_stats else None, ptr(stats) if C and want_stats else None, nv, nf,
-                                       stream_ptr(dev)))
+                                       *_mesh_output_ptrs(out), ptr(labels) if V and want_stats else None,
+                                       ptr(stats) if C and want_stats else None, nv, nf, stream_ptr(dev)))
   info = dict(components=C, kept_components=kept, vertices_in=V, faces_in=F, vertices=nv, faces=nf)
-  return o_pos, o_nrm, o_col, o_faces, vmap, labels, stats, info
+  return (*out, labels, stats, info)
 
 
 def clean_mesh_arrays(pos, faces, normals=None, colors=None, keep='largest', min_faces=1, min_fraction=0.0, return_map=False):

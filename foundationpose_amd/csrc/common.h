@@ -94,13 +94,18 @@ struct PendingEvent {
   double flops;
 };
 
+inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// one thread per element
+inline dim3 grid_for(long long n, int threads = 256) { return dim3((unsigned)((n + threads - 1) / threads)); }
+
 // Bump arena over one hipMalloc; reset at the start of every forward.
 struct Arena {
   char *base = nullptr;
   size_t cap = 0, off = 0;
   int generation = 0;      // bumped whenever the arena is (re)allocated: captured hipGraphs hold its addresses
   void *take(size_t bytes) {
-    size_t o = (off + 255) & ~(size_t)255;
+    size_t o = align256(off);
     if (o + bytes > cap) return nullptr;
     off = o + bytes;
     return base + o;
@@ -116,6 +121,48 @@ struct ArenaScope {
   ~ArenaScope() { arena.off = off; }
   ArenaScope(const ArenaScope &) = delete;
   ArenaScope &operator=(const ArenaScope &) = delete;
+};
+
+// One device allocation that only grows: what a *_count call leaves in its context for the *_write call (mesh_simplify.hip,
+// mesh_components.hip, segment.hip).  A call lays its arrays out with BlobLayout, ensures the total, then takes its pointers with at():
+//   BlobLayout l;  const size_t o_a = l.put(a_bytes), o_b = l.put(b_bytes);
+//   FP_TRY(blob.ensure(l.bytes, "fp_xxx_count", "the state"));
+//   a = blob.at<A>(o_a), b = blob.at<B>(o_b);
+// A blob that is large enough is reused as it is, so the arrays of a smaller call lie at other offsets over stale contents: a call
+// initialises everything it reads.
+struct DevBlob {
+  char *base = nullptr;
+  size_t cap = 0;
+  // at least `bytes` bytes; `fn` and `what` name the caller and the contents in the out-of-memory message
+  int ensure(size_t bytes, const char *fn, const char *what) {
+    if (bytes <= cap) return FP_OK;
+    if (base) FP_CHECK_HIP(hipFree(base));      // synchronises: nothing of an earlier call still runs on it
+    base = nullptr, cap = 0;
+    if (hipMalloc((void **)&base, bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      base = nullptr;
+      fp_set_error("%s: out of device memory for %s (%zu bytes)", fn, what, bytes);
+      return FP_ENOMEM;
+    }
+    cap = bytes;
+    return FP_OK;
+  }
+  void release() {
+    if (base) (void)hipFree(base);
+    base = nullptr, cap = 0;
+  }
+  template <typename T>
+  T *at(size_t offset) const { return (T *)(base + offset); }
+};
+
+// offsets of consecutive arrays, each at a multiple of 256 bytes; `bytes` is the total so far
+struct BlobLayout {
+  size_t bytes = 0;
+  size_t put(size_t n) {
+    const size_t o = bytes;
+    bytes = align256(bytes + n);
+    return o;
+  }
 };
 
 struct fp_ctx {

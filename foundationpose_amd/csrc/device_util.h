@@ -73,6 +73,22 @@ __device__ __forceinline__ int wave_max(int v) { return wave_reduce(v, [](int a,
 __device__ __forceinline__ float wave_max(float v) { return wave_reduce(v, [](float a, float b) { return fmaxf(a, b); }); }
 __device__ __forceinline__ double wave_max(double v) { return wave_reduce(v, [](double a, double b) { return fmax(a, b); }); }
 
+// cnt[r] += 1 for every lane with `on`; called by all lanes of a wave together.  Integer adds: the grouping does not change the sum.
+// The counts of ONE component would be an add per lane to one address; a wave whose active lanes all name the same r adds their number
+// once instead.
+__device__ __forceinline__ void wave_add_one(int *cnt, int r, bool on) {
+  const unsigned long long act = __ballot(on);
+  if (act == 0) return;
+  const int first = __ffsll((long long)act) - 1;
+  const int lead = __shfl(r, first, 64);
+  const unsigned long long same = __ballot(on && r == lead);
+  if (same == act) {
+    if ((int)(threadIdx.x & 63) == first) atomicAdd(&cnt[lead], __popcll(act));
+  } else if (on) {
+    atomicAdd(&cnt[r], 1);
+  }
+}
+
 // sum over a workgroup of THREADS threads in a fixed order (the butterfly within each wave, then the waves in order), valid in thread 0.
 // `red` holds THREADS / 64 doubles of LDS; the first barrier lets the previous sum's `red` be read before it is written again.  The
 // butterfly is wave_sum written out: through the call hipcc orders the instructions of pose_errors_kernel (metrics.hip) differently.

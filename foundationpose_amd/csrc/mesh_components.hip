@@ -2,23 +2,21 @@
 // stated in include/foundationpose_amd.h and restated in numpy by tests/mesh_components_oracle.py.
 //
 // Everything written out is a function of the input alone, whatever order the lanes run in:
-//   * the components come from a lock-free union-find over parent[V] in global memory.  parent[v] <= v always: a ROOT (parent[r] == r)
-//     is only ever changed by a compare-and-swap from r to a smaller root, a non-root only by an atomicMin to one of its ancestors.
-//     Every value in the array only decreases, the trees only merge, and the root a component ends with is its lowest vertex index -
-//     WHICH unions won their compare-and-swap depends on the race, the final root does not;
+//   * the components come from the lock-free union-find of union_find.h over parent[V] in global memory, started from singletons; the
+//     invariants and the termination arguments are written there.  The root a component ends with is its lowest vertex index;
 //   * one flatten pass then makes parent[v] that lowest index for every vertex: the label;
 //   * components are numbered by an exclusive scan over "v is its own label" (scan_exclusive, scan.hip), as fp_mesh_simplify numbers
 //     its clusters; kept vertices and kept faces are numbered by two more scans, so both keep their input order;
 //   * the per-component counts are int32 atomic adds and the largest count an atomicMax: exact, so the order does not matter.  The
 //     lowest-numbered component among those of the largest count is an atomicMin over their labels.
-// No kernel waits for a value another workgroup is to write: a reader of parent[] that sees an old value sees an older ancestor, which
-// is still an ancestor, and the compare-and-swap decides.  One launch of hooks, one of compression; no host loop.
+// One launch of hooks, one of compression; no host loop.
 //
 // All kernels are one thread per vertex or face.  The hooks are scattered 4-byte atomics, which execute at the memory side: the pass is
 // bound by atomic requests, not by bytes.  The counts of a mesh that is ONE component would be F adds to one address; a wave whose
 // active lanes all name the same label adds their number once instead (wave_add_one).
 #include "common.h"
 #include "device_util.h"
+#include "union_find.h"
 
 #include <math.h>
 #include <algorithm>
@@ -41,52 +39,6 @@ struct CcRule {
   int min_faces, largest_only;
   float min_fraction;
 };
-
-__device__ __forceinline__ int cc_load(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// The root of x's tree as far as this thread can see, with path halving on the way up.
-// Terminates: a non-root's parent is strictly below it, so x strictly decreases and is bounded by 0.  The atomicMin writes an ancestor
-// of x over x's parent; x is not a root at that point (its parent differed from it, and a root never becomes one again), so it cannot
-// undo a hook, and the value only goes down.
-__device__ __forceinline__ int cc_find(int *parent, int x) {
-  for (;;) {
-    const int p = cc_load(&parent[x]);
-    if (p == x) return x;
-    const int g = cc_load(&parent[p]);
-    if (g != p) atomicMin(&parent[x], g);
-    x = g;
-  }
-}
-
-// Puts a and b into one tree: the larger of the two roots goes under the smaller one.
-// Terminates: every turn either returns or continues with a strictly smaller (hi, lo) pair.  A failed compare-and-swap means that
-// parent[hi] was no longer hi - another thread had ALREADY hooked that root under a smaller one, the progress is made, nothing is
-// waited for - and it returns that smaller value, from which the walk goes on.  Vertex indices are bounded below by 0.
-__device__ __forceinline__ void cc_unite(int *parent, int a, int b) {
-  for (;;) {
-    a = cc_find(parent, a);
-    b = cc_find(parent, b);
-    if (a == b) return;
-    const int hi = max(a, b), lo = min(a, b);
-    const int seen = atomicCAS(&parent[hi], hi, lo);
-    if (seen == hi) return;
-    a = seen, b = lo;      // seen < hi
-  }
-}
-
-// cnt[r] += 1 for every lane with `on`; called by all lanes of a wave together.  Integer adds: the grouping does not change the sum.
-__device__ __forceinline__ void wave_add_one(int *cnt, int r, bool on) {
-  const u64 act = __ballot(on);
-  if (act == 0) return;
-  const int first = __ffsll((long long)act) - 1;
-  const int lead = __shfl(r, first, 64);
-  const u64 same = __ballot(on && r == lead);
-  if (same == act) {
-    if ((int)(threadIdx.x & 63) == first) atomicAdd(&cnt[lead], __popcll(act));
-  } else if (on) {
-    atomicAdd(&cnt[r], 1);
-  }
-}
 
 __device__ __forceinline__ bool cc_kept(int n_faces, int label, const CcHead *head, CcRule rule) {
   const bool cand = n_faces >= 1 && n_faces >= rule.min_faces && (double)n_faces >= (double)rule.min_fraction * (double)head->max_faces;
@@ -115,18 +67,11 @@ __global__ __launch_bounds__(CC_THREADS) void cc_hook_kernel(const int32_t *__re
 
 // parent[v] becomes the lowest index of v's component (the roots are final: the hooks have all run); data[v] = 1 where v is that
 // lowest index, data[V] = 0 closes the scan; cnt[2 r] counts the vertices of the component of label r.
-// The walk needs no halving and writes nothing on the way; a neighbour's store of ITS label into a cell this walk passes through only
-// shortens the walk (the label is the root).
 __global__ __launch_bounds__(CC_THREADS) void cc_flatten_kernel(int V, int *parent, int *__restrict__ cnt, u64 *__restrict__ data) {
   const int v = blockIdx.x * CC_THREADS + threadIdx.x;
   int r = -1;
   if (v < V) {
-    r = v;
-    for (;;) {      // ends: parent[r] < r for a non-root
-      const int p = cc_load(&parent[r]);
-      if (p == r) break;
-      r = p;
-    }
+    r = cc_root(parent, v);
     __hip_atomic_store(&parent[v], r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   if (v <= V) data[v] = v < V && r == v ? 1 : 0;
@@ -227,16 +172,11 @@ __global__ __launch_bounds__(CC_THREADS) void cc_face_write_kernel(const int32_t
   for (int k = 0; k < 3; ++k) out_faces[(size_t)o * 3 + k] = (int32_t)vdata[faces[(size_t)f * 3 + k]];      // a kept face's vertices are all kept
 }
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-dim3 grid_for(long long n) { return dim3((unsigned)((n + CC_THREADS - 1) / CC_THREADS)); }
-
 }  // namespace
 
 // What fp_mesh_components_count leaves for fp_mesh_components_write: one allocation owned by the context, grown when a larger mesh arrives.
 struct fp_components_state {
-  char *blob = nullptr;
-  size_t blob_bytes = 0;
+  DevBlob blob;
   // views into blob
   CcHead *head = nullptr;
   int *parent = nullptr, *cnt = nullptr;      // the label of every vertex; {n_vertices, n_faces} at the label of every component
@@ -251,35 +191,21 @@ struct fp_components_state {
 void fp_components_state_free(fp_ctx *ctx) {
   fp_components_state *st = ctx->components;
   if (!st) return;
-  if (st->blob) (void)hipFree(st->blob);
+  st->blob.release();
   delete st;
   ctx->components = nullptr;
 }
 
 static int components_layout(fp_components_state *st, int V, int F) {
   const long long nscan = (long long)(V > F ? V : F) + 1;
-  size_t off = 0;
-  auto put = [&off](size_t bytes) {
-    const size_t o = off;
-    off = align256(off + bytes);
-    return o;
-  };
-  const size_t o_head = put(sizeof(CcHead)), o_parent = put((size_t)V * 4), o_cnt = put((size_t)V * 8), o_scan = put(((size_t)V + 1) * 8),
-               o_vdata = put(((size_t)V + 1) * 8), o_fdata = put(((size_t)F + 1) * 8), o_sums = put(scan_sums_words(nscan) * 8);
-  if (off > st->blob_bytes) {
-    if (st->blob) FP_CHECK_HIP(hipFree(st->blob));      // synchronises: nothing of an earlier call still runs on it
-    st->blob = nullptr, st->blob_bytes = 0;
-    if (hipMalloc((void **)&st->blob, off) != hipSuccess) {
-      (void)hipGetLastError();
-      fp_set_error("fp_mesh_components_count: out of device memory for the state of %d vertices and %d faces (%zu bytes)", V, F, off);
-      return FP_ENOMEM;
-    }
-    st->blob_bytes = off;
-  }
-  char *b = st->blob;
-  st->head = (CcHead *)(b + o_head);
-  st->parent = (int *)(b + o_parent), st->cnt = (int *)(b + o_cnt);
-  st->scan_v = (u64 *)(b + o_scan), st->vdata = (u64 *)(b + o_vdata), st->fdata = (u64 *)(b + o_fdata), st->sums = (u64 *)(b + o_sums);
+  BlobLayout l;
+  const size_t o_head = l.put(sizeof(CcHead)), o_parent = l.put((size_t)V * 4), o_cnt = l.put((size_t)V * 8), o_scan = l.put(((size_t)V + 1) * 8),
+               o_vdata = l.put(((size_t)V + 1) * 8), o_fdata = l.put(((size_t)F + 1) * 8), o_sums = l.put(scan_sums_words(nscan) * 8);
+  FP_TRY(st->blob.ensure(l.bytes, "fp_mesh_components_count", "the state"));
+  const DevBlob &b = st->blob;
+  st->head = b.at<CcHead>(o_head);
+  st->parent = b.at<int>(o_parent), st->cnt = b.at<int>(o_cnt);
+  st->scan_v = b.at<u64>(o_scan), st->vdata = b.at<u64>(o_vdata), st->fdata = b.at<u64>(o_fdata), st->sums = b.at<u64>(o_sums);
   return FP_OK;
 }
 

@@ -253,18 +253,12 @@ unsigned table_slots(long long n) {
   return cap;
 }
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-dim3 grid_for(long long n) { return dim3((unsigned)((n + MS_THREADS - 1) / MS_THREADS)); }
-
 }  // namespace
 
 // What fp_mesh_simplify_count leaves for fp_mesh_simplify_write: one allocation owned by the context, grown when a larger mesh arrives.
 struct fp_simplify_state {
-  char *blob = nullptr;
-  size_t blob_bytes = 0;
-  u64 *acc = nullptr;         // the attribute sums of fp_mesh_simplify_write: 80 bytes per output vertex
-  size_t acc_bytes = 0;
+  DevBlob blob;
+  DevBlob acc;                // the attribute sums of fp_mesh_simplify_write: 80 bytes per output vertex
   // views into blob
   MsHead *head = nullptr;
   u64 *vkeys = nullptr, *fkeys = nullptr, *scan_v = nullptr, *rdata = nullptr, *fdata = nullptr, *sums = nullptr;
@@ -281,8 +275,8 @@ struct fp_simplify_state {
 void fp_simplify_state_free(fp_ctx *ctx) {
   fp_simplify_state *st = ctx->simplify;
   if (!st) return;
-  if (st->blob) (void)hipFree(st->blob);
-  if (st->acc) (void)hipFree(st->acc);
+  st->blob.release();
+  st->acc.release();
   delete st;
   ctx->simplify = nullptr;
 }
@@ -290,30 +284,16 @@ void fp_simplify_state_free(fp_ctx *ctx) {
 static int simplify_layout(fp_simplify_state *st, int V, int F) {
   const unsigned vcap = table_slots(V), fcap = F > 0 ? table_slots(F) : 0;
   const long long nscan = (long long)(V > F ? V : F) + 1;
-  size_t off = 0;
-  auto put = [&off](size_t bytes) {
-    const size_t o = off;
-    off = align256(off + bytes);
-    return o;
-  };
-  const size_t o_head = put(sizeof(MsHead)), o_vkeys = put((size_t)vcap * 8), o_fkeys = put((size_t)fcap * 8), o_scan = put(((size_t)V + 1) * 8),
-               o_rdata = put(((size_t)V + 1) * 8), o_fdata = put(((size_t)F + 1) * 8), o_sums = put(scan_sums_words(nscan) * 8),
-               o_vlow = put((size_t)vcap * 4), o_flow = put((size_t)fcap * 4), o_cid = put((size_t)V * 4), o_fslot = put((size_t)F * 4);
-  if (off > st->blob_bytes) {
-    if (st->blob) FP_CHECK_HIP(hipFree(st->blob));      // synchronises: nothing of an earlier call still runs on it
-    st->blob = nullptr, st->blob_bytes = 0;
-    if (hipMalloc((void **)&st->blob, off) != hipSuccess) {
-      (void)hipGetLastError();
-      fp_set_error("fp_mesh_simplify_count: out of device memory for the tables of %d vertices and %d faces (%zu bytes)", V, F, off);
-      return FP_ENOMEM;
-    }
-    st->blob_bytes = off;
-  }
-  char *b = st->blob;
-  st->head = (MsHead *)(b + o_head);
-  st->vkeys = (u64 *)(b + o_vkeys), st->fkeys = (u64 *)(b + o_fkeys), st->scan_v = (u64 *)(b + o_scan), st->rdata = (u64 *)(b + o_rdata);
-  st->fdata = (u64 *)(b + o_fdata), st->sums = (u64 *)(b + o_sums);
-  st->vlow = (int *)(b + o_vlow), st->flow = (int *)(b + o_flow), st->cid = (int *)(b + o_cid), st->fslot = (int *)(b + o_fslot);
+  BlobLayout l;
+  const size_t o_head = l.put(sizeof(MsHead)), o_vkeys = l.put((size_t)vcap * 8), o_fkeys = l.put((size_t)fcap * 8), o_scan = l.put(((size_t)V + 1) * 8),
+               o_rdata = l.put(((size_t)V + 1) * 8), o_fdata = l.put(((size_t)F + 1) * 8), o_sums = l.put(scan_sums_words(nscan) * 8),
+               o_vlow = l.put((size_t)vcap * 4), o_flow = l.put((size_t)fcap * 4), o_cid = l.put((size_t)V * 4), o_fslot = l.put((size_t)F * 4);
+  FP_TRY(st->blob.ensure(l.bytes, "fp_mesh_simplify_count", "the tables"));
+  const DevBlob &b = st->blob;
+  st->head = b.at<MsHead>(o_head);
+  st->vkeys = b.at<u64>(o_vkeys), st->fkeys = b.at<u64>(o_fkeys), st->scan_v = b.at<u64>(o_scan), st->rdata = b.at<u64>(o_rdata);
+  st->fdata = b.at<u64>(o_fdata), st->sums = b.at<u64>(o_sums);
+  st->vlow = b.at<int>(o_vlow), st->flow = b.at<int>(o_flow), st->cid = b.at<int>(o_cid), st->fslot = b.at<int>(o_fslot);
   return FP_OK;
 }
 
@@ -417,26 +397,18 @@ extern "C" int fp_mesh_simplify_write(fp_ctx *ctx, const float *d_pos, const flo
   const uint8_t *col = d_out_colors ? d_colors : nullptr;
   const u64 *rdata = F > 0 ? st->rdata : nullptr;
   const size_t acc_bytes = (size_t)n_vertices * 64, need = acc_bytes + (size_t)n_vertices * 16;
-  if (need > st->acc_bytes) {
-    if (st->acc) FP_CHECK_HIP(hipFree(st->acc));
-    st->acc = nullptr, st->acc_bytes = 0;
-    if (hipMalloc((void **)&st->acc, need) != hipSuccess) {
-      (void)hipGetLastError();
-      fp_set_error("fp_mesh_simplify_write: out of device memory for the sums of %lld vertices", (long long)n_vertices);
-      return FP_ENOMEM;
-    }
-    st->acc_bytes = need;
-  }
-  unsigned *cacc = (unsigned *)((char *)st->acc + acc_bytes);
+  FP_TRY(st->acc.ensure(need, "fp_mesh_simplify_write", "the sums"));
+  u64 *acc = st->acc.at<u64>(0);
+  unsigned *cacc = st->acc.at<unsigned>(acc_bytes);
   if (n_vertices > 0 || d_out_vertex_map) {
-    if (need) FP_CHECK_HIP(hipMemsetAsync(st->acc, 0, need, s));
+    if (need) FP_CHECK_HIP(hipMemsetAsync(acc, 0, need, s));
     hipLaunchKernelGGL(ms_accumulate_kernel, grid_for(V), dim3(MS_THREADS), 0, s, d_pos, nrm, col, V, (const MsHead *)st->head, (const int *)st->cid,
-                       rdata, st->acc, cacc, d_out_vertex_map);
+                       rdata, acc, cacc, d_out_vertex_map);
     FP_CHECK_HIP(hipGetLastError());
   }
   if (n_vertices > 0) {
     hipLaunchKernelGGL(ms_vertex_write_kernel, grid_for(V), dim3(MS_THREADS), 0, s, d_pos, nrm, col, V, (const MsHead *)st->head,
-                       (const u64 *)st->scan_v, rdata, (const u64 *)st->acc, (const unsigned *)cacc, d_out_pos, d_out_normals, d_out_colors);
+                       (const u64 *)st->scan_v, rdata, (const u64 *)acc, (const unsigned *)cacc, d_out_pos, d_out_normals, d_out_colors);
     FP_CHECK_HIP(hipGetLastError());
   }
   if (n_faces > 0) {

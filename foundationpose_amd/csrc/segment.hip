@@ -9,14 +9,12 @@
 //     a lane keeps its PS_PIX points in registers, the planes arrive wave-uniformly from the table plane_hyp_kernel wrote;
 //   * the 10 moments take the way of gn_sums.h: a lane's pixels in order, the butterfly over the wave, the waves in order through LDS, the
 //     workgroup's own slot of a slab, gn_fold_kernel over the tiles in order.  No atomics;
-//   * the components come from the lock-free union-find of mesh_components.hip over parent[n_views H W] in global memory, and its argument
-//     holds here word for word: parent[i] <= i for every foreground pixel (background: -1, never followed), a ROOT is only ever changed
-//     by a compare-and-swap from r to a smaller root, a non-root only by an atomicMin to one of its ancestors, so every value only
-//     decreases and the root a component ends with is its lowest pixel index, whichever unions won.  The forest does not START as
-//     singletons: seg_init_kernel points every pixel at the first pixel of its horizontal run inside its wave (a ballot, no memory
-//     traffic), which is a forest of the same kind; seg_hook_kernel then joins a pixel with the one above it, and with the one to its
-//     left only where a run was cut by a wave's first lane.  One launch of hooks, one flatten pass, no host loop, and no kernel waits for
-//     a value another workgroup is to write;
+//   * the components come from the lock-free union-find of union_find.h over parent[n_views H W] in global memory; the invariants and
+//     the termination arguments are written there.  The members are the foreground pixels (background: -1, never passed in), and the
+//     root a component ends with is its lowest pixel index.  The forest does not START as singletons: seg_init_kernel points every
+//     pixel at the first pixel of its horizontal run inside its wave (a ballot, no memory traffic), which keeps parent[i] <= i;
+//     seg_hook_kernel then joins a pixel with the one above it, and with the one to its left only where a run was cut by a wave's
+//     first lane.  One launch of hooks, one flatten pass, no host loop;
 //   * components and kept components are numbered by ONE exclusive scan (scan_exclusive) of a word that carries "is a root" in its low
 //     half and "is a kept root" in its high half; the numbers of a view are differences against the word at the view's first pixel,
 //     so a view does not depend on its batch;
@@ -27,6 +25,7 @@
 #include "common.h"
 #include "device_util.h"
 #include "gn_sums.h"
+#include "union_find.h"
 
 #include <math.h>
 
@@ -212,32 +211,6 @@ __global__ __launch_bounds__(SEG_THREADS) void plane_moments_kernel(const float 
 
 // ---- fp_depth_segment_* -----------------------------------------------------------------------------------------------------------
 
-__device__ __forceinline__ int cc_load(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// cc_find / cc_unite of mesh_components.hip (the termination arguments are written there): the root of x's tree with path halving; the
-// larger of two roots goes under the smaller one by compare-and-swap.  x, a and b are foreground pixels: parent[] of them is >= 0.
-__device__ __forceinline__ int cc_find(int *parent, int x) {
-  for (;;) {
-    const int p = cc_load(&parent[x]);
-    if (p == x) return x;
-    const int g = cc_load(&parent[p]);
-    if (g != p) atomicMin(&parent[x], g);
-    x = g;
-  }
-}
-
-__device__ __forceinline__ void cc_unite(int *parent, int a, int b) {
-  for (;;) {
-    a = cc_find(parent, a);
-    b = cc_find(parent, b);
-    if (a == b) return;
-    const int hi = max(a, b), lo = min(a, b);
-    const int seen = atomicCAS(&parent[hi], hi, lo);
-    if (seen == hi) return;
-    a = seen, b = lo;      // seen < hi
-  }
-}
-
 // One thread per pixel of the batch, i = view H W + row W + col; a workgroup starts at a multiple of 64, so lane == i & 63.
 // parent[i] = -1 for background; for foreground the first pixel of the run of joined pixels that ends at i, as far as it lies in this
 // wave: i - 1 is in the same row when col > 0 and in the same wave when lane > 0.
@@ -275,20 +248,6 @@ __global__ __launch_bounds__(SEG_THREADS) void seg_hook_kernel(const float *__re
   if ((threadIdx.x & 63) == 0 && col > 0 && cc_load(&parent[i - 1]) >= 0 && fabsf(d - depth[i - 1]) <= max_jump) cc_unite(parent, i, i - 1);
 }
 
-// cnt[r] += 1 for every lane with `on`; called by all lanes of a wave together (wave_add_one of mesh_components.hip)
-__device__ __forceinline__ void wave_add_one(int *cnt, int r, bool on) {
-  const u64 act = __ballot(on);
-  if (act == 0) return;
-  const int first = __ffsll((long long)act) - 1;
-  const int lead = __shfl(r, first, 64);
-  const u64 same = __ballot(on && r == lead);
-  if (same == act) {
-    if ((int)(threadIdx.x & 63) == first) atomicAdd(&cnt[lead], __popcll(act));
-  } else if (on) {
-    atomicAdd(&cnt[r], 1);
-  }
-}
-
 // parent[i] becomes the lowest pixel of i's component (the roots are final: the hooks have all run); cnt[r] counts the pixels of root r
 __global__ __launch_bounds__(SEG_THREADS) void seg_flatten_kernel(int total, int *parent, int *__restrict__ cnt) {
   const int i = blockIdx.x * SEG_THREADS + threadIdx.x;
@@ -296,11 +255,7 @@ __global__ __launch_bounds__(SEG_THREADS) void seg_flatten_kernel(int total, int
   if (i < total) {
     r = cc_load(&parent[i]);
     if (r >= 0) {
-      for (;;) {      // ends: parent[r] < r for a non-root
-        const int p = cc_load(&parent[r]);
-        if (p == r) break;
-        r = p;
-      }
+      r = cc_root(parent, r);
       __hip_atomic_store(&parent[i], r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
@@ -387,10 +342,6 @@ __global__ __launch_bounds__(SEG_THREADS) void seg_label_kernel(const float *__r
     stats_atomics(stats + k * FP_SEGMENT_STATS, s);
   }
 }
-
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-dim3 grid_for(long long n) { return dim3((unsigned)((n + SEG_THREADS - 1) / SEG_THREADS)); }
 
 // the checks the four calls share, each before the first look into ctx
 int seg_check_frame(const char *fn, int n_views, int H, int W, const double *K, float zfar) {
@@ -492,8 +443,7 @@ extern "C" int fp_plane_moments(fp_ctx *ctx, const float *d_depth, const uint8_t
 
 // What fp_depth_segment_count leaves for fp_depth_segment_write: one allocation owned by the context, grown when a larger batch arrives.
 struct fp_segment_state {
-  char *blob = nullptr;
-  size_t blob_bytes = 0;
+  DevBlob blob;
   // views into blob
   int *head = nullptr, *parent = nullptr, *cnt = nullptr;      // {components, kept} per view; the label of every pixel; pixels at every root
   u64 *data = nullptr, *sums = nullptr;
@@ -509,33 +459,19 @@ struct fp_segment_state {
 void fp_segment_state_free(fp_ctx *ctx) {
   fp_segment_state *st = ctx->segment;
   if (!st) return;
-  if (st->blob) (void)hipFree(st->blob);
+  st->blob.release();
   delete st;
   ctx->segment = nullptr;
 }
 
 static int segment_layout(fp_segment_state *st, long long total) {
-  size_t off = 0;
-  auto put = [&off](size_t bytes) {
-    const size_t o = off;
-    off = align256(off + bytes);
-    return o;
-  };
-  const size_t o_head = put(FP_TSDF_MAX_VIEWS * 2 * sizeof(int)), o_parent = put((size_t)total * 4), o_cnt = put((size_t)total * 4),
-               o_data = put(((size_t)total + 1) * 8), o_sums = put(scan_sums_words(total + 1) * 8);
-  if (off > st->blob_bytes) {
-    if (st->blob) FP_CHECK_HIP(hipFree(st->blob));      // synchronises: nothing of an earlier call still runs on it
-    st->blob = nullptr, st->blob_bytes = 0;
-    if (hipMalloc((void **)&st->blob, off) != hipSuccess) {
-      (void)hipGetLastError();
-      fp_set_error("fp_depth_segment_count: out of device memory for the state of %lld pixels (%zu bytes)", total, off);
-      return FP_ENOMEM;
-    }
-    st->blob_bytes = off;
-  }
-  char *b = st->blob;
-  st->head = (int *)(b + o_head), st->parent = (int *)(b + o_parent), st->cnt = (int *)(b + o_cnt);
-  st->data = (u64 *)(b + o_data), st->sums = (u64 *)(b + o_sums);
+  BlobLayout l;
+  const size_t o_head = l.put(FP_TSDF_MAX_VIEWS * 2 * sizeof(int)), o_parent = l.put((size_t)total * 4), o_cnt = l.put((size_t)total * 4),
+               o_data = l.put(((size_t)total + 1) * 8), o_sums = l.put(scan_sums_words(total + 1) * 8);
+  FP_TRY(st->blob.ensure(l.bytes, "fp_depth_segment_count", "the state"));
+  const DevBlob &b = st->blob;
+  st->head = b.at<int>(o_head), st->parent = b.at<int>(o_parent), st->cnt = b.at<int>(o_cnt);
+  st->data = b.at<u64>(o_data), st->sums = b.at<u64>(o_sums);
   return FP_OK;
 }
 

@@ -139,6 +139,23 @@ def test_scan_block_boundaries():
   _check(V, faces, keep='largest')
 
 
+def test_one_context_serves_meshes_of_changing_size():
+  """One context, four count / write rounds - 4, 3 000, 4 and 9 002 vertices: the first allocation of the state, growth by free and
+  malloc, a big blob under a small layout (every offset moves, stale contents lie behind it) and growth again; the scan has 1, 3, 1
+  and 9 blocks.  Every round equals the restatement, and the tiny rounds are the same bits."""
+  from tests import util
+  tiny = (4, np.array([[3, 1, 2]], dtype=np.int32))                      # vertex 0 is named by no face
+  strip_v, strip_f = C.strip(2998, np.random.RandomState(41).permutation(3000))
+  soup_v, soup_f = C.soup(2834, 500, seed=43)
+  assert (strip_v, soup_v) == (3000, 9002)
+  rounds = [tiny, (strip_v, strip_f), tiny, (soup_v, soup_f)]
+  rule = dict(keep='all', min_faces=1)
+  with util.own_context():
+    got = [_check(V, faces, seed=V, **rule)[0] for V, faces in rounds]
+  _assert_same(got[2], got[0])
+  assert [len(g['stats']) for g in got] == [2, 1, 2, 2834 + 500]
+
+
 def test_empty_inputs():
   from foundationpose_amd import Utils as U
   pos = C.positions(5)[0]

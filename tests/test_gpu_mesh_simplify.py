@@ -104,6 +104,26 @@ def test_edge_cases():
   assert len(_device(tri, f, 0.0005)['pos']) == 4          # the context still works
 
 
+def test_one_context_serves_meshes_of_changing_size():
+  """One context, four count / write rounds - 4, 3 002, 4 and 9 002 vertices: the first allocation of the tables and of the sums, growth
+  by free and malloc, big blobs under a small layout (every offset moves, stale contents lie behind it) and growth again; the scan has
+  1, 3, 1 and 9 blocks.  Every round equals the restatement, and the tiny rounds are the same bits."""
+  from tests import util
+  rs = np.random.RandomState(61)
+  tiny, mid, big = [(v, f, n, rs.randint(0, 256, size=v.shape).astype(np.uint8)) for v, f, n in (M.lattice_sheet(2), M.uv_sphere(30, 100), M.uv_sphere(60, 150))]
+  rounds = [tiny, mid, tiny, big]
+  assert [len(r[0]) for r in rounds] == [4, 3002, 4, 9002]
+  cells = [0.001, 0.004, 0.001, 0.003]                                   # pitch 1.1 mm: the sheet keeps its 4 vertices
+  with util.own_context():
+    got = []
+    for (v, f, n, c), cell in zip(rounds, cells):
+      want = M.simplify(v, f, cell, n, c)
+      got.append(_device(v, f, cell, n, c))
+      _assert_same(got[-1], want)
+      assert 0 < len(want['faces']) <= len(f) and (len(v) == 4) == (len(want['pos']) == len(v))
+  _assert_same(got[2], got[0])
+
+
 def test_write_needs_its_own_fresh_count(mesh):
   from foundationpose_amd import _lib
   from foundationpose_amd._lib import lib, ptr, stream_ptr

@@ -225,6 +225,22 @@ def test_segment_random_levels(H, W):
   assert_equals_oracle(d, K_SMALL, plane, h_min=0.1, h_max=1.2, max_jump=1.0, min_pixels=1)
 
 
+def test_one_context_serves_frames_of_changing_size():
+  """One context, four count / write rounds - 3 x 5, 40 x 70, 3 x 5 and 48 x 130 pixels of random levels: the first allocation of the
+  state, growth by free and malloc, a big blob under a small layout (every offset moves, stale contents lie behind it) and growth again.
+  Widths above 64 give the left link at a wave's first lane work to do.  Every round equals the oracle, and the tiny rounds are the same
+  bits."""
+  from tests import util
+  tiny = random_levels(3, 5, 8)
+  frames = [tiny, random_levels(40, 70, 110), tiny, random_levels(48, 130, 178)]
+  plane = np.array([0.0, 0, -1, 1.5])
+  with util.own_context():
+    got = [assert_equals_oracle(d, K_SMALL, plane, h_min=0.1, h_max=1.2, max_jump=0.02, min_pixels=2) for d in frames]
+  assert np.array_equal(got[0][0], got[2][0]) and np.array_equal(got[0][1]['rows'], got[2][1]['rows'])
+  assert got[0][1]['components'] == got[2][1]['components'] > 0
+  assert [0 < lab.max() < st['components'] for lab, st in got[1::2]] == [True, True]      # kept and dropped components in the big frames
+
+
 # ---- 4. determinism --------------------------------------------------------------------------------------------------------------------
 def test_segment_is_deterministic_and_independent_of_the_batch(tables):
   from foundationpose_amd.segment import segment_on_plane

@@ -1,4 +1,5 @@
 """Shared builders for the parity tests (seeded synthetic scene, oracle handles)."""
+import contextlib
 import functools
 
 import numpy as np
@@ -81,3 +82,22 @@ def nearest_pose_error(got, want):
   order (a ranking by nearly tied scores) may differ."""
   got, want = np.asarray(got, dtype=np.float64).reshape(-1, 16), np.asarray(want, dtype=np.float64).reshape(-1, 16)
   return float(np.abs(got[:, None] - want[None]).max(-1).min(1).max())
+
+
+@contextlib.contextmanager
+def own_context():
+  """A context of its own in place of the device's shared one (_lib.Context.get) while the block runs: the first call in it is a first
+  allocation of whatever state the context keeps, whichever tests ran before.  Destroyed on the way out, which frees that state."""
+  from foundationpose_amd import _lib
+  idx = torch.cuda.current_device()
+  shared = _lib.Context._by_device.get(idx)
+  ctx = _lib.Context(idx)
+  _lib.Context._by_device[idx] = ctx
+  try:
+    yield ctx
+  finally:
+    if shared is None:
+      del _lib.Context._by_device[idx]
+    else:
+      _lib.Context._by_device[idx] = shared
+    assert _lib.lib().fp_ctx_destroy(ctx.handle) == 0
