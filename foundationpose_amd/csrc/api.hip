@@ -1361,69 +1361,36 @@ extern "C" int fp_register_objects(fp_ctx *ctx, fp_register_objects_args *a, voi
   return launch_register_rank(ro, hyp, scores, s);          // the call's last launch: the results land in the objects' buffers (pinned host: no copy)
 }
 
-int conv_ksplit(const ConvArgs &a, int num_cu);      // conv.hip
-
 // ---- building blocks ---------------------------------------------------------------------------------
-// one convolution launch on its own: fp16 NHWC output, no split, no post-add
-static ConvArgs conv_args(const void *d_in, const void *d_w, const float *d_bias, const void *d_res, void *d_out, int Nimg, int H, int W, int Cin,
-                          int Cout, int KH, int KW, int stride, int pad, int relu) {
-  ConvArgs a;
-  memset(&a, 0, sizeof(a));
-  a.in = (const f16 *)d_in;
-  a.w = (const f16 *)d_w;
-  a.bias = d_bias;
-  a.res = (const f16 *)d_res;
-  a.out = d_out;
-  a.Nimg = Nimg, a.H = H, a.W = W, a.Cin = Cin, a.Cout = Cout, a.KH = KH, a.KW = KW, a.stride = stride, a.pad = pad;
-  a.Ho = (H + 2 * pad - KH) / stride + 1;
-  a.Wo = (W + 2 * pad - KW) / stride + 1;
-  a.Kpad = (KH * KW * Cin + 31) / 32 * 32;
-  a.M = Nimg * a.Ho * a.Wo;
-  a.relu = relu;
-  a.out_ld = Cout;
-  a.split_m = 0x7fffffff;
-  a.post_period = 1;
-  a.tokens = 400;
-  return a;
+// What the plan of a stand-alone launch asks for, from the arena (under the caller's ArenaScope; consumed on the stream before anything
+// else takes it): the packed copy of the weights its form reads, packed here as a network packs it at load, and the split-K scratch
+static int conv_materialise(fp_ctx *ctx, ConvArgs &a, const ConvPlan &plan, hipStream_t s) {
+  const size_t bytes = plan.packing ? conv_packed_halfs(plan.packing, a.Cout, a.Cin) * sizeof(f16) : plan.splitk_bytes;
+  if (bytes == 0) return FP_OK;
+  FP_TRY(fp_arena_ensure(ctx, bytes + 4096));
+  void *p = ctx->arena.take(bytes);
+  if (!p) return FP_ENOMEM;
+  if (!plan.packing) {
+    a.splitk = (float *)p;
+    return FP_OK;
+  }
+  (plan.packing == CONV_OFFER_SMALL ? a.wsm : a.wpk) = (const f16 *)p;
+  return conv_pack_weights(plan.packing, a.w, a.Cout, a.Cin, a.Kpad, (f16 *)p, s);
 }
 
+// one convolution launch on its own: fp16 or fp32 NHWC output, no split, no post-add.  Planned with everything on offer that a network
+// holds for a layer but the s1b packing (conv_plan.h: where the callers differ), so that the parity tests reach each form
 extern "C" int fp_conv2d_f16(fp_ctx *ctx, const void *d_in, int Nimg, int H, int W, int Cin, const void *d_w_packed, const float *d_bias,
                              int Cout, int KH, int KW, int stride, int pad, const void *d_res, int relu, void *d_out, int out_f32,
                              void *stream) {
   FP_REQUIRE(ctx && d_in && d_w_packed && d_bias && d_out, "fp_conv2d_f16: null argument");
   FP_REQUIRE(stride >= 1 && pad >= 0 && Nimg >= 0, "fp_conv2d_f16: bad stride/pad/N");
-  ConvArgs a = conv_args(d_in, d_w_packed, d_bias, d_res, d_out, Nimg, H, W, Cin, Cout, KH, KW, stride, pad, relu);
-  a.out_mode = out_f32 ? 1 : 0;
-  ArenaScope scope(ctx->arena);        // the forms below take packed weights or scratch, consumed on the stream before anything else takes them
-  // a few images of a 3x3 stride-1 trunk layer: conv_small.hip on weights packed here, as inside the networks (a tracking frame)
-  if (!out_f32 && conv_small_shape(a, ctx->num_cu)) {
-    const size_t bytes = small_packed_halfs(Cout, Cin) * sizeof(f16);
-    FP_TRY(fp_arena_ensure(ctx, bytes + 4096));
-    f16 *pk = (f16 *)ctx->arena.take(bytes);
-    if (!pk) return FP_ENOMEM;
-    FP_TRY(small_pack_weights(a.w, Cout, Cin, a.Kpad, pk, (hipStream_t)stream));
-    a.wsm = pk;
-    return launch_conv(ctx, a, (hipStream_t)stream);
-  }
-  // launches of a few workgroups take the split-K form of the 3x3 stride-1 kernel, as inside the networks (2 .. 4 hypotheses)
-  a.ksplit = out_f32 ? 0 : conv_ksplit(a, ctx->num_cu);
-  if (a.ksplit > 1) {
-    const size_t bytes = (size_t)a.ksplit * a.M * a.Cout * sizeof(float);
-    FP_TRY(fp_arena_ensure(ctx, bytes + 4096));
-    a.splitk = (float *)ctx->arena.take(bytes);
-    return a.splitk ? launch_conv(ctx, a, (hipStream_t)stream) : FP_ENOMEM;
-  }
-  a.ksplit = 0;
-  if (!out_f32 && a.M >= S2_MIN_PIXELS && s2_supported(a)) {       // the band-in-LDS form of the 3x3 stride-2 layers, as inside the networks
-    const size_t bytes = s2_packed_halfs(Cout, Cin) * sizeof(f16);
-    FP_TRY(fp_arena_ensure(ctx, bytes + 4096));
-    f16 *pk = (f16 *)ctx->arena.take(bytes);
-    if (!pk) return FP_ENOMEM;
-    FP_TRY(s2_pack_weights(a.w, Cout, Cin, a.Kpad, pk, (hipStream_t)stream));
-    a.wpk = pk;
-    return launch_conv(ctx, a, (hipStream_t)stream);
-  }
-  return launch_conv(ctx, a, (hipStream_t)stream);
+  ConvArgs a = conv_args((const f16 *)d_in, Nimg, H, W, Cin, (const f16 *)d_w_packed, d_bias, Cout, KH, KW, stride, pad, conv_kpad(KH, KW, Cin), d_out);
+  a.res = (const f16 *)d_res, a.relu = relu, a.out_mode = out_f32 ? 1 : 0;
+  ArenaScope scope(ctx->arena);
+  const unsigned offer = out_f32 ? 0 : CONV_OFFER_SMALL | CONV_OFFER_S2 | CONV_OFFER_SPLITK;
+  FP_TRY(conv_materialise(ctx, a, conv_plan(a, ctx->num_cu, offer, conv_knobs()), (hipStream_t)stream));
+  return launch_conv(ctx, a, (hipStream_t)stream);      // (plans again from what `a` now holds: the same form)
 }
 
 // Building block for the parity tests: the band-in-LDS form of the C -> C 3x3 stride-1 layers on 40x40 maps (conv_s1b.hip; C = 128 or 256),
@@ -1432,15 +1399,13 @@ extern "C" int fp_conv3x3_band_f16(fp_ctx *ctx, const void *d_in, int Nimg, int 
                                    int relu, void *d_out, void *stream) {
   FP_REQUIRE(ctx && d_in && d_w_packed && d_bias && d_out && Nimg >= 0, "fp_conv3x3_band_f16: bad argument");
   FP_REQUIRE(C == 128 || C == 256, "fp_conv3x3_band_f16: C=%d (128 or 256)", C);
-  ConvArgs a = conv_args(d_in, d_w_packed, d_bias, d_res, d_out, Nimg, 40, 40, C, C, 3, 3, 1, 1, relu);
+  ConvArgs a = conv_args((const f16 *)d_in, Nimg, 40, 40, C, (const f16 *)d_w_packed, d_bias, C, 3, 3, 1, 1, conv_kpad(3, 3, C), d_out);
+  a.res = (const f16 *)d_res, a.relu = relu;
   if (a.M == 0) return FP_OK;
-  const size_t bytes = s2_packed_halfs(C, C) * sizeof(f16);
-  FP_TRY(fp_arena_ensure(ctx, bytes + 4096));
+  const ConvPlan plan = conv_plan(a, ctx->num_cu, CONV_FORCE_S1B, conv_knobs());
+  FP_REQUIRE(plan.form == CONV_S1B, "fp_conv3x3_band_f16: %d images are more than the band kernel addresses", Nimg);
   ArenaScope scope(ctx->arena);
-  f16 *pk = (f16 *)ctx->arena.take(bytes);
-  if (!pk) return FP_ENOMEM;
-  FP_TRY(s2_pack_weights(a.w, C, C, a.Kpad, pk, (hipStream_t)stream, 2, 1));
-  a.wpk = pk;
+  FP_TRY(conv_materialise(ctx, a, plan, (hipStream_t)stream));
   return launch_conv_s1b(ctx, a, (hipStream_t)stream);
 }
 

@@ -12,7 +12,10 @@
 
 #include "../../include/foundationpose_amd.h"
 
+#ifndef FP_F16_TYPEDEF
+#define FP_F16_TYPEDEF
 typedef _Float16 f16;
+#endif
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 typedef float floatx16 __attribute__((ext_vector_type(16)));
@@ -336,47 +339,24 @@ void raster_kernel_lds(std::vector<KernelLds> &v);      // raster.hip
 int fp_set_kernel_attributes(fp_ctx *ctx);              // api.hip: all of the above on ctx->device
 
 // ---- kernel launchers implemented in the .hip files ----
-struct ConvArgs {
-  const f16 *in;
-  const f16 *w;
-  const float *bias;
-  const f16 *res;
-  const float *post_add;
-  void *out;
-  int Nimg, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, Kpad, M;
-  int relu, out_mode;  // 0 fp16 NHWC, 1 fp32 NHWC, 2 fp16 V-transposed [b][4][128][416], token t in column vt_col(t)
-  int out_ld, split_m, coff_hi, post_period, tokens;
-  // split-K of the 3x3 stride-1 kernel for launches of a few workgroups (3 .. 4 hypotheses; 1 .. 2, a tracking frame, run conv_small.hip): `ksplit` workgroups share
-  // the input-channel chunks of a tile and leave fp32 partial sums in `splitk` [ksplit][M][Cout]; a finishing pass adds them in a
-  // fixed order and applies bias-free epilogue (the bias rides in split 0).  0 / nullptr: off.
-  float *splitk = nullptr;
-  int ksplit = 0;
-  // 3x3 stride-2 layers: the weights in the fragment order of conv_s2.hip (s2_pack_weights); nullptr: the implicit-GEMM kernel runs
-  const f16 *wpk = nullptr;
-  // 3x3 stride-1 layers: the weights in the fragment order of conv_small.hip (small_pack_weights); nullptr: that form is not used
-  const f16 *wsm = nullptr;
-  // hypotheses of the network pass this launch belongs to (0: a stand-alone call): the few-image form is chosen by it, so that the two sides
-  // of encodeA as one chain or two (twice the images per launch) take the same kernel
-  int hyp = 0;
-};
-int launch_conv(fp_ctx *ctx, const ConvArgs &a, hipStream_t s);
-// conv_s2.hip: band-in-LDS form of the 3x3 stride-2 layers
-#define S2_MIN_PIXELS 2000      // below (1 .. 4 hypotheses at 20x20 outputs: the sizes whose 3x3 stride-1 layers run split-K) the implicit-GEMM kernel with its 64-pixel tail tiles runs
-bool s2_supported(const ConvArgs &a);
-int s2_ct_for(int Cout);
+// The convolutions: ConvArgs, the plan that picks the kernel form of a launch and every shape predicate are in conv_plan.h
+#include "conv_plan.h"
+int launch_conv(fp_ctx *ctx, const ConvArgs &a, hipStream_t s);      // conv.hip: offer from a.wsm / a.wpk / a.splitk, conv_plan, launch
+// the per-form launchers, next to their kernels; each checks that the layer is one its kernel runs
+int launch_conv_small(fp_ctx *ctx, const ConvArgs &a, hipStream_t s);                          // conv_small.hip
+int launch_conv_s1b(fp_ctx *ctx, const ConvArgs &a, hipStream_t s);                            // conv_s1b.hip
+int launch_conv_halo(const ConvArgs &a, const ConvPlan &plan, hipStream_t s);                  // conv_halo.hip: the plan's tiling, or a.ksplit shares + the finishing pass
+int launch_splitk_finish(const ConvArgs &a, hipStream_t s);                                    // conv_halo.hip: adds the shares in order (also behind conv.hip's stride-2 split-K)
+int launch_stem(fp_ctx *ctx, const ConvArgs &a, hipStream_t s);                                // stem.hip
+int launch_conv_s2(fp_ctx *ctx, const ConvArgs &a, hipStream_t s);                             // conv_s2.hip
+// packed copies of a layer's [Cout][Kpad] weights
 size_t s2_packed_halfs(int Cout, int Cin);
 int s2_pack_weights(const f16 *d_w, int Cout, int Cin, int Kpad, f16 *d_out, hipStream_t s, int ct_force = 0, int order = 0);   // ct_force: co tiles of 32 per wave group (0: s2_ct_for); order 1: conv_s1b.hip
-int launch_conv_s2(fp_ctx *ctx, const ConvArgs &a, hipStream_t s);
-// conv_s1b.hip: band-in-LDS form of the 128 -> 128 stride-1 layers on 40x40 maps (bit-identical to the halo kernel; FP_C128_BAND=0: off)
-bool s1b_supported(const ConvArgs &a);
-int launch_conv_s1b(fp_ctx *ctx, const ConvArgs &a, hipStream_t s);
-
-// conv_small.hip: the 3x3 layers of the trunk in the passes of one or two hypotheses (a tracking frame): 32 x 32 tiles, K split over the waves of a workgroup
-bool conv_small_shape(const ConvArgs &a, int num_cu);     // the layer shapes and launch sizes it runs
-bool conv_small_use(const ConvArgs &a, int num_cu);       // ... and the caller holds the packed weights (ConvArgs::wsm)
 size_t small_packed_halfs(int Cout, int Cin);
 int small_pack_weights(const f16 *d_w, int Cout, int Cin, int Kpad, f16 *d_out, hipStream_t s);
-int launch_conv_small(fp_ctx *ctx, const ConvArgs &a, hipStream_t s);
+// conv.hip: the copy `packing` (one ConvOffer bit) names - its size, and the launch that writes it
+size_t conv_packed_halfs(unsigned packing, int Cout, int Cin);
+int conv_pack_weights(unsigned packing, const f16 *d_w, int Cout, int Cin, int Kpad, f16 *d_out, hipStream_t s);
 
 // Column of token t inside the transposed V image [b][4][128][416].  Within each group of 16 tokens the order is
 // {0-3, 8-11, 4-7, 12-15}: the 8 keys that one lane half of the attention kernel's P^T operand carries (the S^T

@@ -28,7 +28,7 @@
 // step's 16 MFMAs per wave.  Used for the 1x1 (Linear) layers, the stride-2 3x3 and the 7x7 stem.
 // ------------------------------------------------------------------------------------------------
 #define C2_BN 256
-#define C2_BK 32
+// (C2_BK = 32, K per step: conv_plan.h)
 
 #ifdef HALO_STAMP
 // diagnostic build only (make -B EXTRA=-DHALO_STAMP): per-wave cycle counts of prologue / K loop / epilogue
@@ -439,22 +439,6 @@ __global__ __launch_bounds__(256, 2) void conv_igemm2_splitk_kernel(ConvArgs p, 
   igemm2_tile<BM, KW, false, 1, false, true>(p, zero_page, m0, (t % n_ct) * BM, smem, ks);
 }
 
-void halo_split(int n_tiles, int slots, int *n_main, int *n_tail4);      // conv_halo.hip: main / quarter-tile split
-int launch_splitk_finish(const ConvArgs &a, hipStream_t s);              // conv_halo.hip
-int conv_halo_ksplit(const ConvArgs &a, int num_cu);                     // conv_halo.hip
-
-// Split factor of a launch (0: none): the 3x3 stride-1 layers by conv_halo_ksplit; the 3x3 stride-2 layer from 36 K-steps on when
-// its 64-pixel tiles fill at most a quarter of the workgroup slots (1 .. 4 hypotheses).  Decided by the caller that owns the scratch.
-int conv_ksplit(const ConvArgs &a, int num_cu) {
-  if (conv_small_use(a, num_cu)) return 0;           // conv_small.hip splits K inside its workgroups
-  if (const int k = conv_halo_ksplit(a, num_cu)) return k;
-  const int nk = a.Kpad / C2_BK;
-  if (a.KH == 3 && a.KW == 3 && a.stride == 2 && a.out_mode == 0 && a.Cin % 32 == 0 && a.Cout % 128 == 0 && a.M < S2_MIN_PIXELS && nk >= 36 && nk % 4 == 0 &&
-      ((a.M + 63) / 64) * (a.Cout / 128) * 4 <= 2 * num_cu)
-    return 4;
-  return 0;
-}
-
 template <int BM>
 constexpr int igemm2_lds_bytes() {
   constexpr int main_b = 3 * (C2_BN * C2_BK + BM * C2_BK) * 2, epi_b = C2_BN * (BM + 8) * 2;
@@ -478,7 +462,7 @@ template <int BM, int KW, bool CIN8, bool RES>
 static int launch_two_r(fp_ctx *ctx, const ConvArgs &a, const f16 *zero_page, hipStream_t s) {
   const int n_tiles = ((a.M + C2_BN - 1) / C2_BN) * (a.Cout / BM);
   int n_main, n_tail4;
-  halo_split(n_tiles, 2 * ctx->num_cu, &n_main, &n_tail4);
+  halo_split(n_tiles, 2 * ctx->num_cu, conv_knobs(), &n_main, &n_tail4);
   constexpr int lds = igemm2_lds_bytes<BM>();
   FP_REQUIRE(a.out_mode != 0 || (a.out_ld % 8 == 0 && a.coff_hi % 8 == 0), "conv: out_ld/coff must be multiples of 8 for fp16 output");
   hipLaunchKernelGGL((conv_igemm2_kernel<BM, KW, CIN8, RES>), dim3(n_main + n_tail4), dim3(256), lds, s, a, zero_page, n_main);
@@ -492,12 +476,33 @@ static int launch_two(fp_ctx *ctx, const ConvArgs &a, const f16 *zero_page, hipS
   return (a.res && a.out_mode == 0) ? launch_two_r<BM, KW, CIN8, true>(ctx, a, zero_page, s) : launch_two_r<BM, KW, CIN8, false>(ctx, a, zero_page, s);
 }
 
-bool conv_halo_supported(const ConvArgs &a);
-int launch_conv_halo(fp_ctx *ctx, const ConvArgs &a, hipStream_t s);
-bool stem_supported(const ConvArgs &a);                     // stem.hip
-int launch_stem(fp_ctx *ctx, const ConvArgs &a, hipStream_t s);
+// The knobs of conv_plan.h, read once per process: the only place that names their variables
+const ConvKnobs &conv_knobs() {
+  static const ConvKnobs knobs = [] {
+    ConvKnobs k;
+    k.small = (int)fp_env_int("FP_SMALL", k.small);
+    k.small_max_wg = (int)fp_env_int("FP_SMALL_MAX_WG", k.small_max_wg);
+    k.c128_band = (int)fp_env_int("FP_C128_BAND", k.c128_band);
+    k.ksplit_max = (int)fp_env_int("FP_KSPLIT_MAX", k.ksplit_max);
+    k.ksplit_min_chunks = (int)fp_env_int("FP_KSPLIT_MIN_CHUNKS", k.ksplit_min_chunks);
+    k.halo_tail = fp_env_int("FP_HALO_TAIL", k.halo_tail) != 0;
+    k.halo_nt = (int)fp_env_int("FP_HALO_NT", k.halo_nt);
+    return k;
+  }();
+  return knobs;
+}
 
-int launch_conv(fp_ctx *ctx, const ConvArgs &a, hipStream_t s) {
+size_t conv_packed_halfs(unsigned packing, int Cout, int Cin) { return packing == CONV_OFFER_SMALL ? small_packed_halfs(Cout, Cin) : s2_packed_halfs(Cout, Cin); }
+
+int conv_pack_weights(unsigned packing, const f16 *d_w, int Cout, int Cin, int Kpad, f16 *d_out, hipStream_t s) {
+  if (packing == CONV_OFFER_SMALL) return small_pack_weights(d_w, Cout, Cin, Kpad, d_out, s);
+  if (packing == CONV_OFFER_S2) return s2_pack_weights(d_w, Cout, Cin, Kpad, d_out, s);
+  FP_REQUIRE(packing == CONV_OFFER_S1B, "conv_pack_weights: packing %u is not one copy", packing);
+  return s2_pack_weights(d_w, Cout, Cin, Kpad, d_out, s, 2, 1);      // (conv_s1b.hip: 64 couts per wave group)
+}
+
+int launch_conv(fp_ctx *ctx, const ConvArgs &args, hipStream_t s) {
+  ConvArgs a = args;
   FP_REQUIRE(a.Cin == 8 || a.Cin % 32 == 0, "conv: Cin=%d must be 8 or a multiple of 32", a.Cin);
   FP_REQUIRE(a.Cout % 64 == 0, "conv: Cout=%d must be a multiple of 64", a.Cout);
   FP_REQUIRE(a.Kpad % CV_BK == 0 && a.Kpad >= a.KH * a.KW * a.Cin, "conv: bad Kpad=%d", a.Kpad);
@@ -505,34 +510,36 @@ int launch_conv(fp_ctx *ctx, const ConvArgs &a, hipStream_t s) {
   FP_REQUIRE(a.M == a.Nimg * a.Ho * a.Wo, "conv: M mismatch");
   FP_REQUIRE(a.out_ld % 4 == 0 && a.coff_hi % 4 == 0, "conv: out_ld/coff must be multiples of 4");
   if (a.M == 0) return FP_OK;
-  const double flops = 2.0 * (double)a.M * a.Cout * a.KH * a.KW * (a.Cin == 8 ? 6 : a.Cin);
-  const bool halo = conv_halo_supported(a);
-  const char *cls = halo ? "conv3x3_halo" : (a.KW == 3) ? "conv3x3_s2" : (a.KW == 7 ? "conv7x7" : "linear");
-  ProfScope ps(ctx, s, cls, flops);
-  if (!(a.splitk && a.ksplit > 1) && conv_small_use(a, ctx->num_cu)) return launch_conv_small(ctx, a, s);      // a few images: conv_small.hip
-  {
-    static const int band = fp_env_int("FP_C128_BAND", 1);   // conv_s1b.hip (bit-identical to the halo kernel); 0: off, 2: also the 256 -> 256 layers
-    // ... from the batch size on at which the general kernel needs more than one round of its 512-pixel tiles (82 images on 256 CUs): below,
-    // one round of those is faster (32 hypotheses per GPU: 6.67 against 6.79 ms per step; 63: 10.24 against 10.13)
-    if (band != 0 && (a.Cin == 128 || band == 2) && (long long)a.M > (long long)ctx->num_cu * 512 && s1b_supported(a)) return launch_conv_s1b(ctx, a, s);
-  }
-  if (halo) return launch_conv_halo(ctx, a, s);
-  if (a.splitk && a.ksplit > 1) {        // (conv_ksplit: the 3x3 stride-2 layer with the long K at 3 .. 4 hypotheses; 1 .. 2 run conv_small.hip)
-    FP_REQUIRE(a.KW == 3 && a.stride == 2 && a.Cout % 128 == 0 && (a.Kpad / C2_BK) % a.ksplit == 0 && a.out_mode == 0, "conv split-K: unsupported layer");
-    const int n_t = ((a.M + 63) / 64) * (a.Cout / 128);
-    hipLaunchKernelGGL((conv_igemm2_splitk_kernel<128, 3>), dim3(n_t * a.ksplit), dim3(256), igemm2_lds_bytes<128>(), s, a, (const f16 *)ctx->zero_page);
-    FP_CHECK_HIP(hipGetLastError());
-    return launch_splitk_finish(a, s);
-  }
-  if (stem_supported(a)) return launch_stem(ctx, a, s);
-  if (a.wpk && a.M >= S2_MIN_PIXELS && s2_supported(a)) return launch_conv_s2(ctx, a, s);
-  const bool bm128 = (a.Cout % 128 == 0);
+  // what the caller holds: the packed copies by their pointers (one wpk: conv_s2.hip's order for a stride-2 layer, conv_s1b.hip's for stride 1), scratch
+  const unsigned offer = (a.wsm ? CONV_OFFER_SMALL : 0) | (a.wpk ? (a.stride == 1 ? CONV_OFFER_S1B : CONV_OFFER_S2) : 0) | (a.splitk ? CONV_OFFER_SPLITK : 0);
+  const ConvPlan plan = conv_plan(a, ctx->num_cu, offer, conv_knobs());
+  a.ksplit = plan.ksplit;                              // the kernels of the one-launch forms see no scratch
+  if (plan.ksplit <= 1) a.splitk = nullptr;
+  ProfScope ps(ctx, s, plan.cls, plan.flops);
   const f16 *zp = (const f16 *)ctx->zero_page;
-  if (a.Cin == 8) {
-    FP_REQUIRE(a.KW == 7, "conv: Cin=8 path is the 7x7 stem");
-    return bm128 ? launch_two<128, 7, true>(ctx, a, zp, s) : launch_two<64, 7, true>(ctx, a, zp, s);
+  const bool bm128 = (a.Cout % 128 == 0);
+  switch (plan.form) {
+    case CONV_SMALL: return launch_conv_small(ctx, a, s);
+    case CONV_S1B: return launch_conv_s1b(ctx, a, s);
+    case CONV_HALO:
+    case CONV_HALO_SPLITK: return launch_conv_halo(a, plan, s);
+    case CONV_S2_SPLITK: {
+      FP_REQUIRE(a.KW == 3 && a.stride == 2 && a.Cout % 128 == 0 && (a.Kpad / C2_BK) % a.ksplit == 0 && a.out_mode == 0, "conv split-K: unsupported layer");
+      const int n_t = ((a.M + 63) / 64) * (a.Cout / 128);
+      hipLaunchKernelGGL((conv_igemm2_splitk_kernel<128, 3>), dim3(n_t * a.ksplit), dim3(256), igemm2_lds_bytes<128>(), s, a, zp);
+      FP_CHECK_HIP(hipGetLastError());
+      return launch_splitk_finish(a, s);
+    }
+    case CONV_STEM: return launch_stem(ctx, a, s);
+    case CONV_S2: return launch_conv_s2(ctx, a, s);
+    case CONV_IGEMM2:
+      if (a.Cin == 8) {
+        FP_REQUIRE(a.KW == 7, "conv: Cin=8 path is the 7x7 stem");
+        return bm128 ? launch_two<128, 7, true>(ctx, a, zp, s) : launch_two<64, 7, true>(ctx, a, zp, s);
+      }
+      if (a.KW == 3) return bm128 ? launch_two<128, 3, false>(ctx, a, zp, s) : launch_two<64, 3, false>(ctx, a, zp, s);
+      if (a.KW == 1) return bm128 ? launch_two<128, 1, false>(ctx, a, zp, s) : launch_two<64, 1, false>(ctx, a, zp, s);
   }
-  if (a.KW == 3) return bm128 ? launch_two<128, 3, false>(ctx, a, zp, s) : launch_two<64, 3, false>(ctx, a, zp, s);
-  if (a.KW == 1) return bm128 ? launch_two<128, 1, false>(ctx, a, zp, s) : launch_two<64, 1, false>(ctx, a, zp, s);
   FP_REQUIRE(false, "conv: unsupported configuration KW=%d Cin=%d", a.KW, a.Cin);
 }
+

@@ -15,8 +15,7 @@
 #include <cstdlib>
 
 
-#define HL_BM 128
-#define HL_CK 32
+// (HL_BM = 128 couts per tile, HL_CK = 32 input channels per chunk: conv_plan.h)
 #define HL_SLD 136  // halfs per staged output row (128 + 8 pad) -> 272 B
 
 #ifdef HALO_STAMP
@@ -448,76 +447,6 @@ __global__ __launch_bounds__(256) void splitk_finish_kernel(ConvArgs p) {
 }
 
 
-bool conv_halo_supported(const ConvArgs &a) {
-  return a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 && a.H == a.W && (a.W == 40 || a.W == 20) && a.Cin % HL_CK == 0 &&
-         a.Cout % HL_BM == 0 && a.out_mode == 0 && a.Kpad == 9 * a.Cin && a.out_ld % 8 == 0 && a.coff_hi % 8 == 0;
-}
-
-// FP_HALO_TAIL=0 disables the tail split of halo_split and halo_plan (A/B timing only; results are identical)
-static bool halo_tail_on() {
-  static const bool on = fp_env_int("FP_HALO_TAIL", 1) != 0;
-  return on;
-}
-
-// main/tail split: whole rounds of `slots` main tiles stay; the remainder is cut in four when that shortens the last round
-// (a quarter tile costs ~0.35 of a main tile: less operand reuse), i.e. when the remainder fills < ~70 % of a round.
-void halo_split(int n_tiles, int slots, int *n_main, int *n_tail4) {
-  const int rem = n_tiles % slots;
-  *n_main = n_tiles;
-  *n_tail4 = 0;
-  if (!halo_tail_on() || rem == 0) return;
-  if (n_tiles < slots) {
-    // less than one round (tracking; a rank's shard of an 8-way job: 32 hypotheses = 100 tiles at C = 512): the launch lasts as
-    // long as ONE workgroup, so quarter tiles (4 x the workgroups, ~0.35 x the time each) win as long as they fit two rounds
-    if (4 * n_tiles <= 2 * slots) {
-      *n_main = 0;
-      *n_tail4 = 4 * n_tiles;
-    }
-    return;
-  }
-  const double cost_whole = 1.0, cost_quarter = 0.35 * ((4 * rem + slots - 1) / slots);
-  if (cost_quarter < cost_whole) {
-    *n_main = n_tiles - rem;
-    *n_tail4 = 4 * rem;
-  }
-}
-
-// Tiling of a launch (M pixels, n_ct cout tiles of 128, `slots` CUs, one workgroup each): whole rounds of 512-pixel tiles, and what is
-// left - less than a round, or the whole of a small launch (a rank's shard of an 8-way job, a tracking frame) - as tiles of nt x 128
-// pixels, nt chosen for the shortest finish.  Relative cost of a tile by its nt (measured on one-round launches at C = 512: a round
-// of 128-pixel tiles lasts 0.43 of a round of 512-pixel ones - less operand reuse, the same prologue and epilogue).
-static const double kHaloTileCost[5] = {0.0, 0.43, 0.62, 0.81, 1.0};
-void halo_plan(int M, int n_ct, int slots, int *n_main, int *nt_tail, int *n_tail) {
-  const int qm = (M + 127) / 128;                       // 128-pixel quarters along the pixel axis
-  const int per_round = (slots / n_ct) * 4;             // quarters a round of 512-pixel tiles covers
-  int full = per_round > 0 ? qm / per_round : 0;
-  int rem = qm - full * per_round;
-  *n_main = full * (slots / n_ct) * n_ct;
-  *nt_tail = 4;
-  *n_tail = 0;
-  if (rem == 0) return;
-  if (!halo_tail_on()) {                                 // FP_HALO_TAIL=0: 512-pixel tiles only
-    *n_tail = ((rem + 3) / 4) * n_ct;
-    return;
-  }
-  static const int force_nt = fp_env_int("FP_HALO_NT", 0);      // experiments: tiles of this many x 128 pixels for whatever is not a whole round
-  if (force_nt >= 1 && force_nt <= 4) {
-    *nt_tail = force_nt;
-    *n_tail = ((rem + force_nt - 1) / force_nt) * n_ct;
-    return;
-  }
-  double best = 1e30;
-  for (int nt = 4; nt >= 1; --nt) {
-    const int wgs = ((rem + nt - 1) / nt) * n_ct;
-    const double cost = ((wgs + slots - 1) / slots) * kHaloTileCost[nt];
-    if (cost < best - 1e-9) {
-      best = cost;
-      *nt_tail = nt;
-      *n_tail = wgs;
-    }
-  }
-}
-
 template <int W>
 static void halo_lds_all(std::vector<KernelLds> &v) {
   using C = HaloCfgD<W, 512>;
@@ -530,22 +459,19 @@ static void halo_lds_all(std::vector<KernelLds> &v) {
 void conv_halo_kernel_lds(std::vector<KernelLds> &v) { halo_lds_all<40>(v), halo_lds_all<20>(v); }
 
 template <int W, bool RES, bool POST>
-static int launch_halo_dma(fp_ctx *ctx, const ConvArgs &a, hipStream_t s) {
+static int launch_halo_dma(const ConvArgs &a, const ConvPlan &plan, hipStream_t s) {
   using C = HaloCfgD<W, 512>;
   static_assert(HaloCfgD<W, 128>::LDS_BYTES <= C::LDS_BYTES, "tail tiles fit the main tile's LDS");
-  const int slots = ctx->num_cu;
-  int n_main, nt_tail, n_tail;
-  halo_plan(a.M, a.Cout / HL_BM, slots, &n_main, &nt_tail, &n_tail);
-  if (n_main + n_tail > 0)
-    hipLaunchKernelGGL((conv3x3_halo_dma_kernel<W, RES, POST>), dim3(n_main + n_tail), dim3(512), C::LDS_BYTES, s, a, n_main, 0, nt_tail);
+  if (plan.n_main + plan.n_tail > 0)
+    hipLaunchKernelGGL((conv3x3_halo_dma_kernel<W, RES, POST>), dim3(plan.n_main + plan.n_tail), dim3(512), C::LDS_BYTES, s, a, plan.n_main, 0, plan.nt_tail);
   FP_CHECK_HIP(hipGetLastError());
   return FP_OK;
 }
 
 template <int W>
-static int launch_halo_dma_flags(fp_ctx *ctx, const ConvArgs &a, hipStream_t s) {
-  if (a.post_add) return a.res ? launch_halo_dma<W, true, true>(ctx, a, s) : launch_halo_dma<W, false, true>(ctx, a, s);
-  return a.res ? launch_halo_dma<W, true, false>(ctx, a, s) : launch_halo_dma<W, false, false>(ctx, a, s);
+static int launch_halo_dma_flags(const ConvArgs &a, const ConvPlan &plan, hipStream_t s) {
+  if (a.post_add) return a.res ? launch_halo_dma<W, true, true>(a, plan, s) : launch_halo_dma<W, false, true>(a, plan, s);
+  return a.res ? launch_halo_dma<W, true, false>(a, plan, s) : launch_halo_dma<W, false, false>(a, plan, s);
 }
 
 int launch_splitk_finish(const ConvArgs &a, hipStream_t s) {
@@ -563,29 +489,14 @@ static int launch_halo_splitk(const ConvArgs &a, hipStream_t s) {
   return launch_splitk_finish(a, s);
 }
 
-// Split factor for a launch of this shape: 0 unless the quarter tiles fill at most a quarter of the CUs (1 .. 4 hypotheses);
-// then, from 8 chunks (256 channels) on, as many shares (at most 8; FP_KSPLIT_MAX) as keep >= 2 chunks per share and the grid within the chip.  Decided by the caller
-// that owns the scratch (its size: shares x M x Cout floats <= 4 x hypotheses x 1600 x 256 for every layer of the networks).
-int conv_halo_ksplit(const ConvArgs &a, int num_cu) {
-  if (!conv_halo_supported(a)) return 0;
-  const int n_q = ((a.M + 127) / 128) * (a.Cout / HL_BM), nchunk = a.Cin / HL_CK;
-  if (n_q * 4 > num_cu) return 0;
-  static const int k_max = fp_env_int("FP_KSPLIT_MAX", 8);
-  // from 256 input channels on: with the four chunks of a 128-channel layer two shares + the finishing launch take longer than the one
-  // launch (one-hypothesis step 2.17 -> 2.12 ms, four hypotheses 2.74 -> 2.56 without them; FP_KSPLIT_MIN_CHUNKS=0: split those too)
-  static const int min_chunks = fp_env_int("FP_KSPLIT_MIN_CHUNKS", 8);
-  if (nchunk < min_chunks) return 0;
-  int k = k_max;
-  while (k > 1 && (nchunk % k != 0 || nchunk / k < 2 || n_q * k > num_cu)) k >>= 1;
-  return k > 1 ? k : 0;
-}
-
-int launch_conv_halo(fp_ctx *ctx, const ConvArgs &a, hipStream_t s) {
+int launch_conv_halo(const ConvArgs &a, const ConvPlan &plan, hipStream_t s) {
+  FP_REQUIRE(conv_halo_supported(a), "conv3x3: unsupported layer");
   // lane offsets into the input tensor are 32-bit byte offsets from its base
   FP_REQUIRE((double)a.M * a.Cin * 2.0 < 4294967296.0, "conv3x3: input tensor of %.1f GB exceeds the 4 GB the kernel addresses", (double)a.M * a.Cin * 2e-9);
-  if (a.splitk && a.ksplit > 1) {
-    FP_REQUIRE((a.Cin / HL_CK) % a.ksplit == 0 && a.out_ld % 4 == 0 && a.coff_hi % 4 == 0, "conv3x3 split-K: %d shares do not divide %d chunks", a.ksplit, a.Cin / HL_CK);
+  if (plan.form == CONV_HALO_SPLITK) {
+    FP_REQUIRE(a.splitk && a.ksplit == plan.ksplit && (a.Cin / HL_CK) % a.ksplit == 0 && a.out_ld % 4 == 0 && a.coff_hi % 4 == 0,
+               "conv3x3 split-K: %d shares do not divide %d chunks", a.ksplit, a.Cin / HL_CK);
     return a.W == 40 ? launch_halo_splitk<40>(a, s) : launch_halo_splitk<20>(a, s);
   }
-  return a.W == 40 ? launch_halo_dma_flags<40>(ctx, a, s) : launch_halo_dma_flags<20>(ctx, a, s);
+  return a.W == 40 ? launch_halo_dma_flags<40>(a, plan, s) : launch_halo_dma_flags<20>(a, plan, s);
 }

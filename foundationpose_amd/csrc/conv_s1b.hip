@@ -26,7 +26,7 @@
 #include "device_util.h"
 
 #define B1_THREADS 256
-#define B1_W 40
+// (B1_W = 40, the map edge: conv_plan.h)
 #define B1_ROWS 8
 #define B1_P 56
 #define B1_BROWS (B1_ROWS + 2)
@@ -193,19 +193,13 @@ __global__ __launch_bounds__(B1_THREADS, 2) void conv3x3_s1_band_kernel(ConvArgs
   }
 }
 
-bool s1b_supported(const ConvArgs &a) {
-  return a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 && a.out_mode == 0 && !a.post_add && a.H == B1_W && a.W == B1_W && a.Cin % 32 == 0 &&
-         a.Cout % 128 == 0 && a.Kpad == 9 * a.Cin && a.out_ld % 8 == 0 && a.coff_hi % 8 == 0 && a.wpk != nullptr && !(a.splitk && a.ksplit > 1) &&
-         (long long)a.Nimg * B1_W * B1_W * a.Cin * 2 < (1ll << 31);        // 32-bit byte offsets into the input (above: the general 3x3 kernel, 4 GB)
-}
-
 void conv_s1b_kernel_lds(std::vector<KernelLds> &v) {
   v.push_back({(const void *)conv3x3_s1_band_kernel<true>, B1_LDS_BYTES});
   v.push_back({(const void *)conv3x3_s1_band_kernel<false>, B1_LDS_BYTES});
 }
 
 int launch_conv_s1b(fp_ctx *ctx, const ConvArgs &a, hipStream_t s) {
-  FP_REQUIRE(s1b_supported(a), "launch_conv_s1b: unsupported layer");
+  FP_REQUIRE(a.wpk && s1b_supported(a), "launch_conv_s1b: unsupported layer or no packed weights");
   const int n_cob = a.Cout / 128, n_tiles = a.Nimg * (B1_W / B1_ROWS) * n_cob;
   if (a.res) {
     hipLaunchKernelGGL(conv3x3_s1_band_kernel<true>, dim3(n_tiles), dim3(B1_THREADS), B1_LDS_BYTES, s, a, a.wpk, (const f16 *)ctx->zero_page, n_tiles, n_cob);

@@ -222,16 +222,6 @@ __global__ __launch_bounds__(S2_THREADS, 2) void conv3x3_s2_kernel(ConvArgs p, c
   }
 }
 
-// co tiles of 32 per wave: 2 -> 256-cout blocks, 1 -> 128-cout blocks; 0: this Cout is not handled here.  A function of Cout alone,
-// so that the weights can be packed when the network is loaded (the spatial size is not known then).
-int s2_ct_for(int Cout) { return Cout % 256 == 0 ? 2 : Cout % 128 == 0 ? 1 : 0; }
-
-bool s2_supported(const ConvArgs &a) {
-  return a.KH == 3 && a.KW == 3 && a.stride == 2 && a.pad == 1 && a.out_mode == 0 && !a.res && !a.post_add && a.out_ld == a.Cout && a.split_m >= a.M &&
-         a.H == a.W && a.Ho == a.Wo && a.H == 2 * a.Ho && a.Wo == 20 && a.Cin >= 16 && a.Cin % 16 == 0 && a.Kpad >= 9 * a.Cin &&
-         s2_ct_for(a.Cout) != 0;
-}
-
 size_t s2_packed_halfs(int Cout, int Cin) { return (size_t)Cout * 9 * Cin + 3 * 2 * 512; }    // + three taps of prefetch past the end
 
 int s2_pack_weights(const f16 *d_w, int Cout, int Cin, int Kpad, f16 *d_out, hipStream_t s, int ct_force, int order) {

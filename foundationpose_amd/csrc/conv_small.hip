@@ -195,28 +195,8 @@ int small_pack_weights(const f16 *d_w, int Cout, int Cin, int Kpad, f16 *d_out, 
   return FP_OK;
 }
 
-// The layers this form runs: the 3x3 stride-1 layers of the trunks (128 / 256 channels on 40x40 maps, 512 on 20x20) and the two
-// stride-2 layers (64 -> 128 on 80x80, 256 -> 512 on 40x40) in the network passes
-// of one or two hypotheses, and stand-alone launches of at most FP_SMALL_MAX_WG workgroups (default 2 per CU), when the caller holds the
-// packed weights (ConvArgs::wsm).  FP_SMALL=0: off (A/B timing).
-bool conv_small_shape(const ConvArgs &a, int num_cu) {
-  static const int on = fp_env_int("FP_SMALL", 1);
-  static const int max_wg = fp_env_int("FP_SMALL_MAX_WG", 0);
-  if (!on) return false;
-  const bool s1 = a.stride == 1 && a.Ho == a.H && a.Wo == a.W && ((a.W == 40 && (a.Cin == 128 || a.Cin == 256)) || (a.W == 20 && a.Cin == 512));
-  const bool s2 = a.stride == 2 && ((a.W == 40 && a.Ho == 20 && a.Wo == 20 && a.Cin == 256) ||   // the 256 -> 512 stride-2 layer between the two halves of encodeAB
-                                    (a.W == 80 && a.Ho == 40 && a.Wo == 40 && a.Cin == 64));     // the 64 -> 128 stride-2 layer behind the stem
-  if (!(a.KH == 3 && a.KW == 3 && a.pad == 1 && a.H == a.W && a.out_mode == 0 && (s1 || s2) && a.Cout % 32 == 0 && a.Kpad == 9 * a.Cin &&
-        a.out_ld % 4 == 0 && a.coff_hi % 4 == 0 && a.M > 0))
-    return false;
-  if (a.hyp > 0 && max_wg == 0) return a.hyp <= 2;           // inside a network pass: by its hypotheses, whatever the launch's share of them
-  const long long wgs = (long long)((a.M + 31) / 32) * (a.Cout / 32);
-  return wgs <= (max_wg > 0 ? max_wg : 2 * num_cu);
-}
-bool conv_small_use(const ConvArgs &a, int num_cu) { return a.wsm != nullptr && conv_small_shape(a, num_cu); }
-
 int launch_conv_small(fp_ctx *ctx, const ConvArgs &a, hipStream_t s) {
-  FP_REQUIRE(conv_small_use(a, ctx->num_cu), "conv3x3 small: unsupported layer");
+  FP_REQUIRE(a.wsm && conv_small_shape(a, ctx->num_cu, conv_knobs()), "conv3x3 small: unsupported layer or no packed weights");
   FP_REQUIRE((double)a.M * a.Cin * 2.0 < 2147483648.0, "conv3x3 small: input tensor too large");
   const int grid = ((a.M + 31) / 32) * (a.Cout / 32);
   constexpr int l1 = SmallCfg<1, 40, 1>::LDS_BYTES, l2 = SmallCfg<2, 40, 1>::LDS_BYTES, l4 = SmallCfg<4, 20, 1>::LDS_BYTES, l2s = SmallCfg<2, 40, 2>::LDS_BYTES;

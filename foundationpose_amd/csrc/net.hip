@@ -126,7 +126,7 @@ int make_conv(fp_net *net, const SD &sd, const std::string &wkey, const std::str
   }
   const int CinP = (Cin < 8) ? 8 : Cin;
   FP_REQUIRE(CinP == 8 || CinP % 32 == 0, "conv '%s': Cin=%d unsupported", wkey.c_str(), Cin);
-  const int Kraw = K * K * CinP, Kpad = (Kraw + 31) / 32 * 32;
+  const int Kpad = conv_kpad(K, K, CinP);
   std::vector<f16> hw((size_t)Cout * Kpad, (f16)0.f);
   std::vector<float> hb(Cout);
   for (int co = 0; co < Cout; ++co) {
@@ -143,21 +143,15 @@ int make_conv(fp_net *net, const SD &sd, const std::string &wkey, const std::str
   out->stride = stride;
   FP_TRY(upload(net, hw, &out->w));
   FP_TRY(upload(net, hb, &out->bias));
-  // fragment-ordered copy for the band kernels: the 3x3 stride-2 layers (conv_s2.hip) and the 128 -> 128 / 256 -> 256 stride-1 layers, which run on 40x40 maps (conv_s1b.hip)
-  if (K == 3 && (stride == 2 || (stride == 1 && CinP == Cout && (Cout == 128 || Cout == 256))) && CinP % 16 == 0 && s2_ct_for(Cout) != 0) {
-    void *pk = nullptr;
-    FP_CHECK_HIP(hipMalloc(&pk, s2_packed_halfs(Cout, CinP) * sizeof(f16)));
-    net->allocs.push_back(pk);
-    out->wpk = (f16 *)pk;
-    FP_TRY(s2_pack_weights(out->w, Cout, CinP, Kpad, out->wpk, nullptr, stride == 1 ? 2 : 0, stride == 1 ? 1 : 0));      // (conv_s1b.hip: 64 couts per wave group)
-    FP_CHECK_HIP(hipStreamSynchronize(nullptr));
-  }
-  if (K == 3 && ((stride == 1 && (CinP == 128 || CinP == 256 || CinP == 512)) || (stride == 2 && (CinP == 256 || CinP == 64))) && Cout % 32 == 0 && Kpad == 9 * CinP) {
-    void *pk = nullptr;
-    FP_CHECK_HIP(hipMalloc(&pk, small_packed_halfs(Cout, CinP) * sizeof(f16)));
-    net->allocs.push_back(pk);
-    out->wsm = (f16 *)pk;
-    FP_TRY(small_pack_weights(out->w, Cout, CinP, Kpad, out->wsm, nullptr));
+  // the packed copies a layer of this shape can ever use: the band kernels' (conv_s2.hip or conv_s1b.hip: one wpk), then conv_small.hip's
+  const unsigned packings = conv_packings(CinP, Cout, K, stride, Kpad);
+  for (const unsigned pk : {packings & (CONV_OFFER_S2 | CONV_OFFER_S1B), packings & CONV_OFFER_SMALL}) {
+    if (!pk) continue;
+    void *d = nullptr;
+    FP_CHECK_HIP(hipMalloc(&d, conv_packed_halfs(pk, Cout, CinP) * sizeof(f16)));
+    net->allocs.push_back(d);
+    (pk == CONV_OFFER_SMALL ? out->wsm : out->wpk) = (f16 *)d;
+    FP_TRY(conv_pack_weights(pk, out->w, Cout, CinP, Kpad, (f16 *)d, nullptr));
     FP_CHECK_HIP(hipStreamSynchronize(nullptr));
   }
   return FP_OK;
@@ -344,8 +338,6 @@ extern "C" int fp_net_rot_dim(const fp_net *net) { return (net && net->kind == F
 // ---------------------------------------------------------------------------------------------
 // forward schedules
 // ---------------------------------------------------------------------------------------------
-int conv_ksplit(const ConvArgs &a, int num_cu);      // conv.hip
-
 namespace {
 
 struct Conv2dCall {
@@ -362,42 +354,37 @@ struct Conv2dCall {
   int tokens = 400;
 };
 
+// `splitk_scratch`: offered to the launch (conv_plan decides whether it splits K); `hyp`: the hypotheses of the pass
 int run_conv(fp_ctx *ctx, const Conv2dCall &c, hipStream_t s, float *splitk_scratch = nullptr, int hyp = 0) {
-  ConvArgs a;
   const ConvW &w = *c.cw;
-  a.in = c.in;
-  a.w = w.w;
-  a.wpk = w.wpk;
-  a.wsm = w.wsm;
-  a.hyp = hyp;
-  a.bias = w.bias;
-  a.res = c.res;
-  a.post_add = c.post_add;
-  a.out = c.out;
-  a.Nimg = c.Nimg;
-  a.H = c.H;
-  a.W = c.W;
-  a.Cin = w.Cin;
-  a.KH = a.KW = w.K;
-  a.stride = w.stride;
-  a.pad = (w.K - 1) / 2;
-  a.Ho = (c.H + 2 * a.pad - w.K) / w.stride + 1;
-  a.Wo = (c.W + 2 * a.pad - w.K) / w.stride + 1;
-  a.Cout = w.Cout;
-  a.Kpad = w.Kpad;
-  a.M = c.Nimg * a.Ho * a.Wo;
-  a.relu = c.relu;
-  a.out_mode = c.out_mode;
-  a.out_ld = c.out_ld ? c.out_ld : w.Cout;
-  a.split_m = c.split_m;
-  a.coff_hi = c.coff_hi;
-  a.post_period = c.post_period;
-  a.tokens = c.tokens;
-  if (splitk_scratch) {
-    a.ksplit = conv_ksplit(a, ctx->num_cu);
-    a.splitk = a.ksplit > 1 ? splitk_scratch : nullptr;
-  }
+  ConvArgs a = conv_args(c.in, c.Nimg, c.H, c.W, w.Cin, w.w, w.bias, w.Cout, w.K, w.K, w.stride, (w.K - 1) / 2, w.Kpad, c.out);
+  a.wpk = w.wpk, a.wsm = w.wsm, a.splitk = splitk_scratch, a.hyp = hyp;
+  a.res = c.res, a.relu = c.relu, a.out_mode = c.out_mode;
+  if (c.out_ld) a.out_ld = c.out_ld;
+  a.split_m = c.split_m, a.coff_hi = c.coff_hi;
+  a.post_add = c.post_add, a.post_period = c.post_period, a.tokens = c.tokens;
   return launch_conv(ctx, a, s);
+}
+
+// encodeA / encoderA of `n` images: the stem (x -> a0; x = nullptr: a0 holds the stem's output already), the stride-2 layer and the two
+// residual blocks.  The last layer writes rows of `out_ld` halfs to `out`: image rows from split_m on go to row (m - split_m), column coff_hi
+// (the channel concat cat((a, b), 1): side A -> channels [0, 128), side B -> [128, 256) of the same rows).
+struct EncodeA {
+  f16 *a0, *a1, *tA, *a2;      // n x 80x80x64, 3 x (n x 40x40x128)
+  float *sk;                   // split-K scratch offered to every launch (nullptr: none)
+  int hyp;                     // hypotheses of the pass
+};
+int encode_a(fp_ctx *ctx, const ConvW *t, const f16 *x, int n, const EncodeA &b, hipStream_t s, f16 *out, int out_ld = 0, int split_m = 0x7fffffff, int coff_hi = 0) {
+  Conv2dCall c;
+  if (x) {
+    c = Conv2dCall{x, n, 160, 160, &t[0]}; c.out = b.a0; FP_TRY(run_conv(ctx, c, s, b.sk, b.hyp));
+  }
+  c = Conv2dCall{b.a0, n, 80, 80, &t[1]}; c.out = b.a1; FP_TRY(run_conv(ctx, c, s, b.sk, b.hyp));
+  c = Conv2dCall{b.a1, n, 40, 40, &t[2]}; c.out = b.tA; FP_TRY(run_conv(ctx, c, s, b.sk, b.hyp));
+  c = Conv2dCall{b.tA, n, 40, 40, &t[3]}; c.res = b.a1; c.out = b.a2; FP_TRY(run_conv(ctx, c, s, b.sk, b.hyp));
+  c = Conv2dCall{b.a2, n, 40, 40, &t[4]}; c.out = b.tA; FP_TRY(run_conv(ctx, c, s, b.sk, b.hyp));
+  c = Conv2dCall{b.tA, n, 40, 40, &t[5]}; c.res = b.a2; c.out = out; c.out_ld = out_ld; c.split_m = split_m; c.coff_hi = coff_hi;
+  return run_conv(ctx, c, s, b.sk, b.hyp);
 }
 
 #define TAKE(ptr, type, count)                                                            \
@@ -443,55 +430,37 @@ int run_trunk(fp_ctx *ctx, const fp_net *net, const f16 *xA, const f16 *xB, int 
     TAKE(tok_, f16, (size_t)N * 400 * 512);
     tok = tok_;
   }
-  // split-K scratch of the 3x3 stride-1 layers for 1 .. 4 hypotheses: 4 shares x the largest fp32 output (256 channels at 40x40)
+  // split-K scratch of the 3x3 stride-1 layers, offered to every launch of a pass of 1 .. 4 hypotheses (conv_plan.h): 4 shares x the largest
+  // fp32 output (256 channels at 40x40)
   float *sk = nullptr;
-  if (N <= 4) {
+  if (N <= CONV_NET_SPLITK_MAX_HYP) {
     TAKE(sk_, float, (size_t)4 * N * 1600 * 256 + (size_t)2 * n2 * 1600 * 128);
     sk = sk_;
   }
-  Conv2dCall c;
   if (sb) {
     // side A alone; side B = the objects' encoded crops (SharedB)
     if (ab) FP_TRY(ab->join());                       // (the crops were encoded on the side stream)
-    c = Conv2dCall{xA, N, 160, 160, &t[0]}; c.out = a0; FP_TRY(run_conv(ctx, c, s, sk, N));
-    c = Conv2dCall{a0, N, 80, 80, &t[1]}; c.out = a1; FP_TRY(run_conv(ctx, c, s, sk, N));
-    c = Conv2dCall{a1, N, 40, 40, &t[2]}; c.out = tA; FP_TRY(run_conv(ctx, c, s, sk, N));
-    c = Conv2dCall{tA, N, 40, 40, &t[3]}; c.res = a1; c.out = a2; FP_TRY(run_conv(ctx, c, s, sk, N));
-    c = Conv2dCall{a2, N, 40, 40, &t[4]}; c.out = tA; FP_TRY(run_conv(ctx, c, s, sk, N));
-    c = Conv2dCall{tA, N, 40, 40, &t[5]}; c.res = a2; c.out = ab0; c.out_ld = 256; FP_TRY(run_conv(ctx, c, s, sk, N));
+    FP_TRY(encode_a(ctx, t, xA, N, EncodeA{a0, a1, tA, a2, sk, N}, s, ab0, 256));
     hipLaunchKernelGGL(broadcast_side_b_kernel, dim3((unsigned)(((long long)N * 1600 * 16 + 255) / 256)), dim3(256), 0, s, sb->feat, *sb, h0, N, ab0);
     FP_CHECK_HIP(hipGetLastError());
   } else if (ab && ab->fan) {
-    // encodeA / encoderA, one chain per side; side `h` owns images [h N, h N + N) of every buffer (and its own half of the split-K scratch)
+    // one chain per side; side `h` owns images [h N, h N + N) of every buffer (and its own half of the split-K scratch)
     for (int h = 0; h < 2; ++h) {
-      hipStream_t st = h == 0 ? s : ab->stream_for(0);
-      float *skh = sk ? sk + (size_t)h * 4 * N * 1600 * 128 : nullptr;
       const size_t o80 = (size_t)h * N * 80 * 80 * 64, o40 = (size_t)h * N * 1600 * 128;
-      c = Conv2dCall{h == 0 ? xA : xB, N, 160, 160, &t[0]}; c.out = a0 + o80; FP_TRY(run_conv(ctx, c, st, skh, N));
-      c = Conv2dCall{a0 + o80, N, 80, 80, &t[1]}; c.out = a1 + o40; FP_TRY(run_conv(ctx, c, st, skh, N));
-      c = Conv2dCall{a1 + o40, N, 40, 40, &t[2]}; c.out = tA + o40; FP_TRY(run_conv(ctx, c, st, skh, N));
-      c = Conv2dCall{tA + o40, N, 40, 40, &t[3]}; c.res = a1 + o40; c.out = a2 + o40; FP_TRY(run_conv(ctx, c, st, skh, N));
-      c = Conv2dCall{a2 + o40, N, 40, 40, &t[4]}; c.out = tA + o40; FP_TRY(run_conv(ctx, c, st, skh, N));
-      // the channel concat cat((a,b),1): side A -> channels [0,128), side B -> [128,256) of the same rows
-      c = Conv2dCall{tA + o40, N, 40, 40, &t[5]}; c.res = a2 + o40; c.out = ab0; c.out_ld = 256;
-      if (h == 1) c.split_m = 0, c.coff_hi = 128;
-      FP_TRY(run_conv(ctx, c, st, skh, N));
+      const EncodeA b{a0 + o80, a1 + o40, tA + o40, a2 + o40, sk ? sk + (size_t)h * 4 * N * 1600 * 128 : nullptr, N};
+      FP_TRY(encode_a(ctx, t, h == 0 ? xA : xB, N, b, h == 0 ? s : ab->stream_for(0), ab0, 256, h == 0 ? 0x7fffffff : 0, h == 0 ? 0 : 128));
     }
     FP_TRY(ab->join());
   } else {
-  // encodeA / encoderA on cat([A,B],0)
-  // (A and B halves of the net tensor may come from different places when the batch is processed in chunks)
-  c = Conv2dCall{xA, N, 160, 160, &t[0]}; c.out = a0; FP_TRY(run_conv(ctx, c, s, sk, N));
-  c = Conv2dCall{xB, N, 160, 160, &t[0]}; c.out = a0 + (size_t)N * 80 * 80 * 64; FP_TRY(run_conv(ctx, c, s, sk, N));
-  c = Conv2dCall{a0, (int)n2, 80, 80, &t[1]}; c.out = a1; FP_TRY(run_conv(ctx, c, s, sk, N));
-  c = Conv2dCall{a1, (int)n2, 40, 40, &t[2]}; c.out = tA; FP_TRY(run_conv(ctx, c, s, sk, N));
-  c = Conv2dCall{tA, (int)n2, 40, 40, &t[3]}; c.res = a1; c.out = a2; FP_TRY(run_conv(ctx, c, s, sk, N));
-  c = Conv2dCall{a2, (int)n2, 40, 40, &t[4]}; c.out = tA; FP_TRY(run_conv(ctx, c, s, sk, N));
-  // last conv of encodeA writes the channel-concat cat((a,b),1) directly: image n<N -> channels [0,128), n>=N -> [128,256)
-  c = Conv2dCall{tA, (int)n2, 40, 40, &t[5]}; c.res = a2; c.out = ab0; c.out_ld = 256; c.split_m = N * 1600; c.coff_hi = 128;
-  FP_TRY(run_conv(ctx, c, s, sk, N));
+    // one chain on cat([A,B],0): the two stems apart (the A and B halves of the net tensor may come from different places when the batch is
+    // processed in chunks), then 2N images per launch; image n < N -> channels [0,128), n >= N -> [128,256)
+    Conv2dCall c;
+    c = Conv2dCall{xA, N, 160, 160, &t[0]}; c.out = a0; FP_TRY(run_conv(ctx, c, s, sk, N));
+    c = Conv2dCall{xB, N, 160, 160, &t[0]}; c.out = a0 + (size_t)N * 80 * 80 * 64; FP_TRY(run_conv(ctx, c, s, sk, N));
+    FP_TRY(encode_a(ctx, t, nullptr, (int)n2, EncodeA{a0, a1, tA, a2, sk, N}, s, ab0, 256, N * 1600, 128));
   }
   // encodeAB
+  Conv2dCall c;
   c = Conv2dCall{ab0, N, 40, 40, &t[6]}; c.out = tB; FP_TRY(run_conv(ctx, c, s, sk, N));
   c = Conv2dCall{tB, N, 40, 40, &t[7]}; c.res = ab0; c.out = ab1; FP_TRY(run_conv(ctx, c, s, sk, N));
   c = Conv2dCall{ab1, N, 40, 40, &t[8]}; c.out = tB; FP_TRY(run_conv(ctx, c, s, sk, N));
@@ -579,20 +548,12 @@ extern "C" int fp_refine_forward(fp_ctx *ctx, const fp_net *net, const void *d_n
 // encodeA of `n_groups` observed crops (one per object), with the kernels the batch of `hyp` hypotheses takes for these layers (run_conv's
 // `hyp`: the few-image forms are chosen by the pass, not by the launch) -> feat [n_groups][1600][128]
 int fp_encode_side_b(fp_ctx *ctx, const fp_net *net, const f16 *xB, int n_groups, int hyp, f16 *feat, hipStream_t s) {
-  const ConvW *t = net->trunk;
   const int G = n_groups;
   TAKE(a0, f16, (size_t)G * 80 * 80 * 64);
   TAKE(a1, f16, (size_t)G * 1600 * 128);
   TAKE(tA, f16, (size_t)G * 1600 * 128);
   TAKE(a2, f16, (size_t)G * 1600 * 128);
-  Conv2dCall c;
-  c = Conv2dCall{xB, G, 160, 160, &t[0]}; c.out = a0; FP_TRY(run_conv(ctx, c, s, nullptr, hyp));
-  c = Conv2dCall{a0, G, 80, 80, &t[1]}; c.out = a1; FP_TRY(run_conv(ctx, c, s, nullptr, hyp));
-  c = Conv2dCall{a1, G, 40, 40, &t[2]}; c.out = tA; FP_TRY(run_conv(ctx, c, s, nullptr, hyp));
-  c = Conv2dCall{tA, G, 40, 40, &t[3]}; c.res = a1; c.out = a2; FP_TRY(run_conv(ctx, c, s, nullptr, hyp));
-  c = Conv2dCall{a2, G, 40, 40, &t[4]}; c.out = tA; FP_TRY(run_conv(ctx, c, s, nullptr, hyp));
-  c = Conv2dCall{tA, G, 40, 40, &t[5]}; c.res = a2; c.out = feat; FP_TRY(run_conv(ctx, c, s, nullptr, hyp));
-  return FP_OK;
+  return encode_a(ctx, net->trunk, xB, G, EncodeA{a0, a1, tA, a2, nullptr, hyp}, s, feat);      // (no split-K scratch on this path)
 }
 
 int fp_refine_forward_ab(fp_ctx *ctx, const fp_net *net, const void *d_net_in, int N, float *d_trans, float *d_rot, hipStream_t s, StreamFanout *ab,

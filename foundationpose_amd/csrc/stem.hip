@@ -17,7 +17,7 @@
 #include "device_util.h"
 
 #define ST_THREADS 512
-#define ST_BLK 16                         // output block edge
+// (ST_BLK = 16, the output block edge: conv_plan.h)
 #define ST_REG 37                         // input region edge: 2*16 + 5
 #define ST_ROW_SLOTS 40                   // 16-byte slots per region row: plane 0 (even columns) 20 + plane 1 (odd columns) 20
 #define ST_REGION_BYTES (ST_REG * ST_ROW_SLOTS * 16)      // 23680
@@ -161,14 +161,10 @@ __global__ __launch_bounds__(ST_THREADS, 1) void stem7x7_kernel(ConvArgs p, cons
   }
 }
 
-bool stem_supported(const ConvArgs &a) {
-  return a.KH == 7 && a.KW == 7 && a.stride == 2 && a.pad == 3 && a.Cin == 8 && a.Cout == 64 && a.Kpad >= 400 && a.out_mode == 0 && !a.res &&
-         !a.post_add && a.out_ld == 64 && a.split_m >= a.M && a.Ho % ST_BLK == 0 && a.Wo % ST_BLK == 0 && a.H == 2 * a.Ho && a.W == 2 * a.Wo;
-}
-
 void stem_kernel_lds(std::vector<KernelLds> &v) { v.push_back({(const void *)stem7x7_kernel, ST_LDS_BYTES}); }
 
 int launch_stem(fp_ctx *ctx, const ConvArgs &a, hipStream_t s) {
+  FP_REQUIRE(stem_supported(a), "launch_stem: unsupported layer");
   const int blocks_x = a.Wo / ST_BLK, per_img = blocks_x * (a.Ho / ST_BLK), n_blocks = a.Nimg * per_img, n_pairs = (n_blocks + 1) / 2;
   const int grid = n_pairs < ctx->num_cu ? n_pairs : ctx->num_cu;
   hipLaunchKernelGGL(stem7x7_kernel, dim3(grid), dim3(ST_THREADS), ST_LDS_BYTES, s, a, (const f16 *)ctx->zero_page, n_pairs, blocks_x, per_img, n_blocks);

@@ -501,9 +501,9 @@ def _pack_conv_weight(w, cin_pad):
 
 
 @pytest.mark.parametrize('shape', [
-  # (N, H, W, Cin, Cout, k, stride, residual, relu).  The form named is the one the fp16 output runs on 256 CUs (fp_conv2d_f16, launch_conv,
-  # conv_small_shape, conv_ksplit, halo_plan); the fp32 output of every shape runs the generic conv_igemm2_kernel.  tests/tools/conv_ref.py
-  # lists one case per form and instantiation.
+  # (N, H, W, Cin, Cout, k, stride, residual, relu).  The form named is the one the fp16 output runs on 256 CUs (conv_plan, csrc/conv_plan.h);
+  # the fp32 output of every shape runs the generic conv_igemm2_kernel.  tests/tools/conv_ref.py lists one case per form and instantiation,
+  # and tests/test_conv_plan_host.py asserts the forms of those cases and what FP_SMALL=0 moves.
   (3, 40, 40, 128, 128, 3, 1, True, True),          # conv_halo.hip, tail tiles only: 38 tiles of 128 pixels (600 workgroups would be too many for conv_small.hip, 4 chunks too few to split K)
   (2, 40, 40, 256, 256, 3, 1, False, True),         # conv_halo.hip split-K, 4 shares of 2 chunks + finishing pass (800 workgroups: not conv_small.hip)
   (2, 80, 80, 64, 128, 3, 2, False, True),          # conv_small.hip <1, 80, 2, 4>: 400 workgroups, tiles that straddle rows and the two images

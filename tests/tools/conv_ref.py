@@ -9,8 +9,9 @@ ACTIVATIONS and nonzero garbage WEIGHTS.  Every partial sum is an integer below 
 with |value| <= 2048 is exact in fp16: whatever form runs - one launch, K split over waves, split-K with its finishing pass - has to give the integer reference bit for bit, in fp16 and in fp32.  The reference is
 torch's float32 conv2d; the host test shows on every case that it equals the float64 one and that max |conv + bias + residual| <= 2048.
 
-The form each case runs was worked out from fp_conv2d_f16, launch_conv, conv_small_shape, conv_ksplit, conv_halo_ksplit and halo_plan for the
-256 CUs of an MI355X (`form` below; the kernel names a profiler shows are in the docstring of tests/test_gpu_conv_numerics.py):
+The form each case runs (`form` below) was worked out by hand for the 256 CUs of an MI355X, from the rules that csrc/conv_plan.h now states in
+one place; tests/test_conv_plan_host.py plans every case with that header and asserts the form named here (the kernel names a profiler shows are
+in the docstring of tests/test_gpu_conv_numerics.py):
   conv_small.hip takes a launch of at most 2 x 256 workgroups of 32 pixels x 32 couts: two images of every layer but 256 -> 256 (one).
   halo split-K: n_q = ceil(M / 128) (Cout / 128) quarter tiles with 4 n_q <= 256 and at least 8 chunks of 32 input channels.  512 channels at
     20x20: up to FIVE images (16 x 4 x 4 = 256) - so the smallest batch that runs one-launch tail tiles there is 6, not 5.
