@@ -759,13 +759,7 @@ static size_t pass_arena_bytes(int N, size_t render_scratch) {
   return (size_t)N * ((size_t)1 << 20) + ((size_t)1 << 20) + render_scratch + fp_arena_inner_bytes(N);
 }
 
-// One run of like objects in a batch that the trunk does not cut in two by hypotheses: the rendered side (crop window -> rasteriser ->
-// encodeA) and the observed side (crop window -> observed crop -> encodeA) are two chains on two streams up to the channel concat
-// (run_trunk): side B does not wait for the rasteriser.  Bit-identical to one chain.
-static bool two_side_chains(int n_runs, int N) {
-  static const bool one_chain = fp_env_int("FP_ONE_CHAIN", 0) != 0;      // FP_ONE_CHAIN=1: the two sides of encodeA as one chain (A/B timing; identical results)
-  return n_runs == 1 && N < fp_trunk_split_min() && !one_chain;
-}
+static_assert(FP_REFINE_SHARED_TRANSLATION == PASS_FLAG_SHARED_TRANSLATION && FP_NET_REFINE == PASS_REFINE && FP_NET_SCORE == PASS_SCORE, "pass_plan.h restates them");
 
 struct NetInputOpts {
   int mode;                  // of the observed crop (fp_crop_observed)
@@ -781,13 +775,15 @@ struct NetInputOpts {
 };
 
 // The input of ONE network pass over every object: per run of like objects the crop windows (tf, bbox) and the render (side A: net_in[0, N))
-// on the run's stream, per object the observed crop (side B: net_in[N, 2N)).  `ab` (set for two side chains or a shared side B; forked
-// behind the crop windows) is left for the forward pass to join; the runs' streams are joined here.
-static int build_net_input(fp_ctx *ctx, const fp_object_batch *objs, const std::vector<RenderRun> &runs, int N, const float *d_poses,
+// on the run's stream, per object the observed crop (side B: net_in[N, 2N)).  `ab` (set for two side chains - PassPlan::fork_sides: the
+// rendered side (crop window -> rasteriser -> encodeA) and the observed side (crop window -> observed crop -> encodeA) on two streams up to
+// the channel concat of run_trunk, bit-identical to one chain - or a shared side B; forked behind the crop windows) is left for the forward
+// pass to join; the runs' streams are joined here.
+static int build_net_input(fp_ctx *ctx, const fp_object_batch *objs, const std::vector<RenderRun> &runs, int N, const PassPlan &plan, const float *d_poses,
                            const NetInputOpts &op, float *tf, float *bbox, f16 *net_in, char *rscratch, hipStream_t s,
                            std::unique_ptr<StreamFanout> &ab) {
   const size_t img = (size_t)160 * 160 * 8;
-  const bool two_sides = two_side_chains((int)runs.size(), N);
+  const bool two_sides = plan.fork_sides;
   StreamFanout fo(ctx, s, two_sides ? 1 : (int)runs.size());
   if (op.sb) op.sb->n_groups = 0;
   int k = 0;
@@ -861,11 +857,9 @@ static int refine_predict_impl(fp_ctx *ctx, const fp_net *net, const fp_object_b
   const int rot_dim = fp_net_rot_dim(net);
   std::vector<RenderRun> runs;          // once per call: every iteration walks the same runs over the same scratch blocks
   const size_t rs_total = render_runs(ctx, objs, n_obj, &runs);
-  const int n_runs = (int)runs.size();
   FP_TRY(fp_arena_ensure(ctx, pass_arena_bytes(N, rs_total) + (size_t)n_obj * ((size_t)4 << 20)));
   ArenaScope scope(ctx->arena);
   const size_t img = (size_t)160 * 160 * 8;
-  static const bool no_shared = fp_env_set("FP_NO_SHARED_B");       // A/B knob: ignore FP_REFINE_SHARED_TRANSLATION (identical results)
   TAKE(tf, float, (size_t)N * 9);
   TAKE(bbox, float, (size_t)N * 4);
   TAKE(trans, float, (size_t)N * 3);
@@ -873,31 +867,29 @@ static int refine_predict_impl(fp_ctx *ctx, const fp_net *net, const fp_object_b
   TAKE(net_in, f16, (size_t)2 * N * img);
   float *tr = d_trans ? d_trans : trans, *ro = d_rot ? d_rot : rot;
   TAKE(rscratch, char, rs_total);                              // reused by every iteration
-  // One run of like objects (one camera, one mesh, one diameter): the heads' token means, the pose update and the crop windows of
-  // the next iteration are ONE launch behind the heads (refine_tail_kernel) instead of four.  Bit-identical (FP_TAIL_SPLIT=1: the four).
-  static const bool tail_split = fp_env_set("FP_TAIL_SPLIT");
-  const bool fused_tail = n_runs == 1 && !tail_split && fp_hyp_chunk(N) == N;
-  // FP_REFINE_SHARED_TRANSLATION: in the FIRST iteration every hypothesis of an object has the crop window of the object's first one, so
+  // plan.fused_tail - one run of like objects (one camera, one mesh, one diameter): the heads' token means, the pose update and the crop windows of
+  // the next iteration are ONE launch behind the heads (refine_tail_kernel) instead of four.  Bit-identical.
+  // plan.shared_b - FP_REFINE_SHARED_TRANSLATION: in the FIRST iteration every hypothesis of an object has the crop window of the object's first one, so
   // side B - the observed crop and its way through encodeA - is ONE image per object: cropped and encoded once on the side stream
   // (fp_encode_side_b), copied into the B half of the channel concat by run_trunk.  One run of like objects, at most 8 of them, no
   // hypothesis chunks; otherwise the plain pass runs.
   int n_live = 0;
   for (int o = 0; o < n_obj; ++o) n_live += objs[o].n > 0;
-  const bool shared0 = (flags & FP_REFINE_SHARED_TRANSLATION) && !no_shared && n_runs == 1 && n_live <= 8 && fp_hyp_chunk(N) == N;
+  const PassPlan plan = pass_plan(PASS_REFINE, N, (int)runs.size(), n_live, flags, pass_knobs());
   NetInputOpts op = {0, 0.001f, cfg->crop_ratio, cfg->normalize_xyz, false, net, nullptr, nullptr, nullptr};
   SharedB sb;
   sb.feat = nullptr;
-  if (shared0) {
+  if (plan.shared_b) {
     TAKE(xB1, f16, (size_t)n_live * img);
     TAKE(featB, f16, (size_t)n_live * 1600 * 128);
     op.xB1 = xB1, op.featB = featB, sb.feat = featB;
   }
   for (int it = 0; it < iteration; ++it) {
     std::unique_ptr<StreamFanout> ab;
-    op.windows_written = fused_tail && it > 0;       // (from the second iteration on the previous pass' tail has written the windows)
-    op.sb = shared0 && it == 0 ? &sb : nullptr;
-    FP_TRY(build_net_input(ctx, objs, runs, N, d_poses, op, tf, bbox, net_in, rscratch, s, ab));
-    if (fused_tail) {
+    op.windows_written = plan.fused_tail && it > 0;       // (from the second iteration on the previous pass' tail has written the windows)
+    op.sb = plan.shared_b && it == 0 ? &sb : nullptr;
+    FP_TRY(build_net_input(ctx, objs, runs, N, plan, d_poses, op, tf, bbox, net_in, rscratch, s, ab));
+    if (plan.fused_tail) {
       const fp_object_batch &ob = objs[runs[0].o0];
       RefineTailArgs t = fill_refine_tail(cfg, ob.K, ob.mesh_diameter, tf, bbox, d_poses, it, iteration);
       t.trans_scale = cfg->normalize_xyz ? (float)(ob.mesh_diameter / 2) : 1.f;
@@ -908,7 +900,7 @@ static int refine_predict_impl(fp_ctx *ctx, const fp_net *net, const fp_object_b
       FP_TRY(fp_refine_forward_ab(ctx, net, net_in, N, tr, ro, s, ab.get(), &t, op.sb));
       continue;
     }
-    FP_REQUIRE(!fin, "refine pass: the centred poses come from the fused tail launch (one run of like objects, FP_TAIL_SPLIT unset)");
+    FP_REQUIRE(!fin, "refine pass: the centred poses come from the fused tail launch (one run of like objects, no chunks, the tail not split by its knob)");
     FP_TRY(fp_refine_forward_ab(ctx, net, net_in, N, tr, ro, s, ab.get(), nullptr, op.sb));     // ONE network pass for every object (joins `ab`)
     // pose update: one launch per run of objects with the same translation scale (one launch when they share a mesh).  Not the render
     // runs: the key here is the scale alone, and trans_rep='deepim' also needs the object's intrinsics (one launch per object)
@@ -964,7 +956,8 @@ static int score_features_impl(fp_ctx *ctx, const fp_net *net, const fp_object_b
   TAKE(rscratch, char, rs_total);
   std::unique_ptr<StreamFanout> ab;
   const NetInputOpts op = {1, 0.1f, crop_ratio, normalize_xyz, false, nullptr, nullptr, nullptr, nullptr};
-  FP_TRY(build_net_input(ctx, objs, runs, N, d_poses, op, tf, bbox, net_in, rscratch, s, ab));
+  const PassPlan plan = pass_plan(PASS_SCORE, N, (int)runs.size(), n_obj, 0, pass_knobs());
+  FP_TRY(build_net_input(ctx, objs, runs, N, plan, d_poses, op, tf, bbox, net_in, rscratch, s, ab));
   return fp_score_features_ab(ctx, net, net_in, N, d_feats, s, ab.get(), feat_ld, with_pose ? d_poses : nullptr);
 }
 
@@ -1105,7 +1098,7 @@ static int track_objects_pass(fp_ctx *ctx, const fp_track_objects_args *a, const
   for (int i = 0; i < 9; ++i) ca.K[i] = a->K[i];
   ca.H = a->H, ca.W = a->W, ca.N = N, ca.Ho = 160, ca.Wo = 160, ca.mode = 0, ca.normalize_xyz = cfg->normalize_xyz, ca.out_fmt = 1;
   ca.out = net_in + (size_t)N * img;
-  const bool two_sides = two_side_chains(1, N);       // the objects share the camera: one run, as in the one-object pass
+  const bool two_sides = pass_plan(PASS_REFINE, N, 1, N, 0, pass_knobs()).fork_sides;       // the objects share the camera: one run, as in the one-object pass
   for (int it = 0; it < a->iteration; ++it) {
     if (it == 0)         // (from the second iteration on the previous pass' tail has written the windows)
       FP_TRY(launch_crop_window_objects(pose_in, a->K, cfg->crop_ratio, diam_d, N, 160, 160, poses, tf, bbox, s));
@@ -1153,7 +1146,7 @@ extern "C" int fp_track_objects(fp_ctx *ctx, const fp_track_objects_args *a, voi
     FP_REQUIRE(ob.mesh && ob.d_pose && ob.d_pose_of_mesh, "fp_track_objects: object %d has a null field", o);
     FP_REQUIRE(ob.mesh_diameter > 0, "fp_track_objects: object %d has a bad mesh_diameter", o);
   }
-  FP_REQUIRE(fp_hyp_chunk(a->n_obj) == a->n_obj, "fp_track_objects: FP_CHUNK cuts the pass of %d images (the fused tail needs it whole)", a->n_obj);
+  FP_REQUIRE(hyp_chunk(a->n_obj, pass_knobs()) == a->n_obj, "fp_track_objects: the chunk knob cuts the pass of %d images (the fused tail needs it whole)", a->n_obj);
   hipStream_t s = (hipStream_t)stream;
   // the depth prelude of fp_track_frame, once for all objects
   double K32[9];

@@ -535,8 +535,7 @@ void attn_kernel_lds(std::vector<KernelLds> &v) {
 int launch_attention(fp_ctx *ctx, const f16 *qk, const f16 *vt, int B, int T, f16 *out, hipStream_t s) {
   FP_REQUIRE(T > 0 && T <= AT_MAXT, "attention: T=%d must be in [1,%d]", T, AT_MAXT);
   if (B == 0) return FP_OK;
-  static const int small_max = fp_env_int("FP_ATTN_SMALL", 2);      // hypotheses up to which the split-K form runs (0: off)
-  if (B <= small_max) {
+  if (attn_form(B, pass_knobs()) == ATTN_SMALL) {
     ProfScope ps(ctx, s, "attention", 4.0 * B * 4 * (double)T * T * AT_DH);
     hipLaunchKernelGGL(attention_small_kernel, dim3(((T + 31) / 32) * 4 * B), dim3(FS_WAVES * 64), FS_LDS_BYTES, s, qk, vt, T, out);
     FP_CHECK_HIP(hipGetLastError());

@@ -11,6 +11,9 @@
 #include <map>
 
 #include "../../include/foundationpose_amd.h"
+// The convolutions: ConvArgs, the plan that picks the kernel form of a launch and every shape predicate are in conv_plan.h; the schedule of a
+// network pass and the forms of its other stages in pass_plan.h
+#include "pass_plan.h"
 
 #ifndef FP_F16_TYPEDEF
 #define FP_F16_TYPEDEF
@@ -183,7 +186,7 @@ struct fp_ctx {
   // side streams for the per-object stages (crop window, render, observed crop) of a multi-object pass: with 8 objects
   // x 32 hypotheses a render launch fills a quarter of the chip, so the objects' stages run side by side and join the
   // launch stream before the (single) network pass
-  static constexpr int NSIDE = 8;
+  static constexpr int NSIDE = PASS_SIDE_STREAMS;
   hipStream_t side[NSIDE] = {};
   hipEvent_t ev_fork = nullptr, ev_join[NSIDE] = {};
   bool side_ready = false;
@@ -250,11 +253,9 @@ struct StreamFanout {
 
 
 // net.hip: the network passes with the two sides of encodeA as two chains (`ab` forked by the caller: side B's input is produced on
-// ab->stream_for(0), side A's on `s`; nullptr: one chain); batches below fp_trunk_split_min() hypotheses only (larger ones are cut in two by hypotheses)
+// ab->stream_for(0), side A's on `s`; nullptr: one chain); batches below trunk_split_min() hypotheses only (larger ones are cut in two by hypotheses)
 struct fp_net;
-int fp_trunk_split_min();
 struct RefineTailArgs;
-int fp_hyp_chunk(int n_total);             // hypotheses per network pass (FP_CHUNK; default: the whole batch)
 // `tail` (optional; pose / window fields filled by the caller, head fields by the forward pass): the heads' token means, the pose update
 // and the next crop windows as ONE launch behind the join of the heads (refine_tail_kernel) instead of two mean_head launches here
 // `sb` (optional): side B of this pass is ONE observed crop per object - every hypothesis of an object has the same crop window (the first
@@ -339,8 +340,6 @@ void raster_kernel_lds(std::vector<KernelLds> &v);      // raster.hip
 int fp_set_kernel_attributes(fp_ctx *ctx);              // api.hip: all of the above on ctx->device
 
 // ---- kernel launchers implemented in the .hip files ----
-// The convolutions: ConvArgs, the plan that picks the kernel form of a launch and every shape predicate are in conv_plan.h
-#include "conv_plan.h"
 int launch_conv(fp_ctx *ctx, const ConvArgs &a, hipStream_t s);      // conv.hip: offer from a.wsm / a.wpk / a.splitk, conv_plan, launch
 // the per-form launchers, next to their kernels; each checks that the layer is one its kernel runs
 int launch_conv_small(fp_ctx *ctx, const ConvArgs &a, hipStream_t s);                          // conv_small.hip
@@ -385,8 +384,7 @@ struct TokGemmArgs {
 enum { TG_EPI_ROWS = 0, TG_EPI_VT = 1, TG_EPI_LN = 2, TG_EPI_LNSUM = 3 };
 int launch_tok_gemm(fp_ctx *ctx, const TokGemmArgs &a, int epi, hipStream_t s);
 // tok_qkv.hip: the in-projections - all blocks over a resident 128-token tile (fp16 rows or the transposed V image per block)
-int tok_qkv_small_max();        // passes of up to this many hypotheses run tok_qkv_small_kernel (FP_QKV_SMALL)
-int launch_tok_qkv(fp_ctx *ctx, const TokGemmArgs &a, hipStream_t s, int hyp = 0);      // hyp: hypotheses of the network pass (1 .. 2: tok_qkv_small_kernel; 0: a stand-alone call)
+int launch_tok_qkv(fp_ctx *ctx, const TokGemmArgs &a, hipStream_t s, int hyp = 0);      // hyp: images of the forward body (qkv_form: 1 .. 2 tok_qkv_small_kernel; 0: a stand-alone call)
 // head_mlp.hip: out-projection + LayerNorm1 + linear1 + ReLU + linear2 + LayerNorm2 statistics of one transformer head in one launch
 struct HeadMlpArgs {
   const f16 *att, *tok;        // [M][512]: attention output, residual tokens

@@ -47,20 +47,24 @@ struct fp_net {
   std::vector<void *> allocs;
 };
 
-// Hypotheses per network pass: the whole batch.  FP_CHUNK=n (environment, experiments only) splits it.
-int fp_hyp_chunk(int n_total) {
-  static int env = fp_env_int("FP_CHUNK", -1);
-  int ch = env >= 0 ? env : 0;
-  if (ch <= 0 || ch > n_total) ch = n_total;
-  return ch;
-}
-
-int fp_trunk_split_min() {
-  // from 48 hypotheses on (round 4, refine x5 + score of one object: 40 hypotheses 6.55 ms as one batch / 7.08 split, 48: 7.82 / 7.55, 56: 8.87 / 8.17,
-  // 63: 9.85 / 9.23, 64: 9.95 / 9.32, 96: 13.97 / 13.71; scripts/bench_nhyp.py): below, the halves' tiles get too small
-  static const int n_min = fp_env_int("FP_TRUNK_MIN", 48);
-  static const int n_streams = fp_env_int("FP_TRUNK_STREAMS", 2);
-  return n_streams < 2 ? 0x7fffffff : n_min;
+// The knobs of pass_plan.h: the process's values, read from the environment once (the only reader of these eleven names)
+const PassKnobs &pass_knobs() {
+  static const PassKnobs knobs = [] {
+    PassKnobs k;
+    k.chunk = (int)fp_env_int("FP_CHUNK", k.chunk);
+    k.trunk_min = (int)fp_env_int("FP_TRUNK_MIN", k.trunk_min);
+    k.trunk_streams = (int)fp_env_int("FP_TRUNK_STREAMS", k.trunk_streams);
+    k.one_chain = fp_env_int("FP_ONE_CHAIN", 0) != 0;
+    k.no_shared_b = fp_env_set("FP_NO_SHARED_B");
+    k.tail_split = fp_env_set("FP_TAIL_SPLIT");
+    k.qkv_small = (int)fp_env_int("FP_QKV_SMALL", k.qkv_small);
+    k.qkv64 = fp_env_set("FP_QKV64");
+    k.attn_small = (int)fp_env_int("FP_ATTN_SMALL", k.attn_small);
+    k.headmlp64 = fp_env_set("FP_HEADMLP64");
+    k.heads_serial = fp_env_set("FP_HEADS_SERIAL");
+    return k;
+  }();
+  return knobs;
 }
 
 namespace {
@@ -411,9 +415,11 @@ __global__ __launch_bounds__(256) void broadcast_side_b_kernel(const f16 *__rest
 // pass side A waits for the rasteriser while side B (observed crop -> stem -> ...) does not.  The caller has forked `ab` (two chains),
 // side B's input is produced on ab->stream_for(0), side A's on `s`; the chains join in front of encodeAB.  Each side's launches are the
 // 2N-image launches cut in two: a pixel's arithmetic does not depend on its batch, so the tokens are those of the single chain bit for bit.
-int run_trunk(fp_ctx *ctx, const fp_net *net, const f16 *xA, const f16 *xB, int N, f16 **tokens_out, hipStream_t s, f16 *tok_dst = nullptr,
+// `part`: its images, the hyp its convolutions are planned with and the scratch offer (trunk_part, pass_plan.h); h0: its first hypothesis in the pass
+int run_trunk(fp_ctx *ctx, const fp_net *net, const f16 *xA, const f16 *xB, const TrunkPart &part, f16 **tokens_out, hipStream_t s, f16 *tok_dst = nullptr,
               StreamFanout *ab = nullptr, const SharedB *sb = nullptr, int h0 = 0) {
   const ConvW *t = net->trunk;
+  const int N = part.n, hyp = part.conv_hyp;
   const size_t n2 = (size_t)2 * N;
   TAKE(a0, f16, n2 * 80 * 80 * 64);
   TAKE(a1, f16, n2 * 40 * 40 * 128);
@@ -430,24 +436,24 @@ int run_trunk(fp_ctx *ctx, const fp_net *net, const f16 *xA, const f16 *xB, int 
     TAKE(tok_, f16, (size_t)N * 400 * 512);
     tok = tok_;
   }
-  // split-K scratch of the 3x3 stride-1 layers, offered to every launch of a pass of 1 .. 4 hypotheses (conv_plan.h): 4 shares x the largest
+  // split-K scratch of the 3x3 stride-1 layers, offered to every launch of a part of 1 .. 4 hypotheses (net_offers_splitk): 4 shares x the largest
   // fp32 output (256 channels at 40x40)
   float *sk = nullptr;
-  if (N <= CONV_NET_SPLITK_MAX_HYP) {
+  if (part.splitk) {
     TAKE(sk_, float, (size_t)4 * N * 1600 * 256 + (size_t)2 * n2 * 1600 * 128);
     sk = sk_;
   }
   if (sb) {
     // side A alone; side B = the objects' encoded crops (SharedB)
     if (ab) FP_TRY(ab->join());                       // (the crops were encoded on the side stream)
-    FP_TRY(encode_a(ctx, t, xA, N, EncodeA{a0, a1, tA, a2, sk, N}, s, ab0, 256));
+    FP_TRY(encode_a(ctx, t, xA, N, EncodeA{a0, a1, tA, a2, sk, hyp}, s, ab0, 256));
     hipLaunchKernelGGL(broadcast_side_b_kernel, dim3((unsigned)(((long long)N * 1600 * 16 + 255) / 256)), dim3(256), 0, s, sb->feat, *sb, h0, N, ab0);
     FP_CHECK_HIP(hipGetLastError());
   } else if (ab && ab->fan) {
     // one chain per side; side `h` owns images [h N, h N + N) of every buffer (and its own half of the split-K scratch)
     for (int h = 0; h < 2; ++h) {
       const size_t o80 = (size_t)h * N * 80 * 80 * 64, o40 = (size_t)h * N * 1600 * 128;
-      const EncodeA b{a0 + o80, a1 + o40, tA + o40, a2 + o40, sk ? sk + (size_t)h * 4 * N * 1600 * 128 : nullptr, N};
+      const EncodeA b{a0 + o80, a1 + o40, tA + o40, a2 + o40, sk ? sk + (size_t)h * 4 * N * 1600 * 128 : nullptr, hyp};
       FP_TRY(encode_a(ctx, t, h == 0 ? xA : xB, N, b, h == 0 ? s : ab->stream_for(0), ab0, 256, h == 0 ? 0x7fffffff : 0, h == 0 ? 0 : 128));
     }
     FP_TRY(ab->join());
@@ -455,49 +461,46 @@ int run_trunk(fp_ctx *ctx, const fp_net *net, const f16 *xA, const f16 *xB, int 
     // one chain on cat([A,B],0): the two stems apart (the A and B halves of the net tensor may come from different places when the batch is
     // processed in chunks), then 2N images per launch; image n < N -> channels [0,128), n >= N -> [128,256)
     Conv2dCall c;
-    c = Conv2dCall{xA, N, 160, 160, &t[0]}; c.out = a0; FP_TRY(run_conv(ctx, c, s, sk, N));
-    c = Conv2dCall{xB, N, 160, 160, &t[0]}; c.out = a0 + (size_t)N * 80 * 80 * 64; FP_TRY(run_conv(ctx, c, s, sk, N));
-    FP_TRY(encode_a(ctx, t, nullptr, (int)n2, EncodeA{a0, a1, tA, a2, sk, N}, s, ab0, 256, N * 1600, 128));
+    c = Conv2dCall{xA, N, 160, 160, &t[0]}; c.out = a0; FP_TRY(run_conv(ctx, c, s, sk, hyp));
+    c = Conv2dCall{xB, N, 160, 160, &t[0]}; c.out = a0 + (size_t)N * 80 * 80 * 64; FP_TRY(run_conv(ctx, c, s, sk, hyp));
+    FP_TRY(encode_a(ctx, t, nullptr, (int)n2, EncodeA{a0, a1, tA, a2, sk, hyp}, s, ab0, 256, N * 1600, 128));
   }
   // encodeAB
   Conv2dCall c;
-  c = Conv2dCall{ab0, N, 40, 40, &t[6]}; c.out = tB; FP_TRY(run_conv(ctx, c, s, sk, N));
-  c = Conv2dCall{tB, N, 40, 40, &t[7]}; c.res = ab0; c.out = ab1; FP_TRY(run_conv(ctx, c, s, sk, N));
-  c = Conv2dCall{ab1, N, 40, 40, &t[8]}; c.out = tB; FP_TRY(run_conv(ctx, c, s, sk, N));
-  c = Conv2dCall{tB, N, 40, 40, &t[9]}; c.res = ab1; c.out = ab0; FP_TRY(run_conv(ctx, c, s, sk, N));
-  c = Conv2dCall{ab0, N, 40, 40, &t[10]}; c.out = c0; FP_TRY(run_conv(ctx, c, s, sk, N));
-  c = Conv2dCall{c0, N, 20, 20, &t[11]}; c.out = tC; FP_TRY(run_conv(ctx, c, s, sk, N));
-  c = Conv2dCall{tC, N, 20, 20, &t[12]}; c.res = c0; c.out = c1; FP_TRY(run_conv(ctx, c, s, sk, N));
-  c = Conv2dCall{c1, N, 20, 20, &t[13]}; c.out = tC; FP_TRY(run_conv(ctx, c, s, sk, N));
+  c = Conv2dCall{ab0, N, 40, 40, &t[6]}; c.out = tB; FP_TRY(run_conv(ctx, c, s, sk, hyp));
+  c = Conv2dCall{tB, N, 40, 40, &t[7]}; c.res = ab0; c.out = ab1; FP_TRY(run_conv(ctx, c, s, sk, hyp));
+  c = Conv2dCall{ab1, N, 40, 40, &t[8]}; c.out = tB; FP_TRY(run_conv(ctx, c, s, sk, hyp));
+  c = Conv2dCall{tB, N, 40, 40, &t[9]}; c.res = ab1; c.out = ab0; FP_TRY(run_conv(ctx, c, s, sk, hyp));
+  c = Conv2dCall{ab0, N, 40, 40, &t[10]}; c.out = c0; FP_TRY(run_conv(ctx, c, s, sk, hyp));
+  c = Conv2dCall{c0, N, 20, 20, &t[11]}; c.out = tC; FP_TRY(run_conv(ctx, c, s, sk, hyp));
+  c = Conv2dCall{tC, N, 20, 20, &t[12]}; c.res = c0; c.out = c1; FP_TRY(run_conv(ctx, c, s, sk, hyp));
+  c = Conv2dCall{c1, N, 20, 20, &t[13]}; c.out = tC; FP_TRY(run_conv(ctx, c, s, sk, hyp));
   // reshape(bs,C,-1).permute(0,2,1) is the NHWC tensor itself; pos_embed.pe added in the epilogue
   c = Conv2dCall{tC, N, 20, 20, &t[14]}; c.res = c1; c.out = tok; c.post_add = net->pe; c.post_period = 400;
-  FP_TRY(run_conv(ctx, c, s, sk, N));
+  FP_TRY(run_conv(ctx, c, s, sk, hyp));
   *tokens_out = tok;
   return FP_OK;
 }
 
-// The trunk of a batch as TWO half batches on two streams (from 48 hypotheses on; FP_TRUNK_STREAMS=1: one).  The halves are
+// The trunk of a batch as TWO half batches on two streams (trunk_parts, pass_plan.h: where and why).  The halves are
 // independent (nothing in the trunk couples hypotheses) and every 3x3 launch fills the chip alone - one workgroup per CU - so two
 // streams do not run side by side: what they buy is the LAST ROUND of each launch.  At 252 hypotheses a launch is 788 or 1575 tiles on
 // 256 CUs, 3.08 or 6.15 rounds, and the partial last round costs 3 - 8 % of it (as quarter tiles, round 1); with two half-batch launches
 // queued on two streams the workgroups of the other half start on the CUs the last round leaves idle.  Results are those of the single
 // batch bit for bit (a hypothesis' arithmetic does not depend on its batch).
-int run_trunk_maybe_split(fp_ctx *ctx, const fp_net *net, const f16 *in, int s0, int NT, int N, f16 **tokens_out, hipStream_t s, StreamFanout *ab = nullptr,
-                          const SharedB *sb = nullptr) {
-  static const int n_streams = fp_env_int("FP_TRUNK_STREAMS", 2);
+int run_trunk_maybe_split(fp_ctx *ctx, const fp_net *net, const f16 *in, int s0, int NT, const ForwardPlan &fp, f16 **tokens_out, hipStream_t s,
+                          StreamFanout *ab = nullptr, const SharedB *sb = nullptr) {
   const size_t img = (size_t)160 * 160 * 8;
-  if (N < fp_trunk_split_min()) return run_trunk(ctx, net, in + s0 * img, in + ((size_t)NT + s0) * img, N, tokens_out, s, nullptr, ab, sb, s0);
+  if (fp.trunk_parts == 1) return run_trunk(ctx, net, in + s0 * img, in + ((size_t)NT + s0) * img, trunk_part(fp, 0), tokens_out, s, nullptr, ab, sb, s0);
   if (ab) FP_TRY(ab->join());          // (a batch that is cut in two by hypotheses keeps both sides of a half on one stream)
-  TAKE(tok, f16, (size_t)N * 400 * 512);
-  const int n_parts = std::min(n_streams, std::min(fp_ctx::NSIDE, std::max(2, N / 32)));
-  StreamFanout fo(ctx, s, n_parts);
+  TAKE(tok, f16, (size_t)fp.n * 400 * 512);
+  StreamFanout fo(ctx, s, fp.trunk_parts);
   f16 *t = nullptr;
   int rc = FP_OK;
-  for (int k = 0, a0 = 0; k < n_parts && rc == FP_OK; ++k) {
-    const int a1 = (int)((long long)N * (k + 1) / n_parts);
-    rc = run_trunk(ctx, net, in + (s0 + a0) * img, in + ((size_t)NT + s0 + a0) * img, a1 - a0, &t, k == 0 ? s : fo.stream_for(k - 1), tok + (size_t)a0 * 400 * 512,
-                   nullptr, sb, s0 + a0);
-    a0 = a1;
+  for (int k = 0; k < fp.trunk_parts && rc == FP_OK; ++k) {
+    const TrunkPart part = trunk_part(fp, k);
+    const int a0 = s0 + part.start;
+    rc = run_trunk(ctx, net, in + a0 * img, in + ((size_t)NT + a0) * img, part, &t, k == 0 ? s : fo.stream_for(k - 1), tok + (size_t)part.start * 400 * 512, nullptr, sb, a0);
   }
   const int rj = fo.join();            // on every path: the caller resets the arena, which the side streams may still be writing
   FP_TRY(rc);
@@ -508,15 +511,14 @@ int run_trunk_maybe_split(fp_ctx *ctx, const fp_net *net, const f16 *in, int s0,
 
 // q|k and transposed-V in-projections of up to two attention layers that read the SAME tokens (RefineNet's two heads;
 // one for ScoreNet): one launch for every q / k block (fp16 rows [M][1024] = q | k per layer), one for the V^T images
-int run_qkv(fp_ctx *ctx, const LinP *const *q, const LinP *const *k, const LinP *const *v, int n_layers, const f16 *tok, int N, f16 *const *qk,
+int run_qkv(fp_ctx *ctx, const LinP *const *q, const LinP *const *k, const LinP *const *v, int n_layers, const f16 *tok, const ForwardPlan &fp, f16 *const *qk,
             f16 *const *vt, hipStream_t s) {
   TokGemmArgs a;
   memset(&a, 0, sizeof(a));
   a.in = tok;
-  a.M = N * 400;
+  a.M = fp.n * 400;
   a.tokens = 400;
-  static const bool old_form = fp_env_set("FP_QKV64");          // A/B knob: the 64-token kernel, one launch for q | k, one for v (bit-identical)
-  if (old_form && N > tok_qkv_small_max()) {          // (the few-image form of one and two hypotheses has its own bits: the knob compares the two batch kernels)
+  if (fp.qkv == QKV_PAIR64) {          // A/B knob: the 64-token kernel, one launch for q | k, one for v (bit-identical to the 128-token one)
     a.nblk = 2 * n_layers;
     for (int l = 0; l < n_layers; ++l) {
       a.blk[2 * l] = TokGemmBlock{q[l]->w, q[l]->bias, qk[l], 1024, 0, 0};
@@ -534,7 +536,26 @@ int run_qkv(fp_ctx *ctx, const LinP *const *q, const LinP *const *k, const LinP 
     a.blk[3 * l + 1] = TokGemmBlock{k[l]->w, k[l]->bias, qk[l], 1024, 512, 0, 0};
     a.blk[3 * l + 2] = TokGemmBlock{v[l]->w, v[l]->bias, vt[l], 0, 0, 0, 1};
   }
-  return launch_tok_qkv(ctx, a, s, N);
+  return launch_tok_qkv(ctx, a, s, fp.n);
+}
+
+// The forward bodies of a pass of NT hypotheses: body(s0, plan of its images, whole) once, or once per chunk (FP_CHUNK; `whole` false, and the
+// two chains of `ab` joined first: hypothesis chunks run one chain).  The chunks reuse the SAME arena addresses.  Chunking to keep
+// producer -> consumer tensors inside the 256 MiB Infinity Cache was measured and is slower (smaller grids, same traffic)
+template <typename Body>
+int for_each_chunk(fp_ctx *ctx, int kind, int NT, StreamFanout *ab, Body body) {
+  const PassKnobs &knobs = pass_knobs();
+  const int CH = hyp_chunk(NT, knobs);
+  FP_TRY(fp_arena_ensure(ctx, fp_arena_inner_bytes(CH)));
+  const size_t mark = ctx->arena.off;
+  int rc = FP_OK;
+  if (ab && CH != NT) rc = ab->join();
+  for (int s0 = 0; s0 < NT && rc == FP_OK; s0 += CH) {
+    rc = body(s0, forward_plan(kind, std::min(CH, NT - s0), knobs), CH == NT);
+    ctx->arena.off = mark;
+  }
+  if (ab && rc != FP_OK) (void)ab->join();      // never leave the side stream unjoined
+  return rc;
 }
 
 }  // namespace
@@ -563,15 +584,12 @@ int fp_refine_forward_ab(fp_ctx *ctx, const fp_net *net, const void *d_net_in, i
   FP_REQUIRE(N >= 0, "fp_refine_forward: N<0");
   if (N == 0) return ab ? ab->join() : FP_OK;
   const int NT = N;                                   // whole batch
-  const int CH = fp_hyp_chunk(NT);
-  FP_TRY(fp_arena_ensure(ctx, fp_arena_inner_bytes(CH)));
-  const size_t mark = ctx->arena.off;
-  if (CH != NT) tail = nullptr;                       // (hypothesis chunks: the building-block launches)
-  auto body = [&](int s0, int N) -> int {
+  return for_each_chunk(ctx, PASS_REFINE, NT, ab, [&](int s0, const ForwardPlan &fp, bool whole) -> int {
+    const int N = fp.n, M = N * 400;
+    RefineTailArgs *tail_ = whole ? tail : nullptr;       // (hypothesis chunks: the building-block launches)
     f16 *tok = nullptr;
     const f16 *in = (const f16 *)d_net_in;
-    FP_TRY(run_trunk_maybe_split(ctx, net, in, s0, NT, N, &tok, s, CH == NT ? ab : nullptr, sb));
-    const int M = N * 400;
+    FP_TRY(run_trunk_maybe_split(ctx, net, in, s0, NT, fp, &tok, s, whole ? ab : nullptr, sb));
     // The translation and rotation heads are independent transformer layers on the same tokens: each gets its own
     // buffers and its own stream, so the tail of one head's kernels overlaps the other's (their launches are 3.08 rounds of
     // workgroups each)
@@ -588,9 +606,8 @@ int fp_refine_forward_ab(fp_ctx *ctx, const fp_net *net, const void *d_net_in, i
     // in-projections of BOTH heads: the tokens are staged once per workgroup for 512 output columns of either head
     const LinP *q_[2] = {&net->heads[0].q, &net->heads[1].q}, *k_[2] = {&net->heads[0].k, &net->heads[1].k}, *v_[2] = {&net->heads[0].v, &net->heads[1].v};
     ProfScope wall(ctx, s, "heads_wall", 0.0);      // first in-projection .. join of both heads, on the main stream: the heads' share of wall time
-    FP_TRY(run_qkv(ctx, q_, k_, v_, 2, tok, N, qk, vt, s));
-    static const bool serial_heads = fp_env_set("FP_HEADS_SERIAL");      // A/B timing knob
-    StreamFanout fo(ctx, s, serial_heads ? 1 : 2);
+    FP_TRY(run_qkv(ctx, q_, k_, v_, 2, tok, fp, qk, vt, s));
+    StreamFanout fo(ctx, s, fp.head_streams);
     for (int h = 0; h < 2; ++h) {
       const HeadW &H = net->heads[h];
       hipStream_t sh = h == 0 ? s : fo.stream_for(0);
@@ -607,31 +624,21 @@ int fp_refine_forward_ab(fp_ctx *ctx, const fp_net *net, const void *d_net_in, i
       a.g1 = H.ln1g, a.be1 = H.ln1b;
       a.gsum = gsum[h];
       FP_TRY(launch_head_mlp(ctx, a, sh));
-      if (!tail) FP_TRY(launch_mean_head(gsum[h], 25, H.ln2g, H.ln2b, N, 400, H.hw, H.hb, H.out_dim, outs[h], sh));
+      if (!tail_) FP_TRY(launch_mean_head(gsum[h], 25, H.ln2g, H.ln2b, N, 400, H.hw, H.hb, H.out_dim, outs[h], sh));
     }
     FP_TRY(fo.join());
-    if (tail) {
+    if (tail_) {
       for (int h = 0; h < 2; ++h) {
         const HeadW &H = net->heads[h];
-        tail->partial[h] = gsum[h], tail->gam[h] = H.ln2g, tail->bet[h] = H.ln2b, tail->hw[h] = H.hw, tail->hb[h] = H.hb;
+        tail_->partial[h] = gsum[h], tail_->gam[h] = H.ln2g, tail_->bet[h] = H.ln2b, tail_->hw[h] = H.hw, tail_->hb[h] = H.hb;
       }
-      tail->nparts = 25, tail->T = 400, tail->rot_dim = net->heads[1].out_dim;
-      tail->trans = outs[0], tail->rot = outs[1];
+      tail_->nparts = 25, tail_->T = 400, tail_->rot_dim = net->heads[1].out_dim;
+      tail_->trans = outs[0], tail_->rot = outs[1];
       FP_REQUIRE(net->heads[0].out_dim == 3, "refine tail: translation head of %d outputs", net->heads[0].out_dim);
-      FP_TRY(launch_refine_tail(*tail, N, s));
+      FP_TRY(launch_refine_tail(*tail_, N, s));
     }
     return FP_OK;
-  };
-  // hypothesis chunks (FP_CHUNK, default: the whole batch in one pass) reuse the SAME arena addresses.  Chunking to keep
-  // producer -> consumer tensors inside the 256 MiB Infinity Cache was measured and is slower (smaller grids, same traffic)
-  int rc = FP_OK;
-  if (ab && CH != NT) rc = ab->join();          // (hypothesis chunks: one chain)
-  for (int s0 = 0; s0 < NT && rc == FP_OK; s0 += CH) {
-    rc = body(s0, std::min(CH, NT - s0));
-    ctx->arena.off = mark;
-  }
-  if (ab && rc != FP_OK) (void)ab->join();      // never leave the side stream unjoined
-  return rc;
+  });
 }
 
 // Building block for the parity tests: one 512 -> 512 token Linear with one of the fused epilogues of tok_gemm.hip.
@@ -721,7 +728,7 @@ extern "C" int fp_net_tokens(fp_ctx *ctx, const fp_net *net, const void *d_net_i
   const size_t mark = ctx->arena.off;
   f16 *tok = nullptr;
   const f16 *in = (const f16 *)d_net_in;
-  int rc = run_trunk(ctx, net, in, in + (size_t)N * 160 * 160 * 8, N, &tok, s);
+  int rc = run_trunk(ctx, net, in, in + (size_t)N * 160 * 160 * 8, TrunkPart{0, N, N, net_offers_splitk(N)}, &tok, s);      // one part, whatever N
   if (rc == FP_OK && hipMemcpyAsync(d_tokens, tok, (size_t)N * 400 * 512 * sizeof(f16), hipMemcpyDeviceToDevice, s) != hipSuccess) {
     fp_set_error("fp_net_tokens: copy failed");
     rc = FP_EHIP;
@@ -741,34 +748,23 @@ int fp_score_features_ab(fp_ctx *ctx, const fp_net *net, const void *d_net_in, i
   FP_REQUIRE(N >= 0, "fp_score_features: N<0");
   if (N == 0) return ab ? ab->join() : FP_OK;
   const int NT = N;
-  const int CH = fp_hyp_chunk(NT);
-  FP_TRY(fp_arena_ensure(ctx, fp_arena_inner_bytes(CH)));
-  const size_t mark = ctx->arena.off;
-  auto body = [&](int s0, int N) -> int {
+  return for_each_chunk(ctx, PASS_SCORE, NT, ab, [&](int s0, const ForwardPlan &fp, bool whole) -> int {
+    const int N = fp.n, M = N * 400;
     f16 *tok = nullptr;
     const f16 *in = (const f16 *)d_net_in;
-    FP_TRY(run_trunk_maybe_split(ctx, net, in, s0, NT, N, &tok, s, CH == NT ? ab : nullptr));
-    const int M = N * 400;
+    FP_TRY(run_trunk_maybe_split(ctx, net, in, s0, NT, fp, &tok, s, whole ? ab : nullptr));
     TAKE(qk, f16, (size_t)M * 1024);
     TAKE(vt, f16, (size_t)N * 4 * 128 * 416);
     TAKE(att, f16, (size_t)M * 512);
     const LinP *q_[1] = {&net->att_q}, *k_[1] = {&net->att_k}, *v_[1] = {&net->att_v};
     f16 *qk_[1] = {qk}, *vt_[1] = {vt};
     ProfScope wall(ctx, s, "heads_wall", 0.0);
-    FP_TRY(run_qkv(ctx, q_, k_, v_, 1, tok, N, qk_, vt_, s));
+    FP_TRY(run_qkv(ctx, q_, k_, v_, 1, tok, fp, qk_, vt_, s));
     FP_TRY(launch_attention(ctx, qk, vt, N, 400, att, s));
     // mean over tokens commutes with out_proj (score_network.py:73-74): both in one launch
     FP_TRY(launch_score_feat(att, N, 400, net->att_out.wt, net->att_out.b, d_feats + (size_t)s0 * feat_ld, feat_ld, d_poses ? d_poses + (size_t)s0 * 16 : nullptr, s));
     return FP_OK;
-  };
-  int rc = FP_OK;
-  if (ab && CH != NT) rc = ab->join();
-  for (int s0 = 0; s0 < NT && rc == FP_OK; s0 += CH) {
-    rc = body(s0, std::min(CH, NT - s0));
-    ctx->arena.off = mark;
-  }
-  if (ab && rc != FP_OK) (void)ab->join();
-  return rc;
+  });
 }
 
 int fp_score_tail_impl(fp_ctx *ctx, const fp_net *net, const float *d_feats, int feat_ld, int groups, int L, const ScoreTailOut &o, hipStream_t s) {
