@@ -137,6 +137,21 @@ class FpTextureCfg(Structure):
   _fields_ = [('struct_size', ctypes.c_size_t), ('tex_size', c_int), ('top_n', c_int), ('depth_tol', c_float), ('cos_min', c_float), ('zfar', c_float)]
 
 
+FP_STEREO_MAX_DISPARITY, FP_STEREO_MAX_CELLS = 256, 1 << 31                # fp_stereo_sgm
+
+
+class FpStereoOpts(Structure):
+  """fp_stereo_opts (include/foundationpose_amd.h)."""
+  _fields_ = [('struct_size', ctypes.c_size_t), ('max_disparity', c_int), ('p1', c_int), ('p2', c_int), ('paths', c_uint), ('lr_max', c_int),
+              ('min_disparity', c_int), ('subpixel', c_int), ('fx', c_double), ('baseline', c_double), ('zfar', c_float)]
+
+
+class FpStereoDebug(Structure):
+  """fp_stereo_debug: device pointers (or None) that receive the stages of fp_stereo_sgm."""
+  _fields_ = [('struct_size', ctypes.c_size_t), ('d_census_left', c_void_p), ('d_census_right', c_void_p), ('d_cost', c_void_p), ('d_sum', c_void_p),
+              ('d_dstar', c_void_p), ('d_dright', c_void_p)]
+
+
 class FpObjectBatch(Structure):
   _fields_ = [('mesh', c_void_p), ('d_rgb', c_void_p), ('d_geom', c_void_p), ('H', c_int), ('W', c_int), ('K', c_void_p),
               ('mesh_diameter', c_double), ('n', c_int)]
@@ -207,6 +222,8 @@ _PROTOS = {
   'fp_depth_segment_count': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_float, c_void_p, c_float, c_float, c_float,
                                      c_int, c_void_p, c_void_p]),
   'fp_depth_segment_write': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
+  'fp_stereo_sgm': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, POINTER(FpStereoOpts), c_void_p, c_void_p, POINTER(FpStereoDebug),
+                            c_void_p]),
   'fp_texture_bake': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                               POINTER(FpTextureCfg), c_void_p, c_void_p, c_void_p, c_void_p]),
   'fp_point_mesh_distance': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -118,6 +118,7 @@ extern "C" int fp_ctx_destroy(fp_ctx *ctx) {
   fp_simplify_state_free(ctx);
   fp_components_state_free(ctx);
   fp_segment_state_free(ctx);
+  fp_stereo_state_free(ctx);
   if (ctx->arena.base) (void)hipFree(ctx->arena.base);
   if (ctx->zero_page) (void)hipFree(ctx->zero_page);
   delete ctx;

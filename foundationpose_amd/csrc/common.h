@@ -193,10 +193,21 @@ struct fp_ctx {
   struct fp_simplify_state *simplify = nullptr;   // mesh_simplify.hip: what fp_mesh_simplify_count leaves for fp_mesh_simplify_write
   struct fp_components_state *components = nullptr;   // mesh_components.hip: what fp_mesh_components_count leaves for fp_mesh_components_write
   struct fp_segment_state *segment = nullptr;         // segment.hip: what fp_depth_segment_count leaves for fp_depth_segment_write
+  struct fp_stereo_state *stereo = nullptr;           // stereo.hip: the working memory of fp_stereo_sgm
 };
 void fp_simplify_state_free(fp_ctx *ctx);         // mesh_simplify.hip; fp_ctx_destroy
 void fp_components_state_free(fp_ctx *ctx);       // mesh_components.hip; fp_ctx_destroy
 void fp_segment_state_free(fp_ctx *ctx);          // segment.hip; fp_ctx_destroy
+void fp_stereo_state_free(fp_ctx *ctx);           // stereo.hip; fp_ctx_destroy
+
+// stereo.hip: the host side of fp_stereo_sgm that needs no device - where the arrays of a call lie in the context's blob, and every
+// check of a value (`o` receives the options as the call uses them).  scripts/stereo_host_check.cpp runs both under sanitizers.
+struct StereoLayout {
+  size_t o_grey_l = 0, o_grey_r = 0, o_census_l = 0, o_census_r = 0, o_sum = 0, o_dstar = 0, o_dright = 0, bytes = 0;
+};
+StereoLayout fp_stereo_layout(int n, int H, int W, int D, int channels);
+int fp_stereo_check(const void *ctx, const void *d_left, const void *d_right, int n, int H, int W, int channels, const fp_stereo_opts *opts,
+                    const float *d_depth, const fp_stereo_debug *dbg, fp_stereo_opts *o);
 
 int fp_arena_ensure(fp_ctx *ctx, size_t bytes);
 size_t fp_arena_bytes_for(int n_hyp);     // whole refine/score pass (outer buffers + network)

@@ -3,6 +3,7 @@ binary, the form of the BOP object models) -> SimpleMesh with angle-weighted ver
 texture array.  Images are decoded with PIL, imported only where one is decoded."""
 import logging
 import os
+import re
 
 import numpy as np
 
@@ -383,9 +384,50 @@ def load_mesh(path, scale=1.0, split_uv=True):
   return mesh
 
 
-def load_intrinsics(path):
-  """3x3 matrix as 9 whitespace/comma separated numbers (the cam_K.txt convention)."""
-  vals = np.fromstring(open(path).read().replace(',', ' '), sep=' ')
+_NUMBER = r'([-+]?(?:\d+\.?\d*|\.\d+)(?:[eE][-+]?\d+)?)'
+
+
+def _calibration_section(path, text, section):
+  """The text between `[section]` and the next `[` of a sectioned calibration file."""
+  m = re.search(r'^[ \t]*\[' + re.escape(section) + r'\][ \t]*$(.*?)(?=^[ \t]*\[|\Z)', text, re.S | re.M)
+  if m is None:
+    raise ValueError(f'{path}: no section [{section}]')
+  return m.group(1)
+
+
+def _calibration_value(path, body, section, key):
+  m = re.search(r'^[ \t]*' + re.escape(key) + r'[ \t]*=[ \t]*' + _NUMBER + r'[ \t]*$', body, re.M)
+  if m is None:
+    raise ValueError(f'{path}: no {key}= in section [{section}]')
+  return float(m.group(1))
+
+
+def _is_sectioned(text):
+  first = next((l for l in text.splitlines() if l.strip()), '')
+  return first.lstrip().startswith('[')
+
+
+def load_intrinsics(path, camera_section='LEFT_CAM_FHD1200'):
+  """3x3 matrix as 9 whitespace/comma separated numbers (the cam_K.txt convention).  A file whose first non-blank line starts with `[`
+  is a stereo camera's sectioned calibration file instead (src/file_processing.py:36-81): the fx=, fy=, cx=, cy= of `[camera_section]`
+  become [[fx, 0, cx], [0, fy, cy], [0, 0, 1]]."""
+  text = open(path).read()
+  if _is_sectioned(text):
+    body = _calibration_section(path, text, camera_section)
+    fx, fy, cx, cy = (_calibration_value(path, body, camera_section, k) for k in ('fx', 'fy', 'cx', 'cy'))
+    return np.array([[fx, 0.0, cx], [0.0, fy, cy], [0.0, 0.0, 1.0]], dtype=np.float64)
+  vals = np.fromstring(text.replace(',', ' '), sep=' ')
   if vals.size != 9:
     raise ValueError(f'{path}: expected 9 numbers, got {vals.size}')
   return vals.reshape(3, 3).astype(np.float64)
+
+
+def load_stereo_baseline(path, scale=0.001):
+  """`Baseline=` of the `[STEREO]` section of a sectioned calibration file, times `scale`, as metres.  The reference reads only the
+  camera sections of that file and never says in which unit the baseline is written; cameras of this kind write millimetres, hence the
+  default 0.001 - `scale` is a parameter because that is an assumption: pass 1.0 for a file in metres."""
+  text = open(path).read()
+  if not _is_sectioned(text):
+    raise ValueError(f'{path}: not a sectioned calibration file (its first non-blank line does not start with "[")')
+  return _calibration_value(path, _calibration_section(path, text, 'STEREO'), 'STEREO', 'Baseline') * float(scale)
+

@@ -16,6 +16,7 @@ class PipelineData:
 
   def __init__(self, **kw):
     self.rgb = self.depth = self.mask = self.K = None
+    self.right = None         # the right image of a rectified stereo pair (StereoDepth), rgb being the left one
     self.pose = None          # 4x4 ob_in_cam of the original (un-centred) mesh
     self.pose_6d = None       # (x, y, z, roll, pitch, yaw)
     self.errors = []
@@ -85,6 +86,32 @@ class PoseTransformer(Processor):
 
   def process(self, data):
     data.pose_6d = self.transform_pose(data.pose)
+    return data
+
+
+class StereoDepth(Processor):
+  """Fills `data.depth` from the rectified pair `data.rgb` (left) / `data.right` when `data.depth is None`, and leaves `data` alone
+  otherwise: the stage in front of FoundationPoseEstimator on a stereo camera whose vendor SDK is not there (the reference loads that
+  SDK's depth, src/file_processing.py:99-138).  baseline in metres; K: the left camera's 3x3 matrix, `data.K` when that is set; **kw:
+  the arguments of Utils.stereo_depth (max_disparity, p1, p2, paths, lr_max, min_disparity, subpixel, zfar).  Device tensors in give a
+  device tensor in `data.depth`, without a host copy.  The pair must already be rectified and undistorted."""
+
+  def __init__(self, baseline, K=None, **kw):
+    self.baseline = float(baseline)
+    self.K = None if K is None else np.asarray(K, dtype=np.float64)
+    self._kw = kw
+
+  def process(self, data):
+    if data.depth is not None:
+      return data
+    right = getattr(data, 'right', None)
+    if data.rgb is None or right is None:
+      raise ValueError('StereoDepth: data.depth is None and data.rgb / data.right do not hold a pair')
+    K = self.K if data.K is None else data.K
+    if K is None:
+      raise ValueError('StereoDepth: no camera matrix (K=... or data.K)')
+    from .stereo import stereo_depth
+    data.depth = stereo_depth(data.rgb, right, K, self.baseline, **self._kw)
     return data
 
 

@@ -972,6 +972,65 @@ int fp_depth_segment_count(fp_ctx *ctx, const float *d_depth, const uint8_t *d_m
 int fp_depth_segment_write(fp_ctx *ctx, const float *d_depth, int n_views, int H, int W, int32_t *d_labels, int64_t *d_stats, int64_t n_kept,
                            void *stream);
 
+/* ---- depth from a rectified stereo pair: semi-global matching on census costs (csrc/stereo.hip).  The reference loads a depth image
+ *      that its camera vendor's SDK computed (src/file_processing.py:99-138); this rule is the library's own, NOT
+ *      OpenCV's StereoSGBM, and tests/stereo_oracle.py restates all of it in numpy.  The arithmetic is integer from the images to the
+ *      winning disparity: every stage is bit-identical from run to run, in any batch and at any index of it.  The pair must already be
+ *      rectified and undistorted: a point of left pixel (y, x) is looked for at right pixels (y, x - d), 0 <= d < D = max_disparity.
+ *      d_left, d_right (n,H,W) uint8 with channels = 1, (n,H,W,3) uint8 RGB with channels = 3, on the device; n >= 1 pairs of one size,
+ *      H, W >= 1; D a multiple of 64, 64 .. FP_STEREO_MAX_DISPARITY; n H W D <= FP_STEREO_MAX_CELLS and n <= 65535.
+ *      1 Grey.  One channel is used as given; RGB becomes (77 R + 150 G + 29 B + 128) >> 8.
+ *      2 Census, 9 wide x 7 high.  The 62 neighbours dy = -3 .. 3, dx = -4 .. 4 without the centre, scanned row-major (dy outer), the
+ *        first neighbour in bit 61 of a uint64, the last in bit 0; coordinates clamped to the image; a bit is set when the neighbour is
+ *        smaller than the centre.
+ *      3 Cost.  C(y,x,d) = popcount(cl(y,x) ^ cr(y,x-d)) where x - d >= 0, else 64 (one above anything a comparison can give).
+ *      4 Paths.  Bit b of `paths` selects the direction r = (dy, dx): 0 (0,+1), 1 (0,-1), 2 (+1,0), 3 (-1,0), 4 (+1,+1), 5 (+1,-1),
+ *        6 (-1,+1), 7 (-1,-1) (this numbering is pinned here); 0xFF is all eight, 0x0F the four axis-aligned ones.  With q = p - r and
+ *        m_q = min_k L_r(q,k):
+ *          L_r(p,d) = C(p,d) + min(L_r(q,d), L_r(q,d-1) + P1, L_r(q,d+1) + P1, m_q + P2) - m_q
+ *        L_r = C where q lies outside the image; d - 1 < 0 and d + 1 >= D are not considered.  L_r <= 64 + P2.  S = the sum of the
+ *        selected L_r, uint16.  P1 and P2 are constants (no gradient-adaptive P2); the defaults 8 and 32 are this library's own choice.
+ *      5 Winner.  d*(p) = the lowest d at which S(p, .) is minimal.
+ *      6 Left-right check.  d_R(y,x) = the lowest d minimising S(y,x+d,d) over x + d < W.  A pixel is valid when x - d* >= 0 and
+ *        |d_R(y,x-d*) - d*| <= lr_max and d* >= min_disparity; lr_max < 0 switches the middle test off.
+ *      7 Sub-pixel (subpixel = 1).  With 0 < d* < D - 1, a, b, c = S(d*-1), S(d*), S(d*+1) as int and a - 2b + c > 0:
+ *        disparity = (float)d* + (float)(a - c) / (float)(2 (a - 2b + c)), fp32, / correctly rounded; in every other case (float)d*.
+ *      8 Outputs, either may be null.  d_disparity (n,H,W) fp32, -1 where the pixel is not valid.  d_depth (n,H,W) fp32 =
+ *        fb / disparity with fb = (float)(fx * baseline), the product formed in double; 0 where the pixel is not valid, where the depth
+ *        is above zfar (infinity: no limit) and where the disparity is not > 0 (possible only with min_disparity = 0; pinned here).
+ *      dbg (may be null): device pointers, each may be null, that receive the stages: d_census_left / d_census_right (n,H,W) uint64,
+ *      d_cost (n,H,W,D) uint8, d_sum (n,H,W,D) uint16, d_dstar / d_dright (n,H,W) int32.  C is formed only for this output: the
+ *      aggregation computes its costs from the census images.
+ *      Working memory is one allocation owned by the context (16 + 2 D bytes a pixel, + 2 with RGB; kept until a larger call arrives or
+ *      the context is destroyed); a call writes everything it reads.  The call queues one chain of launches on `stream` and does not
+ *      synchronise; after a first call of a size, a call of that size allocates nothing and can be captured into a graph.
+ *      FP_EINVAL, each checked before ctx is looked into: a null ctx, d_left, d_right or opts; a struct_size the library does not know;
+ *      n, H or W < 1; channels other than 1 or 3; max_disparity as above; too many cells; p1 < 0, p1 > p2 or 8 (64 + p2) > 65535;
+ *      paths outside 1 .. 0xFF; min_disparity outside 0 .. D - 1; subpixel other than 0 or 1; with d_depth: fx baseline not positive
+ *      and finite as fp32, zfar not > 0.  FP_ENOMEM: the working memory does not fit the device. */
+#define FP_STEREO_MAX_DISPARITY 256
+#define FP_STEREO_MAX_CELLS (1LL << 31) /* n H W max_disparity of one call */
+typedef struct fp_stereo_opts {
+  size_t struct_size;      /* = sizeof(fp_stereo_opts) */
+  int max_disparity;       /* D */
+  int p1, p2;
+  unsigned paths;          /* one bit per direction */
+  int lr_max;              /* < 0: no left-right check */
+  int min_disparity;
+  int subpixel;            /* 0 or 1 */
+  double fx, baseline;     /* pixels, metres; read only with d_depth */
+  float zfar;              /* metres; read only with d_depth */
+} fp_stereo_opts;
+typedef struct fp_stereo_debug {
+  size_t struct_size;      /* = sizeof(fp_stereo_debug) */
+  uint64_t *d_census_left, *d_census_right;
+  uint8_t *d_cost;
+  uint16_t *d_sum;
+  int32_t *d_dstar, *d_dright;
+} fp_stereo_debug;
+int fp_stereo_sgm(fp_ctx *ctx, const uint8_t *d_left, const uint8_t *d_right, int n, int H, int W, int channels, const fp_stereo_opts *opts,
+                  float *d_disparity, float *d_depth, const fp_stereo_debug *dbg, void *stream);
+
 /* ---- texture baking: the colours of posed RGB-D reference views gathered into a per-face texture atlas of a mesh - the last stage of
  *      the model-free set-up, after the simplification (fp_mesh_simplify_* refuses textured meshes: simplify first, then bake).  The
  *      reference does this in mesh_texture_from_train_images (bundlesdf/nerf_runner.py:1122) with a UV parametrisation and the equal
