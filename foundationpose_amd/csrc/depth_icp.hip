@@ -4,13 +4,13 @@
 // library is built without contraction).  The joint solve over all views is the caller's (foundationpose_amd/reconstruct.py).
 //
 // Both kernels move memory.  The normals kernel is one thread per pixel: five depth reads (the pixel and its four neighbours, the rows
-// above and below come from L2) and one 16-byte write.  The pairs kernel has the launch shape of tsdf_align_kernel (tsdf.hip): a workgroup
-// owns (pair, a tile of PA_TILE source pixels); the pair is uniform in the workgroup, so its matrices arrive as scalar loads from the
-// pair table.  A lane takes PA_PIX pixels, PA_THREADS apart (the source reads coalesce), in three passes over them: source normal and
-// depth; then the projection into the target and the two gathers of each pixel (16-byte normal, 4-byte depth) - nothing in this pass
-// depends on a gathered value, so all PA_PIX x 2 gathers are in flight together; then the arithmetic.  The row, the 29 sums in double
-// and their way through the wave, LDS and the slab to gn_fold_kernel are those of gn_sums.h, where the summation order is stated.  No
-// atomics.  A wave whose 256 source pixels have no normal (the background of a masked view) skips passes two and three.
+// above and below come from L2) and one 16-byte write.  The pairs kernel is one of the three aligners of gn_sums.h, which holds what they
+// share: the tile, the three passes, the association, the point-to-plane row, the 29 sums in double and their way to gn_fold_kernel;
+// the camera and the transforms are those of view_geom.h.  A workgroup owns (pair, a tile of GN_TILE source pixels); the pair is uniform
+// in the workgroup, so its matrices arrive as scalar loads from the pair table.  Pass one reads the source normal and depth (the reads
+// coalesce); pass two projects into the target and gathers each pixel's 16-byte normal and 4-byte depth, all GN_PIX x 2 gathers in
+// flight together; pass three is the arithmetic.  No atomics.  A wave whose 256 source pixels have no normal (the background of a
+// masked view) skips passes two and three.
 //
 // The photometric term (fp_view_intensity, fp_depth_pairs_align_photo) rides on the same association.  view_intensity_kernel is one thread
 // per pixel again: the pixel's normal, the rgb of the pixel and of its four neighbours where the normal is there, one 16-byte write.
@@ -26,28 +26,20 @@
 
 namespace {
 
-constexpr int PA_THREADS = 256;
-constexpr int PA_PIX = 4;
-constexpr int PA_TILE = PA_THREADS * PA_PIX;      // 1024 source pixels per workgroup
-
-struct DepthCam {
-  float fx, fy, cx, cy;
-  int H, W;
-};
+constexpr int PX_THREADS = 256;      // the two kernels of one thread per pixel
 
 // what a pair (s, t) needs of its two views, as fp32
 struct PairRec {
-  float rcs[9], tcs[3];      // C_s: camera s -> object
-  float rit[9], tit[3];      // D_t: object -> camera t
+  Rigid cs;                  // C_s: camera s -> object
+  Rigid it;                  // D_t: object -> camera t
   float rct[9];              // the rotation of C_t
   int s, t, pad;
 };
+static_assert(sizeof(PairRec) == 144, "the pair table is read as scalar loads of this layout");
 
-__device__ __forceinline__ bool depth_ok(float d, float zfar) { return d >= 0.001f && d < zfar; }
-
-__global__ __launch_bounds__(PA_THREADS) void depth_normals_kernel(const float *__restrict__ depth, const uint8_t *__restrict__ mask, DepthCam cam,
+__global__ __launch_bounds__(PX_THREADS) void depth_normals_kernel(const float *__restrict__ depth, const uint8_t *__restrict__ mask, Pinhole cam,
                                                                    float zfar, float max_jump, long long total, float4 *__restrict__ out) {
-  const long long idx = (long long)blockIdx.x * PA_THREADS + threadIdx.x;
+  const long long idx = (long long)blockIdx.x * PX_THREADS + threadIdx.x;
   if (idx >= total) return;
   const long long hw = (long long)cam.H * cam.W;
   const long long pix = idx % hw;
@@ -59,8 +51,8 @@ __global__ __launch_bounds__(PA_THREADS) void depth_normals_kernel(const float *
     if (mask) ok = ok && mask[idx] != 0 && mask[idx - 1] != 0 && mask[idx + 1] != 0 && mask[idx - cam.W] != 0 && mask[idx + cam.W] != 0;
     ok = ok && fabsf(dl - d) <= max_jump && fabsf(dr - d) <= max_jump && fabsf(du - d) <= max_jump && fabsf(dd - d) <= max_jump;
     if (ok) {
-      const float kl = ((float)(c - 1) - cam.cx) / cam.fx, kr = ((float)(c + 1) - cam.cx) / cam.fx, kc = ((float)c - cam.cx) / cam.fx;
-      const float ku = ((float)(r - 1) - cam.cy) / cam.fy, kd = ((float)(r + 1) - cam.cy) / cam.fy, km = ((float)r - cam.cy) / cam.fy;
+      const float kl = pinhole_ray_x(cam, (float)(c - 1)), kr = pinhole_ray_x(cam, (float)(c + 1)), kc = pinhole_ray_x(cam, (float)c);
+      const float ku = pinhole_ray_y(cam, (float)(r - 1)), kd = pinhole_ray_y(cam, (float)(r + 1)), km = pinhole_ray_y(cam, (float)r);
       const float ax = kr * dr - kl * dl, ay = km * dr - km * dl, az = dr - dl;      // p(r,c+1) - p(r,c-1)
       const float bx = kc * dd - kc * du, by = kd * dd - ku * du, bz = dd - du;      // p(r+1,c) - p(r-1,c)
       const float mx = by * az - bz * ay, my = bz * ax - bx * az, mz = bx * ay - by * ax;
@@ -80,9 +72,9 @@ __device__ __forceinline__ float grey(const uint8_t *__restrict__ rgb, long long
   return ((0.299f * (float)p[0] + 0.587f * (float)p[1]) + 0.114f * (float)p[2]) / 255.f;
 }
 
-__global__ __launch_bounds__(PA_THREADS) void view_intensity_kernel(const uint8_t *__restrict__ rgb, const float4 *__restrict__ normals, int H, int W,
+__global__ __launch_bounds__(PX_THREADS) void view_intensity_kernel(const uint8_t *__restrict__ rgb, const float4 *__restrict__ normals, int H, int W,
                                                                     long long total, float4 *__restrict__ out) {
-  const long long idx = (long long)blockIdx.x * PA_THREADS + threadIdx.x;
+  const long long idx = (long long)blockIdx.x * PX_THREADS + threadIdx.x;
   if (idx >= total) return;
   const long long hw = (long long)H * W;
   const long long pix = idx % hw;
@@ -97,13 +89,13 @@ __global__ __launch_bounds__(PA_THREADS) void view_intensity_kernel(const uint8_
 // PHOTO: the photometric rows and their 29 sums behind the geometric ones (the header's second rule); `intensity` and i_max are not
 // looked at without it.
 template <bool PHOTO>
-__global__ __launch_bounds__(PA_THREADS) void depth_pairs_kernel(const float *__restrict__ depth, const float4 *__restrict__ normals,
-                                                                 const float4 *__restrict__ intensity, DepthCam cam,
+__global__ __launch_bounds__(GN_THREADS) void depth_pairs_kernel(const float *__restrict__ depth, const float4 *__restrict__ normals,
+                                                                 const float4 *__restrict__ intensity, Pinhole cam,
                                                                  const PairRec *__restrict__ recs, int n_tiles, float dist2_max, float cos_min,
                                                                  float i_max, float *__restrict__ rows, double *__restrict__ slab) {
   constexpr int TERMS = PHOTO ? FP_PHOTO_ALIGN_TERMS : FP_DEPTH_ALIGN_TERMS;
   constexpr int ROW = PHOTO ? 16 : 8;                               // floats per pixel of `rows`
-  __shared__ double red[PA_THREADS / 64][TERMS];
+  __shared__ double red[GN_THREADS / 64][TERMS];
   const int tid = threadIdx.x;
   const int tile = blockIdx.x % n_tiles, pr = blockIdx.x / n_tiles;
   const PairRec &m = recs[pr];
@@ -111,14 +103,14 @@ __global__ __launch_bounds__(PA_THREADS) void depth_pairs_kernel(const float *__
   const size_t src0 = (size_t)m.s * (size_t)hw, tgt0 = (size_t)m.t * (size_t)hw;      // 0 <= s, t < n_views: checked on the host
 
   // pass 1: the source pixel's normal and depth
-  float d[PA_PIX];
-  float4 ns[PA_PIX];
-  bool ok[PA_PIX];
-  long long pix[PA_PIX];
-  float4 ia[PA_PIX];                                               // PHOTO: the source pixel's intensity record
+  float d[GN_PIX];
+  float4 ns[GN_PIX];
+  bool ok[GN_PIX];
+  long long pix[GN_PIX];
+  float4 ia[GN_PIX];                                               // PHOTO: the source pixel's intensity record
 #pragma unroll
-  for (int q = 0; q < PA_PIX; ++q) {
-    pix[q] = (long long)tile * PA_TILE + q * PA_THREADS + tid;
+  for (int q = 0; q < GN_PIX; ++q) {
+    pix[q] = (long long)tile * GN_TILE + q * GN_THREADS + tid;
     const bool in = pix[q] < hw;                                   // the last tile of a view is ragged
     ns[q] = in ? normals[src0 + (size_t)pix[q]] : make_float4(0.f, 0.f, 0.f, 0.f);
     d[q] = in ? depth[src0 + (size_t)pix[q]] : 0.f;
@@ -126,45 +118,29 @@ __global__ __launch_bounds__(PA_THREADS) void depth_pairs_kernel(const float *__
     ok[q] = ns[q].w != 0.f;
   }
 
-  // A wave without a single source normal - most waves of a masked object's view - has nothing to project: its rows are zeros and its
-  // 29 (58) partial sums are +0.0, the value the passes below would arrive at (0.f x 0.f widened and added to +0.0).  Uniform in the wave.
-  if (!__any(ok[0] || ok[1] || ok[2] || ok[3])) {
-    if (rows) {
-#pragma unroll
-      for (int q = 0; q < PA_PIX; ++q)
-        if (pix[q] < hw) {
-          float4 *o = (float4 *)(rows + ((size_t)pr * (size_t)hw + (size_t)pix[q]) * ROW);
-          o[0] = o[1] = make_float4(0.f, 0.f, 0.f, 0.f);
-          if constexpr (PHOTO) o[2] = o[3] = make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    }
-    if ((tid & 63) < TERMS) red[tid >> 6][tid & 63] = 0.0;
-  } else {
+  // A wave without a single source normal - most waves of a masked object's view - skips the passes below (gn_sums.h).
+  if (!gn_empty_wave<ROW>(ok, rows, (size_t)pr * (size_t)hw, pix, hw, red[tid >> 6])) {
   // pass 2: the point in the object frame and in camera t, its pixel there, the two gathers
-  float x[PA_PIX][3], y[PA_PIX][3], cf[PA_PIX], rf[PA_PIX], dt[PA_PIX];
-  float4 nt[PA_PIX];
-  float4 ib[PA_PIX];                                               // PHOTO: the target pixel's intensity record,
-  float du[PA_PIX], dv[PA_PIX];                                    // the projection's offset from that pixel's centre,
-  bool geo[PA_PIX];                                                // and whether the pixel passed every geometric gate
+  float x[GN_PIX][3], y[GN_PIX][3], cf[GN_PIX], rf[GN_PIX], dt[GN_PIX];
+  float4 nt[GN_PIX];
+  float4 ib[GN_PIX];                                               // PHOTO: the target pixel's intensity record,
+  float du[GN_PIX], dv[GN_PIX];                                    // the projection's offset from that pixel's centre,
+  bool geo[GN_PIX];                                                // and whether the pixel passed every geometric gate
 #pragma unroll
-  for (int q = 0; q < PA_PIX; ++q) {
+  for (int q = 0; q < GN_PIX; ++q) {
     const int row = (int)(pix[q] / cam.W), col = (int)(pix[q] - (long long)row * cam.W);
-    const float px = (((float)col - cam.cx) / cam.fx) * d[q], py = (((float)row - cam.cy) / cam.fy) * d[q], pz = d[q];
+    const float3 p = pinhole_point(cam, (float)col, (float)row, d[q]);
 #pragma unroll
-    for (int a = 0; a < 3; ++a) x[q][a] = ((m.rcs[a * 3] * px + m.rcs[a * 3 + 1] * py) + m.rcs[a * 3 + 2] * pz) + m.tcs[a];
+    for (int a = 0; a < 3; ++a) x[q][a] = rigid_apply(m.cs, a, p.x, p.y, p.z);
 #pragma unroll
-    for (int a = 0; a < 3; ++a) y[q][a] = ((m.rit[a * 3] * x[q][0] + m.rit[a * 3 + 1] * x[q][1]) + m.rit[a * 3 + 2] * x[q][2]) + m.tit[a];
+    for (int a = 0; a < 3; ++a) y[q][a] = rigid_apply(m.it, a, x[q][0], x[q][1], x[q][2]);
     ok[q] = ok[q] && y[q][2] >= 0.001f;
-    const float u = (cam.fx * y[q][0]) / y[q][2] + cam.cx, v = (cam.fy * y[q][1]) / y[q][2] + cam.cy;
-    cf[q] = floorf(u + 0.5f), rf[q] = floorf(v + 0.5f);
-    // decided in float so that a NaN or a huge value never reaches the cast
-    ok[q] = ok[q] && cf[q] >= 0.f && cf[q] <= (float)(cam.W - 1) && rf[q] >= 0.f && rf[q] <= (float)(cam.H - 1);
-    const size_t tp = tgt0 + (ok[q] ? (size_t)(int)rf[q] * cam.W + (size_t)(int)cf[q] : 0);      // inside view t whenever ok
-    nt[q] = ok[q] ? normals[tp] : make_float4(0.f, 0.f, 0.f, 0.f);
-    dt[q] = ok[q] ? depth[tp] : 0.f;
+    PixelHit h;
+    const size_t tp = gn_associate(cam, y[q], ok[q], normals, depth, tgt0, h, nt[q], dt[q]);
+    cf[q] = h.cf, rf[q] = h.rf;
     if constexpr (PHOTO) {
       ib[q] = ok[q] ? intensity[tp] : make_float4(0.f, 0.f, 0.f, 0.f);
-      du[q] = u - cf[q], dv[q] = v - rf[q];
+      du[q] = h.u - cf[q], dv[q] = h.v - rf[q];
     }
   }
 
@@ -173,23 +149,17 @@ __global__ __launch_bounds__(PA_THREADS) void depth_pairs_kernel(const float *__
 #pragma unroll
   for (int e = 0; e < GN_TERMS; ++e) acc[e] = 0.0;
 #pragma unroll
-  for (int q = 0; q < PA_PIX; ++q) {
+  for (int q = 0; q < GN_PIX; ++q) {
     bool valid = ok[q] && nt[q].w != 0.f;
-    const float qx = ((cf[q] - cam.cx) / cam.fx) * dt[q], qy = ((rf[q] - cam.cy) / cam.fy) * dt[q], qz = dt[q];
-    const float ex = y[q][0] - qx, ey = y[q][1] - qy, ez = y[q][2] - qz;
-    valid = valid && (ex * ex + ey * ey) + ez * ez < dist2_max;
-    const float nx = nt[q].x, ny = nt[q].y, nz = nt[q].z;
-    float w[3], g[3], no[3];
+    float w[3], g[3], no[3], J[6];                                 // the source normal in the object frame and in camera t
 #pragma unroll
-    for (int a = 0; a < 3; ++a) w[a] = (m.rcs[a * 3] * ns[q].x + m.rcs[a * 3 + 1] * ns[q].y) + m.rcs[a * 3 + 2] * ns[q].z;
+    for (int a = 0; a < 3; ++a) w[a] = rigid_rotate(m.cs, a, ns[q].x, ns[q].y, ns[q].z);
 #pragma unroll
-    for (int a = 0; a < 3; ++a) g[a] = (m.rit[a * 3] * w[0] + m.rit[a * 3 + 1] * w[1]) + m.rit[a * 3 + 2] * w[2];
-    valid = valid && (g[0] * nx + g[1] * ny) + g[2] * nz >= cos_min;
-    float r = (nx * ex + ny * ey) + nz * ez;
+    for (int a = 0; a < 3; ++a) g[a] = rigid_rotate(m.it, a, w[0], w[1], w[2]);
+    float r = gn_plane_residual(cam, valid, y[q], cf[q], rf[q], dt[q], nt[q], g, dist2_max, cos_min);
 #pragma unroll
-    for (int a = 0; a < 3; ++a) no[a] = (m.rct[a * 3] * nx + m.rct[a * 3 + 1] * ny) + m.rct[a * 3 + 2] * nz;
-    const float X = x[q][0], Y = x[q][1], Z = x[q][2];
-    float J[6] = {no[0], no[1], no[2], Y * no[2] - Z * no[1], Z * no[0] - X * no[2], X * no[1] - Y * no[0]};
+    for (int a = 0; a < 3; ++a) no[a] = mat3_row(m.rct, a, nt[q].x, nt[q].y, nt[q].z);
+    gn_twist_row(J, no[0], no[1], no[2], x[q][0], x[q][1], x[q][2]);
     gn_mask(J, r, valid);
     if (rows && pix[q] < hw) gn_store_row((float4 *)(rows + ((size_t)pr * (size_t)hw + (size_t)pix[q]) * ROW), J, r, valid);
     if constexpr (PHOTO) geo[q] = valid;
@@ -202,17 +172,16 @@ __global__ __launch_bounds__(PA_THREADS) void depth_pairs_kernel(const float *__
 #pragma unroll
     for (int e = 0; e < GN_TERMS; ++e) acc[e] = 0.0;
 #pragma unroll
-    for (int q = 0; q < PA_PIX; ++q) {
+    for (int q = 0; q < GN_PIX; ++q) {
       bool valid = geo[q] && ia[q].w != 0.f && ib[q].w != 0.f;
       float r = ((ib[q].x + ib[q].y * du[q]) + ib[q].z * dv[q]) - ia[q].x;
       valid = valid && fabsf(r) < i_max;
       const float jx = (ib[q].y * cam.fx) / y[q][2], jy = (ib[q].z * cam.fy) / y[q][2];
       const float jz = -((jx * y[q][0] + jy * y[q][1]) / y[q][2]);
-      float a[3];
+      float a[3], J[6];
 #pragma unroll
-      for (int k = 0; k < 3; ++k) a[k] = (m.rct[k * 3] * jx + m.rct[k * 3 + 1] * jy) + m.rct[k * 3 + 2] * jz;
-      const float X = x[q][0], Y = x[q][1], Z = x[q][2];
-      float J[6] = {a[0], a[1], a[2], Y * a[2] - Z * a[1], Z * a[0] - X * a[2], X * a[1] - Y * a[0]};
+      for (int k = 0; k < 3; ++k) a[k] = mat3_row(m.rct, k, jx, jy, jz);
+      gn_twist_row(J, a[0], a[1], a[2], x[q][0], x[q][1], x[q][2]);
       gn_mask(J, r, valid);
       if (rows && pix[q] < hw) gn_store_row((float4 *)(rows + ((size_t)pr * (size_t)hw + (size_t)pix[q]) * ROW) + 2, J, r, valid);
       gn_accumulate(acc, J, r, valid);
@@ -237,12 +206,12 @@ extern "C" int fp_depth_normals(fp_ctx *ctx, const float *d_depth, const uint8_t
   FP_REQUIRE(zfar > 0.f, "fp_depth_normals: zfar %g (> 0)", (double)zfar);
   FP_REQUIRE(max_jump > 0.f, "fp_depth_normals: max_jump %g (> 0)", (double)max_jump);
   FP_TRY(fp_check_camera("fp_depth_normals", K));
-  const DepthCam cam{(float)K[0], (float)K[4], (float)K[2], (float)K[5], H, W};
+  const Pinhole cam = pinhole_of(K, H, W);
   const long long total = (long long)n_views * H * W;
-  const long long blocks = (total + PA_THREADS - 1) / PA_THREADS;
+  const long long blocks = (total + PX_THREADS - 1) / PX_THREADS;
   FP_REQUIRE(blocks <= 0x7fffffff, "fp_depth_normals: %d views of %d x %d pixels are too many for one launch", n_views, H, W);
   if (n_views == 0) return FP_OK;
-  hipLaunchKernelGGL(depth_normals_kernel, dim3((unsigned)blocks), dim3(PA_THREADS), 0, (hipStream_t)stream, d_depth, d_mask, cam, zfar, max_jump,
+  hipLaunchKernelGGL(depth_normals_kernel, dim3((unsigned)blocks), dim3(PX_THREADS), 0, (hipStream_t)stream, d_depth, d_mask, cam, zfar, max_jump,
                      total, (float4 *)d_normals);
   FP_CHECK_HIP(hipGetLastError());
   return FP_OK;
@@ -269,7 +238,7 @@ int pairs_align(const char *fn, fp_ctx *ctx, const float *d_depth, const float *
   FP_REQUIRE(!photo || i_max > 0.f, "%s: i_max %g (> 0)", fn, (double)i_max);
   FP_TRY(fp_check_camera(fn, K));
   FP_TRY(fp_check_view_matrices(fn, cam_in_ob, n_views));
-  const DepthCam cam{(float)K[0], (float)K[4], (float)K[2], (float)K[5], H, W};
+  const Pinhole cam = pinhole_of(K, H, W);
   std::vector<PairRec> recs((size_t)n_pairs);
   for (int p = 0; p < n_pairs; ++p) {
     const int s = pairs[2 * p], t = pairs[2 * p + 1];
@@ -277,18 +246,11 @@ int pairs_align(const char *fn, fp_ctx *ctx, const float *d_depth, const float *
     FP_REQUIRE(s != t, "%s: pair %d joins view %d to itself", fn, p, s);
     const double *ms = cam_in_ob + (size_t)s * 16, *mt = cam_in_ob + (size_t)t * 16;
     PairRec &r = recs[p];
-    for (int a = 0; a < 3; ++a) {
-      for (int i = 0; i < 3; ++i) {
-        r.rcs[a * 3 + i] = (float)ms[a * 4 + i];
-        r.rct[a * 3 + i] = (float)mt[a * 4 + i];
-        r.rit[a * 3 + i] = (float)mt[i * 4 + a];
-      }
-      r.tcs[a] = (float)ms[a * 4 + 3];
-      r.tit[a] = (float)(-((mt[a] * mt[3] + mt[4 + a] * mt[7]) + mt[8 + a] * mt[11]));
-    }
+    r.cs = rigid_of(ms), r.it = rigid_inverse_of(mt);
+    memcpy(r.rct, rigid_of(mt).r, sizeof(r.rct));
     r.s = s, r.t = t, r.pad = 0;
   }
-  const long long n_tiles = ((long long)H * W + PA_TILE - 1) / PA_TILE;
+  const long long n_tiles = ((long long)H * W + GN_TILE - 1) / GN_TILE;
   FP_REQUIRE(n_tiles * FP_DEPTH_ALIGN_MAX_PAIRS <= 0x7fffffff, "%s: %d x %d pixels are too many for one launch", fn, H, W);
   if (n_pairs == 0) return FP_OK;
   hipStream_t s = (hipStream_t)stream;
@@ -304,25 +266,18 @@ int pairs_align(const char *fn, fp_ctx *ctx, const float *d_depth, const float *
   FP_REQUIRE(slab && sums && d_recs, "%s: arena exhausted", fn);
   // `recs` outlives the copy: the stream is synchronised before this returns
   FP_CHECK_HIP(hipMemcpyAsync(d_recs, recs.data(), recs_bytes, hipMemcpyHostToDevice, s));
-  const dim3 grid((unsigned)(n_tiles * n_pairs)), fold_grid((unsigned)((n_pairs * terms + 63) / 64));
+  const dim3 grid((unsigned)(n_tiles * n_pairs));
+  // the slab, the sums and the pair table go back to the arena, and `recs` goes, when this returns: gn_fold_to_host has synchronised by then
   if (photo) {
-    hipLaunchKernelGGL(depth_pairs_kernel<true>, grid, dim3(PA_THREADS), 0, s, d_depth, (const float4 *)d_normals, (const float4 *)d_intensity, cam,
+    hipLaunchKernelGGL(depth_pairs_kernel<true>, grid, dim3(GN_THREADS), 0, s, d_depth, (const float4 *)d_normals, (const float4 *)d_intensity, cam,
                        (const PairRec *)d_recs, (int)n_tiles, dist_max * dist_max, cos_min, i_max, d_rows, slab);
     FP_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(gn_fold_kernel<FP_PHOTO_ALIGN_TERMS>, fold_grid, dim3(64), 0, s, (const double *)slab, n_pairs, (int)n_tiles, sums);
-  } else {
-    hipLaunchKernelGGL(depth_pairs_kernel<false>, grid, dim3(PA_THREADS), 0, s, d_depth, (const float4 *)d_normals, (const float4 *)nullptr, cam,
-                       (const PairRec *)d_recs, (int)n_tiles, dist_max * dist_max, cos_min, 0.f, d_rows, slab);
-    FP_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(gn_fold_kernel<FP_DEPTH_ALIGN_TERMS>, fold_grid, dim3(64), 0, s, (const double *)slab, n_pairs, (int)n_tiles, sums);
+    return gn_fold_to_host<FP_PHOTO_ALIGN_TERMS>(slab, n_pairs, (int)n_tiles, sums, h_sums, s);
   }
+  hipLaunchKernelGGL(depth_pairs_kernel<false>, grid, dim3(GN_THREADS), 0, s, d_depth, (const float4 *)d_normals, (const float4 *)nullptr, cam,
+                     (const PairRec *)d_recs, (int)n_tiles, dist_max * dist_max, cos_min, 0.f, d_rows, slab);
   FP_CHECK_HIP(hipGetLastError());
-  // the slab, the sums and the pair table go back to the arena when this returns: the stream has been synchronised by then
-  hipError_t e1 = hipMemcpyAsync(h_sums, sums, sums_bytes, hipMemcpyDeviceToHost, s);
-  hipError_t e2 = hipStreamSynchronize(s);      // also after a failed copy: `recs` and the arena must not be in use when this returns
-  FP_CHECK_HIP(e1);
-  FP_CHECK_HIP(e2);
-  return FP_OK;
+  return gn_fold_to_host<FP_DEPTH_ALIGN_TERMS>(slab, n_pairs, (int)n_tiles, sums, h_sums, s);
 }
 
 }  // namespace
@@ -349,10 +304,10 @@ extern "C" int fp_view_intensity(fp_ctx *ctx, const uint8_t *d_rgb, const float 
   FP_REQUIRE(n_views >= 0 && n_views <= FP_TSDF_MAX_VIEWS, "fp_view_intensity: n_views %d (0 .. %d)", n_views, FP_TSDF_MAX_VIEWS);
   FP_REQUIRE(H >= 1 && W >= 1, "fp_view_intensity: H %d, W %d", H, W);
   const long long total = (long long)n_views * H * W;
-  const long long blocks = (total + PA_THREADS - 1) / PA_THREADS;
+  const long long blocks = (total + PX_THREADS - 1) / PX_THREADS;
   FP_REQUIRE(blocks <= 0x7fffffff, "fp_view_intensity: %d views of %d x %d pixels are too many for one launch", n_views, H, W);
   if (n_views == 0) return FP_OK;
-  hipLaunchKernelGGL(view_intensity_kernel, dim3((unsigned)blocks), dim3(PA_THREADS), 0, (hipStream_t)stream, d_rgb, (const float4 *)d_normals, H, W,
+  hipLaunchKernelGGL(view_intensity_kernel, dim3((unsigned)blocks), dim3(PX_THREADS), 0, (hipStream_t)stream, d_rgb, (const float4 *)d_normals, H, W,
                      total, (float4 *)d_intensity);
   FP_CHECK_HIP(hipGetLastError());
   return FP_OK;

@@ -11,6 +11,7 @@
 // adds in tile order and divides by N, so a pose's result is bit-identical whatever batch it is in and at whatever index.
 #include "common.h"
 #include "device_util.h"
+#include "view_geom.h"
 
 namespace {
 
@@ -337,13 +338,6 @@ struct VsdArgs {
   unsigned *counts;                               // [pose][2 + FP_VSD_MAX_TAUS]: |union|, |inter|, cost_tau (zeroed by the caller)
 };
 
-// bop_toolkit misc.depth_im_to_dist_im_fast at one pixel: float64, the products and sums in the order written, not contracted
-__device__ __forceinline__ double dist_of(double d, double u_cx, double v_cy, double inv_fx, double inv_fy) {
-#pragma clang fp contract(off)
-  const double X = (u_cx * d) * inv_fx, Y = (v_cy * d) * inv_fy;
-  return sqrt((X * X + Y * Y) + d * d);
-}
-
 // grid (bands of `rows` rows, poses); the pose's counts start at counts + blockIdx.y * (2 + FP_VSD_MAX_TAUS)
 __global__ __launch_bounds__(VSD_THREADS) void vsd_count_kernel(VsdArgs a) {
   __shared__ unsigned red[VSD_THREADS / 64][2 + FP_VSD_MAX_TAUS];
@@ -374,9 +368,9 @@ __global__ __launch_bounds__(VSD_THREADS) void vsd_count_kernel(VsdArgs a) {
         const int p = pb + j * VSD_THREADS;
         const int v = p / a.W, u = p - v * a.W;
         const double u_cx = (double)u - a.cx, v_cy = (double)v - a.cy;
-        const double Dt = dist_of((double)dt[p], u_cx, v_cy, a.inv_fx, a.inv_fy);
-        const double Dg = dist_of((double)g4[j], u_cx, v_cy, a.inv_fx, a.inv_fy);
-        const double De = dist_of((double)e4[j], u_cx, v_cy, a.inv_fx, a.inv_fy);
+        const double Dt = ray_distance((double)dt[p], u_cx, v_cy, a.inv_fx, a.inv_fy);
+        const double Dg = ray_distance((double)g4[j], u_cx, v_cy, a.inv_fx, a.inv_fy);
+        const double De = ray_distance((double)e4[j], u_cx, v_cy, a.inv_fx, a.inv_fy);
         const float ft = (float)Dt;
         vg = Dg > 0.0 && ((double)((float)Dg - ft) <= a.delta || Dt == 0.0);
         ve = (De > 0.0 && ((double)((float)De - ft) <= a.delta || Dt == 0.0)) || (vg && De > 0.0);

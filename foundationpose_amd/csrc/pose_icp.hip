@@ -4,14 +4,13 @@
 // stated in include/foundationpose_amd.h and restated in numpy by tests/pose_icp_oracle.py; this file follows it operation for operation
 // (the library is built without contraction).
 //
-// pose_align_kernel is a front end of gn_sums.h with the launch shape of depth_pairs_kernel<false> (depth_icp.hip): a workgroup owns
-// (pose, a tile of PI_TILE map pixels); the pose is uniform in the workgroup, so its origin arrives as three scalar loads.  A lane takes
-// PI_PIX pixels, PI_THREADS apart (the map reads coalesce: 12-byte records), in three passes over them: the model's point and normal;
-// then the projection into the frame and the two gathers of each pixel (16-byte normal, 4-byte depth) - nothing in this pass depends on
-// a gathered value, so all PI_PIX x 2 gathers are in flight together; then the arithmetic.  The row, the 29 sums in double and their
-// way through the wave, LDS and the slab to gn_fold_kernel are those of gn_sums.h, where the summation order is stated.  No atomics on
-// the sums.  A wave whose 256 map pixels are all background (most of a crop's border) writes zero rows and +0.0 sums and skips passes two
-// and three.  The two pixel counts are integers: ballots per wave, one pair per workgroup in a slab of their own, added per pose by
+// pose_align_kernel is one of the three aligners of gn_sums.h, which holds what they share: the tile, the three passes, the association,
+// the point-to-plane row, the 29 sums in double and their way to gn_fold_kernel; the camera is that of view_geom.h.  A workgroup owns
+// (pose, a tile of GN_TILE map pixels); the pose is uniform in the workgroup, so its origin arrives as three scalar loads.  Pass one
+// reads the model's point and normal (12-byte records, the reads coalesce); pass two projects into the frame and gathers each pixel's
+// 16-byte normal and 4-byte depth, all GN_PIX x 2 gathers in flight together; pass three is the arithmetic.  No atomics on the sums.
+// A wave whose 256 map pixels are all background (most of a crop's border) writes zero rows and +0.0 sums and skips passes two and
+// three.  The two pixel counts are integers: ballots per wave, one pair per workgroup in a slab of their own, added per pose by
 // pose_counts_fold_kernel.  No atomics there either, and no memset: every launch writes all it later reads.
 //
 // pose_gn_step_kernel is one thread per pose in double: the gates of the loop, LDL^T of the damped 6 x 6 system without square roots,
@@ -27,33 +26,24 @@ static_assert(sizeof(fp_pose_state) == 136, "fp_pose_state is laid out as the he
 
 namespace {
 
-constexpr int PI_THREADS = 256;
-constexpr int PI_PIX = 4;
-constexpr int PI_TILE = PI_THREADS * PI_PIX;      // 1024 map pixels per workgroup
-
-struct PoseCam {
-  float fx, fy, cx, cy;
-  int H, W;
-};
-
-__global__ __launch_bounds__(PI_THREADS) void pose_align_kernel(const float *__restrict__ xyz, const float *__restrict__ normal,
-                                                                const float *__restrict__ depth, const float4 *__restrict__ normals, PoseCam cam,
+__global__ __launch_bounds__(GN_THREADS) void pose_align_kernel(const float *__restrict__ xyz, const float *__restrict__ normal,
+                                                                const float *__restrict__ depth, const float4 *__restrict__ normals, Pinhole cam,
                                                                 const float *__restrict__ poses, int hw, int n_tiles, float dist2_max, float cos_min,
                                                                 float *__restrict__ rows, double *__restrict__ slab, int *__restrict__ cslab) {
-  __shared__ double red[PI_THREADS / 64][GN_TERMS];
-  __shared__ int cnt[PI_THREADS / 64][2];
+  __shared__ double red[GN_THREADS / 64][GN_TERMS];
+  __shared__ int cnt[GN_THREADS / 64][2];
   const int tid = threadIdx.x;
   const int tile = blockIdx.x % n_tiles, pr = blockIdx.x / n_tiles;
   const float c0 = poses[(size_t)pr * 16 + 3], c1 = poses[(size_t)pr * 16 + 7], c2 = poses[(size_t)pr * 16 + 11];      // uniform: scalar loads
   const size_t map0 = (size_t)pr * (size_t)hw;
 
   // pass 1: the model's point and normal in the camera frame
-  float y[PI_PIX][3], nm[PI_PIX][3];
-  bool ok[PI_PIX];
-  int pix[PI_PIX];
+  float y[GN_PIX][3], nm[GN_PIX][3];
+  bool ok[GN_PIX];
+  int pix[GN_PIX];
 #pragma unroll
-  for (int q = 0; q < PI_PIX; ++q) {
-    pix[q] = tile * PI_TILE + q * PI_THREADS + tid;
+  for (int q = 0; q < GN_PIX; ++q) {
+    pix[q] = tile * GN_TILE + q * GN_THREADS + tid;
     const bool in = pix[q] < hw;                                   // the last tile of a map is ragged
     const float *py = xyz + (map0 + (size_t)(in ? pix[q] : 0)) * 3, *pn = normal + (map0 + (size_t)(in ? pix[q] : 0)) * 3;
 #pragma unroll
@@ -65,32 +55,16 @@ __global__ __launch_bounds__(PI_THREADS) void pose_align_kernel(const float *__r
   }
   int n_rendered = 0, n_observed = 0;                              // of the wave; uniform in it
 
-  // A wave without a single rendered pixel has nothing to project: its rows are zeros and its 29 partial sums are +0.0, the value the
-  // passes below would arrive at (0.f x 0.f widened and added to +0.0).  Uniform in the wave.
-  if (!__any(ok[0] || ok[1] || ok[2] || ok[3])) {
-    if (rows) {
-#pragma unroll
-      for (int q = 0; q < PI_PIX; ++q)
-        if (pix[q] < hw) {
-          float4 *o = (float4 *)(rows + (map0 + (size_t)pix[q]) * 8);
-          o[0] = o[1] = make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    }
-    if ((tid & 63) < GN_TERMS) red[tid >> 6][tid & 63] = 0.0;
-  } else {
+  // A wave without a single rendered pixel skips the passes below (gn_sums.h).
+  if (!gn_empty_wave<8>(ok, rows, map0, pix, hw, red[tid >> 6])) {
     // pass 2: the point's pixel in the frame, the two gathers
-    float cf[PI_PIX], rf[PI_PIX], dt[PI_PIX];
-    float4 nt[PI_PIX];
+    PixelHit h[GN_PIX];
+    float dt[GN_PIX];
+    float4 nt[GN_PIX];
 #pragma unroll
-    for (int q = 0; q < PI_PIX; ++q) {
+    for (int q = 0; q < GN_PIX; ++q) {
       n_rendered += __popcll(__ballot(ok[q]));
-      const float u = (cam.fx * y[q][0]) / y[q][2] + cam.cx, v = (cam.fy * y[q][1]) / y[q][2] + cam.cy;
-      cf[q] = floorf(u + 0.5f), rf[q] = floorf(v + 0.5f);
-      // decided in float so that a NaN or a huge value never reaches the cast
-      ok[q] = ok[q] && cf[q] >= 0.f && cf[q] <= (float)(cam.W - 1) && rf[q] >= 0.f && rf[q] <= (float)(cam.H - 1);
-      const size_t tp = ok[q] ? (size_t)(int)rf[q] * cam.W + (size_t)(int)cf[q] : 0;      // inside the frame whenever ok
-      nt[q] = ok[q] ? normals[tp] : make_float4(0.f, 0.f, 0.f, 0.f);
-      dt[q] = ok[q] ? depth[tp] : 0.f;
+      gn_associate(cam, y[q], ok[q], normals, depth, 0, h[q], nt[q], dt[q]);
     }
 
     // pass 3: the gates, the row, the sums
@@ -98,17 +72,11 @@ __global__ __launch_bounds__(PI_THREADS) void pose_align_kernel(const float *__r
 #pragma unroll
     for (int e = 0; e < GN_TERMS; ++e) acc[e] = 0.0;
 #pragma unroll
-    for (int q = 0; q < PI_PIX; ++q) {
+    for (int q = 0; q < GN_PIX; ++q) {
       bool valid = ok[q] && nt[q].w != 0.f;
       n_observed += __popcll(__ballot(valid));
-      const float qx = ((cf[q] - cam.cx) / cam.fx) * dt[q], qy = ((rf[q] - cam.cy) / cam.fy) * dt[q], qz = dt[q];
-      const float ex = y[q][0] - qx, ey = y[q][1] - qy, ez = y[q][2] - qz;
-      valid = valid && (ex * ex + ey * ey) + ez * ez < dist2_max;
-      const float nx = nt[q].x, ny = nt[q].y, nz = nt[q].z;
-      valid = valid && (nm[q][0] * nx + nm[q][1] * ny) + nm[q][2] * nz >= cos_min;
-      float r = (nx * ex + ny * ey) + nz * ez;
-      const float X = y[q][0] - c0, Y = y[q][1] - c1, Z = y[q][2] - c2;
-      float J[6] = {nx, ny, nz, Y * nz - Z * ny, Z * nx - X * nz, X * ny - Y * nx};
+      float r = gn_plane_residual(cam, valid, y[q], h[q].cf, h[q].rf, dt[q], nt[q], nm[q], dist2_max, cos_min), J[6];
+      gn_twist_row(J, nt[q].x, nt[q].y, nt[q].z, y[q][0] - c0, y[q][1] - c1, y[q][2] - c2);
       gn_mask(J, r, valid);
       if (rows && pix[q] < hw) gn_store_row((float4 *)(rows + (map0 + (size_t)pix[q]) * 8), J, r, valid);
       gn_accumulate(acc, J, r, valid);
@@ -121,7 +89,7 @@ __global__ __launch_bounds__(PI_THREADS) void pose_align_kernel(const float *__r
   if (cslab && tid < 2) {
     int s = 0;
 #pragma unroll
-    for (int wv = 0; wv < PI_THREADS / 64; ++wv) s += cnt[wv][tid];
+    for (int wv = 0; wv < GN_THREADS / 64; ++wv) s += cnt[wv][tid];
     cslab[((size_t)pr * n_tiles + tile) * 2 + tid] = s;
   }
 }
@@ -260,7 +228,7 @@ __global__ __launch_bounds__(64) void pose_gn_step_kernel(const double *__restri
 }
 
 struct AlignShape {
-  PoseCam cam;
+  Pinhole cam;
   int hw, n_tiles;
 };
 
@@ -272,28 +240,27 @@ int align_shape(const char *fn, int N, int h, int w, int H, int W, const double 
   FP_REQUIRE(dist_max > 0.f, "%s: dist_max %g (> 0)", fn, (double)dist_max);
   FP_REQUIRE(cos_min >= -1.f && cos_min <= 1.f, "%s: cos_min %g (-1 .. 1)", fn, (double)cos_min);
   FP_TRY(fp_check_camera(fn, K));
-  o.cam = PoseCam{(float)K[0], (float)K[4], (float)K[2], (float)K[5], H, W};
+  o.cam = pinhole_of(K, H, W);
   o.hw = h * w;
-  o.n_tiles = (o.hw + PI_TILE - 1) / PI_TILE;      // <= 2^14, times 1024 poses: inside a grid
+  o.n_tiles = (o.hw + GN_TILE - 1) / GN_TILE;      // <= 2^14, times 1024 poses: inside a grid
   return FP_OK;
 }
 
 size_t align_slab_bytes(const AlignShape &sh, int N) { return (size_t)N * (size_t)sh.n_tiles * GN_TERMS * sizeof(double); }
 size_t align_cslab_bytes(const AlignShape &sh, int N) { return (size_t)N * (size_t)sh.n_tiles * 2 * sizeof(int); }
 
-// the launches of one linearisation; `slab` holds align_slab_bytes and, with `counts`, `cslab` align_cslab_bytes
+// the launches of one linearisation; `slab` holds align_slab_bytes and, with `counts`, `cslab` align_cslab_bytes.  With h_sums the sums
+// are copied there and the stream is synchronised; without, nothing synchronises
 int launch_pose_align(const AlignShape &sh, const float *xyz, const float *normal, const float *depth, const float *normals, const float *poses, int N,
-                      float dist_max, float cos_min, float *rows, double *slab, int *cslab, double *sums, int *counts, hipStream_t s) {
-  hipLaunchKernelGGL(pose_align_kernel, dim3((unsigned)(sh.n_tiles * N)), dim3(PI_THREADS), 0, s, xyz, normal, depth, (const float4 *)normals, sh.cam,
+                      float dist_max, float cos_min, float *rows, double *slab, int *cslab, double *sums, int *counts, double *h_sums, hipStream_t s) {
+  hipLaunchKernelGGL(pose_align_kernel, dim3((unsigned)(sh.n_tiles * N)), dim3(GN_THREADS), 0, s, xyz, normal, depth, (const float4 *)normals, sh.cam,
                      poses, sh.hw, sh.n_tiles, dist_max * dist_max, cos_min, rows, slab, counts ? cslab : nullptr);
-  FP_CHECK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(gn_fold_kernel<GN_TERMS>, dim3((unsigned)((N * GN_TERMS + 63) / 64)), dim3(64), 0, s, (const double *)slab, N, sh.n_tiles, sums);
   FP_CHECK_HIP(hipGetLastError());
   if (counts) {
     hipLaunchKernelGGL(pose_counts_fold_kernel, dim3((unsigned)((N * 2 + 63) / 64)), dim3(64), 0, s, (const int *)cslab, N, sh.n_tiles, counts);
     FP_CHECK_HIP(hipGetLastError());
   }
-  return FP_OK;
+  return gn_fold_to_host<GN_TERMS>(slab, N, sh.n_tiles, sums, h_sums, s);
 }
 
 int step_checks(const char *fn, int N, double damping, int min_pixels) {
@@ -328,19 +295,12 @@ extern "C" int fp_pose_depth_align(fp_ctx *ctx, const float *d_xyz, const float 
   const size_t slab_bytes = align_slab_bytes(sh, N);
   const size_t cslab_bytes = d_counts ? align_cslab_bytes(sh, N) : 0;
   FP_TRY(fp_arena_ensure(ctx, slab_bytes + cslab_bytes + 4096));
-  // the slab goes back to the arena when the launches are queued - the next taker runs behind them on the same stream
+  // the slab goes back to the arena when the launches are queued (with h_sums: synchronised) - the next taker runs behind them on the same stream
   ArenaScope scope(ctx->arena);
   double *slab = (double *)ctx->arena.take(slab_bytes);
   int *cslab = (int *)ctx->arena.take(cslab_bytes);
   FP_REQUIRE(slab && cslab, "fp_pose_depth_align: arena exhausted");
-  FP_TRY(launch_pose_align(sh, d_xyz, d_normal, d_depth, d_normals, d_poses, N, dist_max, cos_min, d_rows, slab, cslab, d_sums, d_counts, s));
-  if (h_sums) {
-    hipError_t e1 = hipMemcpyAsync(h_sums, d_sums, (size_t)N * GN_TERMS * sizeof(double), hipMemcpyDeviceToHost, s);
-    hipError_t e2 = hipStreamSynchronize(s);
-    FP_CHECK_HIP(e1);
-    FP_CHECK_HIP(e2);
-  }
-  return FP_OK;
+  return launch_pose_align(sh, d_xyz, d_normal, d_depth, d_normals, d_poses, N, dist_max, cos_min, d_rows, slab, cslab, d_sums, d_counts, h_sums, s);
 }
 
 extern "C" int fp_pose_gn_step(fp_ctx *ctx, const double *d_sums, float *d_poses, fp_pose_state *d_state, int N, double damping, int min_pixels,
@@ -398,7 +358,7 @@ extern "C" int fp_pose_polish(fp_ctx *ctx, const fp_mesh *mesh, float *d_poses, 
   for (int it = 0; it <= iterations; ++it) {
     if (crop) FP_TRY(launch_crop_window_tf(d_poses, N, K, crop_ratio, mesh_diameter, w, h, tf, bbox, s));
     FP_TRY(launch_render(ctx, a, s));
-    FP_TRY(launch_pose_align(sh, xyz, nrm, d_depth, d_normals, d_poses, N, dist_max, cos_min, nullptr, slab, cslab, d_sums, d_counts, s));
+    FP_TRY(launch_pose_align(sh, xyz, nrm, d_depth, d_normals, d_poses, N, dist_max, cos_min, nullptr, slab, cslab, d_sums, d_counts, nullptr, s));
     FP_TRY(launch_pose_gn_step(d_sums, d_poses, d_state, N, damping, min_pixels, it == iterations, it == 0, s));      // round 0 starts fresh records
   }
   return FP_OK;

@@ -13,6 +13,7 @@
 // field that it changed.  Integer sums, minima and maxima do not depend on their order: the results are deterministic.
 #include "common.h"
 #include "device_util.h"
+#include "view_geom.h"
 #include <algorithm>
 #include <climits>
 
@@ -35,13 +36,6 @@ struct SceneArgs {
   uint8_t *mask, *mask_visib;                     // (n_inst, H, W) of the whole call (indexed by i0 + i), or null
   int *acc;                                       // (n_inst, SC_COLS) accumulators of the whole call, or null
 };
-
-// bop_toolkit misc.depth_im_to_dist_im_fast at one pixel: float64, the products and sums in the order written, not contracted
-__device__ __forceinline__ double scene_dist(double d, double u_cx, double v_cy, double inv_fx, double inv_fy) {
-#pragma clang fp contract(off)
-  const double X = (u_cx * d) * inv_fx, Y = (v_cy * d) * inv_fy;
-  return sqrt((X * X + Y * Y) + d * d);
-}
 
 __device__ __forceinline__ bool is_min_col(int c) { return c == FP_SCENE_INFO_BBOX_OBJ || c == FP_SCENE_INFO_BBOX_OBJ + 1 ||
                                                            c == FP_SCENE_INFO_BBOX_VISIB || c == FP_SCENE_INFO_BBOX_VISIB + 1; }
@@ -133,9 +127,9 @@ __global__ __launch_bounds__(SC_THREADS) void scene_instances_kernel(SceneArgs a
 #pragma unroll
     for (int j = 0; j < PX; ++j) {
       valid[j] = t[j] > 0.f;
-      double Docc = a.occ_depth ? scene_dist((double)t[j], u_cx[j], v_cy, a.inv_fx, a.inv_fy) : 0.0;
+      double Docc = a.occ_depth ? ray_distance((double)t[j], u_cx[j], v_cy, a.inv_fx, a.inv_fy) : 0.0;
       if (a.occ_inst && dmin[j] > 0.f) {
-        const double Dmin = scene_dist((double)dmin[j], u_cx[j], v_cy, a.inv_fx, a.inv_fy);
+        const double Dmin = ray_distance((double)dmin[j], u_cx[j], v_cy, a.inv_fx, a.inv_fy);
         if (Dmin > 0.0 && (!(Docc > 0.0) || Dmin < Docc)) Docc = Dmin;
       }
       focc[j] = (float)Docc, no_occ[j] = Docc == 0.0;
@@ -163,7 +157,7 @@ __global__ __launch_bounds__(SC_THREADS) void scene_instances_kernel(SceneArgs a
 #pragma unroll
         for (int j = 0; j < PX; ++j)
           if (m[j]) {
-            const double Dm = scene_dist((double)d[j], u_cx[j], v_cy, a.inv_fx, a.inv_fy);
+            const double Dm = ray_distance((double)d[j], u_cx[j], v_cy, a.inv_fx, a.inv_fy);
             vis[j] = Dm > 0.0 && ((double)((float)Dm - focc[j]) <= a.delta || no_occ[j]);
           }
       }

@@ -40,11 +40,6 @@ constexpr int PS_CHUNK = 256;                      // hypotheses per workgroup o
 constexpr int PM_TERMS = FP_PLANE_MOMENT_TERMS;
 static_assert(PM_TERMS == 10 && FP_SEGMENT_STATS == 16 && FP_PLANE_MAX_HYP % PS_CHUNK == 0, "the header's sizes are those of this file");
 
-struct SegCam {
-  float fx, fy, cx, cy, zfar;
-  int H, W;
-};
-
 struct SegPlanes {
   float4 p[FP_TSDF_MAX_VIEWS];      // (n.x, n.y, n.z, dd) of every view
 };
@@ -54,11 +49,8 @@ struct SegRule {
   int min_pixels;
 };
 
-__device__ __forceinline__ bool seg_ok(float d, float zfar) { return d >= 0.001f && d < zfar; }
-
-__device__ __forceinline__ float3 seg_point(const SegCam &cam, int row, int col, float d) {
-  return make_float3((((float)col - cam.cx) / cam.fx) * d, (((float)row - cam.cy) / cam.fy) * d, d);
-}
+// the point of an integer pixel at depth d (view_geom.h)
+__device__ __forceinline__ float3 seg_point(const Pinhole &cam, int row, int col, float d) { return pinhole_point(cam, (float)col, (float)row, d); }
 
 __device__ __forceinline__ float seg_height(float4 pl, float3 p) { return ((pl.x * p.x + pl.y * p.y) + pl.z * p.z) + pl.w; }
 
@@ -67,7 +59,7 @@ __device__ __forceinline__ long long seg_q(float x) { return (long long)rintf(fm
 // ---- fp_plane_score ---------------------------------------------------------------------------------------------------------------
 
 // one thread per (view, hypothesis): the plane through the three pixels, or (0,0,0,0)
-__global__ __launch_bounds__(SEG_THREADS) void plane_hyp_kernel(const float *__restrict__ depth, const uint8_t *__restrict__ mask, SegCam cam,
+__global__ __launch_bounds__(SEG_THREADS) void plane_hyp_kernel(const float *__restrict__ depth, const uint8_t *__restrict__ mask, Pinhole cam, float zfar,
                                                                 const int32_t *__restrict__ trip, int n_hyp, int total,
                                                                 float4 *__restrict__ planes) {
   const int t = blockIdx.x * SEG_THREADS + threadIdx.x;
@@ -83,7 +75,7 @@ __global__ __launch_bounds__(SEG_THREADS) void plane_hyp_kernel(const float *__r
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
       const float d = depth[view0 + idx[a]];
-      valid = valid && seg_ok(d, cam.zfar) && (!mask || mask[view0 + idx[a]] != 0);
+      valid = valid && depth_ok(d, zfar) && (!mask || mask[view0 + idx[a]] != 0);
       const int row = idx[a] / cam.W;
       p[a] = seg_point(cam, row, idx[a] - row * cam.W, d);
     }
@@ -105,7 +97,7 @@ __global__ __launch_bounds__(SEG_THREADS) void plane_hyp_kernel(const float *__r
 }
 
 // blockIdx = (tile, chunk of hypotheses, view).  counts[view][hypothesis] has been zeroed.
-__global__ __launch_bounds__(SEG_THREADS) void plane_count_kernel(const float *__restrict__ depth, const uint8_t *__restrict__ mask, SegCam cam,
+__global__ __launch_bounds__(SEG_THREADS) void plane_count_kernel(const float *__restrict__ depth, const uint8_t *__restrict__ mask, Pinhole cam, float zfar,
                                                                   const float4 *__restrict__ planes, int n_hyp, float tol,
                                                                   int *__restrict__ counts) {
   __shared__ int cnt[PS_CHUNK];
@@ -123,7 +115,7 @@ __global__ __launch_bounds__(SEG_THREADS) void plane_count_kernel(const float *_
     const long long pix = (long long)blockIdx.x * PS_TILE + q * SEG_THREADS + tid;
     const bool in = pix < hw;                                      // the last tile of a view is ragged
     const float d = in ? depth[view0 + (size_t)pix] : 0.f;
-    ok[q] = in && seg_ok(d, cam.zfar);
+    ok[q] = in && depth_ok(d, zfar);
     if (mask) ok[q] = ok[q] && mask[view0 + (size_t)(in ? pix : 0)] != 0;
     const int row = (int)(pix / cam.W);
     p[q] = seg_point(cam, row, (int)(pix - (long long)row * cam.W), d);
@@ -173,7 +165,7 @@ __global__ __launch_bounds__(SEG_THREADS) void plane_best_kernel(const int *__re
 // ---- fp_plane_moments -------------------------------------------------------------------------------------------------------------
 
 // blockIdx.x = view * n_tiles + tile; the summation order is that of gn_sums.h with 10 terms
-__global__ __launch_bounds__(SEG_THREADS) void plane_moments_kernel(const float *__restrict__ depth, const uint8_t *__restrict__ mask, SegCam cam,
+__global__ __launch_bounds__(SEG_THREADS) void plane_moments_kernel(const float *__restrict__ depth, const uint8_t *__restrict__ mask, Pinhole cam, float zfar,
                                                                     SegPlanes planes, float tol, int n_tiles, double *__restrict__ slab) {
   __shared__ double red[SEG_THREADS / 64][PM_TERMS];
   const int tid = threadIdx.x;
@@ -189,7 +181,7 @@ __global__ __launch_bounds__(SEG_THREADS) void plane_moments_kernel(const float 
     const long long pix = (long long)tile * PS_TILE + q * SEG_THREADS + tid;
     const bool in = pix < hw;
     const float d = in ? depth[view0 + (size_t)pix] : 0.f;
-    bool ok = in && seg_ok(d, cam.zfar);
+    bool ok = in && depth_ok(d, zfar);
     if (mask) ok = ok && mask[view0 + (size_t)(in ? pix : 0)] != 0;
     const int row = (int)(pix / cam.W);
     const float3 p = seg_point(cam, row, (int)(pix - (long long)row * cam.W), d);
@@ -214,7 +206,7 @@ __global__ __launch_bounds__(SEG_THREADS) void plane_moments_kernel(const float 
 // One thread per pixel of the batch, i = view H W + row W + col; a workgroup starts at a multiple of 64, so lane == i & 63.
 // parent[i] = -1 for background; for foreground the first pixel of the run of joined pixels that ends at i, as far as it lies in this
 // wave: i - 1 is in the same row when col > 0 and in the same wave when lane > 0.
-__global__ __launch_bounds__(SEG_THREADS) void seg_init_kernel(const float *__restrict__ depth, const uint8_t *__restrict__ mask, SegCam cam,
+__global__ __launch_bounds__(SEG_THREADS) void seg_init_kernel(const float *__restrict__ depth, const uint8_t *__restrict__ mask, Pinhole cam, float zfar,
                                                                SegPlanes planes, SegRule rule, int total, int *__restrict__ parent,
                                                                int *__restrict__ cnt) {
   const int i = blockIdx.x * SEG_THREADS + threadIdx.x, lane = threadIdx.x & 63;
@@ -222,7 +214,7 @@ __global__ __launch_bounds__(SEG_THREADS) void seg_init_kernel(const float *__re
   const int hw = cam.H * cam.W;
   const int v = in ? i / hw : 0, pix = i - v * hw, row = pix / cam.W, col = pix - row * cam.W;
   const float d = in ? depth[i] : 0.f;
-  bool fg = in && seg_ok(d, cam.zfar);
+  bool fg = in && depth_ok(d, zfar);
   if (mask) fg = fg && mask[in ? i : 0] != 0;
   const float h = seg_height(planes.p[v], seg_point(cam, row, col, d));
   fg = fg && h >= rule.h_min && h <= rule.h_max;
@@ -238,7 +230,7 @@ __global__ __launch_bounds__(SEG_THREADS) void seg_init_kernel(const float *__re
 }
 
 // joins a foreground pixel with the one above it, and with the one to its left where seg_init_kernel could not (lane 0)
-__global__ __launch_bounds__(SEG_THREADS) void seg_hook_kernel(const float *__restrict__ depth, SegCam cam, float max_jump, int total, int *parent) {
+__global__ __launch_bounds__(SEG_THREADS) void seg_hook_kernel(const float *__restrict__ depth, Pinhole cam, float max_jump, int total, int *parent) {
   const int i = blockIdx.x * SEG_THREADS + threadIdx.x;
   if (i >= total || cc_load(&parent[i]) < 0) return;
   const int hw = cam.H * cam.W;
@@ -304,7 +296,7 @@ __device__ __forceinline__ void stats_atomics(long long *row, const long long (&
 }
 
 // the label image and, with `stats`, the statistics of the kept components; stats rows have been initialised
-__global__ __launch_bounds__(SEG_THREADS) void seg_label_kernel(const float *__restrict__ depth, SegCam cam, SegPlanes planes, int min_pixels,
+__global__ __launch_bounds__(SEG_THREADS) void seg_label_kernel(const float *__restrict__ depth, Pinhole cam, SegPlanes planes, int min_pixels,
                                                                 int total, const int *__restrict__ label, const int *__restrict__ cnt,
                                                                 const u64 *__restrict__ data, int32_t *__restrict__ labels,
                                                                 long long *__restrict__ stats) {
@@ -376,7 +368,7 @@ extern "C" int fp_plane_score(fp_ctx *ctx, const float *d_depth, const uint8_t *
   FP_REQUIRE(tol > 0.f, "fp_plane_score: tol %g (> 0)", (double)tol);
   FP_TRY(seg_check_frame("fp_plane_score", n_views, H, W, K, zfar));
   if (n_views == 0) return FP_OK;
-  const SegCam cam{(float)K[0], (float)K[4], (float)K[2], (float)K[5], zfar, H, W};
+  const Pinhole cam = pinhole_of(K, H, W);
   hipStream_t s = (hipStream_t)stream;
   if (n_hyp == 0) {
     FP_CHECK_HIP(hipStreamSynchronize(s));
@@ -395,12 +387,12 @@ extern "C" int fp_plane_score(fp_ctx *ctx, const float *d_depth, const uint8_t *
   FP_REQUIRE(trip && planes && counts && best, "fp_plane_score: arena exhausted");
   FP_CHECK_HIP(hipMemcpyAsync(trip, triplets, nvh * 12, hipMemcpyHostToDevice, s));
   FP_CHECK_HIP(hipMemsetAsync(counts, 0, nvh * 4, s));
-  hipLaunchKernelGGL(plane_hyp_kernel, grid_for((long long)nvh), dim3(SEG_THREADS), 0, s, d_depth, d_mask, cam, (const int32_t *)trip, n_hyp, (int)nvh,
+  hipLaunchKernelGGL(plane_hyp_kernel, grid_for((long long)nvh), dim3(SEG_THREADS), 0, s, d_depth, d_mask, cam, zfar, (const int32_t *)trip, n_hyp, (int)nvh,
                      planes);
   FP_CHECK_HIP(hipGetLastError());
   const unsigned n_tiles = (unsigned)(((long long)H * W + PS_TILE - 1) / PS_TILE);
   hipLaunchKernelGGL(plane_count_kernel, dim3(n_tiles, (unsigned)((n_hyp + PS_CHUNK - 1) / PS_CHUNK), (unsigned)n_views), dim3(SEG_THREADS), 0, s, d_depth,
-                     d_mask, cam, (const float4 *)planes, n_hyp, tol, counts);
+                     d_mask, cam, zfar, (const float4 *)planes, n_hyp, tol, counts);
   FP_CHECK_HIP(hipGetLastError());
   hipLaunchKernelGGL(plane_best_kernel, dim3((unsigned)n_views), dim3(SEG_THREADS), 0, s, (const int *)counts, n_hyp, best);
   FP_CHECK_HIP(hipGetLastError());
@@ -421,7 +413,7 @@ extern "C" int fp_plane_moments(fp_ctx *ctx, const float *d_depth, const uint8_t
   SegPlanes pl;
   FP_TRY(seg_check_planes("fp_plane_moments", planes, n_views, &pl));
   if (n_views == 0) return FP_OK;
-  const SegCam cam{(float)K[0], (float)K[4], (float)K[2], (float)K[5], zfar, H, W};
+  const Pinhole cam = pinhole_of(K, H, W);
   hipStream_t s = (hipStream_t)stream;
   FP_CHECK_HIP(hipSetDevice(ctx->device));
   const int n_tiles = (int)(((long long)H * W + PS_TILE - 1) / PS_TILE);
@@ -431,14 +423,9 @@ extern "C" int fp_plane_moments(fp_ctx *ctx, const float *d_depth, const uint8_t
   double *slab = (double *)ctx->arena.take(slab_bytes);
   double *sums = (double *)ctx->arena.take(sums_bytes);
   FP_REQUIRE(slab && sums, "fp_plane_moments: arena exhausted");
-  hipLaunchKernelGGL(plane_moments_kernel, dim3((unsigned)(n_tiles * n_views)), dim3(SEG_THREADS), 0, s, d_depth, d_mask, cam, pl, tol, n_tiles, slab);
+  hipLaunchKernelGGL(plane_moments_kernel, dim3((unsigned)(n_tiles * n_views)), dim3(SEG_THREADS), 0, s, d_depth, d_mask, cam, zfar, pl, tol, n_tiles, slab);
   FP_CHECK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(gn_fold_kernel<PM_TERMS>, dim3((unsigned)((n_views * PM_TERMS + 63) / 64)), dim3(64), 0, s, (const double *)slab, n_views, n_tiles,
-                     sums);
-  FP_CHECK_HIP(hipGetLastError());
-  FP_CHECK_HIP(hipMemcpyAsync(h_sums, sums, sums_bytes, hipMemcpyDeviceToHost, s));
-  FP_CHECK_HIP(hipStreamSynchronize(s));
-  return FP_OK;
+  return gn_fold_to_host<PM_TERMS>(slab, n_views, n_tiles, sums, h_sums, s);
 }
 
 // What fp_depth_segment_count leaves for fp_depth_segment_write: one allocation owned by the context, grown when a larger batch arrives.
@@ -452,7 +439,7 @@ struct fp_segment_state {
   const float *depth = nullptr;
   int n_views = 0, H = 0, W = 0, min_pixels = 0;
   long long kept = 0;
-  SegCam cam;
+  Pinhole cam;
   SegPlanes planes;
 };
 
@@ -495,10 +482,10 @@ extern "C" int fp_depth_segment_count(fp_ctx *ctx, const float *d_depth, const u
   if (n_views > 0) {
     const long long total = (long long)n_views * H * W;
     FP_TRY(segment_layout(st, total));
-    const SegCam cam{(float)K[0], (float)K[4], (float)K[2], (float)K[5], zfar, H, W};
+    const Pinhole cam = pinhole_of(K, H, W);
     const SegRule rule{h_min, h_max, max_jump, min_pixels};
     st->cam = cam, st->planes = pl;
-    hipLaunchKernelGGL(seg_init_kernel, grid_for(total), dim3(SEG_THREADS), 0, s, d_depth, d_mask, cam, pl, rule, (int)total, st->parent, st->cnt);
+    hipLaunchKernelGGL(seg_init_kernel, grid_for(total), dim3(SEG_THREADS), 0, s, d_depth, d_mask, cam, zfar, pl, rule, (int)total, st->parent, st->cnt);
     FP_CHECK_HIP(hipGetLastError());
     hipLaunchKernelGGL(seg_hook_kernel, grid_for(total), dim3(SEG_THREADS), 0, s, d_depth, cam, max_jump, (int)total, st->parent);
     FP_CHECK_HIP(hipGetLastError());

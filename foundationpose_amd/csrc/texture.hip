@@ -9,8 +9,9 @@
 // the wave: scalar loads), the views loop inside the thread in index order, and a texel belongs to one thread: no atomics, no
 // synchronisation, the same bits on every run.  Neighbouring texels of a face project to neighbouring pixels, so the depth and colour
 // reads of a wave fall into a few cache lines per view.  Plain vector loads and stores; there is no LDS stage: nothing is shared beyond
-// what the cache already merges.
+// what the cache already merges.  The camera, the object -> camera transforms and the projection (the ratio rule) are those of view_geom.h.
 #include "common.h"
+#include "view_geom.h"
 
 #include <math.h>
 
@@ -18,17 +19,9 @@ namespace {
 
 constexpr int TB_X = 64, TB_Y = 4;
 
-struct TexView {
-  float r[9], t[3];      // object -> camera
-};
-
-struct TexViews {
-  TexView v[FP_TSDF_MAX_VIEWS];
-};
-
 struct TexCfg {
-  int T, c, g, F, V, top_n, H, W, n_views;
-  float fx, fy, cx, cy, zfar, depth_tol, cos_min;
+  int T, c, g, F, V, top_n, n_views;
+  float zfar, depth_tol, cos_min;
 };
 
 __device__ __forceinline__ uint8_t to_u8(float x) { return (uint8_t)fminf(fmaxf(floorf(x + 0.5f), 0.f), 255.f); }
@@ -36,7 +29,7 @@ __device__ __forceinline__ uint8_t to_u8(float x) { return (uint8_t)fminf(fmaxf(
 __global__ __launch_bounds__(TB_X *TB_Y) void texture_bake_kernel(const float *__restrict__ pos, const int32_t *__restrict__ faces,
                                                                    const uint8_t *__restrict__ vcol, const uint8_t *__restrict__ rgb,
                                                                    const float *__restrict__ depth, const uint8_t *__restrict__ mask,
-                                                                   uint8_t *__restrict__ tex, int8_t *__restrict__ used, TexCfg k, TexViews views) {
+                                                                   uint8_t *__restrict__ tex, int8_t *__restrict__ used, TexCfg k, Pinhole cam, Rigids views) {
   const int X = blockIdx.x * TB_X + threadIdx.x, Y = blockIdx.y * TB_Y + threadIdx.y;
   if (X >= k.T || Y >= k.T) return;
   const size_t o = (size_t)Y * k.T + X;
@@ -80,22 +73,24 @@ __global__ __launch_bounds__(TB_X *TB_Y) void texture_bake_kernel(const float *_
 
   float tw[4] = {-1.f, -1.f, -1.f, -1.f}, tr[4] = {0.f, 0.f, 0.f, 0.f}, tg[4] = {0.f, 0.f, 0.f, 0.f}, tb[4] = {0.f, 0.f, 0.f, 0.f};
   int cnt = 0;
-  const float Wl = (float)(k.W - 1), Hl = (float)(k.H - 1);
-  const size_t hw = (size_t)k.H * k.W;
+  const float Wl = (float)(cam.W - 1), Hl = (float)(cam.H - 1);
+  const size_t hw = (size_t)cam.H * cam.W;
   for (int v = 0; v < k.n_views; ++v) {
-    const TexView &m = views.v[v];
+    const Rigid &m = views.v[v];
+    // rigid_apply of view_geom.h, written out: through the helper this loop's arithmetic is packed differently and the bake is 1.5 % slower
     const float qz = ((m.r[6] * px + m.r[7] * py) + m.r[8] * pz) + m.t[2];
     if (!(qz >= 0.001f)) continue;
     const float qx = ((m.r[0] * px + m.r[1] * py) + m.r[2] * pz) + m.t[0];
     const float qy = ((m.r[3] * px + m.r[4] * py) + m.r[5] * pz) + m.t[1];
-    const float xf = k.fx * (qx / qz) + k.cx, yf = k.fy * (qy / qz) + k.cy;
+    const float2 uv = project_ratio(cam, qx, qy, qz);
+    const float xf = uv.x, yf = uv.y;
     const float x0 = floorf(xf), y0 = floorf(yf);
     if (!(x0 >= 0.f && x0 < Wl && y0 >= 0.f && y0 < Hl)) continue;      // the 2 x 2 footprint (x0 .. x0 + 1, y0 .. y0 + 1) lies inside
     const float cn = floorf(xf + 0.5f), rn = floorf(yf + 0.5f);          // x0 <= cn <= x0 + 1: inside too
     const size_t base = (size_t)v * hw;
-    const size_t pn = base + (size_t)(int)rn * k.W + (size_t)(int)cn;
+    const size_t pn = base + (size_t)(int)rn * cam.W + (size_t)(int)cn;
     const float d = depth[pn];
-    if (!(d >= 0.001f && d < k.zfar)) continue;
+    if (!depth_ok(d, k.zfar)) continue;
     if (mask && mask[pn] == 0) continue;
     if (!(fabsf(d - qz) <= k.depth_tol)) continue;
     // the camera centre in the object frame, from the same fp32 matrix
@@ -110,7 +105,7 @@ __global__ __launch_bounds__(TB_X *TB_Y) void texture_bake_kernel(const float *_
     const float last = k.top_n == 1 ? tw[0] : k.top_n == 2 ? tw[1] : k.top_n == 3 ? tw[2] : tw[3];      // (no indexed register array)
     if (!(cosang > last)) continue;                 // not among the best top_n: its sample would be dropped
     const float wx = xf - x0, wy = yf - y0;
-    const size_t a00 = (base + (size_t)(int)y0 * k.W + (size_t)(int)x0) * 3, a01 = a00 + (size_t)k.W * 3;
+    const size_t a00 = (base + (size_t)(int)y0 * cam.W + (size_t)(int)x0) * 3, a01 = a00 + (size_t)cam.W * 3;
     float smp[3];
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
@@ -199,22 +194,13 @@ extern "C" int fp_texture_bake(fp_ctx *ctx, const float *d_pos, int V, const int
   FP_REQUIRE(cfg->top_n >= 1 && cfg->top_n <= FP_TEXTURE_MAX_TOP_N, "fp_texture_bake: top_n %d (1 .. %d)", cfg->top_n, FP_TEXTURE_MAX_TOP_N);
   FP_REQUIRE(cfg->depth_tol >= 0.f && cfg->cos_min > 0.f && cfg->cos_min <= 1.f && cfg->zfar > 0.f,
              "fp_texture_bake: depth_tol %g (>= 0), cos_min %g (in (0, 1]), zfar %g (> 0)", (double)cfg->depth_tol, (double)cfg->cos_min, (double)cfg->zfar);
-  TexCfg k{T, c, g, F, V, cfg->top_n, H, W, n_views, (float)K[0], (float)K[4], (float)K[2], (float)K[5], cfg->zfar, cfg->depth_tol, cfg->cos_min};
+  TexCfg k{T, c, g, F, V, cfg->top_n, n_views, cfg->zfar, cfg->depth_tol, cfg->cos_min};
   FP_TRY(fp_check_camera("fp_texture_bake", K));
-  TexViews views;
-  memset(&views, 0, sizeof(views));
   FP_TRY(fp_check_view_matrices("fp_texture_bake", cam_in_ob, n_views));
-  for (int v = 0; v < n_views; ++v) {
-    const double *m = cam_in_ob + (size_t)v * 16;
-    for (int i = 0; i < 3; ++i) {
-      for (int a = 0; a < 3; ++a) views.v[v].r[i * 3 + a] = (float)m[a * 4 + i];
-      views.v[v].t[i] = (float)-((m[0 * 4 + i] * m[3] + m[1 * 4 + i] * m[7]) + m[2 * 4 + i] * m[11]);
-    }
-  }
   hipLaunchKernelGGL(texture_uv_kernel, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_uv, F, T, c, g);
   FP_CHECK_HIP(hipGetLastError());
   hipLaunchKernelGGL(texture_bake_kernel, dim3((unsigned)(T / TB_X), (unsigned)(T / TB_Y)), dim3(TB_X, TB_Y), 0, (hipStream_t)stream, d_pos, d_faces,
-                     d_vertex_colors, d_rgb, d_depth, d_mask, d_texture, d_used, k, views);
+                     d_vertex_colors, d_rgb, d_depth, d_mask, d_texture, d_used, k, pinhole_of(K, H, W), rigids_of(cam_in_ob, n_views, true));
   FP_CHECK_HIP(hipGetLastError());
   return FP_OK;
 }

@@ -6,7 +6,8 @@
 // Both big kernels move memory, they do not compute: one thread per sample point, the linear point index is the thread index, so the six
 // volume planes stream coalesced (i is fastest in memory and in the wave); the depth images are gathered through L2 - neighbouring points
 // project to neighbouring pixels.  The view matrices are kernel arguments: a view index is uniform in the wave, so they arrive as scalar
-// loads.  The views loop inside the thread: a call reads and writes the volume once however many views it gets.
+// loads.  The views loop inside the thread: a call reads and writes the volume once however many views it gets.  The camera, the
+// transforms and the projection (the ratio rule) are those of view_geom.h.
 //
 // Extraction: flag + count per point (7-bit edge mask, faces of the point's cube) -> exclusive scan of (vertices | faces << 32) as one
 // 64-bit word -> vertex write -> face write.  A vertex id is the scanned base of the owning point plus the rank of the edge slot in the
@@ -28,19 +29,6 @@ struct TsdfGrid {
   float ox, oy, oz, vs, trunc;
 };
 
-struct TsdfView {
-  float r[9], t[3];      // object -> camera
-};
-
-struct TsdfViews {
-  TsdfView v[FP_TSDF_MAX_VIEWS];
-};
-
-struct TsdfCam {
-  float fx, fy, cx, cy, zfar;
-  int H, W, n_views;
-};
-
 // corner code = dx | dy << 1 | dz << 2.  The far end of edge slot s, and the slot of a corner-code difference.
 __device__ __constant__ const int SLOT_CORNER[7] = {1, 2, 4, 3, 5, 6, 7};
 constexpr int HOST_SLOT_OF_CODE[8] = {-1, 0, 1, 3, 2, 4, 5, 6};
@@ -53,8 +41,8 @@ constexpr int HOST_TET_C2[6] = {3, 5, 3, 6, 5, 6};
 __global__ __launch_bounds__(TS_THREADS) void tsdf_integrate_kernel(TsdfGrid g, float *__restrict__ pT, float *__restrict__ pW,
                                                                     float *__restrict__ pR, float *__restrict__ pG, float *__restrict__ pB,
                                                                     float *__restrict__ pC, const float *__restrict__ depth,
-                                                                    const uint8_t *__restrict__ rgb, const uint8_t *__restrict__ mask, TsdfCam cam,
-                                                                    TsdfViews views) {
+                                                                    const uint8_t *__restrict__ rgb, const uint8_t *__restrict__ mask, Pinhole cam,
+                                                                    float zfar, int n_views, Rigids views) {      // object -> camera
   const int idx = blockIdx.x * TS_THREADS + threadIdx.x;
   if (idx >= g.n) return;
   const int i = idx % g.nx, j = (idx / g.nx) % g.ny, k = idx / (g.nx * g.ny);
@@ -65,18 +53,16 @@ __global__ __launch_bounds__(TS_THREADS) void tsdf_integrate_kernel(TsdfGrid g, 
   bool touched = false, touched_c = false;
   const float Wf = (float)cam.W, Hf = (float)cam.H;
   const size_t hw = (size_t)cam.H * cam.W;
-  for (int v = 0; v < cam.n_views; ++v) {
-    const TsdfView &m = views.v[v];
-    const float qz = ((m.r[6] * sx + m.r[7] * sy) + m.r[8] * sz) + m.t[2];
+  for (int v = 0; v < n_views; ++v) {
+    const Rigid &m = views.v[v];
+    const float qz = rigid_apply(m, 2, sx, sy, sz);
     if (!(qz >= 0.001f)) continue;
-    const float qx = ((m.r[0] * sx + m.r[1] * sy) + m.r[2] * sz) + m.t[0];
-    const float qy = ((m.r[3] * sx + m.r[4] * sy) + m.r[5] * sz) + m.t[1];
-    const float cf = floorf((cam.fx * (qx / qz) + cam.cx) + 0.5f);
-    const float rf = floorf((cam.fy * (qy / qz) + cam.cy) + 0.5f);
+    const float2 uv = project_ratio(cam, rigid_apply(m, 0, sx, sy, sz), rigid_apply(m, 1, sx, sy, sz), qz);
+    const float cf = floorf(uv.x + 0.5f), rf = floorf(uv.y + 0.5f);
     if (!(cf >= 0.f && cf < Wf && rf >= 0.f && rf < Hf)) continue;
     const size_t px = (size_t)v * hw + (size_t)(int)rf * cam.W + (size_t)(int)cf;       // 0 <= row < H, 0 <= col < W: inside view v
     const float d = depth[px];
-    if (!(d >= 0.001f && d < cam.zfar)) continue;
+    if (!depth_ok(d, zfar)) continue;
     if (mask && mask[px] == 0) continue;
     const float sdf = d - qz;
     if (sdf < -g.trunc) continue;
@@ -394,23 +380,14 @@ extern "C" int fp_tsdf_integrate(fp_ctx *ctx, fp_tsdf *vol, const float *d_depth
   FP_REQUIRE(n_views >= 0 && n_views <= FP_TSDF_MAX_VIEWS, "fp_tsdf_integrate: n_views %d (0 .. %d)", n_views, FP_TSDF_MAX_VIEWS);
   FP_REQUIRE(H >= 1 && W >= 1, "fp_tsdf_integrate: H %d, W %d", H, W);
   FP_REQUIRE(zfar > 0.f, "fp_tsdf_integrate: zfar %g (> 0)", (double)zfar);
-  TsdfCam cam{(float)K[0], (float)K[4], (float)K[2], (float)K[5], zfar, H, W, n_views};
   FP_TRY(fp_check_camera("fp_tsdf_integrate", K));
   if (n_views == 0) return FP_OK;
-  TsdfViews views;
-  memset(&views, 0, sizeof(views));
   FP_TRY(fp_check_view_matrices("fp_tsdf_integrate", cam_in_ob, n_views));
-  for (int v = 0; v < n_views; ++v) {
-    const double *m = cam_in_ob + (size_t)v * 16;
-    for (int i = 0; i < 3; ++i) {
-      for (int a = 0; a < 3; ++a) views.v[v].r[i * 3 + a] = (float)m[a * 4 + i];
-      views.v[v].t[i] = (float)-((m[0 * 4 + i] * m[3] + m[1 * 4 + i] * m[7]) + m[2 * 4 + i] * m[11]);
-    }
-  }
   ++vol->generation;
   const TsdfGrid &g = vol->g;
   hipLaunchKernelGGL(tsdf_integrate_kernel, dim3((unsigned)((g.n + TS_THREADS - 1) / TS_THREADS)), dim3(TS_THREADS), 0, (hipStream_t)stream, g,
-                     vol->plane[0], vol->plane[1], vol->plane[2], vol->plane[3], vol->plane[4], vol->plane[5], d_depth, d_rgb, d_mask, cam, views);
+                     vol->plane[0], vol->plane[1], vol->plane[2], vol->plane[3], vol->plane[4], vol->plane[5], d_depth, d_rgb, d_mask, pinhole_of(K, H, W),
+                     zfar, n_views, rigids_of(cam_in_ob, n_views, true));
   FP_CHECK_HIP(hipGetLastError());
   return FP_OK;
 }
@@ -472,58 +449,46 @@ extern "C" int fp_tsdf_read_plane(fp_ctx *ctx, const fp_tsdf *vol, int plane, fl
 }
 
 // ---- frame-to-model alignment: one Gauss-Newton linearisation of every view against the volume (fp_tsdf_align) -----------------------
-// A workgroup owns (view, a tile of AL_TILE pixels); the view is uniform in the workgroup, so its matrix arrives as scalar loads.  A lane
-// takes AL_PIX pixels, TS_THREADS apart (the depth reads coalesce), in three passes over them: depth and mask, then the cell and the 16
-// gathers of each pixel (tsdf and weight of the 8 corners) - nothing in this pass depends on a gathered value, so all AL_PIX x 16 loads
-// are in flight together - then the arithmetic.  The row, the 29 sums in double and their way through the wave, LDS and the slab to
-// gn_fold_kernel are those of gn_sums.h, where the summation order is stated.  No atomics: a view's sums depend on nothing but its own
-// pixels.
+// One of the three aligners of gn_sums.h, which holds what they share: the tile, the three passes, the twist row, the 29 sums in double
+// and their way to gn_fold_kernel; the camera and the transforms are those of view_geom.h.  A workgroup owns (view, a tile of GN_TILE
+// pixels); the view is uniform in the workgroup, so its matrix arrives as scalar loads.  Pass one reads depth and mask (the reads
+// coalesce); pass two finds the cell and gathers tsdf and weight of its 8 corners, all GN_PIX x 16 loads in flight together; pass three
+// is the arithmetic.  No atomics: a view's sums depend on nothing but its own pixels.
 namespace {
 
-constexpr int AL_PIX = 4;
-constexpr int AL_TILE = TS_THREADS * AL_PIX;
-
-struct AlignView {
-  float r[9], t[3];      // camera -> object
-};
-
-struct AlignViews {
-  AlignView v[FP_TSDF_MAX_VIEWS];
-};
-
-__global__ __launch_bounds__(TS_THREADS) void tsdf_align_kernel(TsdfGrid g, const float *__restrict__ pT, const float *__restrict__ pW,
-                                                                const float *__restrict__ depth, const uint8_t *__restrict__ mask, TsdfCam cam,
-                                                                float min_w, int n_tiles, AlignViews views, float *__restrict__ rows,
-                                                                double *__restrict__ slab) {
-  __shared__ double red[TS_THREADS / 64][GN_TERMS];
+__global__ __launch_bounds__(GN_THREADS) void tsdf_align_kernel(TsdfGrid g, const float *__restrict__ pT, const float *__restrict__ pW,
+                                                                const float *__restrict__ depth, const uint8_t *__restrict__ mask, Pinhole cam,
+                                                                float zfar, float min_w, int n_tiles, Rigids views,      // camera -> object
+                                                                float *__restrict__ rows, double *__restrict__ slab) {
+  __shared__ double red[GN_THREADS / 64][GN_TERMS];
   const int tid = threadIdx.x;
   const int tile = blockIdx.x % n_tiles, v = blockIdx.x / n_tiles;
-  const AlignView &m = views.v[v];
+  const Rigid &m = views.v[v];
   const long long hw = (long long)cam.H * cam.W;
   const size_t view0 = (size_t)v * (size_t)hw;
   const int sxy = g.nx * g.ny;
 
   // pass 1: depth and mask
-  float d[AL_PIX];
-  bool ok[AL_PIX];
-  long long pix[AL_PIX];
+  float d[GN_PIX];
+  bool ok[GN_PIX];
+  long long pix[GN_PIX];
 #pragma unroll
-  for (int q = 0; q < AL_PIX; ++q) {
-    pix[q] = (long long)tile * AL_TILE + q * TS_THREADS + tid;
+  for (int q = 0; q < GN_PIX; ++q) {
+    pix[q] = (long long)tile * GN_TILE + q * GN_THREADS + tid;
     const bool in = pix[q] < hw;                                   // the last tile of a view is ragged
     d[q] = in ? depth[view0 + (size_t)pix[q]] : 0.f;
-    ok[q] = d[q] >= 0.001f && d[q] < cam.zfar;
+    ok[q] = depth_ok(d[q], zfar);
     if (mask) ok[q] = ok[q] && (in ? mask[view0 + (size_t)pix[q]] : (uint8_t)0) != 0;
   }
 
   // pass 2: the point in the object frame, its cell, the 16 gathers
-  float x[AL_PIX][3], f[AL_PIX][3], Tc[AL_PIX][8], Wc[AL_PIX][8];
+  float x[GN_PIX][3], f[GN_PIX][3], Tc[GN_PIX][8], Wc[GN_PIX][8];
 #pragma unroll
-  for (int q = 0; q < AL_PIX; ++q) {
+  for (int q = 0; q < GN_PIX; ++q) {
     const int row = (int)(pix[q] / cam.W), col = (int)(pix[q] - (long long)row * cam.W);
-    const float px = (((float)col - cam.cx) / cam.fx) * d[q], py = (((float)row - cam.cy) / cam.fy) * d[q], pz = d[q];
+    const float3 p = pinhole_point(cam, (float)col, (float)row, d[q]);
 #pragma unroll
-    for (int a = 0; a < 3; ++a) x[q][a] = ((m.r[a * 3] * px + m.r[a * 3 + 1] * py) + m.r[a * 3 + 2] * pz) + m.t[a];
+    for (int a = 0; a < 3; ++a) x[q][a] = rigid_apply(m, a, p.x, p.y, p.z);
     const float gx = (x[q][0] - g.ox) / g.vs, gy = (x[q][1] - g.oy) / g.vs, gz = (x[q][2] - g.oz) / g.vs;
     const float fi = floorf(gx), fj = floorf(gy), fk = floorf(gz);
     f[q][0] = gx - fi, f[q][1] = gy - fj, f[q][2] = gz - fk;
@@ -544,7 +509,7 @@ __global__ __launch_bounds__(TS_THREADS) void tsdf_align_kernel(TsdfGrid g, cons
   for (int e = 0; e < GN_TERMS; ++e) acc[e] = 0.0;
   const float gscale = g.trunc / g.vs;
 #pragma unroll
-  for (int q = 0; q < AL_PIX; ++q) {
+  for (int q = 0; q < GN_PIX; ++q) {
     const float *T = Tc[q];
     const float u = f[q][0], w = f[q][1], z = f[q][2];
     bool valid = ok[q];
@@ -559,9 +524,8 @@ __global__ __launch_bounds__(TS_THREADS) void tsdf_align_kernel(TsdfGrid g, cons
     valid = valid && fabsf(Ti) < 1.f;
     const float h0 = d00 + (d10 - d00) * w, h1 = d01 + (d11 - d01) * w;
     const float Gx = (h0 + (h1 - h0) * z) * gscale, Gy = (e0 + (e1 - e0) * z) * gscale, Gz = dz * gscale;
-    const float X = x[q][0], Y = x[q][1], Z = x[q][2];
-    float J[6] = {Gx, Gy, Gz, Y * Gz - Z * Gy, Z * Gx - X * Gz, X * Gy - Y * Gx};
-    float r = Ti * g.trunc;
+    float J[6], r = Ti * g.trunc;
+    gn_twist_row(J, Gx, Gy, Gz, x[q][0], x[q][1], x[q][2]);
     gn_mask(J, r, valid);
     if (rows && pix[q] < hw) gn_store_row((float4 *)(rows + (view0 + (size_t)pix[q]) * 8), J, r, valid);
     gn_accumulate(acc, J, r, valid);
@@ -583,19 +547,9 @@ extern "C" int fp_tsdf_align(fp_ctx *ctx, const fp_tsdf *vol, const float *d_dep
   FP_REQUIRE(H >= 1 && W >= 1, "fp_tsdf_align: H %d, W %d", H, W);
   FP_REQUIRE(zfar > 0.f, "fp_tsdf_align: zfar %g (> 0)", (double)zfar);
   FP_REQUIRE(min_weight > 0.f, "fp_tsdf_align: min_weight %g (> 0)", (double)min_weight);
-  TsdfCam cam{(float)K[0], (float)K[4], (float)K[2], (float)K[5], zfar, H, W, n_views};
   FP_TRY(fp_check_camera("fp_tsdf_align", K));
-  AlignViews views;
-  memset(&views, 0, sizeof(views));
   FP_TRY(fp_check_view_matrices("fp_tsdf_align", cam_in_ob, n_views));
-  for (int v = 0; v < n_views; ++v) {
-    const double *m = cam_in_ob + (size_t)v * 16;
-    for (int a = 0; a < 3; ++a) {
-      for (int i = 0; i < 3; ++i) views.v[v].r[a * 3 + i] = (float)m[a * 4 + i];
-      views.v[v].t[a] = (float)m[a * 4 + 3];
-    }
-  }
-  const long long n_tiles = ((long long)H * W + AL_TILE - 1) / AL_TILE;
+  const long long n_tiles = ((long long)H * W + GN_TILE - 1) / GN_TILE;
   FP_REQUIRE(n_tiles * FP_TSDF_MAX_VIEWS <= 0x7fffffff, "fp_tsdf_align: %d x %d pixels are too many for one launch", H, W);
   FP_REQUIRE(ctx->device == vol->device, "fp_tsdf_align: the volume lives on device %d, the context on %d", vol->device, ctx->device);
   if (n_views == 0) return FP_OK;
@@ -608,14 +562,10 @@ extern "C" int fp_tsdf_align(fp_ctx *ctx, const fp_tsdf *vol, const float *d_dep
   double *sums = (double *)ctx->arena.take(sums_bytes);
   FP_REQUIRE(slab && sums, "fp_tsdf_align: arena exhausted");
   const TsdfGrid &g = vol->g;
-  hipLaunchKernelGGL(tsdf_align_kernel, dim3((unsigned)(n_tiles * n_views)), dim3(TS_THREADS), 0, s, g, (const float *)vol->plane[0],
-                     (const float *)vol->plane[1], d_depth, d_mask, cam, min_weight, (int)n_tiles, views, d_rows, slab);
+  hipLaunchKernelGGL(tsdf_align_kernel, dim3((unsigned)(n_tiles * n_views)), dim3(GN_THREADS), 0, s, g, (const float *)vol->plane[0],
+                     (const float *)vol->plane[1], d_depth, d_mask, pinhole_of(K, H, W), zfar, min_weight, (int)n_tiles,
+                     rigids_of(cam_in_ob, n_views, false), d_rows, slab);
   FP_CHECK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(gn_fold_kernel<FP_TSDF_ALIGN_TERMS>, dim3((unsigned)((n_views * FP_TSDF_ALIGN_TERMS + 63) / 64)), dim3(64), 0, s,
-                     (const double *)slab, n_views, (int)n_tiles, sums);
-  FP_CHECK_HIP(hipGetLastError());
-  // the slab and the sums go back to the arena when this returns: the stream has been synchronised by then
-  FP_CHECK_HIP(hipMemcpyAsync(h_sums, sums, sums_bytes, hipMemcpyDeviceToHost, s));
-  FP_CHECK_HIP(hipStreamSynchronize(s));
-  return FP_OK;
+  // the slab and the sums go back to the arena when this returns: gn_fold_to_host has synchronised by then
+  return gn_fold_to_host<FP_TSDF_ALIGN_TERMS>(slab, n_views, (int)n_tiles, sums, h_sums, s);
 }

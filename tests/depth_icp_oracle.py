@@ -314,12 +314,13 @@ def mean_mm(poses, truth, views):
   return float(np.mean([A.displacement(poses[v], truth[v]) for v in views])) * 1e3
 
 
-def row_case(H=48, W=64, focal=130.0):
+def row_case(H=48, W=64, focal=130.0, K=None):
   """5 views of W x H of the three spheres on an arc, 20 degrees apart in azimuth at elevations of 10, -5, 15, 0 and -10 degrees (so
   that neighbours see much of the same surface), masks that cut a part of every view, poses perturbed by a seeded 3 mm / 1 degree, and
   a sixth entry: view 4's depth map again at a pose pushed 0.41 m along its optical axis, into the scene - its partners' points lie
-  partly behind it and partly outside its image.  Pairs in both directions.  Returns (K, truth, depths, masks, query, pairs)."""
-  K = np.array([[focal, 0, W / 2 - 0.5], [0, focal, H / 2 - 0.5], [0, 0, 1.0]])
+  partly behind it and partly outside its image.  Pairs in both directions.  K, when given, replaces the centred camera of `focal`.
+  Returns (K, truth, depths, masks, query, pairs)."""
+  K = np.array([[focal, 0, W / 2 - 0.5], [0, focal, H / 2 - 0.5], [0, 0, 1.0]]) if K is None else K
   az, el = np.deg2rad([0.0, 20.0, 40.0, 60.0, 80.0]), np.deg2rad([10.0, -5.0, 15.0, 0.0, -10.0])
   eyes = 0.4 * np.stack([np.cos(el) * np.cos(az), np.cos(el) * np.sin(az), np.sin(el)], 1)
   truth = np.stack([O.look_at(e) for e in eyes])
@@ -335,11 +336,11 @@ def row_case(H=48, W=64, focal=130.0):
   return K, truth, depths, masks, query, pairs
 
 
-def tiny_case(H=5, W=7, focal=130.0):
+def tiny_case(H=5, W=7, focal=130.0, K=None):
   """6 views of W x H (35 pixels: less than one wave of a tile) of the middle of the scene, all within a seeded 1 mm / 0.3 degrees of
   view 0 of the row case, so that the few pixels of a view land inside its partner; no mask cuts, the queries another 0.3 mm / 0.1
-  degrees off, the pairs of the row case.  Returns what row_case returns."""
-  K = np.array([[focal, 0, W / 2 - 0.5], [0, focal, H / 2 - 0.5], [0, 0, 1.0]])
+  degrees off, the pairs of the row case.  K as in row_case.  Returns what row_case returns."""
+  K = np.array([[focal, 0, W / 2 - 0.5], [0, focal, H / 2 - 0.5], [0, 0, 1.0]]) if K is None else K
   rs = np.random.RandomState(5)
   first = O.look_at(0.4 * np.array([np.cos(np.deg2rad(10.0)), 0.0, np.sin(np.deg2rad(10.0))]))
   truth = np.stack([first] + [A.perturb(first, 0.001, 0.3, rs) for _ in range(5)])

@@ -224,9 +224,9 @@ def row_case(*size):
   return K, truth, depths, masks, query, pairs, textured_rgbs(depths, K, truth)
 
 
-def tiny_case():
+def tiny_case(**kw):
   """depth_icp_oracle.tiny_case() with the texture"""
-  K, truth, depths, masks, query, pairs = D.tiny_case()
+  K, truth, depths, masks, query, pairs = D.tiny_case(**kw)
   return K, truth, depths, masks, query, pairs, textured_rgbs(depths, K, truth)
 
 

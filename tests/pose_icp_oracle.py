@@ -263,13 +263,13 @@ def frame_camera(H, W, focal, shift=0.0):
   return np.array([[focal, 0, W / 2 - 0.5 + shift * W], [0, focal, H / 2 - 0.5], [0, 0, 1.0]])
 
 
-def row_case(n=7, H=48, W=64, h=40, w=41, seed=6):
+def row_case(n=7, H=48, W=64, h=40, w=41, seed=6, K=None):
   """n poses of the spheres against ONE observed frame of H x W: the spheres at `truth`, seen off-centre so that the frame's right border
   cuts them.  Poses 0 .. n-1 are `truth` perturbed by 4 mm / 1.5 degrees (seeded), rendered analytically into maps of h x w through a
   camera that zooms on the object as a crop does (several map pixels land on one frame pixel) - except that pose 1's map is all
-  background, pose 2 is pushed wholly outside the frame and pose 4 (when n > 4) holds a NaN and has NaN maps.
-  Returns dict(K, depth, normals, poses (n,4,4) float32, xyz, normal, truth)."""
-  K = frame_camera(H, W, 1.35 * W, shift=0.42)
+  background, pose 2 is pushed wholly outside the frame and pose 4 (when n > 4) holds a NaN and has NaN maps.  K, when given, replaces
+  the frame's camera.  Returns dict(K, depth, normals, poses (n,4,4) float32, xyz, normal, truth)."""
+  K = frame_camera(H, W, 1.35 * W, shift=0.42) if K is None else K
   truth = object_poses(3)[1]
   depth, nrm4 = sphere_frame(truth, K, H, W)
   rs = np.random.RandomState(seed)

@@ -124,7 +124,8 @@ def test_sums_are_within_the_bound_of_any_summation_order(oracle_step, device_st
   print(f'largest |sum - fsum| / bound: {worst:.3e}')
 
 
-@pytest.mark.parametrize('make', [lambda: D.row_case(96, 100, 200.0), D.tiny_case, D.row_case], ids=['96x100', '5x7', 'masked 48x64'])
+@pytest.mark.parametrize('make', [lambda: D.row_case(96, 100, 200.0), D.tiny_case, D.row_case, lambda: D.tiny_case(K=O.skew_camera(5, 7, 130.0))],
+                         ids=['96x100', '5x7', 'masked 48x64', '5x7 fx != fy'])
 def test_sums_have_the_bits_of_the_stated_order(make):
   """The device's sums against tests/gn_sums_oracle.py (the order stated in csrc/gn_sums.h) applied to the device's own rows, bit for
   bit.  96 x 100: 10 tiles - the fold's body of eight and a remainder of two - and a last tile of 384 pixels; 5 x 7: one tile of which
@@ -140,6 +141,24 @@ def test_sums_have_the_bits_of_the_stated_order(make):
   print(f'{rows.shape[1:3]}: valid per pair {sums[:, 28]}; differing words {(sums.view(np.uint64) != want.view(np.uint64)).sum()} of {want.size}')
   assert sums[:, 28].sum() > 0
   assert np.array_equal(sums.view(np.uint64), want.view(np.uint64))
+
+
+def test_normals_and_rows_under_a_camera_with_fx_not_fy():
+  """The 5 x 7 case through tsdf_oracle.skew_camera (fy = 1.25 fx, cx and cy off the middle by different amounts): a kernel that takes
+  fx for fy or cx for cy anywhere - the rays of the normals, the back-projections, the projection - differs from the restatement.
+  Every pair has valid pixels."""
+  from foundationpose_amd import reconstruct as R
+  c = dict(zip(('K', 'truth', 'depths', 'masks', 'query', 'pairs'), D.tiny_case(K=O.skew_camera(5, 7, 130.0))))
+  assert c['K'][0, 0] != c['K'][1, 1] and c['K'][0, 2] - 3.0 != c['K'][1, 2] - 2.0
+  nrm = np.stack([D.normals(c['depths'][v], c['K'], c['masks'][v]) for v in range(6)])
+  want = np.stack([D.pair_rows(c['depths'], nrm, c['K'], c['query'], s, t, *D.ROW_GATE) for s, t in c['pairs']])
+  print(f'valid per pair {[int(w[..., 7].sum()) for w in want]}')
+  assert all(w[..., 7].sum() > 0 for w in want)
+  dn = R.depth_normals(c['depths'], c['K'], c['masks'])
+  assert _same_bits(dn.cpu().numpy(), nrm)
+  sums, got = R.align_pairs_step(torch.as_tensor(c['depths'], device=dn.device), dn, c['K'], c['query'], c['pairs'], *D.ROW_GATE, rows=True)
+  assert _same_bits(got.cpu().numpy(), want)
+  assert np.array_equal(sums[:, 28], want[..., 7].reshape(len(want), -1).sum(1))
 
 
 def test_a_pair_does_not_depend_on_its_batch(case, device_step):

@@ -142,7 +142,8 @@ def test_photometric_sums_are_within_the_bound_of_any_summation_order(oracle_ste
   assert (device_step[3][:10, 57] >= 60).all()
 
 
-@pytest.mark.parametrize('make', [lambda: P.row_case(96, 100, 200.0), P.tiny_case, P.row_case], ids=['96x100', '5x7', 'masked 48x64'])
+@pytest.mark.parametrize('make', [lambda: P.row_case(96, 100, 200.0), P.tiny_case, P.row_case, lambda: P.tiny_case(K=O.skew_camera(5, 7, 130.0))],
+                         ids=['96x100', '5x7', 'masked 48x64', '5x7 fx != fy'])
 def test_sums_have_the_bits_of_the_stated_order(make):
   """All 58 of the device's sums against tests/gn_sums_oracle.py (the order stated in csrc/gn_sums.h) applied to the device's own
   rows, floats 0 .. 7 for terms 0 .. 28 and floats 8 .. 15 for terms 29 .. 57, bit for bit.  The shapes of the same test of
@@ -161,6 +162,27 @@ def test_sums_have_the_bits_of_the_stated_order(make):
         f'{(sums.view(np.uint64) != want.view(np.uint64)).sum()} of {want.size}')
   assert sums[:, 28].sum() > 0 and sums[:, 57].sum() > 0
   assert sums.shape == (len(c['pairs']), 58) and np.array_equal(sums.view(np.uint64), want.view(np.uint64))
+
+
+def test_rows_under_a_camera_with_fx_not_fy():
+  """The 5 x 7 case through tsdf_oracle.skew_camera (fy = 1.25 fx, cx and cy off the middle by different amounts): the photometric row
+  takes fx and fy themselves (the image gradient through the projection), the geometric one the rays and the projection.  Every pair has
+  geometric and photometric rows."""
+  from foundationpose_amd import reconstruct as R
+  c = dict(zip(('K', 'truth', 'depths', 'masks', 'query', 'pairs', 'rgbs'), P.tiny_case(K=O.skew_camera(5, 7, 130.0))))
+  nrm = np.stack([D.normals(c['depths'][v], c['K'], c['masks'][v]) for v in range(6)])
+  inten = np.stack(P.row_intensity(c['depths'], c['masks'], c['rgbs'], c['K']))
+  want = np.stack([P.pair_rows(c['depths'], nrm, inten, c['K'], c['query'], s, t, *D.ROW_GATE, P.ROW_I_MAX) for s, t in c['pairs']])
+  print(f'rows per pair: geometric {[int(w[..., 7].sum()) for w in want]}, photometric {[int(w[..., 15].sum()) for w in want]}')
+  assert all(w[..., 7].sum() > 0 and w[..., 15].sum() > 0 for w in want)
+  dn = R.depth_normals(c['depths'], c['K'], c['masks'])
+  di = R.view_intensity(c['rgbs'], R.depth_normals(c['depths'], c['K'], c['masks'], max_jump=P.ROW_INTENSITY_MAX_JUMP))
+  assert _same_bits(di.cpu().numpy(), inten)
+  sums, got = R.align_pairs_step(torch.as_tensor(c['depths'], device=dn.device), dn, c['K'], c['query'], c['pairs'], *D.ROW_GATE, rows=True,
+                                 intensity=di, i_max=P.ROW_I_MAX)
+  assert _same_bits(got.cpu().numpy(), want)
+  assert np.array_equal(sums[:, 28], want[..., 7].reshape(len(want), -1).sum(1))
+  assert np.array_equal(sums[:, 57], want[..., 15].reshape(len(want), -1).sum(1))
 
 
 def test_a_pair_does_not_depend_on_its_batch(case, device_step):

@@ -48,6 +48,27 @@ def test_rows_counts_and_sums_have_the_restatements_bits(size, frame, N):
       assert not bits(rows[i]).any() and not bits(sums[i]).any()
 
 
+def test_rows_counts_and_sums_under_a_camera_with_fx_not_fy():
+  """Maps of 5 x 7 against a frame of 30 x 40 seen through a camera with fy = 1.25 fx and cx, cy off the middle by different amounts (the
+  row case's own focal length and shift, so that the spheres stay in the frame): a kernel that takes fx for fy or cx for cy in the
+  projection or the back-projection differs from the restatement.  Poses 0 and 3 - those of the row case that see the spheres - both
+  have valid pixels."""
+  from foundationpose_amd import Utils as U
+  from tests import tsdf_oracle as O
+  K = O.skew_camera(30, 40, 1.35 * 40)
+  K[0, 2] += 0.42 * 40
+  c = P.row_case(n=4, H=30, W=40, h=5, w=7, K=K)
+  keep = [0, 3]
+  want = [P.rows(c['xyz'][i], c['normal'][i], c['depth'], c['normals'], c['poses'][i], K, *P.ROW_GATE) for i in keep]
+  print(f'valid per pose {[int(w[0][..., 7].sum()) for w in want]}, counts {[w[1] for w in want]}')
+  assert all(w[0][..., 7].sum() > 0 for w in want)
+  sums, counts, rows = U.align_poses_step(c['xyz'][keep], c['normal'][keep], c['depth'], c['normals'], c['poses'][keep], K, *P.ROW_GATE, rows=True)
+  rows = rows.cpu().numpy()
+  for k, (want_rows, want_counts) in enumerate(want):
+    assert np.array_equal(bits(rows[k]), bits(want_rows)) and tuple(counts[k]) == want_counts
+    assert np.array_equal(bits(sums[k]), bits(P.device_sums(want_rows))) and sums[k, 28] == want_rows[..., 7].sum()
+
+
 def test_a_pose_does_not_depend_on_its_batch_and_the_device_form_has_the_same_bits():
   from foundationpose_amd import Utils as U
   c = P.row_case(n=7)

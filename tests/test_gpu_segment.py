@@ -113,6 +113,21 @@ def test_plane_score_collinear_pixels_and_a_map_without_a_valid_pixel():
   assert best[0] == -1 and (counts == 0).all()
 
 
+def test_plane_score_under_a_camera_with_fx_not_fy():
+  """31 x 33 random depths through a camera with fy = 1.25 fx and cx, cy off the middle by different amounts: a kernel that takes fx for
+  fy or cx for cy in the back-projection gives other planes and other counts than the oracle."""
+  from foundationpose_amd.segment import plane_score
+  H, W = 31, 33
+  K = np.array([[50.0, 0, W / 2 - 0.5 + 0.37], [0, 62.5, H / 2 - 0.5 - 0.61], [0, 0, 1]])
+  depth = random_depth(H, W, 77)
+  trip = np.random.RandomState(78).randint(0, H * W, (1024, 3)).astype(np.int32)
+  want_p, want_c, want_b = O.plane_score(depth, K, trip, 0.05)
+  print(f'largest count {want_c.max()}, hypotheses with a plane {(want_p != 0).any(1).sum()}')
+  assert want_c.max() > 3 and want_b >= 0
+  planes, counts, best = plane_score(depth[None], K, trip, 0.05)
+  assert np.array_equal(counts[0], want_c) and np.array_equal(bits(planes[0]), bits(want_p)) and best[0] == want_b
+
+
 # ---- 2. fp_plane_moments -------------------------------------------------------------------------------------------------------------
 def test_plane_moments_bit_equal_alone_and_in_a_batch(tables):
   from foundationpose_amd.segment import plane_moments

@@ -55,10 +55,9 @@ def _mesh(n_faces):
   return v.astype(np.float32), f, colours
 
 
-@functools.lru_cache(maxsize=None)
-def _views():
+def _render_views(H, W, K, least):
   """Five views of the vertex-coloured 80-face sphere rendered by the rasteriser; depths rounded to millimetres (what a 16-bit PNG holds);
-  masks: the object, with the left half of view 1 and the lower two thirds of view 3 cut away."""
+  masks: the object, with the left half of view 1 and the lower two thirds of view 3 cut away.  More than `least` object pixels a view."""
   from foundationpose_amd import Utils as U
   from foundationpose_amd import synthetic as S
   v, f, colours = _mesh(80)
@@ -72,8 +71,13 @@ def _views():
   masks = (mm > 0).astype(np.uint8)
   masks[1, :, :W // 2] = 0
   masks[3, H // 3:, :] = 0
-  assert all((d > 0).sum() > 500 for d in depths)
+  assert all((d > 0).sum() > least for d in depths)
   return dict(rgbs=rgbs, depths=depths, masks=masks, K=K, cam_in_obs=poses)
+
+
+@functools.lru_cache(maxsize=None)
+def _views():
+  return _render_views(H, W, K, 500)
 
 
 @functools.lru_cache(maxsize=None)
@@ -116,6 +120,22 @@ def test_bits_equal_the_restatement(n_faces, T, top_n, with_masks):
   assert np.array_equal(got[0], want[0])
   for a, b in zip(got, again):
     assert a.tobytes() == b.tobytes()
+
+
+def test_bits_under_a_camera_with_fx_not_fy():
+  """Views of 31 x 33 pixels through tsdf_oracle.skew_camera (fy = 1.25 fx, cx and cy off the middle by different amounts): a kernel that
+  takes fx for fy or cx for cy in the projection samples other pixels than the restatement.  Views feed most texels."""
+  from foundationpose_amd import Utils as U
+  Ks = TO.skew_camera(31, 33, 60.0)
+  vw = _render_views(31, 33, Ks, 100)
+  v, f, colours = _mesh(80)
+  want = O.bake(v, f, colours, vw['rgbs'], vw['depths'], vw['masks'], Ks, vw['cam_in_obs'], 64, top_n=4)
+  own = want[2] >= 0
+  print(f'used histogram {np.bincount(want[2][own], minlength=5).tolist()}')
+  assert (want[2][own] >= 1).mean() > 0.5
+  tex, uv, used = U.bake_texture_arrays(v, f, vw['rgbs'], vw['depths'], Ks, vw['cam_in_obs'], 64, colors=colours, masks=vw['masks'], top_n=4)
+  assert np.array_equal(used.cpu().numpy(), want[2]) and np.array_equal(tex.cpu().numpy(), want[0])
+  assert np.array_equal(uv.cpu().numpy().view(np.uint32), want[1].view(np.uint32))
 
 
 def test_masks_matter():

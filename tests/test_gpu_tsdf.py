@@ -74,6 +74,31 @@ def test_planes_are_bit_equal_to_the_restatement(device_volume, oracle):
   assert torch.equal(device_volume.tsdf, device_volume.plane('tsdf')) and device_volume.weight.shape == DIMS[::-1]
 
 
+def test_planes_under_a_camera_with_fx_not_fy():
+  """Three of the views at 31 x 33 pixels through tsdf_oracle.skew_camera (fy = 1.25 fx, cx and cy off the middle by different amounts),
+  colours and masks included: a kernel that takes fx for fy or cx for cy in the projection differs from the restatement."""
+  from foundationpose_amd.reconstruct import TsdfVolume
+  h, w = 31, 33
+  Ks = O.skew_camera(h, w, 40.0)
+  poses = np.stack([O.look_at(e) for e in O.fibonacci_eyes(3, 0.4)])
+  depths = np.stack([O.sphere_depth(p, Ks, h, w, O.SPHERE_RADIUS) for p in poses])
+  depths[depths == 0] = 0.6
+  rs = np.random.RandomState(9)
+  rgbs = rs.randint(0, 256, (3, h, w, 3)).astype(np.uint8)
+  masks = np.ones((3, h, w), dtype=np.uint8)
+  masks[1, :, :w // 2] = 0
+  origin = -(np.array(DIMS) - 1) * VOXEL / 2 + np.array([0.0007, -0.0011, 0.0013])
+  want = O.Volume(origin, VOXEL, DIMS)
+  want.integrate(depths, Ks, poses, rgbs=rgbs, masks=masks, zfar=ZFAR)
+  print(f"weights {np.unique(want.planes['weight'], return_counts=True)}")
+  assert len(np.unique(want.planes['weight'])) >= 3 and (want.planes['color_weight'] > 0).any()
+  vol = TsdfVolume(origin, VOXEL, DIMS)
+  vol.integrate(depths, Ks, poses, rgbs=rgbs, masks=masks, zfar=ZFAR)
+  got = _planes(vol)
+  for p in O.PLANES:
+    assert _same_bits(got[p], want.planes[p]), p
+
+
 def test_one_call_is_five_calls_and_reset_repeats(device_volume, views):
   from foundationpose_amd.reconstruct import TsdfVolume
   want = _planes(device_volume)

@@ -21,7 +21,8 @@ ORIGIN = np.array([-0.004, -0.006, 0.004]) - (np.array(DIMS) - 1) * VOXEL / 2 + 
 
 
 def _case(H, W, focal):
-  K = np.array([[focal, 0, W / 2 - 0.5], [0, focal, H / 2 - 0.5], [0, 0, 1.0]])
+  """`focal`: the focal length of a centred camera, or a camera matrix"""
+  K = np.array([[focal, 0, W / 2 - 0.5], [0, focal, H / 2 - 0.5], [0, 0, 1.0]]) if np.ndim(focal) == 0 else focal
   poses = np.stack([O.look_at(e) for e in O.fibonacci_eyes(5, 0.4)])
   depths = np.stack([A.scene_depth(p, K, H, W) for p in poses])
   masks = (depths > 0).astype(np.uint8)
@@ -115,7 +116,10 @@ def test_sums_are_within_the_bound_of_any_summation_order(oracle_rows, device_st
   print(f'largest |sum - fsum| / bound: {worst:.3e}')
 
 
-@pytest.mark.parametrize('H,W,focal', [(96, 100, 200.0), (5, 7, 130.0), (48, 64, 130.0)])
+SKEW = O.skew_camera(5, 7, 130.0)      # fy = 1.25 fx, cx and cy off the middle by different amounts
+
+
+@pytest.mark.parametrize('H,W,focal', [(96, 100, 200.0), (5, 7, 130.0), (48, 64, 130.0), pytest.param(5, 7, SKEW, id='5-7-fx != fy')])
 def test_sums_have_the_bits_of_the_stated_order(H, W, focal, device_volumes):
   """The device's sums against tests/gn_sums_oracle.py (the order stated in csrc/gn_sums.h) applied to the device's own rows, bit for
   bit.  96 x 100: 10 tiles - the fold's body of eight and a remainder of two - and a last tile of 384 pixels; 5 x 7: one tile of which
@@ -128,6 +132,18 @@ def test_sums_have_the_bits_of_the_stated_order(H, W, focal, device_volumes):
   print(f'{H} x {W}: valid per view {sums[:, 28]}; differing words {(sums.view(np.uint64) != want.view(np.uint64)).sum()} of {want.size}')
   assert sums[:, 28].sum() > 0
   assert np.array_equal(sums.view(np.uint64), want.view(np.uint64))
+
+
+def test_rows_under_a_camera_with_fx_not_fy(oracle_volumes, device_volumes):
+  """5 x 7 pixels through SKEW, without masks (a mask of the case would cut all of so small a view): a kernel that takes fx for fy or
+  cx for cy in the back-projection differs from the restatement.  Every view has valid pixels."""
+  c = _case(5, 7, SKEW)
+  want = np.stack([A.rows(oracle_volumes[0], c['depths'][v], c['K'], c['query'][v], None) for v in range(5)])
+  print(f'valid per view {[int(w[..., 7].sum()) for w in want]}')
+  assert all(w[..., 7].sum() > 0 for w in want)
+  sums, got = device_volumes[0].align_step(c['depths'], c['K'], c['query'], rows=True)
+  assert _same_bits(got.cpu().numpy(), want)
+  assert np.array_equal(sums[:, 28], want[..., 7].reshape(5, -1).sum(1))
 
 
 def test_a_view_does_not_depend_on_its_batch(case, device_volumes, device_step):

@@ -215,6 +215,11 @@ def extract(planes, origin, vs, min_weight=1):
 
 
 # ---- analytic scenes and mesh conditions ------------------------------------------------------------------------------------------
+def skew_camera(H, W, fx):
+  """A camera that tells fx from fy and cx from cy: fy = 1.25 fx, the principal point off the middle of the image by (0.37, -0.61) pixels."""
+  return np.array([[fx, 0, W / 2 - 0.5 + 0.37], [0, 1.25 * fx, H / 2 - 0.5 - 0.61], [0, 0, 1.0]])
+
+
 def look_at(eye, target=(0, 0, 0), up=(0, 0, 1)):
   """camera-to-object pose (4,4) float64: z looks from eye to target, x right, y down"""
   eye, target = np.asarray(eye, dtype=np.float64), np.asarray(target, dtype=np.float64)
