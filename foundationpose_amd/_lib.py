@@ -152,6 +152,25 @@ class FpStereoDebug(Structure):
               ('d_dstar', c_void_p), ('d_dright', c_void_p)]
 
 
+FP_REMAP_COLOUR, FP_REMAP_DEPTH, FP_REMAP_MAX_SIDE = 0, 1, 16384             # fp_remap
+
+
+class FpRemapPlan(Structure):
+  """fp_remap_plan (include/foundationpose_amd.h)."""
+  _fields_ = [('k_new', c_float * 4), ('rot', c_float * 9), ('k_raw', c_float * 4), ('dist', c_float * 8), ('r2_max', c_float), ('src_h', c_int),
+              ('src_w', c_int), ('dst_h', c_int), ('dst_w', c_int)]
+
+
+class FpRemapOpts(Structure):
+  """fp_remap_opts."""
+  _fields_ = [('struct_size', ctypes.c_size_t), ('mode', c_int), ('channels', c_int), ('n_plans', c_int), ('zfar', c_float), ('plan', FpRemapPlan * 2)]
+
+
+class FpRemapDebug(Structure):
+  """fp_remap_debug: device pointers (or None) that receive the (u, v) map of fp_remap."""
+  _fields_ = [('struct_size', ctypes.c_size_t), ('d_map0', c_void_p), ('d_map1', c_void_p)]
+
+
 class FpObjectBatch(Structure):
   _fields_ = [('mesh', c_void_p), ('d_rgb', c_void_p), ('d_geom', c_void_p), ('H', c_int), ('W', c_int), ('K', c_void_p),
               ('mesh_diameter', c_double), ('n', c_int)]
@@ -224,6 +243,8 @@ _PROTOS = {
   'fp_depth_segment_write': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
   'fp_stereo_sgm': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, POINTER(FpStereoOpts), c_void_p, c_void_p, POINTER(FpStereoDebug),
                             c_void_p]),
+  'fp_remap': (c_int, [c_void_p, c_void_p, c_void_p, c_int, POINTER(FpRemapOpts), c_void_p, c_void_p, c_void_p, c_void_p, POINTER(FpRemapDebug),
+                       c_void_p]),
   'fp_texture_bake': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                               POINTER(FpTextureCfg), c_void_p, c_void_p, c_void_p, c_void_p]),
   'fp_point_mesh_distance': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -209,6 +209,10 @@ StereoLayout fp_stereo_layout(int n, int H, int W, int D, int channels);
 int fp_stereo_check(const void *ctx, const void *d_left, const void *d_right, int n, int H, int W, int channels, const fp_stereo_opts *opts,
                     const float *d_depth, const fp_stereo_debug *dbg, fp_stereo_opts *o);
 
+// rectify.hip: every check of a value of fp_remap, which needs no device.  scripts/rectify_host_check.cpp runs it under sanitizers.
+int fp_remap_check(const void *ctx, const void *d_src0, const void *d_src1, int n, const fp_remap_opts *opts, const void *d_dst0, const void *d_dst1,
+                   const fp_remap_debug *dbg);
+
 int fp_arena_ensure(fp_ctx *ctx, size_t bytes);
 size_t fp_arena_bytes_for(int n_hyp);     // whole refine/score pass (outer buffers + network)
 size_t fp_arena_inner_bytes(int n_hyp);   // network forward only

@@ -431,3 +431,50 @@ def load_stereo_baseline(path, scale=0.001):
     raise ValueError(f'{path}: not a sectioned calibration file (its first non-blank line does not start with "[")')
   return _calibration_value(path, _calibration_section(path, text, 'STEREO'), 'STEREO', 'Baseline') * float(scale)
 
+
+
+def _calibration_optional(path, body, section, key):
+  return _calibration_value(path, body, section, key) if re.search(r'^[ \t]*' + re.escape(key) + r'[ \t]*=', body, re.M) else 0.0
+
+
+def _rotation_of_vector(rvec):
+  """Rodrigues: the rotation by |rvec| radians about rvec, float64."""
+  rvec = np.asarray(rvec, dtype=np.float64)
+  theta = float(np.linalg.norm(rvec))
+  if theta == 0.0:
+    return np.eye(3)
+  k = rvec / theta
+  Kx = np.array([[0.0, -k[2], k[1]], [k[2], 0.0, -k[0]], [-k[1], k[0], 0.0]])
+  return np.eye(3) + np.sin(theta) * Kx + (1.0 - np.cos(theta)) * (Kx @ Kx)
+
+
+def load_stereo_calibration(path, left_section='LEFT_CAM_FHD1200', right_section=None, scale=0.001):
+  """Both cameras and their relative pose from a stereo camera's sectioned calibration file, as plain arrays: a dict with K1, K2 (3x3),
+  dist1, dist2 (k1 k2 p1 p2 k3 of each camera section, absent keys = 0), R (3x3) and T (3) in the convention of rectify.rectify_stereo,
+  x2 = R x1 + T, T in metres.  right_section defaults to left_section with LEFT replaced by RIGHT.
+  **The reading of the [STEREO] section is an ASSUMPTION.**  The reference reads fx, fy, cx, cy of the camera sections only
+  (src/file_processing.py:36-81) and never the [STEREO] keys, so their meaning cannot be taken from it.  Assumed here: the right camera's
+  centre lies at (Baseline, TY, TZ) * scale in the left camera's frame (scale 0.001: a file in millimetres), and its orientation in that
+  frame is the rotation vector (RX_<res>, CV_<res>, RZ_<res>) in radians, <res> being the resolution suffix of the section name
+  (FHD1200 for LEFT_CAM_FHD1200); absent keys are 0.  With that orientation Q and centre c: R = Q^T, T = -Q^T c.  Only arrays are
+  returned: a caller whose camera follows another convention builds R and T themselves from the same numbers."""
+  text = open(path).read()
+  if not _is_sectioned(text):
+    raise ValueError(f'{path}: not a sectioned calibration file (its first non-blank line does not start with "[")')
+  if right_section is None:
+    if 'LEFT' not in left_section:
+      raise ValueError(f'right_section must be given: "{left_section}" does not contain LEFT')
+    right_section = left_section.replace('LEFT', 'RIGHT')
+  out = {}
+  for i, section in ((1, left_section), (2, right_section)):
+    body = _calibration_section(path, text, section)
+    fx, fy, cx, cy = (_calibration_value(path, body, section, k) for k in ('fx', 'fy', 'cx', 'cy'))
+    out[f'K{i}'] = np.array([[fx, 0.0, cx], [0.0, fy, cy], [0.0, 0.0, 1.0]], dtype=np.float64)
+    out[f'dist{i}'] = np.array([_calibration_optional(path, body, section, k) for k in ('k1', 'k2', 'p1', 'p2', 'k3')], dtype=np.float64)
+  stereo = _calibration_section(path, text, 'STEREO')
+  res = left_section.rsplit('_', 1)[-1]
+  centre = np.array([_calibration_value(path, stereo, 'STEREO', 'Baseline'), _calibration_optional(path, stereo, 'STEREO', 'TY'),
+                     _calibration_optional(path, stereo, 'STEREO', 'TZ')]) * float(scale)
+  Q = _rotation_of_vector([_calibration_optional(path, stereo, 'STEREO', f'{k}_{res}') for k in ('RX', 'CV', 'RZ')])
+  out['R'], out['T'] = Q.T, -Q.T @ centre
+  return out

@@ -16,7 +16,8 @@ class PipelineData:
 
   def __init__(self, **kw):
     self.rgb = self.depth = self.mask = self.K = None
-    self.right = None         # the right image of a rectified stereo pair (StereoDepth), rgb being the left one
+    self.right = None         # the right image of a stereo pair (StereoRectify, StereoDepth), rgb being the left one
+    self.baseline = None      # metres, set by StereoRectify for a StereoDepth(baseline=None) behind it
     self.pose = None          # 4x4 ob_in_cam of the original (un-centred) mesh
     self.pose_6d = None       # (x, y, z, roll, pitch, yaw)
     self.errors = []
@@ -94,10 +95,11 @@ class StereoDepth(Processor):
   otherwise: the stage in front of FoundationPoseEstimator on a stereo camera whose vendor SDK is not there (the reference loads that
   SDK's depth, src/file_processing.py:99-138).  baseline in metres; K: the left camera's 3x3 matrix, `data.K` when that is set; **kw:
   the arguments of Utils.stereo_depth (max_disparity, p1, p2, paths, lr_max, min_disparity, subpixel, zfar).  Device tensors in give a
-  device tensor in `data.depth`, without a host copy.  The pair must already be rectified and undistorted."""
+  device tensor in `data.depth`, without a host copy.  The pair must already be rectified and undistorted: StereoRectify in front
+  does that for a raw pair, and with baseline=None the baseline it left in `data.baseline` is used."""
 
-  def __init__(self, baseline, K=None, **kw):
-    self.baseline = float(baseline)
+  def __init__(self, baseline=None, K=None, **kw):
+    self.baseline = None if baseline is None else float(baseline)
     self.K = None if K is None else np.asarray(K, dtype=np.float64)
     self._kw = kw
 
@@ -110,8 +112,45 @@ class StereoDepth(Processor):
     K = self.K if data.K is None else data.K
     if K is None:
       raise ValueError('StereoDepth: no camera matrix (K=... or data.K)')
+    baseline = self.baseline if self.baseline is not None else getattr(data, 'baseline', None)
+    if baseline is None:
+      raise ValueError('StereoDepth: no baseline (baseline=... or a StereoRectify in front)')
     from .stereo import stereo_depth
-    data.depth = stereo_depth(data.rgb, right, K, self.baseline, **self._kw)
+    data.depth = stereo_depth(data.rgb, right, K, baseline, **self._kw)
+    return data
+
+
+class StereoRectify(Processor):
+  """Replaces the RAW pair `data.rgb` (left) / `data.right` by the rectified, undistorted one and sets `data.K = rect.K_new` and
+  `data.baseline = rect.baseline`: the stage in front of StereoDepth on a raw stereo camera.  rect: rectify.rectify_stereo(...).  Leaves
+  `data` alone when `data.right` is missing (a frame that is no pair), the way StereoDepth leaves a frame with a depth alone.  One launch
+  for both images; device tensors in give device tensors, without a host copy."""
+
+  def __init__(self, rect):
+    self.rect = rect
+
+  def process(self, data):
+    if data.rgb is None or getattr(data, 'right', None) is None:
+      return data
+    from .rectify import rectify_pair
+    data.rgb, data.right = rectify_pair(data.rgb, data.right, self.rect)
+    data.K = self.rect.K_new.copy()
+    data.baseline = self.rect.baseline
+    return data
+
+
+class Undistort(Processor):
+  """Replaces `data.rgb` and `data.depth` of a camera with lens distortion by their undistorted versions (whichever of the two is there)
+  and sets `data.K = plan.K_new`: the stage in front of FoundationPoseEstimator on such an RGB-D stream.  plan: rectify.undistort_plan(...).
+  A mask in `data.mask` is NOT warped: make it on the undistorted frame."""
+
+  def __init__(self, plan, zfar=np.inf):
+    self.plan, self.zfar = plan, zfar
+
+  def process(self, data):
+    from .rectify import undistort_frame
+    data.rgb, data.depth = undistort_frame(data.rgb, data.depth, self.plan, zfar=self.zfar)
+    data.K = self.plan.K_new.copy()
     return data
 
 

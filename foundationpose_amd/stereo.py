@@ -6,8 +6,9 @@ include/foundationpose_amd.h and restated in numpy by tests/stereo_oracle.py).
 
 The reference reads a depth image that its camera vendor's SDK computed (src/file_processing.py:99-138); this is the library's own rule
 in that place, integer up to the winning disparity and therefore the same on every run and in any batch.  **The pair must already be
-rectified and undistorted; textureless and specular surfaces are not matched; the band x < d has no partner; one disparity step is
-z^2 / (fx b) of depth; P2 is constant.**
+rectified and undistorted - rectify.rectify_pair does that for a raw pair with a calibration, stereo_depth(..., rectify=rect) in one
+chain; textureless and specular surfaces are not matched; the band x < d has no partner; one disparity step is z^2 / (fx b) of depth;
+P2 is constant.**
 """
 import ctypes
 
@@ -101,23 +102,36 @@ def stereo_disparity(left, right, max_disparity=128, p1=8, p2=32, paths=0xFF, lr
   lr_max: the largest difference the left-right check accepts (negative: no check); min_disparity: smaller winners are invalid;
   subpixel: the parabola through the three sums around the winner.  return_debug: (disparity, stages) with the stages as numpy arrays of
   the leading n - census_left, census_right (uint64), cost (uint8), sum (uint16), dstar, dright (int32); this synchronises.
-  **Rectified, undistorted input only; textureless and specular surfaces are not matched; the band x < d has no partner.**"""
+  **Rectified, undistorted input only (rectify.rectify_pair makes one from a raw pair); textureless and specular surfaces are not
+  matched; the band x < d has no partner.**"""
   dev, l, r, channels, batch, on_device = _pair_on(left, right, device)
   disparity, _, stages = _sgm(dev, l, r, channels, max_disparity, p1, p2, paths, lr_max, min_disparity, subpixel, return_debug=return_debug)
   out = _finish(disparity, batch, on_device)
   return (out, _debug_numpy(stages)) if return_debug else out
 
 
-def stereo_depth(left, right, K, baseline, zfar=np.inf, **kw):
+def stereo_depth(left, right, K=None, baseline=None, zfar=np.inf, *, rectify=None, **kw):
   """Metric depth of a rectified pair: float32 metres, (H,W) or (n,H,W), 0 where there is none (no accepted match, or farther than
   zfar) - the depth image register, track_one, depth_prefilter and segment_on_plane take.  K: the 3x3 matrix of the (rectified) left
   camera, of which fx is used; baseline: the distance of the two cameras in metres; depth = (float)(fx baseline) / disparity.  **One
   disparity step is z^2 / (fx baseline) of depth: the error grows with the square of the distance.**  The other arguments are those of
-  stereo_disparity (return_debug gives (depth, stages)).  Numpy in gives numpy out, device tensors give a device tensor without a host copy."""
+  stereo_disparity (return_debug gives (depth, stages)).  Numpy in gives numpy out, device tensors give a device tensor without a host copy.
+  rectify: a rectify.StereoRectification (rectify_stereo) for a RAW pair - both images are first warped into its rectified cameras
+  (one fp_remap launch in front of the matching, on the same stream) and K, baseline default to rectify.K_new, rectify.baseline; the
+  depth then belongs to the rectified left camera rectify.K_new, size rectify.size_new.  Without it the pair must already be rectified
+  and undistorted, and K and baseline are required."""
   return_debug = bool(kw.pop('return_debug', False))
   device = kw.pop('device', 'cuda')
+  if rectify is not None:
+    K = rectify.K_new if K is None else K
+    baseline = rectify.baseline if baseline is None else baseline
+  if K is None or baseline is None:
+    raise ValueError('stereo_depth: K and baseline are required (or rectify=...)')
   Kh = np.asarray(K.detach().cpu() if torch.is_tensor(K) else K, dtype=np.float64).reshape(3, 3)
   dev, l, r, channels, batch, on_device = _pair_on(left, right, device)
+  if rectify is not None:
+    from .rectify import remap
+    (l, r), _, _ = remap([l, r], [rectify.left, rectify.right], 'colour')
   _, depth, stages = _sgm(dev, l, r, channels, fx=float(Kh[0, 0]), baseline=float(baseline), zfar=zfar, want_disparity=False, return_debug=return_debug, **kw)
   out = _finish(depth, batch, on_device)
   return (out, _debug_numpy(stages)) if return_debug else out

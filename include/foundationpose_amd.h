@@ -1031,6 +1031,72 @@ typedef struct fp_stereo_debug {
 int fp_stereo_sgm(fp_ctx *ctx, const uint8_t *d_left, const uint8_t *d_right, int n, int H, int W, int channels, const fp_stereo_opts *opts,
                   float *d_disparity, float *d_depth, const fp_stereo_debug *dbg, void *stream);
 
+/* ---- warping images and depth maps through a camera model: undistortion and stereo rectification (csrc/rectify.hip), the stage in
+ *      front of fp_stereo_sgm on a raw stereo pair and in front of every depth toolkit on a camera with lens distortion.  The reference
+ *      has nothing in this place (its camera vendor's SDK delivers rectified images); the rule is the library's own (DESIGN.md section
+ *      5), NOT OpenCV's remap, and tests/rectify_oracle.py restates all of it in numpy.  The plans are built on the host in float64
+ *      (foundationpose_amd/rectify.py) and rounded to fp32 once.  The map is computed per pixel, no map is read from memory.
+ *      A plan (fp_remap_plan) says for one image: k_new = fx, fy, cx, cy of the new (ideal pinhole) camera; rot = the rotation from the
+ *      new frame to the raw frame, row-major; k_raw = fx, fy, cx, cy of the raw camera; dist = k1 k2 p1 p2 k3 k4 k5 k6 (OpenCV's order);
+ *      r2_max (infinity: no limit); the size of the source (raw) and of the destination (new) image.
+ *      1 Map, per destination pixel (col, row), fp32, each operation rounded once, in this order and with these parentheses:
+ *          x = (col - cx_new) / fx_new, y = (row - cy_new) / fy_new                      (pinhole_ray_x / _y of csrc/view_geom.h)
+ *          X = (rot[0] x + rot[1] y) + rot[2], Y = (rot[3] x + rot[4] y) + rot[5], Z = (rot[6] x + rot[7] y) + rot[8]   (mat3_row, z = 1)
+ *          the pixel is invalid unless Z > 0;  xr = X / Z, yr = Y / Z;  r2 = xr xr + yr yr;  the pixel is invalid unless r2 < r2_max
+ *          radial = (1 + r2 (k1 + r2 (k2 + r2 k3))) / (1 + r2 (k4 + r2 (k5 + r2 k6)))
+ *          xy2 = 2 (xr yr)
+ *          xd = (xr radial + p1 xy2) + p2 (r2 + 2 (xr xr)),  yd = (yr radial + p1 (r2 + 2 (yr yr))) + p2 xy2
+ *          u = fx_raw xd + cx_raw,  v = fy_raw yd + cy_raw
+ *      2 Colour mode (FP_REMAP_COLOUR): uint8, channels 1 or 3, bilinear with 1/256-pixel weights, integer from here on.
+ *          fu = floor(u 256 + 0.5), fv = floor(v 256 + 0.5) in fp32; the pixel is valid when 0 <= fu <= 256 (W_src - 1) and
+ *          0 <= fv <= 256 (H_src - 1), decided in float, so that a NaN or a huge value never reaches a cast: exactly the pixels whose
+ *          taps of non-zero weight lie inside the source.  qu = (int)fu, u0 = qu >> 8, a = qu & 255, likewise qv, v0, b;
+ *          out = ((256-a)(256-b) p(v0,u0) + a (256-b) p(v0,u0+1) + (256-a) b p(v0+1,u0) + a b p(v0+1,u0+1) + 32768) >> 16 per
+ *          channel (a tap of weight 0 is not read outside the source).  Invalid pixels are 0 in every channel.  An identity plan
+ *          (rot = 1, k_new = k_raw, dist = 0, equal sizes) reproduces its input on every pixel.
+ *      3 Depth mode (FP_REMAP_DEPTH): float32 metres, channels = 1, the NEAREST source pixel cf = floor(u + 0.5), rf = floor(v + 0.5),
+ *          valid when 0 <= cf <= W_src - 1 and 0 <= rf <= H_src - 1, decided in float.  out = d / Z with d the source depth and Z of
+ *          step 1 (the depth along the new optical axis of the point at depth d along the raw one); 0 where the pixel is invalid or d
+ *          is not a depth (d >= 0.001 and d < zfar fails, a NaN too).  Depth is never blended across an edge; with rot = 1, Z is
+ *          exactly 1 and the depth is copied bit for bit.
+ *      Batching: n images of one source size and one destination size, n_plans = 1 or 2, image i uses plan i mod n_plans.  With
+ *      n_plans = 1 all images lie in d_src0 / d_dst0.  With n_plans = 2 (a stereo pair, or n / 2 pairs) the images of plan 0 lie in
+ *      d_src0 (n / 2, H_src, W_src[, 3]) and those of plan 1 in d_src1, likewise d_dst0 / d_dst1: left and right are two device pointers
+ *      and one launch, without a staging copy.  Optional outputs: d_valid0 / d_valid1 (.., H_dst, W_dst) uint8, 1 where the pixel is valid
+ *      in the sense of step 2 or 3 (in depth mode whatever the source depth); dbg->d_map0 / d_map1 (.., H_dst, W_dst, 2) fp32, the (u, v)
+ *      of step 1, both the quiet NaN 0x7fc00000 where step 1 declared the pixel invalid.
+ *      One launch on `stream`, the plans travel as kernel arguments; no allocation, no synchronisation, no atomics: the call can be
+ *      captured into a graph at once.
+ *      FP_EINVAL, each checked before ctx is looked into: a null ctx, opts, d_src0 or d_dst0 (with n_plans = 2 also d_src1, d_dst1); a
+ *      struct_size the library does not know; mode other than the two; channels other than 1 or 3 (depth: 1); n_plans other than 1 or
+ *      2; n < 1 or no multiple of n_plans; a size < 1 or > FP_REMAP_MAX_SIDE; plans of different sizes; a plan value that is not finite
+ *      (r2_max: not > 0), fx or fy not > 0; in depth mode zfar not > 0. */
+#define FP_REMAP_COLOUR 0
+#define FP_REMAP_DEPTH 1
+#define FP_REMAP_MAX_SIDE 16384
+typedef struct fp_remap_plan {
+  float k_new[4];          /* fx, fy, cx, cy of the new camera */
+  float rot[9];            /* new frame -> raw frame, row-major */
+  float k_raw[4];          /* fx, fy, cx, cy of the raw camera */
+  float dist[8];           /* k1 k2 p1 p2 k3 k4 k5 k6 */
+  float r2_max;            /* rays with r2 >= r2_max are refused; infinity: none */
+  int src_h, src_w, dst_h, dst_w;
+} fp_remap_plan;
+typedef struct fp_remap_opts {
+  size_t struct_size;      /* = sizeof(fp_remap_opts) */
+  int mode;                /* FP_REMAP_COLOUR or FP_REMAP_DEPTH */
+  int channels;            /* 1 or 3 */
+  int n_plans;             /* 1 or 2 */
+  float zfar;              /* metres; read only in depth mode (infinity: no limit) */
+  fp_remap_plan plan[2];
+} fp_remap_opts;
+typedef struct fp_remap_debug {
+  size_t struct_size;      /* = sizeof(fp_remap_debug) */
+  float *d_map0, *d_map1;
+} fp_remap_debug;
+int fp_remap(fp_ctx *ctx, const void *d_src0, const void *d_src1, int n, const fp_remap_opts *opts, void *d_dst0, void *d_dst1, uint8_t *d_valid0,
+             uint8_t *d_valid1, const fp_remap_debug *dbg, void *stream);
+
 /* ---- texture baking: the colours of posed RGB-D reference views gathered into a per-face texture atlas of a mesh - the last stage of
  *      the model-free set-up, after the simplification (fp_mesh_simplify_* refuses textured meshes: simplify first, then bake).  The
  *      reference does this in mesh_texture_from_train_images (bundlesdf/nerf_runner.py:1122) with a UV parametrisation and the equal
