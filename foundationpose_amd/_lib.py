@@ -171,6 +171,9 @@ class FpRemapDebug(Structure):
   _fields_ = [('struct_size', ctypes.c_size_t), ('d_map0', c_void_p), ('d_map1', c_void_p)]
 
 
+FP_REPROJECT_MAX_VIEWS, FP_REPROJECT_MAX_SPLAT, FP_REPROJECT_MAX_FRAMES = 8, 8, 65535      # fp_depth_reproject
+
+
 class FpObjectBatch(Structure):
   _fields_ = [('mesh', c_void_p), ('d_rgb', c_void_p), ('d_geom', c_void_p), ('H', c_int), ('W', c_int), ('K', c_void_p),
               ('mesh_diameter', c_double), ('n', c_int)]
@@ -245,6 +248,8 @@ _PROTOS = {
                             c_void_p]),
   'fp_remap': (c_int, [c_void_p, c_void_p, c_void_p, c_int, POINTER(FpRemapOpts), c_void_p, c_void_p, c_void_p, c_void_p, POINTER(FpRemapDebug),
                        c_void_p]),
+  'fp_depth_reproject': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p,
+                                 c_void_p, c_void_p]),
   'fp_texture_bake': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                               POINTER(FpTextureCfg), c_void_p, c_void_p, c_void_p, c_void_p]),
   'fp_point_mesh_distance': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -213,6 +213,10 @@ int fp_stereo_check(const void *ctx, const void *d_left, const void *d_right, in
 int fp_remap_check(const void *ctx, const void *d_src0, const void *d_src1, int n, const fp_remap_opts *opts, const void *d_dst0, const void *d_dst1,
                    const fp_remap_debug *dbg);
 
+// reproject.hip: every check of a value of fp_depth_reproject, which needs no device.  scripts/reproject_host_check.cpp runs it under sanitizers.
+int fp_depth_reproject_check(const void *ctx, const void *d_depth, int n, int V, int Hs, int Ws, const double *Ks, const double *T_dst_src,
+                             const double *K_dst, int Hd, int Wd, float zfar, const void *d_keys, const void *d_depth_out);
+
 int fp_arena_ensure(fp_ctx *ctx, size_t bytes);
 size_t fp_arena_bytes_for(int n_hyp);     // whole refine/score pass (outer buffers + network)
 size_t fp_arena_inner_bytes(int n_hyp);   // network forward only

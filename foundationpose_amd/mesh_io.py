@@ -478,3 +478,56 @@ def load_stereo_calibration(path, left_section='LEFT_CAM_FHD1200', right_section
   Q = _rotation_of_vector([_calibration_optional(path, stereo, 'STEREO', f'{k}_{res}') for k in ('RX', 'CV', 'RZ')])
   out['R'], out['T'] = Q.T, -Q.T @ centre
   return out
+
+
+RGBD_CALIBRATION_KEYS = ('K_depth', 'dist_depth', 'K_colour', 'dist_colour', 'T_colour_depth', 'size_depth', 'size_colour')
+
+
+def load_rgbd_calibration(path):
+  """The calibration of an RGB-D sensor whose depth and colour come from two sensors, from this project's own small JSON file (written
+  down in INTEGRATION.md, "Aligning depth to the colour camera"): a dict with K_depth, K_colour (3x3), dist_depth, dist_colour (0, 4, 5
+  or 8 coefficients k1 k2 p1 p2 [k3 [k4 k5 k6]]; an absent key is no distortion), T_colour_depth (4x4, metres: x_colour = T x_depth),
+  size_depth and size_colour ((H, W) tuples) - the arguments of Utils.rgbd_rig, in its order.  save_rgbd_calibration writes one."""
+  import json
+  with open(path) as f:
+    raw = json.load(f)
+  if not isinstance(raw, dict):
+    raise ValueError(f'{path}: expected a JSON object with the keys {", ".join(RGBD_CALIBRATION_KEYS)}')
+  unknown = sorted(set(raw) - set(RGBD_CALIBRATION_KEYS))
+  if unknown:
+    raise ValueError(f'{path}: unknown key(s) {", ".join(unknown)} (known: {", ".join(RGBD_CALIBRATION_KEYS)})')
+  out = {}
+  for key in RGBD_CALIBRATION_KEYS:
+    if key not in raw:
+      if key.startswith('dist_'):
+        out[key] = np.zeros(0)
+        continue
+      raise ValueError(f'{path}: the key "{key}" is missing')
+    v = np.asarray(raw[key], dtype=np.float64)
+    if key.startswith('K_'):
+      if v.size != 9:
+        raise ValueError(f'{path}: {key} must hold 3x3 numbers, got {v.size}')
+      out[key] = v.reshape(3, 3)
+    elif key == 'T_colour_depth':
+      if v.size != 16:
+        raise ValueError(f'{path}: T_colour_depth must hold 4x4 numbers, got {v.size}')
+      out[key] = v.reshape(4, 4)
+    elif key.startswith('size_'):
+      if v.size != 2 or (v != np.round(v)).any():
+        raise ValueError(f'{path}: {key} must be [H, W], got {raw[key]}')
+      out[key] = (int(v.reshape(-1)[0]), int(v.reshape(-1)[1]))
+    else:
+      out[key] = v.reshape(-1)
+  return out
+
+
+def save_rgbd_calibration(path, K_depth, dist_depth, K_colour, dist_colour, T_colour_depth, size_depth, size_colour):
+  """Writes the file load_rgbd_calibration reads; float64 values survive the round trip bit for bit (JSON numbers are written with repr)."""
+  import json
+  lists = lambda a: np.asarray(a, dtype=np.float64).tolist()
+  rec = dict(K_depth=lists(np.reshape(K_depth, (3, 3))), dist_depth=lists(np.reshape([] if dist_depth is None else dist_depth, -1)),
+             K_colour=lists(np.reshape(K_colour, (3, 3))), dist_colour=lists(np.reshape([] if dist_colour is None else dist_colour, -1)),
+             T_colour_depth=lists(np.reshape(T_colour_depth, (4, 4))), size_depth=[int(v) for v in size_depth], size_colour=[int(v) for v in size_colour])
+  with open(path, 'w') as f:
+    json.dump(rec, f, indent=1)
+    f.write('\n')

@@ -154,6 +154,21 @@ class Undistort(Processor):
     return data
 
 
+class AlignDepth(Processor):
+  """Replaces `data.rgb` and `data.depth` of an RGB-D camera whose depth and colour come from two sensors by the frame aligned to the
+  colour camera (whichever of the two is there) and sets `data.K = rig.K`: the stage in front of FoundationPoseEstimator on such a
+  stream.  rig: reproject.rgbd_rig(...).  A mask in `data.mask` is NOT warped: make it on the colour image, which is the aligned one."""
+
+  def __init__(self, rig, zfar=np.inf):
+    self.rig, self.zfar = rig, zfar
+
+  def process(self, data):
+    from .reproject import align_frame
+    data.rgb, data.depth = align_frame(data.rgb, data.depth, self.rig, zfar=self.zfar)
+    data.K = self.rig.K.copy()
+    return data
+
+
 class FoundationPoseEstimator(Processor):
   """Wraps foundationpose_amd.estimater.FoundationPose as a pipeline stage (what main.py:34-79 does by hand):
   first frame -> register(), later frames -> track_one()."""

@@ -1097,6 +1097,51 @@ typedef struct fp_remap_debug {
 int fp_remap(fp_ctx *ctx, const void *d_src0, const void *d_src1, int n, const fp_remap_opts *opts, void *d_dst0, void *d_dst1, uint8_t *d_valid0,
              uint8_t *d_valid1, const fp_remap_debug *dbg, void *stream);
 
+/* ---- registering depth into another camera: the depth maps of V calibrated pinhole cameras reprojected into ONE target pinhole camera
+ *      of another size, with a z-buffer (csrc/reproject.hip).  The stage between fp_remap and fp_depth_prefilter on an RGB-D sensor whose
+ *      depth and colour come from two sensors (V = 1, the target is the colour camera), and the merge of a rig of depth cameras into one
+ *      view (V > 1).  The reference has nothing in this place (its camera vendor's SDK delivers depth aligned to colour); the rule is the
+ *      library's own and tests/depth_reproject_oracle.py restates all of it in numpy.  Lens distortion is not seen
+ *      here: fp_remap removes it on either side.
+ *      d_depth (n, V, Hs, Ws) fp32 metres: n frames of V views of one size.  Ks (V, 3, 3) and K_dst (3, 3) are host double camera
+ *      matrices, T_dst_src (V, 4, 4) host double rigid transforms, row-major, from the frame of source camera s to the target frame
+ *      (x_dst = R x_src + t; the last row is not used).  They are the same for every frame, are rounded to fp32 once (pinhole_of /
+ *      rigid_of of csrc/view_geom.h) and travel as kernel arguments.
+ *      The rule, fp32, each operation rounded once, in this order, with the functions of csrc/view_geom.h.  For view s, source pixel
+ *      (c, r) with depth d:
+ *        1 Source.  The pixel is skipped unless depth_ok(d, zfar): d >= 0.001 and d < zfar (a NaN fails).
+ *        2 Centre.  p = pinhole_point(cam_s, c, r, d); q = (rigid_apply(T_s, 0, p), rigid_apply(T_s, 1, p), rigid_apply(T_s, 2, p)).
+ *          Skipped unless depth_ok(q.z, zfar).  z_out = q.z.
+ *        3 Footprint.  The corners pinhole_point(cam_s, c - 0.5, r - 0.5, d) and pinhole_point(cam_s, c + 0.5, r + 0.5, d) go through
+ *          T_s the same way: q0, q1.  Skipped unless q0.z > 0 and q1.z > 0.  (uc, vc), (u0, v0), (u1, v1) = project_ratio(dst, .) of q,
+ *          q0, q1.  Skipped unless all six are finite.
+ *        4 Range.  xa = ceil(min(u0, u1)), xb = ceil(max(u0, u1)) - 1, pc = floor(uc + 0.5); x_lo = min(xa, pc), x_hi = max(xb, pc);
+ *          likewise y_lo, y_hi, pr from the v: the target pixels whose centres lie in the source pixel's footprint [min, max), and always
+ *          the centre's own pixel (pc, pr).  All in float; skipped unless the four values are finite, so nothing huge reaches a cast.
+ *        5 Cap.  If (x_hi - x_lo) + 1 or (y_hi - y_lo) + 1 exceeds FP_REPROJECT_MAX_SPLAT, the range is (pc, pr) alone: a grazing
+ *          surface or an absurd magnification.
+ *        6 Clip.  x_lo = max(x_lo, 0), x_hi = min(x_hi, Wd - 1), likewise y with Hd; an empty range writes nothing.
+ *        7 Write.  Every target pixel of the range takes the minimum of its 64-bit key and (bits of z_out << 32 | (s Hs + r) Ws + c):
+ *          z_out is positive, so the order of its bits is the order of its value.  The nearest surface wins, among equal depths the
+ *          lowest source index; the result does not depend on the order of the threads and is the same on every run and in any batch.
+ *      d_depth_out (n, Hd, Wd) fp32: z_out of the winner, 0 where nothing arrived.  d_source (n, Hd, Wd) int32, optional: the winner's
+ *      index (s Hs + r) Ws + c within its frame, -1 where nothing arrived.  With one view, cam_s = dst and T = 1 of one size every
+ *      depth is copied bit for bit onto its own pixel.
+ *      d_keys: n Hd Wd uint64 of working memory from the caller, 8-byte aligned; its contents before the call do not matter and are
+ *      undefined after it.  One memset node and two launches on `stream`; no allocation, no synchronisation: the call can be captured
+ *      into a graph at once.
+ *      Depth is piecewise constant over a source pixel: nearest neighbour, nothing is interpolated across an edge.  A background can
+ *      show through a foreground at the foreground's rim and where the magnification exceeds the cap; what no source sees stays 0.
+ *      FP_EINVAL, each checked before ctx is looked into: a null ctx, d_depth, Ks, T_dst_src, K_dst, d_keys or d_depth_out; n outside
+ *      1 .. FP_REPROJECT_MAX_FRAMES; V outside 1 .. FP_REPROJECT_MAX_VIEWS; a side < 1 or > FP_REMAP_MAX_SIDE; V Hs Ws > 2^31 - 1; an
+ *      entry of a K or a T that is not finite (as a double or rounded to fp32); fx or fy not > 0; zfar not > 0 (infinity: no limit);
+ *      d_keys not 8-byte aligned. */
+#define FP_REPROJECT_MAX_VIEWS 8
+#define FP_REPROJECT_MAX_SPLAT 8
+#define FP_REPROJECT_MAX_FRAMES 65535
+int fp_depth_reproject(fp_ctx *ctx, const float *d_depth, int n, int V, int Hs, int Ws, const double *Ks, const double *T_dst_src, const double *K_dst,
+                       int Hd, int Wd, float zfar, uint64_t *d_keys, float *d_depth_out, int32_t *d_source, void *stream);
+
 /* ---- texture baking: the colours of posed RGB-D reference views gathered into a per-face texture atlas of a mesh - the last stage of
  *      the model-free set-up, after the simplification (fp_mesh_simplify_* refuses textured meshes: simplify first, then bake).  The
  *      reference does this in mesh_texture_from_train_images (bundlesdf/nerf_runner.py:1122) with a UV parametrisation and the equal
