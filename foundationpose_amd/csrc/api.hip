@@ -61,7 +61,7 @@ int fp_arena_ensure(fp_ctx *ctx, size_t bytes) {
 
 int fp_set_kernel_attributes(fp_ctx *ctx) {
   std::vector<KernelLds> v;
-  conv_kernel_lds(v), conv_halo_kernel_lds(v), conv_s1b_kernel_lds(v), conv_small_kernel_lds(v), conv_s2_kernel_lds(v), stem_kernel_lds(v);
+  conv_kernel_lds(v), conv_halo_kernel_lds(v), conv_s1b_kernel_lds(v), conv_small_kernel_lds(v), conv_s2_kernel_lds(v), stem_kernel_lds(v), front_kernel_lds(v);
   tok_gemm_kernel_lds(v), tok_qkv_kernel_lds(v), head_mlp_kernel_lds(v), attn_kernel_lds(v), raster_kernel_lds(v);
   FP_CHECK_HIP(hipSetDevice(ctx->device));
   for (const KernelLds &k : v)
@@ -1401,6 +1401,24 @@ extern "C" int fp_conv3x3_band_f16(fp_ctx *ctx, const void *d_in, int Nimg, int 
   ArenaScope scope(ctx->arena);
   FP_TRY(conv_materialise(ctx, a, plan, (hipStream_t)stream));
   return launch_conv_s1b(ctx, a, (hipStream_t)stream);
+}
+
+// Building block for the parity tests: the front end of encodeA as the networks run it from three hypotheses on (front.hip) - the 7x7 stem and the
+// 64 -> 128 stride-2 layer in one launch, the stem's output in LDS only.  Operands as fp_conv2d_f16 takes them ([64][416] and [128][576] fp16
+// rows, folded biases); the fragment-order copies a network makes at load are made here, in the arena.
+extern "C" int fp_front_end_f16(fp_ctx *ctx, const void *d_x, int Nimg, const void *d_w0_packed, const float *d_b0, const void *d_w1_packed,
+                                const float *d_b1, void *d_a1, void *d_a0, void *stream) {
+  FP_REQUIRE(ctx && d_x && d_w0_packed && d_b0 && d_w1_packed && d_b1 && d_a1 && Nimg >= 0, "fp_front_end_f16: bad argument");
+  if (Nimg == 0) return FP_OK;
+  hipStream_t s = (hipStream_t)stream;
+  ArenaScope scope(ctx->arena);
+  const size_t h0 = front_packed_stem_halfs(), h1 = conv_packed_halfs(CONV_OFFER_S2, 128, 64);
+  FP_TRY(fp_arena_ensure(ctx, (h0 + h1) * sizeof(f16) + 4096));
+  f16 *wst = (f16 *)ctx->arena.take(h0 * sizeof(f16)), *wpk = (f16 *)ctx->arena.take(h1 * sizeof(f16));
+  if (!wst || !wpk) return FP_ENOMEM;
+  FP_TRY(front_pack_stem((const f16 *)d_w0_packed, conv_kpad(7, 7, 8), wst, s));
+  FP_TRY(conv_pack_weights(CONV_OFFER_S2, (const f16 *)d_w1_packed, 128, 64, conv_kpad(3, 3, 64), wpk, s));
+  return launch_front(ctx, (const f16 *)d_x, Nimg, wst, d_b0, wpk, d_b1, (f16 *)d_a1, (f16 *)d_a0, s);
 }
 
 extern "C" int fp_attention_f16(fp_ctx *ctx, const void *d_qk, const void *d_vt, int B, int T, void *d_out, void *stream) {

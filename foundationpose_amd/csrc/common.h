@@ -351,6 +351,7 @@ void conv_s1b_kernel_lds(std::vector<KernelLds> &v);    // conv_s1b.hip
 void conv_small_kernel_lds(std::vector<KernelLds> &v);  // conv_small.hip
 void conv_s2_kernel_lds(std::vector<KernelLds> &v);     // conv_s2.hip
 void stem_kernel_lds(std::vector<KernelLds> &v);        // stem.hip
+void front_kernel_lds(std::vector<KernelLds> &v);       // front.hip
 void tok_gemm_kernel_lds(std::vector<KernelLds> &v);    // tok_gemm.hip
 void tok_qkv_kernel_lds(std::vector<KernelLds> &v);     // tok_qkv.hip
 void head_mlp_kernel_lds(std::vector<KernelLds> &v);    // head_mlp.hip
@@ -367,6 +368,12 @@ int launch_conv_halo(const ConvArgs &a, const ConvPlan &plan, hipStream_t s);   
 int launch_splitk_finish(const ConvArgs &a, hipStream_t s);                                    // conv_halo.hip: adds the shares in order (also behind conv.hip's stride-2 split-K)
 int launch_stem(fp_ctx *ctx, const ConvArgs &a, hipStream_t s);                                // stem.hip
 int launch_conv_s2(fp_ctx *ctx, const ConvArgs &a, hipStream_t s);                             // conv_s2.hip
+// front.hip: the 7x7 stem and the 64 -> 128 stride-2 layer of encodeA as one launch, x [n][160][160][8] -> a1 [n][40][40][128]; bit-identical
+// to launch_stem + the implicit GEMM.  wst: the stem's weights by front_pack_stem (front_packed_stem_halfs() halfs); wpk: the stride-2 layer's
+// by s2_pack_weights (order 0); a0_dbg (optional, tests): receives the stem's output [n][80][80][64] as the kernel's tiles hold it
+int launch_front(fp_ctx *ctx, const f16 *x, int n, const f16 *wst, const float *b0, const f16 *wpk, const float *b1, f16 *a1, f16 *a0_dbg, hipStream_t s);
+size_t front_packed_stem_halfs();
+int front_pack_stem(const f16 *d_w, int Kpad, f16 *d_out, hipStream_t s);
 // packed copies of a layer's [Cout][Kpad] weights
 size_t s2_packed_halfs(int Cout, int Cin);
 int s2_pack_weights(const f16 *d_w, int Cout, int Cin, int Kpad, f16 *d_out, hipStream_t s, int ct_force = 0, int order = 0);   // ct_force: co tiles of 32 per wave group (0: s2_ct_for); order 1: conv_s1b.hip

@@ -13,6 +13,7 @@ struct ConvW {
   f16 *w = nullptr;
   f16 *wpk = nullptr;     // 3x3 stride-2 layers: the same weights in the fragment order of conv_s2.hip
   f16 *wsm = nullptr;     // 3x3 stride-1 layers with 128 / 256 / 512 input channels: fragment order of conv_small.hip (launches of a few images)
+  f16 *wfr = nullptr;     // the 7x7 stem: fragment order of front.hip (front_pack_stem)
   float *bias = nullptr;
   int Cin = 0, Cout = 0, K = 1, Kpad = 0, stride = 1;
 };
@@ -47,7 +48,7 @@ struct fp_net {
   std::vector<void *> allocs;
 };
 
-// The knobs of pass_plan.h: the process's values, read from the environment once (the only reader of these eleven names)
+// The knobs of pass_plan.h: the process's values, read from the environment once (the only reader of these twelve names)
 const PassKnobs &pass_knobs() {
   static const PassKnobs knobs = [] {
     PassKnobs k;
@@ -62,6 +63,7 @@ const PassKnobs &pass_knobs() {
     k.attn_small = (int)fp_env_int("FP_ATTN_SMALL", k.attn_small);
     k.headmlp64 = fp_env_set("FP_HEADMLP64");
     k.heads_serial = fp_env_set("FP_HEADS_SERIAL");
+    k.front_fused = fp_env_int("FP_FRONT_FUSED", 1) != 0;
     return k;
   }();
   return knobs;
@@ -156,6 +158,14 @@ int make_conv(fp_net *net, const SD &sd, const std::string &wkey, const std::str
     net->allocs.push_back(d);
     (pk == CONV_OFFER_SMALL ? out->wsm : out->wpk) = (f16 *)d;
     FP_TRY(conv_pack_weights(pk, out->w, Cout, CinP, Kpad, (f16 *)d, nullptr));
+    FP_CHECK_HIP(hipStreamSynchronize(nullptr));
+  }
+  if (K == 7 && CinP == 8 && Cout == 64 && stride == 2) {      // the stem: front.hip's copy
+    void *d = nullptr;
+    FP_CHECK_HIP(hipMalloc(&d, front_packed_stem_halfs() * sizeof(f16)));
+    net->allocs.push_back(d);
+    out->wfr = (f16 *)d;
+    FP_TRY(front_pack_stem(out->w, Kpad, out->wfr, nullptr));
     FP_CHECK_HIP(hipStreamSynchronize(nullptr));
   }
   return FP_OK;
@@ -370,20 +380,28 @@ int run_conv(fp_ctx *ctx, const Conv2dCall &c, hipStream_t s, float *splitk_scra
   return launch_conv(ctx, a, s);
 }
 
-// encodeA / encoderA of `n` images: the stem (x -> a0; x = nullptr: a0 holds the stem's output already), the stride-2 layer and the two
-// residual blocks.  The last layer writes rows of `out_ld` halfs to `out`: image rows from split_m on go to row (m - split_m), column coff_hi
+// encodeA / encoderA of `n` images: the front end (x -> a1: the stem and the stride-2 layer as one launch, front.hip, or as two through a0;
+// x = nullptr: a1 holds the front end's output already) and the two residual blocks.  The last layer writes rows of `out_ld` halfs to `out`: image rows from split_m on go to row (m - split_m), column coff_hi
 // (the channel concat cat((a, b), 1): side A -> channels [0, 128), side B -> [128, 256) of the same rows).
 struct EncodeA {
-  f16 *a0, *a1, *tA, *a2;      // n x 80x80x64, 3 x (n x 40x40x128)
+  f16 *a0, *a1, *tA, *a2;      // n x 80x80x64 (nullptr with the fused front end: not needed), 3 x (n x 40x40x128)
   float *sk;                   // split-K scratch offered to every launch (nullptr: none)
   int hyp;                     // hypotheses of the pass
 };
+// whether the front end of `images` images (the stride-2 launch's count) in a pass of `hyp` hypotheses is the fused launch (front_fused, pass_plan.h)
+bool front_is_fused(const fp_ctx *ctx, const ConvW *t, int images, int hyp, bool splitk) {
+  return t[0].wfr && t[1].wpk && t[1].Cin == 64 && t[1].Cout == 128 && front_fused(images, hyp, splitk, ctx->num_cu, pass_knobs(), conv_knobs());
+}
 int encode_a(fp_ctx *ctx, const ConvW *t, const f16 *x, int n, const EncodeA &b, hipStream_t s, f16 *out, int out_ld = 0, int split_m = 0x7fffffff, int coff_hi = 0) {
   Conv2dCall c;
   if (x) {
-    c = Conv2dCall{x, n, 160, 160, &t[0]}; c.out = b.a0; FP_TRY(run_conv(ctx, c, s, b.sk, b.hyp));
+    if (!b.a0) {
+      FP_TRY(launch_front(ctx, x, n, t[0].wfr, t[0].bias, t[1].wpk, t[1].bias, b.a1, nullptr, s));
+    } else {
+      c = Conv2dCall{x, n, 160, 160, &t[0]}; c.out = b.a0; FP_TRY(run_conv(ctx, c, s, b.sk, b.hyp));
+      c = Conv2dCall{b.a0, n, 80, 80, &t[1]}; c.out = b.a1; FP_TRY(run_conv(ctx, c, s, b.sk, b.hyp));
+    }
   }
-  c = Conv2dCall{b.a0, n, 80, 80, &t[1]}; c.out = b.a1; FP_TRY(run_conv(ctx, c, s, b.sk, b.hyp));
   c = Conv2dCall{b.a1, n, 40, 40, &t[2]}; c.out = b.tA; FP_TRY(run_conv(ctx, c, s, b.sk, b.hyp));
   c = Conv2dCall{b.tA, n, 40, 40, &t[3]}; c.res = b.a1; c.out = b.a2; FP_TRY(run_conv(ctx, c, s, b.sk, b.hyp));
   c = Conv2dCall{b.a2, n, 40, 40, &t[4]}; c.out = b.tA; FP_TRY(run_conv(ctx, c, s, b.sk, b.hyp));
@@ -421,7 +439,13 @@ int run_trunk(fp_ctx *ctx, const fp_net *net, const f16 *xA, const f16 *xB, cons
   const ConvW *t = net->trunk;
   const int N = part.n, hyp = part.conv_hyp;
   const size_t n2 = (size_t)2 * N;
-  TAKE(a0, f16, n2 * 80 * 80 * 64);
+  // the stride-2 launch of the front end has N images per side chain (and with a shared side B), 2 N as one chain: the same form either way
+  const bool fused = front_is_fused(ctx, t, (sb || (ab && ab->fan)) ? N : (int)n2, hyp, part.splitk);
+  f16 *a0 = nullptr;                   // the stem's output: with the fused front end it stays in LDS
+  if (!fused) {
+    TAKE(a0_, f16, n2 * 80 * 80 * 64);
+    a0 = a0_;
+  }
   TAKE(a1, f16, n2 * 40 * 40 * 128);
   TAKE(tA, f16, n2 * 40 * 40 * 128);
   TAKE(a2, f16, n2 * 40 * 40 * 128);
@@ -453,7 +477,7 @@ int run_trunk(fp_ctx *ctx, const fp_net *net, const f16 *xA, const f16 *xB, cons
     // one chain per side; side `h` owns images [h N, h N + N) of every buffer (and its own half of the split-K scratch)
     for (int h = 0; h < 2; ++h) {
       const size_t o80 = (size_t)h * N * 80 * 80 * 64, o40 = (size_t)h * N * 1600 * 128;
-      const EncodeA b{a0 + o80, a1 + o40, tA + o40, a2 + o40, sk ? sk + (size_t)h * 4 * N * 1600 * 128 : nullptr, hyp};
+      const EncodeA b{a0 ? a0 + o80 : nullptr, a1 + o40, tA + o40, a2 + o40, sk ? sk + (size_t)h * 4 * N * 1600 * 128 : nullptr, hyp};
       FP_TRY(encode_a(ctx, t, h == 0 ? xA : xB, N, b, h == 0 ? s : ab->stream_for(0), ab0, 256, h == 0 ? 0x7fffffff : 0, h == 0 ? 0 : 128));
     }
     FP_TRY(ab->join());
@@ -461,8 +485,14 @@ int run_trunk(fp_ctx *ctx, const fp_net *net, const f16 *xA, const f16 *xB, cons
     // one chain on cat([A,B],0): the two stems apart (the A and B halves of the net tensor may come from different places when the batch is
     // processed in chunks), then 2N images per launch; image n < N -> channels [0,128), n >= N -> [128,256)
     Conv2dCall c;
-    c = Conv2dCall{xA, N, 160, 160, &t[0]}; c.out = a0; FP_TRY(run_conv(ctx, c, s, sk, hyp));
-    c = Conv2dCall{xB, N, 160, 160, &t[0]}; c.out = a0 + (size_t)N * 80 * 80 * 64; FP_TRY(run_conv(ctx, c, s, sk, hyp));
+    if (fused) {
+      FP_TRY(launch_front(ctx, xA, N, t[0].wfr, t[0].bias, t[1].wpk, t[1].bias, a1, nullptr, s));
+      FP_TRY(launch_front(ctx, xB, N, t[0].wfr, t[0].bias, t[1].wpk, t[1].bias, a1 + (size_t)N * 1600 * 128, nullptr, s));
+    } else {
+      c = Conv2dCall{xA, N, 160, 160, &t[0]}; c.out = a0; FP_TRY(run_conv(ctx, c, s, sk, hyp));
+      c = Conv2dCall{xB, N, 160, 160, &t[0]}; c.out = a0 + (size_t)N * 80 * 80 * 64; FP_TRY(run_conv(ctx, c, s, sk, hyp));
+      c = Conv2dCall{a0, (int)n2, 80, 80, &t[1]}; c.out = a1; FP_TRY(run_conv(ctx, c, s, sk, hyp));
+    }
     FP_TRY(encode_a(ctx, t, nullptr, (int)n2, EncodeA{a0, a1, tA, a2, sk, hyp}, s, ab0, 256, N * 1600, 128));
   }
   // encodeAB
@@ -570,7 +600,11 @@ extern "C" int fp_refine_forward(fp_ctx *ctx, const fp_net *net, const void *d_n
 // `hyp`: the few-image forms are chosen by the pass, not by the launch) -> feat [n_groups][1600][128]
 int fp_encode_side_b(fp_ctx *ctx, const fp_net *net, const f16 *xB, int n_groups, int hyp, f16 *feat, hipStream_t s) {
   const int G = n_groups;
-  TAKE(a0, f16, (size_t)G * 80 * 80 * 64);
+  f16 *a0 = nullptr;
+  if (!front_is_fused(ctx, net->trunk, G, hyp, false)) {
+    TAKE(a0_, f16, (size_t)G * 80 * 80 * 64);
+    a0 = a0_;
+  }
   TAKE(a1, f16, (size_t)G * 1600 * 128);
   TAKE(tA, f16, (size_t)G * 1600 * 128);
   TAKE(a2, f16, (size_t)G * 1600 * 128);

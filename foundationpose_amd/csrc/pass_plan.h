@@ -50,6 +50,7 @@ struct PassKnobs {
   int attn_small = 2;          // FP_ATTN_SMALL: images up to which attention_small_kernel (split-K) runs (0: off)
   bool headmlp64 = false;      // FP_HEADMLP64 set: the 64-token head MLP (two resident tiles) at every size
   bool heads_serial = false;   // FP_HEADS_SERIAL set: both RefineNet heads on one stream
+  bool front_fused = true;     // FP_FRONT_FUSED: 0 runs the stem and the 64 -> 128 stride-2 layer of encodeA as two launches (bit-identical)
 };
 const PassKnobs &pass_knobs();
 
@@ -76,6 +77,18 @@ inline QkvForm qkv_form(int hyp, int images, const PassKnobs &k) {
   if (hyp > 0 && hyp <= k.qkv_small) return QKV_SMALL;
   if (hyp > 0 && k.qkv64 && images > k.qkv_small) return QKV_PAIR64;
   return QKV_TOK128;
+}
+
+// The front end of encodeA (x -> a1: the 7x7 stem, then the 64 -> 128 stride-2 layer) as ONE launch (front.hip) wherever the two launches
+// would be the stem form followed by the implicit GEMM: not in the passes of one and two hypotheses, whose stride-2 layer is the few-image form.
+// `images`: of the stride-2 launch as it would run; hyp: the pass's hypotheses (ConvArgs::hyp); splitk: whether scratch is on offer.
+inline bool front_fused(int images, int hyp, bool splitk, int num_cu, const PassKnobs &k, const ConvKnobs &ck) {
+  if (!k.front_fused || images <= 0) return false;
+  ConvArgs st = conv_args(nullptr, images, 160, 160, 8, nullptr, nullptr, 64, 7, 7, 2, 3, conv_kpad(7, 7, 8), nullptr);
+  ConvArgs dn = conv_args(nullptr, images, 80, 80, 64, nullptr, nullptr, 128, 3, 3, 2, 1, conv_kpad(3, 3, 64), nullptr);
+  st.relu = dn.relu = 1, st.hyp = dn.hyp = hyp;
+  const unsigned sk = splitk ? CONV_OFFER_SPLITK : 0u;
+  return conv_plan(st, num_cu, sk, ck).form == CONV_STEM && conv_plan(dn, num_cu, CONV_OFFER_SMALL | CONV_OFFER_S2 | sk, ck).form == CONV_IGEMM2;
 }
 
 // from 48 hypotheses on (round 4, refine x5 + score of one object: 40 hypotheses 6.55 ms as one batch / 7.08 split, 48: 7.82 / 7.55, 56: 8.87 / 8.17,

@@ -1324,6 +1324,13 @@ int fp_conv2d_f16(fp_ctx *ctx, const void *d_in, int Nimg, int H, int W, int Cin
  * kernel behind fp_conv2d_f16. */
 int fp_conv3x3_band_f16(fp_ctx *ctx, const void *d_in, int Nimg, int C, const void *d_w_packed, const float *d_bias, const void *d_res,
                         int relu, void *d_out, void *stream);
+/* The front end of encodeA / encoderA in one launch (csrc/front.hip): a1 = ConvBNReLU_3x3s2(ConvBNReLU_7x7s2(x)), the first two layers
+ * of the trunk (learning/models/refine_network.py:37-38, score_network.py:36-37), with the stem's output kept in LDS.  x [Nimg][160][160][8]
+ * fp16 NHWC (channels 6, 7 zero); w0_packed [64][416], w1_packed [128][576] fp16 and the folded biases as fp_conv2d_f16 takes them;
+ * a1 [Nimg][40][40][128] fp16.  d_a0 (optional, may be null): [Nimg][80][80][64] fp16, receives the stem's output as the kernel's tiles
+ * hold it.  Bit-identical to fp_conv2d_f16 on the two layers in turn, at any image count. */
+int fp_front_end_f16(fp_ctx *ctx, const void *d_x, int Nimg, const void *d_w0_packed, const float *d_b0, const void *d_w1_packed,
+                     const float *d_b1, void *d_a1, void *d_a0, void *stream);
 /* fused multi-head self-attention core, 4 heads x 128: qk [M][1024] fp16 (q|k), vt [B][4][128][416] fp16 -> out [M][512] fp16.
  * vt is V transposed, token t of a hypothesis in column (t & ~15) | ((t>>2 & 1) << 3) | ((t>>3 & 1) << 2) | (t & 3)
  * (tokens of a group of 16 in the order 0-3, 8-11, 4-7, 12-15); columns of tokens >= T must hold zeros. */
