@@ -1,6 +1,6 @@
 // 3x3 / stride-1 / pad-1 convolutions on 40x40 maps - 128 -> 128 (the four ResnetBasicBlock convolutions of encodeA / encoderA) and
 // 256 -> 256 (those of encodeAB's first stage; network_modules.py:73-111 via refine_network.py:39-47) - on the structure of conv_s2.hip
-// instead of conv_halo.hip.
+// (the band pieces of conv_band.h) instead of conv_halo.hip.
 // Bit-identical to conv3x3_halo_dma_kernel<40>: an output element accumulates in the same order - 32-channel groups, inside a group
 // kernel row by kernel row, inside a row tap by tap, inside a tap the two 16-channel MFMA steps - from the same bias, and the epilogue
 // rounds once after the same fp32 residual add (tests/test_gpu_kernels.py::test_band_kernel_equals_halo_kernel).  Full-batch launches
@@ -11,8 +11,7 @@
 //   * a workgroup (4 waves) owns 8 output rows x 40 = 320 pixels of ONE image (5 tiles per image: no tile straddles two) x a block of
 //     128 output channels (the blocks of a pixel tile are neighbours in the grid: they share the band in L2): wave (c, p) owns 64 couts (2 accumulator tiles) x the 160 pixels of rows 4p .. 4p+3 (5 pixel tiles of 32);
 //   * per 32-channel group the band goes to LDS once by LDS-DMA as two 16-channel planes (10 input rows x 42 columns of 32-byte
-//     pixels each, row pitch 56 slots: 56 = 40 (mod 16) keeps the lane -> bank map of a 32-pixel tile unchanged across its row breaks;
-//     the two 16-byte halves of slot q swapped when bit 3 of q is set), double buffered (72 KB), and feeds all 9 taps of both planes;
+//     pixels each in the stride-1 layout of conv_band.h, row pitch 56 = 40 (mod 16)), double buffered (72 KB), and feeds all 9 taps of both;
 //   * weights never touch LDS: packed at load time in MFMA-fragment order (s2_pack_weights, order 1: group, tap, 16-channel half,
 //     co tile), each wave streams the fragments of its 64 couts L2 -> registers three steps ahead: 2 KB per 10 MFMAs;
 //   * two workgroups per CU (<= 256 VGPRs each).
@@ -23,7 +22,7 @@
 // eight K groups the halo kernel's prologue / epilogue share is small and its weights are shared through LDS (here each cout block
 // re-reads the band and each wave streams its own weights).
 #include "common.h"
-#include "device_util.h"
+#include "conv_band.h"
 
 #define B1_THREADS 256
 // (B1_W = 40, the map edge: conv_plan.h)
@@ -52,103 +51,48 @@ __global__ __launch_bounds__(B1_THREADS, 2) void conv3x3_s1_band_kernel(ConvArgs
   const int img = pt / (H / B1_ROWS), oy0 = (pt - img * (H / B1_ROWS)) * B1_ROWS;
   const int ngrp = p.Cin >> 5;                             // 32-channel groups
 
-  // ---- band DMA: instruction u = wave + 4 v, lane l -> slot 32 u + l/2 of the group's 1120 (plane ks = slot / 560, slot q of the plane),
-  // physical half l&1 = logical half ^ bit 3 of q ----
-  unsigned src_off[DPW];                                   // byte offset of (pixel, plane, logical half) in the input, group 0; ~0u: zeros
-#pragma unroll
-  for (int v = 0; v < DPW; ++v) {
-    const int qq = (wave + 4 * v) * 32 + (lane >> 1);
-    const int ks = qq >= B1_BROWS * P ? 1 : 0, q = qq - ks * (B1_BROWS * P), hl = (lane & 1) ^ ((q >> 3) & 1);
-    const int b = q / P, c = q - b * P;
-    const int iy = oy0 - 1 + b, ix = c - 1;
-    const bool ok = b < B1_BROWS && c < W + 2 && iy >= 0 && iy < H && ix >= 0 && ix < W;
-    src_off[v] = ok ? (unsigned)((((img * H + iy) * W + ix) * p.Cin + ks * 16 + hl * 8) * 2) : 0xffffffffu;
-  }
-  auto band_dma = [&](int grp, int buf) __attribute__((always_inline)) {
+  // ---- band DMA (conv_band.h): slot qq of the group's 1120 = plane ks = qq / 560, slot q of the plane; band row b holds input row oy0 - 1 + b ----
+  static_assert((B1_BROWS * B1_P) % 16 == 0, "bit 3 of a plane's slot is bit 3 of the group's slot");
+  unsigned src_off[DPW];                                   // byte offset of (pixel, plane, logical half) in the input, group 0
+  band_dma_offsets(src_off, wave, lane, [&](int qq, int hl) {
+    const int ks = qq >= B1_BROWS * P ? 1 : 0;
+    const BandSrc s = s1_band_src(P, W, B1_BROWS, oy0, qq - ks * (B1_BROWS * P));
+    return s.ok ? (unsigned)((((img * H + s.iy) * W + s.ix) * p.Cin + ks * 16 + hl * 8) * 2) : BAND_ZERO;
+  });
+  // (written out here and in conv_s2.hip: through a shared helper hipcc allocates the kernels' scalar registers differently)
+  auto dma = [&](int grp, int buf) __attribute__((always_inline)) {
 #pragma unroll
     for (int v = 0; v < DPW; ++v) {
-      const char *src = src_off[v] != 0xffffffffu ? (const char *)p.in + src_off[v] + grp * 64 : (const char *)zero_page;
+      const char *src = src_off[v] != BAND_ZERO ? (const char *)p.in + src_off[v] + grp * 64 : (const char *)zero_page;
       glds16(src, lds0 + buf * B1_BAND_BYTES + (wave + 4 * v) * 1024);
     }
   };
-  // ---- B fragments: lane = output pixel 32 j + lr of the wave's 160 (local row jr of its 4, column ox), k half lh; tap (ky, kx) of
-  // that pixel is slot qb[j] + ky P + kx (band row 4 ph + jr + ky holds input row oy0 + 4 ph + jr + ky - 1, slot c holds column c - 1)
+  // ---- B fragments: lane = output pixel 32 j + lr of the wave's 160 (local row jr of its 4, column ox), k half lh; band row 4 ph + jr + ky
+  // holds input row oy0 + 4 ph + jr + ky - 1 ----
   int qb[NPT];
 #pragma unroll
   for (int j = 0; j < NPT; ++j) {
     const int pl = 32 * j + lr, jr = pl / W, ox = pl - jr * W;
-    qb[j] = (((4 * ph + jr) * P + ox) << 5) | (lh << 4);
+    qb[j] = band_addr((4 * ph + jr) * P + ox, lh);
   }
   // ---- A fragments: this wave's stream of 1-KB fragments, (group, tap, 16-channel half, co tile) in order (s2_pack_weights order 1) ----
-  const half8 *wp = reinterpret_cast<const half8 *>(wpk) + ((size_t)(cob * 2 + ch) * ngrp * 18 * CT) * 64 + lane;
-  half8 aq[3][CT];
-  int f = 0;
-  auto a_fetch = [&](int slot) __attribute__((always_inline)) {
+  WeightRing<CT> ring{reinterpret_cast<const half8 *>(wpk) + ((size_t)(cob * 2 + ch) * ngrp * 18 * CT) * 64 + lane};
+  dma(0, 0);
 #pragma unroll
-    for (int ct = 0; ct < CT; ++ct) aq[slot][ct] = wp[(size_t)(f * CT + ct) * 64];
-    ++f;
-  };
-  band_dma(0, 0);
-#pragma unroll
-  for (int d = 0; d < 3; ++d) a_fetch(d);
+  for (int d = 0; d < 3; ++d) ring.fetch(d);
 
+  const int co0 = cob * 128 + ch * 64;
   floatx16 acc[CT][NPT];
-  {
-    const int co0 = cob * 128 + ch * 64;
-#pragma unroll
-    for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-      for (int rg = 0; rg < 4; ++rg) {
-        const float4 bv = *reinterpret_cast<const float4 *>(p.bias + co0 + ct * 32 + rg * 8 + lh * 4);
-#pragma unroll
-        for (int j = 0; j < NPT; ++j) {
-          acc[ct][j][rg * 4 + 0] = bv.x;
-          acc[ct][j][rg * 4 + 1] = bv.y;
-          acc[ct][j][rg * 4 + 2] = bv.z;
-          acc[ct][j][rg * 4 + 3] = bv.w;
-        }
-      }
-  }
-  for (int grp = 0; grp < ngrp; ++grp) {
-    wait_vm_lgkm<0>();
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    if (grp + 1 < ngrp) band_dma(grp + 1, (grp + 1) & 1);
-    const unsigned char *band = b1_smem + (grp & 1) * B1_BAND_BYTES;
-    // step st = tap * 2 + ks (tap = ky * 3 + kx): the halo kernel's order inside a 32-channel group
-    auto b_read = [&](int st, int j) __attribute__((always_inline)) -> half8 {
-      const int t = st >> 1, ks = st & 1, ky = t / 3, kx = t - ky * 3;
-      int x = qb[j];
-      asm volatile("" : "+v"(x));
-      x += (ky * P + kx) << 5;
-      return *reinterpret_cast<const half8 *>(band + ks * B1_PLANE_BYTES + (x ^ ((x >> 4) & 16)));
-    };
-    half8 b[NPT];
-#pragma unroll
-    for (int j = 0; j < NPT; ++j) b[j] = b_read(0, j);
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int st = 0; st < 18; ++st) {
-#pragma unroll
-      for (int j = 0; j < NPT; ++j) {
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct) acc[ct][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(aq[st % 3][ct], b[j], acc[ct][j], 0, 0, 0);
-        if (st < 17) b[j] = b_read(st + 1, j);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      a_fetch(st % 3);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  }
-  wait_vm_lgkm<0>();
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_sched_barrier(0);
+  acc_from_bias(acc, p.bias, co0, lh);
+  // step st = tap * 2 + ks (tap = ky * 3 + kx): the halo kernel's order inside a 32-channel group
+  band_k_loop<18>(acc, ring, ngrp, dma, [&](int buf, int st, int j) __attribute__((always_inline)) {
+    return band_read_s1<P>(b1_smem + buf * B1_BAND_BYTES + (st & 1) * B1_PLANE_BYTES, qb[j], st >> 1);
+  });
 
   // ---- epilogue: one 32-pixel tile at a time through this wave's staging rows (32 px x 64 couts) ----
   f16 *stage = reinterpret_cast<f16 *>(b1_smem) + (size_t)wave * (32 * B1_STAGE_LD);
   const float lo = p.relu ? 0.f : -__builtin_inff();
   const int m_wave = (img * H + oy0 + 4 * ph) * W;        // first output pixel of this wave (flattened over images)
-  const int co0 = cob * 128 + ch * 64;
 #pragma unroll
   for (int j = 0; j < NPT; ++j) {
     if constexpr (RES) {
@@ -162,34 +106,12 @@ __global__ __launch_bounds__(B1_THREADS, 2) void conv3x3_s1_band_kernel(ConvArgs
       }
       wait_vm_lgkm<0>();
     }
-#pragma unroll
-    for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-      for (int rg = 0; rg < 4; ++rg) {
-        f16 *sp = &stage[lr * B1_STAGE_LD + ct * 32 + rg * 8 + lh * 4];
-        float v[4] = {acc[ct][j][rg * 4 + 0], acc[ct][j][rg * 4 + 1], acc[ct][j][rg * 4 + 2], acc[ct][j][rg * 4 + 3]};
-        if constexpr (RES) {
-          const half4 rq = *reinterpret_cast<const half4 *>(sp);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] += (float)rq[e];
-        }
-        half4 hv;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) hv[e] = (f16)fmaxf(v[e], lo);
-        *reinterpret_cast<half4 *>(sp) = hv;
-      }
-    wait_lgkm();
-    uint4 v4[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) v4[u] = *reinterpret_cast<const uint4 *>(&stage[(u * 8 + (lane >> 3)) * B1_STAGE_LD + (lane & 7) * 8]);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int m = m_wave + 32 * j + u * 8 + (lane >> 3);
+    band_store_tile<B1_STAGE_LD>(stage, acc, j, lane, lr, lh, ReluThenRound<RES>{lo}, [&](int px, int c16) {
+      const int m = m_wave + 32 * j + px;                 // (the channel-concat addressing of the last encodeA layer)
       const bool hi = m >= p.split_m;
       const long long orow = hi ? (long long)(m - p.split_m) : (long long)m;
-      *reinterpret_cast<uint4 *>((f16 *)p.out + orow * p.out_ld + (hi ? p.coff_hi : 0) + co0 + (lane & 7) * 8) = v4[u];
-    }
-    wait_lgkm();
+      return BandDst{(f16 *)p.out + orow * p.out_ld + (hi ? p.coff_hi : 0) + co0 + c16 * 8};
+    });
   }
 }
 

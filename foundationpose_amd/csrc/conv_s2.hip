@@ -8,11 +8,8 @@
 //     images) x 256 (or 128) output channels; wave w owns 64 (32) couts x ALL 160 pixels = CT x 5 accumulator tiles of
 //     v_mfma_f32_32x32x16_f16;
 //   * per 16-channel input chunk the band of input rows the tile needs (<= 18 rows x 41 columns of 32-byte pixels = 24 KB) goes to
-//     LDS ONCE by LDS-DMA, double buffered, and feeds all 9 taps.  A band row is stored as two column-parity planes (even input
-//     columns, then odd ones), so the stride-2 taps of consecutive output pixels are consecutive LDS slots; the two 16-byte halves
-//     of pixel slot q are swapped when bit 3 of q is set, and the row pitch P obeys 2P = W_out (mod 16): every 16-lane group of a
-//     ds_read_b128 covers all 64 banks once, also across the row breaks of a 32-pixel tile.  The swizzle is applied on the DMA's
-//     source address (an LDS-DMA destination is lane-linear);
+//     LDS ONCE by LDS-DMA, double buffered, and feeds all 9 taps, in the stride-2 layout of conv_band.h (two column-parity planes per band
+//     row, swizzled halves, 2P = W_out (mod 16): conflict-free ds_read_b128, but for a 16-lane group that spans two images of a tile);
 //   * the waves split the output channels and nothing else, so no weight is shared between waves: weights never touch LDS.  They are
 //     packed at load time in MFMA-fragment order (s2_pack_weights) and each wave streams its own fragments L2 -> registers with
 //     coalesced 1-KB loads, three taps ahead;
@@ -24,7 +21,7 @@
 // 208 us in a bench step - a 16-channel chunk pass touches every 128-byte line of the band and uses 32 bytes of it, and with Cin = 64 the
 // bands in flight on an XCD (64 workgroups x 104 KB of lines) overflow its 4-MB L2 before the other three chunks come by.
 #include "common.h"
-#include "device_util.h"
+#include "conv_band.h"
 
 #define S2_THREADS 256
 #define S2_STAGE_PAD 8
@@ -91,135 +88,76 @@ __global__ __launch_bounds__(S2_THREADS, 2) void conv3x3_s2_kernel(ConvArgs p, c
   const int jb = HO - oy0;                                              // first local row that belongs to the next image (>= ROWS: none)
   const int nch = p.Cin >> 4;
 
-  // ---- band DMA: instruction u = wave + 4 v, lane l -> pixel slot q = 32 u + l/2, physical half l&1 = logical half ^ bit 3 of q ----
-  // band row b: b <= 2 jb -> input row 2 oy0 + b - 1 of image img0; b > 2 jb -> input row b - 2 jb - 2 of image img0 + 1 (-1: zero row)
-  unsigned src_off[DPW];                                                // byte offset of (pixel, logical half) in the input, chunk 0; ~0u: zeros
-#pragma unroll
-  for (int v = 0; v < DPW; ++v) {
-    const int q = (wave + 4 * v) * 32 + (lane >> 1), hl = (lane & 1) ^ ((q >> 3) & 1);
-    const int b = q / P, c = q - b * P;
-    const int ix = c < WO ? 2 * c : 2 * (c - WO) - 1;
-    const bool second = b > 2 * jb;
-    const int img = img0 + (second ? 1 : 0), iy = second ? b - 2 * jb - 2 : 2 * oy0 + b - 1;
-    const bool ok = b < C::BROWS && iy >= 0 && iy < HI && ix >= 0 && ix < WI && img < p.Nimg;
-    src_off[v] = ok ? (unsigned)((((img * HI + iy) * WI + ix) * p.Cin + hl * 8) * 2) : 0xffffffffu;
-  }
-  auto band_dma = [&](int ch, int buf) __attribute__((always_inline)) {
+  // ---- band DMA (conv_band.h): band row b <= 2 jb holds input row 2 oy0 + b - 1 of image img0; b > 2 jb row b - 2 jb - 2 of image img0 + 1 ----
+  unsigned src_off[DPW];                                                // byte offset of (pixel, logical half) in the input, chunk 0
+  band_dma_offsets(src_off, wave, lane, [&](int q, int hl) {
+    const BandSrc s = s2_band_src(P, WO, C::BROWS, oy0, jb, p.Nimg - img0, q);
+    return s.ok ? (unsigned)(((((img0 + s.img) * HI + s.iy) * WI + s.ix) * p.Cin + hl * 8) * 2) : BAND_ZERO;
+  });
+  // (written out here and in conv_s1b.hip: through a shared helper hipcc allocates this kernel's scalar registers differently)
+  auto dma = [&](int ch, int buf) __attribute__((always_inline)) {
 #pragma unroll
     for (int v = 0; v < DPW; ++v) {
-      const char *src = src_off[v] != 0xffffffffu ? (const char *)p.in + src_off[v] + ch * 32 : (const char *)zero_page;
+      const char *src = src_off[v] != BAND_ZERO ? (const char *)p.in + src_off[v] + ch * 32 : (const char *)zero_page;
       glds16(src, lds0 + buf * C::BAND_BYTES + (wave + 4 * v) * 1024);
     }
   };
 
-  // ---- B fragments: lane = output pixel 32 j + lr of the tile (local row jr, column ox), k half lh.  Tap (ky, kx) of that pixel is pixel
-  // slot qb[j] + ky P + {WO, 0, WO + 1}[kx] (odd plane slot WO + s = input column 2 s - 1, even plane slot s = column 2 s) ----
-  int qb[NPT];                                                          // byte address of (slot qb, half lh) before the swizzle
+  // ---- B fragments: lane = output pixel 32 j + lr of the tile (local row jr, column ox), k half lh ----
+  int qb[NPT];                                                          // byte address of (base slot, half lh) before the swizzle
 #pragma unroll
   for (int j = 0; j < NPT; ++j) {
     const int pl = 32 * j + lr, jr = pl / WO, ox = pl - jr * WO;
-    qb[j] = (((2 * jr + (jr >= jb ? 1 : 0)) * P + ox) << 5) | (lh << 4);
+    qb[j] = band_addr(s2_tile_row(jr, jb) * P + ox, lh);
   }
 
   // ---- A fragments: this wave's stream of 1-KB fragments, (chunk, tap, co tile) in order ----
-  const half8 *wp = reinterpret_cast<const half8 *>(wpk) + ((size_t)(cb * 4 + wave) * nch * 9 * CT) * 64 + lane;
-  half8 aq[3][CT];                                                      // ring: taps t, t+1, t+2
-  int f = 0;                                                            // next fragment group (tap) to fetch
-  auto a_fetch = [&](int slot) __attribute__((always_inline)) {
-#pragma unroll
-    for (int ct = 0; ct < CT; ++ct) aq[slot][ct] = wp[(size_t)(f * CT + ct) * 64];
-    ++f;
-  };
+  WeightRing<CT> ring{reinterpret_cast<const half8 *>(wpk) + ((size_t)(cb * 4 + wave) * nch * 9 * CT) * 64 + lane};
 
-  band_dma(0, 0);
+  dma(0, 0);
 #pragma unroll
-  for (int d = 0; d < 3; ++d) a_fetch(d);
+  for (int d = 0; d < 3; ++d) ring.fetch(d);
 
+  const int co0 = (cb * 4 + wave) * CT * 32;
   floatx16 acc[CT][NPT];
-  {
-    const int co0 = (cb * 4 + wave) * CT * 32;
-#pragma unroll
-    for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-      for (int rg = 0; rg < 4; ++rg) {
-        const float4 bv = *reinterpret_cast<const float4 *>(p.bias + co0 + ct * 32 + rg * 8 + lh * 4);
-#pragma unroll
-        for (int j = 0; j < NPT; ++j) {
-          acc[ct][j][rg * 4 + 0] = bv.x;
-          acc[ct][j][rg * 4 + 1] = bv.y;
-          acc[ct][j][rg * 4 + 2] = bv.z;
-          acc[ct][j][rg * 4 + 3] = bv.w;
-        }
-      }
-  }
-
+  acc_from_bias(acc, p.bias, co0, lh);
+  // conv_band.h's band_k_loop<9> written out: through the helper hipcc lays this kernel's chunk loop out differently and allocates other registers
   for (int ch = 0; ch < nch; ++ch) {
-    // this wave's part of chunk ch has landed (everything this wave has in flight: the three prefetched weight taps are needed next
-    // anyway); after the barrier every wave's part has, and every wave is done reading the other buffer (chunk ch - 1)
     wait_vm_lgkm<0>();
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
-    if (ch + 1 < nch) band_dma(ch + 1, (ch + 1) & 1);
+    if (ch + 1 < nch) dma(ch + 1, (ch + 1) & 1);
     const unsigned char *band = s2_smem + (ch & 1) * C::BAND_BYTES;
-    // B fragment (tap t, pixel tile j): read while the MFMAs of (tap t - 1, tiles j + 1 ..) run - its register is free once MFMA
-    // (t - 1, j) has issued - so a read has five MFMA pairs to land.  Only tap 0 of a chunk waits for its reads (the band is new).
-    auto b_read = [&](int t, int j) __attribute__((always_inline)) -> half8 {
-      const int ky = t / 3, kx = t - ky * 3;
-      int x = qb[j];
-      asm volatile("" : "+v"(x));                                       // keep the 45 tap addresses out of registers: three VALU ops per read instead
-      x += (ky * P + (kx == 1 ? 0 : WO + (kx == 2 ? 1 : 0))) << 5;
-      return *reinterpret_cast<const half8 *>(band + (x ^ ((x >> 4) & 16)));      // swap the halves when bit 3 of the slot (bit 8 of the address) is set
-    };
     half8 b[NPT];
 #pragma unroll
-    for (int j = 0; j < NPT; ++j) b[j] = b_read(0, j);
+    for (int j = 0; j < NPT; ++j) b[j] = band_read_s2<P, WO>(band, qb[j], 0);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int t = 0; t < 9; ++t) {
 #pragma unroll
       for (int j = 0; j < NPT; ++j) {
 #pragma unroll
-        for (int ct = 0; ct < CT; ++ct) acc[ct][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(aq[t % 3][ct], b[j], acc[ct][j], 0, 0, 0);
-        if (t < 8) b[j] = b_read(t + 1, j);
+        for (int ct = 0; ct < CT; ++ct) acc[ct][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ring.aq[t % 3][ct], b[j], acc[ct][j], 0, 0, 0);
+        if (t < 8) b[j] = band_read_s2<P, WO>(band, qb[j], t + 1);
         __builtin_amdgcn_sched_barrier(0);
       }
-      a_fetch(t % 3);                                                   // tap t + 3 (possibly of the next chunk; past the end: the padding of the packed image)
+      ring.fetch(t % 3);
       __builtin_amdgcn_sched_barrier(0);
     }
   }
-  wait_vm_lgkm<0>();          // the trailing weight prefetches
-  __builtin_amdgcn_s_barrier();                                         // every wave is done with the bands: staging may overwrite them
+  wait_vm_lgkm<0>();
+  __builtin_amdgcn_s_barrier();
   __builtin_amdgcn_sched_barrier(0);
 
   // ---- epilogue: ReLU, fp16, one 32-pixel tile at a time through this wave's staging rows, 16-byte NHWC stores ----
   f16 *stage = reinterpret_cast<f16 *>(s2_smem) + (size_t)wave * (32 * C::STAGE_LD);
-  const float lo = p.relu ? 0.f : -__builtin_inff();
   const size_t m0 = (size_t)g0 * WO;
-  const int co0 = (cb * 4 + wave) * CT * 32;
-  constexpr int LPP = CT * 4;                                           // lanes per pixel row (16 bytes each)
-  constexpr int PPI = 64 / LPP;                                         // pixels per store instruction
 #pragma unroll
-  for (int j = 0; j < NPT; ++j) {
-#pragma unroll
-    for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-      for (int rg = 0; rg < 4; ++rg) {
-        half4 hv;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) hv[e] = (f16)fmaxf(acc[ct][j][rg * 4 + e], lo);
-        *reinterpret_cast<half4 *>(&stage[lr * C::STAGE_LD + ct * 32 + rg * 8 + lh * 4]) = hv;
-      }
-    wait_lgkm();
-    uint4 v[32 / PPI];
-#pragma unroll
-    for (int u = 0; u < 32 / PPI; ++u) v[u] = *reinterpret_cast<const uint4 *>(&stage[(u * PPI + lane / LPP) * C::STAGE_LD + (lane % LPP) * 8]);
-#pragma unroll
-    for (int u = 0; u < 32 / PPI; ++u) {
-      const size_t m = m0 + 32 * j + u * PPI + lane / LPP;
-      if (m < (size_t)p.M) *reinterpret_cast<uint4 *>((f16 *)p.out + m * p.Cout + co0 + (lane % LPP) * 8) = v[u];
-    }
-    wait_lgkm();
-  }
+  for (int j = 0; j < NPT; ++j)
+    band_store_tile<C::STAGE_LD>(stage, acc, j, lane, lr, lh, ReluThenRound<>{p.relu ? 0.f : -__builtin_inff()}, [&](int px, int c16) {
+      const size_t m = m0 + 32 * j + px;
+      return BandDst{(f16 *)p.out + m * p.Cout + co0 + c16 * 8, m < (size_t)p.M};
+    });
 }
 
 size_t s2_packed_halfs(int Cout, int Cin) { return (size_t)Cout * 9 * Cin + 3 * 2 * 512; }    // + three taps of prefetch past the end

@@ -1,6 +1,7 @@
 // Device-side primitives shared by the gfx950 kernel files: LDS-DMA, counted waits, lane and workgroup reductions, the token-tile load and the
-// bias start of the token GEMM accumulators.  Device only; include after common.h.  Everything is __forceinline__: a kernel
-// that uses a helper from here compiles to the instructions it had with a private copy.
+// bias start of the MFMA accumulators (token GEMMs and the band convolutions; the band family's own pieces are in conv_band.h).  Device
+// only; include after common.h.  Everything is __forceinline__: a kernel that uses a helper from here compiles to the instructions it
+// had with a private copy.
 #pragma once
 #include "common.h"
 
@@ -125,24 +126,36 @@ __device__ __forceinline__ void tok_tile_dma(const f16 *src, int m0, int M, int 
     }
 }
 
-// Accumulators of a token GEMM start at the bias.  col0 is the first of the wave's NI * 32 output columns; acc[i][j] is the 32x32 MFMA
-// tile of columns col0 + i*32 .. +31 and tokens j*32 .. +31; lr = lane & 31, lh = lane >> 5.
+// Accumulators of a token GEMM or a convolution start at the bias.  col0 is the first of the wave's NI * 32 output columns; acc[i][j] is the
+// 32x32 MFMA tile of columns col0 + i*32 .. +31 and tokens (pixels) j*32 .. +31; lr = lane & 31, lh = lane >> 5.
 // Row layout: a lane owns one token and channels col0 + i*32 + rg*8 + lh*4 + (0..3) in register quad rg.
-template <int NI, int NJ>
-__device__ __forceinline__ void acc_from_bias(floatx16 (&acc)[NI][NJ], const float *bias, int col0, int lh) {
+template <int NI>
+__device__ __forceinline__ void bias_quads(float4 (&bq)[NI][4], const float *bias, int col0, int lh) {
 #pragma unroll
   for (int i = 0; i < NI; ++i)
 #pragma unroll
-    for (int rg = 0; rg < 4; ++rg) {
-      const float4 bv = *reinterpret_cast<const float4 *>(bias + col0 + i * 32 + rg * 8 + lh * 4);
+    for (int rg = 0; rg < 4; ++rg) bq[i][rg] = *reinterpret_cast<const float4 *>(bias + col0 + i * 32 + rg * 8 + lh * 4);
+}
+// ... from bias quads already in registers (the persistent kernels of stem.hip and front.hip hold them across their tile loops)
+template <int NI, int NJ>
+__device__ __forceinline__ void acc_from_bias(floatx16 (&acc)[NI][NJ], const float4 (&bq)[NI][4]) {
+#pragma unroll
+  for (int i = 0; i < NI; ++i)
+#pragma unroll
+    for (int rg = 0; rg < 4; ++rg)
 #pragma unroll
       for (int j = 0; j < NJ; ++j) {
-        acc[i][j][rg * 4 + 0] = bv.x;
-        acc[i][j][rg * 4 + 1] = bv.y;
-        acc[i][j][rg * 4 + 2] = bv.z;
-        acc[i][j][rg * 4 + 3] = bv.w;
+        acc[i][j][rg * 4 + 0] = bq[i][rg].x;
+        acc[i][j][rg * 4 + 1] = bq[i][rg].y;
+        acc[i][j][rg * 4 + 2] = bq[i][rg].z;
+        acc[i][j][rg * 4 + 3] = bq[i][rg].w;
       }
-    }
+}
+template <int NI, int NJ>
+__device__ __forceinline__ void acc_from_bias(floatx16 (&acc)[NI][NJ], const float *bias, int col0, int lh) {
+  float4 bq[NI][4];
+  bias_quads(bq, bias, col0, lh);
+  acc_from_bias(acc, bq);
 }
 // Swapped operands (the transposed V image): a lane owns ONE channel col0 + i*32 + lr and 4 consecutive tokens per register quad.
 template <int NI, int NJ>

@@ -13,14 +13,13 @@
 // 17 x 41 pixels of a0 (rows 2 oy0 - 1 .. + 16, columns 2 ox0 - 1 .. + 40; row / column -1 is the stride-2 layer's padding: zeros) and
 // 39 x 87 pixels of x.  The stem is recomputed for the halo: 17 x 41 / (16 x 40) = 1.09.  Per tile:
 //   1. the input region (39 rows x 89 columns, 16-byte pixels) is in LDS, brought by LDS-DMA; outside the image the source is the zero
-//      page.  A region row is two column-parity planes (45 even + 44 odd slots, pitch 93), as in stem.hip.
+//      page.  A region row is two column-parity planes (45 even + 44 odd slots, pitch 93): the region layout of conv_band.h.
 //   2. stem phase: the a0 tile as 23 pixel tiles of 32 (17 rows of 42 flattened; column 41 and the tail are computed and dropped) x 64
 //      couts; wave w owns cout tile w & 1 and pixel tiles (w >> 1) + 4 j, j < 6: 6 accumulator tiles, 150 MFMAs, one B read per MFMA and
 //      one weight fragment per k-step.  2 x pitch = 42 (mod 16): the 32 lanes of a B read cover 32 consecutive 16-byte slots (mod 16) also
 //      across a row break - conflict free.  The wave's 25 weight fragments stream L2 -> registers through a buffer descriptor
-//      (front_pack_stem's order), four k-steps ahead.  a0 -> LDS in the layout of conv_s2.hip: four 16-channel planes of 17 rows x 42 pixel
-//      slots x 32 bytes, a row = even-column plane (20) + odd-column plane (21), the 16-byte halves of a slot swapped when bit 3 of the slot
-//      is set; written 16 bytes per lane after a v_permlane32_swap of the two lane halves' channel quads.
+//      (front_pack_stem's order), four k-steps ahead.  a0 -> LDS in the stride-2 band layout of conv_band.h: four 16-channel planes of 17
+//      rows x 42 pixel slots x 32 bytes; written 16 bytes per lane after a v_permlane32_swap of the two lane halves' channel quads.
 //   3. the input region is dead: the NEXT tile's region streams into it (issued by waves 4 .. 7) while
 //   4. the stride-2 phase runs: wave w owns cout tile w & 3 and pixel tiles {0, 1, 2} (w < 4) or {3, 4}: a SIMD's two waves share one
 //      stream of 36 weight fragments (conv_s2.hip's packing with one cout tile per wave, read tap-major, eight k-steps ahead) and issue
@@ -30,7 +29,7 @@
 // LDS: 65536 (input region, 64 DMA instructions of 1 KB) + 91392 (a0 planes) = 156928 bytes.  243 VGPRs, no AGPRs, scratch 0
 // (-Rpass-analysis=kernel-resource-usage; 16 SGPRs live in VGPR lanes).
 #include "common.h"
-#include "device_util.h"
+#include "conv_band.h"
 
 #define FR_THREADS 512
 #define FR_TILES_PER_IMG 10
@@ -69,7 +68,7 @@ __global__ void front_pack_stem_kernel(const f16 *__restrict__ w, int Kpad, f16 
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= 50 * 512) return;
   const int e = idx & 7, lane = (idx >> 3) & 63, f = idx >> 9, s = f >> 1, i = f & 1;
-  out[idx] = w[(size_t)(i * 32 + (lane & 31)) * Kpad + (2 * s + (lane >> 5)) * 8 + e];
+  out[idx] = w[stem_frag_src(Kpad, i, s, lane) + e];
 }
 
 // One 1-KB weight fragment through a buffer descriptor: wave-uniform descriptor and fragment offset (scalar registers) + 16 bytes per
@@ -80,32 +79,18 @@ __device__ __forceinline__ half8 front_frag(__amdgpu_buffer_rsrc_t rsrc, int fra
 
 // The stride-2 phase of one wave: NJ pixel tiles from J0 on x cout tile cg.  `aq`: the first 8 weight fragments, already requested.
 template <int NJ, int J0>
-__device__ __forceinline__ void front_s2_mma(const FrontArgs &p, const unsigned char *a0s, __amdgpu_buffer_rsrc_t wp, half8 (&aq)[8], const float4 (&bias1)[4], floatx16 (&acc)[1][NJ],
+__device__ __forceinline__ void front_s2_mma(const FrontArgs &p, const unsigned char *a0s, __amdgpu_buffer_rsrc_t wp, half8 (&aq)[8], const float4 (&bias1)[1][4], floatx16 (&acc)[1][NJ],
                                              int cg, int lane) {
   const int lr = lane & 31, lh = lane >> 5;
-  int qb[NJ];                                                           // byte address of (slot, half lh) of tap (0, 1) before the swizzle
+  int qb[NJ];                                                           // byte address of (base slot, half lh) before the swizzle
 #pragma unroll
   for (int j = 0; j < NJ; ++j) {
     const int pl = 32 * (J0 + j) + lr, jr = pl / 20, ox = pl - jr * 20;
-    qb[j] = ((2 * jr * FR_A0_P + ox) << 5) | (lh << 4);
+    qb[j] = band_addr(s2_tile_row(jr, 8) * FR_A0_P + ox, lh);           // (8: a tile lies in one image)
   }
-#pragma unroll
-  for (int rg = 0; rg < 4; ++rg)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      acc[0][j][rg * 4 + 0] = bias1[rg].x;
-      acc[0][j][rg * 4 + 1] = bias1[rg].y;
-      acc[0][j][rg * 4 + 2] = bias1[rg].z;
-      acc[0][j][rg * 4 + 3] = bias1[rg].w;
-    }
-  // k-step k = tap * 4 + chunk: tap (ky, kx) of a pixel is slot qb + ky P + {20, 0, 21}[kx] of plane `chunk`
-  auto b_read = [&](int k, int j) __attribute__((always_inline)) -> half8 {
-    const int tap = k >> 2, q = k & 3, ky = tap / 3, kx = tap - ky * 3;
-    int x = qb[j];
-    asm volatile("" : "+v"(x));
-    x += (ky * FR_A0_P + (kx == 1 ? 0 : 20 + (kx == 2 ? 1 : 0))) << 5;
-    return *reinterpret_cast<const half8 *>(a0s + q * FR_A0_PLANE + (x ^ ((x >> 4) & 16)));
-  };
+  acc_from_bias(acc, bias1);
+  // k-step k = tap * 4 + chunk: plane `chunk` of the a0 tile
+  auto b_read = [&](int k, int j) __attribute__((always_inline)) -> half8 { return band_read_s2<FR_A0_P, 20>(a0s + (k & 3) * FR_A0_PLANE, qb[j], k >> 2); };
   half8 b[2][NJ];
 #pragma unroll
   for (int d = 0; d < 2; ++d)
@@ -133,27 +118,12 @@ template <int NJ, int J0>
 __device__ __forceinline__ void front_s2_store(const FrontArgs &p, f16 *stage, const floatx16 (&acc)[1][NJ], int cg, int lane, int img, int oy0, int ox0) {
   const int lr = lane & 31, lh = lane >> 5;
 #pragma unroll
-  for (int j = 0; j < NJ; ++j) {
-#pragma unroll
-    for (int rg = 0; rg < 4; ++rg) {
-      half4 hv;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) hv[e] = (f16)acc[0][j][rg * 4 + e];
-      hv = __builtin_elementwise_max(hv, half4{(f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f});
-      *reinterpret_cast<half4 *>(&stage[lr * FR_STAGE_LD + rg * 8 + lh * 4]) = hv;
-    }
-    wait_lgkm();
-    uint4 v[2];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) v[u] = *reinterpret_cast<const uint4 *>(&stage[(u * 16 + (lane >> 2)) * FR_STAGE_LD + (lane & 3) * 8]);
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const int pl = 32 * (J0 + j) + u * 16 + (lane >> 2), jr = pl / 20, ox = pl - jr * 20;
+  for (int j = 0; j < NJ; ++j)
+    band_store_tile<FR_STAGE_LD>(stage, acc, j, lane, lr, lh, RoundThenRelu{}, [&](int px, int c16) {
+      const int pl = 32 * (J0 + j) + px, jr = pl / 20, ox = pl - jr * 20;
       const size_t m = ((size_t)img * 40 + oy0 + jr) * 40 + ox0 + ox;
-      *reinterpret_cast<uint4 *>(p.a1 + m * 128 + cg * 32 + (lane & 3) * 8) = v[u];
-    }
-    wait_lgkm();
-  }
+      return BandDst{p.a1 + m * 128 + cg * 32 + c16 * 8};
+    });
 }
 
 __global__ __launch_bounds__(FR_THREADS, 1) void front_kernel(FrontArgs p) {
@@ -177,8 +147,7 @@ __global__ __launch_bounds__(FR_THREADS, 1) void front_kernel(FrontArgs p) {
     for (int v = 0; v < FR_IN_INSTR / 4; ++v) {
       const int u = (wave - 4) + 4 * v;
       const int slot = u * 64 + lv, r = slot / FR_IN_PITCH, q = slot - r * FR_IN_PITCH;
-      const int j = q < FR_IN_ODD ? 2 * q : 2 * (q - FR_IN_ODD) + 1;
-      const int iy = iyb + r, ix = ixb + j;
+      const int iy = iyb + r, ix = ixb + stem_slot_col(FR_IN_ODD, q);
       const bool ok = r < FR_IN_ROWS && q < FR_IN_COLS && iy >= 0 && iy < 160 && ix >= 0 && ix < 160;
       glds16(ok ? src_img + ((size_t)iy * 160 + ix) * 8 : p.zero_page, lds0 + u * 1024);
     }
@@ -192,9 +161,8 @@ __global__ __launch_bounds__(FR_THREADS, 1) void front_kernel(FrontArgs p) {
   const __amdgpu_buffer_rsrc_t wp2 = __builtin_amdgcn_make_buffer_rsrc((void *)(p.wpk + (size_t)(cg * 4 * 9) * 512), 0, 36 * 1024, 0x00020000);
   const __amdgpu_buffer_rsrc_t wst = __builtin_amdgcn_make_buffer_rsrc((void *)p.wst, 0, 50 * 1024, 0x00020000);
   f16 *stage = reinterpret_cast<f16 *>(a0s) + (size_t)wave * (32 * FR_STAGE_LD);
-  float4 bias0[4];
-#pragma unroll
-  for (int rg = 0; rg < 4; ++rg) bias0[rg] = *reinterpret_cast<const float4 *>(p.b0 + ci * 32 + rg * 8 + lh * 4);
+  float4 bias0[1][4];
+  bias_quads(bias0, p.b0, ci * 32, lh);
   half8 aw[4];                                               // stem weight ring: k-steps s .. s + 3 of this wave's cout tile
   auto aw_prologue = [&]() __attribute__((always_inline)) {
 #pragma unroll
@@ -216,16 +184,9 @@ __global__ __launch_bounds__(FR_THREADS, 1) void front_kernel(FrontArgs p) {
     const int img = tile / FR_TILES_PER_IMG, r10 = tile - img * FR_TILES_PER_IMG;
     const int oy0 = (r10 >> 1) * 8, ox0 = (r10 & 1) * 20;
 
-    floatx16 acc[6];
-#pragma unroll
-    for (int rg = 0; rg < 4; ++rg)
-#pragma unroll
-      for (int j = 0; j < 6; ++j) {
-        acc[j][rg * 4 + 0] = bias0[rg].x;
-        acc[j][rg * 4 + 1] = bias0[rg].y;
-        acc[j][rg * 4 + 2] = bias0[rg].z;
-        acc[j][rg * 4 + 3] = bias0[rg].w;
-      }
+    floatx16 acc0[1][6];
+    acc_from_bias(acc0, bias0);
+    floatx16(&acc)[6] = acc0[0];
     int lrv = lr, lhv = lh;                                  // opaque per tile: what is derived from them does not live in registers across the tile loop
     asm volatile("" : "+v"(lrv), "+v"(lhv));
     unsigned pix_off[6];
@@ -233,7 +194,7 @@ __global__ __launch_bounds__(FR_THREADS, 1) void front_kernel(FrontArgs p) {
     for (int j = 0; j < 6; ++j) {
       int row, col;
       (void)a0_pixel(j, lrv, &row, &col);
-      pix_off[j] = (unsigned)((2 * row * FR_IN_PITCH + col) * 16);
+      pix_off[j] = (unsigned)(stem_pixel_slot(FR_IN_PITCH, row, col) * 16);
     }
     // This tile's region has landed.  First tile: everything this wave has in flight.  Later tiles: the region's DMAs were issued in front
     // of the stride-2 phase's weight loads, which have been consumed (vector-memory operations retire in issue order); behind them are
@@ -247,9 +208,9 @@ __global__ __launch_bounds__(FR_THREADS, 1) void front_kernel(FrontArgs p) {
 
     // this lane half's tap of k-step s: tap 2 s, + the step to tap 2 s + 1 in the upper half (tap 49 = zero weights: any slot)
     const int lmask = -lhv;
-    auto tap_a = [](int t) { return ((t / 7) * FR_IN_PITCH + ((t % 7) & 1) * FR_IN_ODD + ((t % 7) >> 1)) * 16; };
+    auto tap_a = [](int s, int h) { return stem_tap_slots(FR_IN_PITCH, FR_IN_ODD, stem_step_tap(s, h)) * 16; };
     auto b_read = [&](int s, int j) __attribute__((always_inline)) -> half8 {
-      const int o0 = tap_a(2 * s), o1 = tap_a(min(2 * s + 1, 48));
+      const int o0 = tap_a(s, 0), o1 = tap_a(s, 1);
       return *reinterpret_cast<const half8 *>(fr_smem + (pix_off[j] + (unsigned)((o1 - o0) & lmask)) + o0);
     };
     half8 bf[6];
@@ -271,9 +232,9 @@ __global__ __launch_bounds__(FR_THREADS, 1) void front_kernel(FrontArgs p) {
     half8 aq[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) aq[k] = front_frag(wp2, (k & 3) * 9 + (k >> 2), lane * 16);
-    float4 bias1[4];                                         // ... and the bias its accumulators start at
+    float4 bias1[1][4];                                      // ... and the bias its accumulators start at
 #pragma unroll
-    for (int rg = 0; rg < 4; ++rg) bias1[rg] = *reinterpret_cast<const float4 *>(p.b1 + cg * 32 + rg * 8 + lh * 4);
+    for (int rg = 0; rg < 4; ++rg) bias1[0][rg] = *reinterpret_cast<const float4 *>(p.b1 + cg * 32 + rg * 8 + lh * 4); // (bias_quads written out: hipcc moves waits)
 
     // ---- a0 -> LDS planes: bias + ReLU + fp16 as stem7x7_kernel; zeros where the pixel is the stride-2 layer's padding ----
 #pragma unroll
@@ -282,10 +243,10 @@ __global__ __launch_bounds__(FR_THREADS, 1) void front_kernel(FrontArgs p) {
       const bool keep = a0_pixel(j, lrv, &row, &c);
       const int gy = 2 * oy0 - 1 + row, gx = 2 * ox0 - 1 + c;
       const bool inside = gy >= 0 && gx >= 0;
-      const int ps = row * FR_A0_P + ((c & 1) ? (c - 1) >> 1 : 20 + (c >> 1));      // a0 column 2 ox0 + g: even g -> slot g / 2, odd g -> 20 + (g + 1) / 2
+      const int ps = row * FR_A0_P + s2_col_slot(20, c - 1);                       // the slot conv_band.h's stride-2 read expects a0 column 2 ox0 - 1 + c in
       // a lane holds channels rg*8 + lh*4 .. +4 of its pixel: the half exchange of v_permlane32_swap leaves channels (2m)*8 .. +8 in lane
       // (lr, 0) and (2m+1)*8 .. +8 in lane (lr, 1) - the two 16-byte halves of the pixel's slot in plane ci*2 + m, one 16-byte write each
-      unsigned char *dst = a0s + ps * 32 + ((lh ^ ((ps >> 3) & 1)) << 4);
+      unsigned char *dst = a0s + band_swizzle(band_addr(ps, lh));
 #pragma unroll
       for (int m = 0; m < 2; ++m) {
         half4 h0, h1;

@@ -4,7 +4,7 @@
 // The implicit-GEMM kernel of conv.hip gathers every tap of every output pixel separately (one 16-byte pixel per lane and tap
 // through LDS-DMA: each input pixel is staged 12 times, 51 FLOP per staged byte) and is bound by that fill: 336 TF/s useful.
 // Here a 16 x 16 block of output pixels needs a 37 x 37 region of the (r,g,b,x,y,z,0,0) fp16 input = 22 KB, staged ONCE:
-//   * region rows in LDS as two column-parity planes (20 + 20 sixteen-byte slots): tap (ky,kx) of output column ox is slot
+//   * region rows in LDS as two column-parity planes (20 + 20 sixteen-byte slots; conv_band.h): tap (ky,kx) of output column ox is slot
 //     ox + (kx >> 1) of plane kx & 1 - the 16 columns of a lane group read 16 consecutive slots, the two output rows of a
 //     32-pixel MFMA tile sit 1280 B (= 5 x 256) apart: every ds_read_b128 lane group covers all 64 banks once;
 //   * one 16-byte input pixel IS one tap's k-slice (8 channels); a k-step of 16 = two taps, chosen per lane half: 25 steps;
@@ -14,12 +14,13 @@
 // Epilogue: accumulators start at the folded BN bias, ReLU, fp16, staged per wave, 16-byte NHWC stores (2 KB per output row
 // of a block).  The accumulation order of an output element (taps in order, 8 channels per tap) does not depend on the block.
 #include "common.h"
-#include "device_util.h"
+#include "conv_band.h"
 
 #define ST_THREADS 512
 // (ST_BLK = 16, the output block edge: conv_plan.h)
 #define ST_REG 37                         // input region edge: 2*16 + 5
 #define ST_ROW_SLOTS 40                   // 16-byte slots per region row: plane 0 (even columns) 20 + plane 1 (odd columns) 20
+#define ST_ODD 20                         // first slot of the odd-column plane
 #define ST_REGION_BYTES (ST_REG * ST_ROW_SLOTS * 16)      // 23680
 #define ST_REGION_INSTR ((ST_REG * ST_ROW_SLOTS + 63) / 64)   // 24 DMA instructions (the last one partly past the region)
 #define ST_REGION_ALLOC (ST_REGION_INSTR * 1024)              // 24576
@@ -37,28 +38,21 @@ __global__ __launch_bounds__(ST_THREADS, 1) void stem7x7_kernel(ConvArgs p, cons
   const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) void *)st_smem;
   unsigned char *wlds = st_smem;
 
-  // ---- weights -> LDS in fragment order: fragment f = i*25 + s, lane (lr, lh) = W[i*32 + lr][(2s + lh)*8 .. +8] ----
+  // ---- weights -> LDS in fragment order (conv_band.h): fragment f = i*25 + s ----
   for (int f = wave; f < 50; f += 8) {
     const int i = f / 25, s = f - i * 25;
-    glds16(p.w + (size_t)(i * 32 + lr) * p.Kpad + (2 * s + lh) * 8, lds0 + f * 1024);
+    glds16(p.w + stem_frag_src(p.Kpad, i, s, lane), lds0 + f * 1024);
   }
   float4 bias[2][4];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int rg = 0; rg < 4; ++rg) bias[i][rg] = *reinterpret_cast<const float4 *>(p.bias + i * 32 + rg * 8 + lh * 4);
+  bias_quads(bias, p.bias, 0, lh);
 
-  // ---- B fragments: lane = output pixel (row lr >> 4, column lr & 15) of a 2-row tile; tile jj of a block covers rows 2jj, 2jj+1
-  // of it.  Region slot of tap (ky,kx): (4 jj + 2 (lr>>4) + ky) * 40 + (kx & 1) * 20 + (lr & 15) + (kx >> 1).
-  const unsigned pix_off = (unsigned)(((2 * (lr >> 4)) * ST_ROW_SLOTS + (lr & 15)) * 16);
-  unsigned tap_off[25];                                      // this lane half's tap of every k-step (tap 49 = zero weights: any slot)
+  // ---- B fragments: lane = output pixel (row lr >> 4, column lr & 15) of a 2-row tile; tile jj of a block covers rows 2jj, 2jj+1 of it ----
+  const unsigned pix_off = (unsigned)(stem_pixel_slot(ST_ROW_SLOTS, lr >> 4, lr & 15) * 16);
+  unsigned tap_off[25];                                      // this lane half's tap of every k-step
 #pragma unroll
-  for (int s = 0; s < 25; ++s) {
-    const int t = min(2 * s + lh, 48), ky = t / 7, kx = t - ky * 7;
-    tap_off[s] = (unsigned)((ky * ST_ROW_SLOTS + (kx & 1) * 20 + (kx >> 1)) * 16);
-  }
+  for (int s = 0; s < 25; ++s) tap_off[s] = (unsigned)(stem_tap_slots(ST_ROW_SLOTS, ST_ODD, stem_step_tap(s, lh)) * 16);
 
-  // region of block `half` of pair `pr` -> LDS set `set`: slot q of region row r = input pixel (2 oy0 - 3 + r, 2 ox0 - 3 + 2 (q % 20) + q / 20);
+  // region of block `half` of pair `pr` -> LDS set `set`: slot q of region row r = input pixel (2 oy0 - 3 + r, 2 ox0 - 3 + column of slot q);
   // outside the image: zeros.  Exactly ST_REGION_INSTR / 4 = 6 DMA instructions per wave (the counted waits below rely on it).
   auto load_region = [&](int pr, int set) __attribute__((always_inline)) {
     const int blk = min(pr * 2 + half, n_blocks - 1);
@@ -69,7 +63,7 @@ __global__ __launch_bounds__(ST_THREADS, 1) void stem7x7_kernel(ConvArgs p, cons
     for (int v = 0; v < ST_REGION_INSTR / 4; ++v) {
       const int u = wq + 4 * v;
       const int slot = u * 64 + lane, r = slot / ST_ROW_SLOTS, q = slot - r * ST_ROW_SLOTS;
-      const int iy = 2 * oy0 - 3 + r, ix = 2 * ox0 - 3 + 2 * (q % 20) + q / 20;
+      const int iy = 2 * oy0 - 3 + r, ix = 2 * ox0 - 3 + stem_slot_col(ST_ODD, q);
       const bool ok = r < ST_REG && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
       glds16(ok ? src_img + ((size_t)iy * p.W + ix) * 8 : zero_page, lds0 + ST_W_BYTES + (set * 2 + half) * ST_REGION_ALLOC + u * 1024);
     }
@@ -99,17 +93,7 @@ __global__ __launch_bounds__(ST_THREADS, 1) void stem7x7_kernel(ConvArgs p, cons
     __builtin_amdgcn_sched_barrier(0);
 
     floatx16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int rg = 0; rg < 4; ++rg)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          acc[i][j][rg * 4 + 0] = bias[i][rg].x;
-          acc[i][j][rg * 4 + 1] = bias[i][rg].y;
-          acc[i][j][rg * 4 + 2] = bias[i][rg].z;
-          acc[i][j][rg * 4 + 3] = bias[i][rg].w;
-        }
+    acc_from_bias(acc, bias);
     const unsigned char *region = st_smem + ST_W_BYTES + (set * 2 + half) * ST_REGION_ALLOC;
     const unsigned char *rb = region + pix_off + (wq * 2) * (4 * ST_ROW_SLOTS * 16);       // tile jj = wq*2 + j
 #pragma unroll
@@ -129,6 +113,8 @@ __global__ __launch_bounds__(ST_THREADS, 1) void stem7x7_kernel(ConvArgs p, cons
     __builtin_amdgcn_sched_barrier(0);
 
     // ---- epilogue: ReLU, fp16, per-wave staging of one 32-pixel tile at a time (in this set's regions), 16-byte NHWC stores ----
+    // (conv_band.h's band_store_tile with ReluThenRound, written out: through the helper hipcc schedules this kernel's K loop, which no
+    // sched_barrier pins, with other waits and two more registers)
     f16 *stage = reinterpret_cast<f16 *>(st_smem + ST_W_BYTES + set * 2 * ST_REGION_ALLOC) + (size_t)wave * (32 * ST_STAGE_LD);
     const float lo = p.relu ? 0.f : -__builtin_inff();
 #pragma unroll
