@@ -21,6 +21,7 @@ from .stereo import stereo_depth, stereo_disparity  # noqa: F401  (depth from a 
 from .rectify import (distort_points, monotonic_r2_max, rectify_pair, rectify_stereo, remap_image, undistort_frame,  # noqa: F401
                       undistort_plan, undistort_points)      # raw stereo pairs and distorted cameras; a build extension
 from .reproject import align_frame, gather_by_source, reproject_depth, rgbd_rig  # noqa: F401  (depth and colour from two sensors; a build extension)
+from .detect import TemplateSet, build_templates, detect, match_templates, templates_from_depths  # noqa: F401  (objects without a mask; a build extension)
 from .pose_icp import align_poses_step, polish_poses, pose_gn_step  # noqa: F401  (polishing poses against depth; a build extension)
 from .vis import cv_draw_text, depth_to_vis, make_grid_image  # noqa: F401  (src/Utils.py:630-653, 456-478, 293-300)
 

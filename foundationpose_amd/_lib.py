@@ -174,6 +174,9 @@ class FpRemapDebug(Structure):
 FP_REPROJECT_MAX_VIEWS, FP_REPROJECT_MAX_SPLAT, FP_REPROJECT_MAX_FRAMES = 8, 8, 65535      # fp_depth_reproject
 
 
+FP_TEMPLATE_MAX_OBJECTS, FP_TEMPLATE_MAX_SAMPLES, FP_TEMPLATE_MAX_ANCHORS, FP_TEMPLATE_MAX_FRAMES = 64, 1024, 4, 65535      # fp_template_match
+
+
 class FpObjectBatch(Structure):
   _fields_ = [('mesh', c_void_p), ('d_rgb', c_void_p), ('d_geom', c_void_p), ('H', c_int), ('W', c_int), ('K', c_void_p),
               ('mesh_diameter', c_double), ('n', c_int)]
@@ -250,6 +253,9 @@ _PROTOS = {
                        c_void_p]),
   'fp_depth_reproject': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p,
                                  c_void_p, c_void_p]),
+  'fp_template_match': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                c_float, c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p]),
+  'fp_template_match_info': (c_int, [c_int, POINTER(c_int)]),
   'fp_texture_bake': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                               POINTER(FpTextureCfg), c_void_p, c_void_p, c_void_p, c_void_p]),
   'fp_point_mesh_distance': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),

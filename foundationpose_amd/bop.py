@@ -357,15 +357,42 @@ def build_estimators(models, obj_ids, refiner, scorer, diameter='info'):
   return out
 
 
-def image_instances(scene, im_id, targets, mask_source='gt_visib', models=None, pad='bop'):
+def detect_instances(scene, im_id, targets, estimators, delta=0.015, **detect_kw):
+  """[(obj_id, mask bool (H,W), det_score)] of an image without any ground truth: for every target the inst_count best detections of
+  its object's estimator (FoundationPose.detect on the recorded depth: templates of the model, geometry only) and, per detection, the
+  pixels the model shows at the detected pose in front of the recorded depth (Utils.scene_instances, mask_visib); det_score is the
+  match score as a fraction of n_in n_out.  What mask_source='detect' feeds image_instances."""
+  from . import Utils as U
+  depth, K = scene.depth(im_id), scene.K(im_id)
+  H, W = depth.shape[:2]
+  out = []
+  for t in targets:
+    est = estimators[t['obj_id']]
+    found = est.detect(depth, K, top_k=int(t['inst_count']), **detect_kw)
+    if not found:
+      continue
+    ts = est.templates()
+    masks = U.scene_instances(K, H, W, est.mesh_tensors, np.stack([d['ob_in_cam'] for d in found]), depth=depth, occluders='depth', delta=delta,
+                              want=('mask_visib',))['mask_visib'].cpu().numpy() > 0
+    out += [(t['obj_id'], m, d['score'] / float(ts.n_in * ts.n_out)) for d, m in zip(found, masks)]
+  return out
+
+
+def image_instances(scene, im_id, targets, mask_source='gt_visib', models=None, pad='bop', estimators=None):
   """The instances run_bop registers in one image, in order: [(obj_id, mask bool (H,W))].  targets: the image's targets.
   mask_source='gt_visib': for every target the `mask_visib` of the object's counted ground-truth instances (visib_fract >= 0.1), in
   gt_id order, inst_count at most; a callable (scene, im_id) -> [(obj_id, mask, det_score)]: the inst_count best-scored detections of
   the object.  An instance without a mask file, or with an empty mask, is left out.
   mask_source='gt_render' (needs `models`, a BopModels): as 'gt_visib', but an instance without a mask file gets the mask_visib that
   annotate_scene would write (Utils.scene_instances on the image's ground truth, the recorded depth as the occluder), and without
-  scene_gt_info.json the instances are counted by the computed visib_fract; `pad` as annotate_scene takes it."""
+  scene_gt_info.json the instances are counted by the computed visib_fract; `pad` as annotate_scene takes it.
+  mask_source='detect' (needs `estimators`, {obj_id: FoundationPose}): no ground truth is read; detect_instances finds the objects in
+  the recorded depth."""
   out = []
+  if mask_source == 'detect':
+    if estimators is None:
+      raise ValueError("mask_source='detect' needs estimators={obj_id: FoundationPose}")
+    mask_source = lambda sc, im: detect_instances(sc, im, targets, estimators)
   if callable(mask_source):
     dets = list(mask_source(scene, im_id))
     for t in targets:
@@ -373,7 +400,7 @@ def image_instances(scene, im_id, targets, mask_source='gt_visib', models=None, 
       out += [(t['obj_id'], np.asarray(d[1]) > 0) for d in mine if d[1] is not None and np.any(d[1])]
     return out
   if mask_source not in ('gt_visib', 'gt_render'):
-    raise ValueError(f"mask_source must be 'gt_visib', 'gt_render' or a callable, got {mask_source!r}")
+    raise ValueError(f"mask_source must be 'gt_visib', 'gt_render', 'detect' or a callable, got {mask_source!r}")
   gts, counted = scene.gt(im_id), scene.counted(im_id)
   rendered = None
   if mask_source == 'gt_render':
@@ -415,6 +442,8 @@ def run_bop(dataset_dir, split, models, refiner, scorer, targets=None, iteration
   (image_instances) are registered by MultiObjectTracker(...).register(rgb, depth, K, masks, iteration) in groups of at most
   max_objects (None: FP_TRACK_MAX_OBJECTS), the image handed over as the numpy arrays BopScene reads.  An instance with fewer than 4
   usable depth pixels in its mask gets register()'s fallback pose with score 0.  pad: the canvas of mask_source='gt_render'.
+  mask_source='detect' reads no ground truth at all: the masks come from detect_instances (templates of the models matched against the
+  recorded depth; geometry only, so expect far lower recall than with ground-truth masks).
   polish (False; True; or a dict of MultiObjectTracker.polish's arguments): the registered poses of a group are then moved onto the
   depth by geometry alone (fp_pose_polish), each against the normals of its own mask; the score stays the registration's.  Off, the
   rows are what they were before the option existed."""
@@ -433,7 +462,7 @@ def run_bop(dataset_dir, split, models, refiner, scorer, targets=None, iteration
     if scene_id not in scenes:
       scenes[scene_id] = BopScene(dirs[scene_id])
     scene = scenes[scene_id]
-    inst = image_instances(scene, im_id, ts, mask_source, models=models, pad=pad)
+    inst = image_instances(scene, im_id, ts, mask_source, models=models, pad=pad, estimators=estimators)
     if not inst:
       continue
     rgb, depth, K = scene.color(im_id), scene.depth(im_id), scene.K(im_id)

@@ -217,6 +217,11 @@ int fp_remap_check(const void *ctx, const void *d_src0, const void *d_src1, int 
 int fp_depth_reproject_check(const void *ctx, const void *d_depth, int n, int V, int Hs, int Ws, const double *Ks, const double *T_dst_src,
                              const double *K_dst, int Hd, int Wd, float zfar, const void *d_keys, const void *d_depth_out);
 
+// detect.hip: every check of a value of fp_template_match, which needs no device
+int fp_template_match_check(const void *ctx, const void *d_depth, int n_frames, int H, int W, const double *K, const void *d_table,
+                            const int32_t *ranges, int n_obj, int n_in, int n_out, int anchors, int stride, int r0, int c0, float z_min, float z_max,
+                            float zfar, float tol_in, float tol_out, const void *d_keys);
+
 int fp_arena_ensure(fp_ctx *ctx, size_t bytes);
 size_t fp_arena_bytes_for(int n_hyp);     // whole refine/score pass (outer buffers + network)
 size_t fp_arena_inner_bytes(int n_hyp);   // network forward only

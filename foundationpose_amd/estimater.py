@@ -104,6 +104,7 @@ class FoundationPose:
     self.symmetry_tfs = sym.to(device='cuda', dtype=torch.float)
     # tracking workspaces (and their captured graphs) hold the previous object's mesh handle and centre: none survives a new object
     self._track_ws = {}
+    self._templates = None          # the cached TemplateSet of detect: (build keywords, set)
     logging.info("reset done")
 
   def instance(self):
@@ -187,14 +188,17 @@ class FoundationPose:
     return U.pose_errors(poses, gt_c, self.mesh.vertices, symmetry_tfs=self.symmetry_tfs, metrics=('add_sym',))['add_sym']
 
   # ------------------------------------------------------------------ hot path
-  def _refine_and_score(self, K, rgb, depth, xyz_map, hyp, iteration):
+  def _refine_and_score(self, K, rgb, depth, xyz_map, hyp, iteration, shared_translation=True):
     if self.dist_group is not None:
+      if not shared_translation:
+        raise NotImplementedError('hypotheses around several centres are not sharded over ranks: give register_at one centre per call')
       from .dist import sharded_refine_and_score
       return sharded_refine_and_score(self, K, rgb, depth, xyz_map, hyp, iteration)
     shared = dict(mesh=self.mesh, mesh_tensors=self.mesh_tensors, rgb=rgb, depth=depth, K=K, glctx=self.glctx,
                   mesh_diameter=self.diameter, get_vis=self.debug >= 2)
     # (register's hypotheses are the rotation grid around ONE guessed centre: the refiner encodes the observed crop of its first iteration once)
-    refined, vis = self.refiner.predict(ob_in_cams=hyp, xyz_map=xyz_map, normal_map=None, iteration=iteration, shared_translation=True, **shared)
+    refined, vis = self.refiner.predict(ob_in_cams=hyp, xyz_map=xyz_map, normal_map=None, iteration=iteration, shared_translation=shared_translation,
+                                        **shared)
     if vis is not None:                  # src/estimater.py:216-217 (debug >= 2)
       from .vis import write_png
       write_png(f'{self.debug_dir}/vis_refiner.png', vis)
@@ -223,15 +227,78 @@ class FoundationPose:
     self.H, self.W = depth.shape[:2]
     self.K, self.ob_id, self.ob_mask = K, ob_id, ob_mask
     hyp = self.generate_random_pose_hypo(K=K, rgb=rgb, depth=depth, mask=ob_mask, stats=stats)
+    return self._register_hypotheses(K, rgb, depth, hyp, iteration, True)
+
+  def _register_hypotheses(self, K, rgb, depth, hyp, iteration, shared_translation):
+    """The second half of register and register_at: refine and score `hyp` against the filtered device depth, rank, keep."""
     # the colour image goes up once, in its own dtype (uint8: 0.9 MB), and is widened on the device; refiner and scorer
     # both read that tensor
     rgb = torch.as_tensor(np.ascontiguousarray(rgb) if isinstance(rgb, np.ndarray) else rgb, device='cuda').to(torch.float)
-    refined, scores = self._refine_and_score(K, rgb, depth, U.depth2xyzmap(depth, K), hyp, iteration)
+    refined, scores = self._refine_and_score(K, rgb, depth, U.depth2xyzmap(depth, K), hyp, iteration, shared_translation)
     order = torch.as_tensor(scores).argsort(descending=True)
     self.poses, self.scores = refined[order], scores[order]
     self.best_id = order[0]
     self.pose_last = self.poses[0]
     return (self.pose_last @ self.get_tf_to_centered_mesh()).data.cpu().numpy()
+
+  # ------------------------------------------------------------------ finding the object without a mask (a build extension)
+  def _prelude(self, depth):
+    """register's depth prelude: the frame on the device, eroded and bilateral-filtered."""
+    depth = torch.as_tensor(np.ascontiguousarray(depth) if isinstance(depth, np.ndarray) else depth, dtype=torch.float, device='cuda')
+    return U.bilateral_filter_depth(U.erode_depth(depth, radius=2, device='cuda'), radius=2, device='cuda')
+
+  def templates(self, **build_kw):
+    """The object's TemplateSet (Utils.build_templates on the centred mesh with this object's diameter), built at the first call and kept
+    until reset_object or other build keywords."""
+    key = tuple(sorted(build_kw.items()))
+    if self._templates is None or self._templates[0] != key:
+      if self.glctx is None:
+        self.glctx = U.RasterizeContext()
+      self._templates = (key, U.build_templates(mesh_tensors=self.mesh_tensors, diameter=self.diameter, glctx=self.glctx, **build_kw))
+    return self._templates[1]
+
+  def detect(self, depth, K, top_k=4, **kw):
+    """Where the object may be in a depth frame, without a mask (Utils.detect; geometry only - see its limits): up to top_k records, the
+    best first, each with `ob_in_cam` (4,4) float64 = [R_t | centre], a pose of the CENTRED mesh as self.poses holds them, `pose`, the same
+    for the original mesh as register returns it, `centre`, the pass fractions, the anchor pixel and the template index.  The frame goes
+    through register's prelude (erode + bilateral).  Keywords of Utils.build_templates (n_views, inplane_step, n_in, n_out, anchors,
+    margin_px, render_size, z0) go to the cached template set, the others to Utils.detect."""
+    build = {k: kw.pop(k) for k in ('n_views', 'inplane_step', 'n_in', 'n_out', 'anchors', 'margin_px', 'render_size', 'z0') if k in kw}
+    found = U.detect(self._prelude(depth), K, self.templates(**build), top_k=top_k, **kw)
+    to_mesh = self.get_tf_to_centered_mesh().double().cpu().numpy()
+    for rec in found:
+      rec['pose'] = rec['ob_in_cam'] @ to_mesh
+    return found
+
+  def register_at(self, K, rgb, depth, centres, iteration=5):
+    """register with the translation(s) given instead of guessed from a mask: centres (3,) or (n,3), metres, camera frame, of the CENTRED
+    mesh's origin (what detect calls `centre`, what guess_translation returns).  The hypotheses are the rotation grid at each centre; one
+    refine + score pass runs over all of them and the best is kept, with self.poses / self.scores / self.best_id as register leaves them.
+    With the centre register guesses it returns register's bits."""
+    U.set_seed(0)
+    if self.glctx is None:
+      self.glctx = U.RasterizeContext()
+    centres = np.asarray(centres, dtype=np.float64).reshape(-1, 3)
+    if len(centres) < 1 or not np.isfinite(centres).all():
+      raise ValueError('register_at needs at least one finite centre')
+    depth = self._prelude(depth)
+    self.H, self.W = depth.shape[:2]
+    self.K, self.ob_id, self.ob_mask = K, None, None
+    hyps = []
+    for c in centres:
+      hyp = self.rot_grid.clone()
+      hyp[:, :3, 3] = torch.as_tensor(c, device='cuda', dtype=torch.float).reshape(1, 3)
+      hyps.append(hyp)
+    return self._register_hypotheses(K, rgb, depth, hyps[0] if len(hyps) == 1 else torch.cat(hyps, 0), iteration, len(hyps) == 1)
+
+  def register_detected(self, K, rgb, depth, top_k=4, iteration=5, **detect_kw):
+    """register without a mask: detect, then register_at over the centres found - several, because clutter can score close to the
+    object and the trained scorer, not the detector, makes the final choice.  self.detections keeps detect's records.  Raises
+    RuntimeError when nothing is found (no depth in range)."""
+    self.detections = self.detect(depth, K, top_k=top_k, **detect_kw)
+    if not self.detections:
+      raise RuntimeError('register_detected: no candidate in the frame (no depth inside z_range, or min_score too high)')
+    return self.register_at(K, rgb, depth, [rec['centre'] for rec in self.detections], iteration=iteration)
 
   def polish(self, depth, K, mask=None, poses=None, **kw):
     """Move a pose onto the measured depth by geometry alone (Utils.polish_poses, a build extension; off unless called): point-to-plane

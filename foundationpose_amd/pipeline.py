@@ -18,6 +18,8 @@ class PipelineData:
     self.rgb = self.depth = self.mask = self.K = None
     self.right = None         # the right image of a stereo pair (StereoRectify, StereoDepth), rgb being the left one
     self.baseline = None      # metres, set by StereoRectify for a StereoDepth(baseline=None) behind it
+    self.lost = False         # set by the caller when the track is lost: Detect then looks for the object again
+    self.detections = None    # Utils.detect's records of the frame, left by Detect
     self.pose = None          # 4x4 ob_in_cam of the original (un-centred) mesh
     self.pose_6d = None       # (x, y, z, roll, pitch, yaw)
     self.errors = []
@@ -166,6 +168,45 @@ class AlignDepth(Processor):
     from .reproject import align_frame
     data.rgb, data.depth = align_frame(data.rgb, data.depth, self.rig, zfar=self.zfar)
     data.K = self.rig.K.copy()
+    return data
+
+
+class Detect(Processor):
+  """Fills `data.mask` when there is none, from the depth image and the model alone (Utils.detect: depth templates of the model matched
+  against the whole frame; geometry only - see foundationpose_amd/detect.py for the limits): the stage in front of FoundationPoseEstimator
+  on a stream that nobody paints a mask for.  It acts on the first frame it sees without a mask and afterwards only on frames with
+  `data.lost` set (a mask makes FoundationPoseEstimator register again), and leaves `data.detections` = Utils.detect's records; the mask
+  is what the model shows at the best record's pose in front of the frame's depth (Utils.scene_instances).  A frame without a candidate
+  keeps `data.mask` None.  Keywords of Utils.build_templates go to the template set (built at the first use), the others to Utils.detect."""
+
+  def __init__(self, mesh_file=None, mesh=None, K=None, intrinsics_file=None, delta=0.015, **kw):
+    from .mesh_io import load_intrinsics, load_obj
+    self.mesh = load_obj(mesh_file) if mesh is None else mesh
+    self.K = np.asarray(K, dtype=np.float64) if K is not None else (load_intrinsics(intrinsics_file) if intrinsics_file else None)
+    self._build = {k: kw.pop(k) for k in ('n_views', 'inplane_step', 'n_in', 'n_out', 'anchors', 'margin_px', 'render_size', 'z0') if k in kw}
+    self._kw, self.delta = kw, delta
+    self.templates = self.mesh_tensors = None
+    self._seen = False
+
+  def process(self, data):
+    from . import Utils as U
+    if data.mask is not None or (self._seen and not getattr(data, 'lost', False)):
+      return data
+    self._seen = True
+    if self.templates is None:
+      centred = self.mesh.copy()
+      centred.vertices = centred.vertices - (self.mesh.vertices.min(axis=0) + self.mesh.vertices.max(axis=0)) / 2      # as FoundationPose.reset_object
+      self.mesh_tensors = U.make_mesh_tensors(centred)
+      self.templates = U.build_templates(mesh_tensors=self.mesh_tensors, **self._build)
+    K = self.K if data.K is None else np.asarray(data.K, dtype=np.float64)
+    depth = np.ascontiguousarray(data.depth, dtype=np.float32)
+    filtered = U.bilateral_filter_depth(U.erode_depth(depth, radius=2, device='cuda'), radius=2, device='cuda')      # register's prelude
+    data.detections = U.detect(filtered, K, self.templates, **self._kw)
+    if data.detections:
+      H, W = depth.shape
+      visib = U.scene_instances(K, H, W, self.mesh_tensors, data.detections[0]['ob_in_cam'][None], depth=depth, occluders='depth', delta=self.delta,
+                                want=('mask_visib',))['mask_visib']
+      data.mask = visib[0].cpu().numpy() > 0
     return data
 
 

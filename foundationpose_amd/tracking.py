@@ -338,6 +338,37 @@ class MultiObjectTracker:
     self.segments = dict(stats=stats, cost=cost)
     return label_image, labels
 
+  def detect(self, depth, K, delta=0.015, **kw):
+    """Masks for `register` from the depth image and the models alone, with nothing said about the scene (Utils.detect; geometry only -
+    see its limits): (detections, masks).  ONE match call runs over the concatenated template sets of all objects
+    (FoundationPose.templates, built once per object); detections[o] is object o's best record - ob_in_cam of the CENTRED mesh, centre,
+    pass fractions, anchor pixel, template - or None when the frame holds no candidate for it, and masks[o] the (H,W) uint8 DEVICE tensor
+    (0 / 255) of the pixels the object shows at that pose in front of the frame's depth (Utils.scene_instances, mask_visib with the depth
+    image and the other detections as occluders), all zero without a detection.  `tracker.register(rgb, depth, K, masks)` follows
+    unchanged.  Two instances of one model get the same detection: give them apart by hand.  Keywords of Utils.build_templates go to the
+    sets, the others to Utils.detect.  Also leaves `self.detections` = detections."""
+    from . import Utils as U
+    from .detect import TemplateSet
+    ests = self.estimators
+    build = {k: kw.pop(k) for k in ('n_views', 'inplane_step', 'n_in', 'n_out', 'anchors', 'margin_px', 'render_size', 'z0') if k in kw}
+    dev = ests[0].mesh_tensors['pos'].device
+    raw = torch.as_tensor(np.ascontiguousarray(depth) if isinstance(depth, np.ndarray) else depth, dtype=torch.float, device=dev)
+    if raw.dim() != 2:
+      raise ValueError(f'MultiObjectTracker.detect: depth must be one (H,W) image, got {tuple(raw.shape)}')
+    H, W = (int(x) for x in raw.shape)
+    sets = TemplateSet.concat([e.templates(**build) for e in ests])
+    found = U.detect(ests[0]._prelude(raw), K, sets, top_k=1, **kw)
+    found = [found] if len(ests) == 1 else found
+    self.detections = [f[0] if f else None for f in found]
+    masks = [torch.zeros((H, W), dtype=torch.uint8, device=dev) for _ in ests]
+    have = [o for o, d in enumerate(self.detections) if d is not None]
+    if have:
+      out = U.scene_instances(K, H, W, [ests[o].mesh_tensors for o in have], np.stack([self.detections[o]['ob_in_cam'] for o in have]), depth=raw,
+                              occluders='both', delta=delta, want=('mask_visib',), glctx=ests[0].refiner.ctx)
+      for k, o in enumerate(have):
+        masks[o] = out['mask_visib'][k]
+    return self.detections, masks
+
   def instance_masks(self, depth=None, K=None, occluders=None, delta=0.015):
     """Which pixels every object covers at its current pose, after `register` / `track`: dict(owner (H,W) int32 device tensor, the
     object in front at the pixel, -1 = none; mask_visib (n_obj,H,W) uint8 0 / 255; visib_fract (n_obj,) float64 numpy, the visible

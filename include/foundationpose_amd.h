@@ -1142,6 +1142,52 @@ int fp_remap(fp_ctx *ctx, const void *d_src0, const void *d_src1, int n, const f
 int fp_depth_reproject(fp_ctx *ctx, const float *d_depth, int n, int V, int Hs, int Ws, const double *Ks, const double *T_dst_src, const double *K_dst,
                        int Hd, int Wd, float zfar, uint64_t *d_keys, float *d_depth_out, int32_t *d_source, void *stream);
 
+/* ---- finding an object in a depth frame without a mask: depth templates of the model matched at every pixel of an anchor lattice
+ *      (csrc/detect.hip).  What register() needs in place of a mask is a centre (x, y, z); this gives a few, each with a rough rotation.
+ *      The reference has nothing in this place (a person paints the mask); the rule is the library's own and
+ *      tests/detect_oracle.py restates all of it in numpy.  Geometry only, nothing learned.
+ *      d_depth (n_frames, H, W) fp32 metres.  K: host double 3x3; fx, fy, cx, cy are rounded to fp32 once (pinhole_of of csrc/view_geom.h).
+ *      d_table (T, n_in + n_out, 4) fp32, 16-byte aligned: per template its n_in in-samples, then its n_out out-samples, each the offset
+ *      (x, y, z, 0) in metres, camera axes, of a point from the object's centre: in-samples lie on the model's surface inside the
+ *      silhouette, out-samples just outside the silhouette at the depth of its rim; the first `anchors` in-samples are the anchors
+ *      (foundationpose_amd/detect.py builds the table).  ranges: host int32 (n_obj + 1), ranges[0] = 0, ascending: object o owns the
+ *      templates ranges[o] .. ranges[o + 1] - 1, T = ranges[n_obj].
+ *      The anchor lattice: pixel (r, c) = (r0 + i stride, c0 + j stride), i < Hs = ceil((H - r0) / stride), j < Ws = ceil((W - c0) / stride).
+ *      The rule, fp32, each operation rounded once, in this order, / correctly rounded, every comparison written so that a NaN fails it.
+ *      Per frame, object, anchor pixel (r, c), template t of the object's range (t_local = t - ranges[o]) and anchor a < anchors:
+ *        d = D[r, c];                 no candidate unless d >= 0.001 and d < zfar
+ *        A = in-sample a of t;        zc = d - A.z;      no candidate unless z_min <= zc and zc <= z_max
+ *        Cx = ((((float)c - cx) / fx) * d) - A.x;        Cy = ((((float)r - cy) / fy) * d) - A.y
+ *        per sample S:  X = Cx + S.x, Y = Cy + S.y, Z = zc + S.z;      the sample fails unless Z >= 0.001
+ *                       u = (fx X) / Z + cx, v = (fy Y) / Z + cy;  cf = floorf(u + 0.5f), rf = floorf(v + 0.5f)      (project_icp)
+ *                       the sample fails unless 0 <= cf <= W - 1 and 0 <= rf <= H - 1, compared as floats;      o = D[rf, cf]
+ *           an in-sample passes when   o >= 0.001 and |o - Z| <= tol_in
+ *           an out-sample passes when  not (o >= 0.001), or |o - Z| > tol_out      (no reading, or a depth step at the silhouette)
+ *        score = n_in_pass * n_out_pass      the product: a plane fits every in-sample and no out-sample, free space the reverse
+ *        key   = (score << 16) | (0xFFFF - (4 t_local + a))
+ *      d_keys (n_frames, n_obj, Hs, Ws) uint32: the maximum key over the object's candidates at that anchor pixel - among equal scores
+ *      the lowest (t, a) -, 0 where there is no candidate.  d_counts, optional, same shape: n_in_pass << 16 | n_out_pass of the winner, 0
+ *      where there is none.  The centre of a candidate is (Cx, Cy, zc); foundationpose_amd/detect.py recomputes it in double.
+ *      One thread owns an anchor pixel and carries the maximum in a register: no atomics, no allocation, no synchronisation, one launch
+ *      that can be captured into a graph; a frame's map has the same bits in any batch and on every run.  Candidates that can no longer
+ *      reach the maximum are left early; that prune is exact.  n_frames = 0 does nothing; T = 0 zeroes the maps.
+ *      FP_EINVAL, each checked before ctx is looked into: a null ctx, d_depth, K, d_table, ranges or d_keys; n_frames outside 0 ..
+ *      FP_TEMPLATE_MAX_FRAMES; H or W < 1 or > FP_REMAP_MAX_SIDE; stride < 1; r0 outside 0 .. H - 1 or c0 outside 0 .. W - 1; tol_in or
+ *      tol_out not > 0; z_min > z_max (or a NaN); zfar not > 0; an entry of K that is not finite, fx or fy not > 0; n_in or n_out < 1,
+ *      n_in n_out > 65535, n_in + n_out > FP_TEMPLATE_MAX_SAMPLES; anchors outside 1 .. FP_TEMPLATE_MAX_ANCHORS or > n_in; n_obj outside
+ *      1 .. FP_TEMPLATE_MAX_OBJECTS; ranges[0] != 0, descending ranges, an object with more than 16384 templates (4 T <= 65536); d_table
+ *      not 16-byte aligned.
+ *      fp_template_match_info: *chunk_templates = the number of templates of n_samples = n_in + n_out samples each that the kernel stages
+ *      at once (a host function; the tests put template counts around its multiples). */
+#define FP_TEMPLATE_MAX_OBJECTS 64
+#define FP_TEMPLATE_MAX_SAMPLES 1024
+#define FP_TEMPLATE_MAX_ANCHORS 4
+#define FP_TEMPLATE_MAX_FRAMES 65535
+int fp_template_match(fp_ctx *ctx, const float *d_depth, int n_frames, int H, int W, const double *K, const float *d_table, const int32_t *ranges,
+                      int n_obj, int n_in, int n_out, int anchors, int stride, int r0, int c0, float z_min, float z_max, float zfar, float tol_in,
+                      float tol_out, uint32_t *d_keys, uint32_t *d_counts, void *stream);
+int fp_template_match_info(int n_samples, int *chunk_templates);
+
 /* ---- texture baking: the colours of posed RGB-D reference views gathered into a per-face texture atlas of a mesh - the last stage of
  *      the model-free set-up, after the simplification (fp_mesh_simplify_* refuses textured meshes: simplify first, then bake).  The
  *      reference does this in mesh_texture_from_train_images (bundlesdf/nerf_runner.py:1122) with a UV parametrisation and the equal
