@@ -14,6 +14,7 @@
 // The convolutions: ConvArgs, the plan that picks the kernel form of a launch and every shape predicate are in conv_plan.h; the schedule of a
 // network pass and the forms of its other stages in pass_plan.h
 #include "pass_plan.h"
+#include "raster_tri.h"         // the rasteriser's integer rules, LDS / scratch layouts and RenderPlan
 
 #ifndef FP_F16_TYPEDEF
 #define FP_F16_TYPEDEF
@@ -503,13 +504,6 @@ struct RenderArgs {
   float light_color[3] = {1.f, 1.f, 1.f};
   int has_proj = 0;                     // 1: proj replaces projection_matrix_from_intrinsics(K, H, W, 0.001, 100)
   double proj[16] = {0};
-};
-struct RenderPlan {
-  int S, strip_rows, lds_verts;         // strips per hypothesis, rows per strip, whether the triangle pass keeps the vertex records in LDS
-  int G, Fg;                            // face ranges per hypothesis in the classification, faces per range
-  size_t lds_bytes, a_lds, c_bytes, b_bytes, a_bytes, count_bytes, list_bytes, total;
-  int solo;                             // one or two hypotheses: the whole render in the strip kernel's launch (raster.hip: render_kernel<.., true>)
-  size_t solo_lds;
 };
 RenderPlan render_plan(int N, int V, int F, int Ho, int Wo, int num_cu);
 // A render of N hypotheses goes out in sub-batches of render_chunk(...) when the worst-case scratch of all N at once (two face lists of

@@ -28,17 +28,14 @@
 //   written as one coalesced 16-byte store per pixel.
 // Triangles that straddle the camera plane are rasterised in homogeneous coordinates (below).
 // The arithmetic is mirrored 1:1 by oracle/raster_c.c.
+// raster_tri.h holds the rules the host and the kernels share, with the LDS layout of a strip workgroup, the scratch layout and the plan (render_plan,
+// render_chunk, the strip limits), and is checked on the CPU (tests/test_raster_tri_host.py); its head comment lists who calls what, and
+// render_kernel says which rules stay written out and why.  Here: the vertex transform and records, the two classification forms, the strip kernel, the
+// launches and the FP_RENDER_* knobs (raster_knobs), the crop-window kernels.
 #include "common.h"
 #include "pose_math.h"
 #include <cstdlib>
 #include <type_traits>
-
-#define RB_THREADS 1024
-
-__device__ __forceinline__ unsigned ordered_key(float z) {
-  unsigned b = __float_as_uint(z);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
 
 struct Vtx {
   int X, Y;
@@ -173,7 +170,12 @@ __device__ void clip_matrix(const RenderArgs &a, int b, const float *pose, float
 //               and bits of w;
 //   B (2 x float4): camera-space position (pts_cam, src/Utils.py:168) and the vertex' Lambert term (src/Utils.py:200-206) - the
 //               expressions the per-pixel resolve evaluated until round 3, moved here verbatim -, then colour and w.
-#define RB_A_NONE 0x7fff7fffu
+// camera-space normal of a model-space one; R: the pose's rotation, row-major
+__device__ __forceinline__ void normal_to_cam(const float *R, float nx, float ny, float nz, float *nc) {
+  nc[0] = fmaf(R[0], nx, fmaf(R[1], ny, R[2] * nz));
+  nc[1] = fmaf(R[3], nx, fmaf(R[4], ny, R[5] * nz));
+  nc[2] = fmaf(R[6], nx, fmaf(R[7], ny, R[8] * nz));
+}
 struct VtxRecords {
   int4 c;
   uint2 a;
@@ -191,10 +193,8 @@ __device__ __forceinline__ VtxRecords vertex_records(const RenderArgs &a, const 
   pc[0] = fmaf(P0, px, fmaf(P1, py, fmaf(P2, pz, P3)));
   pc[1] = fmaf(P4, px, fmaf(P5, py, fmaf(P6, pz, P7)));
   pc[2] = fmaf(P8, px, fmaf(P9, py, fmaf(P10, pz, P11)));
-  const float nx = m.vnormals[v * 3], ny = m.vnormals[v * 3 + 1], nz = m.vnormals[v * 3 + 2];
-  nc[0] = fmaf(P0, nx, fmaf(P1, ny, P2 * nz));
-  nc[1] = fmaf(P4, nx, fmaf(P5, ny, P6 * nz));
-  nc[2] = fmaf(P8, nx, fmaf(P9, ny, P10 * nz));
+  const float R[9] = {P0, P1, P2, P4, P5, P6, P8, P9, P10};
+  normal_to_cam(R, m.vnormals[v * 3], m.vnormals[v * 3 + 1], m.vnormals[v * 3 + 2], nc);
   float nn = sqrtf(fmaf(nc[0], nc[0], fmaf(nc[1], nc[1], nc[2] * nc[2])));
   nn = nn > 1e-12f ? nn : 1e-12f;
   float dv;
@@ -211,10 +211,10 @@ __device__ __forceinline__ VtxRecords vertex_records(const RenderArgs &a, const 
   }
   VtxRecords r;
   r.c = make_int4(o.ok ? o.X : (int)0x80000000, o.Y, __float_as_int(o.zn), __float_as_int(o.w));
-  const bool small = o.ok && abs(o.X) < 16384 && abs(o.Y) < 16384;
+  const bool small = o.ok && rt_a_describable(o.X, o.Y);
   // (where A cannot describe the vertex its second word carries w instead of z/w: the classification drops faces whose three
   // vertices are all on or behind the camera plane - a drifted tracking pose puts the whole mesh there - without reading C)
-  r.a = small ? make_uint2(((unsigned)o.X & 0xffffu) | ((unsigned)o.Y << 16), __float_as_uint(o.zn)) : make_uint2(RB_A_NONE, __float_as_uint(o.w));
+  r.a = small ? make_uint2(rt_a_pack(o.X, o.Y), __float_as_uint(o.zn)) : make_uint2(RB_A_NONE, __float_as_uint(o.w));
   r.b0 = make_float4(pc[0], pc[1], pc[2], dv);
   r.b1 = make_float4(0.f, 0.f, 0.f, o.w);
   if (m.vcolor) r.b1.x = m.vcolor[v * 3], r.b1.y = m.vcolor[v * 3 + 1], r.b1.z = m.vcolor[v * 3 + 2];
@@ -240,17 +240,15 @@ __global__ __launch_bounds__(256) void xform_vertices_kernel(RenderArgs a, int4 
   recB[2 * r + 1] = q.b1;
 }
 
-#define RB_SMALL 4                      // candidate pixels of a "small" triangle
-#define RB_MEDIUM 32                    // ... of a "medium" one; larger triangles are rasterised by a whole wave
-#define RB_SLOW 0x80000000u             // list B entry flag: needs the C records (64-bit edge functions or the homogeneous form)
-#define RB_MAXS 255                     // strips per hypothesis
+#define RB_THREADS 1024
 
 // Per (hypothesis, strip) face lists.  A face is dropped here exactly when it cannot touch a pixel of the crop (pixel range empty
 // after clamping to the crop, or zero area): the same integers as in the triangle pass, so the images are bit-identical to a walk
 // over all faces.  The faces of a hypothesis are cut into G contiguous ranges of Fg, one workgroup each (G = 1 from 64 hypotheses on;
 // a handful of hypotheses - tracking - would otherwise leave the classification to a handful of workgroups).  Per (hypothesis b, strip s,
 // range g): count[((b*S + s)*G + g)*4 + {0,1,2}] = small, medium, list-B entries; listA[(b*S + s)*G*Fg + g*Fg ..]: small from the
-// front of the range's segment, medium from its back; listB likewise: large 32-bit triangles and RB_SLOW ones.
+// front of the range's segment, medium from its back; listB likewise: large 32-bit triangles and RB_SLOW ones.  The counters are in
+// LDS; the order inside a list is not deterministic and does not matter (visibility is a minimum over keys).
 // FUSED (the A records fit LDS: lds_verts): the vertex pre-pass runs HERE - every workgroup of a hypothesis transforms all its vertices
 // (it needs their A records in LDS for its face range anyway; 8 vertices per thread) and writes the records of its own share to global
 // memory for the strip kernel: one launch and one LDS fill from global memory less than xform_vertices_kernel + this kernel.
@@ -306,8 +304,8 @@ __global__ __launch_bounds__(RB_THREADS) void classify_faces_kernel(RenderArgs a
       for (int sI = 0; sI < S; ++sI) lB[(size_t)sI * seg + atomicAdd(&cs[sI][2], 1)] = (unsigned)t | RB_SLOW;
       continue;
     }
-    const int X0 = (short)(a0.x & 0xffffu), Y0 = (int)a0.x >> 16, X1 = (short)(a1.x & 0xffffu), Y1 = (int)a1.x >> 16,
-              X2 = (short)(a2.x & 0xffffu), Y2 = (int)a2.x >> 16;
+    const RtTri<int> T = rt_tri_a(a0, a1, a2);
+    const int X0 = T.X0, Y0 = T.Y0, X1 = T.X1, Y1 = T.Y1, X2 = T.X2, Y2 = T.Y2;
     if ((X1 - X0) * (Y2 - Y0) - (X2 - X0) * (Y1 - Y0) == 0) continue;
     const int xmin = min(X0, min(X1, X2)), xmax = max(X0, max(X1, X2));
     const int ymin = min(Y0, min(Y1, Y2)), ymax = max(Y0, max(Y1, Y2));
@@ -327,18 +325,53 @@ __global__ __launch_bounds__(RB_THREADS) void classify_faces_kernel(RenderArgs a
   for (int i = threadIdx.x; i < S * 3; i += RB_THREADS) count[(((size_t)b * S + i / 3) * G + grp) * 4 + i % 3] = cs[i / 3][i % 3];
 }
 
+// ---- the strip kernel ------------------------------------------------------------------------------------------------------
 // MODE 0: the API form (fp32 channels-last maps), 1: the fused network tensor, 2: dr.rasterize's own output only (u, v, z/w, triangle id + 1: parity tests)
 // SOLO: the whole render of a hypothesis' strip in THIS launch - for one or two hypotheses (a tracking frame), where the vertex pass,
 // the classification and this kernel are three dependent launches of a few workgroups each (4.5 + 7.8 + 31 us and two 5-us gaps at
 // one hypothesis, 37 us of it with nothing to draw).  Every strip's workgroup transforms all vertices itself (A records straight
 // into LDS), files the faces that touch ITS strip into lists in LDS (16-bit entries; the same tests and size classes as
-// classify_faces_kernel), and takes the B / C records of the few vertices it needs from vertex_records() directly: the same
-// functions on the same inputs, and a z-buffer of (depth, face) keys under atomicMin does not depend on the order of the lists,
-// so the images are bit-identical to the three-launch form (test_render_solo_equals_three_launches).
+// classify_faces_kernel), and takes the B / C records of the few vertices it needs from vertex_records() directly: the same functions on the same inputs, and a
+// z-buffer of (depth, face) keys under atomicMin does not depend on the order of the lists, so the images are bit-identical to the
+// three-launch form (test_render_solo_equals_three_launches).
 //
 // OBJ = RenderObjs (launch_render_objects, fp_track_objects): several objects' solo renders as ONE launch.  Workgroup L is strip L - wg0[o] of
 // object o, which keeps the strips of its own plan and its own mesh and diameter, so its image is the one render_kernel<1, true> makes of
 // it alone.  The table rides in the kernel arguments.
+//
+// From raster_tri.h: the LDS carve (RtStripLds, the layout the plan sized), the A unpack, the key, and the resolve's edge functions and
+// weights.  The body is ONE function, and the candidate range, the top-left flags and the filing by size class are written out here and in
+// classify_faces_kernel, because hipcc's code for this kernel, at the 128-VGPR ceiling of a 1024-thread workgroup, does not survive either:
+// a phase as a __forceinline__ function spills (scratch 0 -> 8 .. 28 B/lane in the three-launch forms, 44 -> 188 in the one-launch form),
+// and at unchanged register counts the range / edge / cover functions in passes 1a and 1b cost about 1 % of a render, the range / size-class
+// functions in the two classification forms 1.4 % at 252 hypotheses and 6 % at one (profiles/HISTORY.md has the sessions).
+// a.dbg's bits (FP_RENDER_DBG, timing experiments only - wrong images): 1 no per-lane rasterisation, 2 no resolve, 4 no triangle pass, 16 no
+// per-wave rasterisation, 32 / 64 (SOLO) no classification / no describable vertex.
+__device__ __forceinline__ Vtx vtx_of_c(const int4 &q) {      // record C: exactly xform_vertex's values
+  return Vtx{q.x, q.y, __int_as_float(q.w), __int_as_float(q.z), q.x != (int)0x80000000};
+}
+// bilinear texture fetch with wrap-around at texture coordinates (tu, tv)
+__device__ __forceinline__ void texture_fetch(const MeshDev &m, float tu, float tv, float *base) {
+  float x = tu * (float)m.texW - 0.5f, y = tv * (float)m.texH - 0.5f;
+  float fx0 = floorf(x), fy0 = floorf(y);
+  float fx = x - fx0, fy = y - fy0;
+  // (a whole number beyond the int range: its residue taken in float, where it is exact - the conversion alone would saturate)
+  if (fabsf(fx0) >= 2147483648.f) fx0 = fmodf(fx0, (float)m.texW);
+  if (fabsf(fy0) >= 2147483648.f) fy0 = fmodf(fy0, (float)m.texH);
+  int x0 = (int)fx0 % m.texW;
+  if (x0 < 0) x0 += m.texW;
+  int y0 = (int)fy0 % m.texH;
+  if (y0 < 0) y0 += m.texH;
+  int x1 = (x0 + 1) % m.texW, y1 = (y0 + 1) % m.texH;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    float t00 = m.tex[(y0 * m.texW + x0) * 3 + c], t10 = m.tex[(y0 * m.texW + x1) * 3 + c];
+    float t01 = m.tex[(y1 * m.texW + x0) * 3 + c], t11 = m.tex[(y1 * m.texW + x1) * 3 + c];
+    float ta = __fadd_rn(t00, __fmul_rn(fx, (t10 - t00)));
+    float tb = __fadd_rn(t01, __fmul_rn(fx, (t11 - t01)));
+    base[c] = __fadd_rn(ta, __fmul_rn(fy, (tb - ta)));
+  }
+}
 struct NoObjs {};
 struct RenderObjs {
   int n;
@@ -346,14 +379,14 @@ struct RenderObjs {
   float diameter[FP_TRACK_MAX_OBJECTS];
   MeshDev mesh[FP_TRACK_MAX_OBJECTS];
 };
+
 template <int MODE, bool SOLO, typename OBJ = NoObjs>
 __global__ __launch_bounds__(RB_THREADS) void render_kernel(RenderArgs a, int strip_rows, int n_strips, const int4 *__restrict__ recC,
                                                             const float4 *__restrict__ recB, const uint2 *__restrict__ recA, const int *__restrict__ count,
                                                             const unsigned *__restrict__ listA, const unsigned *__restrict__ listB, int lds_verts, int G, int Fg,
                                                             OBJ t) {
   constexpr bool OBJS = !std::is_same<OBJ, NoObjs>::value;
-  // dynamic LDS: the strip (8 B per pixel), the queue of its covered pixels (2 B per pixel), then (lds_verts) the hypothesis' A records,
-  // then (SOLO) the strip's two face lists, 2 B per face each
+  // dynamic LDS: carved below by RtStripLds, the layout the plan sized it with
   extern __shared__ __attribute__((aligned(16))) unsigned long long zbuf[];
   __shared__ float sM[16];
   __shared__ float sP[12];
@@ -380,10 +413,11 @@ __global__ __launch_bounds__(RB_THREADS) void render_kernel(RenderArgs a, int st
   const float *pose = a.poses + (size_t)b * 16;
   const MeshDev &m = *mp;
   const uint2 *gA = recA + (size_t)b * m.V;
-  unsigned short *covq = reinterpret_cast<unsigned short *>(zbuf + (size_t)strip_rows * Wo);
-  uint2 *ldsA = reinterpret_cast<uint2 *>(reinterpret_cast<char *>(covq) + ((((size_t)strip_rows * Wo * 2) + 15) & ~(size_t)15));
-  unsigned short *soloA = reinterpret_cast<unsigned short *>(ldsA + ((m.V + 1) & ~1));
-  unsigned short *soloB = soloA + ((m.F + 7) & ~7);
+  const RtStripLds lds = rt_strip_lds(strip_rows, Wo, m.V, m.F, lds_verts, SOLO);
+  char *const lds0 = reinterpret_cast<char *>(zbuf);
+  unsigned short *covq = reinterpret_cast<unsigned short *>(lds0 + lds.covq);
+  uint2 *ldsA = reinterpret_cast<uint2 *>(lds0 + lds.recA);
+  unsigned short *soloA = reinterpret_cast<unsigned short *>(lds0 + lds.listA), *soloB = reinterpret_cast<unsigned short *>(lds0 + lds.listB);
 
   if (threadIdx.x == 0) {
     clip_matrix(a, b, pose, sM);
@@ -408,8 +442,8 @@ __global__ __launch_bounds__(RB_THREADS) void render_kernel(RenderArgs a, int st
         if (front) soloB[atomicAdd(&scnt[2], 1)] = (unsigned short)t;
         return;
       }
-      const int X0 = (short)(a0.x & 0xffffu), Y0 = (int)a0.x >> 16, X1 = (short)(a1.x & 0xffffu), Y1 = (int)a1.x >> 16,
-                X2 = (short)(a2.x & 0xffffu), Y2 = (int)a2.x >> 16;
+      const RtTri<int> T = rt_tri_a(a0, a1, a2);
+      const int X0 = T.X0, Y0 = T.Y0, X1 = T.X1, Y1 = T.Y1, X2 = T.X2, Y2 = T.Y2;
       if ((X1 - X0) * (Y2 - Y0) - (X2 - X0) * (Y1 - Y0) == 0) return;
       const int xmin = min(X0, min(X1, X2)), xmax = max(X0, max(X1, X2));
       const int ymin = min(Y0, min(Y1, Y2)), ymax = max(Y0, max(Y1, Y2));
@@ -445,15 +479,6 @@ __global__ __launch_bounds__(RB_THREADS) void render_kernel(RenderArgs a, int st
     if constexpr (SOLO) return vertex_records(a, m, i, sM, sP).c;
     else return vc[i];
   };
-  auto unpack = [](const int4 &q) -> Vtx {      // record C: exactly xform_vertex's values
-    Vtx o;
-    o.X = q.x;
-    o.Y = q.y;
-    o.zn = __int_as_float(q.z);
-    o.w = __int_as_float(q.w);
-    o.ok = q.x != (int)0x80000000;
-    return o;
-  };
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if constexpr (SOLO) G = 1, Fg = m.F;
   for (int grp = 0; grp < G; ++grp) {             // the face ranges the classification was cut into (one from 64 hypotheses on)
@@ -485,8 +510,8 @@ __global__ __launch_bounds__(RB_THREADS) void render_kernel(RenderArgs a, int st
       }
       if (a.dbg & 1) continue;
       const uint2 a0 = getA(f.x), a1 = getA(f.y), a2 = getA(f.z);
-      const int X0 = (short)(a0.x & 0xffffu), Y0 = (int)a0.x >> 16, X1 = (short)(a1.x & 0xffffu), Y1 = (int)a1.x >> 16,
-                X2 = (short)(a2.x & 0xffffu), Y2 = (int)a2.x >> 16;
+      const RtTri<int> T = rt_tri_a(a0, a1, a2);
+      const int X0 = T.X0, Y0 = T.Y0, X1 = T.X1, Y1 = T.Y1, X2 = T.X2, Y2 = T.Y2;
       int area = (X1 - X0) * (Y2 - Y0) - (X2 - X0) * (Y1 - Y0);
       const int xmin = min(X0, min(X1, X2)), xmax = max(X0, max(X1, X2));
       const int ymin = min(Y0, min(Y1, Y2)), ymax = max(Y0, max(Y1, Y2));
@@ -516,8 +541,7 @@ __global__ __launch_bounds__(RB_THREADS) void render_kernel(RenderArgs a, int st
           const float b0 = (float)e0 / fa, b1 = (float)e1 / fa, b2 = (float)e2 / fa;
           const float zp = fmaf(b2, z2, fmaf(b1, z1, b0 * z0));
           if (!(zp >= -1.f && zp <= 1.f)) continue;
-          const unsigned long long key = ((unsigned long long)ordered_key(zp) << 32) | (unsigned)t;
-          atomicMin(&zbuf[(j - row0) * Wo + i], key);
+          atomicMin(&zbuf[(j - row0) * Wo + i], rt_key(zp, t));
         }
       }
     }
@@ -542,7 +566,7 @@ __global__ __launch_bounds__(RB_THREADS) void render_kernel(RenderArgs a, int st
       };
       const int t = __builtin_amdgcn_readlane(my_t, q);
       const int4 f = bc4(my_f);
-      const Vtx v0 = unpack(bc4(my_c0)), v1 = unpack(bc4(my_c1)), v2 = unpack(bc4(my_c2));
+      const Vtx v0 = vtx_of_c(bc4(my_c0)), v1 = vtx_of_c(bc4(my_c1)), v2 = vtx_of_c(bc4(my_c2));
       if (!(v0.ok && v1.ok && v2.ok)) {
         // a vertex on or behind the camera plane (or projected out of range): homogeneous edge functions, every pixel of the strip
         if (!(v0.w > 0.f || v1.w > 0.f || v2.w > 0.f)) continue;      // entirely behind the camera
@@ -555,9 +579,7 @@ __global__ __launch_bounds__(RB_THREADS) void render_kernel(RenderArgs a, int st
         for (int p = lane; p < npix; p += 64) {
           const int jl = p / Wo, i = p - jl * Wo;
           float l[3], zp;
-          if (!clip_eval(T, i, row0 + jl, l, &zp)) continue;
-          const unsigned long long key = ((unsigned long long)ordered_key(zp) << 32) | (unsigned)t;
-          atomicMin(&zbuf[p], key);
+          if (clip_eval(T, i, row0 + jl, l, &zp)) atomicMin(&zbuf[p], rt_key(zp, t));
         }
         continue;
       }
@@ -593,8 +615,7 @@ __global__ __launch_bounds__(RB_THREADS) void render_kernel(RenderArgs a, int st
         const float b0 = (float)e0 / fa, b1 = (float)e1 / fa, b2 = (float)e2 / fa;
         const float zp = fmaf(b2, v2.zn, fmaf(b1, v1.zn, b0 * v0.zn));
         if (!(zp >= -1.f && zp <= 1.f)) continue;
-        const unsigned long long key = ((unsigned long long)ordered_key(zp) << 32) | (unsigned)t;
-        atomicMin(&zbuf[(int)(j - row0) * Wo + (int)i], key);
+        atomicMin(&zbuf[(int)(j - row0) * Wo + (int)i], rt_key(zp, t));
       }
     }
   }
@@ -605,10 +626,11 @@ __global__ __launch_bounds__(RB_THREADS) void render_kernel(RenderArgs a, int st
   // zeros at once; (b) one covered pixel per lane: attribute interpolation, shading, fused epilogue.  Per pixel: the face's index quad,
   // the three A records (LDS) and the three 32-byte B records - 7 scattered 16-byte loads on 4 cache lines (27 + 9 scattered 4-byte
   // loads until round 3, with the position / normal transform and Lambert term of all three vertices recomputed per pixel).
-  float P0 = 0.f, P1 = 0.f, P2 = 0.f, P4 = 0.f, P5 = 0.f, P6 = 0.f, P8 = 0.f, P9 = 0.f, P10 = 0.f;
   constexpr bool API = MODE == 0, RAST = MODE == 2;
-  if (API) {                            // the API form also interpolates the camera-space normals
-    P0 = pose[0], P1 = pose[1], P2 = pose[2], P4 = pose[4], P5 = pose[5], P6 = pose[6], P8 = pose[8], P9 = pose[9], P10 = pose[10];
+  float R[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (API) {                            // the API form also interpolates the camera-space normals: the pose's rotation
+#pragma unroll
+    for (int k = 0; k < 9; ++k) R[k] = pose[(k / 3) * 4 + k % 3];
   }
   auto emit = [&](int p, const float *col, const float *nrm, const float *p3, const float *r4) __attribute__((always_inline)) {
     const int jl = p / Wo, i = p - jl * Wo;
@@ -696,54 +718,33 @@ __global__ __launch_bounds__(RB_THREADS) void render_kernel(RenderArgs a, int st
         rc0 = vbB[2 * i0 + 1], rc1 = vbB[2 * i1 + 1], rc2 = vbB[2 * i2 + 1];
       }
       const uint2 a0 = getA(i0), a1 = getA(i1), a2 = getA(i2);
-      float fa, b0, b1, b2;
-      float u, v, w2;
-      if (a0.x != RB_A_NONE && a1.x != RB_A_NONE && a2.x != RB_A_NONE) {      // the same integers in 32-bit arithmetic (see pass 1)
-        const int X0 = (short)(a0.x & 0xffffu), Y0 = (int)a0.x >> 16, X1 = (short)(a1.x & 0xffffu), Y1 = (int)a1.x >> 16,
-                  X2 = (short)(a2.x & 0xffffu), Y2 = (int)a2.x >> 16;
-        int area = (X1 - X0) * (Y2 - Y0) - (X2 - X0) * (Y1 - Y0);
-        const int sg = area > 0 ? 1 : -1;
-        area *= sg;
-        const int Px = 16 * i + 8, Py = 16 * j + 8;
-        const int e0 = sg * ((X2 - X1) * (Py - Y1) - (Y2 - Y1) * (Px - X1));
-        const int e1 = sg * ((X0 - X2) * (Py - Y2) - (Y0 - Y2) * (Px - X2));
-        const int e2 = sg * ((X1 - X0) * (Py - Y0) - (Y1 - Y0) * (Px - X0));
-        fa = (float)area;
-        b0 = (float)e0 / fa, b1 = (float)e1 / fa, b2 = (float)e2 / fa;
-        float q0 = b0 / rc0.w, q1 = b1 / rc1.w, q2 = b2 / rc2.w;
-        float qs = (q0 + q1) + q2;
-        u = q0 / qs, v = q1 / qs, w2 = (1.f - u) - v;
-        if (RAST) r4[2] = fmaf(b2, __uint_as_float(a2.y), fmaf(b1, __uint_as_float(a1.y), b0 * __uint_as_float(a0.y)));
+      float b0, b1, b2, zp, u, v, w2;
+      if (rt_a_all(a0, a1, a2)) {       // the same integers in 32-bit arithmetic (see pass 1)
+        const RtEdges<int> E(rt_tri_a(a0, a1, a2));
+        int e0, e1, e2;
+        E.at(E.centre(i), E.centre(j), e0, e1, e2);
+        (void)E.depth(e0, e1, e2, __uint_as_float(a0.y), __uint_as_float(a1.y), __uint_as_float(a2.y), b0, b1, b2, zp);
+        rt_persp(b0, b1, b2, rc0.w, rc1.w, rc2.w, u, v, w2);
       } else {
-        const Vtx v0 = unpack(SOLO ? cc0 : vc[i0]), v1 = unpack(SOLO ? cc1 : vc[i1]), v2 = unpack(SOLO ? cc2 : vc[i2]);
+        const Vtx v0 = vtx_of_c(SOLO ? cc0 : vc[i0]), v1 = vtx_of_c(SOLO ? cc1 : vc[i1]), v2 = vtx_of_c(SOLO ? cc2 : vc[i2]);
         if (!(v0.ok && v1.ok && v2.ok)) {         // straddles the camera plane: weights from the homogeneous edge functions
           float c[3][4];
           const int id3[3] = {i0, i1, i2};
 #pragma unroll
           for (int k = 0; k < 3; ++k) clip_coords(m.pos, id3[k], M, c[k]);
           const ClipTri T = clip_setup(c, hw, hh);
-          float l[3], zp;
+          float l[3];
           (void)clip_eval(T, i, j, l, &zp);
-          const float ls = __fadd_rn(__fadd_rn(l[0], l[1]), l[2]);
-          u = __fdiv_rn(l[0], ls), v = __fdiv_rn(l[1], ls), w2 = (1.f - u) - v;
-          if (RAST) r4[2] = zp;
+          rt_persp_hom(l, u, v, w2);
         } else {
-          long long X0 = v0.X, Y0 = v0.Y, X1 = v1.X, Y1 = v1.Y, X2 = v2.X, Y2 = v2.Y;
-          long long area = (X1 - X0) * (Y2 - Y0) - (X2 - X0) * (Y1 - Y0);
-          long long sg = area > 0 ? 1 : -1;
-          area *= sg;
-          long long Px = 16ll * i + 8, Py = 16ll * j + 8;
-          long long e0 = sg * ((X2 - X1) * (Py - Y1) - (Y2 - Y1) * (Px - X1));
-          long long e1 = sg * ((X0 - X2) * (Py - Y2) - (Y0 - Y2) * (Px - X2));
-          long long e2 = sg * ((X1 - X0) * (Py - Y0) - (Y1 - Y0) * (Px - X0));
-          fa = (float)area;
-          b0 = (float)e0 / fa, b1 = (float)e1 / fa, b2 = (float)e2 / fa;
-          float q0 = b0 / v0.w, q1 = b1 / v1.w, q2 = b2 / v2.w;
-          float qs = (q0 + q1) + q2;
-          u = q0 / qs, v = q1 / qs, w2 = (1.f - u) - v;
-          if (RAST) r4[2] = fmaf(b2, v2.zn, fmaf(b1, v1.zn, b0 * v0.zn));
+          const RtEdges<long long> E(RtTri<long long>{v0.X, v0.Y, v1.X, v1.Y, v2.X, v2.Y});
+          long long e0, e1, e2;
+          E.at(E.centre(i), E.centre(j), e0, e1, e2);
+          (void)E.depth(e0, e1, e2, v0.zn, v1.zn, v2.zn, b0, b1, b2, zp);
+          rt_persp(b0, b1, b2, v0.w, v1.w, v2.w, u, v, w2);
         }
       }
+      if (RAST) r4[2] = zp;
       if (RAST) r4[0] = u, r4[1] = v, r4[3] = (float)(t + 1);
       if (!RAST) {
       // camera-space position and Lambert term of the three vertices: the pre-pass' records
@@ -753,12 +754,7 @@ __global__ __launch_bounds__(RB_THREADS) void render_kernel(RenderArgs a, int st
       if (API) {
         const int idx[3] = {i0, i1, i2};
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          float nx = m.vnormals[idx[k] * 3], ny = m.vnormals[idx[k] * 3 + 1], nz = m.vnormals[idx[k] * 3 + 2];
-          nc[k][0] = fmaf(P0, nx, fmaf(P1, ny, P2 * nz));
-          nc[k][1] = fmaf(P4, nx, fmaf(P5, ny, P6 * nz));
-          nc[k][2] = fmaf(P8, nx, fmaf(P9, ny, P10 * nz));
-        }
+        for (int k = 0; k < 3; ++k) normal_to_cam(R, m.vnormals[idx[k] * 3], m.vnormals[idx[k] * 3 + 1], m.vnormals[idx[k] * 3 + 2], nc[k]);
       }
       float base[3];
 #pragma unroll
@@ -770,25 +766,7 @@ __global__ __launch_bounds__(RB_THREADS) void render_kernel(RenderArgs a, int st
         int a0 = m.uv_idx[t * 3], a1 = m.uv_idx[t * 3 + 1], a2 = m.uv_idx[t * 3 + 2];
         float tu = fmaf(u, m.uv[a0 * 2], fmaf(v, m.uv[a1 * 2], w2 * m.uv[a2 * 2]));
         float tv = fmaf(u, m.uv[a0 * 2 + 1], fmaf(v, m.uv[a1 * 2 + 1], w2 * m.uv[a2 * 2 + 1]));
-        float x = tu * (float)m.texW - 0.5f, y = tv * (float)m.texH - 0.5f;
-        float fx0 = floorf(x), fy0 = floorf(y);
-        float fx = x - fx0, fy = y - fy0;
-        // (a whole number beyond the int range: its residue taken in float, where it is exact - the conversion alone would saturate)
-        if (fabsf(fx0) >= 2147483648.f) fx0 = fmodf(fx0, (float)m.texW);
-        if (fabsf(fy0) >= 2147483648.f) fy0 = fmodf(fy0, (float)m.texH);
-        int x0 = (int)fx0 % m.texW;
-        if (x0 < 0) x0 += m.texW;
-        int y0 = (int)fy0 % m.texH;
-        if (y0 < 0) y0 += m.texH;
-        int x1 = (x0 + 1) % m.texW, y1 = (y0 + 1) % m.texH;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          float t00 = m.tex[(y0 * m.texW + x0) * 3 + c], t10 = m.tex[(y0 * m.texW + x1) * 3 + c];
-          float t01 = m.tex[(y1 * m.texW + x0) * 3 + c], t11 = m.tex[(y1 * m.texW + x1) * 3 + c];
-          float ta = __fadd_rn(t00, __fmul_rn(fx, (t10 - t00)));
-          float tb = __fadd_rn(t01, __fmul_rn(fx, (t11 - t01)));
-          base[c] = __fadd_rn(ta, __fmul_rn(fy, (tb - ta)));
-        }
+        texture_fetch(m, tu, tv, base);
       } else {
         base[0] = fmaf(u, rc0.x, fmaf(v, rc1.x, w2 * rc2.x));
         base[1] = fmaf(u, rc0.y, fmaf(v, rc1.y, w2 * rc2.y));
@@ -812,102 +790,70 @@ __global__ __launch_bounds__(RB_THREADS) void render_kernel(RenderArgs a, int st
   }
 }
 
-// Strips per hypothesis and the scratch a launch needs: the vertex records C (16 B), B (32 B) and A (8 B), the list counters and
-// the two face lists of every (hypothesis, strip) (worst case: every face in every strip).
-RenderPlan render_plan(int N, int V, int F, int Ho, int Wo, int num_cu) {
-  RenderPlan p;
-  const size_t budget = 148 * 1024;               // dynamic LDS of a workgroup
-  p.lds_verts = (size_t)V * 8 <= 64 * 1024 ? 1 : 0;                          // the hypothesis' A records beside the strip
-  p.a_lds = p.lds_verts ? (((size_t)V * 8 + 15) & ~(size_t)15) : 0;
-  int rows_max = (int)((budget - p.a_lds - 16) / ((size_t)Wo * 10));        // 8 B framebuffer + 2 B covered-pixel queue per pixel
-  if (p.lds_verts && (rows_max < 1 || (Ho + rows_max - 1) / rows_max > RB_MAXS)) {
-    // a large full frame (1920x1200 beside 8k vertices) would need more than RB_MAXS strips: the A records stay in global memory
-    p.lds_verts = 0;
-    p.a_lds = 0;
-    rows_max = (int)((budget - 16) / ((size_t)Wo * 10));
-  }
-  if (rows_max > Ho) rows_max = Ho;
-  if (rows_max < 1) rows_max = 1;
-  int S = (Ho + rows_max - 1) / rows_max;
-  // 27-row strips of a 160-row crop; thinner ones while the launch is under ~0.8 workgroups per CU (a workgroup's resolve pass shrinks
-  // with its strip; twice the strips are then still under two rounds)
-  while (S < 4 && Ho / (S * 2) >= 8) S *= 2;
-  // (measured, 160x160 crops of the 16k-face mesh, strips 6 -> 12: 24 hypotheses 58 -> 49 us, 32: 72 -> 62, 40: 72 -> 78, 63: 92 -> 100)
-  while ((size_t)N * S * 5 <= (size_t)num_cu * 4 && S < 16 && Ho / (S * 2) >= 8) S *= 2;
-  static const int force_s = fp_env_int("FP_RENDER_S", 0);      // experiments: strips per hypothesis
-  if (force_s > 0 && (Ho + force_s - 1) / force_s <= rows_max) S = force_s;
-  p.strip_rows = (Ho + S - 1) / S;
-  p.S = (Ho + p.strip_rows - 1) / p.strip_rows;
-  p.lds_bytes = (size_t)p.strip_rows * Wo * 8 + ((((size_t)p.strip_rows * Wo * 2) + 15) & ~(size_t)15) + p.a_lds;
-  p.c_bytes = ((size_t)N * V * 16 + 255) & ~(size_t)255;
-  p.b_bytes = ((size_t)N * V * 32 + 255) & ~(size_t)255;
-  p.a_bytes = ((size_t)N * V * 8 + 255) & ~(size_t)255;
-  p.G = 1;                                        // face ranges per hypothesis in the classification: more while it would fill < 1/4 of the chip
-  while ((size_t)N * p.G * 4 <= (size_t)num_cu && p.G < 8 && F / (p.G * 2) >= 1024) p.G *= 2;
-  p.Fg = (F + p.G - 1) / p.G;
-  p.count_bytes = ((size_t)N * p.S * p.G * 16 + 255) & ~(size_t)255;
-  p.list_bytes = ((size_t)N * p.S * p.G * p.Fg * 4 + 255) & ~(size_t)255;
-  p.total = p.c_bytes + p.b_bytes + p.a_bytes + p.count_bytes + 2 * p.list_bytes;
-  // one or two hypotheses (a tracking frame): vertex pass, classification and triangle pass as ONE launch (render_kernel<.., true>) when a
-  // strip, the A records and the strip's two 16-bit face lists fit a workgroup's LDS.  FP_RENDER_SOLO = largest batch that takes it (0: off).
-  static const int solo_max = fp_env_int("FP_RENDER_SOLO", 2);
-  p.solo_lds = (((size_t)p.strip_rows * Wo * 8 + ((((size_t)p.strip_rows * Wo * 2) + 15) & ~(size_t)15) + (size_t)((V + 1) & ~1) * 8 + 15) & ~(size_t)15) +
-               2 * (size_t)((F + 7) & ~7) * 2;
-  p.solo = (N <= solo_max && p.lds_verts && F <= 65535 && p.solo_lds <= budget) ? 1 : 0;
-  return p;
+// ---- host ------------------------------------------------------------------------------------------------------------------
+struct RasterKnobs : RenderKnobs {
+  int dbg = 0;                          // FP_RENDER_DBG: phases switched off (render_kernel)
+  bool two_launches = false;            // FP_RENDER_PREPASS2: A/B knob, vertex pre-pass and classification as two launches (identical images)
+};
+static const RasterKnobs &raster_knobs() {
+  static const RasterKnobs k = [] {
+    RasterKnobs k;
+    k.force_s = (int)fp_env_int("FP_RENDER_S", 0);
+    k.solo_max = (int)fp_env_int("FP_RENDER_SOLO", 2);
+    k.scratch_max = (size_t)fp_env_int("FP_RENDER_SCRATCH_MAX", 1ll << 30);
+    k.dbg = (int)fp_env_int("FP_RENDER_DBG", 0);
+    k.two_launches = fp_env_set("FP_RENDER_PREPASS2");
+    return k;
+  }();
+  return k;
+}
+
+RenderPlan render_plan(int N, int V, int F, int Ho, int Wo, int num_cu) { return rt_render_plan(N, V, F, Ho, Wo, num_cu, raster_knobs()); }
+int render_chunk(int N, int V, int F, int Ho, int Wo, int num_cu) { return rt_render_chunk(N, V, F, Ho, Wo, num_cu, raster_knobs()); }
+size_t render_scratch_bytes(int N, int V, int F, int Ho, int Wo, int num_cu) {
+  return render_plan(render_chunk(N, V, F, Ho, Wo, num_cu), V, F, Ho, Wo, num_cu).total;
+}
+// does launch_render take N hypotheses of this mesh at this output size (the limits launch_render_one checks)
+bool render_fits(int N, int V, int F, int Ho, int Wo, int num_cu) { return rt_render_fits(N, V, F, Ho, Wo, num_cu, raster_knobs()); }
+bool render_objects_form(int V, int F, int Ho, int Wo, int num_cu) {
+  const RenderPlan pl = render_plan(1, V, F, Ho, Wo, num_cu);
+  return pl.solo && rt_strip_limits(pl, Wo);
 }
 
 void raster_kernel_lds(std::vector<KernelLds> &v) {
   v.push_back({(const void *)classify_faces_kernel<true>, 64 * 1024});
   v.push_back({(const void *)classify_faces_kernel<false>, 64 * 1024});
-  v.push_back({(const void *)render_kernel<1, false>, 148 * 1024});        // the largest strip
-  v.push_back({(const void *)render_kernel<0, false>, 148 * 1024});
-  v.push_back({(const void *)render_kernel<2, false>, 148 * 1024});
-  v.push_back({(const void *)render_kernel<1, true>, 148 * 1024});
-  v.push_back({(const void *)render_kernel<0, true>, 148 * 1024});
-  v.push_back({(const void *)render_kernel<2, true>, 148 * 1024});
-  v.push_back({(const void *)render_kernel<1, true, RenderObjs>, 148 * 1024});
-}
-
-int render_chunk(int N, int V, int F, int Ho, int Wo, int num_cu) {
-  static const size_t cap = (size_t)fp_env_int("FP_RENDER_SCRATCH_MAX", 1ll << 30);
-  int chunk = N < 1 ? 1 : N;
-  while (chunk > 1 && render_plan(chunk, V, F, Ho, Wo, num_cu).total > cap) chunk = (chunk + 1) / 2;
-  return chunk;
-}
-
-size_t render_scratch_bytes(int N, int V, int F, int Ho, int Wo, int num_cu) {
-  return render_plan(render_chunk(N, V, F, Ho, Wo, num_cu), V, F, Ho, Wo, num_cu).total;
+  for (const void *k : {(const void *)render_kernel<1, false>, (const void *)render_kernel<0, false>, (const void *)render_kernel<2, false>,
+                        (const void *)render_kernel<1, true>, (const void *)render_kernel<0, true>, (const void *)render_kernel<2, true>,
+                        (const void *)render_kernel<1, true, RenderObjs>})
+    v.push_back({k, (int)RT_LDS_BUDGET});           // the largest strip
 }
 
 // one sub-batch; plan_n: the batch size the plan (strips, face ranges, list strides) is made for (>= a.N: a smaller last sub-batch runs on
 // the plan of the full ones, so the scratch of a full one always holds it)
 static int launch_render_one(fp_ctx *ctx, const RenderArgs &a_in, int plan_n, hipStream_t s) {
   RenderArgs a = a_in;
-  static const int dbg_env = fp_env_int("FP_RENDER_DBG", 0);      // timing experiments only (wrong images): 1 no per-lane rasterisation, 2 no resolve, 4 no triangle pass, 16 no per-wave rasterisation
-  a.dbg = dbg_env;
+  a.dbg = raster_knobs().dbg;
   FP_REQUIRE(a.N >= 0 && a.Ho > 0 && a.Wo > 0, "render: bad shape N=%d out=%dx%d", a.N, a.Ho, a.Wo);
   if (a.N == 0) return FP_OK;
   FP_REQUIRE((size_t)a.Wo * 10 <= 64 * 1024, "render: output width %d too large for one LDS strip", a.Wo);
   FP_REQUIRE(a.mesh.F < (1 << 30), "render: %d faces", a.mesh.F);
   const RenderPlan pl = render_plan(plan_n, a.mesh.V, a.mesh.F, a.Ho, a.Wo, ctx->num_cu);
-  FP_REQUIRE(pl.S <= RB_MAXS && pl.strip_rows * a.Wo <= 65535, "render: output %dx%d needs %d strips of %d pixels", a.Ho, a.Wo, pl.S, pl.strip_rows * a.Wo);
+  FP_REQUIRE(rt_strip_limits(pl, a.Wo), "render: output %dx%d needs %d strips of %d pixels", a.Ho, a.Wo, pl.S, pl.strip_rows * a.Wo);
   FP_REQUIRE(a.scratch && a.scratch_bytes >= pl.total, "render: scratch of %zu bytes needed, %zu given", pl.total, a.scratch_bytes);
   char *sc = (char *)a.scratch;
-  int4 *recC = (int4 *)sc;
-  float4 *recB = (float4 *)(sc + pl.c_bytes);
-  uint2 *recA = (uint2 *)(sc + pl.c_bytes + pl.b_bytes);
-  int *count = (int *)(sc + pl.c_bytes + pl.b_bytes + pl.a_bytes);
-  unsigned *listA = (unsigned *)(sc + pl.c_bytes + pl.b_bytes + pl.a_bytes + pl.count_bytes);
-  unsigned *listB = (unsigned *)(sc + pl.c_bytes + pl.b_bytes + pl.a_bytes + pl.count_bytes + pl.list_bytes);
+  int4 *recC = (int4 *)(sc + pl.sc.recC);
+  float4 *recB = (float4 *)(sc + pl.sc.recB);
+  uint2 *recA = (uint2 *)(sc + pl.sc.recA);
+  int *count = (int *)(sc + pl.sc.count);
+  unsigned *listA = (unsigned *)(sc + pl.sc.listA), *listB = (unsigned *)(sc + pl.sc.listB);
   // (profiling: the class' work figure is BYTES WRITTEN - the fused fp16 net tensor, or the API's fp32 maps - for the HBM-stage line of bench.py)
   ProfScope ps(ctx, s, "render", a.net_out ? (double)a.N * a.Ho * a.Wo * 16.0 : (double)a.N * a.Ho * a.Wo * 40.0);
-  static const bool two_launches = fp_env_set("FP_RENDER_PREPASS2");       // A/B knob: vertex pre-pass and classification as two launches (identical images)
   // fused where one workgroup per hypothesis classifies (G == 1: from 64 hypotheses on): 220 -> 210 us at 252 hypotheses, 144 -> 136 at 126; with
   // the faces of a hypothesis cut into G ranges every range's workgroup would redo the vertex pass (32 hypotheses: 70 -> 73 us, 1: 32 -> 34)
   if (pl.solo) {
     // (nothing in front of the strip kernel)
-  } else if (pl.lds_verts && pl.G == 1 && !two_launches) {
+  } else if (pl.lds_verts && pl.G == 1 && !raster_knobs().two_launches) {
     hipLaunchKernelGGL(classify_faces_kernel<true>, dim3(a.N, pl.G), dim3(RB_THREADS), pl.a_lds, s, a, recA, recC, recB, count, listA, listB, pl.S,
                        pl.strip_rows, pl.lds_verts, pl.G, pl.Fg);
   } else {
@@ -932,24 +878,11 @@ static int launch_render_one(fp_ctx *ctx, const RenderArgs &a_in, int plan_n, hi
   return FP_OK;
 }
 
-// does launch_render take N hypotheses of this mesh at this output size (the strip limits launch_render_one checks)
-bool render_fits(int N, int V, int F, int Ho, int Wo, int num_cu) {
-  if (Ho < 1 || Wo < 1 || (size_t)Wo * 10 > 64 * 1024 || F >= (1 << 30)) return false;
-  const RenderPlan pl = render_plan(render_chunk(N, V, F, Ho, Wo, num_cu), V, F, Ho, Wo, num_cu);
-  return pl.S <= RB_MAXS && pl.strip_rows * Wo <= 65535;
-}
-
-bool render_objects_form(int V, int F, int Ho, int Wo, int num_cu) {
-  const RenderPlan pl = render_plan(1, V, F, Ho, Wo, num_cu);
-  return pl.solo && pl.S <= RB_MAXS && pl.strip_rows * Wo <= 65535;
-}
-
 int launch_render_objects(fp_ctx *ctx, const RenderArgs &a_in, const MeshDev *const *mesh, const float *diameter, const int *hyp, int n, hipStream_t s) {
   FP_REQUIRE(n >= 1 && n <= FP_TRACK_MAX_OBJECTS, "render: %d objects in one launch (1 .. %d)", n, FP_TRACK_MAX_OBJECTS);
   FP_REQUIRE(a_in.net_out && a_in.Ho > 0 && a_in.Wo > 0, "render: the multi-object form writes the network tensor");
   RenderArgs a = a_in;
-  static const int dbg_env = fp_env_int("FP_RENDER_DBG", 0);      // as launch_render_one
-  a.dbg = dbg_env;
+  a.dbg = raster_knobs().dbg;
   RenderObjs t;
   memset(&t, 0, sizeof(t));
   t.n = n;
