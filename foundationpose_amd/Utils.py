@@ -23,6 +23,7 @@ from .rectify import (distort_points, monotonic_r2_max, rectify_pair, rectify_st
 from .reproject import align_frame, gather_by_source, reproject_depth, rgbd_rig  # noqa: F401  (depth and colour from two sensors; a build extension)
 from .detect import TemplateSet, build_templates, detect, match_templates, templates_from_depths  # noqa: F401  (objects without a mask; a build extension)
 from .pose_icp import align_poses_step, polish_poses, pose_gn_step  # noqa: F401  (polishing poses against depth; a build extension)
+from .mesh_align import align_points_step, align_to_mesh, transform_mesh  # noqa: F401  (a mesh or a point cloud onto a model; a build extension)
 from .vis import cv_draw_text, depth_to_vis, make_grid_image  # noqa: F401  (src/Utils.py:630-653, 456-478, 293-300)
 
 glcam_in_cvcam = np.array([[1, 0, 0, 0],
@@ -1382,7 +1383,7 @@ def distance_stats(dist, taus=()):
               within=[int(x) for x in s[L.FP_SURFDIST_STATS_TAU0:]])
 
 
-def mesh_distance(mesh_a, mesh_b, n_samples=100_000, seed=0, taus=(0.001, 0.002, 0.005), use_vertices=True):
+def mesh_distance(mesh_a, mesh_b, n_samples=100_000, seed=0, taus=(0.001, 0.002, 0.005), use_vertices=True, align=False):
   """How far apart two meshes are, measured on the device: Chamfer and Hausdorff distance and precision / recall / F-score.
 
   The points of A are its vertices (use_vertices) plus n_samples surface samples (sample_surface, seeded); each is measured against B's
@@ -1398,10 +1399,25 @@ def mesh_distance(mesh_a, mesh_b, n_samples=100_000, seed=0, taus=(0.001, 0.002,
     'fscore'             their harmonic mean, 0 when both are 0
   With A a reconstruction and B the CAD model this is the usual reporting of model-free results.  Meshes: objects with .vertices and
   .faces or (vertices, faces) tuples.  The statistics are deterministic sums (fp_distance_stats) and are read back together at the end;
-  sampling a mesh synchronises once more per mesh (the library reads its total area)."""
+  sampling a mesh synchronises once more per mesh (the library reads its total area).
+
+  align: False measures the meshes as they lie.  True first lays A onto B with align_to_mesh(mesh_a, mesh_b) - for meshes of one object
+  in two frames, such as a reconstruction with estimated poses against its CAD model; A should be the partial surface, B the complete
+  one - and a (4,4) array is used as that transform, `B from A`.  The result then also holds 'a_to_b_transform' (4,4) float64 and, for
+  True, 'align_info' (align_to_mesh's: look at 'ambiguous')."""
   n_samples = int(n_samples)
   if n_samples < 0 or (n_samples == 0 and not use_vertices):
     raise ValueError('mesh_distance: nothing to measure (n_samples = 0 and use_vertices = False)')
+  if align is not False and align is not None:
+    if align is True:
+      T, align_info = align_to_mesh(mesh_a, mesh_b, seed=seed)
+      extra = dict(a_to_b_transform=T, align_info=align_info)
+    else:
+      T = np.asarray(align.cpu() if torch.is_tensor(align) else align, dtype=np.float64).reshape(4, 4)
+      extra = dict(a_to_b_transform=T)
+    va, fa = _mesh_parts(mesh_a)[:2]
+    va = np.asarray(va.cpu() if torch.is_tensor(va) else va, dtype=np.float64) @ T[:3, :3].T + T[:3, 3]
+    return dict(mesh_distance((va, fa), mesh_b, n_samples=n_samples, seed=seed, taus=taus, use_vertices=use_vertices), **extra)
   dev = _device_of(_mesh_parts(mesh_a)[0])
   surf = [_surface_on(m, None, None, dev, 'mesh_distance') for m in (mesh_a, mesh_b)]
   pts = []

@@ -130,6 +130,10 @@ FP_SURFDIST_MAX_POINTS, FP_SURFDIST_MAX_FACES, FP_SURFDIST_MAX_TAUS, FP_SURFDIST
 FP_SURFDIST_TILE, FP_SURFDIST_CHUNK = 1024, 256          # queries of a workgroup, face records of an LDS chunk
 FP_SURFDIST_STATS_COUNT, FP_SURFDIST_STATS_SUM, FP_SURFDIST_STATS_SUM_SQ, FP_SURFDIST_STATS_MAX, FP_SURFDIST_STATS_NOT_FINITE = 0, 1, 2, 3, 4
 FP_SURFDIST_STATS_TAU0 = 5                               # d_stats[5 + k]: the count of d <= taus[k]
+# fp_points_mesh_align, fp_points_mesh_polish
+FP_MESH_ALIGN_PLANE, FP_MESH_ALIGN_POINT, FP_MESH_ALIGN_MAX_STAGES = 0, 1, 8
+FP_MESH_ALIGN_MODES = {'plane': FP_MESH_ALIGN_PLANE, 'point': FP_MESH_ALIGN_POINT}
+MESH_ALIGN_STAGE_DTYPE = np.dtype([('mode', '<i4'), ('dist_max', '<f4'), ('iterations', '<i4')])      # fp_mesh_align_stage (12 bytes)
 
 
 class FpTextureCfg(Structure):
@@ -262,6 +266,10 @@ _PROTOS = {
   'fp_distance_stats': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
   'fp_symmetry_residuals': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
                                     c_void_p, c_void_p]),
+  'fp_points_mesh_align': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+  'fp_points_mesh_polish': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_double, c_int,
+                                    c_void_p, c_void_p, c_void_p, c_void_p]),
   'fp_mesh_sample_surface': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_uint, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
   'fp_net_create': (c_int, [c_void_p, c_int, POINTER(FpTensor), c_int, c_int, POINTER(c_void_p)]),
   'fp_net_destroy': (c_int, [c_void_p]),

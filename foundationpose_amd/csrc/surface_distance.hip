@@ -11,8 +11,19 @@
 // index) and folds the pair into the query's 64-bit key (d2 bits << 32 | face) with one integer atomicMin: non-negative fp32 bit
 // patterns order as unsigned integers, so the key keeps the tie rule whatever the face slices are.  surfdist_finish_kernel unpacks the
 // keys and, for `closest`, evaluates the winning pair again with the same function.  No float atomics; 20 KiB of static LDS.
+//
+// fp_points_mesh_align / fp_points_mesh_polish (rigid alignment of a point set to the mesh) sit on the same search: the queries are
+// formed from (pose, point) with a transform stride of 16 floats, and mesh_align_kernel - one of the aligners of gn_sums.h - unpacks the
+// keys as surfdist_finish_kernel does, evaluates the winning pair again with pair_d2 and turns (closest point, face normal) into the
+// rows and the 29 sums of a Gauss-Newton step; fp_pose_gn_step (pose_icp.hip) takes the step.
 #include "common.h"
 #include "device_util.h"
+#include "gn_sums.h"
+
+#include <math.h>
+
+static_assert(FP_POSE_ALIGN_TERMS == GN_TERMS, "the sums of fp_points_mesh_align are those fp_pose_gn_step reads");
+static_assert(sizeof(fp_pose_state) % 8 == 0, "the records of d_state are reset as 64-bit words");
 
 namespace {
 
@@ -136,9 +147,9 @@ struct SurfDistArgs {
   const int32_t *faces;    // (F, 3)
   int n, V, F, chunks_per_slice;
   u64 *keys;               // [n]: d2 bits << 32 | face, all ones before the launch
-  // fp_symmetry_residuals (TRANSFORMED): the n queries are g = k n_per + i, query g the point pts[i] under tfs[k]
-  const float *tfs;        // (n / n_per, 3, 4) row-major [R|t]
-  int n_per;
+  // fp_symmetry_residuals, fp_points_mesh_align (TRANSFORMED): the n queries are g = k n_per + i, query g the point pts[i] under tfs[k]
+  const float *tfs;        // (n / n_per, 3, 4) row-major [R|t], tf_stride floats apart: 12, or 16 for the first three rows of (4,4) poses
+  int n_per, tf_stride;
   float *q_out;            // (n, 3) or null: the transformed points
 };
 
@@ -163,7 +174,7 @@ __global__ __launch_bounds__(SD_THREADS) void surfdist_kernel(SurfDistArgs a) {
     const int i = min(q0 + q * SD_THREADS + tid, a.n - 1);      // a query past n repeats the last one and is not written
     if (TRANSFORMED) {
       const int k = i / a.n_per, j = i - k * a.n_per;
-      transform_point(a.tfs + (size_t)k * 12, a.pts[(size_t)j * 3], a.pts[(size_t)j * 3 + 1], a.pts[(size_t)j * 3 + 2], px[q], py[q], pz[q]);
+      transform_point(a.tfs + (size_t)k * a.tf_stride, a.pts[(size_t)j * 3], a.pts[(size_t)j * 3 + 1], a.pts[(size_t)j * 3 + 2], px[q], py[q], pz[q]);
       if (a.q_out && blockIdx.y == 0 && i == q0 + q * SD_THREADS + tid)
         a.q_out[(size_t)i * 3] = px[q], a.q_out[(size_t)i * 3 + 1] = py[q], a.q_out[(size_t)i * 3 + 2] = pz[q];
     } else {
@@ -222,6 +233,100 @@ __global__ __launch_bounds__(SD_THREADS) void surfdist_finish_kernel(SurfDistArg
     cx = r.ax + qx, cy = r.ay + qy, cz = r.az + qz;
   }
   closest[(size_t)i * 3] = cx, closest[(size_t)i * 3 + 1] = cy, closest[(size_t)i * 3 + 2] = cz;
+}
+
+// ---- rigid alignment: the rows and the 29 sums of one linearisation (fp_points_mesh_align) ---------------------------------------------
+// One of the aligners of gn_sums.h: a workgroup owns (pose, a tile of GN_TILE source points); the pose is uniform in the workgroup.  A
+// point's query is formed again by transform_point - the bits the search saw -, its key is unpacked and the winning pair evaluated again
+// as in surfdist_finish_kernel; from e = y - closest on, plain products, sums and differences (the header's rule).  ROWS rows a point:
+// one (point to plane) or three (point to point, in axis order, the count on the first).  A wave past the pose's last point has +0.0
+// sums and nothing to write.
+struct MeshAlignArgs {
+  const float *pts;        // (n, 3)
+  const float *poses;      // (N, 16)
+  const float *pos;        // (V, 3)
+  const int32_t *faces;    // (F, 3)
+  const u64 *keys;         // [N n], as the search left them
+  int n, V, n_tiles;
+  float dist_max;
+  float *dist;             // (N n) or null
+  int32_t *face;           // (N n) or null
+  float *closest, *normal; // (N n, 3) or null
+  float *rows;             // (N n, ROWS, 8) or null
+  double *slab;            // [N][n_tiles][GN_TERMS]
+};
+
+template <int ROWS>
+__global__ __launch_bounds__(GN_THREADS) void mesh_align_kernel(MeshAlignArgs a) {
+  static_assert(ROWS == 1 || ROWS == 3, "point to plane or point to point");
+  __shared__ double red[GN_THREADS / 64][GN_TERMS];
+  const int tid = threadIdx.x;
+  const int tile = blockIdx.x % a.n_tiles, pr = blockIdx.x / a.n_tiles;
+  const float *P = a.poses + (size_t)pr * 16;                      // uniform: scalar loads
+  const float t0 = P[3], t1 = P[7], t2 = P[11];
+  const size_t item0 = (size_t)pr * (size_t)a.n;
+  int pix[GN_PIX];
+  bool ok[GN_PIX];
+#pragma unroll
+  for (int q = 0; q < GN_PIX; ++q) {
+    pix[q] = tile * GN_TILE + q * GN_THREADS + tid;
+    ok[q] = pix[q] < a.n;                                          // the last tile of a pose is ragged
+  }
+  if (!gn_empty_wave<ROWS * 8>(ok, a.rows, item0, pix, a.n, red[tid >> 6])) {
+    double acc[GN_TERMS];
+#pragma unroll
+    for (int e = 0; e < GN_TERMS; ++e) acc[e] = 0.0;
+    const float nan = __builtin_nanf("");
+#pragma unroll
+    for (int q = 0; q < GN_PIX; ++q) {
+      const size_t i = ok[q] ? (size_t)pix[q] : 0, g = item0 + i;
+      float y0, y1, y2;
+      transform_point(P, a.pts[i * 3], a.pts[i * 3 + 1], a.pts[i * 3 + 2], y0, y1, y2);
+      const u64 key = ok[q] ? a.keys[g] : ~(u64)0;
+      const int f = (int)(unsigned)(key & 0xffffffffu);
+      const bool found = key != ~(u64)0;
+      const float dist = found ? sqrtf(__uint_as_float((unsigned)(key >> 32))) : nan;      // as surfdist_finish_kernel
+      float cx = nan, cy = nan, cz = nan, nx = 0.f, ny = 0.f, nz = 0.f;
+      bool triangle = false;
+      if (found) {
+        const FaceRec r = face_record(a.pos, a.V, a.faces, f);
+        float qx, qy, qz;
+        (void)pair_d2(r, r.flag != SD_FLAG_TRIANGLE, y0, y1, y2, qx, qy, qz);
+        cx = r.ax + qx, cy = r.ay + qy, cz = r.az + qz;
+        nx = r.nx, ny = r.ny, nz = r.nz;
+        triangle = r.flag == SD_FLAG_TRIANGLE;
+      }
+      if (ok[q]) {
+        if (a.dist) a.dist[g] = dist;
+        if (a.face) a.face[g] = found ? f : -1;
+        if (a.closest) a.closest[g * 3] = cx, a.closest[g * 3 + 1] = cy, a.closest[g * 3 + 2] = cz;
+        if (a.normal) a.normal[g * 3] = nx, a.normal[g * 3 + 1] = ny, a.normal[g * 3 + 2] = nz;
+      }
+      const float e[3] = {y0 - cx, y1 - cy, y2 - cz};
+      const float X0 = y0 - t0, X1 = y1 - t1, X2 = y2 - t2;
+      const bool within = found && dist <= a.dist_max;               // NaN fails
+      if (ROWS == 1) {
+        const bool valid = within && triangle;
+        float r = (nx * e[0] + ny * e[1]) + nz * e[2], J[6];
+        gn_twist_row(J, nx, ny, nz, X0, X1, X2);
+        gn_mask(J, r, valid);
+        if (a.rows && ok[q]) gn_store_row((float4 *)(a.rows + g * 8), J, r, valid);
+        gn_accumulate(acc, J, r, valid);
+      } else {
+#pragma unroll
+        for (int ax = 0; ax < 3; ++ax) {
+          float r = e[ax], J[6];
+          gn_twist_row(J, ax == 0 ? 1.f : 0.f, ax == 1 ? 1.f : 0.f, ax == 2 ? 1.f : 0.f, X0, X1, X2);
+          gn_mask(J, r, within);
+          if (a.rows && ok[q]) gn_store_row((float4 *)(a.rows + (g * 3 + ax) * 8), J, r, within && ax == 0);      // the count rides on the first row
+          gn_accumulate(acc, J, r, within && ax == 0);
+        }
+      }
+    }
+    gn_wave_to_lds(acc, red[tid >> 6], 0);
+  }
+  __syncthreads();
+  gn_lds_to_slab(red, a.slab + ((size_t)pr * a.n_tiles + tile) * GN_TERMS);
 }
 
 // ---- statistics of a distance array ---------------------------------------------------------------------------------------------------
@@ -497,7 +602,7 @@ extern "C" int fp_point_mesh_distance(fp_ctx *ctx, const float *d_points, int n,
   FP_CHECK_HIP(hipMemsetAsync(keys, 0xff, bytes, s));
   const int tiles = (n + SD_TILE - 1) / SD_TILE, chunks = (F + SD_CHUNK - 1) / SD_CHUNK;
   const int slices = std::min(chunks, std::max(1, (SD_MIN_GROUPS + tiles - 1) / tiles));
-  SurfDistArgs a{d_points, d_pos, d_faces, n, V, F, (chunks + slices - 1) / slices, keys, nullptr, 0, nullptr};
+  SurfDistArgs a{d_points, d_pos, d_faces, n, V, F, (chunks + slices - 1) / slices, keys, nullptr, 0, 0, nullptr};
   const int slices_used = (chunks + a.chunks_per_slice - 1) / a.chunks_per_slice;
   hipLaunchKernelGGL(surfdist_kernel<false>, dim3((unsigned)tiles, (unsigned)slices_used), dim3(SD_THREADS), 0, s, a);
   FP_CHECK_HIP(hipGetLastError());
@@ -539,7 +644,7 @@ extern "C" int fp_symmetry_residuals(fp_ctx *ctx, const float *d_points, int n, 
   st.keys = keys;
   FP_CHECK_HIP(hipMemsetAsync(keys, 0xff, key_bytes, s));
   const int slices = std::min(chunks, std::max(1, (SD_MIN_GROUPS + tiles - 1) / tiles));
-  SurfDistArgs a{d_points, d_pos, d_faces, total, V, F, (chunks + slices - 1) / slices, keys, d_tfs, n, d_q};
+  SurfDistArgs a{d_points, d_pos, d_faces, total, V, F, (chunks + slices - 1) / slices, keys, d_tfs, n, 12, d_q};
   const int slices_used = (chunks + a.chunks_per_slice - 1) / a.chunks_per_slice;
   hipLaunchKernelGGL(surfdist_kernel<true>, dim3((unsigned)tiles, (unsigned)slices_used), dim3(SD_THREADS), 0, s, a);
   FP_CHECK_HIP(hipGetLastError());
@@ -548,6 +653,137 @@ extern "C" int fp_symmetry_residuals(fp_ctx *ctx, const float *d_points, int n, 
   hipLaunchKernelGGL(sym_stats_finish_kernel, dim3((unsigned)(((long long)T * n_terms + DS_THREADS - 1) / DS_THREADS)), dim3(DS_THREADS), 0, s,
                      (const double *)st.slab, st.n_cols, n, T, n_terms, d_stats);
   FP_CHECK_HIP(hipGetLastError());
+  return FP_OK;
+}
+
+namespace {
+
+struct MeshAlignOut {
+  float *q, *dist;
+  int32_t *face;
+  float *closest, *normal, *rows;
+};
+
+// the value checks the two calls share; nothing here looks into ctx
+int mesh_align_checks(const char *fn, const float *d_points, int n, int N, int V, int F, const void *d_keys) {
+  FP_REQUIRE(N >= 0 && N <= FP_POSE_ALIGN_MAX_POSES, "%s: N %d (0 .. %d)", fn, N, FP_POSE_ALIGN_MAX_POSES);
+  FP_REQUIRE(n >= 0 && (long long)N * n <= FP_SURFDIST_MAX_POINTS, "%s: N %d, n %d (n at least 0, N n at most %d)", fn, N, n, FP_SURFDIST_MAX_POINTS);
+  FP_REQUIRE(V >= 1 && F >= 1 && F <= FP_SURFDIST_MAX_FACES, "%s: V %d, F %d (at least 1; at most %d faces)", fn, V, F, FP_SURFDIST_MAX_FACES);
+  FP_REQUIRE(d_points || n == 0, "%s: d_points null with n %d", fn, n);
+  FP_REQUIRE(((uintptr_t)d_keys & 7) == 0, "%s: d_keys is not 8-byte aligned", fn);
+  return FP_OK;
+}
+
+int mesh_align_stage_checks(const char *fn, int mode, float dist_max) {
+  FP_REQUIRE(mode == FP_MESH_ALIGN_PLANE || mode == FP_MESH_ALIGN_POINT, "%s: mode %d (FP_MESH_ALIGN_PLANE or FP_MESH_ALIGN_POINT)", fn, mode);
+  FP_REQUIRE(dist_max > 0.f, "%s: dist_max %g (> 0)", fn, (double)dist_max);
+  return FP_OK;
+}
+
+int mesh_align_tiles(int n) { return (n + GN_TILE - 1) / GN_TILE; }      // <= 2^14, times 1024 poses: inside a grid
+size_t mesh_align_slab_bytes(int N, int n) { return (size_t)N * (size_t)mesh_align_tiles(n) * GN_TERMS * sizeof(double); }
+
+// Sets n 64-bit words: the keys to all ones, the records of d_state and empty sums to zero bytes.  A launch, not hipMemsetAsync: these
+// calls are made to sit in a captured graph, and no captured path of the library holds a memset node.
+__global__ __launch_bounds__(256) void fill_words_kernel(u64 *__restrict__ p, size_t n, u64 value) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) p[i] = value;
+}
+
+int launch_fill_words(u64 *p, size_t n, u64 value, hipStream_t s) {
+  if (n == 0) return FP_OK;
+  hipLaunchKernelGGL(fill_words_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p, n, value);
+  FP_CHECK_HIP(hipGetLastError());
+  return FP_OK;
+}
+
+// the launches of one linearisation, N >= 1: the keys set to all ones, the search, the rows, the fold.  `slab` holds
+// mesh_align_slab_bytes.  With h_sums the sums are copied there and the stream is synchronised; without, nothing synchronises
+int launch_mesh_align(const float *pts, int n, const float *poses, int N, const float *pos, int V, const int32_t *faces, int F, int mode,
+                      float dist_max, u64 *keys, const MeshAlignOut &o, double *slab, double *sums, double *h_sums, hipStream_t s) {
+  if (n == 0) {                           // no rows: zero sums
+    FP_TRY(launch_fill_words((u64 *)sums, (size_t)N * GN_TERMS, 0, s));
+    if (h_sums) {
+      memset(h_sums, 0, (size_t)N * GN_TERMS * sizeof(double));
+      FP_CHECK_HIP(hipStreamSynchronize(s));
+    }
+    return FP_OK;
+  }
+  const int total = N * n;
+  FP_TRY(launch_fill_words(keys, (size_t)total, ~(u64)0, s));
+  const int tiles = (total + SD_TILE - 1) / SD_TILE, chunks = (F + SD_CHUNK - 1) / SD_CHUNK;
+  const int slices = std::min(chunks, std::max(1, (SD_MIN_GROUPS + tiles - 1) / tiles));
+  SurfDistArgs a{pts, pos, faces, total, V, F, (chunks + slices - 1) / slices, keys, poses, n, 16, o.q};
+  const int slices_used = (chunks + a.chunks_per_slice - 1) / a.chunks_per_slice;
+  hipLaunchKernelGGL(surfdist_kernel<true>, dim3((unsigned)tiles, (unsigned)slices_used), dim3(SD_THREADS), 0, s, a);
+  FP_CHECK_HIP(hipGetLastError());
+  const int n_tiles = mesh_align_tiles(n);
+  MeshAlignArgs m{pts, poses, pos, faces, keys, n, V, n_tiles, dist_max, o.dist, o.face, o.closest, o.normal, o.rows, slab};
+  if (mode == FP_MESH_ALIGN_PLANE)
+    hipLaunchKernelGGL(mesh_align_kernel<1>, dim3((unsigned)(n_tiles * N)), dim3(GN_THREADS), 0, s, m);
+  else
+    hipLaunchKernelGGL(mesh_align_kernel<3>, dim3((unsigned)(n_tiles * N)), dim3(GN_THREADS), 0, s, m);
+  FP_CHECK_HIP(hipGetLastError());
+  return gn_fold_to_host<GN_TERMS>(slab, N, n_tiles, sums, h_sums, s);
+}
+
+}  // namespace
+
+extern "C" int fp_points_mesh_align(fp_ctx *ctx, const float *d_points, int n, const float *d_poses, int N, const float *d_pos, int V,
+                                    const int32_t *d_faces, int F, int mode, float dist_max, uint64_t *d_keys, float *d_q, float *d_dist,
+                                    int32_t *d_face, float *d_closest, float *d_normal, float *d_rows, double *d_sums, double *h_sums,
+                                    void *stream) {
+  // Every check of a value comes before the first look INTO ctx, as in pose_icp.hip: tests/test_mesh_align_host.py calls this without a
+  // GPU, with a pointer for ctx that must not be dereferenced.
+  FP_REQUIRE(ctx && d_poses && d_pos && d_faces && d_keys && d_sums, "fp_points_mesh_align: null argument");
+  FP_TRY(mesh_align_checks("fp_points_mesh_align", d_points, n, N, V, F, d_keys));
+  FP_TRY(mesh_align_stage_checks("fp_points_mesh_align", mode, dist_max));
+  FP_REQUIRE(((uintptr_t)d_rows & 15) == 0, "fp_points_mesh_align: d_rows is not 16-byte aligned (it is written as float4)");
+  if (N == 0) return FP_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const size_t slab_bytes = mesh_align_slab_bytes(N, n);
+  FP_TRY(fp_arena_ensure(ctx, slab_bytes + 4096));
+  // the slab goes back to the arena when the launches are queued (with h_sums: synchronised) - the next taker runs behind them on the same stream
+  ArenaScope scope(ctx->arena);
+  double *slab = (double *)ctx->arena.take(slab_bytes);
+  FP_REQUIRE(slab, "fp_points_mesh_align: arena exhausted");
+  const MeshAlignOut o{d_q, d_dist, d_face, d_closest, d_normal, d_rows};
+  return launch_mesh_align(d_points, n, d_poses, N, d_pos, V, d_faces, F, mode, dist_max, (u64 *)d_keys, o, slab, d_sums, h_sums, s);
+}
+
+extern "C" int fp_points_mesh_polish(fp_ctx *ctx, const float *d_points, int n, float *d_poses, int N, const float *d_pos, int V,
+                                     const int32_t *d_faces, int F, const fp_mesh_align_stage *h_stages, int n_stages, double damping,
+                                     int min_points, fp_pose_state *d_state, double *d_sums, uint64_t *d_keys, void *stream) {
+  // As above: every check of a value before the first look into ctx.
+  FP_REQUIRE(ctx && d_poses && d_pos && d_faces && d_keys && d_sums && d_state && h_stages, "fp_points_mesh_polish: null argument");
+  FP_TRY(mesh_align_checks("fp_points_mesh_polish", d_points, n, N, V, F, d_keys));
+  FP_REQUIRE(((uintptr_t)d_state & 7) == 0, "fp_points_mesh_polish: d_state is not 8-byte aligned");
+  FP_REQUIRE(n_stages >= 1 && n_stages <= FP_MESH_ALIGN_MAX_STAGES, "fp_points_mesh_polish: n_stages %d (1 .. %d)", n_stages, FP_MESH_ALIGN_MAX_STAGES);
+  for (int k = 0; k < n_stages; ++k) {
+    FP_TRY(mesh_align_stage_checks("fp_points_mesh_polish", h_stages[k].mode, h_stages[k].dist_max));
+    FP_REQUIRE(h_stages[k].iterations >= 0 && h_stages[k].iterations <= FP_POSE_POLISH_MAX_ITERATIONS,
+               "fp_points_mesh_polish: stage %d has %d iterations (0 .. %d)", k, h_stages[k].iterations, FP_POSE_POLISH_MAX_ITERATIONS);
+  }
+  FP_REQUIRE(damping >= 0.0 && isfinite(damping), "fp_points_mesh_polish: damping %g (>= 0, finite)", damping);
+  FP_REQUIRE(min_points >= 1, "fp_points_mesh_polish: min_points %d (>= 1)", min_points);
+  if (N == 0) return FP_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const size_t slab_bytes = mesh_align_slab_bytes(N, n);
+  FP_TRY(fp_arena_ensure(ctx, slab_bytes + 4096));
+  // the slab goes back when the launches are queued - the next taker runs behind them on the same stream
+  ArenaScope scope(ctx->arena);
+  double *slab = (double *)ctx->arena.take(slab_bytes);
+  FP_REQUIRE(slab, "fp_points_mesh_polish: arena exhausted");
+  const MeshAlignOut none{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  for (int k = 0; k < n_stages; ++k) {
+    const fp_mesh_align_stage &st = h_stages[k];
+    const bool last = k == n_stages - 1;
+    FP_TRY(launch_fill_words((u64 *)d_state, (size_t)N * (sizeof(fp_pose_state) / sizeof(u64)), 0, s));      // every stage starts fresh records
+    for (int it = 0; it < st.iterations + (last ? 1 : 0); ++it) {                         // the last stage ends with the closing round
+      FP_TRY(launch_mesh_align(d_points, n, d_poses, N, d_pos, V, d_faces, F, st.mode, st.dist_max, (u64 *)d_keys, none, slab, d_sums, nullptr, s));
+      FP_TRY(fp_pose_gn_step(ctx, d_sums, d_poses, d_state, N, damping, min_points, last && it == st.iterations, stream));
+    }
+  }
   return FP_OK;
 }
 

@@ -755,13 +755,18 @@ def segment_views(views, keep='central', device='cuda', **kw):
 
 def reconstruct_object(views, voxel_size=0.002, trunc=None, min_weight=1, depth_filter=True, margin=None, device='cuda', refine_poses=False,
                        max_vertices=None, simplify_cell=None, components='largest', texture=None, symmetries=None, estimate_poses=False,
-                       photometric=False, segment=False):
+                       photometric=False, segment=False, align_to=None):
   """_reconstruct_mesh (which documents every other argument) and, with `symmetries`, the rotational symmetries of the finished mesh:
   symmetries=True runs Utils.find_symmetries with its defaults, a dict gives its keyword arguments (tol, max_order, ..), and the call
   then returns (mesh, info) - info['symmetry_tfs'] is what FoundationPose(symmetry_tfs=) takes, and bop.write_models_info writes the
   rest to models_info.json.  The default (None or False) returns the mesh alone, as before.
   segment (False, True or a dict of segment_views' keyword arguments) is for views WITHOUT masks, of an object standing on a plane:
-  segment_views makes them from the depth maps first; a folder is then read without mask/.  Views that have masks keep them."""
+  segment_views makes them from the depth maps first; a folder is then read without mask/.  Views that have masks keep them.
+  align_to (default None: the mesh in the frame the poses define) is a mesh of the same object, e.g. its CAD model: the finished mesh is
+  laid onto it with Utils.align_to_mesh (a dict {'mesh': .., and align_to_mesh's keyword arguments} sets them) and returned in THAT
+  mesh's frame, and the call returns (mesh, info) with info['model_from_reconstruction'] (4,4) float64 - cam_in_ob of a view in the
+  model's frame is that matrix times the view's pose - and info['align'], align_to_mesh's info: with estimate_poses the object frame is
+  otherwise `view 0's camera moved to the object`, which no ground truth is given in.  Symmetries, if asked for, are found after it."""
   if segment is not False and segment is not None:
     if isinstance(views, (str, os.PathLike)):
       views = load_reference_views(views, poses=not estimate_poses, masks=False)
@@ -770,11 +775,19 @@ def reconstruct_object(views, voxel_size=0.002, trunc=None, min_weight=1, depth_
   mesh = _reconstruct_mesh(views, voxel_size=voxel_size, trunc=trunc, min_weight=min_weight, depth_filter=depth_filter, margin=margin,
                            device=device, refine_poses=refine_poses, max_vertices=max_vertices, simplify_cell=simplify_cell,
                            components=components, texture=texture, estimate_poses=estimate_poses, photometric=photometric)
+  info = {}
+  if align_to is not None:
+    from .Utils import align_to_mesh, transform_mesh
+    kw = dict(align_to) if isinstance(align_to, dict) else dict(mesh=align_to)
+    with torch.cuda.device(_device(device)):
+      T, ainfo = align_to_mesh(mesh, kw.pop('mesh'), **kw)
+    mesh = transform_mesh(mesh, T)
+    info.update(model_from_reconstruction=T, align=ainfo)
   if symmetries is None or symmetries is False:
-    return mesh
+    return (mesh, info) if align_to is not None else mesh
   from .Utils import find_symmetries
   with torch.cuda.device(_device(device)):
-    return mesh, find_symmetries(mesh, **(symmetries if isinstance(symmetries, dict) else {}))
+    return mesh, dict(find_symmetries(mesh, **(symmetries if isinstance(symmetries, dict) else {})), **info)
 
 
 def _reconstruct_mesh(views, voxel_size=0.002, trunc=None, min_weight=1, depth_filter=True, margin=None, device='cuda', refine_poses=False,

@@ -1340,6 +1340,65 @@ int fp_symmetry_residuals(fp_ctx *ctx, const float *d_points, int n, const float
                           const int32_t *d_faces, int F, const double *h_taus, int n_taus, double *d_stats, float *d_q, float *d_dist,
                           void *stream);
 
+/* Rigid alignment of a point set to a mesh: one Gauss-Newton linearisation of ICP against the EXACT nearest triangle for N poses at
+ * once (fp_points_mesh_align) and the loop of it with fp_pose_gn_step behind it (fp_points_mesh_polish).  The reference has no such
+ * step.  tests/mesh_align_oracle.py restates the rows in fp32 numpy, operation for operation.
+ *   d_points (n,3) float32: the source points, in the source's frame.  d_poses (N,4,4) float32 row-major, "target from source"; the
+ * first 12 floats of a pose are the (3,4) record [R|t] of fp_symmetry_residuals, read in place (a transform stride of 16 floats).
+ * d_pos (V,3), d_faces (F,3): the target.  d_keys: N n 64-bit words of the caller's, 8-byte aligned, scratch.
+ *   Search.  The query of (pose k, point i) is y = R_k p_i + t_k by fp_symmetry_residuals' rule; d_keys is set to all ones - by a small
+ * launch, not a memset node: the call is made to sit in a captured graph, and no captured path of the library holds one - and the
+ * search kernel of fp_point_mesh_distance runs over the N n queries.  dist, face and closest of a query are bit for bit what
+ * fp_point_mesh_distance returns for the point y.
+ *   Rows.  Per query, fp32, nothing contracted, every operation written out:
+ *     c = closest, nu = the record's unit normal of the winning face (zeros for a degenerate face), t = (pose[3], pose[7], pose[11])
+ *     e = y - c;  X = y - t
+ *     valid = a face was found and dist <= dist_max (the fp32 value written to d_dist: NaN fails)
+ *     FP_MESH_ALIGN_PLANE, one row:  valid = valid and the winning face is not degenerate
+ *       r = (nu.x e.x + nu.y e.y) + nu.z e.z;   J = (nu.x, nu.y, nu.z, X.y nu.z - X.z nu.y, X.z nu.x - X.x nu.z, X.x nu.y - X.y nu.x)
+ *     FP_MESH_ALIGN_POINT, three rows, a = 0, 1, 2 in that order:  r = e[a];  J as above with nu = the unit vector of axis a
+ *   The face normal, not the direction e / |e|: e vanishes at the solution, so its direction is noise exactly where the last steps are
+ * taken, and off an edge or a vertex it is not the normal of any plane of the model.
+ *   J is dr / dxi for R <- exp([w]) R, t <- t + tau, xi = (tau, w) in the target's frame, about the pose's own translation: the twist
+ * fp_pose_gn_step applies.  An invalid point is a zero row.  d_sums (N,29) float64, device: the terms of fp_pose_depth_align in the
+ * same order, formed and added as csrc/gn_sums.h states - one workgroup per (pose, tile of 1024 points), 256 threads x 4 points, a
+ * lane's rows in point order and within a point in axis order, the butterfly, the waves, then the tiles by a second launch.  In POINT
+ * mode only the row of axis 0 carries the count: term 28 counts points and term 27 is the sum of e.e, the squared distances.  No float
+ * atomics (the one integer atomicMin per (query, face slice) is the search's): a pose's 29 numbers are bit-identical from run to run,
+ * in any batch and at any index of it.
+ *   Optional outputs, device, each may be null: d_q (N,n,3) the queries; d_dist (N,n); d_face (N,n) int32; d_closest (N,n,3); d_normal
+ * (N,n,3) nu (zeros where no face was found); d_rows (N,n,R,8), R = 1 (PLANE) or 3 (POINT), 16-byte aligned: (J0 .. J5, r, flag) per row,
+ * flag = 1 on the row that carries the count (POINT: the row of axis 0) and 0 on the other two; eight zeros for an invalid point.  h_sums, when not null, HOST (N,29): the call copies d_sums there and SYNCHRONISES; without it
+ * nothing synchronises.  The arena holds the partial sums only (N tiles 232 bytes).
+ *   Loop.  fp_points_mesh_polish takes n_stages <= FP_MESH_ALIGN_MAX_STAGES records (mode, dist_max, iterations) from the host.  Every
+ * stage first sets the N records of d_state to zero bytes (a pose that stopped because its residual rose has converged at that
+ * stage's gate and is taken up again by the next), then enqueues `iterations` rounds of (the keys set to all ones, the search, the
+ * rows and their fold, fp_pose_gn_step with min_points in the place of min_pixels).  After the last stage one closing round at that
+ * stage's mode and gate, closing = 1: d_state holds the fit of the returned poses and describes the last stage alone.  Nothing
+ * synchronises and nothing is read on the host; with the arena reserved the call sits in a captured graph and replays bit for bit.  It
+ * equals the same launches issued through the public calls.
+ *   Work: N n F pair tests per round at the rate of fp_point_mesh_distance - no spatial cull.  Rigid only, no scale.  Align the PARTIAL
+ * surface to the COMPLETE one: every source point looks for a partner, so source points without a counterpart pull.
+ *   FP_EINVAL, each checked before ctx is looked into: a null ctx, d_poses, d_pos, d_faces, d_keys or d_sums (polish: d_state, h_stages);
+ * d_points null with n > 0; N outside 0 .. FP_POSE_ALIGN_MAX_POSES; n < 0; N n above FP_SURFDIST_MAX_POINTS; V < 1; F outside
+ * 1 .. FP_SURFDIST_MAX_FACES; a mode that is neither of the two; dist_max not > 0; d_keys or d_state not 8-byte, d_rows not 16-byte
+ * aligned; n_stages outside 1 .. FP_MESH_ALIGN_MAX_STAGES; iterations of a stage outside 0 .. FP_POSE_POLISH_MAX_ITERATIONS; damping
+ * negative or not finite; min_points < 1.  N = 0 writes nothing; n = 0 writes zero sums. */
+#define FP_MESH_ALIGN_PLANE 0             /* point to plane: one row per point */
+#define FP_MESH_ALIGN_POINT 1             /* point to point: three rows per point */
+#define FP_MESH_ALIGN_MAX_STAGES 8
+typedef struct fp_mesh_align_stage {
+  int32_t mode;                           /* FP_MESH_ALIGN_* */
+  float dist_max;                         /* the gate, in the mesh's unit */
+  int32_t iterations;
+} fp_mesh_align_stage;
+int fp_points_mesh_align(fp_ctx *ctx, const float *d_points, int n, const float *d_poses, int N, const float *d_pos, int V,
+                         const int32_t *d_faces, int F, int mode, float dist_max, uint64_t *d_keys, float *d_q, float *d_dist,
+                         int32_t *d_face, float *d_closest, float *d_normal, float *d_rows, double *d_sums, double *h_sums, void *stream);
+int fp_points_mesh_polish(fp_ctx *ctx, const float *d_points, int n, float *d_poses, int N, const float *d_pos, int V,
+                          const int32_t *d_faces, int F, const fp_mesh_align_stage *h_stages, int n_stages, double damping, int min_points,
+                          fp_pose_state *d_state, double *d_sums, uint64_t *d_keys, void *stream);
+
 /* n points on the surface of a mesh, area-weighted, stratified along the face order, a function of (mesh, n, seed) alone.
  *   Face choice, exact.  area_f = 0.5 |ab x ac| in double from the fp32 positions (edge differences, cross product and square root in
  * double; 0 for a face with an index outside [0, V) or a non-finite area), A = their double sum, area_q[f] = rint(area_f / A 2^40) as
