@@ -24,6 +24,7 @@ from .reproject import align_frame, gather_by_source, reproject_depth, rgbd_rig 
 from .detect import TemplateSet, build_templates, detect, match_templates, templates_from_depths  # noqa: F401  (objects without a mask; a build extension)
 from .pose_icp import align_poses_step, polish_poses, pose_gn_step  # noqa: F401  (polishing poses against depth; a build extension)
 from .mesh_align import align_points_step, align_to_mesh, transform_mesh  # noqa: F401  (a mesh or a point cloud onto a model; a build extension)
+from .bounds import box_extents, oriented_bounds  # noqa: F401  (the minimum-volume box of a model, main.py:38-39; a build extension)
 from .vis import cv_draw_text, depth_to_vis, make_grid_image  # noqa: F401  (src/Utils.py:630-653, 456-478, 293-300)
 
 glcam_in_cvcam = np.array([[1, 0, 0, 0],
@@ -1170,10 +1171,15 @@ def project_3d_to_2d(pt, K, ob_in_cam):
   return uvw[:2].round().astype(int)
 
 
-def model_box(mesh_or_pts):
+def model_box(mesh_or_pts, oriented=False):
   """(to_origin (4,4), bbox (2,3)) of a model in the shape main.py:38-39 builds: bbox = [-extents / 2, extents / 2] and to_origin moves the
-  model into it, so that a pose of the model is drawn with `pose @ inv(to_origin)`.  This is the AXIS-ALIGNED box about the middle of
-  the vertices' extent; trimesh's minimum-volume `oriented_bounds`, which the reference calls, is out of scope."""
+  model into it, so that a pose of the model is drawn with `pose @ inv(to_origin)`.  By default this is the AXIS-ALIGNED box about the
+  middle of the vertices' extent.  oriented=True takes the minimum-volume box that the reference asks of trimesh, from
+  Utils.oriented_bounds (the candidate class, the convention of axes and signs and the limits are stated there; the search runs on
+  the device and hull and frame building take a few tenths of a second on an 8 000-vertex model, so cache the pair)."""
+  if oriented:
+    to_origin, extents = oriented_bounds(mesh_or_pts)
+    return to_origin, np.stack([-extents / 2, extents / 2], axis=0)
   pts = np.asarray(getattr(mesh_or_pts, 'vertices', mesh_or_pts), dtype=np.float64).reshape(-1, 3)
   lo, hi = pts.min(axis=0), pts.max(axis=0)
   to_origin = np.eye(4)

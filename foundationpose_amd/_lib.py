@@ -22,6 +22,8 @@ FP_ERR_ADD, FP_ERR_ADDS, FP_ERR_ADD_SYM = 1, 2, 4      # fp_pose_errors' `which`
 FP_BOP_MSSD, FP_BOP_MSPD = 1, 2                       # fp_pose_errors_bop's `which` bits
 FP_VSD_MAX_TAUS = 32
 FP_MESH_DIAMETER_MAX_POINTS = 1 << 21                     # fp_mesh_diameter's largest n_pts
+FP_BOX_EXTENTS_MAX_POINTS, FP_BOX_EXTENTS_MAX_FRAMES, FP_BOX_EXTENTS_MAX_EVALS = 1 << 21, 1 << 24, 1 << 40      # fp_box_extents
+FP_BOX_EXTENTS_TILE, FP_BOX_EXTENTS_CAND = 1024, 1024    # points of its LDS tile, candidates of its workgroup
 FP_MESH_SIMPLIFY_MAX_VERTICES, FP_MESH_SIMPLIFY_MAX_FACES = 1 << 21, 1 << 23      # fp_mesh_simplify_count
 FP_MESH_COMPONENTS_MAX_VERTICES, FP_MESH_COMPONENTS_MAX_FACES = 1 << 21, 1 << 23  # fp_mesh_components_count
 FP_SCENE_MAX_INSTANCES = 1024                             # fp_scene_instances
@@ -217,6 +219,7 @@ _PROTOS = {
   'fp_vsd': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_double, c_void_p, c_int,
                      c_void_p, c_void_p, c_void_p]),
   'fp_mesh_diameter': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+  'fp_box_extents': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
   'fp_mesh_simplify_count': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_float, c_void_p, c_void_p]),
   'fp_mesh_simplify_write': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_int64, c_int64, c_void_p]),

@@ -528,6 +528,23 @@ extern "C" int fp_mesh_diameter(fp_ctx *ctx, const float *d_pts, int n_pts, floa
   return launch_mesh_diameter(d_pts, n_pts, slab, d_out_diameter, d_out_pair, (hipStream_t)stream);
 }
 
+extern "C" int fp_box_extents(fp_ctx *ctx, const float *d_points, int n, const float *d_frames, int C, int32_t *d_best_index, float *d_best_lohi,
+                              float *d_best_volume, float *d_all_lohi, float *d_all_volume, void *stream) {
+  FP_REQUIRE(ctx && d_points && d_frames && d_best_index && d_best_lohi && d_best_volume, "fp_box_extents: null argument");
+  FP_REQUIRE(n >= 1 && n <= FP_BOX_EXTENTS_MAX_POINTS, "fp_box_extents: n %d (1 .. %d)", n, FP_BOX_EXTENTS_MAX_POINTS);
+  FP_REQUIRE(C >= 1 && C <= FP_BOX_EXTENTS_MAX_FRAMES, "fp_box_extents: C %d (1 .. %d)", C, FP_BOX_EXTENTS_MAX_FRAMES);
+  FP_REQUIRE((long long)n * C <= FP_BOX_EXTENTS_MAX_EVALS, "fp_box_extents: n C = %lld above %lld: cut the candidates into several calls",
+             (long long)n * C, (long long)FP_BOX_EXTENTS_MAX_EVALS);
+  const size_t bytes = box_extents_slab_bytes(n, C);
+  FP_TRY(fp_arena_ensure(ctx, bytes + 4096));
+  ArenaScope scope(ctx->arena);
+  void *slab = ctx->arena.take(bytes);
+  FP_REQUIRE(slab, "fp_box_extents: arena exhausted");
+  // the slab is consumed by the finishing launches on the same stream before anything else takes it
+  return launch_box_extents(d_points, n, d_frames, C, slab, d_best_index, d_best_lohi, d_best_volume, d_all_lohi, d_all_volume,
+                            (hipStream_t)stream);
+}
+
 // poses per render chunk of fp_vsd: their depth images (and those of their ground truth, one per pose) within this many bytes
 static const size_t kVsdDepthBudget = (size_t)512 << 20;
 

@@ -578,6 +578,11 @@ int launch_pose_errors(const float *pts, int n_pts, const float *pred, const flo
 // bytes of per-workgroup candidates
 size_t mesh_diameter_slab_bytes(int n_pts);
 int launch_mesh_diameter(const float *pts, int n_pts, void *slab, float *out, int32_t *pair, hipStream_t s);
+// bounds.hip: the boxes of n points in C frames and the smallest of them (fp_box_extents); `slab` holds box_extents_slab_bytes(n, C)
+// bytes: the bounds per (point slice, candidate) and the per-workgroup winners
+size_t box_extents_slab_bytes(int n, int C);
+int launch_box_extents(const float *pts, int n, const float *frames, int C, void *slab, int32_t *out_index, float *out_lohi, float *out_vol,
+                       float *all_lohi, float *all_vol, hipStream_t s);
 // scan.hip: in-place exclusive scan of n 64-bit words (reduce, scan of the block sums, add: a workgroup never waits for another one);
 // `sums` holds scan_sums_words(n) words for the block sums of every level
 size_t scan_sums_words(long long n);

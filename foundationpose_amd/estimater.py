@@ -105,6 +105,7 @@ class FoundationPose:
     # tracking workspaces (and their captured graphs) hold the previous object's mesh handle and centre: none survives a new object
     self._track_ws = {}
     self._templates = None          # the cached TemplateSet of detect: (build keywords, set)
+    self._model_box = {}            # model_box's pairs of this object, by `oriented`
     logging.info("reset done")
 
   def instance(self):
@@ -115,6 +116,16 @@ class FoundationPose:
     other._track_ws = {}
     other.pose_last = other.poses = other.scores = other.best_id = None
     return other
+
+  def model_box(self, oriented=False):
+    """Utils.model_box of the ORIGINAL mesh (the frame the returned poses are in): (to_origin (4,4), bbox (2,3)), so that main.py:67's
+    center_pose is `pose @ inv(to_origin)`.  oriented=True is the minimum-volume box of Utils.oriented_bounds - hull and search cost
+    a few tenths of a second, so the pair is kept per object until the next reset_object.  Copies are returned."""
+    key = bool(oriented)
+    if key not in self._model_box:
+      self._model_box[key] = U.model_box(self.mesh_ori, oriented=key)
+    to_origin, bbox = self._model_box[key]
+    return to_origin.copy(), bbox.copy()
 
   def get_tf_to_centered_mesh(self):
     tf = torch.eye(4, dtype=torch.float, device='cuda')

@@ -21,6 +21,7 @@ class PipelineData:
     self.lost = False         # set by the caller when the track is lost: Detect then looks for the object again
     self.detections = None    # Utils.detect's records of the frame, left by Detect
     self.pose = None          # 4x4 ob_in_cam of the original (un-centred) mesh
+    self.center_pose = None   # pose @ inv(to_origin) of the model's oriented box (main.py:67), set by FoundationPoseEstimator(box='oriented')
     self.pose_6d = None       # (x, y, z, roll, pitch, yaw)
     self.errors = []
     self.__dict__.update(kw)
@@ -212,10 +213,15 @@ class Detect(Processor):
 
 class FoundationPoseEstimator(Processor):
   """Wraps foundationpose_amd.estimater.FoundationPose as a pipeline stage (what main.py:34-79 does by hand):
-  first frame -> register(), later frames -> track_one()."""
+  first frame -> register(), later frames -> track_one().  box='aabb' draws the axis-aligned box of the model in `visualize`;
+  box='oriented' draws the minimum-volume box of Utils.oriented_bounds, as main.py:38-39 does with trimesh, and `process` then also sets
+  `data.center_pose = data.pose @ inv(to_origin)`, the matrix main.py:67 publishes."""
 
   def __init__(self, mesh_file=None, intrinsics_file=None, mesh=None, K=None, est_refine_iter=5, track_refine_iter=2,
-               scorer=None, refiner=None, debug=0):
+               scorer=None, refiner=None, debug=0, box='aabb'):
+    if box not in ('aabb', 'oriented'):
+      raise ValueError(f"box must be 'aabb' or 'oriented', got {box!r}")
+    self.box = box
     from .mesh_io import load_intrinsics, load_obj
     self.mesh = load_obj(mesh_file) if mesh is None else mesh
     self.K = np.asarray(K, dtype=np.float64) if K is not None else (load_intrinsics(intrinsics_file) if intrinsics_file else None)
@@ -233,13 +239,18 @@ class FoundationPoseEstimator(Processor):
                                     iteration=self.est_refine_iter)
     else:
       data.pose = self.est.track_one(rgb=data.rgb, depth=data.depth, K=K, iteration=self.track_refine_iter)
+    if self.box == 'oriented':
+      data.center_pose = np.asarray(data.pose, dtype=np.float64).reshape(4, 4) @ np.linalg.inv(self.est.model_box(oriented=True)[0])
     return data
 
   def visualize(self, data):
     """The picture main.py:67-71 saves: the model's box and the xyz axes at `data.pose` on `data.rgb`; sets and returns `data.vis`."""
     from . import Utils as U
     K = self.K if data.K is None else np.asarray(data.K, dtype=np.float64)
-    to_origin, bbox = U.model_box(self.mesh)
+    if self.box == 'oriented':
+      to_origin, bbox = self.est.model_box(oriented=True) if self.est is not None else U.model_box(self.mesh, oriented=True)
+    else:
+      to_origin, bbox = U.model_box(self.mesh)
     data.vis = U.draw_poses(data.rgb, K, np.asarray(data.pose, dtype=np.float64).reshape(1, 4, 4), bboxes=bbox, offsets=np.linalg.inv(to_origin),
                             colors=(0, 255, 0))
     return data.vis

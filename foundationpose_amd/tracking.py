@@ -384,10 +384,11 @@ class MultiObjectTracker:
                             delta=delta, want=('mask_visib', 'owner', 'info'), glctx=self.estimators[0].refiner.ctx)
     return dict(owner=out['owner'], mask_visib=out['mask_visib'], visib_fract=np.array([r['visib_fract'] for r in out['info']], dtype=np.float64))
 
-  def draw(self, rgb, fill_alpha=0.0, contour=False, depth=None, **kw):
+  def draw(self, rgb, fill_alpha=0.0, contour=False, depth=None, oriented=False, **kw):
     """The frame `rgb` (H,W,3) uint8, numpy or device tensor, with every object's box and xyz axes at its current pose of the ORIGINAL
     mesh - the poses the last `register` / `track` returned - in one Utils.draw_poses call; the result is of the kind of `rgb`.  The box
-    of object o is Utils.model_box of its mesh, in object o's palette colour.  fill_alpha > 0 tints each object's visible pixels,
+    of object o is Utils.model_box of its mesh (oriented=True: its minimum-volume box, FoundationPose.model_box(oriented=True), found once
+    per object), in object o's palette colour.  fill_alpha > 0 tints each object's visible pixels,
     contour=True outlines them: the owner map then comes from instance_masks(depth=depth).  Other keywords go to Utils.draw_poses."""
     from . import Utils as U
     ests = self.estimators
@@ -398,7 +399,7 @@ class MultiObjectTracker:
       if held is not e.pose_last:                           # set elsewhere since: the pose of the original mesh as track_one forms it
         last = torch.as_tensor(e.pose_last, dtype=torch.float).reshape(4, 4)
         pose = (last.to(e.get_tf_to_centered_mesh().device) @ e.get_tf_to_centered_mesh()).cpu().numpy()
-      to_origin, bbox = U.model_box(e.mesh_ori)
+      to_origin, bbox = e.model_box(oriented=True) if oriented else U.model_box(e.mesh_ori)
       poses.append(pose), boxes.append(bbox), offs.append(np.linalg.inv(to_origin))
     owner = None
     if fill_alpha > 0 or contour:

@@ -249,6 +249,33 @@ int fp_scene_instances(fp_ctx *ctx, const fp_mesh *const *meshes, const float *d
  * n_pts > 0, n_pts < 0 or above FP_MESH_DIAMETER_MAX_POINTS (2^21: 2.1 M tile pairs, 34 MB of arena). */
 int fp_mesh_diameter(fp_ctx *ctx, const float *d_pts, int n_pts, float *d_out_diameter, int32_t *d_out_pair, void *stream);
 
+#define FP_BOX_EXTENTS_MAX_POINTS (1 << 21)
+#define FP_BOX_EXTENTS_MAX_FRAMES (1 << 24)
+#define FP_BOX_EXTENTS_MAX_EVALS (1ll << 40)
+#define FP_BOX_EXTENTS_TILE 1024          /* points of an LDS tile */
+#define FP_BOX_EXTENTS_CAND 1024          /* candidates of a workgroup */
+/* The boxes of n points in C candidate frames and the smallest of them: the search of a minimum-volume oriented box
+ * (Utils.oriented_bounds), and the box of any cloud in given frames (Utils.box_extents).  d_points (n,3) float32; d_frames (C,3,3)
+ * float32 row-major, the rows r_0, r_1, r_2 of a frame being its axes - normalised by the caller: the device takes no root and divides
+ * nothing.  The rule per candidate c is the project's own, restated op for op by tests/oriented_bounds_oracle.py:
+ *     q_k  = ((r_k0 * x) + (r_k1 * y)) + (r_k2 * z)             fp32, in that order, nothing contracted
+ *     lo_k = min, hi_k = max of q_k over all points             fminf / fmaxf from +inf / -inf: a NaN projection is passed over
+ *     vol  = ((hi_0 - lo_0) * (hi_1 - lo_1)) * (hi_2 - lo_2)    fp32
+ * The winner is chosen by a total order: among the candidates with vol >= 0 (a NaN volume never wins, nor the negative one of a
+ * candidate that saw no finite projection) the smaller volume first, then the lower index.  min and max do not depend on the order of
+ * their operands, so every output is the same bits whatever the tiling, the launch shape, the batch a candidate sits in or the run.
+ *   Outputs, device: d_best_index 1 int32 (-1 when no candidate is eligible; the three others are then NaN), d_best_lohi 6 float32
+ * lo[3], hi[3], d_best_volume 1 float32.  Optional, null to skip: d_all_lohi (C,6) and d_all_volume (C).
+ *   grid = (blocks of FP_BOX_EXTENTS_CAND candidates, slices of the points), a lane holding four frames and their bounds in registers
+ * and a tile of FP_BOX_EXTENTS_TILE points in LDS; a second launch folds the slices and forms the volumes, a third folds the
+ * per-workgroup winners.  No atomics, no arrival counters; the per-slice bounds go to the context's arena (24 bytes per candidate and
+ * slice; more than one slice only below 2^20 candidates).  Nothing synchronises and nothing is allocated once the arena holds the call:
+ * it sits in a captured graph.  FP_EINVAL, before anything is queued: a null ctx, d_points, d_frames, d_best_index, d_best_lohi or
+ * d_best_volume; n < 1 or above FP_BOX_EXTENTS_MAX_POINTS; C < 1 or above FP_BOX_EXTENTS_MAX_FRAMES; n C above
+ * FP_BOX_EXTENTS_MAX_EVALS (2^40 projections of a point on a frame, seconds of work: cut the candidates into several calls). */
+int fp_box_extents(fp_ctx *ctx, const float *d_points, int n, const float *d_frames, int C, int32_t *d_best_index, float *d_best_lohi,
+                   float *d_best_volume, float *d_all_lohi, float *d_all_volume, void *stream);
+
 #define FP_MESH_SIMPLIFY_MAX_VERTICES (1 << 21)
 #define FP_MESH_SIMPLIFY_MAX_FACES (1 << 23)
 /* Vertex clustering: a mesh (or, with F = 0, a point cloud) reduced to one vertex per occupied cell of a grid of pitch `cell`.  The
