@@ -45,7 +45,7 @@
 //   online softmax     : per key block, max / sum finish with one xor-32 shuffle; exp((s-m)/sqrt(128)).
 //   O^T += V^T P^T     : the S^T accumulator registers 8s..8s+7 ARE the B operand of k-step s (key order
 //                       16s + {4h+0..3, 8+4h+0..3}); the transposed V image stores its tokens in that order
-//                       (vt_col(), common.h), so a V^T fragment is ONE conflict-free ds_read_b128 like a K fragment.
+//                       (vt_col(), tok_tile.h), so a V^T fragment is ONE conflict-free ds_read_b128 like a K fragment.
 //                       O^T keeps the query on the lane, so the rescale is lane-local.
 // The loop is bound by vector-instruction ISSUE, not by the matrix pipe (SQ counters: 643 vector instructions per wave per
 // key block beside 32 MFMAs, two waves sharing one SIMD's issue port), so the body is written to issue few of them:

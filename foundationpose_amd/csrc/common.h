@@ -389,10 +389,7 @@ int small_pack_weights(const f16 *d_w, int Cout, int Cin, int Kpad, f16 *d_out, 
 size_t conv_packed_halfs(unsigned packing, int Cout, int Cin);
 int conv_pack_weights(unsigned packing, const f16 *d_w, int Cout, int Cin, int Kpad, f16 *d_out, hipStream_t s);
 
-// Column of token t inside the transposed V image [b][4][128][416].  Within each group of 16 tokens the order is
-// {0-3, 8-11, 4-7, 12-15}: the 8 keys that one lane half of the attention kernel's P^T operand carries (the S^T
-// accumulator registers of a k-step) are then 16 contiguous bytes - one ds_read_b128 per V^T fragment.
-__host__ __device__ __forceinline__ int vt_col(int t) { return (t & ~15) | (((t >> 2) & 1) << 3) | (((t >> 3) & 1) << 2) | (t & 3); }
+// (the transposed V image [b][4][128][416] and its token order vt_col(): tok_tile.h)
 int launch_attention(fp_ctx *ctx, const f16 *qk, const f16 *vt, int B, int T, f16 *out, hipStream_t s);
 
 // Token GEMM (tok_gemm.hip): out = x (M x 512) @ W^T + b for up to TG_MAXBLK blocks of 512 output columns in one launch.
@@ -415,6 +412,10 @@ struct TokGemmArgs {
 };
 enum { TG_EPI_ROWS = 0, TG_EPI_VT = 1, TG_EPI_LN = 2, TG_EPI_LNSUM = 3 };
 int launch_tok_gemm(fp_ctx *ctx, const TokGemmArgs &a, int epi, hipStream_t s);
+// the argument checks launch_tok_gemm and launch_tok_qkv share (tok_gemm.hip): pointers, block count, the 32-bit lane-offset limit and per
+// block the conditions of its output - `out`: what the blocks write, TOK_OUT_BLK = each block's own `vt`; coff_align: of rows / V image blocks
+enum { TOK_OUT_NONE, TOK_OUT_ROWS, TOK_OUT_VT, TOK_OUT_BLK };
+int tok_check_args(const char *who, const TokGemmArgs &a, int out, int coff_align);
 // tok_qkv.hip: the in-projections - all blocks over a resident 128-token tile (fp16 rows or the transposed V image per block)
 int launch_tok_qkv(fp_ctx *ctx, const TokGemmArgs &a, hipStream_t s, int hyp = 0);      // hyp: images of the forward body (qkv_form: 1 .. 2 tok_qkv_small_kernel; 0: a stand-alone call)
 // head_mlp.hip: out-projection + LayerNorm1 + linear1 + ReLU + linear2 + LayerNorm2 statistics of one transformer head in one launch

@@ -16,6 +16,7 @@
 // have their own kernel (conv_halo.hip).
 #include "common.h"
 #include "device_util.h"
+#include "tok_tile.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -398,8 +399,7 @@ __device__ __forceinline__ void igemm2_tile(const ConvArgs &p, const f16 *__rest
         } else {
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            const int c = co + e, h = c >> 7, d = c & 127;
-            ((f16 *)p.out)[(((size_t)tb * 4 + h) * 128 + d) * 416 + tt] = (f16)v[e];
+            ((f16 *)p.out)[vt_row(tb, co + e) + tt] = (f16)v[e];
           }
         }
       }

@@ -1,5 +1,5 @@
-// Device-side primitives shared by the gfx950 kernel files: LDS-DMA, counted waits, lane and workgroup reductions, the token-tile load and the
-// bias start of the MFMA accumulators (token GEMMs and the band convolutions; the band family's own pieces are in conv_band.h).  Device
+// Device-side primitives shared by the gfx950 kernel files: LDS-DMA, counted waits, lane and workgroup reductions and the bias start of
+// the MFMA accumulators (token GEMMs and the band convolutions; the families' own pieces are in tok_tile.h and conv_band.h).  Device
 // only; include after common.h.  Everything is __forceinline__: a kernel that uses a helper from here compiles to the instructions it
 // had with a private copy.
 #pragma once
@@ -106,26 +106,7 @@ __device__ __forceinline__ double block_sum(double v, double *red) {
   return s;
 }
 
-// ---- token tile (tok_gemm.hip, tok_qkv.hip, head_mlp.hip) ----
-// ROWS rows x 512 fp16 of `src` (rows past M repeat the last one) -> LDS [k segment of 128][row][256 B], 16-byte chunk c of a
-// row segment stored at c ^ (row & 15): conflict-free ds_read_b128.  One DMA instruction = 4 rows of one segment (1 KB,
-// lane-linear destination; the swizzle is applied on the source address); ROWS / WAVES instructions per wave.
-// PIN_LANE: the lane offsets are recomputed per call - hoisted out of a loop over tiles they would live across the K loops.
-template <int ROWS, int WAVES, bool PIN_LANE = false>
-__device__ __forceinline__ void tok_tile_dma(const f16 *src, int m0, int M, int wave, int lane, unsigned lds0) {
-  constexpr int U = ROWS / 4 / WAVES;
-  if constexpr (PIN_LANE) asm volatile("" : "+v"(lane));
-#pragma unroll
-  for (int seg = 0; seg < 4; ++seg)
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int r4 = wave * U + u, row = r4 * 4 + (lane >> 4);
-      const int m = min(m0 + row, M - 1);
-      const unsigned voff = (unsigned)(((size_t)m * 512 + seg * 128 + (((lane & 15) ^ (row & 15)) * 8)) * 2);
-      glds16(src, voff, lds0 + seg * (ROWS * 256) + r4 * 1024);
-    }
-}
-
+// ---- bias start of the MFMA accumulators (token GEMMs: tok_tile.h has their other pieces; band convolutions) ----
 // Accumulators of a token GEMM or a convolution start at the bias.  col0 is the first of the wave's NI * 32 output columns; acc[i][j] is the
 // 32x32 MFMA tile of columns col0 + i*32 .. +31 and tokens (pixels) j*32 .. +31; lr = lane & 31, lh = lane >> 5.
 // Row layout: a lane owns one token and channels col0 + i*32 + rg*8 + lh*4 + (0..3) in register quad rg.

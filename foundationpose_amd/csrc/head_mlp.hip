@@ -9,11 +9,11 @@
 // Until round 3 these were three launches of tok_gemm.hip (out-projection + LN, linear1, linear2 + LN sums): x1 was written once
 // and read twice, ff written and read once - 515 MB of the 734 MB the three launches moved per head and pass at 252 hypotheses.
 // Here a workgroup (8 waves) owns 64 tokens for the whole chain and the intermediates never leave the CU:
-//   * two 64-KB tile buffers P and Q in the layout of tok_gemm.hip's activation tile (k segments of 128, 256-byte row segments,
-//     16-byte chunk c of a row stored at c ^ (row & 15): conflict-free ds_read_b128).  At the start the attention output goes to P and
-//     the residual tokens to Q by LDS-DMA, together; the first K loop starts when P has landed;
-//   * K loop as in tok_gemm.hip: weights packed in MFMA-fragment order stream L2 -> registers (each wave its own 64 output columns,
-//     2 fragments per k-step of 16, prefetched 4 k-steps ahead), token fragments from LDS, no barrier and no LDS write inside;
+//   * two 64-KB tile buffers P and Q in the token-tile layout (tok_tile.h: that layout, the weight fragments, the accumulator layout
+//     and the pieces shared with tok_gemm.hip / tok_qkv.hip).  At the start the attention output goes to P and the residual tokens to
+//     Q by LDS-DMA, together; the first K loop starts when P has landed;
+//   * K loop as in tok_gemm.hip (tok_kloop_db): weights stream L2 -> registers (each wave its own 64 output columns, 2 fragments per
+//     k-step of 16, prefetched 4 k-steps ahead), token fragments from LDS, no barrier and no LDS write inside;
 //   * the accumulator layout (lane = token, 4 consecutive channels per register quad) IS an 8-byte half chunk of the tile layout, so
 //     LayerNorm1 reads its residual from Q and writes x1 (fp16) back IN PLACE - Q is then the A tile of linear1 and the residual of
 //     LayerNorm2 -, and ReLU(linear1) is written into P, dead since the first K loop, as the A tile of linear2;
@@ -23,6 +23,7 @@
 // K loop - is bought here by having no loads behind the first 128 KB.
 #include "common.h"
 #include "device_util.h"
+#include "tok_tile.h"
 #include <cstdlib>
 
 #define HM_THREADS 512
@@ -30,57 +31,28 @@
 #define HM_RED_OFF (2 * HM_TILE)                 // [2][8 waves][64 tokens] floats
 #define HM_LDS_BYTES (2 * HM_TILE + 4096)
 
-struct HmCtx {
-  int lane, wave, lr, lh;
+struct HmLane : TokLane {      // + the fragment-offset table of the double-buffered K loop (tile_frag_xo)
   unsigned xo[8];
 };
 
 // acc[i][j] (channels wave*64 + i*32 + ..., tokens j*32 + lr) = bias + tile (64 x 512, LDS) @ W^T
-__device__ __forceinline__ void hm_gemm(const HmCtx &c, const f16 *w, const float *bias, const unsigned char *tile, floatx16 (&acc)[2][2]) {
+__device__ __forceinline__ void hm_gemm(const HmLane &c, const f16 *w, const float *bias, const unsigned char *tile, floatx16 (&acc)[2][2]) {
   acc_from_bias(acc, bias, c.wave * 64, c.lh);
-  // packed [wave4][k16 32][i4 4][lane 64][8 halfs] (pack_tok_weights): this wave's fragments are (wave >> 1, k16, (wave & 1) * 2 + i)
-  const u32x4 *wp = reinterpret_cast<const u32x4 *>(w) + (size_t)(c.wave >> 1) * (32 * 4 * 64) + ((c.wave & 1) * 2) * 64 + c.lane;
-  constexpr int D = 4;
-  u32x4 wr[D][2];
-#pragma unroll
-  for (int d = 0; d < D; ++d)
-#pragma unroll
-    for (int i = 0; i < 2; ++i) wr[d][i] = wp[(d * 4 + i) * 64];
-  const unsigned char *xb = tile + c.lr * 256;
-  half8 bf[2][2];
-#pragma unroll
-  for (int j = 0; j < 2; ++j) bf[0][j] = *reinterpret_cast<const half8 *>(xb + j * 8192 + c.xo[0]);
-#pragma unroll
-  for (int k = 0; k < 32; ++k) {
-    const int cur = k & 1, slot = k % D;
-    half8 af[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) af[i] = *reinterpret_cast<half8 *>(&wr[slot][i]);
-    __builtin_amdgcn_sched_barrier(0);      // pin the prefetch (hipcc otherwise sinks the loads next to their use)
-    if (k + D < 32) {
-#pragma unroll
-      for (int i = 0; i < 2; ++i) wr[slot][i] = wp[((k + D) * 4 + i) * 64];
-    }
-    if (k + 1 < 32) {
-      const int kn = k + 1;
-#pragma unroll
-      for (int j = 0; j < 2; ++j) bf[cur ^ 1][j] = *reinterpret_cast<const half8 *>(xb + (kn >> 3) * 16384 + j * 8192 + c.xo[kn & 7]);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int i = 0; i < 2; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[i], bf[cur][j], acc[i][j], 0, 0, 0);
-  }
+  const u32x4 *wp = reinterpret_cast<const u32x4 *>(w) + wfrag_own8(c.wave, 0, 0) * 64 + c.lane;
+  u32x4 wr[4][2];                         // weights 4 k-steps ahead
+  tok_w_prefetch(wr, wp);
+  tok_kloop_db<2, 4, false>(wr, wp, tile + c.lr * 256, c.xo, acc);
 }
 
-// byte offset inside a tile of the 8-byte half chunk that holds channels wave*64 + i*32 + rg*8 + lh*4 .. +3 of token row
-__device__ __forceinline__ unsigned hm_off(const HmCtx &c, int row, int i, int rg) {
-  return (unsigned)((c.wave >> 1) * 16384 + row * 256 + ((((c.wave & 1) * 8 + i * 4 + rg) ^ (row & 15)) * 16) + c.lh * 8);
+// byte offset inside a tile of ROWS rows of the 8-byte half chunk that holds channels wave*64 + i*32 + rg*8 + lh*4 .. +3 of token row
+template <int ROWS>
+__device__ __forceinline__ unsigned hm_off(const TokLane &c, int row, int i, int rg) {
+  return (unsigned)tile_quad_off<ROWS, 8>(c.wave, i, rg, row, c.lh);
 }
 
 // acc += residual tile (fp16, fp32 add); then the LayerNorm statistics of every token over the 512 columns -> acc = (acc - mean), rstd
-__device__ __forceinline__ void hm_residual_stats(const HmCtx &c, const unsigned char *res_tile, float *red, floatx16 (&acc)[2][2], float (&rstd)[2]) {
+// (written out here and in tok_gemm.hip: as templates shared between the two files both pieces change registers or waits of either kernel)
+__device__ __forceinline__ void hm_residual_stats(const HmLane &c, const unsigned char *res_tile, float *red, floatx16 (&acc)[2][2], float (&rstd)[2]) {
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int row = j * 32 + c.lr;
@@ -88,7 +60,7 @@ __device__ __forceinline__ void hm_residual_stats(const HmCtx &c, const unsigned
     for (int i = 0; i < 2; ++i)
 #pragma unroll
       for (int rg = 0; rg < 4; ++rg) {
-        const half4 rq = *reinterpret_cast<const half4 *>(res_tile + hm_off(c, row, i, rg));
+        const half4 rq = *reinterpret_cast<const half4 *>(res_tile + hm_off<64>(c, row, i, rg));
 #pragma unroll
         for (int e = 0; e < 4; ++e) acc[i][j][rg * 4 + e] += (float)rq[e];
       }
@@ -137,14 +109,14 @@ __device__ __forceinline__ void hm_residual_stats(const HmCtx &c, const unsigned
 
 __global__ __launch_bounds__(HM_THREADS, 1) void head_mlp_kernel(HeadMlpArgs p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char hm_smem[];
-  HmCtx c;
+  HmLane c;                     // (filled in here: through a shared init function this kernel's VGPRs, LDS writes and waits change)
   const int tid = threadIdx.x;
   c.lane = tid & 63;
   c.wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   c.lr = c.lane & 31;
   c.lh = c.lane >> 5;
 #pragma unroll
-  for (int s = 0; s < 8; ++s) c.xo[s] = (unsigned)(((2 * s + c.lh) ^ (c.lr & 15)) * 16);
+  for (int s = 0; s < 8; ++s) c.xo[s] = (unsigned)tile_frag_xo(s, c.lr, c.lh);
   const int m0 = blockIdx.x * 64;
   unsigned char *P = hm_smem, *Q = hm_smem + HM_TILE;
   float *red = reinterpret_cast<float *>(hm_smem + HM_RED_OFF);
@@ -175,7 +147,7 @@ __global__ __launch_bounds__(HM_THREADS, 1) void head_mlp_kernel(HeadMlpArgs p) 
         hv[1] = (f16)(acc[i][j][rg * 4 + 1] * rstd[j] * gv.y + bv.y);
         hv[2] = (f16)(acc[i][j][rg * 4 + 2] * rstd[j] * gv.z + bv.z);
         hv[3] = (f16)(acc[i][j][rg * 4 + 3] * rstd[j] * gv.w + bv.w);
-        *reinterpret_cast<half4 *>(Q + hm_off(c, j * 32 + c.lr, i, rg)) = hv;     // the residual chunk this lane read: same address
+        *reinterpret_cast<half4 *>(Q + hm_off<64>(c, j * 32 + c.lr, i, rg)) = hv;     // the residual chunk this lane read: same address
       }
     }
   __syncthreads();
@@ -187,29 +159,13 @@ __global__ __launch_bounds__(HM_THREADS, 1) void head_mlp_kernel(HeadMlpArgs p) 
     for (int rg = 0; rg < 4; ++rg)
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
-        half4 hv;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) hv[e] = (f16)acc[i][j][rg * 4 + e];
-        hv = __builtin_elementwise_max(hv, half4{(f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f});
-        *reinterpret_cast<half4 *>(P + hm_off(c, j * 32 + c.lr, i, rg)) = hv;
+        *reinterpret_cast<half4 *>(P + hm_off<64>(c, j * 32 + c.lr, i, rg)) = relu4(acc_quad_f16(acc[i][j], rg));
       }
   __syncthreads();
   // ---- linear2 + residual x1 + LayerNorm2 statistics -> sums of the normalised rows over groups of 16 tokens ----
   hm_gemm(c, p.w2, p.b2, P, acc);
   hm_residual_stats(c, Q, red, acc, rstd);
-#pragma unroll
-  for (int j = 0; j < 2; ++j)
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int rg = 0; rg < 4; ++rg) {
-        float v[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = row16_sum(acc[i][j][rg * 4 + e] * rstd[j]);
-        const int g = (m0 + j * 32 + (c.lr & 16)) >> 4;          // global 16-token group (16 divides 400: never two hypotheses)
-        if ((c.lr & 15) == 0 && g * 16 < p.M)
-          *reinterpret_cast<float4 *>(p.gsum + (size_t)g * 512 + c.wave * 64 + i * 32 + rg * 8 + c.lh * 4) = make_float4(v[0], v[1], v[2], v[3]);
-      }
+  tok_gsum_store<2>(c, acc, rstd, m0, p.M, p.gsum);
 }
 
 
@@ -219,10 +175,10 @@ __global__ __launch_bounds__(HM_THREADS, 1) void head_mlp_kernel(HeadMlpArgs p) 
 // the MFMAs need 8.2 k.  With 128 tokens per workgroup a fragment feeds FOUR MFMAs (32 B/clk/CU) and the K loops run at the MFMA
 // rate (stamps: 16.3 k cycles for the 2 x 256 MFMAs of the two waves of a SIMD) - but two 128-KB tiles do not fit 160 KB of LDS.
 // They do not have to:
-//   * ONE resident 128-KB tile Q (tok_gemm.hip's image).  The residual tokens land in it at the start; LayerNorm1 writes x1 over
+//   * ONE resident 128-KB tile Q (tok_tile.h's image).  The residual tokens land in it at the start; LayerNorm1 writes x1 over
 //     them in place (the 64-token form does the same): A of linear1; then ff: A of linear2;
 //   * the attention output, the A operand of the out-projection, is read exactly once per k: it streams through a 2-slot ring of
-//     64-k segments (2 x 16 KB; 128-byte rows, chunk c at c ^ (row & 7)) by LDS-DMA, one barrier per segment: the barrier that says
+//     64-k segments (2 x 16 KB; tok_tile.h's ring slot) by LDS-DMA, one barrier per segment: the barrier that says
 //     "segment s has landed everywhere" also says "everybody is done with segment s - 1", whose slot the DMA of s + 1 then takes;
 //     the wait is a counted vmcnt (the 8 weight loads issued since may stay in flight).  (Tried instead: the attention output
 //     resident and the residual read from global memory straight into the accumulators - 8-byte pieces of 32 rows per instruction:
@@ -256,35 +212,26 @@ extern "C" __attribute__((visibility("default"))) int fp_dbg_hm_stamps(unsigned 
 #define H2_RED_OFF H2_RING_OFF                    // reduction scratch [8 waves][128 tokens] x (sum, sum of squares) floats = 8 KB: in the idle ring
 #define H2_LDS_BYTES (H2_TILE + 2 * H2_SLOT)      // 160 KB
 
-// 64-k segment s8 (0 .. 7) of 128 rows of `src` -> ring slot: [row][128 B], chunk c (0 .. 7) at c ^ (row & 7); 2 DMA instructions per wave
+// 64-k segment s8 (0 .. 7) of 128 rows of `src` -> ring slot; 2 DMA instructions per wave
 __device__ __forceinline__ void h2_ring_dma(const f16 *src, int m0, int M, int s8, int wave, int lane, unsigned slot_addr) {
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
-    const int r8 = wave * 2 + u, row = r8 * 8 + (lane >> 3);
-    const int m = min(m0 + row, M - 1);
-    const unsigned voff = (unsigned)(((size_t)m * 512 + s8 * 64 + (((lane & 7) ^ (row & 7)) * 8)) * 2);
+    const int r8 = wave * 2 + u, row = ring_dma_row(r8, lane);
+    const unsigned voff = (unsigned)tok_src_bytes(tok_src_row(m0, row, M), s8 * 64, ring_dma_chunk(row, lane));
     glds16(src, voff, slot_addr + r8 * 1024);
   }
 }
-
-struct H2Ctx {
-  int lane, wave, lr, lh;
-};
 
 // acc[i][j] = C0 + A (128 tokens x 512: the resident tile, or RING: the two ring slots) @ W^T for the wave's 64 columns; C0 = the bias (BIAS: it is the C operand of
 // the first k-step's MFMAs - no 128 register copies) or what acc holds on entry.  `before_loop` runs once the first weight fragments
 // have been requested: the barrier (and wait) that makes the tile valid, so the fragments' L2 latency passes behind it.
 template <bool RING, bool BIAS, typename Pre>
-__device__ __forceinline__ void h2_gemm(const H2Ctx &c, const f16 *w, const float *bias, const unsigned char *smem, floatx16 (&acc)[2][4], Pre before_loop,
+__device__ __forceinline__ void h2_gemm(const TokLane &c, const f16 *w, const float *bias, const unsigned char *smem, floatx16 (&acc)[2][4], Pre before_loop,
                                         unsigned lds0 = 0, const f16 *ring_src = nullptr, int m0 = 0, int M = 0) {
-  // packed [wave4][k16 32][i4 4][lane 64][8 halfs] (pack_tok_weights): this wave's fragments are (wave >> 1, k16, (wave & 1) * 2 + i)
-  const u32x4 *wp = reinterpret_cast<const u32x4 *>(w) + (size_t)(c.wave >> 1) * (32 * 4 * 64) + ((c.wave & 1) * 2) * 64 + c.lane;
+  const u32x4 *wp = reinterpret_cast<const u32x4 *>(w) + wfrag_own8(c.wave, 0, 0) * 64 + c.lane;
   constexpr int D = 3;
   u32x4 wr[D][2];
-#pragma unroll
-  for (int d = 0; d < D; ++d)
-#pragma unroll
-    for (int i = 0; i < 2; ++i) wr[d][i] = wp[(d * 4 + i) * 64];
+  tok_w_prefetch(wr, wp);
   __builtin_amdgcn_sched_barrier(0);
   if constexpr (RING) {
     // RING: A streams through the two ring slots; segment 0 was requested by the caller in front of this call (and in front of the 6 weight
@@ -305,59 +252,56 @@ __device__ __forceinline__ void h2_gemm(const H2Ctx &c, const f16 *w, const floa
   }
   __builtin_amdgcn_sched_barrier(0);
   before_loop();
-  // token fragment (k16, j): resident tile: row j*32 + lr, chunk (2*(k16&7) + lh) ^ (lr & 15) of segment k16 >> 3 (tok_gemm.hip);
-  // ring: slot (k16 >> 2) & 1, row j*32 + lr, chunk (2*(k16&3) + lh) ^ (lr & 7).  The even part of the XOR is applied per k-step, the odd
-  // part and the row sit in the base
-  const unsigned char *xb = RING ? smem + H2_RING_OFF + c.lr * 128 + ((c.lh ^ (c.lr & 1)) * 16) : smem + c.lr * 256 + ((c.lh ^ (c.lr & 1)) * 16);
-  const unsigned xe = (unsigned)(c.lr & (RING ? 6 : 14));
-  auto frag_addr = [&](int k, int j) __attribute__((always_inline)) -> const unsigned char * {
-    if constexpr (RING) return xb + ((k >> 2) & 1) * H2_SLOT + j * 4096 + (((unsigned)(2 * (k & 3)) ^ xe) << 4);
-    else return xb + (k >> 3) * H2_SEG + j * 8192 + (((unsigned)(2 * (k & 7)) ^ xe) << 4);
-  };
-  half8 bf[4];
+  if constexpr (!RING) {
+    tok_kloop_rot<false, BIAS>(wr, wp, smem, c.lr, c.lh, acc, bvec);
+  } else {
+    // ring: the rotating K loop of tok_tile.h over the two slots, plus the segment edges (own body: the edge's wait, barrier and DMA sit inside the k-step)
+    const unsigned char *xb = smem + H2_RING_OFF + ring_frag_base(c.lr, c.lh);
+    const unsigned xe = ring_frag_xe(c.lr);
+    auto frag_addr = [&](int k, int j) __attribute__((always_inline)) -> const unsigned char * {
+      return xb + ring_frag_slot(H2_ROWS, k) + j * 4096 + ring_frag_x(k, xe);
+    };
+    half8 bf[4];
 #pragma unroll
-  for (int j = 0; j < 4; ++j) bf[j] = *reinterpret_cast<const half8 *>(frag_addr(0, j));
+    for (int j = 0; j < 4; ++j) bf[j] = *reinterpret_cast<const half8 *>(frag_addr(0, j));
 #pragma unroll
-  for (int k = 0; k < 32; ++k) {
-    const int slot = k % D;
-    half8 af[2];
+    for (int k = 0; k < 32; ++k) {
+      const int slot = k % D;
+      half8 af[2];
 #pragma unroll
-    for (int i = 0; i < 2; ++i) af[i] = *reinterpret_cast<half8 *>(&wr[slot][i]);
-    __builtin_amdgcn_sched_barrier(0);      // pin the prefetch (hipcc otherwise sinks the loads next to their use)
-    if (k + D < 32) {
+      for (int i = 0; i < 2; ++i) af[i] = *reinterpret_cast<half8 *>(&wr[slot][i]);
+      __builtin_amdgcn_sched_barrier(0);      // pin the prefetch (hipcc otherwise sinks the loads next to their use)
+      if (k + D < 32) {
 #pragma unroll
-      for (int i = 0; i < 2; ++i) wr[slot][i] = wp[((k + D) * 4 + i) * 64];
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    const int kn = k + 1;
-    const bool seg_edge = RING && (kn & 3) == 0 && kn < 32;        // the next k-step opens ring segment kn >> 2
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-#pragma unroll
-      for (int i = 0; i < 2; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[i], bf[j], (BIAS && k == 0) ? bvec[i] : acc[i][j], 0, 0, 0);
+        for (int i = 0; i < 2; ++i) wr[slot][i] = wp[wfrag(0, k + D, i) * 64];
+      }
       __builtin_amdgcn_sched_barrier(0);
-      if (kn < 32 && !seg_edge) bf[j] = *reinterpret_cast<const half8 *>(frag_addr(kn, j));
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if (seg_edge) {
-      // segment kn >> 2 was requested at the top of the previous segment; since then this wave has issued 8 weight loads (2 per k-step)
-      wait_vm_lgkm<8>();
-      __syncthreads();                                          // landed everywhere, and everybody is done with the other slot
-      if ((kn >> 2) + 1 < 8) h2_ring_dma(ring_src, m0, M, (kn >> 2) + 1, c.wave, c.lane, lds0 + H2_RING_OFF + (((kn >> 2) + 1) & 1) * H2_SLOT);
+      const int kn = k + 1;
+      const bool seg_edge = (kn & 3) == 0 && kn < 32;        // the next k-step opens ring segment kn >> 2
 #pragma unroll
-      for (int j = 0; j < 4; ++j) bf[j] = *reinterpret_cast<const half8 *>(frag_addr(kn, j));
+      for (int j = 0; j < 4; ++j) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[i], bf[j], (BIAS && k == 0) ? bvec[i] : acc[i][j], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        if (kn < 32 && !seg_edge) bf[j] = *reinterpret_cast<const half8 *>(frag_addr(kn, j));
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      if (seg_edge) {
+        // segment kn >> 2 was requested at the top of the previous segment; since then this wave has issued 8 weight loads (2 per k-step)
+        wait_vm_lgkm<8>();
+        __syncthreads();                                          // landed everywhere, and everybody is done with the other slot
+        if ((kn >> 2) + 1 < 8) h2_ring_dma(ring_src, m0, M, (kn >> 2) + 1, c.wave, c.lane, lds0 + H2_RING_OFF + (((kn >> 2) + 1) & 1) * H2_SLOT);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) bf[j] = *reinterpret_cast<const half8 *>(frag_addr(kn, j));
+      }
     }
   }
 }
 
-// byte offset inside the resident tile of the 8-byte half chunk that holds channels wave*64 + i*32 + rg*8 + lh*4 .. +3 of token `row`
-__device__ __forceinline__ unsigned h2_off(const H2Ctx &c, int row, int i, int rg) {
-  return (unsigned)((c.wave >> 1) * H2_SEG + row * 256 + ((((c.wave & 1) * 8 + i * 4 + rg) ^ (row & 15)) * 16) + c.lh * 8);
-}
 // a copy of the lane coordinates the compiler cannot see through: addresses derived from it are recomputed where they are used instead
 // of being shared between the phases of the kernel (and living in registers across the K loops in between)
-__device__ __forceinline__ H2Ctx h2_fresh(const H2Ctx &c0) {
-  H2Ctx c = c0;
+__device__ __forceinline__ TokLane h2_fresh(const TokLane &c0) {
+  TokLane c = c0;
   asm volatile("" : "+v"(c.lr), "+v"(c.lh), "+v"(c.lane));
   return c;
 }
@@ -365,8 +309,8 @@ __device__ __forceinline__ H2Ctx h2_fresh(const H2Ctx &c0) {
 // LayerNorm statistics of every token over the 512 columns, ONE pass in fp32 (sum and sum of squares together: one barrier round instead
 // of two; the rows are O(1) residual-stream values with a variance of the same order, so E[x^2] - mean^2 loses nothing that matters in
 // fp32): lane -> partner lane -> the 8 waves through LDS in a fixed order.  Returns mean and rstd per token tile.
-__device__ __forceinline__ void h2_stats(const H2Ctx &c0, float *red, const floatx16 (&acc)[2][4], float (&mean)[4], float (&rstd)[4]) {
-  H2Ctx c = c0;
+__device__ __forceinline__ void h2_stats(const TokLane &c0, float *red, const floatx16 (&acc)[2][4], float (&mean)[4], float (&rstd)[4]) {
+  TokLane c = c0;
   asm volatile("" : "+v"(c.lr));          // the scratch addresses are recomputed per call: shared between the two calls they would live across two K loops
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
@@ -399,7 +343,7 @@ __device__ __forceinline__ void h2_stats(const H2Ctx &c0, float *red, const floa
 
 __global__ __launch_bounds__(HM_THREADS, 1) void head_mlp128_kernel(HeadMlpArgs p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char h2_smem[];
-  H2Ctx c;
+  TokLane c;
   const int tid = threadIdx.x;
   c.lane = tid & 63;
   c.wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -421,7 +365,7 @@ __global__ __launch_bounds__(HM_THREADS, 1) void head_mlp128_kernel(HeadMlpArgs 
   // ---- + residual (Q) + LayerNorm1 -> x1 (fp16) in place into Q ----
   __syncthreads();                                               // every wave is done with the ring: it becomes the reduction scratch
   {
-    const H2Ctx cr = h2_fresh(c);
+    const TokLane cr = h2_fresh(c);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int row = j * 32 + cr.lr;
@@ -429,14 +373,14 @@ __global__ __launch_bounds__(HM_THREADS, 1) void head_mlp128_kernel(HeadMlpArgs 
       for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int rg = 0; rg < 4; ++rg) {
-          const half4 rq = *reinterpret_cast<const half4 *>(Q + h2_off(cr, row, i, rg));
+          const half4 rq = *reinterpret_cast<const half4 *>(Q + hm_off<H2_ROWS>(cr, row, i, rg));
 #pragma unroll
           for (int e = 0; e < 4; ++e) acc[i][j][rg * 4 + e] += (float)rq[e];
         }
     }
   }
   h2_stats(c, red, acc, mean, rstd);
-  const H2Ctx c1 = h2_fresh(c);
+  const TokLane c1 = h2_fresh(c);
   float4 gv[2][4], bv[2][4];
 #pragma unroll
   for (int i = 0; i < 2; ++i)
@@ -458,7 +402,7 @@ __global__ __launch_bounds__(HM_THREADS, 1) void head_mlp128_kernel(HeadMlpArgs 
         hv[1] = (f16)__builtin_fmaf(__builtin_fmaf(acc[i][j][rg * 4 + 1], rstd[j], nm), gv[i][rg].y, bv[i][rg].y);
         hv[2] = (f16)__builtin_fmaf(__builtin_fmaf(acc[i][j][rg * 4 + 2], rstd[j], nm), gv[i][rg].z, bv[i][rg].z);
         hv[3] = (f16)__builtin_fmaf(__builtin_fmaf(acc[i][j][rg * 4 + 3], rstd[j], nm), gv[i][rg].w, bv[i][rg].w);
-        *reinterpret_cast<half4 *>(Q + h2_off(c1, j * 32 + c1.lr, i, rg)) = hv;
+        *reinterpret_cast<half4 *>(Q + hm_off<H2_ROWS>(c1, j * 32 + c1.lr, i, rg)) = hv;
       }
   }
   HSTAMP(2);
@@ -472,12 +416,9 @@ __global__ __launch_bounds__(HM_THREADS, 1) void head_mlp128_kernel(HeadMlpArgs 
     for (int j = 0; j < 4; ++j)
 #pragma unroll
       for (int rg = 0; rg < 4; ++rg) {
-        half4 hv;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) hv[e] = (f16)acc[i][j][rg * 4 + e];
-        ff[i][j][rg] = __builtin_elementwise_max(hv, half4{(f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f});
+        ff[i][j][rg] = relu4(acc_quad_f16(acc[i][j], rg));
       }
-  const H2Ctx c2 = h2_fresh(c);
+  const TokLane c2 = h2_fresh(c);
   float4 b2v[2][4];
 #pragma unroll
   for (int i = 0; i < 2; ++i)
@@ -491,7 +432,7 @@ __global__ __launch_bounds__(HM_THREADS, 1) void head_mlp128_kernel(HeadMlpArgs 
     for (int rg = 0; rg < 4; ++rg)
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        unsigned char *q = Q + h2_off(c2, j * 32 + c2.lr, i, rg);
+        unsigned char *q = Q + hm_off<H2_ROWS>(c2, j * 32 + c2.lr, i, rg);
         const half4 xq = *reinterpret_cast<const half4 *>(q);
         acc[i][j][rg * 4 + 0] = b2v[i][rg].x + (float)xq[0];
         acc[i][j][rg * 4 + 1] = b2v[i][rg].y + (float)xq[1];
@@ -509,7 +450,7 @@ __global__ __launch_bounds__(HM_THREADS, 1) void head_mlp128_kernel(HeadMlpArgs 
   // leave as one 256-byte store.
   h2_stats(c, red, acc, mean, rstd);
   {
-    const H2Ctx c3 = h2_fresh(c);
+    const TokLane c3 = h2_fresh(c);
     unsigned char *tb = Q + c.wave * 16384;
 #pragma unroll
     for (int h = 0; h < 2; ++h) {

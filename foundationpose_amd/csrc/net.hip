@@ -3,6 +3,7 @@
 // (learning/models/score_network.py:60-90) as sequences of the gfx950 kernels in conv.hip / attn.hip.
 #include "common.h"
 #include "device_util.h"
+#include "tok_tile.h"
 
 #include <algorithm>
 #include <cmath>
@@ -171,15 +172,14 @@ int make_conv(fp_net *net, const SD &sd, const std::string &wkey, const std::str
   return FP_OK;
 }
 
-// 512 x 512 row-major fp32 -> fp16 in the fragment order of tok_gemm.hip
+// 512 x 512 row-major fp32 -> fp16 in the fragment order of the token GEMMs (tok_tile.h)
 void pack_tok_weights(const float *w, f16 *out) {
   for (int wave = 0; wave < 4; ++wave)
     for (int k16 = 0; k16 < 32; ++k16)
       for (int i = 0; i < 4; ++i)
         for (int lane = 0; lane < 64; ++lane) {
-          const int lr = lane & 31, lh = lane >> 5;
-          const float *src = w + (size_t)(wave * 128 + i * 32 + lr) * 512 + k16 * 16 + lh * 8;
-          f16 *dst = out + ((((size_t)wave * 32 + k16) * 4 + i) * 64 + lane) * 8;
+          const float *src = w + wfrag_src(wave, k16, i, lane);
+          f16 *dst = out + (wfrag(wave, k16, i) * 64 + lane) * 8;
           for (int e = 0; e < 8; ++e) dst[e] = (f16)src[e];
         }
 }

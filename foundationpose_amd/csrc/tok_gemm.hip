@@ -8,11 +8,11 @@
 // A 1x1 layer has no spatial reuse: in the implicit-GEMM kernel of conv.hip both operands stream through LDS-DMA and the
 // L2 -> LDS fill (25 B/clk/CU measured) bounds the K loop at half the MFMA rate, with a workgroup barrier per K-step.
 // Here
-//   * the ACTIVATION tile (64 tokens x 512 = 64 KB) is brought into LDS ONCE (LDS-DMA, XOR-swizzled 256-byte row
-//     segments: conflict-free ds_read_b128) and stays resident for the whole K loop;
+//   * the ACTIVATION tile (64 tokens x 512 = 64 KB) is brought into LDS ONCE (LDS-DMA; the swizzled layout, the weight-fragment
+//     image, the accumulator and V image layouts and the pieces shared with tok_qkv.hip / head_mlp.hip: tok_tile.h) and stays
+//     resident for the whole K loop;
 //   * the WEIGHTS never touch LDS: each of the 4 waves owns 128 output columns and loads its MFMA fragments straight
-//     from global memory / L2 into registers (fragment-ordered packing done at load time: one coalesced 1-KB
-//     global_load_dwordx4 per fragment), prefetched TG_D k-steps ahead;
+//     from global memory / L2 into registers (one coalesced 1-KB global_load_dwordx4 per fragment), prefetched TG_D k-steps ahead;
 //   * so the K loop has NO barrier and no LDS write: per k-step of 16 a wave issues 4 global loads, 2 ds_read_b128 and
 //     8 v_mfma_f32_32x32x16_f16 (128 columns x 64 tokens = 4 x 2 accumulator tiles, 128 VGPRs);
 //   * TWO workgroups share a CU (76 KB of LDS, <= 256 VGPRs each): the three phases of a workgroup's life - tile load
@@ -21,8 +21,8 @@
 //     workgroup's K loop runs beside the other's load or epilogue instead of after it.
 // Epilogues (compile-time):
 //   EPI_ROWS   bias (+ReLU) -> fp16 rows (q|k projection, linear1)
-//   EPI_VT     bias -> transposed V image [b][4][128][416] in the attention kernel's token order (vt_col); the MFMA
-//              operands are swapped for this one so that a lane owns one channel and 4 consecutive tokens per register quad
+//   EPI_VT     bias -> transposed V image; the MFMA operands are swapped for this one so that a lane owns one channel and 4
+//              consecutive tokens per register quad
 //   EPI_LN     bias + residual (fp32) -> LayerNorm over the 512 columns (two-pass statistics in fp32 on the accumulators,
 //              cross-wave through LDS) -> fp16 rows (out-projection + norm1)
 //   EPI_LNSUM  the same LayerNorm, but instead of the rows only their sums over groups of 16 tokens are written (fp32):
@@ -32,13 +32,10 @@
 // promotes, layer_norm runs in fp32); only GEMM operands are fp16.
 #include "common.h"
 #include "device_util.h"
+#include "tok_tile.h"
 
 #define TG_ROWS 64
-#define TG_K 512
 #define TG_THREADS 256
-#define TG_SEG_BYTES (TG_ROWS * 256)            // one k segment of 128 of the resident tile: 16 KB
-#define TG_STAGE_LD 136                         // halfs per staged row of 128 columns (256 B + 16 B pad: conflict-free 8-byte writes)
-#define TG_VT_LD 72                             // halfs per staged channel row of 64 tokens (128 B + 16 B pad)
 #define TG_LDS_BYTES 77824                      // 76 KB: two workgroups per CU.  Tile 64 KB; the epilogue staging (68 - 72 KB) re-uses it
 #define TG_RED_OFF 73728                        // reduction scratch [2][4 waves][64] floats behind the staging
 
@@ -68,9 +65,9 @@ __global__ __launch_bounds__(TG_THREADS, 2) void tok_gemm_kernel(TokGemmArgs p) 
   TSTAMP(0);
   tok_tile_dma<TG_ROWS, 4>(p.in, m0, p.M, wave, lane, lds0);
 
-  // ---- weight fragments: packed [wave][k16][i][lane][8 halfs]; accumulators start at the bias (device_util.h's acc_from_bias /
-  // acc_from_bias_vt written out: through the calls hipcc allocates this kernel's registers differently) ----
-  const u32x4 *wp = reinterpret_cast<const u32x4 *>(blk.w) + (size_t)wave * (32 * 4 * 64) + lane;
+  // ---- this wave's weight fragments; accumulators start at the bias (device_util.h's acc_from_bias / acc_from_bias_vt written out:
+  // through the calls hipcc allocates this kernel's registers differently) ----
+  const u32x4 *wp = reinterpret_cast<const u32x4 *>(blk.w) + wfrag_own4(wave, 0, 0) * 64 + lane;
   floatx16 acc[4][2];
   if constexpr (EPI == EPI_VT) {          // swapped operands: a lane owns ONE channel (i*32 + lr) of the wave's 128
 #pragma unroll
@@ -99,108 +96,62 @@ __global__ __launch_bounds__(TG_THREADS, 2) void tok_gemm_kernel(TokGemmArgs p) 
   constexpr int TG_D = (EPI == EPI_LN || EPI == EPI_LNSUM) ? 3 : 4;   // weight prefetch distance in k-steps of 16 (3 where the
                                                                         // LayerNorm epilogue needs the registers: no spills)
   u32x4 wr[TG_D][4];
-#pragma unroll
-  for (int d = 0; d < TG_D; ++d)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) wr[d][i] = wp[(d * 4 + i) * 64];
+  tok_w_prefetch(wr, wp);
 
-  // ---- token fragments: row j*32 + lr, chunk (2*(k16&7) + lh) ^ (lr & 15) of segment k16 >> 3 ----
-  const unsigned char *xb = tg_smem + lr * 256;
-  unsigned xo[8];
+  unsigned xo[8];                          // token fragments: the table form of tok_tile.h
 #pragma unroll
-  for (int s = 0; s < 8; ++s) xo[s] = (unsigned)(((2 * s + lh) ^ (lr & 15)) * 16);
+  for (int s = 0; s < 8; ++s) xo[s] = (unsigned)tile_frag_xo(s, lr, lh);
 
   wait_vm<0>();      // tile (and the first weight fragments) landed
   __syncthreads();
   TSTAMP(1);
 
-  half8 bf[2][2];
-#pragma unroll
-  for (int j = 0; j < 2; ++j) bf[0][j] = *reinterpret_cast<const half8 *>(xb + j * 8192 + xo[0]);
-#pragma unroll
-  for (int k = 0; k < 32; ++k) {
-    const int cur = k & 1, slot = k % TG_D;
-    half8 af[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) af[i] = *reinterpret_cast<half8 *>(&wr[slot][i]);
-    __builtin_amdgcn_sched_barrier(0);      // pin the prefetch: hipcc otherwise sinks the loads next to their use (distance 1)
-    if (k + TG_D < 32) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) wr[slot][i] = wp[((k + TG_D) * 4 + i) * 64];
-    }
-    if (k + 1 < 32) {
-      const int kn = k + 1;
-#pragma unroll
-      for (int j = 0; j < 2; ++j) bf[cur ^ 1][j] = *reinterpret_cast<const half8 *>(xb + (kn >> 3) * TG_SEG_BYTES + j * 8192 + xo[kn & 7]);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        if constexpr (EPI == EPI_VT) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bf[cur][j], af[i], acc[i][j], 0, 0, 0);
-        else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[i], bf[cur][j], acc[i][j], 0, 0, 0);
-      }
-  }
+  tok_kloop_db<4, TG_D, EPI == EPI_VT>(wr, wp, tg_smem + lr * 256, xo, acc);
 
   TSTAMP(2);
   __syncthreads();                                       // every wave is done with the tile: the epilogues re-use its LDS
   float *red = reinterpret_cast<float *>(tg_smem + TG_RED_OFF);
 
   if constexpr (EPI == EPI_VT) {
-    // acc[i][j][r]: channel c = wave*128 + i*32 + lr, token j*32 + (r&3) + 8*(r>>2) + 4*lh.  Stage as [channel][token in vt
-    // order] (row = 64 tokens = 128 B + pad), then 16-byte stores along the token axis of the image.
+    // swapped accumulator layout: stage as [channel][token in vt order] (row = 64 tokens = 128 B + pad), then 16-byte stores along
+    // the token axis of the image
     f16 *vs = reinterpret_cast<f16 *>(tg_smem) + (size_t)wave * (128 * TG_VT_LD);
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
       for (int j = 0; j < 2; ++j)
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          half4 hv;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) hv[e] = (f16)acc[i][j][q * 4 + e];
-          const int t = j * 32 + 8 * q + 4 * lh;        // first of 4 consecutive tokens (tile-relative); the tile starts at a multiple of 16
-          *reinterpret_cast<half4 *>(&vs[(i * 32 + lr) * TG_VT_LD + vt_col(t)]) = hv;
-        }
+        for (int q = 0; q < 4; ++q)       // 4 consecutive tokens (tile-relative; the tile starts at a multiple of 16)
+          *reinterpret_cast<half4 *>(&vs[tg_vt_off(acc_vt_chan(i, lr), vt_col(acc_vt_token(j, q * 4, lh)))]) = acc_quad_f16(acc[i][j], q);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     // read back: instruction u covers 8 channel rows x 8 chunks of 8 tokens
     f16 *img = (f16 *)blk.out;
 #pragma unroll
     for (int u = 0; u < 16; ++u) {
       const int c = u * 8 + (lane >> 3), ch8 = lane & 7;
-      const uint4 v = *reinterpret_cast<const uint4 *>(&vs[c * TG_VT_LD + ch8 * 8]);
+      const uint4 v = *reinterpret_cast<const uint4 *>(&vs[tg_vt_off(c, ch8 * 8)]);
       const int m = m0 + ch8 * 8;                       // the 8 tokens of a chunk lie in one group of 16: one hypothesis
-      if (m < p.M) {
-        const int b = m / p.tokens, t = m - b * p.tokens;
-        const int col = blk.coff + wave * 128 + c, h = col >> 7, d = col & 127;
-        f16 *row = img + (((size_t)b * 4 + h) * 128 + d) * 416;
-        *reinterpret_cast<uint4 *>(row + (t & ~15) + (ch8 & 1) * 8) = v;
-        // the image is 416 tokens wide: the lanes that store a hypothesis' last 16 tokens also zero the columns behind them
-        // (the attention kernel reads whole 64-key blocks; was a launch of its own)
-        if ((t & ~15) + 16 == p.tokens)
-          for (int z = p.tokens; z < 416; z += 16) *reinterpret_cast<uint4 *>(row + z + (ch8 & 1) * 8) = uint4{0u, 0u, 0u, 0u};
-      }
+      if (m < p.M) vt_store_unit(img, blk.coff + wave * 128 + c, m, p.tokens, ch8 & 1, v);
     }
     TSTAMP(3);
     return;
   }
 
   if constexpr (EPI == EPI_LN || EPI == EPI_LNSUM) {
-    // residual tile -> the (now free) tile region by LDS-DMA, then added in fp32 in the accumulator layout: global column
-    // wave*128 + i*32 + rg*8 + lh*4 is chunk i*4 + rg of k segment `wave`, 8-byte half lh
+    // residual tile -> the (now free) tile region by LDS-DMA, then added in fp32 in the accumulator layout (a register quad is an
+    // 8-byte half chunk of the tile).  The add and the statistics below stay written out - the independent second implementation
+    // beside head_mlp.hip's: as functions shared with it they cost this kernel 2 VGPRs (EPI_LN) and change the SGPRs of EPI_LNSUM
     tok_tile_dma<TG_ROWS, 4>(p.res, m0, p.M, wave, lane, lds0);
     wait_vm<0>();
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      const int row = j * 32 + lr;
-      const unsigned char *rb = tg_smem + wave * TG_SEG_BYTES + row * 256 + lh * 8;
+      const int row = acc_row_token(j, lr);
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int rg = 0; rg < 4; ++rg) {
-          const half4 rq = *reinterpret_cast<const half4 *>(rb + (((i * 4 + rg) ^ (row & 15)) * 16));
+          const half4 rq = *reinterpret_cast<const half4 *>(tg_smem + tile_quad_off<TG_ROWS, 4>(wave, i, rg, row, lh));
 #pragma unroll
           for (int e = 0; e < 4; ++e) acc[i][j][rg * 4 + e] += (float)rq[e];
         }
@@ -248,21 +199,7 @@ __global__ __launch_bounds__(TG_THREADS, 2) void tok_gemm_kernel(TokGemmArgs p) 
       rstd[j] = rsqrtf(s * (1.f / 512.f) + 1e-5f);
     }
     if constexpr (EPI == EPI_LNSUM) {
-      // sums of the normalised values over groups of 16 tokens (lanes lr 0-15 / 16-31 of a token tile = one DPP row each);
-      // gamma / beta are applied after the token mean (mean_head_kernel)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int rg = 0; rg < 4; ++rg) {
-            float v[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = row16_sum(acc[i][j][rg * 4 + e] * rstd[j]);
-            const int g = (m0 + j * 32 + (lr & 16)) >> 4;          // global 16-token group
-            if ((lr & 15) == 0 && g * 16 < p.M)
-              *reinterpret_cast<float4 *>(p.gsum + (size_t)g * 512 + wave * 128 + i * 32 + rg * 8 + lh * 4) = make_float4(v[0], v[1], v[2], v[3]);
-          }
+      tok_gsum_store<4>(TokLane{lane, wave, lr, lh}, acc, rstd, m0, p.M, p.gsum);   // gamma / beta are applied after the token mean (mean_head_kernel)
       TSTAMP(3);
       return;
     }
@@ -295,18 +232,16 @@ __global__ __launch_bounds__(TG_THREADS, 2) void tok_gemm_kernel(TokGemmArgs p) 
       for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int rg = 0; rg < 4; ++rg) {
-          half4 hv;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) hv[e] = (f16)acc[i][j][rg * 4 + e];
-          if (relu) hv = __builtin_elementwise_max(hv, half4{(f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f});
-          *reinterpret_cast<half4 *>(&stage[(j * 32 + lr) * TG_STAGE_LD + i * 32 + rg * 8 + lh * 4]) = hv;
+          half4 hv = acc_quad_f16(acc[i][j], rg);
+          if (relu) hv = relu4(hv);
+          *reinterpret_cast<half4 *>(&stage[tg_stage_off(acc_row_token(j, lr), acc_row_chan(i, rg, lh))]) = hv;
         }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     f16 *obase = (f16 *)blk.out + blk.coff + wave * 128;
 #pragma unroll
     for (int u = 0; u < 16; ++u) {
       const int px = u * 4 + (lane >> 4), c16 = lane & 15;
-      const uint4 v = *reinterpret_cast<const uint4 *>(&stage[px * TG_STAGE_LD + c16 * 8]);
+      const uint4 v = *reinterpret_cast<const uint4 *>(&stage[tg_stage_off(px, c16 * 8)]);
       if (m0 + px < p.M) *reinterpret_cast<uint4 *>(obase + (size_t)(m0 + px) * blk.ld + c16 * 8) = v;
     }
     TSTAMP(3);
@@ -328,22 +263,33 @@ void tok_gemm_kernel_lds(std::vector<KernelLds> &v) {
   v.push_back({(const void *)tok_gemm_kernel<EPI_LNSUM>, TG_LDS_BYTES});
 }
 
-int launch_tok_gemm(fp_ctx *ctx, const TokGemmArgs &a, int epi, hipStream_t s) {
-  FP_REQUIRE(a.in && a.M >= 0 && a.nblk >= 1 && a.nblk <= TG_MAXBLK, "tok_gemm: bad arguments");
+int tok_check_args(const char *who, const TokGemmArgs &a, int out, int coff_align) {
+  FP_REQUIRE(a.in && a.M >= 0 && a.nblk >= 1 && a.nblk <= TG_MAXBLK, "%s: bad arguments", who);
   if (a.M == 0) return FP_OK;
-  FP_REQUIRE((double)a.M * TG_K * 2.0 < 4294967296.0, "tok_gemm: M=%d too large for 32-bit lane offsets", a.M);
-  for (int b = 0; b < a.nblk; ++b) FP_REQUIRE(a.blk[b].w && a.blk[b].bias, "tok_gemm: block %d has null weights", b);
+  FP_REQUIRE((double)a.M * TOK_K * 2.0 < 4294967296.0, "%s: M=%d too large for 32-bit lane offsets", who, a.M);
+  for (int b = 0; b < a.nblk; ++b) {
+    const TokGemmBlock &k = a.blk[b];
+    FP_REQUIRE(k.w && k.bias, "%s: block %d has null weights", who, b);
+    const int o = out == TOK_OUT_BLK ? (k.vt ? TOK_OUT_VT : TOK_OUT_ROWS) : out;
+    if (o == TOK_OUT_NONE) continue;
+    FP_REQUIRE(k.out && k.coff % coff_align == 0, "%s: bad output of block %d", who, b);
+    if (o == TOK_OUT_VT) FP_REQUIRE(a.tokens > 0 && a.tokens % 16 == 0 && a.tokens <= VT_LD, "%s: tokens=%d must be a multiple of 16, <= 416", who, a.tokens);
+    else FP_REQUIRE(k.ld % 8 == 0, "%s: row stride of block %d is not a multiple of 8", who, b);
+  }
+  return FP_OK;
+}
+
+int launch_tok_gemm(fp_ctx *ctx, const TokGemmArgs &a, int epi, hipStream_t s) {
+  FP_TRY(tok_check_args("tok_gemm", a, epi == EPI_VT ? TOK_OUT_VT : epi == EPI_LNSUM ? TOK_OUT_NONE : TOK_OUT_ROWS, epi == EPI_ROWS ? 128 : 1));
+  if (a.M == 0) return FP_OK;
   ProfScope ps(ctx, s, "linear", 2.0 * (double)a.M * 512.0 * 512.0 * a.nblk);
   switch (epi) {
     case EPI_ROWS:
-      for (int b = 0; b < a.nblk; ++b) FP_REQUIRE(a.blk[b].out && a.blk[b].ld % 8 == 0 && a.blk[b].coff % 128 == 0, "tok_gemm: bad output of block %d", b);
       return tg_launch<EPI_ROWS>(a, s);
     case EPI_VT:
-      FP_REQUIRE(a.tokens > 0 && a.tokens % 16 == 0 && a.tokens <= 416, "tok_gemm: tokens=%d must be a multiple of 16, <= 416", a.tokens);
-      for (int b = 0; b < a.nblk; ++b) FP_REQUIRE(a.blk[b].out, "tok_gemm: block %d has no output", b);
       return tg_launch<EPI_VT>(a, s);
     case EPI_LN:
-      FP_REQUIRE(a.nblk == 1 && a.res && a.gamma && a.beta && a.blk[0].out && a.blk[0].ld % 8 == 0, "tok_gemm: LN epilogue needs one block, residual, gamma, beta");
+      FP_REQUIRE(a.nblk == 1 && a.res && a.gamma && a.beta, "tok_gemm: LN epilogue needs one block, residual, gamma, beta");
       return tg_launch<EPI_LN>(a, s);
     case EPI_LNSUM:
       FP_REQUIRE(a.nblk == 1 && a.res && a.gsum && a.M % 16 == 0, "tok_gemm: LN-sum epilogue needs one block, residual, gsum, M %% 16 == 0");

@@ -5,22 +5,22 @@
 // What bounds a token GEMM on this chip is the weight stream L2 -> registers: tok_gemm.hip's 64-token tile re-streams the 512 KB of a
 // 512-column block per 64 tokens, 64 B/clk/CU at the MFMA rate where the path delivers ~30-35 (MI355X_MICROARCH.md: 66-73 GB/s per CU
 // from the XCD's L2), and it loads the token tile once per block.  Here
-//   * a workgroup (8 waves, one per CU) keeps a tile of 128 tokens x 512 (128 KB) resident in LDS - tok_gemm.hip's image: k segments
-//     of 128, 256-byte row segments, 16-byte chunk c of a row at c ^ (row & 15): conflict-free ds_read_b128 - and walks the column
-//     blocks over it: the tile is loaded once for all blocks, and a weight fragment (one coalesced 1-KB load per wave, fragment order
-//     of pack_tok_weights) now feeds FOUR MFMAs: 32 B/clk/CU at the MFMA rate;
+//   * a workgroup (8 waves, one per CU) keeps a tile of 128 tokens x 512 (128 KB) resident in LDS (layouts of the tile, the weight
+//     fragments, the accumulators, the stagings and the V image: tok_tile.h) and walks the column blocks over it: the tile is loaded
+//     once for all blocks, and a weight fragment (one coalesced 1-KB load per wave) now feeds FOUR MFMAs: 32 B/clk/CU at the MFMA rate;
 //   * a wave owns 64 output columns x 128 tokens (2 x 4 accumulator tiles, v_mfma_f32_32x32x16_f16); the K loop has no barrier and no
 //     LDS write: per k-step of 16 two weight fragments (prefetched 3 steps ahead), four token fragments, eight MFMAs;
 //   * work = (tile, block) units in tile-major order, cut into equal contiguous ranges over the workgroups (at most one per CU): a
 //     launch is balanced to one unit whatever M is - 252 hypotheses are 788 tiles x 6 blocks = 18.5 units per CU, 32 hypotheses 100
 //     x 6 = 2.3 - and a workgroup reloads the tile only when its range crosses into the next one;
 //   * epilogues, per wave and 32-token slice through a private 4-KB staging area (the two waves of a SIMD drift apart: one's epilogue
-//     runs beside the other's K loop): fp16 rows as whole 128-byte segments (q | k), or the transposed V image [b][4][128][416] in the
-//     attention kernel's token order (vt_col; MFMA operands swapped so that a lane owns a channel and 4 consecutive tokens).
+//     runs beside the other's K loop): fp16 rows as whole 128-byte segments (q | k), or the transposed V image (MFMA operands
+//     swapped so that a lane owns a channel and 4 consecutive tokens).
 // Arithmetic per output element is that of tok_gemm.hip (bias first, k ascending in steps of 16, one rounding to fp16): bit-identical
 // (tests/test_gpu_kernels.py::test_token_qkv_equals_the_64_token_kernel).
 #include "common.h"
 #include "device_util.h"
+#include "tok_tile.h"
 
 #define TQ_ROWS 128
 #define TQ_THREADS 512
@@ -35,48 +35,10 @@ __device__ __forceinline__ void tq_kloop(const TokGemmBlock &blk, const unsigned
   const int lr = lane & 31, lh = lane >> 5;
   if constexpr (VT) acc_from_bias_vt(acc, blk.bias, wave * 64, lr);
   else acc_from_bias(acc, blk.bias, wave * 64, lh);
-  // packed [wave4][k16 32][i4 4][lane 64][8 halfs] (pack_tok_weights): this wave's fragments are (wave >> 1, k16, (wave & 1) * 2 + i)
-  const u32x4 *wp = reinterpret_cast<const u32x4 *>(blk.w) + (size_t)(wave >> 1) * (32 * 4 * 64) + ((wave & 1) * 2) * 64 + lane;
-  constexpr int D = 3;                    // weight prefetch distance in k-steps (4 spills)
-  u32x4 wr[D][2];
-#pragma unroll
-  for (int d = 0; d < D; ++d)
-#pragma unroll
-    for (int i = 0; i < 2; ++i) wr[d][i] = wp[(d * 4 + i) * 64];
-  // token fragments: row j*32 + lr, chunk (2*(k16&7) + lh) ^ (lr & 15) of segment k16 >> 3 - the even part of the XOR is applied per
-  // k-step (one v_xor), the odd part and the row sit in the base.  The four fragments of a k-step rotate through ONE register set: the
-  // fragment of (k+1, j) is requested right behind the MFMAs of (k, j) - six MFMAs (192 cycles) cover its latency.
-  const unsigned char *xb = tile + lr * 256 + ((lh ^ (lr & 1)) * 16);
-  const unsigned xe = (unsigned)(lr & 14);
-  half8 bf[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) bf[j] = *reinterpret_cast<const half8 *>(xb + j * 8192 + (xe << 4));
-#pragma unroll
-  for (int k = 0; k < 32; ++k) {
-    const int slot = k % D;
-    half8 af[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) af[i] = *reinterpret_cast<half8 *>(&wr[slot][i]);
-    __builtin_amdgcn_sched_barrier(0);      // pin the prefetch (hipcc otherwise sinks the loads next to their use)
-    if (k + D < 32) {
-#pragma unroll
-      for (int i = 0; i < 2; ++i) wr[slot][i] = wp[((k + D) * 4 + i) * 64];
-    }
-    const int kn = k + 1;
-    const unsigned char *xn = xb + (kn >> 3) * TQ_SEG_BYTES + (((unsigned)(2 * (kn & 7)) ^ xe) << 4);
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        if constexpr (VT) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bf[j], af[i], acc[i][j], 0, 0, 0);
-        else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[i], bf[j], acc[i][j], 0, 0, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      if (kn < 32) bf[j] = *reinterpret_cast<const half8 *>(xn + j * 8192);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  }
+  const u32x4 *wp = reinterpret_cast<const u32x4 *>(blk.w) + wfrag_own8(wave, 0, 0) * 64 + lane;
+  u32x4 wr[3][2];                         // weight prefetch distance 3 k-steps (4 spills)
+  tok_w_prefetch(wr, wp);
+  tok_kloop_rot<VT, false>(wr, wp, tile, lr, lh, acc, nullptr);
 }
 
 __global__ __launch_bounds__(TQ_THREADS, 1) void tok_qkv_kernel(TokGemmArgs p, int n_units, int units_per_wg) {
@@ -101,44 +63,29 @@ __global__ __launch_bounds__(TQ_THREADS, 1) void tok_qkv_kernel(TokGemmArgs p, i
     floatx16 acc[2][4];
     if (blk.vt) {
       tq_kloop<true>(blk, tq_smem, wave, lane, acc);
-      // acc[i][j][r]: channel c = wave*64 + i*32 + lr, token j*32 + (r&3) + 8*(r>>2) + 4*lh.  Per 32-token slice: stage [channel][token
-      // in vt order] (64-byte rows, 16-byte units XORed with (c >> 1) & 3), then 16-byte stores along the token axis of the image
+      // swapped accumulator layout.  Per 32-token slice: stage [channel][token in vt order] (tq_vt_off), then 16-byte stores along the
+      // token axis of the image
       f16 *img = (f16 *)blk.out;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            half4 hv;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) hv[e] = (f16)acc[i][j][q * 4 + e];
-            const int c = i * 32 + lr, t = 8 * q + 4 * lh;           // first of 4 consecutive tokens inside the slice
-            const int pos = vt_col(t);                                // a multiple of 4
-            *reinterpret_cast<half4 *>(stage + c * 64 + ((((pos >> 3) ^ ((c >> 1) & 3)) * 16) + (pos & 4) * 2)) = hv;
-          }
+          for (int q = 0; q < 4; ++q)       // 4 consecutive tokens inside the slice
+            *reinterpret_cast<half4 *>(stage + tq_vt_off(acc_vt_chan(i, lr), vt_col(acc_vt_token(0, q * 4, lh)))) = acc_quad_f16(acc[i][j], q);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
 #pragma unroll
         for (int v = 0; v < 4; ++v) {
           const int c = v * 16 + (lane >> 2), unit = lane & 3;
-          const uint4 val = *reinterpret_cast<const uint4 *>(stage + c * 64 + ((unit ^ ((c >> 1) & 3)) * 16));
+          const uint4 val = *reinterpret_cast<const uint4 *>(stage + tq_vt_off(c, unit * 8));
           const int m = m0 + j * 32 + unit * 8;                     // the 8 tokens of a unit lie in one group of 16: one hypothesis
-          if (m < p.M) {
-            const int bb = m / p.tokens, t = m - bb * p.tokens;
-            const int col = blk.coff + wave * 64 + c, h = col >> 7, d = col & 127;
-            f16 *row = img + (((size_t)bb * 4 + h) * 128 + d) * 416;
-            *reinterpret_cast<uint4 *>(row + (t & ~15) + (unit & 1) * 8) = val;
-            // the image is 416 tokens wide: the lanes that store a hypothesis' last 16 tokens also zero the columns behind them
-            if ((t & ~15) + 16 == p.tokens)
-              for (int z = p.tokens; z < 416; z += 16) *reinterpret_cast<uint4 *>(row + z + (unit & 1) * 8) = uint4{0u, 0u, 0u, 0u};
-          }
+          if (m < p.M) vt_store_unit(img, blk.coff + wave * 64 + c, m, p.tokens, unit & 1, val);
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       }
     } else {
       tq_kloop<false>(blk, tq_smem, wave, lane, acc);
-      // fp16 rows: per 32-token slice the wave's 64 columns through its staging (128-byte rows, 16-byte units XORed with row & 7),
-      // then whole 128-byte row segments
+      // fp16 rows: per 32-token slice the wave's 64 columns through its staging (tq_stage_off), then whole 128-byte row segments
       const bool relu = blk.relu != 0;
       f16 *obase = (f16 *)blk.out + blk.coff + wave * 64;
 #pragma unroll
@@ -147,17 +94,15 @@ __global__ __launch_bounds__(TQ_THREADS, 1) void tok_qkv_kernel(TokGemmArgs p, i
         for (int i = 0; i < 2; ++i)
 #pragma unroll
           for (int rg = 0; rg < 4; ++rg) {
-            half4 hv;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) hv[e] = (f16)acc[i][j][rg * 4 + e];
-            if (relu) hv = __builtin_elementwise_max(hv, half4{(f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f});
-            *reinterpret_cast<half4 *>(stage + lr * 128 + (((i * 4 + rg) ^ (lr & 7)) * 16) + lh * 8) = hv;
+            half4 hv = acc_quad_f16(acc[i][j], rg);
+            if (relu) hv = relu4(hv);
+            *reinterpret_cast<half4 *>(stage + tq_stage_off(lr, acc_row_chan(i, rg, lh))) = hv;
           }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
 #pragma unroll
         for (int v = 0; v < 4; ++v) {
           const int row = v * 8 + (lane >> 3), unit = lane & 7;
-          const uint4 val = *reinterpret_cast<const uint4 *>(stage + row * 128 + ((unit ^ (row & 7)) * 16));
+          const uint4 val = *reinterpret_cast<const uint4 *>(stage + tq_stage_off(row, unit * 8));
           const int m = m0 + j * 32 + row;
           if (m < p.M) *reinterpret_cast<uint4 *>(obase + (size_t)m * blk.ld + unit * 8) = val;
         }
@@ -185,14 +130,15 @@ __global__ __launch_bounds__(512, 2) void tok_qkv_small_kernel(TokGemmArgs p) {
   const int g = blockIdx.x & 3, b = (blockIdx.x >> 2) % p.nblk, tl = (blockIdx.x >> 2) / p.nblk;
   const TokGemmBlock &blk = p.blk[b];
   const int m0 = tl * 32;
-  // weights: fragment (g, k16, i) of the packed image is 64 lanes x 16 bytes
+  // weights: this wave's 16 fragments (column quarter g, K quarter kq, column half chh)
   u32x4 wf[8][2];
   {
-    const u32x4 *wp = reinterpret_cast<const u32x4 *>(blk.w) + ((size_t)g * 32 + kq * 8) * 4 * 64 + (chh * 2) * 64 + lane;
+    // (wfrag is linear in its arguments: the wave-uniform and the per-wave part as two terms; as one term: one more lgkmcnt wait)
+    const u32x4 *wp = reinterpret_cast<const u32x4 *>(blk.w) + wfrag_own_small(g, kq, 0, 0, 0) * 64 + wfrag_own_small(0, 0, chh, 0, 0) * 64 + lane;
 #pragma unroll
     for (int k = 0; k < 8; ++k)
 #pragma unroll
-      for (int i = 0; i < 2; ++i) wf[k][i] = wp[(k * 4 + i) * 64];
+      for (int i = 0; i < 2; ++i) wf[k][i] = wp[wfrag(0, k, i) * 64];
   }
   // the token tile: rows m0 .. m0 + 31 (rows past M repeat the last one), 2048 pieces of 16 bytes
   {
@@ -272,6 +218,7 @@ __global__ __launch_bounds__(512, 2) void tok_qkv_small_kernel(TokGemmArgs p) {
     if (pos < 8) lo[pos] = hx;
     else hi[pos - 8] = hx;
   }
+  // (tok_tile.h's vt_row and vt_store_unit written out: either one moves this kernel's lgkmcnt waits; two calls of the latter are 9 more stores)
   f16 *rowp = (f16 *)blk.out + (((size_t)bb * 4 + hh) * 128 + d) * 416;
   *reinterpret_cast<half8 *>(rowp + t0) = lo;
   *reinterpret_cast<half8 *>(rowp + t0 + 8) = hi;
@@ -285,15 +232,8 @@ void tok_qkv_kernel_lds(std::vector<KernelLds> &v) {
 }
 
 int launch_tok_qkv(fp_ctx *ctx, const TokGemmArgs &a, hipStream_t s, int hyp) {
-  FP_REQUIRE(a.in && a.M >= 0 && a.nblk >= 1 && a.nblk <= TG_MAXBLK, "tok_qkv: bad arguments");
+  FP_TRY(tok_check_args("tok_qkv", a, TOK_OUT_BLK, 64));
   if (a.M == 0) return FP_OK;
-  FP_REQUIRE((double)a.M * 512 * 2.0 < 4294967296.0, "tok_qkv: M=%d too large for 32-bit lane offsets", a.M);
-  for (int b = 0; b < a.nblk; ++b) {
-    const TokGemmBlock &k = a.blk[b];
-    FP_REQUIRE(k.w && k.bias && k.out, "tok_qkv: block %d has a null pointer", b);
-    if (k.vt) FP_REQUIRE(a.tokens > 0 && a.tokens % 16 == 0 && a.tokens <= 416 && k.coff % 64 == 0, "tok_qkv: tokens=%d must be a multiple of 16, <= 416", a.tokens);
-    else FP_REQUIRE(k.ld % 8 == 0 && k.coff % 64 == 0, "tok_qkv: bad output of block %d", b);
-  }
   ProfScope ps(ctx, s, "linear", 2.0 * (double)a.M * 512.0 * 512.0 * a.nblk);
   if (qkv_form(hyp, hyp, pass_knobs()) == QKV_SMALL) {          // (the 64-token pair is two launch_tok_gemm launches: run_qkv, net.hip)
     hipLaunchKernelGGL(tok_qkv_small_kernel, dim3(((a.M + 31) / 32) * a.nblk * 4), dim3(512), TS_LDS_BYTES, s, a);

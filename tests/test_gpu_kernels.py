@@ -965,6 +965,66 @@ def test_head_mlp_vs_fp32_reference(fp, n_hyp):
   assert d <= 2.5e-3 * float(ref.abs().max()) + 1e-3
 
 
+def token_kernel_digests(ctx):
+  """SHA-256 of every output buffer of the token kernels on seeded CPU inputs, NaN-prefilled: {case: hex digest}."""
+  import hashlib
+  from foundationpose_amd._lib import check, lib, ptr, stream_ptr
+  sha = lambda t: hashlib.sha256(t.cpu().numpy().tobytes()).hexdigest()
+  mk = lambda g: (torch.randn((512, 512), generator=g) * (1.0 / 512) ** 0.5).half().float()
+  out = {}
+  for M in (400, 800, 1200):
+    g = torch.Generator().manual_seed(900 + M)
+    x = torch.randn((M, 512), generator=g).half()
+    w, b = mk(g), torch.randn((512,), generator=g) * 0.1
+    res = (torch.randn((M, 512), generator=g) * 2 + 0.5).half()
+    gam, bet = torch.rand((512,), generator=g) + 0.5, torch.randn((512,), generator=g) * 0.1
+    x_d, res_d = x.cuda(), res.cuda()
+    for epi in ((6, 7) if M == 800 else range(8) if M == 400 else range(6)):    # 6 / 7: the few-image form, one and two hypotheses
+      for relu in ((0, 1) if epi in (0, 2, 4, 6) else (0,)):                    # (the V image and the group sums have no ReLU)
+        if epi in (1, 5, 7):
+          buf = torch.full((M // 400, 4, 128, 416), float('nan'), dtype=torch.float16, device='cuda')
+        elif epi == 3:
+          buf = torch.full((M // 16, 512), float('nan'), dtype=torch.float32, device='cuda')
+        else:
+          buf = torch.full((M, 512), float('nan'), dtype=torch.float16, device='cuda')
+        check(lib().fp_token_linear_f16(ctx.handle, ptr(x_d), M, ptr(w.numpy()), ptr(b.numpy()), epi, relu, ptr(res_d) if epi in (2, 3) else None,
+                                        ptr(gam.numpy()) if epi == 2 else None, ptr(bet.numpy()) if epi == 2 else None, 400, ptr(buf), stream_ptr()))
+        out[f'linear_epi{epi}_relu{relu}_M{M}'] = sha(buf)
+  for M in (400, 2000):
+    g = torch.Generator().manual_seed(950 + M)
+    att = torch.randn((M, 512), generator=g).half()
+    tok = (torch.randn((M, 512), generator=g) * 2 + 0.5).half()
+    w_out, w1, w2 = mk(g), mk(g), mk(g)
+    b_out, b1, b2 = (torch.randn((512,), generator=g) * 0.1 for _ in range(3))
+    gam, bet = torch.rand((512,), generator=g) + 0.5, torch.randn((512,), generator=g) * 0.1
+    att_d, tok_d = att.cuda(), tok.cuda()
+    buf = torch.full((M // 16, 512), float('nan'), dtype=torch.float32, device='cuda')
+    check(lib().fp_head_mlp_f16(ctx.handle, ptr(att_d), ptr(tok_d), M, *[ptr(t.numpy()) for t in (w_out, b_out, gam, bet, w1, b1, w2, b2)],
+                                ptr(buf), stream_ptr()))
+    out[f'head_mlp_M{M}'] = sha(buf)
+  return out
+
+
+def test_token_kernels_bits_are_the_recorded_ones(fp):
+  """The token kernels (csrc/tok_gemm.hip, tok_qkv.hip, head_mlp.hip; layouts in csrc/tok_tile.h) write the bits they wrote before
+  csrc/tok_tile.h existed.  fp_token_linear_f16 epilogues 0 .. 7 (ReLU off and on for the row epilogues) with 400 tokens per hypothesis at
+  M = 400 and 1200 - 400 = 6 x 64 + 16 = 3 x 128 + 16 ends both tile sizes ragged, 1200 makes a tok_qkv workgroup's range cross tiles -
+  and the few-image epilogues 6 / 7 at M = 400 and 800; fp_head_mlp_f16 at M = 400 (the 64-token form, M <= 1600) and
+  M = 2000 = 15 x 128 + 80 (the 128-token form with a ragged tile).  Seeded CPU inputs, every output buffer prefilled with NaN, the
+  SHA-256 of each whole buffer against tests/golden/token_kernels_bits.json.
+  How the file was recorded: token_kernel_digests() above, run on an MI355X with the library built from the commit before tok_tile.h
+  (6ffbf84), before any kernel file was touched; its dict written as JSON.  A digest may be re-recorded only by a pull request that
+  means to change the arithmetic of these kernels, and says so."""
+  import json
+  import os
+  with open(os.path.join(os.path.dirname(__file__), 'golden', 'token_kernels_bits.json')) as f:
+    want = json.load(f)
+  got = token_kernel_digests(fp['ctx'])
+  assert sorted(got) == sorted(want)
+  bad = [k for k in sorted(want) if got[k] != want[k]]
+  assert not bad, bad
+
+
 def test_profiling_busy_time_is_the_union_of_launch_spans(fp):
   """fp_prof_read / fp_prof_read_busy (bench.py's roofline figure): per kernel class the sum of the launch spans and the time with at
   least one launch executing.  A RefineNet pass on 8 hypotheses: the convolutions follow one another on one stream (busy == sum of
