@@ -389,7 +389,7 @@ int small_pack_weights(const f16 *d_w, int Cout, int Cin, int Kpad, f16 *d_out, 
 size_t conv_packed_halfs(unsigned packing, int Cout, int Cin);
 int conv_pack_weights(unsigned packing, const f16 *d_w, int Cout, int Cin, int Kpad, f16 *d_out, hipStream_t s);
 
-// (the transposed V image [b][4][128][416] and its token order vt_col(): tok_tile.h)
+// attn.hip (the transposed V image [b][4][128][416] and its token order vt_col(): tok_tile.h; the kernels' layouts: attn_tile.h)
 int launch_attention(fp_ctx *ctx, const f16 *qk, const f16 *vt, int B, int T, f16 *out, hipStream_t s);
 
 // Token GEMM (tok_gemm.hip): out = x (M x 512) @ W^T + b for up to TG_MAXBLK blocks of 512 output columns in one launch.
@@ -427,7 +427,7 @@ struct HeadMlpArgs {
   float *gsum;                 // [M/16][512] sums of the LayerNorm2-normalised rows over groups of 16 tokens
 };
 int launch_head_mlp(fp_ctx *ctx, const HeadMlpArgs &a, hipStream_t s);
-// Sum of `nparts` consecutive partial rows per hypothesis (fixed order) / T, gamma, beta, Linear(512 -> out_dim)
+// refine_tail.hip: sum of `nparts` consecutive partial rows per hypothesis (fixed order) / T, gamma, beta, Linear(512 -> out_dim)
 int launch_mean_head(const float *partial, int nparts, const float *g, const float *b, int Bn, int T, const float *hw, const float *hb,
                      int out_dim, float *out, hipStream_t s);
 // score_tail.hip: token mean + att.out_proj of ScoreNet in one launch; att_cross + linear + argmax in two
@@ -448,7 +448,7 @@ int launch_score_tail(const float *feats, int feat_ld, const float *wqk_t, const
 #define FP_TAIL_MAX_GROUPS 4096
 int fp_score_tail_impl(fp_ctx *ctx, const fp_net *net, const float *d_feats, int feat_ld, int groups, int L, const ScoreTailOut &o, hipStream_t s);      // net.hip
 // trans_tanh: 0 raw, 1 tanh * trans_normalizer, 2 trans_rep='deepim' (needs tf N x 9, K, resize = input_resize[0])
-// The tail of a refinement pass as one launch (attn.hip: refine_tail_kernel): both heads' token mean + output Linear, the pose update in
+// The tail of a refinement pass as one launch (refine_tail.hip: refine_tail_kernel): both heads' token mean + output Linear, the pose update in
 // place and, with `next_window`, the crop windows of the next iteration (tf / bbox overwritten; the deepim branch reads tf first)
 struct CropWindowK {             // intrinsics as float, radius = diameter * crop_ratio / 2, output size (crop_window_tf_one, pose_math.h)
   float k00, k01, k02, k10, k11, k12, k20, k21, k22, radius, ow, oh;

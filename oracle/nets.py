@@ -132,7 +132,7 @@ def score_forward(sd, A, B, L, use_bn=True, taps=None, chunk=None):
 # the weights ONCE (net.hip make_conv); every conv output after bias + residual + ReLU (+ pe) in fp32 (conv*.hip epilogues);
 # q, k, v rows (tok_qkv.hip); the un-normalised softmax numerators per 64-key block against the running maximum, and the
 # attention output (attn.hip); x1 = LayerNorm1(..) and ReLU(linear1) (head_mlp.hip).  LayerNorm2, token mean and the output
-# Linear stay fp32 (attn.hip refine_tail_kernel).
+# Linear stay fp32 (refine_tail.hip refine_tail_kernel).
 # ------------------------------------------------------------------------------------------------------------------------
 def _h(t):
   return t.half().float()

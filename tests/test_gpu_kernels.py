@@ -1025,6 +1025,49 @@ def test_token_kernels_bits_are_the_recorded_ones(fp):
   assert not bad, bad
 
 
+ATTENTION_BITS_CASES = [(3, 400), (3, 230), (3, 64), (3, 37), (3, 1), (33, 400), (300, 37), (1, 400), (1, 37), (2, 400), (2, 37)]
+
+
+def attention_digests(ctx):
+  """SHA-256 of the NaN-prefilled output of fp_attention_f16 on seeded CPU inputs: {'B<B>_T<T>': hex digest}."""
+  import hashlib
+  from foundationpose_amd._lib import check, lib, ptr, stream_ptr
+  out = {}
+  for B, T in ATTENTION_BITS_CASES:
+    g = torch.Generator().manual_seed(7000 + 1000 * B + T)
+    qk = (torch.randn((B * T, 1024), generator=g) * 1.5).half()
+    v = torch.randn((B, 4, 128, T), generator=g).half()
+    vt = torch.zeros((B, 4, 128, 416), dtype=torch.float16)
+    t = np.arange(T)
+    vt[..., torch.from_numpy((t & ~15) | (((t >> 2) & 1) << 3) | (((t >> 3) & 1) << 2) | (t & 3))] = v       # the image's token order (vt_col, csrc/tok_tile.h)
+    qk_d, vt_d = qk.cuda(), vt.cuda()
+    buf = torch.full((B * T, 512), float('nan'), dtype=torch.float16, device='cuda')
+    check(lib().fp_attention_f16(ctx.handle, ptr(qk_d), ptr(vt_d), B, T, ptr(buf), stream_ptr()))
+    out[f'B{B}_T{T}'] = hashlib.sha256(buf.cpu().numpy().tobytes()).hexdigest()
+  return out
+
+
+def test_attention_bits_are_the_recorded_ones(fp):
+  """The attention kernels (csrc/attn.hip; layouts, DMA slots and wait counts in csrc/attn_tile.h) write the bits they wrote before
+  csrc/attn_tile.h existed.  fp_attention_f16 at the smallest sizes that reach every path.  attention_kernel, 3 hypotheses: T = 400
+  (tail key block 16 / 64 full, two query blocks), 230 (second query block partly empty: waves without a query), 64 (one block, no tail),
+  37 and 1 (single partial block); 33 x 400 = 264 items (some workgroups walk a second item: the DMA ring, the Q^T staging and the
+  store accounting cross an item boundary); 300 x 37 (one key block per item, several items per workgroup).  attention_small_kernel (the
+  few-image form): 1 and 2 hypotheses at T = 400 and 37.  Seeded CPU inputs, the output prefilled with NaN, the SHA-256 of the whole
+  buffer against tests/golden/attention_bits.json.
+  How the file was recorded: attention_digests() above, run on an MI355X with the library built from the commit before attn_tile.h
+  (fb23685), before any kernel file was touched; its dict written as JSON.  A digest may be re-recorded only by a pull request that
+  means to change the arithmetic of these kernels, and says so."""
+  import json
+  import os
+  with open(os.path.join(os.path.dirname(__file__), 'golden', 'attention_bits.json')) as f:
+    want = json.load(f)
+  got = attention_digests(fp['ctx'])
+  assert sorted(got) == sorted(want)
+  bad = [k for k in sorted(want) if got[k] != want[k]]
+  assert not bad, bad
+
+
 def test_profiling_busy_time_is_the_union_of_launch_spans(fp):
   """fp_prof_read / fp_prof_read_busy (bench.py's roofline figure): per kernel class the sum of the launch spans and the time with at
   least one launch executing.  A RefineNet pass on 8 hypotheses: the convolutions follow one another on one stream (busy == sum of
