@@ -15,8 +15,7 @@
 // v_mfma_f32_32x32x16_f16; both operands staged by LDS-DMA through a 3-deep ring (below).  The 3x3 stride-1 layers
 // have their own kernel (conv_halo.hip).
 #include "common.h"
-#include "device_util.h"
-#include "tok_tile.h"
+#include "conv_tile.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -24,12 +23,11 @@
 
 // ------------------------------------------------------------------------------------------------
 // 256 pixels x BM couts per workgroup, both operands staged by LDS-DMA (global_load_lds_dwordx4,
-// per-lane gather address, out-of-image taps read a zero page), XOR-swizzled 64-byte rows
-// (conflict-free ds_read_b128), 3-deep ring: two K-steps of DMA are in flight under the current
+// per-lane gather address, out-of-image taps read a zero page), the swizzled 64-byte row tile of
+// conv_tile.h (conflict-free ds_read_b128), 3-deep ring: two K-steps of DMA are in flight under the current
 // step's 16 MFMAs per wave.  Used for the 1x1 (Linear) layers, the stride-2 3x3 and the 7x7 stem.
 // ------------------------------------------------------------------------------------------------
-#define C2_BN 256
-// (C2_BK = 32, K per step: conv_plan.h)
+// (C2_BK = 32, K per step: conv_plan.h; C2_BN = 256 pixels and every index rule: conv_tile.h)
 
 #ifdef HALO_STAMP
 // diagnostic build only (make -B EXTRA=-DHALO_STAMP): per-wave cycle counts of prologue / K loop / epilogue
@@ -51,23 +49,22 @@ template <int BM, int KW, bool CIN8, int NT, bool RES, bool SPLIT = false>
 __device__ __forceinline__ void igemm2_tile(const ConvArgs &p, const f16 *__restrict__ zero_page, const int m0, const int c0, f16 *smem, const int ks = 0) {
   constexpr int TN = 64 * NT;                              // pixels per workgroup
   constexpr int XH = TN * C2_BK, WH = BM * C2_BK;          // halfs per stage
-  constexpr int SLD = BM + 8;                              // halfs per staged output row
   ISTAMP(const unsigned long long t_entry = __builtin_amdgcn_s_memtime();)
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
   constexpr int WM = BM / 2, MT = WM / 32;
-  constexpr int WQ = BM / 64;                              // weight DMA instructions per wave per stage
+  constexpr int WQ = c2_wq(BM);                            // weight DMA instructions per wave per stage
   const int lr = lane & 31, lh = lane >> 5;
   const int HoWo = p.Ho * p.Wo;
   const int ntaps = p.KH * p.KW;
 
-  // ---- DMA source bookkeeping: this lane feeds LDS chunk (px = (q*4+wave)*16 + lane/4, chp = lane&3) ----
+  // ---- DMA source bookkeeping: instruction q of this wave is slot q*4 + wave of the pixel image (gather form, conv_tile.h) ----
   const int chp = lane & 3;
   long long xbase[NT];
   int iy0[NT], ix0[NT], xch[NT];
 #pragma unroll
   for (int q = 0; q < NT; ++q) {
-    const int px = (q * 4 + wave) * 16 + (lane >> 2);
+    const int px = ct_dma_row(ct_dma_slot(q, 4, wave), lane);
     const int m = m0 + px;
     const bool mv = m < p.M;
     const int mm = mv ? m : 0;
@@ -76,9 +73,9 @@ __device__ __forceinline__ void igemm2_tile(const ConvArgs &p, const f16 *__rest
     iy0[q] = mv ? oy * p.stride - p.pad : -100000;          // invalid pixel -> every tap out of range
     ix0[q] = ox * p.stride - p.pad;
     xbase[q] = (long long)n * p.H * p.W * p.Cin;
-    xch[q] = chp ^ ((px >> 2) & 3);                          // source chunk (swizzle on the SOURCE side)
+    xch[q] = ct_dma_chunk(px, lane);                         // source chunk (swizzle on the SOURCE side)
   }
-  // weights: instruction q of wave w covers couts (q*4 + w)*16 + lane/4; the swizzle term ((co>>2)&3) = (lane>>4)&3 does not
+  // weights (the rule is ct_w_off; written out: profiles/conv_tile_isa.md): instruction q of wave w covers couts (q*4 + w)*16 + lane/4; the swizzle term ((co>>2)&3) = (lane>>4)&3 does not
   // depend on q, so ONE 32-bit lane offset serves every q and K-step, the rest of the address is scalar
   const unsigned woff = (unsigned)(((wave * 16 + (lane >> 2)) * p.Kpad + ((chp ^ ((lane >> 4) & 3)) * 8)) * 2);
   const f16 *wbase = p.w + (size_t)c0 * p.Kpad;
@@ -91,7 +88,7 @@ __device__ __forceinline__ void igemm2_tile(const ConvArgs &p, const f16 *__rest
   if (lin) {
 #pragma unroll
     for (int q = 0; q < NT; ++q) {
-      const int m = min(m0 + (q * 4 + wave) * 16 + (lane >> 2), p.M - 1);
+      const int m = min(m0 + ct_dma_row(ct_dma_slot(q, 4, wave), lane), p.M - 1);
       xlin[q] = (unsigned)(m * p.Cin + xch[q] * 8) * 2u;
     }
   }
@@ -100,7 +97,7 @@ __device__ __forceinline__ void igemm2_tile(const ConvArgs &p, const f16 *__rest
     if (d < NT) {
       const int q = d;
       if (lin) {
-        glds16(p.in + kt * C2_BK, xlin[q], xs + (q * 4 + wave) * 512);
+        glds16(p.in + kt * C2_BK, xlin[q], xs + ct_dma_lds(ct_dma_slot(q, 4, wave)));
         return;
       }
       const int k = kt * C2_BK + xch[q] * 8;
@@ -116,10 +113,10 @@ __device__ __forceinline__ void igemm2_tile(const ConvArgs &p, const f16 *__rest
       const int iy = iy0[q] + ky, ix = ix0[q] + kx;
       const bool ok = tap < ntaps && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
       const f16 *src = ok ? p.in + xbase[q] + ((long long)iy * p.W + ix) * p.Cin + ci : zero_page;
-      glds16(src, xs + (q * 4 + wave) * 512);
+      glds16(src, xs + ct_dma_lds(ct_dma_slot(q, 4, wave)));
     } else {
       const int q = d - NT;
-      glds16(wbase + (size_t)(q * 64) * p.Kpad + (size_t)kt * C2_BK, woff, ws + (q * 4 + wave) * 512);
+      glds16(wbase + (size_t)(q * 64) * p.Kpad + (size_t)kt * C2_BK, woff, ws + ct_dma_lds(ct_dma_slot(q, 4, wave)));
     }
   };
   auto stage = [&](int kt, int buf) __attribute__((always_inline)) {
@@ -127,21 +124,16 @@ __device__ __forceinline__ void igemm2_tile(const ConvArgs &p, const f16 *__rest
     for (int d = 0; d < NT + WQ; ++d) stage_one(kt, buf, d);
   };
 
-  // ---- fragment bases (swizzled rows: chunk ^ ((row>>2)&3); rows +32 keep the same swizzle) ----
+  // ---- fragment bases (conv_tile.h; rows +32 keep the same swizzle) ----
   int wa[2], xa[NT][2];
-  {
-    const int co = wm * WM + lr;
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks) wa[ks] = co * 32 + (((ks * 2 + lh) ^ ((co >> 2) & 3)) * 8);
+  for (int ks = 0; ks < 2; ++ks) {
+    wa[ks] = ct_frag(wm * WM + lr, ks, lh);
 #pragma unroll
-    for (int j = 0; j < NT; ++j) {
-      const int px = wn * (32 * NT) + j * 32 + lr;
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) xa[j][ks] = px * 32 + (((ks * 2 + lh) ^ ((px >> 2) & 3)) * 8);
-    }
+    for (int j = 0; j < NT; ++j) xa[j][ks] = ct_frag(wn * (32 * NT) + acc_row_token(j, lr), ks, lh);
   }
 
-  // accumulators start at the bias (fp32): a lane owns channels wm*WM + i*32 + rg*8 + lh*4 + (0..3) of its pixels
+  // accumulators start at the bias (fp32): a lane owns channels wm*WM + acc_row_chan(i, rg, lh) + (0..3) of its pixels (written out: profiles/conv_tile_isa.md)
   floatx16 acc[MT][NT];
 #pragma unroll
   for (int i = 0; i < MT; ++i)
@@ -162,17 +154,17 @@ __device__ __forceinline__ void igemm2_tile(const ConvArgs &p, const f16 *__rest
   const int nk = SPLIT ? p.Kpad / C2_BK / p.ksplit : p.Kpad / C2_BK, kb = SPLIT ? ks * nk : 0;
   // 3-deep LDS-DMA ring: K-steps kt+1 and kt+2 stay in flight across the barrier (counted vmcnt + raw s_barrier;
   // a __syncthreads() would drain them).  Every wave issues exactly DMAW instructions per stage.
-  constexpr int DMAW = NT + WQ;
+  constexpr int DMAW = c2_dmaw(NT, BM);
   ISTAMP(const unsigned long long t_loop = __builtin_amdgcn_s_memtime();)
   stage(kb, 0);
   if (nk > 1) stage(kb + 1, 1);
   for (int kt = 0; kt < nk; ++kt) {
-    const int cur = kt % 3;
-    if (kt + 1 < nk) wait_vm_lgkm<DMAW>();
+    const int cur = c2_slot(kt);
+    if (c2_wait_allowed(kt, nk, DMAW) != 0) wait_vm_lgkm<DMAW>();
     else wait_vm_lgkm<0>();
     __builtin_amdgcn_s_barrier();          // stage kt landed for every wave; slot (kt+2)%3 was last read in step kt-1: free
     __builtin_amdgcn_sched_barrier(0);
-    if (kt + 2 < nk) stage(kb + kt + 2, (kt + 2) % 3);
+    if (kt + 2 < nk) stage(kb + kt + 2, c2_slot(kt + 2));
     const f16 *xs = smem + cur * (XH + WH), *ws = xs + XH;
     // two k-steps per stage, software-pipelined like the halo kernel: pixel-tile-major MFMA order, the pixel fragment of
     // step 1 is requested as soon as step 0's MFMAs on that register have been issued (counted lgkmcnt waits).  (Issuing
@@ -180,11 +172,11 @@ __device__ __forceinline__ void igemm2_tile(const ConvArgs &p, const f16 *__rest
     // are bound by the L2 -> LDS fill, and the fill wants its requests as early as possible.)
     half8 af[2][MT], bf[NT];
 #pragma unroll
-    for (int i = 0; i < MT; ++i) af[0][i] = *reinterpret_cast<const half8 *>(&ws[wa[0] + i * 32 * 32]);
+    for (int i = 0; i < MT; ++i) af[0][i] = *reinterpret_cast<const half8 *>(&ws[wa[0] + i * CT_TILE32]);
 #pragma unroll
     for (int j = 0; j < NT; ++j) bf[j] = *reinterpret_cast<const half8 *>(&xs[xa[j][0]]);
 #pragma unroll
-    for (int i = 0; i < MT; ++i) af[1][i] = *reinterpret_cast<const half8 *>(&ws[wa[1] + i * 32 * 32]);
+    for (int i = 0; i < MT; ++i) af[1][i] = *reinterpret_cast<const half8 *>(&ws[wa[1] + i * CT_TILE32]);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
@@ -205,18 +197,8 @@ __device__ __forceinline__ void igemm2_tile(const ConvArgs &p, const f16 *__rest
   // it), no per-row output select when the whole tile lies on one side of split_m.  (Reading the residual as 8-byte
   // gathers in the accumulator layout behind the first DMA stages was measured: epilogue -6.8k cycles, K loop +16k.) ----
   ISTAMP(const unsigned long long t_epi = __builtin_amdgcn_s_memtime();)
-  if constexpr (SPLIT) {      // fp32 sums of this share -> p.splitk[ks][m][Cout], 16-byte stores in the accumulator layout
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-      const int m = m0 + wn * (32 * NT) + j * 32 + lr;
-      if (m >= p.M) continue;
-      float *o = p.splitk + ((size_t)ks * p.M + m) * p.Cout + c0 + wm * WM + lh * 4;
-#pragma unroll
-      for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int rg = 0; rg < 4; ++rg)
-          *reinterpret_cast<float4 *>(o + i * 32 + rg * 8) = make_float4(acc[i][j][rg * 4 + 0], acc[i][j][rg * 4 + 1], acc[i][j][rg * 4 + 2], acc[i][j][rg * 4 + 3]);
-    }
+  if constexpr (SPLIT) {      // fp32 sums of this share for splitk_finish_kernel
+    ct_splitk_store(p, acc, ks, m0 + wn * (32 * NT), c0, wm * WM, lr, lh);
     return;
   }
   if (p.out_mode == 0) {
@@ -225,7 +207,7 @@ __device__ __forceinline__ void igemm2_tile(const ConvArgs &p, const f16 *__rest
     constexpr int NCH = TN * CPR / 256;
     constexpr int RB = NCH < 8 ? NCH : 8;
     u32x4 rv[NCH];
-    if constexpr (RES) {                  // residual tile: ONE batch of coalesced 16-byte loads before the barrier, staged through LDS
+    if constexpr (RES) {                  // residual tile: ONE batch of coalesced 16-byte loads before the barrier, staged through LDS (row pieces: ct_piece_px / ct_piece_c16)
 #pragma unroll
       for (int u = 0; u < NCH; ++u) {
         const int idx = tid + 256 * u, px = idx / CPR, c16 = idx % CPR;
@@ -238,17 +220,17 @@ __device__ __forceinline__ void igemm2_tile(const ConvArgs &p, const f16 *__rest
 #pragma unroll
       for (int u = 0; u < NCH; ++u) {
         const int idx = tid + 256 * u, px = idx / CPR, c16 = idx % CPR;
-        *reinterpret_cast<u32x4 *>(&stage[px * SLD + c16 * 8]) = rv[u];
+        *reinterpret_cast<u32x4 *>(&stage[ct_stage_off(BM, px, c16 * 8)]) = rv[u];
       }
       __syncthreads();
 #pragma unroll
       for (int j = 0; j < NT; ++j) {      // each lane reads back exactly the 8-byte slots it overwrites below: no barrier in between
-        const int pxl = wn * (32 * NT) + j * 32 + lr;
+        const int pxl = wn * (32 * NT) + acc_row_token(j, lr);
 #pragma unroll
         for (int i = 0; i < MT; ++i)
 #pragma unroll
           for (int rg = 0; rg < 4; ++rg) {
-            const half4 rq = *reinterpret_cast<const half4 *>(&stage[pxl * SLD + wm * WM + i * 32 + rg * 8 + lh * 4]);
+            const half4 rq = *reinterpret_cast<const half4 *>(&stage[ct_stage_off(BM, pxl, wm * WM + acc_row_chan(i, rg, lh))]);
 #pragma unroll
             for (int e = 0; e < 4; ++e) acc[i][j][rg * 4 + e] += (float)rq[e];
           }
@@ -258,27 +240,27 @@ __device__ __forceinline__ void igemm2_tile(const ConvArgs &p, const f16 *__rest
       const float lo = p.relu ? 0.f : -__builtin_inff();
 #pragma unroll
       for (int j = 0; j < NT; ++j) {
-        const int pxl = wn * (32 * NT) + j * 32 + lr;
+        const int pxl = wn * (32 * NT) + acc_row_token(j, lr);
         const int prow = min(m0 + pxl, p.M - 1) % p.post_period;
 #pragma unroll
         for (int i = 0; i < MT; ++i)
 #pragma unroll
           for (int rg = 0; rg < 4; ++rg) {
-            const int col = wm * WM + i * 32 + rg * 8 + lh * 4;
+            const int col = wm * WM + acc_row_chan(i, rg, lh);
             const float4 pv = *reinterpret_cast<const float4 *>(p.post_add + (size_t)prow * p.Cout + c0 + col);
             half4 hv;
             hv[0] = (f16)(fmaxf(acc[i][j][rg * 4 + 0], lo) + pv.x);
             hv[1] = (f16)(fmaxf(acc[i][j][rg * 4 + 1], lo) + pv.y);
             hv[2] = (f16)(fmaxf(acc[i][j][rg * 4 + 2], lo) + pv.z);
             hv[3] = (f16)(fmaxf(acc[i][j][rg * 4 + 3], lo) + pv.w);
-            *reinterpret_cast<half4 *>(&stage[pxl * SLD + col]) = hv;
+            *reinterpret_cast<half4 *>(&stage[ct_stage_off(BM, pxl, col)]) = hv;
           }
       }
     } else {
       auto convert = [&](auto relu_c) __attribute__((always_inline)) {
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
-          const int pxl = wn * (32 * NT) + j * 32 + lr;
+          const int pxl = wn * (32 * NT) + acc_row_token(j, lr);
 #pragma unroll
           for (int i = 0; i < MT; ++i)
 #pragma unroll
@@ -287,7 +269,7 @@ __device__ __forceinline__ void igemm2_tile(const ConvArgs &p, const f16 *__rest
 #pragma unroll
               for (int e = 0; e < 4; ++e) hv[e] = (f16)acc[i][j][rg * 4 + e];
               if constexpr (decltype(relu_c)::value) hv = __builtin_elementwise_max(hv, half4{(f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f});
-              *reinterpret_cast<half4 *>(&stage[pxl * SLD + wm * WM + i * 32 + rg * 8 + lh * 4]) = hv;
+              *reinterpret_cast<half4 *>(&stage[ct_stage_off(BM, pxl, wm * WM + acc_row_chan(i, rg, lh))]) = hv;
             }
         }
       };
@@ -297,14 +279,14 @@ __device__ __forceinline__ void igemm2_tile(const ConvArgs &p, const f16 *__rest
     __syncthreads();
     const bool side_hi = m0 >= p.split_m;
     if (side_hi || m0 + TN <= p.split_m) {          // whole tile on one side: one scalar base, rows at a fixed stride
-      f16 *obase = (f16 *)p.out + (long long)(side_hi ? m0 - p.split_m : m0) * p.out_ld + (side_hi ? p.coff_hi : 0) + c0;
+      f16 *obase = ct_out_ptr(p, m0) + c0;
 #pragma unroll
       for (int i0 = 0; i0 < NCH; i0 += RB) {
         uint4 ov[RB];
 #pragma unroll
         for (int u = 0; u < RB; ++u) {
           const int idx = tid + 256 * (i0 + u), px = idx / CPR, c16 = idx % CPR;
-          ov[u] = *reinterpret_cast<const uint4 *>(&stage[px * SLD + c16 * 8]);
+          ov[u] = *reinterpret_cast<const uint4 *>(&stage[ct_stage_off(BM, px, c16 * 8)]);
         }
 #pragma unroll
         for (int u = 0; u < RB; ++u) {
@@ -319,16 +301,15 @@ __device__ __forceinline__ void igemm2_tile(const ConvArgs &p, const f16 *__rest
 #pragma unroll
         for (int u = 0; u < RB; ++u) {
           const int idx = tid + 256 * (i0 + u), px = idx / CPR, c16 = idx % CPR;
-          ov[u] = *reinterpret_cast<const uint4 *>(&stage[px * SLD + c16 * 8]);
+          ov[u] = *reinterpret_cast<const uint4 *>(&stage[ct_stage_off(BM, px, c16 * 8)]);
         }
 #pragma unroll
         for (int u = 0; u < RB; ++u) {
           const int idx = tid + 256 * (i0 + u), px = idx / CPR, c16 = idx % CPR;
           const int m = m0 + px;
           if (m < p.M) {
-            const bool hi = m >= p.split_m;
-            const long long orow = hi ? (long long)(m - p.split_m) : (long long)m;
-            const int coff = hi ? p.coff_hi : 0;
+            const long long orow = ct_out_row(m, p.split_m);
+            const int coff = ct_out_col(m, p.split_m, p.coff_hi);
             *reinterpret_cast<uint4 *>((f16 *)p.out + orow * p.out_ld + coff + c0 + c16 * 8) = ov[u];
           }
         }
@@ -353,9 +334,8 @@ __device__ __forceinline__ void igemm2_tile(const ConvArgs &p, const f16 *__rest
   for (int j = 0; j < NT; ++j) {
     const int m = m0 + wn * (32 * NT) + j * 32 + lr;
     if (m >= p.M) continue;
-    const bool hi = m >= p.split_m;
-    const long long orow = hi ? (long long)(m - p.split_m) : (long long)m;
-    const int coff = hi ? p.coff_hi : 0;
+    const long long orow = ct_out_row(m, p.split_m);
+    const int coff = ct_out_col(m, p.split_m, p.coff_hi);
     int prow = 0;
     if (p.post_add) prow = m % p.post_period;
     int tb = 0, tt = 0;
@@ -414,14 +394,12 @@ __global__ __launch_bounds__(256, 2) void conv_igemm2_kernel(ConvArgs p, const f
   extern __shared__ __attribute__((aligned(16))) f16 smem[];
   const int n_ct = p.Cout / BM;
   if ((int)blockIdx.x < n_main) {
-    const int L = xcd_remap(blockIdx.x, n_main);
-    igemm2_tile<BM, KW, CIN8, 4, RES>(p, zero_page, (L / n_ct) * C2_BN, (L % n_ct) * BM, smem);
+    const CtTile T = ct_grid_main(xcd_remap(blockIdx.x, n_main), n_ct, C2_BN, BM);
+    igemm2_tile<BM, KW, CIN8, 4, RES>(p, zero_page, T.m0, T.c0, smem);
   } else {
-    const int t = xcd_remap(blockIdx.x - n_main, gridDim.x - n_main);
-    const int L = n_main + (t >> 2);
-    const int m0 = (L / n_ct) * C2_BN + (t & 3) * (C2_BN / 4);
-    if (m0 >= p.M) return;
-    igemm2_tile<BM, KW, CIN8, 1, RES>(p, zero_page, m0, (L % n_ct) * BM, smem);
+    const CtTile T = c2_grid_tail(xcd_remap(blockIdx.x - n_main, gridDim.x - n_main), n_main, n_ct, BM);
+    if (T.m0 >= p.M) return;
+    igemm2_tile<BM, KW, CIN8, 1, RES>(p, zero_page, T.m0, T.c0, smem);
   }
 }
 
@@ -433,17 +411,13 @@ template <int BM, int KW>
 __global__ __launch_bounds__(256, 2) void conv_igemm2_splitk_kernel(ConvArgs p, const f16 *__restrict__ zero_page) {
   extern __shared__ __attribute__((aligned(16))) f16 smem[];
   const int n_ct = p.Cout / BM;
-  const int ks = blockIdx.x % p.ksplit, t = blockIdx.x / p.ksplit;
-  const int m0 = (t / n_ct) * 64;
-  if (m0 >= p.M) return;
-  igemm2_tile<BM, KW, false, 1, false, true>(p, zero_page, m0, (t % n_ct) * BM, smem, ks);
+  const CtTile T = ct_grid_split(blockIdx.x, p.ksplit, n_ct, 64, BM);
+  if (T.m0 >= p.M) return;
+  igemm2_tile<BM, KW, false, 1, false, true>(p, zero_page, T.m0, T.c0, smem, T.ks);
 }
 
 template <int BM>
-constexpr int igemm2_lds_bytes() {
-  constexpr int main_b = 3 * (C2_BN * C2_BK + BM * C2_BK) * 2, epi_b = C2_BN * (BM + 8) * 2;
-  return main_b > epi_b ? main_b : epi_b;
-}
+constexpr int igemm2_lds_bytes() { return c2_lds_bytes(BM); }
 
 template <int BM, int KW, bool CIN8>
 static void igemm2_lds_both(std::vector<KernelLds> &v) {

@@ -11,12 +11,10 @@
 // Epilogue: accumulators start at the bias; residual (staged through LDS) + ReLU (+ positional embedding) in fp32, one
 // rounding to fp16, LDS transpose, 16-byte row-contiguous NHWC stores.
 #include "common.h"
-#include "device_util.h"
+#include "conv_tile.h"
 #include <cstdlib>
 
-
-// (HL_BM = 128 couts per tile, HL_CK = 32 input channels per chunk: conv_plan.h)
-#define HL_SLD 136  // halfs per staged output row (128 + 8 pad) -> 272 B
+// (HL_BM = 128 couts per tile, HL_CK = 32 input channels per chunk: conv_plan.h; HL_SLD, HaloCfgD and every index rule: conv_tile.h)
 
 #ifdef HALO_STAMP
 // diagnostic build only (make -B EXTRA=-DHALO_STAMP): per-wave cycle sums of [wait + barrier] and [group body], see scripts/halo_stamps.py
@@ -44,32 +42,15 @@ struct IC {
 // ------------------------------------------------------------------------------------------------------------------------
 // 8-wave tile (512 px x 128 co, one workgroup per CU) with the halo band staged by LDS-DMA as well, double
 // buffered:
-//   * halo pixels are 64 bytes, UNPADDED (so a DMA instruction's 64 lanes x 16 B land linearly: 16 pixels x 4 channel groups);
-//     bank conflicts are avoided by an XOR swizzle instead: pixel P keeps channel group c at position c ^ ((P >> 2) & 3),
-//     applied on the SOURCE address of the DMA (the destination of an LDS-DMA is always lane-linear).  A ds_read_b128 lane
-//     group ({0-3,12-15,20-27}, ...) then reads 16 pixels whose four members of each residue class mod 4 carry four
-//     different swizzle values, for any tile alignment and tap shift: conflict free;
+//   * halo pixels are 64-byte rows of the swizzled row tile of conv_tile.h, fetched by the linear DMA map (instruction h of wave w is
+//     slot h*8 + w).  The band's fragment reads are conflict free at every tile alignment and tap shift, in the ds_read_b128 lane
+//     groups ({0-3,12-15,20-27}, ...) as in contiguous quarters; border lanes, which take the zero chunk, can make a read two-way (conv_tile.h);
 //   * no staging registers, no ds_write of the band, no barrier pair at the top of a chunk: the band of chunk cc+1 streams
 //     into the other buffer while chunk cc is multiplied, one DMA instruction per pixel-tile visit;
 //   * v_mfma_f32_32x32x16_f16, a wave holds 64 co x 128 px (2 x 4 accumulator tiles); a kernel row is 24 "tile visits" of 2
 //     MFMAs, pixel fragments rotate through 4 registers, weight fragments of the next step go to a spare set.
 // (A 16x16x32 MFMA form of this tile was measured too: ~7 % more cycles at a ~8 % higher clock, the same time.)
 // ------------------------------------------------------------------------------------------------------------------------
-template <int W, int TM>
-struct HaloCfgD {
-  static constexpr int MAXSLOT = (W - 1 + TM - 1) / W + 1 + 2;
-  static constexpr int NB = MAXSLOT * W + 2;                       // band pixels in use (pixel p at index p+1)
-  static constexpr int HQ = ((NB + 15) / 16 + 7) / 8;              // halo DMA instructions per wave per chunk (8 waves)
-  static constexpr int BPX = HQ * 8 * 16;                          // band pixels allocated
-  static constexpr int HBUF_HALFS = BPX * 32;
-  static constexpr int ZERO_OFF = 2 * HBUF_HALFS;                  // half offset of the zero chunk
-  static constexpr int WBUF_OFF = ZERO_OFF + 8;
-  static constexpr int WBUF_HALFS = 3 * HL_BM * HL_CK;
-  static constexpr int LDS_HALFS_MAIN = WBUF_OFF + 2 * WBUF_HALFS;
-  static constexpr int LDS_HALFS_EPI = TM * HL_SLD;
-  static constexpr int LDS_BYTES = 2 * (LDS_HALFS_MAIN > LDS_HALFS_EPI ? LDS_HALFS_MAIN : LDS_HALFS_EPI);
-};
-
 // Epilogue of a tile: residual (staged through LDS) + ReLU (+ positional embedding) in fp32, one rounding to fp16,
 // LDS transpose, 16-byte row-contiguous NHWC stores.
 template <int NT, bool RES, bool POST>
@@ -83,7 +64,7 @@ __device__ __forceinline__ void halo_epilogue(const ConvArgs &p, const int m0, c
   u32x4 rv[NRES];
   if constexpr (RES) {
 #pragma unroll
-    for (int u = 0; u < NRES; ++u) {
+    for (int u = 0; u < NRES; ++u) {      // row pieces ct_piece_px / ct_piece_c16 (written out: profiles/conv_tile_isa.md)
       const int idx = tid + NTH * u, px = idx >> 4, c16 = idx & 15;
       const int m = min(m0 + px, p.M - 1);
       rv[u] = *reinterpret_cast<const u32x4 *>(p.res + (size_t)m * p.Cout + c0 + c16 * 8);
@@ -101,7 +82,7 @@ __device__ __forceinline__ void halo_epilogue(const ConvArgs &p, const int m0, c
   }
 #pragma unroll
   for (int j = 0; j < NT; ++j) {
-    const int pxl = wn * PXW + j * 32 + lr;
+    const int pxl = wn * PXW + acc_row_token(j, lr);
     float4 pvs[2][4];
     if constexpr (POST) {
       const int prow = min(m0 + pxl, p.M - 1) % p.post_period;
@@ -109,14 +90,14 @@ __device__ __forceinline__ void halo_epilogue(const ConvArgs &p, const int m0, c
       for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int rg = 0; rg < 4; ++rg)
-          pvs[i][rg] = *reinterpret_cast<const float4 *>(p.post_add + (size_t)prow * p.Cout + c0 + wm * 64 + i * 32 + rg * 8 + lh * 4);
+          pvs[i][rg] = *reinterpret_cast<const float4 *>(p.post_add + (size_t)prow * p.Cout + c0 + wm * 64 + i * 32 + rg * 8 + lh * 4);      // acc_row_chan (written out: profiles/conv_tile_isa.md)
     }
     half4 rq[2][4];
     if constexpr (RES) {
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int rg = 0; rg < 4; ++rg) rq[i][rg] = *reinterpret_cast<const half4 *>(&stage[pxl * HL_SLD + wm * 64 + i * 32 + rg * 8 + lh * 4]);
+        for (int rg = 0; rg < 4; ++rg) rq[i][rg] = *reinterpret_cast<const half4 *>(&stage[ct_stage_off(HL_BM, pxl, wm * 64 + acc_row_chan(i, rg, lh))]);
     }
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -139,7 +120,7 @@ __device__ __forceinline__ void halo_epilogue(const ConvArgs &p, const int m0, c
         half4 hv;
 #pragma unroll
         for (int e = 0; e < 4; ++e) hv[e] = (f16)v[e];
-        *reinterpret_cast<half4 *>(&stage[pxl * HL_SLD + wm * 64 + i * 32 + rg * 8 + lh * 4]) = hv;
+        *reinterpret_cast<half4 *>(&stage[ct_stage_off(HL_BM, pxl, wm * 64 + acc_row_chan(i, rg, lh))]) = hv;
       }
     }
   }
@@ -160,9 +141,8 @@ __device__ __forceinline__ void halo_epilogue(const ConvArgs &p, const int m0, c
       const int idx = tid + NTH * (i0 + u), px = idx >> 4, c16 = idx & 15;
       const int m = m0 + px;
       if (m < p.M) {
-        const bool hi = m >= p.split_m;
-        const long long orow = hi ? (long long)(m - p.split_m) : (long long)m;
-        const int coff = hi ? p.coff_hi : 0;
+        const long long orow = ct_out_row(m, p.split_m);
+        const int coff = ct_out_col(m, p.split_m, p.coff_hi);
         *reinterpret_cast<u32x4 *>((f16 *)p.out + orow * p.out_ld + coff + c0 + c16 * 8) = ov[u];
       }
     }
@@ -177,7 +157,7 @@ __device__ __forceinline__ void halo_tile_dma(const ConvArgs &p, const int m0, c
   // (512 threads)
   constexpr int PXW = 32 * NT;          // pixels per wave
   constexpr int HQ = C::HQ;
-  constexpr int WQ = 24 / (2 * NPW);    // weight DMA instructions per wave per group
+  constexpr int WQ = HL_WSLOTS / (2 * NPW);    // weight DMA instructions per wave per group
   STAMP(const unsigned long long t_entry = __builtin_amdgcn_s_memtime(); const unsigned long long r_entry = __builtin_amdgcn_s_memrealtime();)
   f16 *wbuf = lds + C::WBUF_OFF;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -186,7 +166,7 @@ __device__ __forceinline__ void halo_tile_dma(const ConvArgs &p, const int m0, c
   // static priority for the second-dispatched half of the workgroup (waves 4-7 are the arbitration loser of each SIMD pair at
   // equal priority): measured A/B in one session, 39.55 / 39.33 -> 38.99 / 38.92 ms per step, 1139 / 1145 -> 1153 / 1157 TF/s
   if (wave >= 4) __builtin_amdgcn_s_setprio(1);
-  const int GR0 = m0 / W - 1;                       // global input row (n*H + iy) held by band row 0
+  const int GR0 = hl_gr0(m0, W);
   const int total_rows = p.Nimg * H;
   // input-channel chunks [cbeg, nchunk) of this workgroup: all of them, or (SPLIT) share ks of p.ksplit equal shares
   const int call = p.Cin / HL_CK;
@@ -194,7 +174,7 @@ __device__ __forceinline__ void halo_tile_dma(const ConvArgs &p, const int m0, c
   const int nchunk = SPLIT ? cbeg + call / p.ksplit : call;
 
   // ---- B fragments: band index of the top-left tap of this lane's pixel in tile 0 (tile j, taps: see load_b) ----
-  const int pb = m0 + wn * PXW + lr - GR0 * W - W;
+  const int pb = hl_pb(m0 + wn * PXW + lr, GR0, W);
   unsigned vmp[(NT + 2) / 3];          // 9 validity bits (ky*3+kx) per 32-pixel tile, three tiles per register
 #pragma unroll
   for (int t = 0; t < (NT + 2) / 3; ++t) vmp[t] = 0;
@@ -206,19 +186,14 @@ __device__ __forceinline__ void halo_tile_dma(const ConvArgs &p, const int m0, c
     for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
       for (int kx = 0; kx < 3; ++kx) {
-        const int iy = oy + ky - 1, ix = ox + kx - 1;
-        if (iy >= 0 && iy < H && ix >= 0 && ix < W) vmp[j / 3] |= 1u << ((j % 3) * 9 + ky * 3 + kx);
+        if (hl_tap_valid(oy, ox, W, ky, kx)) vmp[j / 3] |= 1u << hl_vbit(j, ky, kx);
       }
   }
-  // ---- A fragments: row co = wm*64 + i*32 + lr, channel group ks*2 + lh at position ^ ((co>>2)&3) (same for co and co+32)
-  int wa[2];
-  {
-    const int co = wm * 64 + lr;
-    wa[0] = co * 32 + ((lh ^ ((co >> 2) & 3)) * 8);
-    wa[1] = co * 32 + (((2 + lh) ^ ((co >> 2) & 3)) * 8);
-  }
+  // ---- A fragments: row co = wm*64 + i*32 + lr, channel group ks*2 + lh
+  const int wa[2] = {ct_frag(wm * 64 + lr, 0, lh), ct_frag(wm * 64 + lr, 1, lh)};
 
-  // ---- halo band by LDS-DMA: instruction h of wave w lands band pixels (h*8 + w)*16 .. +15, lane i = (pixel i/4, position i%4)
+  // ---- halo band by LDS-DMA: instruction h of wave w lands band pixels (h*8 + w)*16 .. +15, lane i = (pixel i/4, position i%4): slot
+  // ct_dma_slot(h, 8, w), row ct_dma_row, chunk ct_dma_chunk, source hl_band_src (written out: profiles/conv_tile_isa.md)
   const int hpix_max = total_rows * W - 1;
   auto halo_dma = [&](int cc, int hb, auto hc) __attribute__((always_inline)) {
     constexpr int h = decltype(hc)::value;
@@ -226,11 +201,11 @@ __device__ __forceinline__ void halo_tile_dma(const ConvArgs &p, const int m0, c
     asm volatile("" : "+v"(l4));                    // recompute per use: six hoisted offsets would cost six registers
     const int P = (h * 8 + wave) * 16 + l4;
     const int c = (lane & 3) ^ ((P >> 2) & 3);
-    const int gp = min(max(GR0 * W + P - 1, 0), hpix_max);      // clamped: what lands for rows outside the tensor is never read
+    const int gp = min(max(GR0 * W + P - 1, 0), hpix_max);      // clamped: what lands from a clamped source is never read (conv_tile.h)
     const unsigned off = (unsigned)(gp * p.Cin + cc * HL_CK + c * 8) * 2u;
     glds16(p.in, off, lds + hb * C::HBUF_HALFS + (h * 8 + wave) * 512);
   };
-  // ---- weights: row (g%8)*16 + lane/4 -> (row>>2)&3 = (lane>>4)&3
+  // ---- weights: row (g%8)*16 + lane/4 -> (row>>2)&3 = (lane>>4)&3: ct_w_off, hl_w_src, slot g0 + wave (written out: profiles/conv_tile_isa.md)
   const unsigned woff = (unsigned)(((wave * 16 + (lane >> 2)) * p.Kpad + (((lane & 3) ^ ((lane >> 4) & 3)) * 8)) * 2);
   auto wstage = [&](int cc, int ky, int buf, auto q0c, auto q1c) __attribute__((always_inline)) {
     constexpr int Q0 = decltype(q0c)::value, Q1 = decltype(q1c)::value;
@@ -242,7 +217,7 @@ __device__ __forceinline__ void halo_tile_dma(const ConvArgs &p, const int m0, c
     }
   };
 
-  // accumulators start at the bias (fp32): a lane owns channels wm*64 + i*32 + rg*8 + lh*4 + (0..3) of its pixels
+  // accumulators start at the bias (fp32): a lane owns channels wm*64 + acc_row_chan(i, rg, lh) + (0..3) of its pixels (written out: profiles/conv_tile_isa.md)
   floatx16 acc[2][NT];
 #pragma unroll
   for (int i = 0; i < 2; ++i)
@@ -278,6 +253,8 @@ __device__ __forceinline__ void halo_tile_dma(const ConvArgs &p, const int m0, c
       STAMP(unsigned long long ta = __builtin_amdgcn_s_memtime();)
       // weights(g) - and at ky=0 the band of this chunk - must have landed.  The band DMAs of the NEXT chunk, issued in
       // group ky=0, are younger than the weights needed at ky=1: a counted vmcnt leaves them in flight there.
+      static_assert(halo_wait_allowed(1, true, HQ) == HQ && halo_wait_allowed(1, false, HQ) == 0 && halo_wait_allowed(0, true, HQ) == 0 && halo_wait_allowed(2, true, HQ) == 0,
+                    "the condition below is halo_wait_allowed(ky, cc + 1 < nchunk) != 0 (written out: as a call hipcc took more registers)");
       if (ky == 1 && cc + 1 < nchunk) {
         wait_vm_lgkm<HQ>();
       } else {
@@ -307,20 +284,20 @@ __device__ __forceinline__ void halo_tile_dma(const ConvArgs &p, const int m0, c
       int tapb[3][2];                      // half offset of (tap pixel, channel group ks*2 + lh) of tile 0
 #pragma unroll
       for (int kx = 0; kx < 3; ++kx) {
-        const int Pt = pb + ky * W + kx, sw = (Pt >> 2) & 3;
-        tapb[kx][0] = Pt * 32 + ((lh ^ sw) * 8);
-        tapb[kx][1] = Pt * 32 + (((2 + lh) ^ sw) * 8);
+        const int Pt = hl_tap(pb, W, ky, kx);
+        tapb[kx][0] = ct_frag(Pt, 0, lh);
+        tapb[kx][1] = ct_frag(Pt, 1, lh);
       }
       auto load_a = [&](int st, int set) __attribute__((always_inline)) {
         const int kx = st >> 1, ks = st & 1;
 #pragma unroll
-        for (int i = 0; i < 2; ++i) af[set][i] = *reinterpret_cast<const half8 *>(&wb[wa[ks] + i * (32 * 32) + kx * (HL_BM * HL_CK)]);
+        for (int i = 0; i < 2; ++i) af[set][i] = *reinterpret_cast<const half8 *>(&wb[wa[ks] + i * CT_TILE32 + hl_w_tap(kx)]);
       };
       auto load_b = [&](auto tc) __attribute__((always_inline)) {
         constexpr int t = decltype(tc)::value, st = t / NT, j = t % NT, kx = st >> 1, ks = st & 1;
-        constexpr int imm = j * 32 * 32;
-        const bool ok = (vm[j / 3] >> ((j % 3) * 9 + ky * 3 + kx)) & 1u;
-        const int base = ok ? tapb[kx][ks] : (C::ZERO_OFF - (cc & 1) * C::HBUF_HALFS - imm);
+        constexpr int imm = j * CT_TILE32;
+        const bool ok = (vm[j / 3] >> hl_vbit(j, ky, kx)) & 1u;
+        const int base = ok ? tapb[kx][ks] : hl_zero_base<C>(cc & 1, imm);
         bf[t % BD] = *reinterpret_cast<const half8 *>(&halo[base + imm]);
       };
       load_a(0, 0);
@@ -342,9 +319,9 @@ __device__ __forceinline__ void halo_tile_dma(const ConvArgs &p, const int m0, c
         // weight DMAs of the next group in the first visits, the next chunk's band DMAs right after them
         // (program order "weights, then band": the counted vmcnt at ky=1 relies on it)
         static_assert(WQ + HQ <= NV, "DMA issue slots");
-        if constexpr (t < WQ) {
+        if constexpr (hl_visit_is_w(t, WQ)) {
           if (more_w) wstage(ncc, nky, buf ^ 1, IC<t>{}, IC<t + 1>{});
-        } else if constexpr (t - WQ < HQ) {
+        } else if constexpr (hl_visit_is_band(t, WQ, HQ)) {
           if (more_h) halo_dma(cc + 1, (cc + 1) & 1, IC<t - WQ>{});
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -359,19 +336,8 @@ __device__ __forceinline__ void halo_tile_dma(const ConvArgs &p, const int m0, c
   STAMP(const unsigned long long t_loop_end = __builtin_amdgcn_s_memtime();)
 
   if constexpr (SPLIT) {
-    // fp32 partial sums of this share -> p.splitk[ks][m][Cout] (16-byte stores in the accumulator layout); splitk_finish adds
-    // the shares in a fixed order and applies residual / ReLU / positional embedding
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-      const int m = m0 + wn * PXW + j * 32 + lr;
-      if (m >= p.M) continue;
-      float *o = p.splitk + ((size_t)ks * p.M + m) * p.Cout + c0 + wm * 64 + lh * 4;
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int rg = 0; rg < 4; ++rg)
-          *reinterpret_cast<float4 *>(o + i * 32 + rg * 8) = make_float4(acc[i][j][rg * 4 + 0], acc[i][j][rg * 4 + 1], acc[i][j][rg * 4 + 2], acc[i][j][rg * 4 + 3]);
-    }
+    // fp32 partial sums of this share; splitk_finish adds the shares in a fixed order and applies residual / ReLU / positional embedding
+    ct_splitk_store(p, acc, ks, m0 + wn * PXW, c0, wm * 64, lr, lh);
     return;
   }
   halo_epilogue<NT, RES, POST>(p, m0, c0, lds, acc);
@@ -391,11 +357,11 @@ __global__ __launch_bounds__(512, 1) void conv3x3_halo_dma_kernel(ConvArgs p, in
   const int n_ct = p.Cout / HL_BM;
   // tile0: the logical tile at which this launch starts (0: the launch is the whole layer, as launch_halo_dma always makes it)
   if ((int)blockIdx.x < n_main) {
-    const int L = tile0 + xcd_remap(blockIdx.x, n_main);
-    halo_tile_dma<W, 4, RES, POST>(p, (L / n_ct) * TMM, (L % n_ct) * HL_BM, lds);
+    const CtTile T = ct_grid_main(tile0 + xcd_remap(blockIdx.x, n_main), n_ct, TMM, HL_BM);
+    halo_tile_dma<W, 4, RES, POST>(p, T.m0, T.c0, lds);
   } else {
-    const int t = xcd_remap(blockIdx.x - n_main, gridDim.x - n_main);
-    const int m0 = ((tile0 + n_main) / n_ct) * TMM + (t / n_ct) * (nt_tail * 128), c0 = (t % n_ct) * HL_BM;
+    const CtTile T = hl_grid_tail(xcd_remap(blockIdx.x - n_main, gridDim.x - n_main), tile0 + n_main, n_ct, nt_tail);
+    const int m0 = T.m0, c0 = T.c0;
     if (m0 >= p.M) return;
     if (nt_tail == 1) halo_tile_dma<W, 1, RES, POST>(p, m0, c0, lds);
     else if (nt_tail == 2) halo_tile_dma<W, 2, RES, POST>(p, m0, c0, lds);
@@ -413,10 +379,9 @@ template <int W>
 __global__ __launch_bounds__(512, 1) void conv3x3_halo_splitk_kernel(ConvArgs p) {
   extern __shared__ __attribute__((aligned(16))) f16 lds[];
   const int n_ct = p.Cout / HL_BM;
-  const int ks = blockIdx.x % p.ksplit, t = blockIdx.x / p.ksplit;
-  const int m0 = (t / n_ct) * 128;
-  if (m0 >= p.M) return;
-  halo_tile_dma<W, 1, false, false, true>(p, m0, (t % n_ct) * HL_BM, lds, ks);
+  const CtTile T = ct_grid_split(blockIdx.x, p.ksplit, n_ct, 128, HL_BM);
+  if (T.m0 >= p.M) return;
+  halo_tile_dma<W, 1, false, false, true>(p, T.m0, T.c0, lds, T.ks);
 }
 
 // out = [+ pos.emb.] relu?( sum_ks partial[ks] [+ residual] ), one thread per pixel x 4 channels, shares added in order
@@ -424,26 +389,12 @@ __global__ __launch_bounds__(256) void splitk_finish_kernel(ConvArgs p) {
   const int q = blockIdx.x * 256 + threadIdx.x, c4 = p.Cout / 4;
   if (q >= p.M * c4) return;
   const int m = q / c4, c = (q - m * c4) * 4;
-  float4 v = *reinterpret_cast<const float4 *>(p.splitk + (size_t)m * p.Cout + c);
+  float4 v = *reinterpret_cast<const float4 *>(p.splitk + ct_splitk_index(0, m, c, p.M, p.Cout));
   for (int ks = 1; ks < p.ksplit; ++ks) {
-    const float4 w = *reinterpret_cast<const float4 *>(p.splitk + ((size_t)ks * p.M + m) * p.Cout + c);
+    const float4 w = *reinterpret_cast<const float4 *>(p.splitk + ct_splitk_index(ks, m, c, p.M, p.Cout));
     v.x += w.x, v.y += w.y, v.z += w.z, v.w += w.w;
   }
-  if (p.res) {
-    const half4 r = *reinterpret_cast<const half4 *>(p.res + (size_t)m * p.Cout + c);
-    v.x += (float)r[0], v.y += (float)r[1], v.z += (float)r[2], v.w += (float)r[3];
-  }
-  const float lo = p.relu ? 0.f : -__builtin_inff();
-  v.x = fmaxf(v.x, lo), v.y = fmaxf(v.y, lo), v.z = fmaxf(v.z, lo), v.w = fmaxf(v.w, lo);
-  if (p.post_add) {
-    const float4 pv = *reinterpret_cast<const float4 *>(p.post_add + (size_t)(m % p.post_period) * p.Cout + c);
-    v.x += pv.x, v.y += pv.y, v.z += pv.z, v.w += pv.w;
-  }
-  half4 hv;
-  hv[0] = (f16)v.x, hv[1] = (f16)v.y, hv[2] = (f16)v.z, hv[3] = (f16)v.w;
-  const bool hi = m >= p.split_m;
-  const long long orow = hi ? (long long)(m - p.split_m) : (long long)m;
-  *reinterpret_cast<half4 *>((f16 *)p.out + orow * p.out_ld + (hi ? p.coff_hi : 0) + c) = hv;
+  ct_finish_quad(p, m, c, v);
 }
 
 

@@ -23,6 +23,7 @@
 // re-reads the band and each wave streams its own weights).
 #include "common.h"
 #include "conv_band.h"
+#include "conv_tile.h"
 
 #define B1_THREADS 256
 // (B1_W = 40, the map edge: conv_plan.h)
@@ -108,9 +109,7 @@ __global__ __launch_bounds__(B1_THREADS, 2) void conv3x3_s1_band_kernel(ConvArgs
     }
     band_store_tile<B1_STAGE_LD>(stage, acc, j, lane, lr, lh, ReluThenRound<RES>{lo}, [&](int px, int c16) {
       const int m = m_wave + 32 * j + px;                 // (the channel-concat addressing of the last encodeA layer)
-      const bool hi = m >= p.split_m;
-      const long long orow = hi ? (long long)(m - p.split_m) : (long long)m;
-      return BandDst{(f16 *)p.out + orow * p.out_ld + (hi ? p.coff_hi : 0) + co0 + c16 * 8};
+      return BandDst{ct_out_ptr(p, m) + co0 + c16 * 8};
     });
   }
 }

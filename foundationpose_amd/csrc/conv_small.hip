@@ -22,7 +22,7 @@
 // fp32 accumulation; one summation order of its own (per wave: taps in order, 16-channel steps in order; then the waves in
 // order), so results differ in the last fp32 bits from the large-batch kernels' - like the split-K form it replaces.
 #include "common.h"
-#include "device_util.h"
+#include "conv_tile.h"
 
 namespace {
 
@@ -127,7 +127,7 @@ __global__ __launch_bounds__(NW * 64) void conv3x3_small_kernel(ConvArgs p, cons
     *reinterpret_cast<float4 *>(&part[w][lr][rg * 8 + lh * 4]) = make_float4(acc[rg * 4 + 0], acc[rg * 4 + 1], acc[rg * 4 + 2], acc[rg * 4 + 3]);
   __syncthreads();
   if (NW * 64 > 256 && tid >= 256) return;
-  // 256 threads: pixel tid / 8, four couts each; the waves' shares in wave order, then bias, residual, ReLU, positional embedding
+  // 256 threads: pixel tid / 8, four couts each; the waves' shares in wave order, then bias, and the tail splitk_finish_kernel ends in
   const int px = tid >> 3, c4 = (tid & 7) * 4;
   const int mo = m0 + px;
   if (mo >= p.M) return;
@@ -140,21 +140,7 @@ __global__ __launch_bounds__(NW * 64) void conv3x3_small_kernel(ConvArgs p, cons
   const int c = co0 + c4;
   const float4 bv = *reinterpret_cast<const float4 *>(p.bias + c);
   v.x += bv.x, v.y += bv.y, v.z += bv.z, v.w += bv.w;
-  if (p.res) {
-    const half4 r = *reinterpret_cast<const half4 *>(p.res + (size_t)mo * p.Cout + c);
-    v.x += (float)r[0], v.y += (float)r[1], v.z += (float)r[2], v.w += (float)r[3];
-  }
-  const float lo = p.relu ? 0.f : -__builtin_inff();
-  v.x = fmaxf(v.x, lo), v.y = fmaxf(v.y, lo), v.z = fmaxf(v.z, lo), v.w = fmaxf(v.w, lo);
-  if (p.post_add) {
-    const float4 pv = *reinterpret_cast<const float4 *>(p.post_add + (size_t)(mo % p.post_period) * p.Cout + c);
-    v.x += pv.x, v.y += pv.y, v.z += pv.z, v.w += pv.w;
-  }
-  half4 hv;
-  hv[0] = (f16)v.x, hv[1] = (f16)v.y, hv[2] = (f16)v.z, hv[3] = (f16)v.w;
-  const bool hi = mo >= p.split_m;
-  const long long orow = hi ? (long long)(mo - p.split_m) : (long long)mo;
-  *reinterpret_cast<half4 *>((f16 *)p.out + orow * p.out_ld + (hi ? p.coff_hi : 0) + c) = hv;
+  ct_finish_quad(p, mo, c, v);
 }
 
 // [Cout][9][Cin] -> per (cout tile of 32, wave, tap, 16-channel step) one block of 64 lanes x 8 halfs: lane (lh, lr) holds

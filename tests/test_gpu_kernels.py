@@ -1068,6 +1068,87 @@ def test_attention_bits_are_the_recorded_ones(fp):
   assert not bad, bad
 
 
+# (N, H, W, Cin, Cout, k, stride, fp32 output): shapes of tests/tools/conv_ref.py, each run with (residual, ReLU) and with (none, none)
+CONV_BITS_CASES = [
+  ('halo-splitk', 2, 40, 40, 256, 256, 3, 1, 0), ('halo-splitk', 3, 20, 20, 512, 512, 3, 1, 0),
+  ('halo-tail1', 6, 20, 20, 512, 512, 3, 1, 0), ('halo-tail2', 32, 20, 20, 512, 512, 3, 1, 0), ('halo-tail3', 50, 20, 20, 512, 512, 3, 1, 0),
+  ('halo-tail4', 63, 20, 20, 512, 512, 3, 1, 0), ('halo-tail1', 3, 40, 40, 128, 128, 3, 1, 0), ('halo-tail2', 37, 40, 40, 128, 128, 3, 1, 0),
+  ('halo-round', 42, 40, 40, 256, 256, 3, 1, 0), ('halo-round', 83, 20, 20, 512, 512, 3, 1, 0),
+  ('s2-splitk', 3, 40, 40, 256, 512, 3, 2, 0),
+  ('igemm2', 3, 80, 80, 64, 128, 3, 2, 0), ('igemm2', 2, 17, 23, 32, 64, 3, 1, 0), ('igemm2', 1, 33, 9, 64, 128, 3, 1, 0),
+  ('igemm2', 2, 41, 37, 32, 64, 3, 2, 0), ('igemm2', 1, 34, 30, 6, 64, 7, 2, 0), ('igemm2', 1, 34, 30, 6, 128, 7, 2, 0),
+  ('igemm2', 1, 1, 1000, 512, 1024, 1, 1, 0), ('igemm2', 1, 1, 130, 512, 64, 1, 1, 0), ('igemm2', 3, 7, 5, 32, 64, 1, 1, 0),
+  ('fp32', 3, 40, 40, 128, 128, 3, 1, 1), ('fp32', 1, 1, 1000, 512, 1024, 1, 1, 1), ('fp32', 1, 1, 130, 512, 64, 1, 1, 1),
+]
+
+
+def conv_kernel_digests(ctx):
+  """SHA-256 of the NaN-prefilled outputs of fp_conv2d_f16 (CONV_BITS_CASES) and of fp_net_tokens (both networks, synthetic weights, 3 and
+  6 hypotheses) on seeded CPU inputs: {case: hex digest}.  Cases of one (map, Cin, Cout, k, stride) share inputs drawn once at the largest
+  batch."""
+  import hashlib
+  from foundationpose_amd import _lib, synthetic as S
+  from foundationpose_amd._lib import check, lib, ptr, stream_ptr
+  sha = lambda t: hashlib.sha256(t.cpu().numpy().tobytes()).hexdigest()
+  out, drawn = {}, {}
+  for form, N, H, W, Cin, Cout, k, stride, f32 in CONV_BITS_CASES:
+    key = (H, W, Cin, Cout, k, stride)
+    if key not in drawn:
+      nmax = max(c[1] for c in CONV_BITS_CASES if c[2:8] == key)
+      g = torch.Generator().manual_seed(4000 + sum(key))
+      cin_pad, pad = (8 if Cin < 8 else Cin), (k - 1) // 2
+      Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+      x = torch.zeros((nmax, H, W, cin_pad), dtype=torch.float16)
+      x[..., :Cin] = torch.randn((nmax, H, W, Cin), generator=g).half()
+      x[..., ::3] = x[..., ::3].relu()                                   # some exact zeros, as behind a ReLU
+      w = (torch.randn((Cout, Cin, k, k), generator=g) * (2.0 / (Cin * k * k)) ** 0.5).half()
+      b = torch.randn((Cout,), generator=g) * 0.1
+      res = torch.randn((nmax, Ho, Wo, Cout), generator=g).half()
+      drawn[key] = (x.cuda(), _pack_conv_weight(w.float(), cin_pad).cuda(), b.cuda(), res.cuda(), cin_pad, pad, Ho, Wo)
+    x_d, wp, b_d, res_d, cin_pad, pad, Ho, Wo = drawn[key]
+    for use_res, relu in ((True, 1), (False, 0)):
+      buf = torch.full((N, Ho, Wo, Cout), float('nan'), dtype=torch.float32 if f32 else torch.float16, device='cuda')
+      check(lib().fp_conv2d_f16(ctx.handle, ptr(x_d), N, H, W, cin_pad, ptr(wp), ptr(b_d), Cout, k, k, stride, pad,
+                                ptr(res_d) if use_res else None, relu, ptr(buf), f32, stream_ptr()))
+      hw = str(H) if H == W else f'{H}x{W}'
+      out[f'{form}_{N}x{hw}_{Cin}to{Cout}_k{k}s{stride}_f{"32" if f32 else "16"}_res{int(use_res)}relu{relu}'] = sha(buf)
+  drawn.clear()
+  # the positional-embedding epilogue and the split_m / coff_hi placement (the channel concat behind encodeA) are reached through the trunk only
+  for name, kind, sd in (('refine', _lib.FP_NET_REFINE, S.make_refine_state_dict(0)), ('score', _lib.FP_NET_SCORE, S.make_score_state_dict(1))):
+    net = _lib.DeviceNet(ctx, kind, sd, True)
+    for n in (3, 6):
+      g = torch.Generator().manual_seed(4500 + n)
+      x = torch.zeros((2 * n, 160, 160, 8), dtype=torch.float16)
+      x[..., :6] = torch.randn((2 * n, 160, 160, 6), generator=g).half()
+      x_d = x.cuda()
+      tok = torch.full((n, 400, 512), float('nan'), dtype=torch.float16, device='cuda')
+      check(lib().fp_net_tokens(ctx.handle, net.handle, ptr(x_d), n, ptr(tok), stream_ptr()))
+      out[f'tokens_{name}_{n}'] = sha(tok)
+  return out
+
+
+def test_conv_kernels_bits_are_the_recorded_ones(fp):
+  """The 3x3 halo kernels, the generic implicit GEMM and the few-image kernels (csrc/conv_halo.hip, conv.hip, conv_small.hip; layouts,
+  DMA maps and wait counts in csrc/conv_tile.h) write the bits they wrote before csrc/conv_tile.h existed.  fp_conv2d_f16 at the smallest
+  shapes of tests/tools/conv_ref.py that reach every instantiation of the two files, each with (residual, ReLU) and with neither: halo
+  split-K at W = 40 and 20, tail tiles of 1 .. 4 x 128 pixels, a round of 512-pixel tiles plus tail, the stride-2 split-K, the nine generic
+  shapes, and the fp32 output of one 3x3 shape and the two Linear shapes.  The positional-embedding epilogue and the split_m / coff_hi
+  placement are reached through fp_net_tokens on synthetic weights, RefineNet and ScoreNet at 3 hypotheses (split-K finish) and 6 (the
+  halo <20, RES, POST> form).  Seeded CPU inputs, every output prefilled with NaN, SHA-256 of each whole buffer against
+  tests/golden/conv_kernels_bits.json.
+  How the file was recorded: conv_kernel_digests() above, run on an MI355X with the library built from the commit before conv_tile.h
+  (db57e2f), before any kernel file was touched; its dict written as JSON.  A digest may be re-recorded only by a pull request that
+  means to change the arithmetic of these kernels, and says so."""
+  import json
+  import os
+  with open(os.path.join(os.path.dirname(__file__), 'golden', 'conv_kernels_bits.json')) as f:
+    want = json.load(f)
+  got = conv_kernel_digests(fp['ctx'])
+  assert sorted(got) == sorted(want)
+  bad = [k for k in sorted(want) if got[k] != want[k]]
+  assert not bad, bad
+
+
 def test_profiling_busy_time_is_the_union_of_launch_spans(fp):
   """fp_prof_read / fp_prof_read_busy (bench.py's roofline figure): per kernel class the sum of the launch spans and the time with at
   least one launch executing.  A RefineNet pass on 8 hypotheses: the convolutions follow one another on one stream (busy == sum of
